@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — headline benchmark of the hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (config.workload = "c2"): BASELINE.json configs[1] — LinearBin 4096x4096 XNOR-popcount
 GEMM, batch 4096 PER GPU (weak scaling: the op is batch-sharded, no collective on the data path).
@@ -14,7 +14,13 @@ launches called at the ops level (the headline of rounds 1-5), timed in the same
 For N > 1 the driver launches one rank per GPU with torch.distributed.run; ranks only meet in the
 barriers that bracket the timed region and in the MAX reduction of the elapsed time.
 
-Extra objects on the JSON line: "roofline" (dominant kernel, HIP-event timed inside the timed
+A plain run sets up, warms up, times the K headline steps, writes the last step's output if --dump-outputs DIR is given
+(DIR/y.npy, float32; a fixed, seeded row sample when the output is larger than DUMP_CAP_BYTES) and prints the line: the
+contract keys, config, per-rank times, "dist" and roofline.step_hbm (from the headline's own time).  Everything below takes
+runs of its own and happens only with --full (which also writes bench_detail.json); the other flags (--no-extras,
+--alexnet-batch, --no-cpu-baseline, ...) select among those legs.
+
+Extra objects on the JSON line (--full): "roofline" (dominant kernel, HIP-event timed inside the timed
 region) and "cpu_baseline" (reference op sequence on the host cores, rank 0, N=1 only), "alexnet" (second half
 of the metric) and "extra": the other BASELINE configs, each timed by the same process and each with the roofline
 SURVEY.md 8(d) prescribes (ops = 2 * MACs, bytes = fp32 activations in + fp32 weights + fp32 activations out per
@@ -44,6 +50,8 @@ HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 VALU_PEAK_TOPS = 2516.6        # 256 CU x 4 SIMD x 32 lanes x 2.4 GHz x 32 MAC / 2 lane-ops x 2 ops
 MFMA_FP4_PEAK_TFLOPS = 10000.0  # dense MXFP4 (MI355X_MICROARCH.md)
 EVENT_EVERY = 10                # GEMM launches bracketed by HIP events: every 10th timed step (a pair costs ~7.6 us of stream time)
+DUMP_CAP_BYTES = 32 << 20       # --dump-outputs: all ranks together write at most this much (a fixed row sample of larger outputs)
+DUMP_SEED = 0
 
 
 def parse_args():
@@ -76,6 +84,12 @@ def parse_args():
     ap.add_argument("--launch-check", action="store_true",
                     help="only bring the ranks up (self-launch when no launcher is around), meet in the barrier / MAX reduction the "
                          "timed region uses and print the 'dist' object: runs without a GPU (tests/test_dist_gloo.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement of the line: ops-level leg, kernel roofline, C2 layer legs, reference ops "
+                         "on the GPU, AlexNet, the extra configs, CPU baseline, bench_detail.json (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; a fixed, "
+                         f"seeded sample of rows when the output of all ranks is larger than {DUMP_CAP_BYTES >> 20} MiB)")
     return ap.parse_args()
 
 
@@ -188,97 +202,102 @@ def main():
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-
-    # ---- the same work at the ops level (the two C-ABI wrappers the layer ends in), same bracket; HIP events bracket the GEMM on
-    # every EVENT_EVERY-th step only: a recorded pair costs ~7.6 us of stream time per step (tools/bench_step_overheads.py)
-    for _ in range(args.warmup):
-        ops_step()
-    sync_all()
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        ops_step(record=(i % EVENT_EVERY == 0))
-    torch.cuda.synchronize()
-    ops_elapsed = time.perf_counter() - t0
-    sync_all()
-    if dist is not None:
-        tt = torch.tensor([ops_elapsed], device=dev, dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        ops_elapsed = float(tt.item())
-    same_as_ops = bool(torch.equal(y_layer.detach(), y))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y": y_layer}, rank, world)
 
     ops_per_step = 2.0 * B * K * N
     value = world * ops_per_step * args.steps / elapsed / 1e12
-    gemm_ms = sum(a.elapsed_time(b) for a, b in ev_pairs) / len(ev_pairs)
-    # what an event pair measures around NOTHING on a busy stream (marker packets only): the part of the bracket that is
-    # not kernel time; calibrated outside the timed region, behind the same pack kernel as in a step
-    empty = []
-    for _ in range(20):
+    roofline, c2_ops_level = {}, None
+    if args.full:
+        # ---- the same work at the ops level (the two C-ABI wrappers the layer ends in), same bracket; HIP events bracket the GEMM on
+        # every EVENT_EVERY-th step only: a recorded pair costs ~7.6 us of stream time per step (tools/bench_step_overheads.py)
+        for _ in range(args.warmup):
+            ops_step()
+        sync_all()
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            ops_step(record=(i % EVENT_EVERY == 0))
+        torch.cuda.synchronize()
+        ops_elapsed = time.perf_counter() - t0
+        sync_all()
+        if dist is not None:
+            tt = torch.tensor([ops_elapsed], device=dev, dtype=torch.float64)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            ops_elapsed = float(tt.item())
+        same_as_ops = bool(torch.equal(y_layer.detach(), y))
+
+        gemm_ms = sum(a.elapsed_time(b) for a, b in ev_pairs) / len(ev_pairs)
+        # what an event pair measures around NOTHING on a busy stream (marker packets only): the part of the bracket that is
+        # not kernel time; calibrated outside the timed region, behind the same pack kernel as in a step
+        empty = []
+        for _ in range(20):
+            ops.pack_linear_operands(x, w, "binary", gemm_impl)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            e1.record()
+            empty.append((e0, e1))
+        torch.cuda.synchronize()
+        empty_ms = sorted(a.elapsed_time(b) for a, b in empty)[len(empty) // 2]
+
+        # the same launch as a burst behind the pack kernel, one event pair around BURST launches, marker cost subtracted:
+        # per-launch time with only the ~1 us kernel-to-kernel hand-over on top of the kernel duration rocprofv3 reports
+        BURST = 50
+        xp_b, wp_b = ops.pack_linear_operands(x, w, "binary", gemm_impl)
+        b0, b1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ops.pack_linear_operands(x, w, "binary", gemm_impl)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        e1.record()
-        empty.append((e0, e1))
-    torch.cuda.synchronize()
-    empty_ms = sorted(a.elapsed_time(b) for a, b in empty)[len(empty) // 2]
+        b0.record()
+        for _ in range(BURST):
+            ops.packed_gemm(xp_b, wp_b, None, out=y, impl=gemm_impl)
+        b1.record()
+        torch.cuda.synchronize()
+        burst_ms = max(b0.elapsed_time(b1) - empty_ms, 0.0) / BURST
 
-    # the same launch as a burst behind the pack kernel, one event pair around BURST launches, marker cost subtracted:
-    # per-launch time with only the ~1 us kernel-to-kernel hand-over on top of the kernel duration rocprofv3 reports
-    BURST = 50
-    xp_b, wp_b = ops.pack_linear_operands(x, w, "binary", gemm_impl)
-    b0, b1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ops.pack_linear_operands(x, w, "binary", gemm_impl)
-    b0.record()
-    for _ in range(BURST):
-        ops.packed_gemm(xp_b, wp_b, None, out=y, impl=gemm_impl)
-    b1.record()
-    torch.cuda.synchronize()
-    burst_ms = max(b0.elapsed_time(b1) - empty_ms, 0.0) / BURST
-
-    # ---- roofline of the dominant kernel (the packed GEMM) ------------------------------------
-    gemm_bytes = ops.packed_gemm_algorithmic_bytes(B, N, K, gemm_impl)  # DESIGN.md "Kernels"
-    timing = {"kernel_ms": burst_ms,
-              "kernel_ms_what": f"{BURST} launches back to back behind the pack kernel, one HIP-event pair around the burst, the "
-                                "cost of an empty event pair subtracted; `achieved` and `frac` use THIS figure; the rocprofv3 "
-                                "--kernel-trace --stats average of the same command is quoted beside it (rocprof_avg_us, from "
-                                "profiles/pmc_latest.json, refreshed by tools/collect_profiles.sh)",
-              "kernel_ms_in_step_bracket": gemm_ms,
-              "kernel_ms_in_step_bracket_what": f"HIP-event pair around the single launch on every {EVENT_EVERY}th step of the timed "
-                                                "region; includes the marker packets / kernel boundary (~3-5 us)",
-              "event_pair_empty_ms": empty_ms}
-    if gemm_impl == "mfma":
-        achieved = ops_per_step / (burst_ms * 1e-3) / 1e12
-        roofline = {"bound": "mfma", "kernel_name": ops.nib_gemm_kernel_name(B, N, K),
-                    "kernel": ops.nib_gemm_kernel_name(B, N, K) + " (fp4 MFMA packed GEMM; name from the library's own dispatch)",
-                    "achieved": achieved, "peak": MFMA_FP4_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / MFMA_FP4_PEAK_TFLOPS,
-                    "frac_on_in_step_bracket": ops_per_step / (gemm_ms * 1e-3) / 1e12 / MFMA_FP4_PEAK_TFLOPS,
-                    "traffic": None, **timing,
-                    "hbm_equiv": {"algorithmic_bytes": gemm_bytes,
-                                  "achieved_GBs": gemm_bytes / (burst_ms * 1e-3) / 1e9,
-                                  "frac_of_8TBs": gemm_bytes / (burst_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}}
-    else:
-        achieved = gemm_bytes / (burst_ms * 1e-3) / 1e9
-        valu = ops_per_step / (burst_ms * 1e-3) / 1e12
-        roofline = {"bound": "hbm", "kernel_name": "popc_gemm_kernel", "kernel": "popc_gemm_kernel (xnor popcount GEMM, VALU)", "achieved": achieved,
-                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                    **timing, "algorithmic_bytes": gemm_bytes,
-                    "note": "at this shape the popcount formulation is VALU-bound, not HBM-bound "
-                            "(SURVEY.md 8d); the instruction ceiling is reported beside it",
-                    "valu_ceiling": {"achieved_TOPS": valu, "peak_TOPS": VALU_PEAK_TOPS,
-                                     "frac": valu / VALU_PEAK_TOPS}}
+        # ---- roofline of the dominant kernel (the packed GEMM) ------------------------------------
+        gemm_bytes = ops.packed_gemm_algorithmic_bytes(B, N, K, gemm_impl)  # DESIGN.md "Kernels"
+        timing = {"kernel_ms": burst_ms,
+                  "kernel_ms_what": f"{BURST} launches back to back behind the pack kernel, one HIP-event pair around the burst, the "
+                                    "cost of an empty event pair subtracted; `achieved` and `frac` use THIS figure; the rocprofv3 "
+                                    "--kernel-trace --stats average of the same command is quoted beside it (rocprof_avg_us, from "
+                                    "profiles/pmc_latest.json, refreshed by tools/collect_profiles.sh)",
+                  "kernel_ms_in_step_bracket": gemm_ms,
+                  "kernel_ms_in_step_bracket_what": f"HIP-event pair around the single launch on every {EVENT_EVERY}th step of the timed "
+                                                    "region; includes the marker packets / kernel boundary (~3-5 us)",
+                  "event_pair_empty_ms": empty_ms}
+        if gemm_impl == "mfma":
+            achieved = ops_per_step / (burst_ms * 1e-3) / 1e12
+            roofline = {"bound": "mfma", "kernel_name": ops.nib_gemm_kernel_name(B, N, K),
+                        "kernel": ops.nib_gemm_kernel_name(B, N, K) + " (fp4 MFMA packed GEMM; name from the library's own dispatch)",
+                        "achieved": achieved, "peak": MFMA_FP4_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / MFMA_FP4_PEAK_TFLOPS,
+                        "frac_on_in_step_bracket": ops_per_step / (gemm_ms * 1e-3) / 1e12 / MFMA_FP4_PEAK_TFLOPS,
+                        "traffic": None, **timing,
+                        "hbm_equiv": {"algorithmic_bytes": gemm_bytes,
+                                      "achieved_GBs": gemm_bytes / (burst_ms * 1e-3) / 1e9,
+                                      "frac_of_8TBs": gemm_bytes / (burst_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}}
+        else:
+            achieved = gemm_bytes / (burst_ms * 1e-3) / 1e9
+            valu = ops_per_step / (burst_ms * 1e-3) / 1e12
+            roofline = {"bound": "hbm", "kernel_name": "popc_gemm_kernel", "kernel": "popc_gemm_kernel (xnor popcount GEMM, VALU)", "achieved": achieved,
+                        "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+                        **timing, "algorithmic_bytes": gemm_bytes,
+                        "note": "at this shape the popcount formulation is VALU-bound, not HBM-bound "
+                                "(SURVEY.md 8d); the instruction ceiling is reported beside it",
+                        "valu_ceiling": {"achieved_TOPS": valu, "peak_TOPS": VALU_PEAK_TOPS,
+                                         "frac": valu / VALU_PEAK_TOPS}}
     step_bytes = 4.0 * (B * K + N * K + B * N) + 4.0 * N  # fp32 in / fp32 out, SURVEY.md 8d
     step_ms = elapsed / args.steps * 1e3
     roofline["step_hbm"] = {"algorithmic_bytes": step_bytes,
                             "achieved_GBs": step_bytes / (step_ms * 1e-3) / 1e9,
                             "frac_of_8TBs": step_bytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
 
-    # HBM-side bytes per launch: counters cannot be read from inside the process, so this is QUOTED from the committed PMC
-    # passes of this same command (tools/collect_profiles.sh refreshes profiles/pmc_latest.json), not measured in this run
-    roofline["traffic"], src, roofline["rocprof_avg_us"] = pmc_traffic(gemm_impl)
-    roofline["traffic_source"] = None if src is None else f"quoted (not measured in this run): {src}"
+    if args.full:
+        # HBM-side bytes per launch: counters cannot be read from inside the process, so this is QUOTED from the committed PMC
+        # passes of this same command (tools/collect_profiles.sh refreshes profiles/pmc_latest.json), not measured in this run
+        roofline["traffic"], src, roofline["rocprof_avg_us"] = pmc_traffic(gemm_impl)
+        roofline["traffic_source"] = None if src is None else f"quoted (not measured in this run): {src}"
 
-    c2_ops_level = {"ms_per_step": ops_elapsed / args.steps * 1e3, "TOPS": world * ops_per_step * args.steps / ops_elapsed / 1e12,
-                    "what": "ops.pack_linear_operands + ops.packed_gemm called directly (rounds 1-5's headline): the layer's dispatch, "
-                            "autograd node and output view are NOT in this figure", "same_result_as_headline": same_as_ops}
+        c2_ops_level = {"ms_per_step": ops_elapsed / args.steps * 1e3, "TOPS": world * ops_per_step * args.steps / ops_elapsed / 1e12,
+                        "what": "ops.pack_linear_operands + ops.packed_gemm called directly (rounds 1-5's headline): the layer's dispatch, "
+                                "autograd node and output view are NOT in this figure", "same_result_as_headline": same_as_ops}
     result = {
         "metric": "XNOR-popcount GEMM TOPS (LinearBin 4096x4096 forward, batch 4096 per GPU)",
         "value": value, "unit": "TOPS", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -300,7 +319,6 @@ def main():
                            "AlexNet conv1 on the direct kernel (per-tile two-term fp16 split), VGG conv1 on bf16 triples", "deferred_activations": "on (lazy.ENABLED, lazy.DEFER_CODES): bit-identical "
                    "to the module-by-module graph on this device"},
         "roofline": roofline,
-        "c2_ops_level": c2_ops_level,
         "per_rank_ms_per_step": per_rank_ms,
         "dist": {"initialised": dist is not None, "backend": (dist.get_backend() if dist is not None else None),
                  "world_size_seen_by_the_process_group": (dist.get_world_size() if dist is not None else 1),
@@ -308,6 +326,8 @@ def main():
                  "scaling_measured": "this line is ONE point; the driver computes efficiency from the per-N lines. No N > 1 run "
                                      "has been possible for this repo so far (1-GPU boxes): multi-GPU behaviour is unmeasured"},
     }
+    if c2_ops_level is not None:
+        result["c2_ops_level"] = c2_ops_level
     if dist is not None:
         names = [None] * world
         dist.all_gather_object(names, f"rank {rank}: cuda:{local_rank} {torch.cuda.get_device_name(dev)} "
@@ -316,66 +336,67 @@ def main():
     result["dist"]["self_check"] = dist_self_check(args.gpus, result["dist"]["world_size_seen_by_the_process_group"],
                                                    result["dist"]["devices"] if dist is not None else None)
 
-    # ---- the same step THROUGH THE MODULE: LinearBin(K, N).train().forward(x) — the layer's dispatch, its
-    # autograd node (the weight requires grad: inputs are saved for backward) and the output view are inside this figure; the
-    # headline above calls the two ops the layer ends in.  binary_input=True = "the caller guarantees +-1 activations" (what a
-    # BinaryConnect in front of the layer establishes in the reference's models); the default None asks the device per call
-    # (detect_mode 'verify': one 4-byte readback = a host sync per forward), reported beside it.
-    result["c2_layer_forward"] = bench_c2_layer(args, dev, dist, world, x, w, y, ops_per_step, sync_all)
-    result["c2_layer_forward"]["headline_is_this_leg"] = "value / ms_per_step above ARE the binary_input=True, autograd-on form of this leg"
+    if args.full:
+        # ---- the same step THROUGH THE MODULE: LinearBin(K, N).train().forward(x) — the layer's dispatch, its
+        # autograd node (the weight requires grad: inputs are saved for backward) and the output view are inside this figure; the
+        # headline above calls the two ops the layer ends in.  binary_input=True = "the caller guarantees +-1 activations" (what a
+        # BinaryConnect in front of the layer establishes in the reference's models); the default None asks the device per call
+        # (detect_mode 'verify': one 4-byte readback = a host sync per forward), reported beside it.
+        result["c2_layer_forward"] = bench_c2_layer(args, dev, dist, world, x, w, y, ops_per_step, sync_all)
+        result["c2_layer_forward"]["headline_is_this_leg"] = "value / ms_per_step above ARE the binary_input=True, autograd-on form of this leg"
 
-    # ---- the reference's own op sequence on THIS GPU (torch.sign + masked write + F.linear fp32 through ROCm PyTorch):
-    # what the un-modified QuantTorch package gets here; per-rank work like the headline, a reported baseline only
-    if not args.no_extras:
-        from oracle import torch_port
-        with torch.no_grad():
-            yr = torch_port.linear_bin_forward(x, w)
-            same = bool(torch.equal(yr, y))
-            del yr
-            for _ in range(2):
-                torch_port.linear_bin_forward(x, w)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(10):
-                torch_port.linear_bin_forward(x, w)
-            torch.cuda.synchronize()
-            ref_ms = (time.perf_counter() - t0) / 10 * 1e3
-        result["reference_ops_on_gpu"] = {"value": ops_per_step / (ref_ms * 1e-3) / 1e12, "unit": "TOPS (per GPU)",
-                                          "ms_per_step": ref_ms, "same_result": same,
-                                          "what": "oracle/torch_port.linear_bin_forward on the device tensors, 10 calls"}
+        # ---- the reference's own op sequence on THIS GPU (torch.sign + masked write + F.linear fp32 through ROCm PyTorch):
+        # what the un-modified QuantTorch package gets here; per-rank work like the headline, a reported baseline only
+        if not args.no_extras:
+            from oracle import torch_port
+            with torch.no_grad():
+                yr = torch_port.linear_bin_forward(x, w)
+                same = bool(torch.equal(yr, y))
+                del yr
+                for _ in range(2):
+                    torch_port.linear_bin_forward(x, w)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    torch_port.linear_bin_forward(x, w)
+                torch.cuda.synchronize()
+                ref_ms = (time.perf_counter() - t0) / 10 * 1e3
+            result["reference_ops_on_gpu"] = {"value": ops_per_step / (ref_ms * 1e-3) / 1e12, "unit": "TOPS (per GPU)",
+                                              "ms_per_step": ref_ms, "same_result": same,
+                                              "what": "oracle/torch_port.linear_bin_forward on the device tensors, 10 calls"}
 
-    # ---- BinaryNet-AlexNet images/s (second half of BASELINE.json's metric) ---------------------------
-    if args.alexnet_batch > 0:
-        result["alexnet"] = bench_alexnet(args, dev, dist, world, rank)
-    if not args.no_extras:
-        result["extra"] = bench_extras(args, dev, dist, world, rank, x, w)
+        # ---- BinaryNet-AlexNet images/s (second half of BASELINE.json's metric) ---------------------------
+        if args.alexnet_batch > 0:
+            result["alexnet"] = bench_alexnet(args, dev, dist, world, rank)
+        if not args.no_extras:
+            result["extra"] = bench_extras(args, dev, dist, world, rank, x, w)
 
-    # ---- parity gate + CPU baseline (rank 0, N = 1 only) --------------------------------------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        from oracle import torch_port
-        xc, wc = x.cpu(), w.cpu()
-        ref = torch_port.linear_bin_forward(xc, wc)
-        result["parity_vs_cpu_port"] = bool(torch.equal(ref, y.cpu()))
-        # the host has far more logical CPUs than MKL scales to: use the fastest thread count
-        nthreads, _ = torch_port.best_thread_count(lambda: torch_port.linear_bin_forward(xc, wc))
-        med, iters = torch_port.time_callable(lambda: torch_port.linear_bin_forward(xc, wc),
-                                              budget_s=args.cpu_budget_s)
-        result["cpu_baseline"] = {
-            "value": ops_per_step / med / 1e12, "unit": "TOPS", "cores": torch.get_num_threads(),
-            "kind": "port", "ms_per_step": med * 1e3,
-            "sample": f"{iters} full-size calls of the reference op sequence "
-                      f"(torch.sign + masked write + F.linear fp32, B={B} K={K} N={N}), median",
-            "host": _cpu_model()}
-        # "plus a 1-thread run" — the same op sequence on ONE host core (bounded: 2 calls)
-        torch.set_num_threads(1)
-        med1, it1 = torch_port.time_callable(lambda: torch_port.linear_bin_forward(xc, wc), budget_s=0.0, warmup=0,
-                                             min_iters=2, max_iters=2)
-        torch.set_num_threads(nthreads)
-        result["cpu_baseline"]["one_thread"] = {"value": ops_per_step / med1 / 1e12, "unit": "TOPS", "cores": 1,
-                                                "ms_per_step": med1 * 1e3, "sample": f"{it1} full-size calls"}
+        # ---- parity gate + CPU baseline (rank 0, N = 1 only) --------------------------------------------
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            from oracle import torch_port
+            xc, wc = x.cpu(), w.cpu()
+            ref = torch_port.linear_bin_forward(xc, wc)
+            result["parity_vs_cpu_port"] = bool(torch.equal(ref, y.cpu()))
+            # the host has far more logical CPUs than MKL scales to: use the fastest thread count
+            nthreads, _ = torch_port.best_thread_count(lambda: torch_port.linear_bin_forward(xc, wc))
+            med, iters = torch_port.time_callable(lambda: torch_port.linear_bin_forward(xc, wc),
+                                                  budget_s=args.cpu_budget_s)
+            result["cpu_baseline"] = {
+                "value": ops_per_step / med / 1e12, "unit": "TOPS", "cores": torch.get_num_threads(),
+                "kind": "port", "ms_per_step": med * 1e3,
+                "sample": f"{iters} full-size calls of the reference op sequence "
+                          f"(torch.sign + masked write + F.linear fp32, B={B} K={K} N={N}), median",
+                "host": _cpu_model()}
+            # "plus a 1-thread run" — the same op sequence on ONE host core (bounded: 2 calls)
+            torch.set_num_threads(1)
+            med1, it1 = torch_port.time_callable(lambda: torch_port.linear_bin_forward(xc, wc), budget_s=0.0, warmup=0,
+                                                 min_iters=2, max_iters=2)
+            torch.set_num_threads(nthreads)
+            result["cpu_baseline"]["one_thread"] = {"value": ops_per_step / med1 / 1e12, "unit": "TOPS", "cores": 1,
+                                                    "ms_per_step": med1 * 1e3, "sample": f"{it1} full-size calls"}
     if rank == 0:
         result["calls"] = {k: int(v) for k, v in _lib.call_counts.items()}
-        detail_paths = write_detail(result)
+        detail_paths = write_detail(result) if args.full else ()
         line = compact_line(result, detail_paths)
         print(line)
         sys.stdout.flush()
@@ -422,6 +443,26 @@ def _r(v, nd=4):
     if isinstance(v, (list, tuple)):
         return [_r(x, nd) for x in v]
     return v
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """--dump-outputs: each named output of the last timed step as out_dir/<name>.npy in float32 (<name>_rank<r>.npy with more
+    than one rank).  Each rank may write DUMP_CAP_BYTES / world, so the ranks together stay within DUMP_CAP_BYTES; a larger
+    output is written as the rows picked by a generator seeded with DUMP_SEED, in ascending order: the same rows for the same
+    shape in every run, so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_CAP_BYTES // max(1, world)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        rows = t.shape[0]
+        row_bytes = t[0].numel() * 4 if rows else 0
+        if rows and rows * row_bytes > cap:
+            keep = max(1, cap // row_bytes)
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=keep, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        fname = name if world == 1 else f"{name}_rank{rank}"
+        np.save(os.path.join(out_dir, fname + ".npy"), t.cpu().numpy())
 
 
 def write_detail(result):
@@ -532,7 +573,8 @@ def compact_line(result, detail_paths=()):
                 if "dense_library_calls_in_the_steps" in t:
                     e[short]["dense_library_calls"] = t["dense_library_calls_in_the_steps"]
         out["extra"] = e
-    out["detail"] = {"files": list(detail_paths), "what": "full result object: every leg, per-block rooflines, C-ABI call counters"}
+    if detail_paths:
+        out["detail"] = {"files": list(detail_paths), "what": "full result object: every leg, per-block rooflines, C-ABI call counters"}
     out = _r(out)
     line = json.dumps(out, separators=(",", ":"))
     if len(line) > LINE_TARGET_BYTES:                       # shed the optional objects first, the contract keys never

@@ -75,3 +75,44 @@ def test_multi_rank_line_fits():
     line = bench.compact_line(full)
     assert len(line) <= bench.LINE_TARGET_BYTES
     assert len(json.loads(line)["per_rank_ms_per_step"]) == 8
+
+
+def test_compact_line_of_a_plain_run():
+    """A plain run (no --full) fills only the contract keys, config, per-rank times, dist and roofline.step_hbm."""
+    full = _canned()
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                                  "scaling", "vs_baseline", "dtype", "data", "config", "per_rank_ms_per_step", "dist")}
+    plain["roofline"] = {"step_hbm": full["roofline"]["step_hbm"]}
+    out = json.loads(bench.compact_line(plain))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert out[k] == bench._r(full[k]), k
+    assert out["roofline"]["step_hbm"]["frac_of_8TBs"] is not None
+    assert "detail" not in out and "c2_ops_level" not in out and "alexnet" not in out
+
+
+def test_bench_flags(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse_args()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "outs"])
+    a = bench.parse_args()
+    assert a.full and a.dump_outputs == "outs"
+
+
+def test_dump_outputs_is_a_fixed_float32_row_sample(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 10 * 64 * 4)              # room for 10 rows of 64 fp32
+    y = torch.arange(100 * 64, dtype=torch.float32).view(100, 64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"y": y})
+    a, b = np.load(tmp_path / "a" / "y.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert a.dtype == np.float32 and a.shape == (10, 64) and np.array_equal(a, b)
+    rows = (a[:, 0] // 64).astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, y.numpy()[rows])
+    bench.dump_outputs(str(tmp_path / "c"), {"y": torch.ones(3, 5, dtype=torch.float64)}, rank=1, world=2)
+    c = np.load(tmp_path / "c" / "y_rank1.npy")
+    assert c.dtype == np.float32 and c.shape == (3, 5)
+    # with several ranks the cap holds for all of them together: each rank writes cap / world
+    bench.dump_outputs(str(tmp_path / "d"), {"y": y}, rank=0, world=2)
+    assert np.load(tmp_path / "d" / "y_rank0.npy").shape == (5, 64)

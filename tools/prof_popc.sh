@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-C2="python $R/bench.py --gemm valu --steps 20 --warmup 5 --no-cpu-baseline --alexnet-batch 0 --no-extras"
+C2="python $R/bench.py --full --gemm valu --steps 20 --warmup 5 --no-cpu-baseline --alexnet-batch 0 --no-extras"
 rocprofv3 --kernel-trace --stats -d "$O/kt" -o bench --output-format csv -- $C2 > "$O/kt.log" 2>&1
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY -d "$O/pmc_sq" -o bench --output-format csv -- $C2 > "$O/pmc_sq.log" 2>&1
 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_INSTS_SALU -d "$O/pmc_lds" -o bench --output-format csv -- $C2 > "$O/pmc_lds.log" 2>&1

@@ -54,7 +54,7 @@ if all(v is not None for v in g.values()):
     if all(v is not None for v in p.values()):
         cur["kernels"]["nib_pack_pair_kernel"] = p
     cur["source"] = (f"profiles/{tag}_bench_rocprof.md (rocprofv3 --kernel-trace --stats of the default bench command; --kernel-trace --pmc FETCH_SIZE / "
-                     f"--pmc WRITE_SIZE passes of `python bench.py --steps 40 --warmup 10 --no-cpu-baseline --alexnet-batch 0 --no-extras`, "
+                     f"--pmc WRITE_SIZE passes of `python bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --alexnet-batch 0 --no-extras`, "
                      f"tools/collect_profiles.sh {tag})")
     json.dump(cur, open("profiles/pmc_latest.json", "w"))
     print("pmc_latest.json <-", tag, g)
