@@ -120,6 +120,36 @@ int qt_lin_quantize_f32(const float* x, float* y, int64_t n, int fsr, int bit_wi
 int qt_log_quantize_f32(const float* x, float* y, int64_t n, int fsr, int bit_width, int with_sign,
                         qt_stream_t stream);
 
+/* Loss-aware quantisation families, Elastic and WQR (functions/elastic_quant_connect.py, functions/WQR_connect.py).
+ *
+ * Level projection (_proj_val): y[i] = levels[argmin_j |x[i] - levels[j]|], the distance rounded in fp32, ties to the first
+ * index, a NaN distance wins (torch.argmin): NaN and +-inf inputs give levels[0].  `levels` is a HOST array of
+ * 1 <= n_levels <= QT_LEVELS_MAX values, copied into the kernel arguments (no allocation, no sync: graph-capturable). */
+#define QT_LEVELS_MAX 64
+int qt_level_project_f32(const float* x, float* y, int64_t n, const float* levels, int n_levels, qt_stream_t stream);
+
+/* Fused regulariser of a weight gradient: out = (g - R1(w)) - R2(w), or out = R1(w) when g is NULL (then n_terms2 must be 0).
+ * R1 is the first n_terms1 entries of `terms` (a HOST array, copied into the kernel arguments), R2 the next n_terms2; each
+ * starts at +0 and every entry, in order, does  res = res +- ((V(x) * [x op1 t1]) * [x op2 t2])  with V of the entry's kind
+ * and the family coefficient a (alpha / beta / kapa) — *coef_dev when non-NULL (a 1-element device tensor, read on the
+ * device), else coef:
+ *   QT_REG_L2_LIN      V = a*x + k, k = c (host: fl((-level) * a) in double) or, with coef_dev, fl(c * a) (c = fl(-level))
+ *   QT_REG_L2_EXP      V = a*(x - c)
+ *   QT_REG_L1          V = a
+ *   QT_REG_WQR_LIN     V = a*(sign(x)*|x - c| + |x|*sign(x - c))
+ *   QT_REG_WQR_EXP_POS V = a*(sign(x)*|x - c| + |x|)
+ *   QT_REG_WQR_EXP_NEG V = a*(sign(x)*|x - c| - |x|)
+ * code = kind | op1 << 4 | op2 << 6 | subtract << 8, op in QT_CMP_*; sign() is torch.sign.  n_terms1 + n_terms2 <= QT_REG_TERMS_MAX. */
+#define QT_REG_TERMS_MAX 128
+enum { QT_REG_L2_LIN = 0, QT_REG_L2_EXP = 1, QT_REG_L1 = 2, QT_REG_WQR_LIN = 3, QT_REG_WQR_EXP_POS = 4, QT_REG_WQR_EXP_NEG = 5 };
+enum { QT_CMP_LT = 0, QT_CMP_LE = 1, QT_CMP_GT = 2, QT_CMP_GE = 3 };
+typedef struct qt_reg_term {
+    int32_t code;
+    float t1, t2, c;
+} qt_reg_term;
+int qt_weight_reg_f32(const float* w, const float* g, float* out, int64_t n, const qt_reg_term* terms, int n_terms1, int n_terms2,
+                      float coef1, const float* coef1_dev, float coef2, const float* coef2_dev, qt_stream_t stream);
+
 /* AP2 of the shift-based batch norm (functions/binary_connect.py:157-169): safeSign(x) * 2^round(log2|x|). */
 int qt_ap2_f32(const float* x, float* y, int64_t n, qt_stream_t stream);
 

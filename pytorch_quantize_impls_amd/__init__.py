@@ -5,13 +5,14 @@ from . import functions, layers, ops, packed, utils
 from .device import device
 from ._lib import QtLibraryError, QtStatusError
 
-# family aliases, as QuantTorch/{BinaryNet,TernerNet,DorefaNet,XnorNet,LogLinNet}.py (imported lazily: `import pkg.BinaryNet`)
+# family aliases, as QuantTorch/{BinaryNet,TernerNet,DorefaNet,XnorNet,LogLinNet,ElasticNet,WqrNet}.py (imported lazily: `import pkg.BinaryNet`)
 __all__ = ["functions", "layers", "ops", "packed", "utils", "device", "QtLibraryError", "QtStatusError",
-           "BinaryNet", "TernerNet", "DorefaNet", "XnorNet", "LogLinNet"]
+           "BinaryNet", "TernerNet", "DorefaNet", "XnorNet", "LogLinNet",
+           "ElasticNet", "WqrNet"]
 
 
 def __getattr__(name):
-    if name in ("BinaryNet", "TernerNet", "DorefaNet", "XnorNet", "LogLinNet"):
+    if name in ("BinaryNet", "TernerNet", "DorefaNet", "XnorNet", "LogLinNet", "ElasticNet", "WqrNet"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -61,6 +61,8 @@ SIGNATURES = {
     "qt_lin_quantize_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_int, _c_int, _c_p]),
     "qt_log_quantize_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_int, _c_int, _c_p]),
     "qt_ap2_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_p]),
+    "qt_level_project_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_int, _c_p]),
+    "qt_weight_reg_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_int, _c_int, _c_f32, _c_p, _c_f32, _c_p, _c_p]),
     "qt_xnor_gemm_variant": (_c_int, [_c_int, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
     "qt_tern_gemm_variant": (_c_int, [_c_int, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64,
                                       _c_p]),

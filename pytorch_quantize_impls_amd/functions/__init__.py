@@ -7,4 +7,9 @@ from .terner_connect import (TernaryConnectDeterministic, TernaryConnectStochast
                              TernaryDense, TernaryConv2d)
 from .xnor_connect import nnQuantXnor, QuantXnor, XNORDense, XNORConv2d
 from .log_lin_connect import LogQuant, LinQuant, nnQuant, Quant
+from .elastic_quant_connect import (lin_proj, exp_proj, lin_deriv_l2, exp_deriv_l2, lin_deriv_l1, exp_deriv_l1, QuantWeightLin,
+                                    QuantWeightExp, QuantLinDense, QuantLogDense)
+from .WQR_connect import lin_deriv_WQR, exp_deriv_WQR, QuantWeightWLin, QuantWeightWExp, QuantWLinDense, QuantWLogDense
 from .common import safeSign
+# functions.QuantConv2d stays DoReFa's: upstream the deprecated Elastic conv op shadows it here; it is
+# elastic_quant_connect.QuantConv2d (and ElasticNet.QuantConv2d).

@@ -13,6 +13,7 @@ import functools
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -390,6 +391,58 @@ def log_quantize(x: torch.Tensor, fsr: int, bit_width: int, with_sign: bool = Tr
 def ap2(x: torch.Tensor) -> torch.Tensor:
     """safeSign(x) * 2^round(log2|x|) (functions/binary_connect.py:157-169)."""
     return _unary("qt_ap2_f32", x)
+
+
+#: capacities of the by-value tables of qt_level_project_f32 / qt_weight_reg_f32 (include/qt_hip.h)
+LEVELS_MAX = 64
+REG_TERMS_MAX = 128
+
+
+def level_project(x: torch.Tensor, levels) -> torch.Tensor:
+    """levels[argmin_j |x - levels[j]|] (functions/elastic_quant_connect.py _proj_val).  ``levels``: a host sequence of at most
+    LEVELS_MAX fp32 values, passed by value in the kernel arguments."""
+    lv = np.ascontiguousarray(np.asarray(levels, dtype=np.float32).reshape(-1))
+    if not 1 <= lv.size <= LEVELS_MAX:
+        raise ValueError(f"level table of {lv.size} entries (1..{LEVELS_MAX})")
+    return _unary("qt_level_project_f32", x, lv.ctypes.data, int(lv.size))
+
+
+def _reg_coef(a, device):
+    """(value, device pointer) of a regulariser coefficient: a Python number, or a 1-element fp32 tensor on ``device``."""
+    if isinstance(a, torch.Tensor):
+        if a.numel() != 1 or a.dtype != torch.float32 or a.device != device:
+            raise TypeError("coefficient: expected a Python number or a 1-element fp32 tensor on the weight's device")
+        return 0.0, a.data_ptr()
+    return float(np.float32(a)), None
+
+
+def weight_reg(w: torch.Tensor, g: Optional[torch.Tensor], terms1, coef1, terms2=None, coef2=0.0) -> torch.Tensor:
+    """(g - R1(w)) - R2(w), or R1(w) when ``g`` is None: the Elastic / WQR regulariser of a weight gradient in one pass.  ``terms*``:
+    int32 arrays [n, 4] of qt_reg_term entries (functions/elastic_quant_connect.py builds them); ``coef*``: Python numbers or 1-element
+    fp32 device tensors (read on the device, no host sync)."""
+    w = _require(w, "weight")
+    if not w.is_contiguous():
+        w = w.contiguous()
+    t1 = np.zeros((0, 4), np.int32) if terms1 is None else terms1
+    t2 = np.zeros((0, 4), np.int32) if terms2 is None else terms2
+    if g is None and len(t2):
+        raise ValueError("weight_reg: a second regulariser needs a gradient")
+    if g is not None:
+        g = _require(g, "grad")
+        if g.shape != w.shape:
+            raise ValueError(f"shape mismatch {tuple(g.shape)} vs {tuple(w.shape)}")
+        if not g.is_contiguous():
+            g = g.contiguous()
+    table = np.ascontiguousarray(np.concatenate([t1, t2]).astype(np.int32, copy=False))
+    if len(table) > REG_TERMS_MAX:
+        raise ValueError(f"regulariser table of {len(table)} entries (at most {REG_TERMS_MAX})")
+    a1, p1 = _reg_coef(coef1, w.device)
+    a2, p2 = _reg_coef(coef2, w.device)
+    out = torch.empty_like(w)
+    with _on(w.device):
+        _lib.call("qt_weight_reg_f32", _p(w), _p(g), _p(out), int(w.numel()), table.ctypes.data if len(table) else None,
+                  int(len(t1)), int(len(t2)), a1, p1, a2, p2, _stream(w.device))
+    return out
 
 
 def _binary(name: str, a: torch.Tensor, b: torch.Tensor, *extra) -> torch.Tensor:

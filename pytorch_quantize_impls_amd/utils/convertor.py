@@ -24,6 +24,7 @@ from ..layers.terner_layers import LinearTer, TerConv2d
 from ..layers.dorefa_layers import LinearDorefa, DorefaConv2d
 from ..layers.xnor_layers import LinearXNOR, XNORConv2d
 from ..layers.log_lin_layers import LinearQuant, QuantConv2d
+from ..layers import elastic_layers
 
 
 def _target(entry):
@@ -72,3 +73,15 @@ def log_lin_net_convert(net, fsr=7, bit_width=3, dtype="lin", bitwight=None):
     """Lin / Log fixed-point family (utils/convertor.py:60-64)."""
     kw = {"fsr": fsr, "bit_width": bit_width if bitwight is None else bitwight, "dtype": dtype}
     return convert(net, {nn.Linear: (LinearQuant, kw), nn.Conv2d: (QuantConv2d, kw)})
+
+
+def loss_quant_log_convert(net, gamma=2, init=0.25, size=5, alpha=1):
+    """Elastic Log layers (utils/convertor.py:66-70): note the default alpha=1 and no ``beta``."""
+    kw = {"gamma": gamma, "init": init, "size": size, "alpha": alpha}
+    return convert(net, {nn.Linear: (elastic_layers.LinearQuantLog, kw), nn.Conv2d: (elastic_layers.QuantConv2dLog, kw)})
+
+
+def loss_quant_lin_convert(net, bottom=-1, top=1, size=5, alpha=0, beta=0):
+    """Elastic Lin layers (utils/convertor.py:72-76)."""
+    kw = {"bottom": bottom, "top": top, "size": size, "alpha": alpha, "beta": beta}
+    return convert(net, {nn.Linear: (elastic_layers.LinearQuantLin, kw), nn.Conv2d: (elastic_layers.QuantConv2dLin, kw)})
