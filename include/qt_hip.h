@@ -637,6 +637,25 @@ int qt_f16x2_s2d_pack_spec_f32(const float* x, int64_t sN, int64_t sC, int64_t s
 int qt_f16x2_pack_conv_weight_f32(const float* w, int64_t stride_o, int64_t stride_i, int64_t stride_h, int64_t stride_w, int64_t Cout,
                                   int64_t Cin, int64_t kh, int64_t kw, int mode, int transpose_flip, uint16_t* out, int64_t ld_bytes,
                                   qt_stream_t stream);
+/* Quantise-and-pack of Lin / Log fixed-point weights for a training step (csrc/loglin_pack.hip).  One read of the fp32 weight
+ * [Cout][Cin][kh][kw] (element strides: contiguous or channels-last) applies the quantiser of qt_lin_quantize_f32 (dtype 0,
+ * mode 1 if with_sign else 0; bit_width 32 = identity) or qt_log_quantize_f32 (dtype 1) — bit-identical — and writes, each
+ * optional (null = skip, at least one given):
+ *   fwd: the forward operand of qt_conv2d_implicit(elem = 2): the quantised value as bf16 (round to nearest even) replicated into
+ *        the three slots of a bf16 triple, rows = Cout, tap-major with 16-byte tap granules (6*Cin bytes rounded up to 16), zero
+ *        padded to fwd_ld_bytes = max(128, kh*kw*granule rounded up to 128);
+ *   gx:  the same plane of Q(W).flip(2, 3).transpose(0, 1) (the grad_x operand: rows = Cin, channels = Cout, taps flipped),
+ *        gx_ld_bytes likewise from Cout;
+ *   wq:  the fp32 quantised image, written with the weight's strides.
+ * The Linear form takes W [N][K] by its two strides: fwd is the plane of qt_bf16x3_pack_f32(mode 4) of Q(W) (row granule 128),
+ * gx that of Q(W)^T.  Bounds: -60 <= fsr <= 60, 1 <= bit_width <= 32 (Lin) / 16 (Log). */
+int qt_bf16x3_pack_conv_levels_f32(const float* w, int64_t stride_o, int64_t stride_i, int64_t stride_h, int64_t stride_w,
+                                   int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int dtype, int fsr, int bit_width,
+                                   int with_sign, uint16_t* fwd, int64_t fwd_ld_bytes, uint16_t* gx, int64_t gx_ld_bytes,
+                                   float* wq, qt_stream_t stream);
+int qt_bf16x3_pack_levels_f32(const float* w, int64_t stride_n, int64_t stride_k, int64_t N, int64_t K, int dtype, int fsr,
+                              int bit_width, int with_sign, uint16_t* fwd, int64_t fwd_ld_bytes, uint16_t* gx, int64_t gx_ld_bytes,
+                              float* wq, qt_stream_t stream);
 int qt_f16_gemm(const uint32_t* Xh, int64_t ldxp, const uint32_t* Wh, int64_t ldwp, const float* bias, float scale,
                 const float* scale_dev, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, qt_stream_t stream);
 

@@ -1,6 +1,7 @@
 // Elementwise quantisers and STE masks (fp32 -> fp32).  All HBM-bound: 16-byte loads/stores per
 // lane, grid-stride, scalar head/tail so any pointer alignment and any n is accepted.
 #include "qt_common.h"
+#include "loglin_quant.h"
 
 namespace {
 
@@ -21,29 +22,17 @@ struct OpCopy {
     __device__ __forceinline__ float operator()(float x) const { return x; }
 };
 
-// ---- Lin / Log fixed-point quantisers (functions/log_lin_connect.py) -----------------------------------------
-// torch.sign = (0 < x) - (x < 0): sign(+-0) = +0, sign(NaN) = NaN
-__device__ __forceinline__ float qt_torch_sign(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : (x != x ? x : 0.0f)); }
-__device__ __forceinline__ float qt_torch_clamp(float v, float lo, float hi) {   // torch.clamp propagates NaN
-    return v != v ? v : (v < lo ? lo : (v > hi ? hi : v));   // compare chain: clamp(-0, 0, hi) stays -0, like ATen
-}
-struct OpLinQuant {   // log_lin_connect.py:61-67: mode 0: clamp(round(x/step)*step, 0, 2^fsr); mode 1: sign(x) * the
-    float step, maxv;  // same of |x|; mode 2: sign(g) * clamp(round(g/step)*step, 0, 2^fsr) (the quantised-gradient
-    int mode;          // backward, :79 — negative g clamps to 0, so it yields -0: reproduced)
-    __device__ __forceinline__ float operator()(float x) const {
-        const float a = mode == 1 ? fabsf(x) : x;
-        const float q = qt_torch_clamp(rintf(a / step) * step, 0.0f, maxv);
-        return mode == 0 ? q : qt_torch_sign(x) * q;
-    }
+// ---- Lin / Log fixed-point quantisers (functions/log_lin_connect.py): the per-element math lives in loglin_quant.h, shared with
+// the quantise-and-pack kernel of csrc/loglin_pack.hip ----------------------------------------------------------------------
+struct OpLinQuant {   // mode 0 / 1 / 2: see qt_lin_quant
+    float step, maxv;
+    int mode;
+    __device__ __forceinline__ float operator()(float x) const { return qt_lin_quant(x, step, maxv, mode); }
 };
-struct OpLogQuant {   // log_lin_connect.py:31-33: [sign(x) *] 2^clamp(round(log2|x|), fsr - 2^bits, fsr)
+struct OpLogQuant {   // with_sign 0 / 1 / 2: see qt_log_quant
     float lo, hi;
     int with_sign;
-    __device__ __forceinline__ float operator()(float x) const {
-        const float e = qt_torch_clamp(rintf(log2f(fabsf(x))), lo, hi);   // x = 0: -inf -> lo
-        const float p = exp2f(e);                                        // integer e: exact (0 below 2^-149)
-        return with_sign == 2 ? qt_safe_sign(x) * p : (with_sign ? qt_torch_sign(x) * p : p);   // 2: AP2's safeSign
-    }
+    __device__ __forceinline__ float operator()(float x) const { return qt_log_quant(x, lo, hi, with_sign); }
 };
 
 template <class Op>

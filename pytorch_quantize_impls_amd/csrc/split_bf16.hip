@@ -25,19 +25,47 @@ __device__ __forceinline__ float bf16_bits_to_f32(uint32_t b) { return __uint_as
 // mode: 0 = activation split, 1 = safeSign weight, 2 = ternary weight, 3 = torch.sign weight (0 -> 0),
 //       4 = raw weight: bf16_rn(w) replicated (for weights that are exact in bf16: Lin / Log fixed-point levels)
 template <int MODE>
+__device__ __forceinline__ void triple_of(float v, const float* __restrict__ alpha, int64_t k, uint32_t* h) {
+    if (MODE == 0) {
+        if (alpha) v *= alpha[k];
+        const uint32_t a = bf16_rn_bits(v);
+        const float r1 = v - bf16_bits_to_f32(a);
+        const uint32_t b = bf16_rn_bits(r1);
+        const float r2 = r1 - bf16_bits_to_f32(b);
+        h[0] = a; h[1] = b; h[2] = bf16_rn_bits(r2);
+    } else {
+        float q;
+        if (MODE == 1) q = qt_safe_sign(v);
+        else if (MODE == 2) q = qt_ternarize(v);
+        else if (MODE == 3) q = v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f);
+        else q = v;
+        const uint32_t qb = bf16_rn_bits(q);
+        h[0] = h[1] = h[2] = qb;
+    }
+}
+
+template <int MODE>
 __global__ __launch_bounds__(256) void triple_kernel(const float* __restrict__ x, int64_t ldx,
                                                      const float* __restrict__ alpha,
                                                      uint16_t* __restrict__ out, int64_t ld_elems,
                                                      int64_t rows, int64_t K) {
     const int64_t pairs_per_row = ld_elems / 6;          // one work item = 2 elements = 6 bf16 = 12 B
-    const int64_t tail_words = (ld_elems - pairs_per_row * 6) / 2;  // leftover 32-bit words to zero
+    const int64_t tail_words = (ld_elems - pairs_per_row * 6) / 2;  // leftover 32-bit words
     const int64_t total = rows * (pairs_per_row + 1);
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
          t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t row = t / (pairs_per_row + 1), p = t - row * (pairs_per_row + 1);
         uint32_t* orow = reinterpret_cast<uint32_t*>(out + row * ld_elems);
-        if (p == pairs_per_row) {  // zero the (< 12-byte) remainder of the row
-            for (int64_t w = 0; w < tail_words; ++w) orow[pairs_per_row * 3 + w] = 0;
+        if (p == pairs_per_row) {  // the (< 12-byte) remainder of the row: the triple of the last element of an odd K when
+            int64_t w0 = 0;        // only it fits there (8 bytes: a tight row stride, e.g. K = 13 in 80 bytes), then zeros
+            if (tail_words == 2 && 2 * p < K) {
+                uint32_t h[3];
+                triple_of<MODE>(x[row * ldx + 2 * p], alpha, 2 * p, h);
+                orow[p * 3 + 0] = h[0] | (h[1] << 16);
+                orow[p * 3 + 1] = h[2];
+                w0 = 2;
+            }
+            for (int64_t w = w0; w < tail_words; ++w) orow[pairs_per_row * 3 + w] = 0;
             continue;
         }
         uint32_t h[6] = {0, 0, 0, 0, 0, 0};
@@ -45,23 +73,7 @@ __global__ __launch_bounds__(256) void triple_kernel(const float* __restrict__ x
         for (int e = 0; e < 2; ++e) {
             const int64_t k = p * 2 + e;
             if (k >= K) continue;
-            float v = x[row * ldx + k];
-            if (MODE == 0) {
-                if (alpha) v *= alpha[k];
-                const uint32_t a = bf16_rn_bits(v);
-                const float r1 = v - bf16_bits_to_f32(a);
-                const uint32_t b = bf16_rn_bits(r1);
-                const float r2 = r1 - bf16_bits_to_f32(b);
-                h[3 * e] = a; h[3 * e + 1] = b; h[3 * e + 2] = bf16_rn_bits(r2);
-            } else {
-                float q;
-                if (MODE == 1) q = qt_safe_sign(v);
-                else if (MODE == 2) q = qt_ternarize(v);
-                else if (MODE == 3) q = v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f);
-                else q = v;
-                const uint32_t qb = bf16_rn_bits(q);
-                h[3 * e] = h[3 * e + 1] = h[3 * e + 2] = qb;
-            }
+            triple_of<MODE>(x[row * ldx + k], alpha, k, h + 3 * e);
         }
         orow[p * 3 + 0] = h[0] | (h[1] << 16);
         orow[p * 3 + 1] = h[2] | (h[3] << 16);

@@ -1506,6 +1506,104 @@ class RealConv2dFn(QtFunction):
         return grad_input, grad_weight, grad_bias, None
 
 
+# ---- Lin / Log fixed-point family (layers/log_lin_layers.py) in training mode -----------------------------------------------------
+# Reference: F.linear / F.conv2d(x, Q(W), b) with Q = LinQuant / LogQuant(lin_back=True): the weight quantiser's backward is the
+# identity, so grad_W is the UN-masked dL/dQ(W).  Q(W) is exact in bf16 (ops.levels_exact_in_bf16) -> the forward and grad_x are
+# exact three-term splits of the real operand (x, g) against the replicated levels; grad_W multiplies two real operands (six-term
+# routes of RealLinearFn / RealConv2dFn).  Both weight operands come from ONE quantise-and-pack launch per step
+# (ops.pack_levels_bf16x3).  Configurations whose levels are not exact in bf16 train on RealLinearFn / RealConv2dFn instead.
+
+class LogLinLinearFn(QtFunction):
+    """F.linear(x, Q(W), b) for a device fp32 x, Q the Lin / Log quantiser ``quant`` = (dtype, fsr, bit_width, with_sign) with
+    levels exact in bf16."""
+
+    @staticmethod
+    def forward(ctx, input, weight, bias, quant):
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(input)
+        fwd, gx, _ = ops.pack_levels_bf16x3(weight, *quant, grad_x=ctx.needs_input_grad[0])
+        ctx.gx, ctx.w_shape = gx, tuple(weight.shape)
+        x2 = input.reshape(-1, input.shape[-1])
+        y = ops.float_linear(x2.detach().contiguous(), weight.detach(), "raw", bias.detach() if bias is not None else None,
+                             weight_triples=fwd, terms=3)
+        return y.view(*input.shape[:-1], weight.shape[0])
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        input, = ctx.saved_tensors
+        g2 = grad_output.reshape(-1, grad_output.shape[-1])
+        x2 = input.reshape(-1, input.shape[-1])
+        grad_input = grad_weight = grad_bias = None
+        if ctx.needs_input_grad[0]:
+            N, K = ctx.w_shape
+            shape_t = torch.empty((K, N), dtype=torch.float32, device="meta")
+            grad_input = ops.float_linear(g2.contiguous(), shape_t, "raw", weight_triples=ctx.gx, terms=3).view(input.shape)
+        if ctx.needs_input_grad[1]:
+            grad_weight = real_matmul(g2.t(), x2)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            grad_bias = g2.sum(0)
+        ctx.gx = None
+        return grad_input, grad_weight, grad_bias, None
+
+
+def _conv_grad_input_route(weight_shape, stride, padding, dilation) -> bool:
+    """Geometry ops.conv2d_grad_input_q takes (square stride, un-dilated, padding <= k - 1)."""
+    (sh, sw), (ph, pw), (dh, dw) = ops._pairs(stride), ops._pairs(padding), ops._pairs(dilation)
+    kh, kw = int(weight_shape[2]), int(weight_shape[3])
+    return (dh, dw) == (1, 1) and sh == sw and sh >= 1 and ph <= kh - 1 and pw <= kw - 1
+
+
+class LogLinConv2dFn(QtFunction):
+    """F.conv2d(x, Q(W), b) (groups == 1, zero padding) for a device fp32 NCHW / channels-last x, Q as in LogLinLinearFn.  grad_x
+    outside conv2d_grad_input_q's geometry (dilation, non-square stride, ...) uses the counted library helper on Q(W), whose fp32
+    image then comes from the same pack launch."""
+
+    @staticmethod
+    def forward(ctx, input, weight, bias, quant, conv_args):
+        stride, padding, dilation, groups = conv_args
+        ctx.has_bias, ctx.conv_args, ctx.quant = bias is not None, conv_args, quant
+        ctx.save_for_backward(input, weight)
+        want_gx = ctx.needs_input_grad[0]
+        routed = _conv_grad_input_route(weight.shape, stride, padding, dilation)
+        fwd, gx, wq = ops.pack_levels_bf16x3(weight, *quant, grad_x=want_gx and routed, image=want_gx and not routed)
+        ctx.gx, ctx.wq, ctx.w_shape = gx, wq, tuple(weight.shape)
+        N, C, H, W = input.shape
+        Cout, _, kh, kw = (int(v) for v in weight.shape)
+        y2 = ops.float_conv2d(input.detach(), weight.detach(), "raw", bias.detach() if bias is not None else None, stride, padding,
+                              dilation, weight_triples=fwd, terms=3)
+        Ho, Wo = ops.conv_out_hw(H, W, kh, kw, stride, padding, dilation)
+        y = y2.view(N, Ho, Wo, Cout).permute(0, 3, 1, 2)
+        if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
+            y = y.contiguous()
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        input, weight = ctx.saved_tensors
+        stride, padding, dilation, groups = ctx.conv_args
+        go = _dense(grad_output)
+        grad_input = grad_weight = grad_bias = None
+        if ctx.needs_input_grad[0]:
+            if ctx.gx is not None and go.numel() > 0:
+                shape = torch.empty(ctx.w_shape, dtype=torch.float32, device="meta")
+                grad_input = ops.conv2d_grad_input_q(input.shape, shape, go, stride, padding, dilation, kind="raw", terms=3,
+                                                     weight_triples=ctx.gx)
+                if grad_input is not None and input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
+                    grad_input = grad_input.contiguous()
+            if grad_input is None:
+                wq = ctx.wq
+                if wq is None:            # (an empty gradient: nothing was packed for it)
+                    _, _, wq = ops.pack_levels_bf16x3(weight, *ctx.quant, forward=False, grad_x=False, image=True)
+                grad_input = lib_conv2d_input(input.shape, wq, go, stride, padding, dilation, groups)
+        if ctx.needs_input_grad[1]:
+            grad_weight = conv_grad_weight(input, ctx.w_shape, go, stride, padding, dilation, groups, x_is_pm1=False,
+                                           real_any_channels=True)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            grad_bias = go.sum((0, 2, 3))
+        ctx.gx = ctx.wq = None
+        return grad_input, grad_weight, grad_bias, None, None
+
+
 def grouped_quant_conv(layer, input, kind: str, quant_op):
     """BinConv2d / TerConv2d with ``groups`` > 1 (layers/binary_layers.py:59-60,103-106 hand ``groups`` to F.conv2d): group g is
     an independent conv of its channel slice with its rows of the weight, and the element-wise quantisers (safeSign, the fixed

@@ -4,6 +4,11 @@ The quantised weight levels — multiples of 2^(fsr - bit_width) up to 2^fsr (Li
 of two (Log) — are exactly representable in bf16, so on a HIP device the contraction of a real-valued activation
 with them runs on the bf16 matrix cores through the exact bf16-triple split (same route as the first layer of a
 binary net): fp32-GEMM accuracy, and for Log weights this IS the shift-add GEMM the paper motivates.
+
+Under autograd a device fp32 input trains on functions._fused.LogLinLinearFn / LogLinConv2dFn (one quantise-and-pack launch of the
+weight per step, exact three-term forward and grad_x, six-term grad_W); configurations whose levels are not exact in bf16
+(ops.levels_exact_in_bf16: Lin bit_width > 8, Log levels below 2^-126) on RealLinearFn / RealConv2dFn.  Only grouped convs,
+non-"zeros" padding modes, string padding and non-fp32 dtypes take the (counted) dense library.
 """
 import torch
 
@@ -14,6 +19,13 @@ from .common import EvalSwapMixin, QLayer
 
 def _exact_in_bf16(dtype, bit_width):
     return dtype == "log" or (dtype == "lin" and bit_width <= 8)
+
+
+def _autograd_on_device(layer, input) -> bool:
+    """A device fp32 input of a device fp32 layer with autograd recording: the training routes of functions._fused."""
+    return (input.is_cuda and input.dtype == torch.float32 and input.numel() > 0 and layer.weight.is_cuda
+            and layer.weight.dtype == torch.float32 and torch.is_grad_enabled()
+            and (input.requires_grad or layer.weight.requires_grad))
 
 
 class _WeightInit:
@@ -51,6 +63,10 @@ class LinearQuant(_WeightInit, EvalSwapMixin, torch.nn.Linear, QLayer):
     def forward(self, input):
         lazy.note_inference_call(self, input)
         input = lazy.resolve(input)
+        if _autograd_on_device(self, input):
+            if _fused.ops.levels_exact_in_bf16(self.qdtype, self.fsr, self.bit_width):
+                return _fused.LogLinLinearFn.apply(input, self.weight, self.bias, (self.qdtype, self.fsr, self.bit_width, True))
+            return _fused.RealLinearFn.apply(input, self.weight_op.forward(self.weight), self.bias)
         wq = self.weight_op.forward(self.weight)
         if (input.is_cuda and input.dtype == torch.float32 and input.numel() > 0 and _exact_in_bf16(self.qdtype, self.bit_width)
                 and not (torch.is_grad_enabled() and (input.requires_grad or self.weight.requires_grad))):
@@ -58,7 +74,7 @@ class LinearQuant(_WeightInit, EvalSwapMixin, torch.nn.Linear, QLayer):
             wt = None if self.training else self._eval_planes(
                 lambda w2: _fused.ops.weight_bf16x3(w2, "raw", terms=3), key="bf16x3_raw")
             return _fused.ops.float_linear(input, wq.detach(), "raw", self.bias, weight_triples=wt, terms=3)
-        _fused.note_library_path(input, "Lin/Log linear: autograd, a non-fp32 dtype or levels beyond bf16")
+        _fused.note_library_path(input, "Lin/Log linear: a non-fp32 dtype, or levels beyond bf16 without autograd")
         return torch.nn.functional.linear(input, wq, self.bias)
 
 
@@ -83,6 +99,15 @@ class QuantConv2d(_WeightInit, EvalSwapMixin, torch.nn.Conv2d, QLayer):
     def forward(self, input):
         lazy.note_inference_call(self, input)
         input = lazy.resolve(input)
+        if (_autograd_on_device(self, input) and input.dim() == 4 and self.groups == 1 and self.padding_mode == "zeros"
+                and not isinstance(self.padding, str)):
+            args = (self.stride, self.padding, self.dilation, 1)
+            if _fused.ops.levels_exact_in_bf16(self.qdtype, self.fsr, self.bit_width):
+                # eval: the swapped weight already holds the levels -> packed as it is (LinQuant(bit_width = 32) = identity)
+                quant = (self.qdtype, self.fsr, self.bit_width, True) if self.training else ("lin", 0, 32, True)
+                return _fused.LogLinConv2dFn.apply(input, self.weight, self.bias, quant, args)
+            wq = self.weight_op.forward(self.weight) if self.training else self.weight
+            return _fused.RealConv2dFn.apply(input, wq, self.bias, args)
         wq = self.weight_op.forward(self.weight) if self.training else self.weight
         if (input.is_cuda and input.dtype == torch.float32 and input.numel() > 0 and input.dim() == 4
                 and self.groups == 1 and self.padding_mode == "zeros" and not isinstance(self.padding, str)
@@ -100,5 +125,5 @@ class QuantConv2d(_WeightInit, EvalSwapMixin, torch.nn.Conv2d, QLayer):
             if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
                 y = y.contiguous()
             return y
-        _fused.note_library_path(input, "Lin/Log conv: autograd, groups, a non-fp32 dtype or levels beyond bf16")
+        _fused.note_library_path(input, "Lin/Log conv: groups, padding mode, a non-fp32 dtype, or levels beyond bf16 without autograd")
         return torch.nn.functional.conv2d(input, wq, self.bias, self.stride, self.padding, self.dilation, self.groups)

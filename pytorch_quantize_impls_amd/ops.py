@@ -2141,6 +2141,73 @@ def pack_conv_weight_bf16x3(weight: torch.Tensor, kind: str, terms: Optional[int
     return TriplePlanes(data=data, rows=Cout, K=kbytes // (2 * terms), terms=terms)   # K only used for consistency checks
 
 
+_LEVEL_DTYPES = {"lin": 0, "log": 1}
+
+
+def levels_exact_in_bf16(dtype: str, fsr, bit_width) -> bool:
+    """Is every level of the Lin / Log weight quantiser (functions/log_lin_connect.py) a NORMAL bf16 number, so that the weight
+    can enter the matrix cores as one exact bf16 term?  Lin: multiples m * 2^(fsr - bit_width), m <= 2^bit_width — at most 8
+    significant bits for bit_width <= 8; bit_width 32 is the identity.  Log: +-2^e, e in [fsr - 2^bit_width, fsr] — exact down
+    to 2^-126; below that they would be bf16 denormals, which nothing here relies on.  Configurations outside the quantise
+    kernels' window (-60 <= fsr <= 60, Log bit_width <= 16; the torch expression runs there) are not taken either."""
+    try:
+        f, b = int(fsr), int(bit_width)
+    except (TypeError, ValueError):
+        return False
+    if f != fsr or b != bit_width or not -60 <= f <= 60:
+        return False
+    if dtype == "lin":
+        return 1 <= b <= 8
+    if dtype == "log":
+        return 1 <= b <= 16 and f - 2 ** b >= -126
+    return False
+
+
+def pack_levels_bf16x3(weight: torch.Tensor, dtype: str, fsr: int, bit_width: int, with_sign: bool = True,
+                       forward: bool = True, grad_x: bool = True, image: bool = False):
+    """Quantise-and-pack of a Lin / Log weight for a training step, one launch (qt_bf16x3_pack_levels_f32 /
+    qt_bf16x3_pack_conv_levels_f32): returns (fwd, gx, wq), each None unless asked for.
+      * Linear weight [N, K]: fwd = weight_bf16x3(Q(W), "raw", terms=3), gx = weight_bf16x3(Q(W).t(), "raw", terms=3);
+      * conv weight [Cout, Cin, kh, kw]: fwd = pack_conv_weight_bf16x3(Q(W), "raw", terms=3), gx = the same with
+        transpose_flip=True;
+      * wq: the fp32 image Q(W) (the bits of lin_quantize(W, fsr, bit_width, 1 if with_sign else 0) / log_quantize), with the
+        weight's strides.
+    Q is the quantiser of log_lin_connect.LinQuant / LogQuant; the planes hold bf16_rn(Q(W)), exact when
+    ``levels_exact_in_bf16(dtype, fsr, bit_width)``."""
+    _require(weight, "weight")
+    if dtype not in _LEVEL_DTYPES:
+        raise ValueError(f"dtype must be 'lin' or 'log', got {dtype!r}")
+    if weight.dim() not in (2, 4) or weight.numel() == 0:
+        raise ValueError(f"expected a non-empty [N, K] or [Cout, Cin, kh, kw] weight, got shape {tuple(weight.shape)}")
+    if not (forward or grad_x or image):
+        raise ValueError("nothing to produce")
+    w = weight.detach()
+    if not (_storage_dense(w) or (w.dim() == 2 and w.t().is_contiguous())) or w.data_ptr() % 4:
+        w = w.contiguous()
+    conv = w.dim() == 4
+    Cout, Cin = int(w.shape[0]), int(w.shape[1])
+    kh, kw = (int(w.shape[2]), int(w.shape[3])) if conv else (1, 1)
+
+    def plane(rows, chans):
+        kbytes = kh * kw * triple_ld_bytes(chans, 16, 3)
+        ld = max(128, (kbytes + 127) // 128 * 128)
+        data = torch.empty((rows, ld // 2), dtype=torch.int16, device=w.device)
+        return TriplePlanes(data=data, rows=rows, K=kbytes // 6 if conv else chans), ld
+
+    fwd, ld_f = plane(Cout, Cin) if forward else (None, 0)
+    gx, ld_g = plane(Cin, Cout) if grad_x else (None, 0)
+    wq = torch.empty_like(w) if image else None
+    args = (_p(fwd.data if fwd is not None else None), int(ld_f), _p(gx.data if gx is not None else None), int(ld_g), _p(wq),
+            _stream(w.device))
+    q = (_LEVEL_DTYPES[dtype], int(fsr), int(bit_width), int(bool(with_sign)))
+    with _on(w.device):
+        if conv:
+            _lib.call("qt_bf16x3_pack_conv_levels_f32", _p(w), *(int(v) for v in w.stride()), Cout, Cin, kh, kw, *q, *args)
+        else:
+            _lib.call("qt_bf16x3_pack_levels_f32", _p(w), int(w.stride(0)), int(w.stride(1)), Cout, Cin, *q, *args)
+    return fwd, gx, wq
+
+
 #: fixed power-of-two scale the first layer's space-to-depth pack speculates with (None / 0: always the separate max|x| pass).
 #: 2^-11 is admissible for max|x| in [2^-3, 2^4) (max|x| / s in [2^8, 2^15): below fp16's overflow with a binade to spare):
 #: unit-variance and [0, 1] images; anything else is repacked on the device.
@@ -2435,7 +2502,8 @@ def zero_dilated_gradient(grad_output: torch.Tensor, input_shape, kernel_hw, str
 
 
 def conv2d_grad_input_q(input_shape, weight_q: torch.Tensor, grad_output: torch.Tensor, stride, padding, dilation,
-                        kind: str = "sign", out_scale: float = 1.0, out_scale_dev: Optional[torch.Tensor] = None):
+                        kind: str = "sign", out_scale: float = 1.0, out_scale_dev: Optional[torch.Tensor] = None,
+                        terms: Optional[int] = None, weight_triples: Optional[TriplePlanes] = None):
     """grad wrt the input of conv2d(x, Q(weight_q)): ``weight_q`` already quantised — +-1 / 0 (``kind`` "sign") or integer
     levels (``kind`` "raw": the k-bit DoReFa levels c = n * w_q, the caller scales by 1 / n) — or the latent weight with its
     quantiser (``kind`` "binary" / "ternary": applied inside the operand pack): the forward's exact-split conv
@@ -2445,7 +2513,9 @@ def conv2d_grad_input_q(input_shape, weight_q: torch.Tensor, grad_output: torch.
     zeros appended, which turns conv_transpose(g, W, stride s) into the stride-1 conv above (3/4 of its products are with the
     inserted zeros; these layers are the small ones).  ``out_scale`` / ``out_scale_dev``: see ``float_conv2d`` (1 / n of the
     levels, DoReFa's E).  None when the shape is outside the route (dilation != 1, padding > k - 1, non-square stride): the
-    caller uses torch.nn.grad.conv2d_input."""
+    caller uses torch.nn.grad.conv2d_input.  ``terms``: the split of the gradient (default FLOAT_SPLIT; 3 = exact, for weight levels
+    that are exact in bf16 but not in fp16); ``weight_triples``: the grad_x operand already packed (pack_levels_bf16x3's gx plane,
+    ``weight_q`` then only gives the shape)."""
     (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
     Cout, Cin, kh, kw = (int(v) for v in weight_q.shape)
     if (dh, dw) != (1, 1) or sh != sw or sh < 1 or ph > kh - 1 or pw > kw - 1:
@@ -2457,10 +2527,11 @@ def conv2d_grad_input_q(input_shape, weight_q: torch.Tensor, grad_output: torch.
         if g is None:
             return None
     # the flipped, transposed weight [Cin, Cout, kh, kw] only ever exists as the conv's packed operand
-    wt = pack_conv_weight_bf16x3(weight_q.detach(), kind, transpose_flip=True)
+    wt = weight_triples if weight_triples is not None else \
+        pack_conv_weight_bf16x3(weight_q.detach(), kind, terms=terms, transpose_flip=True)
     shape_t = torch.empty((Cin, Cout, kh, kw), dtype=torch.float32, device="meta")
     y2 = float_conv2d(g, shape_t, kind, None, 1, (kh - 1 - ph, kw - 1 - pw), 1, weight_triples=wt, out_scale=out_scale,
-                      out_scale_dev=out_scale_dev)
+                      out_scale_dev=out_scale_dev, terms=terms if terms is not None else wt.terms)
     return y2.view(N, H, W, C).permute(0, 3, 1, 2)
 
 
