@@ -79,6 +79,22 @@ def note_library_path(input, reason: str) -> None:
         LIBRARY_PATHS[reason] += 1
 
 
+def autograd_records(input, weight, bias=None) -> bool:
+    """Autograd records this call: grad mode is on and the input or the weight requires grad.  ``bias`` is consulted only
+    when it is passed (the loss-aware layers, which regularise it)."""
+    return torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad
+                                        or (bias is not None and bias.requires_grad))
+
+
+def nchw_result(y2: torch.Tensor, input: torch.Tensor, N: int, H: int, W: int, C: int) -> torch.Tensor:
+    """The NHWC result rows ``y2`` as an (N, C, H, W) view; copied to NCHW storage when ``input`` is in it (the caller works
+    in NCHW storage)."""
+    y = y2.view(N, H, W, C).permute(0, 3, 1, 2)
+    if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
+        y = y.contiguous()
+    return y
+
+
 def _safe_sign_t(w: torch.Tensor) -> torch.Tensor:
     one = torch.ones((), dtype=w.dtype, device=w.device)
     return torch.where(w < 0, -one, one)
@@ -389,10 +405,7 @@ def quant_conv2d_forward(input, weight, bias, stride, padding, dilation, groups,
             Ho, Wo = ops.conv_out_hw(H, W, kh, kw, stride, padding, dilation)
             if epi is not None:
                 return y2, (N, int(weight.shape[0]), Ho, Wo)
-            y = y2.view(N, Ho, Wo, weight.shape[0]).permute(0, 3, 1, 2)   # NCHW view, NHWC storage
-            if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
-                y = y.contiguous()                                         # caller works in NCHW storage
-            return y
+            return nchw_result(y2, input, N, Ho, Wo, weight.shape[0])
     if packable and _cfg("FLOAT_PATH") == "bf16x3" and input.dtype == torch.float32 and input.numel() > 0:
         # real-valued activation (first layer): exact bf16 triples + implicit-GEMM conv on the bf16
         # matrix cores; the quantisers are idempotent so an explicit quantised image is packed the same way
@@ -417,10 +430,7 @@ def quant_conv2d_forward(input, weight, bias, stride, padding, dilation, groups,
                     if nib_epi is not None and isinstance(y2, ops.BitPlanes):
                         y2 = ops.bits_to_nib_pad(y2, N, Ho, Wo, nib_epi.out_halo, ld=ops.pixel_ld_nib(y2.K))
                     return y2, (N, int(weight.shape[0]), Ho, Wo)
-                y = y2.view(N, Ho, Wo, weight.shape[0]).permute(0, 3, 1, 2)
-                if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
-                    y = y.contiguous()
-                return y
+                return nchw_result(y2, input, N, Ho, Wo, weight.shape[0])
         if ops.first_direct_applicable(C, (kh, kw), stride, padding, dilation):
             # (both epilogues on ONE route: the threshold bits of the fused / deferred chain must come from the very accumulators
             # the fp32 output of the module-by-module execution shows, or the two executions differ at ties.  The kernel's fp32
@@ -440,10 +450,7 @@ def quant_conv2d_forward(input, weight, bias, stride, padding, dilation, groups,
                     if nib_epi is not None:
                         y2 = ops.bits_to_nib_pad(y2, N, Ho, Wo, nib_epi.out_halo, ld=ops.pixel_ld_nib(y2.K))
                     return y2, (N, int(weight.shape[0]), Ho, Wo)
-                y = y2.view(N, Ho, Wo, weight.shape[0]).permute(0, 3, 1, 2)
-                if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
-                    y = y.contiguous()
-                return y
+                return nchw_result(y2, input, N, Ho, Wo, weight.shape[0])
         if USE_S2D and ops.s2d_applicable(C, kh, kw, stride, dilation, padding):
             # strided few-channel conv (conv1) == stride-1 conv on the space-to-depth image; the gather and
             # the exact bf16 split are one kernel, the transformed weight is cached by eval-mode layers
@@ -472,19 +479,15 @@ def quant_conv2d_forward(input, weight, bias, stride, padding, dilation, groups,
                 if nib_epi is not None and isinstance(y2, ops.BitPlanes):
                     y2 = ops.bits_to_nib_pad(y2, N, Ho, Wo, nib_epi.out_halo, ld=ops.pixel_ld_nib(y2.K))
                 return y2, (N, int(weight.shape[0]), Ho, Wo)
-            y = y2.view(N, H2, W2, weight.shape[0])[:, :Ho, :Wo, :].permute(0, 3, 1, 2)
-            if H2 != Ho or W2 != Wo:
-                y = y.contiguous(memory_format=torch.channels_last)
+            if H2 != Ho or W2 != Wo:   # drop the pixels the space-to-depth rounding added
+                y2 = y2.view(N, H2, W2, -1)[:, :Ho, :Wo, :].contiguous()
         else:
             wt = weight_triples_fn("plain") if weight_triples_fn is not None else None
             y2 = ops.float_conv2d(input, weight_q if weight_q is not None else weight, kind, bias, stride, padding,
                                   dilation, weight_triples=wt, epi=epi)
             if epi is not None:
                 return y2, (N, int(weight.shape[0]), Ho, Wo)
-            y = y2.view(N, Ho, Wo, weight.shape[0]).permute(0, 3, 1, 2)
-        if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
-            y = y.contiguous()
-        return y
+        return nchw_result(y2, input, N, Ho, Wo, weight.shape[0])
     if epi is not None:
         raise ValueError("the threshold-bit epilogue needs a device fp32 NCHW input, groups == 1 and zero padding")
     wq = weight_q if weight_q is not None else quantize_weight_f32(weight, kind)
@@ -514,10 +517,7 @@ def real_weight_conv2d(input: torch.Tensor, weight_q: torch.Tensor, bias, stride
         if y2 is not None:
             N_, _, H, W = input.shape
             Ho, Wo = ops.conv_out_hw(H, W, weight_q.shape[2], weight_q.shape[3], stride, padding, dilation)
-            y = y2.view(N_, Ho, Wo, weight_q.shape[0]).permute(0, 3, 1, 2)
-            if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
-                y = y.contiguous()
-            return y
+            return nchw_result(y2, input, N_, Ho, Wo, weight_q.shape[0])
     return F.conv2d(input, weight_q, bias=bias, stride=stride, padding=padding, dilation=dilation, groups=groups)
 
 
@@ -664,10 +664,6 @@ def xnor_linear_operands(layer=None, weight=None):
     if layer is not None:
         return layer._eval_planes(build, key="xnor_pairs")
     return build(weight.detach())
-
-
-#: dispatch used by the layers' forward for PackedActivation inputs: [is_linear] -> function
-PACKED_FWD = {True: packed_linear, False: packed_conv2d}
 
 
 def _dense(t: torch.Tensor) -> torch.Tensor:
@@ -1053,9 +1049,7 @@ def dorefa_w1_conv_forward(input, weight, bias, conv_args, prequantized: bool, w
         Ho, Wo = ops.conv_out_hw(H, W, kh, kw, stride, padding, dilation)
         y2 = ops.float_conv2d(input.detach(), weight.detach(), "binary", bias.detach() if bias is not None else None, stride,
                               padding, dilation, out_scale_dev=E)
-        y = y2.view(N_, Ho, Wo, weight.shape[0]).permute(0, 3, 1, 2)
-        if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
-            y = y.contiguous()
+        y = nchw_result(y2, input, N_, Ho, Wo, weight.shape[0])
         if route is not None:
             route.append("split")
         return y
@@ -1138,10 +1132,7 @@ def dorefa_levels_conv_forward(input, weight_q, bias, conv_args, bit_width: int,
     y2 = ops.float_conv2d(input.detach(), _weight_levels(weight_q, bit_width), "raw",
                           bias.detach() if bias is not None else None, stride, padding, dilation,
                           weight_triples=level_planes, out_scale=_inv_levels(bit_width))
-    y = y2.view(N_, Ho, Wo, weight_q.shape[0]).permute(0, 3, 1, 2)
-    if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
-        y = y.contiguous()
-    return y
+    return nchw_result(y2, input, N_, Ho, Wo, weight_q.shape[0])
 
 
 def dorefa_levels_linear_forward(input, weight_q, bias, bit_width: int, level_planes=None):
@@ -1493,9 +1484,7 @@ class RealConv2dFn(QtFunction):
                 y2 = ops.real_conv2d(gd, wt, None, 1, (kh - 1 - ph, kw - 1 - pw), 1) if gd is not None else None
                 if y2 is not None:
                     N_, C, H, W = input.shape
-                    grad_input = y2.view(N_, H, W, C).permute(0, 3, 1, 2)
-                    if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
-                        grad_input = grad_input.contiguous()
+                    grad_input = nchw_result(y2, input, N_, H, W, C)
             if grad_input is None:
                 grad_input = lib_conv2d_input(input.shape, weight, go, stride, padding, dilation, groups)
         if ctx.needs_input_grad[1]:
@@ -1572,10 +1561,7 @@ class LogLinConv2dFn(QtFunction):
         y2 = ops.float_conv2d(input.detach(), weight.detach(), "raw", bias.detach() if bias is not None else None, stride, padding,
                               dilation, weight_triples=fwd, terms=3)
         Ho, Wo = ops.conv_out_hw(H, W, kh, kw, stride, padding, dilation)
-        y = y2.view(N, Ho, Wo, Cout).permute(0, 3, 1, 2)
-        if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
-            y = y.contiguous()
-        return y
+        return nchw_result(y2, input, N, Ho, Wo, Cout)
 
     @staticmethod
     def backward(ctx, grad_output):
@@ -1614,7 +1600,7 @@ def grouped_quant_conv(layer, input, kind: str, quant_op):
     cin, cout = int(input.shape[1]) // G, int(layer.weight.shape[0]) // G
     args = (layer.stride, layer.padding, layer.dilation, 1)
     if not layer.training:
-        if torch.is_grad_enabled() and (input.requires_grad or layer.weight.requires_grad):
+        if autograd_records(input, layer.weight):
             return None
         if not layer._eval_on_grid():
             return None

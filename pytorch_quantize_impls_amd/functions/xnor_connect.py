@@ -157,10 +157,7 @@ def XNORConv2d(dim=[0, 1], quant_input=False, stride=1, padding=1, dilation=1, g
                     ctx.save_for_backward(input, weight, taps.alpha.view(1, 1, kh, kw), bias)
                     N_, _, H, W = input.shape
                     Ho, Wo = ops.conv_out_hw(H, W, kh, kw, stride, padding, dilation)
-                    y = y2.view(N_, Ho, Wo, weight.shape[0]).permute(0, 3, 1, 2)
-                    if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
-                        y = y.contiguous()
-                    return y
+                    return _fused.nchw_result(y2, input, N_, Ho, Wo, weight.shape[0])
             if quant_input:
                 # both operands binarised (:142-143): x -> sign(x) * mean(|x|, 1) per pixel; backward sees this quantised tensor
                 # (:144).  With one alpha per tap the conv is  sum_t alpha_t A[pixel(m, t)] D_t[m, co]  (D_t: integer dot of the two
@@ -210,10 +207,7 @@ def XNORConv2d(dim=[0, 1], quant_input=False, stride=1, padding=1, dilation=1, g
                 if y2 is not None:
                     N_, _, H, W = input.shape
                     Ho, Wo = ops.conv_out_hw(H, W, weight.shape[2], weight.shape[3], stride, padding, dilation)
-                    y = y2.view(N_, Ho, Wo, weight.shape[0]).permute(0, 3, 1, 2)
-                    if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
-                        y = y.contiguous()
-                    return y
+                    return _fused.nchw_result(y2, input, N_, Ho, Wo, weight.shape[0])
             _fused.note_library_path(input, "XNOR conv outside the matrix-core routes")
             return torch.nn.functional.conv2d(input, weight_b, bias=bias, stride=stride,
                                               padding=padding, dilation=dilation, groups=groups)

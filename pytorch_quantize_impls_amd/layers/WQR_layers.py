@@ -17,7 +17,7 @@ from .. import lazy
 from ..functions import WQR_connect
 from ..utils.tools import flat_net
 from .common import QLayer
-from .elastic_layers import LossQuantMixin
+from .elastic_layers import _LossQuantLinear, LossQuantMixin, _copy_params
 
 
 class _WqrTrain:
@@ -42,34 +42,8 @@ class _WqrTrain:
     def set_beta(self, beta):
         self._set_coef("beta", beta)
 
-    def _init_coefs(self, kapa, beta):
-        self.register_buffer("kapa", torch.Tensor([kapa]))
-        self.register_buffer("beta", torch.Tensor([beta]))
 
-
-class _WqrLinear(_WqrTrain, LossQuantMixin, torch.nn.Module, QLayer):
-    def _init_linear(self, in_features, out_features, bias, kapa, beta):
-        self.in_features, self.out_features = in_features, out_features
-        self._init_coefs(kapa, beta)
-        self.weight = torch.nn.Parameter(torch.empty(out_features, in_features))
-        if bias:
-            self.bias = torch.nn.Parameter(torch.empty(out_features))
-        else:
-            self.register_parameter("bias", None)
-        self.reset_parameters()
-
-    def reset_parameters(self):
-        lo, hi = self._range()
-        self.weight.data.uniform_(lo, hi)
-        if self.bias is not None:
-            self.bias.data.zero_()
-
-    def clamp(self):
-        lo, hi = self._range()
-        self.weight.data.clamp_(lo, hi)
-        if self.bias is not None:
-            self.bias.data.clamp_(lo, hi)
-
+class _WqrLinear(_WqrTrain, _LossQuantLinear):
     def forward(self, input):
         lazy.note_inference_call(self, input)
         input = lazy.resolve(input)
@@ -81,21 +55,14 @@ class LinearQuantWLin(_WqrLinear):
     def convert(other, bottom=-1, top=1, size=5, kapa=0, beta=0):
         if not isinstance(other, torch.nn.Linear):
             raise TypeError("Expected a torch.nn.Linear ! Receive:  {}".format(other.__class__))
-        result = LinearQuantWLin(other.in_features, other.out_features, other.bias is not None, bottom=bottom, top=top, size=size,
-                                 kapa=kapa, beta=beta)
-        result.weight.data.copy_(other.weight.data)
-        if other.bias is not None:
-            result.bias.data.copy_(other.bias.data)
-        return result
+        return _copy_params(other, LinearQuantWLin(other.in_features, other.out_features, other.bias is not None, bottom=bottom,
+                                                  top=top, size=size, kapa=kapa, beta=beta))
 
     def __init__(self, in_features, out_features, bias=True, bottom=-1, top=1, size=5, kapa=0, beta=0):
         torch.nn.Module.__init__(self)
         self.bottom, self.top, self.size = bottom, top, size
-        self._init_linear(in_features, out_features, bias, kapa, beta)
+        self._init_linear(in_features, out_features, bias, kapa=kapa, beta=beta)
         self.linear_op = WQR_connect.QuantWLinDense(size=size, bottom=bottom, top=top)
-
-    def _range(self):
-        return self.bottom, self.top
 
 
 class LinearQuantWLog(_WqrLinear):
@@ -103,37 +70,20 @@ class LinearQuantWLog(_WqrLinear):
     def convert(other, gamma=2, init=0.25, size=5, kapa=0, beta=0):
         if not isinstance(other, torch.nn.Linear):
             raise TypeError("Expected a torch.nn.Linear ! Receive:  {}".format(other.__class__))
-        result = LinearQuantWLog(other.in_features, other.out_features, other.bias is not None, gamma=gamma, init=init, size=size,
-                                 kapa=kapa, beta=beta)
-        result.weight.data.copy_(other.weight.data)
-        if other.bias is not None:
-            result.bias.data.copy_(other.bias.data)
-        return result
+        return _copy_params(other, LinearQuantWLog(other.in_features, other.out_features, other.bias is not None, gamma=gamma,
+                                                  init=init, size=size, kapa=kapa, beta=beta))
 
     def __init__(self, in_features, out_features, bias=True, gamma=2, init=0.25, size=5, kapa=0, beta=0):
         torch.nn.Module.__init__(self)
         self.gamma, self.init, self.size = gamma, init, size
-        self._init_linear(in_features, out_features, bias, kapa, beta)
+        self._init_linear(in_features, out_features, bias, kapa=kapa, beta=beta)
         self.linear_op = WQR_connect.QuantWLogDense(gamma=gamma, init=init, size=size)
-
-    def _range(self):
-        b = self.init * self.gamma ** (self.size - 1)
-        return -b, b
 
 
 class _WqrConv(_WqrTrain, LossQuantMixin, torch.nn.Conv2d, QLayer):
     def reset_parameters(self):
         """Uniform over the level range, bias 0 (upstream's QuantConv2dWLin; the Log conv's is fixed to +-init*gamma^(size-1))."""
-        lo, hi = self._range()
-        self.weight.data.uniform_(lo, hi)
-        if self.bias is not None:
-            self.bias.data.zero_()
-
-    def clamp(self):
-        lo, hi = self._range()
-        self.weight.data.clamp_(lo, hi)
-        if self.bias is not None:
-            self.bias.data.clamp_(lo, hi)
+        _LossQuantLinear.reset_parameters(self)
 
     def forward(self, input):
         lazy.note_inference_call(self, input)
@@ -146,24 +96,18 @@ class QuantConv2dWLin(_WqrConv):
     def convert(other, bottom=-1, top=1, size=5, kapa=0, beta=0):
         if not isinstance(other, torch.nn.Conv2d):
             raise TypeError("Expected a torch.nn.Conv2d ! Receive:  {}".format(other.__class__))
-        result = QuantConv2dWLin(other.in_channels, other.out_channels, other.kernel_size, stride=other.stride, padding=other.padding,
-                                 dilation=other.dilation, groups=other.groups, bias=other.bias is not None, bottom=bottom, top=top,
-                                 size=size, kapa=kapa, beta=beta)
-        result.weight.data.copy_(other.weight.data)
-        if other.bias is not None:
-            result.bias.data.copy_(other.bias.data)
-        return result
+        return _copy_params(other, QuantConv2dWLin(other.in_channels, other.out_channels, other.kernel_size, stride=other.stride,
+                                                  padding=other.padding, dilation=other.dilation, groups=other.groups,
+                                                  bias=other.bias is not None, bottom=bottom, top=top, size=size, kapa=kapa,
+                                                  beta=beta))
 
     def __init__(self, in_channels, out_channels, kernel_size, bottom=-1, top=1, size=5, kapa=0, beta=0, stride=1, padding=1,
                  dilation=1, groups=1, bias=True):
         self.top, self.bottom, self.size = top, bottom, size
         torch.nn.Conv2d.__init__(self, in_channels, out_channels, kernel_size, stride=stride, padding=padding, dilation=dilation,
                                  groups=groups, bias=bias)
-        self._init_coefs(kapa, beta)
+        self._init_coefs(kapa=kapa, beta=beta)
         self.weight_op = WQR_connect.QuantWeightWLin(self.top, self.bottom, self.size)
-
-    def _range(self):
-        return self.bottom, self.top
 
 
 class QuantConv2dWLog(_WqrConv):
@@ -171,25 +115,18 @@ class QuantConv2dWLog(_WqrConv):
     def convert(other, gamma=2, init=0.25, size=5, kapa=0, beta=0):
         if not isinstance(other, torch.nn.Conv2d):
             raise TypeError("Expected a torch.nn.Conv2d ! Receive:  {}".format(other.__class__))
-        result = QuantConv2dWLog(other.in_channels, other.out_channels, other.kernel_size, stride=other.stride, padding=other.padding,
-                                 dilation=other.dilation, groups=other.groups, bias=other.bias is not None, gamma=gamma, init=init,
-                                 size=size, kapa=kapa, beta=beta)
-        result.weight.data.copy_(other.weight.data)
-        if other.bias is not None:
-            result.bias.data.copy_(other.bias.data)
-        return result
+        return _copy_params(other, QuantConv2dWLog(other.in_channels, other.out_channels, other.kernel_size, stride=other.stride,
+                                                  padding=other.padding, dilation=other.dilation, groups=other.groups,
+                                                  bias=other.bias is not None, gamma=gamma, init=init, size=size, kapa=kapa,
+                                                  beta=beta))
 
     def __init__(self, in_channels, out_channels, kernel_size, gamma=2, init=0.25, size=5, kapa=0, beta=0, stride=1, padding=1,
                  dilation=1, groups=1, bias=True):
         self.gamma, self.init, self.size = gamma, init, size
         torch.nn.Conv2d.__init__(self, in_channels, out_channels, kernel_size, stride=stride, padding=padding, dilation=dilation,
                                  groups=groups, bias=bias)
-        self._init_coefs(kapa, beta)
+        self._init_coefs(kapa=kapa, beta=beta)
         self.weight_op = WQR_connect.QuantWeightWExp(gamma=self.gamma, init=self.init, size=self.size)
-
-    def _range(self):
-        b = self.init * self.gamma ** (self.size - 1)
-        return -b, b
 
     def set_beta(self, beta):
         """Writes ``alpha``, as upstream (WQR_layers.py QuantConv2dWLog.set_beta)."""

@@ -28,13 +28,43 @@ def _real_dev(input, weight) -> bool:
     return input.is_cuda and input.dtype == torch.float32 and weight.dtype == torch.float32 and input.numel() > 0
 
 
+def _copy_params(other, layer):
+    """``layer`` with ``other``'s weight and bias copied in: the loss-aware ``convert``s keep the trained values."""
+    layer.weight.data.copy_(other.weight.data)
+    if other.bias is not None:
+        layer.bias.data.copy_(other.bias.data)
+    return layer
+
+
 class LossQuantMixin:
-    """Shared plumbing: level table, cached eval projection, the device routes."""
+    """Shared plumbing of the Elastic and WQR layers: level table and range, coefficient buffers, clamp, cached eval projection,
+    the device routes."""
 
     def _levels(self):
         if hasattr(self, "gamma"):
             return EQ.exp_levels(self.gamma, self.init, self.size)
         return EQ.lin_levels(self.top, self.bottom, self.size)
+
+    def _range(self):
+        """(low, high) of the level set.  The Log set spans +-init*gamma^(size-1) (upstream's Log convs read the missing
+        ``bottom`` / ``top``: fixed)."""
+        if hasattr(self, "gamma"):
+            b = self.init * self.gamma ** (self.size - 1)
+            return -b, b
+        return self.bottom, self.top
+
+    def clamp(self):
+        lo, hi = self._range()
+        self.weight.data.clamp_(lo, hi)
+        if self.bias is not None:
+            self.bias.data.clamp_(lo, hi)
+
+    def _init_coefs(self, **coefs):
+        for name, value in coefs.items():
+            self.register_buffer(name, torch.Tensor([value]))
+
+    def _set_coef(self, name, value):
+        setattr(self, name, torch.Tensor([value]).to(self.weight.device))
 
     def _project(self, w):
         return EQ.project(w, self._levels())
@@ -54,22 +84,16 @@ class LossQuantMixin:
     def reset_quant_cache(self):
         self._qt_proj = None
 
-    def _no_grad_for(self, input) -> bool:
-        return not (torch.is_grad_enabled() and (input.requires_grad or self.weight.requires_grad
-                                                 or (self.bias is not None and self.bias.requires_grad)))
-
     def _eval_linear(self, input):
         if not _real_dev(input, self.weight):
             _fused.note_library_path(input, "loss-aware linear (eval): a non-fp32 dtype")
             return torch.nn.functional.linear(input, self._project(self.weight), self.bias)
         cache = self._proj_cache()
         wq = cache["wq"]
-        if self._no_grad_for(input):
-            if _exact_in_bf16(self._levels()):
-                if "bf16x3" not in cache:
-                    cache["bf16x3"] = _fused.ops.weight_bf16x3(wq, "raw", terms=3)
-                return _fused.ops.float_linear(input, wq, "raw", self.bias, weight_triples=cache["bf16x3"], terms=3)
-            return _fused.RealLinearFn.apply(input, wq, self.bias)
+        if not _fused.autograd_records(input, self.weight, self.bias) and _exact_in_bf16(self._levels()):
+            if "bf16x3" not in cache:
+                cache["bf16x3"] = _fused.ops.weight_bf16x3(wq, "raw", terms=3)
+            return _fused.ops.float_linear(input, wq, "raw", self.bias, weight_triples=cache["bf16x3"], terms=3)
         return _fused.RealLinearFn.apply(input, wq, self.bias)
 
     def _conv_args(self):
@@ -90,7 +114,7 @@ class LossQuantMixin:
             return self._conv(input, self._project(self.weight))
         cache = self._proj_cache()
         wq = cache["wq"]
-        if self._no_grad_for(input) and _exact_in_bf16(self._levels()):
+        if not _fused.autograd_records(input, self.weight, self.bias) and _exact_in_bf16(self._levels()):
             if "conv_bf16x3" not in cache:
                 cache["conv_bf16x3"] = _fused.ops.pack_conv_weight_bf16x3(wq, "raw", terms=3)
             N, C, H, W = input.shape
@@ -98,14 +122,29 @@ class LossQuantMixin:
             y2 = _fused.ops.float_conv2d(input, wq, "raw", self.bias, self.stride, self.padding, self.dilation,
                                          weight_triples=cache["conv_bf16x3"], terms=3)
             Ho, Wo = _fused.ops.conv_out_hw(H, W, kh, kw, self.stride, self.padding, self.dilation)
-            y = y2.view(N, Ho, Wo, wq.shape[0]).permute(0, 3, 1, 2)
-            if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
-                y = y.contiguous()
-            return y
+            return _fused.nchw_result(y2, input, N, Ho, Wo, wq.shape[0])
         return self._conv(input, wq)
 
-    def _set_coef(self, name, value):
-        setattr(self, name, torch.Tensor([value]).to(self.weight.device))
+
+class _LossQuantLinear(LossQuantMixin, torch.nn.Module, QLayer):
+    """Parameter setup of the loss-aware Linear layers (Elastic and WQR)."""
+
+    def _init_linear(self, in_features, out_features, bias, **coefs):
+        self.in_features, self.out_features = in_features, out_features
+        self._init_coefs(**coefs)
+        self.weight = torch.nn.Parameter(torch.empty(out_features, in_features))
+        if bias:
+            self.bias = torch.nn.Parameter(torch.empty(out_features))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        """Weight uniform over the level range, bias 0."""
+        lo, hi = self._range()
+        self.weight.data.uniform_(lo, hi)
+        if self.bias is not None:
+            self.bias.data.zero_()
 
 
 class _ElasticTrain:
@@ -114,49 +153,14 @@ class _ElasticTrain:
         self.training = mode
         return self
 
-
-class LinearQuantLin(_ElasticTrain, LossQuantMixin, torch.nn.Module, QLayer):
-    @staticmethod
-    def convert(other, bottom=-1, top=1, size=5, alpha=0, beta=0):
-        if not isinstance(other, torch.nn.Linear):
-            raise TypeError("Expected a torch.nn.Linear ! Receive:  {}".format(other.__class__))
-        result = LinearQuantLin(other.in_features, other.out_features, other.bias is not None, bottom=bottom, top=top, size=size,
-                                alpha=alpha, beta=beta)
-        result.weight.data.copy_(other.weight.data)
-        if other.bias is not None:
-            result.bias.data.copy_(other.bias.data)
-        return result
-
-    def __init__(self, in_features, out_features, bias=True, bottom=-1, top=1, size=5, alpha=0, beta=0):
-        torch.nn.Module.__init__(self)
-        self.in_features, self.out_features = in_features, out_features
-        self.bottom, self.top, self.size = bottom, top, size
-        self.register_buffer("alpha", torch.Tensor([alpha]))
-        self.register_buffer("beta", torch.Tensor([beta]))
-        self.weight = torch.nn.Parameter(torch.empty(out_features, in_features))
-        if bias:
-            self.bias = torch.nn.Parameter(torch.empty(out_features))
-        else:
-            self.register_parameter("bias", None)
-        self.reset_parameters()
-        self.linear_op = EQ.QuantLinDense(size=size, bottom=bottom, top=top)
-
-    def reset_parameters(self):
-        self.weight.data.uniform_(self.bottom, self.top)
-        if self.bias is not None:
-            self.bias.data.zero_()
-
-    def clamp(self):
-        self.weight.data.clamp_(self.bottom, self.top)
-        if self.bias is not None:
-            self.bias.data.clamp_(self.bottom, self.top)
-
     def set_alpha(self, alpha):
         self._set_coef("alpha", alpha)
 
     def set_beta(self, beta):
         self._set_coef("beta", beta)
 
+
+class _ElasticLinear(_ElasticTrain, _LossQuantLinear):
     def forward(self, input):
         lazy.note_inference_call(self, input)
         input = lazy.resolve(input)
@@ -165,142 +169,85 @@ class LinearQuantLin(_ElasticTrain, LossQuantMixin, torch.nn.Module, QLayer):
         return self._eval_linear(input)
 
 
-class LinearQuantLog(_ElasticTrain, LossQuantMixin, torch.nn.Module, QLayer):
+class _ElasticConv(_ElasticTrain, LossQuantMixin, torch.nn.Conv2d, QLayer):
+    def forward(self, input):
+        lazy.note_inference_call(self, input)
+        input = lazy.resolve(input)
+        if self.training:
+            return self._conv(input, self.weight_op.apply(self.weight, self.alpha, self.beta))
+        return self._eval_conv(input)
+
+
+class LinearQuantLin(_ElasticLinear):
+    @staticmethod
+    def convert(other, bottom=-1, top=1, size=5, alpha=0, beta=0):
+        if not isinstance(other, torch.nn.Linear):
+            raise TypeError("Expected a torch.nn.Linear ! Receive:  {}".format(other.__class__))
+        return _copy_params(other, LinearQuantLin(other.in_features, other.out_features, other.bias is not None, bottom=bottom,
+                                                 top=top, size=size, alpha=alpha, beta=beta))
+
+    def __init__(self, in_features, out_features, bias=True, bottom=-1, top=1, size=5, alpha=0, beta=0):
+        torch.nn.Module.__init__(self)
+        self.bottom, self.top, self.size = bottom, top, size
+        self._init_linear(in_features, out_features, bias, alpha=alpha, beta=beta)
+        self.linear_op = EQ.QuantLinDense(size=size, bottom=bottom, top=top)
+
+
+class LinearQuantLog(_ElasticLinear):
     @staticmethod
     def convert(other, gamma=2, init=0.25, size=5, alpha=0, beta=0):
         if not isinstance(other, torch.nn.Linear):
             raise TypeError("Expected a torch.nn.Linear ! Receive:  {}".format(other.__class__))
-        result = LinearQuantLog(other.in_features, other.out_features, other.bias is not None, gamma=gamma, init=init, size=size,
-                                alpha=alpha, beta=beta)
-        result.weight.data.copy_(other.weight.data)
-        if other.bias is not None:
-            result.bias.data.copy_(other.bias.data)
-        return result
+        return _copy_params(other, LinearQuantLog(other.in_features, other.out_features, other.bias is not None, gamma=gamma,
+                                                 init=init, size=size, alpha=alpha, beta=beta))
 
     def __init__(self, in_features, out_features, bias=True, gamma=2, init=0.25, size=5, alpha=0, beta=0):
         torch.nn.Module.__init__(self)
-        self.in_features, self.out_features = in_features, out_features
         self.gamma, self.init, self.size = gamma, init, size
-        self.register_buffer("alpha", torch.Tensor([alpha]))
-        self.register_buffer("beta", torch.Tensor([beta]))
-        self.weight = torch.nn.Parameter(torch.empty(out_features, in_features))
-        if bias:
-            self.bias = torch.nn.Parameter(torch.empty(out_features))
-        else:
-            self.register_parameter("bias", None)
-        self.reset_parameters()
+        self._init_linear(in_features, out_features, bias, alpha=alpha, beta=beta)
         self.linear_op = EQ.QuantLogDense(gamma=gamma, init=init, size=size)
 
-    def _bound(self):
-        return self.init * self.gamma ** (self.size - 1)
 
-    def reset_parameters(self):
-        self.weight.data.uniform_(-self._bound(), self._bound())
-        if self.bias is not None:
-            self.bias.data.zero_()
-
-    def clamp(self):
-        self.weight.data.clamp_(-self._bound(), self._bound())
-        if self.bias is not None:
-            self.bias.data.clamp_(-self._bound(), self._bound())
-
-    def set_alpha(self, alpha):
-        self._set_coef("alpha", alpha)
-
-    def set_beta(self, beta):
-        self._set_coef("beta", beta)
-
-    def forward(self, input):
-        lazy.note_inference_call(self, input)
-        input = lazy.resolve(input)
-        if self.training:
-            return self.linear_op.apply(input, self.weight, self.bias, self.alpha, self.beta)
-        return self._eval_linear(input)
-
-
-class QuantConv2dLin(_ElasticTrain, LossQuantMixin, torch.nn.Conv2d, QLayer):
+class QuantConv2dLin(_ElasticConv):
     @staticmethod
     def convert(other, bottom=-1, top=1, size=5, alpha=0, beta=0):
         if not isinstance(other, torch.nn.Conv2d):
             raise TypeError("Expected a torch.nn.Conv2d ! Receive:  {}".format(other.__class__))
-        result = QuantConv2dLin(other.in_channels, other.out_channels, other.kernel_size, stride=other.stride, padding=other.padding,
-                                dilation=other.dilation, groups=other.groups, bias=other.bias is not None, bottom=bottom, top=top,
-                                size=size, alpha=alpha, beta=beta)
-        result.weight.data.copy_(other.weight.data)
-        if other.bias is not None:
-            result.bias.data.copy_(other.bias.data)
-        return result
+        return _copy_params(other, QuantConv2dLin(other.in_channels, other.out_channels, other.kernel_size, stride=other.stride,
+                                                 padding=other.padding, dilation=other.dilation, groups=other.groups,
+                                                 bias=other.bias is not None, bottom=bottom, top=top, size=size, alpha=alpha,
+                                                 beta=beta))
 
     def __init__(self, in_channels, out_channels, kernel_size, bottom=-1, top=1, size=5, alpha=0, beta=0, stride=1, padding=1,
                  dilation=1, groups=1, bias=True):
         self.top, self.bottom, self.size = top, bottom, size
         torch.nn.Conv2d.__init__(self, in_channels, out_channels, kernel_size, stride=stride, padding=padding, dilation=dilation,
                                  groups=groups, bias=bias)
-        self.register_buffer("alpha", torch.Tensor([alpha]))
-        self.register_buffer("beta", torch.Tensor([beta]))
+        self._init_coefs(alpha=alpha, beta=beta)
         self.weight_op = EQ.QuantWeightLin(self.top, self.bottom, self.size)
 
-    def clamp(self):
-        self.weight.data.clamp_(self.bottom, self.top)
-        if self.bias is not None:
-            self.bias.data.clamp_(self.bottom, self.top)
 
-    def set_alpha(self, alpha):
-        self._set_coef("alpha", alpha)
-
-    def set_beta(self, beta):
-        self._set_coef("beta", beta)
-
-    def forward(self, input):
-        lazy.note_inference_call(self, input)
-        input = lazy.resolve(input)
-        if self.training:
-            return self._conv(input, self.weight_op.apply(self.weight, self.alpha, self.beta))
-        return self._eval_conv(input)
-
-
-class QuantConv2dLog(_ElasticTrain, LossQuantMixin, torch.nn.Conv2d, QLayer):
+class QuantConv2dLog(_ElasticConv):
     @staticmethod
     def convert(other, gamma=2, init=0.25, size=5, alpha=0, beta=0):
         if not isinstance(other, torch.nn.Conv2d):
             raise TypeError("Expected a torch.nn.Conv2d ! Receive:  {}".format(other.__class__))
-        result = QuantConv2dLog(other.in_channels, other.out_channels, other.kernel_size, stride=other.stride, padding=other.padding,
-                                dilation=other.dilation, groups=other.groups, bias=other.bias is not None, gamma=gamma, init=init,
-                                size=size, alpha=alpha, beta=beta)
-        result.weight.data.copy_(other.weight.data)
-        if other.bias is not None:
-            result.bias.data.copy_(other.bias.data)
-        return result
+        return _copy_params(other, QuantConv2dLog(other.in_channels, other.out_channels, other.kernel_size, stride=other.stride,
+                                                 padding=other.padding, dilation=other.dilation, groups=other.groups,
+                                                 bias=other.bias is not None, gamma=gamma, init=init, size=size, alpha=alpha,
+                                                 beta=beta))
 
     def __init__(self, in_channels, out_channels, kernel_size, gamma=2, init=0.25, size=5, alpha=0, beta=0, stride=1, padding=1,
                  dilation=1, groups=1, bias=True):
         torch.nn.Conv2d.__init__(self, in_channels, out_channels, kernel_size, stride=stride, padding=padding, dilation=dilation,
                                  groups=groups, bias=bias)
         self.gamma, self.init, self.size = gamma, init, size
-        self.register_buffer("alpha", torch.Tensor([alpha]))
-        self.register_buffer("beta", torch.Tensor([beta]))
+        self._init_coefs(alpha=alpha, beta=beta)
         self.weight_op = EQ.QuantWeightExp(gamma=self.gamma, init=self.init, size=self.size)
-
-    def clamp(self):
-        """Fixed: upstream reads the missing ``bottom`` / ``top``; the Log set spans +-init*gamma^(size-1)."""
-        bound = self.init * self.gamma ** (self.size - 1)
-        self.weight.data.clamp_(-bound, bound)
-        if self.bias is not None:
-            self.bias.data.clamp_(-bound, bound)
-
-    def set_alpha(self, alpha):
-        self._set_coef("alpha", alpha)
 
     def set_beta(self, beta):
         """Writes ``alpha``, as upstream (elastic_layers.py QuantConv2dLog.set_beta)."""
         self._set_coef("alpha", beta)
-
-    def forward(self, input):
-        lazy.note_inference_call(self, input)
-        input = lazy.resolve(input)
-        if self.training:
-            return self._conv(input, self.weight_op.apply(self.weight, self.alpha, self.beta))
-        return self._eval_conv(input)
 
 
 _ELASTIC = (LinearQuantLin, LinearQuantLog, QuantConv2dLin, QuantConv2dLog)

@@ -24,8 +24,7 @@ def _exact_in_bf16(dtype, bit_width):
 def _autograd_on_device(layer, input) -> bool:
     """A device fp32 input of a device fp32 layer with autograd recording: the training routes of functions._fused."""
     return (input.is_cuda and input.dtype == torch.float32 and input.numel() > 0 and layer.weight.is_cuda
-            and layer.weight.dtype == torch.float32 and torch.is_grad_enabled()
-            and (input.requires_grad or layer.weight.requires_grad))
+            and layer.weight.dtype == torch.float32 and _fused.autograd_records(input, layer.weight))
 
 
 class _WeightInit:
@@ -69,7 +68,7 @@ class LinearQuant(_WeightInit, EvalSwapMixin, torch.nn.Linear, QLayer):
             return _fused.RealLinearFn.apply(input, self.weight_op.forward(self.weight), self.bias)
         wq = self.weight_op.forward(self.weight)
         if (input.is_cuda and input.dtype == torch.float32 and input.numel() > 0 and _exact_in_bf16(self.qdtype, self.bit_width)
-                and not (torch.is_grad_enabled() and (input.requires_grad or self.weight.requires_grad))):
+                and not _fused.autograd_records(input, self.weight)):
             # Lin / Log levels are exact in bf16 (fp32's exponent range), not necessarily in fp16: the exact three-term route
             wt = None if self.training else self._eval_planes(
                 lambda w2: _fused.ops.weight_bf16x3(w2, "raw", terms=3), key="bf16x3_raw")
@@ -111,8 +110,7 @@ class QuantConv2d(_WeightInit, EvalSwapMixin, torch.nn.Conv2d, QLayer):
         wq = self.weight_op.forward(self.weight) if self.training else self.weight
         if (input.is_cuda and input.dtype == torch.float32 and input.numel() > 0 and input.dim() == 4
                 and self.groups == 1 and self.padding_mode == "zeros" and not isinstance(self.padding, str)
-                and _exact_in_bf16(self.qdtype, self.bit_width)
-                and not (torch.is_grad_enabled() and (input.requires_grad or self.weight.requires_grad))):
+                and _exact_in_bf16(self.qdtype, self.bit_width) and not _fused.autograd_records(input, self.weight)):
             wt = None if self.training else self._eval_planes(
                 lambda _w2: _fused.ops.pack_conv_weight_bf16x3(self.weight.detach(), "raw", terms=3), key="conv_bf16x3_raw")
             N, C, H, W = input.shape
@@ -121,9 +119,6 @@ class QuantConv2d(_WeightInit, EvalSwapMixin, torch.nn.Conv2d, QLayer):
             y2 = _fused.ops.float_conv2d(input, wq.detach(), "raw", self.bias, self.stride, self.padding, self.dilation,
                                          weight_triples=wt, terms=3)
             Ho, Wo = _fused.ops.conv_out_hw(H, W, kh, kw, self.stride, self.padding, self.dilation)
-            y = y2.view(N, Ho, Wo, self.weight.shape[0]).permute(0, 3, 1, 2)
-            if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
-                y = y.contiguous()
-            return y
+            return _fused.nchw_result(y2, input, N, Ho, Wo, self.weight.shape[0])
         _fused.note_library_path(input, "Lin/Log conv: groups, padding mode, a non-fp32 dtype, or levels beyond bf16 without autograd")
         return torch.nn.functional.conv2d(input, wq, self.bias, self.stride, self.padding, self.dilation, self.groups)

@@ -113,8 +113,5 @@ class XNORConv2d(EvalSwapMixin, torch.nn.Conv2d, QLayer):
                 ops = _fused.ops
                 N_, _, H, W = input.shape
                 Ho, Wo = ops.conv_out_hw(H, W, self.kernel_size[0], self.kernel_size[1], self.stride, self.padding, self.dilation)
-                y = out[0].view(N_, Ho, Wo, self.out_channels).permute(0, 3, 1, 2)
-                if input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
-                    y = y.contiguous()
-                return y
+                return _fused.nchw_result(out[0], input, N_, Ho, Wo, self.out_channels)
         return self.conv_op.apply(input, self.weight, self.bias)
