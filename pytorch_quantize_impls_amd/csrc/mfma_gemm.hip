@@ -134,53 +134,86 @@ struct NibSign0 {  // torch.sign: 0 (and NaN) -> 0x0 — the XNOR-Net weight ima
     __device__ __forceinline__ static uint32_t nib(float x) { return x > 0.0f ? 0x2u : (x < 0.0f ? 0xAu : 0x0u); }
 };
 
-// One work item = one float4 slot of the padded row (ldp words = ldp*2 slots); two adjacent lanes
-// form one output word.  Slots past K/4 produce zero nibbles, so the pad-is-zero invariant holds.
 template <class Enc>
-__global__ __launch_bounds__(256) void nib_pack_vec_kernel(const float* __restrict__ x, int64_t ldx,
-                                                           uint32_t* __restrict__ out, int64_t ldp,
-                                                           int64_t rows, int64_t K) {
-    const int64_t slots_per_row = ldp * 2;
-    const int64_t total = rows * slots_per_row;  // even
-    const int64_t k4 = K / 4;
-    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < total;
-         s += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t row = s / slots_per_row, slot = s - row * slots_per_row;
-        uint32_t h = 0;
-        if (slot < k4) {
-            const float4 v = *reinterpret_cast<const float4*>(x + row * ldx + slot * 4);
-            h = Enc::nib(v.x) | (Enc::nib(v.y) << 4) | (Enc::nib(v.z) << 8) | (Enc::nib(v.w) << 12);
+__device__ __forceinline__ uint32_t nib_half(const float4& v) {   // 4 elements -> 16 bits
+    return Enc::nib(v.x) | (Enc::nib(v.y) << 4) | (Enc::nib(v.z) << 8) | (Enc::nib(v.w) << 12);
+}
+
+// Write-through (sc1) dword store: the nibble plane is read by the GEMM that follows, through the L2s / MALL, and a kernel
+// that leaves its output dirty in the L2s pays the write-back at its end-of-kernel boundary (the GEMM epilogue's stores,
+// mfma_gemm_kernel.h).  s_nop: the store reads its data register late and the hazard recogniser does not look inside asm.
+__device__ __forceinline__ void store_wt(uint32_t* p, uint32_t v) {
+    asm volatile("global_store_dword %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(v) : "memory");
+}
+
+// fp32 rows -> nibble plane, the work of one wave.  Unit = 256 consecutive float4 slots of one padded row (ldp words =
+// 2 ldp slots); lane l takes slots 64 j + l of the unit, j = 0..3: four independent dwordx4 loads per lane in flight, each
+// load instruction one contiguous KiB.  The 16-bit halves of lanes (2i, 2i + 1) form one word (one DPP swap per pair of
+// groups): even lanes store the words of groups 0 / 2, odd lanes those of groups 1 / 3, so each store instruction has all
+// lanes active on 256 contiguous bytes.  Slots past K/4 produce zero nibbles (the pad-is-zero invariant).  Units are walked
+// wave-strided (gw, gw + nw, ...) with the (row, unit) position advanced by a precomputed step: 32-bit arithmetic, no
+// division in the loop.  Host contract (pack_fits_32bit): rows, 2 ldp, K/4 < 2^30; K >= 4.
+template <class Enc>
+__device__ __forceinline__ void nib_pack_rows(const float* __restrict__ x, int64_t ldx, uint32_t* __restrict__ out,
+                                              int64_t ldp, int rows, int k4, int gw, int nw) {
+    const int lane = threadIdx.x & 63;
+    const bool odd = lane & 1;
+    const int spr = (int)ldp * 2, upr = (spr + 255) >> 8;
+    int row = gw / upr, seg = gw - row * upr;
+    const int srow = nw / upr, sseg = nw - srow * upr;
+    while (row < rows) {
+        const float* xr = x + (int64_t)row * ldx;
+        uint32_t* orow = out + (int64_t)row * ldp;
+        const int s0 = seg * 256 + lane;
+        // unconditional loads (slot clamped into the row's K), masked after: a guarded load becomes a branch around a load
+        // and its wait, i.e. one load in flight
+        float4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const float4*>(xr + min(s0 + 64 * j, k4 - 1) * 4);
+        uint32_t h[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) h[j] = nib_half<Enc>(v[j]) & (s0 + 64 * j < k4 ? 0xFFFFu : 0u);
+        uint32_t word[2];
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const uint32_t send = odd ? h[2 * p] : h[2 * p + 1];
+            const uint32_t recv = (uint32_t)__builtin_amdgcn_mov_dpp((int)send, 0xB1, 0xF, 0xF, false);  // quad_perm [1,0,3,2]
+            word[p] = odd ? (recv | (h[2 * p + 1] << 16)) : (h[2 * p] | (recv << 16));
         }
-        const uint32_t other = __shfl_xor(h, 1);
-        if ((threadIdx.x & 1) == 0) out[row * ldp + (slot >> 1)] = h | (other << 16);
+        // both stores after the last load is consumed: the compiler does not count the asm stores, so a store issued
+        // between the loads would turn its later vmcnt waits into waits for the store's completion
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int ws = seg * 256 + 128 * p + (odd ? 63 + lane : lane);   // first slot of the word this lane stores
+            if (ws < spr) store_wt(orow + (ws >> 1), word[p]);
+        }
+        seg += sseg;
+        row += srow;
+        if (seg >= upr) { seg -= upr; ++row; }
     }
 }
 
+template <class Enc>
+__global__ __launch_bounds__(256) void nib_pack_vec_kernel(const float* __restrict__ x, int64_t ldx,
+                                                           uint32_t* __restrict__ out, int64_t ldp, int rows, int k4) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    nib_pack_rows<Enc>(x, ldx, out, ldp, rows, k4, blockIdx.x * 4 + wave, gridDim.x * 4);
+}
+
 // Both operands of one LinearBin / LinearTer forward in ONE launch (activation: safeSign, weight: EncW): saves a
-// kernel boundary and one ramp / tail of a ~12 us HBM-bound kernel.  Same work item as nib_pack_vec_kernel.
+// kernel boundary and one ramp / tail of a ~12 us HBM-bound kernel.  Workgroups [0, ga) pack the activation, the rest
+// the weight (ga: the activation's share of the units).
 template <class EncW>
 __global__ __launch_bounds__(256) void nib_pack_pair_kernel(const float* __restrict__ xa, int64_t lda,
-                                                            uint32_t* __restrict__ oa, int64_t ldpa, int64_t rowsa,
+                                                            uint32_t* __restrict__ oa, int64_t ldpa, int rowsa,
                                                             const float* __restrict__ xb, int64_t ldb,
-                                                            uint32_t* __restrict__ ob, int64_t ldpb, int64_t rowsb,
-                                                            int64_t K) {
-    const int64_t ta = rowsa * ldpa * 2, total = ta + rowsb * ldpb * 2;   // both even
-    const int64_t k4 = K / 4;
-    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < total;
-         s += (int64_t)gridDim.x * blockDim.x) {
-        const bool second = s >= ta;
-        const int64_t t = second ? s - ta : s;
-        const int64_t spr = (second ? ldpb : ldpa) * 2;
-        const int64_t row = t / spr, slot = t - row * spr;
-        uint32_t h = 0;
-        if (slot < k4) {
-            const float4 v = *reinterpret_cast<const float4*>((second ? xb + row * ldb : xa + row * lda) + slot * 4);
-            h = second ? (EncW::nib(v.x) | (EncW::nib(v.y) << 4) | (EncW::nib(v.z) << 8) | (EncW::nib(v.w) << 12))
-                       : (NibSign::nib(v.x) | (NibSign::nib(v.y) << 4) | (NibSign::nib(v.z) << 8) | (NibSign::nib(v.w) << 12));
-        }
-        const uint32_t other = __shfl_xor(h, 1);
-        if ((threadIdx.x & 1) == 0) (second ? ob + row * ldpb : oa + row * ldpa)[slot >> 1] = h | (other << 16);
-    }
+                                                            uint32_t* __restrict__ ob, int64_t ldpb, int rowsb,
+                                                            int k4, int ga) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int b = blockIdx.x;
+    if (b < ga) nib_pack_rows<NibSign>(xa, lda, oa, ldpa, rowsa, k4, b * 4 + wave, ga * 4);
+    else nib_pack_rows<EncW>(xb, ldb, ob, ldpb, rowsb, k4, (b - ga) * 4 + wave, ((int)gridDim.x - ga) * 4);
 }
 
 // Generic path (any K / alignment): one thread per output word, scalar loads.
@@ -271,6 +304,10 @@ __global__ __launch_bounds__(256) void bits_to_nib_pad_kernel(const uint32_t* __
     }
 }
 
+// nib_pack_rows' 32-bit position arithmetic: row + units-per-wave step and the slot index stay below 2^31
+bool pack_fits_32bit(int64_t rows, int64_t ldp) { return rows < (1ll << 30) && ldp < (1ll << 29); }
+int64_t pack_units(int64_t rows, int64_t ldp) { return rows * ((ldp * 2 + 255) / 256); }   // one unit = one wave's work
+
 template <class Enc>
 int launch_nib_pack(const float* x, int64_t ldx, uint32_t* out, int64_t ldp, int64_t rows, int64_t K,
                     qt_stream_t stream) {
@@ -280,11 +317,11 @@ int launch_nib_pack(const float* x, int64_t ldx, uint32_t* out, int64_t ldp, int
     const int64_t kw = (K + 7) / 8;
     if (ldp < kw || (ldp & 3) != 0 || !qt_aligned16(out)) return QT_ERR_ALIGNMENT;
     if (ldp == 0) return QT_OK;
-    const bool vec = (K % 4 == 0) && (ldx % 4 == 0) && qt_aligned16(x);
+    const bool vec = K > 0 && (K % 4 == 0) && (ldx % 4 == 0) && qt_aligned16(x) && pack_fits_32bit(rows, ldp);
     if (vec) {
-        const int grid = qt_stream_grid((rows * ldp * 2 + 255) / 256);
+        const int grid = qt_stream_grid((pack_units(rows, ldp) + 3) / 4);
         hipLaunchKernelGGL((nib_pack_vec_kernel<Enc>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x,
-                           ldx, out, ldp, rows, K);
+                           ldx, out, ldp, (int)rows, (int)(K / 4));
     } else {
         const int grid = qt_stream_grid((rows * ldp + 255) / 256);
         hipLaunchKernelGGL((nib_pack_scalar_kernel<Enc>), dim3(grid), dim3(256), 0, (hipStream_t)stream,
@@ -335,13 +372,22 @@ int qt_pack_pair_nib_f32(const float* x, int64_t ldx, uint32_t* x_plane, int64_t
     const int64_t kw = (K + 7) / 8;
     if (ldxp < kw || ldwp < kw || (ldxp & 3) || (ldwp & 3) || !qt_aligned16(x_plane) || !qt_aligned16(w_plane))
         return QT_ERR_ALIGNMENT;
-    const int grid = qt_stream_grid(((rows_x * ldxp + rows_w * ldwp) * 2 + 255) / 256);
+    if (!pack_fits_32bit(rows_x, ldxp) || !pack_fits_32bit(rows_w, ldwp)) {
+        const int rc = launch_nib_pack<NibSign>(x, ldx, x_plane, ldxp, rows_x, K, stream);
+        if (rc != QT_OK) return rc;
+        return w_ternary ? launch_nib_pack<NibTernary>(w, ldw, w_plane, ldwp, rows_w, K, stream)
+                         : launch_nib_pack<NibSign>(w, ldw, w_plane, ldwp, rows_w, K, stream);
+    }
+    // workgroups (4 waves each) split between the operands in proportion to their units, at least one each
+    const int64_t ua = pack_units(rows_x, ldxp), ub = pack_units(rows_w, ldwp);
+    const int grid = qt_stream_grid((ua + 3) / 4 + (ub + 3) / 4);   // >= 2: both operands have rows and K > 0
+    const int ga = (int)std::min<int64_t>(std::max<int64_t>(1, (grid * ua + (ua + ub) / 2) / (ua + ub)), grid - 1);
     if (w_ternary)
         hipLaunchKernelGGL((nib_pack_pair_kernel<NibTernary>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx,
-                           x_plane, ldxp, rows_x, w, ldw, w_plane, ldwp, rows_w, K);
+                           x_plane, ldxp, (int)rows_x, w, ldw, w_plane, ldwp, (int)rows_w, (int)(K / 4), ga);
     else
         hipLaunchKernelGGL((nib_pack_pair_kernel<NibSign>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx,
-                           x_plane, ldxp, rows_x, w, ldw, w_plane, ldwp, rows_w, K);
+                           x_plane, ldxp, (int)rows_x, w, ldw, w_plane, ldwp, (int)rows_w, (int)(K / 4), ga);
     return qt_check_launch();
 }
 
