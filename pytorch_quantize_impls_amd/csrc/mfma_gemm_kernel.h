@@ -165,7 +165,9 @@ struct ElemBf16 {
         __builtin_memcpy(&bv, &b, 16);
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, c, 0, 0, 0);
     }
-    __device__ __forceinline__ static float out(float v, float scale, float bias) { return v + bias; }
+    // the conv's output scale (1 / n of DoReFa levels, E = mean|W|) applies here as in ElemF16: the implicit conv returns this
+    // result as it is.  scale == 1 leaves v + bias unchanged.
+    __device__ __forceinline__ static float out(float v, float scale, float bias) { return v * scale + bias; }
 };
 
 // fp16 operands (round 3, "pair planes"): the same idea with TWO terms.  An fp32 activation divided by a power-of-two

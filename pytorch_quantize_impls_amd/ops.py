@@ -2751,6 +2751,41 @@ def wgrad_gemm_applicable(x_shape, g_shape, kernel_hw, stride, dilation) -> bool
             and int(x_shape[1]) >= 128 and int(g_shape[1]) >= 128)
 
 
+def wgrad_chunk_images(N: int, fits) -> int:
+    """Images per batch chunk of a weight-gradient route: the batch halved (rounding up) until ``fits(nc)`` holds for the route's
+    launch plan, or 1.  The last chunk holds the remaining N % nc images when nc does not divide N."""
+    nc = int(N)
+    while nc > 1 and not fits(nc):
+        nc = (nc + 1) // 2
+    return nc
+
+
+def wgrad_gemm_plan(nc: int, Cout: int, Cin: int, H: int, W: int, kh: int, kw: int, ph: int, pw: int):
+    """Launch plan of ``conv2d_grad_weight_gemm`` for ``nc`` images of a stride-1 conv: (fits the byte budget?, K slice length,
+    lda, ldb, K slices).  The slice count does not depend on ``nc``, so the plan is monotone in the chunk size.  Host logic
+    only (the tests take the batch chunks of the route from it)."""
+    Ho = H + 2 * ph - kh + 1
+    Wq = _round_up(W + 2 * pw, 8)
+    Hp = H + 2 * ph
+    M, taps = 3 * Cout, kh * kw
+    ldc = _round_up(Cin, 4)
+    tn = 256
+    for c in (192, 128, 64):                                  # the GEMM's own tile-width rule (pick_tile_n)
+        if _round_up(Cin, c) < _round_up(Cin, tn):
+            tn = c
+    tm = 384 if (tn == 192 and _round_up(M, 384) <= _round_up(M, 256)) else 256
+    tiles = (_round_up(M, tm) // tm) * (_round_up(Cin, tn) // tn)
+    nslice = max(1, min(64, -(-WGRAD_WORKGROUPS // (tiles * taps))))
+    ktot = Ho * nc * Wq
+    ks = _round_up(-(-ktot // nslice), 32)
+    kpad = ks * nslice
+    lda = _round_up(kpad, 64)
+    ldb = _round_up(max(Hp * nc * Wq, (kh - 1) * nc * Wq + kpad), 64)
+    nbytes = M * lda * 2 + kw * Cin * ldb * 2 + taps * nslice * M * ldc * 4
+    ok = M * lda * 2 < (1 << 31) and Cin * ldb * 2 < (1 << 31) and nbytes <= WGRAD_GEMM_BYTES
+    return ok, ks, lda, ldb, nslice
+
+
 def conv2d_grad_weight_gemm(x_pm1: torch.Tensor, grad_output: torch.Tensor, kernel_hw, padding,
                             weight: Optional[torch.Tensor] = None, ste_threshold: float = STE_THRESHOLD,
                             x_levels: float = 1.0):
@@ -2768,30 +2803,14 @@ def conv2d_grad_weight_gemm(x_pm1: torch.Tensor, grad_output: torch.Tensor, kern
     if N2 != N or Ho != H + 2 * ph - kh + 1 or Wo != W + 2 * pw - kw + 1 or Ho <= 0 or Wo <= 0 or kw > 8 or N == 0:
         return None
     Wq = _round_up(W + 2 * pw, 8)
-    Hp = H + 2 * ph
     M, taps = 3 * Cout, kh * kw
     ldc = _round_up(Cin, 4)
-    tn = 256
-    for c in (192, 128, 64):                                  # the GEMM's own tile-width rule (pick_tile_n)
-        if _round_up(Cin, c) < _round_up(Cin, tn):
-            tn = c
-    tm = 384 if (tn == 192 and _round_up(M, 384) <= _round_up(M, 256)) else 256
-    tiles = (_round_up(M, tm) // tm) * (_round_up(Cin, tn) // tn)
-    nslice = max(1, min(64, -(-WGRAD_WORKGROUPS // (tiles * taps))))
+    nslice = wgrad_gemm_plan(1, Cout, Cin, H, W, kh, kw, ph, pw)[4]
 
     def plan(nc):
-        ktot = Ho * nc * Wq
-        ks = _round_up(-(-ktot // nslice), 32)
-        kpad = ks * nslice
-        lda = _round_up(kpad, 64)
-        ldb = _round_up(max(Hp * nc * Wq, (kh - 1) * nc * Wq + kpad), 64)
-        nbytes = M * lda * 2 + kw * Cin * ldb * 2 + taps * nslice * M * ldc * 4
-        ok = M * lda * 2 < (1 << 31) and Cin * ldb * 2 < (1 << 31) and nbytes <= WGRAD_GEMM_BYTES
-        return ok, ks, lda, ldb
+        return wgrad_gemm_plan(nc, Cout, Cin, H, W, kh, kw, ph, pw)[:4]
 
-    nc = N
-    while nc > 1 and not plan(nc)[0]:
-        nc = (nc + 1) // 2
+    nc = wgrad_chunk_images(N, lambda n: plan(n)[0])
     ok, ks, lda, ldb = plan(nc)
     if not ok:
         return None
@@ -2891,9 +2910,7 @@ def _wgrad_pm_run(grad_output: torch.Tensor, geom, pack_act, weight, ste_thresho
     def plan(nc):
         return wgrad_pm_plan(nc, Cout, Cin, H, W, Ho, kh, kw, ph, pw, slots)
 
-    nc = N
-    while nc > 1 and not plan(nc)[0]:
-        nc = (nc + 1) // 2
+    nc = wgrad_chunk_images(N, lambda n: plan(n)[0])
     ok, nslice, qa, qx = plan(nc)
     if not ok:
         return None
