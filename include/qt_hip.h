@@ -260,6 +260,31 @@ int qt_ternary_pack_f32(const float* x, int64_t ldx, uint32_t* mask_plane, uint3
 int qt_check_pm1_f32(const float* x, int64_t n, int32_t* flag, qt_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Half-precision operands (bf16 / fp16 models: model.bfloat16(), model.half(), torch.autocast).
+ * Every "_h" entry point is the counterpart of the "_f32" one of the same name and takes the element type
+ * as `dtype` right after the data pointer it describes: QT_DTYPE_BF16 or QT_DTYPE_F16 (anything else:
+ * QT_ERR_INVALID_ARG; fp32 data stays on the _f32 entry points).  Pointers are to 2-byte elements, leading
+ * dimensions and counts are in elements, planes have the same formats and contracts as for fp32.
+ * The elements are classified on their BIT PATTERN (no compare that could flush a subnormal):
+ *   safeSign   : -1 iff the sign bit is set and the magnitude bits are in [1, inf]  (-0.0, NaN -> +1; a negative
+ *                subnormal -> -1)
+ *   ternary    : +1 iff x >= 0.5 or NaN, -1 iff x < -0.5, else 0 (0.5 is exact in both formats)
+ *   "is +-1"   : (bits & 0x7fff) == 0x3c00 (fp16) / 0x3f80 (bf16)
+ * Rows with K % 8 == 0, ldx % 8 == 0 and a 16-byte aligned base are read with 16-byte loads (8 elements = 8 plane
+ * bits = one 32-bit word of fp4 nibbles); other rows take the element-wise kernels.
+ * ---------------------------------------------------------------------------------------- */
+#define QT_DTYPE_F32 0
+#define QT_DTYPE_BF16 1
+#define QT_DTYPE_F16 2
+
+/* qt_sign_pack_f32 for half rows; y (may be NULL) receives the +-1 image in the SAME element type as x. */
+int qt_sign_pack_h(const void* x, int dtype, int64_t ldx, uint32_t* sign_plane, int64_t ldp, void* y, int64_t ldy,
+                   int64_t rows, int64_t K, qt_stream_t stream);
+int qt_ternary_pack_h(const void* x, int dtype, int64_t ldx, uint32_t* mask_plane, uint32_t* sign_plane, int64_t ldp,
+                      int64_t rows, int64_t K, qt_stream_t stream);
+int qt_check_pm1_h(const void* x, int dtype, int64_t n, int32_t* flag, qt_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Packed GEMMs.  Y[M,N] (fp32, row stride ldy) = dot over K of the +-1 / {-1,0,+1} values the
  * planes encode, + bias[n] (bias may be NULL).  Replaces torch.nn.functional.linear on
  * quantised operands: layers/binary_layers.py:44,46; layers/terner_layers.py:49,51;
@@ -324,6 +349,23 @@ int qt_nib_gemm_describe(int64_t M, int64_t N, int64_t K, int64_t ldxp, int64_t 
 int qt_nib_gemm(const uint32_t* Xn, int64_t ldxp, const uint32_t* Wn, int64_t ldwp,
                 const float* bias, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K,
                 qt_stream_t stream);
+
+/* Half-precision counterparts (see "Half-precision operands" above). */
+int qt_sign_pack_nib_h(const void* x, int dtype, int64_t ldx, uint32_t* nib_plane, int64_t ldp, int64_t rows, int64_t K,
+                       qt_stream_t stream);
+int qt_ternary_pack_nib_h(const void* x, int dtype, int64_t ldx, uint32_t* nib_plane, int64_t ldp, int64_t rows, int64_t K,
+                          qt_stream_t stream);
+/* x and w have the same element type. */
+int qt_pack_pair_nib_h(const void* x, int dtype, int64_t ldx, uint32_t* x_plane, int64_t ldxp, int64_t rows_x, const void* w,
+                       int64_t ldw, uint32_t* w_plane, int64_t ldwp, int64_t rows_w, int64_t K, int w_ternary,
+                       qt_stream_t stream);
+
+/* qt_nib_gemm with a bf16 / fp16 result: Y[M,N] (2-byte elements of `dtype`, row stride ldy elements) = the exact
+ * integer sum + bias (bias stays fp32; NULL = none), rounded ONCE to nearest even — what a half-precision dense GEMM
+ * returns for these operands.  NaN in the bias comes out as NaN, fp16 overflow as +-inf.  ldy % 8 == 0, N % 8 == 0 and a
+ * 16-byte aligned Y take the 16-byte store path; anything else is stored element by element. */
+int qt_nib_gemm_h(const uint32_t* Xn, int64_t ldxp, const uint32_t* Wn, int64_t ldwp, const float* bias, void* Y, int dtype,
+                  int64_t ldy, int64_t M, int64_t N, int64_t K, qt_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * DoReFa k-bit path: int8 code planes + int8 MFMA (v_mfma_i32_32x32x32_i8), exact int32 accumulate.
@@ -751,6 +793,14 @@ int qt_conv2d_implicit(int elem, const uint32_t* P, int64_t N, int64_t H, int64_
                        int64_t dh, int64_t dw, const uint32_t* Wmat, int64_t ldwp, const float* bias,
                        float scale, const float* scale_dev, float* Y, int64_t ldy, int64_t Cout,
                        qt_stream_t stream);
+
+/* qt_conv2d_implicit on fp4 nibble planes (elem 0) with a bf16 / fp16 result ("Half-precision operands" above): y is the NHWC
+ * result [N * Ho * Wo][ldy] in 2-byte elements of `dtype`, the exact integer sum + bias (fp32, may be NULL) rounded once to
+ * nearest even — qt_nib_gemm_h's epilogue on the conv kernels.  Plain output only: the threshold / code / BatchNorm epilogues
+ * keep their fp32 arithmetic and are not offered here. */
+int qt_conv2d_implicit_h(const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, int64_t Cw, int64_t kh, int64_t kw, int64_t sh,
+                         int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw, const uint32_t* Wmat, int64_t ldwp,
+                         const float* bias, void* Y, int dtype, int64_t ldy, int64_t Cout, qt_stream_t stream);
 
 /* qt_conv2d_implicit with the main loop chosen by the caller (tests / tuning; an argument, not process state):
  * variant 0 = automatic (ping-pong 384x192 tile for 192-wide column tiles, double-buffered otherwise),

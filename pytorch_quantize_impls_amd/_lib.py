@@ -58,6 +58,15 @@ SIGNATURES = {
     "qt_sign_pack_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
     "qt_ternary_pack_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
     "qt_check_pm1_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p]),
+    "qt_sign_pack_h": (_c_int, [_c_p, _c_int, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
+    "qt_ternary_pack_h": (_c_int, [_c_p, _c_int, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
+    "qt_check_pm1_h": (_c_int, [_c_p, _c_int, _c_i64, _c_p, _c_p]),
+    "qt_sign_pack_nib_h": (_c_int, [_c_p, _c_int, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
+    "qt_ternary_pack_nib_h": (_c_int, [_c_p, _c_int, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
+    "qt_pack_pair_nib_h": (_c_int, [_c_p, _c_int, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64,
+                                    _c_int, _c_p]),
+    "qt_nib_gemm_h": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
+    "qt_conv2d_implicit_h": (_c_int, [_c_p] + [_c_i64] * 12 + [_c_p, _c_i64, _c_p, _c_p, _c_int, _c_i64, _c_i64, _c_p]),
     "qt_lin_quantize_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_int, _c_int, _c_p]),
     "qt_log_quantize_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_int, _c_int, _c_p]),
     "qt_ap2_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_p]),

@@ -48,6 +48,7 @@
 
 #include <cstdio>
 #include "mfma_gemm_kernel.h"
+#include "qt_elt.h"
 
 namespace {
 
@@ -64,33 +65,41 @@ int check_common(const void* Xn, int64_t ldxp, const void* Wn, int64_t ldwp, con
     return QT_OK;
 }
 
+#define QT_GO(...) return launch_cfg<__VA_ARGS__>(Xn, ldxp, Wn, ldwp, bias, scale, scale_dev, Y, ldy, M, N, K, stream)
+// automatic dispatch: tile width by N and CU fill, fast path when its contract holds
+template <class E>
+int dispatch_gemm_auto(const uint32_t* Xn, int64_t ldxp, const uint32_t* Wn, int64_t ldwp,
+                       const float* bias, float scale, const float* scale_dev, float* Y, int64_t ldy, int64_t M,
+                       int64_t N, int64_t K, qt_stream_t stream) {
+    const bool pipe_ok = !(ldxp & 31) && !(ldwp & 31) && M * ldxp * 4 < (1ll << 31) &&
+                         N * ldwp * 4 < (1ll << 31);
+    const int tn = pick_tile_n_gemm(M, N);
+    // skinny (FC at batch <= 512): the K loop is a chain of latency-bound stage round trips on a quarter of
+    // the CUs — 128x64 tiles and 256-byte stages (tools/bench_gemm_variants.py: 256x4096x25088 75 -> 48 us)
+    // ... and 64x64 tiles with 512-byte stages up to M = 256 (256x4096x9216: 21.4 -> 13.7 us)
+    if (pipe_ok && M <= 256 && !((ldxp | ldwp) & 127)) QT_GO(CfgSkinny512<E>);
+    if (pipe_ok && M <= 512 && !((ldxp | ldwp) & 63)) QT_GO(CfgSkinny<E>);
+    if (pipe_ok) {
+        if (tn == 256) QT_GO(PP256<E>);
+        if (tn == 192 && prefer_384_rows(M, N)) QT_GO(PP384x192<E>);
+        if (tn == 192) QT_GO(PP192<E>);
+        if (tn == 128) QT_GO(PP128<E>);
+        QT_GO(Cfg64<E, 1>);
+    }
+    if (tn == 256) QT_GO(Cfg256<E, 0>);
+    if (tn == 192) QT_GO(Cfg192<E, 0>);
+    if (tn == 128) QT_GO(Cfg128<E, 0>);
+    QT_GO(Cfg64<E, 0>);
+}
+
 template <class E>
 int dispatch_gemm(int variant, const uint32_t* Xn, int64_t ldxp, const uint32_t* Wn, int64_t ldwp,
                   const float* bias, float scale, const float* scale_dev, float* Y, int64_t ldy, int64_t M,
                   int64_t N, int64_t K, qt_stream_t stream) {
     const bool pipe_ok = !(ldxp & 31) && !(ldwp & 31) && M * ldxp * 4 < (1ll << 31) &&
                          N * ldwp * 4 < (1ll << 31);
-#define QT_GO(...) return launch_cfg<__VA_ARGS__>(Xn, ldxp, Wn, ldwp, bias, scale, scale_dev, Y, ldy, M, N, K, stream)
     switch (variant) {
-        case 0: {  // automatic: tile width by N and CU fill, fast path when its contract holds
-            const int tn = pick_tile_n_gemm(M, N);
-            // skinny (FC at batch <= 512): the K loop is a chain of latency-bound stage round trips on a quarter of
-            // the CUs — 128x64 tiles and 256-byte stages (tools/bench_gemm_variants.py: 256x4096x25088 75 -> 48 us)
-            // ... and 64x64 tiles with 512-byte stages up to M = 256 (256x4096x9216: 21.4 -> 13.7 us)
-            if (pipe_ok && M <= 256 && !((ldxp | ldwp) & 127)) QT_GO(CfgSkinny512<E>);
-            if (pipe_ok && M <= 512 && !((ldxp | ldwp) & 63)) QT_GO(CfgSkinny<E>);
-            if (pipe_ok) {
-                if (tn == 256) QT_GO(PP256<E>);
-                if (tn == 192 && prefer_384_rows(M, N)) QT_GO(PP384x192<E>);
-                if (tn == 192) QT_GO(PP192<E>);
-                if (tn == 128) QT_GO(PP128<E>);
-                QT_GO(Cfg64<E, 1>);
-            }
-            if (tn == 256) QT_GO(Cfg256<E, 0>);
-            if (tn == 192) QT_GO(Cfg192<E, 0>);
-            if (tn == 128) QT_GO(Cfg128<E, 0>);
-            QT_GO(Cfg64<E, 0>);
-        }
+        case 0: return dispatch_gemm_auto<E>(Xn, ldxp, Wn, ldwp, bias, scale, scale_dev, Y, ldy, M, N, K, stream);
         case 15: if (!pipe_ok) return QT_ERR_ALIGNMENT; QT_GO(Cfg192<E, 1>);
         case 16: QT_GO(Cfg192<E, 0>);
         case 5: QT_GO(Cfg256<E, 0>);
@@ -119,14 +128,19 @@ int dispatch_gemm(int variant, const uint32_t* Xn, int64_t ldxp, const uint32_t*
 #undef QT_GO
 }
 
-// ---- fp32 -> nibble plane ------------------------------------------------------------------------
+// ---- fp32 / bf16 / fp16 -> nibble plane (element types: qt_elt.h) ---------------------------------
 struct NibSign {  // safeSign: +1 -> 0x2, -1 -> 0xA
     __device__ __forceinline__ static uint32_t nib(float x) { return x < 0.0f ? 0xAu : 0x2u; }
+    template <class E> __device__ __forceinline__ static uint32_t nib(uint16_t h) { return E::neg(h) ? 0xAu : 0x2u; }
 };
 struct NibTernary {  // TernaryConnectDeterministic: 0 -> 0x0
     __device__ __forceinline__ static uint32_t nib(float x) {
         const float t = qt_ternarize(x);
         return t == 0.0f ? 0x0u : (t < 0.0f ? 0xAu : 0x2u);
+    }
+    template <class E> __device__ __forceinline__ static uint32_t nib(uint16_t h) {
+        const int t = E::tern(h);
+        return t == 0 ? 0x0u : (t < 0 ? 0xAu : 0x2u);
     }
 };
 
@@ -137,6 +151,18 @@ struct NibSign0 {  // torch.sign: 0 (and NaN) -> 0x0 — the XNOR-Net weight ima
 template <class Enc>
 __device__ __forceinline__ uint32_t nib_half(const float4& v) {   // 4 elements -> 16 bits
     return Enc::nib(v.x) | (Enc::nib(v.y) << 4) | (Enc::nib(v.z) << 8) | (Enc::nib(v.w) << 12);
+}
+template <class Enc, class E>
+__device__ __forceinline__ uint32_t nib_word(const typename E::vec& v) {   // 8 half elements -> one whole word
+    uint32_t w = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w |= Enc::template nib<E>(v.e[i]) << (4 * i);
+    return w;
+}
+template <class Enc, class E>
+__device__ __forceinline__ uint32_t nib_of(typename E::scalar x) {
+    if constexpr (E::EPV == 4) return Enc::nib(x);
+    else return Enc::template nib<E>(x);
 }
 
 // Write-through (sc1) dword store: the nibble plane is read by the GEMM that follows, through the L2s / MALL, and a kernel
@@ -153,40 +179,55 @@ __device__ __forceinline__ void store_wt(uint32_t* p, uint32_t v) {
 // lanes active on 256 contiguous bytes.  Slots past K/4 produce zero nibbles (the pad-is-zero invariant).  Units are walked
 // wave-strided (gw, gw + nw, ...) with the (row, unit) position advanced by a precomputed step: 32-bit arithmetic, no
 // division in the loop.  Host contract (pack_fits_32bit): rows, 2 ldp, K/4 < 2^30; K >= 4.
-template <class Enc>
-__device__ __forceinline__ void nib_pack_rows(const float* __restrict__ x, int64_t ldx, uint32_t* __restrict__ out,
+// Half elements (E::EPV == 8): a 16-byte slot is eight elements = one whole word, a padded row is ldp slots, and the
+// unit's four loads per lane become four full-wave dword stores of 256 contiguous bytes each — no lane exchange.
+template <class Enc, class E>
+__device__ __forceinline__ void nib_pack_rows(const typename E::scalar* __restrict__ x, int64_t ldx, uint32_t* __restrict__ out,
                                               int64_t ldp, int rows, int k4, int gw, int nw) {
     const int lane = threadIdx.x & 63;
     const bool odd = lane & 1;
-    const int spr = (int)ldp * 2, upr = (spr + 255) >> 8;
+    const int spr = (int)ldp * (8 / E::EPV), upr = (spr + 255) >> 8;
     int row = gw / upr, seg = gw - row * upr;
     const int srow = nw / upr, sseg = nw - srow * upr;
     while (row < rows) {
-        const float* xr = x + (int64_t)row * ldx;
+        const typename E::scalar* xr = x + (int64_t)row * ldx;
         uint32_t* orow = out + (int64_t)row * ldp;
         const int s0 = seg * 256 + lane;
-        // unconditional loads (slot clamped into the row's K), masked after: a guarded load becomes a branch around a load
-        // and its wait, i.e. one load in flight
-        float4 v[4];
+        if constexpr (E::EPV == 8) {
+            typename E::vec v[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const float4*>(xr + min(s0 + 64 * j, k4 - 1) * 4);
-        uint32_t h[4];
+            for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const typename E::vec*>(xr + min(s0 + 64 * j, k4 - 1) * 8);
+            uint32_t word[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) h[j] = nib_half<Enc>(v[j]) & (s0 + 64 * j < k4 ? 0xFFFFu : 0u);
-        uint32_t word[2];
+            for (int j = 0; j < 4; ++j) word[j] = nib_word<Enc, E>(v[j]) & (s0 + 64 * j < k4 ? 0xFFFFFFFFu : 0u);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const uint32_t send = odd ? h[2 * p] : h[2 * p + 1];
-            const uint32_t recv = (uint32_t)__builtin_amdgcn_mov_dpp((int)send, 0xB1, 0xF, 0xF, false);  // quad_perm [1,0,3,2]
-            word[p] = odd ? (recv | (h[2 * p + 1] << 16)) : (h[2 * p] | (recv << 16));
-        }
-        // both stores after the last load is consumed: the compiler does not count the asm stores, so a store issued
-        // between the loads would turn its later vmcnt waits into waits for the store's completion
-        __builtin_amdgcn_sched_barrier(0);
+            for (int j = 0; j < 4; ++j)
+                if (s0 + 64 * j < spr) store_wt(orow + s0 + 64 * j, word[j]);
+        } else {
+            // unconditional loads (slot clamped into the row's K), masked after: a guarded load becomes a branch around a load
+            // and its wait, i.e. one load in flight
+            float4 v[4];
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const int ws = seg * 256 + 128 * p + (odd ? 63 + lane : lane);   // first slot of the word this lane stores
-            if (ws < spr) store_wt(orow + (ws >> 1), word[p]);
+            for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const float4*>(xr + min(s0 + 64 * j, k4 - 1) * 4);
+            uint32_t h[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) h[j] = nib_half<Enc>(v[j]) & (s0 + 64 * j < k4 ? 0xFFFFu : 0u);
+            uint32_t word[2];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const uint32_t send = odd ? h[2 * p] : h[2 * p + 1];
+                const uint32_t recv = (uint32_t)__builtin_amdgcn_mov_dpp((int)send, 0xB1, 0xF, 0xF, false);  // quad_perm [1,0,3,2]
+                word[p] = odd ? (recv | (h[2 * p + 1] << 16)) : (h[2 * p] | (recv << 16));
+            }
+            // both stores after the last load is consumed: the compiler does not count the asm stores, so a store issued
+            // between the loads would turn its later vmcnt waits into waits for the store's completion
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const int ws = seg * 256 + 128 * p + (odd ? 63 + lane : lane);   // first slot of the word this lane stores
+                if (ws < spr) store_wt(orow + (ws >> 1), word[p]);
+            }
         }
         seg += sseg;
         row += srow;
@@ -194,31 +235,31 @@ __device__ __forceinline__ void nib_pack_rows(const float* __restrict__ x, int64
     }
 }
 
-template <class Enc>
-__global__ __launch_bounds__(256) void nib_pack_vec_kernel(const float* __restrict__ x, int64_t ldx,
+template <class Enc, class E>
+__global__ __launch_bounds__(256) void nib_pack_vec_kernel(const typename E::scalar* __restrict__ x, int64_t ldx,
                                                            uint32_t* __restrict__ out, int64_t ldp, int rows, int k4) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    nib_pack_rows<Enc>(x, ldx, out, ldp, rows, k4, blockIdx.x * 4 + wave, gridDim.x * 4);
+    nib_pack_rows<Enc, E>(x, ldx, out, ldp, rows, k4, blockIdx.x * 4 + wave, gridDim.x * 4);
 }
 
 // Both operands of one LinearBin / LinearTer forward in ONE launch (activation: safeSign, weight: EncW): saves a
 // kernel boundary and one ramp / tail of a ~12 us HBM-bound kernel.  Workgroups [0, ga) pack the activation, the rest
 // the weight (ga: the activation's share of the units).
-template <class EncW>
-__global__ __launch_bounds__(256) void nib_pack_pair_kernel(const float* __restrict__ xa, int64_t lda,
+template <class EncW, class E>
+__global__ __launch_bounds__(256) void nib_pack_pair_kernel(const typename E::scalar* __restrict__ xa, int64_t lda,
                                                             uint32_t* __restrict__ oa, int64_t ldpa, int rowsa,
-                                                            const float* __restrict__ xb, int64_t ldb,
+                                                            const typename E::scalar* __restrict__ xb, int64_t ldb,
                                                             uint32_t* __restrict__ ob, int64_t ldpb, int rowsb,
                                                             int k4, int ga) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.x;
-    if (b < ga) nib_pack_rows<NibSign>(xa, lda, oa, ldpa, rowsa, k4, b * 4 + wave, ga * 4);
-    else nib_pack_rows<EncW>(xb, ldb, ob, ldpb, rowsb, k4, (b - ga) * 4 + wave, ((int)gridDim.x - ga) * 4);
+    if (b < ga) nib_pack_rows<NibSign, E>(xa, lda, oa, ldpa, rowsa, k4, b * 4 + wave, ga * 4);
+    else nib_pack_rows<EncW, E>(xb, ldb, ob, ldpb, rowsb, k4, (b - ga) * 4 + wave, ((int)gridDim.x - ga) * 4);
 }
 
 // Generic path (any K / alignment): one thread per output word, scalar loads.
-template <class Enc>
-__global__ __launch_bounds__(256) void nib_pack_scalar_kernel(const float* __restrict__ x, int64_t ldx,
+template <class Enc, class E>
+__global__ __launch_bounds__(256) void nib_pack_scalar_kernel(const typename E::scalar* __restrict__ x, int64_t ldx,
                                                               uint32_t* __restrict__ out, int64_t ldp,
                                                               int64_t rows, int64_t K) {
     const int64_t total = rows * ldp;
@@ -229,7 +270,7 @@ __global__ __launch_bounds__(256) void nib_pack_scalar_kernel(const float* __res
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int64_t k = w * 8 + e;
-            if (k < K) word |= Enc::nib(x[row * ldx + k]) << (4 * e);
+            if (k < K) word |= nib_of<Enc, E>(x[row * ldx + k]) << (4 * e);
         }
         out[i] = word;
     }
@@ -306,27 +347,66 @@ __global__ __launch_bounds__(256) void bits_to_nib_pad_kernel(const uint32_t* __
 
 // nib_pack_rows' 32-bit position arithmetic: row + units-per-wave step and the slot index stay below 2^31
 bool pack_fits_32bit(int64_t rows, int64_t ldp) { return rows < (1ll << 30) && ldp < (1ll << 29); }
-int64_t pack_units(int64_t rows, int64_t ldp) { return rows * ((ldp * 2 + 255) / 256); }   // one unit = one wave's work
+// one unit = one wave's work = 256 16-byte slots; spw = slots per plane word (2 for fp32, 1 for the half types)
+int64_t pack_units(int64_t rows, int64_t ldp, int spw = 2) { return rows * ((ldp * spw + 255) / 256); }
 
-template <class Enc>
-int launch_nib_pack(const float* x, int64_t ldx, uint32_t* out, int64_t ldp, int64_t rows, int64_t K,
+template <class Enc, class E = EltF32>
+int launch_nib_pack(const typename E::scalar* x, int64_t ldx, uint32_t* out, int64_t ldp, int64_t rows, int64_t K,
                     qt_stream_t stream) {
+    constexpr int EPV = E::EPV;
     if (rows < 0 || K < 0 || ldx < K) return QT_ERR_INVALID_ARG;
     if (rows == 0) return QT_OK;
     if (!out || (!x && K > 0)) return QT_ERR_INVALID_ARG;
     const int64_t kw = (K + 7) / 8;
     if (ldp < kw || (ldp & 3) != 0 || !qt_aligned16(out)) return QT_ERR_ALIGNMENT;
     if (ldp == 0) return QT_OK;
-    const bool vec = K > 0 && (K % 4 == 0) && (ldx % 4 == 0) && qt_aligned16(x) && pack_fits_32bit(rows, ldp);
+    const bool vec = K > 0 && (K % EPV == 0) && (ldx % EPV == 0) && qt_aligned16(x) && pack_fits_32bit(rows, ldp);
     if (vec) {
-        const int grid = qt_stream_grid((pack_units(rows, ldp) + 3) / 4);
-        hipLaunchKernelGGL((nib_pack_vec_kernel<Enc>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x,
-                           ldx, out, ldp, (int)rows, (int)(K / 4));
+        const int grid = qt_stream_grid((pack_units(rows, ldp, 8 / EPV) + 3) / 4);
+        hipLaunchKernelGGL((nib_pack_vec_kernel<Enc, E>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x,
+                           ldx, out, ldp, (int)rows, (int)(K / EPV));
     } else {
         const int grid = qt_stream_grid((rows * ldp + 255) / 256);
-        hipLaunchKernelGGL((nib_pack_scalar_kernel<Enc>), dim3(grid), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL((nib_pack_scalar_kernel<Enc, E>), dim3(grid), dim3(256), 0, (hipStream_t)stream,
                            x, ldx, out, ldp, rows, K);
     }
+    return qt_check_launch();
+}
+
+// Both operands of a training-mode Linear in one launch (qt_pack_pair_nib_f32 / _h).
+template <class E>
+int pack_pair_any(const typename E::scalar* x, int64_t ldx, uint32_t* x_plane, int64_t ldxp, int64_t rows_x,
+                  const typename E::scalar* w, int64_t ldw, uint32_t* w_plane, int64_t ldwp, int64_t rows_w, int64_t K,
+                  int w_ternary, qt_stream_t stream) {
+    constexpr int EPV = E::EPV;
+    if (rows_x < 0 || rows_w < 0 || K < 0 || ldx < K || ldw < K) return QT_ERR_INVALID_ARG;
+    const bool vec = rows_x > 0 && rows_w > 0 && K > 0 && (K % EPV == 0) && (ldx % EPV == 0) && (ldw % EPV == 0) &&
+                     qt_aligned16(x) && qt_aligned16(w) && x && w && x_plane && w_plane;
+    if (!vec) {   // ragged / empty operands: the two single-operand launches handle every case
+        const int rc = launch_nib_pack<NibSign, E>(x, ldx, x_plane, ldxp, rows_x, K, stream);
+        if (rc != QT_OK) return rc;
+        return w_ternary ? launch_nib_pack<NibTernary, E>(w, ldw, w_plane, ldwp, rows_w, K, stream)
+                         : launch_nib_pack<NibSign, E>(w, ldw, w_plane, ldwp, rows_w, K, stream);
+    }
+    const int64_t kw = (K + 7) / 8;
+    if (ldxp < kw || ldwp < kw || (ldxp & 3) || (ldwp & 3) || !qt_aligned16(x_plane) || !qt_aligned16(w_plane))
+        return QT_ERR_ALIGNMENT;
+    if (!pack_fits_32bit(rows_x, ldxp) || !pack_fits_32bit(rows_w, ldwp)) {
+        const int rc = launch_nib_pack<NibSign, E>(x, ldx, x_plane, ldxp, rows_x, K, stream);
+        if (rc != QT_OK) return rc;
+        return w_ternary ? launch_nib_pack<NibTernary, E>(w, ldw, w_plane, ldwp, rows_w, K, stream)
+                         : launch_nib_pack<NibSign, E>(w, ldw, w_plane, ldwp, rows_w, K, stream);
+    }
+    // workgroups (4 waves each) split between the operands in proportion to their units, at least one each
+    const int64_t ua = pack_units(rows_x, ldxp, 8 / EPV), ub = pack_units(rows_w, ldwp, 8 / EPV);
+    const int grid = qt_stream_grid((ua + 3) / 4 + (ub + 3) / 4);   // >= 2: both operands have rows and K > 0
+    const int ga = (int)std::min<int64_t>(std::max<int64_t>(1, (grid * ua + (ua + ub) / 2) / (ua + ub)), grid - 1);
+    if (w_ternary)
+        hipLaunchKernelGGL((nib_pack_pair_kernel<NibTernary, E>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx,
+                           x_plane, ldxp, (int)rows_x, w, ldw, w_plane, ldwp, (int)rows_w, (int)(K / EPV), ga);
+    else
+        hipLaunchKernelGGL((nib_pack_pair_kernel<NibSign, E>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx,
+                           x_plane, ldxp, (int)rows_x, w, ldw, w_plane, ldwp, (int)rows_w, (int)(K / EPV), ga);
     return qt_check_launch();
 }
 
@@ -360,35 +440,34 @@ int qt_sign0_pack_nib_f32(const float* x, int64_t ldx, uint32_t* nib_plane, int6
 int qt_pack_pair_nib_f32(const float* x, int64_t ldx, uint32_t* x_plane, int64_t ldxp, int64_t rows_x,
                          const float* w, int64_t ldw, uint32_t* w_plane, int64_t ldwp, int64_t rows_w, int64_t K,
                          int w_ternary, qt_stream_t stream) {
-    if (rows_x < 0 || rows_w < 0 || K < 0 || ldx < K || ldw < K) return QT_ERR_INVALID_ARG;
-    const bool vec = rows_x > 0 && rows_w > 0 && K > 0 && (K % 4 == 0) && (ldx % 4 == 0) && (ldw % 4 == 0) &&
-                     qt_aligned16(x) && qt_aligned16(w) && x && w && x_plane && w_plane;
-    if (!vec) {   // ragged / empty operands: the two single-operand launches handle every case
-        const int rc = launch_nib_pack<NibSign>(x, ldx, x_plane, ldxp, rows_x, K, stream);
-        if (rc != QT_OK) return rc;
-        return w_ternary ? launch_nib_pack<NibTernary>(w, ldw, w_plane, ldwp, rows_w, K, stream)
-                         : launch_nib_pack<NibSign>(w, ldw, w_plane, ldwp, rows_w, K, stream);
-    }
-    const int64_t kw = (K + 7) / 8;
-    if (ldxp < kw || ldwp < kw || (ldxp & 3) || (ldwp & 3) || !qt_aligned16(x_plane) || !qt_aligned16(w_plane))
-        return QT_ERR_ALIGNMENT;
-    if (!pack_fits_32bit(rows_x, ldxp) || !pack_fits_32bit(rows_w, ldwp)) {
-        const int rc = launch_nib_pack<NibSign>(x, ldx, x_plane, ldxp, rows_x, K, stream);
-        if (rc != QT_OK) return rc;
-        return w_ternary ? launch_nib_pack<NibTernary>(w, ldw, w_plane, ldwp, rows_w, K, stream)
-                         : launch_nib_pack<NibSign>(w, ldw, w_plane, ldwp, rows_w, K, stream);
-    }
-    // workgroups (4 waves each) split between the operands in proportion to their units, at least one each
-    const int64_t ua = pack_units(rows_x, ldxp), ub = pack_units(rows_w, ldwp);
-    const int grid = qt_stream_grid((ua + 3) / 4 + (ub + 3) / 4);   // >= 2: both operands have rows and K > 0
-    const int ga = (int)std::min<int64_t>(std::max<int64_t>(1, (grid * ua + (ua + ub) / 2) / (ua + ub)), grid - 1);
-    if (w_ternary)
-        hipLaunchKernelGGL((nib_pack_pair_kernel<NibTernary>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx,
-                           x_plane, ldxp, (int)rows_x, w, ldw, w_plane, ldwp, (int)rows_w, (int)(K / 4), ga);
-    else
-        hipLaunchKernelGGL((nib_pack_pair_kernel<NibSign>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx,
-                           x_plane, ldxp, (int)rows_x, w, ldw, w_plane, ldwp, (int)rows_w, (int)(K / 4), ga);
-    return qt_check_launch();
+    return pack_pair_any<EltF32>(x, ldx, x_plane, ldxp, rows_x, w, ldw, w_plane, ldwp, rows_w, K, w_ternary, stream);
+}
+
+int qt_sign_pack_nib_h(const void* x, int dtype, int64_t ldx, uint32_t* nib_plane, int64_t ldp, int64_t rows, int64_t K,
+                       qt_stream_t stream) {
+    const uint16_t* xh = static_cast<const uint16_t*>(x);
+    if (dtype == QT_DTYPE_BF16) return launch_nib_pack<NibSign, EltBf16>(xh, ldx, nib_plane, ldp, rows, K, stream);
+    if (dtype == QT_DTYPE_F16) return launch_nib_pack<NibSign, EltF16>(xh, ldx, nib_plane, ldp, rows, K, stream);
+    return QT_ERR_INVALID_ARG;
+}
+
+int qt_ternary_pack_nib_h(const void* x, int dtype, int64_t ldx, uint32_t* nib_plane, int64_t ldp, int64_t rows, int64_t K,
+                          qt_stream_t stream) {
+    const uint16_t* xh = static_cast<const uint16_t*>(x);
+    if (dtype == QT_DTYPE_BF16) return launch_nib_pack<NibTernary, EltBf16>(xh, ldx, nib_plane, ldp, rows, K, stream);
+    if (dtype == QT_DTYPE_F16) return launch_nib_pack<NibTernary, EltF16>(xh, ldx, nib_plane, ldp, rows, K, stream);
+    return QT_ERR_INVALID_ARG;
+}
+
+int qt_pack_pair_nib_h(const void* x, int dtype, int64_t ldx, uint32_t* x_plane, int64_t ldxp, int64_t rows_x, const void* w,
+                       int64_t ldw, uint32_t* w_plane, int64_t ldwp, int64_t rows_w, int64_t K, int w_ternary,
+                       qt_stream_t stream) {
+    const uint16_t *xh = static_cast<const uint16_t*>(x), *wh = static_cast<const uint16_t*>(w);
+    if (dtype == QT_DTYPE_BF16)
+        return pack_pair_any<EltBf16>(xh, ldx, x_plane, ldxp, rows_x, wh, ldw, w_plane, ldwp, rows_w, K, w_ternary, stream);
+    if (dtype == QT_DTYPE_F16)
+        return pack_pair_any<EltF16>(xh, ldx, x_plane, ldxp, rows_x, wh, ldw, w_plane, ldwp, rows_w, K, w_ternary, stream);
+    return QT_ERR_INVALID_ARG;
 }
 
 int qt_nib_gemm_variant(int variant, const uint32_t* Xn, int64_t ldxp, const uint32_t* Wn,
@@ -420,6 +499,18 @@ int qt_nib_gemm_describe(int64_t M, int64_t N, int64_t K, int64_t ldxp, int64_t 
 int qt_nib_gemm(const uint32_t* Xn, int64_t ldxp, const uint32_t* Wn, int64_t ldwp, const float* bias,
                 float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, qt_stream_t stream) {
     return qt_nib_gemm_variant(0, Xn, ldxp, Wn, ldwp, bias, Y, ldy, M, N, K, stream);
+}
+
+int qt_nib_gemm_h(const uint32_t* Xn, int64_t ldxp, const uint32_t* Wn, int64_t ldwp, const float* bias, void* Y, int dtype,
+                  int64_t ldy, int64_t M, int64_t N, int64_t K, qt_stream_t stream) {
+    if (dtype != QT_DTYPE_BF16 && dtype != QT_DTYPE_F16) return QT_ERR_INVALID_ARG;
+    float* Yf = static_cast<float*>(Y);          // the kernel's pointer type; the half epilogue re-types it
+    const int rc = check_common(Xn, ldxp, Wn, ldwp, Yf, ldy, M, N, K, (K + 7) / 8);
+    if (rc != QT_OK) return rc > 0 ? QT_OK : rc;
+    if (K >= (1 << 24)) return QT_ERR_UNSUPPORTED;  // fp32-exact bound of the accumulator
+    if (dtype == QT_DTYPE_BF16)
+        return dispatch_gemm_auto<ElemFp4Out<1>>(Xn, ldxp, Wn, ldwp, bias, 1.0f, nullptr, Yf, ldy, M, N, K, stream);
+    return dispatch_gemm_auto<ElemFp4Out<2>>(Xn, ldxp, Wn, ldwp, bias, 1.0f, nullptr, Yf, ldy, M, N, K, stream);
 }
 
 int qt_bf16_gemm(const uint32_t* Xh, int64_t ldxp, const uint32_t* Wh, int64_t ldwp, const float* bias,
@@ -516,7 +607,8 @@ static int conv_implicit_impl(int elem, const uint32_t* P, int64_t Nimg, int64_t
                               int64_t kh, int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh,
                               int64_t dw, const uint32_t* Wmat, int64_t ldwp, const float* bias, float scale,
                               const float* scale_dev, float* Y, int64_t ldy, int64_t Cout, qt_stream_t stream,
-                              const EpiArgs& epi_in, int64_t hy = 0, int64_t hx = 0, int g_conv_force = 0) {
+                              const EpiArgs& epi_in, int64_t hy = 0, int64_t hx = 0, int g_conv_force = 0, int out_dtype = 0) {
+    // out_dtype (fp4 planes, plain epilogue only): QT_DTYPE_BF16 / QT_DTYPE_F16 = Y holds 2-byte elements (ElemFp4Out)
     // (hy, hx): halo of the INPUT plane, [N][H + 2hy][W + 2hx][Cw] with a zero border: a conv whose padding fits in
     // the halo runs as the un-padded conv on the window that starts (hy - ph, hx - pw) into the plane.
     EpiArgs epi = epi_in;
@@ -627,6 +719,8 @@ static int conv_implicit_impl(int elem, const uint32_t* P, int64_t Nimg, int64_t
         if (tn == 128) return launch_cfg<Conv128<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
         return launch_cfg<Conv64<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi);                 \
     } while (0)
+    if (elem == 0 && out_dtype == QT_DTYPE_BF16) QT_CONV(ElemFp4Out<1>);
+    if (elem == 0 && out_dtype == QT_DTYPE_F16) QT_CONV(ElemFp4Out<2>);
     if (elem == 0) QT_CONV(ElemFp4);
     if (elem == 1) QT_CONV(ElemI8);
     if (elem == 3) QT_CONV(ElemF16);
@@ -651,6 +745,14 @@ int qt_conv2d_implicit(int elem, const uint32_t* P, int64_t Nimg, int64_t H, int
                        const float* scale_dev, float* Y, int64_t ldy, int64_t Cout, qt_stream_t stream) {
     return conv_implicit_impl(elem, P, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, Wmat, ldwp, bias, scale,
                               scale_dev, Y, ldy, Cout, stream, EpiArgs{});
+}
+
+int qt_conv2d_implicit_h(const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, int64_t Cw, int64_t kh, int64_t kw, int64_t sh,
+                         int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw, const uint32_t* Wmat, int64_t ldwp,
+                         const float* bias, void* Y, int dtype, int64_t ldy, int64_t Cout, qt_stream_t stream) {
+    if (dtype != QT_DTYPE_BF16 && dtype != QT_DTYPE_F16) return QT_ERR_INVALID_ARG;
+    return conv_implicit_impl(0, P, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, Wmat, ldwp, bias, 1.0f, nullptr,
+                              static_cast<float*>(Y), ldy, Cout, stream, EpiArgs{}, 0, 0, 0, dtype);
 }
 
 int qt_conv2d_implicit_bits(int elem, const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, int64_t Cw,

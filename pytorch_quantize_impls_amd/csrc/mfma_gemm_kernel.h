@@ -228,6 +228,37 @@ struct ElemFp4T : ElemFp4 {
     static constexpr bool SWAPT = true;
     __device__ __forceinline__ static acc_t mfma(const uint4& a, const uint4& b, acc_t c) { return ElemFp4::mfma(b, a, c); }
 };
+// Output-dtype variants of the PLAIN epilogue (half-precision models, layers/sign_layers.py): the fp32 accumulator plus the
+// fp32 bias is rounded ONCE, to nearest even, to bf16 (OUT_DTYPE 1, v_cvt_pk_bf16_f32) or fp16 (2, v_cvt_f16_f32 — not the
+// truncating v_cvt_pkrtz) and leaves as whole dwords: what the dense library's half GEMM returns for +-1 / 0 operands (the exact
+// integer sum + bias, rounded once).  NaN (a poisoned bias) stays NaN, fp16 overflow becomes +-inf.  Y then points to 2-byte
+// elements and ldy counts them.  The threshold / code epilogues are not instantiated for these elements.
+template <int OD> struct ElemFp4Out : ElemFp4 {
+    static constexpr int OUT_DTYPE = OD;
+};
+template <class E, class = void> struct elem_out : std::integral_constant<int, 0> {};
+template <class E> struct elem_out<E, std::void_t<decltype(E::OUT_DTYPE)>> : std::integral_constant<int, E::OUT_DTYPE> {};
+template <int OD>
+__device__ __forceinline__ uint32_t cvt_half_bits(float a) {
+    uint16_t u;
+    if constexpr (OD == 1) { const __bf16 h = (__bf16)a; __builtin_memcpy(&u, &h, 2); }
+    else { const _Float16 h = (_Float16)a; __builtin_memcpy(&u, &h, 2); }
+    return u;
+}
+template <int OD>
+__device__ __forceinline__ uint32_t cvt_half_pair(float a, float b) {   // a in the low half: element order in memory
+    uint32_t u;
+    if constexpr (OD == 1) {
+        typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+        typedef float f2 __attribute__((ext_vector_type(2)));
+        const f2 f = {a, b};
+        const bf2 h = __builtin_convertvector(f, bf2);
+        __builtin_memcpy(&u, &h, 4);
+    } else {
+        u = cvt_half_bits<2>(a) | (cvt_half_bits<2>(b) << 16);
+    }
+    return u;
+}
 template <class E, class = void> struct elem_swapt : std::false_type {};
 template <class E> struct elem_swapt<E, std::void_t<decltype(E::SWAPT)>> : std::bool_constant<E::SWAPT> {};
 template <class E, class = void> struct elem_rows : std::false_type {};
@@ -836,7 +867,9 @@ __global__ __launch_bounds__(C::NTHREADS, C::WAVES_PER_SIMD) void mfma_gemm_kern
     // patch (the stage buffers are dead: every fragment read was waited for before the last barrier and
     // no DMA is in flight) and leaves as 4 dwordx4 wave-stores of 8 full 128-byte lines each: 4x fewer
     // store instructions.  LDS ops of one wave execute in issue order, so the patch needs no barrier.
-    const bool wide = ((ldy & 3) == 0) && ((N & 3) == 0) && ((reinterpret_cast<uintptr_t>(Y) & 15) == 0);
+    constexpr int OD = elem_out<E>::value;               // 0: fp32 result; 1 / 2: bf16 / fp16 (16-byte stores hold 8 elements)
+    constexpr int WIDE_MASK = OD ? 7 : 3;
+    const bool wide = ((ldy & WIDE_MASK) == 0) && ((N & WIDE_MASK) == 0) && ((reinterpret_cast<uintptr_t>(Y) & 15) == 0);
     if constexpr (SWAPT) {
         // ---- threshold epilogue, weights-as-rows form: lane (l % 32, l / 32) holds channels 16 (l / 32) .. + 15 of position l % 32 of
         // every 32 x 32 block; the bit of channel r is the sign bit of register r (flipped where alpha < 0).  Host: epi.alpha and
@@ -1171,7 +1204,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::WAVES_PER_SIMD) void mfma_gemm_kern
         if (__any(bad) && lane == 0) atomicOr(epi.overflow, 1);
         return;
     }
-    if (epi.alpha) {
+    if (OD == 0 && epi.alpha) {      // (the half-output elements have the plain epilogue only)
         // threshold bits: a v_cmp over the wave yields, per accumulator register, the 32-channel word of
         // two output rows (lanes 0-31 -> row R, lanes 32-63 -> row R + 4); lane i keeps row i's word and
         // one 32-lane store per 32x32 tile writes them.  Channels >= N compare 0 < 0 -> bit 0.
@@ -1277,7 +1310,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::WAVES_PER_SIMD) void mfma_gemm_kern
         }
     } else if (wide) {
         float* T = reinterpret_cast<float*>(smem) + wave * 1024;
-        const bool stream_out = (int64_t)M * N >= (int64_t)(8 << 20);     // >= 32 MiB of fp32: more than the eight L2s hold
+        const bool stream_out = (int64_t)M * N >= (int64_t)((OD ? 16 : 8) << 20);     // >= 32 MiB of result: more than the eight L2s hold
 #pragma unroll
         for (int b = 0; b < C::TNW; ++b) {
             const int nb = n0 + (wave_n * C::TNW + b) * 32;
@@ -1291,23 +1324,44 @@ __global__ __launch_bounds__(C::NTHREADS, C::WAVES_PER_SIMD) void mfma_gemm_kern
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                if constexpr (OD != 0) {
+                    // half result: a tile row is 64 bytes; lane (row, c8) rounds eight values and stores one dwordx4, so a
+                    // wave-store covers 16 rows x 64 contiguous bytes (the neighbouring tile b + 1 completes the 128-byte lines)
+                    uint16_t* Yh = reinterpret_cast<uint16_t*>(Y);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int row = i * 8 + (lane >> 3), c4 = (lane & 7) * 4;
-                    const float4 v = *reinterpret_cast<const float4*>(T + row * 32 + c4);
-                    const int m = mb + row, n = nb + c4;
-                    if (m < M && n < N) {
-                        float* dst = Y + (int64_t)m * ldy + n;
-                        if (stream_out) {
-                            // a result larger than the L2s is not re-read from them: write-through (sc1) stores leave no
-                            // dirty lines for the end-of-kernel write-back (4096^2 fp32: 40.5 -> 38.5 us per launch; `nt`
-                            // measured neutral).  s_nop: the store reads its data registers late and the hazard
-                            // recogniser does not look inside inline asm.
-                            typedef float epi_v4f __attribute__((ext_vector_type(4)));
-                            const epi_v4f ev = {v.x, v.y, v.z, v.w};
-                            asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(dst), "v"(ev) : "memory");
-                        } else {
-                            *reinterpret_cast<float4*>(dst) = v;
+                    for (int i = 0; i < 2; ++i) {
+                        const int row = i * 16 + (lane >> 2), c8 = (lane & 3) * 8;
+                        const float4 v0 = *reinterpret_cast<const float4*>(T + row * 32 + c8);
+                        const float4 v1 = *reinterpret_cast<const float4*>(T + row * 32 + c8 + 4);
+                        const int m = mb + row, n = nb + c8;
+                        if (m < M && n < N) {
+                            typedef uint32_t epi_v4u __attribute__((ext_vector_type(4)));
+                            const epi_v4u ev = {cvt_half_pair<OD>(v0.x, v0.y), cvt_half_pair<OD>(v0.z, v0.w),
+                                                cvt_half_pair<OD>(v1.x, v1.y), cvt_half_pair<OD>(v1.z, v1.w)};
+                            uint16_t* dst = Yh + (int64_t)m * ldy + n;
+                            if (stream_out) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(dst), "v"(ev) : "memory");
+                            else *reinterpret_cast<epi_v4u*>(dst) = ev;
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int row = i * 8 + (lane >> 3), c4 = (lane & 7) * 4;
+                        const float4 v = *reinterpret_cast<const float4*>(T + row * 32 + c4);
+                        const int m = mb + row, n = nb + c4;
+                        if (m < M && n < N) {
+                            float* dst = Y + (int64_t)m * ldy + n;
+                            if (stream_out) {
+                                // a result larger than the L2s is not re-read from them: write-through (sc1) stores leave no
+                                // dirty lines for the end-of-kernel write-back (4096^2 fp32: 40.5 -> 38.5 us per launch; `nt`
+                                // measured neutral).  s_nop: the store reads its data registers late and the hazard
+                                // recogniser does not look inside inline asm.
+                                typedef float epi_v4f __attribute__((ext_vector_type(4)));
+                                const epi_v4f ev = {v.x, v.y, v.z, v.w};
+                                asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(dst), "v"(ev) : "memory");
+                            } else {
+                                *reinterpret_cast<float4*>(dst) = v;
+                            }
                         }
                     }
                 }
@@ -1326,7 +1380,11 @@ __global__ __launch_bounds__(C::NTHREADS, C::WAVES_PER_SIMD) void mfma_gemm_kern
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int m = mb + (r & 3) + 8 * (r >> 2);
-                    if (m < M && n < N) Y[(int64_t)m * ldy + n] = E::out(acc[a][b][r], scale, bv);
+                    if (m >= M || n >= N) continue;
+                    if constexpr (OD != 0)   // half result with a ragged N / ldy: one 2-byte store per value
+                        reinterpret_cast<uint16_t*>(Y)[(int64_t)m * ldy + n] = (uint16_t)cvt_half_bits<OD>(E::out(acc[a][b][r], scale, bv));
+                    else
+                        Y[(int64_t)m * ldy + n] = E::out(acc[a][b][r], scale, bv);
                 }
             }
         }

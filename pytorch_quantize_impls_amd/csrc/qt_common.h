@@ -5,7 +5,7 @@
 #include <atomic>
 #include "../../include/qt_hip.h"
 
-#define QT_VERSION_INT 100 /* 0.1.0 */
+#define QT_VERSION_INT 200 /* 0.2.0: half-precision operand packers and output-dtype GEMM */
 
 static inline int qt_check_launch() {
     hipError_t e = hipGetLastError();

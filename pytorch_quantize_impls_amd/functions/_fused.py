@@ -265,6 +265,69 @@ def detect_pm1(input: torch.Tensor, weight: Optional[torch.Tensor]):
     return ok, None
 
 
+# ---- half precision (bf16 / fp16) -----------------------------------------------------------------------------------------------
+# The sign families take a half activation on the packed routes when it is (treated as) exactly +-1; the result is the exact
+# integer sum + bias rounded once to the activation's dtype, which is what the dense library's half GEMM / conv returns for these
+# operands.  A real-valued half activation (first layers) keeps the counted torch expression.
+
+def half_route(input, weight: torch.Tensor) -> bool:
+    """May this call take the half-precision packed routes?  Device activation in bf16 / fp16 and a weight of the same dtype —
+    or an fp32 weight while autocast to that dtype is on (the reference expression would then cast both; the result has the
+    autocast dtype).  While autocast to ANOTHER dtype is on (a bf16 model under fp16 autocast) the reference expression casts
+    both operands to that dtype: the route declines, and so does every other mix — on to the torch expression, which casts or
+    raises as F.linear / F.conv2d do."""
+    if not (isinstance(input, torch.Tensor) and input.is_cuda and input.dtype in ops.HALF_DTYPES and input.numel() > 0
+            and weight.is_cuda and weight.numel() > 0):
+        return False
+    if torch.is_autocast_enabled():
+        get = getattr(torch, "get_autocast_dtype", None)
+        if (get("cuda") if get is not None else torch.get_autocast_gpu_dtype()) != input.dtype:
+            return False
+        return weight.dtype in (input.dtype, torch.float32)
+    return weight.dtype == input.dtype
+
+
+def _tag_fits(input: torch.Tensor, layout) -> bool:
+    """Does the tensor carry a quantiser's planes that the consumer of ``layout`` will accept (activation_planes / _pixel_planes)?"""
+    tagged = packed.lookup(input, layout)
+    if tagged is None:
+        return False
+    if layout == packed.NHWC:
+        return input.dim() == 4 and tagged.K == input.shape[1] and tagged.rows * tagged.K == input.numel()
+    return tagged.K == input.shape[-1] and tagged.rows * tagged.K == input.numel()
+
+
+def half_gate(input: torch.Tensor, weight: torch.Tensor, binary_input: Optional[bool], layout):
+    """Is this half activation (treated as) exactly +-1?  Returns the ``binary_input`` argument for the forward that follows:
+    False — not +-1 (the caller takes the torch expression); True — tag of a quantiser, the layer's hint, or a device check that
+    was just verified on the host; an int32 device flag — a REMEMBERED "+-1" verdict whose check of this tensor rides along: the
+    forward treats the activation as +-1 and folds the flag into the bias (``split_hint``), so the layer detects once per call."""
+    if binary_input or _tag_fits(input, layout):
+        return True
+    if binary_input is False or not _cfg("DETECT_BINARY_INPUT"):
+        return False
+    ok, flag = detect_pm1(input, weight)
+    if not ok:
+        return False
+    return True if flag is None else flag
+
+
+def split_hint(binary_input):
+    """(binary_input as True / False / None, device flag to fold into the bias or None) — see ``half_gate``."""
+    if isinstance(binary_input, torch.Tensor):
+        return True, binary_input
+    return binary_input, None
+
+
+def half_bias(bias: Optional[torch.Tensor], dtype) -> Optional[torch.Tensor]:
+    """The bias as the fp32 vector the epilogues add: a half bias upcast (exact); an fp32 bias under autocast rounded to the
+    autocast dtype first, as the cast in front of the reference's F.linear does."""
+    if bias is None:
+        return None
+    b = bias.detach()
+    return b.to(dtype).float() if b.dtype != dtype else b.float()
+
+
 def codes_route(codes, weight: Optional[torch.Tensor]):
     """(use the int8 code planes?, device flag or None) for DoReFa activation codes whose range flag is on the device."""
     if ops._cfg("ASSUME_CODES_FIT") or codes.overflow is None:
@@ -287,10 +350,11 @@ def poison_bias(bias: Optional[torch.Tensor], flag: Optional[torch.Tensor], n: i
 
 
 def activation_planes(input: torch.Tensor, binary_input: Optional[bool], impl: str = "valu",
-                      weight: Optional[torch.Tensor] = None):
+                      weight: Optional[torch.Tensor] = None, half_ok: bool = False):
     """(packed image of a device activation in the format of ``impl`` if it is (treated as) exactly +-1 else None,
-    device flag to fold into the bias or None)."""
-    if input.dtype != torch.float32 or input.numel() == 0:
+    device flag to fold into the bias or None).  ``half_ok``: bf16 / fp16 activations are packed as well (the sign layers'
+    half route); every other caller keeps fp32 only."""
+    if input.dtype not in (ops.PACK_DTYPES if half_ok else (torch.float32,)) or input.numel() == 0:
         return None, None
     tagged = packed.lookup(input, packed.ROWS_LAST)
     if tagged is not None:
@@ -312,7 +376,7 @@ def activation_planes(input: torch.Tensor, binary_input: Optional[bool], impl: s
 def quant_linear_forward(input: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
                          kind: str, weight_q: Optional[torch.Tensor] = None,
                          weight_planes: Optional[ops.BitPlanes] = None,
-                         binary_input: Optional[bool] = None) -> torch.Tensor:
+                         binary_input: Optional[bool] = None, half_ok: bool = False) -> torch.Tensor:
     """y = input . Q(weight)^T + bias.
 
     ``weight_q``: explicit fp32 quantised weight (stochastic draw, or eval-mode pre-quantised
@@ -326,23 +390,32 @@ def quant_linear_forward(input: torch.Tensor, weight: torch.Tensor, bias: Option
     N = weight.shape[0]
     M = input.numel() // max(K, 1)
     impl = ops.select_gemm_impl(_cfg("GEMM_IMPL"), M, N, K)
-    if (impl == "mfma" and weight_planes is None and input.dtype == torch.float32 and input.numel() > 0
+    binary_input, hint_flag = split_hint(binary_input)
+    # ``half_ok`` (the sign layers' half route): a bf16 / fp16 activation is packed and the result has its dtype
+    odt = input.dtype if (half_ok and input.dtype in ops.HALF_DTYPES) else None
+    if odt is not None:
+        bias = half_bias(bias, odt)
+    if (impl == "mfma" and weight_planes is None and (input.dtype == torch.float32 or odt is not None) and input.numel() > 0
             and binary_input is not False and packed.lookup(input, packed.ROWS_LAST) is None):
-        ok, flag = (True, None) if binary_input else (detect_pm1(input, weight) if _cfg("DETECT_BINARY_INPUT") else (False, None))
+        ok, flag = (True, hint_flag) if binary_input else (detect_pm1(input, weight) if _cfg("DETECT_BINARY_INPUT") else (False, None))
         if ok:
             # neither operand is packed yet (un-tagged +-1 activation, training-mode weight): one launch packs both
             wq = weight_q if weight_q is not None else weight
             xp, wp = ops.pack_linear_operands(input, wq.reshape(N, -1), kind, impl)
-            return ops.packed_gemm(xp, wp, poison_bias(bias, flag, N, input.device), impl=impl).view(*input.shape[:-1], N)
+            return ops.packed_gemm(xp, wp, poison_bias(bias, flag, N, input.device), impl=impl,
+                                   out_dtype=odt).view(*input.shape[:-1], N)
         binary_input = False                      # verdict known: do not ask again below
-    xp, flag = activation_planes(input, binary_input, impl, weight)
+    xp, flag = activation_planes(input, binary_input, impl, weight, half_ok=odt is not None)
     if xp is not None:
+        flag = hint_flag if flag is None else flag
         wp = weight_planes
         if wp is None:
             wq = weight_q if weight_q is not None else weight
             wp = pack_weight(wq.reshape(N, -1), kind, impl)
-        y = ops.packed_gemm(xp, wp, poison_bias(bias, flag, N, input.device), impl=impl)
+        y = ops.packed_gemm(xp, wp, poison_bias(bias, flag, N, input.device), impl=impl, out_dtype=odt)
         return y.view(*input.shape[:-1], N)
+    if odt is not None:
+        raise RuntimeError("a half-precision activation that is not +-1 has no packed route: the layers send it to the torch expression")
 
     if _cfg("FLOAT_PATH") == "bf16x3" and input.dtype == torch.float32 and input.numel() > 0:
         # the quantisers are idempotent, so an explicit quantised image (eval / stochastic) goes through
@@ -354,10 +427,12 @@ def quant_linear_forward(input: torch.Tensor, weight: torch.Tensor, bias: Option
     return F.linear(input, wq, bias)
 
 
-def _pixel_planes(input: torch.Tensor, binary_input: Optional[bool], weight: Optional[torch.Tensor] = None, ld_fn=None):
+def _pixel_planes(input: torch.Tensor, binary_input: Optional[bool], weight: Optional[torch.Tensor] = None, ld_fn=None,
+                  half_ok: bool = False):
     """(NHWC nibble pixel plane of a device activation that is (treated as) exactly +-1 else None, device flag to fold
-    into the bias or None).  ``ld_fn``: words per pixel as a function of the channel count (default ops.pixel_ld_nib)."""
-    if input.dtype != torch.float32 or input.dim() != 4 or input.numel() == 0:
+    into the bias or None).  ``ld_fn``: words per pixel as a function of the channel count (default ops.pixel_ld_nib);
+    ``half_ok``: as in ``activation_planes``."""
+    if input.dtype not in (ops.PACK_DTYPES if half_ok else (torch.float32,)) or input.dim() != 4 or input.numel() == 0:
         return None, None
     ld_fn = ld_fn or ops.pixel_ld_nib
     tagged = packed.lookup(input, packed.NHWC)
@@ -380,7 +455,7 @@ def _pixel_planes(input: torch.Tensor, binary_input: Optional[bool], weight: Opt
 def quant_conv2d_forward(input, weight, bias, stride, padding, dilation, groups, kind: str,
                          weight_q: Optional[torch.Tensor] = None, weight_planes=None,
                          binary_input: Optional[bool] = None, padding_mode: str = "zeros",
-                         weight_triples_fn=None, epi=None):
+                         weight_triples_fn=None, epi=None, half_ok: bool = False):
     """conv2d(input, Q(weight), bias, ...).
 
     ``epi`` = (alpha, beta) (inference fusion, layers/fused.py): the conv does not write fp32 but the
@@ -393,19 +468,29 @@ def quant_conv2d_forward(input, weight, bias, stride, padding, dilation, groups,
     conv library on the exact +-1/0 weight image."""
     packable = (input.is_cuda and groups == 1 and padding_mode == "zeros" and input.dim() == 4
                 and not isinstance(padding, str))
+    # ``half_ok`` (the sign layers' half route): a bf16 / fp16 +-1 activation is packed and the result has its dtype
+    odt = input.dtype if (half_ok and input.is_cuda and input.dtype in ops.HALF_DTYPES) else None
+    if odt is not None and epi is not None:
+        raise ValueError("the threshold / code epilogues take fp32 activations")
+    binary_input, hint_flag = split_hint(binary_input)
     if packable:
-        px, flag = _pixel_planes(input, binary_input, weight)
+        px, flag = _pixel_planes(input, binary_input, weight, half_ok=odt is not None)
         if px is not None:
+            flag = hint_flag if flag is None else flag
+            if odt is not None:
+                bias = half_bias(bias, odt)
             bias = poison_bias(bias, flag, int(weight.shape[0]), input.device)
             wq = weight_q if weight_q is not None else weight
             wp = weight_planes if isinstance(weight_planes, ops.NibPlanes) else ops.pack_conv_weight_nib(wq, kind)
             N, C, H, W = input.shape
             kh, kw = int(weight.shape[2]), int(weight.shape[3])
-            y2 = ops.conv2d_nib(px, (N, C, H, W), wp, (kh, kw), bias, stride, padding, dilation, epi=epi)
+            y2 = ops.conv2d_nib(px, (N, C, H, W), wp, (kh, kw), bias, stride, padding, dilation, epi=epi, out_dtype=odt)
             Ho, Wo = ops.conv_out_hw(H, W, kh, kw, stride, padding, dilation)
             if epi is not None:
                 return y2, (N, int(weight.shape[0]), Ho, Wo)
             return nchw_result(y2, input, N, Ho, Wo, weight.shape[0])
+    if odt is not None:
+        raise RuntimeError("a half-precision activation that is not +-1 has no packed route: the layers send it to the torch expression")
     if packable and _cfg("FLOAT_PATH") == "bf16x3" and input.dtype == torch.float32 and input.numel() > 0:
         # real-valued activation (first layer): exact bf16 triples + implicit-GEMM conv on the bf16
         # matrix cores; the quantisers are idempotent so an explicit quantised image is packed the same way
@@ -682,14 +767,15 @@ class QuantConv2dFn(QtFunction):
     @staticmethod
     def forward(ctx, input, weight, bias, kind, weight_q, binary_input, conv_args):
         ctx.kind, ctx.conv_args, ctx.has_bias = kind, conv_args, bias is not None
+        ctx.bias_dtype = bias.dtype if bias is not None else None
         ctx.save_for_backward(input, weight, weight_q)
         stride, padding, dilation, groups = conv_args
         # +-1 activation known without a device check (tag of a quantiser, or the layer's binary_input hint)?
-        ctx.x_is_pm1 = bool(binary_input) or (input.is_cuda and input.dtype == torch.float32 and input.dim() == 4
+        ctx.x_is_pm1 = bool(split_hint(binary_input)[0]) or (input.is_cuda and input.dtype in ops.PACK_DTYPES and input.dim() == 4
                                               and packed.lookup(input, packed.NHWC) is not None)
         clear_last_detection()
         out = quant_conv2d_forward(input, weight, bias, stride, padding, dilation, groups, kind,
-                                   weight_q=weight_q, binary_input=binary_input)
+                                   weight_q=weight_q, binary_input=binary_input, half_ok=True)
         if not ctx.x_is_pm1 and binary_input is None and input.is_cuda and input.dim() == 4:
             # un-tagged activation THIS forward detected as +-1 (e.g. behind a MaxPool2d): same knowledge for the backward
             ctx.x_is_pm1 = last_detection_said_pm1(input)
@@ -701,6 +787,11 @@ class QuantConv2dFn(QtFunction):
         input, weight, weight_q = ctx.saved_tensors
         stride, padding, dilation, groups = ctx.conv_args
         grad_input = grad_weight = grad_bias = None
+        in_dtype, w_dtype = input.dtype, weight.dtype
+        if grad_output.is_cuda and grad_output.dtype in ops.HALF_DTYPES:
+            # half model: the matrix-core routes contract the upcast operands (exact), their fp32 result is rounded once below
+            grad_output, input, weight = grad_output.float(), input.float(), weight.float()
+            weight_q = weight_q.float() if weight_q is not None else None
         go = _dense(grad_output)
         mfma = (_cfg("BWD_CONV_MFMA") and go.is_cuda and go.dtype == torch.float32 and groups == 1 and not isinstance(padding, str)
                 and go.numel() * weight[0].numel() >= _cfg("BWD_MFMA_MIN_MACS"))
@@ -747,6 +838,12 @@ class QuantConv2dFn(QtFunction):
                 grad_weight = ste_mask(gw.contiguous(), weight)
         if want_bias:
             grad_bias = bias_by_product[0] if bias_by_product else go.sum((0, 2, 3))
+        if grad_input is not None and grad_input.dtype != in_dtype:
+            grad_input = grad_input.to(in_dtype)
+        if grad_weight is not None and grad_weight.dtype != w_dtype:
+            grad_weight = grad_weight.to(w_dtype)
+        if grad_bias is not None and grad_bias.dtype != ctx.bias_dtype:
+            grad_bias = grad_bias.to(ctx.bias_dtype)
         return grad_input, grad_weight, grad_bias, None, None, None, None
 
 
@@ -1672,13 +1769,14 @@ class QuantLinearFn(QtFunction):
     def forward(ctx, input, weight, bias, kind, weight_q, binary_input):
         ctx.kind = kind
         ctx.has_bias = bias is not None
+        ctx.bias_dtype = bias.dtype if bias is not None else None
         # a stochastic draw must be kept; the deterministic image is recomputed in backward
         ctx.save_for_backward(input, weight, weight_q)
         # +-1 activation known without a device check (tag of a quantiser, or the layer's binary_input hint)?
-        ctx.x_is_pm1 = bool(binary_input) or (input.is_cuda and input.dtype == torch.float32
+        ctx.x_is_pm1 = bool(split_hint(binary_input)[0]) or (input.is_cuda and input.dtype in ops.PACK_DTYPES
                                               and packed.lookup(input, packed.ROWS_LAST) is not None)
         clear_last_detection()
-        out = quant_linear_forward(input, weight, bias, kind, weight_q=weight_q, binary_input=binary_input)
+        out = quant_linear_forward(input, weight, bias, kind, weight_q=weight_q, binary_input=binary_input, half_ok=True)
         if not ctx.x_is_pm1 and binary_input is None and input.is_cuda:
             # un-tagged activation THIS forward detected as +-1 (a reshaped / flattened sign image): the backward's g^T . x then
             # runs on the matrix cores as well instead of the dense library
@@ -1691,6 +1789,12 @@ class QuantLinearFn(QtFunction):
         input, weight, weight_q = ctx.saved_tensors
         g2 = grad_output.reshape(-1, grad_output.shape[-1])
         grad_input = grad_weight = grad_bias = None
+        in_dtype, w_dtype = input.dtype, weight.dtype
+        if g2.is_cuda and g2.dtype in ops.HALF_DTYPES:
+            # half model: a half value is exact in fp32, so the matrix-core routes below contract the upcast operands and their fp32
+            # result is rounded once to the dtype autograd expects (input's / the parameter's)
+            g2, input, weight = g2.float(), input.float(), weight.float()
+            weight_q = weight_q.float() if weight_q is not None else None
         if ctx.needs_input_grad[0]:
             Nf, Kf = int(weight.shape[0]), int(weight[0].numel())
             if (_cfg("LINEAR_GRAD_X_ONE_PACK") and weight_q is None and ctx.kind in ("binary", "ternary") and g2.is_cuda and g2.dtype == torch.float32
@@ -1714,4 +1818,10 @@ class QuantLinearFn(QtFunction):
             grad_weight = ste_mask(gw, weight)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             grad_bias = g2.sum(0)
+        if grad_input is not None and grad_input.dtype != in_dtype:
+            grad_input = grad_input.to(in_dtype)
+        if grad_weight is not None and grad_weight.dtype != w_dtype:
+            grad_weight = grad_weight.to(w_dtype)
+        if grad_bias is not None and grad_bias.dtype != ctx.bias_dtype:
+            grad_bias = grad_bias.to(ctx.bias_dtype)
         return grad_input, grad_weight, grad_bias, None, None, None

@@ -15,8 +15,9 @@ _warnings.simplefilter("always", DeprecationWarning)
 
 
 def _binarize_and_tag(input: torch.Tensor) -> torch.Tensor:
-    """safeSign(input); on the GPU the sign plane is produced in the same pass and attached."""
-    if input.is_cuda and input.dtype == torch.float32 and input.dim() >= 2 and input.numel() > 0:
+    """safeSign(input); on the GPU the sign plane is produced in the same pass and attached (fp32, bf16 and fp16 tensors: the
+    image has the input's dtype)."""
+    if input.is_cuda and input.dtype in ops.PACK_DTYPES and input.dim() >= 2 and input.numel() > 0:
         if input.dim() == 4 and input.is_contiguous(memory_format=torch.channels_last) \
                 and not input.is_contiguous():
             # NHWC storage: pack the channel dimension (what a binarised conv consumes)

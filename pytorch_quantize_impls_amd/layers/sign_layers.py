@@ -42,6 +42,10 @@ class _SignLinear(EvalSwapMixin, torch.nn.Linear, QLayer):
     def _forward_impl(self, input):
         if isinstance(input, _PackedActivation):
             return _fused.packed_linear(self, input, self.kind)
+        if _fused.half_route(input, self.weight):
+            y = self._half_forward(input)         # bf16 / fp16 activation that is (treated as) +-1: the packed routes
+            if y is not None:
+                return y
         if not input.is_cuda or input.dtype != torch.float32 or self.weight.dtype != torch.float32:
             # host tensors, and device models in half / bfloat16 / double: the reference expression in torch
             _fused.note_library_path(input, "non-fp32 dtype")
@@ -52,6 +56,30 @@ class _SignLinear(EvalSwapMixin, torch.nn.Linear, QLayer):
             return _fused.QuantLinearFn.apply(input, self.weight, self.bias, self.kind, wq, self.binary_input)
         # eval: weight already holds the quantised image; planes are cached
         return self._eval_forward(input)
+
+    def _half_forward(self, input):
+        """bf16 / fp16 device activation (``_fused.half_route``): the packed routes when it is tagged, hinted or detected as +-1 —
+        result in the activation's dtype, the exact sum + bias rounded once — else None (real-valued half activations and
+        off-grid eval weights keep the counted torch expression below)."""
+        from ..packed import ROWS_LAST
+        kind = self.kind
+        pm1 = _fused.half_gate(input, self.weight, self.binary_input, ROWS_LAST)     # True, or the device flag of a remembered verdict
+        if pm1 is False:
+            return None
+        if self.training:
+            wq = None if self.deterministic else self._op.apply(self.weight.detach())
+            return _fused.QuantLinearFn.apply(input, self.weight, self.bias, kind, wq, pm1)
+        if not self._eval_on_grid():
+            return None
+        if _fused.autograd_records(input, self.weight):      # the training node on the stored image (see _eval_forward)
+            return _fused.QuantLinearFn.apply(input, self.weight, self.bias, kind, self.weight.detach(), pm1)
+        K, N = input.shape[-1], self.weight.shape[0]
+        impl = _fused.ops.select_gemm_impl(_fused._cfg("GEMM_IMPL"), input.numel() // max(K, 1), N, K)
+        hint, flag = _fused.split_hint(pm1)
+        xp, _ = _fused.activation_planes(input, hint, impl, self.weight, half_ok=True)
+        wp = self._eval_planes(lambda w2: _fused.pack_weight(w2, kind, impl), key=impl)
+        bias = _fused.poison_bias(_fused.half_bias(self.bias, input.dtype), flag, N, input.device)
+        return _fused.ops.packed_gemm(xp, wp, bias, impl=impl, out_dtype=input.dtype).view(*input.shape[:-1], N)
 
     def _eval_forward(self, input):
         """Eval-mode forward of a device layer: F.linear(input, weight, bias) (binary_layers.py:46) with the packed path when
@@ -123,6 +151,30 @@ class _SignConv2d(EvalSwapMixin, torch.nn.Conv2d, QLayer):
             return tuple(ws.shape), ops.pack_conv_weight_bf16x3(ws, "sign", terms=terms)
         return self._eval_planes(build, key=f"conv_split{terms}_s2d")
 
+    def _half_forward(self, input):
+        """bf16 / fp16 device activation (``_fused.half_route``) that is tagged, hinted or detected as +-1: the implicit-GEMM conv
+        on fp4 planes with the result in the activation's dtype (the exact sum + bias rounded once); None for everything the
+        packed conv does not take (real-valued activations, grouped convs, non-zero padding modes, off-grid eval weights), which
+        keeps the counted torch expression below.  Never deferred: the modules between the layers stay torch ops in half."""
+        from ..packed import NHWC
+        if self.groups != 1 or self.padding_mode != "zeros" or input.dim() != 4 or isinstance(self.padding, str):
+            return None
+        kind = self.kind
+        args = (self.stride, self.padding, self.dilation, self.groups)
+        pm1 = _fused.half_gate(input, self.weight, self.binary_input, NHWC)          # True, or the device flag of a remembered verdict
+        if pm1 is False:
+            return None
+        if self.training:
+            wq = None if self.deterministic else self._op.apply(self.weight.detach())
+            return _fused.QuantConv2dFn.apply(input, self.weight, self.bias, kind, wq, pm1, args)
+        if not self._eval_on_grid():
+            return None
+        if _fused.autograd_records(input, self.weight):
+            return _fused.QuantConv2dFn.apply(input, self.weight, self.bias, kind, self.weight.detach(), pm1, args)
+        wp = self._eval_planes(lambda _w2: _fused.ops.pack_conv_weight_nib(self.weight.detach(), kind), key="conv_nib")
+        return _fused.quant_conv2d_forward(input, self.weight, self.bias, *args, kind, weight_q=self.weight, weight_planes=wp,
+                                           binary_input=pm1, padding_mode=self.padding_mode, half_ok=True)
+
     def forward(self, input):
         """Eval mode without autograd on a HIP device: returns a deferred activation (``lazy.LazyActivation``: a Tensor
         that runs this conv fused with the BatchNorm / pooling / Hardtanh / BinaryConnect modules that follow it, or
@@ -133,6 +185,10 @@ class _SignConv2d(EvalSwapMixin, torch.nn.Conv2d, QLayer):
         kind = self.kind
         if isinstance(input, _PackedActivation):
             return _fused.packed_conv2d(self, input, kind)
+        if _fused.half_route(input, self.weight):
+            y = self._half_forward(input)         # bf16 / fp16 activation that is (treated as) +-1: the packed routes
+            if y is not None:
+                return y
         if not input.is_cuda or input.dtype != torch.float32 or self.weight.dtype != torch.float32:
             _fused.note_library_path(input, "non-fp32 dtype")
             w = self._op.apply(self.weight) if self.training else self.weight

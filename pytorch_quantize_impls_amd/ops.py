@@ -154,7 +154,7 @@ class NibEpilogue:
 
 
 def _conv_implicit(elem: int, pixels_words: torch.Tensor, N, H, W, Cw, kh, kw, geom, wmat: torch.Tensor,
-                   ldw_words: int, bias, scale: float, scale_dev, Cout: int, epi=None, in_halo=(0, 0)):
+                   ldw_words: int, bias, scale: float, scale_dev, Cout: int, epi=None, in_halo=(0, 0), out_dtype=None):
     """qt_conv2d_implicit; returns None if the shape is outside its limits (caller falls back).
     ``epi`` = (alpha, beta): threshold-bit epilogue (qt_conv2d_implicit_bits) — returns the BitPlanes of
     [(acc + bias) * alpha + beta < 0] per output pixel instead of the fp32 result."""
@@ -171,6 +171,16 @@ def _conv_implicit(elem: int, pixels_words: torch.Tensor, N, H, W, Cw, kh, kw, g
         return None                      # the caller strips the halo
     dev = pixels_words.device
     I = int
+    odt = _half_out(out_dtype)
+    if odt is not None:
+        # half result (fp4 planes, plain output): the conv kernels' own epilogue rounds once and stores bf16 / fp16
+        if elem != 0 or epi is not None or hy or hx or float(scale) != 1.0 or scale_dev is not None:
+            raise ValueError("the half-precision conv output exists for +-1 / 0 nibble planes with the plain epilogue")
+        y = torch.empty((M, Cout), dtype=odt, device=dev)
+        with _on(dev):
+            _lib.call("qt_conv2d_implicit_h", _p(pixels_words), I(N), I(H), I(W), I(Cw), I(kh), I(kw), I(sh), I(sw), I(ph), I(pw),
+                      I(dh), I(dw), _p(wmat), I(ldw_words), _p(bias), _p(y), _DTYPE_CODE[odt], I(Cout), I(Cout), _stream(dev))
+        return y
     head = (int(elem), _p(pixels_words), I(N), I(H), I(W), I(Cw), I(kh), I(kw), I(sh), I(sw), I(ph), I(pw),
             I(dh), I(dw), _p(wmat), I(ldw_words), _p(bias), float(float(scale)),
             _p(_require(scale_dev, "scale_dev").reshape(1) if scale_dev is not None else None))
@@ -303,6 +313,28 @@ def _require(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
     if t.dtype != dtype:
         raise TypeError(f"{name}: expected dtype {dtype}, got {t.dtype}")
     return t
+
+
+#: half-precision element types of the "_h" entry points (include/qt_hip.h: QT_DTYPE_BF16 / QT_DTYPE_F16)
+HALF_DTYPES = (torch.bfloat16, torch.float16)
+_DTYPE_CODE = {torch.bfloat16: 1, torch.float16: 2}
+PACK_DTYPES = (torch.float32,) + HALF_DTYPES
+
+
+def _require_packable(t: torch.Tensor, name: str) -> torch.Tensor:
+    """A device tensor the operand packers read: fp32 (the "_f32" entry points) or bf16 / fp16 (the "_h" ones)."""
+    if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in HALF_DTYPES:
+        return t
+    return _require(t, name)
+
+
+def _half_out(dtype) -> Optional[torch.dtype]:
+    """None for an fp32 result, the dtype for a bf16 / fp16 one; anything else is an error."""
+    if dtype is None or dtype == torch.float32:
+        return None
+    if dtype not in HALF_DTYPES:
+        raise TypeError(f"result dtype must be float32, bfloat16 or float16, got {dtype}")
+    return dtype
 
 
 def packed_ld(K: int) -> int:
@@ -628,18 +660,22 @@ def _as_rows(x: torch.Tensor) -> torch.Tensor:
 def sign_pack(x: torch.Tensor, want_f32: bool = False) -> Tuple[BitPlanes, Optional[torch.Tensor]]:
     """Sign plane of safeSign(x) packed along the last dimension.
 
-    Returns (planes, y) where y is the +-1 fp32 image (same shape as x) when ``want_f32``.
+    Returns (planes, y) where y is the +-1 image (same shape and dtype as x: fp32, bf16 or fp16) when ``want_f32``.
     """
-    _require(x, "input")
+    _require_packable(x, "input")
     x2 = _as_rows(x)
     rows, K = int(x2.shape[0]), int(x2.shape[1])
     ld = packed_ld(K)
     plane = torch.empty((rows, ld), dtype=torch.int32, device=x.device)
-    y = torch.empty((rows, K), dtype=torch.float32, device=x.device) if want_f32 else None
+    y = torch.empty((rows, K), dtype=x.dtype, device=x.device) if want_f32 else None
     with _on(x.device):
-        _lib.call("qt_sign_pack_f32", _p(x2), int(x2.stride(0) if rows > 1 else max(K, 1)),
-                  _p(plane), int(ld), _p(y), int(K), int(rows),
-                  int(K), _stream(x.device))
+        if x.dtype in HALF_DTYPES:
+            _lib.call("qt_sign_pack_h", _p(x2), _DTYPE_CODE[x.dtype], int(x2.stride(0) if rows > 1 else max(K, 1)),
+                      _p(plane), int(ld), _p(y), int(K), int(rows), int(K), _stream(x.device))
+        else:
+            _lib.call("qt_sign_pack_f32", _p(x2), int(x2.stride(0) if rows > 1 else max(K, 1)),
+                      _p(plane), int(ld), _p(y), int(K), int(rows),
+                      int(K), _stream(x.device))
     if y is not None:
         y = y.view(x.shape)
     return BitPlanes(sign=plane, rows=rows, K=K), y
@@ -647,16 +683,20 @@ def sign_pack(x: torch.Tensor, want_f32: bool = False) -> Tuple[BitPlanes, Optio
 
 def ternary_pack(x: torch.Tensor) -> BitPlanes:
     """Mask + sign planes of TernaryConnectDeterministic(x), packed along the last dimension."""
-    _require(x, "input")
+    _require_packable(x, "input")
     x2 = _as_rows(x)
     rows, K = int(x2.shape[0]), int(x2.shape[1])
     ld = packed_ld(K)
     mask = torch.empty((rows, ld), dtype=torch.int32, device=x.device)
     sign = torch.empty((rows, ld), dtype=torch.int32, device=x.device)
     with _on(x.device):
-        _lib.call("qt_ternary_pack_f32", _p(x2), int(x2.stride(0) if rows > 1 else max(K, 1)),
-                  _p(mask), _p(sign), int(ld), int(rows), int(K),
-                  _stream(x.device))
+        if x.dtype in HALF_DTYPES:
+            _lib.call("qt_ternary_pack_h", _p(x2), _DTYPE_CODE[x.dtype], int(x2.stride(0) if rows > 1 else max(K, 1)),
+                      _p(mask), _p(sign), int(ld), int(rows), int(K), _stream(x.device))
+        else:
+            _lib.call("qt_ternary_pack_f32", _p(x2), int(x2.stride(0) if rows > 1 else max(K, 1)),
+                      _p(mask), _p(sign), int(ld), int(rows), int(K),
+                      _stream(x.device))
     return BitPlanes(sign=sign, rows=rows, K=K, mask=mask)
 
 
@@ -702,13 +742,16 @@ def pool_affine_sign_pack(x: torch.Tensor, alpha: torch.Tensor, beta: torch.Tens
 def check_pm1(x: torch.Tensor, limit: Optional[int] = None) -> torch.Tensor:
     """Device flag (int32 scalar tensor): non-zero iff some element of x (of its first ``limit``
     elements in storage order) is not exactly +-1."""
-    x = _require(x, "input")
+    x = _require_packable(x, "input")
     if not (x.is_contiguous() or (x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last))):
         x = x.contiguous()
     n = x.numel() if limit is None else min(int(limit), x.numel())
     flag = torch.zeros((1,), dtype=torch.int32, device=x.device)
     with _on(x.device):
-        _lib.call("qt_check_pm1_f32", _p(x), int(n), _p(flag), _stream(x.device))
+        if x.dtype in HALF_DTYPES:
+            _lib.call("qt_check_pm1_h", _p(x), _DTYPE_CODE[x.dtype], int(n), _p(flag), _stream(x.device))
+        else:
+            _lib.call("qt_check_pm1_f32", _p(x), int(n), _p(flag), _stream(x.device))
     return flag
 
 
@@ -728,6 +771,8 @@ def is_pm1(x: torch.Tensor) -> bool:
 def _check_bias(bias, N, device):
     if bias is None:
         return None
+    if isinstance(bias, torch.Tensor) and bias.dtype in HALF_DTYPES:
+        bias = bias.detach().float()            # the epilogues add the bias in fp32 (a half value is exact there)
     bias = _require(bias, "bias").contiguous()
     if bias.numel() != N or bias.device != device:
         raise ValueError("bias must be a length-N fp32 tensor on the same device")
@@ -741,7 +786,7 @@ CONV_VARIANT = 0
 
 
 def xnor_gemm(x: BitPlanes, w: BitPlanes, bias: Optional[torch.Tensor] = None,
-              out: Optional[torch.Tensor] = None, variant: Optional[int] = None) -> torch.Tensor:
+              out: Optional[torch.Tensor] = None, variant: Optional[int] = None, out_dtype=None) -> torch.Tensor:
     """Y[M,N] = sum_k x[m,k]*w[n,k] (+ bias) for +-1 operands given as sign planes.  ``variant``: force one of the popcount kernels
     (1 = tiled, 2 = skinny, 3 = streaming) for this call; default: the library's own choice (POPC_VARIANT, a tools-only default)."""
     if x.K != w.K:
@@ -761,11 +806,12 @@ def xnor_gemm(x: BitPlanes, w: BitPlanes, bias: Optional[torch.Tensor] = None,
             _lib.call("qt_xnor_gemm_variant", int(v), *args)
         else:
             _lib.call("qt_xnor_gemm", *args)
-    return out
+    # half result: the popcount kernels (latency-bound shapes) keep their fp32 store; ONE round-to-nearest-even conversion follows
+    return out if _half_out(out_dtype) is None else out.to(out_dtype)
 
 
 def tern_gemm(x: BitPlanes, w: BitPlanes, bias: Optional[torch.Tensor] = None,
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+              out: Optional[torch.Tensor] = None, out_dtype=None) -> torch.Tensor:
     """Y[M,N] = sum_k x[m,k]*w[n,k] (+ bias): +-1 activations (sign plane) x ternary weights."""
     if x.K != w.K:
         raise ValueError(f"K mismatch: activations {x.K} vs weights {w.K}")
@@ -783,7 +829,7 @@ def tern_gemm(x: BitPlanes, w: BitPlanes, bias: Optional[torch.Tensor] = None,
             _lib.call("qt_tern_gemm_variant", int(_cfg("POPC_VARIANT")), *args)
         else:
             _lib.call("qt_tern_gemm", *args)
-    return out
+    return out if _half_out(out_dtype) is None else out.to(out_dtype)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -814,15 +860,25 @@ class NibPlanes:
         return self.words.device
 
 
+_NIB_PACK_H = {"qt_sign_pack_nib_f32": "qt_sign_pack_nib_h", "qt_ternary_pack_nib_f32": "qt_ternary_pack_nib_h"}
+
+
 def _nib_pack(entry: str, x: torch.Tensor, ld: Optional[int] = None) -> NibPlanes:
-    _require(x, "input")
+    if entry in _NIB_PACK_H:
+        _require_packable(x, "input")
+    else:
+        _require(x, "input")
     x2 = _as_rows(x)
     rows, K = int(x2.shape[0]), int(x2.shape[1])
     ld = packed_ld_nib(K) if ld is None else int(ld)
     words = torch.empty((rows, ld), dtype=torch.int32, device=x.device)
     with _on(x.device):
-        _lib.call(entry, _p(x2), int(x2.stride(0) if rows > 1 else max(K, 1)), _p(words),
-                  int(ld), int(rows), int(K), _stream(x.device))
+        if x.dtype in HALF_DTYPES:
+            _lib.call(_NIB_PACK_H[entry], _p(x2), _DTYPE_CODE[x.dtype], int(x2.stride(0) if rows > 1 else max(K, 1)), _p(words),
+                      int(ld), int(rows), int(K), _stream(x.device))
+        else:
+            _lib.call(entry, _p(x2), int(x2.stride(0) if rows > 1 else max(K, 1)), _p(words),
+                      int(ld), int(rows), int(K), _stream(x.device))
     return NibPlanes(words=words, rows=rows, K=K)
 
 
@@ -916,14 +972,25 @@ def bits_to_nib_pad(planes: BitPlanes, N: int, H: int, W: int, padding, ld: Opti
 
 
 def nib_gemm(x: NibPlanes, w: NibPlanes, bias: Optional[torch.Tensor] = None,
-             out: Optional[torch.Tensor] = None, variant: Optional[int] = None) -> torch.Tensor:
+             out: Optional[torch.Tensor] = None, variant: Optional[int] = None, out_dtype=None) -> torch.Tensor:
     """Y[M,N] = sum_k x[m,k]*w[n,k] (+ bias) on the matrix cores; bit-identical to the popcount
-    GEMMs.  ``variant`` selects an explicit kernel configuration (tuning only)."""
+    GEMMs.  ``variant`` selects an explicit kernel configuration (tuning only).  ``out_dtype`` = torch.bfloat16 / float16:
+    the kernel's epilogue rounds the fp32 sum + bias once, to nearest even, and stores the half result itself (qt_nib_gemm_h)."""
     if x.K != w.K:
         raise ValueError(f"K mismatch: activations {x.K} vs weights {w.K}")
     M, N, K = x.rows, w.rows, x.K
     dev = x.device
     bias = _check_bias(bias, N, dev)
+    odt = _half_out(out_dtype if out is None else out.dtype)
+    if odt is not None:
+        if variant is not None:
+            raise ValueError("explicit kernel variants exist for the fp32 result only")
+        if out is None:
+            out = torch.empty((M, N), dtype=odt, device=dev)
+        with _on(dev):
+            _lib.call("qt_nib_gemm_h", _p(x.words), int(x.ld), _p(w.words), int(w.ld), _p(bias), _p(out), _DTYPE_CODE[odt],
+                      int(out.stride(0) if M > 1 else max(N, 1)), int(M), int(N), int(K), _stream(dev))
+        return out
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=dev)
     args = (_p(x.words), int(x.ld), _p(w.words), int(w.ld), _p(bias), _p(out),
@@ -1318,10 +1385,13 @@ def conv_out_hw(H, W, kh, kw, stride, padding, dilation):
 
 
 def pack_conv_weight_nib(weight: torch.Tensor, kind: str, cw: Optional[int] = None) -> NibPlanes:
-    """[Cout, Cin, kh, kw] fp32 -> nibble plane [Cout, kh*kw*Cw] (tap-major, channels inside a tap,
-    Cw words per tap = pixel_ld_nib(Cin), or ``cw``), row stride padded to a whole GEMM stage.  ``kind``: "binary" (safeSign),
-    "ternary", or "sign" (torch.sign: the XNOR-Net weight image)."""
-    _require(weight, "weight")
+    """[Cout, Cin, kh, kw] fp32 (bf16 / fp16 for "binary" / "ternary") -> nibble plane [Cout, kh*kw*Cw] (tap-major, channels
+    inside a tap, Cw words per tap = pixel_ld_nib(Cin), or ``cw``), row stride padded to a whole GEMM stage.  ``kind``: "binary"
+    (safeSign), "ternary", or "sign" (torch.sign: the XNOR-Net weight image)."""
+    if kind == "sign":
+        _require(weight, "weight")
+    else:
+        _require_packable(weight, "weight")
     Cout, Cin, kh, kw = (int(v) for v in weight.shape)
     Cw = pixel_ld_nib(Cin) if cw is None else int(cw)
     wt = weight.permute(0, 2, 3, 1).contiguous().view(Cout * kh * kw, Cin)   # plumbing (weights are small)
@@ -1337,8 +1407,9 @@ def pack_conv_weight_nib(weight: torch.Tensor, kind: str, cw: Optional[int] = No
 
 
 def pack_pixels_nib(x: torch.Tensor, ld: Optional[int] = None) -> NibPlanes:
-    """+-1 activation [N, C, H, W] (any memory format) -> NHWC nibble pixel plane [N*H*W, Cw] (Cw = pixel_ld_nib(C) or ``ld``)."""
-    _require(x, "input")
+    """+-1 activation [N, C, H, W] (any memory format; fp32, bf16 or fp16) -> NHWC nibble pixel plane [N*H*W, Cw]
+    (Cw = pixel_ld_nib(C) or ``ld``)."""
+    _require_packable(x, "input")
     N, C, H, W = (int(v) for v in x.shape)
     nhwc = x.permute(0, 2, 3, 1)
     if not nhwc.is_contiguous():
@@ -1500,10 +1571,11 @@ def zero_halo(words: torch.Tensor, N: int, H: int, W: int, halo) -> torch.Tensor
 
 
 def conv2d_nib(pixels: NibPlanes, in_shape, wplanes: NibPlanes, kernel_hw, bias=None, stride=1,
-               padding=0, dilation=1, epi=None):
+               padding=0, dilation=1, epi=None, out_dtype=None):
     """Quantised conv2d on packed operands.  pixels: NHWC nibble pixel plane of the +-1 activation
     (shape ``in_shape`` = (N, C, H, W)); wplanes: pack_conv_weight_nib(...).  Returns the NHWC result
-    as a [N*Ho*Wo, Cout] fp32 matrix."""
+    as a [N*Ho*Wo, Cout] fp32 matrix — or, ``out_dtype`` = torch.bfloat16 / float16 (plain output only), in that dtype: the
+    exact sum + bias rounded once by the kernel's epilogue."""
     N, C, H, W = (int(v) for v in in_shape)
     kh, kw = kernel_hw
     (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
@@ -1522,12 +1594,12 @@ def conv2d_nib(pixels: NibPlanes, in_shape, wplanes: NibPlanes, kernel_hw, bias=
         if _cfg("PAD_PIXEL_PLANES") and (ph or pw):
             pw_, H_, W_, pad_ = pad_pixel_plane(pixels.words, N, H, W, (ph, pw)), H + 2 * ph, W + 2 * pw, (0, 0)
         y = _conv_implicit(0, pw_, N, H_, W_, Cw, kh, kw, ((sh, sw), pad_, (dh, dw)), wplanes.words,
-                           ldA, bias, 1.0, None, Cout, epi=epi)
+                           ldA, bias, 1.0, None, Cout, epi=epi, out_dtype=out_dtype)
         if y is not None:
             return y
     if epi is not None:
         raise ValueError("the threshold-bit epilogue needs the implicit-GEMM conv (shape outside its limits)")
-    y = torch.empty((M, Cout), dtype=torch.float32, device=dev)
+    y = torch.empty((M, Cout), dtype=_half_out(out_dtype) or torch.float32, device=dev)
     rows_per_chunk = max(1, min(M, IM2COL_MAX_BYTES // (ldA * 4)))
     A = torch.empty((rows_per_chunk, ldA), dtype=torch.int32, device=dev)
     I = int
@@ -3346,10 +3418,10 @@ def pack_weights(w: torch.Tensor, kind: str = "binary", impl: str = "valu"):
 def pack_linear_operands(x: torch.Tensor, w: torch.Tensor, kind: str = "binary", impl: str = "valu"):
     """(packed safeSign(x), packed Q(w)) for one quantised linear forward.  On the matrix-core route both nibble
     planes come out of ONE launch (qt_pack_pair_nib_f32)."""
-    if impl != "mfma":
+    if impl != "mfma" or x.dtype != w.dtype:      # (autocast: half activation, fp32 weight — one launch per operand)
         return pack_activations(x, impl), pack_weights(w, kind, impl)
-    _require(x, "input")
-    _require(w, "weight")
+    _require_packable(x, "input")
+    _require_packable(w, "weight")
     x2, w2 = _as_rows(x), _as_rows(w.reshape(w.shape[0], -1))
     (M, K), (N, Kw) = (int(v) for v in x2.shape), (int(v) for v in w2.shape)
     if K != Kw:
@@ -3359,9 +3431,14 @@ def pack_linear_operands(x: torch.Tensor, w: torch.Tensor, kind: str = "binary",
     wn = torch.empty((N, ld), dtype=torch.int32, device=x.device)
     I = int
     with _on(x.device):
-        _lib.call("qt_pack_pair_nib_f32", _p(x2), I(x2.stride(0) if M > 1 else max(K, 1)), _p(xn), I(ld), I(M),
-                  _p(w2), I(w2.stride(0) if N > 1 else max(K, 1)), _p(wn), I(ld), I(N), I(K),
-                  int(0 if kind == "binary" else 1), _stream(x.device))
+        if x.dtype in HALF_DTYPES:
+            _lib.call("qt_pack_pair_nib_h", _p(x2), _DTYPE_CODE[x.dtype], I(x2.stride(0) if M > 1 else max(K, 1)), _p(xn), I(ld),
+                      I(M), _p(w2), I(w2.stride(0) if N > 1 else max(K, 1)), _p(wn), I(ld), I(N), I(K),
+                      int(0 if kind == "binary" else 1), _stream(x.device))
+        else:
+            _lib.call("qt_pack_pair_nib_f32", _p(x2), I(x2.stride(0) if M > 1 else max(K, 1)), _p(xn), I(ld), I(M),
+                      _p(w2), I(w2.stride(0) if N > 1 else max(K, 1)), _p(wn), I(ld), I(N), I(K),
+                      int(0 if kind == "binary" else 1), _stream(x.device))
     return NibPlanes(words=xn, rows=M, K=K), NibPlanes(words=wn, rows=N, K=K)
 
 
@@ -3378,11 +3455,13 @@ def to_impl(planes, impl: str):
     return bits_to_nib(planes)
 
 
-def packed_gemm(x, w, bias=None, out=None, impl: str = "valu") -> torch.Tensor:
+def packed_gemm(x, w, bias=None, out=None, impl: str = "valu", out_dtype=None) -> torch.Tensor:
+    """``out_dtype``: torch.bfloat16 / float16 for a half result (the exact sum + bias rounded once, to nearest even): stored by
+    the matrix-core kernel's own epilogue ('mfma'), or converted once after the popcount kernels' fp32 store ('valu')."""
     if impl == "valu":
-        return tern_gemm(x, w, bias, out) if w.is_ternary else xnor_gemm(x, w, bias, out)
+        return tern_gemm(x, w, bias, out, out_dtype=out_dtype) if w.is_ternary else xnor_gemm(x, w, bias, out, out_dtype=out_dtype)
     if impl == "mfma":
-        return nib_gemm(to_impl(x, "mfma"), to_impl(w, "mfma"), bias, out)
+        return nib_gemm(to_impl(x, "mfma"), to_impl(w, "mfma"), bias, out, out_dtype=out_dtype)
     raise NotImplementedError(impl)
 
 
