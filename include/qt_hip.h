@@ -698,6 +698,36 @@ int qt_bf16x3_pack_conv_levels_f32(const float* w, int64_t stride_o, int64_t str
 int qt_bf16x3_pack_levels_f32(const float* w, int64_t stride_n, int64_t stride_k, int64_t N, int64_t K, int dtype, int fsr,
                               int bit_width, int with_sign, uint16_t* fwd, int64_t fwd_ld_bytes, uint16_t* gx, int64_t gx_ld_bytes,
                               float* wq, qt_stream_t stream);
+/* The same launch with a ONE-TERM forward plane: every level once (2*Cin bytes per tap, same 16-byte tap and 128-byte row
+ * granules), the operand of qt_bf16_gemm / qt_conv2d_implicit(elem = 2) against an activation that is itself exact in bf16
+ * (qt_linlog_quantize_bf16_f32).  gx (three slots: the gradient is real) and wq as above.  Replaces the F.linear / F.conv2d
+ * operand Q(W) of layers/log_lin_layers.py:41,97 for the layers that read the output of nnQuant. */
+int qt_bf16x1_pack_conv_levels_f32(const float* w, int64_t stride_o, int64_t stride_i, int64_t stride_h, int64_t stride_w,
+                                   int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int dtype, int fsr, int bit_width,
+                                   int with_sign, uint16_t* fwd, int64_t fwd_ld_bytes, uint16_t* gx, int64_t gx_ld_bytes,
+                                   float* wq, qt_stream_t stream);
+int qt_bf16x1_pack_levels_f32(const float* w, int64_t stride_n, int64_t stride_k, int64_t N, int64_t K, int dtype, int fsr,
+                              int bit_width, int with_sign, uint16_t* fwd, int64_t fwd_ld_bytes, uint16_t* gx, int64_t gx_ld_bytes,
+                              float* wq, qt_stream_t stream);
+/* ---- Lin / Log quantised activations as one-term bf16 operands (csrc/loglin_act.hip) ----------------------------------------
+ * qt_linlog_quantize_bf16_f32: LinQuant.forward (dtype 0; mode 0 / 1 of qt_lin_quantize_f32: functions/log_lin_connect.py:61-67)
+ * or LogQuant.forward (dtype 1; mode = with_sign of qt_log_quantize_f32: log_lin_connect.py:31-33) of an fp32 tensor
+ * [N][C][H][W] given by its element strides (rows [N][C]: H = W = 1; NCHW; channels-last).  One pass writes
+ *   y:     the fp32 image with x's strides, bit-identical to qt_lin_quantize_f32 / qt_log_quantize_f32;
+ *   plane: [N*H*W][ld_bytes / 2] bf16, element c of row (n, h, w) = the high half of y's pattern (the value itself: a level has
+ *          at most 8 significant bits; a NaN stays a NaN), bytes from 2*C to ld_bytes zero.  ld_bytes: a multiple of 16,
+ *          >= 2*C and <= 128 * ceil(C / 64) (the 16-byte pixel granule of conv operands, the 128-byte row granule of GEMM operands).
+ * Only configurations whose levels are normal bf16 numbers: Lin bit_width <= 8, Log fsr - 2^bit_width >= -126 (else
+ * QT_ERR_UNSUPPORTED).
+ * qt_bf16_pack_check_f32: the same plane of x itself, for an activation that carries no tag of its quantiser (a pooled or
+ * reshaped one); *flag |= 1 when some element is not exact: not finite, low 16 pattern bits set, or a denormal.
+ * qt_check_bf16_exact_f32: that predicate over n contiguous values (the analogue of qt_check_pm1_f32). */
+int qt_linlog_quantize_bf16_f32(const float* x, int64_t stride_n, int64_t stride_c, int64_t stride_h, int64_t stride_w, int64_t N,
+                                int64_t C, int64_t H, int64_t W, int dtype, int fsr, int bit_width, int mode, float* y,
+                                uint16_t* plane, int64_t ld_bytes, qt_stream_t stream);
+int qt_bf16_pack_check_f32(const float* x, int64_t stride_n, int64_t stride_c, int64_t stride_h, int64_t stride_w, int64_t N,
+                           int64_t C, int64_t H, int64_t W, uint16_t* plane, int64_t ld_bytes, int32_t* flag, qt_stream_t stream);
+int qt_check_bf16_exact_f32(const float* x, int64_t n, int32_t* flag, qt_stream_t stream);
 int qt_f16_gemm(const uint32_t* Xh, int64_t ldxp, const uint32_t* Wh, int64_t ldwp, const float* bias, float scale,
                 const float* scale_dev, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, qt_stream_t stream);
 

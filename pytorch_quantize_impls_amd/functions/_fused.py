@@ -42,7 +42,7 @@ LIBRARY_PATHS: Counter = Counter()
 # ---- route switches: module attributes = process-wide DEFAULTS; ``with _fused.scope(GEMM_IMPL="valu"):`` = per-thread overrides ----
 # (same mechanism as ops.scope; the autograd Functions re-open the forward's scope around their backward: functions.common.QtFunction)
 _SCOPED = ("GEMM_IMPL", "DETECT_BINARY_INPUT", "FLOAT_PATH", "PAD_PLANES", "XNOR_LINEAR_DIGITS", "BWD_CONV_MFMA", "LINEAR_GRAD_X_ONE_PACK",
-           "BWD_MFMA_MIN_MACS")
+           "BWD_MFMA_MIN_MACS", "LOGLIN_ONE_TERM")
 _scope_tls = threading.local()
 
 
@@ -263,6 +263,53 @@ def detect_pm1(input: torch.Tensor, weight: Optional[torch.Tensor]):
     if ok and cached:
         return True, ops.check_pm1(input)       # int32[1] on the device, non-zero = some element is not +-1; no sync
     return ok, None
+
+
+def detect_bf16_exact(input: torch.Tensor, weight: Optional[torch.Tensor]):
+    """(one-term bf16 plane or None, device flag to fold into the bias or None) for an UN-TAGGED dense device fp32 activation of a
+    Lin / Log layer: is every element exact in bf16 (a pooled or reshaped output of nnQuant)?  Same store and semantics as
+    ``detect_pm1`` under the question ("bf16", shape[1:]): a negative verdict is cached in every mode (a real-valued first layer
+    asks once); a positive one is re-verified per call ("verify": the check rides in the pack launch, one sync) or trusted
+    ("remember": the pack's flag poisons the output if it ever stops holding).  None when the tensor has no plane geometry."""
+    got = []
+
+    def resolve():
+        got.append(ops.pack_bf16_check(input))
+        return got[0] is not None and int(got[0][1].item()) == 0
+
+    ok, cached = _verdict(weight, ("bf16", tuple(input.shape[1:])), resolve)
+    if not ok:
+        return None, None
+    if cached:
+        res = ops.pack_bf16_check(input)          # no sync: the flag travels with the result
+        return (None, None) if res is None else (res[0], res[1])
+    return got[0][0], None
+
+
+#: Lin / Log layers contract an activation that is exact in bf16 (the tagged output of nnQuant, or a detected one) as ONE bf16
+#: term against a one-term weight plane; grad_W multiplies 3 terms of g with it instead of 6.  False: every activation is split
+#: into three terms, as for a real number (A/B tools, tests).
+LOGLIN_ONE_TERM = True
+
+
+def loglin_act_planes(input: torch.Tensor, weight: Optional[torch.Tensor], layout):
+    """(one-term plane of the activation of a Lin / Log layer or None, device flag or None): the tag of LinQuant / LogQuant
+    (packed.attach_levels) when it fits the consumer's layout, else the detection."""
+    if not _cfg("LOGLIN_ONE_TERM") or not (input.is_cuda and input.dtype == torch.float32 and input.numel() > 0):
+        return None, None
+    x = input.detach()
+    tagged = packed.lookup_levels(input, layout)
+    if tagged is not None:
+        K = input.shape[1] if layout == packed.NHWC else input.shape[-1]
+        if tagged.terms == 1 and tagged.K == K and tagged.rows * K == input.numel():
+            return tagged, None
+    if layout == packed.ROWS_LAST:
+        if not x.is_contiguous():
+            return None, None
+        x = x.view(-1, x.shape[-1])
+    elif x.dim() != 4:
+        return None, None
+    return detect_bf16_exact(x, weight)
 
 
 # ---- half precision (bf16 / fp16) -----------------------------------------------------------------------------------------------
@@ -954,14 +1001,39 @@ def conv_grad_input(input_shape, weight_q, grad_output, stride, padding, dilatio
     return lib_conv2d_input(input_shape, wq, grad_output, stride, padding, dilation, groups)
 
 
+def levels_conv_grad_weight(input, go, weight_shape, stride, padding, dilation):
+    """UN-masked grad wrt the weight of conv2d(x, .) for an activation whose values are exact in bf16 (Lin / Log levels): the
+    sub-routes of ``pm1_conv_grad_weight`` that store the activation as bf16_rn(x) — the pixel-major kernel with the gradient in
+    three exact bf16 terms, the K-major batched GEMMs, the strided 1 x 1 form.  Left out: the pixel-major kernel's fp16 planes
+    (terms = 2; Log levels reach 2^-126) and therefore the strided k x k form, which picks its split by FLOAT_SPLIT, and the
+    swapped conv, which packs sign(x).  None: the caller keeps the real-valued route."""
+    ksz = weight_shape[2:]
+    if ops.wgrad_pm_applicable(input.shape, go.shape, ksz, stride, dilation):
+        gw = ops.conv2d_grad_weight_pm(input, go, ksz, padding, weight=None, terms=3)
+        if gw is not None:
+            return gw
+    if ops.wgrad_gemm_applicable(input.shape, go.shape, ksz, stride, dilation):
+        gw = ops.conv2d_grad_weight_gemm(input, go, ksz, padding, weight=None)
+        if gw is not None:
+            return gw
+    if int(ksz[0]) == 1 and int(ksz[1]) == 1 and ops.wgrad_strided_applicable(input.shape, go.shape, ksz, stride, padding, dilation):
+        return ops.conv2d_grad_weight_strided(input, go, ksz, stride, padding)
+    return None
+
+
 def conv_grad_weight(input, weight_shape, grad_output, stride, padding, dilation, groups, x_is_pm1: bool, bias_by_product=None,
-                     real_any_channels: bool = False):
+                     real_any_channels: bool = False, x_exact_bf16: bool = False):
     """UN-masked grad wrt the weight of conv2d(x, .): +-1 activations on the weight-gradient routes, a real-valued image with few
-    channels (first layers) through the space-to-depth form; anything else on the library, counted."""
+    channels (first layers) through the space-to-depth form; anything else on the library, counted.  ``x_exact_bf16``: the
+    activation holds Lin / Log levels (levels_conv_grad_weight first, then the real-valued routes)."""
     go = _dense(grad_output)
     if (_cfg("BWD_CONV_MFMA") and go.is_cuda and go.dtype == torch.float32 and groups == 1 and not isinstance(padding, str)
             and go.numel() > 0 and input.dtype == torch.float32):
         gw = None
+        if x_exact_bf16:
+            gw = levels_conv_grad_weight(input, go, weight_shape, stride, padding, dilation)
+            if gw is not None:
+                return gw
         if x_is_pm1:
             gw = pm1_conv_grad_weight(input, go, weight_shape, stride, padding, dilation, bias_by_product)
         elif ops.wgrad_s2d_applicable(input.shape, weight_shape[2:], stride, dilation):
@@ -1598,6 +1670,8 @@ class RealConv2dFn(QtFunction):
 # exact three-term splits of the real operand (x, g) against the replicated levels; grad_W multiplies two real operands (six-term
 # routes of RealLinearFn / RealConv2dFn).  Both weight operands come from ONE quantise-and-pack launch per step
 # (ops.pack_levels_bf16x3).  Configurations whose levels are not exact in bf16 train on RealLinearFn / RealConv2dFn instead.
+# An activation that is itself exact in bf16 — the tagged output of nnQuant, or a detected one (loglin_act_planes) — enters the
+# forward as ONE term against a one-term weight plane, and grad_W as the exact operand of three terms of g (LOGLIN_ONE_TERM).
 
 class LogLinLinearFn(QtFunction):
     """F.linear(x, Q(W), b) for a device fp32 x, Q the Lin / Log quantiser ``quant`` = (dtype, fsr, bit_width, with_sign) with
@@ -1607,11 +1681,17 @@ class LogLinLinearFn(QtFunction):
     def forward(ctx, input, weight, bias, quant):
         ctx.has_bias = bias is not None
         ctx.save_for_backward(input)
-        fwd, gx, _ = ops.pack_levels_bf16x3(weight, *quant, grad_x=ctx.needs_input_grad[0])
+        planes, flag = loglin_act_planes(input, weight, packed.ROWS_LAST)
+        ctx.x_exact = planes is not None
+        fwd, gx, _ = ops.pack_levels_bf16x3(weight, *quant, grad_x=ctx.needs_input_grad[0], fwd_terms=1 if ctx.x_exact else 3)
         ctx.gx, ctx.w_shape = gx, tuple(weight.shape)
-        x2 = input.reshape(-1, input.shape[-1])
-        y = ops.float_linear(x2.detach().contiguous(), weight.detach(), "raw", bias.detach() if bias is not None else None,
-                             weight_triples=fwd, terms=3)
+        b = bias.detach() if bias is not None else None
+        if ctx.x_exact:          # one term x one term
+            y = ops.float_linear(None, weight.detach(), "raw", poison_bias(b, flag, weight.shape[0], input.device),
+                                 weight_triples=fwd, planes=planes)
+        else:
+            x2 = input.reshape(-1, input.shape[-1])
+            y = ops.float_linear(x2.detach().contiguous(), weight.detach(), "raw", b, weight_triples=fwd, terms=3)
         return y.view(*input.shape[:-1], weight.shape[0])
 
     @staticmethod
@@ -1625,7 +1705,11 @@ class LogLinLinearFn(QtFunction):
             shape_t = torch.empty((K, N), dtype=torch.float32, device="meta")
             grad_input = ops.float_linear(g2.contiguous(), shape_t, "raw", weight_triples=ctx.gx, terms=3).view(input.shape)
         if ctx.needs_input_grad[1]:
-            grad_weight = real_matmul(g2.t(), x2)
+            if ctx.x_exact and _hip2d(g2, x2):
+                # x is exact in bf16: three exact terms of g^T against the levels replicated ("raw" — pm1_matmul would take sign(x))
+                grad_weight = ops.float_linear(g2.t().contiguous(), x2.detach().t().contiguous(), "raw", terms=3)
+            else:
+                grad_weight = real_matmul(g2.t(), x2)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             grad_bias = g2.sum(0)
         ctx.gx = None
@@ -1651,12 +1735,19 @@ class LogLinConv2dFn(QtFunction):
         ctx.save_for_backward(input, weight)
         want_gx = ctx.needs_input_grad[0]
         routed = _conv_grad_input_route(weight.shape, stride, padding, dilation)
-        fwd, gx, wq = ops.pack_levels_bf16x3(weight, *quant, grad_x=want_gx and routed, image=want_gx and not routed)
+        planes, flag = loglin_act_planes(input, weight, packed.NHWC)
+        ctx.x_exact = planes is not None
+        fwd, gx, wq = ops.pack_levels_bf16x3(weight, *quant, grad_x=want_gx and routed, image=want_gx and not routed,
+                                             fwd_terms=1 if ctx.x_exact else 3)
         ctx.gx, ctx.wq, ctx.w_shape = gx, wq, tuple(weight.shape)
         N, C, H, W = input.shape
         Cout, _, kh, kw = (int(v) for v in weight.shape)
-        y2 = ops.float_conv2d(input.detach(), weight.detach(), "raw", bias.detach() if bias is not None else None, stride, padding,
-                              dilation, weight_triples=fwd, terms=3)
+        b = bias.detach() if bias is not None else None
+        if ctx.x_exact:          # one term x one term on the same implicit GEMM
+            y2 = ops.float_conv2d(None, weight.detach(), "raw", poison_bias(b, flag, Cout, input.device), stride, padding, dilation,
+                                  weight_triples=fwd, pixels=planes, in_shape=tuple(input.shape))
+        else:
+            y2 = ops.float_conv2d(input.detach(), weight.detach(), "raw", b, stride, padding, dilation, weight_triples=fwd, terms=3)
         Ho, Wo = ops.conv_out_hw(H, W, kh, kw, stride, padding, dilation)
         return nchw_result(y2, input, N, Ho, Wo, Cout)
 
@@ -1680,7 +1771,7 @@ class LogLinConv2dFn(QtFunction):
                 grad_input = lib_conv2d_input(input.shape, wq, go, stride, padding, dilation, groups)
         if ctx.needs_input_grad[1]:
             grad_weight = conv_grad_weight(input, ctx.w_shape, go, stride, padding, dilation, groups, x_is_pm1=False,
-                                           real_any_channels=True)
+                                           real_any_channels=True, x_exact_bf16=ctx.x_exact)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             grad_bias = go.sum((0, 2, 3))
         ctx.gx = ctx.wq = None

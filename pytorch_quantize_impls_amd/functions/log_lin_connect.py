@@ -1,6 +1,7 @@
 """Lin / Log fixed-point quantisers of "Convolutional Neural Networks using Logarithmic Data Representation"
 (reference: QuantTorch/functions/log_lin_connect.py).  HIP device tensors go through qt_lin_quantize_f32 /
-qt_log_quantize_f32; CPU tensors evaluate the same expressions in torch.
+qt_log_quantize_f32 — or, when the levels are single bf16 terms, qt_linlog_quantize_bf16_f32, which also writes the one-term
+operand plane of the next Lin / Log layer; CPU tensors evaluate the same expressions in torch.
 
 Upstream defect kept out: ``LinQuant(lin_back=False).backward`` calls ``torch.clamp(Tensor, int, Tensor)``
 (log_lin_connect.py:79), which raises under torch 2.x; here it evaluates the expression that line intends,
@@ -8,7 +9,7 @@ sign(g) * clamp(round(g/step)*step, 0, 2^fsr) (note: negative g therefore yields
 """
 import torch
 
-from .. import ops
+from .. import ops, packed
 from .common import QtFunction, front
 
 
@@ -20,6 +21,20 @@ def _kernel_takes(fsr, bit_width, log):
     """Parameter window of qt_log_quantize_f32 / qt_lin_quantize_f32 (csrc/elementwise.hip); configurations outside it
     (e.g. a 32-bit Log quantiser) run the torch expression on the device, like the reference."""
     return -60 <= fsr <= 60 and 1 <= bit_width <= (16 if log else 32)
+
+
+def _quantize_and_tag(input, dtype, fsr, bit_width, with_sign):
+    """The quantiser on a device fp32 tensor.  When every level is one bf16 term (ops.levels_exact_in_bf16) and the one-term route
+    is on, the same launch writes the plane the next Lin / Log layer contracts and parks it on the result (packed.attach_levels),
+    the way BinaryConnect hands over its sign planes; the returned values are the same bits either way."""
+    from . import _fused
+    if (_fused._cfg("LOGLIN_ONE_TERM") and input.dim() >= 2 and ops.levels_exact_in_bf16(dtype, fsr, bit_width)
+            and not isinstance(input, torch.nn.Parameter)):       # (a parameter is a weight: the layers pack it themselves)
+        y, planes, layout = ops.quantize_levels_bf16(input, dtype, fsr, bit_width, with_sign)
+        return y if planes is None else packed.attach_levels(y, planes, layout)
+    if dtype == "log":
+        return ops.log_quantize(input, fsr, bit_width, with_sign)
+    return ops.lin_quantize(input, fsr, bit_width, 1 if with_sign else 0)
 
 
 def _log_expr(x, fsr, bit_width, with_sign):
@@ -44,7 +59,7 @@ def LogQuant(fsr=7, bit_width=3, with_sign=True, lin_back=True):
         @staticmethod
         def forward(ctx, input):
             if _is_dev(input) and _kernel_takes(fsr, bit_width, True):
-                return ops.log_quantize(input, fsr, bit_width, with_sign)
+                return _quantize_and_tag(input, "log", fsr, bit_width, with_sign)
             return _log_expr(input, fsr, bit_width, with_sign)
 
         @staticmethod
@@ -68,7 +83,7 @@ def LinQuant(fsr=7, bit_width=3, with_sign=True, lin_back=True):
             if bit_width == 32:
                 return input
             if _is_dev(input) and _kernel_takes(fsr, bit_width, False):
-                return ops.lin_quantize(input, fsr, bit_width, 1 if with_sign else 0)
+                return _quantize_and_tag(input, "lin", fsr, bit_width, with_sign)
             return _lin_expr(input, fsr, bit_width, 1 if with_sign else 0)
 
         @staticmethod

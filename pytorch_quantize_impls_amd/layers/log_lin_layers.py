@@ -9,10 +9,14 @@ Under autograd a device fp32 input trains on functions._fused.LogLinLinearFn / L
 weight per step, exact three-term forward and grad_x, six-term grad_W); configurations whose levels are not exact in bf16
 (ops.levels_exact_in_bf16: Lin bit_width > 8, Log levels below 2^-126) on RealLinearFn / RealConv2dFn.  Only grouped convs,
 non-"zeros" padding modes, string padding and non-fp32 dtypes take the (counted) dense library.
+
+An activation that is itself exact in bf16 — the output of nnQuant, which carries its one-term plane as a tag, or a pooled /
+reshaped one that the detection recognises (_fused.loglin_act_planes) — is contracted as ONE bf16 term against a one-term
+weight plane, in training, no-grad and eval mode alike (_fused.LOGLIN_ONE_TERM).
 """
 import torch
 
-from .. import lazy
+from .. import lazy, packed
 from ..functions import _fused, log_lin_connect
 from .common import EvalSwapMixin, QLayer
 
@@ -66,6 +70,20 @@ class LinearQuant(_WeightInit, EvalSwapMixin, torch.nn.Linear, QLayer):
             if _fused.ops.levels_exact_in_bf16(self.qdtype, self.fsr, self.bit_width):
                 return _fused.LogLinLinearFn.apply(input, self.weight, self.bias, (self.qdtype, self.fsr, self.bit_width, True))
             return _fused.RealLinearFn.apply(input, self.weight_op.forward(self.weight), self.bias)
+        if (input.is_cuda and input.dtype == torch.float32 and input.numel() > 0 and self.weight.is_cuda
+                and self.weight.dtype == torch.float32 and not _fused.autograd_records(input, self.weight)
+                and _fused.ops.levels_exact_in_bf16(self.qdtype, self.fsr, self.bit_width)):
+            planes, flag = _fused.loglin_act_planes(input, self.weight, packed.ROWS_LAST)
+            if planes is not None:      # one term x one term; the weight plane comes from the quantise-and-pack launch
+                quant = (self.qdtype, self.fsr, self.bit_width, True)
+                wt = _fused.ops.pack_levels_bf16x3(self.weight, *quant, grad_x=False, fwd_terms=1)[0] if self.training else \
+                    self._eval_planes(lambda _w2: _fused.ops.pack_levels_bf16x3(self.weight, *quant, grad_x=False, fwd_terms=1)[0],
+                                      key="bf16x1_levels")
+                bias = self.bias.detach() if self.bias is not None else None
+                y = _fused.ops.float_linear(None, self.weight.detach(), "raw",
+                                            _fused.poison_bias(bias, flag, self.weight.shape[0], input.device),
+                                            weight_triples=wt, planes=planes)
+                return y.view(*input.shape[:-1], self.weight.shape[0])
         wq = self.weight_op.forward(self.weight)
         if (input.is_cuda and input.dtype == torch.float32 and input.numel() > 0 and _exact_in_bf16(self.qdtype, self.bit_width)
                 and not _fused.autograd_records(input, self.weight)):
@@ -107,6 +125,26 @@ class QuantConv2d(_WeightInit, EvalSwapMixin, torch.nn.Conv2d, QLayer):
                 return _fused.LogLinConv2dFn.apply(input, self.weight, self.bias, quant, args)
             wq = self.weight_op.forward(self.weight) if self.training else self.weight
             return _fused.RealConv2dFn.apply(input, wq, self.bias, args)
+        if (input.is_cuda and input.dtype == torch.float32 and input.numel() > 0 and input.dim() == 4
+                and self.groups == 1 and self.padding_mode == "zeros" and not isinstance(self.padding, str)
+                and self.weight.is_cuda and self.weight.dtype == torch.float32
+                and not _fused.autograd_records(input, self.weight)
+                and _fused.ops.levels_exact_in_bf16(self.qdtype, self.fsr, self.bit_width)):
+            planes, flag = _fused.loglin_act_planes(input, self.weight, packed.NHWC)
+            if planes is not None:      # one term x one term on the implicit GEMM
+                # eval: the swapped weight already holds the levels -> packed as it is (LinQuant(bit_width = 32) = identity)
+                quant = (self.qdtype, self.fsr, self.bit_width, True) if self.training else ("lin", 0, 32, True)
+                wt = _fused.ops.pack_levels_bf16x3(self.weight, *quant, grad_x=False, fwd_terms=1)[0] if self.training else \
+                    self._eval_planes(lambda _w2: _fused.ops.pack_levels_bf16x3(self.weight, *quant, grad_x=False, fwd_terms=1)[0],
+                                      key="conv_bf16x1_levels")
+                N, C, H, W = input.shape
+                Cout, kh, kw = int(self.weight.shape[0]), int(self.weight.shape[2]), int(self.weight.shape[3])
+                bias = self.bias.detach() if self.bias is not None else None
+                y2 = _fused.ops.float_conv2d(None, self.weight.detach(), "raw", _fused.poison_bias(bias, flag, Cout, input.device),
+                                             self.stride, self.padding, self.dilation, weight_triples=wt, pixels=planes,
+                                             in_shape=tuple(input.shape))
+                Ho, Wo = _fused.ops.conv_out_hw(H, W, kh, kw, self.stride, self.padding, self.dilation)
+                return _fused.nchw_result(y2, input, N, Ho, Wo, Cout)
         wq = self.weight_op.forward(self.weight) if self.training else self.weight
         if (input.is_cuda and input.dtype == torch.float32 and input.numel() > 0 and input.dim() == 4
                 and self.groups == 1 and self.padding_mode == "zeros" and not isinstance(self.padding, str)

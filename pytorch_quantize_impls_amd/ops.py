@@ -1934,7 +1934,8 @@ def split_terms(terms: Optional[int] = None) -> int:
 
 
 def triple_ld_bytes(K: int, granule: int = 128, terms: int = 3) -> int:
-    """Row stride in bytes of a bf16 triple (terms = 3: 6 bytes per feature) or fp16 pair (terms = 2: 4 bytes) plane."""
+    """Row stride in bytes of a bf16 triple (terms = 3: 6 bytes per feature), fp16 pair (terms = 2: 4 bytes) or one-term bf16
+    (terms = 1: 2 bytes) plane."""
     return max(granule, (2 * int(terms) * int(K) + granule - 1) // granule * granule)
 
 
@@ -1943,7 +1944,8 @@ class TriplePlanes:
     """Split image of a [rows, K] fp32 matrix for the bf16 / fp16 matrix cores: int16 tensor [rows, ld_bytes/2].
     terms = 3: bf16, element 3k+t is term t of x[k] = hi + mid + lo (activations) or the quantised weight value replicated
     (weights).  terms = 2: fp16, element 2k+t is term t of x[k] / scale[0] (activations; ``scale`` = device fp32 [s, 1/s])
-    or the weight value replicated twice."""
+    or the weight value replicated twice.  terms = 1: bf16, element k is x[k] itself — an operand whose values are exact in bf16
+    (a Lin / Log level: quantize_levels_bf16, pack_bf16_check; the one-term weight plane of pack_levels_bf16x3(fwd_terms=1))."""
     data: torch.Tensor
     rows: int
     K: int
@@ -1974,8 +1976,8 @@ class TriplePlanes:
 
     @property
     def elem(self) -> int:
-        """Element code of the conv / GEMM entry points: 2 = bf16 triples, 3 = fp16 pairs."""
-        return 2 if self.terms == 3 else 3
+        """Element code of the conv / GEMM entry points: 2 = bf16 (triples, or one term), 3 = fp16 pairs."""
+        return 3 if self.terms == 2 else 2
 
 
 _ABS_MEAN_WORK = {}      # (device index, stream handle) -> zero-initialised ticket / partial buffer (the kernel leaves it zero)
@@ -2031,6 +2033,8 @@ def _triple_pack(x: torch.Tensor, mode: int, alpha: Optional[torch.Tensor], ld_b
     x2 = _as_rows(x)
     rows, K = int(x2.shape[0]), int(x2.shape[1])
     terms = 3 if alpha is not None else split_terms(terms)        # the per-feature alpha is folded by the triple kernel only
+    if terms not in (2, 3):
+        raise ValueError(f"a real-valued operand is split into 2 or 3 terms, not {terms} (one-term planes: pack_bf16_check)")
     ld = triple_ld_bytes(K, terms=terms) if ld_bytes is None else int(ld_bytes)
     out = torch.empty((rows, ld // 2), dtype=torch.int16, device=x.device)
     if terms == 2:
@@ -2095,7 +2099,7 @@ def bf16_gemm(x: TriplePlanes, w: TriplePlanes, bias: Optional[torch.Tensor] = N
         else:
             _lib.call("qt_bf16_gemm", _p(x.data), int(x.ld_words), _p(w.data), int(w.ld_words),
                       _p(bias), _p(out), int(out.stride(0) if M > 1 else max(N, 1)), int(M),
-                      int(N), int(3 * x.K), _stream(dev))
+                      int(N), int(x.terms * x.K), _stream(dev))
     return out
 
 
@@ -2165,12 +2169,18 @@ def real_conv2d(x: torch.Tensor, weight: torch.Tensor, bias=None, stride=1, padd
                           bias, 1.0, None, Cout, epi=epi)
 
 
-def float_linear(x: torch.Tensor, weight: torch.Tensor, kind: str, bias=None, alpha=None,
-                 weight_triples: Optional[TriplePlanes] = None, terms: Optional[int] = None) -> torch.Tensor:
+def float_linear(x: Optional[torch.Tensor], weight: torch.Tensor, kind: str, bias=None, alpha=None,
+                 weight_triples: Optional[TriplePlanes] = None, terms: Optional[int] = None,
+                 planes: Optional[TriplePlanes] = None) -> torch.Tensor:
     """y = x . Q(weight)^T (+ bias) for REAL-valued x: Q in {safeSign, ternary, torch.sign}; ``alpha``
     (per input feature) multiplies x first (XNORDense).  fp32-GEMM accuracy on the bf16 matrix cores.  ``terms``: the split
     of x (default FLOAT_SPLIT; 3 = exact, for an x whose ROWS are separate quantities of very different magnitude)."""
     N = weight.shape[0]
+    if planes is not None:
+        # a ready activation plane (terms = 1: values exact in bf16) against the weight plane of the same form; [rows, N] back
+        if weight_triples is None or weight_triples.terms != planes.terms or alpha is not None:
+            raise ValueError("a ready activation plane needs the weight plane of the same number of terms (and no alpha)")
+        return bf16_gemm(planes, weight_triples, bias)
     xp = split_bf16x3(x, alpha, terms=terms)
     wt = weight_triples if (weight_triples is not None and weight_triples.terms == xp.terms) else \
         weight_bf16x3(weight.reshape(N, -1), kind, terms=xp.terms)
@@ -2236,7 +2246,7 @@ def levels_exact_in_bf16(dtype: str, fsr, bit_width) -> bool:
 
 
 def pack_levels_bf16x3(weight: torch.Tensor, dtype: str, fsr: int, bit_width: int, with_sign: bool = True,
-                       forward: bool = True, grad_x: bool = True, image: bool = False):
+                       forward: bool = True, grad_x: bool = True, image: bool = False, fwd_terms: int = 3):
     """Quantise-and-pack of a Lin / Log weight for a training step, one launch (qt_bf16x3_pack_levels_f32 /
     qt_bf16x3_pack_conv_levels_f32): returns (fwd, gx, wq), each None unless asked for.
       * Linear weight [N, K]: fwd = weight_bf16x3(Q(W), "raw", terms=3), gx = weight_bf16x3(Q(W).t(), "raw", terms=3);
@@ -2245,7 +2255,8 @@ def pack_levels_bf16x3(weight: torch.Tensor, dtype: str, fsr: int, bit_width: in
       * wq: the fp32 image Q(W) (the bits of lin_quantize(W, fsr, bit_width, 1 if with_sign else 0) / log_quantize), with the
         weight's strides.
     Q is the quantiser of log_lin_connect.LinQuant / LogQuant; the planes hold bf16_rn(Q(W)), exact when
-    ``levels_exact_in_bf16(dtype, fsr, bit_width)``."""
+    ``levels_exact_in_bf16(dtype, fsr, bit_width)``.  ``fwd_terms`` = 1: fwd holds every level once (qt_bf16x1_pack_levels_f32 /
+    qt_bf16x1_pack_conv_levels_f32) — the operand against a one-term activation plane; gx keeps three slots."""
     _require(weight, "weight")
     if dtype not in _LEVEL_DTYPES:
         raise ValueError(f"dtype must be 'lin' or 'log', got {dtype!r}")
@@ -2260,13 +2271,16 @@ def pack_levels_bf16x3(weight: torch.Tensor, dtype: str, fsr: int, bit_width: in
     Cout, Cin = int(w.shape[0]), int(w.shape[1])
     kh, kw = (int(w.shape[2]), int(w.shape[3])) if conv else (1, 1)
 
-    def plane(rows, chans):
-        kbytes = kh * kw * triple_ld_bytes(chans, 16, 3)
+    if fwd_terms not in (1, 3):
+        raise ValueError(f"fwd_terms must be 1 or 3, got {fwd_terms!r}")
+
+    def plane(rows, chans, terms=3):
+        kbytes = kh * kw * triple_ld_bytes(chans, 16, terms)
         ld = max(128, (kbytes + 127) // 128 * 128)
         data = torch.empty((rows, ld // 2), dtype=torch.int16, device=w.device)
-        return TriplePlanes(data=data, rows=rows, K=kbytes // 6 if conv else chans), ld
+        return TriplePlanes(data=data, rows=rows, K=kbytes // (2 * terms) if conv else chans, terms=terms), ld
 
-    fwd, ld_f = plane(Cout, Cin) if forward else (None, 0)
+    fwd, ld_f = plane(Cout, Cin, int(fwd_terms)) if forward else (None, 0)
     gx, ld_g = plane(Cin, Cout) if grad_x else (None, 0)
     wq = torch.empty_like(w) if image else None
     args = (_p(fwd.data if fwd is not None else None), int(ld_f), _p(gx.data if gx is not None else None), int(ld_g), _p(wq),
@@ -2274,10 +2288,91 @@ def pack_levels_bf16x3(weight: torch.Tensor, dtype: str, fsr: int, bit_width: in
     q = (_LEVEL_DTYPES[dtype], int(fsr), int(bit_width), int(bool(with_sign)))
     with _on(w.device):
         if conv:
-            _lib.call("qt_bf16x3_pack_conv_levels_f32", _p(w), *(int(v) for v in w.stride()), Cout, Cin, kh, kw, *q, *args)
+            _lib.call("qt_bf16x1_pack_conv_levels_f32" if fwd_terms == 1 else "qt_bf16x3_pack_conv_levels_f32", _p(w),
+                      *(int(v) for v in w.stride()), Cout, Cin, kh, kw, *q, *args)
         else:
-            _lib.call("qt_bf16x3_pack_levels_f32", _p(w), int(w.stride(0)), int(w.stride(1)), Cout, Cin, *q, *args)
+            _lib.call("qt_bf16x1_pack_levels_f32" if fwd_terms == 1 else "qt_bf16x3_pack_levels_f32", _p(w), int(w.stride(0)),
+                      int(w.stride(1)), Cout, Cin, *q, *args)
     return fwd, gx, wq
+
+
+# ---- Lin / Log quantised activations as one-term bf16 planes (csrc/loglin_act.hip) -------------------------------------------
+
+def _act_plane_geometry(x: torch.Tensor):
+    """(layout, (N, C, H, W), element strides, ld_bytes) of the one-term plane of a dense fp32 activation, or None when the tensor
+    has no such plane: 4-D (any dense storage) -> the NHWC pixel plane [N*H*W][Cb], 16-byte granule; otherwise a contiguous
+    tensor of >= 2 dimensions -> rows over its last dimension, 128-byte granule."""
+    if x.dim() == 4:
+        if not _storage_dense(x):
+            return None
+        N, C, H, W = (int(v) for v in x.shape)
+        return "nhwc", (N, C, H, W), tuple(int(v) for v in x.stride()), triple_ld_bytes(C, 16, 1)
+    if x.dim() >= 2 and x.is_contiguous():
+        K = int(x.shape[-1])
+        return "rows_last", (x.numel() // K, K, 1, 1), (K, 1, 0, 0), triple_ld_bytes(K, 128, 1)
+    return None
+
+
+def quantize_levels_bf16(x: torch.Tensor, dtype: str, fsr: int, bit_width: int, with_sign: bool = True):
+    """LinQuant / LogQuant forward of a device fp32 activation and its one-term bf16 plane in one launch
+    (qt_linlog_quantize_bf16_f32): returns (y, planes, layout) — y the bits of lin_quantize(x, fsr, bit_width, 1 if with_sign else 0)
+    / log_quantize(x, fsr, bit_width, with_sign) in x's own layout; planes = TriplePlanes(terms=1) of y ("rows_last" /
+    "nhwc": packed.ROWS_LAST / packed.NHWC).  (y, None, None) — the plain quantise kernel — for a tensor without a plane geometry
+    (fewer than 2 dimensions, a non-dense view).  Needs ``levels_exact_in_bf16(dtype, fsr, bit_width)``."""
+    _require(x, "input")
+    if dtype not in _LEVEL_DTYPES:
+        raise ValueError(f"dtype must be 'lin' or 'log', got {dtype!r}")
+    if not levels_exact_in_bf16(dtype, fsr, bit_width):
+        raise ValueError(f"the levels of {dtype}(fsr={fsr}, bit_width={bit_width}) are not single bf16 terms")
+    geo = _act_plane_geometry(x) if x.numel() > 0 and x.data_ptr() % 4 == 0 else None
+    if geo is None:
+        y = lin_quantize(x, fsr, bit_width, 1 if with_sign else 0) if dtype == "lin" else log_quantize(x, fsr, bit_width, with_sign)
+        return y, None, None
+    layout, (N, C, H, W), strides, ld = geo
+    y = torch.empty_like(x)                       # dense input: the same strides
+    if tuple(y.stride()) != tuple(x.stride()):
+        y = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=x.device)
+    plane = torch.empty((N * H * W, ld // 2), dtype=torch.int16, device=x.device)
+    with _on(x.device):
+        _lib.call("qt_linlog_quantize_bf16_f32", _p(x), *strides, N, C, H, W, _LEVEL_DTYPES[dtype], int(fsr), int(bit_width),
+                  int(bool(with_sign)), _p(y), _p(plane), int(ld), _stream(x.device))
+    return y, TriplePlanes(data=plane, rows=N * H * W, K=C, terms=1), layout
+
+
+def pack_bf16_check(x: torch.Tensor, flag: Optional[torch.Tensor] = None):
+    """One-term bf16 plane of a dense device fp32 activation that is BELIEVED to hold values exact in bf16 (qt_bf16_pack_check_f32):
+    (planes, flag, layout) with flag an int32[1] device tensor, non-zero = some element is not exact (not finite, low 16 pattern
+    bits set, or a denormal) — the plane is then not the activation.  None when the tensor has no plane geometry."""
+    _require(x, "input")
+    geo = _act_plane_geometry(x) if x.numel() > 0 and x.data_ptr() % 4 == 0 else None
+    if geo is None:
+        return None
+    layout, (N, C, H, W), strides, ld = geo
+    if flag is None:
+        flag = torch.zeros((1,), dtype=torch.int32, device=x.device)
+    plane = torch.empty((N * H * W, ld // 2), dtype=torch.int16, device=x.device)
+    with _on(x.device):
+        _lib.call("qt_bf16_pack_check_f32", _p(x), *strides, N, C, H, W, _p(plane), int(ld), _p(flag), _stream(x.device))
+    return TriplePlanes(data=plane, rows=N * H * W, K=C, terms=1), flag, layout
+
+
+def check_bf16_exact(x: torch.Tensor) -> torch.Tensor:
+    """int32[1] device flag, non-zero when some element of the fp32 tensor is not exact in bf16 (qt_check_bf16_exact_f32; the
+    analogue of check_pm1).  No host sync."""
+    _require(x, "input")
+    x = x.detach()
+    if not _storage_dense(x):
+        x = x.contiguous()
+    flag = torch.zeros((1,), dtype=torch.int32, device=x.device)
+    if x.numel():
+        with _on(x.device):
+            _lib.call("qt_check_bf16_exact_f32", _p(x), int(x.numel()), _p(flag), _stream(x.device))
+    return flag
+
+
+def is_bf16_exact(x: torch.Tensor) -> bool:
+    """Host answer (one sync): every element is finite, has the low 16 bits of its pattern zero and is zero or a normal number."""
+    return int(check_bf16_exact(x).item()) == 0
 
 
 #: fixed power-of-two scale the first layer's space-to-depth pack speculates with (None / 0: always the separate max|x| pass).
@@ -2354,8 +2449,9 @@ def float_conv2d(x: Optional[torch.Tensor], weight: torch.Tensor, kind: str, bia
     if weight_triples is not None and weight_triples.terms == terms:
         wt = weight_triples
     else:
-        if weight.device.type == "meta":
-            raise ValueError(f"cached weight planes have {weight_triples.terms} terms, the pixel planes {terms}")
+        if weight.device.type == "meta" or terms == 1:
+            raise ValueError(f"weight planes have {weight_triples.terms if weight_triples is not None else 'no'} terms, "
+                             f"the pixel planes {terms}")
         wt = pack_conv_weight_bf16x3(weight, kind, terms=terms)
     Cw, ldA = Cb // 4, wt.ld_words
     M = N * Ho * Wo

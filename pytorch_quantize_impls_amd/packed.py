@@ -20,6 +20,7 @@ from .ops import BitPlanes
 
 _ATTR = "_qt_planes"
 _ATTR_CODES = "_qt_codes"
+_ATTR_LEVELS = "_qt_levels"
 
 ROWS_LAST = "rows_last"  # planes pack the LAST dimension of the (logically row-major) tensor
 NHWC = "nhwc"            # planes pack the channel dimension of an [N,C,H,W] tensor, rows = N*H*W
@@ -58,6 +59,24 @@ def lookup_codes(t: torch.Tensor, layout: str):
     if lay != layout or version != t._version or shape != tuple(t.shape):
         return None
     return codes
+
+
+def attach_levels(t: torch.Tensor, planes, layout: str) -> torch.Tensor:
+    """Same side channel for the one-term bf16 plane (ops.TriplePlanes, terms = 1) that LinQuant / LogQuant produce with their
+    fp32 image (functions/log_lin_connect.py): layout ROWS_LAST (rows over the last dimension) or NHWC (pixel plane)."""
+    if not t.is_inference():
+        setattr(t, _ATTR_LEVELS, (planes, layout, t._version, tuple(t.shape)))
+    return t
+
+
+def lookup_levels(t: torch.Tensor, layout: str):
+    tag = getattr(t, _ATTR_LEVELS, None)
+    if tag is None or t.is_inference():
+        return None
+    planes, lay, version, shape = tag
+    if lay != layout or version != t._version or shape != tuple(t.shape):
+        return None
+    return planes
 
 
 class PackedActivation:
