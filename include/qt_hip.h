@@ -728,6 +728,34 @@ int qt_linlog_quantize_bf16_f32(const float* x, int64_t stride_n, int64_t stride
 int qt_bf16_pack_check_f32(const float* x, int64_t stride_n, int64_t stride_c, int64_t stride_h, int64_t stride_w, int64_t N,
                            int64_t C, int64_t H, int64_t W, uint16_t* plane, int64_t ld_bytes, int32_t* flag, qt_stream_t stream);
 int qt_check_bf16_exact_f32(const float* x, int64_t n, int32_t* flag, qt_stream_t stream);
+/* ---- the deferred inference chain of the Lin / Log family: level planes from layer to layer (lazy.py, kind "levels") ----------
+ * qt_conv2d_implicit_levels: the bf16 implicit conv (elem = 2 of qt_conv2d_implicit; P is a one-term level plane or the three-term
+ * plane of a real image: K counts terms * channels) with the LEVEL EPILOGUE.  Per output element, with v the fp32 value
+ * qt_conv2d_implicit would have stored (bias included):
+ *   t = fma(fl(fl(v - mean_c) * rs_c), bn_weight_c, bn_bias_c)     bn_stats = [mean | rs]: qt_bn_eval_device_f32's expression
+ *   t = relu(t) if relu (NaN stays NaN)
+ *   q = the Lin (dtype 0, mode 0 / 1) or Log (dtype 1, mode = with_sign) quantiser of qt_linlog_quantize_bf16_f32
+ * and the plane element is the high half of q's pattern, as qt_linlog_quantize_bf16_f32 defines it.  plane:
+ * [N][Ho + 2*out_halo_h][Wo + 2*out_halo_w][ld_bytes / 2], ld_bytes = 2*Cout rounded up to 16 (pad zero), border zero: the next
+ * conv's operand with its padding physical.  (in_halo_h, in_halo_w): zero border of P, as in qt_conv2d_implicit_halo.  The tile
+ * configuration is the one qt_conv2d_implicit / _halo picks for the geometry, so v is that call's value bit for bit.
+ * qt_pool_levels_bf16: MaxPool2d(pool_k, pool_s), no padding, floor mode, on a level plane [N][H][W][ld_bytes] -> [N][Ho + 2hy]
+ * [Wo + 2hx][ld_bytes]; compared as floats, NaN propagates (ATen's window order and update rule).  The quantisers are monotone,
+ * so this is the plane of F.max_pool2d of the fp32 image.
+ * qt_bn_relu_linlog_bf16_f32: fp32 [rows][C] (ldx) -> BatchNorm (bn_form 0: the expression above; 1: fma(fl(weight * fl(x - mean)),
+ * rs, bias), the order of the library's kernel for 2-D tensors — the caller's probe decides) -> [relu] -> the quantiser -> the
+ * one-term row plane [rows][ld_bytes / 2] (ld_bytes a multiple of 16, >= 2*C, pad zero) and, when y != NULL, the fp32 image
+ * [rows][ldy]. */
+int qt_conv2d_implicit_levels(const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, int64_t Cw, int64_t in_halo_h, int64_t in_halo_w,
+                              int64_t kh, int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw,
+                              const uint32_t* Wmat, int64_t ldwp, const float* bias, const float* bn_weight, const float* bn_bias,
+                              const float* bn_stats, int relu, int dtype, int fsr, int bit_width, int mode, uint16_t* plane,
+                              int64_t ld_bytes, int64_t Cout, int64_t out_halo_h, int64_t out_halo_w, qt_stream_t stream);
+int qt_pool_levels_bf16(const uint16_t* in_plane, int64_t N, int64_t H, int64_t W, int64_t ld_bytes, int64_t pool_k, int64_t pool_s,
+                        uint16_t* out_plane, int64_t out_halo_h, int64_t out_halo_w, qt_stream_t stream);
+int qt_bn_relu_linlog_bf16_f32(const float* x, int64_t ldx, const float* weight, const float* bias, const float* bn_stats, int bn_form,
+                               int relu, int dtype, int fsr, int bit_width, int mode, float* y, int64_t ldy, uint16_t* plane,
+                               int64_t ld_bytes, int64_t rows, int64_t C, qt_stream_t stream);
 int qt_f16_gemm(const uint32_t* Xh, int64_t ldxp, const uint32_t* Wh, int64_t ldwp, const float* bias, float scale,
                 const float* scale_dev, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, qt_stream_t stream);
 

@@ -149,6 +149,11 @@ SIGNATURES = {
     "qt_linlog_quantize_bf16_f32": (_c_int, [_c_p] + [_c_i64] * 8 + [_c_int] * 4 + [_c_p, _c_p, _c_i64, _c_p]),
     "qt_bf16_pack_check_f32": (_c_int, [_c_p] + [_c_i64] * 8 + [_c_p, _c_i64, _c_p, _c_p]),
     "qt_check_bf16_exact_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p]),
+    "qt_conv2d_implicit_levels": (_c_int, [_c_p] + [_c_i64] * 14 + [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p] + [_c_int] * 5
+                                  + [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
+    "qt_pool_levels_bf16": (_c_int, [_c_p] + [_c_i64] * 6 + [_c_p, _c_i64, _c_i64, _c_p]),
+    "qt_bn_relu_linlog_bf16_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p] + [_c_int] * 6 + [_c_p, _c_i64, _c_p, _c_i64, _c_i64,
+                                                                                             _c_i64, _c_p]),
     "qt_f16x2_s2d_pack_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_i64] + [_c_i64] * 7 + [_c_p]),
     "qt_f16x2_s2d_spec_work_words": (_c_i64, [_c_i64] * 4),
     "qt_f16x2_s2d_pack_spec_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_f32, _c_p, _c_p, _c_p, _c_p, _c_i64] + [_c_i64] * 7

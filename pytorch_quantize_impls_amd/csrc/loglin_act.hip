@@ -8,6 +8,10 @@
 //   qt_bf16_pack_check_f32       the same plane of an fp32 tensor that is only BELIEVED to hold such values, OR-ing a device flag
 //                                when an element is not exact;
 //   qt_check_bf16_exact_f32      the predicate alone.
+// The deferred inference chain (lazy.py, kind "levels") keeps such planes between the layers and never writes the fp32 image:
+//   qt_pool_levels_bf16          MaxPool2d(k, s) on an NHWC level plane into the next conv's halo plane;
+//   qt_bn_relu_linlog_bf16_f32   BatchNorm1d (device arithmetic) -> [ReLU] -> quantiser over the fp32 result of a Linear layer, one
+//                                pass that writes the next Linear layer's row plane (and, on request, the fp32 image).
 // One kernel serves every layout: a block owns a 64 pixel x 64 channel tile, reads it along whichever of the two has unit stride
 // (rows / channels-last: channels; NCHW: pixels), passes the bf16 bits through LDS and writes whole 16-byte words along the
 // plane rows.  Pad bytes of a row (channel granule, 128-byte row granule of GEMM operands) are written as zeros by the tile that
@@ -26,14 +30,6 @@ struct ActQuant {   // kind 0: qt_lin_quant(step = a, maxv = b, mode); 1: qt_log
         return kind ? qt_log_quant(x, a, b, mode) : qt_lin_quant(x, a, b, mode);
     }
 };
-
-// high half of the fp32 pattern; a NaN whose payload sits in the low half only would become an infinity: made quiet instead
-__device__ __forceinline__ uint32_t act_bf16_hi(float f) {
-    const uint32_t u = __float_as_uint(f);
-    uint32_t h = u >> 16;
-    if ((u & 0x7fffffffu) > 0x7f800000u && !(h & 0x7fu)) h |= 0x40u;
-    return h;
-}
 
 // finite, low 16 bits zero, and zero or a NORMAL number (bf16 denormals on the matrix cores are not relied on)
 __device__ __forceinline__ bool act_bf16_exact(float f) {
@@ -100,6 +96,93 @@ __global__ __launch_bounds__(256) void check_exact_kernel(const float* __restric
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
 }
 
+// MaxPool2d(k, s), no padding, floor mode, on a one-term level plane: in [N][H][W][ld bytes] -> out [N][Ho + 2hy][Wo + 2hx][ld] (the
+// halo border is written as zeros).  The quantisers are monotone non-decreasing, so the max of the levels is the level of the max:
+// the plane of F.max_pool2d of the fp32 image.  Values are compared as floats in ATen's window order with ATen's update rule
+// (val > max or val is NaN), so NaN propagates and ties between +0 and -0 resolve as they do there.  One thread = 8 channels (one
+// 16-byte word) of one output pixel.
+__global__ __launch_bounds__(256) void pool_levels_kernel(const uint4* __restrict__ in, uint4* __restrict__ out, int64_t ldq, int64_t N,
+                                                          int H, int W, int pk, int ps, int Ho, int Wo, int hy, int hx) {
+    const int Hop = Ho + 2 * hy, Wop = Wo + 2 * hx;
+    const int64_t total = N * Hop * Wop * ldq;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t pix = i / ldq;
+        const int q = (int)(i - pix * ldq);
+        const int64_t n = pix / ((int64_t)Hop * Wop);
+        const int rem = (int)(pix - n * Hop * Wop);
+        const int ho = rem / Wop - hy, wo = rem % Wop - hx;
+        uint4 o = make_uint4(0, 0, 0, 0);
+        if ((unsigned)ho < (unsigned)Ho && (unsigned)wo < (unsigned)Wo) {
+            const uint4* base = in + ((n * H + (int64_t)ho * ps) * W + (int64_t)wo * ps) * ldq + q;
+            uint32_t best[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) best[e] = 0xff80u;                  // -inf
+            for (int a = 0; a < pk; ++a)
+                for (int b = 0; b < pk; ++b) {
+                    const uint4 v = base[((int64_t)a * W + b) * ldq];
+                    const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const uint32_t h = (w4[e >> 1] >> (16 * (e & 1))) & 0xffffu;
+                        const float f = __uint_as_float(h << 16), m = __uint_as_float(best[e] << 16);
+                        if (f > m || f != f) best[e] = h;
+                    }
+                }
+            o = make_uint4(best[0] | (best[1] << 16), best[2] | (best[3] << 16), best[4] | (best[5] << 16), best[6] | (best[7] << 16));
+        }
+        out[pix * ldq + q] = o;
+    }
+}
+
+// fp32 [rows][C] (the result of a Linear layer) -> BatchNorm1d(eval) in the device's arithmetic with st = [mean | rs]: form 0
+// t = fma(fl(fl(x - mean) * rs), weight, bias) (bn_eval_device_kernel's expression, what the library evaluates on 4-D tensors), form 1
+// t = fma(fl(weight * fl(x - mean)), rs, bias) (the order of ATen's own row kernel); the caller's probe says which one F.batch_norm
+// is on a 2-D tensor (layers.fused.device_bn_fold_rows) -> [ReLU] -> Lin / Log quantiser -> the one-term row plane [rows][ld bytes]
+// (128-byte row granule, pad zero) and, when y != nullptr, the fp32 image [rows][ldy].  One thread = 8 channels: one 16-byte word
+// of the plane.
+__global__ __launch_bounds__(256) void bn_relu_quant_rows_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ w,
+                                                                 const float* __restrict__ b, const float* __restrict__ st, int form,
+                                                                 int relu, ActQuant quant, float* __restrict__ y, int64_t ldy,
+                                                                 uint4* __restrict__ plane, int64_t ldq, int64_t rows, int C) {
+    const int64_t total = rows * ldq;
+    const bool vec = !(C & 3) && !(ldx & 3) && !(reinterpret_cast<uintptr_t>(x) & 15);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t row = i / ldq;
+        const int c0 = (int)(i - row * ldq) * 8;
+        float v[8];
+        if (vec && c0 + 8 <= C) {
+            const float4 lo = *reinterpret_cast<const float4*>(x + row * ldx + c0), hi = *reinterpret_cast<const float4*>(x + row * ldx + c0 + 4);
+            v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = c0 + e < C ? x[row * ldx + c0 + e] : 0.0f;
+        }
+        uint32_t h[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            h[e] = 0u;
+            const int c = c0 + e;
+            if (c < C) {
+                const float d = __fsub_rn(v[e], st[c]);
+                float t = form ? __fmaf_rn(__fmul_rn(w[c], d), st[C + c], b[c]) : __fmaf_rn(__fmul_rn(d, st[C + c]), w[c], b[c]);
+                if (relu) t = qt_torch_relu(t);
+                const float q = quant(t);
+                if (y) y[row * ldy + c] = q;
+                h[e] = act_bf16_hi(q);
+            }
+        }
+        plane[i] = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+    }
+}
+
+// the quantiser parameters of qt_linlog_quantize_bf16_f32's (dtype, fsr, bit_width, mode), or an error code
+int make_act_quant(int dtype, int fsr, int bit_width, int mode, ActQuant& quant) {
+    float a = 0.0f, b = 0.0f;
+    const int rc = qt_act_level_params(dtype, fsr, bit_width, mode, a, b);
+    if (rc == QT_OK) quant = ActQuant{dtype, a, b, mode};
+    return rc;
+}
+
 int launch_act_plane(const float* x, int64_t sn, int64_t sc, int64_t sh, int64_t sw, int64_t N, int64_t C, int64_t H, int64_t W,
                      ActQuant quant, float* y, uint16_t* plane, int64_t ld, int32_t* flag, qt_stream_t stream) {
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || !x || !plane) return QT_ERR_INVALID_ARG;
@@ -126,15 +209,10 @@ extern "C" {
 int qt_linlog_quantize_bf16_f32(const float* x, int64_t stride_n, int64_t stride_c, int64_t stride_h, int64_t stride_w, int64_t N,
                                 int64_t C, int64_t H, int64_t W, int dtype, int fsr, int bit_width, int mode, float* y,
                                 uint16_t* plane, int64_t ld_bytes, qt_stream_t stream) {
-    if (!y || dtype < 0 || dtype > 1 || mode < 0 || mode > 1 || fsr < -60 || fsr > 60 || bit_width < 1) return QT_ERR_INVALID_ARG;
+    if (!y) return QT_ERR_INVALID_ARG;
     ActQuant quant;
-    if (dtype == 0) {            // the parameters of qt_lin_quantize_f32; more than 8 bits are not one bf16 term
-        if (bit_width > 8) return QT_ERR_UNSUPPORTED;
-        quant = ActQuant{0, ldexpf(1.0f, fsr - bit_width), ldexpf(1.0f, fsr), mode};
-    } else {                     // the parameters of qt_log_quantize_f32; levels below 2^-126 would be bf16 denormals
-        if (bit_width > 16 || fsr - (1 << bit_width) < -126) return QT_ERR_UNSUPPORTED;
-        quant = ActQuant{1, (float)fsr - (float)(1 << bit_width), (float)fsr, mode};
-    }
+    const int rc = make_act_quant(dtype, fsr, bit_width, mode, quant);
+    if (rc != QT_OK) return rc;
     return launch_act_plane(x, stride_n, stride_c, stride_h, stride_w, N, C, H, W, quant, y, plane, ld_bytes, nullptr, stream);
 }
 
@@ -149,6 +227,42 @@ int qt_check_bf16_exact_f32(const float* x, int64_t n, int32_t* flag, qt_stream_
     if (n < 0 || !flag || (n > 0 && !x)) return QT_ERR_INVALID_ARG;
     if (n == 0) return QT_OK;
     hipLaunchKernelGGL(check_exact_kernel, dim3(qt_stream_grid((n + 2047) / 2048)), dim3(256), 0, (hipStream_t)stream, x, n, flag);
+    return qt_check_launch();
+}
+
+int qt_pool_levels_bf16(const uint16_t* in_plane, int64_t N, int64_t H, int64_t W, int64_t ld_bytes, int64_t pool_k, int64_t pool_s,
+                        uint16_t* out_plane, int64_t out_halo_h, int64_t out_halo_w, qt_stream_t stream) {
+    if (N < 0 || H <= 0 || W <= 0 || ld_bytes <= 0 || pool_k < 1 || pool_s < 1 || out_halo_h < 0 || out_halo_w < 0)
+        return QT_ERR_INVALID_ARG;
+    if (pool_k > H || pool_k > W) return QT_ERR_INVALID_ARG;
+    if (N == 0) return QT_OK;
+    if (!in_plane || !out_plane) return QT_ERR_INVALID_ARG;
+    if ((ld_bytes & 15) || !qt_aligned16(in_plane) || !qt_aligned16(out_plane)) return QT_ERR_ALIGNMENT;
+    if (H > 32767 || W > 32767 || out_halo_h > 64 || out_halo_w > 64) return QT_ERR_UNSUPPORTED;
+    const int64_t Ho = (H - pool_k) / pool_s + 1, Wo = (W - pool_k) / pool_s + 1;  // floor mode, no padding
+    const int64_t ldq = ld_bytes / 16;
+    const int grid = qt_stream_grid((N * (Ho + 2 * out_halo_h) * (Wo + 2 * out_halo_w) * ldq + 255) / 256);
+    hipLaunchKernelGGL(pool_levels_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint4*>(in_plane),
+                       reinterpret_cast<uint4*>(out_plane), ldq, N, (int)H, (int)W, (int)pool_k, (int)pool_s, (int)Ho, (int)Wo,
+                       (int)out_halo_h, (int)out_halo_w);
+    return qt_check_launch();
+}
+
+int qt_bn_relu_linlog_bf16_f32(const float* x, int64_t ldx, const float* weight, const float* bias, const float* bn_stats, int bn_form,
+                               int relu, int dtype, int fsr, int bit_width, int mode, float* y, int64_t ldy, uint16_t* plane,
+                               int64_t ld_bytes, int64_t rows, int64_t C, qt_stream_t stream) {
+    if (rows < 0 || C <= 0 || relu < 0 || relu > 1 || bn_form < 0 || bn_form > 1 || ldx < C || (y && ldy < C)) return QT_ERR_INVALID_ARG;
+    ActQuant quant;
+    const int rc = make_act_quant(dtype, fsr, bit_width, mode, quant);
+    if (rc != QT_OK) return rc;
+    if (rows == 0) return QT_OK;
+    if (!x || !weight || !bias || !bn_stats || !plane) return QT_ERR_INVALID_ARG;
+    if ((ld_bytes & 15) || ld_bytes < 2 * C || !qt_aligned16(plane)) return QT_ERR_ALIGNMENT;
+    if (C >= (1ll << 28) || rows * ld_bytes >= (1ll << 40)) return QT_ERR_UNSUPPORTED;
+    const int64_t ldq = ld_bytes / 16;
+    const int grid = qt_stream_grid((rows * ldq + 255) / 256);
+    hipLaunchKernelGGL(bn_relu_quant_rows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx, weight, bias, bn_stats, bn_form,
+                       relu, quant, y, ldy, reinterpret_cast<uint4*>(plane), ldq, rows, (int)C);
     return qt_check_launch();
 }
 

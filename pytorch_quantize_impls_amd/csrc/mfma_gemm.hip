@@ -643,6 +643,8 @@ static int conv_implicit_impl(int elem, const uint32_t* P, int64_t Nimg, int64_t
     // out, no depth-to-space; QT_NO_SWAPT=1: the compare form (A/B runs and the bit-identity test; read per call like the line above)
     const bool swapt = elem == 0 && epi.alpha && epi.thr && (Cout & 31) == 0 && !epi.d2s_cout && (epi.mode == 0 || epi.mode == 3) &&
                        !getenv("QT_NO_SWAPT");
+    // the level epilogue (mode 5) walks the tiles of the plain conv of its geometry: the accumulators are then the same bits
+    const bool plain_tiles = (!epi.alpha && epi.mode == 0) || epi.mode == 5;
 #define QT_CONV(E)                                                                                              \
     do {                                                                                                        \
         const int tn = pick_tile_n(Cout);                                                                       \
@@ -692,7 +694,7 @@ static int conv_implicit_impl(int elem, const uint32_t* P, int64_t Nimg, int64_t
             return launch_cfg<Conv128x128<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
         if (g_conv_force == 6 && !epi.alpha && epi.mode == 0 && kwords * 4 >= 2048 && !(ldwp & 127))            \
             return launch_cfg<ConvSkinny<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-        if (g_conv_force == 0 && !epi.alpha && epi.mode == 0 && ((M + 255) / 256) * ((Cout + tn - 1) / tn) < 200) {     \
+        if (g_conv_force == 0 && plain_tiles && ((M + 255) / 256) * ((Cout + tn - 1) / tn) < 200) {     \
             /* small maps: fewer 256-row tiles than CUs (tools/bench_conv_small_maps.py: 256 ch @ 8x8 137 -> 83 us,  */ \
             /* 512 ch @ 4x4 239 -> 102 us incl. the operand split; same accumulation order, bit-identical results)   */ \
             if (((M + 127) / 128) * ((Cout + 127) / 128) < 200 && kwords * 4 >= 2048 && !(ldwp & 127))          \
@@ -724,6 +726,7 @@ static int conv_implicit_impl(int elem, const uint32_t* P, int64_t Nimg, int64_t
     if (elem == 0) QT_CONV(ElemFp4);
     if (elem == 1) QT_CONV(ElemI8);
     if (elem == 3) QT_CONV(ElemF16);
+    if (epi.mode == 5) QT_CONV(ElemBf16L);
     QT_CONV(ElemBf16);
 #undef QT_CONV
 #undef QT_CONV_STAMPS
@@ -844,6 +847,33 @@ int qt_conv2d_implicit_codes(int elem, const uint32_t* P, int64_t Nimg, int64_t 
     return conv_implicit_impl(elem, P, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, Wmat, ldwp, bias, scale,
                               scale_dev, reinterpret_cast<float*>(codes), ldc_bytes, Cout, stream, epi, in_halo_h,
                               in_halo_w);
+}
+
+int qt_conv2d_implicit_levels(const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, int64_t Cw, int64_t in_halo_h, int64_t in_halo_w,
+                              int64_t kh, int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw,
+                              const uint32_t* Wmat, int64_t ldwp, const float* bias, const float* bn_weight, const float* bn_bias,
+                              const float* bn_stats, int relu, int dtype, int fsr, int bit_width, int mode, uint16_t* plane,
+                              int64_t ld_bytes, int64_t Cout, int64_t out_halo_h, int64_t out_halo_w, qt_stream_t stream) {
+    if (!bn_weight || !bn_bias || !bn_stats || !plane || relu < 0 || relu > 1) return QT_ERR_INVALID_ARG;
+    if (out_halo_h < 0 || out_halo_w < 0 || out_halo_h > 64 || out_halo_w > 64) return QT_ERR_INVALID_ARG;
+    if (!qt_aligned16(plane)) return QT_ERR_ALIGNMENT;
+    if (ld_bytes != ((2 * Cout + 15) & ~15ll)) return QT_ERR_INVALID_ARG;      // every byte of a pixel is written by a column block
+    EpiArgs epi;
+    epi.alpha = bn_weight;
+    epi.beta = bn_bias;
+    epi.bn_stats = bn_stats;
+    epi.mode = 5;
+    epi.relu = relu;
+    epi.lq_kind = dtype;
+    epi.lq_mode = mode;
+    {   // the parameter windows of qt_linlog_quantize_bf16_f32: every level one bf16 term
+        const int rc = qt_act_level_params(dtype, fsr, bit_width, mode, epi.lq_a, epi.lq_b);
+        if (rc != QT_OK) return rc;
+    }
+    epi.ohy = (int)out_halo_h;
+    epi.ohx = (int)out_halo_w;
+    return conv_implicit_impl(2, P, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, Wmat, ldwp, bias, 1.0f, nullptr,
+                              reinterpret_cast<float*>(plane), ld_bytes, Cout, stream, epi, in_halo_h, in_halo_w);
 }
 
 int qt_conv2d_implicit_halo(int elem, const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, int64_t Cw,

@@ -4,8 +4,10 @@
 #pragma once
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 #include "qt_common.h"
 #include "pp_common.h"
+#include "loglin_quant.h"
 
 namespace {
 
@@ -47,7 +49,8 @@ struct EpiArgs {
     const float* beta = nullptr;
     int mode = 0;                      // 0: threshold bits iff alpha != nullptr ; 2: int8 codes ; 3: threshold bits
                                        // expanded to the NEXT conv's fp4 nibble pixel plane (+1 = 0x2, -1 = 0xA), ldy WORDS per
-                                       // pixel, optionally with an (ohy, ohx) zero halo (border zeroed by the caller)
+                                       // pixel, optionally with an (ohy, ohx) zero halo (border zeroed by the caller) ;
+                                       // 4: fp32 through the device's BatchNorm ; 5: bf16 Lin / Log levels (see lq_kind)
     int relu = 0;
     float levels = 0.0f;               // 2^k - 1
     float rscale = 0.0f;
@@ -85,6 +88,14 @@ struct EpiArgs {
     // ElemFp4TapsRows only: per-pixel scale plane A [Nimg][aH][aW] of the conv's (logical, un-padded) input and its padding
     const float* row_A = nullptr;
     int aH = 0, aW = 0, aph = 0, apw = 0;
+    // Level epilogue (mode == 5, ElemBf16L kernels; inference fusion of QuantConv2d -> BatchNorm(eval) [-> ReLU] -> nnQuant(lin | log)):
+    //     t = fma(fl(fl(v - mean) * rs), weight, bias)   v = the fp32 value the plain epilogue would have stored; alpha / beta hold
+    //     t = relu(t) if relu                            weight / bias and bn_stats = [mean | rs], as in the device-form code epilogue
+    //     q = qt_lin_quant(t, lq_a, lq_b, lq_mode) | qt_log_quant(t, lq_a, lq_b, lq_mode)              (lq_kind 0 | 1, loglin_quant.h)
+    // stored as the high half of q's pattern (act_bf16_hi) into the one-term bf16 pixel plane (uint16_t*)Y with ldy BYTES per pixel
+    // (= 2 N rounded up to 16, pad zero), optionally with an (ohy, ohx) zero halo: the operand the next Lin / Log layer contracts.
+    int lq_kind = 0, lq_mode = 0;
+    float lq_a = 0.0f, lq_b = 0.0f;
 };
 
 // spread the 8 bits of a byte to bit 0 of 8 nibbles
@@ -236,6 +247,20 @@ struct ElemFp4T : ElemFp4 {
 template <int OD> struct ElemFp4Out : ElemFp4 {
     static constexpr int OUT_DTYPE = OD;
 };
+// bf16 operands with the LEVEL epilogue (EpiArgs::mode 5) in place of the fp32 store: a separate element so that the plain bf16
+// kernels keep their code and register budget; main loop and accumulators are ElemBf16's, bit for bit
+struct ElemBf16L : ElemBf16 {
+    static constexpr bool LEVEL_EPI = true;
+};
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant by construction (the level
+// epilogue's tile loops: their unrolled body is past the size up to which `#pragma unroll` is honoured on the 8- and 9-tile
+// configurations, and a loop left rolled indexes the accumulators dynamically, i.e. keeps them in scratch memory)
+template <class F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
+template <class E, class = void> struct elem_level : std::false_type {};
+template <class E> struct elem_level<E, std::void_t<decltype(E::LEVEL_EPI)>> : std::bool_constant<E::LEVEL_EPI> {};
 template <class E, class = void> struct elem_out : std::integral_constant<int, 0> {};
 template <class E> struct elem_out<E, std::void_t<decltype(E::OUT_DTYPE)>> : std::integral_constant<int, E::OUT_DTYPE> {};
 template <int OD>
@@ -327,7 +352,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::WAVES_PER_SIMD) void mfma_gemm_kern
         if constexpr (C::CONV) {
             if (b >= 8 * per_xcd) {                    // appended by launch_cfg for halo output planes
                 const int zs = epi.d2s_cout ? 2 : 1;
-                zero_halo_border(Y, (int)(epi.mode == 2 ? ldy / 16 : ldy / 4), (int64_t)M / (cg.Ho * cg.Wo), zs * cg.Ho,
+                zero_halo_border(Y, (int)((epi.mode == 2 || epi.mode == 5) ? ldy / 16 : ldy / 4), (int64_t)M / (cg.Ho * cg.Wo), zs * cg.Ho,
                                  zs * cg.Wo, epi.ohy, epi.ohx, b - 8 * per_xcd, (int)gridDim.x - 8 * per_xcd);
                 return;
             }
@@ -1204,6 +1229,100 @@ __global__ __launch_bounds__(C::NTHREADS, C::WAVES_PER_SIMD) void mfma_gemm_kern
         if (__any(bad) && lane == 0) atomicOr(epi.overflow, 1);
         return;
     }
+    if constexpr (elem_level<E>::value && C::CONV) {
+        // bf16 levels (mode 5): the 32x32 tile is transposed through the wave-private LDS patch as in the code epilogue, so a lane
+        // holds 4 consecutive channels of one output pixel: BatchNorm in the device's arithmetic, ReLU, the Lin / Log quantiser of
+        // loglin_quant.h, and one 8-byte word of bf16 patterns per lane — no fp32 activation in HBM between two quantised layers.
+        char* Q = reinterpret_cast<char*>(Y);
+        float* T = reinterpret_cast<float*>(smem) + wave * 1024;
+        const bool halo = (epi.ohy | epi.ohx) != 0;
+        int orow[C::TMW][4];                   // plane rows of this lane's 4 x TMW output pixels (identity without a halo)
+#pragma unroll
+        for (int a = 0; a < C::TMW; ++a)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int m = m0 + (wave_m * C::TMW + a) * 32 + i * 8 + (lane >> 3);
+                orow[a][i] = m;
+                if (halo && m < M) {
+                    const unsigned um = (unsigned)m;
+                    unsigned img, ho, wo;
+                    if (cg.sh_w >= 0) {                 // wave-uniform: power-of-two maps
+                        img = um >> cg.sh_hw;
+                        const unsigned rem = um & (unsigned)(cg.Ho * cg.Wo - 1);
+                        ho = rem >> cg.sh_w;
+                        wo = rem & (unsigned)(cg.Wo - 1);
+                    } else {
+                        img = epi.magic_hw ? (unsigned)__umul64hi((unsigned long long)um, epi.magic_hw) : um;
+                        const unsigned rem = um - img * (unsigned)(cg.Ho * cg.Wo);
+                        ho = epi.magic_w ? (unsigned)__umul64hi((unsigned long long)rem, epi.magic_w) : rem;
+                        wo = rem - ho * (unsigned)cg.Wo;
+                    }
+                    orow[a][i] = (int)((img * (unsigned)(cg.Ho + 2 * epi.ohy) + ho + epi.ohy) * (unsigned)(cg.Wo + 2 * epi.ohx) + wo + epi.ohx);
+                }
+            }
+        const float qa = epi.lq_a, qb = epi.lq_b;
+        const int qmode = epi.lq_mode;
+        // WHOLE: every row and every channel of the tile exists (the straight-line form: no per-element bounds, the quantiser kind a
+        // template flag of the body, the ReLU a select); otherwise the bounds-checked form.  Same roundings, same levels.
+        // (always_inline: a body left as a function would take the accumulators by reference, i.e. through scratch memory)
+        const bool relu = epi.relu != 0;
+        auto body = [&](auto whole_tag, auto log_tag) __attribute__((always_inline)) {
+            constexpr bool WHOLE = decltype(whole_tag)::value, LOG = decltype(log_tag)::value;
+            const bool qlog = WHOLE ? LOG : epi.lq_kind != 0;
+            static_for<C::TNW>([&](auto b_tag) __attribute__((always_inline)) {
+                constexpr int b = decltype(b_tag)::value;
+                const int nb = n0 + (wave_n * C::TNW + b) * 32;
+                const float bv = (bias && nb + lrow < N) ? bias[nb + lrow] : 0.0f;
+                const int n = nb + (lane & 7) * 4;
+                float bw[4], bb[4], mean[4], rs[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const bool in = WHOLE || n + e < N;
+                    bw[e] = in ? epi.alpha[n + e] : 0.0f;
+                    bb[e] = in ? epi.beta[n + e] : 0.0f;
+                    mean[e] = in ? epi.bn_stats[n + e] : 0.0f;
+                    rs[e] = in ? epi.bn_stats[N + n + e] : 0.0f;
+                }
+                static_for<C::TMW>([&](auto a_tag) __attribute__((always_inline)) {
+                    constexpr int a = decltype(a_tag)::value;
+                    const int mb = m0 + (wave_m * C::TMW + a) * 32;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        T[((r & 3) + 8 * (r >> 2) + 4 * lhalf) * 32 + lrow] = E::out(acc[a][b][r], scale, bv);
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int row = i * 8 + (lane >> 3);
+                        const float4 v4 = *reinterpret_cast<const float4*>(T + row * 32 + (lane & 7) * 4);
+                        // (2 n < ldy: the lane's 8 bytes lie in the pixel — its channels, or the zero pad of the 16-byte granule)
+                        if (WHOLE || (mb + row < M && 2 * n < ldy)) {
+                            const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+                            uint32_t h[4];
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                float t = __builtin_fmaf((v[e] - mean[e]) * rs[e], bw[e], bb[e]);
+                                t = relu ? qt_torch_relu(t) : t;
+                                const float q = qlog ? qt_log_quant(t, qa, qb, qmode) : qt_lin_quant(t, qa, qb, qmode);
+                                h[e] = (WHOLE || n + e < N) ? act_bf16_hi(q) : 0u;
+                            }
+                            *reinterpret_cast<uint2*>(Q + (int64_t)orow[a][i] * ldy + 2 * n) = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
+                        }
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                });
+            });
+        };
+        if ((N & 3) == 0 && n0 + C::TN <= N && m0 + C::TM <= M) {
+            if (epi.lq_kind) body(std::true_type{}, std::true_type{});
+            else body(std::true_type{}, std::false_type{});
+        } else {
+            body(std::false_type{}, std::false_type{});
+        }
+        return;
+    }
     if (OD == 0 && epi.alpha) {      // (the half-output elements have the plain epilogue only)
         // threshold bits: a v_cmp over the wave yields, per accumulator register, the 32-channel word of
         // two output rows (lanes 0-31 -> row R, lanes 32-63 -> row R + 4); lane i keeps row i's word and
@@ -1411,7 +1530,7 @@ int launch_cfg(const uint32_t* Xn, int64_t ldxp, const uint32_t* Wn, int64_t ldw
     const int64_t gy = (M + C::TM - 1) / C::TM, gx = (N + C::TN - 1) / C::TN;
     if (gx * gy > (1ll << 30)) return QT_ERR_UNSUPPORTED;
     unsigned grid = (unsigned)((gx * gy + 7) / 8 * 8);
-    if (C::CONV && (epi.mode == 2 || epi.mode == 3) && (epi.ohy | epi.ohx)) grid += 64;   // border-zeroing workgroups
+    if (C::CONV && (epi.mode == 2 || epi.mode == 3 || epi.mode == 5) && (epi.ohy | epi.ohx)) grid += 64;   // border-zeroing workgroups
     // > 64 KiB of dynamic LDS needs the opt-in attribute (per kernel and device: qt_ensure_dyn_lds raises it once)
     // VALID conv: + the tap table, one 4-byte offset per (stage, chunk)
     const int lds_bytes = C::LDS_BYTES + (C::VALID ? ((cg.kbytes + C::STAGE_BYTES - 1) / C::STAGE_BYTES) * C::CHUNKS * 4 : 0) +
@@ -1548,7 +1667,7 @@ static int conv_prepare(int elem, const uint32_t*& P, int64_t Nimg, int64_t H, i
     if (Ho <= 0 || Wo <= 0) return QT_ERR_INVALID_ARG;
     M = Nimg * Ho * Wo;
     if (M == 0 || Cout == 0) return 1;
-    if (!P || !Wmat || !Y || ldy < (epi.mode == 2 ? ((Cout + 3) & ~3ll) : epi.mode == 3 ? ((epi.d2s_cout ? epi.d2s_cout : Cout) + 31) / 32 * 4 : epi.alpha ? (Cout + 31) / 32 : Cout))
+    if (!P || !Wmat || !Y || ldy < (epi.mode == 2 ? ((Cout + 3) & ~3ll) : epi.mode == 5 ? ((2 * Cout + 15) & ~15ll) : epi.mode == 3 ? ((epi.d2s_cout ? epi.d2s_cout : Cout) + 31) / 32 * 4 : epi.alpha ? (Cout + 31) / 32 : Cout))
         return QT_ERR_INVALID_ARG;
     kwords = kh * kw * Cw;                 // words per (virtual) im2col row
     if ((Cw & 3) || (ldwp & 31) || ldwp < kwords || !qt_aligned16(P) || !qt_aligned16(Wmat)) return QT_ERR_ALIGNMENT;
@@ -1556,7 +1675,7 @@ static int conv_prepare(int elem, const uint32_t*& P, int64_t Nimg, int64_t H, i
     if (M > INT32_MAX || kwords * 4 >= (1 << 20) || Cout * ldwp * 4 >= (1ll << 31) || Hp > 32767 || Wp > 32767 ||
         Hp * Wp * Cw * 4 >= (1ll << 31))   // per-image plane bytes: 32-bit tap offsets
         return QT_ERR_UNSUPPORTED;
-    if ((epi.mode == 2 || epi.mode == 3) && (epi.ohy | epi.ohx | epi.rhy | epi.rhx | epi.d2s_cout)) {
+    if ((epi.mode == 2 || epi.mode == 3 || epi.mode == 5) && (epi.ohy | epi.ohx | epi.rhy | epi.rhx | epi.d2s_cout)) {
         const int64_t zs = epi.d2s_cout ? 2 : 1;
         if (Nimg * (zs * Ho + 2 * epi.ohy) * (zs * Wo + 2 * epi.ohx) > INT32_MAX || Nimg * (Ho + 2 * epi.rhy) * (Wo + 2 * epi.rhx) > INT32_MAX)
             return QT_ERR_UNSUPPORTED;

@@ -312,6 +312,42 @@ def loglin_act_planes(input: torch.Tensor, weight: Optional[torch.Tensor], layou
     return detect_bf16_exact(x, weight)
 
 
+def loglin_conv_weight_plane(conv, terms: int):
+    """The eval-mode weight plane of a QuantConv2d as its own eval path caches it: one term against a level plane (the swapped weight
+    already holds the levels, packed as it is), three against the exact split of a real image."""
+    if terms == 1:
+        return conv._eval_planes(lambda _w2: ops.pack_levels_bf16x3(conv.weight, "lin", 0, 32, True, grad_x=False, fwd_terms=1)[0],
+                                 key="conv_bf16x1_levels")
+    return conv._eval_planes(lambda _w2: ops.pack_conv_weight_bf16x3(conv.weight.detach(), "raw", terms=3), key="conv_bf16x3_raw")
+
+
+def loglin_conv_operands(conv, input: torch.Tensor):
+    """(pixel plane, weight plane, device flag or None) of an eval-mode QuantConv2d for a device fp32 (N, C, H, W) tensor, built as
+    the layer's own eval path builds them: the one-term plane of a tagged / detected quantised activation, else the exact
+    three-term split of the (real-valued) tensor."""
+    planes, flag = loglin_act_planes(input, conv.weight, packed.NHWC)
+    if planes is not None:
+        return planes, loglin_conv_weight_plane(conv, 1), flag
+    N, C, H, W = (int(v) for v in input.shape)
+    nhwc = input.detach().permute(0, 2, 3, 1)
+    if not nhwc.is_contiguous():
+        nhwc = nhwc.contiguous()
+    px = ops.split_bf16x3(nhwc.view(N * H * W, C), ld_bytes=ops.triple_ld_bytes(C, 16, 3), terms=3)
+    return px, loglin_conv_weight_plane(conv, 3), None
+
+
+def loglin_linear_weight_plane(layer, hwc=None):
+    """One-term eval-mode weight plane of a LinearQuant (the quantise-and-pack launch, as its own eval path caches it); ``hwc`` =
+    (C, H, W): the columns permuted to the (h, w, c) order of a flattened level plane, cached under a key of its own."""
+    quant = (layer.qdtype, layer.fsr, layer.bit_width, True)
+    if hwc is None:
+        return layer._eval_planes(lambda _w2: ops.pack_levels_bf16x3(layer.weight, *quant, grad_x=False, fwd_terms=1)[0],
+                                  key="bf16x1_levels")
+    from ..layers.fused import permute_fc_weight_hwc
+    return layer._eval_planes(lambda w2: ops.pack_levels_bf16x3(permute_fc_weight_hwc(w2, *hwc), *quant, grad_x=False, fwd_terms=1)[0],
+                              key=("bf16x1_levels_hwc",) + tuple(hwc))
+
+
 # ---- half precision (bf16 / fp16) -----------------------------------------------------------------------------------------------
 # The sign families take a half activation on the packed routes when it is (treated as) exactly +-1; the result is the exact
 # integer sum + bias rounded once to the activation's dtype, which is what the dense library's half GEMM / conv returns for these

@@ -77,6 +77,9 @@ class _FunctionModule(torch.nn.Module):
             bits = getattr(self.core, "_qt_quant_bits", None)
             if bits is not None:                   # nnDorefaQuant(k) on a deferred DorefaConv2d chain
                 out = lazy.quant(x, bits)
+            spec = getattr(self.core, "_qt_level_spec", None)
+            if spec is not None:                   # nnQuant(lin | log) on a deferred Lin / Log chain
+                out = lazy.levels(x, spec)
             if out is not None:
                 return out
             x = x.value()

@@ -9,7 +9,7 @@ sign(g) * clamp(round(g/step)*step, 0, 2^fsr) (note: negative g therefore yields
 """
 import torch
 
-from .. import ops, packed
+from .. import lazy, ops, packed
 from .common import QtFunction, front
 
 
@@ -51,11 +51,37 @@ def _lin_expr(x, fsr, bit_width, mode):
     return q if mode == 0 else torch.sign(x) * q
 
 
+def quantize_spec(input, spec):
+    """The forward of LinQuant / LogQuant for ``spec`` = (dtype, fsr, bit_width, with_sign) on a plain tensor: what a quantiser
+    recorded on a deferred chain (lazy.levels) evaluates when the chain materialises."""
+    dtype, fsr, bit_width, with_sign = spec
+    if dtype == "lin" and bit_width == 32:
+        return input
+    if _is_dev(input) and _kernel_takes(fsr, bit_width, dtype == "log"):
+        return _quantize_and_tag(input, dtype, fsr, bit_width, with_sign)
+    return _log_expr(input, fsr, bit_width, with_sign) if dtype == "log" else _lin_expr(input, fsr, bit_width, 1 if with_sign else 0)
+
+
+def _apply_recording(cls, input):
+    """``apply`` of the quantiser Functions: on a deferred Lin / Log chain (lazy.py, kind "levels") the quantiser is recorded."""
+    if isinstance(input, lazy.LazyActivation):
+        out = lazy.levels(input, cls._qt_level_spec)
+        if out is not None:
+            return out
+    return super(cls, cls).apply(input)
+
+
 def LogQuant(fsr=7, bit_width=3, with_sign=True, lin_back=True):
     """autograd.Function class: forward [sign(x) *] 2^clamp(round(log2|x|), fsr - 2^bit_width, fsr); backward the
     identity (lin_back) or the same quantiser applied to the gradient, signed (log_lin_connect.py:9-41)."""
 
     class _LogQuant(QtFunction):
+        _qt_level_spec = ("log", fsr, bit_width, bool(with_sign))
+
+        @classmethod
+        def apply(cls, input):
+            return _apply_recording(cls, input)
+
         @staticmethod
         def forward(ctx, input):
             if _is_dev(input) and _kernel_takes(fsr, bit_width, True):
@@ -78,6 +104,12 @@ def LinQuant(fsr=7, bit_width=3, with_sign=True, lin_back=True):
     (bit_width 32: identity); backward the identity (lin_back) or the quantised gradient (log_lin_connect.py:43-80)."""
 
     class _LinQuant(QtFunction):
+        _qt_level_spec = ("lin", fsr, bit_width, bool(with_sign))
+
+        @classmethod
+        def apply(cls, input):
+            return _apply_recording(cls, input)
+
         @staticmethod
         def forward(ctx, input):
             if bit_width == 32:

@@ -141,6 +141,35 @@ def device_bn_fold(bn, like_shape, channels_last: bool):
     return w.contiguous(), b.contiguous(), stats
 
 
+def device_bn_fold_rows(bn):
+    """``device_bn_fold`` for a BatchNorm1d over [rows, C] matrices: (weight, bias, stats, form).  The library evaluates 2-D tensors
+    with another kernel than 4-D ones, so both fma orders are probed: form 0 = fma(fl(fl(x - mean) * rs), weight, bias), form 1 =
+    fma(fl(weight * fl(x - mean)), rs, bias); the first that reproduces F.batch_norm on the probe bit for bit is returned, ValueError
+    when neither does."""
+    import torch.nn.functional as F
+    rm, rv = bn.running_mean.detach(), bn.running_var.detach()
+    C, dev = int(rm.numel()), rm.device
+    one, zero = torch.ones((C,), dtype=torch.float32, device=dev), torch.zeros((C,), dtype=torch.float32, device=dev)
+    w = bn.weight.detach().float() if bn.affine else one
+    b = bn.bias.detach().float() if bn.affine else zero
+    with torch.no_grad():
+        rs = F.batch_norm(torch.ones((2, C), dtype=torch.float32, device=dev), zero, rv, one, zero, False, 0.0, bn.eps)[0].contiguous()
+        g = torch.Generator(device=dev).manual_seed(1234)
+        probe = torch.randn((512, C), generator=g, device=dev) * (torch.sqrt(rv + bn.eps) * 3).view(1, C) + rm.view(1, C)
+        probe[::2] *= 17.0
+        want = F.batch_norm(probe, rm, rv, w if bn.affine else None, b if bn.affine else None, False, 0.0, bn.eps)
+        d = probe - rm.view(1, C)
+        # (the fma formed in fp64 from the fp32 intermediate, rounded once: see device_bn_fold)
+        got = [((d * rs.view(1, C)).double() * w.double().view(1, C) + b.double().view(1, C)).float(),
+               ((w.view(1, C) * d).double() * rs.double().view(1, C) + b.double().view(1, C)).float()]
+    for form in (0, 1):
+        if torch.equal(got[form], want):
+            return w.contiguous(), b.contiguous(), torch.cat([rm.float(), rs]).contiguous(), form
+    raise ValueError("eval-mode F.batch_norm of this device on a 2-D tensor is neither fma((x - mean) * rs, weight, bias) nor "
+                     f"fma(weight * (x - mean), rs, bias): {int((got[0] != want).sum())} / {int((got[1] != want).sum())} of "
+                     f"{want.numel()} probe values differ")
+
+
 def _out_channels_last(x) -> bool:
     """Memory format of the fp32 tensor a quantised conv returns for input ``x`` (functions/_fused.py: NCHW-contiguous
     tensors get NCHW storage back, everything else — channels-last tensors, packed activations — NHWC storage)."""
@@ -437,6 +466,137 @@ class CodeMaxPool(torch.nn.Module):
         out = ops.pool_codes(act.codes, N, H, W, self.pool_k, self.pool_s, self.out_halo)
         Ho, Wo = (H - self.pool_k) // self.pool_s + 1, (W - self.pool_k) // self.pool_s + 1
         return packed.CodeActivation(out, (N, C, Ho, Wo), halo=self.out_halo)
+
+
+def _halo_pair(v):
+    return (int(v),) * 2 if isinstance(v, int) else tuple(int(t) for t in v)
+
+
+def _quant_spec(spec):
+    """(dtype, fsr, bit_width, with_sign) of an nnQuant activation quantiser whose levels the level planes can hold."""
+    dtype, fsr, bit_width, with_sign = spec
+    if not ops.levels_exact_in_bf16(dtype, fsr, bit_width):
+        raise ValueError(f"the levels of {dtype}(fsr={fsr}, bit_width={bit_width}) are not single bf16 terms: no level plane")
+    return str(dtype), int(fsr), int(bit_width), bool(with_sign)
+
+
+class FusedLogLinConvBnQuant(torch.nn.Module):
+    """QuantConv2d (eval) -> BatchNorm2d (eval) [-> ReLU] -> nnQuant(lin | log) with the whole tail in the conv kernel's epilogue
+    (qt_conv2d_implicit_levels): the next layer's one-term bf16 plane comes out of the conv, no fp32 activation in HBM.
+
+    forward(x): a ``packed.LevelActivation`` (the output of a sibling), or a device fp32 (N, C, H, W) tensor — a quantised one is
+    taken as its one-term plane, a real image (the first layer) as the exact three-term split, exactly as QuantConv2d's own eval
+    path does.  Returns the LevelActivation of ``quant_spec`` = (dtype, fsr, bit_width, with_sign) applied to relu(bn(conv(x))), the
+    bits of the module chain: BatchNorm is evaluated in this device's own arithmetic (``device_bn_fold``, verified on a probe;
+    a failed probe raises ValueError).  ``out_halo``: zero border for the consuming conv's padding."""
+
+    def __init__(self, conv, bn, quant_spec, relu=True, out_halo=0):
+        super().__init__()
+        from .log_lin_layers import QuantConv2d
+        if not isinstance(conv, QuantConv2d) or conv.groups != 1 or conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+            raise ValueError("FusedLogLinConvBnQuant takes an un-grouped, zero-padded QuantConv2d")
+        if not ops.levels_exact_in_bf16(conv.qdtype, conv.fsr, conv.bit_width):
+            raise ValueError("the conv's weight levels are not single bf16 terms")
+        self.conv, self.bn, self.quant_spec, self.relu = conv, bn, _quant_spec(quant_spec), bool(relu)
+        self.out_halo = _halo_pair(out_halo)
+        self._folded = None
+
+    def refold(self):
+        self._folded = None
+
+    def forward(self, x):
+        conv = self.conv
+        if conv.training or self.bn.training:
+            raise RuntimeError("FusedLogLinConvBnQuant is an inference form: call .eval() first")
+        from ..functions import _fused
+        x = lazy.resolve(x)
+        flag, in_halo, cl = None, (0, 0), False
+        if isinstance(x, packed.LevelActivation):
+            if len(x.shape) != 4:
+                raise ValueError("FusedLogLinConvBnQuant consumes an (N, C, H, W) LevelActivation")
+            pad = tuple(int(v) for v in ops._pairs(conv.padding))
+            if any(x.halo) and (pad[0] > x.halo[0] or pad[1] > x.halo[1]):
+                x = x.without_halo()
+            pixels, in_halo, cl, shape = x.planes, x.halo, x.channels_last, x.shape
+            wt = _fused.loglin_conv_weight_plane(conv, 1)
+        else:
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0):
+                raise TypeError("FusedLogLinConvBnQuant runs on a device fp32 (N, C, H, W) tensor or a LevelActivation")
+            pixels, wt, flag = _fused.loglin_conv_operands(conv, x)
+            cl, shape = _out_channels_last(x), tuple(int(v) for v in x.shape)
+        if shape[1] != conv.in_channels:
+            raise ValueError(f"input has {shape[1]} channels, the conv {conv.in_channels}")
+        kh, kw = conv.kernel_size
+        Ho, Wo = ops.conv_out_hw(shape[2], shape[3], kh, kw, conv.stride, conv.padding, conv.dilation)
+        Cout = conv.out_channels
+        w, b, stats = _code_fold_for(self, "_folded", self.bn, "device", ((shape[0], Cout, Ho, Wo), cl))
+        bias = conv.bias.detach() if conv.bias is not None else None
+        epi = ops.LevelEpilogue(w, b, stats, self.quant_spec, self.relu, self.out_halo)
+        planes = ops.conv2d_levels(pixels, shape, wt, (kh, kw), epi, _fused.poison_bias(bias, flag, Cout, pixels.device),
+                                   conv.stride, conv.padding, conv.dilation, in_halo=in_halo)
+        out = packed.LevelActivation(planes, (shape[0], Cout, Ho, Wo), halo=self.out_halo)
+        out.channels_last = cl
+        return out
+
+
+class LevelMaxPool(torch.nn.Module):
+    """MaxPool2d on a LevelActivation (the Lin / Log nets pool AFTER the quantiser): the max of the levels, bit-identical to
+    pooling the fp32 image (the quantisers are monotone).  ``out_halo``: zero border for the next conv's padding."""
+
+    def __init__(self, pool, out_halo=0):
+        super().__init__()
+        k = pool.kernel_size if isinstance(pool.kernel_size, int) else pool.kernel_size[0]
+        st = pool.stride if isinstance(pool.stride, int) else pool.stride[0]
+        pad = pool.padding if isinstance(pool.padding, int) else pool.padding[0]
+        dil = pool.dilation if isinstance(pool.dilation, int) else pool.dilation[0]
+        if pad != 0 or dil != 1 or pool.ceil_mode:
+            raise ValueError("only un-padded, un-dilated, floor-mode MaxPool2d runs on level planes")
+        self.pool_k, self.pool_s = int(k), int(st if st is not None else k)
+        self.out_halo = _halo_pair(out_halo)
+
+    def forward(self, act):
+        if not isinstance(act, packed.LevelActivation) or len(act.shape) != 4:
+            raise TypeError("LevelMaxPool consumes the (N, C, H, W) LevelActivation of a fused Lin / Log block")
+        cl = act.channels_last
+        act = act.without_halo()
+        N, C, H, W = act.shape
+        if H < self.pool_k or W < self.pool_k:
+            raise ValueError("pooling window larger than the map")
+        out = ops.pool_levels(act.planes, N, H, W, self.pool_k, self.pool_s, self.out_halo)
+        Ho, Wo = (H - self.pool_k) // self.pool_s + 1, (W - self.pool_k) // self.pool_s + 1
+        res = packed.LevelActivation(out, (N, C, Ho, Wo), halo=self.out_halo)
+        res.channels_last = cl
+        return res
+
+
+class FusedBnLogLinQuant(torch.nn.Module):
+    """BatchNorm1d (eval) [-> ReLU] -> nnQuant(lin | log) over the fp32 [rows, C] result of a LinearQuant, as ONE pass
+    (qt_bn_relu_linlog_bf16_f32) that writes the next LinearQuant's one-term row plane: LevelActivation out.  ``want_f32``: the
+    pass also writes the fp32 image (``LevelActivation.image``), replacing the three launches of the module chain."""
+
+    def __init__(self, bn, quant_spec, relu=True, want_f32=False):
+        super().__init__()
+        self.bn, self.quant_spec, self.relu, self.want_f32 = bn, _quant_spec(quant_spec), bool(relu), bool(want_f32)
+        self._folded = None
+
+    def refold(self):
+        self._folded = None
+
+    def forward(self, x):
+        if self.bn.training:
+            raise RuntimeError("FusedBnLogLinQuant folds running statistics: call .eval() first")
+        x = lazy.resolve(x)
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.numel() > 0):
+            raise TypeError("FusedBnLogLinQuant runs on a non-empty device fp32 [rows, C] matrix")
+        key = _bn_key(self.bn)
+        if self._folded is None or self._folded[0] != key:
+            self._folded = (key, device_bn_fold_rows(self.bn))
+        w, b, stats, form = self._folded[1]
+        x2 = x if x.stride(1) == 1 or x.shape[1] == 1 else x.contiguous()
+        planes, y = ops.bn_relu_quantize_levels(x2, w, b, stats, self.quant_spec, self.relu, self.want_f32, bn_form=form)
+        out = packed.LevelActivation(planes, tuple(x.shape))
+        out.image = y
+        return out
 
 
 class FusedConvPoolBnSign(torch.nn.Module):

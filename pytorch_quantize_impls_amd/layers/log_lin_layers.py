@@ -64,7 +64,12 @@ class LinearQuant(_WeightInit, EvalSwapMixin, torch.nn.Linear, QLayer):
         self.weight_op = log_lin_connect.nnQuant(dtype=dtype, fsr=fsr, bit_width=bit_width, with_sign=True, lin_back=True)
 
     def forward(self, input):
+        if lazy.DEFER_LEVELS:          # opt-in: the deferred level chain (lazy.py, kind "levels")
+            return lazy.levels_linear_forward(self, input)
         lazy.note_inference_call(self, input)
+        return self._forward_impl(input)
+
+    def _forward_impl(self, input):
         input = lazy.resolve(input)
         if _autograd_on_device(self, input):
             if _fused.ops.levels_exact_in_bf16(self.qdtype, self.fsr, self.bit_width):
@@ -114,7 +119,14 @@ class QuantConv2d(_WeightInit, EvalSwapMixin, torch.nn.Conv2d, QLayer):
         self.weight_op = log_lin_connect.nnQuant(dtype=dtype, fsr=fsr, bit_width=bit_width, with_sign=True, lin_back=True)
 
     def forward(self, input):
+        if lazy.DEFER_LEVELS:          # opt-in: the deferred level chain (lazy.py, kind "levels")
+            return lazy.levels_conv_forward(self, input)
         lazy.note_inference_call(self, input)
+        return self._forward_impl(input)
+
+    def _forward_impl(self, input):
+        if isinstance(input, packed.LevelActivation):
+            return self._forward_levels(input)
         input = lazy.resolve(input)
         if (_autograd_on_device(self, input) and input.dim() == 4 and self.groups == 1 and self.padding_mode == "zeros"
                 and not isinstance(self.padding, str)):
@@ -160,3 +172,16 @@ class QuantConv2d(_WeightInit, EvalSwapMixin, torch.nn.Conv2d, QLayer):
             return _fused.nchw_result(y2, input, N, Ho, Wo, self.weight.shape[0])
         _fused.note_library_path(input, "Lin/Log conv: groups, padding mode, a non-fp32 dtype, or levels beyond bf16 without autograd")
         return torch.nn.functional.conv2d(input, wq, self.bias, self.stride, self.padding, self.dilation, self.groups)
+
+    def _forward_levels(self, act):
+        """The fp32 result for an activation that exists as a level plane only (a deferred chain that has to hand out this conv's
+        value): the one-term contraction of the ordinary eval path on that plane — the same bits."""
+        act = act.without_halo()
+        N, C, H, W = act.shape
+        Cout, kh, kw = int(self.weight.shape[0]), int(self.weight.shape[2]), int(self.weight.shape[3])
+        y2 = _fused.ops.float_conv2d(None, self.weight.detach(), "raw", self.bias.detach() if self.bias is not None else None,
+                                     self.stride, self.padding, self.dilation, weight_triples=_fused.loglin_conv_weight_plane(self, 1),
+                                     pixels=act.planes, in_shape=act.shape)
+        Ho, Wo = _fused.ops.conv_out_hw(H, W, kh, kw, self.stride, self.padding, self.dilation)
+        y = y2.view(N, Ho, Wo, Cout).permute(0, 3, 1, 2)
+        return y if act.channels_last else y.contiguous()

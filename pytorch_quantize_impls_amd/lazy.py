@@ -30,6 +30,11 @@ module-by-module graph's exactly (tests assert ``torch.equal`` against ``lazy.ea
 reduced to thresholds (a residual is added before the quantiser): its epilogue evaluates BatchNorm in this device's own
 arithmetic instead, verified on a probe (``layers.fused.device_bn_fold``).
 
+The Lin / Log family has the same mechanism, opt-in (``DEFER_LEVELS`` / ``levels_deferred()``, node kind "levels"): QuantConv2d ->
+BatchNorm2d -> [ReLU] -> nnQuant(lin | log) -> [MaxPool2d] -> [flatten] -> QuantConv2d | LinearQuant runs with BatchNorm (device
+arithmetic), ReLU and the quantiser in the conv's epilogue, which writes the next layer's one-term bf16 plane
+(``layers.fused.FusedLogLinConvBnQuant`` / ``LevelMaxPool`` / ``FusedBnLogLinQuant``).
+
 Nothing is deferred in training mode, with autograd enabled, on CPU tensors, for non-fp32 dtypes, grouped convs or
 non-zero padding modes.  ``lazy.ENABLED = False`` (or the ``eager()`` context manager) switches the mechanism off;
 ``lazy.STATS`` counts what happened (tests assert on it).
@@ -62,6 +67,12 @@ DEFER_CODES = True
 #: with this device's own BatchNorm thresholds: the bits of the module chain) instead of three launches; any other use reads the
 #: value.  The classifier of an un-modified AlexNet then executes like the explicit fused form.
 DEFER_DENSE = True
+#: Lin / Log chains (QuantConv2d -> BatchNorm2d -> [ReLU] -> nnQuant(lin | log) -> [MaxPool2d] -> [flatten] -> QuantConv2d |
+#: LinearQuant, and LinearQuant -> BatchNorm1d -> [ReLU] -> nnQuant): node kind "levels".  The conv's epilogue applies BatchNorm (this
+#: device's arithmetic, verified on a probe as for the DoReFa chains), ReLU and the quantiser to the accumulators and writes the next
+#: layer's one-term bf16 plane (layers.fused.FusedLogLinConvBnQuant): no fp32 activation between two quantised layers.  Opt-in:
+#: False = the Lin / Log layers never defer and run call for call as without this mechanism (``levels_deferred()`` switches it on).
+DEFER_LEVELS = False
 #: "deferred" convs that returned a LazyActivation, "fused" chains executed as fused blocks, "materialised" lazies that
 #: had to produce their fp32 value, "fallback:<func>" the functions that forced it
 STATS = collections.Counter()
@@ -115,6 +126,17 @@ def codes_deferred(on: bool = True):
         DEFER_CODES = prev
 
 
+@contextlib.contextmanager
+def levels_deferred(on: bool = True):
+    """Defer Lin / Log level chains (``DEFER_LEVELS``) inside the block; process-wide, restores the previous setting."""
+    global DEFER_LEVELS
+    prev, DEFER_LEVELS = DEFER_LEVELS, bool(on)
+    try:
+        yield
+    finally:
+        DEFER_LEVELS = prev
+
+
 class _Node:
     """One recorded step.  ``parent is None``: the deferred conv itself (``layer``, ``kind``, ``input`` = device tensor or
     PackedActivation); otherwise ``op`` applied to ``parent``.  The flags summarise the chain from the root."""
@@ -159,7 +181,7 @@ class _Node:
             self.stamp = _stamp(op[1])
         elif tag == "relu":
             self.relu = True
-        elif tag == "quant":
+        elif tag in ("quant", "lquant"):
             self.quant = op[1]
 
     def check_unmodified(self):
@@ -220,6 +242,9 @@ class _Node:
                 elif tag == "quant":
                     from .functions.dorefa_connect import _quantize
                     y = _quantize(x, bit_width=self.op[1])
+                elif tag == "lquant":
+                    from .functions.log_lin_connect import quantize_spec
+                    y = quantize_spec(x, self.op[1])
                 else:   # sign
                     from .functions.binary_connect import _binarize_and_tag
                     y = _binarize_and_tag(x)
@@ -234,6 +259,10 @@ class _Node:
             return self._force_codes(halo)
         if self.kind == "dense":
             return self._force_dense()
+        if self.kind == "levels":
+            return self._force_levels(halo)
+        if self.kind == "ldense":
+            return self._force_ldense()
         if not self.signed or self.bn is None:
             return None
         if self.flat:
@@ -327,6 +356,75 @@ def _force_codes(self, halo=None):
     return act
 
 
+def _force_levels(self, halo=None):
+    """LevelActivation of a quantised Lin / Log chain: the (N, C, H, W) one-term bf16 plane with a zero border of ``halo`` pixels
+    (the consuming conv's padding), or (flat chains) row planes in (h, w, c) order.  None if this chain cannot run fused."""
+    if self.quant is None or self.bn is None:
+        return None
+    halo = None if self.flat else (tuple(halo) if halo is not None else (0, 0))
+    if self.packed_cache is None:
+        self.packed_cache = {}
+    if halo in self.packed_cache:
+        return self.packed_cache[halo]
+    self.check_unmodified()
+    from .layers import fused
+    try:
+        with torch.no_grad():
+            blk = _level_block(self.layer, self.bn, self.quant, self.relu, (0, 0) if (self.pool2 is not None or self.flat) else halo)
+            act = blk(self.input)
+            if self.pool2 is not None:
+                act = fused.LevelMaxPool(torch.nn.MaxPool2d(self.pool2[0], self.pool2[1]), out_halo=halo or (0, 0))(act)
+            if self.flat:
+                act = act.flatten_hwc()          # (ValueError when the pixel rows are padded: the chain materialises)
+    except ValueError:
+        act = None
+    if act is not None:
+        STATS["fused"] += 1
+    self.packed_cache[halo] = act
+    return act
+
+
+_LDENSE_BLOCKS = collections.OrderedDict()    # (BatchNorm tensors' ids, quantiser, relu) -> FusedBnLogLinQuant
+
+
+def _force_ldense(self):
+    """LevelActivation (row planes) of a recorded LinearQuant -> BatchNorm1d -> [ReLU] -> nnQuant chain: one pass over the layer's
+    fp32 result (layers.fused.FusedBnLogLinQuant)."""
+    if self.quant is None or self.bn is None:
+        return None
+    if self.packed_cache is None:
+        self.packed_cache = {}
+    if None in self.packed_cache:
+        return self.packed_cache[None]
+    self.check_unmodified()
+    from .layers import fused
+    rm, rv, w, b, eps = self.bn
+    key = (id(rm), id(rv), id(w), id(b), eps, self.quant, self.relu)
+    blk = _LDENSE_BLOCKS.get(key)
+    if blk is None:
+        blk = _LDENSE_BLOCKS[key] = fused.FusedBnLogLinQuant(_BnView1d(rm, rv, w, b, eps), self.quant, relu=self.relu)
+        while len(_LDENSE_BLOCKS) > 64:
+            _LDENSE_BLOCKS.popitem(last=False)
+    else:
+        _LDENSE_BLOCKS.move_to_end(key)
+    root = self
+    while root.parent is not None:
+        root = root.parent
+    try:
+        with torch.no_grad():
+            act = blk(root.value)
+    except ValueError:
+        act = None
+    if act is not None:
+        STATS["levels_dense_fused"] += 1
+    self.packed_cache[None] = act
+    return act
+
+
+_Node._force_levels = _force_levels
+_Node._force_ldense = _force_ldense
+
+
 def _force_any(self):
     """The chain's CodeActivation with whatever halo it was already produced with (a residual may carry any)."""
     for act in (self.packed_cache or {}).values():
@@ -350,16 +448,28 @@ def _bn_view(owner_block, bn):
     return cache[key]
 
 
+def _share_bn_tensors(view, rm, rv, w, b, eps):
+    view.num_features, view.eps, view.momentum = int(rm.numel()), float(eps), None
+    view.affine, view.track_running_stats = w is not None, True
+    for name, t in (("running_mean", rm), ("running_var", rv), ("weight", w), ("bias", b)):
+        object.__setattr__(view, name, t)
+    view.training = False
+
+
 class _BnView(torch.nn.BatchNorm2d):
     """The tensors F.batch_norm was called with, presented as the BatchNorm2d module layers.fused folds (shares them)."""
 
     def __init__(self, rm, rv, w, b, eps):
         torch.nn.Module.__init__(self)
-        self.num_features, self.eps, self.momentum = int(rm.numel()), float(eps), None
-        self.affine, self.track_running_stats = w is not None, True
-        for name, t in (("running_mean", rm), ("running_var", rv), ("weight", w), ("bias", b)):
-            object.__setattr__(self, name, t)
-        self.training = False
+        _share_bn_tensors(self, rm, rv, w, b, eps)
+
+
+class _BnView1d(torch.nn.BatchNorm1d):
+    """The same for a BatchNorm1d."""
+
+    def __init__(self, rm, rv, w, b, eps):
+        torch.nn.Module.__init__(self)
+        _share_bn_tensors(self, rm, rv, w, b, eps)
 
 
 _BLOCKS = weakref.WeakKeyDictionary()      # conv layer -> OrderedDict(key -> FusedConvPoolBnSign)
@@ -397,6 +507,24 @@ def _code_block(layer, bn, bit_width, relu, halo):
     blk = per.get(key)
     if blk is None:
         blk = fused.FusedDorefaConvBnQuant(layer, _BnView(rm, rv, w, b, eps), bit_width, relu=relu, out_halo=halo, fold="device")
+        per[key] = blk
+        while len(per) > _MAX_BLOCKS_PER_LAYER:
+            per.popitem(last=False)
+    else:
+        per.move_to_end(key)
+    return blk
+
+
+def _level_block(layer, bn, spec, relu, halo):
+    from .layers import fused
+    rm, rv, w, b, eps = bn
+    key = (id(rm), id(rv), id(w), id(b), eps, "levels", spec, relu, halo)
+    per = _BLOCKS.get(layer)
+    if per is None:
+        per = _BLOCKS[layer] = collections.OrderedDict()
+    blk = per.get(key)
+    if blk is None:
+        blk = fused.FusedLogLinConvBnQuant(layer, _BnView(rm, rv, w, b, eps), spec, relu=relu, out_halo=halo)
         per[key] = blk
         while len(per) > _MAX_BLOCKS_PER_LAYER:
             per.popitem(last=False)
@@ -498,7 +626,7 @@ def _own_storage(t):
     node = t._qt
     if node.value is not None and node.value.data_ptr() == own.data_ptr():
         node.value = own.clone()
-        if node.kind == "dense":
+        if node.kind in ("dense", "ldense"):
             node.stamp = _stamp(node.value)          # chains recorded on the node now read (and version-check) the copy
     return own
 
@@ -663,6 +791,10 @@ def _h_max_pool2d(input, kernel_size, stride=None, padding=0, dilation=1, ceil_m
     if H < k or W < k:
         return NotImplemented
     shape = (N, C, (H - k) // s + 1, (W - k) // s + 1)
+    if n.kind == "levels":
+        if n.quant is not None and n.pool2 is None and not n.flat:     # the Lin / Log nets pool AFTER the quantiser: max of the levels
+            return _wrap(_Node(n, ("pool2", k, s), shape))
+        return NotImplemented
     if n.kind == "dorefa":
         if n.quant is not None and n.pool2 is None:          # DoReFa CNNs pool AFTER the quantiser: max of the codes
             return _wrap(_Node(n, ("pool2", k, s), shape))
@@ -678,7 +810,7 @@ def _h_batch_norm(input, running_mean, running_var, weight=None, bias=None, trai
     if not isinstance(input, LazyActivation) or training or running_mean is None or running_var is None:
         return NotImplemented
     n = input._qt
-    if n.kind == "dense":
+    if n.kind in ("dense", "ldense"):
         if n.bn is not None or len(n.shape) != 2:
             return NotImplemented
     elif n.bn is not None or n.flat or len(n.shape) != 4 or n.add is not None:
@@ -699,7 +831,7 @@ def _h_hardtanh(input, min_val=-1.0, max_val=1.0, inplace=False):
     if not isinstance(input, LazyActivation):
         return NotImplemented
     n = input._qt
-    if n.kind == "dorefa" or n.bn is None or n.hardtanh is not None or n.signed or not (min_val < 0 < max_val):
+    if n.kind in ("dorefa", "levels", "ldense") or n.bn is None or n.hardtanh is not None or n.signed or not (min_val < 0 < max_val):
         return NotImplemented
     child = _Node(n, ("hardtanh", float(min_val), float(max_val)), n.shape)
     if inplace:                      # same shape: the wrapper object itself moves on, as an in-place op's result would
@@ -718,7 +850,7 @@ def _h_relu(input, inplace=False):
     if not isinstance(input, LazyActivation):
         return NotImplemented
     n = input._qt
-    if n.kind != "dorefa" or n.bn is None or n.relu or n.quant is not None:
+    if n.kind not in ("dorefa", "levels", "ldense") or n.bn is None or n.relu or n.quant is not None:
         return NotImplemented
     child = _Node(n, ("relu",), n.shape)
     if inplace:
@@ -779,7 +911,7 @@ def _h_iadd(a, b, *, alpha=1):
 
 def _flat_target(n: _Node, shape):
     """True iff ``shape`` (ints, at most one -1) flattens the (N, C, H, W) chain to (N, C*H*W)."""
-    if len(n.shape) != 4 or n.flat or n.bn is None or n.kind == "dorefa":
+    if len(n.shape) != 4 or n.flat or n.bn is None or n.kind == "dorefa" or (n.kind == "levels" and n.quant is None):
         return False
     N, C, H, W = n.shape
     shape = tuple(int(v) for v in shape)
@@ -818,7 +950,7 @@ def _h_flatten(input, start_dim=0, end_dim=-1):
         return NotImplemented
     n = input._qt
     ok = (len(n.shape) == 4 and start_dim == 1 and end_dim in (-1, 3) and not n.flat and n.bn is not None
-          and n.kind != "dorefa")
+          and n.kind != "dorefa" and not (n.kind == "levels" and n.quant is None))
     return _as_flat(input, ok)
 
 
@@ -864,7 +996,7 @@ def sign(x: LazyActivation):
     """BinaryConnect (deterministic) of a deferred activation: recorded if the chain allows it, else None (the caller
     then binarises the materialised value)."""
     n = x._qt
-    if n.kind in ("dorefa", "const"):
+    if n.kind in ("dorefa", "const", "levels", "ldense"):
         return None
     if n.signed:
         return x                     # sign(+-1) == itself
@@ -880,6 +1012,21 @@ def quant(x: LazyActivation, bit_width: int):
     if n.kind != "dorefa" or n.bn is None or n.quant is not None or n.flat or not 2 <= int(bit_width) <= 8:
         return None
     return _wrap(_Node(n, ("quant", int(bit_width)), n.shape))
+
+
+def levels(x: LazyActivation, spec):
+    """nnQuant(lin | log) of a deferred Lin / Log chain (QuantConv2d -> BatchNorm2d [-> ReLU], or LinearQuant -> BatchNorm1d
+    [-> ReLU]): recorded when the level epilogue can produce it — ``spec`` = (dtype, fsr, bit_width, with_sign) with levels that are
+    single bf16 terms — else None (the caller quantises the materialised value)."""
+    n = x._qt
+    if n.kind not in ("levels", "ldense"):
+        return None
+    dtype, fsr, bit_width, with_sign = spec
+    if (n.bn is None or n.quant is not None or (n.kind == "levels" and n.flat)
+            or not ops.levels_exact_in_bf16(dtype, fsr, bit_width)):
+        STATS["fallback:nnQuant"] += 1
+        return None
+    return _wrap(_Node(n, ("lquant", (dtype, int(fsr), int(bit_width), bool(with_sign))), n.shape))
 
 
 # ---- layer entry points ----------------------------------------------------------------------------------------------
@@ -1031,3 +1178,98 @@ def linear_forward(layer, input, kind: str):
     if type(input) in lazy_train._DEFERRED:
         input = lazy_train.resolve(input)
     return _dense_result(layer, lazy_train.wrap(layer, layer._forward_impl(input)))
+
+
+# ---- Lin / Log level chains (DEFER_LEVELS) ---------------------------------------------------------------------------------------------
+
+def _levels_layer_ok(layer) -> bool:
+    """An eval-mode, no-autograd device fp32 Lin / Log layer whose levels are single bf16 terms, with the one-term route on."""
+    from .functions import _fused
+    w = layer.weight
+    return (not layer.training and _no_autograd(layer) and w.is_cuda and w.dtype == torch.float32 and w.numel() > 0
+            and ops.levels_exact_in_bf16(layer.qdtype, layer.fsr, layer.bit_width) and bool(_fused._cfg("LOGLIN_ONE_TERM"))
+            and not _untracked(w, layer.bias))
+
+
+def _levels_conv_can_defer(layer, input=None, shape=None) -> bool:
+    """``input``: what the conv was called with (a tensor or a LevelActivation); ``shape``: instead of it, the logical NCHW shape of a
+    level plane that is not produced yet."""
+    if (not _levels_layer_ok(layer) or layer.groups != 1 or layer.padding_mode != "zeros" or isinstance(layer.padding, str)
+            or not ops._cfg("CONV_IMPLICIT")):
+        return False
+    if shape is None and isinstance(input, packed.LevelActivation):
+        shape = input.shape
+    if shape is None:
+        if not (isinstance(input, torch.Tensor) and not isinstance(input, LazyActivation) and input.is_cuda
+                and input.dtype == torch.float32 and input.dim() == 4 and input.numel() > 0 and not input.requires_grad
+                and not _untracked(input)):
+            return False
+        shape = input.shape
+    return len(shape) == 4 and int(shape[1]) == layer.in_channels
+
+
+def levels_conv_forward(layer, input):
+    """forward() of QuantConv2d under DEFER_LEVELS: consumes a deferred quantised chain as its level plane (the conv's padding as
+    the plane's zero border) and, when it may, defers itself; everything else goes to the layer's ordinary path."""
+    note_inference_call(layer, input)
+    if isinstance(input, LazyActivation):
+        n = input._qt
+        act = None
+        if n.kind == "levels" and n.quant is not None and not n.flat and n.value is None \
+                and _levels_conv_can_defer(layer, shape=n.shape):
+            pad = tuple(int(v) for v in ops._pairs(layer.padding))
+            # a plane already produced for another consumer serves this one too if its zero border covers the padding
+            for halo, done in (n.packed_cache or {}).items():
+                if done is not None and halo is not None and halo[0] >= pad[0] and halo[1] >= pad[1]:
+                    act = done
+                    break
+            if act is None:
+                act = n.force(pad)
+        if act is None:
+            STATS["fallback:QuantConv2d"] += 1
+        input = act if act is not None else n.materialise()
+    if enabled() and DEFER_LEVELS and _levels_conv_can_defer(layer, input):
+        N, C, H, W = (int(v) for v in input.shape)
+        kh, kw = layer.kernel_size
+        Ho, Wo = ops.conv_out_hw(H, W, kh, kw, layer.stride, layer.padding, layer.dilation)
+        if Ho > 0 and Wo > 0:
+            STATS["deferred"] += 1
+            return _wrap(_Node(None, None, (N, int(layer.out_channels), int(Ho), int(Wo)), layer=layer, kind="levels", input=input))
+    return layer._forward_impl(input)
+
+
+def _ldense_node(value: torch.Tensor) -> _Node:
+    """Root that holds the computed [B, N] result of a LinearQuant: BatchNorm1d, ReLU and nnQuant can be recorded on it (kind
+    "ldense"); everything else reads the value."""
+    n = _dense_node(value)
+    n.kind = "ldense"
+    return n
+
+
+def _levels_dense_result(layer, y):
+    if (DEFER_LEVELS and enabled() and type(y) is torch.Tensor and y.dim() == 2 and y.is_cuda and y.dtype == torch.float32
+            and y.numel() > 0 and not y.requires_grad and not layer.training and _no_autograd(layer) and not _untracked(y)):
+        STATS["levels_dense_deferred"] += 1
+        return LazyDense(_ldense_node(y))
+    return y
+
+
+def levels_linear_forward(layer, input):
+    """forward() of LinearQuant under DEFER_LEVELS: a flattened quantised chain arrives as row planes in (h, w, c) order and meets
+    the one-term weight plane with its columns permuted to that order (cached per weight version); a quantised LinearQuant ->
+    BatchNorm1d chain arrives as the row plane its one pass wrote.  The result goes out as a dense deferred activation."""
+    note_inference_call(layer, input)
+    if isinstance(input, LazyActivation):
+        n = input._qt
+        act = None
+        if n.quant is not None and n.value is None and len(n.shape) == 2 and n.shape[1] == layer.in_features \
+                and (n.kind == "ldense" or (n.kind == "levels" and n.flat)) and _levels_layer_ok(layer):
+            act = n.force()
+        if act is not None:
+            from .functions import _fused
+            wt = _fused.loglin_linear_weight_plane(layer, hwc=act.hwc)
+            bias = layer.bias.detach() if layer.bias is not None else None
+            return _levels_dense_result(layer, ops.bf16_gemm(act.planes, wt, bias))
+        STATS["fallback:LinearQuant"] += 1
+        input = n.materialise()
+    return _levels_dense_result(layer, layer._forward_impl(input))

@@ -2375,6 +2375,113 @@ def is_bf16_exact(x: torch.Tensor) -> bool:
     return int(check_bf16_exact(x).item()) == 0
 
 
+# ---- level planes from layer to layer: the deferred inference chain of the Lin / Log family (lazy.py, kind "levels") -----------
+
+@dataclass
+class LevelEpilogue:
+    """Arguments of the conv's level epilogue (qt_conv2d_implicit_levels): eval-mode BatchNorm in the device's arithmetic
+    (``weight`` / ``bias`` / ``stats`` = [mean | rs] as layers.fused.device_bn_fold supplies them), optional ReLU, the Lin / Log
+    activation quantiser ``quant`` = (dtype, fsr, bit_width, with_sign); ``out_halo`` = zero border of the produced plane."""
+    weight: torch.Tensor
+    bias: torch.Tensor
+    stats: torch.Tensor
+    quant: tuple
+    relu: bool = True
+    out_halo: tuple = (0, 0)
+
+
+def _level_quant_args(quant):
+    dtype, fsr, bit_width, with_sign = quant
+    if dtype not in _LEVEL_DTYPES or not levels_exact_in_bf16(dtype, fsr, bit_width):
+        raise ValueError(f"the levels of {dtype}(fsr={fsr}, bit_width={bit_width}) are not single bf16 terms")
+    return _LEVEL_DTYPES[dtype], int(fsr), int(bit_width), int(bool(with_sign))
+
+
+def conv2d_levels(pixels: TriplePlanes, in_shape, wplanes: TriplePlanes, kernel_hw, epi: LevelEpilogue, bias=None, stride=1,
+                  padding=0, dilation=1, in_halo=(0, 0)) -> TriplePlanes:
+    """conv2d -> BatchNorm(eval) -> [ReLU] -> Lin / Log quantiser with the whole tail in the conv kernel's epilogue
+    (qt_conv2d_implicit_levels): ``pixels`` = the NHWC bf16 plane of the (N, C, H, W) input — one term (a level plane, optionally
+    with a zero border ``in_halo``) or three (a real image) — against a weight plane of the same number of terms.  Returns the
+    one-term plane [N*(Ho + 2hy)*(Wo + 2hx), ld] of the quantised activation, border zero: the bits of
+    quantize_levels_bf16(relu(F.batch_norm(conv))).  ValueError for a shape outside the implicit kernel's limits."""
+    N, C, H, W = (int(v) for v in in_shape)
+    kh, kw = kernel_hw
+    (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
+    Ho, Wo = conv_out_hw(H, W, kh, kw, stride, padding, dilation)
+    hy, hx = (int(v) for v in in_halo)
+    Hp, Wp = H + 2 * hy, W + 2 * hx
+    if pixels.terms != wplanes.terms or pixels.terms == 2:
+        raise ValueError(f"pixel planes have {pixels.terms} terms, the weight planes {wplanes.terms} (bf16 planes of 1 or 3 terms)")
+    Cb = triple_ld_bytes(C, 16, pixels.terms)
+    if int(pixels.data.shape[1]) * 2 != Cb or pixels.rows != N * Hp * Wp or int(pixels.data.shape[0]) < N * Hp * Wp:
+        raise ValueError(f"pixel plane does not hold in_shape {tuple(in_shape)} with halo {(hy, hx)}")
+    Cw, ldw = Cb // 4, wplanes.ld_words
+    Cout = wplanes.rows
+    M = N * Ho * Wo
+    if (Ho <= 0 or Wo <= 0 or M >= (1 << 31) or kh * kw * Cw * 4 >= (1 << 20) or Hp > 32767 or Wp > 32767 or ldw % 32
+            or ldw < kh * kw * Cw or Hp * Wp * Cw * 4 >= (1 << 31)):
+        raise ValueError("shape outside the implicit-GEMM conv's limits")
+    if (hy or hx) and (ph > hy or pw > hx or N * Hp * Wp * Cw * 4 >= (1 << 32) or kh * kw * Cw * 4 > 32768):
+        raise ValueError("padding larger than the input plane's halo, or a plane beyond the un-padded kernels' limits")
+    dev = pixels.device
+    bias = _check_bias(bias, Cout, dev)
+    bw, bb = _check_bias(epi.weight, Cout, dev), _check_bias(epi.bias, Cout, dev)
+    stats = _require(epi.stats, "bn_stats").contiguous()
+    if stats.numel() != 2 * Cout:
+        raise ValueError("bn_stats must hold [mean | rs]: 2 * Cout values")
+    q = _level_quant_args(epi.quant)
+    ohy, ohx = (int(v) for v in epi.out_halo)
+    ld = triple_ld_bytes(Cout, 16, 1)
+    rows = N * (Ho + 2 * ohy) * (Wo + 2 * ohx)
+    plane = torch.empty((rows, ld // 2), dtype=torch.int16, device=dev)       # the launch writes every byte, border included
+    I = int
+    with _on(dev):
+        _lib.call("qt_conv2d_implicit_levels", _p(pixels.data), I(N), I(H), I(W), I(Cw), I(hy), I(hx), I(kh), I(kw), I(sh), I(sw),
+                  I(ph), I(pw), I(dh), I(dw), _p(wplanes.data), I(ldw), _p(bias), _p(bw), _p(bb), _p(stats), int(bool(epi.relu)), *q,
+                  _p(plane), I(ld), I(Cout), I(ohy), I(ohx), _stream(dev))
+    return TriplePlanes(data=plane, rows=rows, K=Cout, terms=1)
+
+
+def pool_levels(planes: TriplePlanes, N: int, H: int, W: int, pool_k: int, pool_s: int, out_halo=(0, 0)) -> TriplePlanes:
+    """MaxPool2d(pool_k, pool_s) on an NHWC level plane [N*H*W, ld] -> [N*(Ho+2hy)*(Wo+2hx), ld] (qt_pool_levels_bf16): the quantisers
+    are monotone, so pooling the levels is pooling the fp32 image."""
+    if planes.terms != 1 or planes.rows != N * H * W:
+        raise ValueError(f"a one-term level plane of {N * H * W} pixels is needed, got {planes.rows} pixels, {planes.terms} terms")
+    hy, hx = (int(v) for v in out_halo)
+    Ho, Wo = (H - pool_k) // pool_s + 1, (W - pool_k) // pool_s + 1
+    ld2 = int(planes.data.shape[1])
+    out = torch.empty((N * (Ho + 2 * hy) * (Wo + 2 * hx), ld2), dtype=torch.int16, device=planes.device)
+    I = int
+    with _on(planes.device):
+        _lib.call("qt_pool_levels_bf16", _p(planes.data), I(N), I(H), I(W), I(ld2 * 2), I(pool_k), I(pool_s), _p(out), I(hy), I(hx),
+                  _stream(planes.device))
+    return TriplePlanes(data=out, rows=int(out.shape[0]), K=planes.K, terms=1)
+
+
+def bn_relu_quantize_levels(x2: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, bn_stats: torch.Tensor, quant, relu: bool = True,
+                            want_f32: bool = False, bn_form: int = 0):
+    """BatchNorm1d(eval, device arithmetic) -> [ReLU] -> Lin / Log quantiser over an fp32 [rows, C] matrix in one pass
+    (qt_bn_relu_linlog_bf16_f32): (one-term row plane with the 128-byte row granule, fp32 image or None).  ``bn_form``: which of the
+    two fma orders the device's 2-D F.batch_norm is (layers.fused.device_bn_fold_rows)."""
+    _require(x2, "input")
+    if x2.dim() != 2 or (x2.shape[1] > 1 and x2.stride(1) != 1) or x2.numel() == 0:
+        raise ValueError("bn_relu_quantize_levels takes a non-empty [rows, C] fp32 matrix with unit channel stride")
+    rows, C = int(x2.shape[0]), int(x2.shape[1])
+    dev = x2.device
+    bw, bb = _check_bias(weight, C, dev), _check_bias(bias, C, dev)
+    stats = _require(bn_stats, "bn_stats").contiguous()
+    if stats.numel() != 2 * C:
+        raise ValueError("bn_stats must hold [mean | rs]: 2 * C values")
+    q = _level_quant_args(quant)
+    ld = triple_ld_bytes(C, 128, 1)
+    plane = torch.empty((rows, ld // 2), dtype=torch.int16, device=dev)
+    y = torch.empty((rows, C), dtype=torch.float32, device=dev) if want_f32 else None
+    with _on(dev):
+        _lib.call("qt_bn_relu_linlog_bf16_f32", _p(x2), int(x2.stride(0) if rows > 1 else max(C, 1)), _p(bw), _p(bb), _p(stats),
+                  int(bn_form), int(bool(relu)), *q, _p(y), int(C), _p(plane), int(ld), int(rows), int(C), _stream(dev))
+    return TriplePlanes(data=plane, rows=rows, K=C, terms=1), y
+
+
 #: fixed power-of-two scale the first layer's space-to-depth pack speculates with (None / 0: always the separate max|x| pass).
 #: 2^-11 is admissible for max|x| in [2^-3, 2^4) (max|x| / s in [2^8, 2^15): below fp16's overflow with a binade to spare):
 #: unit-variance and [0, 1] images; anything else is repacked on the device.

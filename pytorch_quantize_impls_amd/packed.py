@@ -224,3 +224,86 @@ class CodeActivation:
         from . import ops
         N, _, H, W = self.shape
         return ops.codes_to_f32(self.codes, N, H, W, self.halo, int(kernel_size), not ops._cfg("ASSUME_CODES_FIT")).permute(0, 3, 1, 2)
+
+
+class LevelActivation:
+    """A Lin / Log quantised activation that exists ONLY as its one-term bf16 plane (no fp32 image): what the level epilogue of
+    layers.fused.FusedLogLinConvBnQuant hands to the next QuantConv2d / LinearQuant in eval mode.  The counterpart of
+    ``CodeActivation``.
+
+    ``planes``: ops.TriplePlanes (terms = 1); ``shape``: logical shape, (N, C, H, W) with an NHWC plane — optionally with a zero
+    border of ``halo`` pixels around every image, rows = N*(H + 2hy)*(W + 2hx) — or (rows, K) with a row plane."""
+    is_cuda = True
+    dtype = torch.float32
+    requires_grad = False
+
+    def __init__(self, planes, shape, halo=(0, 0)):
+        self.planes = planes
+        self.shape = tuple(int(v) for v in shape)
+        self.halo = tuple(int(v) for v in halo)
+        self.hwc = None               # (C, H, W) when the rows are a feature map flattened in (h, w, c) order (flatten_hwc)
+        self.channels_last = False    # memory format the module graph's fp32 tensor would have (selects the BatchNorm probe)
+        self.image = None             # the fp32 image, where the producer was asked to write it as well
+        if planes.terms != 1:
+            raise ValueError("a LevelActivation holds a one-term bf16 plane")
+        if any(self.halo) and len(self.shape) != 4:
+            raise ValueError("only (N, C, H, W) activations carry a halo")
+        if len(self.shape) == 4:
+            N, C, H, W = self.shape
+            want = N * (H + 2 * self.halo[0]) * (W + 2 * self.halo[1])
+        else:
+            want = 1
+            for v in self.shape[:-1]:
+                want *= v
+        if planes.rows != want or planes.K != (self.shape[1] if len(self.shape) == 4 else self.shape[-1]):
+            raise ValueError(f"level plane [{planes.rows}, {planes.K}] does not hold shape {self.shape} with halo {self.halo}")
+
+    @property
+    def device(self):
+        return self.planes.device
+
+    def dim(self):
+        return len(self.shape)
+
+    def size(self, i=None):
+        return self.shape if i is None else self.shape[i]
+
+    def without_halo(self) -> "LevelActivation":
+        """The same activation as a plain [N*H*W, ld] plane (one copy; identity without a halo)."""
+        if not any(self.halo):
+            return self
+        from . import ops
+        N, C, H, W = self.shape
+        hy, hx = self.halo
+        inner = self.planes.data.view(N, H + 2 * hy, W + 2 * hx, -1)[:, hy:hy + H, hx:hx + W].contiguous()
+        act = LevelActivation(ops.TriplePlanes(data=inner.view(N * H * W, -1), rows=N * H * W, K=C, terms=1), self.shape)
+        act.channels_last = self.channels_last
+        return act
+
+    def can_flatten_hwc(self) -> bool:
+        """(N, C, H, W) -> (N, H*W*C) is a view: no halo, un-padded pixel rows (ld_bytes == 2 C) and whole 16-byte words per row."""
+        if len(self.shape) != 4 or any(self.halo):
+            return False
+        N, C, H, W = self.shape
+        return int(self.planes.data.shape[1]) == C and (H * W * C) % 8 == 0
+
+    def flatten_hwc(self) -> "LevelActivation":
+        """Row planes in (h, w, c) order for a LinearQuant whose weight columns were permuted to that order
+        (layers.fused.permute_fc_weight_hwc)."""
+        if not self.can_flatten_hwc():
+            raise ValueError("flatten_hwc needs an (N, C, H, W) plane without halo whose pixel rows are un-padded (C % 8 == 0)")
+        from . import ops
+        N, C, H, W = self.shape
+        flat = LevelActivation(ops.TriplePlanes(data=self.planes.data.view(N, H * W * C), rows=N, K=H * W * C, terms=1), (N, H * W * C))
+        flat.hwc = (C, H, W)
+        return flat
+
+    def float(self) -> torch.Tensor:
+        """The fp32 image the quantiser would have returned (a level IS its bf16 value); (N, C, H, W) comes back channels_last."""
+        act = self.without_halo()
+        K = act.planes.K
+        v = (act.planes.data[:, :K].to(torch.int32) << 16).view(torch.float32)
+        if len(self.shape) == 4:
+            N, C, H, W = self.shape
+            return v.view(N, H, W, C).permute(0, 3, 1, 2)
+        return v.reshape(self.shape)

@@ -6,10 +6,30 @@ The C-ABI kernels are launched on torch's current stream, so they are captured l
 requirement is a forward without host synchronisation (no un-tagged +-1 detection: give first layers
 ``binary_input = False``; no DoReFa code-overflow check inside the captured region).
 """
+import contextlib
+import gc
+
 import torch
 from torch.utils._pytree import tree_map_only
 
 from .. import lazy
+
+
+@contextlib.contextmanager
+def _no_collection_inside():
+    """Around a stream capture: a full garbage collection first, none inside.  A model that was replayed implicitly is a reference
+    cycle (root -> its instance ``forward`` -> engine -> root) that owns hipGraphs, so it dies in whatever allocation happens to
+    trigger the cyclic collector; when that fell inside another model's capture, the destruction of its graphs and of their memory
+    pool there aborted the process.  ``torch.cuda.graph`` itself no longer collects on entry.  The collector's switch is
+    process-wide: a thread that toggles it while another captures is not guarded against."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_on:
+            gc.enable()
 
 
 class GraphedModule(torch.nn.Module):
@@ -35,7 +55,7 @@ class GraphedModule(torch.nn.Module):
             for _ in range(warmup):                 # allocations, weight packing and caches settle before capture
                 module(self._static_in)
             torch.cuda.synchronize(example_input.device)
-            with torch.cuda.graph(self._graph, stream=self._stream):
+            with _no_collection_inside(), torch.cuda.graph(self._graph, stream=self._stream):
                 out = module(self._static_in)
                 # a module that ends in a quantised conv chain returns a deferred activation (lazy.py): its kernels
                 # have to be part of the graph, so it is turned into its value inside the captured region
@@ -237,7 +257,7 @@ class GraphedTrainStep:
                 for _ in range(max(1, warmup)):       # verdicts asked (and remembered), allocations and weight caches settle
                     self._one()
                 torch.cuda.synchronize(example_input.device)
-                with torch.cuda.graph(self._graph, stream=self._stream):
+                with _no_collection_inside(), torch.cuda.graph(self._graph, stream=self._stream):
                     self._loss = self._one()
             torch.cuda.synchronize(example_input.device)
 
