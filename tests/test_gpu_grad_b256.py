@@ -18,8 +18,9 @@ taken (_fused.LIBRARY_PATHS), and records the kernel instances it compared.
   (e) one batch-256 training step of each benchmark model: every backward kernel instance it launches was compared here, is
       torch's own (allow-list with reasons) or is named in KNOWN_UNCOVERED with where it is checked instead.
 
-Not here: the training chains at batch 256 (d), XNOR-Net and Lin / Log layers at batch 256, the plane past 2^31 bytes, the
-DoReFa digit route, the channels-last parameter (layout_like) and AlexNet conv4 (conv3 and conv5 share its kernels).
+Not here: the training chains at batch 256 (d), XNOR-Net at batch 256, the plane past 2^31 bytes, the DoReFa digit route, the
+channels-last parameter (layout_like) and AlexNet conv4 (conv3 and conv5 share its kernels).  The Lin / Log layers at batch 256
+(level chain and gradients) are in tests/test_gpu_loglin_b256.py.
 Run the whole module: the coverage test reads what the cases before it recorded; it prints the module's peak device memory
 (59 cases; 12.2 GiB and 21 s measured on an MI355X)."""
 import re

@@ -234,10 +234,12 @@ def _explicit_forward(m, x):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dtype,bits,width", [("lin", 8, 16), ("log", 3, 16), ("lin", 8, 64), ("log", 3, 64)])
-def test_vgg_logits_equal_eager_explicit_and_replayed(dev, dtype, bits, width):
+@pytest.mark.parametrize("dtype,bits,width,batch", [("lin", 8, 16, 16), ("log", 3, 16, 16), ("lin", 8, 64, 16), ("log", 3, 64, 16),
+                                                    ("lin", 8, 64, 256), ("log", 3, 64, 256)],          # 256: the benchmarked batch
+                         ids=["lin-8-16", "log-3-16", "lin-8-64", "log-3-64", "lin-8-64-b256", "log-3-64-b256"])
+def test_vgg_logits_equal_eager_explicit_and_replayed(dev, dtype, bits, width, batch):
     m = _vgg(dev, dtype, bits, width)
-    x = torch.randn((16, 3, 32, 32), device=dev)
+    x = torch.randn((batch, 3, 32, 32), device=dev)
     with torch.no_grad():
         with lazy.eager():
             want = m(x).clone()
