@@ -18,9 +18,10 @@ taken (_fused.LIBRARY_PATHS), and records the kernel instances it compared.
   (e) one batch-256 training step of each benchmark model: every backward kernel instance it launches was compared here, is
       torch's own (allow-list with reasons) or is named in KNOWN_UNCOVERED with where it is checked instead.
 
-Not here: the training chains at batch 256 (d), XNOR-Net at batch 256, the plane past 2^31 bytes, the DoReFa digit route, the
+Not here: the training chains at batch 256 (d), the plane past 2^31 bytes, the DoReFa digit route, the
 channels-last parameter (layout_like) and AlexNet conv4 (conv3 and conv5 share its kernels).  The Lin / Log layers at batch 256
-(level chain and gradients) are in tests/test_gpu_loglin_b256.py.
+(level chain and gradients) are in tests/test_gpu_loglin_b256.py, XNOR-Net at batch 256 (tap convs, grad_x) in
+tests/test_gpu_xnor_b256.py.
 Run the whole module: the coverage test reads what the cases before it recorded; it prints the module's peak device memory
 (59 cases; 12.2 GiB and 21 s measured on an MI355X)."""
 import re
@@ -539,7 +540,8 @@ KNOWN_UNCOVERED = [
      "DoReFa chain BatchNorm [+ residual] -> ReLU -> quantiser: vs fp64 at small batch, "
      "tests/test_gpu_r3.py::test_dorefa_training_chain_vs_fp64_of_the_module_chain"),
     (r"ElemF16Taps",
-     "XNOR-Net per-tap grad_x: vs fp64 at small batch, tests/test_gpu_r4.py::test_xnor_conv_function_vs_reference_fp64"),
+     "XNOR-Net per-tap grad_x: bit-exact vs float64 on every configuration and at batch 256, "
+     "tests/test_gpu_xnor_b256.py::test_grad_input_is_bit_exact_on_designed_operands"),
 ]
 
 
