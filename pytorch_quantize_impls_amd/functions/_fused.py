@@ -876,48 +876,25 @@ class QuantConv2dFn(QtFunction):
             grad_output, input, weight = grad_output.float(), input.float(), weight.float()
             weight_q = weight_q.float() if weight_q is not None else None
         go = _dense(grad_output)
-        mfma = (_cfg("BWD_CONV_MFMA") and go.is_cuda and go.dtype == torch.float32 and groups == 1 and not isinstance(padding, str)
-                and go.numel() * weight[0].numel() >= _cfg("BWD_MFMA_MIN_MACS"))
+        mfma = own_conv_backward(go, groups, padding, go.numel() * weight[0].numel())
         if ctx.needs_input_grad[0]:
             if mfma:     # real gradient x +-1 / 0 weight: the forward's exact-split conv on flipped weights (the deterministic
                 #          quantiser runs inside the operand pack; a stochastic draw was saved)
                 grad_input = (ops.conv2d_grad_input_q(input.shape, weight_q, go, stride, padding, dilation) if weight_q is not None
                               else ops.conv2d_grad_input_q(input.shape, weight, go, stride, padding, dilation, kind=ctx.kind))
             if grad_input is None:
-                note_library_path(go, "conv grad_input outside the matrix-core route")
                 wq = weight_q if weight_q is not None else quantize_weight_f32(weight, ctx.kind)
-                grad_input = torch.nn.grad.conv2d_input(input.shape, wq, go, stride=stride, padding=padding,
-                                                        dilation=dilation, groups=groups)
+                grad_input = lib_conv2d_input(input.shape, wq, go, stride, padding, dilation, groups)
         want_bias = ctx.has_bias and ctx.needs_input_grad[2]
         bias_by_product = []              # filled by the weight-gradient route when its gradient pack can sum the channels on the way
         if ctx.needs_input_grad[1]:
-            gw = None
-            if mfma and ctx.x_is_pm1:     # +-1 activation x real gradient, contraction over the pixels
-                if ops.wgrad_pm_applicable(input.shape, go.shape, weight.shape[2:], stride, dilation):
-                    # pixel-major kernel: every tap of a tile in one workgroup; the STE mask of the weight quantiser is the
-                    # epilogue of its reduce step
-                    grad_weight = ops.conv2d_grad_weight_pm(input, go, weight.shape[2:], padding, weight=weight,
-                                                            bias_grad=bias_by_product if want_bias else None)
-                if grad_weight is None and ops.wgrad_gemm_applicable(input.shape, go.shape, weight.shape[2:], stride, dilation):
-                    # batched bf16 GEMMs over K-major planes (other kernel sizes)
-                    grad_weight = ops.conv2d_grad_weight_gemm(input, grad_output, weight.shape[2:], padding, weight=weight)
-                if grad_weight is None and ops.wgrad_strided_applicable(input.shape, go.shape, weight.shape[2:], stride, padding,
-                                                                        dilation):
-                    # strided convs (ResNet stage transitions): 1x1 -> GEMM over the sub-sampled positions, 3x3 -> the
-                    # pixel-major kernel on the space-to-depth image; STE mask below
-                    gw = ops.conv2d_grad_weight_strided(input, go, weight.shape[2:], stride, padding)
-                if grad_weight is None and gw is None:
-                    gw = ops.conv2d_grad_weight_pm1(input, go, weight.shape[2:], stride, padding, dilation)
-            if (mfma and grad_weight is None and gw is None and not ctx.x_is_pm1
-                    and ops.wgrad_s2d_applicable(input.shape, weight.shape[2:], stride, dilation)):
-                # strided first layer over a real-valued image: space-to-depth + the pixel-major kernel
-                grad_weight = ops.conv2d_grad_weight_s2d(input, go, weight.shape, stride, padding, weight=weight,
-                                                         bias_grad=bias_by_product if want_bias else None)
+            if mfma:     # +-1 activation (or the real-valued image of a first layer) x real gradient, contraction over the pixels;
+                #          the STE mask of the weight quantiser comes back applied
+                grad_weight = conv_grad_weight_routes(input, go, weight.shape, stride, padding, dilation,
+                                                      X_PM1 if ctx.x_is_pm1 else X_REAL, weight=weight,
+                                                      bias_grad=bias_by_product if want_bias else None)
             if grad_weight is None:
-                if gw is None:
-                    note_library_path(go, "conv grad_weight outside the matrix-core route")
-                    gw = torch.nn.grad.conv2d_weight(input, weight.shape, go, stride=stride, padding=padding,
-                                                     dilation=dilation, groups=groups)
+                gw = lib_conv2d_weight(input, weight.shape, go, stride, padding, dilation, groups)
                 grad_weight = ste_mask(gw.contiguous(), weight)
         if want_bias:
             grad_bias = bias_by_product[0] if bias_by_product else go.sum((0, 2, 3))
@@ -928,23 +905,6 @@ class QuantConv2dFn(QtFunction):
         if grad_bias is not None and grad_bias.dtype != ctx.bias_dtype:
             grad_bias = grad_bias.to(ctx.bias_dtype)
         return grad_input, grad_weight, grad_bias, None, None, None, None
-
-
-def pm1_conv_grad_weight(input, go, weight_shape, stride, padding, dilation, bias_by_product=None):
-    """UN-masked grad wrt the weight of conv2d(x, .) for a +-1 / 0 activation x on this backend's weight-gradient routes
-    (pixel-major kernel, K-major batched GEMMs, strided forms, swapped conv); None when no route takes the shape.  The callers
-    apply their quantiser's backward to it (STE mask: QuantConv2dFn; the XNOR-Net combination: xnor_connect.py:158-159)."""
-    ksz = weight_shape[2:]
-    gw = None
-    if ops.wgrad_pm_applicable(input.shape, go.shape, ksz, stride, dilation):
-        gw = ops.conv2d_grad_weight_pm(input, go, ksz, padding, weight=None, bias_grad=bias_by_product)
-    if gw is None and ops.wgrad_gemm_applicable(input.shape, go.shape, ksz, stride, dilation):
-        gw = ops.conv2d_grad_weight_gemm(input, go, ksz, padding, weight=None)
-    if gw is None and ops.wgrad_strided_applicable(input.shape, go.shape, ksz, stride, padding, dilation):
-        gw = ops.conv2d_grad_weight_strided(input, go, ksz, stride, padding)
-    if gw is None:
-        gw = ops.conv2d_grad_weight_pm1(input, go, ksz, stride, padding, dilation)
-    return gw
 
 
 # ---- backward of the functional (fused Function) forms ------------------------------------------------------------------------------
@@ -971,6 +931,82 @@ def lib_conv2d_weight(input, weight_shape, grad_output, stride, padding, dilatio
     note_library_path(grad_output, reason)
     return torch.nn.grad.conv2d_weight(input, weight_shape, grad_output, stride=stride, padding=padding, dilation=dilation,
                                        groups=groups)
+
+
+def own_conv_backward(go: torch.Tensor, groups, padding, macs: Optional[int] = None) -> bool:
+    """May the backward of a conv use this backend's own routes for the (dense) gradient ``go``?  The switch is on, a device fp32
+    gradient, groups == 1, numeric zero padding.  ``macs``: the multiply-accumulates of the contraction, held against
+    BWD_MFMA_MIN_MACS (the autograd nodes of the layers); the functional forms leave it out and ask for a non-empty gradient."""
+    return bool(_cfg("BWD_CONV_MFMA") and go.is_cuda and go.dtype == torch.float32 and groups == 1 and not isinstance(padding, str)
+                and (macs is None or macs >= _cfg("BWD_MFMA_MIN_MACS")))
+
+
+#: what the activation of a weight gradient holds (``conv_grad_weight_routes``): +-1 / 0; a k-bit DoReFa image q / n (with
+#: ``x_levels`` = n; also its bare digits, n = 1); Lin / Log levels, exact in bf16 (always with ``terms`` = 3); a real-valued image
+X_PM1, X_CODES, X_LEVELS, X_REAL = "pm1", "codes", "levels", "real"
+
+
+def conv_grad_weight_routes(input, go, weight_shape, stride, padding, dilation, x_kind, x_levels: float = 1.0,
+                            terms: Optional[int] = None, weight: Optional[torch.Tensor] = None,
+                            ste_threshold: float = ops.STE_THRESHOLD, bias_grad: Optional[list] = None,
+                            layout_like: Optional[torch.Tensor] = None, any_channels: bool = False, taken: Optional[list] = None):
+    """THE ladder of this backend's weight-gradient routes: grad wrt the weight of conv2d(x, .) for the dense fp32 gradient ``go``
+    on the first rung whose predicate holds and that returns a result (a rung returns None when its launch plan does not fit the
+    byte budget); None when no rung does — the caller uses the library.  The gate (``own_conv_backward``) is the caller's.
+
+    ``x_kind``: X_PM1 / X_CODES / X_LEVELS / X_REAL.  ``terms``: the split of the gradient on the pixel-major kernel — None =
+    FLOAT_SPLIT, or pinned to 2 / 3.  ``weight``: the result comes back with the quantiser's straight-through mask
+    1[|W| <= ste_threshold] applied, otherwise un-masked (the XNOR-Net combination, DoReFa's and Lin / Log's identity STE).
+    ``bias_grad``: a list that receives the bias gradient when the gradient pack of the rung can sum the channels on the way.
+    ``layout_like``: the parameter — the result takes its memory format where the rung can write it.  ``any_channels``: a
+    real-valued activation of any width may run (channel groups of the pixel-major kernel, else one six-term GEMM per tap).
+    ``taken``: a list that receives the name of the rung that produced the result (tools/bench_conv_backward.py)."""
+    ksz = weight_shape[2:]
+    xs, gs = input.shape, go.shape
+    gw, rung, masked = None, None, True
+    if x_kind != X_REAL:
+        if ops.wgrad_pm_applicable(xs, gs, ksz, stride, dilation):
+            # pixel-major kernel: every tap of a tile in one workgroup; STE mask and bias gradient in its own launches
+            rung = "pm"
+            gw = ops.conv2d_grad_weight_pm(input, go, ksz, padding, weight=weight, ste_threshold=ste_threshold, x_levels=x_levels,
+                                           bias_grad=bias_grad, terms=terms, layout_like=layout_like)
+        # terms pinned to 2: the activation needs the pixel-major kernel's fp16 plane (DoReFa codes beyond +-256), so no rung
+        # that stores it as bf16 — the K-major GEMMs, the strided 1 x 1 form
+        if gw is None and terms != 2 and ops.wgrad_gemm_applicable(xs, gs, ksz, stride, dilation):
+            # batched bf16 GEMMs over K-major planes (other kernel sizes); STE mask in the reduce step
+            rung = "gemm"
+            gw = ops.conv2d_grad_weight_gemm(input, go, ksz, padding, weight=weight, ste_threshold=ste_threshold, x_levels=x_levels)
+        # terms pinned to 3: not the strided k x k form — it runs the pixel-major kernel with the split FLOAT_SPLIT names (and gets
+        # no ``bias_grad``: it never did)
+        if (gw is None and terms != (2 if int(ksz[0]) == 1 else 3)
+                and ops.wgrad_strided_applicable(xs, gs, ksz, stride, padding, dilation)):
+            # strided convs (ResNet stage transitions): 1x1 -> GEMM over the sub-sampled positions, k x k -> the pixel-major
+            # kernel on the space-to-depth image
+            rung, masked = "strided", False
+            gw = ops.conv2d_grad_weight_strided(input, go, ksz, stride, padding, x_levels=x_levels, layout_like=layout_like)
+        if gw is None and x_kind == X_PM1:
+            # the older swapped conv packs sign(x): +-1 / 0 only; it tests its own shapes
+            rung, masked = "swapped", False
+            gw = ops.conv2d_grad_weight_pm1(input, go, ksz, stride, padding, dilation)
+    else:
+        few = ops.wgrad_s2d_applicable(xs, ksz, stride, dilation)
+        if few or (any_channels and ops.wgrad_s2d_applicable(xs, ksz, stride, dilation, True)):
+            # a real-valued image — few channels (first layers, any stride), or any width at stride 1: space-to-depth + the
+            # pixel-major kernel, the image's terms as channel groups
+            rung = "s2d"
+            gw = ops.conv2d_grad_weight_s2d(input, go, weight_shape, stride, padding, weight=weight, ste_threshold=ste_threshold,
+                                            bias_grad=bias_grad, any_channels=not few)
+    if gw is None and any_channels:
+        rung, masked = "taps", False
+        gw = real_conv_grad_weight_taps(input, go, weight_shape, stride, padding, dilation)
+    if gw is None:
+        return None
+    if weight is not None and not masked:
+        from .common import ste_mask
+        gw = ste_mask(gw.contiguous(), weight, ste_threshold)
+    if taken is not None:
+        taken.append(rung)
+    return gw
 
 
 def _hip2d(*ts) -> bool:
@@ -1023,8 +1059,7 @@ def conv_grad_input(input_shape, weight_q, grad_output, stride, padding, dilatio
     "ternary": +-1 / 0; "raw": small integers or multiples of 1/2, the caller scales) on ops.conv2d_grad_input_q; anything else
     (groups, dilation, a real-valued image) on the library, counted."""
     go = _dense(grad_output)
-    if (_cfg("BWD_CONV_MFMA") and kind is not None and go.is_cuda and go.dtype == torch.float32 and groups == 1
-            and not isinstance(padding, str) and go.numel() > 0):
+    if kind is not None and own_conv_backward(go, groups, padding) and go.numel() > 0:
         gx = ops.conv2d_grad_input_q(input_shape, weight_q, go, stride, padding, dilation, kind=kind, out_scale=out_scale,
                                      out_scale_dev=out_scale_dev)
         if gx is not None:
@@ -1037,48 +1072,20 @@ def conv_grad_input(input_shape, weight_q, grad_output, stride, padding, dilatio
     return lib_conv2d_input(input_shape, wq, grad_output, stride, padding, dilation, groups)
 
 
-def levels_conv_grad_weight(input, go, weight_shape, stride, padding, dilation):
-    """UN-masked grad wrt the weight of conv2d(x, .) for an activation whose values are exact in bf16 (Lin / Log levels): the
-    sub-routes of ``pm1_conv_grad_weight`` that store the activation as bf16_rn(x) — the pixel-major kernel with the gradient in
-    three exact bf16 terms, the K-major batched GEMMs, the strided 1 x 1 form.  Left out: the pixel-major kernel's fp16 planes
-    (terms = 2; Log levels reach 2^-126) and therefore the strided k x k form, which picks its split by FLOAT_SPLIT, and the
-    swapped conv, which packs sign(x).  None: the caller keeps the real-valued route."""
-    ksz = weight_shape[2:]
-    if ops.wgrad_pm_applicable(input.shape, go.shape, ksz, stride, dilation):
-        gw = ops.conv2d_grad_weight_pm(input, go, ksz, padding, weight=None, terms=3)
-        if gw is not None:
-            return gw
-    if ops.wgrad_gemm_applicable(input.shape, go.shape, ksz, stride, dilation):
-        gw = ops.conv2d_grad_weight_gemm(input, go, ksz, padding, weight=None)
-        if gw is not None:
-            return gw
-    if int(ksz[0]) == 1 and int(ksz[1]) == 1 and ops.wgrad_strided_applicable(input.shape, go.shape, ksz, stride, padding, dilation):
-        return ops.conv2d_grad_weight_strided(input, go, ksz, stride, padding)
-    return None
-
-
 def conv_grad_weight(input, weight_shape, grad_output, stride, padding, dilation, groups, x_is_pm1: bool, bias_by_product=None,
                      real_any_channels: bool = False, x_exact_bf16: bool = False):
-    """UN-masked grad wrt the weight of conv2d(x, .): +-1 activations on the weight-gradient routes, a real-valued image with few
-    channels (first layers) through the space-to-depth form; anything else on the library, counted.  ``x_exact_bf16``: the
-    activation holds Lin / Log levels (levels_conv_grad_weight first, then the real-valued routes)."""
+    """UN-masked grad wrt the weight of conv2d(x, .) on ``conv_grad_weight_routes``: +-1 activations, a real-valued image with few
+    channels (first layers) or, with ``real_any_channels``, of any geometry; anything else on the library, counted.
+    ``x_exact_bf16``: the activation holds Lin / Log levels — first the rungs that store it as bf16_rn(x), with the gradient in
+    three exact bf16 terms (the pixel-major kernel's fp16 planes are out: Log levels reach 2^-126), then the real-valued ones."""
     go = _dense(grad_output)
-    if (_cfg("BWD_CONV_MFMA") and go.is_cuda and go.dtype == torch.float32 and groups == 1 and not isinstance(padding, str)
-            and go.numel() > 0 and input.dtype == torch.float32):
+    if own_conv_backward(go, groups, padding) and go.numel() > 0 and input.dtype == torch.float32:
         gw = None
         if x_exact_bf16:
-            gw = levels_conv_grad_weight(input, go, weight_shape, stride, padding, dilation)
-            if gw is not None:
-                return gw
-        if x_is_pm1:
-            gw = pm1_conv_grad_weight(input, go, weight_shape, stride, padding, dilation, bias_by_product)
-        elif ops.wgrad_s2d_applicable(input.shape, weight_shape[2:], stride, dilation):
-            gw = ops.conv2d_grad_weight_s2d(input, go, weight_shape, stride, padding, weight=None, bias_grad=bias_by_product)
-        elif real_any_channels and ops.wgrad_s2d_applicable(input.shape, weight_shape[2:], stride, dilation, True):
-            gw = ops.conv2d_grad_weight_s2d(input, go, weight_shape, stride, padding, weight=None, bias_grad=bias_by_product,
-                                            any_channels=True)
-        if gw is None and real_any_channels:
-            gw = real_conv_grad_weight_taps(input, go, weight_shape, stride, padding, dilation)
+            gw = conv_grad_weight_routes(input, go, weight_shape, stride, padding, dilation, X_LEVELS, terms=3)
+        if gw is None:
+            gw = conv_grad_weight_routes(input, go, weight_shape, stride, padding, dilation, X_PM1 if x_is_pm1 else X_REAL,
+                                         bias_grad=bias_by_product, any_channels=real_any_channels)
         if gw is not None:
             return gw
     return lib_conv2d_weight(input, weight_shape, grad_output, stride, padding, dilation, groups)
@@ -1432,27 +1439,22 @@ class DorefaW1Conv2dFn(QtFunction):
         stride, padding, dilation, groups = ctx.conv_args
         go = _dense(grad_output)
         grad_input = grad_weight = grad_bias = None
-        mfma = (_cfg("BWD_CONV_MFMA") and go.is_cuda and go.dtype == torch.float32 and groups == 1 and not isinstance(padding, str)
-                and go.numel() * weight[0].numel() >= _cfg("BWD_MFMA_MIN_MACS"))
+        mfma = own_conv_backward(go, groups, padding, go.numel() * weight[0].numel())
         if ctx.needs_input_grad[0]:
             E = ctx.E if ctx.E is not None else ops.abs_mean(weight)
             if mfma:     # g * (sign(W) E) = E * (g * sign(W)): the exact-split conv on the flipped +-1 weight, scaled after
                 grad_input = ops.conv2d_grad_input_q(input.shape, weight, go, stride, padding, dilation, kind="binary",
                                                      out_scale_dev=E)
             if grad_input is None:
-                note_library_path(go, "conv grad_input outside the matrix-core route")
-                sgn = quantize_weight_f32(weight, "binary")
-                grad_input = torch.nn.grad.conv2d_input(input.shape, sgn * E, go, stride=stride, padding=padding,
-                                                        dilation=dilation, groups=groups)
+                grad_input = lib_conv2d_input(input.shape, quantize_weight_f32(weight, "binary") * E, go, stride, padding, dilation,
+                                              groups)
         if ctx.needs_input_grad[1]:
             if mfma and ctx.x_levels is not None and ctx.x_levels <= 255:
                 # UNscaled and un-masked, as upstream (_ignore_factor_op, identity STE): functions/dorefa_connect.py:66-79
-                grad_weight = dorefa_conv_grad_weight(input, go, weight.shape[2:], stride, padding, dilation, ctx.x_levels,
+                grad_weight = dorefa_conv_grad_weight(input, go, weight.shape, stride, padding, dilation, ctx.x_levels,
                                                       ctx.codes_fit, ctx.code_flag, layout_like=weight)
             if grad_weight is None:
-                note_library_path(go, "conv grad_weight outside the matrix-core route")
-                grad_weight = torch.nn.grad.conv2d_weight(input, weight.shape, go, stride=stride, padding=padding,
-                                                          dilation=dilation, groups=groups)
+                grad_weight = lib_conv2d_weight(input, weight.shape, go, stride, padding, dilation, groups)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             grad_bias = go.sum((0, 2, 3))
         return grad_input, grad_weight, grad_bias, None
@@ -1474,7 +1476,7 @@ def _act_levels(t: torch.Tensor, layout):
     return None
 
 
-def dorefa_conv_grad_weight(input, go, ksz, stride, padding, dilation, x_levels: float, codes_fit: bool, code_flag=None,
+def dorefa_conv_grad_weight(input, go, weight_shape, stride, padding, dilation, x_levels: float, codes_fit: bool, code_flag=None,
                             layout_like=None):
     """grad wrt the (quantised) weight of a DoReFa conv whose activation is a k-bit image q / n (n = ``x_levels``): the
     integer codes q are exact in bf16 while |q| <= 256, so the contraction runs on the weight-gradient routes (pixel-major,
@@ -1487,25 +1489,14 @@ def dorefa_conv_grad_weight(input, go, ksz, stride, padding, dilation, x_levels:
         (256 GW(hi) + GW(lo)) / n (ops.digit_combine: one launch), NaN from |q| >= 2^16 through the device flag.
     ``layout_like``: the parameter — the result takes its memory format where the route can write it (no re-layout copy when
     autograd accumulates it).  No route for the shape: None, the caller uses the library."""
-    def run(xt, levels):
-        gw = None
-        if ops.wgrad_pm_applicable(xt.shape, go.shape, ksz, stride, dilation):
-            gw = ops.conv2d_grad_weight_pm(xt, go, ksz, padding, x_levels=levels, layout_like=layout_like)
-        if gw is None and ops.wgrad_gemm_applicable(xt.shape, go.shape, ksz, stride, dilation):
-            gw = ops.conv2d_grad_weight_gemm(xt, go, ksz, padding, x_levels=levels)
-        if gw is None and ops.wgrad_strided_applicable(xt.shape, go.shape, ksz, stride, padding, dilation):
-            gw = ops.conv2d_grad_weight_strided(xt, go, ksz, stride, padding, x_levels=levels, layout_like=layout_like)
-        return gw
+    def run(xt, levels, terms=None):
+        return conv_grad_weight_routes(xt, go, weight_shape, stride, padding, dilation, X_CODES, x_levels=levels,
+                                       terms=terms, layout_like=layout_like)
 
     if codes_fit:
         return run(input, x_levels)
     if code_flag is not None and ops.split_terms() == 2:
-        gw = None
-        if ops.wgrad_pm_applicable(input.shape, go.shape, ksz, stride, dilation):
-            gw = ops.conv2d_grad_weight_pm(input, go, ksz, padding, x_levels=x_levels, terms=2, layout_like=layout_like)
-        elif int(ksz[0]) > 1 and ops.wgrad_strided_applicable(input.shape, go.shape, ksz, stride, padding, dilation):
-            gw = ops.conv2d_grad_weight_strided(input, go, ksz, stride, padding, x_levels=x_levels,
-                                                layout_like=layout_like)     # the pixel-major kernel too
+        gw = run(input, x_levels, terms=2)            # only the rungs on the pixel-major kernel
         if gw is not None:
             if code_flag.dtype != torch.int32:
                 return gw + torch.where((code_flag.reshape(()) & 2) != 0, float("nan"), 0.0)
@@ -1563,25 +1554,19 @@ class DorefaWkConv2dFn(QtFunction):
         go = _dense(grad_output)
         k = ctx.bit_width
         grad_input = grad_weight = grad_bias = None
-        mfma = (_cfg("BWD_CONV_MFMA") and go.is_cuda and go.dtype == torch.float32 and groups == 1 and not isinstance(padding, str)
-                and go.numel() * weight_q[0].numel() >= _cfg("BWD_MFMA_MIN_MACS"))
+        mfma = own_conv_backward(go, groups, padding, go.numel() * weight_q[0].numel())
         if ctx.needs_input_grad[0]:
             if mfma:
                 grad_input = ops.conv2d_grad_input_q(input.shape, _weight_levels(weight_q, k), go, stride, padding, dilation,
                                                      kind="raw", out_scale=_inv_levels(k))
             if grad_input is None:
-                note_library_path(go, "conv grad_input outside the matrix-core route")
-                grad_input = torch.nn.grad.conv2d_input(input.shape, weight_q, go, stride=stride, padding=padding,
-                                                        dilation=dilation, groups=groups)
+                grad_input = lib_conv2d_input(input.shape, weight_q, go, stride, padding, dilation, groups)
         if ctx.needs_input_grad[1]:
-            ksz = weight_q.shape[2:]
             if mfma and ctx.x_levels is not None:
-                grad_weight = dorefa_conv_grad_weight(input, go, ksz, stride, padding, dilation, ctx.x_levels, ctx.codes_fit,
+                grad_weight = dorefa_conv_grad_weight(input, go, weight_q.shape, stride, padding, dilation, ctx.x_levels, ctx.codes_fit,
                                                       ctx.code_flag)
             if grad_weight is None:
-                note_library_path(go, "conv grad_weight outside the matrix-core route")
-                grad_weight = torch.nn.grad.conv2d_weight(input, weight_q.shape, go, stride=stride, padding=padding,
-                                                          dilation=dilation, groups=groups)
+                grad_weight = lib_conv2d_weight(input, weight_q.shape, go, stride, padding, dilation, groups)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             grad_bias = go.sum((0, 2, 3))
         return grad_input, grad_weight, grad_bias, None, None

@@ -217,8 +217,7 @@ def XNORConv2d(dim=[0, 1], quant_input=False, stride=1, padding=1, dilation=1, g
             input, weight, mean, bias = ctx.saved_tensors
             grad_input = grad_weight = grad_bias = None
             go = _fused._dense(grad_output)
-            mfma = (_fused._cfg("BWD_CONV_MFMA") and ctx.taps is not None and go.is_cuda and go.dtype == torch.float32 and groups == 1
-                    and not isinstance(padding, str))
+            mfma = ctx.taps is not None and _fused.own_conv_backward(go, groups, padding)
             if ctx.needs_input_grad[0]:
                 if mfma:
                     grad_input = ops.conv2d_grad_input_taps(input.shape, weight, go, ctx.taps.bwd, stride, padding, dilation)

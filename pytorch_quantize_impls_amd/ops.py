@@ -3015,6 +3015,20 @@ def _round_up(v: int, m: int) -> int:
     return (v + m - 1) // m * m
 
 
+def _wgrad_stride1_geom(x: torch.Tensor, grad_output: torch.Tensor, kernel_hw, padding):
+    """(N, Cin, H, W, kh, kw, ph, pw) of a stride-1, un-dilated weight gradient on device fp32 operands; None when the batch is
+    empty or the gradient is not the output of that conv over ``x``."""
+    _require(x, "input")
+    _require(grad_output, "grad_output")
+    kh, kw = (int(v) for v in kernel_hw)
+    ph, pw = _pairs(padding)
+    N, Cin, H, W = (int(v) for v in x.shape)
+    N2, _, Ho, Wo = (int(v) for v in grad_output.shape)
+    if N2 != N or Ho != H + 2 * ph - kh + 1 or Wo != W + 2 * pw - kw + 1 or Ho <= 0 or Wo <= 0 or N == 0:
+        return None
+    return N, Cin, H, W, kh, kw, ph, pw
+
+
 def wgrad_gemm_applicable(x_shape, g_shape, kernel_hw, stride, dilation) -> bool:
     """Shapes for which conv2d_grad_weight_gemm beats the fp32 library (tools/check_wgrad_gemm.py, batch 256, MI355X):
     27 x 27 x 192 -> 576 k5 5.1 vs 11.1 ms, 13 x 13 x 576 -> 1152 2.4 vs 4.2, 13 x 13 x 1152 -> 768 3.0 vs 5.5, 28 x 28 x
@@ -3069,14 +3083,11 @@ def conv2d_grad_weight_gemm(x_pm1: torch.Tensor, grad_output: torch.Tensor, kern
     quantiser's straight-through mask 1[|W| <= ste_threshold] to the result.  ``x_levels`` = n: the activation is a k-bit
     DoReFa image q / n (n = 2^k - 1 <= 255); it enters the GEMM as its integer codes (x * n, exact in bf16) and the result
     is scaled by fl(1 / n).  Returns [Cout, Cin, kh, kw] fp32, or None when the shape is outside the route."""
-    _require(x_pm1, "input")
-    _require(grad_output, "grad_output")
-    kh, kw = (int(v) for v in kernel_hw)
-    ph, pw = _pairs(padding)
-    N, Cin, H, W = (int(v) for v in x_pm1.shape)
-    N2, Cout, Ho, Wo = (int(v) for v in grad_output.shape)
-    if N2 != N or Ho != H + 2 * ph - kh + 1 or Wo != W + 2 * pw - kw + 1 or Ho <= 0 or Wo <= 0 or kw > 8 or N == 0:
+    geom = _wgrad_stride1_geom(x_pm1, grad_output, kernel_hw, padding)
+    if geom is None or geom[5] > 8:
         return None
+    N, Cin, H, W, kh, kw, ph, pw = geom
+    _, Cout, Ho, Wo = (int(v) for v in grad_output.shape)
     Wq = _round_up(W + 2 * pw, 8)
     M, taps = 3 * Cout, kh * kw
     ldc = _round_up(Cin, 4)
@@ -3266,15 +3277,10 @@ def conv2d_grad_weight_pm(x_pm1: torch.Tensor, grad_output: torch.Tensor, kernel
     the gradient planes are read once instead of once per tap.  Returns None outside (3, 3) / (5, 5) stride-1 convs.
     ``bias_grad``: see ``_wgrad_pm_run`` (the bias gradient as a by-product of the gradient pack).  ``terms``: how the
     real-valued gradient is split (default: FLOAT_SPLIT — two fp16 terms, or three exact bf16 terms)."""
-    _require(x_pm1, "input")
-    _require(grad_output, "grad_output")
-    kh, kw = (int(v) for v in kernel_hw)
-    ph, pw = _pairs(padding)
-    N, Cin, H, W = (int(v) for v in x_pm1.shape)
-    N2, Cout, Ho, Wo = (int(v) for v in grad_output.shape)
-    if (N2 != N or Ho != H + 2 * ph - kh + 1 or Wo != W + 2 * pw - kw + 1 or Ho <= 0 or Wo <= 0 or N == 0
-            or (kh, kw) not in ((3, 3), (5, 5))):
+    geom = _wgrad_stride1_geom(x_pm1, grad_output, kernel_hw, padding)
+    if geom is None or geom[4:6] not in ((3, 3), (5, 5)):
         return None
+    N, Cin, H, W, kh, kw, ph, pw = geom
     x = x_pm1.detach()
     out_scale = _inv_f32(x_levels)
     I = int
@@ -3285,8 +3291,8 @@ def conv2d_grad_weight_pm(x_pm1: torch.Tensor, grad_output: torch.Tensor, kernel
                   I(xs.stride(2)), I(xs.stride(3)), I(cnt), I(Cin), I(H), I(W), I(ph), I(pw), I(Wq), I(Cpi), I(qx), float(x_levels),
                   _p(XP), st)
 
-    return _wgrad_pm_run(grad_output, (N, Cin, H, W, kh, kw, ph, pw), pack_act, weight, ste_threshold, out_scale, workgroups,
-                         bias_grad, terms=split_terms(terms), layout_like=layout_like)
+    return _wgrad_pm_run(grad_output, geom, pack_act, weight, ste_threshold, out_scale, workgroups, bias_grad,
+                         terms=split_terms(terms), layout_like=layout_like)
 
 
 def wgrad_s2d_applicable(x_shape, kernel_hw, stride, dilation, any_channels: bool = False) -> bool:

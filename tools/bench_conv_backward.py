@@ -4,6 +4,7 @@ import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
 from pytorch_quantize_impls_amd import ops
+from pytorch_quantize_impls_amd.functions import _fused
 dev = torch.device("cuda:0")
 def t(fn, n=5):
     for _ in range(2): fn()
@@ -26,9 +27,9 @@ for (Cin, Cout, k, pd, H, B) in [(192, 576, 5, 2, 27, 256), (576, 1152, 3, 1, 13
     c3 = t(lambda: ops.conv2d_grad_weight_pm(x, g, (k, k), pd)) if ops.wgrad_pm_applicable(x.shape, g.shape, (k, k), 1, 1) else float("nan")
     d = t(lambda: torch.nn.grad.conv2d_weight(x, wq.shape, g, padding=pd))
     gi, gi_ref = ops.conv2d_grad_input_q(x.shape, wq, g, 1, pd, 1), torch.nn.grad.conv2d_input(x.shape, wq, g, padding=pd)
-    pm = ops.wgrad_pm_applicable(x.shape, g.shape, (k, k), 1, 1)
-    gw = ops.conv2d_grad_weight_pm(x, g, (k, k), pd) if pm else ops.conv2d_grad_weight_gemm(x, g, (k, k), pd)
+    taken = []          # the rung the layers' ladder takes for this shape
+    gw = _fused.conv_grad_weight_routes(x, g, wq.shape, 1, pd, 1, _fused.X_PM1, taken=taken)
     gw_ref = torch.nn.grad.conv2d_weight(x, wq.shape, g, padding=pd)
     e1 = float((gi - gi_ref).abs().max() / gi_ref.abs().max()); e2 = float((gw - gw_ref).abs().max() / gw_ref.abs().max())
     print(f"{Cin}->{Cout} k{k} {H}x{H} B{B}: grad_input {a:.3f} ms (MIOpen {b:.3f})  grad_weight: pixel-major {c3:.3f} ms, K-major GEMMs {c2:.3f} ms, swapped conv {c:.3f} ms "
-          f"(MIOpen {d:.3f}; dispatched: {'pixel-major' if pm else 'gemm' if ops.wgrad_gemm_applicable(x.shape, g.shape, (k, k), 1, 1) else 'other'})  |diff| {e1:.1e} {e2:.1e}")
+          f"(MIOpen {d:.3f}; dispatched: {taken[0] if taken else 'library'})  |diff| {e1:.1e} {e2:.1e}")
