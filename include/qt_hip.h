@@ -1076,6 +1076,52 @@ int qt_nib_gemm_variant(int variant, const uint32_t* Xn, int64_t ldxp, const uin
                         int64_t ldwp, const float* bias, float* Y, int64_t ldy, int64_t M,
                         int64_t N, int64_t K, qt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training update: optimiser recurrence + weight clamp + (optionally) the nibble plane of the new weight, for a
+ * whole parameter group in one launch sequence (csrc/optim_step.hip).
+ *
+ * `table` is a HOST array of n descriptors; the library forwards it to the kernel by value in chunks of
+ * qt_optim_chunk_capacity() descriptors (one launch per chunk, no device allocation, no host-to-device copy), so it
+ * may be rebuilt or freed as soon as the call returns.  All tensors are contiguous fp32 device memory:
+ *   p, g       : parameter (updated in place) and its gradient (read only), numel elements, 4-byte aligned; tensors whose
+ *                pointers are all 16-byte aligned are walked with 16-byte loads and stores.
+ *   s0, s1     : state.  SGD with momentum: s0 = momentum_buffer (s1 unused).  Adam: s0 = exp_avg, s1 = exp_avg_sq.
+ *   lo, hi     : the value about to be stored is clamped to [lo, hi] (torch.clamp: NaN stays NaN); -inf / +inf = no clamp.
+ *   c0, c1     : Adam only, per tensor, computed by the caller in double precision from the tensor's step count t:
+ *                c0 = lr / (1 - beta1^t), c1 = sqrt(1 - beta2^t).
+ *   kind       : 0 = no plane; 1 = safeSign plane, 2 = ternary plane of the STORED value, exactly the words
+ *                qt_sign_pack_nib_f32 / qt_ternary_pack_nib_f32 would produce from it (one shared device function):
+ *                p is then a [rows, K] matrix (rows * K == numel), `words` its [rows, ld] nibble plane, ld >= ceil(K/8),
+ *                ld % 4 == 0, 16-byte aligned (QT_ERR_ALIGNMENT otherwise).  Every word of every row up to ld is written,
+ *                pad words and tail nibbles as zero.
+ *   flags      : bit 0 (SGD with momentum): first step of this tensor, momentum_buffer = gradient (its old content is ignored).
+ * The whole table is validated before anything is enqueued (null table with n > 0, negative counts, null tensors,
+ * inconsistent planes: a negative status, nothing launched).
+ *
+ *   qt_optim_sgd_f32  : torch.optim.SGD with dampening 0: g += weight_decay p; buf = momentum buf + g; g = nesterov ?
+ *                       g + momentum buf : buf; p -= lr g.  momentum == 0: no state is read (nesterov must be 0).
+ *   qt_optim_adam_f32 : torch.optim.Adam (L2 weight decay, no amsgrad): g += weight_decay p; m = beta1 m + (1 - beta1) g;
+ *                       v = beta2 v + (1 - beta2) g g; p -= c0 m / (sqrt(v) / c1 + eps).  One rounding per operation.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct qt_optim_tensor {
+    float* p;
+    const float* g;
+    float* s0;
+    float* s1;
+    int64_t numel;
+    uint32_t* words;
+    int64_t ld, rows, K;
+    float lo, hi, c0, c1;
+    int32_t kind;
+    int32_t flags;
+} qt_optim_tensor;
+
+int qt_optim_chunk_capacity(void);
+int qt_optim_sgd_f32(const qt_optim_tensor* table, int64_t n, float lr, float momentum, float weight_decay, int nesterov,
+                     qt_stream_t stream);
+int qt_optim_adam_f32(const qt_optim_tensor* table, int64_t n, float beta1, float one_minus_beta1, float beta2,
+                      float one_minus_beta2, float eps, float weight_decay, qt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -209,6 +209,9 @@ SIGNATURES = {
                                                                              _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
     "qt_nib_gemm_variant": (_c_int, [_c_int, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64,
                                      _c_i64, _c_i64, _c_p]),
+    "qt_optim_chunk_capacity": (_c_int, []),
+    "qt_optim_sgd_f32": (_c_int, [_c_p, _c_i64, _c_f32, _c_f32, _c_f32, _c_int, _c_p]),
+    "qt_optim_adam_f32": (_c_int, [_c_p, _c_i64] + [_c_f32] * 6 + [_c_p]),
 }
 
 _lock = threading.Lock()

@@ -49,6 +49,7 @@
 #include <cstdio>
 #include "mfma_gemm_kernel.h"
 #include "qt_elt.h"
+#include "nib_quant.h"
 
 namespace {
 
@@ -129,25 +130,7 @@ int dispatch_gemm(int variant, const uint32_t* Xn, int64_t ldxp, const uint32_t*
 }
 
 // ---- fp32 / bf16 / fp16 -> nibble plane (element types: qt_elt.h) ---------------------------------
-struct NibSign {  // safeSign: +1 -> 0x2, -1 -> 0xA
-    __device__ __forceinline__ static uint32_t nib(float x) { return x < 0.0f ? 0xAu : 0x2u; }
-    template <class E> __device__ __forceinline__ static uint32_t nib(uint16_t h) { return E::neg(h) ? 0xAu : 0x2u; }
-};
-struct NibTernary {  // TernaryConnectDeterministic: 0 -> 0x0
-    __device__ __forceinline__ static uint32_t nib(float x) {
-        const float t = qt_ternarize(x);
-        return t == 0.0f ? 0x0u : (t < 0.0f ? 0xAu : 0x2u);
-    }
-    template <class E> __device__ __forceinline__ static uint32_t nib(uint16_t h) {
-        const int t = E::tern(h);
-        return t == 0 ? 0x0u : (t < 0 ? 0xAu : 0x2u);
-    }
-};
-
-struct NibSign0 {  // torch.sign: 0 (and NaN) -> 0x0 — the XNOR-Net weight image sign(W) (functions/xnor_connect.py:141)
-    __device__ __forceinline__ static uint32_t nib(float x) { return x > 0.0f ? 0x2u : (x < 0.0f ? 0xAu : 0x0u); }
-};
-
+// (the nibble codes NibSign / NibTernary / NibSign0: nib_quant.h, shared with the training update)
 template <class Enc>
 __device__ __forceinline__ uint32_t nib_half(const float4& v) {   // 4 elements -> 16 bits
     return Enc::nib(v.x) | (Enc::nib(v.y) << 4) | (Enc::nib(v.z) << 8) | (Enc::nib(v.w) << 12);

@@ -1,0 +1,292 @@
+// Training update: one multi-tensor launch per parameter group (include/qt_hip.h "Training update").
+//
+// For every tensor of a host table the kernel applies the optimiser recurrence (torch.optim.SGD / torch.optim.Adam,
+// one rounding per operation, -ffp-contract=off), clamps the value it is about to store to the tensor's [lo, hi]
+// (what the layer's clamp() would do in a second pass) and, for the weight of a deterministic LinearBin / LinearTer,
+// writes the fp4 nibble plane of that stored value: the operand the next training forward would otherwise produce by
+// reading the whole fp32 weight again.
+//
+// HBM-bound: 3 (SGD) or 4 (Adam) fp32 streams read, 2 or 3 written, 1/8 of one stream for a plane.  No LDS, no
+// cross-lane traffic, plain vector stores.
+//
+//   * The table travels as a BY-VALUE kernel argument in chunks of QT_OPTIM_CHUNK descriptors: no device allocation
+//     and no host-to-device copy per step.  Next to the descriptors a chunk carries the prefix sums of the tensors'
+//     UNITS; a workgroup walks units grid-strided and finds its tensor by advancing a (wave-uniform) index along the
+//     prefix, so the grid is sized from the whole chunk, not from one tensor.
+//   * flat tensors: unit = 4096 consecutive elements.  16-byte loads / stores when every pointer of the tensor is
+//     16-byte aligned (full units: four independent dwordx4 per stream and lane in flight; the numel % 4 tail goes
+//     to the first lanes of the last unit), a dword-per-lane walk otherwise (views at odd element offsets).
+//   * plane tensors ([rows, K] weight, plane [rows, ld] words): unit = 512 plane words, walked by (row, word).  One
+//     lane owns the 8 consecutive K elements of one word (two dwordx4 per stream when K % 4 == 0 and the pointers
+//     allow it, scalar otherwise) and stores the word; words from ceil(K/8) to ld and the tail nibbles of a row's
+//     last word are written as zero, so the plane may be uninitialised memory.
+#include "qt_common.h"
+#include "nib_quant.h"
+
+#define QT_OPTIM_CHUNK 32
+
+namespace {
+
+constexpr int FLAG_FIRST = 1;          // public: first step of an SGD momentum buffer (buf = grad)
+constexpr int FLAG_VEC = 1 << 8;       // library-internal: every pointer 16-byte aligned (plane tensors: and K % 4 == 0)
+constexpr int FLAT_UNIT = 4096;        // elements
+constexpr int PLANE_UNIT = 512;        // plane words = 4096 elements
+
+struct OptimChunk {
+    qt_optim_tensor t[QT_OPTIM_CHUNK];
+    int32_t ustart[QT_OPTIM_CHUNK + 1];   // units of tensor i: [ustart[i], ustart[i + 1])
+    int32_t n;
+};
+
+// torch.optim.SGD (dampening 0): g += wd p ; buf = first ? g : mu buf + g ; g = nesterov ? g + mu buf : buf ; p -= lr g
+template <int NS_>
+struct SgdRule {
+    static constexpr int NS = NS_;        // state tensors: 0 (no momentum) or 1
+    float lr, mu, wd;
+    int nesterov;
+    __device__ __forceinline__ void operator()(float& p, float g, float& s0, float&, const qt_optim_tensor& t) const {
+        if (wd != 0.0f) g = g + wd * p;
+        if (NS == 1) {
+            const float b = (t.flags & FLAG_FIRST) ? g : s0 * mu + g;
+            s0 = b;
+            g = nesterov ? g + mu * b : b;
+        }
+        p = p - lr * g;
+    }
+};
+
+// torch.optim.Adam (L2 weight decay, no amsgrad).  t.c0 = lr / (1 - beta1^step), t.c1 = sqrt(1 - beta2^step): computed by
+// the host in double precision from the tensor's own step count.
+struct AdamRule {
+    static constexpr int NS = 2;
+    float b1, omb1, b2, omb2, eps, wd;
+    __device__ __forceinline__ void operator()(float& p, float g, float& m, float& v, const qt_optim_tensor& t) const {
+        if (wd != 0.0f) g = g + wd * p;
+        m = b1 * m + omb1 * g;
+        v = b2 * v + omb2 * (g * g);
+        const float denom = sqrtf(v) / t.c1 + eps;
+        p = p - t.c0 * (m / denom);
+    }
+};
+
+// torch.clamp: NaN stays NaN; lo = -inf / hi = +inf leave the value alone
+__device__ __forceinline__ float clamp_store(float p, float lo, float hi) { return p < lo ? lo : (p > hi ? hi : p); }
+
+__device__ __forceinline__ float& at(float4& v, int i) { return reinterpret_cast<float*>(&v)[i]; }
+
+template <class Rule>
+__device__ __forceinline__ void update4(const Rule& r, const qt_optim_tensor& t, float4& p, const float4& g, float4& s0,
+                                        float4& s1) {
+    r(p.x, g.x, s0.x, s1.x, t);
+    r(p.y, g.y, s0.y, s1.y, t);
+    r(p.z, g.z, s0.z, s1.z, t);
+    r(p.w, g.w, s0.w, s1.w, t);
+    p.x = clamp_store(p.x, t.lo, t.hi);
+    p.y = clamp_store(p.y, t.lo, t.hi);
+    p.z = clamp_store(p.z, t.lo, t.hi);
+    p.w = clamp_store(p.w, t.lo, t.hi);
+}
+
+template <class Rule>
+__device__ __forceinline__ float update1(const Rule& r, const qt_optim_tensor& t, int64_t i) {
+    float p = t.p[i], s0 = 0.0f, s1 = 0.0f;
+    if (Rule::NS >= 1) s0 = t.s0[i];
+    if (Rule::NS >= 2) s1 = t.s1[i];
+    r(p, t.g[i], s0, s1, t);
+    p = clamp_store(p, t.lo, t.hi);
+    t.p[i] = p;
+    if (Rule::NS >= 1) t.s0[i] = s0;
+    if (Rule::NS >= 2) t.s1[i] = s1;
+    return p;
+}
+
+template <class Rule>
+__device__ __forceinline__ void load4(const qt_optim_tensor& t, int64_t i4, float4& p, float4& g, float4& s0, float4& s1) {
+    p = reinterpret_cast<const float4*>(t.p)[i4];
+    g = reinterpret_cast<const float4*>(t.g)[i4];
+    if (Rule::NS >= 1) s0 = reinterpret_cast<const float4*>(t.s0)[i4];
+    if (Rule::NS >= 2) s1 = reinterpret_cast<const float4*>(t.s1)[i4];
+}
+
+template <class Rule>
+__device__ __forceinline__ void store4(const qt_optim_tensor& t, int64_t i4, const float4& p, const float4& s0, const float4& s1) {
+    reinterpret_cast<float4*>(t.p)[i4] = p;
+    if (Rule::NS >= 1) reinterpret_cast<float4*>(t.s0)[i4] = s0;
+    if (Rule::NS >= 2) reinterpret_cast<float4*>(t.s1)[i4] = s1;
+}
+
+// unit b of a flat tensor: elements [4096 b, min(numel, 4096 (b + 1)))
+template <class Rule>
+__device__ __forceinline__ void flat_unit(const Rule& r, const qt_optim_tensor& t, int64_t b) {
+    const int tid = threadIdx.x;
+    const int64_t base = b * FLAT_UNIT;
+    if (!(t.flags & FLAG_VEC)) {
+#pragma unroll 4
+        for (int j = 0; j < FLAT_UNIT / 256; ++j) {
+            const int64_t i = base + j * 256 + tid;
+            if (i < t.numel) update1(r, t, i);
+        }
+        return;
+    }
+    const int64_t i0 = b * (FLAT_UNIT / 4) + tid;
+    if (base + FLAT_UNIT <= t.numel) {        // full unit: every load of the lane issued before the first use
+        float4 p[4], g[4], s0[4], s1[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) load4<Rule>(t, i0 + 256 * j, p[j], g[j], s0[j], s1[j]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            update4(r, t, p[j], g[j], s0[j], s1[j]);
+            store4<Rule>(t, i0 + 256 * j, p[j], s0[j], s1[j]);
+        }
+        return;
+    }
+    const int64_t n4 = t.numel >> 2;          // the tensor's last unit
+    for (int j = 0; j < 4; ++j) {
+        const int64_t i4 = i0 + 256 * j;
+        if (i4 < n4) {
+            float4 p, g, s0, s1;
+            load4<Rule>(t, i4, p, g, s0, s1);
+            update4(r, t, p, g, s0, s1);
+            store4<Rule>(t, i4, p, s0, s1);
+        }
+    }
+    const int64_t e = n4 * 4 + tid;           // numel % 4 tail elements (they lie in this unit)
+    if (e < t.numel) update1(r, t, e);
+}
+
+__device__ __forceinline__ uint32_t nib_code(int kind, float x) { return kind == 2 ? NibTernary::nib(x) : NibSign::nib(x); }
+
+// unit b of a plane tensor: plane words [512 b, min(rows ld, 512 (b + 1))) in (row, word) order
+template <class Rule>
+__device__ __forceinline__ void plane_unit(const Rule& r, const qt_optim_tensor& t, int64_t b) {
+    const int64_t total = t.rows * t.ld;
+    const bool vec = t.flags & FLAG_VEC;
+#pragma unroll
+    for (int j = 0; j < PLANE_UNIT / 256; ++j) {
+        const int64_t wi = b * PLANE_UNIT + j * 256 + threadIdx.x;
+        if (wi >= total) continue;
+        const int64_t row = wi / t.ld, col = wi - row * t.ld;
+        const int64_t k0 = col * 8;
+        uint32_t word = 0;
+        if (k0 < t.K) {
+            const int64_t e0 = row * t.K + k0;
+            const int nk = (int)(t.K - k0 < 8 ? t.K - k0 : 8);
+            if (vec) {                          // K % 4 == 0: nk is 4 or 8
+                const int64_t i4 = e0 >> 2;
+                float4 p0, g0, a0, c0, p1, g1, a1, c1;
+                load4<Rule>(t, i4, p0, g0, a0, c0);
+                if (nk == 8) load4<Rule>(t, i4 + 1, p1, g1, a1, c1);
+                update4(r, t, p0, g0, a0, c0);
+                store4<Rule>(t, i4, p0, a0, c0);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) word |= nib_code(t.kind, at(p0, i)) << (4 * i);
+                if (nk == 8) {
+                    update4(r, t, p1, g1, a1, c1);
+                    store4<Rule>(t, i4 + 1, p1, a1, c1);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) word |= nib_code(t.kind, at(p1, i)) << (16 + 4 * i);
+                }
+            } else {
+                for (int i = 0; i < nk; ++i) word |= nib_code(t.kind, update1(r, t, e0 + i)) << (4 * i);
+            }
+        }
+        t.words[wi] = word;
+    }
+}
+
+template <class Rule>
+__global__ __launch_bounds__(256) void optim_step_kernel(const OptimChunk c, const Rule r) {
+    const int total = c.ustart[c.n];
+    int ti = 0;
+    for (int u = blockIdx.x; u < total; u += gridDim.x) {
+        while (c.ustart[ti + 1] <= u) ++ti;          // u < total = ustart[n]: stops at ti < n
+        const qt_optim_tensor& t = c.t[ti];
+        const int64_t b = u - c.ustart[ti];
+        if (t.kind != 0) plane_unit(r, t, b);
+        else flat_unit(r, t, b);
+    }
+}
+
+template <class Rule>
+int check_tensor(const qt_optim_tensor& t) {
+    if (t.numel < 0) return QT_ERR_INVALID_ARG;
+    if (t.kind < 0 || t.kind > 2) return QT_ERR_INVALID_ARG;
+    if (t.numel > 0 && (!t.p || !t.g)) return QT_ERR_INVALID_ARG;
+    if (t.numel > 0 && ((Rule::NS >= 1 && !t.s0) || (Rule::NS >= 2 && !t.s1))) return QT_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.g)) & 3u) return QT_ERR_ALIGNMENT;
+    if (Rule::NS >= 1 && (reinterpret_cast<uintptr_t>(t.s0) & 3u)) return QT_ERR_ALIGNMENT;
+    if (Rule::NS >= 2 && (reinterpret_cast<uintptr_t>(t.s1) & 3u)) return QT_ERR_ALIGNMENT;
+    if (t.kind != 0) {
+        if (t.rows < 0 || t.K < 0 || t.ld < 0) return QT_ERR_INVALID_ARG;
+        if (t.rows > 0 && t.K > (int64_t)INT64_MAX / t.rows) return QT_ERR_INVALID_ARG;
+        if (t.rows * t.K != t.numel) return QT_ERR_INVALID_ARG;
+        if (t.rows > 0 && !t.words) return QT_ERR_INVALID_ARG;
+        if (t.ld < (t.K + 7) / 8 || (t.ld & 3) != 0 || !qt_aligned16(t.words)) return QT_ERR_ALIGNMENT;
+        if (t.rows > 0 && t.ld > (int64_t)INT64_MAX / t.rows) return QT_ERR_INVALID_ARG;
+    }
+    return QT_OK;
+}
+
+int64_t tensor_units(const qt_optim_tensor& t) {
+    if (t.kind != 0) return (t.rows * t.ld + PLANE_UNIT - 1) / PLANE_UNIT;
+    return (t.numel + FLAT_UNIT - 1) / FLAT_UNIT;
+}
+
+template <class Rule>
+int launch_chunk(const OptimChunk& c, const Rule& r, qt_stream_t stream) {
+    const int total = c.ustart[c.n];
+    if (c.n == 0 || total == 0) return QT_OK;
+    hipLaunchKernelGGL(optim_step_kernel<Rule>, dim3(qt_stream_grid(total)), dim3(256), 0, (hipStream_t)stream, c, r);
+    return qt_check_launch();
+}
+
+template <class Rule>
+int optim_step(const qt_optim_tensor* tab, int64_t n, const Rule& r, qt_stream_t stream) {
+    if (n < 0 || (n > 0 && !tab)) return QT_ERR_INVALID_ARG;
+    for (int64_t i = 0; i < n; ++i) {              // the whole table is checked before anything is enqueued
+        const int rc = check_tensor<Rule>(tab[i]);
+        if (rc != QT_OK) return rc;
+        if (tensor_units(tab[i]) > INT32_MAX) return QT_ERR_UNSUPPORTED;
+    }
+    OptimChunk c{};
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t units = tensor_units(tab[i]);
+        if (units == 0) continue;                  // empty tensor
+        if (c.n == QT_OPTIM_CHUNK || (int64_t)c.ustart[c.n] + units > INT32_MAX) {
+            const int rc = launch_chunk(c, r, stream);
+            if (rc != QT_OK) return rc;
+            c.n = 0;
+        }
+        qt_optim_tensor& t = c.t[c.n];
+        t = tab[i];
+        bool vec = qt_aligned16(t.p) && qt_aligned16(t.g) && (Rule::NS < 1 || qt_aligned16(t.s0)) &&
+                   (Rule::NS < 2 || qt_aligned16(t.s1));
+        if (t.kind != 0) vec = vec && (t.K % 4 == 0);
+        if (Rule::NS < 1) t.s0 = nullptr;
+        if (Rule::NS < 2) t.s1 = nullptr;
+        t.flags = (t.flags & FLAG_FIRST) | (vec ? FLAG_VEC : 0);
+        c.ustart[c.n + 1] = c.ustart[c.n] + (int32_t)units;
+        ++c.n;
+    }
+    return launch_chunk(c, r, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int qt_optim_chunk_capacity(void) { return QT_OPTIM_CHUNK; }
+
+int qt_optim_sgd_f32(const qt_optim_tensor* table, int64_t n, float lr, float momentum, float weight_decay, int nesterov,
+                     qt_stream_t stream) {
+    if (nesterov && momentum == 0.0f) return QT_ERR_INVALID_ARG;
+    if (momentum != 0.0f) return optim_step(table, n, SgdRule<1>{lr, momentum, weight_decay, nesterov ? 1 : 0}, stream);
+    return optim_step(table, n, SgdRule<0>{lr, 0.0f, weight_decay, 0}, stream);
+}
+
+int qt_optim_adam_f32(const qt_optim_tensor* table, int64_t n, float beta1, float one_minus_beta1, float beta2,
+                      float one_minus_beta2, float eps, float weight_decay, qt_stream_t stream) {
+    return optim_step(table, n, AdamRule{beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay}, stream);
+}
+
+}  // extern "C"

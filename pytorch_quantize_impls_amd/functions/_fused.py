@@ -1878,7 +1878,9 @@ class QuantLinearFn(QtFunction):
     """
 
     @staticmethod
-    def forward(ctx, input, weight, bias, kind, weight_q, binary_input):
+    def forward(ctx, input, weight, bias, kind, weight_q, binary_input, weight_planes=None):
+        """``weight_planes``: the ready nibble plane of Q(weight) (written by the fused optimiser step, utils/optim.py) — the forward
+        then packs the activation alone.  The backward does not use it: it reads the fp32 weight."""
         ctx.kind = kind
         ctx.has_bias = bias is not None
         ctx.bias_dtype = bias.dtype if bias is not None else None
@@ -1888,7 +1890,8 @@ class QuantLinearFn(QtFunction):
         ctx.x_is_pm1 = bool(split_hint(binary_input)[0]) or (input.is_cuda and input.dtype in ops.PACK_DTYPES
                                               and packed.lookup(input, packed.ROWS_LAST) is not None)
         clear_last_detection()
-        out = quant_linear_forward(input, weight, bias, kind, weight_q=weight_q, binary_input=binary_input, half_ok=True)
+        out = quant_linear_forward(input, weight, bias, kind, weight_q=weight_q, weight_planes=weight_planes, binary_input=binary_input,
+                                   half_ok=True)
         if not ctx.x_is_pm1 and binary_input is None and input.is_cuda:
             # un-tagged activation THIS forward detected as +-1 (a reshaped / flattened sign image): the backward's g^T . x then
             # runs on the matrix cores as well instead of the dense library
@@ -1936,4 +1939,4 @@ class QuantLinearFn(QtFunction):
             grad_weight = grad_weight.to(w_dtype)
         if grad_bias is not None and grad_bias.dtype != ctx.bias_dtype:
             grad_bias = grad_bias.to(ctx.bias_dtype)
-        return grad_input, grad_weight, grad_bias, None, None, None
+        return grad_input, grad_weight, grad_bias, None, None, None, None

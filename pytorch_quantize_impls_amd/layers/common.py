@@ -37,6 +37,7 @@ class EvalSwapMixin:
             return self
         self.training = mode
         self._qt_eval_planes = None
+        self._drop_train_planes()
         if mode:
             self.weight.data.copy_(self.weight.org.data)
         else:
@@ -62,10 +63,20 @@ class EvalSwapMixin:
     def reset_quant_cache(self):
         """Drop the packed planes / scales cached for the eval-mode weight (needed after a manual ``weight.data`` edit)."""
         self._qt_eval_planes = None
+        self._drop_train_planes()
 
     def _load_from_state_dict(self, *args, **kwargs):
         super()._load_from_state_dict(*args, **kwargs)
         self._qt_eval_planes = None
+        self._drop_train_planes()
+
+    def _drop_train_planes(self):
+        """Forget the nibble plane a fused optimiser step recorded for the training-mode weight (``weight._qt_train_planes``,
+        utils/optim.py).  Like the eval cache it is valid for one (version counter, storage) of the weight; train() / eval(),
+        load_state_dict() and reset_quant_cache() write through ``weight.data`` or replace the values, so they drop it."""
+        w = getattr(self, "weight", None)
+        if w is not None and getattr(w, "_qt_train_planes", None) is not None:
+            w._qt_train_planes = None
 
     def _eval_planes(self, packer, key="valu"):
         """Packed image of the eval-mode (already quantised) weight in the operand format ``key``;

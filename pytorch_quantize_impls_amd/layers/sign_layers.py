@@ -53,9 +53,31 @@ class _SignLinear(EvalSwapMixin, torch.nn.Linear, QLayer):
             return torch.nn.functional.linear(input, w, self.bias)
         if self.training:
             wq = None if self.deterministic else self._op.apply(self.weight.detach())
+            wp = self._train_planes(input)
+            if wp is not None:      # the plane the fused optimiser step wrote next to the weight: the activation is packed alone
+                return _fused.QuantLinearFn.apply(input, self.weight, self.bias, self.kind, wq, self.binary_input, wp)
             return _fused.QuantLinearFn.apply(input, self.weight, self.bias, self.kind, wq, self.binary_input)
         # eval: weight already holds the quantised image; planes are cached
         return self._eval_forward(input)
+
+    def _train_planes(self, input):
+        """The nibble plane of Q(weight) recorded by a fused optimiser step (utils/optim.py: ``weight._qt_train_planes``), when it
+        still describes the weight — same version counter and storage — and this call would pack the weight for the matrix-core
+        GEMM; else None.  Writes through ``weight.data`` do not bump the version counter (the hazard documented for the eval
+        cache: ``reset_quant_cache()`` after one); the layer's own ``clamp()`` through ``.data`` cannot change a sign or ternary
+        code and the fused step has already applied it."""
+        w = self.weight
+        rec = getattr(w, "_qt_train_planes", None)
+        if rec is None or not self.deterministic:
+            return None
+        if rec["version"] != w._version or rec["ptr"] != w.data_ptr():
+            return None
+        K, N = input.shape[-1], w.shape[0]
+        if _fused.ops.select_gemm_impl(_fused._cfg("GEMM_IMPL"), input.numel() // max(K, 1), N, K) != "mfma":
+            return None
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        return rec["mfma"]
 
     def _half_forward(self, input):
         """bf16 / fp16 device activation (``_fused.half_route``): the packed routes when it is tagged, hinted or detected as +-1 —

@@ -8,6 +8,7 @@ A CPU tensor is a programming error here (``TypeError``) — there is no fallbac
 from __future__ import annotations
 
 import contextlib
+import ctypes as _ct
 import threading
 import functools
 from dataclasses import dataclass
@@ -3692,3 +3693,108 @@ def packed_gemm_algorithmic_bytes(M: int, N: int, K: int, impl: str = "valu", pl
     if impl == "valu":
         return M * K / 8.0 + planes_w * N * K / 8.0 + 4.0 * M * N + (4.0 * N if bias else 0.0)
     return M * K / 2.0 + N * K / 2.0 + 4.0 * M * N + (4.0 * N if bias else 0.0)
+
+
+# ---- training update: optimiser recurrence + clamp + nibble plane of the new weight (csrc/optim_step.hip) ----
+
+class _OptimTensor(_ct.Structure):
+    """qt_optim_tensor of include/qt_hip.h."""
+    _fields_ = [("p", _ct.c_void_p), ("g", _ct.c_void_p), ("s0", _ct.c_void_p), ("s1", _ct.c_void_p), ("numel", _ct.c_int64),
+                ("words", _ct.c_void_p), ("ld", _ct.c_int64), ("rows", _ct.c_int64), ("K", _ct.c_int64),
+                ("lo", _ct.c_float), ("hi", _ct.c_float), ("c0", _ct.c_float), ("c1", _ct.c_float),
+                ("kind", _ct.c_int32), ("flags", _ct.c_int32)]
+
+
+_PLANE_KIND = {"binary": 1, "ternary": 2}
+_INF = float("inf")
+
+
+def optim_chunk_capacity() -> int:
+    """Tensor descriptors per launch of the training update (the table is forwarded by value in chunks of this many)."""
+    return int(_lib.load().qt_optim_chunk_capacity())
+
+
+def _optim_route_check(t: torch.Tensor, like: Optional[torch.Tensor], name: str) -> None:
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and not t.is_sparse):
+        raise TypeError(f"{name}: the training-update kernel takes contiguous fp32 tensors on a HIP device "
+                        f"(got {t.dtype}, device {t.device}, contiguous={t.is_contiguous()})")
+    if like is not None and (t.device != like.device or t.numel() != like.numel()):
+        raise ValueError(f"{name}: device / size differs from its parameter's")
+
+
+def _optim_table(params, grads, s0, s1, clamps, planes):
+    """ctypes table of the descriptors every recurrence shares (pointers, sizes, clamp range, plane); returns (table, device)."""
+    n = len(params)
+    if not (len(grads) == n and (s0 is None or len(s0) == n) and (s1 is None or len(s1) == n)
+            and (clamps is None or len(clamps) == n) and (planes is None or len(planes) == n)):
+        raise ValueError("optim_step: the tensor lists differ in length")
+    tab = (_OptimTensor * max(n, 1))()
+    dev = params[0].device if n else None
+    for i in range(n):
+        p, g, e = params[i], grads[i], tab[i]
+        _optim_route_check(p, None, "parameter")
+        _optim_route_check(g, p, "gradient")
+        if p.device != dev:
+            raise ValueError("optim_step: one call takes the tensors of one device")
+        e.p, e.g, e.numel = p.data_ptr(), g.data_ptr(), p.numel()
+        if s0 is not None:
+            _optim_route_check(s0[i], p, "optimiser state")
+            e.s0 = s0[i].data_ptr()
+        if s1 is not None:
+            _optim_route_check(s1[i], p, "optimiser state")
+            e.s1 = s1[i].data_ptr()
+        lo, hi = clamps[i] if clamps is not None and clamps[i] is not None else (-_INF, _INF)
+        e.lo, e.hi = lo, hi
+        pl = planes[i] if planes is not None else None
+        if pl is not None:
+            nib, kind = pl
+            w = nib.words
+            if not (w.dtype == torch.int32 and w.is_contiguous() and w.device == dev and w.dim() == 2
+                    and int(w.shape[0]) == nib.rows and nib.rows * nib.K == p.numel()):
+                raise ValueError("optim_step: plane is not the [rows, ld] int32 nibble plane of its parameter")
+            e.words, e.ld, e.rows, e.K, e.kind = w.data_ptr(), int(w.shape[1]), nib.rows, nib.K, _PLANE_KIND[kind]
+    return tab, dev
+
+
+def optim_step_sgd(params, grads, momentum_buffers=None, *, lr: float, momentum: float = 0.0, weight_decay: float = 0.0,
+                   nesterov: bool = False, first=None, clamps=None, planes=None) -> None:
+    """One torch.optim.SGD step (dampening 0) of every tensor in the lists, in place, in one launch sequence
+    (qt_optim_sgd_f32): ``p`` is clamped to ``clamps[i] = (lo, hi)`` as it is stored and, where ``planes[i] =
+    (NibPlanes, "binary" | "ternary")`` is given, the nibble plane of the stored weight is written into those words.
+    ``first[i]``: this is the tensor's first step, its momentum buffer becomes the gradient.  The version counters of the
+    parameters are NOT touched: the caller bumps them (utils.FusedQuantSGD does)."""
+    if not params:
+        return
+    use_mom = momentum != 0
+    if use_mom and momentum_buffers is None:
+        raise ValueError("optim_step_sgd: momentum needs the momentum buffers")
+    tab, dev = _optim_table(params, grads, momentum_buffers if use_mom else None, None, clamps, planes)
+    if use_mom and first is not None:
+        for i, f in enumerate(first):
+            if f:
+                tab[i].flags = 1
+    with _on(dev):
+        _lib.call("qt_optim_sgd_f32", _ct.addressof(tab), len(params), float(lr), float(momentum), float(weight_decay),
+                  int(bool(nesterov)), _stream(dev))
+
+
+def optim_step_adam(params, grads, exp_avgs, exp_avg_sqs, steps, *, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                    weight_decay: float = 0.0, clamps=None, planes=None) -> None:
+    """One torch.optim.Adam step (L2 weight decay, no amsgrad) in one launch sequence (qt_optim_adam_f32).  ``steps[i]``: the
+    step count of tensor i INCLUDING this step; its bias corrections are computed here, in double precision.  Clamp, planes
+    and version counters as in ``optim_step_sgd``."""
+    if not params:
+        return
+    b1, b2 = float(betas[0]), float(betas[1])
+    tab, dev = _optim_table(params, grads, exp_avgs, exp_avg_sqs, clamps, planes)
+    if len(steps) != len(params):
+        raise ValueError("optim_step: the tensor lists differ in length")
+    corr = {}
+    for i, t in enumerate(steps):
+        c = corr.get(t)
+        if c is None:
+            c = corr[t] = (lr / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5)
+        tab[i].c0, tab[i].c1 = c
+    with _on(dev):
+        _lib.call("qt_optim_adam_f32", _ct.addressof(tab), len(params), b1, 1.0 - b1, b2, 1.0 - b2, float(eps),
+                  float(weight_decay), _stream(dev))
