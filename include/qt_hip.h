@@ -9,8 +9,9 @@
  * Conventions (all entry points):
  *   - plain `extern "C"`, raw DEVICE pointers + explicit sizes/strides, no torch types;
  *   - stateless and re-entrant: no allocation, no ownership transfer, no process-global state of any kind (kernel
- *     variants for tests / tuning are ARGUMENTS of the *_variant entry points); the only thing that survives a call is
- *     what it wrote into caller-provided buffers;
+ *     variants for tests / tuning are ARGUMENTS: `variant` of the *_variant entry points, the QT_CONV_* flags of the convs;
+ *     a default build reads no environment variable); the only thing that survives a call is what it wrote into
+ *     caller-provided buffers;
  *   - work is enqueued on `stream` (a hipStream_t, passed as an opaque pointer; NULL = the
  *     default stream) and the call returns without synchronising;
  *   - the caller has already made the right device current (hipSetDevice);
@@ -214,7 +215,7 @@ int qt_xnor_act_backward_f32(const float* g, int64_t ldg, const float* x, int64_
 /* Diagnostic: launches of the persistent direct 3 x 3 code conv (csrc/code_conv3x3.hip) since the library was loaded.
  * qt_conv2d_implicit_codes takes that kernel for 3 x 3 / stride 1 / padding 1 layers with 64 or 128 input channels, Cout % 64 == 0
  * and power-of-two maps (models/Resnet/Resnet_bin.py:63-97 stages 1 and 2), bit-identical to its implicit-GEMM route; tests use the
- * counter to assert which route ran.  Setting the environment variable QT_NO_CODE_CONV3X3 (read per call) keeps every conv on the
+ * counter to assert which route ran.  The flag QT_CONV_NO_DIRECT_CODES of qt_conv2d_implicit_codes keeps that call on the
  * implicit-GEMM kernel. */
 int64_t qt_code_conv3x3_launch_count(void);
 
@@ -860,10 +861,19 @@ int qt_conv2d_implicit_h(const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, 
                          int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw, const uint32_t* Wmat, int64_t ldwp,
                          const float* bias, void* Y, int dtype, int64_t ldy, int64_t Cout, qt_stream_t stream);
 
+/* A/B flags of the implicit-GEMM convs (tests / tuning; arguments, not process state).  They sit above the tile form
+ * (the low 4 bits of `variant` below); every flag selects another kernel that computes the same bits.  Unknown bits are
+ * QT_ERR_INVALID_ARG, checked before anything is launched. */
+#define QT_CONV_NO_DEEP_RING 0x10       /* the double-buffered ConvV128x128 / ConvV128x64 instead of the ring-of-stages ...D forms */
+#define QT_CONV_COMPARE_THRESHOLDS 0x20 /* integer thresholds: the compare-form epilogue (ElemFp4) instead of the sign-bit form */
+#define QT_CONV_NO_DIRECT_CODES 0x40    /* qt_conv2d_implicit_codes: never the persistent direct 3 x 3 kernel (csrc/code_conv3x3.hip) */
+#define QT_CONV_FLAGS_MASK 0x70
+
 /* qt_conv2d_implicit with the main loop chosen by the caller (tests / tuning; an argument, not process state):
- * variant 0 = automatic (ping-pong 384x192 tile for 192-wide column tiles, double-buffered otherwise),
- * 1 = double-buffered, 2 = ping-pong, 4 = automatic without the un-padded fast path (A/B only);
- * 3 (stamped kernel, Y garbage) exists only in -DQT_PROFILING_VARIANTS builds and is QT_ERR_UNSUPPORTED otherwise. */
+ * variant = form | QT_CONV_* flags; form 0 = automatic (ping-pong 384x192 tile for 192-wide column tiles, double-buffered
+ * otherwise), 1 = double-buffered, 2 = ping-pong, 4 = automatic without the un-padded fast path (A/B only), 5 / 6 = the
+ * padded 128x128 / skinny tiles; 3 (stamped kernel, Y garbage) exists only in -DQT_PROFILING_VARIANTS builds and is
+ * QT_ERR_UNSUPPORTED otherwise. */
 int qt_conv2d_implicit_variant(int variant, int elem, const uint32_t* P, int64_t N, int64_t H, int64_t W, int64_t Cw,
                                int64_t kh, int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw,
                                int64_t dh, int64_t dw, const uint32_t* Wmat, int64_t ldwp, const float* bias,
@@ -881,12 +891,14 @@ int qt_conv2d_implicit_variant(int variant, int elem, const uint32_t* P, int64_t
  * |acc| <= K,  fl(fl(acc + bias_c)*alpha_c) + beta_c < 0  <=>  (acc < T_c) xor (alpha_c < 0)  — the left side is a
  * monotone step function of the integer acc, so T_c exists and the caller finds it by bisection once per layer.  The
  * kernel then spends one compare per output instead of add + multiply + compare ("BatchNorm + sign collapses to a
- * per-channel integer threshold on the popcount"); bias / beta are ignored, the sign of alpha is still read. */
+ * per-channel integer threshold on the popcount"); bias / beta are ignored, the sign of alpha is still read.
+ * flags: QT_CONV_* bits (0 = the default kernels); the tile form stays automatic. */
 int qt_conv2d_implicit_bits(int elem, const uint32_t* P, int64_t N, int64_t H, int64_t W, int64_t Cw,
                             int64_t kh, int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw,
                             int64_t dh, int64_t dw, const uint32_t* Wmat, int64_t ldwp, const float* bias,
                             float scale, const float* scale_dev, const float* alpha, const float* beta,
-                            const float* thr, uint32_t* neg_plane, int64_t ldb, int64_t Cout, qt_stream_t stream);
+                            const float* thr, uint32_t* neg_plane, int64_t ldb, int64_t Cout, int flags,
+                            qt_stream_t stream);
 
 /* qt_conv2d_implicit_bits with the sign bits written as the NEXT conv's operand instead: an fp4 nibble pixel plane
  * (+1 = 0x2, -1 = 0xA, channels >= Cout zero), nib_plane [N][Ho + 2*out_halo_h][Wo + 2*out_halo_w][ldn words],
@@ -896,13 +908,14 @@ int qt_conv2d_implicit_bits(int elem, const uint32_t* P, int64_t N, int64_t H, i
  * d2s_cout != 0 (depth-to-space by 2): Cout == 4*d2s_cout columns ordered (dy, dx, channel) are written to pixel
  * (2*ho + dy, 2*wo + dx) of a [N][2*Ho + 2*halo_h][2*Wo + 2*halo_w][ldn] plane with d2s_cout channels
  * (ldn == ceil(d2s_cout/32)*4, d2s_cout % 32 == 0): the epilogue of the 2x2 output-blocked form of a few-channel
- * stride-1 3x3 first layer (a 4x4 stride-2 conv embedding the four shifted copies of the 3x3 kernel). */
+ * stride-1 3x3 first layer (a 4x4 stride-2 conv embedding the four shifted copies of the 3x3 kernel).
+ * flags: as qt_conv2d_implicit_bits. */
 int qt_conv2d_implicit_nib(int elem, const uint32_t* P, int64_t N, int64_t H, int64_t W, int64_t Cw,
                            int64_t kh, int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh,
                            int64_t dw, const uint32_t* Wmat, int64_t ldw, const float* bias, float scale,
                            const float* scale_dev, const float* alpha, const float* beta, const float* thr,
                            uint32_t* nib_plane, int64_t ldn, int64_t Cout, int64_t out_halo_h, int64_t out_halo_w,
-                           int64_t d2s_cout, qt_stream_t stream);
+                           int64_t d2s_cout, int flags, qt_stream_t stream);
 
 /* ---- direct first-layer conv (csrc/conv_first_direct.hip) ---------------------------------------------------------------------------
  * conv2d(x, Q(W), bias, stride S, padding (PH, PW)) for a REAL-valued fp32 image with a few channels (C <= Cp <= 8) and a large /
@@ -1026,7 +1039,8 @@ int qt_pool_bits_nib(const uint32_t* in_plane, int64_t N, int64_t H, int64_t W, 
  * the un-padded kernels (no per-tap bounds checks).  in_halo_*: halo of P (needs ph <= in_halo_h, pw <= in_halo_w;
  * QT_ERR_UNSUPPORTED when the plane exceeds 4 GiB); out_halo_*: halo of `codes` — the launch writes
  * the interior pixels and the zero border (every byte of the plane); res_halo_*: halo of `res_codes`.
- * bn_stats / res_bn_stats: the device BatchNorm arithmetic of qt_affine_dorefa_codes_i8 ([mean | rs], alpha / beta = weight / bias). */
+ * bn_stats / res_bn_stats: the device BatchNorm arithmetic of qt_affine_dorefa_codes_i8 ([mean | rs], alpha / beta = weight / bias).
+ * flags: as qt_conv2d_implicit_bits; QT_CONV_NO_DIRECT_CODES keeps the call off the direct 3 x 3 kernel. */
 int qt_conv2d_implicit_codes(int elem, const uint32_t* P, int64_t N, int64_t H, int64_t W, int64_t Cw,
                              int64_t kh, int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh,
                              int64_t dw, const uint32_t* Wmat, int64_t ldw, const float* bias, float scale,
@@ -1035,7 +1049,8 @@ int qt_conv2d_implicit_codes(int elem, const uint32_t* P, int64_t N, int64_t H, 
                              int64_t ldrc_bytes, float res_scale, int relu, int bit_width, int8_t* codes,
                              int64_t ldc_bytes, int64_t Cout, int32_t* overflow, int64_t in_halo_h,
                              int64_t in_halo_w, int64_t out_halo_h, int64_t out_halo_w, int64_t res_halo_h,
-                             int64_t res_halo_w, const float* bn_stats, const float* res_bn_stats, qt_stream_t stream);
+                             int64_t res_halo_w, const float* bn_stats, const float* res_bn_stats, int flags,
+                             qt_stream_t stream);
 
 /* qt_conv2d_implicit reading a halo plane P [N][H + 2*halo_h][W + 2*halo_w][Cw] (see qt_conv2d_implicit_codes):
  * fp32 output as qt_conv2d_implicit.  ph <= halo_h, pw <= halo_w. */

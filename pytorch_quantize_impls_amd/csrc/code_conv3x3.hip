@@ -369,7 +369,6 @@ int qt_code_conv3x3_try(const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, i
                         const int8_t* res_codes, int64_t ldrc_bytes, float res_scale, int relu, int bit_width, int8_t* codes,
                         int64_t ldc_bytes, int64_t Cout, int32_t* overflow, int64_t ihy, int64_t ihx, int64_t ohy, int64_t ohx,
                         int64_t rhy, int64_t rhx, const float* bn_stats, qt_stream_t stream) {
-    if (getenv("QT_NO_CODE_CONV3X3")) return QT_ERR_UNSUPPORTED;          // A/B switch for tools and tests (read per call)
     const int64_t CB = Cw * 4;
     if (kh != 3 || kw != 3 || sh != 1 || sw != 1 || ph != 1 || pw != 1 || dh != 1 || dw != 1 || ihy < 1 || ihx < 1) return QT_ERR_UNSUPPORTED;
     if ((CB != 64 && CB != 128) || Cout <= 0 || (Cout & 63) || ldc_bytes != Cout || ldwp * 4 < 9 * CB) return QT_ERR_UNSUPPORTED;
@@ -387,24 +386,22 @@ int qt_code_conv3x3_try(const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, i
     const int64_t tiles_m = (rows_total + RT - 1) / RT, tiles_n = Cout / 64;
     const int64_t patch_rows = RT <= H ? RT + 2 : (RT / H) * Hp;
     const int64_t patch_bytes = (patch_rows * Wp * CB + 255) / 256 * 256;
-    // tool-only switches (occupancy / order / loader-mode experiments) are read ONCE per process: no environment walk on the
-    // launch-bound module-graph path and no race with a concurrent setenv; the one A/B switch tests flip inside a
-    // process, QT_NO_CODE_CONV3X3 above, stays per call as include/qt_hip.h documents
-    struct C3Env { const char* mode; bool plain_order; int per_cu; };
+#ifdef QT_PROFILING_VARIANTS
+    // tool-only switches (loader-mode / order / occupancy experiments; make EXTRA=-DQT_PROFILING_VARIANTS), read ONCE per process;
+    // the default build reads no environment: mode by CB, XCD order, LDS-bound per_cu
+    struct C3Env { int mode; bool plain_order; int per_cu; };
     static const C3Env env = [] {
         C3Env e;
-        e.mode = getenv("QT_C3_MODE");
+        const char* fm = getenv("QT_C3_MODE");
+        e.mode = fm ? atoi(fm) : -1;
         e.plain_order = getenv("QT_C3_PLAIN_ORDER") != nullptr;
         const char* pc = getenv("QT_C3_PER_CU");
         e.per_cu = pc ? atoi(pc) : 0;
         return e;
     }();
-    const char* fm0 = env.mode;
-#ifdef QT_PROFILING_VARIANTS
-    const bool single = fm0 && atoi(fm0) == 5;                                  // profiling builds: the single-buffer variant
+    const bool single = env.mode == 5;                                          // the single-buffer variant
 #else
     const bool single = false;
-    (void)fm0;
 #endif
     const int64_t lds = single ? 64 * 9 * CB + std::max<int64_t>(patch_bytes, 4 * 4096) : 64 * 9 * CB + 2 * patch_bytes + 4 * 4096;
     if (lds > 160 * 1024 || tiles_m * tiles_n > (1 << 30)) return QT_ERR_UNSUPPORTED;
@@ -423,19 +420,23 @@ int qt_code_conv3x3_try(const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, i
     a.res_codes = res_codes; a.ldrc = (int)ldrc_bytes; a.rhy = (int)rhy; a.rhx = (int)rhx;
     a.Q = codes; a.ldq = (int)ldc_bytes; a.ohy = (int)ohy; a.ohx = (int)ohx;
     a.overflow = overflow;
-    a.no_xcd_order = env.plain_order ? 1 : 0;
+    a.no_xcd_order = 0;
     // persistent grid: as many workgroups as stay resident (LDS-bound), a multiple of the column tiles
     int per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(4, (160 * 1024) / lds));
+#ifdef QT_PROFILING_VARIANTS
+    a.no_xcd_order = env.plain_order ? 1 : 0;
     if (env.per_cu > 0) per_cu = std::max(1, std::min(per_cu, env.per_cu));     // tools: occupancy experiments
+#endif
     int64_t grid = std::min<int64_t>(tiles_m * tiles_n, 256ll * per_cu);
     grid = std::max<int64_t>(tiles_n, grid / tiles_n * tiles_n);
     hipStream_t st = (hipStream_t)stream;
     // MODE 0: the compute waves issue the next patch's DMA themselves; MODE 2: a fifth (loader) wave does.  Measured per launch
     // (tools/probes/c3_modes.sh, batch 256): 64 -> 64 @ 32 x 32: 22.8 / 29.4 us, 128 -> 128 @ 16 x 16: 23.8 / 22.4 us
-    // (implicit-GEMM kernel: 29.0 / 24.2 us).  QT_C3_MODE overrides (tools only; 1 / 3 / 4 exist in profiling builds).
-    const char* fm = env.mode;
-    const int forced = fm ? atoi(fm) : -1;
-    const int mode = forced >= 0 ? forced : (CB == 64 ? 0 : 2);
+    // (implicit-GEMM kernel: 29.0 / 24.2 us).  QT_C3_MODE overrides in profiling builds (tools only; 1 / 3 / 4 / 5 exist there).
+    int mode = CB == 64 ? 0 : 2;
+#ifdef QT_PROFILING_VARIANTS
+    if (env.mode >= 0) mode = env.mode;
+#endif
 #define QT_C3(CBV, MD)                                                                                                              \
     do {                                                                                                                            \
         static QtLdsOnce once;                                                                                                      \

@@ -439,8 +439,12 @@ int qt_conv3x3_first_f32(const float* x, int64_t stride_n, int64_t stride_c, int
     const dim3 grid((unsigned)(ntiles < 512 ? ntiles : 512));      // persistent: two workgroups per CU
     hipStream_t st = (hipStream_t)stream;
     // three workgroups per CU without the register-hungry pipelining beat two with it: 174 vs 212 us inside the C5 graph, batch 256
-    // (tools/probes/c5_graph_kernels.py).  QT_F3_OCC=2 (tools only, read once): the pipelined form.
+    // (tools/probes/c5_graph_kernels.py).  QT_F3_OCC=2 (profiling builds only, read once): the pipelined form.
+#ifdef QT_PROFILING_VARIANTS
     static const int occ = [] { const char* e = getenv("QT_F3_OCC"); return e ? atoi(e) : 3; }();
+#else
+    const int occ = 3;
+#endif
     const dim3 grid4((unsigned)(ntiles < 768 ? ntiles : 768));
 #define QT_F3(M)                                                                                         \
     do {                                                                                                 \

@@ -693,9 +693,13 @@ extern "C" int qt_conv3x3_direct_nib(int elem, const uint32_t* P, int64_t N, int
     g.scale = 1.0f; g.scale_dev = nullptr; g.rscale = 0.0f; g.levels = 0.0f; g.res_codes = nullptr; g.ldrc = 0; g.relu = 0;
     g.overflow = nullptr;
     // the lean fp4 epilogue: 64 / 128 output channels (whole tiles), 32-bit byte offsets into the output plane, bit rows of 2 / 4 words;
-    // QT_D3_EPI=general keeps the general form (A/B runs and the bit-identity test)
+    // QT_D3_EPI=general (profiling builds only, read once) keeps the general form for A/B runs
     {
+#ifdef QT_PROFILING_VARIANTS
         static const bool general = [] { const char* e = getenv("QT_D3_EPI"); return e && e[0] == 'g'; }();
+#else
+        const bool general = false;
+#endif
         const long long out_bytes = out_bits ? N * H * W * ldo * 4 : g.total * ldo * 4;
         const bool whole = Cout == 64 || Cout == 128;      // every column block of the tile shapes below is a real one
         const bool bits_ok = Cout == 128 ? ldo == 4 : (Cw == 8 && (ldo == 4 || ldo == 2));

@@ -579,7 +579,8 @@ int qt_i8_gemm_splitk(const uint32_t* Xc, int64_t ldxp, const uint32_t* Wc, int6
 #undef QT_GOZ
 }
 
-// conv kernel variant (an ARGUMENT of qt_conv2d_implicit_variant; every other entry point passes 0): 0 = automatic
+// conv kernel variant = tile form | QT_CONV_* flags (an ARGUMENT: qt_conv2d_implicit_variant takes both, the bits / nib / codes entries
+// the flags only, every other entry point passes 0; no environment is read in a default build).  Tile form: 0 = automatic
 // (192-wide tiles: ping-pong on a 384x192 tile, whose 96x96 wave tiles keep the load segment under the compute segment:
 // AlexNet conv2 302 -> 275 us; other widths: double-buffered, equal or faster there), 1 = double-buffered, 2 = ping-pong,
 // 4 = automatic without the un-padded fast path; 3 = stamped 384x192 ping-pong, only in -DQT_PROFILING_VARIANTS builds
@@ -590,11 +591,12 @@ static int conv_implicit_impl(int elem, const uint32_t* P, int64_t Nimg, int64_t
                               int64_t kh, int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh,
                               int64_t dw, const uint32_t* Wmat, int64_t ldwp, const float* bias, float scale,
                               const float* scale_dev, float* Y, int64_t ldy, int64_t Cout, qt_stream_t stream,
-                              const EpiArgs& epi_in, int64_t hy = 0, int64_t hx = 0, int g_conv_force = 0, int out_dtype = 0) {
+                              const EpiArgs& epi_in, int64_t hy = 0, int64_t hx = 0, int variant = 0, int out_dtype = 0) {
     // out_dtype (fp4 planes, plain epilogue only): QT_DTYPE_BF16 / QT_DTYPE_F16 = Y holds 2-byte elements (ElemFp4Out)
     // (hy, hx): halo of the INPUT plane, [N][H + 2hy][W + 2hx][Cw] with a zero border: a conv whose padding fits in
     // the halo runs as the un-padded conv on the window that starts (hy - ph, hx - pw) into the plane.
     EpiArgs epi = epi_in;
+    int g_conv_force = variant & 0xf;          // the entry points have refused unknown bits
 #ifdef QT_EXPERIMENT   // A/B builds only (make EXTRA=-DQT_EXPERIMENT): a variant for the entry points that take none
     if (g_conv_force == 0 && getenv("QT_CONV_FORCE_EXP")) g_conv_force = atoi(getenv("QT_CONV_FORCE_EXP"));
 #endif
@@ -616,16 +618,15 @@ static int conv_implicit_impl(int elem, const uint32_t* P, int64_t Nimg, int64_t
 #define QT_CONV_STAMPS(E)
     if (g_conv_force == 3) return QT_ERR_UNSUPPORTED;
 #endif
-    // ring of 3 / 4 stage buffers on the small-map tiles (ConvV128x128D / ConvV128x64D); QT_NO_CONV_DEEP_RING=1: the double-buffered
-    // configurations of round 4 (A/B runs and the bit-identity test; read per call like the direct kernel's switches)
-    const bool deep_ring = !getenv("QT_NO_CONV_DEEP_RING");
-    // fewer 256-row tiles than this: 128 x 128 tiles with the deep ring (QT_SMALL_GRID: A/B runs)
-    const long long small_grid = getenv("QT_SMALL_GRID") ? atoll(getenv("QT_SMALL_GRID")) : 128;
-    const long long small_tiles = getenv("QT_SMALL_TILES") ? atoll(getenv("QT_SMALL_TILES")) : 512;
+    // ring of 3 / 4 stage buffers on the small-map tiles (ConvV128x128D / ConvV128x64D); QT_CONV_NO_DEEP_RING: the double-buffered
+    // configurations of round 4 (A/B runs and the bit-identity test)
+    const bool deep_ring = !(variant & QT_CONV_NO_DEEP_RING);
+    // at most this many 256-row tiles and 128 x 128 tiles: 128 x 128 tiles with the deep ring (A/B: profiles/r6_c3_pmc.md)
+    const long long small_grid = 128, small_tiles = 512;
     // weights-as-rows threshold epilogue (sign-bit form): fp4, integer thresholds, whole 32-channel blocks, bit plane or nibble plane
-    // out, no depth-to-space; QT_NO_SWAPT=1: the compare form (A/B runs and the bit-identity test; read per call like the line above)
+    // out, no depth-to-space; QT_CONV_COMPARE_THRESHOLDS: the compare form (A/B runs and the bit-identity test)
     const bool swapt = elem == 0 && epi.alpha && epi.thr && (Cout & 31) == 0 && !epi.d2s_cout && (epi.mode == 0 || epi.mode == 3) &&
-                       !getenv("QT_NO_SWAPT");
+                       !(variant & QT_CONV_COMPARE_THRESHOLDS);
     // the level epilogue (mode 5) walks the tiles of the plain conv of its geometry: the accumulators are then the same bits
     const bool plain_tiles = (!epi.alpha && epi.mode == 0) || epi.mode == 5;
 #define QT_CONV(E)                                                                                              \
@@ -720,7 +721,7 @@ int qt_conv2d_implicit_variant(int variant, int elem, const uint32_t* P, int64_t
                                int64_t kh, int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh,
                                int64_t dw, const uint32_t* Wmat, int64_t ldwp, const float* bias, float scale,
                                const float* scale_dev, float* Y, int64_t ldy, int64_t Cout, qt_stream_t stream) {
-    if (variant < 0 || variant > 6) return QT_ERR_INVALID_ARG;
+    if (variant < 0 || (variant & ~(0xf | QT_CONV_FLAGS_MASK)) || (variant & 0xf) > 6) return QT_ERR_INVALID_ARG;
     return conv_implicit_impl(elem, P, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, Wmat, ldwp, bias, scale,
                               scale_dev, Y, ldy, Cout, stream, EpiArgs{}, 0, 0, variant);
 }
@@ -745,8 +746,8 @@ int qt_conv2d_implicit_bits(int elem, const uint32_t* P, int64_t Nimg, int64_t H
                             int64_t kh, int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh,
                             int64_t dw, const uint32_t* Wmat, int64_t ldwp, const float* bias, float scale,
                             const float* scale_dev, const float* alpha, const float* beta, const float* thr,
-                            uint32_t* neg_plane, int64_t ldb, int64_t Cout, qt_stream_t stream) {
-    if (!alpha || !beta) return QT_ERR_INVALID_ARG;
+                            uint32_t* neg_plane, int64_t ldb, int64_t Cout, int flags, qt_stream_t stream) {
+    if (!alpha || !beta || (flags & ~QT_CONV_FLAGS_MASK)) return QT_ERR_INVALID_ARG;
     if (thr && elem >= 2) return QT_ERR_INVALID_ARG;       // integer thresholds need integer accumulators
     if (ldb & 3) return QT_ERR_ALIGNMENT;
     EpiArgs epi;
@@ -754,7 +755,7 @@ int qt_conv2d_implicit_bits(int elem, const uint32_t* P, int64_t Nimg, int64_t H
     epi.beta = beta;
     epi.thr = thr;
     return conv_implicit_impl(elem, P, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, Wmat, ldwp, bias, scale,
-                              scale_dev, reinterpret_cast<float*>(neg_plane), ldb, Cout, stream, epi);
+                              scale_dev, reinterpret_cast<float*>(neg_plane), ldb, Cout, stream, epi, 0, 0, flags);
 }
 
 int qt_conv2d_implicit_nib(int elem, const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, int64_t Cw,
@@ -762,8 +763,8 @@ int qt_conv2d_implicit_nib(int elem, const uint32_t* P, int64_t Nimg, int64_t H,
                            int64_t dw, const uint32_t* Wmat, int64_t ldwp, const float* bias, float scale,
                            const float* scale_dev, const float* alpha, const float* beta, const float* thr,
                            uint32_t* nib_plane, int64_t ldn, int64_t Cout, int64_t out_halo_h, int64_t out_halo_w,
-                           int64_t d2s_cout, qt_stream_t stream) {
-    if (!alpha || !beta) return QT_ERR_INVALID_ARG;
+                           int64_t d2s_cout, int flags, qt_stream_t stream) {
+    if (!alpha || !beta || (flags & ~QT_CONV_FLAGS_MASK)) return QT_ERR_INVALID_ARG;
     if (thr && elem >= 2) return QT_ERR_INVALID_ARG;       // integer thresholds need integer accumulators
     if (out_halo_h < 0 || out_halo_w < 0 || out_halo_h > 64 || out_halo_w > 64) return QT_ERR_INVALID_ARG;
     if ((ldn & 3) || !qt_aligned16(nib_plane)) return QT_ERR_ALIGNMENT;
@@ -779,7 +780,7 @@ int qt_conv2d_implicit_nib(int elem, const uint32_t* P, int64_t Nimg, int64_t H,
     epi.ohx = (int)out_halo_w;
     epi.d2s_cout = (int)d2s_cout;
     return conv_implicit_impl(elem, P, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, Wmat, ldwp, bias, scale,
-                              scale_dev, reinterpret_cast<float*>(nib_plane), ldn, Cout, stream, epi);
+                              scale_dev, reinterpret_cast<float*>(nib_plane), ldn, Cout, stream, epi, 0, 0, flags);
 }
 
 int qt_conv2d_implicit_codes(int elem, const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, int64_t Cw,
@@ -790,7 +791,9 @@ int qt_conv2d_implicit_codes(int elem, const uint32_t* P, int64_t Nimg, int64_t 
                              int64_t ldrc_bytes, float res_scale, int relu, int bit_width, int8_t* codes,
                              int64_t ldc_bytes, int64_t Cout, int32_t* overflow, int64_t in_halo_h,
                              int64_t in_halo_w, int64_t out_halo_h, int64_t out_halo_w, int64_t res_halo_h,
-                             int64_t res_halo_w, const float* bn_stats, const float* res_bn_stats, qt_stream_t stream) {
+                             int64_t res_halo_w, const float* bn_stats, const float* res_bn_stats, int flags,
+                             qt_stream_t stream) {
+    if (flags & ~QT_CONV_FLAGS_MASK) return QT_ERR_INVALID_ARG;
     if (res_bn_stats || (bn_stats && res_alpha)) return QT_ERR_UNSUPPORTED;   // device form: the residual arrives normalised
     if (!alpha || !beta || !overflow || bit_width < 2 || bit_width > 8 || relu < 0 || relu > 2) return QT_ERR_INVALID_ARG;
     if (out_halo_h < 0 || out_halo_w < 0 || res_halo_h < 0 || res_halo_w < 0 || out_halo_h > 64 || out_halo_w > 64 ||
@@ -820,7 +823,8 @@ int qt_conv2d_implicit_codes(int elem, const uint32_t* P, int64_t Nimg, int64_t 
     epi.rhy = (int)res_halo_h;
     epi.rhx = (int)res_halo_w;
     epi.bn_stats = bn_stats;
-    {   // small-channel 3 x 3 / stride 1 layers: the persistent direct kernel (code_conv3x3.hip), bit-identical codes
+    // small-channel 3 x 3 / stride 1 layers: the persistent direct kernel (code_conv3x3.hip), bit-identical codes
+    if (!(flags & QT_CONV_NO_DIRECT_CODES)) {
         const int rc = qt_code_conv3x3_try(P, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, Wmat, ldwp, bias, scale, scale_dev, alpha,
                                            beta, res_f32, res_alpha, res_codes, ldrc_bytes, res_scale, relu, bit_width, codes, ldc_bytes,
                                            Cout, overflow, in_halo_h, in_halo_w, out_halo_h, out_halo_w, res_halo_h, res_halo_w, bn_stats,
@@ -829,7 +833,7 @@ int qt_conv2d_implicit_codes(int elem, const uint32_t* P, int64_t Nimg, int64_t 
     }
     return conv_implicit_impl(elem, P, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, Wmat, ldwp, bias, scale,
                               scale_dev, reinterpret_cast<float*>(codes), ldc_bytes, Cout, stream, epi, in_halo_h,
-                              in_halo_w);
+                              in_halo_w, flags);
 }
 
 int qt_conv2d_implicit_levels(const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, int64_t Cw, int64_t in_halo_h, int64_t in_halo_w,

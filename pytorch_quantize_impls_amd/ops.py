@@ -32,8 +32,10 @@ CONV_IMPLICIT = True
 # ``with ops.scope(FIRST_DIRECT=False):`` changes what THIS thread's calls read and nothing else (two serving threads of one
 # process can hold different routes: SURVEY 8e "one process, one stream per device"); library code reads every switch through
 # ``_cfg``.  The autograd Functions of the package record the scope their forward ran under and re-open it around their backward
-# (functions.common.QtFunction), like ``float_split``.
-_SCOPED = ("FIRST_DIRECT", "CONV_IMPLICIT", "POPC_VARIANT", "CONV_VARIANT", "ASSUME_CODES_FIT", "PAD_PIXEL_PLANES", "FIRST_3X3", "DIRECT_BITS_128")
+# (functions.common.QtFunction), like ``float_split``: the whole override dict is recorded, so every name of ``_SCOPED``, ``CONV_FLAGS``
+# included, is thread-local and follows the autograd graph into backward with no code of its own.
+_SCOPED = ("FIRST_DIRECT", "CONV_IMPLICIT", "POPC_VARIANT", "CONV_VARIANT", "CONV_FLAGS", "ASSUME_CODES_FIT", "PAD_PIXEL_PLANES", "FIRST_3X3",
+           "DIRECT_BITS_128")
 _scope_tls = threading.local()
 
 
@@ -51,12 +53,15 @@ def scope_overrides():
 
 @contextlib.contextmanager
 def scope(_overrides=None, **kw):
-    """Thread-local overrides of the route switches (names: ``_SCOPED``); nests; ``scope(None)`` is a no-op."""
+    """Thread-local overrides of the route switches (names: ``_SCOPED``); nests; ``scope(None)`` is a no-op.
+    A launch captured into a hipGraph keeps the switches it was captured with: a replay reads no scope."""
     if _overrides:
         kw = {**_overrides, **kw}
     bad = [k for k in kw if k not in _SCOPED]
     if bad:
         raise KeyError(f"not a scoped switch of ops: {bad} (known: {_SCOPED})")
+    if int(kw.get("CONV_FLAGS", 0)) & ~CONV_FLAGS_MASK:
+        raise ValueError(f"unknown CONV_FLAGS bits: {kw['CONV_FLAGS']:#x} (known: {CONV_FLAGS_MASK:#x})")
     prev = getattr(_scope_tls, "ov", None)
     if kw:
         _scope_tls.ov = {**(prev or {}), **kw}
@@ -224,7 +229,7 @@ def _conv_implicit(elem: int, pixels_words: torch.Tensor, N, H, W, Cw, kh, kw, g
             _lib.call("qt_conv2d_implicit_codes", *head, _p(alpha), _p(beta), _p(rf), I(ldr), _p(ra), _p(rb), _p(rc),
                       I(ldrc), float(rscale), relu_mode(epi.relu),
                       int(int(epi.bit_width)), _p(codes), I(ldc), I(Cout), _p(flag), I(hy), I(hx), I(ohy),
-                      I(ohx), I(rhy), I(rhx), _p(stats), _p(rstats), _stream(dev))
+                      I(ohx), I(rhy), I(rhx), _p(stats), _p(rstats), int(_cfg("CONV_FLAGS")), _stream(dev))
         inv_n = inv_levels(epi.bit_width)
         return CodePlanes(codes=codes, rows=Mo, K=Cout, inv_n=inv_n, bit_width=int(epi.bit_width), overflow=flag)
     if isinstance(epi, BnEpilogue):
@@ -251,7 +256,7 @@ def _conv_implicit(elem: int, pixels_words: torch.Tensor, N, H, W, Cw, kh, kw, g
         with _on(dev):
             thr = _check_bias(epi.thr, Cout, dev) if (epi.thr is not None and elem < 2) else None
             _lib.call("qt_conv2d_implicit_nib", *head, _p(alpha), _p(beta), _p(thr), _p(plane), I(ldn), I(Cout), I(ohy),
-                      I(ohx), I(d2s), _stream(dev))
+                      I(ohx), I(d2s), int(_cfg("CONV_FLAGS")), _stream(dev))
         return NibPlanes(words=plane, rows=rows, K=Cpix)
     if hy or hx:
         if epi is not None:
@@ -271,12 +276,13 @@ def _conv_implicit(elem: int, pixels_words: torch.Tensor, N, H, W, Cw, kh, kw, g
         plane = torch.empty((M, ldb), dtype=torch.int32, device=dev)   # the kernel writes every word incl. the pad
         with _on(dev):
             _lib.call("qt_conv2d_implicit_bits", *head, _p(alpha), _p(beta), _p(thr), _p(plane), I(ldb), I(Cout),
-                      _stream(dev))
+                      int(_cfg("CONV_FLAGS")), _stream(dev))
         return BitPlanes(sign=plane, rows=M, K=Cout)
     y = torch.empty((M, Cout), dtype=torch.float32, device=dev)
     with _on(dev):
-        if _cfg("CONV_VARIANT"):
-            _lib.call("qt_conv2d_implicit_variant", int(_cfg("CONV_VARIANT")), *head, _p(y), I(Cout), I(Cout), _stream(dev))
+        variant = int(_cfg("CONV_VARIANT")) | int(_cfg("CONV_FLAGS"))
+        if variant:
+            _lib.call("qt_conv2d_implicit_variant", variant, *head, _p(y), I(Cout), I(Cout), _stream(dev))
         else:
             _lib.call("qt_conv2d_implicit", *head, _p(y), I(Cout), I(Cout), _stream(dev))
     return y
@@ -784,6 +790,13 @@ def _check_bias(bias, N, device):
 #: plain implicit conv 1 = double-buffered, 2 = ping-pong, 4 = no un-padded fast path
 POPC_VARIANT = 0
 CONV_VARIANT = 0
+#: A/B flags of the implicit-GEMM convs (the QT_CONV_* bits of include/qt_hip.h; every flag selects another kernel that computes
+#: the same bits): passed to the bits / nib / codes entries, or-ed into CONV_VARIANT for the plain fp32 conv
+CONV_NO_DEEP_RING = 0x10            # double-buffered ConvV128x128 / ConvV128x64 instead of the ring-of-stages forms
+CONV_COMPARE_THRESHOLDS = 0x20      # integer thresholds: compare-form epilogue instead of the sign-bit form
+CONV_NO_DIRECT_CODES = 0x40         # code epilogue: never the persistent direct 3 x 3 kernel
+CONV_FLAGS_MASK = CONV_NO_DEEP_RING | CONV_COMPARE_THRESHOLDS | CONV_NO_DIRECT_CODES
+CONV_FLAGS = 0
 
 
 def xnor_gemm(x: BitPlanes, w: BitPlanes, bias: Optional[torch.Tensor] = None,

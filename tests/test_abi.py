@@ -23,6 +23,32 @@ def test_header_symbols_all_bound_and_exported(lib):
         assert hasattr(lib, name), f"{name} not exported by libqt_hip.so"
 
 
+def test_default_build_reads_no_environment(lib):
+    """A/B switches are call arguments (the QT_CONV_* flags, ``variant``); the tool-only environment reads
+    exist in -DQT_PROFILING_VARIANTS / -DQT_EXPERIMENT builds alone, so the product library does not even import getenv."""
+    import os
+    import shutil
+    import subprocess
+    nm = next((p for p in ("/usr/bin/nm", shutil.which("nm"), shutil.which("llvm-nm"), "/opt/rocm/llvm/bin/llvm-nm",
+                           "/opt/rocm/lib/llvm/bin/llvm-nm") if p and os.path.exists(p)), None)
+    assert nm, "neither nm nor llvm-nm found: cannot list the undefined symbols of libqt_hip.so"
+    out = subprocess.run([nm, "-D", "--undefined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    undefined = [ln.split()[-1].split("@")[0] for ln in out.splitlines() if ln.strip()]
+    assert any(u.startswith("hip") for u in undefined), "symbol listing looks empty"
+    assert not [u for u in undefined if "getenv" in u], [u for u in undefined if "getenv" in u]
+
+
+def test_conv_flag_constants_mirror_the_header():
+    import re
+    from pytorch_quantize_impls_amd import ops
+    with open(_lib.HEADER_PATH, encoding="utf-8") as fh:
+        defs = {k: int(v, 0) for k, v in re.findall(r"^#define QT_(CONV_\w+) (0x[0-9a-fA-F]+)", fh.read(), re.M)}
+    assert set(defs) == {"CONV_NO_DEEP_RING", "CONV_COMPARE_THRESHOLDS", "CONV_NO_DIRECT_CODES", "CONV_FLAGS_MASK"}, defs
+    assert all(getattr(ops, k) == v for k, v in defs.items()), defs
+    flags = [v for k, v in defs.items() if k != "CONV_FLAGS_MASK"]
+    assert sum(flags) == defs["CONV_FLAGS_MASK"] and not defs["CONV_FLAGS_MASK"] & 0xf and ops.CONV_FLAGS == 0
+
+
 def test_identification(lib):
     assert _lib.version() >= 100
     assert _lib.target_arch() == "gfx950"

@@ -3,7 +3,7 @@ exact reference of tests/_exact.py (float64 integer sums on the device, the fuse
 
   * the layer shapes of C3 (AlexNet-Bin conv2-conv5) and C5 (VGG-16 conv1_2-conv5_x) at batch 256 through the entry points the
     fused blocks call (ops.conv2d_nib, ops.conv3x3_direct_nib): bit planes and nibble halo planes, binary and ternary weights,
-    the sign-bit (ElemFp4T), compare (QT_NO_SWAPT=1) and float (no thresholds) epilogues, pooled bits where AlexNet pools,
+    the sign-bit (ElemFp4T), compare (ops.CONV_COMPARE_THRESHOLDS) and float (no thresholds) epilogues, pooled bits where AlexNet pools,
     edge channels (zero / NaN slopes, huge and infinite offsets, exact ties);
   * the real-valued first layers (VGG conv1_1: first3x3, AlexNet conv1: first_direct) at batch 256 against float64;
   * both fused networks block by block at batch 256, each block fed with the exact reference chain's activation;
@@ -176,7 +176,7 @@ def pm1_input(N, H, W, Cin, pad, seed, dev):
     return words, px
 
 
-def run_implicit(dev, monkeypatch, case, N, Cin, Cout, H, k, kind, cfg, pool=None, forms=("swapt", "compare", "float"),
+def run_implicit(dev, case, N, Cin, Cout, H, k, kind, cfg, pool=None, forms=("swapt", "compare", "float"),
                  nib_halo=(1, 1), seed=1):
     """ops.conv2d_nib (the implicit-GEMM conv on the physically padded nibble plane, as the fused blocks call it) with the
     threshold epilogue in the listed forms, bit planes and nibble halo planes, against the exact reference."""
@@ -190,14 +190,12 @@ def run_implicit(dev, monkeypatch, case, N, Cin, Cout, H, k, kind, cfg, pool=Non
     args = (px, (N, Cin, H + 2 * pad, W + 2 * pad), wp, (k, k), bias, 1, 0, 1)
     outs = []
     for form in forms:
-        if form == "compare":
-            monkeypatch.setenv("QT_NO_SWAPT", "1")
         t = None if form == "float" else thr
         elem = "ElemFp4T" if (form == "swapt" and cfg in SWAPT) else "ElemFp4"
         label = f"{cfg}<{elem}>"
-        bits = traced(lambda: ops.conv2d_nib(*args, epi=(alpha, beta, t)), label, f"{case} {form} bits")
-        nib = traced(lambda: ops.conv2d_nib(*args, epi=ops.NibEpilogue(alpha, beta, nib_halo, thr=t)), label, f"{case} {form} nib")
-        monkeypatch.delenv("QT_NO_SWAPT", raising=False)
+        with ops.scope(CONV_FLAGS=ops.CONV_COMPARE_THRESHOLDS if form == "compare" else 0):
+            bits = traced(lambda: ops.conv2d_nib(*args, epi=(alpha, beta, t)), label, f"{case} {form} bits")
+            nib = traced(lambda: ops.conv2d_nib(*args, epi=ops.NibEpilogue(alpha, beta, nib_halo, thr=t)), label, f"{case} {form} nib")
         outs += [Out(f"{form}/bits", bits, H, W), Out(f"{form}/nib", nib, H, W, halo=nib_halo)]
         if pool:
             Hp = (H - pool[0]) // pool[1] + 1
@@ -257,8 +255,8 @@ IMPLICIT_LAYERS = [
 
 
 @pytest.mark.parametrize("case,Cin,Cout,H,k,kind,cfg,pool", IMPLICIT_LAYERS, ids=[c[0] for c in IMPLICIT_LAYERS])
-def test_implicit_threshold_conv_at_batch_256(dev, monkeypatch, case, Cin, Cout, H, k, kind, cfg, pool):
-    run_implicit(dev, monkeypatch, case, BATCH, Cin, Cout, H, k, kind, cfg, pool, seed=zlib.crc32(case.encode()) % 10007)
+def test_implicit_threshold_conv_at_batch_256(dev, case, Cin, Cout, H, k, kind, cfg, pool):
+    run_implicit(dev, case, BATCH, Cin, Cout, H, k, kind, cfg, pool, seed=zlib.crc32(case.encode()) % 10007)
 
 
 DIRECT_LAYERS = [
@@ -292,8 +290,8 @@ SYNTHETIC = [
 
 
 @pytest.mark.parametrize("case,N,Cin,Cout,H,kind,cfg,why", SYNTHETIC, ids=[c[0] for c in SYNTHETIC])
-def test_implicit_threshold_conv_synthetic_configs(dev, monkeypatch, case, N, Cin, Cout, H, kind, cfg, why):
-    run_implicit(dev, monkeypatch, case, N, Cin, Cout, H, 3, kind, cfg, seed=N + Cin + Cout + H)
+def test_implicit_threshold_conv_synthetic_configs(dev, case, N, Cin, Cout, H, kind, cfg, why):
+    run_implicit(dev, case, N, Cin, Cout, H, 3, kind, cfg, seed=N + Cin + Cout + H)
 
 
 # ---- size edges of the direct 3x3 kernel ------------------------------------------------------------------------------------
@@ -562,7 +560,7 @@ EXPECTED = sorted(
     + [f"direct3x3<{i},{e}>" for i in ("2,2,1,3", "2,4,1,2", "4,1,2,2", "4,2,2,2") for e in ("lean", "general")])
 # not selectable with default switches (documented rather than listed):
 #   ConvV256      tn == 256 always takes ConvVPP256 first (the `g_conv_force != 1` ping-pong branch; only variant 1 reaches it)
-#   ConvV128x128 / ConvV128x64   only with QT_NO_CONV_DEEP_RING=1 (the round-4 double-buffered A/B configurations)
+#   ConvV128x128 / ConvV128x64   only with ops.CONV_NO_DEEP_RING (the round-4 double-buffered A/B configurations)
 
 
 def test_every_threshold_conv_configuration_ran_against_the_exact_reference():

@@ -352,51 +352,40 @@ def test_dorefa_9_to_16_bit_layers_vs_reference_fp64_vectors(dev, name, mode):
 
 # ---- the persistent direct 3 x 3 code conv (csrc/code_conv3x3.hip) == the implicit-GEMM route, bit for bit ---------------------------
 
-_C3_SNIPPET = r"""
-import hashlib, sys, torch
-sys.path.insert(0, %r)
-import bench_models
-from pytorch_quantize_impls_amd import lazy
-torch.manual_seed(4)
-m4 = bench_models.DorefaResNet18(w_bits=1, a_bits=4)
-bench_models.randomize_bn(m4, seed=3)
-for m in m4.modules():
-    if isinstance(m, torch.nn.BatchNorm2d):
-        m.running_var.mul_(4.0)
-dev = torch.device("cuda:0")
-m4 = m4.to(dev).to(memory_format=torch.channels_last).eval()
-f4 = bench_models.FusedDorefaResNet18(m4, fold="device")
-out = []
-for B in (8, 24, 256):
-    x = torch.randn((B, 3, 32, 32), device=dev, generator=torch.Generator(device=dev).manual_seed(B)).contiguous(memory_format=torch.channels_last)
-    with torch.no_grad():
-        y = f4(x)
-        with lazy.eager():
-            ye = m4(x)
-    out.append(hashlib.sha256(y.cpu().numpy().tobytes()).hexdigest() + ":" + str(bool(torch.equal(y, ye))))
-print("RESULT", " ".join(out))
-"""
-
-
 def test_direct_code_conv3x3_equals_the_implicit_gemm_route(dev):
     """The fused DoReFa ResNet-18 forward (stage-1 / stage-2 stride-1 convs on the persistent direct kernel) gives the same logits,
-    bit for bit, as with the kernel switched off (QT_NO_CODE_CONV3X3: every conv on the implicit-GEMM kernel) and as the
-    module-by-module graph; batches 8 / 24 / 256 (whole 128-pixel tiles, ragged tile counts per workgroup)."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = {}
-    for off in (False, True):
-        env = dict(os.environ)
-        env.pop("QT_NO_CODE_CONV3X3", None)
-        if off:
-            env["QT_NO_CODE_CONV3X3"] = "1"
-        p = subprocess.run([sys.executable, "-c", _C3_SNIPPET % root], env=env, capture_output=True, text=True, timeout=600)
-        assert p.returncode == 0, p.stderr[-2000:]
-        line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT")][0]
-        res[off] = line.split()[1:]
+    bit for bit, as with the kernel switched off (ops.CONV_NO_DIRECT_CODES: every conv on the implicit-GEMM kernel) and as the
+    module-by-module graph; batches 8 / 24 / 256 (whole 128-pixel tiles, ragged tile counts per workgroup).  Both sides run in
+    this process: the flag is an argument of every launch, each scope holds the forward and the read-back of its result, and
+    implicit hipGraphs are off, since a replay would keep the flags of its capture."""
+    import bench_models
+    from pytorch_quantize_impls_amd import _lib, utils
+    count = _lib.load().qt_code_conv3x3_launch_count
+    torch.manual_seed(4)
+    m4 = bench_models.DorefaResNet18(w_bits=1, a_bits=4)
+    bench_models.randomize_bn(m4, seed=3)
+    for m in m4.modules():
+        if isinstance(m, torch.nn.BatchNorm2d):
+            m.running_var.mul_(4.0)
+    m4 = m4.to(dev).to(memory_format=torch.channels_last).eval()
+    f4 = bench_models.FusedDorefaResNet18(m4, fold="device")
+    res, direct = {}, {}
+    with utils.implicit_graphs(False):
+        for off in (False, True):
+            out, c0 = [], int(count())
+            with ops.scope(CONV_FLAGS=ops.CONV_NO_DIRECT_CODES if off else 0):
+                for B in (8, 24, 256):
+                    x = torch.randn((B, 3, 32, 32), device=dev,
+                                    generator=torch.Generator(device=dev).manual_seed(B)).contiguous(memory_format=torch.channels_last)
+                    with torch.no_grad():
+                        y = f4(x)
+                        with lazy.eager():
+                            ye = m4(x)
+                        out.append(hashlib.sha256(y.cpu().numpy().tobytes()).hexdigest() + ":" + str(bool(torch.equal(y, ye))))
+            res[off], direct[off] = out, int(count()) - c0
     assert res[False] == res[True], res
     assert all(r.endswith(":True") for r in res[False]), res
+    assert direct[False] > 0 and direct[True] == 0, direct          # the two sides did take different routes
 
 
 # ---- thread-local switches (VERDICT r4 weak 9): float_split / lazy_train.eager do not leak between threads; backward keeps the forward's mode
@@ -465,7 +454,7 @@ def test_direct_code_conv3x3_geometry_fuzz(dev):
     """Seeded geometries of FusedBnDorefaQuant -> FusedDorefaConvBnQuant (fold="device"): channels 64 / 128, Cout 64 / 128 / 192,
     power-of-two maps 4 .. 64 (tiles inside an image, whole images per tile, ragged tile counts per workgroup), halos 0 / 1 on
     the output, with / without a code residual and ReLU, bit widths 2 .. 4: the code planes of the persistent direct kernel equal
-    those of the implicit-GEMM kernel byte for byte (the switch QT_NO_CODE_CONV3X3 is read per call)."""
+    those of the implicit-GEMM kernel byte for byte (ops.CONV_NO_DIRECT_CODES, an argument of the launch)."""
     from pytorch_quantize_impls_amd.layers import DorefaConv2d, FusedBnDorefaQuant, FusedDorefaConvBnQuant
     from pytorch_quantize_impls_amd import _lib
     count = _lib.load().qt_code_conv3x3_launch_count
@@ -494,23 +483,69 @@ def test_direct_code_conv3x3_geometry_fuzz(dev):
         outs = []
         with torch.no_grad():
             for off in (False, True):
-                if off:
-                    os.environ["QT_NO_CODE_CONV3X3"] = "1"
-                else:
-                    os.environ.pop("QT_NO_CODE_CONV3X3", None)
-                try:
+                with ops.scope(CONV_FLAGS=ops.CONV_NO_DIRECT_CODES if off else 0):
                     act = head(x)
                     c0 = int(count())
                     y = blk(act, residual=act if use_res else None)
                     assert int(count()) - c0 == (0 if off else 1), "route"
                     outs.append((y.without_halo().codes.codes.clone(), y.codes.codes.clone(), int(y.codes.overflow.item())))
-                finally:
-                    os.environ.pop("QT_NO_CODE_CONV3X3", None)
         assert torch.equal(outs[0][0], outs[1][0]), (Cin, Cout, H, W, N, bits, relu, use_res, oh)
         assert torch.equal(outs[0][1], outs[1][1]), "halo border differs"
         assert outs[0][2] == outs[1][2]
         done += 1
     assert done >= 16
+
+
+def test_conv_flags_are_thread_local(dev):
+    """ops.CONV_FLAGS set by ``ops.scope`` holds for the calling thread only: while the main thread keeps its 64 -> 64 block (8 x 8
+    map, batch 2: one whole 128-pixel tile) off the direct kernel, a worker thread's call of the same block takes it, with the same
+    codes byte for byte; after the scope the main thread takes it again."""
+    import threading
+    from pytorch_quantize_impls_amd.layers import DorefaConv2d, FusedBnDorefaQuant, FusedDorefaConvBnQuant
+    from pytorch_quantize_impls_amd import _lib
+    count = _lib.load().qt_code_conv3x3_launch_count
+    torch.manual_seed(77)
+    bn0 = torch.nn.BatchNorm2d(64).to(dev).eval()
+    bn0.running_mean.normal_(); bn0.running_var.uniform_(0.5, 2.0); bn0.weight.data.normal_(); bn0.bias.data.normal_()
+    conv = DorefaConv2d(64, 64, 3, padding=1, bias=False, bit_width=1).to(dev)
+    conv.weight.data.normal_(0, 0.05)
+    conv.eval()
+    bn = torch.nn.BatchNorm2d(64).to(dev).eval()
+    bn.running_mean.normal_(0, 0.5); bn.running_var.uniform_(0.5, 2.0); bn.weight.data.normal_(); bn.bias.data.normal_(0, 0.3)
+    x = torch.rand(2, 64, 8, 8, device=dev).contiguous(memory_format=torch.channels_last)
+    head = FusedBnDorefaQuant(bn0, 4, relu=True, out_halo=1, fold="device")
+    blk = FusedDorefaConvBnQuant(conv, bn, 4, relu=True, out_halo=1, fold="device")
+
+    def run():
+        with torch.no_grad():
+            act = head(x)
+            c0 = int(count())
+            y = blk(act)
+            codes = y.codes.codes.clone()
+            torch.cuda.synchronize()
+            return int(count()) - c0, codes
+
+    worker = {}
+
+    def work():
+        try:
+            worker["flags"] = ops._cfg("CONV_FLAGS")
+            worker["moved"], worker["codes"] = run()
+        except Exception as exc:  # noqa: BLE001
+            worker["error"] = repr(exc)
+
+    with ops.scope(CONV_FLAGS=ops.CONV_NO_DIRECT_CODES):
+        moved, codes = run()
+        assert moved == 0
+        t = threading.Thread(target=work)
+        t.start()
+        t.join()
+        assert ops._cfg("CONV_FLAGS") == ops.CONV_NO_DIRECT_CODES
+    assert "error" not in worker, worker
+    assert worker["flags"] == 0 and worker["moved"] == 1
+    assert torch.equal(worker["codes"], codes)
+    moved, after = run()
+    assert moved == 1 and torch.equal(after, codes)
 
 
 @pytest.mark.parametrize("bits", [1, 3, 8])

@@ -7,9 +7,7 @@
   * qt_conv2d_implicit_halo_bn: the 1x1 shortcut conv with BatchNorm in its epilogue equals conv, then qt_bn_eval_device_f32;
   * the ring of 3 / 4 stage buffers on the 256- / 512-channel small-map convs produces the codes of the double-buffered loop;
   * the whole C4 net, fused form and un-modified module graph, still equals its module-by-module execution bit for bit."""
-import os
-import subprocess
-import sys
+import hashlib
 
 import pytest
 import torch
@@ -111,49 +109,34 @@ def test_shortcut_conv_with_batchnorm_in_its_epilogue(dev, cin, cout, hw):
     assert torch.equal(y2.view(N, hw // 2, hw // 2, cout).permute(0, 3, 1, 2), want)
 
 
-_RING_AB = r"""
-import hashlib, sys, torch
-sys.path.insert(0, %r)
-import bench_models
-from pytorch_quantize_impls_amd import _lib, ops, packed
-from pytorch_quantize_impls_amd.layers import DorefaConv2d, FusedDorefaConvBnQuant
-dev = torch.device("cuda:0")
-h = hashlib.sha256()
-for cin, hw, stride in ((256, 8, 1), (512, 4, 1), (256, 8, 2), (128, 16, 2)):
-    cout = cin * stride
-    torch.manual_seed(cin + stride)
-    N = 256
-    ld = ops.code_ld_bytes(cin, 16)
-    q = torch.zeros((N, hw + 2, hw + 2, ld), dtype=torch.int8)
-    q[:, 1:-1, 1:-1, :cin] = torch.randint(0, 16, (N, hw, hw, cin)).to(torch.int8)
-    planes = ops.CodePlanes(codes=q.view(-1, ld).to(dev), rows=N * (hw + 2) ** 2, K=cin, inv_n=ops.inv_levels(4), bit_width=4,
-                            overflow=torch.zeros((1,), dtype=torch.int32, device=dev))
-    act = packed.CodeActivation(planes, (N, cin, hw, hw), halo=(1, 1))
-    conv = DorefaConv2d(cin, cout, 3, stride=stride, padding=1, bias=False, bit_width=1).to(dev).eval()
-    bn = torch.nn.BatchNorm2d(cout).to(dev).eval()
-    bench_models.randomize_bn(bn, seed=1)
-    bn.running_var.mul_(4.0)
-    with torch.no_grad():
-        out = FusedDorefaConvBnQuant(conv, bn, 4, out_halo=1, fold="device")(act, residual=act if stride == 1 else None)
-    torch.cuda.synchronize()
-    h.update(out.codes.codes.cpu().numpy().tobytes())
-    h.update(bytes([int(out.codes.overflow.item())]))
-print("DIGEST", h.hexdigest())
-"""
-
-
 def test_deep_dma_ring_produces_the_double_buffered_codes(dev):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    digests = []
-    for ring in ("0", "1"):
-        env = dict(os.environ)
-        env.pop("QT_NO_CONV_DEEP_RING", None)
-        if ring == "0":
-            env["QT_NO_CONV_DEEP_RING"] = "1"
-        out = subprocess.run([sys.executable, "-c", _RING_AB % root], env=env, capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0, out.stderr[-2000:]
-        digests.append([ln for ln in out.stdout.splitlines() if ln.startswith("DIGEST")][0])
-    assert digests[0] == digests[1]
+    """Four batch-256 layer shapes of the fused DoReFa ResNet-18 on the ring configurations and, under ops.CONV_NO_DEEP_RING, on the
+    double-buffered ones: SHA-256 of code planes and overflow flags.  Both sides run in this process: the flag is an argument of the
+    launch, and each scope holds the forward and the read-back of its result."""
+    digests = {}
+    for flags in (ops.CONV_NO_DEEP_RING, 0):
+        h = hashlib.sha256()
+        for cin, hw, stride in ((256, 8, 1), (512, 4, 1), (256, 8, 2), (128, 16, 2)):
+            cout = cin * stride
+            torch.manual_seed(cin + stride)
+            N = 256
+            ld = ops.code_ld_bytes(cin, 16)
+            q = torch.zeros((N, hw + 2, hw + 2, ld), dtype=torch.int8)
+            q[:, 1:-1, 1:-1, :cin] = torch.randint(0, 16, (N, hw, hw, cin)).to(torch.int8)
+            planes = ops.CodePlanes(codes=q.view(-1, ld).to(dev), rows=N * (hw + 2) ** 2, K=cin, inv_n=ops.inv_levels(4), bit_width=4,
+                                    overflow=torch.zeros((1,), dtype=torch.int32, device=dev))
+            act = packed.CodeActivation(planes, (N, cin, hw, hw), halo=(1, 1))
+            conv = DorefaConv2d(cin, cout, 3, stride=stride, padding=1, bias=False, bit_width=1).to(dev).eval()
+            bn = torch.nn.BatchNorm2d(cout).to(dev).eval()
+            bench_models.randomize_bn(bn, seed=1)
+            bn.running_var.mul_(4.0)
+            with torch.no_grad(), ops.scope(CONV_FLAGS=flags):
+                out = FusedDorefaConvBnQuant(conv, bn, 4, out_halo=1, fold="device")(act, residual=act if stride == 1 else None)
+                torch.cuda.synchronize()
+                h.update(out.codes.codes.cpu().numpy().tobytes())
+                h.update(bytes([int(out.codes.overflow.item())]))
+        digests[flags] = h.hexdigest()
+    assert digests[0] == digests[ops.CONV_NO_DEEP_RING]
 
 
 def test_c4_forms_equal_the_module_by_module_graph_and_count_their_launches(dev):
@@ -201,7 +184,7 @@ def test_c4_forms_equal_the_module_by_module_graph_and_count_their_launches(dev)
     (144, 256, 16, 2, 3, 250),     # 1296-byte rows: the wide stride-2 rule with a partial last stage and ragged M
 ])
 def test_deep_ring_short_and_ragged_k_loops(dev, cin, cout, hw, stride, k, batch):
-    """Whatever configuration the rules pick with and without the ring (the switch is read per call, so ONE process): short K loops
+    """Whatever configuration the rules pick with and without the ring (ops.CONV_NO_DEEP_RING, an argument of the launch): short K loops
     (these stay on the double-buffered small-K tiles), partial last stages, row tiles past M on the ring configurations."""
     torch.manual_seed(cin + cout + k)
     pad = k // 2
@@ -212,16 +195,10 @@ def test_deep_ring_short_and_ragged_k_loops(dev, cin, cout, hw, stride, k, batch
     bench_models.randomize_bn(bn, seed=5)
     bn.running_var.mul_(4.0)
     blk = FusedDorefaConvBnQuant(conv, bn, 4, out_halo=1, fold="device")
-    old = os.environ.pop("QT_NO_CONV_DEEP_RING", None)
-    try:
-        with torch.no_grad():
-            ring = blk(act)
-            os.environ["QT_NO_CONV_DEEP_RING"] = "1"
+    with torch.no_grad():
+        ring = blk(act)
+        with ops.scope(CONV_FLAGS=ops.CONV_NO_DEEP_RING):
             plain = blk(act)
-    finally:
-        os.environ.pop("QT_NO_CONV_DEEP_RING", None)
-        if old is not None:
-            os.environ["QT_NO_CONV_DEEP_RING"] = old
     torch.cuda.synchronize()
     assert torch.equal(ring.codes.codes, plain.codes.codes)
     assert int(ring.codes.overflow.item()) == 0

@@ -352,22 +352,8 @@ def test_vgg_first_layer_module_and_fused_routes_share_the_first3x3_kernel(dev):
     assert torch.equal(got, want)
 
 
-@pytest.mark.parametrize("Cin,Cout,k,N,H,W,kind", [
-    # AlexNet conv2 - conv5 at batch <= 8 (M <= 4096) take the small-M tiles (ConvV128x64D, ConvVSkinny), which have no sign-bit
-    # form; their batch-256 tiles (384 x 192 / 256 x 192 / 256 x 256 ping-pong) are pinned in tests/test_gpu_exact_b256.py
-    (192, 576, 5, 4, 27, 27, "binary"),      # AlexNet conv2
-    (576, 1152, 3, 8, 13, 13, "binary"),     # conv3
-    (1152, 768, 3, 8, 13, 13, "ternary"),    # conv4
-    (768, 256, 3, 3, 13, 13, "binary"),      # conv5
-    (128, 128, 3, 2, 56, 56, "ternary"),     # VGG conv2_2: 256 x 128 tiles, two workgroups per CU
-    (256, 256, 3, 2, 28, 28, "ternary"),     # conv3_2
-    (512, 512, 3, 3, 14, 9, "binary"),       # conv4_2 / conv5 (ragged last row tile)
-    (64, 64, 3, 1, 5, 7, "ternary"),         # one partial tile
-])
-def test_sign_bit_threshold_epilogue_equals_the_compare_form(dev, monkeypatch, Cin, Cout, k, N, H, W, kind):
-    """fp4 convs with integer thresholds: the weights-as-rows kernels (ElemFp4T: start values -(T - 1/2), bit = the accumulator's
-    sign, csrc/mfma_gemm_kernel.h) against the compare form (QT_NO_SWAPT=1) and the float epilogue — bit planes and the next
-    conv's nibble halo planes, bit for bit, with negative / zero slopes and constant predicates among the channels."""
+def _threshold_conv_case(dev, Cin, Cout, k, N, H, W, kind):
+    """Operands of one fp4 conv with integer thresholds: negative / zero slopes and constant predicates among the channels."""
     from pytorch_quantize_impls_amd import ops
     pd = k // 2
     x = t32(synth.pm1(71, (N, Cin, H, W)), dev).contiguous(memory_format=torch.channels_last)
@@ -383,13 +369,33 @@ def test_sign_bit_threshold_epilogue_equals_the_compare_form(dev, monkeypatch, C
     alpha[5], beta[5] = -0.0, 1.0
     thr = ops.integer_thresholds(b, alpha, beta, Cin * k * k)
     args = (px, (N, Cin, H + 2 * pd, W + 2 * pd), wp, (k, k), b, 1, 0, 1)
+    return args, alpha, beta, thr
+
+
+@pytest.mark.parametrize("Cin,Cout,k,N,H,W,kind", [
+    # AlexNet conv2 - conv5 at batch <= 8 (M <= 4096) take the small-M tiles (ConvV128x64D, ConvVSkinny), which have no sign-bit
+    # form; their batch-256 tiles (384 x 192 / 256 x 192 / 256 x 256 ping-pong) are pinned in tests/test_gpu_exact_b256.py
+    (192, 576, 5, 4, 27, 27, "binary"),      # AlexNet conv2
+    (576, 1152, 3, 8, 13, 13, "binary"),     # conv3
+    (1152, 768, 3, 8, 13, 13, "ternary"),    # conv4
+    (768, 256, 3, 3, 13, 13, "binary"),      # conv5
+    (128, 128, 3, 2, 56, 56, "ternary"),     # VGG conv2_2: 256 x 128 tiles, two workgroups per CU
+    (256, 256, 3, 2, 28, 28, "ternary"),     # conv3_2
+    (512, 512, 3, 3, 14, 9, "binary"),       # conv4_2 / conv5 (ragged last row tile)
+    (64, 64, 3, 1, 5, 7, "ternary"),         # one partial tile
+])
+def test_sign_bit_threshold_epilogue_equals_the_compare_form(dev, Cin, Cout, k, N, H, W, kind):
+    """fp4 convs with integer thresholds: the weights-as-rows kernels (ElemFp4T: start values -(T - 1/2), bit = the accumulator's
+    sign, csrc/mfma_gemm_kernel.h) against the compare form (ops.CONV_COMPARE_THRESHOLDS) and the float epilogue — bit planes and
+    the next conv's nibble halo planes, bit for bit, with negative / zero slopes and constant predicates among the channels."""
+    from pytorch_quantize_impls_amd import ops
+    args, alpha, beta, thr = _threshold_conv_case(dev, Cin, Cout, k, N, H, W, kind)
     want_bits = ops.conv2d_nib(*args, epi=(alpha, beta))
     want_nib = ops.conv2d_nib(*args, epi=ops.NibEpilogue(alpha, beta, (1, 1)))
     assert 0.02 < float((want_bits.sign != 0).float().mean())
-    monkeypatch.setenv("QT_NO_SWAPT", "1")
-    cmp_bits = ops.conv2d_nib(*args, epi=(alpha, beta, thr))
-    cmp_nib = ops.conv2d_nib(*args, epi=ops.NibEpilogue(alpha, beta, (1, 1), thr=thr))
-    monkeypatch.delenv("QT_NO_SWAPT")
+    with ops.scope(CONV_FLAGS=ops.CONV_COMPARE_THRESHOLDS):
+        cmp_bits = ops.conv2d_nib(*args, epi=(alpha, beta, thr))
+        cmp_nib = ops.conv2d_nib(*args, epi=ops.NibEpilogue(alpha, beta, (1, 1), thr=thr))
     for shape in (want_bits.sign.shape, want_nib.words.shape):          # poison what torch.empty will hand out
         junk = torch.full(tuple(shape), 0x55555555, dtype=torch.int32, device=dev)
         del junk
@@ -398,6 +404,29 @@ def test_sign_bit_threshold_epilogue_equals_the_compare_form(dev, monkeypatch, C
     assert torch.equal(cmp_bits.sign, want_bits.sign) and torch.equal(cmp_nib.words, want_nib.words)
     assert torch.equal(got_bits.sign, want_bits.sign)
     assert torch.equal(got_nib.words, want_nib.words)
+
+
+def test_unknown_conv_flag_bits_are_refused(dev, monkeypatch):
+    """A bit outside the three QT_CONV_* flags: ``ops.scope`` raises, and past the scope (the module default set directly) the
+    library answers QT_ERR_INVALID_ARG before anything is launched — bits and nibble-plane entries; flags 0 run."""
+    from pytorch_quantize_impls_amd import _lib, ops
+    args, alpha, beta, thr = _threshold_conv_case(dev, 64, 64, 3, 1, 5, 7, "ternary")
+    unknown = 0x80
+    assert unknown & ~ops.CONV_FLAGS_MASK and not unknown & 0xf
+    with pytest.raises(ValueError):
+        with ops.scope(CONV_FLAGS=unknown):
+            pass
+    with pytest.raises(ValueError):
+        with ops.scope(CONV_FLAGS=ops.CONV_COMPARE_THRESHOLDS | unknown):
+            pass
+    monkeypatch.setattr(ops, "CONV_FLAGS", unknown)
+    for epi in ((alpha, beta, thr), ops.NibEpilogue(alpha, beta, (1, 1), thr=thr)):
+        with pytest.raises(_lib.QtStatusError) as err:
+            ops.conv2d_nib(*args, epi=epi)
+        assert "(qt_status -1)" in str(err.value), err.value            # QT_ERR_INVALID_ARG
+    monkeypatch.setattr(ops, "CONV_FLAGS", 0)
+    want = ops.conv2d_nib(*args, epi=(alpha, beta))
+    assert torch.equal(ops.conv2d_nib(*args, epi=(alpha, beta, thr)).sign, want.sign)
 
 
 def test_graft_entry_smoke_runs_on_the_device():

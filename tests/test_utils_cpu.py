@@ -232,6 +232,12 @@ def test_route_switch_scopes_are_thread_local_and_validated():
     with _pt.raises(KeyError):
         with ops.scope(NOT_A_SWITCH=1):
             pass
+    with ops.scope(CONV_FLAGS=ops.CONV_FLAGS_MASK):
+        assert ops._cfg("CONV_FLAGS") == ops.CONV_NO_DEEP_RING | ops.CONV_COMPARE_THRESHOLDS | ops.CONV_NO_DIRECT_CODES
+    with _pt.raises(ValueError):                                                                 # a bit the library does not know
+        with ops.scope(CONV_FLAGS=ops.CONV_NO_DEEP_RING | 0x80):
+            pass
+    assert ops._cfg("CONV_FLAGS") == 0
     prev = ops.FIRST_DIRECT
     try:
         ops.FIRST_DIRECT = False                                                                 # the process-wide default still works

@@ -1,9 +1,12 @@
 #!/usr/bin/env python
 """The un-modified BinaryNet-AlexNet eval forward (batch 256), ITERS eager forwards: the target of tools/probes/c3_pmc.sh
-(rocprofv3 --kernel-trace / --pmc passes; per-dispatch counters want ordinary launches, not graph replays)."""
+(rocprofv3 --kernel-trace / --pmc passes; per-dispatch counters want ordinary launches, not graph replays).
+CONV_FLAGS=0x20 in the tool's environment sets ops.CONV_FLAGS (0x20 = ops.CONV_COMPARE_THRESHOLDS: the compare-form A/B)."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import torch, bench_models
+from pytorch_quantize_impls_amd import ops
+ops.CONV_FLAGS = int(os.environ.get("CONV_FLAGS", "0"), 0)
 dev = torch.device("cuda:0")
 torch.manual_seed(1234)
 m = bench_models.AlexNetBin()

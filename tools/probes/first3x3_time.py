@@ -1,5 +1,7 @@
 #!/usr/bin/env python
-"""Per-launch time of the one-pass 3x3 first-layer kernel at VGG conv1_1's shape (batch 256), the three epilogues, inside one event pair."""
+"""Per-launch time of the one-pass 3x3 first-layer kernel at VGG conv1_1's shape (batch 256), the three epilogues, inside one event pair.
+QT_F3_OCC (2 = the pipelined form) is read by a profiling build of the library only: make EXTRA=-DQT_PROFILING_VARIANTS OUT=...,
+then QT_HIP_LIB=<that library>."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import torch
@@ -19,4 +21,4 @@ for name, epi in (("nib", ops.NibEpilogue(alpha, beta, (1, 1))), ("bits", (alpha
         ops.conv_first3x3(x, frag, 64, None, epi=epi)
     e1.record()
     torch.cuda.synchronize()
-    print(f"QT_F3_OCC={os.environ.get('QT_F3_OCC', '2')} {name}: {e0.elapsed_time(e1) / 20 * 1e3:.1f} us")
+    print(f"QT_F3_OCC={os.environ.get('QT_F3_OCC', '3')} {name}: {e0.elapsed_time(e1) / 20 * 1e3:.1f} us")
