@@ -345,6 +345,15 @@ int qt_pack_pair_nib_f32(const float* x, int64_t ldx, uint32_t* x_plane, int64_t
  * out[cap] (bench.py quotes it in roofline.kernel, so the record names the kernel that ran). */
 int qt_nib_gemm_describe(int64_t M, int64_t N, int64_t K, int64_t ldxp, int64_t ldwp, char* out, int cap);
 
+/* The GemmCfg alias (csrc/mfma_gemm_kernel.h) a GEMM launches, e.g. "PP256": the choice of csrc/tile_select.h, which is what the
+ * launching entry points switch on.  family DENSE: qt_nib_gemm_variant's `variant` (0 = the automatic rule every dense GEMM entry
+ * point takes), with its refusals as the status; the two batched families take variant 0 and refuse what their entry points refuse
+ * of the strides.  K and the pointers are not inputs of the choice. */
+#define QT_GEMM_FAMILY_DENSE 0
+#define QT_GEMM_FAMILY_BF16_TAPS 1      /* qt_bf16_gemm_taps */
+#define QT_GEMM_FAMILY_I8_SPLITK 2      /* qt_i8_gemm_splitk */
+int qt_gemm_tile_describe(int family, int variant, int64_t M, int64_t N, int64_t ldxp, int64_t ldwp, char* out, int cap);
+
 /* Y[M,N] = Xn . Wn^T (+ bias): replaces the same F.linear call sites as qt_xnor_gemm /
  * qt_tern_gemm (binary and ternary weights share this entry point: zero is a nibble value). */
 int qt_nib_gemm(const uint32_t* Xn, int64_t ldxp, const uint32_t* Wn, int64_t ldwp,
@@ -868,6 +877,31 @@ int qt_conv2d_implicit_h(const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, 
 #define QT_CONV_COMPARE_THRESHOLDS 0x20 /* integer thresholds: the compare-form epilogue (ElemFp4) instead of the sign-bit form */
 #define QT_CONV_NO_DIRECT_CODES 0x40    /* qt_conv2d_implicit_codes: never the persistent direct 3 x 3 kernel (csrc/code_conv3x3.hip) */
 #define QT_CONV_FLAGS_MASK 0x70
+
+/* Which kernel an implicit-GEMM conv launches, without launching it: "<GemmCfg alias><element class>", e.g. "ConvVPP256<ElemFp4T>"
+ * (both names as in csrc/mfma_gemm_kernel.h).  The arguments are the numbers of the launching entry points — no data pointers —
+ * and `epilogue` says which entry point is meant; the output plane is taken as dense (the smallest row stride that entry point
+ * accepts).  The status is what that entry point returns for these numbers, QT_OK where it launches (and an empty name where there
+ * is nothing to do).  Both functions run the selector the launch runs (csrc/tile_select.h), so the name is the kernel.
+ * The persistent direct 3 x 3 kernel of qt_conv2d_implicit_codes is outside that selector: QT_EPI_CODES names the implicit-GEMM
+ * kernel, i.e. what runs under QT_CONV_NO_DIRECT_CODES.
+ *   has_thr   integer thresholds given (BITS / NIB);   d2s_cout   NIB only;   variant   tile form | QT_CONV_* flags (PLAIN), flags (others)
+ * qt_conv2d_implicit_taps_describe: the per-tap scaled convs (PLAIN / BITS / NIB; halo, has_thr, d2s_cout, variant must be 0). */
+#define QT_EPI_PLAIN 0       /* qt_conv2d_implicit, _variant, _halo */
+#define QT_EPI_BITS 1        /* qt_conv2d_implicit_bits */
+#define QT_EPI_NIB 2         /* qt_conv2d_implicit_nib */
+#define QT_EPI_CODES 3       /* qt_conv2d_implicit_codes (elem 1) */
+#define QT_EPI_HALO_BN 4     /* qt_conv2d_implicit_halo_bn (elem 1) */
+#define QT_EPI_LEVELS 5      /* qt_conv2d_implicit_levels (elem 2) */
+#define QT_EPI_HALF_BF16 6   /* qt_conv2d_implicit_h, bf16 result (elem 0) */
+#define QT_EPI_HALF_F16 7    /* qt_conv2d_implicit_h, fp16 result (elem 0) */
+int qt_conv2d_implicit_describe(int elem, int64_t Nimg, int64_t H, int64_t W, int64_t Cw, int64_t kh, int64_t kw, int64_t sh, int64_t sw,
+                                int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t ldwp, int64_t Cout, int64_t in_halo_h,
+                                int64_t in_halo_w, int epilogue, int has_thr, int64_t d2s_cout, int variant, char* out, int cap);
+int qt_conv2d_implicit_taps_describe(int elem, int64_t Nimg, int64_t H, int64_t W, int64_t Cw, int64_t kh, int64_t kw, int64_t sh,
+                                     int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t ldwp, int64_t Cout,
+                                     int64_t in_halo_h, int64_t in_halo_w, int epilogue, int has_thr, int64_t d2s_cout, int variant,
+                                     char* out, int cap);
 
 /* qt_conv2d_implicit with the main loop chosen by the caller (tests / tuning; an argument, not process state):
  * variant = form | QT_CONV_* flags; form 0 = automatic (ping-pong 384x192 tile for 192-wide column tiles, double-buffered

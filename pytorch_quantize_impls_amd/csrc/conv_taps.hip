@@ -12,7 +12,9 @@
 //
 // Entry points (include/qt_hip.h): qt_conv2d_implicit_taps (fp32 result), qt_conv2d_implicit_taps_bits / _nib (inference
 // fusion: BatchNorm-threshold bits, or the next conv's nibble plane), qt_xnor_tap_prep_f32 (alpha + the Horner tables of a weight).
+#include <cstdio>
 #include "mfma_gemm_kernel.h"
+#include "tile_select.h"
 #include "xnor_alpha.h"
 
 namespace {
@@ -57,66 +59,64 @@ __global__ __launch_bounds__(1024) void tap_tables_kernel(const float* __restric
     }
 }
 
-template <class E>
-int dispatch_taps(const uint32_t* P, const uint32_t* Wmat, int64_t ldwp, const float* bias, float scale, const float* scale_dev,
-                  float* Y, int64_t ldy, int64_t M, int64_t Cout, int64_t K, int64_t kwords, bool valid, qt_stream_t stream,
-                  const ConvArgs& cg, const EpiArgs& epi) {
-#define QT_TAPS(...) return launch_cfg<__VA_ARGS__>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi)
-    // Tile widths: the in-place multiply needs the accumulators in VALU-addressable registers next to the fragments (a wave of an
-    // 8-wave workgroup owns 256 registers, arch + acc together).  256x256 (128 accumulator registers) fits its MAIN LOOP in them —
-    // the ~80 spilled dwords are prologue / epilogue values — and is what Cout = 768 / 256 want (AlexNet conv4: 163 -> 137 us,
-    // conv5: 60 -> 41 us against 256x192 / 256x128 tiles); the 144-register 384x192 tile of the un-scaled conv does not.
-    int tn = 256;
-    {
-        int64_t best = (Cout + 255) / 256 * 256;
-        for (int c : {192, 128, 64})
-            if ((Cout + c - 1) / c * c < best) { tn = c; best = (Cout + c - 1) / c * c; }
+// TileCfg (select_conv_taps, tile_select.h) -> launch: the configurations the per-tap scaled elements are instantiated for.
+// A configuration outside this set is QT_ERR_UNSUPPORTED, never another kernel.  a: the arguments of launch_cfg.
+template <class E, class... A>
+int launch_taps(TileCfg cfg, A&&... a) {
+    switch (cfg) {
+        case TileCfg::ConvV128x128: return launch_cfg<ConvV128x128<E>>(a...);
+        case TileCfg::ConvV128x64: return launch_cfg<ConvV128x64<E>>(a...);
+        case TileCfg::ConvVSkinny: return launch_cfg<ConvVSkinny<E>>(a...);
+        case TileCfg::ConvVPP256: return launch_cfg<ConvVPP256<E>>(a...);
+        case TileCfg::ConvVPP192: return launch_cfg<ConvVPP192<E>>(a...);
+        case TileCfg::ConvVPP256x192: return launch_cfg<ConvVPP256x192<E>>(a...);
+        case TileCfg::ConvVPP128: return launch_cfg<ConvVPP128<E>>(a...);
+        case TileCfg::ConvV64: return launch_cfg<ConvV64<E>>(a...);
+        case TileCfg::ConvSkinny: return launch_cfg<ConvSkinny<E>>(a...);
+        case TileCfg::Conv128x128: return launch_cfg<Conv128x128<E>>(a...);
+        case TileCfg::ConvPP256: return launch_cfg<ConvPP256<E>>(a...);
+        case TileCfg::ConvPP192: return launch_cfg<ConvPP192<E>>(a...);
+        case TileCfg::ConvPP256x192: return launch_cfg<ConvPP256x192<E>>(a...);
+        case TileCfg::ConvPP128: return launch_cfg<ConvPP128<E>>(a...);
+        case TileCfg::Conv64: return launch_cfg<Conv64<E>>(a...);
+        default: return QT_ERR_UNSUPPORTED;
     }
-    const int64_t tiles = ((M + 255) / 256) * ((Cout + tn - 1) / tn);
-    const bool long_k = kwords * 4 >= 2048 && !(ldwp & 127);
-    if (valid) {
-        // small M (small-batch inference, late layers): the same rules as the un-scaled conv (mfma_gemm.hip, QT_CONV)
-        if (long_k && !epi.d2s_cout && (M <= 4096 || (tiles < 256 && (M / 64) * Cout * kwords * 4 <= (256ll << 20)))) {
-            if (M > 4096 && ((M + 127) / 128) * ((Cout + 127) / 128) >= 200) QT_TAPS(ConvV128x128<E>);
-            if (((M + 127) / 128) * ((Cout + 63) / 64) >= 200) QT_TAPS(ConvV128x64<E>);
-            QT_TAPS(ConvVSkinny<E>);
-        }
-        if (tn == 256) QT_TAPS(ConvVPP256<E>);
-        if (tn == 192 && prefer_384_rows(M, Cout)) QT_TAPS(ConvVPP192<E>);
-        if (tn == 192) QT_TAPS(ConvVPP256x192<E>);
-        if (tn == 128) QT_TAPS(ConvVPP128<E>);
-        QT_TAPS(ConvV64<E>);
-    }
-    if (!epi.alpha && epi.mode == 0 && tiles < 200) {
-        if (((M + 127) / 128) * ((Cout + 127) / 128) < 200 && long_k) QT_TAPS(ConvSkinny<E>);
-        QT_TAPS(Conv128x128<E>);
-    }
-    if (tn == 256) QT_TAPS(ConvPP256<E>);
-    if (tn == 192 && prefer_384_rows(M, Cout)) QT_TAPS(ConvPP192<E>);
-    if (tn == 192) QT_TAPS(ConvPP256x192<E>);
-    if (tn == 128) QT_TAPS(ConvPP128<E>);
-    QT_TAPS(Conv64<E>);
-#undef QT_TAPS
+}
+
+// What conv_taps_impl launches, worked out from the numbers alone (the describe entry point calls this and stops here).
+struct TapsPlan {
+    ConvArgs cg;
+    int64_t M, K;
+    TileCfg cfg;
+};
+int conv_taps_plan(int elem, int64_t Nimg, int64_t H, int64_t W, int64_t Cw, int64_t kh, int64_t kw, int64_t sh, int64_t sw, int64_t ph,
+                   int64_t pw, int64_t dh, int64_t dw, int64_t ldwp, int64_t ldy, int64_t Cout, EpiArgs& epi, bool has_rho, ConvPtrs ptrs, TapsPlan& pl) {
+    if (elem != 0 && elem != 3) return QT_ERR_UNSUPPORTED;        // fp4 nibble planes / fp16 pair planes
+    if (!has_rho) return QT_ERR_INVALID_ARG;
+    if (Cw <= 0 || (Cw & 7)) return QT_ERR_ALIGNMENT;             // a tap = whole 32-byte MFMA k-steps
+    bool valid;
+    int64_t kwords, p_offset;
+    const int rc = conv_geometry(elem, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, ldwp, ldy, Cout, epi, 0, 0, ptrs, pl.cg, valid, pl.M,
+                                 pl.K, kwords, p_offset);
+    if (rc != QT_OK) return rc;
+    pl.cfg = select_conv_taps(pl.M, Cout, kwords * 4, ldwp, valid, epi.d2s_cout != 0, !epi.alpha && epi.mode == 0);
+    return QT_OK;
 }
 
 int conv_taps_impl(int elem, const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, int64_t Cw, int64_t kh, int64_t kw, int64_t sh,
                    int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw, const uint32_t* Wmat, int64_t ldwp, const float* bias,
                    float scale, const float* scale_dev, const float* tap_rho, float* Y, int64_t ldy, int64_t Cout, qt_stream_t stream,
                    EpiArgs epi) {
-    if (elem != 0 && elem != 3) return QT_ERR_UNSUPPORTED;        // fp4 nibble planes / fp16 pair planes
-    if (!tap_rho) return QT_ERR_INVALID_ARG;
-    if (Cw <= 0 || (Cw & 7)) return QT_ERR_ALIGNMENT;             // a tap = whole 32-byte MFMA k-steps
-    ConvArgs cg;
-    bool valid;
-    int64_t M, K, kwords;
-    const int rc = conv_prepare(elem, P, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, Wmat, ldwp, Y, ldy, Cout, epi, 0, 0, cg, valid,
-                                M, K, kwords);
+    TapsPlan pl;
+    const int rc = conv_taps_plan(elem, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, ldwp, ldy, Cout, epi, tap_rho != nullptr,
+                                  conv_check_pointers(P, Wmat, Y), pl);
     if (rc != QT_OK) return rc > 0 ? QT_OK : rc;
     epi.tap_rho = tap_rho;
     epi.tap_ksteps = (int)(Cw / 8);
     epi.ntaps = (int)(kh * kw);
-    if (elem == 0) return dispatch_taps<ElemFp4Taps>(P, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, kwords, valid, stream, cg, epi);
-    return dispatch_taps<ElemF16Taps>(P, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, kwords, valid, stream, cg, epi);
+    if (elem == 0)
+        return launch_taps<ElemFp4Taps>(pl.cfg, P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, pl.M, Cout, pl.K, stream, pl.cg, epi);
+    return launch_taps<ElemF16Taps>(pl.cfg, P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, pl.M, Cout, pl.K, stream, pl.cg, epi);
 }
 
 }  // namespace
@@ -164,6 +164,30 @@ int qt_conv2d_implicit_taps_nib(int elem, const uint32_t* P, int64_t Nimg, int64
                           reinterpret_cast<float*>(nib_plane), ldn, Cout, stream, epi);
 }
 
+int qt_conv2d_implicit_taps_describe(int elem, int64_t Nimg, int64_t H, int64_t W, int64_t Cw, int64_t kh, int64_t kw, int64_t sh, int64_t sw,
+                                     int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t ldwp, int64_t Cout, int64_t in_halo_h,
+                                     int64_t in_halo_w, int epilogue, int has_thr, int64_t d2s_cout, int variant, char* out, int cap) {
+    // the arguments of qt_conv2d_implicit_describe; the per-tap scaled convs take no input halo, thresholds, depth-to-space or variant
+    if (!out || cap < 2) return QT_ERR_INVALID_ARG;
+    out[0] = 0;
+    if (in_halo_h || in_halo_w || has_thr || d2s_cout || variant) return QT_ERR_INVALID_ARG;
+    static const float some = 0.0f;        // "a pointer was given": nothing is read through it
+    EpiArgs epi;
+    int64_t ldy = Cout;
+    if (epilogue == QT_EPI_BITS || epilogue == QT_EPI_NIB) {
+        epi.alpha = epi.beta = &some;
+        epi.mode = epilogue == QT_EPI_NIB ? 3 : 0;
+        ldy = epilogue == QT_EPI_NIB ? (Cout + 31) / 32 * 4 : ((Cout + 31) / 32 + 3) & ~3ll;
+    } else if (epilogue != QT_EPI_PLAIN) {
+        return QT_ERR_INVALID_ARG;
+    }
+    TapsPlan pl;
+    const int rc = conv_taps_plan(elem, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, ldwp, ldy, Cout, epi, true, ConvPtrs{true, true}, pl);
+    if (rc != QT_OK) return rc > 0 ? QT_OK : rc;      // nothing to do: QT_OK and an empty name
+    snprintf(out, (size_t)cap, "%s<%s>", tile_cfg_name(pl.cfg), elem == 0 ? "ElemFp4Taps" : "ElemF16Taps");
+    return QT_OK;
+}
+
 int qt_conv2d_implicit_taps_rows(const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, int64_t Cw, int64_t kh, int64_t kw, int64_t sh,
                                  int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw, const uint32_t* Wmat, int64_t ldwp,
                                  const float* bias, const float* tap_rho, const float* a_plane, float* Y, int64_t ldy, int64_t Cout,
@@ -175,8 +199,9 @@ int qt_conv2d_implicit_taps_rows(const uint32_t* P, int64_t Nimg, int64_t H, int
     EpiArgs epi;
     bool valid;
     int64_t M, K, kwords;
-    const int rc = conv_prepare(0, P, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, Wmat, ldwp, Y, ldy, Cout, epi, 0, 0, cg, valid, M,
-                                K, kwords);
+    int64_t p_offset;
+    const int rc = conv_geometry(0, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, ldwp, ldy, Cout, epi, 0, 0, conv_check_pointers(P, Wmat, Y),
+                                 cg, valid, M, K, kwords, p_offset);
     if (rc != QT_OK) return rc > 0 ? QT_OK : rc;
     epi.tap_rho = tap_rho;
     epi.tap_ksteps = (int)(Cw / 8);

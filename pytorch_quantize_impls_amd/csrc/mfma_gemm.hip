@@ -48,6 +48,7 @@
 
 #include <cstdio>
 #include "mfma_gemm_kernel.h"
+#include "tile_select.h"
 #include "qt_elt.h"
 #include "nib_quant.h"
 
@@ -66,67 +67,145 @@ int check_common(const void* Xn, int64_t ldxp, const void* Wn, int64_t ldwp, con
     return QT_OK;
 }
 
-#define QT_GO(...) return launch_cfg<__VA_ARGS__>(Xn, ldxp, Wn, ldwp, bias, scale, scale_dev, Y, ldy, M, N, K, stream)
-// automatic dispatch: tile width by N and CU fill, fast path when its contract holds
+// ---- TileCfg (tile_select.h) -> launch: one switch per family, whose cases are the configurations that family instantiates ----
+// (a: the arguments of launch_cfg.  A configuration outside the family's set is QT_ERR_UNSUPPORTED, never another kernel.)
+
+// automatic GEMM dispatch (select_gemm)
+template <class E, class... A>
+int launch_gemm_auto(TileCfg cfg, A&&... a) {
+    switch (cfg) {
+        case TileCfg::CfgSkinny512: return launch_cfg<CfgSkinny512<E>>(a...);
+        case TileCfg::CfgSkinny: return launch_cfg<CfgSkinny<E>>(a...);
+        case TileCfg::PP256: return launch_cfg<PP256<E>>(a...);
+        case TileCfg::PP384x192: return launch_cfg<PP384x192<E>>(a...);
+        case TileCfg::PP192: return launch_cfg<PP192<E>>(a...);
+        case TileCfg::PP128: return launch_cfg<PP128<E>>(a...);
+        case TileCfg::Cfg64_1: return launch_cfg<Cfg64<E, 1>>(a...);
+        case TileCfg::Cfg256_0: return launch_cfg<Cfg256<E, 0>>(a...);
+        case TileCfg::Cfg192_0: return launch_cfg<Cfg192<E, 0>>(a...);
+        case TileCfg::Cfg128_0: return launch_cfg<Cfg128<E, 0>>(a...);
+        case TileCfg::Cfg64_0: return launch_cfg<Cfg64<E, 0>>(a...);
+        default: return QT_ERR_UNSUPPORTED;
+    }
+}
+
+// explicit variants (gemm_variant_cfg)
+template <class E, class... A>
+int launch_gemm_variant(TileCfg cfg, A&&... a) {
+    switch (cfg) {
+        case TileCfg::Cfg192_1: return launch_cfg<Cfg192<E, 1>>(a...);
+        case TileCfg::Cfg192_0: return launch_cfg<Cfg192<E, 0>>(a...);
+        case TileCfg::Cfg256_0: return launch_cfg<Cfg256<E, 0>>(a...);
+        case TileCfg::Cfg256_1: return launch_cfg<Cfg256<E, 1>>(a...);
+        case TileCfg::Cfg128_1: return launch_cfg<Cfg128<E, 1>>(a...);
+        case TileCfg::Cfg64_1: return launch_cfg<Cfg64<E, 1>>(a...);
+        case TileCfg::Cfg128_0: return launch_cfg<Cfg128<E, 0>>(a...);
+        case TileCfg::Cfg64_0: return launch_cfg<Cfg64<E, 0>>(a...);
+        case TileCfg::CfgSkinny: return launch_cfg<CfgSkinny<E>>(a...);
+        case TileCfg::CfgSkinny512: return launch_cfg<CfgSkinny512<E>>(a...);
+        case TileCfg::PP256: return launch_cfg<PP256<E>>(a...);
+#ifdef QT_PROFILING_VARIANTS   // stamped / ablated kernels (Y is garbage): never in the product library
+        case TileCfg::PP256_A5: return launch_cfg<PP256<E, 5>>(a...);
+        case TileCfg::PP256_A6: return launch_cfg<PP256<E, 6>>(a...);
+        case TileCfg::Cfg256_1_A1: return launch_cfg<Cfg256<E, 1, 1>>(a...);
+        case TileCfg::Cfg256_1_A2: return launch_cfg<Cfg256<E, 1, 2>>(a...);
+        case TileCfg::Cfg256_1_A3: return launch_cfg<Cfg256<E, 1, 3>>(a...);
+        case TileCfg::Cfg256_1_A4: return launch_cfg<Cfg256<E, 1, 4>>(a...);
+#endif
+        case TileCfg::PP128: return launch_cfg<PP128<E>>(a...);
+        case TileCfg::PP192: return launch_cfg<PP192<E>>(a...);
+        case TileCfg::PP64: return launch_cfg<PP64<E>>(a...);
+        case TileCfg::PP384x192: return launch_cfg<PP384x192<E>>(a...);
+        default: return QT_ERR_UNSUPPORTED;
+    }
+}
+
+// batched GEMMs (select_gemm_batched); ROWS384: the bf16 tap GEMM's set has the 384-row tile, the int8 split-K set has not
+template <class E, bool ROWS384, class... A>
+int launch_gemm_batched(TileCfg cfg, A&&... a) {
+    switch (cfg) {
+        case TileCfg::PP256: return launch_cfg<PP256<E>>(a...);
+        case TileCfg::PP384x192:
+            if constexpr (ROWS384) return launch_cfg<PP384x192<E>>(a...);
+            else return QT_ERR_UNSUPPORTED;
+        case TileCfg::PP192: return launch_cfg<PP192<E>>(a...);
+        case TileCfg::PP128: return launch_cfg<PP128<E>>(a...);
+        case TileCfg::PP64: return launch_cfg<PP64<E>>(a...);
+        default: return QT_ERR_UNSUPPORTED;
+    }
+}
+
+// implicit-GEMM convs (select_conv).  t: the weights-as-rows (sign-bit) instantiation of a configuration that has one
+template <class E, class... A>
+int launch_conv(TileCfg cfg, bool t, A&&... a) {
+    switch (cfg) {
+        case TileCfg::ConvV128x128D: return launch_cfg_t<ConvV128x128D, E>(t, a...);
+        case TileCfg::ConvV128x128: return launch_cfg<ConvV128x128<E>>(a...);
+        case TileCfg::ConvV128x64D: return launch_cfg<ConvV128x64D<E>>(a...);
+        case TileCfg::ConvV128x64: return launch_cfg<ConvV128x64<E>>(a...);
+        case TileCfg::ConvVSkinny: return launch_cfg<ConvVSkinny<E>>(a...);
+        case TileCfg::ConvV128x2: return launch_cfg_t<ConvV128x2, E>(t, a...);
+        case TileCfg::ConvVPP192: return launch_cfg_t<ConvVPP192, E>(t, a...);
+        case TileCfg::ConvVPP256: return launch_cfg_t<ConvVPP256, E>(t, a...);
+        case TileCfg::ConvVPP256x192: return launch_cfg_t<ConvVPP256x192, E>(t, a...);
+        case TileCfg::ConvV64x2: return launch_cfg<ConvV64x2<E>>(a...);
+        case TileCfg::ConvV256: return launch_cfg<ConvV256<E>>(a...);
+        case TileCfg::ConvV192: return launch_cfg<ConvV192<E>>(a...);
+        case TileCfg::ConvV128: return launch_cfg<ConvV128<E>>(a...);
+        case TileCfg::ConvV64: return launch_cfg<ConvV64<E>>(a...);
+        case TileCfg::Conv128x128: return launch_cfg<Conv128x128<E>>(a...);
+        case TileCfg::ConvSkinny: return launch_cfg<ConvSkinny<E>>(a...);
+        case TileCfg::ConvPP192: return launch_cfg<ConvPP192<E>>(a...);
+        case TileCfg::ConvPP256: return launch_cfg<ConvPP256<E>>(a...);
+        case TileCfg::ConvPP256x192: return launch_cfg<ConvPP256x192<E>>(a...);
+        case TileCfg::ConvPP128: return launch_cfg<ConvPP128<E>>(a...);
+        case TileCfg::ConvPP64: return launch_cfg<ConvPP64<E>>(a...);
+        case TileCfg::Conv256: return launch_cfg<Conv256<E>>(a...);
+        case TileCfg::Conv192: return launch_cfg<Conv192<E>>(a...);
+        case TileCfg::Conv128: return launch_cfg<Conv128<E>>(a...);
+        case TileCfg::Conv64: return launch_cfg<Conv64<E>>(a...);
+#ifdef QT_PROFILING_VARIANTS
+        case TileCfg::ConvVPP192Stamps: return launch_cfg<ConvVPP192Stamps<E>>(a...);
+        case TileCfg::ConvPP192Stamps: return launch_cfg<ConvPP192Stamps<E>>(a...);
+#endif
+        default: return QT_ERR_UNSUPPORTED;
+    }
+}
+
 template <class E>
 int dispatch_gemm_auto(const uint32_t* Xn, int64_t ldxp, const uint32_t* Wn, int64_t ldwp,
                        const float* bias, float scale, const float* scale_dev, float* Y, int64_t ldy, int64_t M,
                        int64_t N, int64_t K, qt_stream_t stream) {
-    const bool pipe_ok = !(ldxp & 31) && !(ldwp & 31) && M * ldxp * 4 < (1ll << 31) &&
-                         N * ldwp * 4 < (1ll << 31);
-    const int tn = pick_tile_n_gemm(M, N);
-    // skinny (FC at batch <= 512): the K loop is a chain of latency-bound stage round trips on a quarter of
-    // the CUs — 128x64 tiles and 256-byte stages (tools/bench_gemm_variants.py: 256x4096x25088 75 -> 48 us)
-    // ... and 64x64 tiles with 512-byte stages up to M = 256 (256x4096x9216: 21.4 -> 13.7 us)
-    if (pipe_ok && M <= 256 && !((ldxp | ldwp) & 127)) QT_GO(CfgSkinny512<E>);
-    if (pipe_ok && M <= 512 && !((ldxp | ldwp) & 63)) QT_GO(CfgSkinny<E>);
-    if (pipe_ok) {
-        if (tn == 256) QT_GO(PP256<E>);
-        if (tn == 192 && prefer_384_rows(M, N)) QT_GO(PP384x192<E>);
-        if (tn == 192) QT_GO(PP192<E>);
-        if (tn == 128) QT_GO(PP128<E>);
-        QT_GO(Cfg64<E, 1>);
-    }
-    if (tn == 256) QT_GO(Cfg256<E, 0>);
-    if (tn == 192) QT_GO(Cfg192<E, 0>);
-    if (tn == 128) QT_GO(Cfg128<E, 0>);
-    QT_GO(Cfg64<E, 0>);
+    return launch_gemm_auto<E>(select_gemm(M, N, ldxp, ldwp), Xn, ldxp, Wn, ldwp, bias, scale, scale_dev, Y, ldy, M, N, K, stream);
 }
 
 template <class E>
 int dispatch_gemm(int variant, const uint32_t* Xn, int64_t ldxp, const uint32_t* Wn, int64_t ldwp,
                   const float* bias, float scale, const float* scale_dev, float* Y, int64_t ldy, int64_t M,
                   int64_t N, int64_t K, qt_stream_t stream) {
-    const bool pipe_ok = !(ldxp & 31) && !(ldwp & 31) && M * ldxp * 4 < (1ll << 31) &&
-                         N * ldwp * 4 < (1ll << 31);
-    switch (variant) {
-        case 0: return dispatch_gemm_auto<E>(Xn, ldxp, Wn, ldwp, bias, scale, scale_dev, Y, ldy, M, N, K, stream);
-        case 15: if (!pipe_ok) return QT_ERR_ALIGNMENT; QT_GO(Cfg192<E, 1>);
-        case 16: QT_GO(Cfg192<E, 0>);
-        case 5: QT_GO(Cfg256<E, 0>);
-        case 6: if (!pipe_ok) return QT_ERR_ALIGNMENT; QT_GO(Cfg256<E, 1>);
-        case 7: if (!pipe_ok) return QT_ERR_ALIGNMENT; QT_GO(Cfg128<E, 1>);
-        case 8: if (!pipe_ok) return QT_ERR_ALIGNMENT; QT_GO(Cfg64<E, 1>);
-        case 9: QT_GO(Cfg128<E, 0>);
-        case 10: QT_GO(Cfg64<E, 0>);
-        case 30: if (!pipe_ok || ((ldxp | ldwp) & 63)) return QT_ERR_ALIGNMENT; QT_GO(CfgSkinny<E>);
-        case 31: if (!pipe_ok || ((ldxp | ldwp) & 127)) return QT_ERR_ALIGNMENT; QT_GO(CfgSkinny512<E>);
-        case 20: if (!pipe_ok) return QT_ERR_ALIGNMENT; QT_GO(PP256<E>);
-#ifdef QT_PROFILING_VARIANTS   // stamped / ablated kernels (Y is garbage): never in the product library
-        case 165: if (!pipe_ok) return QT_ERR_ALIGNMENT; QT_GO(PP256<E, 5>);
-        case 166: if (!pipe_ok) return QT_ERR_ALIGNMENT; QT_GO(PP256<E, 6>);
-        case 161: if (!pipe_ok) return QT_ERR_ALIGNMENT; QT_GO(Cfg256<E, 1, 1>);
-        case 162: if (!pipe_ok) return QT_ERR_ALIGNMENT; QT_GO(Cfg256<E, 1, 2>);
-        case 163: if (!pipe_ok) return QT_ERR_ALIGNMENT; QT_GO(Cfg256<E, 1, 3>);
-        case 164: if (!pipe_ok) return QT_ERR_ALIGNMENT; QT_GO(Cfg256<E, 1, 4>);
-#endif
-        case 21: if (!pipe_ok) return QT_ERR_ALIGNMENT; QT_GO(PP128<E>);
-        case 22: if (!pipe_ok) return QT_ERR_ALIGNMENT; QT_GO(PP192<E>);
-        case 23: if (!pipe_ok) return QT_ERR_ALIGNMENT; QT_GO(PP64<E>);
-        case 24: if (!pipe_ok) return QT_ERR_ALIGNMENT; QT_GO(PP384x192<E>);
-        default: return QT_ERR_UNSUPPORTED;
+    if (variant == 0) return dispatch_gemm_auto<E>(Xn, ldxp, Wn, ldwp, bias, scale, scale_dev, Y, ldy, M, N, K, stream);
+    TileCfg cfg;
+    const int rc = gemm_variant_cfg(variant, gemm_pipe_ok(M, N, ldxp, ldwp), ldxp, ldwp, &cfg);
+    if (rc != QT_OK) return rc;
+    return launch_gemm_variant<E>(cfg, Xn, ldxp, Wn, ldwp, bias, scale, scale_dev, Y, ldy, M, N, K, stream);
+}
+
+// "<tile>, <pipeline>" of an automatic-dispatch configuration, as qt_nib_gemm_describe has always printed it
+const char* gemm_tile_text(TileCfg cfg) {
+    switch (cfg) {
+        case TileCfg::CfgSkinny512: return "64x64, 512-byte stages, pipe=1";
+        case TileCfg::CfgSkinny: return "128x64, 256-byte stages, pipe=1";
+        case TileCfg::PP256: return "256x256, pipe=2 (ping-pong)";
+        case TileCfg::PP384x192: return "384x192, pipe=2 (ping-pong)";
+        case TileCfg::PP192: return "256x192, pipe=2 (ping-pong)";
+        case TileCfg::PP128: return "256x128, pipe=2 (ping-pong)";
+        case TileCfg::Cfg64_1: return "256x64, pipe=1";
+        case TileCfg::Cfg256_0: return "256x256, pipe=0";
+        case TileCfg::Cfg192_0: return "256x192, pipe=0";
+        case TileCfg::Cfg128_0: return "256x128, pipe=0";
+        case TileCfg::Cfg64_0: return "256x64, pipe=0";
+        default: return "?";
     }
-#undef QT_GO
 }
 
 // ---- fp32 / bf16 / fp16 -> nibble plane (element types: qt_elt.h) ---------------------------------
@@ -463,19 +542,10 @@ int qt_nib_gemm_variant(int variant, const uint32_t* Xn, int64_t ldxp, const uin
 }
 
 int qt_nib_gemm_describe(int64_t M, int64_t N, int64_t K, int64_t ldxp, int64_t ldwp, char* out, int cap) {
-    // the tile configuration dispatch_gemm's automatic rule (variant 0) launches for this shape: "<kernel><element, tile, pipeline>"
+    // the tile configuration the automatic rule (select_gemm, which dispatch_gemm_auto launches from) gives this shape:
+    // "<kernel><element, tile, pipeline>"
     if (!out || cap < 2 || M <= 0 || N <= 0 || K < 0) return QT_ERR_INVALID_ARG;
-    const bool pipe_ok = !(ldxp & 31) && !(ldwp & 31) && M * ldxp * 4 < (1ll << 31) && N * ldwp * 4 < (1ll << 31);
-    const int tn = pick_tile_n_gemm(M, N);
-    const char* cfg;
-    if (pipe_ok && M <= 256 && !((ldxp | ldwp) & 127)) cfg = "64x64, 512-byte stages, pipe=1";
-    else if (pipe_ok && M <= 512 && !((ldxp | ldwp) & 63)) cfg = "128x64, 256-byte stages, pipe=1";
-    else if (pipe_ok && tn == 256) cfg = "256x256, pipe=2 (ping-pong)";
-    else if (pipe_ok && tn == 192) cfg = prefer_384_rows(M, N) ? "384x192, pipe=2 (ping-pong)" : "256x192, pipe=2 (ping-pong)";
-    else if (pipe_ok && tn == 128) cfg = "256x128, pipe=2 (ping-pong)";
-    else if (pipe_ok) cfg = "256x64, pipe=1";
-    else cfg = tn == 256 ? "256x256, pipe=0" : tn == 192 ? "256x192, pipe=0" : tn == 128 ? "256x128, pipe=0" : "256x64, pipe=0";
-    snprintf(out, (size_t)cap, "mfma_gemm_kernel<ElemFp4, %s>", cfg);
+    snprintf(out, (size_t)cap, "mfma_gemm_kernel<ElemFp4, %s>", gemm_tile_text(select_gemm(M, N, ldxp, ldwp)));
     return QT_OK;
 }
 
@@ -519,7 +589,7 @@ int qt_bf16_gemm_taps(const uint32_t* Xh, int64_t ldxp, const uint32_t* Wh, int6
     if (K <= 0 || (K & 31)) return QT_ERR_ALIGNMENT;                       // whole 64-byte stages per slice
     if ((w_copy_bytes | w_row_bytes) & 15) return QT_ERR_ALIGNMENT;        // every tap's W base stays 16-byte aligned
     if (y_stride < M * ldy || (ldy & 3) || !qt_aligned16(Y) || (y_stride & 3)) return QT_ERR_ALIGNMENT;
-    if ((ldxp & 31) || (ldwp & 31) || M * ldxp * 4 >= (1ll << 31) || N * ldwp * 4 >= (1ll << 31)) return QT_ERR_UNSUPPORTED;
+    if (!gemm_pipe_ok(M, N, ldxp, ldwp)) return QT_ERR_UNSUPPORTED;
     ConvArgs cg{};
     cg.H = (int)(tap_rows * tap_cols);
     cg.z_nslice = (int)nslice;
@@ -528,16 +598,7 @@ int qt_bf16_gemm_taps(const uint32_t* Xh, int64_t ldxp, const uint32_t* Wh, int6
     cg.z_w_copy_bytes = w_copy_bytes;
     cg.z_w_row_bytes = w_row_bytes;
     cg.z_y_stride = y_stride;
-#define QT_GOZ(...) return launch_cfg<__VA_ARGS__>(Xh, ldxp, Wh, ldwp, nullptr, 1.0f, nullptr, Y, ldy, M, N, K, stream, cg)
-    const int tn = pick_tile_n(N);
-    if (tn == 256) QT_GOZ(PP256<ElemBf16>);
-    if (tn == 192) {
-        if ((M + 383) / 384 * 384 <= (M + 255) / 256 * 256) QT_GOZ(PP384x192<ElemBf16>);
-        QT_GOZ(PP192<ElemBf16>);
-    }
-    if (tn == 128) QT_GOZ(PP128<ElemBf16>);
-    QT_GOZ(PP64<ElemBf16>);
-#undef QT_GOZ
+    return launch_gemm_batched<ElemBf16, true>(select_gemm_batched(M, N, true), Xh, ldxp, Wh, ldwp, nullptr, 1.0f, nullptr, Y, ldy, M, N, K, stream, cg);
 }
 
 int qt_i8_gemm(const uint32_t* Xc, int64_t ldxp, const uint32_t* Wc, int64_t ldwp, const float* bias,
@@ -563,20 +624,14 @@ int qt_i8_gemm_splitk(const uint32_t* Xc, int64_t ldxp, const uint32_t* Wc, int6
     if (nslice < 1 || nslice > 65535 || kslice <= 0 || (kslice & 63)) return QT_ERR_ALIGNMENT;          // whole 64-byte stages per slice
     if (127 * kslice * nslice >= (1ll << 24)) return QT_ERR_UNSUPPORTED;                                 // partial sums exact in fp32
     if (y_stride < M * ldy || (ldy & 3) || !qt_aligned16(Y) || (y_stride & 3)) return QT_ERR_ALIGNMENT;
-    if ((ldxp & 31) || (ldwp & 31) || M * ldxp * 4 >= (1ll << 31) || N * ldwp * 4 >= (1ll << 31)) return QT_ERR_UNSUPPORTED;
+    if (!gemm_pipe_ok(M, N, ldxp, ldwp)) return QT_ERR_UNSUPPORTED;
     ConvArgs cg{};
     cg.H = 1;
     cg.z_nslice = (int)nslice;
     cg.z_kw = 1;
     cg.z_kslice_bytes = kslice;
     cg.z_y_stride = y_stride;
-#define QT_GOZ(...) return launch_cfg<__VA_ARGS__>(Xc, ldxp, Wc, ldwp, nullptr, 1.0f, nullptr, Y, ldy, M, N, kslice, stream, cg)
-    const int tn = pick_tile_n(N);
-    if (tn == 256) QT_GOZ(PP256<ElemI8>);
-    if (tn == 192) QT_GOZ(PP192<ElemI8>);
-    if (tn == 128) QT_GOZ(PP128<ElemI8>);
-    QT_GOZ(PP64<ElemI8>);
-#undef QT_GOZ
+    return launch_gemm_batched<ElemI8, false>(select_gemm_batched(M, N, false), Xc, ldxp, Wc, ldwp, nullptr, 1.0f, nullptr, Y, ldy, M, N, kslice, stream, cg);
 }
 
 // conv kernel variant = tile form | QT_CONV_* flags (an ARGUMENT: qt_conv2d_implicit_variant takes both, the bits / nib / codes entries
@@ -584,6 +639,45 @@ int qt_i8_gemm_splitk(const uint32_t* Xc, int64_t ldxp, const uint32_t* Wc, int6
 // (192-wide tiles: ping-pong on a 384x192 tile, whose 96x96 wave tiles keep the load segment under the compute segment:
 // AlexNet conv2 302 -> 275 us; other widths: double-buffered, equal or faster there), 1 = double-buffered, 2 = ping-pong,
 // 4 = automatic without the un-padded fast path; 3 = stamped 384x192 ping-pong, only in -DQT_PROFILING_VARIANTS builds
+
+// What conv_implicit_impl launches, worked out from the numbers alone (the describe entry point calls this and stops here).
+enum class ConvElem { Fp4, Fp4T, Fp4OutBf16, Fp4OutF16, I8, F16, Bf16, Bf16L };
+struct ConvPlan {
+    ConvArgs cg;
+    int64_t M, K, p_offset;
+    TileCfg cfg;
+    ConvElem elem;
+};
+static int conv_plan(int elem, int64_t Nimg, int64_t H, int64_t W, int64_t Cw, int64_t kh, int64_t kw, int64_t sh, int64_t sw,
+                     int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t ldwp, int64_t ldy, int64_t Cout, EpiArgs& epi, int64_t hy,
+                     int64_t hx, int variant, int out_dtype, ConvPtrs ptrs, ConvPlan& pl) {
+    int form = variant & 0xf;          // the entry points have refused unknown bits
+#ifdef QT_EXPERIMENT   // A/B builds only (make EXTRA=-DQT_EXPERIMENT): a variant for the entry points that take none
+    if (form == 0 && getenv("QT_CONV_FORCE_EXP")) form = atoi(getenv("QT_CONV_FORCE_EXP"));
+#endif
+    bool valid;
+    int64_t kwords;
+    const int rc = conv_geometry(elem, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, ldwp, ldy, Cout, epi, hy, hx, ptrs, pl.cg, valid,
+                                 pl.M, pl.K, kwords, pl.p_offset);
+    if (rc != QT_OK) return rc;
+    // weights-as-rows threshold epilogue (sign-bit form): fp4, integer thresholds, whole 32-channel blocks, bit plane or nibble plane
+    // out, no depth-to-space; QT_CONV_COMPARE_THRESHOLDS: the compare form (A/B runs and the bit-identity test)
+    const bool swapt = elem == 0 && epi.alpha && epi.thr && (Cout & 31) == 0 && !epi.d2s_cout && (epi.mode == 0 || epi.mode == 3) &&
+                       !(variant & QT_CONV_COMPARE_THRESHOLDS);
+    // the level epilogue (mode 5) walks the tiles of the plain conv of its geometry: the accumulators are then the same bits
+    const bool plain_tiles = (!epi.alpha && epi.mode == 0) || epi.mode == 5;
+    const ConvChoice pick = select_conv({pl.M, Cout, kwords * 4, ldwp, valid, epi.d2s_cout != 0, plain_tiles, epi.alpha != nullptr, form,
+                                         variant & QT_CONV_FLAGS_MASK});
+    if (pick.cfg == TileCfg::None) return QT_ERR_UNSUPPORTED;
+    pl.cfg = pick.cfg;
+    pl.elem = elem == 0 && out_dtype == QT_DTYPE_BF16 ? ConvElem::Fp4OutBf16
+              : elem == 0 && out_dtype == QT_DTYPE_F16 ? ConvElem::Fp4OutF16
+              : elem == 0 ? (swapt && pick.sign_bit_capable ? ConvElem::Fp4T : ConvElem::Fp4)
+              : elem == 1 ? ConvElem::I8
+              : elem == 3 ? ConvElem::F16
+              : epi.mode == 5 ? ConvElem::Bf16L : ConvElem::Bf16;
+    return QT_OK;
+}
 
 // elem: 0 = fp4 nibble planes, 1 = int8 code planes, 2 = bf16 (triple) planes, 3 = fp16 (pair) planes.  epi.alpha != nullptr:
 // Y is the threshold-bit plane and ldy its row stride in words.
@@ -596,125 +690,24 @@ static int conv_implicit_impl(int elem, const uint32_t* P, int64_t Nimg, int64_t
     // (hy, hx): halo of the INPUT plane, [N][H + 2hy][W + 2hx][Cw] with a zero border: a conv whose padding fits in
     // the halo runs as the un-padded conv on the window that starts (hy - ph, hx - pw) into the plane.
     EpiArgs epi = epi_in;
-    int g_conv_force = variant & 0xf;          // the entry points have refused unknown bits
-#ifdef QT_EXPERIMENT   // A/B builds only (make EXTRA=-DQT_EXPERIMENT): a variant for the entry points that take none
-    if (g_conv_force == 0 && getenv("QT_CONV_FORCE_EXP")) g_conv_force = atoi(getenv("QT_CONV_FORCE_EXP"));
-#endif
-    ConvArgs cg;
-    bool valid;
-    int64_t M, K, kwords;
-    {
-        const int rc = conv_prepare(elem, P, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, Wmat, ldwp, Y, ldy, Cout, epi, hy, hx,
-                                    cg, valid, M, K, kwords);
-        if (rc != QT_OK) return rc > 0 ? QT_OK : rc;
+    ConvPlan pl;
+    const int rc = conv_plan(elem, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, ldwp, ldy, Cout, epi, hy, hx, variant, out_dtype,
+                             conv_check_pointers(P, Wmat, Y), pl);
+    if (rc != QT_OK) return rc > 0 ? QT_OK : rc;
+    P += pl.p_offset;
+    const bool t = pl.elem == ConvElem::Fp4T;
+    switch (pl.elem) {
+#define QT_CONV_AS(E) return launch_conv<E>(pl.cfg, t, P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, pl.M, Cout, pl.K, stream, pl.cg, epi)
+        case ConvElem::Fp4OutBf16: QT_CONV_AS(ElemFp4Out<1>);
+        case ConvElem::Fp4OutF16: QT_CONV_AS(ElemFp4Out<2>);
+        case ConvElem::Fp4: case ConvElem::Fp4T: QT_CONV_AS(ElemFp4);
+        case ConvElem::I8: QT_CONV_AS(ElemI8);
+        case ConvElem::F16: QT_CONV_AS(ElemF16);
+        case ConvElem::Bf16L: QT_CONV_AS(ElemBf16L);
+        case ConvElem::Bf16: QT_CONV_AS(ElemBf16);
+#undef QT_CONV_AS
     }
-#ifdef QT_PROFILING_VARIANTS
-#define QT_CONV_STAMPS_V(E) if (valid && g_conv_force == 3 && tn == 192 && !epi.alpha) \
-        return launch_cfg<ConvVPP192Stamps<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi);
-#define QT_CONV_STAMPS(E) if (g_conv_force == 3 && tn == 192 && !epi.alpha) \
-        return launch_cfg<ConvPP192Stamps<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi);
-#else
-#define QT_CONV_STAMPS_V(E)
-#define QT_CONV_STAMPS(E)
-    if (g_conv_force == 3) return QT_ERR_UNSUPPORTED;
-#endif
-    // ring of 3 / 4 stage buffers on the small-map tiles (ConvV128x128D / ConvV128x64D); QT_CONV_NO_DEEP_RING: the double-buffered
-    // configurations of round 4 (A/B runs and the bit-identity test)
-    const bool deep_ring = !(variant & QT_CONV_NO_DEEP_RING);
-    // at most this many 256-row tiles and 128 x 128 tiles: 128 x 128 tiles with the deep ring (A/B: profiles/r6_c3_pmc.md)
-    const long long small_grid = 128, small_tiles = 512;
-    // weights-as-rows threshold epilogue (sign-bit form): fp4, integer thresholds, whole 32-channel blocks, bit plane or nibble plane
-    // out, no depth-to-space; QT_CONV_COMPARE_THRESHOLDS: the compare form (A/B runs and the bit-identity test)
-    const bool swapt = elem == 0 && epi.alpha && epi.thr && (Cout & 31) == 0 && !epi.d2s_cout && (epi.mode == 0 || epi.mode == 3) &&
-                       !(variant & QT_CONV_COMPARE_THRESHOLDS);
-    // the level epilogue (mode 5) walks the tiles of the plain conv of its geometry: the accumulators are then the same bits
-    const bool plain_tiles = (!epi.alpha && epi.mode == 0) || epi.mode == 5;
-#define QT_CONV(E)                                                                                              \
-    do {                                                                                                        \
-        const int tn = pick_tile_n(Cout);                                                                       \
-        QT_CONV_STAMPS_V(E)                                                                                     \
-        if (valid && g_conv_force != 4 && g_conv_force != 3) {                                                  \
-            if (g_conv_force == 0 && kwords * 4 >= 2048 && !(ldwp & 127) && !epi.d2s_cout &&                  \
-                (M <= 4096 || (((M + 255) / 256) * ((Cout + tn - 1) / tn) < 256 &&                              \
-                               (M / 64) * Cout * kwords * 4 <= (256ll << 20)))) {                               \
-                if (M > 4096 && ((M + 127) / 128) * ((Cout + 127) / 128) >= 200) {                             \
-                    if (deep_ring) return launch_cfg_t<ConvV128x128D, E>(swapt, P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-                    return launch_cfg<ConvV128x128<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-                }                                                                                               \
-                if (((M + 127) / 128) * ((Cout + 63) / 64) >= 200) { /* 512 ch @ 4x4: 128x64 tiles, 256-byte stages */ \
-                    if (deep_ring) return launch_cfg<ConvV128x64D<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-                    return launch_cfg<ConvV128x64<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-                }                                                                                               \
-                return launch_cfg<ConvVSkinny<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-            }                                                                                                   \
-            /* a handful of K stages: a tile is all prologue + epilogue, so 2 co-resident 256x128 workgroups per CU */ \
-            /* that overlap each other's beat the 1-per-CU ping-pong tiles (output-blocked first layers: K = 320 B) */ \
-            if (g_conv_force == 0 && tn == 256 && kwords * 4 <= 1024)                                           \
-                return launch_cfg_t<ConvV128x2, E>(swapt, P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-            /* a few big tiles on a small map (128 -> 256 stride 2 @ 16x16, K = 1152 B: 64 tiles of 256x256): 128x128 tiles */ \
-            /* with the deep ring give every CU one                                                                        */ \
-            if (g_conv_force == 0 && deep_ring && !epi.d2s_cout && ((M + 255) / 256) * ((Cout + tn - 1) / tn) <= small_grid && \
-                ((M + 127) / 128) * ((Cout + 127) / 128) >= 200 && ((M + 127) / 128) * ((Cout + 127) / 128) <= small_tiles) \
-                return launch_cfg_t<ConvV128x128D, E>(swapt, P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-            if (g_conv_force != 1) {                                                                            \
-                if (tn == 192 && (g_conv_force == 2 || prefer_384_rows(M, Cout)))                               \
-                    return launch_cfg_t<ConvVPP192, E>(swapt, P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-                if (tn == 256) return launch_cfg_t<ConvVPP256, E>(swapt, P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-                /* 192-wide tiles whose 384-row form wastes a round (576 -> 1152 @ 13x13): 256x192 ping-pong for long K */ \
-                if (tn == 192 && g_conv_force == 0 && kwords * 4 >= 2048)                                         \
-                    return launch_cfg_t<ConvVPP256x192, E>(swapt, P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-            }                                                                                                   \
-            if (g_conv_force == 0 && tn == 64 && kwords * 4 <= 1024)                                            \
-                return launch_cfg<ConvV64x2<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-            if (g_conv_force == 0 && tn == 128 && kwords * 4 <= 1024)                                           \
-                return launch_cfg_t<ConvV128x2, E>(swapt, P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-            if (tn == 256) return launch_cfg<ConvV256<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-            if (tn == 192) return launch_cfg<ConvV192<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-            if (tn == 128) return launch_cfg<ConvV128<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-            return launch_cfg<ConvV64<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi);                 \
-        }                                                                                                       \
-        QT_CONV_STAMPS(E)                                                                                       \
-        if (g_conv_force == 5 && !epi.alpha && epi.mode == 0)                                                   \
-            return launch_cfg<Conv128x128<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-        if (g_conv_force == 6 && !epi.alpha && epi.mode == 0 && kwords * 4 >= 2048 && !(ldwp & 127))            \
-            return launch_cfg<ConvSkinny<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-        if (g_conv_force == 0 && plain_tiles && ((M + 255) / 256) * ((Cout + tn - 1) / tn) < 200) {     \
-            /* small maps: fewer 256-row tiles than CUs (tools/bench_conv_small_maps.py: 256 ch @ 8x8 137 -> 83 us,  */ \
-            /* 512 ch @ 4x4 239 -> 102 us incl. the operand split; same accumulation order, bit-identical results)   */ \
-            if (((M + 127) / 128) * ((Cout + 127) / 128) < 200 && kwords * 4 >= 2048 && !(ldwp & 127))          \
-                return launch_cfg<ConvSkinny<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-            return launch_cfg<Conv128x128<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-        }                                                                                                       \
-        if (g_conv_force == 0 && tn == 192 && prefer_384_rows(M, Cout))                                         \
-            return launch_cfg<ConvPP192<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-        /* long K (>= 2 KiB per output row), wide tiles: the ping-pong main loop beats the double-buffered one on the   */ \
-        /* padded convs too (tools/bench_grad_input_variants.py: grad_x 512 ch @ 28x28 0.532 -> 0.485 ms, 768 -> 1152   */ \
-        /* @ 13x13 1.34 -> 1.25); the 384-row tile only where its rounds pay (above), else 256 rows                     */ \
-        if (g_conv_force == 0 && kwords * 4 >= 2048) {                                                          \
-            if (tn == 256) return launch_cfg<ConvPP256<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-            if (tn == 192) return launch_cfg<ConvPP256x192<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-        }                                                                                                       \
-        if (g_conv_force == 2) {                                                                                \
-            if (tn == 256) return launch_cfg<ConvPP256<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-            if (tn == 192) return launch_cfg<ConvPP192<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-            if (tn == 128) return launch_cfg<ConvPP128<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-            return launch_cfg<ConvPP64<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi);                 \
-        }                                                                                                       \
-        if (tn == 256) return launch_cfg<Conv256<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-        if (tn == 192) return launch_cfg<Conv192<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-        if (tn == 128) return launch_cfg<Conv128<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi); \
-        return launch_cfg<Conv64<E>>(P, 0, Wmat, ldwp, bias, scale, scale_dev, Y, ldy, M, Cout, K, stream, cg, epi);                 \
-    } while (0)
-    if (elem == 0 && out_dtype == QT_DTYPE_BF16) QT_CONV(ElemFp4Out<1>);
-    if (elem == 0 && out_dtype == QT_DTYPE_F16) QT_CONV(ElemFp4Out<2>);
-    if (elem == 0) QT_CONV(ElemFp4);
-    if (elem == 1) QT_CONV(ElemI8);
-    if (elem == 3) QT_CONV(ElemF16);
-    if (epi.mode == 5) QT_CONV(ElemBf16L);
-    QT_CONV(ElemBf16);
-#undef QT_CONV
-#undef QT_CONV_STAMPS
-#undef QT_CONV_STAMPS_V
+    return QT_ERR_UNSUPPORTED;
 }
 
 int qt_conv2d_implicit_variant(int variant, int elem, const uint32_t* P, int64_t Nimg, int64_t H, int64_t W, int64_t Cw,
@@ -889,6 +882,91 @@ int qt_conv2d_implicit_halo_bn(int elem, const uint32_t* P, int64_t Nimg, int64_
     epi.mode = 4;
     return conv_implicit_impl(elem, P, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, Wmat, ldwp, bias, scale,
                               scale_dev, Y, ldy, Cout, stream, epi, halo_h, halo_w);
+}
+
+int qt_conv2d_implicit_describe(int elem, int64_t Nimg, int64_t H, int64_t W, int64_t Cw, int64_t kh, int64_t kw, int64_t sh, int64_t sw,
+                                int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t ldwp, int64_t Cout, int64_t in_halo_h,
+                                int64_t in_halo_w, int epilogue, int has_thr, int64_t d2s_cout, int variant, char* out, int cap) {
+    // The entry point of this epilogue with a dense output plane, up to the launch: its own argument checks on the numbers, then
+    // conv_plan — the function conv_implicit_impl launches from.
+    if (!out || cap < 2) return QT_ERR_INVALID_ARG;
+    out[0] = 0;
+    if (variant < 0 || (variant & ~(0xf | QT_CONV_FLAGS_MASK)) || (variant & 0xf) > 6) return QT_ERR_INVALID_ARG;
+    const bool halo = (in_halo_h | in_halo_w) != 0;
+    if ((epilogue != QT_EPI_PLAIN && (variant & 0xf)) || (has_thr && epilogue != QT_EPI_BITS && epilogue != QT_EPI_NIB) ||
+        (d2s_cout && epilogue != QT_EPI_NIB))
+        return QT_ERR_INVALID_ARG;         // no entry point takes these together
+    static const float some = 0.0f;        // "a pointer was given": nothing is read through it
+    EpiArgs epi;
+    int64_t ldy = Cout;
+    int out_dtype = 0;
+    switch (epilogue) {
+        case QT_EPI_PLAIN: break;
+        case QT_EPI_HALF_BF16: case QT_EPI_HALF_F16:
+            if (elem != 0 || halo) return QT_ERR_INVALID_ARG;
+            out_dtype = epilogue == QT_EPI_HALF_BF16 ? QT_DTYPE_BF16 : QT_DTYPE_F16;
+            break;
+        case QT_EPI_BITS: case QT_EPI_NIB:
+            if (halo || (has_thr && elem >= 2)) return QT_ERR_INVALID_ARG;
+            epi.alpha = epi.beta = &some;
+            epi.thr = has_thr ? &some : nullptr;
+            ldy = ((Cout + 31) / 32 + 3) & ~3ll;
+            if (epilogue == QT_EPI_NIB) {
+                if (d2s_cout < 0 || (d2s_cout && (d2s_cout % 32 || Cout != 4 * d2s_cout))) return QT_ERR_INVALID_ARG;
+                epi.mode = 3;
+                epi.d2s_cout = (int)d2s_cout;
+                ldy = ((d2s_cout ? d2s_cout : Cout) + 31) / 32 * 4;
+            }
+            break;
+        case QT_EPI_CODES:
+            if (elem != 1) return QT_ERR_UNSUPPORTED;
+            epi.alpha = epi.beta = &some;
+            epi.mode = 2;
+            ldy = (Cout + 15) & ~15ll;
+            break;
+        case QT_EPI_HALO_BN:
+            if (elem != 1) return QT_ERR_UNSUPPORTED;
+            if (Cout & 3) return QT_ERR_ALIGNMENT;
+            epi.alpha = epi.beta = epi.bn_stats = &some;
+            epi.mode = 4;
+            break;
+        case QT_EPI_LEVELS:
+            if (elem != 2) return QT_ERR_INVALID_ARG;
+            epi.alpha = epi.beta = epi.bn_stats = &some;
+            epi.mode = 5;
+            ldy = (2 * Cout + 15) & ~15ll;
+            break;
+        default: return QT_ERR_INVALID_ARG;
+    }
+    ConvPlan pl;
+    const int rc = conv_plan(elem, Nimg, H, W, Cw, kh, kw, sh, sw, ph, pw, dh, dw, ldwp, ldy, Cout, epi, in_halo_h, in_halo_w, variant,
+                             out_dtype, ConvPtrs{true, true}, pl);
+    if (rc != QT_OK) return rc > 0 ? QT_OK : rc;      // nothing to do: QT_OK and an empty name
+    static const char* const elem_name[] = {"ElemFp4", "ElemFp4T", "ElemFp4Out<1>", "ElemFp4Out<2>", "ElemI8", "ElemF16", "ElemBf16", "ElemBf16L"};
+    snprintf(out, (size_t)cap, "%s<%s>", tile_cfg_name(pl.cfg), elem_name[(int)pl.elem]);
+    return QT_OK;
+}
+
+int qt_gemm_tile_describe(int family, int variant, int64_t M, int64_t N, int64_t ldxp, int64_t ldwp, char* out, int cap) {
+    if (!out || cap < 2 || M <= 0 || N <= 0) return QT_ERR_INVALID_ARG;
+    out[0] = 0;
+    TileCfg cfg;
+    if (family == QT_GEMM_FAMILY_DENSE) {
+        if (variant == 0) {
+            cfg = select_gemm(M, N, ldxp, ldwp);
+        } else {
+            const int rc = gemm_variant_cfg(variant, gemm_pipe_ok(M, N, ldxp, ldwp), ldxp, ldwp, &cfg);
+            if (rc != QT_OK) return rc;
+        }
+    } else if (family == QT_GEMM_FAMILY_BF16_TAPS || family == QT_GEMM_FAMILY_I8_SPLITK) {
+        if (variant != 0) return QT_ERR_INVALID_ARG;
+        if (!gemm_pipe_ok(M, N, ldxp, ldwp)) return QT_ERR_UNSUPPORTED;
+        cfg = select_gemm_batched(M, N, family == QT_GEMM_FAMILY_BF16_TAPS);
+    } else {
+        return QT_ERR_INVALID_ARG;
+    }
+    snprintf(out, (size_t)cap, "%s", tile_cfg_name(cfg));
+    return QT_OK;
 }
 
 int qt_bits_to_nib(const uint32_t* sign_plane, const uint32_t* mask_plane, int64_t ldb,

@@ -1619,46 +1619,22 @@ template <class E> using ConvV128x64D = GemmCfg<E, 4, 2, 1, 1, 3, 0, 256, 2>;
 template <class E> using ConvVPP192Stamps = GemmCfg<E, 4, 2, 3, 3, 2, 5, 64, 2>;   // profiling builds only
 #endif
 
-// tile width (256 / 192 / 128 / 64) that wastes the fewest padded columns; ties go to the wider tile
-int pick_tile_n(int64_t N) {
-    int best = 256;
-    int64_t best_pad = (N + 255) / 256 * 256;
-    const int cands[3] = {192, 128, 64};
-    for (int c : cands) {
-        const int64_t pad = (N + c - 1) / c * c;
-        if (pad < best_pad) { best = c; best_pad = pad; }
-    }
-    return best;
-}
-
-// GEMM tile width: the padding-minimal width, narrowed while the launch would leave most of the 256 CUs
-// without a tile (a workgroup walks the whole K loop alone, so a 256x4096x9216 problem on 16 wide tiles
-// takes 50 us and on 64 narrow ones 24 us).
-int pick_tile_n_gemm(int64_t M, int64_t N) {
-    int tn = pick_tile_n(N);
-    const int64_t mt = (M + 255) / 256;
-    while (tn > 64 && mt * ((N + tn - 1) / tn) < 160) tn = tn == 256 ? 128 : 64;
-    return tn;
-}
-
-// 192-wide column tiles come with 256 or 384 rows.  The 384-row tile does 50 % more work per workgroup at a
-// better MFMA : fragment-read ratio; it wins unless it leaves CUs idle (fewer tiles than the 256 CUs) or adds a
-// partial round.  Cost model: rounds of 256 concurrent workgroups x rows per tile; ties go to 384.
-bool prefer_384_rows(int64_t M, int64_t N) {
-    const int64_t nt = (N + 191) / 192;
-    const int64_t c256 = (((M + 255) / 256) * nt + 255) / 256 * 256;
-    const int64_t c384 = (((M + 383) / 384) * nt + 255) / 256 * 384;
-    return c384 <= c256;
-}
-
-// Argument checks and geometry of an implicit-GEMM conv launch, shared by the entry points of mfma_gemm.hip and conv_taps.hip.
+// Argument checks and geometry of an implicit-GEMM conv launch, shared by the entry points of mfma_gemm.hip and conv_taps.hip, in
+// two parts: what can be said of the pointers (conv_check_pointers: the launch path only), and everything that follows from the
+// numbers (conv_geometry: the launch path and the describe entry points, which pass "present and aligned").  The geometry part
+// tests the pointer findings at the place in its sequence of checks where the pointers used to be tested.
 // (hy, hx): halo of the INPUT plane, [N][H + 2hy][W + 2hx][Cw] with a zero border: a conv whose padding fits in the halo runs as
-// the un-padded conv on the window that starts (hy - ph, hx - pw) into the plane (P is advanced accordingly).  Returns QT_OK, an
-// error code, or 1 = nothing to do.  elem: 0 = fp4 nibble planes, 1 = int8 code planes, 2 = bf16 (triple) planes, 3 = fp16 (pair) planes.
-static int conv_prepare(int elem, const uint32_t*& P, int64_t Nimg, int64_t H, int64_t W, int64_t Cw, int64_t kh, int64_t kw,
-                        int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw, const uint32_t* Wmat, int64_t ldwp,
-                        const float* Y, int64_t ldy, int64_t Cout, EpiArgs& epi, int64_t hy, int64_t hx, ConvArgs& cg, bool& valid,
-                        int64_t& M, int64_t& K, int64_t& kwords) {
+// the un-padded conv on the window that starts (hy - ph, hx - pw) into the plane (p_offset: words the caller advances P by).  Returns
+// QT_OK, an error code, or 1 = nothing to do.  elem: 0 = fp4 nibble planes, 1 = int8 code planes, 2 = bf16 (triple) planes, 3 = fp16 (pair) planes.
+struct ConvPtrs { bool present, aligned; };
+static ConvPtrs conv_check_pointers(const void* P, const void* Wmat, const void* Y) {
+    return {P && Wmat && Y, qt_aligned16(P) && qt_aligned16(Wmat)};
+}
+static int conv_geometry(int elem, int64_t Nimg, int64_t H, int64_t W, int64_t Cw, int64_t kh, int64_t kw, int64_t sh, int64_t sw,
+                         int64_t ph, int64_t pw, int64_t dh, int64_t dw, int64_t ldwp, int64_t ldy, int64_t Cout, EpiArgs& epi,
+                         int64_t hy, int64_t hx, ConvPtrs ptrs, ConvArgs& cg, bool& valid, int64_t& M, int64_t& K, int64_t& kwords,
+                         int64_t& p_offset) {
+    p_offset = 0;
     if (hy < 0 || hx < 0 || ((hy | hx) && (ph > hy || pw > hx))) return QT_ERR_INVALID_ARG;
     if (Nimg < 0 || H <= 0 || W <= 0 || Cw <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || dh <= 0 ||
         dw <= 0 || ph < 0 || pw < 0 || Cout < 0 || elem < 0 || elem > 3)
@@ -1667,10 +1643,10 @@ static int conv_prepare(int elem, const uint32_t*& P, int64_t Nimg, int64_t H, i
     if (Ho <= 0 || Wo <= 0) return QT_ERR_INVALID_ARG;
     M = Nimg * Ho * Wo;
     if (M == 0 || Cout == 0) return 1;
-    if (!P || !Wmat || !Y || ldy < (epi.mode == 2 ? ((Cout + 3) & ~3ll) : epi.mode == 5 ? ((2 * Cout + 15) & ~15ll) : epi.mode == 3 ? ((epi.d2s_cout ? epi.d2s_cout : Cout) + 31) / 32 * 4 : epi.alpha ? (Cout + 31) / 32 : Cout))
+    if (!ptrs.present || ldy < (epi.mode == 2 ? ((Cout + 3) & ~3ll) : epi.mode == 5 ? ((2 * Cout + 15) & ~15ll) : epi.mode == 3 ? ((epi.d2s_cout ? epi.d2s_cout : Cout) + 31) / 32 * 4 : epi.alpha ? (Cout + 31) / 32 : Cout))
         return QT_ERR_INVALID_ARG;
     kwords = kh * kw * Cw;                 // words per (virtual) im2col row
-    if ((Cw & 3) || (ldwp & 31) || ldwp < kwords || !qt_aligned16(P) || !qt_aligned16(Wmat)) return QT_ERR_ALIGNMENT;
+    if ((Cw & 3) || (ldwp & 31) || ldwp < kwords || !ptrs.aligned) return QT_ERR_ALIGNMENT;
     const int64_t Hp = H + 2 * hy, Wp = W + 2 * hx;
     if (M > INT32_MAX || kwords * 4 >= (1 << 20) || Cout * ldwp * 4 >= (1ll << 31) || Hp > 32767 || Wp > 32767 ||
         Hp * Wp * Cw * 4 >= (1ll << 31))   // per-image plane bytes: 32-bit tap offsets
@@ -1703,7 +1679,7 @@ static int conv_prepare(int elem, const uint32_t*& P, int64_t Nimg, int64_t H, i
         valid = Nimg * Hp * Wp * Cw * 4 < (1ll << 32) && kwords * 4 <= 32768;
         if (!valid) return QT_ERR_UNSUPPORTED;      // the caller strips the halo and uses the bounds-checked kernels
         cg.H = (int)Hp; cg.W = (int)Wp; cg.ph = cg.pw = 0;
-        P += ((hy - ph) * Wp + (hx - pw)) * Cw;
+        p_offset = ((hy - ph) * Wp + (hx - pw)) * Cw;
     }
     return QT_OK;
 }

@@ -1816,7 +1816,7 @@ def alpha_digits(alpha: torch.Tensor) -> Optional[AlphaDigits]:
 
 
 def _pick_tile_n(N: int) -> int:
-    """csrc/mfma_gemm_kernel.h pick_tile_n: the tile width (256 / 192 / 128 / 64) with the fewest padded columns."""
+    """csrc/tile_select.h pick_tile_n: the tile width (256 / 192 / 128 / 64) with the fewest padded columns."""
     best, best_pad = 256, (N + 255) // 256 * 256
     for c in (192, 128, 64):
         pad = (N + c - 1) // c * c
@@ -3072,10 +3072,8 @@ def wgrad_gemm_plan(nc: int, Cout: int, Cin: int, H: int, W: int, kh: int, kw: i
     Hp = H + 2 * ph
     M, taps = 3 * Cout, kh * kw
     ldc = _round_up(Cin, 4)
-    tn = 256
-    for c in (192, 128, 64):                                  # the GEMM's own tile-width rule (pick_tile_n)
-        if _round_up(Cin, c) < _round_up(Cin, tn):
-            tn = c
+    tn = _pick_tile_n(Cin)
+    # the batched GEMM's own row rule (csrc/tile_select.h select_gemm_batched)
     tm = 384 if (tn == 192 and _round_up(M, 384) <= _round_up(M, 256)) else 256
     tiles = (_round_up(M, tm) // tm) * (_round_up(Cin, tn) // tn)
     nslice = max(1, min(64, -(-WGRAD_WORKGROUPS // (tiles * taps))))
@@ -3688,15 +3686,48 @@ def packed_gemm(x, w, bias=None, out=None, impl: str = "valu", out_dtype=None) -
     raise NotImplementedError(impl)
 
 
-def nib_gemm_kernel_name(M: int, N: int, K: int) -> str:
-    """The kernel configuration nib_gemm's automatic dispatch takes for this shape (qt_nib_gemm_describe)."""
+def nib_gemm_kernel_name(M: int, N: int, K: int, ld: Optional[int] = None) -> str:
+    """The kernel configuration nib_gemm's automatic dispatch takes for this shape (qt_nib_gemm_describe); ``ld``: the row stride
+    of both planes in words where it is not the packers' default."""
     import ctypes
     buf = ctypes.create_string_buffer(128)
-    ld = packed_ld_nib(K)
+    ld = packed_ld_nib(K) if ld is None else int(ld)
     rc = _lib.load().qt_nib_gemm_describe(int(M), int(N), int(K), ld, ld, buf, 128)
     if rc != 0:
         raise _lib.QtStatusError(f"qt_nib_gemm_describe failed: {_lib.strerror(rc)}")
     return buf.value.decode()
+
+
+#: epilogue kinds of conv_kernel_name / conv_taps_kernel_name (include/qt_hip.h QT_EPI_*)
+EPI_PLAIN, EPI_BITS, EPI_NIB, EPI_CODES, EPI_HALO_BN, EPI_LEVELS, EPI_HALF_BF16, EPI_HALF_F16 = range(8)
+
+
+def _conv_describe(fn: str, elem, Nimg, H, W, Cw, kernel, stride, padding, dilation, ldwp, Cout, in_halo, epilogue, has_thr, d2s_cout,
+                   variant) -> str:
+    import ctypes
+    buf = ctypes.create_string_buffer(128)
+    geo = [int(v) for v in (Nimg, H, W, Cw, *kernel, *stride, *padding, *dilation, ldwp, Cout, *in_halo)]
+    rc = getattr(_lib.load(), fn)(int(elem), *geo, int(epilogue), int(bool(has_thr)), int(d2s_cout), int(variant), buf, 128)
+    if rc != 0:
+        raise _lib.QtStatusError(f"{fn} failed: {_lib.strerror(rc)}")
+    return buf.value.decode()
+
+
+def conv_kernel_name(elem: int, Nimg: int, H: int, W: int, Cw: int, kernel, stride, padding, dilation, ldwp: int, Cout: int,
+                     in_halo=(0, 0), epilogue: int = EPI_PLAIN, has_thr: bool = False, d2s_cout: int = 0, variant: int = 0) -> str:
+    """"<GemmCfg alias><element class>" of the implicit-GEMM kernel the conv entry point of this ``epilogue`` launches for these
+    numbers (qt_conv2d_implicit_describe: the selector the launch itself runs).  ``Cw`` / ``ldwp``: words per pixel of the input
+    plane / per weight row; ``variant``: tile form | CONV_* flags.  EPI_CODES names the implicit-GEMM kernel, which the small
+    3 x 3 layers only run under CONV_NO_DIRECT_CODES."""
+    return _conv_describe("qt_conv2d_implicit_describe", elem, Nimg, H, W, Cw, kernel, stride, padding, dilation, ldwp, Cout, in_halo,
+                          epilogue, has_thr, d2s_cout, variant)
+
+
+def conv_taps_kernel_name(elem: int, Nimg: int, H: int, W: int, Cw: int, kernel, stride, padding, dilation, ldwp: int, Cout: int,
+                          epilogue: int = EPI_PLAIN) -> str:
+    """The same for the per-tap scaled convs (qt_conv2d_implicit_taps_describe; EPI_PLAIN / EPI_BITS / EPI_NIB)."""
+    return _conv_describe("qt_conv2d_implicit_taps_describe", elem, Nimg, H, W, Cw, kernel, stride, padding, dilation, ldwp, Cout,
+                          (0, 0), epilogue, False, 0, 0)
 
 
 def packed_gemm_algorithmic_bytes(M: int, N: int, K: int, impl: str = "valu", planes_w: int = 1,

@@ -287,7 +287,7 @@ GRAD_EXPS = (-40, 30)
 VARIANTS = ("plain", "mid", "lead", "lone")     # no zero / an all-zero tap in the middle / a leading one / a lone zero weight
 
 # forward, exact: (id, B, Cin, Cout, H, k, stride, padding, dilation, variant, route of the float result, route of the threshold
-# epilogues or None); routes as dispatch_taps (csrc/conv_taps.hip) selects them, asserted from the profiler's kernel names
+# epilogues or None); routes as select_conv_taps (csrc/tile_select.h) selects them, asserted from the profiler's kernel names
 FWD_CASES = [
     ("c256/valid", 8, 64, 256, 12, 3, 1, 0, 1, "mid", "ConvVPP256", "ConvVPP256"),
     ("c256/padded", 8, 64, 256, 12, 3, 1, 1, 1, "lead", "Conv128x128", "ConvPP256"),

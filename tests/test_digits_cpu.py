@@ -20,8 +20,18 @@ def test_splitk_plan_divides_the_padded_row_into_whole_stages(M, N, ld):
 
 
 def test_pick_tile_n_follows_the_kernel_header():
-    # csrc/mfma_gemm_kernel.h pick_tile_n: fewest padded columns, ties to the wider tile
+    # csrc/tile_select.h pick_tile_n: fewest padded columns, ties to the wider tile
     assert [ops._pick_tile_n(n) for n in (10, 64, 65, 128, 192, 256, 576, 1000, 1152, 4096)] == [64, 64, 128, 128, 192, 256, 192, 256, 192, 256]
+    # ... and the library's own copy of the rule: at M = 65536 (256 row tiles: pick_tile_n_gemm never narrows, and no skinny rung)
+    # the GEMM selector's tile is "<rows>x<pick_tile_n(N)>"
+    import re
+    from pytorch_quantize_impls_amd import _lib
+    if not _lib.is_built():
+        import __graft_entry__ as g
+        g.build()
+    for n in range(1, 4097):
+        tile = re.search(r"ElemFp4, (\d+)x(\d+),", ops.nib_gemm_kernel_name(65536, n, 256))
+        assert tile and int(tile.group(2)) == ops._pick_tile_n(n), (n, tile and tile.group(0))
 
 
 @pytest.mark.parametrize("scale", [1e-3, 0.04, 1.0, 300.0])

@@ -21,6 +21,7 @@ import torch
 import torch.nn.functional as F
 
 import _exact as X
+import _routes as R
 
 pytestmark = pytest.mark.gpu
 
@@ -29,23 +30,6 @@ from pytorch_quantize_impls_amd import ops  # noqa: E402
 BATCH = 256
 BUDGET = 1 << 30            # bytes of float64 temporaries per reference chunk
 
-# GemmCfg<E, WM, WN, TMW, TNW, PIPE, ABL, SB, CONV, OCC> of the un-padded conv configurations (csrc/mfma_gemm_kernel.h)
-_CFG = {
-    (2, 4, 4, 2, 1, 0, 128, 2, 1): "ConvV256",
-    (2, 4, 4, 1, 1, 0, 128, 2, 1): "ConvV128",
-    (4, 2, 2, 1, 1, 0, 128, 2, 1): "ConvV64",
-    (4, 2, 2, 3, 1, 0, 128, 2, 1): "ConvV192",
-    (2, 4, 4, 2, 2, 0, 64, 2, 1): "ConvVPP256",
-    (4, 2, 2, 1, 1, 0, 64, 2, 3): "ConvV64x2",
-    (2, 4, 4, 1, 1, 0, 64, 2, 2): "ConvV128x2",
-    (4, 2, 3, 3, 2, 0, 64, 2, 1): "ConvVPP192",
-    (4, 2, 2, 3, 2, 0, 64, 2, 1): "ConvVPP256x192",
-    (2, 2, 1, 1, 1, 0, 512, 2, 1): "ConvVSkinny",
-    (2, 4, 2, 1, 1, 0, 128, 2, 1): "ConvV128x128",
-    (4, 2, 1, 1, 1, 0, 256, 2, 1): "ConvV128x64",
-    (2, 4, 2, 1, 4, 0, 128, 2, 1): "ConvV128x128D",
-    (4, 2, 1, 1, 3, 0, 256, 2, 1): "ConvV128x64D",
-}
 # the configurations with a sign-bit (ElemFp4T) instance: mfma_gemm.hip launches them through launch_cfg_t
 SWAPT = {"ConvV128x128D", "ConvV128x2", "ConvVPP192", "ConvVPP256", "ConvVPP256x192"}
 COVERED = {}                # route label -> case ids that compared it with the exact reference
@@ -71,13 +55,9 @@ def _free_memory(request):
 
 def routes(names):
     """Profiler kernel names -> labels 'ConvVPP256<ElemFp4T>', 'direct3x3<4,2,2,2,lean>', ..."""
-    out = set()
+    names = [k.replace("(anonymous namespace)::", "") for k in names]
+    out = R.mfma_routes(names, elem="ElemFp4T?")
     for k in names:
-        k = k.replace("(anonymous namespace)::", "")
-        m = re.search(r"GemmCfg<(ElemFp4T?), ([\d, ]+)>", k)
-        if m:
-            t = tuple(int(v) for v in m.group(2).split(","))
-            out.add(f"{_CFG.get(t, t)}<{m.group(1)}>")
         m = re.search(r"direct3x3_kernel<(\d+), (\d+), (\d+), (\d+), 0(?:, (true|false))?>", k)
         if m:
             out.add(f"direct3x3<{m.group(1)},{m.group(2)},{m.group(3)},{m.group(4)},{'lean' if m.group(5) == 'true' else 'general'}>")
@@ -87,8 +67,10 @@ def routes(names):
     return out
 
 
-def traced(fn, expect, case):
-    """Run fn under torch.profiler and assert that the kernel ``expect`` (a label of routes()) ran."""
+def traced(fn, expect, case, described=None):
+    """Run fn under torch.profiler and assert that the kernel ``expect`` (a label of routes()) ran — and, where the case has a
+    describe entry point (``described``: its answer), that it names that kernel."""
+    R.assert_described(described, expect, case)
     from torch.profiler import ProfilerActivity, profile
     with profile(activities=[ProfilerActivity.CUDA]) as prof:
         out = fn()
@@ -193,9 +175,13 @@ def run_implicit(dev, case, N, Cin, Cout, H, k, kind, cfg, pool=None, forms=("sw
         t = None if form == "float" else thr
         elem = "ElemFp4T" if (form == "swapt" and cfg in SWAPT) else "ElemFp4"
         label = f"{cfg}<{elem}>"
-        with ops.scope(CONV_FLAGS=ops.CONV_COMPARE_THRESHOLDS if form == "compare" else 0):
-            bits = traced(lambda: ops.conv2d_nib(*args, epi=(alpha, beta, t)), label, f"{case} {form} bits")
-            nib = traced(lambda: ops.conv2d_nib(*args, epi=ops.NibEpilogue(alpha, beta, nib_halo, thr=t)), label, f"{case} {form} nib")
+        flags = ops.CONV_COMPARE_THRESHOLDS if form == "compare" else 0
+        named = [ops.conv_kernel_name(0, N, H + 2 * pad, W + 2 * pad, px.ld, (k, k), (1, 1), (0, 0), (1, 1), wp.ld, Cout, epilogue=e,
+                                      has_thr=t is not None, variant=flags) for e in (ops.EPI_BITS, ops.EPI_NIB)]
+        with ops.scope(CONV_FLAGS=flags):
+            bits = traced(lambda: ops.conv2d_nib(*args, epi=(alpha, beta, t)), label, f"{case} {form} bits", named[0])
+            nib = traced(lambda: ops.conv2d_nib(*args, epi=ops.NibEpilogue(alpha, beta, nib_halo, thr=t)), label, f"{case} {form} nib",
+                         named[1])
         outs += [Out(f"{form}/bits", bits, H, W), Out(f"{form}/nib", nib, H, W, halo=nib_halo)]
         if pool:
             Hp = (H - pool[0]) // pool[1] + 1
@@ -551,7 +537,7 @@ def test_c3_fused_alexnet_layerwise_at_batch_256(dev):
 
 # ---- coverage: every threshold-epilogue configuration ran against the exact reference ---------------------------------------
 
-# configurations the dispatcher (mfma_gemm.hip conv_implicit_impl, default switches, fp4 threshold epilogue on an un-padded or
+# configurations the dispatcher (csrc/tile_select.h select_conv, default switches, fp4 threshold epilogue on an un-padded or
 # physically padded plane) can select, and the direct kernel's instances
 EXPECTED = sorted(
     [f"{c}<ElemFp4>" for c in ("ConvVSkinny", "ConvV128x128D", "ConvV128x64D", "ConvV128x2", "ConvVPP192", "ConvVPP256",

@@ -49,6 +49,7 @@ from pytorch_quantize_impls_amd.functions import _fused, log_lin_connect  # noqa
 from pytorch_quantize_impls_amd.layers import FusedBnLogLinQuant, LinearQuant, QuantConv2d  # noqa: E402
 from pytorch_quantize_impls_amd.layers import fused as fused_mod  # noqa: E402
 from test_gpu_grad_b256 import kernel_label, profiled  # noqa: E402,F401
+import _routes as R  # noqa: E402
 from test_gpu_loglin_train import _VGGLinLog, _our_kernel_names  # noqa: E402
 
 BATCH = 256
@@ -83,24 +84,11 @@ def _record(kernels, case):
 
 # ---- (a) the level epilogue, tile configuration by tile configuration --------------------------------------------------------------
 
-# GemmCfg<E, WM, WN, TMW, TNW, PIPE, ABL, SB, CONV, OCC> of each configuration (csrc/mfma_gemm_kernel.h); CONV 2 = the un-padded /
-# halo-plane kernels, 1 = the bounds-checked ones.  Tile = 32 WM TMW rows x 32 WN TNW columns.
-CFG = {
-    "ConvVSkinny": "2, 2, 1, 1, 1, 0, 512, 2, 1", "ConvV128x64D": "4, 2, 1, 1, 3, 0, 256, 2, 1",
-    "ConvV128x128D": "2, 4, 2, 1, 4, 0, 128, 2, 1", "ConvV128x2": "2, 4, 4, 1, 1, 0, 64, 2, 2",
-    "ConvV64x2": "4, 2, 2, 1, 1, 0, 64, 2, 3", "ConvVPP256": "2, 4, 4, 2, 2, 0, 64, 2, 1",
-    "ConvVPP256x192": "4, 2, 2, 3, 2, 0, 64, 2, 1", "ConvVPP192": "4, 2, 3, 3, 2, 0, 64, 2, 1",
-    "ConvV192": "4, 2, 2, 3, 1, 0, 128, 2, 1", "ConvV128": "2, 4, 4, 1, 1, 0, 128, 2, 1", "ConvV64": "4, 2, 2, 1, 1, 0, 128, 2, 1",
-    "ConvSkinny": "2, 2, 1, 1, 1, 0, 512, 1, 1", "Conv128x128": "2, 4, 2, 1, 1, 0, 128, 1, 1",
-    "ConvPP192": "4, 2, 3, 3, 2, 0, 64, 1, 1", "ConvPP256": "2, 4, 4, 2, 2, 0, 64, 1, 1",
-    "ConvPP256x192": "4, 2, 2, 3, 2, 0, 64, 1, 1", "Conv256": "2, 4, 4, 2, 1, 0, 128, 1, 1",
-    "Conv192": "4, 2, 2, 3, 1, 0, 128, 1, 1", "Conv128": "2, 4, 4, 1, 1, 0, 128, 1, 1", "Conv64": "4, 2, 2, 1, 1, 0, 128, 1, 1",
-}
-
-
-def _tile(cfg):
-    wm, wn, tmw, tnw = (int(v) for v in CFG[cfg].split(", ")[:4])
-    return 32 * wm * tmw, 32 * wn * tnw
+# the configurations the level epilogue is walked over (tuple <-> name: tests/_routes.py)
+CFG = {c: R.CFG_ARGS[c] for c in (
+    "ConvVSkinny", "ConvV128x64D", "ConvV128x128D", "ConvV128x2", "ConvV64x2", "ConvVPP256", "ConvVPP256x192", "ConvVPP192", "ConvV192",
+    "ConvV128", "ConvV64", "ConvSkinny", "Conv128x128", "ConvPP192", "ConvPP256", "ConvPP256x192", "Conv256", "Conv192", "Conv128", "Conv64")}
+_tile = R.tile_of
 
 
 def _instance(cfg):
@@ -244,6 +232,8 @@ def test_level_epilogue_on_its_tile_configuration(dev, case):
                       stats.data_ptr(), int(relu), *q, plane.data_ptr(), I(2 * ld), I(cout), I(out_halo), I(out_halo),
                       ops._stream(dev))
 
+    R.assert_described(ops.conv_kernel_name(2, N, H, W, pix.shape[1] // 2, (3, 3), (s, s), (p, p), (1, 1), wt.ld_words, cout, in_halo=ih,
+                                            epilogue=ops.EPI_LEVELS), f"{cfg}<ElemBf16L>", cid)
     _, kernels, calls, lib = profiled(launch)
     assert not lib and calls == {"qt_conv2d_implicit_levels": 1}, (calls, lib)
     ours = sorted(k for k in kernels if k.startswith("mfma_gemm_kernel"))

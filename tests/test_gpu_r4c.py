@@ -455,7 +455,7 @@ def test_pool_affine_sign_pack_nib_rows_equal_the_separate_expansion(dev, rows, 
     assert ops.to_impl(both, "mfma") is both.nib
 
 
-# ---- per-tap scaled conv on the un-scaled conv's wide tiles (end of round 4: csrc/conv_taps.hip dispatch_taps) -----------------------
+# ---- per-tap scaled conv on the un-scaled conv's wide tiles (end of round 4: csrc/tile_select.h select_conv_taps) -----------------------
 
 @pytest.mark.parametrize("Cin,Cout,H,k,p,B,tile", [
     (64, 256, 30, 3, 1, 64, "256x256"),        # M = 57 600: 225 tiles -> ConvPP256 / ConvVPP256

@@ -3,7 +3,7 @@ independent float64 reference of tests/_xnor_exact.py.
 
   (a) exact, every bit: +-1 activations, weights +-2^{e_t} (power-of-two tap alphas over the widest span the exactness proof
       allows, ramp up then drop; an all-zero tap in the middle, a leading one, a lone zero weight), ops.conv2d_nib_taps on packed
-      planes with bias == the float64 reference converted to fp32, for every configuration dispatch_taps can select, odd
+      planes with bias == the float64 reference converted to fp32, for every configuration select_conv_taps (csrc/tile_select.h) can select, odd
       k-steps per tap (Cin = 192, 576; 3 x 3 and 5 x 5), 1 x 1, stride 2, anisotropic padding, dilation 2, ragged M and Cout,
       and bench_models.alexnet_xnor's conv2 .. conv5 at batch 256;
   (b) the threshold-bit and nibble-halo-plane epilogues on the same inputs, every word against tests/_exact.predicate on the
@@ -17,7 +17,7 @@ independent float64 reference of tests/_xnor_exact.py.
   (e) Gaussian weights (nearly equal alphas; a second set with per-tap scales over six decades and one tap at 2^-60 of the
       others) through (a), (c), (d), per output ELEMENT:  |got - ref64| <= (S + 2 T + 16) 2^-23 B  (S MFMA k-steps along K, T
       taps, B the element's magnitude bound; derivation at _xnor_exact.horner_bound);
-  (f) closure: every Config<Elem> dispatch_taps can return was compared above, and every kernel instance with `Taps` in its name
+  (f) closure: every Config<Elem> select_conv_taps can return was compared above, and every kernel instance with `Taps` in its name
       that a batch-256 training step of bench_models.alexnet_xnor, its eval-mode deferred forward and an
       XNORConv2d(quant_input=True) training step launch is among them.
 
@@ -28,7 +28,6 @@ Measured on an MI355X (whole module, 118 cases): 9 s, peak device memory 7.75 Gi
 the exact cases with zero mismatching elements / words; worst err / bound of the Gaussian cases 0.115 (forward 1 x 1, nearly
 equal alphas: S = 1, so the bound is at its tightest), at most 0.038 elsewhere — MEASURED_RATIOS below, printed again by the
 closure test."""
-import re
 import time
 
 import pytest
@@ -36,6 +35,7 @@ import torch
 
 import _exact as X
 import _grad_exact as G
+import _routes as R
 import _xnor_exact as XE
 
 pytestmark = pytest.mark.gpu
@@ -44,32 +44,6 @@ from pytorch_quantize_impls_amd import ops  # noqa: E402
 
 F64, F32 = torch.float64, torch.float32
 
-# GemmCfg<E, WM, WN, TMW, TNW, PIPE, ABL, SB, CONV, OCC> of the conv configurations (csrc/mfma_gemm_kernel.h): CONV = 2 on
-# un-padded planes (ConvV*), 1 with bounds-checked taps (Conv*)
-_CFG = {
-    (2, 4, 4, 2, 1, 0, 128, 2, 1): "ConvV256",
-    (2, 4, 4, 1, 1, 0, 128, 2, 1): "ConvV128",
-    (4, 2, 2, 1, 1, 0, 128, 2, 1): "ConvV64",
-    (4, 2, 2, 3, 1, 0, 128, 2, 1): "ConvV192",
-    (2, 4, 4, 2, 2, 0, 64, 2, 1): "ConvVPP256",
-    (4, 2, 3, 3, 2, 0, 64, 2, 1): "ConvVPP192",
-    (2, 4, 4, 1, 2, 0, 64, 2, 1): "ConvVPP128",
-    (4, 2, 2, 3, 2, 0, 64, 2, 1): "ConvVPP256x192",
-    (2, 2, 1, 1, 1, 0, 512, 2, 1): "ConvVSkinny",
-    (2, 4, 2, 1, 1, 0, 128, 2, 1): "ConvV128x128",
-    (4, 2, 1, 1, 1, 0, 256, 2, 1): "ConvV128x64",
-    (2, 4, 4, 2, 2, 0, 64, 1, 1): "ConvPP256",
-    (4, 2, 3, 3, 2, 0, 64, 1, 1): "ConvPP192",
-    (2, 4, 4, 1, 2, 0, 64, 1, 1): "ConvPP128",
-    (4, 2, 2, 3, 2, 0, 64, 1, 1): "ConvPP256x192",
-    (4, 2, 2, 1, 2, 0, 64, 1, 1): "ConvPP64",
-    (2, 4, 4, 2, 1, 0, 128, 1, 1): "Conv256",
-    (2, 4, 4, 1, 1, 0, 128, 1, 1): "Conv128",
-    (4, 2, 2, 1, 1, 0, 128, 1, 1): "Conv64",
-    (4, 2, 2, 3, 1, 0, 128, 1, 1): "Conv192",
-    (2, 4, 2, 1, 1, 0, 128, 1, 1): "Conv128x128",
-    (2, 2, 1, 1, 1, 0, 512, 1, 1): "ConvSkinny",
-}
 ROWS_ROUTE = "Conv128<ElemFp4TapsRows>"
 COVERED = {}                # "Config<Elem>/form" -> case ids that compared it
 RATIOS = {}                 # Gaussian case -> worst err / bound
@@ -105,13 +79,7 @@ def _free_memory(request):
 
 def routes(names):
     """Profiler kernel names -> labels 'ConvVPP256<ElemFp4Taps>', ..."""
-    out = set()
-    for k in names:
-        m = re.search(r"GemmCfg<(Elem\w+), ([\d, ]+)>", k.replace("(anonymous namespace)::", ""))
-        if m:
-            t = tuple(int(v) for v in m.group(2).split(","))
-            out.add(f"{_CFG.get(t, t)}<{m.group(1)}>")
-    return out
+    return R.mfma_routes(names)
 
 
 def profiled(fn):
@@ -122,8 +90,10 @@ def profiled(fn):
     return out, routes(e.key for e in prof.key_averages())
 
 
-def traced(fn, expect, case):
-    """Run fn under torch.profiler and assert that the kernel ``expect`` (a label of routes()) ran."""
+def traced(fn, expect, case, described=None):
+    """Run fn under torch.profiler and assert that the kernel ``expect`` (a label of routes()) ran — and, where the case has a
+    describe entry point (``described``: its answer), that it names that kernel."""
+    R.assert_described(described, expect, case)
     out, seen = profiled(fn)
     assert expect in seen, (case, expect, sorted(map(str, seen)))
     return out
@@ -180,6 +150,11 @@ class Fwd:
     def run(self, epi=None):
         return ops.conv2d_nib_taps(*self.args, epi=epi)
 
+    def named(self, epilogue=ops.EPI_PLAIN):
+        """The kernel the describe entry point names for run() with this epilogue."""
+        return ops.conv_taps_kernel_name(0, self.B, self.H, self.H, self.px.ld, ops._pairs(self.k), ops._pairs(self.s), ops._pairs(self.p), ops._pairs(self.d),
+                                         self.ws.ld, self.Cout, epilogue)
+
     def nhwc(self, t):
         return t.permute(0, 2, 3, 1).reshape(self.B * self.Ho * self.Wo, self.Cout)
 
@@ -232,7 +207,7 @@ def test_forward_is_bit_exact_on_designed_operands(dev, case):
     y64 = XE.tap_sums64(f.x, torch.sign(f.w), f.s, f.p, f.d, alpha=f.alpha64)
     want = XE.to_f32_exact(y64 + f.bias.to(F64).view(1, -1, 1, 1), f.name)
     label = f"{f.float_route}<ElemFp4Taps>"
-    y = traced(f.run, label, f.name)
+    y = traced(f.run, label, f.name, f.named())
     msg = XE.value_report(y.view(f.B, f.Ho, f.Wo, f.Cout).permute(0, 3, 1, 2), want, what=f"{f.name} fp32 result")
     assert not msg, msg
     record(label, "float", f.name)
@@ -246,11 +221,11 @@ def test_forward_is_bit_exact_on_designed_operands(dev, case):
     frac = float(bit[..., 11:].float().mean())
     assert 0.2 < frac < 0.8, (f.name, frac)                                  # real thresholds, not all-0 / all-1 planes
     label = f"{f.thr_route}<ElemFp4Taps>"
-    bits = traced(lambda: f.run(epi=(alpha, beta)), label, f"{f.name} bits")
+    bits = traced(lambda: f.run(epi=(alpha, beta)), label, f"{f.name} bits", f.named(ops.EPI_BITS))
     _check_bits(bits.sign, f.Cout, bit, ynhwc, v, f"{f.name} bits")
     record(label, "bits", f.name)
     halo = (2, 1) if f.name == "aniso" else (1, 1)
-    nib = traced(lambda: f.run(epi=ops.NibEpilogue(alpha, beta, halo)), label, f"{f.name} nib")
+    nib = traced(lambda: f.run(epi=ops.NibEpilogue(alpha, beta, halo)), label, f"{f.name} nib", f.named(ops.EPI_NIB))
     _check_nib(nib.words, f, halo, bit, ynhwc, v, f"{f.name} nib")
     record(label, "nib", f.name)
 
@@ -394,7 +369,7 @@ def test_forward_gaussian_within_the_per_element_bound(dev, name, kind):
     f = Fwd(dev, case, weights=_weights_kw(kind, T, last=name in ("odd9/valid", "stride2")))
     ref, B = XE.xnor_conv64(f.x, f.w, f.bias, f.s, f.p, f.d)
     label = f"{f.float_route}<ElemFp4Taps>"
-    y = traced(f.run, label, f"gauss {name}")
+    y = traced(f.run, label, f"gauss {name}", f.named())
     y = y.view(f.B, f.Ho, f.Wo, f.Cout).permute(0, 3, 1, 2)
     assert _ratio(f"fwd {name} {kind}", y, ref, B, f.ksteps, T) <= 1.0
 
@@ -423,7 +398,7 @@ def test_grad_input_gaussian_within_the_per_element_bound(dev, name, kind):
 
 # ---- (f) closure ----------------------------------------------------------------------------------------------------------------
 
-# what dispatch_taps (csrc/conv_taps.hip) can return.  Un-padded planes (`valid`): the three small-M tiles, then by column tile
+# what select_conv_taps (csrc/tile_select.h) can return.  Un-padded planes (`valid`): the three small-M tiles, then by column tile
 # width; every one of them carries the float and both threshold epilogues.  Bounds-checked taps: the float result of a grid
 # under 200 tiles takes ConvSkinny / Conv128x128 (`!epi.alpha && epi.mode == 0`), everything else the ping-pong tiles / Conv64.
 _VALID = ("ConvV128x128", "ConvV128x64", "ConvVSkinny", "ConvVPP256", "ConvVPP192", "ConvVPP256x192", "ConvVPP128", "ConvV64")
