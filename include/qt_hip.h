@@ -1151,6 +1151,22 @@ int qt_nib_gemm_variant(int variant, const uint32_t* Xn, int64_t ldxp, const uin
  *                       g + momentum buf : buf; p -= lr g.  momentum == 0: no state is read (nesterov must be 0).
  *   qt_optim_adam_f32 : torch.optim.Adam (L2 weight decay, no amsgrad): g += weight_decay p; m = beta1 m + (1 - beta1) g;
  *                       v = beta2 v + (1 - beta2) g g; p -= c0 m / (sqrt(v) / c1 + eps).  One rounding per operation.
+ *
+ * The `_dev` entries are the same updates with the per-step scalars read from DEVICE memory when the kernel runs, not
+ * from the argument block when it is enqueued: a launch captured in a hipGraph then follows the values the caller
+ * writes there before each replay (utils.GraphedTrainStep with an optimiser).  Same arithmetic, operation for
+ * operation: for equal scalars they store the bits of the entries above.
+ *   qt_optim_sgd_dev_f32  : `lr` points to one float.  flags bit 0 keeps its meaning.
+ *   qt_optim_adam_dev_f32 : `coef` points to n pairs, coef[2 i] = c0 and coef[2 i + 1] = c1 of TABLE entry i (empty
+ *                           tensors keep their pair); the descriptors' c0 / c1 are ignored.
+ * `lr` / `coef` are validated with the table, before anything is enqueued: null with n > 0 is QT_ERR_INVALID_ARG,
+ * not 4-byte aligned is QT_ERR_ALIGNMENT; n == 0 is QT_OK whatever they are.  They must stay valid, and hold the
+ * step's values, until the launch (or every replay of it) has run.
+ *   qt_optim_scalars_f32  : writes n HOST floats `values` to DEVICE memory `dst`, ordered on `stream` like a kernel: the
+ *                           values travel in the launch's argument block (copied when the call is made, so `values` may
+ *                           be reused at once; 960 floats per launch), not through a host-to-device copy.  How the
+ *                           caller of a replayed `_dev` launch sets the next step's scalars without a synchronise.
+ *                           Null dst / values with n > 0, n < 0: QT_ERR_INVALID_ARG; dst not 4-byte aligned: QT_ERR_ALIGNMENT.
  * ---------------------------------------------------------------------------------------- */
 typedef struct qt_optim_tensor {
     float* p;
@@ -1170,6 +1186,11 @@ int qt_optim_sgd_f32(const qt_optim_tensor* table, int64_t n, float lr, float mo
                      qt_stream_t stream);
 int qt_optim_adam_f32(const qt_optim_tensor* table, int64_t n, float beta1, float one_minus_beta1, float beta2,
                       float one_minus_beta2, float eps, float weight_decay, qt_stream_t stream);
+int qt_optim_scalars_f32(float* dst, const float* values, int64_t n, qt_stream_t stream);
+int qt_optim_sgd_dev_f32(const qt_optim_tensor* table, int64_t n, const float* lr, float momentum, float weight_decay,
+                         int nesterov, qt_stream_t stream);
+int qt_optim_adam_dev_f32(const qt_optim_tensor* table, int64_t n, const float* coef, float beta1, float one_minus_beta1,
+                          float beta2, float one_minus_beta2, float eps, float weight_decay, qt_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -152,6 +152,26 @@ def pack_weight(weight_2d: torch.Tensor, kind: str, impl: str = "valu"):
 # Activations that carry a tag from their quantiser (BinaryConnect, nnDorefaQuant: packed.py) never get here for the
 # +-1 question.
 DETECT_MODE = "verify"
+_plane_capture_tls = threading.local()
+
+
+@contextlib.contextmanager
+def plane_capture_scope(words):
+    """Inside: a training forward that runs under stream capture may consume these weight-plane buffers (``words`` tensors).  Set by
+    the capture that also captures the update rewriting them (utils/optim.py: ``capturing``); thread-local, restored on exit."""
+    prev = getattr(_plane_capture_tls, "ids", None)
+    _plane_capture_tls.ids = frozenset(id(w) for w in words)
+    try:
+        yield
+    finally:
+        _plane_capture_tls.ids = prev
+
+
+def plane_capture_allows(words) -> bool:
+    ids = getattr(_plane_capture_tls, "ids", None)
+    return ids is not None and id(words) in ids
+
+
 _detect_tls = threading.local()
 
 

@@ -65,7 +65,9 @@ class _SignLinear(EvalSwapMixin, torch.nn.Linear, QLayer):
         still describes the weight — same version counter and storage — and this call would pack the weight for the matrix-core
         GEMM; else None.  Writes through ``weight.data`` do not bump the version counter (the hazard documented for the eval
         cache: ``reset_quant_cache()`` after one); the layer's own ``clamp()`` through ``.data`` cannot change a sign or ternary
-        code and the fused step has already applied it."""
+        code and the fused step has already applied it.  A forward that is being CAPTURED bakes the buffer's address into the graph:
+        it takes the plane only inside the capture that also captures the update rewriting that buffer
+        (``_fused.plane_capture_scope``, utils/optim.py:capturing), never otherwise."""
         w = self.weight
         rec = getattr(w, "_qt_train_planes", None)
         if rec is None or not self.deterministic:
@@ -75,7 +77,7 @@ class _SignLinear(EvalSwapMixin, torch.nn.Linear, QLayer):
         K, N = input.shape[-1], w.shape[0]
         if _fused.ops.select_gemm_impl(_fused._cfg("GEMM_IMPL"), input.numel() // max(K, 1), N, K) != "mfma":
             return None
-        if torch.cuda.is_current_stream_capturing():
+        if torch.cuda.is_current_stream_capturing() and not _fused.plane_capture_allows(rec["mfma"].words):
             return None
         return rec["mfma"]
 

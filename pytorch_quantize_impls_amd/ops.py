@@ -3833,12 +3833,95 @@ def optim_step_adam(params, grads, exp_avgs, exp_avg_sqs, steps, *, lr: float, b
     tab, dev = _optim_table(params, grads, exp_avgs, exp_avg_sqs, clamps, planes)
     if len(steps) != len(params):
         raise ValueError("optim_step: the tensor lists differ in length")
-    corr = {}
-    for i, t in enumerate(steps):
-        c = corr.get(t)
-        if c is None:
-            c = corr[t] = (lr / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5)
+    for i, c in enumerate(adam_coefficients(steps, lr, (b1, b2))):
         tab[i].c0, tab[i].c1 = c
     with _on(dev):
         _lib.call("qt_optim_adam_f32", _ct.addressof(tab), len(params), b1, 1.0 - b1, b2, 1.0 - b2, float(eps),
                   float(weight_decay), _stream(dev))
+
+
+def adam_coefficients(steps, lr: float, betas=(0.9, 0.999)):
+    """[(c0, c1)] per entry of ``steps`` (step counts INCLUDING the step to take): c0 = lr / (1 - beta1^t), c1 = sqrt(1 - beta2^t),
+    in double precision.  The one expression both forms of the Adam update take their bias corrections from: ``optim_step_adam``
+    writes them into its descriptors, a captured step (``optim_step_adam_dev``) reads them from device memory.  Pure."""
+    b1, b2 = float(betas[0]), float(betas[1])
+    corr, out = {}, []
+    for t in steps:
+        c = corr.get(t)
+        if c is None:
+            c = corr[t] = (lr / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5)
+        out.append(c)
+    return out
+
+
+def _optim_scalars_check(t, dev, numel: int, name: str) -> None:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise TypeError(f"{name}: the per-step scalars of a `_dev` training update live in HIP device memory "
+                        f"(got {type(t).__name__}{'' if not isinstance(t, torch.Tensor) else f' on {t.device}'})")
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel or t.device != dev:
+        raise ValueError(f"{name}: expected {numel} contiguous fp32 element(s) on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+
+
+def optim_write_scalars(dst: torch.Tensor, values) -> None:
+    """``dst[:len(values)] = values`` (fp32 device tensor, Python floats) as a kernel launch on the current stream whose argument
+    block carries the values (qt_optim_scalars_f32): ordered like any launch, no synchronise, and no host buffer that has to
+    outlive the call — the runtime copies the argument block when the launch is enqueued.  Each value is rounded to fp32 as a
+    by-value ``float`` argument is."""
+    n = len(values)
+    if not isinstance(dst, torch.Tensor) or not dst.is_cuda:
+        raise TypeError("optim_write_scalars: dst is a tensor in HIP device memory")
+    if dst.dtype != torch.float32 or not dst.is_contiguous():
+        raise ValueError(f"optim_write_scalars: dst is contiguous fp32, got {dst.dtype}, contiguous={dst.is_contiguous()}")
+    if n > dst.numel():
+        raise ValueError(f"optim_write_scalars: {n} values for {dst.numel()} elements")
+    if n == 0:
+        return
+    host = (_ct.c_float * n)(*values)
+    with _on(dst.device):
+        _lib.call("qt_optim_scalars_f32", _p(dst), _ct.addressof(host), n, _stream(dst.device))
+
+
+def optim_step_sgd_dev(params, grads, momentum_buffers, lr_dev: torch.Tensor, *, momentum: float = 0.0, weight_decay: float = 0.0,
+                       nesterov: bool = False, clamps=None, planes=None) -> None:
+    """``optim_step_sgd`` with the learning rate read from ``lr_dev`` (one fp32 element on the parameters' device) when the kernel
+    RUNS (qt_optim_sgd_dev_f32): the form a hipGraph can capture.  No first-step flag: the momentum buffers exist and a zeroed
+    buffer makes ``mu * 0 + g`` the first step's value."""
+    if not params:
+        return
+    use_mom = momentum != 0
+    if use_mom and momentum_buffers is None:
+        raise ValueError("optim_step_sgd_dev: momentum needs the momentum buffers")
+    tab, dev = _optim_table(params, grads, momentum_buffers if use_mom else None, None, clamps, planes)
+    _optim_scalars_check(lr_dev, dev, 1, "lr_dev")
+    with _on(dev):
+        _lib.call("qt_optim_sgd_dev_f32", _ct.addressof(tab), len(params), _p(lr_dev), float(momentum), float(weight_decay),
+                  int(bool(nesterov)), _stream(dev))
+
+
+def optim_step_adam_dev(params, grads, exp_avgs, exp_avg_sqs, coef_dev: torch.Tensor, *, betas=(0.9, 0.999), eps: float = 1e-8,
+                        weight_decay: float = 0.0, clamps=None, planes=None) -> None:
+    """``optim_step_adam`` with the bias corrections read from ``coef_dev`` (``2 * len(params)`` fp32 elements on the parameters'
+    device: ``adam_coefficients`` of tensor i at [2 i], [2 i + 1]) when the kernel RUNS (qt_optim_adam_dev_f32)."""
+    if not params:
+        return
+    b1, b2 = float(betas[0]), float(betas[1])
+    tab, dev = _optim_table(params, grads, exp_avgs, exp_avg_sqs, clamps, planes)
+    _optim_scalars_check(coef_dev, dev, 2 * len(params), "coef_dev")
+    with _on(dev):
+        _lib.call("qt_optim_adam_dev_f32", _ct.addressof(tab), len(params), _p(coef_dev), b1, 1.0 - b1, b2, 1.0 - b2, float(eps),
+                  float(weight_decay), _stream(dev))
+
+
+def pack_weight_nib_into(weight: torch.Tensor, kind: str, planes: NibPlanes) -> None:
+    """The nibble plane of Q(weight) (``kind``: "binary" | "ternary") written into the EXISTING words of ``planes``: what a fused
+    optimiser step leaves there, produced from the weight alone (one qt_sign_pack_nib_f32 / qt_ternary_pack_nib_f32 launch)."""
+    _require(weight, "weight")
+    w2, words = _as_rows(weight), planes.words
+    rows, K = int(w2.shape[0]), int(w2.shape[1])
+    if not (words.dtype == torch.int32 and words.is_contiguous() and words.device == weight.device and words.dim() == 2
+            and (rows, K) == (planes.rows, planes.K) and int(words.shape[0]) == rows and int(words.shape[1]) >= (K + 7) // 8):
+        raise ValueError("pack_weight_nib_into: planes is not the [rows, ld] int32 nibble plane of this weight")
+    entry = {"binary": "qt_sign_pack_nib_f32", "ternary": "qt_ternary_pack_nib_f32"}[kind]
+    with _on(weight.device):
+        _lib.call(entry, _p(w2), int(w2.stride(0) if rows > 1 else max(K, 1)), _p(words), int(words.shape[1]), rows, K,
+                  _stream(weight.device))

@@ -9,6 +9,7 @@ all-reduce is per-link bound and latency matters more than on a switch: few, lar
 292 MB of gradients leave as 5 launches) each started as soon as its last gradient exists, i.e. while backward is still
 producing the earlier layers' gradients.
 """
+import weakref
 from typing import Iterable, List, Optional
 
 import torch
@@ -30,6 +31,40 @@ class _Bucket:
         self.flat: Optional[torch.Tensor] = None
         self.pending = len(params)
         self.work = None
+
+
+_MARK = "_qt_grad_synchronizers"          # attribute of a parameter: a _SyncMark
+
+
+class _SyncMark:
+    """How many live GradientSynchronizers average the gradient of THIS parameter object.  A copy of the parameter that carries
+    its ``__dict__`` along (pickle, ``torch.save`` / load, deepcopy) has no synchroniser behind it: the mark copies as zero."""
+    __slots__ = ("n",)
+
+    def __init__(self):
+        self.n = 0
+
+    def __reduce__(self):
+        return (_SyncMark, ())
+
+    def __deepcopy__(self, memo):
+        return _SyncMark()
+
+
+def _unmark(param_refs):
+    for ref in param_refs:
+        p = ref()
+        mark = getattr(p, _MARK, None) if p is not None else None
+        if mark is not None:
+            mark.n -= 1
+            if mark.n <= 0:
+                delattr(p, _MARK)
+
+
+def is_synchronized(params) -> bool:
+    """A live GradientSynchronizer averages the gradient of one of ``params``.  (utils.GraphedTrainStep refuses to capture the
+    optimiser step of such a model: the all-reduce has to run between backward and the update.)"""
+    return any(getattr(p, _MARK, None) is not None and getattr(p, _MARK).n > 0 for p in params)
 
 
 class GradientSynchronizer:
@@ -73,6 +108,11 @@ class GradientSynchronizer:
             self.buckets.append(_Bucket(cur))
         self._hooks = []
         self._next = 0                      # index of the first bucket whose all-reduce has not been issued
+        for p in plist:                     # counted on the parameter; taken back by remove(), or when this object is dropped
+            if getattr(p, _MARK, None) is None:              # without it
+                setattr(p, _MARK, _SyncMark())
+            getattr(p, _MARK).n += 1
+        self._unmark = weakref.finalize(self, _unmark, [weakref.ref(p) for p in plist])
         if self.world > 1 and overlap:
             for b in self.buckets:
                 for p in b.params:
@@ -124,6 +164,7 @@ class GradientSynchronizer:
         for h in self._hooks:
             h.remove()
         self._hooks = []
+        self._unmark()                      # (a finalizer runs once)
 
 
 def broadcast_parameters(module: torch.nn.Module, src: int = 0, group=None):

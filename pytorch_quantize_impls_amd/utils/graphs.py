@@ -223,7 +223,8 @@ def auto_graphed(module: torch.nn.Module, **kw) -> AutoGraphed:
 
 
 class GraphedTrainStep:
-    """One training step — forward, loss, backward — of a fixed-shape batch captured once as a hipGraph and replayed.
+    """One training step — forward, loss, backward and, given a fused optimiser, the update — of a fixed-shape batch captured once
+    as a hipGraph and replayed.
 
     The training steps of small-map nets are launch-bound (DoReFa ResNet-18 at 32 x 32, batch 256: ~900 kernels of 5-40 us per
     step, 12.5 ms eager, 10.3 ms replayed; DESIGN.md section 1 "Training path").  This backend's autograd Functions launch on
@@ -235,30 +236,79 @@ class GraphedTrainStep:
         step = GraphedTrainStep(model, lambda out, target: F.nll_loss(F.log_softmax(out, 1), target), x0, t0)
         for x, t in loader:            # same shapes / dtypes as x0, t0
             loss = step(x, t)          # gradients are in p.grad (overwritten by the next call)
-            opt.step()                 # the optimizer stays outside the graph
+            opt.step()                 # any optimizer: it stays outside the graph
 
     Gradients are zeroed inside the graph (``zero_grad(set_to_none=False)``), so every replay leaves exactly this batch's
-    gradients behind.  BatchNorm running statistics and ``num_batches_tracked`` advance on every replay, like eager steps."""
+    gradients behind.  BatchNorm running statistics and ``num_batches_tracked`` advance on every replay, like eager steps.
+
+    ``optimizer=``: a ``utils.FusedQuantSGD`` / ``utils.FusedQuantAdam`` whose update — recurrence, the layers' clamp and the
+    weight planes of the next forward — becomes part of the graph, so the whole step of the reference's loops is one replay:
+
+        opt = utils.FusedQuantAdam(model, lr=1e-3)
+        step = GraphedTrainStep(model, loss_fn, x0, t0, optimizer=opt)
+        for x, t in loader:
+            loss = step(x, t)          # forward, loss, backward, optimizer.step(), model.clamp()
+            scheduler.step()           # group["lr"] is read before every replay
+
+      * The warm-up runs forward, loss and backward only: constructing the step applies no update (parameters and optimiser state
+        are what they were; the state tensors exist afterwards, as zeros).
+      * Per-step scalars (learning rate, Adam's bias corrections from ``state["step"]``) are written to device memory before each
+        replay; momentum, betas, eps, weight decay and nesterov are baked into the graph and changing one raises on the next call.
+        ``optimizer.step()`` may still be called eagerly between replays (step counts come from ``state["step"]``).
+      * The captured forward of a deterministic LinearBin / LinearTer reads the plane buffer the captured update rewrites.  Before a
+        replay, a weight whose version counter or plane record is not what the last replay left (``load_state_dict``, an in-place
+        edit under ``no_grad``, ``eval()`` / ``train()``) gets its plane packed again, eagerly.  Writes through ``.data`` are
+        invisible to that check, as they are to the eval cache.  ``emit_planes=False``: the captured forward packs from the fp32
+        weight.
+      * ``p.grad`` holds the batch's gradients after a call, as without an optimiser.  The graph owns those tensors and zeroes them
+        itself: a call after ``zero_grad(set_to_none=True)`` (torch's default) raises, it does not train on buffers nobody reads.
+      * A captured step has no library path: every parameter with a gradient must be a contiguous fp32 device tensor (a
+        channels-last conv weight is not), else the constructor raises ``ValueError`` naming it.  ``optimizer.load_state_dict``
+        replaces the state tensors, so the next call raises: load first, then construct the step.
+      * One optimiser may serve several steps (a full and a tail batch shape): each has its own scalar block, all share the
+        optimiser's state and plane buffers.
+    Other optimiser types stay outside the graph (the form above); so do data-parallel steps: a model whose gradients a
+    ``GradientSynchronizer`` averages is refused, because the all-reduce runs between backward and the update."""
 
     def __init__(self, model: torch.nn.Module, loss_fn, example_input: torch.Tensor, example_target: torch.Tensor,
-                 warmup: int = 3):
+                 warmup: int = 3, optimizer=None):
         from ..functions import _fused
+        if optimizer is not None:
+            from .data_parallel import is_synchronized
+            from .optim import _FusedQuantOptimizer
+            if not isinstance(optimizer, _FusedQuantOptimizer):
+                raise TypeError(f"GraphedTrainStep captures the update of utils.FusedQuantSGD / utils.FusedQuantAdam only, not of "
+                                f"{type(optimizer).__name__}: keep it outside the graph (loss = step(x, t); opt.step())")
+            if is_synchronized(model.parameters()):
+                raise RuntimeError("GraphedTrainStep: a GradientSynchronizer averages this model's gradients between backward and the "
+                                   "update; data-parallel steps keep the optimiser outside the graph (loss = step(x, t); sync.wait(); "
+                                   "opt.step())")
         if not example_input.is_cuda:
             raise TypeError("graph capture needs device tensors")
-        self.model, self.loss_fn = model, loss_fn
+        self.model, self.loss_fn, self.optimizer = model, loss_fn, optimizer
         self._x, self._t = example_input.clone(), example_target.clone()
         self._stream = torch.cuda.Stream(device=example_input.device)
         self._graph = torch.cuda.CUDAGraph()
         for p in model.parameters():
             if p.requires_grad and p.grad is None:
                 p.grad = torch.zeros_like(p)          # static gradient buffers: the captured backward accumulates into them
-        with _fused.detect_scope("remember"):          # thread-local; the Functions carry it into their backward
+        self._capture, planes = None, contextlib.nullcontext()
+        if optimizer is not None:
+            # this graph's handle on the optimiser (its own scalar block; the optimiser may serve other graphs too): state exists,
+            # raises for what a captured step cannot update
+            self._capture = optimizer.prepare_capture()
+            optimizer.refresh_planes(self._capture)   # the planes the captured forward reads: packed once, into the persistent buffers
+            self._stream.wait_stream(torch.cuda.current_stream(example_input.device))     # (packed on the caller's stream)
+            planes = optimizer.capturing(self._capture)
+        with _fused.detect_scope("remember"), planes:  # thread-local; the Functions carry the detect mode into their backward
             with torch.cuda.stream(self._stream):
                 for _ in range(max(1, warmup)):       # verdicts asked (and remembered), allocations and weight caches settle
                     self._one()
                 torch.cuda.synchronize(example_input.device)
                 with _no_collection_inside(), torch.cuda.graph(self._graph, stream=self._stream):
                     self._loss = self._one()
+                    if optimizer is not None:
+                        optimizer.captured_step(self._capture)
             torch.cuda.synchronize(example_input.device)
 
     def _one(self):
@@ -273,5 +323,9 @@ class GraphedTrainStep:
                              f"{self._t.dtype}, got {tuple(x.shape)} {x.dtype} / {tuple(target.shape)} {target.dtype}")
         self._x.copy_(x)
         self._t.copy_(target)
+        if self.optimizer is not None:
+            self.optimizer.before_replay(self._capture)     # this step's scalars to the device, stale planes packed again
         self._graph.replay()
+        if self.optimizer is not None:
+            self.optimizer.after_replay(self._capture)      # version counters, plane records
         return self._loss

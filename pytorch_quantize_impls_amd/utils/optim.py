@@ -6,6 +6,10 @@ benchmark/BinaryNet/mnist.py:42-44) — as ONE multi-tensor launch sequence per 
 fold the layers' ``clamp()`` into the update (``clamp_plan``) and, for deterministic ``LinearBin`` / ``LinearTer``, leave the fp4
 nibble plane of the new weight where the next training forward finds it (``weight._qt_train_planes``), so that forward does
 not read the fp32 weight again only to take its sign.
+
+Capture mode (``prepare_capture`` / ``captured_step`` / ``before_replay`` / ``after_replay``) is what ``utils.GraphedTrainStep``
+uses to put the update inside its hipGraph: the launches read the per-step scalars (learning rate, Adam's bias corrections)
+from a device block the host rewrites before every replay, everything else is baked into the captured launches.
 """
 import functools
 from typing import Dict, Tuple
@@ -93,12 +97,41 @@ def _on_route(p: torch.Tensor, g: torch.Tensor, *state) -> bool:
     return all(s.is_cuda and s.dtype == torch.float32 and s.is_contiguous() and s.device == p.device for s in state)
 
 
+class _CapturedGroup:
+    """What one parameter group contributes to a captured step: the parameters that had a gradient at capture time, their state
+    tensors, clamp ranges and planes, the slice of the scalar block its launches read and the hyper-parameters baked into them."""
+
+    def __init__(self, index, params, baked):
+        self.index, self.params, self.baked = index, params, baked     # index into param_groups (load_state_dict replaces the dicts)
+        self.grads = [p.grad for p in params]
+        self.pointers = [p.data_ptr() for p in params]
+        self.scalars = None                        # view into the scalar block (set by prepare_capture)
+        self.states = self.planes = self.clamps = self.steps = None
+        self.offset = self.numel = 0
+
+
+class _Capture:
+    """One captured step of an optimiser: what ``prepare_capture()`` returns and ``captured_step`` / ``before_replay`` /
+    ``after_replay`` / ``refresh_planes`` take.  It belongs to the graph that was captured with it (``utils.GraphedTrainStep`` keeps
+    it), not to the optimiser: one optimiser may serve several graphs (a full and a tail batch shape), each with its own scalar
+    block, all on the optimiser's one set of state tensors and plane buffers."""
+
+    def __init__(self, groups, block, state_epoch):
+        self.groups, self.block, self.state_epoch = groups, block, state_epoch
+
+
 class _FusedQuantOptimizer(Optimizer):
+    #: the group entries a captured launch takes by value: changing one after the capture cannot reach the graph
+    _BAKED = ()
+
     def __init__(self, params, defaults, clamp, emit_planes):
         module = params if isinstance(params, torch.nn.Module) else None
+        self._names = {}
         if module is not None:
+            self._names = {p: n for n, p in module.named_parameters()}
             params = list(module.parameters())
         super().__init__(params, defaults)
+        self._state_epoch = 0                      # load_state_dict() calls: each replaces every state tensor
         self._clamp_plan = clamp_plan(module) if module is not None and (clamp is None or clamp) else {}
         self._post_clamp = unplanned_clamp_layers(module) if module is not None and (clamp is None or clamp) else []
         self._plane_layers = {}
@@ -124,7 +157,173 @@ class _FusedQuantOptimizer(Optimizer):
         torch.autograd.graph.increment_version(fused_params)
         for p, pl in zip(fused_params, planes):
             if pl is not None:
-                p._qt_train_planes = {"version": p._version, "ptr": p.data_ptr(), "mfma": pl[0]}
+                self._stamp(p, pl)
+
+    @staticmethod
+    def _stamp(p, pl):
+        p._qt_train_planes = {"version": p._version, "ptr": p.data_ptr(), "mfma": pl[0]}
+
+    # ---- capture mode: the update as part of utils.GraphedTrainStep's hipGraph ----
+
+    def _name(self, p):
+        if p in self._names:
+            return self._names[p]
+        for gi, group in enumerate(self.param_groups):
+            for i, q in enumerate(group["params"]):
+                if q is p:
+                    return f"param_groups[{gi}]['params'][{i}] {tuple(p.shape)}"
+        return f"parameter {tuple(p.shape)}"
+
+    def _check_group(self, group):                 # pragma: no cover - abstract
+        raise NotImplementedError
+
+    def _allocate(self, p, group):                 # pragma: no cover - abstract
+        """Create the state of ``p`` if it has none; returns its state tensors in the kernel's order."""
+        raise NotImplementedError
+
+    def allocate_state(self):
+        """The state of every parameter that has a gradient, created up front as zeros (``step``: the host scalar tensor torch
+        keeps): a captured launch needs its pointers before the first step.  A zeroed state is the state before the first step —
+        ``torch.optim`` steps from it as from none (Adam starts from zeros anyway; SGD's first ``buf = g`` becomes ``mu * 0 + g``,
+        which differs only in turning a -0.0 gradient entry into +0.0 in the buffer).  Existing state is kept."""
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is not None:
+                    self._allocate(p, group)
+
+    def prepare_capture(self) -> _Capture:
+        """Fix what a captured step updates — every parameter that has a gradient NOW, with its state allocated
+        (``allocate_state``) — and allocate one device block for the per-step scalars of its launch sequences.  Returns the
+        ``_Capture`` the other capture-mode methods take; every call makes a new one with a block of its own, and earlier ones stay
+        valid.  A captured step has no library path: a parameter off the kernel's route (host, non-fp32, non-contiguous), a sparse
+        gradient or parameters on more than one device raise ``ValueError`` naming the parameter."""
+        self.allocate_state()
+        groups, device, numel = [], None, 0
+        for index, group in enumerate(self.param_groups):
+            self._check_group(group)
+            params = [p for p in group["params"] if p.grad is not None]
+            for p in params:
+                if p.grad.is_sparse:
+                    raise ValueError(f"captured step: {self._name(p)} has a sparse gradient")
+                if not _on_route(p, p.grad, *self._allocate(p, group)):
+                    raise ValueError(f"captured step: {self._name(p)} ({p.dtype}, {p.device}, contiguous={p.is_contiguous()}) is off "
+                                     "the fused kernel's route (contiguous fp32 device tensors) and a captured step has no library path")
+                if device is not None and p.device != device:
+                    raise ValueError(f"captured step: {self._name(p)} is on {p.device}, other parameters on {device}: one graph, one device")
+                device = p.device
+            if params:
+                cg = _CapturedGroup(index, params, {k: group[k] for k in self._BAKED})
+                cg.offset, cg.numel = numel, self._scalars_per_group(len(params))
+                numel += cg.numel
+                groups.append(cg)
+        # ONE block for the scalars of all groups.  before_replay() rewrites it with a launch that carries the values in its argument
+        # block (ops.optim_write_scalars): stream-ordered between the previous replay and the next, no synchronise, and no host
+        # staging buffer an earlier, still pending write could be reading — the runtime copies the arguments at enqueue time.
+        block = torch.zeros(numel, dtype=torch.float32, device=device) if groups else None
+        for cg in groups:
+            cg.scalars = block[cg.offset:cg.offset + cg.numel]
+            cg.states = [self._allocate(p, self.param_groups[cg.index]) for p in cg.params]
+            cg.steps = [self.state[p]["step"] for p in cg.params if "step" in self.state[p]]
+            cg.planes = [self._plane_of(p) for p in cg.params]
+            cg.clamps = [self._clamp_plan.get(p) for p in cg.params]
+        return _Capture(groups, block, self._state_epoch)
+
+    def load_state_dict(self, state_dict):
+        """``Optimizer.load_state_dict``.  It replaces every state tensor, so captured steps of this optimiser would go on updating
+        the old ones: their next ``before_replay`` raises (load the state first, then capture)."""
+        super().load_state_dict(state_dict)
+        self._state_epoch += 1
+
+    def capturing(self, capture: _Capture):
+        """Context for the warm-up and the stream capture of ``capture``'s graph: inside it (and nowhere else) the training forward of
+        a LinearBin / LinearTer may take ``capture``'s plane buffers while the stream is capturing — the graph's own update rewrites
+        them on every replay and ``before_replay`` repacks a stale one.  Any other capture still gets no plane."""
+        return _fused.plane_capture_scope([pl[0].words for cg in capture.groups for pl in cg.planes if pl is not None])
+
+    def refresh_planes(self, capture: _Capture):
+        """The invariant a captured forward relies on: the persistent plane buffer of every captured deterministic LinearBin /
+        LinearTer weight holds the plane of the weight AS IT IS NOW, recorded under its current version counter and storage.  The
+        captured step keeps it (it rewrites the buffer with every update, ``after_replay`` re-stamps the record), and so does an
+        eager ``step()`` of this optimiser (same buffers); whatever else writes the weight — ``load_state_dict``, an in-place edit,
+        ``eval()`` / ``train()``, another optimiser — moves the version counter or drops the record, and the plane is packed again
+        here, eagerly, from the weight alone.  Returns the number of planes packed.  (Writes through ``.data`` are invisible, as
+        they are to the eval cache.)"""
+        packed = 0
+        for cg in capture.groups:
+            for p, pl in zip(cg.params, cg.planes):
+                if pl is None:
+                    continue
+                rec = getattr(p, "_qt_train_planes", None)
+                if rec is not None and rec["mfma"].words is pl[0].words and rec["version"] == p._version and rec["ptr"] == p.data_ptr():
+                    continue
+                with torch.no_grad():
+                    ops.pack_weight_nib_into(p.detach(), pl[1], pl[0])
+                self._stamp(p, pl)
+                packed += 1
+        return packed
+
+    def _launch_captured(self, cg):                # pragma: no cover - abstract
+        raise NotImplementedError
+
+    @staticmethod
+    def _scalars_per_group(n):                     # pragma: no cover - abstract
+        """fp32 scalars the launches of a group of ``n`` captured parameters read."""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def captured_step(self, capture: _Capture):
+        """The update of every captured parameter on the current stream, with the clamps and planes of ``step()`` — the launches a
+        stream capture records.  Nothing on the host changes: ``before_replay`` / ``after_replay`` do what ``step()`` does there."""
+        for cg in capture.groups:
+            self._launch_captured(cg)
+        for m in self._post_clamp:                 # clamp() of layers clamp_plan cannot restate: torch ops, captured as well
+            m.clamp()
+
+    def _scalars_of(self, cg):                     # pragma: no cover - abstract
+        """The fp32 scalars of ``cg``'s launches for the step about to run, from the group's CURRENT entries and, for Adam, the
+        step counts ``state["step"] + 1``.  Changes nothing."""
+        raise NotImplementedError
+
+    def before_replay(self, capture: _Capture):
+        """Host side of a replay, before it: checks that nothing baked into the captured launches was changed, restores the plane
+        invariant (``refresh_planes``), computes the step's scalars from the current ``param_groups`` (LR schedulers, manual
+        ``group['lr']`` edits) and sends them to ``capture``'s device block (``ops.optim_write_scalars``: a launch, no synchronise).
+        The step counts advance last, once nothing can fail any more."""
+        if capture.state_epoch != self._state_epoch:
+            raise RuntimeError(f"{type(self).__name__}: load_state_dict() replaced the state tensors since the step was captured; the "
+                               "graph still updates the old ones — load the state first, then capture a new GraphedTrainStep")
+        for cg in capture.groups:
+            group = self.param_groups[cg.index]
+            self._check_group(group)
+            for k, v in cg.baked.items():
+                now = group[k]
+                if (tuple(now) if isinstance(now, (list, tuple)) else now) != (tuple(v) if isinstance(v, (list, tuple)) else v):
+                    raise RuntimeError(f"{type(self).__name__}: {k} was {v!r} when the step was captured and is {now!r} now; it is "
+                                       "baked into the captured launches — capture a new GraphedTrainStep")
+            for p, g, ptr in zip(cg.params, cg.grads, cg.pointers):
+                if p.grad is not g or p.data_ptr() != ptr:
+                    raise RuntimeError(f"{type(self).__name__}: {self._name(p)} or its gradient was replaced since the step was captured "
+                                       "(zero_grad(set_to_none=True), .to(), an assignment to .grad / .data); the graph still works on the "
+                                       "old storage — keep the gradients (they are zeroed inside the graph) or capture a new "
+                                       "GraphedTrainStep")
+        self.refresh_planes(capture)
+        values = []
+        for cg in capture.groups:
+            values += self._scalars_of(cg)
+        if capture.block is not None:
+            ops.optim_write_scalars(capture.block, values)
+        for cg in capture.groups:
+            if cg.steps:
+                torch._foreach_add_(cg.steps, 1)   # state["step"] as torch keeps it (host scalar tensors): one call for all
+
+    def after_replay(self, capture: _Capture):
+        """Host side of a replay, after it: what ``step()`` does after its launches (version counters, plane records)."""
+        for cg in capture.groups:
+            self._record(cg.params, cg.planes)
+        if hasattr(self.step, "_wrapped_by_lr_sched"):
+            # torch/optim/lr_scheduler.py (LRScheduler.__init__, patch_track_step_called) wraps step() to set this flag and warns
+            # "lr_scheduler.step() before optimizer.step()" while it is unset; a replay IS a step.  Without that wrapper: nothing to do.
+            self._opt_called = True
 
     def _finish(self, library_params):
         """The clamps that were not folded into a launch: parameters off the kernel's route, layers ``clamp_plan`` does not know."""
@@ -178,6 +377,33 @@ class FusedQuantSGD(_FusedQuantOptimizer):
                         maximize=False, foreach=None, differentiable=False, fused=None)
         super().__init__(params, defaults, clamp, emit_planes)
 
+    _BAKED = ("momentum", "weight_decay", "nesterov")
+
+    def _check_group(self, group):
+        _reject("FusedQuantSGD", maximize=group["maximize"], dampening=group["dampening"] != 0)
+
+    def _allocate(self, p, group):
+        if group["momentum"] == 0:
+            return []
+        st = self.state[p]
+        if st.get("momentum_buffer") is None:
+            st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return [st["momentum_buffer"]]
+
+    @staticmethod
+    def _scalars_per_group(n):
+        return 1
+
+    def _launch_captured(self, cg):
+        # no first-step flag: the buffers exist, and from a zeroed buffer mu * 0 + g IS the first step's value (see allocate_state)
+        mu = cg.baked["momentum"]
+        ops.optim_step_sgd_dev(cg.params, [p.grad for p in cg.params], [st[0] for st in cg.states] if mu != 0 else None, cg.scalars,
+                               momentum=mu, weight_decay=cg.baked["weight_decay"], nesterov=cg.baked["nesterov"], clamps=cg.clamps,
+                               planes=cg.planes)
+
+    def _scalars_of(self, cg):
+        return [float(self.param_groups[cg.index]["lr"])]
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -186,7 +412,7 @@ class FusedQuantSGD(_FusedQuantOptimizer):
                 loss = closure()
         off_route = []
         for group in self.param_groups:
-            _reject("FusedQuantSGD", maximize=group["maximize"], dampening=group["dampening"] != 0)
+            self._check_group(group)
             lr, mu, wd, nesterov = group["lr"], group["momentum"], group["weight_decay"], group["nesterov"]
             fused, library = self._split(group, ("momentum_buffer",))
             for plist in fused.values():
@@ -235,6 +461,30 @@ class FusedQuantAdam(_FusedQuantOptimizer):
                         capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False)
         super().__init__(params, defaults, clamp, emit_planes)
 
+    _BAKED = ("betas", "eps", "weight_decay")
+
+    def _check_group(self, group):
+        _reject("FusedQuantAdam", amsgrad=group["amsgrad"], maximize=group["maximize"], capturable=group["capturable"],
+                decoupled_weight_decay=group.get("decoupled_weight_decay", False))
+
+    def _allocate(self, p, group):
+        st = self._init_state(p)
+        return [st["exp_avg"], st["exp_avg_sq"]]
+
+    @staticmethod
+    def _scalars_per_group(n):
+        return 2 * n
+
+    def _launch_captured(self, cg):
+        ops.optim_step_adam_dev(cg.params, [p.grad for p in cg.params], [st[0] for st in cg.states], [st[1] for st in cg.states],
+                                cg.scalars, betas=cg.baked["betas"], eps=cg.baked["eps"], weight_decay=cg.baked["weight_decay"],
+                                clamps=cg.clamps, planes=cg.planes)
+
+    def _scalars_of(self, cg):
+        # the step counts are read from state["step"], so eager step() calls between replays are counted too
+        steps = [int(t) + 1 for t in torch.stack(cg.steps).tolist()]
+        return [c for pair in ops.adam_coefficients(steps, self.param_groups[cg.index]["lr"], cg.baked["betas"]) for c in pair]
+
     def _init_state(self, p):
         st = self.state[p]
         if len(st) == 0:
@@ -251,8 +501,7 @@ class FusedQuantAdam(_FusedQuantOptimizer):
                 loss = closure()
         off_route = []
         for group in self.param_groups:
-            _reject("FusedQuantAdam", amsgrad=group["amsgrad"], maximize=group["maximize"], capturable=group["capturable"],
-                    decoupled_weight_decay=group.get("decoupled_weight_decay", False))
+            self._check_group(group)
             lr, betas, eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
             for p in group["params"]:
                 if p.grad is not None:
