@@ -555,6 +555,149 @@ def _pixel_planes(input: torch.Tensor, binary_input: Optional[bool], weight: Opt
     return ops.pack_pixels_nib(input, ld=ld_fn(int(input.shape[1]))), flag
 
 
+def first_layer_rungs(C, Cout, kernel_hw, stride, padding, dilation, H, W, kind: str, out=None, pooled: bool = False, allowed=None):
+    """The rungs ``first_layer_conv_routes`` tries, in ladder order: pure (predicates and switches, read on every call; nothing is
+    launched).  "binary" / "ternary": first3x3, direct3x3, d2s, first_direct, s2d, plain; "xnor" (the real image sign(W) * alpha):
+    first_direct_real, bf16x6.  ``out``: None = the fp32 result, "bits" = threshold bits, (hy, hx) = the next conv's nibble plane
+    with that halo.  ``pooled``: a pool follows, so a nibble ``out`` names what the BLOCK hands on and the conv writes bits; it
+    matters only with a nibble ``out`` (the fused block asks for bits itself when it pools).  ``allowed``: the caller's rungs
+    (None = all).  The runner walks the same code as a generator and never evaluates the predicates behind the rung that ran."""
+    return tuple(_walk_first_layer_rungs(C, Cout, kernel_hw, stride, padding, dilation, H, W, kind, out, pooled, allowed))
+
+
+def _walk_first_layer_rungs(C, Cout, kernel_hw, stride, padding, dilation, H, W, kind, out, pooled, allowed):
+    # (imported here on purpose: layers.fused imports this module, and its two switches are read from it at call time)
+    from ..layers import fused as blocks
+    kernel_hw = (int(kernel_hw[0]), int(kernel_hw[1]))
+    geom = (kernel_hw, stride, padding, dilation)
+    if kind == "xnor":
+        if (allowed is None or "first_direct_real" in allowed) and ops.first_direct_applicable(C, *geom):
+            yield "first_direct_real"
+        if allowed is None or "bf16x6" in allowed:
+            yield "bf16x6"
+        return
+    nib = isinstance(out, tuple) and not pooled
+    if (allowed is None or "first3x3" in allowed) and ops.first3x3_applicable(C, Cout, *geom):
+        yield "first3x3"
+    # planes only: the direct kernel writes bits or the halo-1 nibble plane, the output-blocked form regroups in the nibble epilogue
+    if ((allowed is None or "direct3x3" in allowed) and blocks.DIRECT_FIRST_LAYER and out is not None
+            and (not nib or tuple(out) == (1, 1)) and ops.direct_first_layer_applicable(C, Cout, *geom)):
+        yield "direct3x3"
+    if ((allowed is None or "d2s" in allowed) and blocks.D2S_FIRST_LAYER and nib
+            and ops.d2s_first_layer_applicable(C, Cout, *geom, H, W)):
+        yield "d2s"
+    if (allowed is None or "first_direct" in allowed) and ops.first_direct_applicable(C, *geom):
+        yield "first_direct"
+    if (allowed is None or "s2d" in allowed) and USE_S2D and ops.s2d_applicable(C, *kernel_hw, stride, dilation, padding):
+        yield "s2d"
+    if allowed is None or "plain" in allowed:
+        yield "plain"
+
+
+def first_layer_weight_planes(form: str, wq: torch.Tensor, kind: str, stride: int, terms: Optional[int] = None):
+    """The QUANTISED weight image ``wq`` as the operand of rung ``form`` (eval-mode layers cache it: ``_conv_triples``)."""
+    if form == "first3x3":                                   # MFMA row fragments of the one-pass 3 x 3 kernel
+        return ops.pack_first3x3_weight(wq)
+    if form in ("first_direct", "first_direct_real"):        # fragment-ordered fp16 weight of the direct kernel (two terms: real)
+        return ops.pack_first_layer_weight(wq, stride, real=form == "first_direct_real")
+    if form == "plain":
+        return ops.pack_conv_weight_bf16x3(wq, kind, terms=terms)
+    if form == "bf16x6":
+        return ops.pack_conv_weight_bf16x6(wq)
+    # "s2d" / "d2s": (shape, split image) of the weight of the stride-1 conv on the space-to-depth image
+    ws = ops.s2d_weight(ops.d2s_first_layer_weight(wq.detach()), 2) if form == "d2s" else ops.s2d_weight(wq.detach(), stride)
+    return tuple(ws.shape), ops.pack_conv_weight_bf16x3(ws, "sign", terms=terms)      # zeros stay zeros
+
+
+def first_layer_conv_routes(input, weight, bias, stride, padding, dilation, kind: str, epi=None, weight_q=None, cache=None,
+                            rungs=None, pooled: bool = False, taken: Optional[list] = None):
+    """THE ladder of the forward routes of a sign-family conv (groups == 1, zero padding) on a REAL-valued device fp32 image, the
+    network's first layer: runs the first rung of ``first_layer_rungs`` whose launch wrapper takes the shape and returns
+    (result, (N, Cout, Ho, Wo)); None when no rung ran.  The result is what ``epi`` asks for: None — the NHWC fp32 matrix;
+    (alpha, beta) — the BitPlanes of [(conv + bias) * alpha + beta < 0]; a NibEpilogue — the next conv's nibble plane.
+
+    Every output form of a rung comes from ONE accumulation: the threshold bits of the fused / deferred chain must come from the
+    very accumulators the fp32 output of the module-by-module execution shows, or the two differ at ties.  A rung that cannot
+    write the requested nibble plane is therefore handed (alpha, beta) and its bits are expanded here, once.
+    ``kind``: "binary" / "ternary", or "xnor" for the real weight image sign(W) * alpha (``weight_q``).  ``cache``: the layer's
+    ``_conv_triples`` (``cache(form[, terms])``: the cached operand of the eval-mode weight) or None: packed on the fly from
+    ``weight_q`` (default: the idempotent quantiser of ``kind`` on ``weight``).  ``rungs``: the rungs the caller allows;
+    ``pooled``: see ``first_layer_rungs``; ``taken``: a list that receives the name of the rung that ran."""
+    N, C, H, W = (int(v) for v in input.shape)
+    Cout, kh, kw = int(weight.shape[0]), int(weight.shape[2]), int(weight.shape[3])
+    nib = epi if isinstance(epi, ops.NibEpilogue) else None
+    out = None if epi is None else (tuple(nib.out_halo) if nib is not None else "bits")
+    # (nothing but the walk in front of the first rung: a caller whose rungs do not apply pays for the predicates alone)
+    for rung in _walk_first_layer_rungs(C, Cout, (kh, kw), stride, padding, dilation, H, W, kind, out, pooled, rungs):
+        y = _first_layer_rung(rung, input, weight, bias, stride, padding, dilation, kind, epi, weight_q, cache)
+        if y is None:
+            continue
+        Ho, Wo = ops.conv_out_hw(H, W, kh, kw, stride, padding, dilation)
+        if nib is not None and isinstance(y, ops.BitPlanes):
+            y = ops.bits_to_nib_pad(y, N, Ho, Wo, nib.out_halo, ld=ops.pixel_ld_nib(y.K))
+        if taken is not None:
+            taken.append(rung)
+        return y, (N, Cout, Ho, Wo)
+    return None
+
+
+def _first_layer_rung(rung, input, weight, bias, stride, padding, dilation, kind, epi, weight_q, cache):
+    """One rung of ``first_layer_conv_routes``: fp32 rows, BitPlanes or NibPlanes; None when the launch wrapper declines the shape."""
+    (N, C, H, W), Cout, sd = (int(v) for v in input.shape), int(weight.shape[0]), ops._pairs(stride)[0]
+    nib = epi if isinstance(epi, ops.NibEpilogue) else None
+    affine = ops.epilogue_affine(epi)[:2] if epi is not None else None
+
+    def planes(form, terms=None):
+        got = cache(form, terms) if cache is not None else None
+        if got is None:
+            got = first_layer_weight_planes(form, weight_q if weight_q is not None else quantize_weight_f32(weight, kind), kind, sd, terms)
+        return got
+
+    def conv_on_s2d_image(px, Hs, Ws, s, wplanes, b, e):      # (the gather and the split were one kernel)
+        return ops.float_conv2d(None, torch.empty(wplanes[0], device="meta"), "sign", b, 1, 0, 1, weight_triples=wplanes[1],
+                                pixels=px, in_shape=(N, C * s * s, Hs, Ws), epi=e)
+
+    if rung == "first3x3":
+        # VGG-16's conv1_1: the one-pass kernel reads the fp32 image where it lies and writes fp32, bits or the halo-1 nibble plane
+        own = nib is None or (tuple(nib.out_halo) == (1, 1) and not nib.d2s_cout)
+        return ops.conv_first3x3(input, planes(rung), Cout, bias, epi=epi if own else affine)
+    if rung == "direct3x3":
+        # 3 x 3 / stride 1 / padding 1, <= 5 channels: the direct kernel on the padded fp16-pair (two taps per MFMA) / bf16-triple plane
+        terms = ops.direct_first_layer_terms(C)
+        px, _ = ops.s2d_triple_pack(input, 1, 1, terms=terms)
+        return ops.conv3x3_direct_nib(px, N, C, H, W, planes("plain", terms), bias, epi)
+    if rung == "d2s":
+        # the 2x2 output-blocked form (ops.d2s_first_layer_weight): 2x2 taps over the space-to-depth(2) image, 4 * Cout columns,
+        # depth-to-space in the nibble epilogue — the same products from a quarter of the gathered bytes (VGG-16 conv1: 550 -> 290 us)
+        wplanes = planes(rung)
+        px, (Hs, Ws) = ops.s2d_triple_pack(input, 2, 1)
+        e = ops.NibEpilogue(affine[0].repeat(4), affine[1].repeat(4), nib.out_halo, d2s_cout=Cout)
+        return conv_on_s2d_image(px, Hs, Ws, 2, wplanes, bias.detach().repeat(4) if bias is not None else None, e)
+    if rung in ("first_direct", "first_direct_real"):
+        # strided few-channel conv (AlexNet conv1): the direct kernel splits its patch in registers, no operand pack pass.  (Its fp32
+        # store tail makes the module-by-module conv1 ~100 us slower than "s2d" there — not the inference path: tools/bench_conv1.py)
+        return ops.conv_first_direct(input, planes(rung), bias, stride, padding, epi=affine)
+    if rung == "s2d":
+        # strided / padded few-channel conv == stride-1 conv on the space-to-depth image; pixels the rounding added are cropped (a
+        # nibble epilogue maps rows with the kernel's own (H2, W2) geometry, so then: bits, cropped, expanded by the runner)
+        px, (Hs, Ws) = ops.s2d_triple_pack(input, sd, padding)
+        wplanes = planes(rung)
+        H2, W2 = Hs - wplanes[0][2] + 1, Ws - wplanes[0][2] + 1
+        Ho, Wo = ops.conv_out_hw(H, W, int(weight.shape[2]), int(weight.shape[3]), stride, padding, dilation)
+        crop = (H2, W2) != (Ho, Wo)
+        y = conv_on_s2d_image(px, Hs, Ws, sd, wplanes, bias, affine if (crop and nib is not None) else epi)
+        if crop:
+            rows = (y if epi is None else y.sign).view(N, H2, W2, -1)[:, :Ho, :Wo, :].contiguous().view(N * Ho * Wo, -1)
+            y = rows if epi is None else ops.BitPlanes(sign=rows, rows=N * Ho * Wo, K=y.K)
+        return y
+    if rung == "plain":
+        return ops.float_conv2d(input, weight_q if weight_q is not None else weight, kind, bias, stride, padding, dilation,
+                                weight_triples=cache("plain") if cache is not None else None, epi=epi)
+    # "bf16x6": real x real on six-term bf16 planes, implicit-GEMM conv on the matrix cores (fp32-GEMM accuracy)
+    return ops.real_conv2d(input, (weight_q if weight_q is not None else weight).detach(), bias, stride, padding, dilation,
+                           weight_planes=cache(rung) if cache is not None else None, epi=epi)
+
+
 def quant_conv2d_forward(input, weight, bias, stride, padding, dilation, groups, kind: str,
                          weight_q: Optional[torch.Tensor] = None, weight_planes=None,
                          binary_input: Optional[bool] = None, padding_mode: str = "zeros",
@@ -595,87 +738,10 @@ def quant_conv2d_forward(input, weight, bias, stride, padding, dilation, groups,
     if odt is not None:
         raise RuntimeError("a half-precision activation that is not +-1 has no packed route: the layers send it to the torch expression")
     if packable and _cfg("FLOAT_PATH") == "bf16x3" and input.dtype == torch.float32 and input.numel() > 0:
-        # real-valued activation (first layer): exact bf16 triples + implicit-GEMM conv on the bf16
-        # matrix cores; the quantisers are idempotent so an explicit quantised image is packed the same way
-        N, C, H, W = input.shape
-        kh, kw = int(weight.shape[2]), int(weight.shape[3])
-        Ho, Wo = ops.conv_out_hw(H, W, kh, kw, stride, padding, dilation)
-        if kind in ("binary", "ternary") and ops.first3x3_applicable(C, int(weight.shape[0]), (kh, kw), stride, padding, dilation) and \
-                (epi is None or isinstance(epi, (tuple, ops.NibEpilogue))):
-            # stride-1 3 x 3 first layer, 64 output channels (VGG-16's conv1_1): the one-pass kernel reads the fp32 image where it lies
-            # (per-tile fp16 split in LDS) and serves all three epilogues from one accumulation — fp32 here for the module-by-module
-            # execution, threshold bits / the next conv's nibble halo plane for the fused chain: same bits at ties by construction
-            fw = weight_triples_fn("first3x3") if weight_triples_fn is not None else None
-            if fw is None:
-                wq = weight_q if weight_q is not None else quantize_weight_f32(weight, kind)
-                fw = ops.pack_first3x3_weight(wq)
-            nib_epi = epi if isinstance(epi, ops.NibEpilogue) else None
-            e3 = epi if (epi is None or (nib_epi is not None and tuple(nib_epi.out_halo) == (1, 1) and not nib_epi.d2s_cout)) else \
-                ((nib_epi.alpha, nib_epi.beta) if nib_epi is not None else epi[:2])
-            y2 = ops.conv_first3x3(input, fw, int(weight.shape[0]), bias, epi=e3)
-            if y2 is not None:
-                if epi is not None:
-                    if nib_epi is not None and isinstance(y2, ops.BitPlanes):
-                        y2 = ops.bits_to_nib_pad(y2, N, Ho, Wo, nib_epi.out_halo, ld=ops.pixel_ld_nib(y2.K))
-                    return y2, (N, int(weight.shape[0]), Ho, Wo)
-                return nchw_result(y2, input, N, Ho, Wo, weight.shape[0])
-        if ops.first_direct_applicable(C, (kh, kw), stride, padding, dilation):
-            # (both epilogues on ONE route: the threshold bits of the fused / deferred chain must come from the very accumulators
-            # the fp32 output of the module-by-module execution shows, or the two executions differ at ties.  The kernel's fp32
-            # store tail makes the module-by-module conv1 ~100 us slower than the space-to-depth route at AlexNet's shape — not the
-            # inference path: tools/bench_conv1.py)
-            # strided few-channel first layer (AlexNet conv1): the direct kernel reads the fp32 image where it lies, splits its
-            # patch in registers and contracts by stride addressing — no operand pack pass, no space-to-depth plane
-            fw = weight_triples_fn("first_direct") if weight_triples_fn is not None else None
-            if fw is None:
-                wq = weight_q if weight_q is not None else quantize_weight_f32(weight, kind)
-                fw = ops.pack_first_layer_weight(wq, ops._pairs(stride)[0])
-            nib_epi = epi if isinstance(epi, ops.NibEpilogue) else None
-            y2 = ops.conv_first_direct(input, fw, bias, stride, padding,
-                                       epi=(nib_epi.alpha, nib_epi.beta) if nib_epi is not None else (epi[:2] if epi is not None else None))
-            if y2 is not None:
-                if epi is not None:
-                    if nib_epi is not None:
-                        y2 = ops.bits_to_nib_pad(y2, N, Ho, Wo, nib_epi.out_halo, ld=ops.pixel_ld_nib(y2.K))
-                    return y2, (N, int(weight.shape[0]), Ho, Wo)
-                return nchw_result(y2, input, N, Ho, Wo, weight.shape[0])
-        if USE_S2D and ops.s2d_applicable(C, kh, kw, stride, dilation, padding):
-            # strided few-channel conv (conv1) == stride-1 conv on the space-to-depth image; the gather and
-            # the exact bf16 split are one kernel, the transformed weight is cached by eval-mode layers
-            sd = ops._pairs(stride)[0]
-            px, (Hs, Ws) = ops.s2d_triple_pack(input, sd, padding)
-            cached = weight_triples_fn("s2d") if weight_triples_fn is not None else None
-            if cached is not None:
-                ws_shape, wtr = cached
-            else:
-                wq = weight_q if weight_q is not None else quantize_weight_f32(weight, kind)
-                ws = ops.s2d_weight(wq.detach(), sd)
-                ws_shape, wtr = tuple(ws.shape), ops.pack_conv_weight_bf16x3(ws, "sign")   # zeros stay zeros
-            k2 = ws_shape[2]
-            # a nibble-plane epilogue maps output rows with the kernel's own (Hs - k2 + 1, Ws - k2 + 1) geometry: when
-            # the space-to-depth rounding added pixels, take threshold bits, crop, and expand afterwards
-            nib_epi = epi if isinstance(epi, ops.NibEpilogue) else None
-            if nib_epi is not None and (Hs - k2 + 1 != Ho or Ws - k2 + 1 != Wo):
-                epi = (nib_epi.alpha, nib_epi.beta)
-            y2 = ops.float_conv2d(None, torch.empty(ws_shape, device="meta"), "sign", bias, 1, 0, 1,
-                                  weight_triples=wtr, pixels=px, in_shape=(N, C * sd * sd, Hs, Ws), epi=epi)
-            H2, W2 = Hs - k2 + 1, Ws - k2 + 1
-            if epi is not None:
-                if H2 != Ho or W2 != Wo:   # drop the pixels the space-to-depth rounding added
-                    sg = y2.sign.view(N, H2, W2, -1)[:, :Ho, :Wo, :].contiguous().view(N * Ho * Wo, -1)
-                    y2 = ops.BitPlanes(sign=sg, rows=N * Ho * Wo, K=y2.K)
-                if nib_epi is not None and isinstance(y2, ops.BitPlanes):
-                    y2 = ops.bits_to_nib_pad(y2, N, Ho, Wo, nib_epi.out_halo, ld=ops.pixel_ld_nib(y2.K))
-                return y2, (N, int(weight.shape[0]), Ho, Wo)
-            if H2 != Ho or W2 != Wo:   # drop the pixels the space-to-depth rounding added
-                y2 = y2.view(N, H2, W2, -1)[:, :Ho, :Wo, :].contiguous()
-        else:
-            wt = weight_triples_fn("plain") if weight_triples_fn is not None else None
-            y2 = ops.float_conv2d(input, weight_q if weight_q is not None else weight, kind, bias, stride, padding,
-                                  dilation, weight_triples=wt, epi=epi)
-            if epi is not None:
-                return y2, (N, int(weight.shape[0]), Ho, Wo)
-        return nchw_result(y2, input, N, Ho, Wo, weight.shape[0])
+        # real-valued activation (first layer): split operands on the matrix cores, on the first rung of the ladder that takes it
+        y2, shape = first_layer_conv_routes(input, weight, bias, stride, padding, dilation, kind, epi=epi, weight_q=weight_q,
+                                            cache=weight_triples_fn, rungs=("first3x3", "first_direct", "s2d", "plain"))
+        return (y2, shape) if epi is not None else nchw_result(y2, input, shape[0], shape[2], shape[3], shape[1])
     if epi is not None:
         raise ValueError("the threshold-bit epilogue needs a device fp32 NCHW input, groups == 1 and zero padding")
     wq = weight_q if weight_q is not None else quantize_weight_f32(weight, kind)

@@ -684,53 +684,23 @@ class FusedConvPoolBnSign(torch.nn.Module):
         else:
             if not (isinstance(x, torch.Tensor) and x.is_cuda):
                 raise TypeError("FusedConvPoolBnSign runs on a HIP device only (use the un-fused modules on CPU)")
-            planes = shape = None
+            if nib_out and not pooled:
+                epi = ops.NibEpilogue(epi[0], epi[1], self.out_nib_halo)
+            geom = (conv.stride, conv.padding, conv.dilation)
             if self.kind == "xnor":
-                planes, shape = self._xnor_real_input(x, epi, nib_out and not pooled)
-                wp = None
+                planes, shape = self._xnor_real_input(x, epi)
             else:
                 wp = conv._eval_planes(lambda _w2: ops.pack_conv_weight_nib(conv.weight.detach(), self.kind), key="conv_nib")
-            if planes is not None:
-                pass
-            elif (self.kind in ("binary", "ternary") and x.dim() == 4 and x.dtype == torch.float32 and conv.binary_input is False
-                    and conv.groups == 1 and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)
-                    and ops.first3x3_applicable(conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride, conv.padding,
-                                                conv.dilation)):
-                # VGG-style first layer (3 -> 64, 3 x 3): one pass from the fp32 image to threshold bits / the next conv's nibble
-                # plane (csrc/conv_first3x3.hip) — the same kernel, hence the same accumulators, as the module-by-module fp32 result
-                N, C, H, W = (int(v) for v in x.shape)
-                e2 = ops.NibEpilogue(epi[0], epi[1], (1, 1)) if (nib_out and not pooled and tuple(self.out_nib_halo) == (1, 1)) else (epi[0], epi[1])
-                planes = ops.conv_first3x3(x, conv._conv_triples("first3x3"), conv.out_channels, conv.bias, epi=e2)
-                shape = (N, conv.out_channels, H, W)
-                if isinstance(planes, ops.NibPlanes):
-                    return packed.PackedActivation(None, shape, nib=planes, halo=(1, 1))
-                if planes is not None and nib_out and not pooled:
-                    planes = ops.bits_to_nib_pad(planes, N, H, W, self.out_nib_halo, ld=ops.pixel_ld_nib(planes.K))
-            elif (DIRECT_FIRST_LAYER and x.dim() == 4 and x.dtype == torch.float32 and conv.binary_input is False
-                    and (not nib_out or pooled or tuple(self.out_nib_halo) == (1, 1))
-                    and ops.direct_first_layer_applicable(conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride,
-                                                          conv.padding, conv.dilation)):
-                # real-valued 3x3 / stride-1 / padding-1 first layer: direct kernel on the padded bf16-triple plane
-                N, C, H, W = (int(v) for v in x.shape)
-                terms = ops.direct_first_layer_terms(C)               # fp16 pair pixels (two taps per MFMA), or exact bf16 triples
-                px, _ = ops.s2d_triple_pack(x, 1, 1, terms=terms)
-                wtr = conv._conv_triples("plain", terms=terms)
-                e2 = ops.NibEpilogue(epi[0], epi[1], (1, 1)) if (nib_out and not pooled) else epi
-                planes = ops.conv3x3_direct_nib(px, N, C, H, W, wtr, conv.bias, e2)
-                shape = (N, conv.out_channels, H, W)
-                if isinstance(planes, ops.NibPlanes):
-                    return packed.PackedActivation(None, shape, nib=planes, halo=(1, 1))
-            elif nib_out and not pooled:
-                if (D2S_FIRST_LAYER and x.dim() == 4 and x.dtype == torch.float32 and conv.binary_input is False
-                        and ops.d2s_first_layer_applicable(conv.in_channels, conv.out_channels, conv.kernel_size,
-                                                           conv.stride, conv.padding, conv.dilation, x.shape[2], x.shape[3])):
-                    return self._first_layer_d2s(x, epi)
-                epi = ops.NibEpilogue(epi[0], epi[1], self.out_nib_halo)
-            if planes is None:
-                planes, shape = _fused.quant_conv2d_forward(
-                    x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups, self.kind,
-                    weight_q=conv.weight, weight_planes=wp, binary_input=conv.binary_input,
-                    padding_mode=conv.padding_mode, weight_triples_fn=conv._conv_triples, epi=epi)
+                out = None          # real-valued first layer: the rungs that exist for fused stacks only, then the conv's own ladder
+                if (x.dim() == 4 and x.dtype == torch.float32 and conv.binary_input is False and conv.groups == 1
+                        and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)):
+                    out = _fused.first_layer_conv_routes(x, conv.weight, conv.bias, *geom, self.kind, epi=epi, cache=conv._conv_triples,
+                                                         rungs=("first3x3", "direct3x3", "d2s"), pooled=pooled)
+                if out is None:
+                    out = _fused.quant_conv2d_forward(
+                        x, conv.weight, conv.bias, *geom, conv.groups, self.kind, weight_q=conv.weight, weight_planes=wp,
+                        binary_input=conv.binary_input, padding_mode=conv.padding_mode, weight_triples_fn=conv._conv_triples, epi=epi)
+                planes, shape = out
         if isinstance(planes, ops.NibPlanes):
             return packed.PackedActivation(None, shape, nib=planes, halo=self.out_nib_halo)
         N, Cout, Ho, Wo = shape
@@ -743,60 +713,22 @@ class FusedConvPoolBnSign(torch.nn.Module):
         return act.flatten_hwc() if self.flatten_hwc else act
 
 
-    def _xnor_real_input(self, x, epi, nib_out: bool):
+    def _xnor_real_input(self, x, epi):
         """XNORConv2d on a device tensor inside a fused stack: a +-1 tensor (tagged / detected) takes the per-tap scaled conv, a
-        real-valued one (the first layer) the real x real conv on six-term bf16 planes, both with the threshold epilogue."""
+        real-valued one (the first layer) the real x real rungs of the first-layer ladder, both with the threshold epilogue."""
         from ..functions import _fused
         conv = self.conv
-        N, C, H, W = (int(v) for v in x.shape)
-        kh, kw = conv.kernel_size
-        Ho, Wo = ops.conv_out_hw(H, W, kh, kw, conv.stride, conv.padding, conv.dilation)
-        shape = (N, conv.out_channels, Ho, Wo)
-        e2 = ops.NibEpilogue(epi[0], epi[1], self.out_nib_halo) if nib_out else (epi[0], epi[1])
+        geom = (conv.stride, conv.padding, conv.dilation)
         known = True if packed.lookup(x, packed.NHWC) is not None else conv.binary_input
-        out = None
         if known is not False:
-            out = _fused.xnor_conv2d_forward(x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation,
-                                             binary_input=known, planes=conv._taps_planes(), epi=e2)
-        if out is not None:
-            return out[0], shape
-        # the op quantises the eval image AGAIN (sign(w) * mean|w| of values that are already +-alpha: the fp32 mean of n equal
-        # numbers is not that number to the last bit), like upstream and like the layer's own forward: same image, same bits
-        y = None
-        if ops.first_direct_applicable(C, (kh, kw), conv.stride, conv.padding, conv.dilation):
-            fw = conv._eval_planes(lambda _w2: ops.pack_first_layer_weight(ops.xnor_weight(conv.weight.detach(), 2)[0],
-                                                                           conv.stride[0], real=True), key="first_direct_real")
-            y = ops.conv_first_direct(x, fw, conv.bias, conv.stride, conv.padding, epi=(epi[0], epi[1]))
-            if y is not None and nib_out:
-                y = ops.bits_to_nib_pad(y, N, Ho, Wo, self.out_nib_halo, ld=ops.pixel_ld_nib(y.K))
-        if y is None:
-            wt = conv._eval_planes(lambda _w2: ops.pack_conv_weight_bf16x6(ops.xnor_weight(conv.weight.detach(), 2)[0]),
-                                   key="conv_bf16x6")
-            y = ops.real_conv2d(x, conv.weight.detach(), conv.bias, conv.stride, conv.padding, conv.dilation, weight_planes=wt, epi=e2)
-        if y is None:
+            out = _fused.xnor_conv2d_forward(x, conv.weight, conv.bias, *geom, binary_input=known, planes=conv._taps_planes(), epi=epi)
+            if out is not None:
+                N, _, H, W = (int(v) for v in x.shape)
+                return out[0], (N, conv.out_channels) + ops.conv_out_hw(H, W, *conv.kernel_size, *geom)
+        out = _fused.first_layer_conv_routes(x, conv.weight, conv.bias, *geom, "xnor", epi=epi, cache=conv._conv_triples)
+        if out is None:
             raise ValueError("XNOR conv outside the implicit kernel's limits")
-        return y, shape
-
-    def _first_layer_d2s(self, x, affine):
-        """Real-valued 3x3 / stride-1 / padding-1 first layer in its 2x2 output-blocked form (ops.d2s_first_layer_weight):
-        space-to-depth(2) bf16-triple gather of the padded image, 2x2-tap conv with 4*Cout columns on the 256-wide tiles,
-        depth-to-space in the nibble epilogue.  Same products as the direct form, a quarter of the gathered bytes
-        (VGG-16 conv1 at batch 256: 550 -> 290 us)."""
-        conv = self.conv
-        N, C, H, W = (int(v) for v in x.shape)
-        Cout = conv.out_channels
-
-        def build(_w2):
-            ws = ops.s2d_weight(ops.d2s_first_layer_weight(conv.weight.detach()), 2)        # [4*Cout, 4*C, 2, 2]
-            return tuple(ws.shape), ops.pack_conv_weight_bf16x3(ws, "sign")                  # zeros stay zeros
-        ws_shape, wtr = conv._eval_planes(build, key=f"conv_split{ops.split_terms()}_d2s")
-        px, (Hs, Ws) = ops.s2d_triple_pack(x, 2, 1)
-        alpha, beta = (t.repeat(4) for t in affine)
-        bias = conv.bias.detach().repeat(4) if conv.bias is not None else None
-        epi = ops.NibEpilogue(alpha, beta, self.out_nib_halo, d2s_cout=Cout)
-        nib = ops.float_conv2d(None, torch.empty(ws_shape, device="meta"), "sign", bias, 1, 0, 1, weight_triples=wtr,
-                               pixels=px, in_shape=(N, 4 * C, Hs, Ws), epi=epi)
-        return packed.PackedActivation(None, (N, Cout, H, W), nib=nib, halo=self.out_nib_halo)
+        return out
 
 
 #: real-valued 3x3 / stride-1 / padding-1 first layers of fused stacks run in the 2x2 output-blocked form

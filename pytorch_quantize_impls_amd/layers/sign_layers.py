@@ -157,23 +157,14 @@ class _SignConv2d(EvalSwapMixin, torch.nn.Conv2d, QLayer):
         return self._op.apply(self.weight)
 
     def _conv_triples(self, form, terms=None):
-        """Cached split image (bf16 triples / fp16 pairs, ops.FLOAT_SPLIT or ``terms``) of the eval-mode (already quantised)
-        weight for real-valued inputs: 'plain' -> TriplePlanes; 's2d' -> (transformed weight shape, TriplePlanes) for the
-        space-to-depth form."""
-        ops = _fused.ops
-        if form == "first3x3":         # MFMA row fragments of the one-pass 3 x 3 first-layer kernel (ops.pack_first3x3_weight)
-            return self._eval_planes(lambda _w2: ops.pack_first3x3_weight(self.weight.detach()), key="first3x3")
-        if form == "first_direct":     # fragment-ordered fp16 weight of the direct first-layer kernel (ops.pack_first_layer_weight)
-            return self._eval_planes(lambda _w2: ops.pack_first_layer_weight(self.weight.detach(), self.stride[0]), key="first_direct")
-        terms = ops.split_terms(terms)
-        if form == "plain":
-            return self._eval_planes(lambda _w2: ops.pack_conv_weight_bf16x3(self.weight.detach(), self.kind, terms=terms),
-                                     key=f"conv_split{terms}")
-
-        def build(_w2):
-            ws = ops.s2d_weight(self.weight.detach(), self.stride[0])
-            return tuple(ws.shape), ops.pack_conv_weight_bf16x3(ws, "sign", terms=terms)
-        return self._eval_planes(build, key=f"conv_split{terms}_s2d")
+        """Cached operand of the eval-mode (already quantised) weight for rung ``form`` of the first-layer ladder on real-valued
+        inputs (_fused.first_layer_weight_planes); the split images ('plain', 's2d', 'd2s') under ops.FLOAT_SPLIT or ``terms``."""
+        key = form
+        if form in ("plain", "s2d", "d2s"):
+            terms = _fused.ops.split_terms(terms)
+            key = f"conv_split{terms}" + ("" if form == "plain" else "_" + form)
+        return self._eval_planes(lambda _w2: _fused.first_layer_weight_planes(form, self.weight.detach(), self.kind, self.stride[0], terms),
+                                 key=key)
 
     def _half_forward(self, input):
         """bf16 / fp16 device activation (``_fused.half_route``) that is tagged, hinted or detected as +-1: the implicit-GEMM conv

@@ -89,6 +89,15 @@ class XNORConv2d(EvalSwapMixin, torch.nn.Conv2d, QLayer):
         return self._eval_planes(lambda _w2: (ops.pack_conv_weight_nib(self.weight.detach(), "sign", cw=cw),
                                               ops.xnor_tap_prep(self.weight)), key="conv_taps")
 
+    def _conv_triples(self, form, terms=None):
+        """Cached operand of the real weight image for rung ``form`` ('first_direct_real' / 'bf16x6') of the first-layer ladder.
+        The op quantises the eval image AGAIN (sign(w) * mean|w| of values that are already +-alpha: the fp32 mean of n equal
+        numbers is not that number to the last bit), like upstream and like the layer's own forward: same image, same bits."""
+        ops = _fused.ops
+        return self._eval_planes(lambda _w2: _fused.first_layer_weight_planes(form, ops.xnor_weight(self.weight.detach(), 2)[0], "xnor",
+                                                                              self.stride[0]),
+                                 key="conv_bf16x6" if form == "bf16x6" else form)
+
     @property
     def _qt_can_defer(self) -> bool:
         """The fused / deferred inference chain runs the per-tap scaled conv: one alpha per filter tap (dim = [0, 1])."""

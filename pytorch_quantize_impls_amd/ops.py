@@ -159,6 +159,15 @@ class NibEpilogue:
     thr: Optional[torch.Tensor] = None      # integer_thresholds(...): exact one-compare form for +-1 / 0 operands
 
 
+def epilogue_affine(epi, Cout: Optional[int] = None, dev=None):
+    """(alpha, beta, thr) of a threshold epilogue in either form, a NibEpilogue or the tuple (alpha, beta[, thr]); with ``Cout``
+    alpha and beta are checked like a bias (Cout entries on ``dev``; fp32, a half vector is upcast exactly) and named in the
+    error — thr by the kernels that read it."""
+    nib = isinstance(epi, NibEpilogue)
+    a, b, t = (epi.alpha, epi.beta, epi.thr) if nib else (epi[0], epi[1], epi[2] if len(epi) > 2 else None)
+    return (a, b, t) if Cout is None else (_check_bias(a, Cout, dev, "alpha"), _check_bias(b, Cout, dev, "beta"), t)
+
+
 def _conv_implicit(elem: int, pixels_words: torch.Tensor, N, H, W, Cw, kh, kw, geom, wmat: torch.Tensor,
                    ldw_words: int, bias, scale: float, scale_dev, Cout: int, epi=None, in_halo=(0, 0), out_dtype=None):
     """qt_conv2d_implicit; returns None if the shape is outside its limits (caller falls back).
@@ -244,7 +253,7 @@ def _conv_implicit(elem: int, pixels_words: torch.Tensor, N, H, W, Cw, kh, kw, g
     if isinstance(epi, NibEpilogue):
         if hy or hx:
             raise ValueError("input halos are passed as a physically padded image for nibble planes")
-        alpha, beta = _check_bias(epi.alpha, Cout, dev), _check_bias(epi.beta, Cout, dev)
+        alpha, beta, thr = epilogue_affine(epi, Cout, dev)
         ohy, ohx = (int(v) for v in epi.out_halo)
         d2s = int(epi.d2s_cout)
         if d2s and (d2s % 32 or Cout != 4 * d2s):
@@ -254,7 +263,7 @@ def _conv_implicit(elem: int, pixels_words: torch.Tensor, N, H, W, Cw, kh, kw, g
         rows = N * (zs * Ho + 2 * ohy) * (zs * Wo + 2 * ohx)
         plane = torch.empty((rows, ldn), dtype=torch.int32, device=dev)     # the launch writes every word, border included
         with _on(dev):
-            thr = _check_bias(epi.thr, Cout, dev) if (epi.thr is not None and elem < 2) else None
+            thr = _check_bias(thr, Cout, dev) if elem < 2 else None
             _lib.call("qt_conv2d_implicit_nib", *head, _p(alpha), _p(beta), _p(thr), _p(plane), I(ldn), I(Cout), I(ohy),
                       I(ohx), I(d2s), int(_cfg("CONV_FLAGS")), _stream(dev))
         return NibPlanes(words=plane, rows=rows, K=Cpix)
@@ -268,13 +277,11 @@ def _conv_implicit(elem: int, pixels_words: torch.Tensor, N, H, W, Cw, kh, kw, g
                       _stream(dev))
         return y
     if epi is not None:
-        alpha, beta = (_require(t, nm).contiguous() for t, nm in zip(epi[:2], ("alpha", "beta")))
-        thr = _check_bias(epi[2], Cout, dev) if (len(epi) > 2 and epi[2] is not None and elem < 2) else None
-        if alpha.numel() != Cout or beta.numel() != Cout:
-            raise ValueError(f"alpha/beta must have {Cout} entries")
+        alpha, beta, thr = epilogue_affine(epi, Cout, dev)
         ldb = packed_ld(Cout)
         plane = torch.empty((M, ldb), dtype=torch.int32, device=dev)   # the kernel writes every word incl. the pad
         with _on(dev):
+            thr = _check_bias(thr, Cout, dev) if elem < 2 else None
             _lib.call("qt_conv2d_implicit_bits", *head, _p(alpha), _p(beta), _p(thr), _p(plane), I(ldb), I(Cout),
                       int(_cfg("CONV_FLAGS")), _stream(dev))
         return BitPlanes(sign=plane, rows=M, K=Cout)
@@ -775,14 +782,14 @@ def is_pm1(x: torch.Tensor) -> bool:
 # packed GEMMs
 # ----------------------------------------------------------------------------------------------
 
-def _check_bias(bias, N, device):
+def _check_bias(bias, N, device, name: str = "bias"):
     if bias is None:
         return None
     if isinstance(bias, torch.Tensor) and bias.dtype in HALF_DTYPES:
         bias = bias.detach().float()            # the epilogues add the bias in fp32 (a half value is exact there)
-    bias = _require(bias, "bias").contiguous()
+    bias = _require(bias, name).contiguous()
     if bias.numel() != N or bias.device != device:
-        raise ValueError("bias must be a length-N fp32 tensor on the same device")
+        raise ValueError(f"{name} must be a length-N fp32 tensor on the same device (N = {N})")
     return bias
 
 
@@ -1300,6 +1307,23 @@ def pack_conv_weight_codes(weight: torch.Tensor, ternary: bool = False) -> CodeP
     return CodePlanes(codes=codes, rows=Cout, K=kbytes)
 
 
+def _im2col_chunks(words: torch.Tensor, N, H, W, Cw, kh, kw, geom, ldA: int, M: int, dtype, gemm) -> None:
+    """The explicit form of a conv (A/B and fallback of the implicit GEMM): packed-domain im2col of the NHWC plane ``words`` into a
+    [rows, ldA words] matrix viewed as ``dtype``, at most IM2COL_MAX_BYTES of it at a time; ``gemm(A, m0)`` contracts the rows
+    [m0, m0 + len(A)) of the result."""
+    (sh, sw), (ph, pw), (dh, dw) = geom
+    dev = words.device
+    rows_per_chunk = max(1, min(M, IM2COL_MAX_BYTES // (ldA * 4)))
+    A = torch.empty((rows_per_chunk, ldA), dtype=torch.int32, device=dev).view(dtype)
+    I = int
+    for m0 in range(0, M, rows_per_chunk):
+        cnt = min(rows_per_chunk, M - m0)
+        with _on(dev):
+            _lib.call("qt_im2col_words", _p(words), I(N), I(H), I(W), I(Cw), I(kh), I(kw), I(sh), I(sw), I(ph), I(pw), I(dh), I(dw),
+                      _p(A), I(ldA), I(m0), I(cnt), _stream(dev))
+            gemm(A[:cnt], m0)
+
+
 def conv2d_codes(pixels: CodePlanes, in_shape, wplanes: CodePlanes, kernel_hw, scale: float, bias=None,
                  stride=1, padding=0, dilation=1, scale_dev=None, max_abs_code: int = 127, epi=None,
                  in_halo=(0, 0)):
@@ -1367,16 +1391,9 @@ def conv2d_codes(pixels: CodePlanes, in_shape, wplanes: CodePlanes, kernel_hw, s
     if epi is not None:
         raise ValueError("the code epilogue exists on the implicit-GEMM conv kernel only (shape outside its limits)")
     y = torch.empty((M, Cout), dtype=torch.float32, device=dev)
-    rows_per_chunk = max(1, min(M, IM2COL_MAX_BYTES // (ldA * 4)))
-    A = torch.empty((rows_per_chunk, ldA * 4), dtype=torch.int8, device=dev)
-    I = int
-    for m0 in range(0, M, rows_per_chunk):
-        cnt = min(rows_per_chunk, M - m0)
-        with _on(dev):
-            _lib.call("qt_im2col_words", _p(pixels.codes), I(N), I(H), I(W), I(Cw), I(kh), I(kw), I(sh),
-                      I(sw), I(ph), I(pw), I(dh), I(dw), _p(A), I(ldA), I(m0), I(cnt), _stream(dev))
-        i8_gemm(CodePlanes(codes=A[:cnt], rows=cnt, K=wplanes.K), wplanes, scale, bias, out=y[m0:m0 + cnt],
-                scale_dev=scale_dev, max_abs_code=max_abs_code)
+    _im2col_chunks(pixels.codes, N, H, W, Cw, kh, kw, ((sh, sw), (ph, pw), (dh, dw)), ldA, M, torch.int8,
+                   lambda A, m0: i8_gemm(CodePlanes(codes=A, rows=len(A), K=wplanes.K), wplanes, scale, bias, out=y[m0:m0 + len(A)],
+                                         scale_dev=scale_dev, max_abs_code=max_abs_code))
     return y
 
 
@@ -1495,8 +1512,7 @@ def conv3x3_direct_nib(pixels, N: int, C: int, H: int, W: int, wplanes, bias, ep
         raise ValueError("direct conv expects the [N, H+2, W+2] halo plane of the activation")
     dev = words.device
     nib_out = isinstance(epi, NibEpilogue)
-    alpha, beta = (epi.alpha, epi.beta) if nib_out else epi[:2]
-    alpha, beta, bias = _check_bias(alpha, Cout, dev), _check_bias(beta, Cout, dev), _check_bias(bias, Cout, dev)
+    (alpha, beta, _), bias = epilogue_affine(epi, Cout, dev), _check_bias(bias, Cout, dev)
     if nib_out:
         ldo = pixel_ld_nib(Cout)
         out = torch.empty((N * (H + 2) * (W + 2), ldo), dtype=torch.int32, device=dev)
@@ -1614,15 +1630,8 @@ def conv2d_nib(pixels: NibPlanes, in_shape, wplanes: NibPlanes, kernel_hw, bias=
     if epi is not None:
         raise ValueError("the threshold-bit epilogue needs the implicit-GEMM conv (shape outside its limits)")
     y = torch.empty((M, Cout), dtype=_half_out(out_dtype) or torch.float32, device=dev)
-    rows_per_chunk = max(1, min(M, IM2COL_MAX_BYTES // (ldA * 4)))
-    A = torch.empty((rows_per_chunk, ldA), dtype=torch.int32, device=dev)
-    I = int
-    for m0 in range(0, M, rows_per_chunk):
-        cnt = min(rows_per_chunk, M - m0)
-        with _on(dev):
-            _lib.call("qt_im2col_words", _p(pixels.words), I(N), I(H), I(W), I(Cw), I(kh), I(kw), I(sh),
-                      I(sw), I(ph), I(pw), I(dh), I(dw), _p(A), I(ldA), I(m0), I(cnt), _stream(dev))
-        nib_gemm(NibPlanes(words=A[:cnt], rows=cnt, K=wplanes.K), wplanes, bias, out=y[m0:m0 + cnt])
+    _im2col_chunks(pixels.words, N, H, W, Cw, kh, kw, ((sh, sw), (ph, pw), (dh, dw)), ldA, M, torch.int32,
+                   lambda A, m0: nib_gemm(NibPlanes(words=A, rows=len(A), K=wplanes.K), wplanes, bias, out=y[m0:m0 + len(A)]))
     return y
 
 
@@ -1698,7 +1707,7 @@ def _conv_taps(elem: int, pixels_words: torch.Tensor, N, H, W, Cw, kh, kw, geom,
     if isinstance(epi, NibEpilogue):
         if epi.d2s_cout:
             raise ValueError("the depth-to-space epilogue does not exist for per-tap scaled convs")
-        alpha, beta = _check_bias(epi.alpha, Cout, dev), _check_bias(epi.beta, Cout, dev)
+        alpha, beta, _ = epilogue_affine(epi, Cout, dev)
         ohy, ohx = (int(v) for v in epi.out_halo)
         ldn = pixel_ld_nib(Cout)
         rows = N * (Ho + 2 * ohy) * (Wo + 2 * ohx)
@@ -1708,7 +1717,7 @@ def _conv_taps(elem: int, pixels_words: torch.Tensor, N, H, W, Cw, kh, kw, geom,
                       _stream(dev))
         return NibPlanes(words=plane, rows=rows, K=Cout)
     if epi is not None:
-        alpha, beta = _check_bias(epi[0], Cout, dev), _check_bias(epi[1], Cout, dev)
+        alpha, beta, _ = epilogue_affine(epi, Cout, dev)
         ldb = packed_ld(Cout)
         plane = torch.empty((M, ldb), dtype=torch.int32, device=dev)
         with _on(dev):
@@ -2589,23 +2598,19 @@ def float_conv2d(x: Optional[torch.Tensor], weight: torch.Tensor, kind: str, bia
     if epi is not None:
         raise ValueError("the threshold-bit epilogue needs the implicit-GEMM conv (shape outside its limits)")
     y = torch.empty((M, Cout), dtype=torch.float32, device=dev)
-    rows_per_chunk = max(1, min(M, IM2COL_MAX_BYTES // (ldA * 4)))
-    A = torch.empty((rows_per_chunk, ldA * 2), dtype=torch.int16, device=dev)
     I = int
     kel = kh * kw * Cb // 2     # bf16 elements per im2col row actually carrying taps
-    for m0 in range(0, M, rows_per_chunk):
-        cnt = min(rows_per_chunk, M - m0)
-        with _on(dev):
-            _lib.call("qt_im2col_words", _p(px.data), I(N), I(H), I(W), I(Cw), I(kh), I(kw), I(sh), I(sw),
-                      I(ph), I(pw), I(dh), I(dw), _p(A), I(ldA), I(m0), I(cnt), _stream(dev))
-            if terms == 2:
-                _lib.call("qt_f16_gemm", _p(A), I(ldA), _p(wt.data), I(wt.ld_words), _p(bias), float(out_scale),
-                          _p(sdev), _p(y[m0:m0 + cnt]), I(Cout), I(cnt), I(Cout), I(kel), _stream(dev))
-            else:
-                plain = sdev is None and float(out_scale) == 1.0
-                _lib.call("qt_bf16_gemm", _p(A), I(ldA), _p(wt.data), I(wt.ld_words), _p(bias if plain else None),
-                          _p(y[m0:m0 + cnt]), I(Cout), I(cnt), I(Cout), I(kel), _stream(dev))
-    if terms != 2 and not (sdev is None and float(out_scale) == 1.0):
+    plain = sdev is None and float(out_scale) == 1.0
+
+    def gemm(A, m0):
+        if terms == 2:
+            _lib.call("qt_f16_gemm", _p(A), I(ldA), _p(wt.data), I(wt.ld_words), _p(bias), float(out_scale),
+                      _p(sdev), _p(y[m0:m0 + len(A)]), I(Cout), I(len(A)), I(Cout), I(kel), _stream(dev))
+        else:
+            _lib.call("qt_bf16_gemm", _p(A), I(ldA), _p(wt.data), I(wt.ld_words), _p(bias if plain else None),
+                      _p(y[m0:m0 + len(A)]), I(Cout), I(len(A)), I(Cout), I(kel), _stream(dev))
+    _im2col_chunks(px.data, N, H, W, Cw, kh, kw, ((sh, sw), (ph, pw), (dh, dw)), ldA, M, torch.int16, gemm)
+    if terms != 2 and not plain:
         y = y * (float(out_scale) if sdev is None else sdev * float(out_scale))
         if bias is not None:
             y = y + bias
@@ -3467,7 +3472,7 @@ def conv_first_direct(x: torch.Tensor, fw: FirstLayerWeights, bias=None, stride=
     head = (_p(x), sN, sC, sH, sW, N, C, H, W, kh, kw, s, ph, pw, int(fw.Cp), _p(fw.hi), _p(fw.lo), 1.0, _p(fw.scale_dev),
             int(fw.Cout), int(fw.Coutp), _p(bias))
     if epi is not None:
-        alpha, beta = _check_bias(epi[0], fw.Cout, dev), _check_bias(epi[1], fw.Cout, dev)
+        alpha, beta, _ = epilogue_affine(epi, fw.Cout, dev)
         ldb = packed_ld(fw.Cout)
         plane = torch.empty((N * Ho * Wo, ldb), dtype=torch.int32, device=dev)
         with _on(dev):
@@ -3522,8 +3527,7 @@ def conv_first3x3(x: torch.Tensor, wfrag: torch.Tensor, Cout: int, bias=None, ep
     nib = isinstance(epi, NibEpilogue)
     if nib and (tuple(epi.out_halo) != (1, 1) or epi.d2s_cout):
         return None
-    alpha, beta = (epi.alpha, epi.beta) if nib else epi[:2]
-    alpha, beta = _check_bias(alpha, Cout, dev), _check_bias(beta, Cout, dev)
+    alpha, beta, _ = epilogue_affine(epi, Cout, dev)
     if nib:
         out = torch.empty((N * (H + 2) * (W + 2), 8), dtype=torch.int32, device=dev)
         with _on(dev):
