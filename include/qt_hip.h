@@ -1167,6 +1167,17 @@ int qt_nib_gemm_variant(int variant, const uint32_t* Xn, int64_t ldxp, const uin
  *                           be reused at once; 960 floats per launch), not through a host-to-device copy.  How the
  *                           caller of a replayed `_dev` launch sets the next step's scalars without a synchronise.
  *                           Null dst / values with n > 0, n < 0: QT_ERR_INVALID_ARG; dst not 4-byte aligned: QT_ERR_ALIGNMENT.
+ *
+ * The `_dev_guard` entries are the `_dev` entries plus `skip`, one int32 of DEVICE memory read when the kernel runs: every
+ * workgroup reads *skip once before it touches any tensor and, if it is non-zero, returns without reading or writing p, the
+ * state or the plane.  With *skip == 0 they store the bits of the `_dev` entries (the same code).  `skip` is validated after
+ * `lr` / `coef`: null with n > 0 is QT_ERR_INVALID_ARG, not 4-byte aligned QT_ERR_ALIGNMENT; n == 0 is QT_OK.
+ *   qt_flags_or_i32 : *guard |= (any *flags[i] != 0).  `flags` is a HOST array of n DEVICE pointers to int32 flags; the pointers
+ *                     travel in the launch's argument block in chunks of qt_flags_chunk_capacity() (one launch per chunk, no
+ *                     device allocation, no host-to-device copy), so the array may be freed as soon as the call returns.  A
+ *                     guard that is already non-zero stays so.  Validated before anything is enqueued: n < 0, or n > 0 with a
+ *                     null `flags`, `guard` or flags[i]: QT_ERR_INVALID_ARG; a pointer that is not 4-byte aligned:
+ *                     QT_ERR_ALIGNMENT; n == 0: QT_OK whatever the pointers are.
  * ---------------------------------------------------------------------------------------- */
 typedef struct qt_optim_tensor {
     float* p;
@@ -1191,6 +1202,13 @@ int qt_optim_sgd_dev_f32(const qt_optim_tensor* table, int64_t n, const float* l
                          int nesterov, qt_stream_t stream);
 int qt_optim_adam_dev_f32(const qt_optim_tensor* table, int64_t n, const float* coef, float beta1, float one_minus_beta1,
                           float beta2, float one_minus_beta2, float eps, float weight_decay, qt_stream_t stream);
+int qt_optim_sgd_dev_guard_f32(const qt_optim_tensor* table, int64_t n, const float* lr, const int32_t* skip, float momentum,
+                               float weight_decay, int nesterov, qt_stream_t stream);
+int qt_optim_adam_dev_guard_f32(const qt_optim_tensor* table, int64_t n, const float* coef, const int32_t* skip, float beta1,
+                                float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float weight_decay,
+                                qt_stream_t stream);
+int qt_flags_chunk_capacity(void);
+int qt_flags_or_i32(const int32_t* const* flags, int64_t n, int32_t* guard, qt_stream_t stream);
 
 #ifdef __cplusplus
 }

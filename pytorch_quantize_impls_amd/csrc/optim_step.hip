@@ -29,8 +29,14 @@
 //     first slot (empty tensors are dropped, later chunks start anywhere) and the launch gets `coef` rebased to that.
 //     qt_optim_scalars_f32 is how the host gets them there between replays: a launch whose ARGUMENT BLOCK carries the values
 //     (up to 960 floats per launch), stream-ordered like any kernel, with no staging buffer for a later call to overwrite.
+//   * the `_dev_guard` entries (qt_optim_sgd_dev_guard_f32 / qt_optim_adam_dev_guard_f32) are the `_dev` entries behind one
+//     device word: every workgroup reads *skip once, before it touches a tensor, and leaves when it is non-zero — how a
+//     captured training step keeps parameters, state and planes untouched when one of its trusted route verdicts turned out
+//     wrong (utils.GraphedTrainStep(recover=True)).  Same body, so *skip == 0 stores the bits of the `_dev` entries.
+//     qt_flags_or_i32 folds the step's verdict flags into that word: the flag POINTERS travel by value, 448 per launch.
 //   * kernel-argument size: OptimChunk = 32 x 96 (descriptors) + 33 x 4 (unit prefix) + 32 x 4 (table indices) + 4 (n)
-//     + 4 (padding) = 3336 bytes; the largest rule (Adam from device memory) adds 32: 3368 of HIP's 4096 bytes.
+//     + 4 (padding) = 3336 bytes; the largest rule (Adam from device memory) adds 32 and the guard
+//     pointer 8: 3376 of HIP's 4096 bytes.
 #include "qt_common.h"
 #include "nib_quant.h"
 
@@ -246,7 +252,7 @@ __device__ __forceinline__ void plane_unit(const Rule& r, const typename Rule::S
 }
 
 template <class Rule>
-__global__ __launch_bounds__(256) void optim_step_kernel(const OptimChunk c, const Rule r) {
+__device__ __forceinline__ void optim_step_body(const OptimChunk& c, const Rule& r) {
     const int total = c.ustart[c.n];
     int ti = 0, have = -1;
     typename Rule::Step st{};
@@ -261,6 +267,19 @@ __global__ __launch_bounds__(256) void optim_step_kernel(const OptimChunk c, con
         if (t.kind != 0) plane_unit(r, st, t, b);
         else flat_unit(r, st, t, b);
     }
+}
+
+template <class Rule>
+__global__ __launch_bounds__(256) void optim_step_kernel(const OptimChunk c, const Rule r) {
+    optim_step_body(c, r);
+}
+
+// The guarded form (`_dev_guard` entries): one wave-uniform read of *skip before any tensor is touched; non-zero = the
+// whole workgroup leaves, so p, the state and the plane keep their bits.  With *skip == 0 it is the body above.
+template <class Rule>
+__global__ __launch_bounds__(256) void optim_step_guard_kernel(const OptimChunk c, const Rule r, const int32_t* skip) {
+    if (*skip != 0) return;
+    optim_step_body(c, r);
 }
 
 template <class Rule>
@@ -288,16 +307,29 @@ int64_t tensor_units(const qt_optim_tensor& t) {
     return (t.numel + FLAT_UNIT - 1) / FLAT_UNIT;
 }
 
+// The guard of a launch sequence is a TYPE, so that only the entries that take one instantiate the guarded kernel.
+struct NoGuard {};
+struct DevGuard { const int32_t* skip; };
+
 template <class Rule>
-int launch_chunk(const OptimChunk& c, const Rule& r, qt_stream_t stream) {
+void enqueue_chunk(const OptimChunk& c, const Rule& r, NoGuard, int grid, hipStream_t s) {
+    hipLaunchKernelGGL(optim_step_kernel<Rule>, dim3(grid), dim3(256), 0, s, c, r);
+}
+template <class Rule>
+void enqueue_chunk(const OptimChunk& c, const Rule& r, DevGuard g, int grid, hipStream_t s) {
+    hipLaunchKernelGGL(optim_step_guard_kernel<Rule>, dim3(grid), dim3(256), 0, s, c, r, g.skip);
+}
+
+template <class Rule, class Guard>
+int launch_chunk(const OptimChunk& c, const Rule& r, Guard g, qt_stream_t stream) {
     const int total = c.ustart[c.n];
     if (c.n == 0 || total == 0) return QT_OK;
-    hipLaunchKernelGGL(optim_step_kernel<Rule>, dim3(qt_stream_grid(total)), dim3(256), 0, (hipStream_t)stream, c, r);
+    enqueue_chunk(c, r, g, qt_stream_grid(total), (hipStream_t)stream);
     return qt_check_launch();
 }
 
-template <class Rule>
-int optim_step(const qt_optim_tensor* tab, int64_t n, const Rule& r, qt_stream_t stream) {
+template <class Rule, class Guard = NoGuard>
+int optim_step(const qt_optim_tensor* tab, int64_t n, const Rule& r, qt_stream_t stream, Guard skip = Guard{}) {
     if (n < 0 || (n > 0 && !tab)) return QT_ERR_INVALID_ARG;
     for (int64_t i = 0; i < n; ++i) {              // the whole table is checked before anything is enqueued
         const int rc = check_tensor<Rule>(tab[i]);
@@ -310,7 +342,7 @@ int optim_step(const qt_optim_tensor* tab, int64_t n, const Rule& r, qt_stream_t
         const int64_t units = tensor_units(tab[i]);
         if (units == 0) continue;                  // empty tensor
         if (c.n == QT_OPTIM_CHUNK || (int64_t)c.ustart[c.n] + units > INT32_MAX || (c.n > 0 && i - base > INT32_MAX)) {
-            const int rc = launch_chunk(c, r.at_base(base), stream);
+            const int rc = launch_chunk(c, r.at_base(base), skip, stream);
             if (rc != QT_OK) return rc;
             c.n = 0;
         }
@@ -327,7 +359,7 @@ int optim_step(const qt_optim_tensor* tab, int64_t n, const Rule& r, qt_stream_t
         c.ustart[c.n + 1] = c.ustart[c.n] + (int32_t)units;
         ++c.n;
     }
-    return launch_chunk(c, r.at_base(base), stream);
+    return launch_chunk(c, r.at_base(base), skip, stream);
 }
 
 #define QT_SCALARS_CHUNK 960               // 3840 bytes of values + pointer + count: below the 4096-byte argument limit
@@ -345,6 +377,26 @@ int check_scalars(const float* s, int64_t n) {
     if (n > 0 && !s) return QT_ERR_INVALID_ARG;
     if (reinterpret_cast<uintptr_t>(s) & 3u) return QT_ERR_ALIGNMENT;
     return QT_OK;
+}
+
+// the skip word of a `_dev_guard` entry: validated like the device scalars, after them
+int check_skip(const int32_t* skip) {
+    if (!skip) return QT_ERR_INVALID_ARG;
+    if (reinterpret_cast<uintptr_t>(skip) & 3u) return QT_ERR_ALIGNMENT;
+    return QT_OK;
+}
+
+#define QT_FLAGS_CHUNK 448                 // 3584 bytes of pointers + guard + count: below the 4096-byte argument limit
+struct FlagChunk {
+    const int32_t* f[QT_FLAGS_CHUNK];
+};
+
+// *guard |= any(*f[i] != 0): every lane ORs its flags, the workgroup votes, lane 0 stores (a plain vector store, and
+// only when there is something to raise: a guard that is already set is never cleared).
+__global__ __launch_bounds__(256) void flags_or_kernel(const FlagChunk c, int n, int32_t* guard) {
+    int any = 0;
+    for (int i = threadIdx.x; i < n; i += 256) any |= (*c.f[i] != 0);
+    if (__syncthreads_or(any) && threadIdx.x == 0) *guard = 1;
 }
 
 }  // namespace
@@ -396,6 +448,50 @@ int qt_optim_adam_dev_f32(const qt_optim_tensor* table, int64_t n, const float* 
     if (rc != QT_OK) return rc;
     return optim_step(table, n, AdamRule<CoefDevice>{{coef}, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay},
                       stream);
+}
+
+int qt_optim_sgd_dev_guard_f32(const qt_optim_tensor* table, int64_t n, const float* lr, const int32_t* skip, float momentum,
+                               float weight_decay, int nesterov, qt_stream_t stream) {
+    if (nesterov && momentum == 0.0f) return QT_ERR_INVALID_ARG;
+    if (n == 0) return QT_OK;
+    int rc = check_scalars(lr, n);
+    if (rc == QT_OK) rc = check_skip(skip);
+    if (rc != QT_OK) return rc;
+    if (momentum != 0.0f)
+        return optim_step(table, n, SgdRule<1, LrDevice>{{lr}, momentum, weight_decay, nesterov ? 1 : 0}, stream, DevGuard{skip});
+    return optim_step(table, n, SgdRule<0, LrDevice>{{lr}, 0.0f, weight_decay, 0}, stream, DevGuard{skip});
+}
+
+int qt_optim_adam_dev_guard_f32(const qt_optim_tensor* table, int64_t n, const float* coef, const int32_t* skip, float beta1,
+                                float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float weight_decay,
+                                qt_stream_t stream) {
+    if (n == 0) return QT_OK;
+    int rc = check_scalars(coef, n);
+    if (rc == QT_OK) rc = check_skip(skip);
+    if (rc != QT_OK) return rc;
+    return optim_step(table, n, AdamRule<CoefDevice>{{coef}, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay},
+                      stream, DevGuard{skip});
+}
+
+int qt_flags_chunk_capacity(void) { return QT_FLAGS_CHUNK; }
+
+int qt_flags_or_i32(const int32_t* const* flags, int64_t n, int32_t* guard, qt_stream_t stream) {
+    if (n < 0 || (n > 0 && (!flags || !guard))) return QT_ERR_INVALID_ARG;
+    if (n == 0) return QT_OK;
+    if (reinterpret_cast<uintptr_t>(guard) & 3u) return QT_ERR_ALIGNMENT;
+    for (int64_t i = 0; i < n; ++i) {              // every pointer is checked before anything is enqueued
+        if (!flags[i]) return QT_ERR_INVALID_ARG;
+        if (reinterpret_cast<uintptr_t>(flags[i]) & 3u) return QT_ERR_ALIGNMENT;
+    }
+    FlagChunk c{};                                 // the whole struct travels as the argument block
+    for (int64_t done = 0; done < n; done += QT_FLAGS_CHUNK) {
+        const int m = (int)(n - done < QT_FLAGS_CHUNK ? n - done : QT_FLAGS_CHUNK);
+        for (int i = 0; i < m; ++i) c.f[i] = flags[done + i];
+        hipLaunchKernelGGL(flags_or_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, c, m, guard);
+        const int rc = qt_check_launch();
+        if (rc != QT_OK) return rc;
+    }
+    return QT_OK;
 }
 
 }  // extern "C"

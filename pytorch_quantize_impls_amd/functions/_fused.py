@@ -200,6 +200,60 @@ def detect_scope(mode: Optional[str]):
         _detect_tls.mode = prev
 
 
+# ---- the flags of trusted verdicts, collected -------------------------------------------------------------------------------
+# In "remember" mode a trusted positive verdict arms an int32 device flag (ops.check_pm1, ops.pack_bf16_check, codes.overflow) that
+# poisons the layer's result when the verdict was wrong.  A caller that wants to KNOW (utils.GraphedTrainStep(recover=True): it
+# ORs them into the guard of its captured update) opens a sink; the three functions that hand such a flag out — detect_pm1,
+# detect_bf16_exact, codes_route: every poisoning site gets its flag from one of them (DESIGN.md lists the sites) — register it.
+_sink_tls = threading.local()
+
+
+class FlagSink:
+    """What ``flag_sink()`` yields: the registered flags in order of registration, each once (by identity).  It holds the tensors, so
+    a flag allocated inside a stream capture stays valid for a later launch of the same capture that reads it."""
+
+    def __init__(self):
+        self.flags, self._ids = [], set()
+
+    def add(self, flag) -> None:
+        if id(flag) not in self._ids:          # (the list keeps the tensor alive, so its id is not reused while it is in the set)
+            self._ids.add(id(flag))
+            self.flags.append(flag)
+
+    def __len__(self):
+        return len(self.flags)
+
+    def __iter__(self):
+        return iter(self.flags)
+
+
+@contextlib.contextmanager
+def flag_sink(sink: Optional[FlagSink] = None):
+    """``with flag_sink() as flags:`` — collects the device flag of every REMEMBERED positive verdict handed out inside, in this
+    thread and in the backward of the autograd Functions whose forward ran inside (functions.common.QtFunction carries the sink to
+    the engine's thread like the detect scope).  Sinks nest: a flag goes to the innermost one only.  ``sink``: re-open an existing
+    one (what QtFunction does).  No sink open: registering is a no-op."""
+    sink = FlagSink() if sink is None else sink
+    prev = getattr(_sink_tls, "sink", None)
+    _sink_tls.sink = sink
+    try:
+        yield sink
+    finally:
+        _sink_tls.sink = prev
+
+
+def current_flag_sink() -> Optional[FlagSink]:
+    return getattr(_sink_tls, "sink", None)
+
+
+def register_flag(flag):
+    """Hand a trusted verdict's device flag to the innermost open sink (if any); returns the flag."""
+    sink = getattr(_sink_tls, "sink", None)
+    if sink is not None and isinstance(flag, torch.Tensor):
+        sink.add(flag)
+    return flag
+
+
 _VERDICTS = {}     # id(weight tensor) -> (weak reference to it, {(question, shape): bool}); tensors compare element-wise, so
 #                    they cannot key a WeakKeyDictionary
 _VERDICTS_LOCK = threading.RLock()   # serving threads share the store; the weak-reference callback may fire inside any of them
@@ -281,7 +335,7 @@ def detect_pm1(input: torch.Tensor, weight: Optional[torch.Tensor]):
     ok, cached = _verdict(weight, ("pm1", tuple(input.shape[1:])), lambda: ops.is_pm1(input))
     _LAST.pm1 = (input.data_ptr(), tuple(input.shape), bool(ok))
     if ok and cached:
-        return True, ops.check_pm1(input)       # int32[1] on the device, non-zero = some element is not +-1; no sync
+        return True, register_flag(ops.check_pm1(input))   # int32[1] on the device, non-zero = some element is not +-1; no sync
     return ok, None
 
 
@@ -302,7 +356,7 @@ def detect_bf16_exact(input: torch.Tensor, weight: Optional[torch.Tensor]):
         return None, None
     if cached:
         res = ops.pack_bf16_check(input)          # no sync: the flag travels with the result
-        return (None, None) if res is None else (res[0], res[1])
+        return (None, None) if res is None else (res[0], register_flag(res[1]))
     return got[0][0], None
 
 
@@ -437,7 +491,7 @@ def codes_route(codes, weight: Optional[torch.Tensor]):
         return True, None
     ok, cached = _verdict(weight, ("codes", int(codes.K)), codes.usable)
     if ok and cached:
-        return True, codes.overflow
+        return True, register_flag(codes.overflow)
     return ok, None
 
 

@@ -3885,11 +3885,19 @@ def optim_write_scalars(dst: torch.Tensor, values) -> None:
         _lib.call("qt_optim_scalars_f32", _p(dst), _ct.addressof(host), n, _stream(dst.device))
 
 
+def _optim_skip_check(skip, dev) -> None:
+    if not isinstance(skip, torch.Tensor) or not skip.is_cuda:
+        raise TypeError("skip: the guard of a guarded training update is one int32 element in HIP device memory")
+    if skip.dtype != torch.int32 or skip.numel() != 1 or skip.device != dev:
+        raise ValueError(f"skip: expected one int32 element on {dev}, got {tuple(skip.shape)} {skip.dtype} on {skip.device}")
+
+
 def optim_step_sgd_dev(params, grads, momentum_buffers, lr_dev: torch.Tensor, *, momentum: float = 0.0, weight_decay: float = 0.0,
-                       nesterov: bool = False, clamps=None, planes=None) -> None:
+                       nesterov: bool = False, clamps=None, planes=None, skip: Optional[torch.Tensor] = None) -> None:
     """``optim_step_sgd`` with the learning rate read from ``lr_dev`` (one fp32 element on the parameters' device) when the kernel
     RUNS (qt_optim_sgd_dev_f32): the form a hipGraph can capture.  No first-step flag: the momentum buffers exist and a zeroed
-    buffer makes ``mu * 0 + g`` the first step's value."""
+    buffer makes ``mu * 0 + g`` the first step's value.  ``skip``: one int32 device element, read when the kernel runs
+    (qt_optim_sgd_dev_guard_f32): non-zero leaves every tensor and plane untouched, zero stores the bits of the unguarded call."""
     if not params:
         return
     use_mom = momentum != 0
@@ -3897,23 +3905,58 @@ def optim_step_sgd_dev(params, grads, momentum_buffers, lr_dev: torch.Tensor, *,
         raise ValueError("optim_step_sgd_dev: momentum needs the momentum buffers")
     tab, dev = _optim_table(params, grads, momentum_buffers if use_mom else None, None, clamps, planes)
     _optim_scalars_check(lr_dev, dev, 1, "lr_dev")
+    hp = (float(momentum), float(weight_decay), int(bool(nesterov)))
     with _on(dev):
-        _lib.call("qt_optim_sgd_dev_f32", _ct.addressof(tab), len(params), _p(lr_dev), float(momentum), float(weight_decay),
-                  int(bool(nesterov)), _stream(dev))
+        if skip is None:
+            _lib.call("qt_optim_sgd_dev_f32", _ct.addressof(tab), len(params), _p(lr_dev), *hp, _stream(dev))
+        else:
+            _optim_skip_check(skip, dev)
+            _lib.call("qt_optim_sgd_dev_guard_f32", _ct.addressof(tab), len(params), _p(lr_dev), _p(skip), *hp, _stream(dev))
 
 
 def optim_step_adam_dev(params, grads, exp_avgs, exp_avg_sqs, coef_dev: torch.Tensor, *, betas=(0.9, 0.999), eps: float = 1e-8,
-                        weight_decay: float = 0.0, clamps=None, planes=None) -> None:
+                        weight_decay: float = 0.0, clamps=None, planes=None, skip: Optional[torch.Tensor] = None) -> None:
     """``optim_step_adam`` with the bias corrections read from ``coef_dev`` (``2 * len(params)`` fp32 elements on the parameters'
-    device: ``adam_coefficients`` of tensor i at [2 i], [2 i + 1]) when the kernel RUNS (qt_optim_adam_dev_f32)."""
+    device: ``adam_coefficients`` of tensor i at [2 i], [2 i + 1]) when the kernel RUNS (qt_optim_adam_dev_f32).  ``skip``: as in
+    ``optim_step_sgd_dev`` (qt_optim_adam_dev_guard_f32)."""
     if not params:
         return
     b1, b2 = float(betas[0]), float(betas[1])
     tab, dev = _optim_table(params, grads, exp_avgs, exp_avg_sqs, clamps, planes)
     _optim_scalars_check(coef_dev, dev, 2 * len(params), "coef_dev")
+    hp = (b1, 1.0 - b1, b2, 1.0 - b2, float(eps), float(weight_decay))
     with _on(dev):
-        _lib.call("qt_optim_adam_dev_f32", _ct.addressof(tab), len(params), _p(coef_dev), b1, 1.0 - b1, b2, 1.0 - b2, float(eps),
-                  float(weight_decay), _stream(dev))
+        if skip is None:
+            _lib.call("qt_optim_adam_dev_f32", _ct.addressof(tab), len(params), _p(coef_dev), *hp, _stream(dev))
+        else:
+            _optim_skip_check(skip, dev)
+            _lib.call("qt_optim_adam_dev_guard_f32", _ct.addressof(tab), len(params), _p(coef_dev), _p(skip), *hp, _stream(dev))
+
+
+def flags_chunk_capacity() -> int:
+    """Flag pointers per launch of ``flags_or`` (they are forwarded by value in chunks of this many)."""
+    return int(_lib.load().qt_flags_chunk_capacity())
+
+
+def flags_or(flags, guard: torch.Tensor) -> None:
+    """``guard |= any(flag != 0 for flag in flags)`` on the current stream (qt_flags_or_i32): ``flags`` are int32 device tensors of
+    one element each (the verdict flags ``functions._fused.flag_sink`` collects), ``guard`` one int32 element on the same device.
+    The flag pointers travel in the launches' argument blocks: no allocation, no copy, no synchronise — capturable."""
+    if not isinstance(guard, torch.Tensor) or not guard.is_cuda:
+        raise TypeError("flags_or: guard is one int32 element in HIP device memory")
+    if guard.dtype != torch.int32 or guard.numel() != 1:
+        raise ValueError(f"flags_or: guard is one int32 element, got {tuple(guard.shape)} {guard.dtype}")
+    n = len(flags)
+    if n == 0:
+        return
+    for f in flags:
+        if not isinstance(f, torch.Tensor) or not f.is_cuda:
+            raise TypeError("flags_or: every flag is an int32 element in HIP device memory")
+        if f.dtype != torch.int32 or f.numel() != 1 or f.device != guard.device:
+            raise ValueError(f"flags_or: expected one int32 element on {guard.device}, got {tuple(f.shape)} {f.dtype} on {f.device}")
+    table = (_ct.c_void_p * n)(*(f.data_ptr() for f in flags))
+    with _on(guard.device):
+        _lib.call("qt_flags_or_i32", _ct.addressof(table), n, _p(guard), _stream(guard.device))
 
 
 def pack_weight_nib_into(weight: torch.Tensor, kind: str, planes: NibPlanes) -> None:

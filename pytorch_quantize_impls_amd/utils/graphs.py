@@ -268,11 +268,36 @@ class GraphedTrainStep:
       * One optimiser may serve several steps (a full and a tail batch shape): each has its own scalar block, all share the
         optimiser's state and plane buffers.
     Other optimiser types stay outside the graph (the form above); so do data-parallel steps: a model whose gradients a
-    ``GradientSynchronizer`` averages is refused, because the all-reduce runs between backward and the update."""
+    ``GradientSynchronizer`` averages is refused, because the all-reduce runs between backward and the update.
+
+    ``recover=True``: survive a wrong remembered verdict.  Training moves activations: a tensor that was +-1, in the int8 code
+    range or exact in bf16 when the step was captured may stop being so, and a replay then poisons that layer's result with NaN —
+    and with it every gradient, the update, the optimiser state and BatchNorm's running statistics (behind a BinaryConnect,
+    ``safeSign(NaN) = +1``, without the loss ever showing it).  With ``recover=True`` the graph ORs the device flags of every
+    trusted verdict of the step (``functions._fused.flag_sink``) into a guard word that its update launches read: raised, the
+    update is skipped on the device.  The host learns of it in ``settle()``, restores the module buffers from a snapshot the
+    graph took, runs the same batch eagerly in "verify" mode — which remembers the negative answer, so each (weight, question)
+    flips at most once — and captures a new graph.  After ``max_recaptures`` re-captures the step warns once and stays eager.
+
+      * ``step(x, t)`` settles the PREVIOUS call first (it needs that call's batch, which is still in the static buffers), then
+        replays.  That settle waits for the previous replay to finish before the next batch is even copied in: an armed step
+        gives up the run-ahead of the host over the device — the device idles while the host enqueues the next replay —
+        and pays for it on launch-bound nets (README, "Fused update", has the figures).  ``step.settle()`` settles the last call
+        now; it returns whether a recovery took place (``recoveries`` / ``recaptures`` count them).
+      * A recovered call equals the plain eager loop on that batch, and the re-capture puts buffers, gradients and the random
+        number generators back.  The REPLAYS of a model that draws random numbers (Dropout, stochastic quantisers) follow
+        torch's graph-safe generator, as with ``recover=False``: such a model is not bit-comparable to its eager loop anyway.
+      * ``p.grad`` and the returned loss are those of the batch only AFTER ``settle()``: until then they may be the poisoned
+        ones of a step that is about to be run again.  The returned tensor is owned by the step and survives a re-capture.
+      * Parameters, optimiser state and module buffers must not be touched from outside between a call and its settle.
+      * ``optimizer=None``: the caller's own optimiser runs right after the call, so every call settles before it returns —
+        one synchronise per call.
+      * A step in which no verdict is trusted (every input tagged by its quantiser) arms nothing: no OR launch, the unguarded
+        update, nothing to settle.
+    ``recover=False`` (default) is the step as it always was, launch for launch."""
 
     def __init__(self, model: torch.nn.Module, loss_fn, example_input: torch.Tensor, example_target: torch.Tensor,
-                 warmup: int = 3, optimizer=None):
-        from ..functions import _fused
+                 warmup: int = 3, optimizer=None, recover: bool = False, max_recaptures: int = 8):
         if optimizer is not None:
             from .data_parallel import is_synchronized
             from .optim import _FusedQuantOptimizer
@@ -285,31 +310,72 @@ class GraphedTrainStep:
                                    "opt.step())")
         if not example_input.is_cuda:
             raise TypeError("graph capture needs device tensors")
+        if recover and optimizer is not None and optimizer._post_clamp:
+            # their clamp() is arbitrary torch code inside the graph: nothing could make it depend on the guard
+            raise ValueError(f"GraphedTrainStep(recover=True): the captured update cannot skip the clamp() of "
+                             f"{sorted({type(m).__name__ for m in optimizer._post_clamp})}, which utils.clamp_plan cannot restate; "
+                             "keep the optimiser outside the graph (optimizer=None) or use recover=False")
         self.model, self.loss_fn, self.optimizer = model, loss_fn, optimizer
+        self.recover, self.max_recaptures = bool(recover), int(max_recaptures)
+        #: steps whose guard was raised and that were run again eagerly / graphs captured anew after one (``recover=True``)
+        self.recoveries = self.recaptures = 0
+        self._warmup = max(1, warmup)
         self._x, self._t = example_input.clone(), example_target.clone()
         self._stream = torch.cuda.Stream(device=example_input.device)
-        self._graph = torch.cuda.CUDAGraph()
         for p in model.parameters():
             if p.requires_grad and p.grad is None:
                 p.grad = torch.zeros_like(p)          # static gradient buffers: the captured backward accumulates into them
+        self._pending = self._armed = self._eager = False
+        if self.recover:
+            dev = example_input.device
+            self._guard = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._guard_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+            self._event = torch.cuda.Event()
+            self._buffers = list(model.buffers())
+            self._snapshot = [torch.empty_like(b) for b in self._buffers]
+            self._flags = self._out = None
+        self._capture_graph()
+
+    def _capture_graph(self):
+        """Warm-up and stream capture under "remember" (the constructor; with ``recover=True`` every re-capture as well)."""
+        from .. import ops
+        from ..functions import _fused
+        optimizer, dev = self.optimizer, self._x.device
+        self._graph = torch.cuda.CUDAGraph()
         self._capture, planes = None, contextlib.nullcontext()
         if optimizer is not None:
             # this graph's handle on the optimiser (its own scalar block; the optimiser may serve other graphs too): state exists,
             # raises for what a captured step cannot update
             self._capture = optimizer.prepare_capture()
             optimizer.refresh_planes(self._capture)   # the planes the captured forward reads: packed once, into the persistent buffers
-            self._stream.wait_stream(torch.cuda.current_stream(example_input.device))     # (packed on the caller's stream)
+            self._stream.wait_stream(torch.cuda.current_stream(dev))     # (packed on the caller's stream)
             planes = optimizer.capturing(self._capture)
         with _fused.detect_scope("remember"), planes:  # thread-local; the Functions carry the detect mode into their backward
             with torch.cuda.stream(self._stream):
-                for _ in range(max(1, warmup)):       # verdicts asked (and remembered), allocations and weight caches settle
-                    self._one()
-                torch.cuda.synchronize(example_input.device)
+                for _ in range(self._warmup):         # verdicts asked (and remembered), allocations and weight caches settle
+                    loss = self._one()
+                if self.recover and self._out is None:
+                    self._out = torch.empty_like(loss)     # what __call__ returns: owned by the step, not by one of its graphs
+                torch.cuda.synchronize(dev)
                 with _no_collection_inside(), torch.cuda.graph(self._graph, stream=self._stream):
-                    self._loss = self._one()
-                    if optimizer is not None:
-                        optimizer.captured_step(self._capture)
-            torch.cuda.synchronize(example_input.device)
+                    if not self.recover:
+                        self._loss = self._one()
+                        if optimizer is not None:
+                            optimizer.captured_step(self._capture)
+                    else:
+                        self._guard.zero_()
+                        if self._buffers:
+                            torch._foreach_copy_(self._snapshot, self._buffers)
+                        with _fused.flag_sink() as flags:
+                            loss = self._one()
+                        self._flags = flags           # the graph's last launches read them: they live as long as it does
+                        self._armed = len(flags) > 0
+                        if self._armed:
+                            ops.flags_or(flags.flags, self._guard)
+                        if optimizer is not None:     # no trusted verdict in the step: nothing to guard against
+                            optimizer.captured_step(self._capture, skip=self._guard if self._armed else None)
+                        self._out.copy_(loss)
+            torch.cuda.synchronize(dev)
 
     def _one(self):
         self.model.zero_grad(set_to_none=False)
@@ -321,11 +387,87 @@ class GraphedTrainStep:
         if x.shape != self._x.shape or x.dtype != self._x.dtype or target.shape != self._t.shape or target.dtype != self._t.dtype:
             raise ValueError(f"captured for input {tuple(self._x.shape)} {self._x.dtype} / target {tuple(self._t.shape)} "
                              f"{self._t.dtype}, got {tuple(x.shape)} {x.dtype} / {tuple(target.shape)} {target.dtype}")
+        if self.recover:
+            self.settle()                                   # the previous step may still need its batch: it is in _x / _t
         self._x.copy_(x)
         self._t.copy_(target)
+        if self._eager:
+            return self._eager_step()
         if self.optimizer is not None:
             self.optimizer.before_replay(self._capture)     # this step's scalars to the device, stale planes packed again
         self._graph.replay()
         if self.optimizer is not None:
             self.optimizer.after_replay(self._capture)      # version counters, plane records
-        return self._loss
+        if not self.recover:
+            return self._loss
+        if self._armed:
+            self._guard_host.copy_(self._guard, non_blocking=True)      # outside the graph, behind the replay on its stream
+            self._event.record()
+            self._pending = True
+            if self.optimizer is None:
+                self.settle()                               # the caller's optimiser runs next: it must not see poisoned gradients
+        return self._out
+
+    def _eager_step(self):
+        """The step as the plain loop runs it, in "verify" mode (a recovery; every call once the re-captures are used up)."""
+        from ..functions import _fused
+        with _fused.detect_scope("verify"):
+            loss = self._one()
+        if self.optimizer is not None:
+            self.optimizer.step()
+        self._out.copy_(loss)
+        return self._out
+
+    def settle(self) -> bool:
+        """``recover=True``: wait for the last call's guard.  Clear (or nothing pending): ``False``.  Raised — a remembered verdict
+        was wrong for that batch, the device skipped the update: restore the module buffers from the graph's snapshot, take the
+        optimiser's host bookkeeping back (``cancel_replay``), run the same batch eagerly in "verify" mode (which remembers the
+        negative answer), capture a new graph, and return ``True``.  ``recoveries`` / ``recaptures`` count."""
+        if not self._pending:
+            return False
+        self._pending = False
+        self._event.synchronize()
+        if int(self._guard_host[0]) == 0:
+            return False
+        self.recoveries += 1
+        with torch.no_grad():
+            if self._buffers:
+                torch._foreach_copy_(self._buffers, self._snapshot)
+        if self.optimizer is not None:
+            self.optimizer.cancel_replay(self._capture)
+        self._eager_step()                                  # the batch is still in the static input buffers
+        if self.recaptures >= self.max_recaptures:
+            import warnings
+            warnings.warn(f"GraphedTrainStep: {self.recaptures} re-captures used up (max_recaptures); the step stays eager from now on",
+                          RuntimeWarning, stacklevel=2)
+            self._eager, self._armed = True, False
+            self._graph = self._flags = self._capture = None
+        else:
+            self.recaptures += 1
+            self._recapture()
+        return True
+
+    def _recapture(self):
+        """A new graph under the verdicts as they are now.  Its warm-up runs forward and backward on the current batch: module
+        buffers, ``p.grad`` and the random-number state (host and device generators: Dropout, stochastic quantisers) are put back
+        afterwards, so the state is the eager step's.  Parameters and optimiser state are not written by a warm-up (it applies no
+        update); a model whose forward writes its own parameters is refused, not mis-trained."""
+        dev = self._x.device
+        torch.cuda.synchronize(dev)
+        rng = torch.get_rng_state(), torch.cuda.get_rng_state(dev)
+        params = [p for p in self.model.parameters() if p.grad is not None]
+        keep = [b.clone() for b in self._buffers], [p.grad.clone() for p in params]
+        versions = [p._version for p in self.model.parameters()]
+        self._graph = self._flags = None                    # the old graph and its memory pool go before the new capture
+        self._capture_graph()
+        if versions != [p._version for p in self.model.parameters()]:
+            raise RuntimeError("GraphedTrainStep(recover=True): the model's forward / backward wrote a parameter during the re-capture "
+                               "warm-up; the step cannot restore the eager state")
+        with torch.no_grad():
+            if self._buffers:
+                torch._foreach_copy_(self._buffers, keep[0])
+            if params:
+                torch._foreach_copy_([p.grad for p in params], keep[1])
+        torch.set_rng_state(rng[0])
+        torch.cuda.set_rng_state(rng[1], dev)
+        torch.cuda.synchronize(dev)

@@ -7,7 +7,7 @@ fold the layers' ``clamp()`` into the update (``clamp_plan``) and, for determini
 nibble plane of the new weight where the next training forward finds it (``weight._qt_train_planes``), so that forward does
 not read the fp32 weight again only to take its sign.
 
-Capture mode (``prepare_capture`` / ``captured_step`` / ``before_replay`` / ``after_replay``) is what ``utils.GraphedTrainStep``
+Capture mode (``prepare_capture`` / ``captured_step`` / ``before_replay`` / ``after_replay`` / ``cancel_replay``) is what ``utils.GraphedTrainStep``
 uses to put the update inside its hipGraph: the launches read the per-step scalars (learning rate, Adam's bias corrections)
 from a device block the host rewrites before every replay, everything else is baked into the captured launches.
 """
@@ -262,7 +262,7 @@ class _FusedQuantOptimizer(Optimizer):
                 packed += 1
         return packed
 
-    def _launch_captured(self, cg):                # pragma: no cover - abstract
+    def _launch_captured(self, cg, skip=None):     # pragma: no cover - abstract
         raise NotImplementedError
 
     @staticmethod
@@ -271,11 +271,17 @@ class _FusedQuantOptimizer(Optimizer):
         raise NotImplementedError
 
     @torch.no_grad()
-    def captured_step(self, capture: _Capture):
+    def captured_step(self, capture: _Capture, skip=None):
         """The update of every captured parameter on the current stream, with the clamps and planes of ``step()`` — the launches a
-        stream capture records.  Nothing on the host changes: ``before_replay`` / ``after_replay`` do what ``step()`` does there."""
+        stream capture records.  Nothing on the host changes: ``before_replay`` / ``after_replay`` do what ``step()`` does there.
+        ``skip``: one int32 device element the launches read when they RUN (the guarded entries, ``ops.optim_step_*_dev(skip=)``):
+        non-zero and the step leaves parameters, state and planes as they are — ``cancel_replay`` is its host side."""
+        if skip is not None and self._post_clamp:
+            # their clamp() is arbitrary torch code: nothing here could make it depend on a device word
+            raise ValueError(f"{type(self).__name__}: a guarded captured step cannot skip the clamp() of "
+                             f"{sorted({type(m).__name__ for m in self._post_clamp})}, which clamp_plan cannot restate")
         for cg in capture.groups:
-            self._launch_captured(cg)
+            self._launch_captured(cg, skip)
         for m in self._post_clamp:                 # clamp() of layers clamp_plan cannot restate: torch ops, captured as well
             m.clamp()
 
@@ -315,6 +321,17 @@ class _FusedQuantOptimizer(Optimizer):
         for cg in capture.groups:
             if cg.steps:
                 torch._foreach_add_(cg.steps, 1)   # state["step"] as torch keeps it (host scalar tensors): one call for all
+
+    def cancel_replay(self, capture: _Capture):
+        """Host side of a replay whose guarded update the device SKIPPED (``captured_step(skip=)`` with the guard raised): takes
+        back what ``before_replay`` / ``after_replay`` did for a step that did not happen.  That is Adam's ``state["step"]``, back
+        by one.  The rest stands: the scalar block is rewritten before the next replay; the version counters moved, which only
+        costs caches keyed on them a rebuild; and the plane records ``after_replay`` stamped under the new versions name buffers
+        the skipped launches did not write, so they still hold the planes of the (unchanged) weights.  No device tensor is
+        touched."""
+        for cg in capture.groups:
+            if cg.steps:
+                torch._foreach_sub_(cg.steps, 1)   # host scalar tensors, as in before_replay
 
     def after_replay(self, capture: _Capture):
         """Host side of a replay, after it: what ``step()`` does after its launches (version counters, plane records)."""
@@ -394,12 +411,12 @@ class FusedQuantSGD(_FusedQuantOptimizer):
     def _scalars_per_group(n):
         return 1
 
-    def _launch_captured(self, cg):
+    def _launch_captured(self, cg, skip=None):
         # no first-step flag: the buffers exist, and from a zeroed buffer mu * 0 + g IS the first step's value (see allocate_state)
         mu = cg.baked["momentum"]
         ops.optim_step_sgd_dev(cg.params, [p.grad for p in cg.params], [st[0] for st in cg.states] if mu != 0 else None, cg.scalars,
                                momentum=mu, weight_decay=cg.baked["weight_decay"], nesterov=cg.baked["nesterov"], clamps=cg.clamps,
-                               planes=cg.planes)
+                               planes=cg.planes, skip=skip)
 
     def _scalars_of(self, cg):
         return [float(self.param_groups[cg.index]["lr"])]
@@ -475,10 +492,10 @@ class FusedQuantAdam(_FusedQuantOptimizer):
     def _scalars_per_group(n):
         return 2 * n
 
-    def _launch_captured(self, cg):
+    def _launch_captured(self, cg, skip=None):
         ops.optim_step_adam_dev(cg.params, [p.grad for p in cg.params], [st[0] for st in cg.states], [st[1] for st in cg.states],
                                 cg.scalars, betas=cg.baked["betas"], eps=cg.baked["eps"], weight_decay=cg.baked["weight_decay"],
-                                clamps=cg.clamps, planes=cg.planes)
+                                clamps=cg.clamps, planes=cg.planes, skip=skip)
 
     def _scalars_of(self, cg):
         # the step counts are read from state["step"], so eager step() calls between replays are counted too
