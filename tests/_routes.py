@@ -69,6 +69,16 @@ def mfma_routes(names, elem=r"Elem\w+(?:<\d+>)?"):
     return out
 
 
+def code_conv3x3_routes(names):
+    """Profiler kernel names -> labels 'code_conv3x3<CB,MODE>' of the persistent direct 3 x 3 code conv (csrc/code_conv3x3.hip)."""
+    out = set()
+    for k in names:
+        m = re.search(r"code_conv3x3_kernel<(\d+), (\d+)>", k.replace("(anonymous namespace)::", ""))
+        if m:
+            out.add(f"code_conv3x3<{m.group(1)},{m.group(2)}>")
+    return out
+
+
 def assert_described(described, expect, case):
     """The describe entry point (``described``: an ops.*_kernel_name(...) result, or None where the case has none) names the
     configuration the profiler saw."""
