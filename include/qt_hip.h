@@ -1178,6 +1178,33 @@ int qt_nib_gemm_variant(int variant, const uint32_t* Xn, int64_t ldxp, const uin
  *                     guard that is already non-zero stays so.  Validated before anything is enqueued: n < 0, or n > 0 with a
  *                     null `flags`, `guard` or flags[i]: QT_ERR_INVALID_ARG; a pointer that is not 4-byte aligned:
  *                     QT_ERR_ALIGNMENT; n == 0: QT_OK whatever the pointers are.
+ *
+ * Global gradient-norm clipping inside the update (torch.nn.utils.clip_grad_norm_, L2 norm, error_if_nonfinite=False), as
+ * three stream-ordered steps with no atomics, no counter and no buffer that must be zero beforehand:
+ *   qt_optim_grad_norm_work_floats : fp32 words of workspace the sum-of-squares pass over `table` writes: one per unit of 4096
+ *                           gradient elements, sum over the tensors of ceil(numel / 4096).  Only g and numel of a descriptor are
+ *                           looked at (here and in qt_optim_grad_sumsq_f32); a negative qt_status for a table that entry rejects.
+ *   qt_optim_grad_sumsq_f32 : work[u] = sum of g^2 over unit u, units numbered in table order (empty tensors have none; a plane
+ *                           tensor's gradient is walked as the flat memory it is).  16-byte loads where g is 16-byte aligned.
+ *                           Fixed order inside a unit: per lane, wave tree, the four waves in order.  Null `table` or `work`
+ *                           with n > 0, a null g with numel > 0, negative counts: QT_ERR_INVALID_ARG; g or work not 4-byte
+ *                           aligned: QT_ERR_ALIGNMENT; n == 0: QT_OK.  Validated before anything is enqueued.
+ *   qt_optim_grad_norm_finalize_f32 : one workgroup adds work[0, m) in fp64 in a fixed order and writes out[0] = norm =
+ *                           (float)sqrt(sum) and out[1] = coef = min(1.0f, max_norm / (norm + 1e-6f)), evaluated in fp32 in that
+ *                           order.  `max_norm_dev` null: `max_norm` by value; else one DEVICE float read when the kernel runs
+ *                           (`max_norm` is ignored).  The words of several tables (parameter groups) laid out one after the
+ *                           other give ONE global norm.  A non-finite sum is not special: an infinite norm gives coef 0, NaN
+ *                           gives NaN, which the update propagates.  m == 0 gives norm 0 and coef 1.  m < 0, null `out`, null
+ *                           `work` with m > 0: QT_ERR_INVALID_ARG; a pointer not 4-byte aligned: QT_ERR_ALIGNMENT.
+ *   qt_optim_sgd_clip_f32 / qt_optim_adam_clip_f32 : the updates above with g = g * (*gscale) first: one separate fp32
+ *                           multiplication, in front of the weight-decay term, with `gscale` one DEVICE float (out + 1 of the
+ *                           finalise) read when the kernel runs.  The gradient in memory is not rewritten.  Same body: with
+ *                           *gscale == 1.0f they store the bits of the unclipped entries.  One entry per rule covers their three
+ *                           forms through nullable pointers: `lr_dev` null = `lr` by value, else `lr` is ignored (`_dev`);
+ *                           `coef` null = the descriptors' c0 / c1, else as in qt_optim_adam_dev_f32; `skip` null = no guard,
+ *                           else as in the `_dev_guard` entries.  Null `gscale` with n > 0: QT_ERR_INVALID_ARG; gscale, lr_dev,
+ *                           coef or skip not 4-byte aligned: QT_ERR_ALIGNMENT; n == 0: QT_OK.  Validated with the table, before
+ *                           anything is enqueued.
  * ---------------------------------------------------------------------------------------- */
 typedef struct qt_optim_tensor {
     float* p;
@@ -1207,6 +1234,15 @@ int qt_optim_sgd_dev_guard_f32(const qt_optim_tensor* table, int64_t n, const fl
 int qt_optim_adam_dev_guard_f32(const qt_optim_tensor* table, int64_t n, const float* coef, const int32_t* skip, float beta1,
                                 float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float weight_decay,
                                 qt_stream_t stream);
+int64_t qt_optim_grad_norm_work_floats(const qt_optim_tensor* table, int64_t n);
+int qt_optim_grad_sumsq_f32(const qt_optim_tensor* table, int64_t n, float* work, qt_stream_t stream);
+int qt_optim_grad_norm_finalize_f32(const float* work, int64_t m, float max_norm, const float* max_norm_dev, float* out,
+                                    qt_stream_t stream);
+int qt_optim_sgd_clip_f32(const qt_optim_tensor* table, int64_t n, float lr, const float* lr_dev, const float* gscale,
+                          const int32_t* skip, float momentum, float weight_decay, int nesterov, qt_stream_t stream);
+int qt_optim_adam_clip_f32(const qt_optim_tensor* table, int64_t n, const float* coef, const float* gscale, const int32_t* skip,
+                           float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float weight_decay,
+                           qt_stream_t stream);
 int qt_flags_chunk_capacity(void);
 int qt_flags_or_i32(const int32_t* const* flags, int64_t n, int32_t* guard, qt_stream_t stream);
 

@@ -221,6 +221,11 @@ SIGNATURES = {
     "qt_optim_adam_dev_f32": (_c_int, [_c_p, _c_i64, _c_p] + [_c_f32] * 6 + [_c_p]),
     "qt_optim_sgd_dev_guard_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_f32, _c_f32, _c_int, _c_p]),
     "qt_optim_adam_dev_guard_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p] + [_c_f32] * 6 + [_c_p]),
+    "qt_optim_grad_norm_work_floats": (_c_i64, [_c_p, _c_i64]),
+    "qt_optim_grad_sumsq_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p]),
+    "qt_optim_grad_norm_finalize_f32": (_c_int, [_c_p, _c_i64, _c_f32, _c_p, _c_p, _c_p]),
+    "qt_optim_sgd_clip_f32": (_c_int, [_c_p, _c_i64, _c_f32, _c_p, _c_p, _c_p, _c_f32, _c_f32, _c_int, _c_p]),
+    "qt_optim_adam_clip_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p] + [_c_f32] * 6 + [_c_p]),
     "qt_flags_chunk_capacity": (_c_int, []),
     "qt_flags_or_i32": (_c_int, [_c_p, _c_i64, _c_p, _c_p]),
 }

@@ -34,9 +34,19 @@
 //     captured training step keeps parameters, state and planes untouched when one of its trusted route verdicts turned out
 //     wrong (utils.GraphedTrainStep(recover=True)).  Same body, so *skip == 0 stores the bits of the `_dev` entries.
 //     qt_flags_or_i32 folds the step's verdict flags into that word: the flag POINTERS travel by value, 448 per launch.
+//   * the `_clip` entries (qt_optim_sgd_clip_f32 / qt_optim_adam_clip_f32) are the same updates with the gradient multiplied by
+//     one device float first: g = g * (*gscale), a separate fp32 multiplication in front of the weight-decay term, where
+//     torch.nn.utils.clip_grad_norm_'s in-place mul_ puts it — but the gradient in memory is not rewritten.  *gscale is read with
+//     the other per-step scalars, once per (workgroup, tensor).  The scale is a SOURCE type as well (NoScale compiles to
+//     nothing), so the body is the one template and *gscale == 1.0f stores the bits of the entries above.  Their learning rate /
+//     bias corrections come from the argument block or from device memory, and their skip word may be null: one kernel per
+//     rule serves the by-value, `_dev` and `_dev_guard` forms.
+//   * the global gradient norm that scale comes from (qt_optim_grad_sumsq_f32 / qt_optim_grad_norm_finalize_f32, below the update):
+//     one fp32 partial per 4096-element unit in a caller's workspace, then one workgroup that adds the partials in fp64.  Fixed
+//     order everywhere, no atomics, no counter, no buffer that has to be zero before the launch.
 //   * kernel-argument size: OptimChunk = 32 x 96 (descriptors) + 33 x 4 (unit prefix) + 32 x 4 (table indices) + 4 (n)
-//     + 4 (padding) = 3336 bytes; the largest rule (Adam from device memory) adds 32 and the guard
-//     pointer 8: 3376 of HIP's 4096 bytes.
+//     + 4 (padding) = 3336 bytes; the largest rule (clipped Adam from device memory: coef and gscale pointers, six floats)
+//     adds 40 and the skip pointer 8: 3384 of HIP's 4096 bytes.
 #include "qt_common.h"
 #include "nib_quant.h"
 
@@ -69,17 +79,30 @@ struct LrDevice {
     LrDevice at_base(int64_t) const { return *this; }
 };
 
-// torch.optim.SGD (dampening 0): g += wd p ; buf = first ? g : mu buf + g ; g = nesterov ? g + mu buf : buf ; p -= lr g
-template <int NS_, class Lr>
-struct SgdRule {
+// What the gradient is multiplied by before the recurrence: nothing, or one float of device memory (the clip coefficient).
+// The rules derive from it, so NoScale takes no room in the argument block.
+struct NoScale {
+    static constexpr bool ON = false;
+    __device__ __forceinline__ float get() const { return 1.0f; }
+};
+struct DevScale {
+    static constexpr bool ON = true;
+    const float* gscale;
+    __device__ __forceinline__ float get() const { return *gscale; }
+};
+
+// torch.optim.SGD (dampening 0): g = g gscale ; g += wd p ; buf = first ? g : mu buf + g ; g = nesterov ? g + mu buf : buf ; p -= lr g
+template <int NS_, class Lr, class Gs = NoScale>
+struct SgdRule : Gs {
     static constexpr int NS = NS_;        // state tensors: 0 (no momentum) or 1
-    struct Step { float lr; };            // what a workgroup reads once per tensor
+    struct Step { float lr, gs; };        // what a workgroup reads once per tensor
     Lr src;
     float mu, wd;
     int nesterov;
-    __device__ __forceinline__ Step step(const qt_optim_tensor&, int) const { return Step{src.get()}; }
-    SgdRule at_base(int64_t b) const { return SgdRule{src.at_base(b), mu, wd, nesterov}; }
+    __device__ __forceinline__ Step step(const qt_optim_tensor&, int) const { return Step{src.get(), Gs::get()}; }
+    SgdRule at_base(int64_t b) const { return SgdRule{static_cast<const Gs&>(*this), src.at_base(b), mu, wd, nesterov}; }
     __device__ __forceinline__ void operator()(float& p, float g, float& s0, float&, const qt_optim_tensor& t, const Step& st) const {
+        if (Gs::ON) g = g * st.gs;
         if (wd != 0.0f) g = g + wd * p;
         if (NS == 1) {
             const float b = (t.flags & FLAG_FIRST) ? g : s0 * mu + g;
@@ -105,19 +128,23 @@ struct CoefDevice {
 
 // torch.optim.Adam (L2 weight decay, no amsgrad).  c0 = lr / (1 - beta1^step), c1 = sqrt(1 - beta2^step): computed by
 // the host in double precision from the tensor's own step count.
-template <class Coef>
-struct AdamRule {
+template <class Coef, class Gs = NoScale>
+struct AdamRule : Gs {
     static constexpr int NS = 2;
-    struct Step { float c0, c1; };
+    struct Step { float c0, c1, gs; };
     Coef src;
     float b1, omb1, b2, omb2, eps, wd;
     __device__ __forceinline__ Step step(const qt_optim_tensor& t, int idx) const {
         Step st;
         src.get(t, idx, st.c0, st.c1);
+        st.gs = Gs::get();
         return st;
     }
-    AdamRule at_base(int64_t b) const { return AdamRule{src.at_base(b), b1, omb1, b2, omb2, eps, wd}; }
+    AdamRule at_base(int64_t b) const {
+        return AdamRule{static_cast<const Gs&>(*this), src.at_base(b), b1, omb1, b2, omb2, eps, wd};
+    }
     __device__ __forceinline__ void operator()(float& p, float g, float& m, float& v, const qt_optim_tensor&, const Step& st) const {
+        if (Gs::ON) g = g * st.gs;
         if (wd != 0.0f) g = g + wd * p;
         m = b1 * m + omb1 * g;
         v = b2 * v + omb2 * (g * g);
@@ -282,6 +309,13 @@ __global__ __launch_bounds__(256) void optim_step_guard_kernel(const OptimChunk 
     optim_step_body(c, r);
 }
 
+// The form of the `_clip` entries: the skip word may be null (no guard), else it is the guard above.
+template <class Rule>
+__global__ __launch_bounds__(256) void optim_step_clip_kernel(const OptimChunk c, const Rule r, const int32_t* skip) {
+    if (skip && *skip != 0) return;
+    optim_step_body(c, r);
+}
+
 template <class Rule>
 int check_tensor(const qt_optim_tensor& t) {
     if (t.numel < 0) return QT_ERR_INVALID_ARG;
@@ -310,6 +344,7 @@ int64_t tensor_units(const qt_optim_tensor& t) {
 // The guard of a launch sequence is a TYPE, so that only the entries that take one instantiate the guarded kernel.
 struct NoGuard {};
 struct DevGuard { const int32_t* skip; };
+struct OptGuard { const int32_t* skip; };          // `_clip` entries: null = no guard
 
 template <class Rule>
 void enqueue_chunk(const OptimChunk& c, const Rule& r, NoGuard, int grid, hipStream_t s) {
@@ -318,6 +353,11 @@ void enqueue_chunk(const OptimChunk& c, const Rule& r, NoGuard, int grid, hipStr
 template <class Rule>
 void enqueue_chunk(const OptimChunk& c, const Rule& r, DevGuard g, int grid, hipStream_t s) {
     hipLaunchKernelGGL(optim_step_guard_kernel<Rule>, dim3(grid), dim3(256), 0, s, c, r, g.skip);
+}
+
+template <class Rule>
+void enqueue_chunk(const OptimChunk& c, const Rule& r, OptGuard g, int grid, hipStream_t s) {
+    hipLaunchKernelGGL(optim_step_clip_kernel<Rule>, dim3(grid), dim3(256), 0, s, c, r, g.skip);
 }
 
 template <class Rule, class Guard>
@@ -399,6 +439,164 @@ __global__ __launch_bounds__(256) void flags_or_kernel(const FlagChunk c, int n,
     if (__syncthreads_or(any) && threadIdx.x == 0) *guard = 1;
 }
 
+// ---- global gradient norm: sum of squares per unit, then one workgroup that finishes ----
+
+// What the sum-of-squares pass needs of a chunk of the table: gradient pointers and sizes, the unit prefix, one bit per slot for
+// the 16-byte walk.  656 bytes of argument block.
+struct NormChunk {
+    const float* g[QT_OPTIM_CHUNK];
+    int64_t numel[QT_OPTIM_CHUNK];
+    int32_t ustart[QT_OPTIM_CHUNK + 1];   // units of slot i: [ustart[i], ustart[i + 1])
+    uint32_t vec;                         // bit i: g[i] is 16-byte aligned
+    int32_t n;
+};
+static_assert(sizeof(NormChunk) == 656, "by-value chunk of the sum-of-squares pass");
+
+// Sum over the 64 lanes of a wave, a fixed tree: four DPP steps inside each row of 16, then the four row sums in lane order.
+// Every step exchanges symmetrically, so the lanes of a row agree bit for bit.
+__device__ __forceinline__ float wave_sum_dpp_f32(float v) {
+    v = v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
+    v = v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
+    v = v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));   // row_half_mirror
+    v = v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));   // row_mirror
+    const int i = __float_as_int(v);
+    return ((__int_as_float(__builtin_amdgcn_readlane(i, 0)) + __int_as_float(__builtin_amdgcn_readlane(i, 16))) +
+            __int_as_float(__builtin_amdgcn_readlane(i, 32))) + __int_as_float(__builtin_amdgcn_readlane(i, 48));
+}
+
+__device__ __forceinline__ float sumsq4(float acc, const float4& g) {
+    acc = acc + g.x * g.x;
+    acc = acc + g.y * g.y;
+    acc = acc + g.z * g.z;
+    return acc + g.w * g.w;
+}
+
+// this lane's share of unit b of a gradient: elements [4096 b, min(numel, 4096 (b + 1))), walked as flat_unit() walks them
+__device__ __forceinline__ float lane_sumsq(const float* g, int64_t numel, int64_t b, bool vec) {
+    const int tid = threadIdx.x;
+    const int64_t base = b * FLAT_UNIT;
+    float acc = 0.0f;
+    if (!vec) {
+#pragma unroll 4
+        for (int j = 0; j < FLAT_UNIT / 256; ++j) {
+            const int64_t i = base + j * 256 + tid;
+            if (i < numel) {
+                const float x = g[i];
+                acc = acc + x * x;
+            }
+        }
+        return acc;
+    }
+    const int64_t i0 = b * (FLAT_UNIT / 4) + tid;
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    if (base + FLAT_UNIT <= numel) {          // full unit: four independent loads in flight
+        float4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = g4[i0 + 256 * j];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc = sumsq4(acc, v[j]);
+        return acc;
+    }
+    const int64_t n4 = numel >> 2;            // the gradient's last unit
+    for (int j = 0; j < 4; ++j) {
+        const int64_t i4 = i0 + 256 * j;
+        if (i4 < n4) acc = sumsq4(acc, g4[i4]);
+    }
+    const int64_t e = n4 * 4 + tid;           // numel % 4 tail elements (they lie in this unit)
+    if (e < numel) {
+        const float x = g[e];
+        acc = acc + x * x;
+    }
+    return acc;
+}
+
+// work[u] = sum of squares of unit u of the chunk: per lane, then the wave tree, then the four waves through LDS in wave order.
+// Every unit's word is written by exactly one workgroup with a plain store: nothing has to be zero beforehand.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const NormChunk c, float* __restrict__ work) {
+    __shared__ float part[4];
+    const int total = c.ustart[c.n];
+    int ti = 0;
+    for (int u = blockIdx.x; u < total; u += gridDim.x) {
+        while (c.ustart[ti + 1] <= u) ++ti;          // u < total = ustart[n]: stops at ti < n
+        float acc = lane_sumsq(c.g[ti], c.numel[ti], u - c.ustart[ti], (c.vec >> ti) & 1u);
+        acc = wave_sum_dpp_f32(acc);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) work[u] = ((part[0] + part[1]) + part[2]) + part[3];
+        __syncthreads();                             // part[] is reused by the next unit
+    }
+}
+
+// One workgroup: total = sum of work[0, m) in fp64 (lane l adds the words l, l + 256, ... in ascending order, then a fixed
+// tree over the lanes), out[0] = norm = (float)sqrt(total), out[1] = coef = min(1, max_norm / (norm + 1e-6f)) in fp32, the
+// expression of torch.nn.utils.clip_grad_norm_.  A NaN quotient stays NaN (torch.clamp), an infinite norm gives 0.
+__global__ __launch_bounds__(256) void grad_norm_finalize_kernel(const float* __restrict__ work, int64_t m, float max_norm,
+                                                                 const float* max_norm_dev, float* __restrict__ out) {
+    __shared__ double sh[256];
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < m; i += 256) s += (double)work[i];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(sh[0]);
+        const float mx = max_norm_dev ? *max_norm_dev : max_norm;
+        const float q = mx / (norm + 1e-6f);
+        out[0] = norm;
+        out[1] = q > 1.0f ? 1.0f : q;
+    }
+}
+
+int check_grad(const qt_optim_tensor& t) {
+    if (t.numel < 0) return QT_ERR_INVALID_ARG;
+    if (t.numel > 0 && !t.g) return QT_ERR_INVALID_ARG;
+    if (reinterpret_cast<uintptr_t>(t.g) & 3u) return QT_ERR_ALIGNMENT;
+    if ((t.numel + FLAT_UNIT - 1) / FLAT_UNIT > INT32_MAX) return QT_ERR_UNSUPPORTED;
+    return QT_OK;
+}
+
+// units of a gradient in the sum-of-squares pass: flat memory, whatever the parameter's plane
+int64_t grad_units(const qt_optim_tensor& t) { return (t.numel + FLAT_UNIT - 1) / FLAT_UNIT; }
+
+// The chunking of the sum-of-squares pass, apart from the launch: emit(chunk, first unit of the chunk in the workspace) for
+// every non-empty chunk, in table order.  Returns the number of units, or a negative status of emit.
+template <class Emit>
+int64_t grad_sumsq_chunks(const qt_optim_tensor* tab, int64_t n, Emit emit) {
+    NormChunk c{};
+    int64_t first = 0;                             // workspace index of the chunk's unit 0
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t units = grad_units(tab[i]);
+        if (units == 0) continue;                  // empty tensor
+        if (c.n == QT_OPTIM_CHUNK || (int64_t)c.ustart[c.n] + units > INT32_MAX) {
+            const int rc = emit(c, first);
+            if (rc != QT_OK) return rc;
+            first += c.ustart[c.n];
+            c = NormChunk{};
+        }
+        c.g[c.n] = tab[i].g;
+        c.numel[c.n] = tab[i].numel;
+        if (qt_aligned16(tab[i].g)) c.vec |= 1u << c.n;
+        c.ustart[c.n + 1] = c.ustart[c.n] + (int32_t)units;
+        ++c.n;
+    }
+    if (c.n > 0) {
+        const int rc = emit(c, first);
+        if (rc != QT_OK) return rc;
+        first += c.ustart[c.n];
+    }
+    return first;
+}
+
+// the gradient scale of a `_clip` entry: validated like the device scalars, after them
+int check_gscale(const float* gscale) {
+    if (!gscale) return QT_ERR_INVALID_ARG;
+    if (reinterpret_cast<uintptr_t>(gscale) & 3u) return QT_ERR_ALIGNMENT;
+    return QT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -422,8 +620,8 @@ int qt_optim_scalars_f32(float* dst, const float* values, int64_t n, qt_stream_t
 int qt_optim_sgd_f32(const qt_optim_tensor* table, int64_t n, float lr, float momentum, float weight_decay, int nesterov,
                      qt_stream_t stream) {
     if (nesterov && momentum == 0.0f) return QT_ERR_INVALID_ARG;
-    if (momentum != 0.0f) return optim_step(table, n, SgdRule<1, LrValue>{{lr}, momentum, weight_decay, nesterov ? 1 : 0}, stream);
-    return optim_step(table, n, SgdRule<0, LrValue>{{lr}, 0.0f, weight_decay, 0}, stream);
+    if (momentum != 0.0f) return optim_step(table, n, SgdRule<1, LrValue>{{}, {lr}, momentum, weight_decay, nesterov ? 1 : 0}, stream);
+    return optim_step(table, n, SgdRule<0, LrValue>{{}, {lr}, 0.0f, weight_decay, 0}, stream);
 }
 
 int qt_optim_sgd_dev_f32(const qt_optim_tensor* table, int64_t n, const float* lr, float momentum, float weight_decay,
@@ -432,13 +630,13 @@ int qt_optim_sgd_dev_f32(const qt_optim_tensor* table, int64_t n, const float* l
     if (n == 0) return QT_OK;
     const int rc = check_scalars(lr, n);
     if (rc != QT_OK) return rc;
-    if (momentum != 0.0f) return optim_step(table, n, SgdRule<1, LrDevice>{{lr}, momentum, weight_decay, nesterov ? 1 : 0}, stream);
-    return optim_step(table, n, SgdRule<0, LrDevice>{{lr}, 0.0f, weight_decay, 0}, stream);
+    if (momentum != 0.0f) return optim_step(table, n, SgdRule<1, LrDevice>{{}, {lr}, momentum, weight_decay, nesterov ? 1 : 0}, stream);
+    return optim_step(table, n, SgdRule<0, LrDevice>{{}, {lr}, 0.0f, weight_decay, 0}, stream);
 }
 
 int qt_optim_adam_f32(const qt_optim_tensor* table, int64_t n, float beta1, float one_minus_beta1, float beta2,
                       float one_minus_beta2, float eps, float weight_decay, qt_stream_t stream) {
-    return optim_step(table, n, AdamRule<CoefTable>{{}, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay}, stream);
+    return optim_step(table, n, AdamRule<CoefTable>{{}, {}, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay}, stream);
 }
 
 int qt_optim_adam_dev_f32(const qt_optim_tensor* table, int64_t n, const float* coef, float beta1, float one_minus_beta1,
@@ -446,7 +644,7 @@ int qt_optim_adam_dev_f32(const qt_optim_tensor* table, int64_t n, const float* 
     if (n == 0) return QT_OK;
     const int rc = check_scalars(coef, n);
     if (rc != QT_OK) return rc;
-    return optim_step(table, n, AdamRule<CoefDevice>{{coef}, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay},
+    return optim_step(table, n, AdamRule<CoefDevice>{{}, {coef}, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay},
                       stream);
 }
 
@@ -458,8 +656,8 @@ int qt_optim_sgd_dev_guard_f32(const qt_optim_tensor* table, int64_t n, const fl
     if (rc == QT_OK) rc = check_skip(skip);
     if (rc != QT_OK) return rc;
     if (momentum != 0.0f)
-        return optim_step(table, n, SgdRule<1, LrDevice>{{lr}, momentum, weight_decay, nesterov ? 1 : 0}, stream, DevGuard{skip});
-    return optim_step(table, n, SgdRule<0, LrDevice>{{lr}, 0.0f, weight_decay, 0}, stream, DevGuard{skip});
+        return optim_step(table, n, SgdRule<1, LrDevice>{{}, {lr}, momentum, weight_decay, nesterov ? 1 : 0}, stream, DevGuard{skip});
+    return optim_step(table, n, SgdRule<0, LrDevice>{{}, {lr}, 0.0f, weight_decay, 0}, stream, DevGuard{skip});
 }
 
 int qt_optim_adam_dev_guard_f32(const qt_optim_tensor* table, int64_t n, const float* coef, const int32_t* skip, float beta1,
@@ -469,8 +667,83 @@ int qt_optim_adam_dev_guard_f32(const qt_optim_tensor* table, int64_t n, const f
     int rc = check_scalars(coef, n);
     if (rc == QT_OK) rc = check_skip(skip);
     if (rc != QT_OK) return rc;
-    return optim_step(table, n, AdamRule<CoefDevice>{{coef}, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay},
+    return optim_step(table, n, AdamRule<CoefDevice>{{}, {coef}, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay},
                       stream, DevGuard{skip});
+}
+
+int64_t qt_optim_grad_norm_work_floats(const qt_optim_tensor* table, int64_t n) {
+    if (n < 0 || (n > 0 && !table)) return QT_ERR_INVALID_ARG;
+    int64_t units = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int rc = check_grad(table[i]);
+        if (rc != QT_OK) return rc;
+        units += grad_units(table[i]);
+    }
+    return units;
+}
+
+int qt_optim_grad_sumsq_f32(const qt_optim_tensor* table, int64_t n, float* work, qt_stream_t stream) {
+    if (n < 0 || (n > 0 && (!table || !work))) return QT_ERR_INVALID_ARG;
+    if (n == 0) return QT_OK;
+    if (reinterpret_cast<uintptr_t>(work) & 3u) return QT_ERR_ALIGNMENT;
+    for (int64_t i = 0; i < n; ++i) {              // the whole table is checked before anything is enqueued
+        const int rc = check_grad(table[i]);
+        if (rc != QT_OK) return rc;
+    }
+    const int64_t rc = grad_sumsq_chunks(table, n, [&](const NormChunk& c, int64_t first) {
+        hipLaunchKernelGGL(grad_sumsq_kernel, dim3(qt_stream_grid(c.ustart[c.n])), dim3(256), 0, (hipStream_t)stream, c, work + first);
+        return qt_check_launch();
+    });
+    return rc < 0 ? (int)rc : QT_OK;
+}
+
+int qt_optim_grad_norm_finalize_f32(const float* work, int64_t m, float max_norm, const float* max_norm_dev, float* out,
+                                    qt_stream_t stream) {
+    if (m < 0 || (m > 0 && !work) || !out) return QT_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(work) | reinterpret_cast<uintptr_t>(max_norm_dev) | reinterpret_cast<uintptr_t>(out)) & 3u)
+        return QT_ERR_ALIGNMENT;
+    hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, work, m, max_norm, max_norm_dev, out);
+    return qt_check_launch();
+}
+
+int qt_optim_sgd_clip_f32(const qt_optim_tensor* table, int64_t n, float lr, const float* lr_dev, const float* gscale,
+                          const int32_t* skip, float momentum, float weight_decay, int nesterov, qt_stream_t stream) {
+    if (nesterov && momentum == 0.0f) return QT_ERR_INVALID_ARG;
+    if (n == 0) return QT_OK;
+    if (n < 0) return QT_ERR_INVALID_ARG;
+    int rc = (reinterpret_cast<uintptr_t>(lr_dev) & 3u) ? QT_ERR_ALIGNMENT : QT_OK;
+    if (rc == QT_OK) rc = check_gscale(gscale);
+    if (rc == QT_OK && skip) rc = check_skip(skip);
+    if (rc != QT_OK) return rc;
+    const DevScale gs{gscale};
+    const OptGuard guard{skip};
+    const int nes = nesterov ? 1 : 0;
+    if (lr_dev) {
+        if (momentum != 0.0f)
+            return optim_step(table, n, SgdRule<1, LrDevice, DevScale>{gs, {lr_dev}, momentum, weight_decay, nes}, stream, guard);
+        return optim_step(table, n, SgdRule<0, LrDevice, DevScale>{gs, {lr_dev}, 0.0f, weight_decay, 0}, stream, guard);
+    }
+    if (momentum != 0.0f)
+        return optim_step(table, n, SgdRule<1, LrValue, DevScale>{gs, {lr}, momentum, weight_decay, nes}, stream, guard);
+    return optim_step(table, n, SgdRule<0, LrValue, DevScale>{gs, {lr}, 0.0f, weight_decay, 0}, stream, guard);
+}
+
+int qt_optim_adam_clip_f32(const qt_optim_tensor* table, int64_t n, const float* coef, const float* gscale, const int32_t* skip,
+                           float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float weight_decay,
+                           qt_stream_t stream) {
+    if (n == 0) return QT_OK;
+    if (n < 0) return QT_ERR_INVALID_ARG;
+    int rc = (reinterpret_cast<uintptr_t>(coef) & 3u) ? QT_ERR_ALIGNMENT : QT_OK;
+    if (rc == QT_OK) rc = check_gscale(gscale);
+    if (rc == QT_OK && skip) rc = check_skip(skip);
+    if (rc != QT_OK) return rc;
+    const DevScale gs{gscale};
+    const OptGuard guard{skip};
+    if (coef)
+        return optim_step(table, n, AdamRule<CoefDevice, DevScale>{gs, {coef}, beta1, one_minus_beta1, beta2, one_minus_beta2, eps,
+                                                                   weight_decay}, stream, guard);
+    return optim_step(table, n, AdamRule<CoefTable, DevScale>{gs, {}, beta1, one_minus_beta1, beta2, one_minus_beta2, eps,
+                                                              weight_decay}, stream, guard);
 }
 
 int qt_flags_chunk_capacity(void) { return QT_FLAGS_CHUNK; }

@@ -3805,12 +3805,14 @@ def _optim_table(params, grads, s0, s1, clamps, planes):
 
 
 def optim_step_sgd(params, grads, momentum_buffers=None, *, lr: float, momentum: float = 0.0, weight_decay: float = 0.0,
-                   nesterov: bool = False, first=None, clamps=None, planes=None) -> None:
+                   nesterov: bool = False, first=None, clamps=None, planes=None, gscale: Optional[torch.Tensor] = None) -> None:
     """One torch.optim.SGD step (dampening 0) of every tensor in the lists, in place, in one launch sequence
     (qt_optim_sgd_f32): ``p`` is clamped to ``clamps[i] = (lo, hi)`` as it is stored and, where ``planes[i] =
     (NibPlanes, "binary" | "ternary")`` is given, the nibble plane of the stored weight is written into those words.
     ``first[i]``: this is the tensor's first step, its momentum buffer becomes the gradient.  The version counters of the
-    parameters are NOT touched: the caller bumps them (utils.FusedQuantSGD does)."""
+    parameters are NOT touched: the caller bumps them (utils.FusedQuantSGD does).  ``gscale``: one fp32 device element the
+    gradient is multiplied by as it is read (qt_optim_sgd_clip_f32; the ``coef`` of ``optim_grad_norm``); the gradients in
+    memory stay as they are.  None: the entry without it."""
     if not params:
         return
     use_mom = momentum != 0
@@ -3822,15 +3824,20 @@ def optim_step_sgd(params, grads, momentum_buffers=None, *, lr: float, momentum:
             if f:
                 tab[i].flags = 1
     with _on(dev):
-        _lib.call("qt_optim_sgd_f32", _ct.addressof(tab), len(params), float(lr), float(momentum), float(weight_decay),
-                  int(bool(nesterov)), _stream(dev))
+        if gscale is None:
+            _lib.call("qt_optim_sgd_f32", _ct.addressof(tab), len(params), float(lr), float(momentum), float(weight_decay),
+                      int(bool(nesterov)), _stream(dev))
+        else:
+            _optim_scalars_check(gscale, dev, 1, "gscale")
+            _lib.call("qt_optim_sgd_clip_f32", _ct.addressof(tab), len(params), float(lr), None, _p(gscale), None, float(momentum),
+                      float(weight_decay), int(bool(nesterov)), _stream(dev))
 
 
 def optim_step_adam(params, grads, exp_avgs, exp_avg_sqs, steps, *, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
-                    weight_decay: float = 0.0, clamps=None, planes=None) -> None:
+                    weight_decay: float = 0.0, clamps=None, planes=None, gscale: Optional[torch.Tensor] = None) -> None:
     """One torch.optim.Adam step (L2 weight decay, no amsgrad) in one launch sequence (qt_optim_adam_f32).  ``steps[i]``: the
-    step count of tensor i INCLUDING this step; its bias corrections are computed here, in double precision.  Clamp, planes
-    and version counters as in ``optim_step_sgd``."""
+    step count of tensor i INCLUDING this step; its bias corrections are computed here, in double precision.  Clamp, planes,
+    version counters and ``gscale`` (qt_optim_adam_clip_f32) as in ``optim_step_sgd``."""
     if not params:
         return
     b1, b2 = float(betas[0]), float(betas[1])
@@ -3840,8 +3847,13 @@ def optim_step_adam(params, grads, exp_avgs, exp_avg_sqs, steps, *, lr: float, b
     for i, c in enumerate(adam_coefficients(steps, lr, (b1, b2))):
         tab[i].c0, tab[i].c1 = c
     with _on(dev):
-        _lib.call("qt_optim_adam_f32", _ct.addressof(tab), len(params), b1, 1.0 - b1, b2, 1.0 - b2, float(eps),
-                  float(weight_decay), _stream(dev))
+        if gscale is None:
+            _lib.call("qt_optim_adam_f32", _ct.addressof(tab), len(params), b1, 1.0 - b1, b2, 1.0 - b2, float(eps),
+                      float(weight_decay), _stream(dev))
+        else:
+            _optim_scalars_check(gscale, dev, 1, "gscale")
+            _lib.call("qt_optim_adam_clip_f32", _ct.addressof(tab), len(params), None, _p(gscale), None, b1, 1.0 - b1, b2, 1.0 - b2,
+                      float(eps), float(weight_decay), _stream(dev))
 
 
 def adam_coefficients(steps, lr: float, betas=(0.9, 0.999)):
@@ -3893,11 +3905,13 @@ def _optim_skip_check(skip, dev) -> None:
 
 
 def optim_step_sgd_dev(params, grads, momentum_buffers, lr_dev: torch.Tensor, *, momentum: float = 0.0, weight_decay: float = 0.0,
-                       nesterov: bool = False, clamps=None, planes=None, skip: Optional[torch.Tensor] = None) -> None:
+                       nesterov: bool = False, clamps=None, planes=None, skip: Optional[torch.Tensor] = None,
+                       gscale: Optional[torch.Tensor] = None) -> None:
     """``optim_step_sgd`` with the learning rate read from ``lr_dev`` (one fp32 element on the parameters' device) when the kernel
     RUNS (qt_optim_sgd_dev_f32): the form a hipGraph can capture.  No first-step flag: the momentum buffers exist and a zeroed
     buffer makes ``mu * 0 + g`` the first step's value.  ``skip``: one int32 device element, read when the kernel runs
-    (qt_optim_sgd_dev_guard_f32): non-zero leaves every tensor and plane untouched, zero stores the bits of the unguarded call."""
+    (qt_optim_sgd_dev_guard_f32): non-zero leaves every tensor and plane untouched, zero stores the bits of the unguarded call.
+    ``gscale``: as in ``optim_step_sgd`` (qt_optim_sgd_clip_f32, with or without ``skip``)."""
     if not params:
         return
     use_mom = momentum != 0
@@ -3906,8 +3920,14 @@ def optim_step_sgd_dev(params, grads, momentum_buffers, lr_dev: torch.Tensor, *,
     tab, dev = _optim_table(params, grads, momentum_buffers if use_mom else None, None, clamps, planes)
     _optim_scalars_check(lr_dev, dev, 1, "lr_dev")
     hp = (float(momentum), float(weight_decay), int(bool(nesterov)))
+    if skip is not None:
+        _optim_skip_check(skip, dev)
     with _on(dev):
-        if skip is None:
+        if gscale is not None:
+            _optim_scalars_check(gscale, dev, 1, "gscale")
+            _lib.call("qt_optim_sgd_clip_f32", _ct.addressof(tab), len(params), 0.0, _p(lr_dev), _p(gscale),
+                      None if skip is None else _p(skip), *hp, _stream(dev))
+        elif skip is None:
             _lib.call("qt_optim_sgd_dev_f32", _ct.addressof(tab), len(params), _p(lr_dev), *hp, _stream(dev))
         else:
             _optim_skip_check(skip, dev)
@@ -3915,22 +3935,88 @@ def optim_step_sgd_dev(params, grads, momentum_buffers, lr_dev: torch.Tensor, *,
 
 
 def optim_step_adam_dev(params, grads, exp_avgs, exp_avg_sqs, coef_dev: torch.Tensor, *, betas=(0.9, 0.999), eps: float = 1e-8,
-                        weight_decay: float = 0.0, clamps=None, planes=None, skip: Optional[torch.Tensor] = None) -> None:
+                        weight_decay: float = 0.0, clamps=None, planes=None, skip: Optional[torch.Tensor] = None,
+                        gscale: Optional[torch.Tensor] = None) -> None:
     """``optim_step_adam`` with the bias corrections read from ``coef_dev`` (``2 * len(params)`` fp32 elements on the parameters'
     device: ``adam_coefficients`` of tensor i at [2 i], [2 i + 1]) when the kernel RUNS (qt_optim_adam_dev_f32).  ``skip``: as in
-    ``optim_step_sgd_dev`` (qt_optim_adam_dev_guard_f32)."""
+    ``optim_step_sgd_dev`` (qt_optim_adam_dev_guard_f32).  ``gscale``: as in ``optim_step_sgd`` (qt_optim_adam_clip_f32)."""
     if not params:
         return
     b1, b2 = float(betas[0]), float(betas[1])
     tab, dev = _optim_table(params, grads, exp_avgs, exp_avg_sqs, clamps, planes)
     _optim_scalars_check(coef_dev, dev, 2 * len(params), "coef_dev")
     hp = (b1, 1.0 - b1, b2, 1.0 - b2, float(eps), float(weight_decay))
+    if skip is not None:
+        _optim_skip_check(skip, dev)
     with _on(dev):
-        if skip is None:
+        if gscale is not None:
+            _optim_scalars_check(gscale, dev, 1, "gscale")
+            _lib.call("qt_optim_adam_clip_f32", _ct.addressof(tab), len(params), _p(coef_dev), _p(gscale),
+                      None if skip is None else _p(skip), *hp, _stream(dev))
+        elif skip is None:
             _lib.call("qt_optim_adam_dev_f32", _ct.addressof(tab), len(params), _p(coef_dev), *hp, _stream(dev))
         else:
             _optim_skip_check(skip, dev)
             _lib.call("qt_optim_adam_dev_guard_f32", _ct.addressof(tab), len(params), _p(coef_dev), _p(skip), *hp, _stream(dev))
+
+
+def _grad_table(grads):
+    """ctypes table of descriptors that carry a gradient pointer and a size only — what the sum-of-squares pass reads —, the
+    gradients' device and the number of 4096-element units (= qt_optim_grad_norm_work_floats of the table)."""
+    n = len(grads)
+    tab = (_OptimTensor * max(n, 1))()
+    dev = grads[0].device if n else None
+    units = 0
+    for i, g in enumerate(grads):
+        _optim_route_check(g, None, "gradient")
+        if g.device != dev:
+            raise ValueError("optim_grad_norm: one call takes the tensors of one device")
+        e, numel = tab[i], g.numel()
+        e.g, e.numel = g.data_ptr(), numel
+        units += (numel + 4095) >> 12
+    return tab, dev, units
+
+
+def optim_grad_norm_work_floats(grads) -> int:
+    """fp32 elements of workspace ``optim_grad_norm`` needs for ``grads``: one per 4096-element unit of every gradient
+    (qt_optim_grad_norm_work_floats)."""
+    tab, _, _ = _grad_table(grads)
+    m = int(_lib.load().qt_optim_grad_norm_work_floats(_ct.addressof(tab), len(grads)))
+    if m < 0:
+        raise _lib.QtStatusError(f"qt_optim_grad_norm_work_floats failed: {_lib.strerror(m)} (qt_status {m})")
+    return m
+
+
+def optim_grad_norm(grads, workspace: torch.Tensor, out: torch.Tensor, *, max_norm: Optional[float] = None,
+                    max_norm_dev: Optional[torch.Tensor] = None) -> None:
+    """The global L2 norm of ``grads`` (contiguous fp32 tensors of one device) and the coefficient
+    ``torch.nn.utils.clip_grad_norm_`` would scale them by, on the current stream with no synchronise:
+    ``out[0] = norm``, ``out[1] = min(1, max_norm / (norm + 1e-6))`` (``out``: two fp32 device elements).  One sum-of-squares
+    launch per 32 gradients writes an fp32 partial per 4096-element unit into ``workspace`` (``optim_grad_norm_work_floats``
+    elements, no initial content needed), one finalise launch adds them in fp64 (qt_optim_grad_sumsq_f32,
+    qt_optim_grad_norm_finalize_f32).  Exactly one of ``max_norm`` (a Python float, by value) and ``max_norm_dev`` (one fp32
+    device element read when the kernel RUNS: the form a hipGraph can capture) is given.  Nothing in ``grads`` is written."""
+    if (max_norm is None) == (max_norm_dev is None):
+        raise ValueError("optim_grad_norm: give exactly one of max_norm and max_norm_dev")
+    if not isinstance(out, torch.Tensor) or not out.is_cuda:
+        raise TypeError("optim_grad_norm: out is two fp32 elements in HIP device memory")
+    dev = out.device
+    _optim_scalars_check(out, dev, 2, "out")
+    tab, gdev, m = _grad_table(grads)                # one walk over the gradients: the table and its unit count
+    if gdev is not None and gdev != dev:
+        raise ValueError("optim_grad_norm: the gradients and out are on different devices")
+    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda:
+        raise TypeError("optim_grad_norm: workspace is an fp32 tensor in HIP device memory")
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.device != dev or workspace.numel() < m:
+        raise ValueError(f"optim_grad_norm: workspace is at least {m} contiguous fp32 elements on {dev}, got "
+                         f"{tuple(workspace.shape)} {workspace.dtype} on {workspace.device}")
+    if max_norm_dev is not None:
+        _optim_scalars_check(max_norm_dev, dev, 1, "max_norm_dev")
+    with _on(dev):
+        if m > 0:
+            _lib.call("qt_optim_grad_sumsq_f32", _ct.addressof(tab), len(grads), _p(workspace), _stream(dev))
+        _lib.call("qt_optim_grad_norm_finalize_f32", _p(workspace), m, 0.0 if max_norm is None else float(max_norm),
+                  None if max_norm_dev is None else _p(max_norm_dev), _p(out), _stream(dev))
 
 
 def flags_chunk_capacity() -> int:

@@ -267,6 +267,11 @@ class GraphedTrainStep:
         replaces the state tensors, so the next call raises: load first, then construct the step.
       * One optimiser may serve several steps (a full and a tail batch shape): each has its own scalar block, all share the
         optimiser's state and plane buffers.
+      * An optimiser built with ``max_grad_norm=`` clips inside the graph: the norm launches over the gradients of all groups sit
+        between the captured backward and the captured update, which multiplies the gradients by the coefficient as it reads
+        them — ``p.grad`` stays unscaled.  ``optimizer.max_grad_norm = x`` reaches the next replay like a learning rate;
+        switching clipping on or off after the capture raises.  With ``recover=True`` the norm launches run in a skipped
+        step too, but they write only their own workspace and the two words behind ``optimizer.grad_norm`` / ``clip_coef``.
     Other optimiser types stay outside the graph (the form above); so do data-parallel steps: a model whose gradients a
     ``GradientSynchronizer`` averages is refused, because the all-reduce runs between backward and the update.
 

@@ -10,8 +10,13 @@ not read the fp32 weight again only to take its sign.
 Capture mode (``prepare_capture`` / ``captured_step`` / ``before_replay`` / ``after_replay`` / ``cancel_replay``) is what ``utils.GraphedTrainStep``
 uses to put the update inside its hipGraph: the launches read the per-step scalars (learning rate, Adam's bias corrections)
 from a device block the host rewrites before every replay, everything else is baked into the captured launches.
+
+``max_grad_norm=``: ``torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm)`` folded into the step — one sum-of-squares pass
+over the gradients, one finalise launch, and the update multiplies each gradient by the coefficient as it reads it.  ``p.grad``
+stays UNSCALED on that path; ``opt.grad_norm`` / ``opt.clip_coef`` hold the step's norm and coefficient on the device.
 """
 import functools
+import math
 from typing import Dict, Tuple
 
 import torch
@@ -118,13 +123,18 @@ class _Capture:
 
     def __init__(self, groups, block, state_epoch):
         self.groups, self.block, self.state_epoch = groups, block, state_epoch
+        # clipping (max_grad_norm at capture time): the device float the finalise launch reads max_norm from (the last slot of the
+        # scalar block), the workspace of the sum-of-squares pass and the two words (norm, coef) it ends in; None = not captured
+        self.max_norm = self.norm_work = self.norm_out = None
 
 
 class _FusedQuantOptimizer(Optimizer):
     #: the group entries a captured launch takes by value: changing one after the capture cannot reach the graph
     _BAKED = ()
+    #: the state tensors of a parameter, in the kernel's order
+    _STATE_KEYS = ()
 
-    def __init__(self, params, defaults, clamp, emit_planes):
+    def __init__(self, params, defaults, clamp, emit_planes, max_grad_norm=None):
         module = params if isinstance(params, torch.nn.Module) else None
         self._names = {}
         if module is not None:
@@ -139,6 +149,68 @@ class _FusedQuantOptimizer(Optimizer):
             from ..layers.sign_layers import _SignLinear
             self._plane_layers = {m.weight: m for m in module.modules() if isinstance(m, _SignLinear)}
         self._plane_words = {}
+        self.max_grad_norm = max_grad_norm         # an attribute of the optimiser, not a group entry: the norm is global
+        self._clip_work = None                     # eager step(): workspace of the sum-of-squares pass, grown on demand
+        self._clip_out = None                      # eager step(): (norm, coef)
+        self._clip_last = None                     # the (norm, coef) words of the last clipped step, whichever path took it
+
+    @property
+    def max_grad_norm(self):
+        """``max_norm`` of the ``torch.nn.utils.clip_grad_norm_`` folded into the step (L2 norm over every parameter of every
+        group that has a gradient), or None: no clipping.  Assignable between steps, also between replays of a captured step
+        (the value travels with the other per-step scalars); switching clipping on or off needs a new capture."""
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        if value is not None:
+            if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or value <= 0:
+                raise ValueError(f"{type(self).__name__}: max_grad_norm must be a positive finite number or None, got {value!r}")
+            value = float(value)
+        self._max_grad_norm = value
+
+    @property
+    def grad_norm(self):
+        """0-dim fp32 tensor on the parameters' device: the global gradient norm of the last clipped step, before clipping (None
+        before the first).  Reading its value is the caller's synchronise; the step has none."""
+        return None if self._clip_last is None else self._clip_last[0]
+
+    @property
+    def clip_coef(self):
+        """0-dim fp32 tensor: ``min(1, max_grad_norm / (grad_norm + 1e-6))`` of the last clipped step, what its gradients were
+        multiplied by (None before the first)."""
+        return None if self._clip_last is None else self._clip_last[1]
+
+    def _clip(self):
+        """The clipping part of an eager ``step()``.  Returns the one-element device tensor the update launches multiply the
+        gradients by, or None when there is nothing left for them to do: no ``max_grad_norm``, no gradient, or — a parameter off
+        the kernel's route, parameters on more than one device — ``torch.nn.utils.clip_grad_norm_`` over all parameters, which
+        rewrites the gradients in place as torch does and is counted once in ``_fused.LIBRARY_PATHS``."""
+        if self._max_grad_norm is None:
+            return None
+        params = [p for group in self.param_groups for p in group["params"] if p.grad is not None]
+        if not params:
+            return None
+        off = None
+        for p in params:
+            st = self.state.get(p) or {}
+            if not _on_route(p, p.grad, *(st[k] for k in self._STATE_KEYS if st.get(k) is not None)) or p.device != params[0].device:
+                off = p
+                break
+        if off is not None:
+            _fused.note_library_path(off, "optimiser step: clip_grad_norm_ (a parameter off the fused kernel's route)")
+            norm = torch.nn.utils.clip_grad_norm_(params, self._max_grad_norm).detach().to(torch.float32)
+            self._clip_last = torch.stack([norm, torch.clamp(self._max_grad_norm / (norm + 1e-6), max=1.0)])
+            return None
+        grads = [p.grad for p in params]
+        device, m = params[0].device, sum((g.numel() + 4095) >> 12 for g in grads)      # one word per 4096-element unit
+        if self._clip_out is None or self._clip_out.device != device:
+            self._clip_out, self._clip_work = torch.zeros(2, dtype=torch.float32, device=device), None
+        if self._clip_work is None or self._clip_work.numel() < m:
+            self._clip_work = torch.empty(max(m, 1), dtype=torch.float32, device=device)
+        ops.optim_grad_norm(grads, self._clip_work, self._clip_out, max_norm=self._max_grad_norm)
+        self._clip_last = self._clip_out
+        return self._clip_out[1:]
 
     def _plane_of(self, p):
         """(NibPlanes, kind) of the persistent plane buffer of a deterministic LinearBin / LinearTer weight, else None."""
@@ -195,7 +267,8 @@ class _FusedQuantOptimizer(Optimizer):
         """Fix what a captured step updates — every parameter that has a gradient NOW, with its state allocated
         (``allocate_state``) — and allocate one device block for the per-step scalars of its launch sequences.  Returns the
         ``_Capture`` the other capture-mode methods take; every call makes a new one with a block of its own, and earlier ones stay
-        valid.  A captured step has no library path: a parameter off the kernel's route (host, non-fp32, non-contiguous), a sparse
+        valid.  With ``max_grad_norm`` set the block gains one slot for it, and the capture its own workspace and (norm, coef)
+        words for the norm launches: allocated here, outside the stream capture.  A captured step has no library path: a parameter off the kernel's route (host, non-fp32, non-contiguous), a sparse
         gradient or parameters on more than one device raise ``ValueError`` naming the parameter."""
         self.allocate_state()
         groups, device, numel = [], None, 0
@@ -219,14 +292,21 @@ class _FusedQuantOptimizer(Optimizer):
         # ONE block for the scalars of all groups.  before_replay() rewrites it with a launch that carries the values in its argument
         # block (ops.optim_write_scalars): stream-ordered between the previous replay and the next, no synchronise, and no host
         # staging buffer an earlier, still pending write could be reading — the runtime copies the arguments at enqueue time.
-        block = torch.zeros(numel, dtype=torch.float32, device=device) if groups else None
+        clip = groups and self._max_grad_norm is not None
+        block = torch.zeros(numel + (1 if clip else 0), dtype=torch.float32, device=device) if groups else None
         for cg in groups:
             cg.scalars = block[cg.offset:cg.offset + cg.numel]
             cg.states = [self._allocate(p, self.param_groups[cg.index]) for p in cg.params]
             cg.steps = [self.state[p]["step"] for p in cg.params if "step" in self.state[p]]
             cg.planes = [self._plane_of(p) for p in cg.params]
             cg.clamps = [self._clamp_plan.get(p) for p in cg.params]
-        return _Capture(groups, block, self._state_epoch)
+        capture = _Capture(groups, block, self._state_epoch)
+        if clip:
+            m = ops.optim_grad_norm_work_floats([g for cg in groups for g in cg.grads])
+            capture.max_norm = block[numel:]
+            capture.norm_work = torch.empty(max(m, 1), dtype=torch.float32, device=device)
+            capture.norm_out = torch.zeros(2, dtype=torch.float32, device=device)
+        return capture
 
     def load_state_dict(self, state_dict):
         """``Optimizer.load_state_dict``.  It replaces every state tensor, so captured steps of this optimiser would go on updating
@@ -262,7 +342,7 @@ class _FusedQuantOptimizer(Optimizer):
                 packed += 1
         return packed
 
-    def _launch_captured(self, cg, skip=None):     # pragma: no cover - abstract
+    def _launch_captured(self, cg, skip=None, gscale=None):     # pragma: no cover - abstract
         raise NotImplementedError
 
     @staticmethod
@@ -275,13 +355,20 @@ class _FusedQuantOptimizer(Optimizer):
         """The update of every captured parameter on the current stream, with the clamps and planes of ``step()`` — the launches a
         stream capture records.  Nothing on the host changes: ``before_replay`` / ``after_replay`` do what ``step()`` does there.
         ``skip``: one int32 device element the launches read when they RUN (the guarded entries, ``ops.optim_step_*_dev(skip=)``):
-        non-zero and the step leaves parameters, state and planes as they are — ``cancel_replay`` is its host side."""
+        non-zero and the step leaves parameters, state and planes as they are — ``cancel_replay`` is its host side.  A capture
+        with clipping enqueues the norm launches over the gradients of ALL its groups first; they write the capture's own
+        workspace and (norm, coef) words and nothing else, so a skipped step still leaves parameters, state and planes alone."""
         if skip is not None and self._post_clamp:
             # their clamp() is arbitrary torch code: nothing here could make it depend on a device word
             raise ValueError(f"{type(self).__name__}: a guarded captured step cannot skip the clamp() of "
                              f"{sorted({type(m).__name__ for m in self._post_clamp})}, which clamp_plan cannot restate")
+        gscale = None
+        if capture.norm_out is not None:
+            ops.optim_grad_norm([g for cg in capture.groups for g in cg.grads], capture.norm_work, capture.norm_out,
+                                max_norm_dev=capture.max_norm)
+            gscale = capture.norm_out[1:]
         for cg in capture.groups:
-            self._launch_captured(cg, skip)
+            self._launch_captured(cg, skip, gscale)
         for m in self._post_clamp:                 # clamp() of layers clamp_plan cannot restate: torch ops, captured as well
             m.clamp()
 
@@ -298,6 +385,11 @@ class _FusedQuantOptimizer(Optimizer):
         if capture.state_epoch != self._state_epoch:
             raise RuntimeError(f"{type(self).__name__}: load_state_dict() replaced the state tensors since the step was captured; the "
                                "graph still updates the old ones — load the state first, then capture a new GraphedTrainStep")
+        if capture.groups and (self._max_grad_norm is not None) != (capture.norm_out is not None):
+            was, now = ("on", "off") if self._max_grad_norm is None else ("off", "on")
+            raise RuntimeError(f"{type(self).__name__}: gradient clipping was {was} when the step was captured and is {now} now "
+                               f"(max_grad_norm={self._max_grad_norm!r}); its launches are baked into the graph — capture a new "
+                               "GraphedTrainStep (a change of the VALUE reaches the replay)")
         for cg in capture.groups:
             group = self.param_groups[cg.index]
             self._check_group(group)
@@ -316,6 +408,8 @@ class _FusedQuantOptimizer(Optimizer):
         values = []
         for cg in capture.groups:
             values += self._scalars_of(cg)
+        if capture.norm_out is not None:
+            values.append(self._max_grad_norm)     # the block's last slot
         if capture.block is not None:
             ops.optim_write_scalars(capture.block, values)
         for cg in capture.groups:
@@ -337,6 +431,8 @@ class _FusedQuantOptimizer(Optimizer):
         """Host side of a replay, after it: what ``step()`` does after its launches (version counters, plane records)."""
         for cg in capture.groups:
             self._record(cg.params, cg.planes)
+        if capture.norm_out is not None:
+            self._clip_last = capture.norm_out
         if hasattr(self.step, "_wrapped_by_lr_sched"):
             # torch/optim/lr_scheduler.py (LRScheduler.__init__, patch_track_step_called) wraps step() to set this flag and warns
             # "lr_scheduler.step() before optimizer.step()" while it is unset; a replay IS a step.  Without that wrapper: nothing to do.
@@ -380,10 +476,19 @@ class FusedQuantSGD(_FusedQuantOptimizer):
     ``params``: an ``nn.Module`` (clamp and planes available) or an iterable of parameters / param groups (plain update).
     ``clamp`` / ``emit_planes``: default on when a module is given.  Parameters off the kernel's route (host tensors, non-fp32,
     non-contiguous, sparse gradient) take ``torch.optim``'s functional ``sgd`` in the same ``step()``, followed by their
-    clamp; they are counted in ``_fused.LIBRARY_PATHS``."""
+    clamp; they are counted in ``_fused.LIBRARY_PATHS``.
+
+    ``max_grad_norm``: positive and finite, or None (default, no clipping).  The step then clips the global L2 gradient norm as
+    ``torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm)`` in front of it would — over every parameter of every group
+    that has a gradient — but inside the update: the gradients are read once more for their sum of squares and the update
+    multiplies them by the coefficient as it reads them.  ``p.grad`` is NOT rewritten: after the step it still holds the
+    unscaled gradient.  ``opt.grad_norm`` / ``opt.clip_coef`` are 0-dim fp32 device tensors with the step's pre-clip norm and
+    coefficient; no host synchronise is involved.  If any parameter with a gradient is off the kernel's route, or they live on
+    more than one device, the whole step is ``clip_grad_norm_`` over all of them (which does rewrite the gradients) followed
+    by the ordinary step.  L2 only; a non-finite norm is not special (``error_if_nonfinite=False``)."""
 
     def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, *, maximize=False,
-                 foreach=None, differentiable=False, fused=None, clamp=None, emit_planes=None):
+                 foreach=None, differentiable=False, fused=None, clamp=None, emit_planes=None, max_grad_norm=None):
         _reject("FusedQuantSGD", maximize=maximize, dampening=dampening != 0, differentiable=differentiable, foreach=foreach,
                 fused=fused)
         if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
@@ -392,9 +497,10 @@ class FusedQuantSGD(_FusedQuantOptimizer):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
                         maximize=False, foreach=None, differentiable=False, fused=None)
-        super().__init__(params, defaults, clamp, emit_planes)
+        super().__init__(params, defaults, clamp, emit_planes, max_grad_norm)
 
     _BAKED = ("momentum", "weight_decay", "nesterov")
+    _STATE_KEYS = ("momentum_buffer",)
 
     def _check_group(self, group):
         _reject("FusedQuantSGD", maximize=group["maximize"], dampening=group["dampening"] != 0)
@@ -411,12 +517,12 @@ class FusedQuantSGD(_FusedQuantOptimizer):
     def _scalars_per_group(n):
         return 1
 
-    def _launch_captured(self, cg, skip=None):
+    def _launch_captured(self, cg, skip=None, gscale=None):
         # no first-step flag: the buffers exist, and from a zeroed buffer mu * 0 + g IS the first step's value (see allocate_state)
         mu = cg.baked["momentum"]
         ops.optim_step_sgd_dev(cg.params, [p.grad for p in cg.params], [st[0] for st in cg.states] if mu != 0 else None, cg.scalars,
                                momentum=mu, weight_decay=cg.baked["weight_decay"], nesterov=cg.baked["nesterov"], clamps=cg.clamps,
-                               planes=cg.planes, skip=skip)
+                               planes=cg.planes, skip=skip, gscale=gscale)
 
     def _scalars_of(self, cg):
         return [float(self.param_groups[cg.index]["lr"])]
@@ -428,10 +534,11 @@ class FusedQuantSGD(_FusedQuantOptimizer):
             with torch.enable_grad():
                 loss = closure()
         off_route = []
+        gscale = self._clip()
         for group in self.param_groups:
             self._check_group(group)
             lr, mu, wd, nesterov = group["lr"], group["momentum"], group["weight_decay"], group["nesterov"]
-            fused, library = self._split(group, ("momentum_buffer",))
+            fused, library = self._split(group, self._STATE_KEYS)
             for plist in fused.values():
                 bufs, first = None, None
                 if mu != 0:
@@ -445,7 +552,7 @@ class FusedQuantSGD(_FusedQuantOptimizer):
                         bufs.append(buf)
                 planes = [self._plane_of(p) for p in plist]
                 ops.optim_step_sgd(plist, [p.grad for p in plist], bufs, lr=lr, momentum=mu, weight_decay=wd, nesterov=nesterov,
-                                   first=first, clamps=[self._clamp_plan.get(p) for p in plist], planes=planes)
+                                   first=first, clamps=[self._clamp_plan.get(p) for p in plist], planes=planes, gscale=gscale)
                 self._record(plist, planes)
             if library:
                 bufs = [self.state[p].get("momentum_buffer") for p in library]
@@ -462,12 +569,13 @@ class FusedQuantSGD(_FusedQuantOptimizer):
 
 class FusedQuantAdam(_FusedQuantOptimizer):
     """``torch.optim.Adam`` (betas, eps, L2 weight decay; no amsgrad) + ``model.clamp()`` + weight planes in one launch sequence
-    per parameter group.  Arguments and the handling of parameters off the kernel's route as in ``FusedQuantSGD``; ``step`` is
+    per parameter group.  Arguments (``max_grad_norm`` included: ``p.grad`` stays unscaled on the fused path) and the handling of
+    parameters off the kernel's route as in ``FusedQuantSGD``; ``step`` is
     kept per parameter as torch keeps it (a host scalar tensor) and the bias corrections are computed from it every step."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, *, foreach=None,
                  maximize=False, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False, clamp=None,
-                 emit_planes=None):
+                 emit_planes=None, max_grad_norm=None):
         _reject("FusedQuantAdam", amsgrad=amsgrad, maximize=maximize, capturable=capturable, differentiable=differentiable,
                 foreach=foreach, fused=fused, decoupled_weight_decay=decoupled_weight_decay)
         if isinstance(lr, torch.Tensor):
@@ -476,9 +584,10 @@ class FusedQuantAdam(_FusedQuantOptimizer):
             raise ValueError("FusedQuantAdam: lr / eps / weight_decay negative or a beta outside [0, 1)")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None,
                         capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False)
-        super().__init__(params, defaults, clamp, emit_planes)
+        super().__init__(params, defaults, clamp, emit_planes, max_grad_norm)
 
     _BAKED = ("betas", "eps", "weight_decay")
+    _STATE_KEYS = ("exp_avg", "exp_avg_sq")
 
     def _check_group(self, group):
         _reject("FusedQuantAdam", amsgrad=group["amsgrad"], maximize=group["maximize"], capturable=group["capturable"],
@@ -492,10 +601,10 @@ class FusedQuantAdam(_FusedQuantOptimizer):
     def _scalars_per_group(n):
         return 2 * n
 
-    def _launch_captured(self, cg, skip=None):
+    def _launch_captured(self, cg, skip=None, gscale=None):
         ops.optim_step_adam_dev(cg.params, [p.grad for p in cg.params], [st[0] for st in cg.states], [st[1] for st in cg.states],
                                 cg.scalars, betas=cg.baked["betas"], eps=cg.baked["eps"], weight_decay=cg.baked["weight_decay"],
-                                clamps=cg.clamps, planes=cg.planes, skip=skip)
+                                clamps=cg.clamps, planes=cg.planes, skip=skip, gscale=gscale)
 
     def _scalars_of(self, cg):
         # the step counts are read from state["step"], so eager step() calls between replays are counted too
@@ -517,13 +626,20 @@ class FusedQuantAdam(_FusedQuantOptimizer):
             with torch.enable_grad():
                 loss = closure()
         off_route = []
+        if self._max_grad_norm is not None:        # the state first: the clip's route check looks at it
+            for group in self.param_groups:
+                self._check_group(group)
+                for p in group["params"]:
+                    if p.grad is not None:
+                        self._init_state(p)
+        gscale = self._clip()
         for group in self.param_groups:
             self._check_group(group)
             lr, betas, eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
             for p in group["params"]:
                 if p.grad is not None:
                     self._init_state(p)
-            fused, library = self._split(group, ("exp_avg", "exp_avg_sq"))
+            fused, library = self._split(group, self._STATE_KEYS)
             for plist in fused.values():
                 states = [self.state[p] for p in plist]
                 steps = []
@@ -533,7 +649,7 @@ class FusedQuantAdam(_FusedQuantOptimizer):
                 planes = [self._plane_of(p) for p in plist]
                 ops.optim_step_adam(plist, [p.grad for p in plist], [st["exp_avg"] for st in states],
                                     [st["exp_avg_sq"] for st in states], steps, lr=lr, betas=betas, eps=eps, weight_decay=wd,
-                                    clamps=[self._clamp_plan.get(p) for p in plist], planes=planes)
+                                    clamps=[self._clamp_plan.get(p) for p in plist], planes=planes, gscale=gscale)
                 self._record(plist, planes)
             if library:
                 states = [self.state[p] for p in library]

@@ -13,6 +13,12 @@ Both sides of a comparison are measured in the same process in alternating round
 implicit hipGraphs are switched off (QT_AUTO_GRAPH=0) so that every call launches what it launches.
 
     python tools/bench_fused_optim.py [--rounds 9] [--steps 20] [--out profiles/fused_optim_bench_line.json]
+
+--clip measures gradient-norm clipping instead, same protocol, same three parameter sets: what a user does without it —
+torch.nn.utils.clip_grad_norm_(params, max_norm, foreach=True) followed by the unclipped FusedQuant*.step() — against the
+clipped fused step (max_grad_norm=), with the unclipped fused step alongside so that the cost of the norm pass itself shows.
+
+    python tools/bench_fused_optim.py --clip [--out profiles/fused_clip_bench_line.json]
 """
 import argparse
 import json
@@ -95,6 +101,42 @@ def bench_steps(dev, rounds, steps):
     return out
 
 
+def bench_clip(dev, rounds, steps, max_norm=1.0):
+    out = {}
+    variants = {"sgd": (utils.FusedQuantSGD, dict(lr=1e-2, momentum=0.9, weight_decay=1e-4)), "adam": (utils.FusedQuantAdam, dict(lr=1e-3))}
+    for name, make in param_sets(dev):
+        res = {}
+        for vname, (Fused, hp) in variants.items():
+            models = []
+            for _ in range(3):
+                torch.manual_seed(0)
+                models.append(make())
+                set_grads(models[-1], 1)
+            a, b, c = models
+            base, clipped, plain = Fused(a, **hp), Fused(b, max_grad_norm=max_norm, **hp), Fused(c, **hp)
+            params = [p for p in a.parameters() if p.grad is not None]
+
+            def torch_clip_then_fused():
+                torch.nn.utils.clip_grad_norm_(params, max_norm, foreach=True)      # rewrites the gradients in place
+                base.step()
+
+            med, raw = alternate({"torch_clip_then_fused": torch_clip_then_fused, "fused_clip": clipped.step, "fused_unclipped": plain.step},
+                                 rounds, steps)
+            assert float(clipped.clip_coef) < 1.0, "the clip does not act: the comparison would time a no-op"
+            res[vname] = {"torch_clip_then_fused_us": med["torch_clip_then_fused"], "fused_clip_us": med["fused_clip"],
+                          "fused_unclipped_us": med["fused_unclipped"],
+                          "speedup": round(med["torch_clip_then_fused"] / med["fused_clip"], 2),
+                          "norm_pass_us": round(med["fused_clip"] - med["fused_unclipped"], 1),
+                          "torch_clip_then_fused_rounds_us": raw["torch_clip_then_fused"], "fused_clip_rounds_us": raw["fused_clip"],
+                          "fused_unclipped_rounds_us": raw["fused_unclipped"]}
+            del models, a, b, c, base, clipped, plain, params
+        n = sum(p.numel() for p in make().parameters())
+        res["parameters"] = n
+        res["norm_pass_bytes"] = 4 * n                                               # every gradient read once
+        out[name] = res
+    return out
+
+
 def bench_forward(dev, rounds, steps):
     torch.manual_seed(0)
     layer, twin = LinearBin(4096, 4096).to(dev).train(), LinearBin(4096, 4096).to(dev).train()
@@ -121,15 +163,24 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join("profiles", "fused_optim_bench_line.json"))
+    ap.add_argument("--clip", action="store_true", help="measure gradient-norm clipping (see the module docstring)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join("profiles", "fused_clip_bench_line.json" if args.clip else "fused_optim_bench_line.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_fused_optim.py measures on a GPU; none is visible")
     dev = torch.device("cuda:0")
     name, cus = _lib.device_info()
-    line = {"what": "optimizer.step() + clamp: torch.optim + clamp_weights_ vs the fused update; LinearBin train forward with / without "
-                    "the emitted weight plane", "device": name, "rounds": args.rounds, "steps_per_round": args.steps,
-            "step": bench_steps(dev, args.rounds, args.steps), "forward_linear_bin_4096_b4096": bench_forward(dev, args.rounds, args.steps)}
+    if args.clip:
+        line = {"what": "gradient-norm clipping: clip_grad_norm_(foreach=True) + unclipped fused step vs the clipped fused step "
+                        "(max_grad_norm=) vs the unclipped fused step", "device": name, "rounds": args.rounds,
+                "steps_per_round": args.steps, "max_norm": 1.0, "step": bench_clip(dev, args.rounds, args.steps)}
+    else:
+        line = {"what": "optimizer.step() + clamp: torch.optim + clamp_weights_ vs the fused update; LinearBin train forward with / "
+                        "without the emitted weight plane", "device": name, "rounds": args.rounds, "steps_per_round": args.steps,
+                "step": bench_steps(dev, args.rounds, args.steps),
+                "forward_linear_bin_4096_b4096": bench_forward(dev, args.rounds, args.steps)}
     text = json.dumps(line)
     print(text)
     if args.out:
