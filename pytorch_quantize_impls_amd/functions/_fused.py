@@ -1018,13 +1018,9 @@ class QuantConv2dFn(QtFunction):
         go = _dense(grad_output)
         mfma = own_conv_backward(go, groups, padding, go.numel() * weight[0].numel())
         if ctx.needs_input_grad[0]:
-            if mfma:     # real gradient x +-1 / 0 weight: the forward's exact-split conv on flipped weights (the deterministic
-                #          quantiser runs inside the operand pack; a stochastic draw was saved)
-                grad_input = (ops.conv2d_grad_input_q(input.shape, weight_q, go, stride, padding, dilation) if weight_q is not None
-                              else ops.conv2d_grad_input_q(input.shape, weight, go, stride, padding, dilation, kind=ctx.kind))
-            if grad_input is None:
-                wq = weight_q if weight_q is not None else quantize_weight_f32(weight, ctx.kind)
-                grad_input = lib_conv2d_input(input.shape, wq, go, stride, padding, dilation, groups)
+            # real gradient x +-1 / 0 weight: the deterministic quantiser runs inside the operand pack; a stochastic draw was saved
+            grad_input = conv_grad_input(input, weight if weight_q is None else weight_q, go, stride, padding, dilation, groups, W_PM1,
+                                         quantiser=ctx.kind if weight_q is None else "sign", gate=mfma)
         want_bias = ctx.has_bias and ctx.needs_input_grad[2]
         bias_by_product = []              # filled by the weight-gradient route when its gradient pack can sum the channels on the way
         if ctx.needs_input_grad[1]:
@@ -1149,6 +1145,38 @@ def conv_grad_weight_routes(input, go, weight_shape, stride, padding, dilation, 
     return gw
 
 
+#: the weight of an input gradient (``conv_grad_input_routes``): +-1 / 0, or the latent weight with its ``quantiser``; levels x
+#: ``out_scale``; ``operand`` = the packed Lin / Log grad_x planes; sign(W) with ``operand`` = XNOR-Net's TapScales.bwd; real-valued
+W_PM1, W_LEVELS, W_PACKED, W_TAPS, W_REAL = "pm1", "levels", "packed", "taps", "real"
+
+
+def conv_grad_input_routes(input, weight, go, stride, padding, dilation, w_kind, quantiser: str = "sign", out_scale: float = 1.0,
+                           out_scale_dev: Optional[torch.Tensor] = None, operand=None, taken: Optional[list] = None):
+    """THE ladder of this backend's input-gradient routes: grad wrt the input of conv2d(x, Q(weight)) for the dense fp32 gradient
+    ``go`` as the stride-1 conv of ``ops.grad_input_operand`` with the flipped, transposed weight, on the rung ``w_kind`` names
+    (W_PM1 / W_LEVELS / W_PACKED: the exact-split conv, W_TAPS: the per-tap scaled fp16 conv, W_REAL: the six-term real one); None
+    outside ``ops.grad_input_route_applicable`` or when the rung returns None — library and gate are the caller's.  A channels-last
+    view, copied for an ``input`` in NCHW storage by W_PACKED and W_REAL.  ``taken``: receives the rung's name (q / taps / real)."""
+    gx = None
+    if w_kind in (W_PM1, W_LEVELS, W_PACKED):     # W_PACKED: three exact terms of g; ``weight`` only gives the shape
+        gx = ops.conv2d_grad_input_q(input.shape, weight, go, stride, padding, dilation, kind=quantiser if w_kind == W_PM1 else "raw",
+                                     out_scale=out_scale, out_scale_dev=out_scale_dev, terms=3 if w_kind == W_PACKED else None,
+                                     weight_triples=operand)
+        if w_kind == W_PACKED and gx is not None and input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
+            gx = gx.contiguous()          # (as ``nchw_result`` below)
+    elif w_kind == W_TAPS:
+        gx = ops.conv2d_grad_input_taps(input.shape, weight, go, operand, stride, padding, dilation)
+    elif ops.grad_input_route_applicable(weight.shape, stride, padding, dilation):
+        wt = weight.detach().flip(2, 3).transpose(0, 1).contiguous()
+        op = ops.grad_input_operand(go, input.shape, weight.shape, stride, padding, dilation)
+        y2 = ops.real_conv2d(op[0], wt, None, 1, op[1], 1) if op is not None else None
+        if y2 is not None:
+            gx = nchw_result(y2, input, *(int(input.shape[i]) for i in (0, 2, 3, 1)))
+    if gx is not None and taken is not None:
+        taken.append({W_TAPS: "taps", W_REAL: "real"}.get(w_kind, "q"))
+    return gx
+
+
 def _hip2d(*ts) -> bool:
     return all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.numel() > 0 for t in ts)
 
@@ -1193,23 +1221,23 @@ def dense_grad_weight(grad_output: torch.Tensor, input: torch.Tensor, x_is_pm1: 
     return lib_mm(grad_output.t(), input)
 
 
-def conv_grad_input(input_shape, weight_q, grad_output, stride, padding, dilation, groups, kind="raw", out_scale=1.0,
-                    out_scale_dev=None):
-    """grad wrt the input of conv2d(x, weight_q) for an image that is exact in fp16 / bf16 (``kind`` "sign" / "binary" /
-    "ternary": +-1 / 0; "raw": small integers or multiples of 1/2, the caller scales) on ops.conv2d_grad_input_q; anything else
-    (groups, dilation, a real-valued image) on the library, counted."""
+def conv_grad_input(input, weight, grad_output, stride, padding, dilation, groups, w_kind, quantiser: str = "sign",
+                    out_scale: float = 1.0, out_scale_dev=None, operand=None, gate: Optional[bool] = None, lib_weight=None):
+    """grad wrt the input of conv2d(x, Q(weight)) on ``conv_grad_input_routes`` behind ``gate`` (None: the functional forms' —
+    ``own_conv_backward`` and a non-empty gradient); ``w_kind`` None (a real-valued image, DoReFa at 8 < k <= 32), a closed gate
+    or no answer: the library, counted, on ``lib_weight()`` (default: the quantised ``weight`` times the scales), built only then."""
     go = _dense(grad_output)
-    if kind is not None and own_conv_backward(go, groups, padding) and go.numel() > 0:
-        gx = ops.conv2d_grad_input_q(input_shape, weight_q, go, stride, padding, dilation, kind=kind, out_scale=out_scale,
-                                     out_scale_dev=out_scale_dev)
+    if gate is None:
+        gate = own_conv_backward(go, groups, padding) and go.numel() > 0
+    if gate and w_kind is not None:
+        gx = conv_grad_input_routes(input, weight, go, stride, padding, dilation, w_kind, quantiser, out_scale, out_scale_dev, operand)
         if gx is not None:
             return gx
-    wq = weight_q
-    if kind in ("binary", "ternary"):
-        wq = quantize_weight_f32(weight_q, kind)
-    if out_scale_dev is not None or out_scale != 1.0:
+    wq = lib_weight() if lib_weight is not None else \
+        quantize_weight_f32(weight, quantiser) if quantiser in ("binary", "ternary") else weight
+    if lib_weight is None and (out_scale_dev is not None or out_scale != 1.0):
         wq = wq * (float(out_scale) if out_scale_dev is None else out_scale_dev * float(out_scale))
-    return lib_conv2d_input(input_shape, wq, grad_output, stride, padding, dilation, groups)
+    return lib_conv2d_input(input.shape, wq, grad_output, stride, padding, dilation, groups)
 
 
 def conv_grad_weight(input, weight_shape, grad_output, stride, padding, dilation, groups, x_is_pm1: bool, bias_by_product=None,
@@ -1582,12 +1610,9 @@ class DorefaW1Conv2dFn(QtFunction):
         mfma = own_conv_backward(go, groups, padding, go.numel() * weight[0].numel())
         if ctx.needs_input_grad[0]:
             E = ctx.E if ctx.E is not None else ops.abs_mean(weight)
-            if mfma:     # g * (sign(W) E) = E * (g * sign(W)): the exact-split conv on the flipped +-1 weight, scaled after
-                grad_input = ops.conv2d_grad_input_q(input.shape, weight, go, stride, padding, dilation, kind="binary",
-                                                     out_scale_dev=E)
-            if grad_input is None:
-                grad_input = lib_conv2d_input(input.shape, quantize_weight_f32(weight, "binary") * E, go, stride, padding, dilation,
-                                              groups)
+            # g * (sign(W) E) = E * (g * sign(W)): the exact-split conv on the flipped +-1 weight, scaled after
+            grad_input = conv_grad_input(input, weight, go, stride, padding, dilation, groups, W_PM1, quantiser="binary", out_scale_dev=E,
+                                         gate=mfma, lib_weight=lambda: quantize_weight_f32(weight, "binary") * E)
         if ctx.needs_input_grad[1]:
             if mfma and ctx.x_levels is not None and ctx.x_levels <= 255:
                 # UNscaled and un-masked, as upstream (_ignore_factor_op, identity STE): functions/dorefa_connect.py:66-79
@@ -1696,11 +1721,8 @@ class DorefaWkConv2dFn(QtFunction):
         grad_input = grad_weight = grad_bias = None
         mfma = own_conv_backward(go, groups, padding, go.numel() * weight_q[0].numel())
         if ctx.needs_input_grad[0]:
-            if mfma:
-                grad_input = ops.conv2d_grad_input_q(input.shape, _weight_levels(weight_q, k), go, stride, padding, dilation,
-                                                     kind="raw", out_scale=_inv_levels(k))
-            if grad_input is None:
-                grad_input = lib_conv2d_input(input.shape, weight_q, go, stride, padding, dilation, groups)
+            grad_input = conv_grad_input(input, _weight_levels(weight_q, k) if mfma else None, go, stride, padding, dilation, groups,
+                                         W_LEVELS, out_scale=_inv_levels(k), gate=mfma, lib_weight=lambda: weight_q)
         if ctx.needs_input_grad[1]:
             if mfma and ctx.x_levels is not None:
                 grad_weight = dorefa_conv_grad_weight(input, go, weight_q.shape, stride, padding, dilation, ctx.x_levels, ctx.codes_fit,
@@ -1804,19 +1826,9 @@ class RealConv2dFn(QtFunction):
         stride, padding, dilation, groups = ctx.conv_args
         go = _dense(grad_output)
         grad_input = grad_weight = grad_bias = None
-        kh, kw = int(weight.shape[2]), int(weight.shape[3])
-        (sh, sw), (ph, pw), (dh, dw) = ops._pairs(stride), ops._pairs(padding), ops._pairs(dilation)
         if ctx.needs_input_grad[0]:
-            if (go.is_cuda and go.dtype == torch.float32 and go.numel() > 0 and sh == sw and (dh, dw) == (1, 1)
-                    and ph <= kh - 1 and pw <= kw - 1):
-                wt = weight.detach().flip(2, 3).transpose(0, 1).contiguous()
-                gd = go if sh == 1 else ops.zero_dilated_gradient(go, input.shape, (kh, kw), sh, (ph, pw))   # stride s: conv_transpose
-                y2 = ops.real_conv2d(gd, wt, None, 1, (kh - 1 - ph, kw - 1 - pw), 1) if gd is not None else None
-                if y2 is not None:
-                    N_, C, H, W = input.shape
-                    grad_input = nchw_result(y2, input, N_, H, W, C)
-            if grad_input is None:
-                grad_input = lib_conv2d_input(input.shape, weight, go, stride, padding, dilation, groups)
+            grad_input = conv_grad_input(input, weight, go, stride, padding, dilation, groups, W_REAL,
+                                         gate=go.is_cuda and go.dtype == torch.float32 and go.numel() > 0)
         if ctx.needs_input_grad[1]:
             grad_weight = conv_grad_weight(input, weight.shape, go, stride, padding, dilation, groups, x_is_pm1=False,
                                            real_any_channels=True)
@@ -1877,16 +1889,9 @@ class LogLinLinearFn(QtFunction):
         return grad_input, grad_weight, grad_bias, None
 
 
-def _conv_grad_input_route(weight_shape, stride, padding, dilation) -> bool:
-    """Geometry ops.conv2d_grad_input_q takes (square stride, un-dilated, padding <= k - 1)."""
-    (sh, sw), (ph, pw), (dh, dw) = ops._pairs(stride), ops._pairs(padding), ops._pairs(dilation)
-    kh, kw = int(weight_shape[2]), int(weight_shape[3])
-    return (dh, dw) == (1, 1) and sh == sw and sh >= 1 and ph <= kh - 1 and pw <= kw - 1
-
-
 class LogLinConv2dFn(QtFunction):
     """F.conv2d(x, Q(W), b) (groups == 1, zero padding) for a device fp32 NCHW / channels-last x, Q as in LogLinLinearFn.  grad_x
-    outside conv2d_grad_input_q's geometry (dilation, non-square stride, ...) uses the counted library helper on Q(W), whose fp32
+    outside ops.grad_input_route_applicable (dilation, non-square stride, ...) uses the counted library helper on Q(W), whose fp32
     image then comes from the same pack launch."""
 
     @staticmethod
@@ -1895,7 +1900,7 @@ class LogLinConv2dFn(QtFunction):
         ctx.has_bias, ctx.conv_args, ctx.quant = bias is not None, conv_args, quant
         ctx.save_for_backward(input, weight)
         want_gx = ctx.needs_input_grad[0]
-        routed = _conv_grad_input_route(weight.shape, stride, padding, dilation)
+        routed = ops.grad_input_route_applicable(weight.shape, stride, padding, dilation)    # what the backward's rung will take
         planes, flag = loglin_act_planes(input, weight, packed.NHWC)
         ctx.x_exact = planes is not None
         fwd, gx, wq = ops.pack_levels_bf16x3(weight, *quant, grad_x=want_gx and routed, image=want_gx and not routed,
@@ -1919,17 +1924,10 @@ class LogLinConv2dFn(QtFunction):
         go = _dense(grad_output)
         grad_input = grad_weight = grad_bias = None
         if ctx.needs_input_grad[0]:
-            if ctx.gx is not None and go.numel() > 0:
-                shape = torch.empty(ctx.w_shape, dtype=torch.float32, device="meta")
-                grad_input = ops.conv2d_grad_input_q(input.shape, shape, go, stride, padding, dilation, kind="raw", terms=3,
-                                                     weight_triples=ctx.gx)
-                if grad_input is not None and input.is_contiguous() and not input.is_contiguous(memory_format=torch.channels_last):
-                    grad_input = grad_input.contiguous()
-            if grad_input is None:
-                wq = ctx.wq
-                if wq is None:            # (an empty gradient: nothing was packed for it)
-                    _, _, wq = ops.pack_levels_bf16x3(weight, *ctx.quant, forward=False, grad_x=False, image=True)
-                grad_input = lib_conv2d_input(input.shape, wq, go, stride, padding, dilation, groups)
+            def image():                  # the forward's; an empty gradient: nothing was packed for it
+                return ctx.wq if ctx.wq is not None else ops.pack_levels_bf16x3(weight, *ctx.quant, forward=False, grad_x=False, image=True)[2]
+            grad_input = conv_grad_input(input, weight, go, stride, padding, dilation, groups, W_PACKED, operand=ctx.gx,
+                                         gate=ctx.gx is not None and go.numel() > 0, lib_weight=image)
         if ctx.needs_input_grad[1]:
             grad_weight = conv_grad_weight(input, ctx.w_shape, go, stride, padding, dilation, groups, x_is_pm1=False,
                                            real_any_channels=True, x_exact_bf16=ctx.x_exact)

@@ -135,8 +135,8 @@ def BinaryConv2d(stride=1, padding=1, dilation=1, groups=1):
             input, weight, bias = ctx.saved_tensors
             grad_input = grad_weight = grad_bias = None
             if ctx.needs_input_grad[0]:
-                grad_input = _fused.conv_grad_input(input.size(), weight, grad_output, stride, padding, dilation, groups,
-                                                    kind="binary")
+                grad_input = _fused.conv_grad_input(input, weight, grad_output, stride, padding, dilation, groups, _fused.W_PM1,
+                                                    quantiser="binary")
             if ctx.needs_input_grad[1]:
                 grad_weight = _fused.conv_grad_weight(input, weight.shape, grad_output, stride, padding, dilation, groups,
                                                       ctx.x_is_pm1)

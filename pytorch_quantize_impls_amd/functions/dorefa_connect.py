@@ -174,15 +174,13 @@ def QuantConv2d(stride=1, padding=1, dilation=1, groups=1, bit_width=3):
             if ctx.needs_input_grad[0]:
                 if 1 < bit_width <= _fused.LEVEL_MAX_BITS:      # odd integer levels / (2^k - 1): the levels are the exact operand, 1 / n after
                     n_w = float((1 << bit_width) - 1)
-                    grad_input = _fused.conv_grad_input(input.size(), torch.round(weight_q.detach() * n_w), grad_output, stride,
-                                                        padding, dilation, groups, kind="raw",
-                                                        out_scale=_fused._inv_levels(bit_width))
+                    grad_input = _fused.conv_grad_input(input, torch.round(weight_q.detach() * n_w), grad_output, stride, padding,
+                                                        dilation, groups, _fused.W_LEVELS, out_scale=_fused._inv_levels(bit_width))
                 elif bit_width == 1:        # sign(W) * E
-                    grad_input = _fused.conv_grad_input(input.size(), weight, grad_output, stride, padding, dilation, groups,
-                                                        kind="binary", out_scale_dev=ops.abs_mean(weight))
+                    grad_input = _fused.conv_grad_input(input, weight, grad_output, stride, padding, dilation, groups, _fused.W_PM1,
+                                                        quantiser="binary", out_scale_dev=ops.abs_mean(weight))
                 else:
-                    grad_input = _fused.conv_grad_input(input.size(), weight_q, grad_output, stride, padding, dilation, groups,
-                                                        kind=None)
+                    grad_input = _fused.conv_grad_input(input, weight_q, grad_output, stride, padding, dilation, groups, None)
             if ctx.needs_input_grad[1]:
                 x_pm1 = input.dim() == 4 and _fused.packed.lookup(input, _fused.packed.NHWC) is not None
                 grad_weight = _fused.conv_grad_weight(input, weight.shape, grad_output, stride, padding, dilation, groups, x_pm1)

@@ -95,7 +95,7 @@ def TernaryDense(stochastic=False):
 
 def TernaryConv2d(stochastic=True, stride=1, padding=1, dilation=1, groups=1):
     """DEPRECATED functional ternary conv (terner_connect.py:113-153).  Backward: the image's entries are multiples of 1/2 (exact
-    in fp16), so grad_input is the split gradient against the flipped image (kind "raw"); grad_weight on the +-1 routes when the
+    in fp16), so grad_input is the split gradient against the flipped image (W_LEVELS); grad_weight on the +-1 routes when the
     activation is +-1."""
     warnings.warn("Deprecated conv op ! Use layers.TerConv2d.", DeprecationWarning, stacklevel=2)
 
@@ -112,8 +112,8 @@ def TernaryConv2d(stochastic=True, stride=1, padding=1, dilation=1, groups=1):
             input, weight, weight_t, bias = ctx.saved_tensors
             grad_input = grad_weight = grad_bias = None
             if ctx.needs_input_grad[0]:
-                grad_input = _fused.conv_grad_input(input.size(), weight_t, grad_output, stride, padding, dilation, groups,
-                                                    kind="raw")
+                grad_input = _fused.conv_grad_input(input, weight_t, grad_output, stride, padding, dilation, groups,
+                                                    _fused.W_LEVELS)
             if ctx.needs_input_grad[1]:
                 grad_weight = _fused.conv_grad_weight(input, weight.shape, grad_output, stride, padding, dilation, groups,
                                                       ctx.x_is_pm1)

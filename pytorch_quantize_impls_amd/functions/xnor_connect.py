@@ -209,14 +209,10 @@ def XNORConv2d(dim=[0, 1], quant_input=False, stride=1, padding=1, dilation=1, g
         def backward(ctx, grad_output):
             input, weight, mean, bias = ctx.saved_tensors
             grad_input = grad_weight = grad_bias = None
-            go = _fused._dense(grad_output)
-            mfma = ctx.taps is not None and _fused.own_conv_backward(go, groups, padding)
             if ctx.needs_input_grad[0]:
-                if mfma:
-                    grad_input = ops.conv2d_grad_input_taps(input.shape, weight, go, ctx.taps.bwd, stride, padding, dilation)
-                if grad_input is None:
-                    grad_input = _fused.lib_conv2d_input(input.size(), torch.sign(weight) * mean, grad_output, stride, padding,
-                                                         dilation, groups)
+                grad_input = _fused.conv_grad_input(input, weight, grad_output, stride, padding, dilation, groups, _fused.W_TAPS,
+                                                    operand=getattr(ctx.taps, "bwd", None), lib_weight=lambda: torch.sign(weight) * mean,
+                                                    gate=ctx.taps is not None and _fused.own_conv_backward(grad_output, groups, padding))
             want_bias = bias is not None and ctx.needs_input_grad[2]
             by_product = []
             if ctx.needs_input_grad[1]:

@@ -2770,13 +2770,31 @@ def bn_act_train_backward(grad_out: torch.Tensor, xs: torch.Tensor, res, gamma, 
 
 # ---- backward of a quantised conv on the bf16 matrix cores ----------------------------------------------
 # Both gradients of conv2d(x, Q(W)) have one +-1 / 0 operand, so the exact-split route of the forward applies:
-#   grad_x = conv2d(g, flip(Q(W))^T, padding k-1-p)                 (stride 1): real g x quantised weight, the forward kernel
+#   grad_x = conv2d(g, flip(Q(W))^T, padding k-1-p): real g x quantised weight, the forward kernel; a square stride s > 1 on the
+#          zero-dilated g.  ONE geometry test and ONE set-up (grad_input_route_applicable, grad_input_operand) for every rung: the
+#          two below and the real-valued one of functions/_fused.conv_grad_input_routes, the ladder that walks them
 #   grad_W[co, ci, i, j] = sum_{n, ho, wo} g[n, co, ho, wo] x[n, ci, ho s - p + i d, wo s - p + j d]
 #          = conv2d(x^T, g^T) with batch <-> channel swapped (x^T: [Cin, N, H, W], "weight" g^T: [Cout, N, Ho, Wo], stride and
 #            dilation exchanged): +-1 x as the replicated bf16 operand, g as the exact hi/mid/lo triple operand, the
 #            contraction over (n, ho, wo) on the matrix cores; the batch is cut into chunks that keep a row of the
 #            "weight" under the kernel's 1 MiB K limit and give the launch enough tiles, partial results added in fp32.
 # Reference expressions: functions/binary_connect.py:141-143 (torch.nn.grad.conv2d_input / conv2d_weight).
+
+def grad_input_route_applicable(weight_shape, stride, padding, dilation) -> bool:
+    """Is grad_x of this conv a stride-1 transposed conv here?  Square stride, un-dilated, padding <= k - 1."""
+    (sh, sw), (ph, pw), (kh, kw) = _pairs(stride), _pairs(padding), _pairs(weight_shape[2:])
+    return _pairs(dilation) == (1, 1) and sh == sw and sh >= 1 and ph <= kh - 1 and pw <= kw - 1
+
+
+def grad_input_operand(grad_output: torch.Tensor, input_shape, weight_shape, stride, padding, dilation):
+    """(operand, padding) of that stride-1 conv: the gradient itself or, for s > 1, ``zero_dilated_gradient``, and
+    (kh-1-ph, kw-1-pw).  None outside ``grad_input_route_applicable`` and when ``zero_dilated_gradient`` gives None."""
+    if not grad_input_route_applicable(weight_shape, stride, padding, dilation):
+        return None
+    (kh, kw), s, (ph, pw) = _pairs(weight_shape[2:]), _pairs(stride)[0], _pairs(padding)
+    g = grad_output if s == 1 else zero_dilated_gradient(grad_output, input_shape, (kh, kw), s, (ph, pw))
+    return None if g is None else (g, (kh - 1 - ph, kw - 1 - pw))
+
 
 def zero_dilated_gradient(grad_output: torch.Tensor, input_shape, kernel_hw, stride: int, padding):
     """The gradient of a stride-s conv (square stride, un-dilated) as the operand of the equivalent STRIDE-1 transposed conv:
@@ -2800,31 +2818,24 @@ def conv2d_grad_input_q(input_shape, weight_q: torch.Tensor, grad_output: torch.
                         terms: Optional[int] = None, weight_triples: Optional[TriplePlanes] = None):
     """grad wrt the input of conv2d(x, Q(weight_q)): ``weight_q`` already quantised — +-1 / 0 (``kind`` "sign") or integer
     levels (``kind`` "raw": the k-bit DoReFa levels c = n * w_q, the caller scales by 1 / n) — or the latent weight with its
-    quantiser (``kind`` "binary" / "ternary": applied inside the operand pack): the forward's exact-split conv
-    of the gradient with the flipped, transposed weight.  Stride 1 directly; stride s > 1 (square, un-dilated — the
-    3x3 / stride-2 and 1x1 / stride-2 convs of the reference's ResNets, models/Resnet/Resnet_bin.py:20-33) through the
-    zero-dilated gradient: g_d[.., s y, s x] = g[.., y, x], zeros elsewhere and ``H + 2p - k - (Ho - 1) s`` rows / columns of
-    zeros appended, which turns conv_transpose(g, W, stride s) into the stride-1 conv above (3/4 of its products are with the
-    inserted zeros; these layers are the small ones).  ``out_scale`` / ``out_scale_dev``: see ``float_conv2d`` (1 / n of the
-    levels, DoReFa's E).  None when the shape is outside the route (dilation != 1, padding > k - 1, non-square stride): the
-    caller uses torch.nn.grad.conv2d_input.  ``terms``: the split of the gradient (default FLOAT_SPLIT; 3 = exact, for weight levels
-    that are exact in bf16 but not in fp16); ``weight_triples``: the grad_x operand already packed (pack_levels_bf16x3's gx plane,
-    ``weight_q`` then only gives the shape)."""
-    (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
-    Cout, Cin, kh, kw = (int(v) for v in weight_q.shape)
-    if (dh, dw) != (1, 1) or sh != sw or sh < 1 or ph > kh - 1 or pw > kw - 1:
+    quantiser (``kind`` "binary" / "ternary": applied inside the operand pack): the forward's exact-split conv of
+    ``grad_input_operand`` with the flipped, transposed weight (for the stride-2 convs of the reference's ResNets,
+    models/Resnet/Resnet_bin.py:20-33, 3/4 of the products are with inserted zeros; these layers are the small ones); None outside
+    its geometry: the caller uses torch.nn.grad.conv2d_input.  ``out_scale`` / ``out_scale_dev``: see ``float_conv2d`` (1 / n of
+    the levels, DoReFa's E).  ``terms``: the split of the gradient (default FLOAT_SPLIT; 3 = exact, for weight levels that are exact
+    in bf16 but not in fp16); ``weight_triples``: the grad_x operand already packed (pack_levels_bf16x3's gx plane, ``weight_q``
+    then only gives the shape)."""
+    op = grad_input_operand(grad_output, input_shape, weight_q.shape, stride, padding, dilation)
+    if op is None:
         return None
+    g, pad = op
+    Cout, Cin, kh, kw = (int(v) for v in weight_q.shape)
     N, C, H, W = (int(v) for v in input_shape)
-    g = grad_output
-    if sh > 1:
-        g = zero_dilated_gradient(g, input_shape, (kh, kw), sh, (ph, pw))
-        if g is None:
-            return None
     # the flipped, transposed weight [Cin, Cout, kh, kw] only ever exists as the conv's packed operand
     wt = weight_triples if weight_triples is not None else \
         pack_conv_weight_bf16x3(weight_q.detach(), kind, terms=terms, transpose_flip=True)
     shape_t = torch.empty((Cin, Cout, kh, kw), dtype=torch.float32, device="meta")
-    y2 = float_conv2d(g, shape_t, kind, None, 1, (kh - 1 - ph, kw - 1 - pw), 1, weight_triples=wt, out_scale=out_scale,
+    y2 = float_conv2d(g, shape_t, kind, None, 1, pad, 1, weight_triples=wt, out_scale=out_scale,
                       out_scale_dev=out_scale_dev, terms=terms if terms is not None else wt.terms)
     return y2.view(N, H, W, C).permute(0, 3, 1, 2)
 
@@ -2833,19 +2844,16 @@ def conv2d_grad_input_taps(input_shape, weight: torch.Tensor, grad_output: torch
                            padding, dilation):
     """grad wrt the input of an XNOR-Net conv, conv2d(x, sign(W) * alpha[1, 1, kh, kw]) (functions/xnor_connect.py:154-155):
     the two-term fp16 split of the gradient against the flipped, transposed sign(W) on the fp16 matrix cores, alpha applied per
-    (flipped) tap on the accumulators (qt_conv2d_implicit_taps, elem 3; ``tap_rho_flipped`` = TapScales.bwd).  Square stride
-    (s > 1 through the zero-dilated gradient), un-dilated, padding <= k - 1, Cout % 8 == 0 (a tap of the pair plane = whole 32-byte
-    k-steps); None otherwise."""
-    (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
+    (flipped) tap on the accumulators (qt_conv2d_implicit_taps, elem 3; ``tap_rho_flipped`` = TapScales.bwd).  The geometry of
+    ``grad_input_operand`` with Cout % 8 == 0 (a tap of the pair plane = whole 32-byte k-steps); None otherwise."""
     Cout, Cin, kh, kw = (int(v) for v in weight.shape)
-    if sh != sw or sh < 1 or (dh, dw) != (1, 1) or ph > kh - 1 or pw > kw - 1 or Cout % 8:
+    if Cout % 8 or not grad_input_route_applicable(weight.shape, stride, padding, dilation):
         return None
     N, C, H, W = (int(v) for v in input_shape)
-    g = _require(grad_output, "grad_output")
-    if sh > 1:                                     # square stride: the zero-dilated gradient (see conv2d_grad_input_q)
-        g = zero_dilated_gradient(g, input_shape, (kh, kw), sh, (ph, pw))
-        if g is None:
-            return None
+    op = grad_input_operand(_require(grad_output, "grad_output"), input_shape, weight.shape, stride, padding, dilation)
+    if op is None:
+        return None
+    g, pad = op
     _, _, Ho, Wo = (int(v) for v in g.shape)
     wt = pack_conv_weight_bf16x3(weight.detach(), "sign", terms=2, transpose_flip=True)        # [Cin, kh*kw*Cb/2] fp16 pairs
     Cb = triple_ld_bytes(Cout, 16, 2)
@@ -2853,7 +2861,7 @@ def conv2d_grad_input_taps(input_shape, weight: torch.Tensor, grad_output: torch
     if not nhwc.is_contiguous():
         nhwc = nhwc.contiguous()
     px = split_bf16x3(nhwc.view(N * Ho * Wo, Cout), ld_bytes=Cb, terms=2)
-    y2 = _conv_taps(3, px.data, N, Ho, Wo, Cb // 4, kh, kw, ((1, 1), (kh - 1 - ph, kw - 1 - pw), (1, 1)), wt.data, wt.ld_words,
+    y2 = _conv_taps(3, px.data, N, Ho, Wo, Cb // 4, kh, kw, ((1, 1), pad, (1, 1)), wt.data, wt.ld_words,
                     None, 1.0, px.scale[0:1], tap_rho_flipped, Cin)
     if y2 is None:
         return None
