@@ -1119,7 +1119,8 @@ int qt_pool_bits(const uint32_t* in_plane, int64_t N, int64_t H, int64_t W, int6
  * 20/21/22/23 = ping-pong kernel (64-byte stages, ring of 4, SIMD partners alternate load / compute
  * segments), tile 256x256 / 256x128 / 256x192 / 256x64, 24 = ping-pong 384x192; 6/7/8/15 = double-buffered pipelined kernel, tile 256x256 /
  * 256x128 / 256x64 / 256x192 (QT_ERR_ALIGNMENT if the contract does not hold); 5/9/10/16 = generic
- * kernel with the same tiles.  (161..166, stamped / ablated profiling kernels whose Y is not valid, exist only in
+ * kernel with the same tiles; 30 = skinny 128x64 tile with 256-byte stages (row strides % 64 words, else
+ * QT_ERR_ALIGNMENT), 31 = skinny 64x64 tile with 512-byte stages (row strides % 128 words), at any M.  (161..166, stamped / ablated profiling kernels whose Y is not valid, exist only in
  * -DQT_PROFILING_VARIANTS builds of the library; the product build answers QT_ERR_UNSUPPORTED.) */
 int qt_nib_gemm_variant(int variant, const uint32_t* Xn, int64_t ldxp, const uint32_t* Wn,
                         int64_t ldwp, const float* bias, float* Y, int64_t ldy, int64_t M,

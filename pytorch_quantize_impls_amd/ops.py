@@ -995,7 +995,21 @@ def bits_to_nib_pad(planes: BitPlanes, N: int, H: int, W: int, padding, ld: Opti
 def nib_gemm(x: NibPlanes, w: NibPlanes, bias: Optional[torch.Tensor] = None,
              out: Optional[torch.Tensor] = None, variant: Optional[int] = None, out_dtype=None) -> torch.Tensor:
     """Y[M,N] = sum_k x[m,k]*w[n,k] (+ bias) on the matrix cores; bit-identical to the popcount
-    GEMMs.  ``variant`` selects an explicit kernel configuration (tuning only).  ``out_dtype`` = torch.bfloat16 / float16:
+    GEMMs.  ``variant`` selects an explicit kernel configuration (tuning only; csrc/tile_select.h gemm_variant_cfg):
+
+        variant  tile      kernel
+        20       256x256   ping-pong (64-byte stages, ring of 4)
+        21       256x128   ping-pong
+        22       256x192   ping-pong
+        23       256x64    ping-pong
+        24       384x192   ping-pong
+        6 / 7 / 8 / 15     256x256 / 256x128 / 256x64 / 256x192, double-buffered
+        5 / 9 / 10 / 16    the same tiles, generic kernel (any row stride % 4 words)
+        30       128x64    skinny, 256-byte stages (row strides % 64 words)
+        31       64x64     skinny, 512-byte stages (row strides % 128 words)
+
+    Every variant but 5 / 9 / 10 / 16 needs row strides of whole 128-byte stages; a stride a variant cannot take is an
+    alignment error, never another kernel.  ``out_dtype`` = torch.bfloat16 / float16:
     the kernel's epilogue rounds the fp32 sum + bias once, to nearest even, and stores the half result itself (qt_nib_gemm_h)."""
     if x.K != w.K:
         raise ValueError(f"K mismatch: activations {x.K} vs weights {w.K}")

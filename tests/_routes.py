@@ -46,6 +46,10 @@ GEMM_CFG = {
     (2, 4, 4, 1, 0, 0, 128, 0, 1): "Cfg128_0",
     (4, 2, 2, 1, 0, 0, 128, 0, 1): "Cfg64_0",
     (4, 2, 2, 1, 1, 0, 128, 0, 1): "Cfg64_1",
+    # ... and the double-buffered tiles only qt_nib_gemm_variant launches (tests/test_gpu_gemm_routes.py)
+    (2, 4, 4, 2, 1, 0, 128, 0, 1): "Cfg256_1",
+    (4, 2, 2, 3, 1, 0, 128, 0, 1): "Cfg192_1",
+    (2, 4, 4, 1, 1, 0, 128, 0, 1): "Cfg128_1",
 }
 CFG_ARGS = {name: ", ".join(map(str, t)) for t, name in GEMM_CFG.items()}      # alias -> "WM, WN, ..., OCC" as the profiler prints it
 assert len(CFG_ARGS) == len(GEMM_CFG)
