@@ -216,6 +216,22 @@ def _code_fold_for(owner, attr, bn, fold, like):
     return cur[1]
 
 
+def _square_pool(pool, what="can be fused", training=False):
+    """(k, s) of a MaxPool2d the pooling kernels can take: square window and stride, no padding, no dilation, floor mode (and,
+    for the training chain, no ``return_indices``: the fused node returns one tensor).  ValueError otherwise — a pair such as
+    kernel_size=(3, 2) is never read as its first entry."""
+    def pair(v):
+        return (int(v),) * 2 if isinstance(v, int) else tuple(int(t) for t in v)
+    k = pair(pool.kernel_size)
+    st = pair(pool.stride if pool.stride is not None else pool.kernel_size)
+    pad, dil = pair(pool.padding), pair(pool.dilation)
+    if len(k) != 2 or len(st) != 2 or k[0] != k[1] or st[0] != st[1]:
+        raise ValueError(f"only a square MaxPool2d window and stride {what}")
+    if pad != (0, 0) or dil != (1, 1) or pool.ceil_mode or (training and pool.return_indices):
+        raise ValueError(f"only un-padded, un-dilated, floor-mode MaxPool2d {what}")
+    return k[0], st[0]
+
+
 class FusedPoolBnSign(torch.nn.Module):
     """[MaxPool2d(k, s)] + eval BatchNorm + [Hardtanh] + BinaryConnect(deterministic) -> PackedActivation."""
 
@@ -224,13 +240,7 @@ class FusedPoolBnSign(torch.nn.Module):
         self.fold = fold or DEFAULT_FOLD
         self.pre_relu = bool(pre_relu)     # ReLU between the pooling and the BatchNorm (MLPBin.py:42-44 pattern)
         if pool is not None:
-            k = pool.kernel_size if isinstance(pool.kernel_size, int) else pool.kernel_size[0]
-            st = pool.stride if isinstance(pool.stride, int) else pool.stride[0]
-            pad = pool.padding if isinstance(pool.padding, int) else pool.padding[0]
-            dil = pool.dilation if isinstance(pool.dilation, int) else pool.dilation[0]
-            if pad != 0 or dil != 1 or pool.ceil_mode:
-                raise ValueError("only un-padded, un-dilated, floor-mode MaxPool2d can be fused")
-            self.pool_k, self.pool_s = int(k), int(st)
+            self.pool_k, self.pool_s = _square_pool(pool, "can be fused")
         else:
             self.pool_k = self.pool_s = 1
         self.bn = bn
@@ -449,13 +459,7 @@ class CodeMaxPool(torch.nn.Module):
 
     def __init__(self, pool, out_halo=0):
         super().__init__()
-        k = pool.kernel_size if isinstance(pool.kernel_size, int) else pool.kernel_size[0]
-        st = pool.stride if isinstance(pool.stride, int) else pool.stride[0]
-        pad = pool.padding if isinstance(pool.padding, int) else pool.padding[0]
-        dil = pool.dilation if isinstance(pool.dilation, int) else pool.dilation[0]
-        if pad != 0 or dil != 1 or pool.ceil_mode:
-            raise ValueError("only un-padded, un-dilated, floor-mode MaxPool2d runs on code planes")
-        self.pool_k, self.pool_s = int(k), int(st)
+        self.pool_k, self.pool_s = _square_pool(pool, "runs on code planes")
         self.out_halo = (int(out_halo),) * 2 if isinstance(out_halo, int) else tuple(int(v) for v in out_halo)
 
     def forward(self, act):
@@ -545,13 +549,7 @@ class LevelMaxPool(torch.nn.Module):
 
     def __init__(self, pool, out_halo=0):
         super().__init__()
-        k = pool.kernel_size if isinstance(pool.kernel_size, int) else pool.kernel_size[0]
-        st = pool.stride if isinstance(pool.stride, int) else pool.stride[0]
-        pad = pool.padding if isinstance(pool.padding, int) else pool.padding[0]
-        dil = pool.dilation if isinstance(pool.dilation, int) else pool.dilation[0]
-        if pad != 0 or dil != 1 or pool.ceil_mode:
-            raise ValueError("only un-padded, un-dilated, floor-mode MaxPool2d runs on level planes")
-        self.pool_k, self.pool_s = int(k), int(st if st is not None else k)
+        self.pool_k, self.pool_s = _square_pool(pool, "runs on level planes")
         self.out_halo = _halo_pair(out_halo)
 
     def forward(self, act):
@@ -751,13 +749,7 @@ class PackedMaxPool(torch.nn.Module):
 
     def __init__(self, pool):
         super().__init__()
-        k = pool.kernel_size if isinstance(pool.kernel_size, int) else pool.kernel_size[0]
-        st = pool.stride if isinstance(pool.stride, int) else pool.stride[0]
-        pad = pool.padding if isinstance(pool.padding, int) else pool.padding[0]
-        dil = pool.dilation if isinstance(pool.dilation, int) else pool.dilation[0]
-        if pad != 0 or dil != 1 or pool.ceil_mode:
-            raise ValueError("only un-padded, un-dilated, floor-mode MaxPool2d can be fused")
-        self.pool_k, self.pool_s = int(k), int(st)
+        self.pool_k, self.pool_s = _square_pool(pool, "can be fused")
         self._zero_mask = None
         self.out_nib_halo = None        # see FusedConvPoolBnSign.out_nib_halo
 
@@ -820,19 +812,22 @@ class FusedTrainPoolBnSign(torch.nn.Module):
         self.sign = _FunctionModule(BinaryConnectDeterministic)
         self.pool_k = self.pool_s = 1
         if pool is not None:
-            k = pool.kernel_size if isinstance(pool.kernel_size, int) else pool.kernel_size[0]
-            st = pool.stride if isinstance(pool.stride, int) else pool.stride[0]
-            pad = pool.padding if isinstance(pool.padding, int) else pool.padding[0]
-            dil = pool.dilation if isinstance(pool.dilation, int) else pool.dilation[0]
-            if pad != 0 or dil != 1 or pool.ceil_mode or pool.return_indices:
-                raise ValueError("only un-padded, un-dilated, floor-mode MaxPool2d can be fused")
-            self.pool_k, self.pool_s = int(k), int(st)
+            self.pool_k, self.pool_s = _square_pool(pool, "can be fused", training=True)
+
+    def _values_per_channel(self, x) -> int:
+        """What BatchNorm's batch statistics see: the POOLED pixels (one value per channel raises in torch.nn.BatchNorm; so
+        does the module chain this module then takes).  0 when the window does not fit the map."""
+        if x.dim() != 4:
+            return int(x.shape[0])
+        k, s = self.pool_k, self.pool_s
+        Ho, Wo = (int(x.shape[2]) - k) // s + 1, (int(x.shape[3]) - k) // s + 1
+        return int(x.shape[0]) * max(Ho, 0) * max(Wo, 0)
 
     def forward(self, x):
         x = lazy.resolve(x)
         bn = self.bn
         fast = (self.training and bn.training and x.is_cuda and x.dtype == torch.float32 and x.dim() in (2, 4)
-                and bn.momentum is not None and bn.track_running_stats and x.shape[0] * (x[0, 0].numel()) > 1
+                and bn.momentum is not None and bn.track_running_stats and self._values_per_channel(x) > 1
                 and x.shape[1] % 4 == 0
                 and (self.pool is None or x.dim() == 4))
         if not fast:

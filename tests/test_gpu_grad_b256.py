@@ -18,8 +18,8 @@ taken (_fused.LIBRARY_PATHS), and records the kernel instances it compared.
   (e) one batch-256 training step of each benchmark model: every backward kernel instance it launches was compared here, is
       torch's own (allow-list with reasons) or is named in KNOWN_UNCOVERED with where it is checked instead.
 
-Not here: the training chains at batch 256 (d), the plane past 2^31 bytes, the DoReFa digit route, the
-channels-last parameter (layout_like) and AlexNet conv4 (conv3 and conv5 share its kernels).  The Lin / Log layers at batch 256
+Not here: the training chains at batch 256 (d: tests/test_gpu_train_chain_b256.py), the plane past 2^31 bytes, the DoReFa
+digit route, the channels-last parameter (layout_like) and AlexNet conv4 (conv3 and conv5 share its kernels).  The Lin / Log layers at batch 256
 (level chain and gradients) are in tests/test_gpu_loglin_b256.py, XNOR-Net at batch 256 (tap convs, grad_x) in
 tests/test_gpu_xnor_b256.py.
 Run the whole module: the coverage test reads what the cases before it recorded; it prints the module's peak device memory
@@ -534,11 +534,11 @@ ALLOW = [
 # backward kernels of the steps that this module does not compare, each with where it is checked instead
 KNOWN_UNCOVERED = [
     (r"^(bwd_dx_kernel|bwd_sum_kernel|fold2_kernel|pool_bwd_kernel)$",
-     "training chains of train_chain.hip ([MaxPool,] BatchNorm, Hardtanh, sign / the DoReFa form): vs fp64 at batch 8, "
-     "tests/test_gpu_r3.py::test_training_chain_vs_fp64_of_the_module_chain and ::test_dorefa_training_chain_vs_fp64_of_the_module_chain"),
+     "training chains of train_chain.hip ([MaxPool,] BatchNorm, Hardtanh, sign / the DoReFa form): exact on designed operands "
+     "and vs fp64 at the batch-256 row counts, tests/test_gpu_train_chain_b256.py"),
     (r"^(act_bwd_dx_kernel|act_bwd_sum_kernel)$",
-     "DoReFa chain BatchNorm [+ residual] -> ReLU -> quantiser: vs fp64 at small batch, "
-     "tests/test_gpu_r3.py::test_dorefa_training_chain_vs_fp64_of_the_module_chain"),
+     "DoReFa chain BatchNorm [+ residual] -> ReLU -> quantiser: exact on designed operands and vs fp64 at the batch-256 row "
+     "counts, tests/test_gpu_train_chain_b256.py"),
     (r"ElemF16Taps",
      "XNOR-Net per-tap grad_x: bit-exact vs float64 on every configuration and at batch 256, "
      "tests/test_gpu_xnor_b256.py::test_grad_input_is_bit_exact_on_designed_operands"),

@@ -332,6 +332,77 @@ def test_fused_module_host_logic():
         q(torch.zeros(1, 12, 3, 3))
 
 
+NON_SQUARE_POOLS = [dict(kernel_size=(3, 2)), dict(kernel_size=3, stride=(2, 1)), dict(kernel_size=3, stride=2, padding=(0, 1))]
+
+
+@pytest.mark.parametrize("kw", NON_SQUARE_POOLS, ids=["kernel(3,2)", "stride(2,1)", "padding(0,1)"])
+def test_non_square_pool_is_never_fused_as_its_first_entry(kw):
+    """The pooling kernels take one k and one s.  MaxPool2d((3, 2)), stride=(2, 1) and padding=(0, 1) were once read as their
+    first entries (3x3 / stride 2 / un-padded) and fused: a wrong result, nothing raised.  Every constructor refuses them,
+    the fusers keep the MaxPool2d where it is, and the training sequence still computes what the original does."""
+    import copy
+    from pytorch_quantize_impls_amd.functions import BinaryConnect
+    from pytorch_quantize_impls_amd.layers import (CodeMaxPool, FusedConvPoolBnSign, FusedPoolBnSign, FusedTrainPoolBnSign,
+                                                   LevelMaxPool, PackedMaxPool, fuse_sequential, fuse_sequential_training)
+    pool = torch.nn.MaxPool2d(**kw)
+    bn = torch.nn.BatchNorm2d(8)
+    for build in (lambda: FusedPoolBnSign(bn, pool), lambda: FusedConvPoolBnSign(BinConv2d(4, 8, 3), bn, pool),
+                  lambda: PackedMaxPool(pool), lambda: CodeMaxPool(pool), lambda: LevelMaxPool(pool),
+                  lambda: FusedTrainPoolBnSign(bn, pool, torch.nn.Hardtanh())):
+        with pytest.raises(ValueError, match="MaxPool2d"):
+            build()
+    torch.manual_seed(5)
+    seq = torch.nn.Sequential(BinConv2d(4, 8, 3, padding=1), pool, bn, torch.nn.Hardtanh(), BinaryConnect(stochastic=False))
+    with torch.no_grad():
+        bn.weight.uniform_(0.5, 1.5)
+        bn.bias.normal_(0, 0.3)
+    for fuse_conv in (False, True):
+        fused = list(fuse_sequential(copy.deepcopy(seq).eval(), fuse_conv=fuse_conv, packed_pool=True))
+        assert [type(m).__name__ for m in fused] == ["BinConv2d", "MaxPool2d", "FusedPoolBnSign"]
+        assert (fused[2].pool_k, fused[2].pool_s) == (1, 1)             # BatchNorm -> Hardtanh -> sign fused WITHOUT the pool
+    ref = copy.deepcopy(seq).train()
+    train = fuse_sequential_training(seq.train())
+    assert [type(m).__name__ for m in train] == ["BinConv2d", "MaxPool2d", "FusedTrainPoolBnSign"]
+    assert train[1] is pool and train[2].pool is None
+    x = torch.randn(3, 4, 9, 10)
+    xa, xb = x.clone().requires_grad_(True), x.clone().requires_grad_(True)
+    ya, yb = train(xa), ref(xb)
+    g = torch.randn(ya.shape)
+    ya.backward(g)
+    yb.backward(g)
+    assert ya.shape == yb.shape and torch.equal(ya, yb) and torch.equal(xa.grad, xb.grad)
+    assert torch.equal(bn.running_var, ref[2].running_var)
+
+
+def test_square_pool_spellings_are_still_fused():
+    from pytorch_quantize_impls_amd.layers import FusedPoolBnSign, FusedTrainPoolBnSign, LevelMaxPool, PackedMaxPool
+    bn = torch.nn.BatchNorm2d(8)
+    for pool, ks in ((torch.nn.MaxPool2d(3, 2), (3, 2)), (torch.nn.MaxPool2d((3, 3), (2, 2), padding=(0, 0)), (3, 2)),
+                     (torch.nn.MaxPool2d(2), (2, 2)), (torch.nn.MaxPool2d([2, 2], dilation=(1, 1)), (2, 2))):
+        for m in (FusedPoolBnSign(bn, pool), PackedMaxPool(pool), LevelMaxPool(pool), FusedTrainPoolBnSign(bn, pool)):
+            assert (m.pool_k, m.pool_s) == ks
+    with pytest.raises(ValueError, match="un-padded"):
+        FusedTrainPoolBnSign(bn, torch.nn.MaxPool2d(3, 2, return_indices=True))
+    FusedPoolBnSign(bn, torch.nn.MaxPool2d(3, 2, return_indices=True))      # the inference block reads values only
+
+
+def test_training_chain_counts_values_per_channel_after_pooling():
+    """N = 1, 3x3 map, 3x3 window: ONE pooled value per channel.  torch's BatchNorm raises; the fused module's shape test once
+    counted the un-pooled pixels (9) and went on to the kernels, which return sign(beta).  The count is of pooled pixels, and
+    a count of one takes the module chain — which raises the same error."""
+    from pytorch_quantize_impls_amd.layers import FusedTrainPoolBnSign
+    mod = FusedTrainPoolBnSign(torch.nn.BatchNorm2d(8), torch.nn.MaxPool2d(3, 3), torch.nn.Hardtanh()).train()
+    assert mod._values_per_channel(torch.zeros(1, 8, 3, 3)) == 1
+    assert mod._values_per_channel(torch.zeros(1, 8, 5, 3)) == 1
+    assert mod._values_per_channel(torch.zeros(2, 8, 3, 3)) == 2
+    assert mod._values_per_channel(torch.zeros(1, 8, 6, 3)) == 2
+    assert mod._values_per_channel(torch.zeros(1, 8, 2, 3)) == 0
+    assert FusedTrainPoolBnSign(torch.nn.BatchNorm1d(8))._values_per_channel(torch.zeros(5, 8)) == 5
+    with pytest.raises(ValueError, match="Expected more than 1 value per channel"):
+        mod(torch.randn(1, 8, 3, 3))
+    assert mod(torch.randn(2, 8, 3, 3)).shape == (2, 8, 1, 1)
+
+
 def test_integer_thresholds_reproduce_the_float_predicate_exactly():
     """ops.integer_thresholds: for every integer accumulator value the one-compare form (acc < T) xor (alpha < 0) equals
     the kernel's float predicate fl(fl(acc + bias) * alpha) < -beta, brute force over the whole accumulator range,
