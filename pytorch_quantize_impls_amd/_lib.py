@@ -3,6 +3,10 @@
 The shared library is built IN-TREE (pytorch_quantize_impls_amd/lib/libqt_hip.so) by
 ``__graft_entry__.build()`` / ``make -C pytorch_quantize_impls_amd/csrc``.  There is no fallback:
 if the library is missing or a symbol is absent, every GPU op raises ``QtLibraryError``.
+
+include/qt_hip.h is the only statement of the ABI: it is parsed once at import into ``SIGNATURES`` (the restype and
+argtypes every entry point gets in ``load()``), ``DEFINES`` (the QT_* integer constants) and ``STRUCTS`` (the ``_fields_`` of
+the structures passed by pointer).  A new entry point is declared in the header and defined under csrc/; nothing is added here.
 """
 from __future__ import annotations
 
@@ -11,6 +15,7 @@ import os
 import re
 import threading
 from collections import Counter
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # QT_HIP_LIB: A/B builds of the same ABI (tools/); the product path is the in-tree library
@@ -26,224 +31,114 @@ class QtStatusError(RuntimeError):
     """A C-ABI entry point returned a negative qt_status."""
 
 
-_c_i64 = ctypes.c_int64
-_c_p = ctypes.c_void_p
-_c_int = ctypes.c_int
-_c_f32 = ctypes.c_float
+class Header(NamedTuple):
+    """What parse_header() reads out of the text of include/qt_hip.h."""
+    functions: dict     # name -> (restype, [(parameter name, ctype), ...]), in declaration order
+    defines: dict       # "QT_<NAME>" -> int, every #define of an integer literal
+    structs: dict       # name -> [(field, ctype), ...]: a ctypes.Structure's _fields_
 
-# name -> (restype, argtypes).  Must list every function include/qt_hip.h declares
-# (tests/test_abi.py parses the header and compares).
-SIGNATURES = {
-    "qt_version": (_c_int, []),
-    "qt_strerror": (ctypes.c_char_p, [_c_int]),
-    "qt_target_arch": (ctypes.c_char_p, []),
-    "qt_device_info": (_c_int, [ctypes.c_char_p, _c_int]),
-    "qt_binarize_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_p]),
-    "qt_binarize_stochastic_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p]),
-    "qt_ternarize_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_p]),
-    "qt_ternarize_stochastic_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p]),
-    "qt_ste_mask_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_f32, _c_p]),
-    "qt_poison_f32": (_c_int, [_c_p, _c_p, _c_int, _c_p, _c_i64, _c_p]),
-    "qt_dorefa_quantize_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_p]),
-    "qt_xnor_weight_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_shift_batch_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_f32, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64,
-                                    _c_i64, _c_p]),
-    "qt_xnor_act_work_floats": (_c_i64, []),
-    "qt_xnor_act_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_int, _c_p]),
-    "qt_xnor_act_backward_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_int,
-                                          _c_p]),
-    "qt_code_conv3x3_launch_count": (_c_i64, []),
-    "qt_xnor_input_quant_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_conv2d_implicit_taps_rows": (_c_int, [_c_p] + [_c_i64] * 12 + [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p]),
-    "qt_sign_pack_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_ternary_pack_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_check_pm1_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p]),
-    "qt_sign_pack_h": (_c_int, [_c_p, _c_int, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_ternary_pack_h": (_c_int, [_c_p, _c_int, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_check_pm1_h": (_c_int, [_c_p, _c_int, _c_i64, _c_p, _c_p]),
-    "qt_sign_pack_nib_h": (_c_int, [_c_p, _c_int, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_ternary_pack_nib_h": (_c_int, [_c_p, _c_int, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_pack_pair_nib_h": (_c_int, [_c_p, _c_int, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64,
-                                    _c_int, _c_p]),
-    "qt_nib_gemm_h": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_conv2d_implicit_h": (_c_int, [_c_p] + [_c_i64] * 12 + [_c_p, _c_i64, _c_p, _c_p, _c_int, _c_i64, _c_i64, _c_p]),
-    "qt_lin_quantize_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_int, _c_int, _c_p]),
-    "qt_log_quantize_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_int, _c_int, _c_int, _c_p]),
-    "qt_ap2_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_p]),
-    "qt_level_project_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_int, _c_p]),
-    "qt_weight_reg_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_p, _c_int, _c_int, _c_f32, _c_p, _c_f32, _c_p, _c_p]),
-    "qt_xnor_gemm_variant": (_c_int, [_c_int, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_tern_gemm_variant": (_c_int, [_c_int, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64,
-                                      _c_p]),
-    "qt_conv2d_implicit_variant": (_c_int, [_c_int, _c_int, _c_p] + [_c_i64] * 12 + [_c_p, _c_i64, _c_p, _c_f32, _c_p, _c_p,
-                                                                                     _c_i64, _c_i64, _c_p]),
-    "qt_xnor_gemm": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64,
-                              _c_i64, _c_p]),
-    "qt_tern_gemm": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64,
-                              _c_i64, _c_i64, _c_p]),
-    "qt_sign_pack_nib_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_ternary_pack_nib_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_sign0_pack_nib_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_pack_pair_nib_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64,
-                                      _c_int, _c_p]),
-    "qt_wgrad_pack_grad_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p,
-                                        _c_i64, _c_p]),
-    "qt_wgrad_pack_act_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
-                                       _c_i64, _c_i64, _c_f32, _c_p, _c_i64, _c_i64, _c_p]),
-    "qt_bf16_gemm_taps": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
-                                   _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_wgrad_reduce_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_f32, _c_f32, _c_int, _c_p,
-                                     _c_p]),
-    "qt_wgrad_pm_pack_grad_f32": (_c_int, [_c_p] + [_c_i64] * 11 + [_c_p, _c_p]),
-    "qt_wgrad_pm_pack_grad_bias_f32": (_c_int, [_c_p] + [_c_i64] * 10 + [_c_p, _c_p, _c_p]),
-    "qt_wgrad_pm_bias_reduce_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_int, _c_p, _c_p]),
-    "qt_wgrad_pm_pack_act_f32": (_c_int, [_c_p] + [_c_i64] * 13 + [_c_f32, _c_p, _c_p]),
-    "qt_wgrad_pm_pack_act_s2d_f32": (_c_int, [_c_p] + [_c_i64] * 17 + [_c_p, _c_p]),
-    "qt_wgrad_pm_pack_act_s2d_f16x2": (_c_int, [_c_p] + [_c_i64] * 17 + [_c_p, _c_p, _c_p]),
-    "qt_wgrad_pm_pack_grad_f16x2": (_c_int, [_c_p] + [_c_i64] * 11 + [_c_p, _c_p, _c_p, _c_p]),
-    "qt_wgrad_pm_pack_act_f16": (_c_int, [_c_p] + [_c_i64] * 13 + [_c_f32, _c_p, _c_p]),
-    "qt_wgrad_pm_f16": (_c_int, [_c_p, _c_p, _c_p] + [_c_i64] * 7 + [_c_p]),
-    "qt_wgrad_pm_f32": (_c_int, [_c_p, _c_p, _c_p] + [_c_i64] * 7 + [_c_p]),
-    "qt_wgrad_pm_reduce_f32": (_c_int, [_c_p] + [_c_i64] * 6 + [_c_p, _c_f32, _c_f32, _c_p, _c_int, _c_p] + [_c_i64] * 4 + [_c_p]),
-    "qt_nib_gemm_describe": (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.c_char_p, _c_int]),
-    "qt_gemm_tile_describe": (_c_int, [_c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.c_char_p, _c_int]),
-    "qt_conv2d_implicit_describe": (_c_int, [_c_int] + [_c_i64] * 16 + [_c_int, _c_int, _c_i64, _c_int, ctypes.c_char_p, _c_int]),
-    "qt_conv2d_implicit_taps_describe": (_c_int, [_c_int] + [_c_i64] * 16 + [_c_int, _c_int, _c_i64, _c_int, ctypes.c_char_p, _c_int]),
-    "qt_nib_gemm": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64,
-                             _c_i64, _c_p]),
-    "qt_bits_to_nib": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_pack_conv_weight_codes_i8": (_c_int, [_c_p] + [_c_i64] * 8 + [_c_int, _c_p, _c_i64, _c_p]),
-    "qt_dorefa_codes_i8": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_int, _c_p, _c_p]),
-    "qt_bn_eval_device_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_affine_dorefa_codes_i8": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_f32,
-                                           _c_int, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p, _c_p]),
-    "qt_affine_dorefa_codes_halo_i8": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_f32,
-                                                _c_int, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_p, _c_p, _c_p,
-                                                _c_i64, _c_i64, _c_p]),
-    "qt_codes_to_f32": (_c_int, [_c_p] + [_c_i64] * 7 + [_c_f32, _c_p, _c_i64, _c_p, _c_i64, _c_p]),
-    "qt_weight_codes_i8": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_int, _c_p]),
-    "qt_i8_gemm": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_f32, _c_p, _c_i64, _c_p, _c_i64, _c_i64,
-                            _c_i64, _c_i64, _c_p]),
-    "qt_pool_affine_sign_pack_nhwc": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p,
-                                               _c_p, _c_i64, _c_int, _c_p]),
-    "qt_pool_affine_sign_pack_nib_nhwc": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p,
-                                                   _c_p, _c_i64, _c_p, _c_i64, _c_int, _c_p]),
-    "qt_bf16x3_pack_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_int, _c_p]),
-    "qt_bf16x3_s2d_pack_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_i64] + [_c_i64] * 7 + [_c_p]),
-    "qt_bf16x6_pack_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_int, _c_p]),
-    "qt_f16x2_scale_f32": (_c_int, [_c_p, _c_p, _c_p, _c_p]),
-    "qt_f16x2_absmax_work_words": (_c_i64, []),
-    "qt_f16x2_absmax_scale_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p]),
-    "qt_conv3x3_first_pack_weight_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p]),
-    "qt_conv3x3_first_f32": (_c_int, [_c_p] + [_c_i64] * 8 + [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_int, _c_p]),
-    "qt_code_digits_f32": (_c_int, [_c_p, _c_i64, _c_f32, _c_p, _c_p, _c_p, _c_int, _c_p]),
-    "qt_digit_combine_f32": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_f32, _c_p, _c_i64, _c_p]),
-    "qt_abs_mean_work_words": (_c_i64, []),
-    "qt_abs_mean_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p]),
-    "qt_f16x2_absmax_pack_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_p]),
-    "qt_f16x2_absmax_ch_work_words": (_c_i64, [_c_i64]),
-    "qt_f16x2_absmax_scale_ch_f32": (_c_int, [_c_p] + [_c_i64] * 9 + [_c_p, _c_p, _c_p]),
-    "qt_f16x2_pack_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_int, _c_p]),
-    "qt_f16x2_pack_conv_weight_f32": (_c_int, [_c_p] + [_c_i64] * 8 + [_c_int, _c_int, _c_p, _c_i64, _c_p]),
-    "qt_bf16x3_pack_conv_levels_f32": (_c_int, [_c_p] + [_c_i64] * 8 + [_c_int] * 4 + [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
-    "qt_bf16x3_pack_levels_f32": (_c_int, [_c_p] + [_c_i64] * 4 + [_c_int] * 4 + [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
-    "qt_bf16x1_pack_conv_levels_f32": (_c_int, [_c_p] + [_c_i64] * 8 + [_c_int] * 4 + [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
-    "qt_bf16x1_pack_levels_f32": (_c_int, [_c_p] + [_c_i64] * 4 + [_c_int] * 4 + [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p]),
-    "qt_linlog_quantize_bf16_f32": (_c_int, [_c_p] + [_c_i64] * 8 + [_c_int] * 4 + [_c_p, _c_p, _c_i64, _c_p]),
-    "qt_bf16_pack_check_f32": (_c_int, [_c_p] + [_c_i64] * 8 + [_c_p, _c_i64, _c_p, _c_p]),
-    "qt_check_bf16_exact_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p]),
-    "qt_conv2d_implicit_levels": (_c_int, [_c_p] + [_c_i64] * 14 + [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p] + [_c_int] * 5
-                                  + [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_pool_levels_bf16": (_c_int, [_c_p] + [_c_i64] * 6 + [_c_p, _c_i64, _c_i64, _c_p]),
-    "qt_bn_relu_linlog_bf16_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p] + [_c_int] * 6 + [_c_p, _c_i64, _c_p, _c_i64, _c_i64,
-                                                                                             _c_i64, _c_p]),
-    "qt_f16x2_s2d_pack_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_i64] + [_c_i64] * 7 + [_c_p]),
-    "qt_f16x2_s2d_spec_work_words": (_c_i64, [_c_i64] * 4),
-    "qt_f16x2_s2d_pack_spec_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_f32, _c_p, _c_p, _c_p, _c_p, _c_i64] + [_c_i64] * 7
-                                   + [_c_p]),
-    "qt_f16_gemm": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_f32, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_train_chain_partial_floats": (_c_i64, [_c_i64, _c_i64]),
-    "qt_bn_train_stats_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_f32, _c_f32, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "qt_bn_act_train_backward_f32": (_c_int, [_c_p, _c_p, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_int] + [_c_p] * 6),
-    "qt_pool_bn_sign_train_f32": (_c_int, [_c_p] + [_c_i64] * 6 + [_c_p, _c_p, _c_f32, _c_f32, _c_f32, _c_f32] + [_c_p] * 9),
-    "qt_pool_bn_sign_train_backward_f32": (_c_int, [_c_p, _c_p, _c_p] + [_c_i64] * 6 + [_c_p] * 4 + [_c_f32] * 3 + [_c_p] * 6),
-    "qt_bf16_gemm": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_conv2d_implicit": (_c_int, [_c_int, _c_p] + [_c_i64] * 12 + [_c_p, _c_i64, _c_p, _c_f32, _c_p, _c_p, _c_i64,
-                                                                    _c_i64, _c_p]),
-    "qt_conv2d_implicit_bits": (_c_int, [_c_int, _c_p] + [_c_i64] * 12 + [_c_p, _c_i64, _c_p, _c_f32, _c_p, _c_p, _c_p,
-                                                                         _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p]),
-    "qt_conv2d_implicit_codes": (_c_int, [_c_int, _c_p] + [_c_i64] * 12 + [_c_p, _c_i64, _c_p, _c_f32, _c_p, _c_p, _c_p,
-                                                                          _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_f32,
-                                                                          _c_int, _c_int, _c_p, _c_i64, _c_i64, _c_p]
-                                 + [_c_i64] * 6 + [_c_p, _c_p, _c_int, _c_p]),
-    "qt_conv2d_implicit_halo": (_c_int, [_c_int, _c_p] + [_c_i64] * 14 + [_c_p, _c_i64, _c_p, _c_f32, _c_p, _c_p, _c_i64,
-                                                                          _c_i64, _c_p]),
-    "qt_conv2d_implicit_halo_bn": (_c_int, [_c_int, _c_p] + [_c_i64] * 14 + [_c_p, _c_i64, _c_p, _c_f32, _c_p, _c_p, _c_p, _c_p,
-                                                                             _c_p, _c_i64, _c_i64, _c_p]),
-    "qt_conv2d_implicit_nib": (_c_int, [_c_int, _c_p] + [_c_i64] * 12 + [_c_p, _c_i64, _c_p, _c_f32, _c_p, _c_p, _c_p,
-                                                                        _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int,
-                                                                        _c_p]),
-    "qt_conv3x3_direct_nib": (_c_int, [_c_int, _c_p] + [_c_i64] * 4 + [_c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64,
-                                        _c_int, _c_p]),
-    "qt_conv3x3_direct_codes": (_c_int, [_c_p] + [_c_i64] * 4 + [_c_p, _c_i64, _c_p, _c_f32, _c_p, _c_p, _c_p, _c_p, _c_i64,
-                                          _c_f32, _c_int, _c_int, _c_p, _c_i64, _c_i64, _c_p, _c_p]),
-    "qt_pool_bits_nib": (_c_int, [_c_p] + [_c_i64] * 6 + [_c_p, _c_p] + [_c_i64] * 4 + [_c_p]),
-    "qt_pool_bits": (_c_int, [_c_p] + [_c_i64] * 6 + [_c_p, _c_p, _c_p]),
-    "qt_pool_codes_i8": (_c_int, [_c_p] + [_c_i64] * 6 + [_c_p, _c_i64, _c_i64, _c_p]),
-    "qt_zero_halo": (_c_int, [_c_p] + [_c_i64] * 6 + [_c_p]),
-    "qt_pad_pixel_plane": (_c_int, [_c_p] + [_c_i64] * 6 + [_c_p, _c_p]),
-    "qt_bits_to_nib_pad": (_c_int, [_c_p, _c_p, _c_i64, _c_p, _c_i64] + [_c_i64] * 6 + [_c_p]),
-    "qt_im2col_words": (_c_int, [_c_p] + [_c_i64] * 12 + [_c_p, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_conv_first_direct_f32": (_c_int, [_c_p] + [_c_i64] * 14 + [_c_p, _c_p, _c_f32, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_i64, _c_p]),
-    "qt_conv_first_direct_bits_f32": (_c_int, [_c_p] + [_c_i64] * 14 + [_c_p, _c_p, _c_f32, _c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p,
-                                               _c_i64, _c_p]),
-    "qt_conv3x3_direct_pairs": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_int, _c_p]),
-    "qt_bits_alpha_pairs_f16x2": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_bits_alpha_digits_i8": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_xnor_head_i8": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_digit_reduce_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_i8_gemm_splitk": (_c_int, [_c_p, _c_i64, _c_p, _c_i64, _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_xnor_tap_prep_work_floats": (_c_i64, [_c_i64, _c_i64]),
-    "qt_xnor_tap_prep_f32": (_c_int, [_c_p, _c_i64, _c_i64, _c_p, _c_p, _c_p, _c_p, _c_p]),
-    "qt_conv2d_implicit_taps": (_c_int, [_c_int, _c_p] + [_c_i64] * 12 + [_c_p, _c_i64, _c_p, _c_f32, _c_p, _c_p, _c_p, _c_i64,
-                                                                         _c_i64, _c_p]),
-    "qt_conv2d_implicit_taps_bits": (_c_int, [_c_int, _c_p] + [_c_i64] * 12 + [_c_p, _c_i64, _c_p, _c_f32, _c_p, _c_p, _c_p, _c_p,
-                                                                              _c_p, _c_i64, _c_i64, _c_p]),
-    "qt_conv2d_implicit_taps_nib": (_c_int, [_c_int, _c_p] + [_c_i64] * 12 + [_c_p, _c_i64, _c_p, _c_f32, _c_p, _c_p, _c_p, _c_p,
-                                                                             _c_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_p]),
-    "qt_nib_gemm_variant": (_c_int, [_c_int, _c_p, _c_i64, _c_p, _c_i64, _c_p, _c_p, _c_i64, _c_i64,
-                                     _c_i64, _c_i64, _c_p]),
-    "qt_optim_chunk_capacity": (_c_int, []),
-    "qt_optim_sgd_f32": (_c_int, [_c_p, _c_i64, _c_f32, _c_f32, _c_f32, _c_int, _c_p]),
-    "qt_optim_adam_f32": (_c_int, [_c_p, _c_i64] + [_c_f32] * 6 + [_c_p]),
-    "qt_optim_scalars_f32": (_c_int, [_c_p, _c_p, _c_i64, _c_p]),
-    "qt_optim_sgd_dev_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_f32, _c_f32, _c_int, _c_p]),
-    "qt_optim_adam_dev_f32": (_c_int, [_c_p, _c_i64, _c_p] + [_c_f32] * 6 + [_c_p]),
-    "qt_optim_sgd_dev_guard_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_f32, _c_f32, _c_int, _c_p]),
-    "qt_optim_adam_dev_guard_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p] + [_c_f32] * 6 + [_c_p]),
-    "qt_optim_grad_norm_work_floats": (_c_i64, [_c_p, _c_i64]),
-    "qt_optim_grad_sumsq_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p]),
-    "qt_optim_grad_norm_finalize_f32": (_c_int, [_c_p, _c_i64, _c_f32, _c_p, _c_p, _c_p]),
-    "qt_optim_sgd_clip_f32": (_c_int, [_c_p, _c_i64, _c_f32, _c_p, _c_p, _c_p, _c_f32, _c_f32, _c_int, _c_p]),
-    "qt_optim_adam_clip_f32": (_c_int, [_c_p, _c_i64, _c_p, _c_p, _c_p] + [_c_f32] * 6 + [_c_p]),
-    "qt_flags_chunk_capacity": (_c_int, []),
-    "qt_flags_or_i32": (_c_int, [_c_p, _c_i64, _c_p, _c_p]),
-}
+
+# The whole type map of the C-ABI.  Any pointer but (const) char* is a c_void_p; every other spelling is an error.
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+            "qt_stream_t": ctypes.c_void_p}
+
+
+def _strip_comments(text: str) -> str:
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return re.sub(r"//[^\n]*", "", text)
+
+
+def _loose_function_names(stripped: str):
+    return sorted(set(re.findall(r"\b(qt_[a-z0-9_]+)\s*\(", stripped)))
+
+
+def _ctype(spelling: str, where: str):
+    words = [w for w in spelling.replace("*", " * ").split() if w != "const"]
+    if len(words) == 1 and words[0] in _SCALARS:
+        return _SCALARS[words[0]]
+    if len(words) >= 2 and re.fullmatch(r"\w+", words[0]) and set(words[1:]) == {"*"}:
+        return ctypes.c_char_p if words == ["char", "*"] else ctypes.c_void_p
+    raise QtLibraryError(f"{where}: the type '{spelling.strip()}' is not in the binding's type map")
+
+
+def _declarators(decl: str, where: str):
+    """'int64_t ld, rows, K' -> [("ld", c_int64), ("rows", c_int64), ("K", c_int64)]."""
+    m = re.fullmatch(r"(.*?[\s*])(\w+(?:\s*,\s*\w+)*)", decl.strip())
+    if not m:
+        raise QtLibraryError(f"{where}: cannot parse '{decl.strip()}'")
+    names = [n.strip() for n in m.group(2).split(",")]
+    if len(names) > 1 and "*" in m.group(1):      # in C the star of 'float* a, b' binds to a alone
+        raise QtLibraryError(f"{where}: several declarators of a pointer type in '{decl.strip()}'")
+    ctype = _ctype(m.group(1), where)
+    return [(n, ctype) for n in names]
+
+
+def parse_header(text: str, source: str = "header") -> Header:
+    """Functions, integer #defines and structs of a C header written like include/qt_hip.h.  Everything that is left after the
+    comments, preprocessor lines, enums, the qt_stream_t typedef and the extern "C" braces must be a struct typedef or a
+    prototype over the closed type map: anything else raises QtLibraryError, so no declaration is dropped quietly."""
+    text = _strip_comments(text)
+    loose = _loose_function_names(text)
+    defines = {name: int(value, 0) for name, value in
+               re.findall(r"^[ \t]*#[ \t]*define[ \t]+(QT_\w+)[ \t]+(-?(?:0[xX][0-9a-fA-F]+|\d+))[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#(?:.*\\\n)*.*$", "", text, flags=re.M)
+    structs = {}
+
+    def take_struct(m):
+        name, where = m.group(1), f"{source}: struct {m.group(1)}"
+        structs[name] = [f for decl in m.group(2).split(";") if decl.strip() for f in _declarators(decl, where)]
+        return ""
+
+    text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;", take_struct, text)
+    text = re.sub(r"(?:typedef\s+)?enum\b[^{};]*\{[^{}]*\}[^;]*;", "", text)
+    text = re.sub(r"typedef\s+void\s*\*\s*qt_stream_t\s*;", "", text)
+    text, n_extern = re.subn(r'extern\s+"C"\s*\{', "", text)
+    *statements, tail = text.split(";")
+    if "".join(tail.split()) != "}" * n_extern:
+        raise QtLibraryError(f"{source}: cannot parse the end of the header '{tail.strip()}'")
+    functions = {}
+    for stmt in statements:
+        stmt = " ".join(stmt.split())
+        if not stmt:
+            continue
+        m = re.fullmatch(r"(.*?[\s*])(qt_[a-z0-9_]+) ?\(([^()]*)\)", stmt)
+        if not m or m.group(2) in functions:
+            raise QtLibraryError(f"{source}: cannot parse the declaration '{stmt}'")
+        ret, name, params = m.groups()
+        where = f"{source}: {name}()"
+        params = [] if params.strip() == "void" else [d for p in params.split(",") for d in _declarators(p, where)]
+        functions[name] = (_ctype(ret, where), params)
+    if sorted(functions) != loose:
+        raise QtLibraryError(f"{source}: parsed functions differ from the names the header mentions: "
+                             f"{sorted(set(functions) ^ set(loose))}")
+    return Header(functions, defines, structs)
+
+
+def _read_header(header_path: str) -> str:
+    try:
+        with open(header_path, "r", encoding="utf-8") as fh:
+            return fh.read()
+    except OSError as e:
+        raise QtLibraryError(f"cannot read the C-ABI header {header_path}: {e}") from e
+
+
+def header_declared_functions(header_path: str = HEADER_PATH):
+    """Names of all functions declared in include/qt_hip.h (comments stripped): a loose scan that knows no types, which
+    parse_header() has to agree with."""
+    return _loose_function_names(_strip_comments(_read_header(header_path)))
+
+
+HEADER = parse_header(_read_header(HEADER_PATH), HEADER_PATH)
+DEFINES = HEADER.defines
+STRUCTS = HEADER.structs
+#: name -> (restype, argtypes) of every function include/qt_hip.h declares
+SIGNATURES = {name: (restype, [ctype for _, ctype in params]) for name, (restype, params) in HEADER.functions.items()}
 
 _lock = threading.Lock()
 _lib = None
 #: number of successful calls per entry point in this process — the GPU tests assert on it so a
 #: silent non-HIP path cannot pass them.
 call_counts: Counter = Counter()
-
-
-def header_declared_functions(header_path: str = HEADER_PATH):
-    """Names of all functions declared in include/qt_hip.h (comments stripped)."""
-    with open(header_path, "r", encoding="utf-8") as fh:
-        text = fh.read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return sorted(set(re.findall(r"\b(qt_[a-z0-9_]+)\s*\(", text)))
 
 
 def load():

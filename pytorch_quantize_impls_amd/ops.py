@@ -331,7 +331,7 @@ def _require(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
 
 #: half-precision element types of the "_h" entry points (include/qt_hip.h: QT_DTYPE_BF16 / QT_DTYPE_F16)
 HALF_DTYPES = (torch.bfloat16, torch.float16)
-_DTYPE_CODE = {torch.bfloat16: 1, torch.float16: 2}
+_DTYPE_CODE = {torch.bfloat16: _lib.DEFINES["QT_DTYPE_BF16"], torch.float16: _lib.DEFINES["QT_DTYPE_F16"]}
 PACK_DTYPES = (torch.float32,) + HALF_DTYPES
 
 
@@ -440,8 +440,8 @@ def ap2(x: torch.Tensor) -> torch.Tensor:
 
 
 #: capacities of the by-value tables of qt_level_project_f32 / qt_weight_reg_f32 (include/qt_hip.h)
-LEVELS_MAX = 64
-REG_TERMS_MAX = 128
+LEVELS_MAX = _lib.DEFINES["QT_LEVELS_MAX"]
+REG_TERMS_MAX = _lib.DEFINES["QT_REG_TERMS_MAX"]
 
 
 def level_project(x: torch.Tensor, levels) -> torch.Tensor:
@@ -799,10 +799,10 @@ POPC_VARIANT = 0
 CONV_VARIANT = 0
 #: A/B flags of the implicit-GEMM convs (the QT_CONV_* bits of include/qt_hip.h; every flag selects another kernel that computes
 #: the same bits): passed to the bits / nib / codes entries, or-ed into CONV_VARIANT for the plain fp32 conv
-CONV_NO_DEEP_RING = 0x10            # double-buffered ConvV128x128 / ConvV128x64 instead of the ring-of-stages forms
-CONV_COMPARE_THRESHOLDS = 0x20      # integer thresholds: compare-form epilogue instead of the sign-bit form
-CONV_NO_DIRECT_CODES = 0x40         # code epilogue: never the persistent direct 3 x 3 kernel
-CONV_FLAGS_MASK = CONV_NO_DEEP_RING | CONV_COMPARE_THRESHOLDS | CONV_NO_DIRECT_CODES
+CONV_NO_DEEP_RING = _lib.DEFINES["QT_CONV_NO_DEEP_RING"]                # double-buffered ConvV128x128 / ConvV128x64 instead of the ring-of-stages forms
+CONV_COMPARE_THRESHOLDS = _lib.DEFINES["QT_CONV_COMPARE_THRESHOLDS"]    # integer thresholds: compare-form epilogue instead of the sign-bit form
+CONV_NO_DIRECT_CODES = _lib.DEFINES["QT_CONV_NO_DIRECT_CODES"]          # code epilogue: never the persistent direct 3 x 3 kernel
+CONV_FLAGS_MASK = _lib.DEFINES["QT_CONV_FLAGS_MASK"]
 CONV_FLAGS = 0
 
 
@@ -2046,6 +2046,12 @@ def abs_mean(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+@functools.lru_cache(maxsize=None)
+def _absmax_work_words() -> int:
+    """int32 words of scratch the f16x2 absmax kernels take (qt_f16x2_absmax_work_words)."""
+    return int(_lib.load().qt_f16x2_absmax_work_words())
+
+
 def pow2_scale(x: torch.Tensor) -> torch.Tensor:
     """Device fp32 [s, 1 / s] with s = 2^k and max|x| / s in [2^14, 2^15) (qt_f16x2_scale_f32): one reduction pass over x
     (torch.aminmax), no host sync."""
@@ -2054,7 +2060,7 @@ def pow2_scale(x: torch.Tensor) -> torch.Tensor:
     if _storage_dense(x) and x.data_ptr() % 16 == 0:
         # dense storage in any dimension order: max|x| at the HBM rate and the scale in one launch (torch.aminmax runs at
         # ~1.2 TB/s: 128 us for AlexNet's 154 MB input batch against 26 us)
-        work = torch.empty((2048,), dtype=torch.int32, device=x.device)        # qt_f16x2_absmax_work_words()
+        work = torch.empty((_absmax_work_words(),), dtype=torch.int32, device=x.device)
         with _on(x.device):
             _lib.call("qt_f16x2_absmax_scale_f32", _p(x), int(x.numel()), _p(work), _p(out), _stream(x.device))
         return out
@@ -2078,8 +2084,9 @@ def _triple_pack(x: torch.Tensor, mode: int, alpha: Optional[torch.Tensor], ld_b
         if (mode == 0 and scale is None and rows > 0 and K > 0 and x2.is_contiguous() and x2.data_ptr() % 16 == 0
                 and (mul_dev is None or (mul_dev.is_cuda and mul_dev.dtype == torch.float32 and mul_dev.numel() == 1))):
             # max|x| partials + (fold, scale, split) in two launches; the consumer's other device scalar rides in scale3[2]
-            ws = torch.empty((2048 + 4,), dtype=torch.int32, device=x.device)      # qt_f16x2_absmax_work_words() + the three scales
-            scale3 = ws[2048:2051].view(torch.float32)
+            nw = _absmax_work_words()
+            ws = torch.empty((nw + 4,), dtype=torch.int32, device=x.device)      # the partial maxima + the three scales
+            scale3 = ws[nw:nw + 3].view(torch.float32)
             md = mul_dev.detach() if mul_dev is not None else None
             with _on(x.device):
                 _lib.call("qt_f16x2_absmax_pack_f32", _p(x2), int(rows), int(K), _p(ws), _p(md), _p(scale3), _p(out), int(ld),
@@ -3725,7 +3732,8 @@ def nib_gemm_kernel_name(M: int, N: int, K: int, ld: Optional[int] = None) -> st
 
 
 #: epilogue kinds of conv_kernel_name / conv_taps_kernel_name (include/qt_hip.h QT_EPI_*)
-EPI_PLAIN, EPI_BITS, EPI_NIB, EPI_CODES, EPI_HALO_BN, EPI_LEVELS, EPI_HALF_BF16, EPI_HALF_F16 = range(8)
+EPI_PLAIN, EPI_BITS, EPI_NIB, EPI_CODES, EPI_HALO_BN, EPI_LEVELS, EPI_HALF_BF16, EPI_HALF_F16 = (
+    _lib.DEFINES["QT_EPI_" + name] for name in ("PLAIN", "BITS", "NIB", "CODES", "HALO_BN", "LEVELS", "HALF_BF16", "HALF_F16"))
 
 
 def _conv_describe(fn: str, elem, Nimg, H, W, Cw, kernel, stride, padding, dilation, ldwp, Cout, in_halo, epilogue, has_thr, d2s_cout,
@@ -3769,10 +3777,7 @@ def packed_gemm_algorithmic_bytes(M: int, N: int, K: int, impl: str = "valu", pl
 
 class _OptimTensor(_ct.Structure):
     """qt_optim_tensor of include/qt_hip.h."""
-    _fields_ = [("p", _ct.c_void_p), ("g", _ct.c_void_p), ("s0", _ct.c_void_p), ("s1", _ct.c_void_p), ("numel", _ct.c_int64),
-                ("words", _ct.c_void_p), ("ld", _ct.c_int64), ("rows", _ct.c_int64), ("K", _ct.c_int64),
-                ("lo", _ct.c_float), ("hi", _ct.c_float), ("c0", _ct.c_float), ("c1", _ct.c_float),
-                ("kind", _ct.c_int32), ("flags", _ct.c_int32)]
+    _fields_ = _lib.STRUCTS["qt_optim_tensor"]
 
 
 _PLANE_KIND = {"binary": 1, "ternary": 2}

@@ -23,6 +23,16 @@ def test_header_symbols_all_bound_and_exported(lib):
         assert hasattr(lib, name), f"{name} not exported by libqt_hip.so"
 
 
+def test_every_bound_function_carries_the_header_signature(lib):
+    """load() leaves no entry point with ctypes' defaults (int result, unchecked arguments): each one converts its arguments as
+    include/qt_hip.h declares them."""
+    assert len(_lib.SIGNATURES) == len(_lib.header_declared_functions())
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype, name
+        assert list(fn.argtypes) == argtypes and all(a is b for a, b in zip(fn.argtypes, argtypes)), name
+
+
 def test_default_build_reads_no_environment(lib):
     """A/B switches are call arguments (the QT_CONV_* flags, ``variant``); the tool-only environment reads
     exist in -DQT_PROFILING_VARIANTS / -DQT_EXPERIMENT builds alone, so the product library does not even import getenv."""
