@@ -1145,34 +1145,47 @@ int qt_nib_gemm_variant(int variant, const uint32_t* Xn, int64_t ldxp, const uin
  *                ld % 4 == 0, 16-byte aligned (QT_ERR_ALIGNMENT otherwise).  Every word of every row up to ld is written,
  *                pad words and tail nibbles as zero.
  *   flags      : bit 0 (SGD with momentum): first step of this tensor, momentum_buffer = gradient (its old content is ignored).
- * The whole table is validated before anything is enqueued (null table with n > 0, negative counts, null tensors,
- * inconsistent planes: a negative status, nothing launched).
  *
+ * Two recurrences, one entry each:
  *   qt_optim_sgd_f32  : torch.optim.SGD with dampening 0: g += weight_decay p; buf = momentum buf + g; g = nesterov ?
  *                       g + momentum buf : buf; p -= lr g.  momentum == 0: no state is read (nesterov must be 0).
  *   qt_optim_adam_f32 : torch.optim.Adam (L2 weight decay, no amsgrad): g += weight_decay p; m = beta1 m + (1 - beta1) g;
  *                       v = beta2 v + (1 - beta2) g g; p -= c0 m / (sqrt(v) / c1 + eps).  One rounding per operation.
  *
- * The `_dev` entries are the same updates with the per-step scalars read from DEVICE memory when the kernel runs, not
- * from the argument block when it is enqueued: a launch captured in a hipGraph then follows the values the caller
- * writes there before each replay (utils.GraphedTrainStep with an optimiser).  Same arithmetic, operation for
- * operation: for equal scalars they store the bits of the entries above.
- *   qt_optim_sgd_dev_f32  : `lr` points to one float.  flags bit 0 keeps its meaning.
- *   qt_optim_adam_dev_f32 : `coef` points to n pairs, coef[2 i] = c0 and coef[2 i + 1] = c1 of TABLE entry i (empty
- *                           tensors keep their pair); the descriptors' c0 / c1 are ignored.
- * `lr` / `coef` are validated with the table, before anything is enqueued: null with n > 0 is QT_ERR_INVALID_ARG,
- * not 4-byte aligned is QT_ERR_ALIGNMENT; n == 0 is QT_OK whatever they are.  They must stay valid, and hold the
- * step's values, until the launch (or every replay of it) has run.
+ * Three optional inputs, each one word (or array of words) of DEVICE memory that is read when the kernel RUNS, not when it is
+ * enqueued.  `form` states which of them are given; a pointer is non-null exactly when its bit is set, so that a forgotten
+ * pointer is an error and never a different update.  The arithmetic is one template in every form: for equal values all
+ * forms store the same bits.
+ *   QT_OPTIM_SCALARS_DEV : the per-step scalars come from device memory, so a launch captured in a hipGraph follows the
+ *                       values the caller writes there before each replay (utils.GraphedTrainStep with an optimiser).  SGD:
+ *                       `lr_dev` points to one float and `lr` is ignored.  Adam: `coef` points to n pairs, coef[2 i] = c0 and
+ *                       coef[2 i + 1] = c1 of TABLE entry i (empty tensors keep their pair), and the descriptors' c0 / c1 are
+ *                       ignored.  Without the bit SGD takes `lr` by value and Adam c0 / c1 from the descriptors.  flags bit 0
+ *                       of a descriptor keeps its meaning in every form.
+ *   QT_OPTIM_GSCALE   : g = g * (*gscale) first: one separate fp32 multiplication, in front of the weight-decay term, with
+ *                       `gscale` one float (out + 1 of qt_optim_grad_norm_finalize_f32 below).  The gradient in memory is not
+ *                       rewritten.  *gscale == 1.0f stores the bits of the update without it.
+ *   QT_OPTIM_SKIP     : `skip` points to one int32.  Every workgroup reads *skip once before it touches any tensor and, if it
+ *                       is non-zero, returns without reading or writing p, the state or the plane.  *skip == 0 stores the
+ *                       bits of the update without it.
+ * The pointers must stay valid, and hold the step's values, until the launch (or every replay of it) has run.
+ *
+ * Everything is validated before anything is enqueued, in this order; a negative status means nothing was launched:
+ *   1. SGD: nesterov with momentum == 0: QT_ERR_INVALID_ARG.
+ *   2. `form` has a bit outside QT_OPTIM_FORM_MASK: QT_ERR_INVALID_ARG.
+ *   3. n == 0: QT_OK, whatever the pointers are.
+ *   4. n < 0: QT_ERR_INVALID_ARG.
+ *   5. The scalars (`lr_dev` / `coef`), then `gscale`, then `skip`: bit set and pointer null, or bit clear and pointer
+ *      non-null: QT_ERR_INVALID_ARG; bit set and pointer not 4-byte aligned: QT_ERR_ALIGNMENT.
+ *   6. The table: null, null tensors, negative counts, inconsistent planes: QT_ERR_INVALID_ARG; misaligned tensors or planes:
+ *      QT_ERR_ALIGNMENT; a tensor of more than INT32_MAX units: QT_ERR_UNSUPPORTED.
+ *
+ * What feeds the optional inputs:
  *   qt_optim_scalars_f32  : writes n HOST floats `values` to DEVICE memory `dst`, ordered on `stream` like a kernel: the
  *                           values travel in the launch's argument block (copied when the call is made, so `values` may
  *                           be reused at once; 960 floats per launch), not through a host-to-device copy.  How the
- *                           caller of a replayed `_dev` launch sets the next step's scalars without a synchronise.
+ *                           caller of a replayed launch sets the next step's scalars without a synchronise.
  *                           Null dst / values with n > 0, n < 0: QT_ERR_INVALID_ARG; dst not 4-byte aligned: QT_ERR_ALIGNMENT.
- *
- * The `_dev_guard` entries are the `_dev` entries plus `skip`, one int32 of DEVICE memory read when the kernel runs: every
- * workgroup reads *skip once before it touches any tensor and, if it is non-zero, returns without reading or writing p, the
- * state or the plane.  With *skip == 0 they store the bits of the `_dev` entries (the same code).  `skip` is validated after
- * `lr` / `coef`: null with n > 0 is QT_ERR_INVALID_ARG, not 4-byte aligned QT_ERR_ALIGNMENT; n == 0 is QT_OK.
  *   qt_flags_or_i32 : *guard |= (any *flags[i] != 0).  `flags` is a HOST array of n DEVICE pointers to int32 flags; the pointers
  *                     travel in the launch's argument block in chunks of qt_flags_chunk_capacity() (one launch per chunk, no
  *                     device allocation, no host-to-device copy), so the array may be freed as soon as the call returns.  A
@@ -1180,8 +1193,8 @@ int qt_nib_gemm_variant(int variant, const uint32_t* Xn, int64_t ldxp, const uin
  *                     null `flags`, `guard` or flags[i]: QT_ERR_INVALID_ARG; a pointer that is not 4-byte aligned:
  *                     QT_ERR_ALIGNMENT; n == 0: QT_OK whatever the pointers are.
  *
- * Global gradient-norm clipping inside the update (torch.nn.utils.clip_grad_norm_, L2 norm, error_if_nonfinite=False), as
- * three stream-ordered steps with no atomics, no counter and no buffer that must be zero beforehand:
+ * The global gradient norm `gscale` comes from (torch.nn.utils.clip_grad_norm_, L2 norm, error_if_nonfinite=False), as
+ * stream-ordered steps with no atomics, no counter and no buffer that must be zero beforehand:
  *   qt_optim_grad_norm_work_floats : fp32 words of workspace the sum-of-squares pass over `table` writes: one per unit of 4096
  *                           gradient elements, sum over the tensors of ceil(numel / 4096).  Only g and numel of a descriptor are
  *                           looked at (here and in qt_optim_grad_sumsq_f32); a negative qt_status for a table that entry rejects.
@@ -1197,15 +1210,6 @@ int qt_nib_gemm_variant(int variant, const uint32_t* Xn, int64_t ldxp, const uin
  *                           other give ONE global norm.  A non-finite sum is not special: an infinite norm gives coef 0, NaN
  *                           gives NaN, which the update propagates.  m == 0 gives norm 0 and coef 1.  m < 0, null `out`, null
  *                           `work` with m > 0: QT_ERR_INVALID_ARG; a pointer not 4-byte aligned: QT_ERR_ALIGNMENT.
- *   qt_optim_sgd_clip_f32 / qt_optim_adam_clip_f32 : the updates above with g = g * (*gscale) first: one separate fp32
- *                           multiplication, in front of the weight-decay term, with `gscale` one DEVICE float (out + 1 of the
- *                           finalise) read when the kernel runs.  The gradient in memory is not rewritten.  Same body: with
- *                           *gscale == 1.0f they store the bits of the unclipped entries.  One entry per rule covers their three
- *                           forms through nullable pointers: `lr_dev` null = `lr` by value, else `lr` is ignored (`_dev`);
- *                           `coef` null = the descriptors' c0 / c1, else as in qt_optim_adam_dev_f32; `skip` null = no guard,
- *                           else as in the `_dev_guard` entries.  Null `gscale` with n > 0: QT_ERR_INVALID_ARG; gscale, lr_dev,
- *                           coef or skip not 4-byte aligned: QT_ERR_ALIGNMENT; n == 0: QT_OK.  Validated with the table, before
- *                           anything is enqueued.
  * ---------------------------------------------------------------------------------------- */
 typedef struct qt_optim_tensor {
     float* p;
@@ -1220,30 +1224,22 @@ typedef struct qt_optim_tensor {
     int32_t flags;
 } qt_optim_tensor;
 
+#define QT_OPTIM_SCALARS_DEV 0x1   /* lr_dev / coef is given: per-step scalars are read from device memory when the kernel runs */
+#define QT_OPTIM_GSCALE      0x2   /* gscale is given: g = g * (*gscale) first */
+#define QT_OPTIM_SKIP        0x4   /* skip is given: non-zero *skip leaves everything untouched */
+#define QT_OPTIM_FORM_MASK   0x7
+
 int qt_optim_chunk_capacity(void);
-int qt_optim_sgd_f32(const qt_optim_tensor* table, int64_t n, float lr, float momentum, float weight_decay, int nesterov,
-                     qt_stream_t stream);
-int qt_optim_adam_f32(const qt_optim_tensor* table, int64_t n, float beta1, float one_minus_beta1, float beta2,
-                      float one_minus_beta2, float eps, float weight_decay, qt_stream_t stream);
+int qt_optim_sgd_f32(const qt_optim_tensor* table, int64_t n, int form, float lr, const float* lr_dev, const float* gscale,
+                     const int32_t* skip, float momentum, float weight_decay, int nesterov, qt_stream_t stream);
+int qt_optim_adam_f32(const qt_optim_tensor* table, int64_t n, int form, const float* coef, const float* gscale,
+                      const int32_t* skip, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2,
+                      float eps, float weight_decay, qt_stream_t stream);
 int qt_optim_scalars_f32(float* dst, const float* values, int64_t n, qt_stream_t stream);
-int qt_optim_sgd_dev_f32(const qt_optim_tensor* table, int64_t n, const float* lr, float momentum, float weight_decay,
-                         int nesterov, qt_stream_t stream);
-int qt_optim_adam_dev_f32(const qt_optim_tensor* table, int64_t n, const float* coef, float beta1, float one_minus_beta1,
-                          float beta2, float one_minus_beta2, float eps, float weight_decay, qt_stream_t stream);
-int qt_optim_sgd_dev_guard_f32(const qt_optim_tensor* table, int64_t n, const float* lr, const int32_t* skip, float momentum,
-                               float weight_decay, int nesterov, qt_stream_t stream);
-int qt_optim_adam_dev_guard_f32(const qt_optim_tensor* table, int64_t n, const float* coef, const int32_t* skip, float beta1,
-                                float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float weight_decay,
-                                qt_stream_t stream);
 int64_t qt_optim_grad_norm_work_floats(const qt_optim_tensor* table, int64_t n);
 int qt_optim_grad_sumsq_f32(const qt_optim_tensor* table, int64_t n, float* work, qt_stream_t stream);
 int qt_optim_grad_norm_finalize_f32(const float* work, int64_t m, float max_norm, const float* max_norm_dev, float* out,
                                     qt_stream_t stream);
-int qt_optim_sgd_clip_f32(const qt_optim_tensor* table, int64_t n, float lr, const float* lr_dev, const float* gscale,
-                          const int32_t* skip, float momentum, float weight_decay, int nesterov, qt_stream_t stream);
-int qt_optim_adam_clip_f32(const qt_optim_tensor* table, int64_t n, const float* coef, const float* gscale, const int32_t* skip,
-                           float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float weight_decay,
-                           qt_stream_t stream);
 int qt_flags_chunk_capacity(void);
 int qt_flags_or_i32(const int32_t* const* flags, int64_t n, int32_t* guard, qt_stream_t stream);
 

@@ -20,27 +20,24 @@
 //     lane owns the 8 consecutive K elements of one word (two dwordx4 per stream when K % 4 == 0 and the pointers
 //     allow it, scalar otherwise) and stores the word; words from ceil(K/8) to ld and the tail nibbles of a row's
 //     last word are written as zero, so the plane may be uninitialised memory.
-//   * per-step scalars (learning rate; Adam's bias corrections c0, c1) reach the recurrence through a SOURCE type: the
-//     by-value entries take them from the argument block / the descriptor, the `_dev` entries (qt_optim_sgd_dev_f32 /
-//     qt_optim_adam_dev_f32) from device memory, so that a launch captured in a hipGraph sees the values of the step
-//     it is replayed for.  A workgroup reads them once per tensor it walks (a wave-uniform load where the tensor index
-//     advances), never per element; the arithmetic is the same template, so equal scalars give equal bits.  Adam's
-//     `coef` is indexed by the TABLE index of a tensor: a chunk carries, per slot, the table index relative to its
-//     first slot (empty tensors are dropped, later chunks start anywhere) and the launch gets `coef` rebased to that.
-//     qt_optim_scalars_f32 is how the host gets them there between replays: a launch whose ARGUMENT BLOCK carries the values
-//     (up to 960 floats per launch), stream-ordered like any kernel, with no staging buffer for a later call to overwrite.
-//   * the `_dev_guard` entries (qt_optim_sgd_dev_guard_f32 / qt_optim_adam_dev_guard_f32) are the `_dev` entries behind one
-//     device word: every workgroup reads *skip once, before it touches a tensor, and leaves when it is non-zero — how a
+//   * one entry per rule (qt_optim_sgd_f32 / qt_optim_adam_f32) and ONE kernel template.  The three optional inputs of an entry
+//     (its `form`: QT_OPTIM_SCALARS_DEV, QT_OPTIM_GSCALE, QT_OPTIM_SKIP) choose the rule's SOURCE types and the skip pointer the
+//     kernel gets; the arithmetic is the one template in every form, so equal values give equal bits.
+//   * per-step scalars (learning rate; Adam's bias corrections c0, c1) come from the argument block / the descriptor, or, with
+//     QT_OPTIM_SCALARS_DEV, from device memory, so that a launch captured in a hipGraph sees the values of the step it is
+//     replayed for.  A workgroup reads them once per tensor it walks (a wave-uniform load where the tensor index advances),
+//     never per element.  Adam's `coef` is indexed by the TABLE index of a tensor: a chunk carries, per slot, the table index
+//     relative to its first slot (empty tensors are dropped, later chunks start anywhere) and the launch gets `coef` rebased to
+//     that.  qt_optim_scalars_f32 is how the host gets them there between replays: a launch whose ARGUMENT BLOCK carries the
+//     values (up to 960 floats per launch), stream-ordered like any kernel, with no staging buffer for a later call to overwrite.
+//   * QT_OPTIM_GSCALE: the gradient is multiplied by one device float first: g = g * (*gscale), a separate fp32 multiplication
+//     in front of the weight-decay term, where torch.nn.utils.clip_grad_norm_'s in-place mul_ puts it — but the gradient in
+//     memory is not rewritten.  *gscale is read with the other per-step scalars, once per (workgroup, tensor).  Without the
+//     bit the scale's source type is NoScale, which compiles to nothing.
+//   * QT_OPTIM_SKIP: every workgroup reads *skip once, before it touches a tensor, and leaves when it is non-zero — how a
 //     captured training step keeps parameters, state and planes untouched when one of its trusted route verdicts turned out
-//     wrong (utils.GraphedTrainStep(recover=True)).  Same body, so *skip == 0 stores the bits of the `_dev` entries.
+//     wrong (utils.GraphedTrainStep(recover=True)).  Without the bit the kernel gets a null pointer and does not read it.
 //     qt_flags_or_i32 folds the step's verdict flags into that word: the flag POINTERS travel by value, 448 per launch.
-//   * the `_clip` entries (qt_optim_sgd_clip_f32 / qt_optim_adam_clip_f32) are the same updates with the gradient multiplied by
-//     one device float first: g = g * (*gscale), a separate fp32 multiplication in front of the weight-decay term, where
-//     torch.nn.utils.clip_grad_norm_'s in-place mul_ puts it — but the gradient in memory is not rewritten.  *gscale is read with
-//     the other per-step scalars, once per (workgroup, tensor).  The scale is a SOURCE type as well (NoScale compiles to
-//     nothing), so the body is the one template and *gscale == 1.0f stores the bits of the entries above.  Their learning rate /
-//     bias corrections come from the argument block or from device memory, and their skip word may be null: one kernel per
-//     rule serves the by-value, `_dev` and `_dev_guard` forms.
 //   * the global gradient norm that scale comes from (qt_optim_grad_sumsq_f32 / qt_optim_grad_norm_finalize_f32, below the update):
 //     one fp32 partial per 4096-element unit in a caller's workspace, then one workgroup that adds the partials in fp64.  Fixed
 //     order everywhere, no atomics, no counter, no buffer that has to be zero before the launch.
@@ -278,8 +275,11 @@ __device__ __forceinline__ void plane_unit(const Rule& r, const typename Rule::S
     }
 }
 
+// skip: null, or one device word.  One wave-uniform read before any tensor is touched; non-zero = the whole workgroup leaves,
+// so p, the state and the plane keep their bits.
 template <class Rule>
-__device__ __forceinline__ void optim_step_body(const OptimChunk& c, const Rule& r) {
+__global__ __launch_bounds__(256) void optim_step_kernel(const OptimChunk c, const Rule r, const int32_t* skip) {
+    if (skip && *skip != 0) return;
     const int total = c.ustart[c.n];
     int ti = 0, have = -1;
     typename Rule::Step st{};
@@ -294,26 +294,6 @@ __device__ __forceinline__ void optim_step_body(const OptimChunk& c, const Rule&
         if (t.kind != 0) plane_unit(r, st, t, b);
         else flat_unit(r, st, t, b);
     }
-}
-
-template <class Rule>
-__global__ __launch_bounds__(256) void optim_step_kernel(const OptimChunk c, const Rule r) {
-    optim_step_body(c, r);
-}
-
-// The guarded form (`_dev_guard` entries): one wave-uniform read of *skip before any tensor is touched; non-zero = the
-// whole workgroup leaves, so p, the state and the plane keep their bits.  With *skip == 0 it is the body above.
-template <class Rule>
-__global__ __launch_bounds__(256) void optim_step_guard_kernel(const OptimChunk c, const Rule r, const int32_t* skip) {
-    if (*skip != 0) return;
-    optim_step_body(c, r);
-}
-
-// The form of the `_clip` entries: the skip word may be null (no guard), else it is the guard above.
-template <class Rule>
-__global__ __launch_bounds__(256) void optim_step_clip_kernel(const OptimChunk c, const Rule r, const int32_t* skip) {
-    if (skip && *skip != 0) return;
-    optim_step_body(c, r);
 }
 
 template <class Rule>
@@ -341,35 +321,16 @@ int64_t tensor_units(const qt_optim_tensor& t) {
     return (t.numel + FLAT_UNIT - 1) / FLAT_UNIT;
 }
 
-// The guard of a launch sequence is a TYPE, so that only the entries that take one instantiate the guarded kernel.
-struct NoGuard {};
-struct DevGuard { const int32_t* skip; };
-struct OptGuard { const int32_t* skip; };          // `_clip` entries: null = no guard
-
 template <class Rule>
-void enqueue_chunk(const OptimChunk& c, const Rule& r, NoGuard, int grid, hipStream_t s) {
-    hipLaunchKernelGGL(optim_step_kernel<Rule>, dim3(grid), dim3(256), 0, s, c, r);
-}
-template <class Rule>
-void enqueue_chunk(const OptimChunk& c, const Rule& r, DevGuard g, int grid, hipStream_t s) {
-    hipLaunchKernelGGL(optim_step_guard_kernel<Rule>, dim3(grid), dim3(256), 0, s, c, r, g.skip);
-}
-
-template <class Rule>
-void enqueue_chunk(const OptimChunk& c, const Rule& r, OptGuard g, int grid, hipStream_t s) {
-    hipLaunchKernelGGL(optim_step_clip_kernel<Rule>, dim3(grid), dim3(256), 0, s, c, r, g.skip);
-}
-
-template <class Rule, class Guard>
-int launch_chunk(const OptimChunk& c, const Rule& r, Guard g, qt_stream_t stream) {
+int launch_chunk(const OptimChunk& c, const Rule& r, const int32_t* skip, qt_stream_t stream) {
     const int total = c.ustart[c.n];
     if (c.n == 0 || total == 0) return QT_OK;
-    enqueue_chunk(c, r, g, qt_stream_grid(total), (hipStream_t)stream);
+    hipLaunchKernelGGL(optim_step_kernel<Rule>, dim3(qt_stream_grid(total)), dim3(256), 0, (hipStream_t)stream, c, r, skip);
     return qt_check_launch();
 }
 
-template <class Rule, class Guard = NoGuard>
-int optim_step(const qt_optim_tensor* tab, int64_t n, const Rule& r, qt_stream_t stream, Guard skip = Guard{}) {
+template <class Rule>
+int optim_step(const qt_optim_tensor* tab, int64_t n, const Rule& r, const int32_t* skip, qt_stream_t stream) {
     if (n < 0 || (n > 0 && !tab)) return QT_ERR_INVALID_ARG;
     for (int64_t i = 0; i < n; ++i) {              // the whole table is checked before anything is enqueued
         const int rc = check_tensor<Rule>(tab[i]);
@@ -402,6 +363,34 @@ int optim_step(const qt_optim_tensor* tab, int64_t n, const Rule& r, qt_stream_t
     return launch_chunk(c, r.at_base(base), skip, stream);
 }
 
+// One optional device word of an update entry (per-step scalars, gscale, skip): given exactly when its form bit says so.
+int check_word(const void* p, bool flagged) {
+    if (flagged != (p != nullptr)) return QT_ERR_INVALID_ARG;
+    if (reinterpret_cast<uintptr_t>(p) & 3u) return QT_ERR_ALIGNMENT;
+    return QT_OK;
+}
+
+// What both update entries check in front of the table, in the order of include/qt_hip.h.  go = false: n == 0, nothing to do.
+int check_form(int form, int64_t n, const float* scalars, const float* gscale, const int32_t* skip, bool& go) {
+    go = false;
+    if (form & ~QT_OPTIM_FORM_MASK) return QT_ERR_INVALID_ARG;
+    if (n == 0) return QT_OK;
+    if (n < 0) return QT_ERR_INVALID_ARG;
+    int rc = check_word(scalars, form & QT_OPTIM_SCALARS_DEV);
+    if (rc == QT_OK) rc = check_word(gscale, form & QT_OPTIM_GSCALE);
+    if (rc == QT_OK) rc = check_word(skip, form & QT_OPTIM_SKIP);
+    go = rc == QT_OK;
+    return rc;
+}
+
+// The rule's two source types, chosen from the form: f(scalar source, gradient scale).
+template <class Value, class Device, class F>
+int with_sources(int form, const Value& value, const Device& device, const float* gscale, F f) {
+    const bool dev = form & QT_OPTIM_SCALARS_DEV;
+    if (form & QT_OPTIM_GSCALE) return dev ? f(device, DevScale{gscale}) : f(value, DevScale{gscale});
+    return dev ? f(device, NoScale{}) : f(value, NoScale{});
+}
+
 #define QT_SCALARS_CHUNK 960               // 3840 bytes of values + pointer + count: below the 4096-byte argument limit
 struct ScalarChunk {
     float v[QT_SCALARS_CHUNK];
@@ -409,21 +398,6 @@ struct ScalarChunk {
 
 __global__ __launch_bounds__(256) void optim_scalars_kernel(float* dst, const ScalarChunk c, int n) {
     for (int i = threadIdx.x; i < n; i += 256) dst[i] = c.v[i];
-}
-
-// the device scalars of a `_dev` entry: looked at only when there is a tensor to update
-int check_scalars(const float* s, int64_t n) {
-    if (n < 0) return QT_ERR_INVALID_ARG;          // the status optim_step() gives: every table rejection comes first
-    if (n > 0 && !s) return QT_ERR_INVALID_ARG;
-    if (reinterpret_cast<uintptr_t>(s) & 3u) return QT_ERR_ALIGNMENT;
-    return QT_OK;
-}
-
-// the skip word of a `_dev_guard` entry: validated like the device scalars, after them
-int check_skip(const int32_t* skip) {
-    if (!skip) return QT_ERR_INVALID_ARG;
-    if (reinterpret_cast<uintptr_t>(skip) & 3u) return QT_ERR_ALIGNMENT;
-    return QT_OK;
 }
 
 #define QT_FLAGS_CHUNK 448                 // 3584 bytes of pointers + guard + count: below the 4096-byte argument limit
@@ -590,13 +564,6 @@ int64_t grad_sumsq_chunks(const qt_optim_tensor* tab, int64_t n, Emit emit) {
     return first;
 }
 
-// the gradient scale of a `_clip` entry: validated like the device scalars, after them
-int check_gscale(const float* gscale) {
-    if (!gscale) return QT_ERR_INVALID_ARG;
-    if (reinterpret_cast<uintptr_t>(gscale) & 3u) return QT_ERR_ALIGNMENT;
-    return QT_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -617,58 +584,31 @@ int qt_optim_scalars_f32(float* dst, const float* values, int64_t n, qt_stream_t
     return QT_OK;
 }
 
-int qt_optim_sgd_f32(const qt_optim_tensor* table, int64_t n, float lr, float momentum, float weight_decay, int nesterov,
-                     qt_stream_t stream) {
+int qt_optim_sgd_f32(const qt_optim_tensor* table, int64_t n, int form, float lr, const float* lr_dev, const float* gscale,
+                     const int32_t* skip, float momentum, float weight_decay, int nesterov, qt_stream_t stream) {
     if (nesterov && momentum == 0.0f) return QT_ERR_INVALID_ARG;
-    if (momentum != 0.0f) return optim_step(table, n, SgdRule<1, LrValue>{{}, {lr}, momentum, weight_decay, nesterov ? 1 : 0}, stream);
-    return optim_step(table, n, SgdRule<0, LrValue>{{}, {lr}, 0.0f, weight_decay, 0}, stream);
+    bool go;
+    const int rc = check_form(form, n, lr_dev, gscale, skip, go);
+    if (!go) return rc;
+    return with_sources(form, LrValue{lr}, LrDevice{lr_dev}, gscale, [&](auto src, auto gs) {
+        using Lr = decltype(src);
+        using Gs = decltype(gs);
+        if (momentum != 0.0f)
+            return optim_step(table, n, SgdRule<1, Lr, Gs>{gs, src, momentum, weight_decay, nesterov ? 1 : 0}, skip, stream);
+        return optim_step(table, n, SgdRule<0, Lr, Gs>{gs, src, 0.0f, weight_decay, 0}, skip, stream);
+    });
 }
 
-int qt_optim_sgd_dev_f32(const qt_optim_tensor* table, int64_t n, const float* lr, float momentum, float weight_decay,
-                         int nesterov, qt_stream_t stream) {
-    if (nesterov && momentum == 0.0f) return QT_ERR_INVALID_ARG;
-    if (n == 0) return QT_OK;
-    const int rc = check_scalars(lr, n);
-    if (rc != QT_OK) return rc;
-    if (momentum != 0.0f) return optim_step(table, n, SgdRule<1, LrDevice>{{}, {lr}, momentum, weight_decay, nesterov ? 1 : 0}, stream);
-    return optim_step(table, n, SgdRule<0, LrDevice>{{}, {lr}, 0.0f, weight_decay, 0}, stream);
-}
-
-int qt_optim_adam_f32(const qt_optim_tensor* table, int64_t n, float beta1, float one_minus_beta1, float beta2,
-                      float one_minus_beta2, float eps, float weight_decay, qt_stream_t stream) {
-    return optim_step(table, n, AdamRule<CoefTable>{{}, {}, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay}, stream);
-}
-
-int qt_optim_adam_dev_f32(const qt_optim_tensor* table, int64_t n, const float* coef, float beta1, float one_minus_beta1,
-                          float beta2, float one_minus_beta2, float eps, float weight_decay, qt_stream_t stream) {
-    if (n == 0) return QT_OK;
-    const int rc = check_scalars(coef, n);
-    if (rc != QT_OK) return rc;
-    return optim_step(table, n, AdamRule<CoefDevice>{{}, {coef}, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay},
-                      stream);
-}
-
-int qt_optim_sgd_dev_guard_f32(const qt_optim_tensor* table, int64_t n, const float* lr, const int32_t* skip, float momentum,
-                               float weight_decay, int nesterov, qt_stream_t stream) {
-    if (nesterov && momentum == 0.0f) return QT_ERR_INVALID_ARG;
-    if (n == 0) return QT_OK;
-    int rc = check_scalars(lr, n);
-    if (rc == QT_OK) rc = check_skip(skip);
-    if (rc != QT_OK) return rc;
-    if (momentum != 0.0f)
-        return optim_step(table, n, SgdRule<1, LrDevice>{{}, {lr}, momentum, weight_decay, nesterov ? 1 : 0}, stream, DevGuard{skip});
-    return optim_step(table, n, SgdRule<0, LrDevice>{{}, {lr}, 0.0f, weight_decay, 0}, stream, DevGuard{skip});
-}
-
-int qt_optim_adam_dev_guard_f32(const qt_optim_tensor* table, int64_t n, const float* coef, const int32_t* skip, float beta1,
-                                float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float weight_decay,
-                                qt_stream_t stream) {
-    if (n == 0) return QT_OK;
-    int rc = check_scalars(coef, n);
-    if (rc == QT_OK) rc = check_skip(skip);
-    if (rc != QT_OK) return rc;
-    return optim_step(table, n, AdamRule<CoefDevice>{{}, {coef}, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay},
-                      stream, DevGuard{skip});
+int qt_optim_adam_f32(const qt_optim_tensor* table, int64_t n, int form, const float* coef, const float* gscale,
+                      const int32_t* skip, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float eps,
+                      float weight_decay, qt_stream_t stream) {
+    bool go;
+    const int rc = check_form(form, n, coef, gscale, skip, go);
+    if (!go) return rc;
+    return with_sources(form, CoefTable{}, CoefDevice{coef}, gscale, [&](auto src, auto gs) {
+        return optim_step(table, n, AdamRule<decltype(src), decltype(gs)>{gs, src, beta1, one_minus_beta1, beta2, one_minus_beta2,
+                                                                         eps, weight_decay}, skip, stream);
+    });
 }
 
 int64_t qt_optim_grad_norm_work_floats(const qt_optim_tensor* table, int64_t n) {
@@ -704,46 +644,6 @@ int qt_optim_grad_norm_finalize_f32(const float* work, int64_t m, float max_norm
         return QT_ERR_ALIGNMENT;
     hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, work, m, max_norm, max_norm_dev, out);
     return qt_check_launch();
-}
-
-int qt_optim_sgd_clip_f32(const qt_optim_tensor* table, int64_t n, float lr, const float* lr_dev, const float* gscale,
-                          const int32_t* skip, float momentum, float weight_decay, int nesterov, qt_stream_t stream) {
-    if (nesterov && momentum == 0.0f) return QT_ERR_INVALID_ARG;
-    if (n == 0) return QT_OK;
-    if (n < 0) return QT_ERR_INVALID_ARG;
-    int rc = (reinterpret_cast<uintptr_t>(lr_dev) & 3u) ? QT_ERR_ALIGNMENT : QT_OK;
-    if (rc == QT_OK) rc = check_gscale(gscale);
-    if (rc == QT_OK && skip) rc = check_skip(skip);
-    if (rc != QT_OK) return rc;
-    const DevScale gs{gscale};
-    const OptGuard guard{skip};
-    const int nes = nesterov ? 1 : 0;
-    if (lr_dev) {
-        if (momentum != 0.0f)
-            return optim_step(table, n, SgdRule<1, LrDevice, DevScale>{gs, {lr_dev}, momentum, weight_decay, nes}, stream, guard);
-        return optim_step(table, n, SgdRule<0, LrDevice, DevScale>{gs, {lr_dev}, 0.0f, weight_decay, 0}, stream, guard);
-    }
-    if (momentum != 0.0f)
-        return optim_step(table, n, SgdRule<1, LrValue, DevScale>{gs, {lr}, momentum, weight_decay, nes}, stream, guard);
-    return optim_step(table, n, SgdRule<0, LrValue, DevScale>{gs, {lr}, 0.0f, weight_decay, 0}, stream, guard);
-}
-
-int qt_optim_adam_clip_f32(const qt_optim_tensor* table, int64_t n, const float* coef, const float* gscale, const int32_t* skip,
-                           float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float weight_decay,
-                           qt_stream_t stream) {
-    if (n == 0) return QT_OK;
-    if (n < 0) return QT_ERR_INVALID_ARG;
-    int rc = (reinterpret_cast<uintptr_t>(coef) & 3u) ? QT_ERR_ALIGNMENT : QT_OK;
-    if (rc == QT_OK) rc = check_gscale(gscale);
-    if (rc == QT_OK && skip) rc = check_skip(skip);
-    if (rc != QT_OK) return rc;
-    const DevScale gs{gscale};
-    const OptGuard guard{skip};
-    if (coef)
-        return optim_step(table, n, AdamRule<CoefDevice, DevScale>{gs, {coef}, beta1, one_minus_beta1, beta2, one_minus_beta2, eps,
-                                                                   weight_decay}, stream, guard);
-    return optim_step(table, n, AdamRule<CoefTable, DevScale>{gs, {}, beta1, one_minus_beta1, beta2, one_minus_beta2, eps,
-                                                              weight_decay}, stream, guard);
 }
 
 int qt_flags_chunk_capacity(void) { return QT_FLAGS_CHUNK; }

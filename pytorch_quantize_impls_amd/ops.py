@@ -3831,15 +3831,39 @@ def _optim_table(params, grads, s0, s1, clamps, planes):
     return tab, dev
 
 
+_OPTIM_SCALARS_DEV, _OPTIM_GSCALE, _OPTIM_SKIP = (_lib.DEFINES[k] for k in ("QT_OPTIM_SCALARS_DEV", "QT_OPTIM_GSCALE", "QT_OPTIM_SKIP"))
+
+
+def _optim_call(entry: str, tab, n: int, dev, by_value, scalars, gscale, skip, hp) -> None:
+    """The one call all four wrappers end in: checks the optional device inputs that are given, states them in ``form`` and
+    enqueues ``entry`` (qt_optim_sgd_f32 / qt_optim_adam_f32).  ``by_value``: what the entry takes between ``form`` and the
+    device-scalar pointer (SGD's ``lr``).  ``scalars``: None, or (tensor, its element count, its name in the wrapper)."""
+    form = 0
+    if scalars is not None:
+        scalars, numel, name = scalars
+        _optim_scalars_check(scalars, dev, numel, name)
+        form |= _OPTIM_SCALARS_DEV
+    if skip is not None:
+        _optim_skip_check(skip, dev)
+        form |= _OPTIM_SKIP
+    if gscale is not None:
+        _optim_scalars_check(gscale, dev, 1, "gscale")
+        form |= _OPTIM_GSCALE
+    with _on(dev):
+        _lib.call(entry, _ct.addressof(tab), n, form, *by_value, _p(scalars), _p(gscale), _p(skip), *hp, _stream(dev))
+
+
 def optim_step_sgd(params, grads, momentum_buffers=None, *, lr: float, momentum: float = 0.0, weight_decay: float = 0.0,
-                   nesterov: bool = False, first=None, clamps=None, planes=None, gscale: Optional[torch.Tensor] = None) -> None:
+                   nesterov: bool = False, first=None, clamps=None, planes=None, gscale: Optional[torch.Tensor] = None,
+                   skip: Optional[torch.Tensor] = None) -> None:
     """One torch.optim.SGD step (dampening 0) of every tensor in the lists, in place, in one launch sequence
     (qt_optim_sgd_f32): ``p`` is clamped to ``clamps[i] = (lo, hi)`` as it is stored and, where ``planes[i] =
     (NibPlanes, "binary" | "ternary")`` is given, the nibble plane of the stored weight is written into those words.
     ``first[i]``: this is the tensor's first step, its momentum buffer becomes the gradient.  The version counters of the
     parameters are NOT touched: the caller bumps them (utils.FusedQuantSGD does).  ``gscale``: one fp32 device element the
-    gradient is multiplied by as it is read (qt_optim_sgd_clip_f32; the ``coef`` of ``optim_grad_norm``); the gradients in
-    memory stay as they are.  None: the entry without it."""
+    gradient is multiplied by as it is read (QT_OPTIM_GSCALE; the ``coef`` of ``optim_grad_norm``); the gradients in
+    memory stay as they are.  ``skip``: one int32 device element, read when the kernel runs (QT_OPTIM_SKIP): non-zero leaves
+    every tensor and plane untouched, zero stores the bits of the unguarded call."""
     if not params:
         return
     use_mom = momentum != 0
@@ -3850,21 +3874,16 @@ def optim_step_sgd(params, grads, momentum_buffers=None, *, lr: float, momentum:
         for i, f in enumerate(first):
             if f:
                 tab[i].flags = 1
-    with _on(dev):
-        if gscale is None:
-            _lib.call("qt_optim_sgd_f32", _ct.addressof(tab), len(params), float(lr), float(momentum), float(weight_decay),
-                      int(bool(nesterov)), _stream(dev))
-        else:
-            _optim_scalars_check(gscale, dev, 1, "gscale")
-            _lib.call("qt_optim_sgd_clip_f32", _ct.addressof(tab), len(params), float(lr), None, _p(gscale), None, float(momentum),
-                      float(weight_decay), int(bool(nesterov)), _stream(dev))
+    _optim_call("qt_optim_sgd_f32", tab, len(params), dev, (float(lr),), None, gscale, skip,
+                (float(momentum), float(weight_decay), int(bool(nesterov))))
 
 
 def optim_step_adam(params, grads, exp_avgs, exp_avg_sqs, steps, *, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
-                    weight_decay: float = 0.0, clamps=None, planes=None, gscale: Optional[torch.Tensor] = None) -> None:
+                    weight_decay: float = 0.0, clamps=None, planes=None, gscale: Optional[torch.Tensor] = None,
+                    skip: Optional[torch.Tensor] = None) -> None:
     """One torch.optim.Adam step (L2 weight decay, no amsgrad) in one launch sequence (qt_optim_adam_f32).  ``steps[i]``: the
     step count of tensor i INCLUDING this step; its bias corrections are computed here, in double precision.  Clamp, planes,
-    version counters and ``gscale`` (qt_optim_adam_clip_f32) as in ``optim_step_sgd``."""
+    version counters, ``gscale`` and ``skip`` as in ``optim_step_sgd``."""
     if not params:
         return
     b1, b2 = float(betas[0]), float(betas[1])
@@ -3873,14 +3892,8 @@ def optim_step_adam(params, grads, exp_avgs, exp_avg_sqs, steps, *, lr: float, b
         raise ValueError("optim_step: the tensor lists differ in length")
     for i, c in enumerate(adam_coefficients(steps, lr, (b1, b2))):
         tab[i].c0, tab[i].c1 = c
-    with _on(dev):
-        if gscale is None:
-            _lib.call("qt_optim_adam_f32", _ct.addressof(tab), len(params), b1, 1.0 - b1, b2, 1.0 - b2, float(eps),
-                      float(weight_decay), _stream(dev))
-        else:
-            _optim_scalars_check(gscale, dev, 1, "gscale")
-            _lib.call("qt_optim_adam_clip_f32", _ct.addressof(tab), len(params), None, _p(gscale), None, b1, 1.0 - b1, b2, 1.0 - b2,
-                      float(eps), float(weight_decay), _stream(dev))
+    _optim_call("qt_optim_adam_f32", tab, len(params), dev, (), None, gscale, skip,
+                (b1, 1.0 - b1, b2, 1.0 - b2, float(eps), float(weight_decay)))
 
 
 def adam_coefficients(steps, lr: float, betas=(0.9, 0.999)):
@@ -3935,56 +3948,30 @@ def optim_step_sgd_dev(params, grads, momentum_buffers, lr_dev: torch.Tensor, *,
                        nesterov: bool = False, clamps=None, planes=None, skip: Optional[torch.Tensor] = None,
                        gscale: Optional[torch.Tensor] = None) -> None:
     """``optim_step_sgd`` with the learning rate read from ``lr_dev`` (one fp32 element on the parameters' device) when the kernel
-    RUNS (qt_optim_sgd_dev_f32): the form a hipGraph can capture.  No first-step flag: the momentum buffers exist and a zeroed
-    buffer makes ``mu * 0 + g`` the first step's value.  ``skip``: one int32 device element, read when the kernel runs
-    (qt_optim_sgd_dev_guard_f32): non-zero leaves every tensor and plane untouched, zero stores the bits of the unguarded call.
-    ``gscale``: as in ``optim_step_sgd`` (qt_optim_sgd_clip_f32, with or without ``skip``)."""
+    RUNS (QT_OPTIM_SCALARS_DEV): the form a hipGraph can capture.  No first-step flag: the momentum buffers exist and a zeroed
+    buffer makes ``mu * 0 + g`` the first step's value.  ``skip`` and ``gscale``: as in ``optim_step_sgd``."""
     if not params:
         return
     use_mom = momentum != 0
     if use_mom and momentum_buffers is None:
         raise ValueError("optim_step_sgd_dev: momentum needs the momentum buffers")
     tab, dev = _optim_table(params, grads, momentum_buffers if use_mom else None, None, clamps, planes)
-    _optim_scalars_check(lr_dev, dev, 1, "lr_dev")
-    hp = (float(momentum), float(weight_decay), int(bool(nesterov)))
-    if skip is not None:
-        _optim_skip_check(skip, dev)
-    with _on(dev):
-        if gscale is not None:
-            _optim_scalars_check(gscale, dev, 1, "gscale")
-            _lib.call("qt_optim_sgd_clip_f32", _ct.addressof(tab), len(params), 0.0, _p(lr_dev), _p(gscale),
-                      None if skip is None else _p(skip), *hp, _stream(dev))
-        elif skip is None:
-            _lib.call("qt_optim_sgd_dev_f32", _ct.addressof(tab), len(params), _p(lr_dev), *hp, _stream(dev))
-        else:
-            _optim_skip_check(skip, dev)
-            _lib.call("qt_optim_sgd_dev_guard_f32", _ct.addressof(tab), len(params), _p(lr_dev), _p(skip), *hp, _stream(dev))
+    _optim_call("qt_optim_sgd_f32", tab, len(params), dev, (0.0,), (lr_dev, 1, "lr_dev"), gscale, skip,
+                (float(momentum), float(weight_decay), int(bool(nesterov))))
 
 
 def optim_step_adam_dev(params, grads, exp_avgs, exp_avg_sqs, coef_dev: torch.Tensor, *, betas=(0.9, 0.999), eps: float = 1e-8,
                         weight_decay: float = 0.0, clamps=None, planes=None, skip: Optional[torch.Tensor] = None,
                         gscale: Optional[torch.Tensor] = None) -> None:
     """``optim_step_adam`` with the bias corrections read from ``coef_dev`` (``2 * len(params)`` fp32 elements on the parameters'
-    device: ``adam_coefficients`` of tensor i at [2 i], [2 i + 1]) when the kernel RUNS (qt_optim_adam_dev_f32).  ``skip``: as in
-    ``optim_step_sgd_dev`` (qt_optim_adam_dev_guard_f32).  ``gscale``: as in ``optim_step_sgd`` (qt_optim_adam_clip_f32)."""
+    device: ``adam_coefficients`` of tensor i at [2 i], [2 i + 1]) when the kernel RUNS (QT_OPTIM_SCALARS_DEV).  ``skip`` and
+    ``gscale``: as in ``optim_step_sgd``."""
     if not params:
         return
     b1, b2 = float(betas[0]), float(betas[1])
     tab, dev = _optim_table(params, grads, exp_avgs, exp_avg_sqs, clamps, planes)
-    _optim_scalars_check(coef_dev, dev, 2 * len(params), "coef_dev")
-    hp = (b1, 1.0 - b1, b2, 1.0 - b2, float(eps), float(weight_decay))
-    if skip is not None:
-        _optim_skip_check(skip, dev)
-    with _on(dev):
-        if gscale is not None:
-            _optim_scalars_check(gscale, dev, 1, "gscale")
-            _lib.call("qt_optim_adam_clip_f32", _ct.addressof(tab), len(params), _p(coef_dev), _p(gscale),
-                      None if skip is None else _p(skip), *hp, _stream(dev))
-        elif skip is None:
-            _lib.call("qt_optim_adam_dev_f32", _ct.addressof(tab), len(params), _p(coef_dev), *hp, _stream(dev))
-        else:
-            _optim_skip_check(skip, dev)
-            _lib.call("qt_optim_adam_dev_guard_f32", _ct.addressof(tab), len(params), _p(coef_dev), _p(skip), *hp, _stream(dev))
+    _optim_call("qt_optim_adam_f32", tab, len(params), dev, (), (coef_dev, 2 * len(params), "coef_dev"), gscale, skip,
+                (b1, 1.0 - b1, b2, 1.0 - b2, float(eps), float(weight_decay)))
 
 
 def _grad_table(grads):

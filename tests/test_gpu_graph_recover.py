@@ -1,21 +1,19 @@
-"""``GraphedTrainStep(recover=True)``: the guarded training-update entries and the flag OR (csrc/optim_step.hip), and a captured step
+"""``GraphedTrainStep(recover=True)``: the guarded training update (QT_OPTIM_SKIP) and the flag OR (csrc/optim_step.hip), and a captured step
 that meets a wrong remembered verdict (utils/graphs.py).  Every comparison is bit equality against a step that cannot be wrong in the
-same way: the unguarded ``_dev`` entry, a ``recover=False`` replay while no verdict flips, and the plain eager loop in "verify" mode
+same way: the unguarded update, a ``recover=False`` replay while no verdict flips, and the plain eager loop in "verify" mode
 on the call that flips one.  The MLP, its batches, optimisers and the state twin are those of tests/test_gpu_optim_capture.py."""
 import warnings
 
 import pytest
 import torch
 
+import _optim_abi as A
 import test_gpu_optim_capture as C
 from pytorch_quantize_impls_amd import _lib, ops, utils
 from pytorch_quantize_impls_amd.functions import _fused, nnDorefaQuant
 from pytorch_quantize_impls_amd.layers import LinearDorefa
 
 pytestmark = pytest.mark.gpu
-
-NEW_ENTRIES = ("qt_flags_or_i32", "qt_optim_sgd_dev_guard_f32", "qt_optim_adam_dev_guard_f32")
-
 
 @pytest.fixture(scope="module")
 def dev():
@@ -200,11 +198,13 @@ def test_pm1_verdict_flip_is_recovered(dev, kind):
         model, plain_model = C._mlp(dev), C._mlp(dev)
         opt, plain_opt = make_opt(model), make_opt(plain_model)
         assert any(isinstance(m, torch.nn.BatchNorm1d) for m in model.modules())
-        step = utils.GraphedTrainStep(model, C._loss, x0, t0, optimizer=opt, recover=True)
+        flags_or = _lib.call_counts["qt_flags_or_i32"]
+        with A.recorded_forms() as calls:
+            step = utils.GraphedTrainStep(model, C._loss, x0, t0, optimizer=opt, recover=True)
         plain = utils.GraphedTrainStep(plain_model, C._loss, x0, t0, optimizer=plain_opt)
         assert step._armed and len(step._flags) >= 1                      # the un-tagged +-1 input of the first LinearBin
-        guarded = "qt_optim_adam_dev_guard_f32" if kind == "adam" else "qt_optim_sgd_dev_guard_f32"
-        assert _lib.call_counts[guarded] > 0 and _lib.call_counts["qt_flags_or_i32"] > 0
+        assert any(name == A.ENTRIES[kind] and form & A.SKIP for name, form in calls)
+        assert _lib.call_counts["qt_flags_or_i32"] > flags_or
 
         # +-1, +-1: nothing flips, and a clear guard costs no bit against the step without one
         for x, t in pm[:2]:
@@ -358,10 +358,11 @@ def test_recover_without_a_captured_optimiser_settles_in_the_call(dev):
 
 def test_default_step_calls_none_of_the_new_entries(dev):
     with _fused.scope(GEMM_IMPL="mfma"):
-        before = {k: _lib.call_counts[k] for k in NEW_ENTRIES}
-        model, opt, step, _ = C._captured(dev, "adam")
-        assert not step.recover
-        for x, t in C._batches(dev, 2):
-            step(x, t)
+        flags_or = _lib.call_counts["qt_flags_or_i32"]
+        with A.recorded_forms() as calls:
+            model, opt, step, _ = C._captured(dev, "adam")
+            assert not step.recover
+            for x, t in C._batches(dev, 2):
+                step(x, t)
         assert not hasattr(step, "_guard")
-        assert {k: _lib.call_counts[k] for k in NEW_ENTRIES} == before
+        assert calls and not any(form & A.SKIP for _, form in calls) and _lib.call_counts["qt_flags_or_i32"] == flags_or

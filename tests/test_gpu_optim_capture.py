@@ -1,5 +1,5 @@
-"""The fused optimiser step inside GraphedTrainStep's hipGraph (csrc/optim_step.hip `_dev` entries, utils/optim.py capture mode,
-utils/graphs.py).  Two oracles, both bit equality: the `_dev` kernels against the by-value kernels for equal scalars, and a
+"""The fused optimiser step inside GraphedTrainStep's hipGraph (csrc/optim_step.hip with QT_OPTIM_SCALARS_DEV, utils/optim.py capture
+mode, utils/graphs.py).  Two oracles, both bit equality: the update with its scalars from device memory against the by-value form for equal scalars, and a
 replayed update against the eager fused update of a twin that starts from the same parameters, state and gradients (the gradient
 is taken out of the picture: captured and eager forwards may differ in torch's own kernels)."""
 import copy
@@ -114,7 +114,7 @@ def test_adam_dev_entry_stores_the_bits_of_the_by_value_entry(dev):
         if b[4][i] is not None:
             p64 = np.clip(p64, *b[4][i])             # clipping is 1-Lipschitz: the bound carries over
         worst = max(worst, X.worst(b[0][i], p64, bound))
-    print(f"qt_optim_adam_dev_f32: worst error / bound = {worst:.3f}")
+    print(f"qt_optim_adam_f32, scalars from the device: worst error / bound = {worst:.3f}")
     assert worst <= 1.0
 
 

@@ -1,5 +1,5 @@
-"""Gradient-norm clipping inside the fused update (csrc/optim_step.hip: the sum-of-squares pass, the finalise launch, the `_clip`
-update entries; utils/optim.py ``max_grad_norm``).  Oracles: exact values where fp32 is exact (all-ones gradients, power-of-two
+"""Gradient-norm clipping inside the fused update (csrc/optim_step.hip: the sum-of-squares pass, the finalise launch, the update
+entries with QT_OPTIM_GSCALE; utils/optim.py ``max_grad_norm``).  Oracles: exact values where fp32 is exact (all-ones gradients, power-of-two
 scales), the float64 restatement of tests/_clip_exact.py with its derived bounds elsewhere, and bit equality between forms that
 must agree (coef 1.0 against the unclipped optimiser, a captured replay against the eager clipped step).  The MLP, its batches and
 the state twin are those of tests/test_gpu_optim_capture.py."""
@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import _clip_exact as CX
+import _optim_abi as A
 import _optim_exact as X
 import test_gpu_optim_capture as C
 from pytorch_quantize_impls_amd import _lib, ops, utils
@@ -126,70 +127,90 @@ def _scaled(tab, s):
     return [g * s for g in tab[1]]
 
 
-@pytest.mark.parametrize("form", ["value", "dev", "guard"])
-@pytest.mark.parametrize("hp", [dict(), dict(momentum=0.9, weight_decay=1e-3, nesterov=True)], ids=["plain", "nesterov_wd"])
-def test_clipped_sgd_entry(dev, hp, form):
-    """Every walk of the update kernel (the 36-entry table of test_gpu_optim_capture.py: two chunks, planes, a dword view, empty
-    tensors).  gscale 1.0 stores the bits of the unclipped entry; gscale 0.25 those of the unclipped entry on 0.25 g (a product with
-    a power of two is exact, so this is an equality, not a bound)."""
-    mom = "momentum" in hp
-    lr = torch.tensor([0.05], device=dev)
-    skip = torch.zeros(1, dtype=torch.int32, device=dev)
+FORMS = ["value", "dev", "guard", "value_guard"]
 
-    def run(tab, grads, gscale):
-        kw = dict(clamps=tab[4], planes=tab[5], gscale=gscale, **hp)
-        if form == "value":
-            ops.optim_step_sgd(tab[0], grads, tab[2] if mom else None, lr=0.05, **kw)
-        else:
-            ops.optim_step_sgd_dev(tab[0], grads, tab[2] if mom else None, lr, skip=skip if form == "guard" else None, **kw)
 
-    before = _lib.call_counts["qt_optim_sgd_clip_f32"]
-    for scale in (1.0, 0.25):
-        a, b = C._tensor_table(dev, 100), C._tensor_table(dev, 100)
-        g0 = [g.clone() for g in b[1]]
-        run(a, _scaled(a, scale), None)
-        run(b, b[1], torch.tensor([scale], device=dev))
-        C._same(a[0], b[0]), C._same(a[2], b[2]), C._same_planes(a[5], b[5])
-        C._same(b[1], g0)                                                  # the gradients in memory are not rewritten
-        assert all(not bool((pl[0].words == -1).any()) for pl in b[5] if pl is not None)
-    assert _lib.call_counts["qt_optim_sgd_clip_f32"] == before + 2
-    if form == "guard":                                                    # a raised guard: nothing moves
+def _raised_guard_moves_nothing(dev, run, n_lists):
+    """A raised guard, with and without ``gscale``: parameters, state and gradients keep their bits and the planes their -1 fill."""
+    for gscale in (torch.tensor([0.25], device=dev), None):
         c = C._tensor_table(dev, 100)
-        snap = [[t.clone() for t in lst] for lst in c[:3]]
-        ops.optim_step_sgd_dev(c[0], c[1], c[2] if mom else None, lr, skip=torch.ones(1, dtype=torch.int32, device=dev),
-                               clamps=c[4], planes=c[5], gscale=torch.tensor([0.25], device=dev), **hp)
-        for k in range(3):
+        snap = [[t.clone() for t in lst] for lst in c[:n_lists]]
+        run(c, c[1], gscale, skip=torch.ones(1, dtype=torch.int32, device=dev))
+        for k in range(n_lists):
             C._same(c[k], snap[k])
         assert all(bool((pl[0].words == -1).all()) for pl in c[5] if pl is not None)
 
 
-@pytest.mark.parametrize("form", ["value", "dev", "guard"])
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("hp", [dict(), dict(momentum=0.9, weight_decay=1e-3, nesterov=True)], ids=["plain", "nesterov_wd"])
+def test_clipped_sgd_entry(dev, hp, form):
+    """Every walk of the update kernel (the 36-entry table of test_gpu_optim_capture.py: two chunks, planes, a dword view, empty
+    tensors).  gscale 1.0 stores the bits of the unclipped entry; gscale 0.25 those of the unclipped entry on 0.25 g (a product with
+    a power of two is exact, so this is an equality, not a bound).  The guarded forms ("guard": scalars from the device,
+    "value_guard": by value) with a clear guard store the bits of the unguarded by-value call, with and without gscale."""
+    mom = "momentum" in hp
+    lr = torch.tensor([0.05], device=dev)
+    clear = torch.zeros(1, dtype=torch.int32, device=dev) if "guard" in form else None
+
+    def run(tab, grads, gscale, skip=clear, form=form):
+        kw = dict(clamps=tab[4], planes=tab[5], gscale=gscale, skip=skip, **hp)
+        if form.startswith("value"):
+            ops.optim_step_sgd(tab[0], grads, tab[2] if mom else None, lr=0.05, **kw)
+        else:
+            ops.optim_step_sgd_dev(tab[0], grads, tab[2] if mom else None, lr, **kw)
+
+    with A.recorded_forms() as calls:
+        for scale in (1.0, 0.25):
+            a, b = C._tensor_table(dev, 100), C._tensor_table(dev, 100)
+            g0 = [g.clone() for g in b[1]]
+            run(a, _scaled(a, scale), None)
+            run(b, b[1], torch.tensor([scale], device=dev))
+            C._same(a[0], b[0]), C._same(a[2], b[2]), C._same_planes(a[5], b[5])
+            C._same(b[1], g0)                                              # the gradients in memory are not rewritten
+            assert all(not bool((pl[0].words == -1).any()) for pl in b[5] if pl is not None)
+            if "guard" in form:                                            # clear guard = the bits of the unguarded run
+                u = C._tensor_table(dev, 100)
+                run(u, _scaled(u, scale), None, skip=None, form="value")
+                C._same(u[0], a[0]), C._same(u[2], a[2]), C._same_planes(u[5], a[5])
+    # exactly the clipped runs carried QT_OPTIM_GSCALE, and every run the form it was asked for
+    want = A.FORMS[form]
+    unguarded = [("qt_optim_sgd_f32", 0)] if "guard" in form else []
+    assert calls == 2 * ([("qt_optim_sgd_f32", want), ("qt_optim_sgd_f32", want | A.GSCALE)] + unguarded)
+    if "guard" in form:
+        _raised_guard_moves_nothing(dev, run, 3)
+
+
+@pytest.mark.parametrize("form", FORMS)
 def test_clipped_adam_entry(dev, form):
     hp = dict(betas=(0.8, 0.95), eps=1e-6, weight_decay=1e-2)
     steps = list(range(1, C.N_TENSORS + 1))
     coef = torch.tensor(ops.adam_coefficients(steps, 3e-3, hp["betas"]), dtype=torch.float32, device=dev).reshape(-1)
-    skip = torch.zeros(1, dtype=torch.int32, device=dev)
+    clear = torch.zeros(1, dtype=torch.int32, device=dev) if "guard" in form else None
 
-    def run(tab, grads, gscale, skip=skip):
-        kw = dict(clamps=tab[4], planes=tab[5], gscale=gscale, **hp)
-        if form == "value":
+    def run(tab, grads, gscale, skip=clear, form=form):
+        kw = dict(clamps=tab[4], planes=tab[5], gscale=gscale, skip=skip, **hp)
+        if form.startswith("value"):
             ops.optim_step_adam(tab[0], grads, tab[2], tab[3], steps, lr=3e-3, **kw)
         else:
-            ops.optim_step_adam_dev(tab[0], grads, tab[2], tab[3], coef, skip=skip if form == "guard" else None, **kw)
+            ops.optim_step_adam_dev(tab[0], grads, tab[2], tab[3], coef, **kw)
 
-    for scale in (1.0, 0.25):
-        a, b = C._tensor_table(dev, 200), C._tensor_table(dev, 200)
-        g0 = [g.clone() for g in b[1]]
-        run(a, _scaled(a, scale), None)
-        run(b, b[1], torch.tensor([scale], device=dev))
-        C._same(a[0], b[0]), C._same(a[2], b[2]), C._same(a[3], b[3]), C._same_planes(a[5], b[5])
-        C._same(b[1], g0)
-    if form == "guard":
-        c = C._tensor_table(dev, 200)
-        snap = [[t.clone() for t in lst] for lst in c[:4]]
-        run(c, c[1], torch.tensor([0.25], device=dev), skip=torch.ones(1, dtype=torch.int32, device=dev))
-        for k in range(4):
-            C._same(c[k], snap[k])
+    with A.recorded_forms() as calls:
+        for scale in (1.0, 0.25):
+            a, b = C._tensor_table(dev, 200), C._tensor_table(dev, 200)
+            g0 = [g.clone() for g in b[1]]
+            run(a, _scaled(a, scale), None)
+            run(b, b[1], torch.tensor([scale], device=dev))
+            C._same(a[0], b[0]), C._same(a[2], b[2]), C._same(a[3], b[3]), C._same_planes(a[5], b[5])
+            C._same(b[1], g0)
+            if "guard" in form:                                            # clear guard = the bits of the unguarded run
+                u = C._tensor_table(dev, 200)
+                run(u, _scaled(u, scale), None, skip=None, form="value")
+                C._same(u[0], a[0]), C._same(u[2], a[2]), C._same(u[3], a[3]), C._same_planes(u[5], a[5])
+    want = A.FORMS[form]
+    unguarded = [("qt_optim_adam_f32", 0)] if "guard" in form else []
+    assert calls == 2 * ([("qt_optim_adam_f32", want), ("qt_optim_adam_f32", want | A.GSCALE)] + unguarded)
+    if "guard" in form:
+        _raised_guard_moves_nothing(dev, run, 4)
 
 
 def test_abi_errors_enqueue_nothing(dev):
@@ -202,16 +223,20 @@ def test_abi_errors_enqueue_nothing(dev):
     t, scal = ctypes.addressof(tab), torch.full((4,), 0.5, device=dev)
     work = torch.full((4,), -7.0, device=dev)
     s = ops._stream(dev)
-    assert lib.qt_optim_sgd_clip_f32(t, 1, 0.1, None, None, None, 0.9, 0.0, 0, s) == INVALID
-    assert lib.qt_optim_sgd_clip_f32(t, 1, 0.1, None, scal.data_ptr() + 2, None, 0.9, 0.0, 0, s) == ALIGNMENT
-    assert lib.qt_optim_sgd_clip_f32(t, 1, 0.1, scal.data_ptr(), None, None, 0.0, 0.0, 0, s) == INVALID
-    assert lib.qt_optim_adam_clip_f32(t, 1, None, None, None, 0.9, 0.1, 0.999, 0.001, 1e-8, 0.0, s) == INVALID
-    assert lib.qt_optim_adam_clip_f32(t, 1, scal.data_ptr(), scal.data_ptr() + 2, None, 0.9, 0.1, 0.999, 0.001, 1e-8, 0.0, s) == ALIGNMENT
+    assert lib.qt_optim_sgd_f32(t, 1, A.GSCALE, 0.1, None, None, None, 0.9, 0.0, 0, s) == INVALID
+    assert lib.qt_optim_sgd_f32(t, 1, A.GSCALE, 0.1, None, scal.data_ptr() + 2, None, 0.9, 0.0, 0, s) == ALIGNMENT
+    assert lib.qt_optim_sgd_f32(t, 1, A.SCALARS_DEV | A.GSCALE, 0.1, scal.data_ptr(), None, None, 0.0, 0.0, 0, s) == INVALID
+    assert lib.qt_optim_adam_f32(t, 1, A.GSCALE, None, None, None, 0.9, 0.1, 0.999, 0.001, 1e-8, 0.0, s) == INVALID
+    assert lib.qt_optim_adam_f32(t, 1, A.SCALARS_DEV | A.GSCALE, scal.data_ptr(), scal.data_ptr() + 2, None, 0.9, 0.1, 0.999, 0.001, 1e-8,
+                                 0.0, s) == ALIGNMENT
+    # a valid pointer whose bit is clear, and a form with an unknown bit: refused, not read
+    assert lib.qt_optim_sgd_f32(t, 1, 0, 0.1, None, scal.data_ptr(), None, 0.9, 0.0, 0, s) == INVALID
+    assert lib.qt_optim_adam_f32(t, 1, A.GSCALE | 0x8, None, scal.data_ptr(), None, 0.9, 0.1, 0.999, 0.001, 1e-8, 0.0, s) == INVALID
     assert lib.qt_optim_grad_sumsq_f32(t, 1, None, s) == INVALID
     assert lib.qt_optim_grad_sumsq_f32(t, 1, work.data_ptr() + 2, s) == ALIGNMENT
     assert lib.qt_optim_grad_norm_finalize_f32(None, 2, 1.0, None, scal.data_ptr(), s) == INVALID
     assert lib.qt_optim_grad_norm_finalize_f32(work.data_ptr() + 2, 2, 1.0, None, scal.data_ptr(), s) == ALIGNMENT
-    assert lib.qt_optim_sgd_clip_f32(None, 0, 0.1, None, None, None, 0.0, 0.0, 0, s) == 0                 # n == 0
+    assert lib.qt_optim_sgd_f32(None, 0, A.GSCALE, 0.1, None, None, None, 0.0, 0.0, 0, s) == 0            # n == 0
     torch.cuda.synchronize()
     for a, b in zip((p, g, m, v), keep):
         assert torch.equal(a, b)
@@ -276,13 +301,15 @@ def test_clipped_step_against_float64(dev, kind):
     opt = _two_groups(model, utils.FusedQuantSGD if kind == "sgd" else utils.FusedQuantAdam, max_grad_norm=1.5, **hp)
     plan = utils.clamp_plan(model)
     assert plan[model.lin.weight] == (-1.0, 1.0)
-    counts = {k: _lib.call_counts[k] for k in ("qt_optim_grad_sumsq_f32", "qt_optim_grad_norm_finalize_f32",
-                                               f"qt_optim_{kind}_clip_f32", f"qt_optim_{kind}_f32")}
+    counts = {k: _lib.call_counts[k] for k in ("qt_optim_grad_sumsq_f32", "qt_optim_grad_norm_finalize_f32")}
     worst = worst_norm = 0.0
+    updates = []
     for step in (1, 2, 3):
         model.set_grads(70 + step)
         snap = _snapshot(model, opt)
-        opt.step()
+        with A.recorded_forms() as calls:
+            opt.step()
+        updates += calls
         norm, coef = opt.grad_norm.cpu().numpy(), opt.clip_coef.cpu().numpy()
         assert opt.grad_norm.dim() == 0 and opt.grad_norm.dtype == torch.float32 and opt.grad_norm.is_cuda
         norm64 = CX.total_norm([s[1] for s in snap])
@@ -314,8 +341,7 @@ def test_clipped_step_against_float64(dev, kind):
     # ONE norm sequence per step over both groups (10 tensors: one chunk), then each group's launches; no unclipped entry
     assert _lib.call_counts["qt_optim_grad_sumsq_f32"] == counts["qt_optim_grad_sumsq_f32"] + 3
     assert _lib.call_counts["qt_optim_grad_norm_finalize_f32"] == counts["qt_optim_grad_norm_finalize_f32"] + 3
-    assert _lib.call_counts[f"qt_optim_{kind}_clip_f32"] == counts[f"qt_optim_{kind}_clip_f32"] + 6
-    assert _lib.call_counts[f"qt_optim_{kind}_f32"] == counts[f"qt_optim_{kind}_f32"]
+    assert updates == 6 * [(f"qt_optim_{kind}_f32", A.GSCALE)]
 
 
 def _assert_models_equal(a, oa, b, ob, versions=True):
@@ -365,14 +391,15 @@ def test_off_route_parameters_send_the_whole_step_to_torch(dev):
     ob = utils.FusedQuantSGD(pb, lr=0.1, momentum=0.9)
     raw = [p.grad.clone() for p in pa]
     before = dict(_fused.LIBRARY_PATHS)
-    clip_calls = _lib.call_counts["qt_optim_sgd_clip_f32"], _lib.call_counts["qt_optim_grad_sumsq_f32"]
-    oa.step()
+    sumsq_calls = _lib.call_counts["qt_optim_grad_sumsq_f32"]
+    with A.recorded_forms() as calls:
+        oa.step()
     norm = torch.nn.utils.clip_grad_norm_(pb, 0.5)
     ob.step()
     grew = {k: v - before.get(k, 0) for k, v in _fused.LIBRARY_PATHS.items() if v != before.get(k, 0)}
     clip_keys = [k for k in grew if "clip_grad_norm_" in k]
     assert len(clip_keys) == 1 and grew[clip_keys[0]] == 1                 # counted once, not per parameter
-    assert (_lib.call_counts["qt_optim_sgd_clip_f32"], _lib.call_counts["qt_optim_grad_sumsq_f32"]) == clip_calls
+    assert not any(form & A.GSCALE for _, form in calls) and _lib.call_counts["qt_optim_grad_sumsq_f32"] == sumsq_calls
     assert torch.equal(oa.grad_norm, norm) and float(oa.clip_coef) < 1
     for p, q, g in zip(pa, pb, raw):
         assert torch.equal(p, q) and torch.equal(p.grad, q.grad) and not torch.equal(p.grad, g)

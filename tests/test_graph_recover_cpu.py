@@ -1,6 +1,6 @@
-"""Host side of ``GraphedTrainStep(recover=True)``: the status codes of qt_flags_or_i32 and of the guarded training-update entries
-(nothing that passes validation here has anything to launch), the thread-local collector of trusted verdict flags
-(``_fused.flag_sink``) and what stays refused.  No GPU needed."""
+"""Host side of ``GraphedTrainStep(recover=True)``: the status codes of qt_flags_or_i32 (nothing that passes validation here has
+anything to launch), the thread-local collector of trusted verdict flags (``_fused.flag_sink``) and what stays refused.  The
+statuses of the guarded training update (QT_OPTIM_SKIP) are in tests/test_optim_abi.py.  No GPU needed."""
 import ctypes
 import threading
 
@@ -12,7 +12,6 @@ from pytorch_quantize_impls_amd.functions import _fused
 from pytorch_quantize_impls_amd.functions.common import QtFunction
 
 INVALID, ALIGNMENT = -1, -2
-SCALARS, SKIP = 0x6000, 0x7000            # never dereferenced on the host
 
 
 @pytest.fixture(scope="module")
@@ -23,58 +22,14 @@ def lib():
     return _lib.load()
 
 
-def _sgd(lib, tab, n, momentum=0.0, nesterov=0, lr=SCALARS, skip=SKIP):
-    ptr = ctypes.addressof(tab) if tab is not None else None
-    return lib.qt_optim_sgd_dev_guard_f32(ptr, n, lr, skip, momentum, 0.0, nesterov, None)
-
-
-def _adam(lib, tab, n, coef=SCALARS, skip=SKIP):
-    ptr = ctypes.addressof(tab) if tab is not None else None
-    return lib.qt_optim_adam_dev_guard_f32(ptr, n, coef, skip, 0.9, 0.1, 0.999, 0.001, 1e-8, 0.0, None)
-
-
-def _table(**fields):
-    tab = (ops._OptimTensor * 1)()
-    e = tab[0]
-    e.p, e.g, e.s0, e.s1, e.numel = 0x1000, 0x2000, 0x3000, 0x4000, 64
-    e.lo, e.hi = float("-inf"), float("inf")
-    for k, v in fields.items():
-        setattr(e, k, v)
-    return tab
-
-
 def test_entries_are_declared_and_bound(lib):
     declared = _lib.header_declared_functions()
-    for name in ("qt_optim_sgd_dev_guard_f32", "qt_optim_adam_dev_guard_f32", "qt_flags_or_i32", "qt_flags_chunk_capacity"):
+    for name in ("qt_optim_sgd_f32", "qt_optim_adam_f32", "qt_flags_or_i32", "qt_flags_chunk_capacity"):
         assert name in declared and name in _lib.SIGNATURES
         assert getattr(lib, name).argtypes == _lib.SIGNATURES[name][1]
-    assert ctypes.sizeof(ops._OptimTensor) == 96            # the guarded entries take the descriptor as it is
+    assert ctypes.sizeof(ops._OptimTensor) == 96            # the guarded form takes the descriptor as it is
     # 8 bytes per pointer, the guard pointer and the count next to them: inside HIP's 4096-byte argument block
     assert 1 <= ops.flags_chunk_capacity() and 8 * ops.flags_chunk_capacity() + 16 <= 4096
-
-
-def test_guarded_entries_validate_the_skip_pointer(lib):
-    assert _sgd(lib, None, 0, lr=None, skip=None) == 0 and _adam(lib, None, 0, coef=None, skip=None) == 0      # nothing to do
-    assert _sgd(lib, None, 0, skip=0x7002) == 0 and _adam(lib, None, 0, skip=0x7002) == 0
-    assert _sgd(lib, _table(), 1, skip=None) == INVALID and _adam(lib, _table(), 1, skip=None) == INVALID
-    assert _sgd(lib, _table(), 1, skip=0x7002) == ALIGNMENT and _adam(lib, _table(), 1, skip=0x7002) == ALIGNMENT
-    assert _sgd(lib, _table(), -1) == INVALID and _adam(lib, _table(), -1) == INVALID
-    assert _sgd(lib, None, 3) == INVALID and _adam(lib, None, 3) == INVALID                                # null table with n > 0
-    assert _sgd(lib, _table(numel=0, p=None, g=None), 1) == 0 and _adam(lib, _table(numel=0, p=None, g=None), 1) == 0
-
-
-def test_guarded_entries_keep_the_statuses_of_the_dev_entries(lib):
-    assert _sgd(lib, _table(), 1, lr=None) == INVALID and _adam(lib, _table(), 1, coef=None) == INVALID
-    assert _sgd(lib, _table(), 1, lr=0x1002) == ALIGNMENT and _adam(lib, _table(), 1, coef=0x1002) == ALIGNMENT
-    assert _sgd(lib, _table(numel=-4), 1) == INVALID
-    assert _sgd(lib, _table(p=None), 1) == INVALID and _sgd(lib, _table(g=None), 1) == INVALID
-    assert _sgd(lib, _table(s0=None), 1, momentum=0.9) == INVALID
-    assert _adam(lib, _table(s0=None), 1) == INVALID and _adam(lib, _table(s1=None), 1) == INVALID
-    assert _sgd(lib, _table(p=0x1002), 1) == ALIGNMENT
-    assert _sgd(lib, _table(), 1, momentum=0.0, nesterov=1) == INVALID
-    ok = dict(kind=1, words=0x5000, rows=2, K=32, ld=4)
-    assert _sgd(lib, _table(**{**ok, "ld": 3}), 1) == ALIGNMENT and _adam(lib, _table(**{**ok, "words": 0x5004}), 1) == ALIGNMENT
-    assert _sgd(lib, _table(**{**ok, "rows": 3}), 1) == INVALID
 
 
 def test_flags_or_status_codes(lib):

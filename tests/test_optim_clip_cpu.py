@@ -1,7 +1,7 @@
 """Gradient-norm clipping of FusedQuantSGD / FusedQuantAdam without a GPU: the bounds of tests/_clip_exact.py pinned against
 torch's own fp32 ``clip_grad_norm_`` + optimiser, argument validation, the library path on host tensors (bit equality with torch),
-the unchanged ``state_dict()`` / ``param_groups``, and the new C entries' declarations and statuses (nothing that passes validation
-here has anything to enqueue)."""
+the unchanged ``state_dict()`` / ``param_groups``, and the norm entries' declarations and statuses (nothing that passes validation
+here has anything to enqueue; the clipped update's own statuses, QT_OPTIM_GSCALE, are in tests/test_optim_abi.py)."""
 import ctypes
 
 import numpy as np
@@ -10,13 +10,13 @@ import torch
 
 import _clip_exact as CX
 import _optim_exact as X
+from _optim_abi import table as _table
 from pytorch_quantize_impls_amd import _lib, ops, utils
 from pytorch_quantize_impls_amd.functions import _fused
 
 INVALID, ALIGNMENT = -1, -2
 DEVPTR = 0x6000             # never dereferenced on the host
-NEW_ENTRIES = ("qt_optim_grad_norm_work_floats", "qt_optim_grad_sumsq_f32", "qt_optim_grad_norm_finalize_f32",
-               "qt_optim_sgd_clip_f32", "qt_optim_adam_clip_f32")
+NEW_ENTRIES = ("qt_optim_grad_norm_work_floats", "qt_optim_grad_sumsq_f32", "qt_optim_grad_norm_finalize_f32")
 
 SIZES = [4099, 1, 517, 8192]          # the gradients of one clipped step: the norm is global over all of them
 MAX_NORM = 10.0                       # far below the norm of X.inputs gradients (entries up to 100): the clip acts
@@ -211,16 +211,6 @@ def lib():
     return _lib.load()
 
 
-def _table(n=1, **fields):
-    tab = (ops._OptimTensor * n)()
-    for e in tab:
-        e.p, e.g, e.s0, e.s1, e.numel = 0x1000, 0x2000, 0x3000, 0x4000, 64
-        e.lo, e.hi = float("-inf"), float("inf")
-        for k, v in fields.items():
-            setattr(e, k, v)
-    return tab
-
-
 def test_entries_are_declared_bound_and_exported(lib):
     declared = _lib.header_declared_functions()
     for name in NEW_ENTRIES:
@@ -259,38 +249,6 @@ def test_sumsq_and_finalise_statuses(lib):
     assert fin(None, 4, 1.0, None, DEVPTR, None) == INVALID and fin(DEVPTR, 4, 1.0, None, None, None) == INVALID
     assert fin(DEVPTR + 2, 4, 1.0, None, DEVPTR, None) == ALIGNMENT and fin(DEVPTR, 4, 1.0, None, DEVPTR + 1, None) == ALIGNMENT
     assert fin(DEVPTR, 4, 1.0, DEVPTR + 2, DEVPTR, None) == ALIGNMENT
-
-
-def _sgd_clip(lib, tab, n, lr_dev=None, gscale=DEVPTR, skip=None, momentum=0.0, nesterov=0):
-    return lib.qt_optim_sgd_clip_f32(ctypes.addressof(tab) if tab is not None else None, n, 0.1, lr_dev, gscale, skip, momentum, 0.0,
-                                     nesterov, None)
-
-
-def _adam_clip(lib, tab, n, coef=None, gscale=DEVPTR, skip=None):
-    return lib.qt_optim_adam_clip_f32(ctypes.addressof(tab) if tab is not None else None, n, coef, gscale, skip, 0.9, 0.1, 0.999,
-                                      0.001, 1e-8, 0.0, None)
-
-
-@pytest.mark.parametrize("entry", [_sgd_clip, _adam_clip], ids=["sgd", "adam"])
-def test_clipped_update_statuses(lib, entry):
-    scalars = "lr_dev" if entry is _sgd_clip else "coef"
-    assert entry(lib, None, 0, gscale=None) == 0 and entry(lib, None, 0, gscale=0x1002) == 0       # n == 0: whatever they are
-    assert entry(lib, _table(), 1, gscale=None) == INVALID
-    assert entry(lib, _table(), 1, gscale=DEVPTR + 2) == ALIGNMENT
-    assert entry(lib, _table(), 1, skip=DEVPTR + 2) == ALIGNMENT
-    assert entry(lib, _table(), 1, **{scalars: DEVPTR + 2}) == ALIGNMENT
-    assert entry(lib, _table(), -1) == INVALID and entry(lib, None, 3) == INVALID
-    # the table is validated as by the unclipped entries
-    assert entry(lib, _table(numel=0, p=None, g=None), 1) == 0                                     # an empty tensor is skipped
-    assert entry(lib, _table(p=None), 1) == INVALID and entry(lib, _table(g=None), 1) == INVALID
-    assert entry(lib, _table(p=0x1002), 1) == ALIGNMENT and entry(lib, _table(kind=3), 1) == INVALID
-    assert entry(lib, _table(numel=0, p=None, g=None), 1, skip=DEVPTR, **{scalars: DEVPTR}) == 0
-
-
-def test_clipped_sgd_keeps_the_momentum_rules(lib):
-    assert _sgd_clip(lib, _table(), 1, nesterov=1) == INVALID
-    assert _sgd_clip(lib, _table(s0=None), 1, momentum=0.9) == INVALID
-    assert _adam_clip(lib, _table(s1=None), 1) == INVALID
 
 
 def test_wrappers_reject_host_tensors_and_ambiguous_max_norm():

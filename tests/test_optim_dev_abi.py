@@ -1,7 +1,6 @@
-"""Argument validation of the training-update entries that read their per-step scalars from device memory
-(qt_optim_sgd_dev_f32 / qt_optim_adam_dev_f32): every status of tests/test_optim_abi.py through the new entries, the scalar
-pointers' own checks, and the bias-correction helper both forms of the Adam update share (no GPU needed: nothing that passes
-validation here has a tensor to update)."""
+"""What feeds a training update that reads its per-step scalars from device memory (QT_OPTIM_SCALARS_DEV): the statuses of the
+scalar writer, the wrappers' refusal of host tensors, and the bias-correction helper both forms of the Adam update share.  The
+statuses of the update entries themselves, in every form, are in tests/test_optim_abi.py.  No GPU needed."""
 import ctypes
 import math
 
@@ -11,9 +10,6 @@ import torch
 from pytorch_quantize_impls_amd import _lib, ops
 
 INVALID, ALIGNMENT = -1, -2
-SCALARS = 0x6000            # never dereferenced on the host
-
-
 @pytest.fixture(scope="module")
 def lib():
     if not _lib.is_built():
@@ -22,42 +18,12 @@ def lib():
     return _lib.load()
 
 
-def _sgd(lib, tab, n, momentum=0.0, nesterov=0, lr=SCALARS):
-    ptr = ctypes.addressof(tab) if tab is not None else None
-    return lib.qt_optim_sgd_dev_f32(ptr, n, lr, momentum, 0.0, nesterov, None)
-
-
-def _adam(lib, tab, n, coef=SCALARS):
-    ptr = ctypes.addressof(tab) if tab is not None else None
-    return lib.qt_optim_adam_dev_f32(ptr, n, coef, 0.9, 0.1, 0.999, 0.001, 1e-8, 0.0, None)
-
-
-def _table(**fields):
-    tab = (ops._OptimTensor * 1)()
-    e = tab[0]
-    e.p, e.g, e.s0, e.s1, e.numel = 0x1000, 0x2000, 0x3000, 0x4000, 64
-    e.lo, e.hi = float("-inf"), float("inf")
-    for k, v in fields.items():
-        setattr(e, k, v)
-    return tab
-
-
 def test_entries_are_declared_and_bound(lib):
     declared = _lib.header_declared_functions()
-    for name in ("qt_optim_sgd_dev_f32", "qt_optim_adam_dev_f32", "qt_optim_scalars_f32"):
+    for name in ("qt_optim_sgd_f32", "qt_optim_adam_f32", "qt_optim_scalars_f32"):
         assert name in declared and name in _lib.SIGNATURES
         assert getattr(lib, name).argtypes == _lib.SIGNATURES[name][1]
-    assert ctypes.sizeof(ops._OptimTensor) == 96            # the descriptor is the by-value entries'
-
-
-def test_scalar_pointers(lib):
-    assert _sgd(lib, None, 0, lr=None) == 0 and _adam(lib, None, 0, coef=None) == 0           # nothing to do
-    assert _sgd(lib, None, 0, lr=0x1002) == 0 and _adam(lib, None, 0, coef=0x1002) == 0
-    assert _sgd(lib, _table(), 1, lr=None) == INVALID and _adam(lib, _table(), 1, coef=None) == INVALID
-    assert _sgd(lib, _table(), 1, lr=0x1002) == ALIGNMENT and _adam(lib, _table(), 1, coef=0x1002) == ALIGNMENT
-    assert _sgd(lib, _table(), -1, lr=0x1002) == INVALID and _adam(lib, _table(), -1, coef=0x1002) == INVALID    # the table's status first
-    assert _sgd(lib, _table(), -1, lr=None) == INVALID and _adam(lib, _table(), -1, coef=None) == INVALID
-    assert _sgd(lib, _table(numel=0, p=None, g=None), 1) == 0 and _adam(lib, _table(numel=0, p=None, g=None), 1) == 0
+    assert ctypes.sizeof(ops._OptimTensor) == 96            # one descriptor for every form
 
 
 def test_scalar_writer(lib):
@@ -69,30 +35,6 @@ def test_scalar_writer(lib):
     assert lib.qt_optim_scalars_f32(0x1002, host, 4, None) == ALIGNMENT
     with pytest.raises(TypeError):
         ops.optim_write_scalars(torch.zeros(4), [1.0])                                           # a host destination
-
-
-def test_tables(lib):
-    assert _sgd(lib, None, 3) == INVALID and _adam(lib, None, 3) == INVALID     # null table with n > 0
-    assert _sgd(lib, _table(), -1) == INVALID and _adam(lib, _table(), -1) == INVALID
-    assert _sgd(lib, _table(numel=0, p=None, g=None), 1) == 0                   # an empty tensor is skipped
-    assert _sgd(lib, _table(numel=-4), 1) == INVALID
-    assert _sgd(lib, _table(p=None), 1) == INVALID and _sgd(lib, _table(g=None), 1) == INVALID
-    assert _sgd(lib, _table(s0=None), 1, momentum=0.9) == INVALID               # momentum needs its buffer
-    assert _adam(lib, _table(s0=None), 1) == INVALID and _adam(lib, _table(s1=None), 1) == INVALID
-    assert _sgd(lib, _table(p=0x1002), 1) == ALIGNMENT                          # not even element-aligned
-    assert _sgd(lib, _table(), 1, momentum=0.0, nesterov=1) == INVALID
-
-
-def test_planes(lib):
-    ok = dict(kind=1, words=0x5000, rows=2, K=32, ld=4)
-    assert _sgd(lib, _table(kind=3), 1) == INVALID and _sgd(lib, _table(kind=-1), 1) == INVALID
-    assert _sgd(lib, _table(**{**ok, "ld": 3}), 1) == ALIGNMENT                 # ld < ceil(K / 8)
-    assert _sgd(lib, _table(**{**ok, "ld": 6}), 1) == ALIGNMENT                 # ld % 4 != 0
-    assert _sgd(lib, _table(**{**ok, "words": 0x5004}), 1) == ALIGNMENT
-    assert _sgd(lib, _table(**{**ok, "words": None}), 1) == INVALID
-    assert _sgd(lib, _table(**{**ok, "rows": 3}), 1) == INVALID                 # rows * K != numel
-    assert _sgd(lib, _table(**{**ok, "rows": -2, "K": -32}), 1) == INVALID
-    assert _adam(lib, _table(**{**ok, "kind": 2, "ld": 2}), 1) == ALIGNMENT
 
 
 def test_wrappers_reject_host_tensors():

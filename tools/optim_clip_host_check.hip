@@ -1,5 +1,5 @@
 // Stand-alone host check of the gradient-clipping entries of csrc/optim_step.hip: the chunking of the sum-of-squares pass, its
-// workspace offsets, and the argument validation of the five new entries.  Nothing here launches a kernel or touches device
+// workspace offsets, and the argument validation of the norm entries and of the two update entries in every form.  Nothing here launches a kernel or touches device
 // memory (every pointer is a made-up address that is only compared and offset), so it runs without a GPU and is meant to be built
 // with the host sanitizers:
 //
@@ -102,6 +102,8 @@ int main() {
     std::vector<qt_optim_tensor> tab(40, tensor(5000, 0x50000000));
     float* const dev = fake(0x6000);
     const int32_t* const skip = reinterpret_cast<const int32_t*>(0x7000);
+    const int32_t* const skip2 = reinterpret_cast<const int32_t*>(0x7002);       // not 4-byte aligned
+    const int DEV = QT_OPTIM_SCALARS_DEV, GS = QT_OPTIM_GSCALE, SK = QT_OPTIM_SKIP;
     CHECK(qt_optim_grad_norm_work_floats(nullptr, 0) == 0 && qt_optim_grad_norm_work_floats(nullptr, 1) == QT_ERR_INVALID_ARG);
     CHECK(qt_optim_grad_norm_work_floats(tab.data(), -1) == QT_ERR_INVALID_ARG);
     CHECK(qt_optim_grad_sumsq_f32(nullptr, 0, nullptr, nullptr) == QT_OK);
@@ -110,23 +112,51 @@ int main() {
     CHECK(qt_optim_grad_sumsq_f32(tab.data(), 40, fake(0x6002), nullptr) == QT_ERR_ALIGNMENT);
     tab[39].g = fake(0x50100002);                                              // the LAST entry is bad: still nothing is enqueued
     CHECK(qt_optim_grad_sumsq_f32(tab.data(), 40, dev, nullptr) == QT_ERR_ALIGNMENT);
-    CHECK(qt_optim_sgd_clip_f32(tab.data(), 40, 0.1f, nullptr, dev, nullptr, 0.9f, 0.0f, 0, nullptr) == QT_ERR_ALIGNMENT);
-    CHECK(qt_optim_adam_clip_f32(tab.data(), 40, dev, dev, skip, 0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, 0.0f, nullptr) == QT_ERR_ALIGNMENT);
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, GS, 0.1f, nullptr, dev, nullptr, 0.9f, 0.0f, 0, nullptr) == QT_ERR_ALIGNMENT);
+    CHECK(qt_optim_adam_f32(tab.data(), 40, DEV | GS | SK, dev, dev, skip, 0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, 0.0f, nullptr) == QT_ERR_ALIGNMENT);
     tab[39].g = nullptr;
     CHECK(qt_optim_grad_sumsq_f32(tab.data(), 40, dev, nullptr) == QT_ERR_INVALID_ARG);
-    CHECK(qt_optim_sgd_clip_f32(tab.data(), 40, 0.1f, dev, dev, skip, 0.0f, 0.0f, 0, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, DEV | GS | SK, 0.1f, dev, dev, skip, 0.0f, 0.0f, 0, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, 0, 0.1f, nullptr, nullptr, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_adam_f32(tab.data(), 40, SK, nullptr, nullptr, skip, 0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, 0.0f, nullptr) == QT_ERR_INVALID_ARG);
     tab[39] = tensor(5000, 0x50000000);
-    CHECK(qt_optim_sgd_clip_f32(tab.data(), 40, 0.1f, nullptr, nullptr, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_INVALID_ARG);
-    CHECK(qt_optim_sgd_clip_f32(tab.data(), 40, 0.1f, nullptr, fake(0x6002), nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_ALIGNMENT);
-    CHECK(qt_optim_sgd_clip_f32(tab.data(), 40, 0.1f, fake(0x6002), dev, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_ALIGNMENT);
-    CHECK(qt_optim_sgd_clip_f32(tab.data(), 40, 0.1f, nullptr, dev, reinterpret_cast<const int32_t*>(0x7002), 0.0f, 0.0f, 0, nullptr) ==
-          QT_ERR_ALIGNMENT);
-    CHECK(qt_optim_sgd_clip_f32(tab.data(), 40, 0.1f, nullptr, dev, nullptr, 0.0f, 0.0f, 1, nullptr) == QT_ERR_INVALID_ARG);
-    CHECK(qt_optim_sgd_clip_f32(tab.data(), -1, 0.1f, nullptr, dev, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_INVALID_ARG);
-    CHECK(qt_optim_sgd_clip_f32(nullptr, 0, 0.1f, nullptr, nullptr, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_OK);
-    CHECK(qt_optim_adam_clip_f32(tab.data(), 40, nullptr, nullptr, nullptr, 0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, 0.0f, nullptr) == QT_ERR_INVALID_ARG);
-    CHECK(qt_optim_adam_clip_f32(tab.data(), 40, fake(0x6002), dev, nullptr, 0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, 0.0f, nullptr) == QT_ERR_ALIGNMENT);
-    CHECK(qt_optim_adam_clip_f32(nullptr, 0, nullptr, nullptr, nullptr, 0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, 0.0f, nullptr) == QT_OK);
+    // a flagged pointer that is null, then one that is not 4-byte aligned
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, GS, 0.1f, nullptr, nullptr, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, GS, 0.1f, nullptr, fake(0x6002), nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_ALIGNMENT);
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, DEV | GS, 0.1f, fake(0x6002), dev, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_ALIGNMENT);
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, GS | SK, 0.1f, nullptr, dev, skip2, 0.0f, 0.0f, 0, nullptr) == QT_ERR_ALIGNMENT);
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, DEV, 0.1f, nullptr, nullptr, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, DEV | SK, 0.1f, dev, nullptr, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, GS, 0.1f, nullptr, dev, nullptr, 0.0f, 0.0f, 1, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_sgd_f32(tab.data(), -1, GS, 0.1f, nullptr, dev, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_sgd_f32(nullptr, 0, GS, 0.1f, nullptr, nullptr, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_OK);
+    CHECK(qt_optim_adam_f32(tab.data(), 40, GS, nullptr, nullptr, nullptr, 0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, 0.0f, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_adam_f32(tab.data(), 40, DEV | GS, fake(0x6002), dev, nullptr, 0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, 0.0f, nullptr) == QT_ERR_ALIGNMENT);
+    CHECK(qt_optim_adam_f32(nullptr, 0, GS, nullptr, nullptr, nullptr, 0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, 0.0f, nullptr) == QT_OK);
+    // a pointer whose bit is clear must be null, aligned or not: nothing becomes legal by being left over from another form
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, 0, 0.1f, dev, nullptr, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, 0, 0.1f, nullptr, dev, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, 0, 0.1f, nullptr, nullptr, skip, 0.0f, 0.0f, 0, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_adam_f32(tab.data(), 40, GS | SK, dev, dev, skip, 0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, 0.0f, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_adam_f32(tab.data(), 40, DEV | SK, dev, fake(0x6002), skip, 0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, 0.0f, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_adam_f32(tab.data(), 40, DEV | GS, dev, dev, skip2, 0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, 0.0f, nullptr) == QT_ERR_INVALID_ARG);
+    // bits outside the mask: refused even where there is nothing to do
+    CHECK(qt_optim_sgd_f32(nullptr, 0, 0x8, 0.1f, nullptr, nullptr, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_adam_f32(nullptr, 0, GS | 0x10, nullptr, dev, nullptr, 0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, 0.0f, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_adam_f32(tab.data(), 40, -1, dev, dev, skip, 0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, 0.0f, nullptr) == QT_ERR_INVALID_ARG);
+    // the order: nesterov before n == 0; n < 0 before the pointers; scalars before gscale before skip; all before the table
+    CHECK(qt_optim_sgd_f32(nullptr, 0, 0, 0.1f, nullptr, nullptr, nullptr, 0.0f, 0.0f, 1, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_sgd_f32(tab.data(), -1, DEV, 0.1f, fake(0x6002), nullptr, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, DEV | GS, 0.1f, fake(0x6002), nullptr, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_ALIGNMENT);
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, DEV | GS, 0.1f, nullptr, fake(0x6002), nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_adam_f32(tab.data(), 40, GS | SK, nullptr, fake(0x6002), nullptr, 0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, 0.0f, nullptr) == QT_ERR_ALIGNMENT);
+    CHECK(qt_optim_adam_f32(tab.data(), 40, GS | SK, nullptr, nullptr, skip2, 0.9f, 0.1f, 0.999f, 0.001f, 1e-8f, 0.0f, nullptr) == QT_ERR_INVALID_ARG);
+    tab[0].p = nullptr;                                                        // INVALID_ARG from the table ...
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, SK, 0.1f, nullptr, nullptr, skip2, 0.0f, 0.0f, 0, nullptr) == QT_ERR_ALIGNMENT);
+    tab[0].p = fake(0x50000002);                                               // ... and ALIGNMENT
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, SK, 0.1f, nullptr, nullptr, nullptr, 0.0f, 0.0f, 0, nullptr) == QT_ERR_INVALID_ARG);
+    CHECK(qt_optim_sgd_f32(tab.data(), 40, SK, 0.1f, nullptr, nullptr, skip, 0.0f, 0.0f, 0, nullptr) == QT_ERR_ALIGNMENT);
+    tab[0] = tensor(5000, 0x50000000);
     CHECK(qt_optim_grad_norm_finalize_f32(dev, -1, 1.0f, nullptr, dev, nullptr) == QT_ERR_INVALID_ARG);
     CHECK(qt_optim_grad_norm_finalize_f32(nullptr, 3, 1.0f, nullptr, dev, nullptr) == QT_ERR_INVALID_ARG);
     CHECK(qt_optim_grad_norm_finalize_f32(dev, 3, 1.0f, nullptr, nullptr, nullptr) == QT_ERR_INVALID_ARG);
