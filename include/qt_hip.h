@@ -1243,6 +1243,73 @@ int qt_optim_grad_norm_finalize_f32(const float* work, int64_t m, float max_norm
 int qt_flags_chunk_capacity(void);
 int qt_flags_or_i32(const int32_t* const* flags, int64_t n, int32_t* guard, qt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Depthwise convolution: F.conv2d(x, Q(w), bias, stride, padding, dilation, groups = C) with one input channel per group and
+ * out_channels = m * C (m >= 1), fp32, forward and both gradients — BinConv2d / TerConv2d / DorefaConv2d(groups = in_channels)
+ * (layers/binary_layers.py:103-106, terner_layers.py:89-92, dorefa_layers.py:76-82 hand `groups` to F.conv2d).  Streaming kernels
+ * on the vector units (K = kh * kw is no matrix-core shape): csrc/dwconv.hip, DESIGN.md "Depthwise convs".
+ *
+ * Operands.  x [N, C, H, W], y / go [N, C m, Ho, Wo] with Ho = (H + 2 ph - dh (kh - 1) - 1) / sh + 1 (Wo alike), each DENSE in
+ * NCHW or in channels-last order and described by its four ELEMENT strides (n, c, h, w): exactly (C H W, H W, W, 1) or
+ * (H W C, 1, W C, C) of that tensor's own shape; the two tensors of a call need not share a layout.  w [C m, kh kw] dense fp32
+ * (row c m + j: multiplier j of input channel c), bias [C m] or NULL.  `kind` is the quantiser Q applied to every tap inside the
+ * kernel (the shared device helpers of csrc/qt_common.h): QT_DW_RAW the stored value, QT_DW_SIGN safeSign (x < 0 ? -1 : +1, so
+ * -0.0 and NaN give +1), QT_DW_TERNARY (w >= 0.5 -> +1, w < -0.5 -> -1, else 0; NaN -> +1).  Zero padding, numeric; stride,
+ * padding and dilation per axis.
+ *
+ * Pinned arithmetic (fp32, one multiply then one add per term, nothing contracted), so that a float32 restatement on a CPU gives
+ * the same bits:
+ *   qt_dwconv2d_f32            : y[n, c m + j, ho, wo] = (sum over taps of x[n, c, ho sh - ph + i dh, wo sw - pw + j' dw]
+ *                                Q(w)[c m + j, i, j']) + bias.  The accumulator starts at +0, the taps are added in row-major
+ *                                (i, j') order, taps outside the image are skipped, the bias is added last (NULL: nothing is).
+ *   qt_dwconv2d_grad_input_f32 : gather form, no atomics.  gx[n, c, h, w] = sum of go[n, c m + j, ho, wo] Q(w)[c m + j, i, j']
+ *                                over j (outermost, ascending) and the taps (row-major), over those (ho, wo) inside the output with
+ *                                ho sh - ph + i dh == h and wo sw - pw + j' dw == w.  Same rules.  gx is written in full.
+ *   qt_dwconv2d_grad_weight_f32: gw[co, i, j'] = sum over (n, ho, wo) of go[n, co, ho, wo] x[n, co / m, ...], L = N Ho Wo terms
+ *                                per element, in two stream-ordered launches with no atomics and no buffer that must be zero
+ *                                beforehand: the first writes one partial per (split, channel, tap) into `work` (a fixed walk
+ *                                per thread, a fixed butterfly over the lanes and the waves in index order), the second adds
+ *                                the splits in index order.  The order depends on the shapes and the layout of go alone: equal
+ *                                inputs give equal bits.  gw[co, t] is then ZERO where |w[co, t]| > ste_threshold — w is the
+ *                                UNquantised weight; ste_threshold 1.001f for the sign families, 0 for no mask (w may then be
+ *                                NULL).  gbias, when not NULL, receives sum of go per channel from the same pass.
+ *                                `work` holds at least qt_dwconv2d_grad_weight_work_floats(...) floats (a bound for either
+ *                                layout of go; no initial content needed), `work_floats` states how many it holds.
+ *
+ * Limits: kh kw <= QT_DW_MAX_TAPS; every tensor below 2^31 elements; C m <= QT_DW_MAX_CHANNELS (the grid is one-dimensional:
+ * channel groups x splits, at most QT_DW_MAX_CHANNELS + 2048 workgroups); beyond them QT_ERR_UNSUPPORTED.
+ *
+ * Everything is validated before anything is enqueued, in this order; a non-zero status means nothing was launched:
+ *   1. negative sizes, m < 1, a kernel / stride / dilation below 1, negative padding: QT_ERR_INVALID_ARG; kh kw > QT_DW_MAX_TAPS:
+ *      QT_ERR_UNSUPPORTED.
+ *   2. N, C, H or W zero: QT_OK whatever the pointers are, nothing is written (the work-size query returns 0).
+ *   3. the other limits: QT_ERR_UNSUPPORTED; a kernel that does not fit the padded image: QT_ERR_INVALID_ARG.
+ *   4. an unknown `kind`, a negative or NaN ste_threshold, a null tensor (bias and gbias may be null), strides that are neither
+ *      dense layout, a workspace smaller than the query: QT_ERR_INVALID_ARG; a pointer that is not 4-byte aligned:
+ *      QT_ERR_ALIGNMENT.
+ * ---------------------------------------------------------------------------------------- */
+#define QT_DW_RAW          0
+#define QT_DW_SIGN         1
+#define QT_DW_TERNARY      2
+#define QT_DW_MAX_TAPS     49
+#define QT_DW_MAX_CHANNELS 1048576
+
+int qt_dwconv2d_f32(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t C, int64_t m, int64_t H,
+                    int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t xs_n, int64_t xs_c,
+                    int64_t xs_h, int64_t xs_w, int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, int kind,
+                    qt_stream_t stream);
+int qt_dwconv2d_grad_input_f32(const float* go, const float* w, float* gx, int64_t N, int64_t C, int64_t m, int64_t H,
+                               int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n,
+                               int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h,
+                               int64_t xs_w, int kind, qt_stream_t stream);
+int64_t qt_dwconv2d_grad_weight_work_floats(int64_t N, int64_t C, int64_t m, int64_t H, int64_t W, int kh, int kw, int sh,
+                                            int sw, int ph, int pw, int dh, int dw);
+int qt_dwconv2d_grad_weight_f32(const float* go, const float* x, const float* w, float* gw, float* gbias, float* work,
+                                int64_t work_floats, int64_t N, int64_t C, int64_t m, int64_t H, int64_t W, int kh, int kw,
+                                int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n, int64_t gs_c, int64_t gs_h,
+                                int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, float ste_threshold,
+                                qt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

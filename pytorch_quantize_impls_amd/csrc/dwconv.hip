@@ -1,0 +1,431 @@
+// Depthwise conv2d (groups == in_channels, out_channels = m * in_channels) in fp32: forward, grad_input, grad_weight.
+// include/qt_hip.h "Depthwise convolution" states the contract; DESIGN.md "Depthwise convs" the layout and the byte counts.
+//
+// These are streaming kernels: K = kh * kw <= 49 is no matrix-core shape.  One thread owns ONE channel for the whole launch and
+// keeps that channel's quantised taps in registers (the quantisers are the shared device helpers of qt_common.h); it then walks
+// the outputs of its channel that the thread map hands it.  Two thread maps, chosen by the layout of the tensor that is written:
+//   NCHW          : tid -> (channel slot, row of the tile, column of the tile), TW x TH x slots = 256, all powers of two.  Lanes
+//                   run along W.  A large plane gives slots = 1 (a workgroup owns 4-row strips of one (n, channel) plane, its taps
+//                   come from wave-uniform addresses); a 14 x 14 or 7 x 7 plane gives a 16 x 16 or 8 x 8 tile and 1 or 4 channel
+//                   slots per workgroup, so the waves stay populated.
+//   channels-last : tid -> (pixel slot, channel lane), lanes run along C (up to 64), 256 / lanes pixels per step.
+// A workgroup is (channel group, split): it walks units split, split + S, ... of its channels, so the grid is one-dimensional and
+// bounded by the plan, never by N * C * m.  The row re-reads of neighbouring taps are left to L1 / L2 (no LDS staging).
+//
+// Arithmetic: one fp32 multiply and one fp32 add per tap (the build has -ffp-contract=off), the accumulator starts at +0, taps in
+// row-major order, taps outside the image skipped, bias last.  grad_weight: per-thread partial sums in walk order, a butterfly over
+// the lanes that share a channel, the waves in index order, one partial per (split, channel, tap) in the workspace; a second launch
+// adds the splits in index order.  No atomics anywhere: equal inputs give equal bits.
+#include "qt_common.h"
+
+namespace {
+
+constexpr int DW_THREADS = 256;
+constexpr int DW_MAX_TAPS = QT_DW_MAX_TAPS;
+constexpr int64_t DW_MAX_ELEMS = (int64_t)1 << 31;
+constexpr int64_t DW_MAX_CHANNELS = QT_DW_MAX_CHANNELS;      // bounds the one-dimensional grid: channel groups + the split target
+
+struct DwGeom {
+    int N, C, m, H, W, Ho, Wo;
+    int kh, kw, sh, sw, ph, pw, dh, dw;
+    int64_t Cout;
+};
+
+struct DwStrides { int64_t n, c, h, w; };
+
+// how the 256 threads of a workgroup and its units cover (channel, n, row, column) of the tensor being walked
+struct DwMap {
+    int cl;              // 1: channels-last map
+    int a_log, b_log;    // NCHW: log2 TW, log2 TH;   channels-last: log2 lanes along C, unused
+    int slots;           // channels per workgroup
+    int tiles_h, tiles_w;
+    int Hm, Wm;          // the plane that is walked (Ho x Wo, or H x W for grad_input)
+    int64_t chans;       // channels that are walked (C * m, or C)
+    int64_t npix;        // N * Hm * Wm
+    int units, splits;
+    int64_t cgs;
+};
+
+inline int dw_pow2ceil(int64_t v) {
+    int p = 1;
+    while (p < v) p <<= 1;
+    return p;
+}
+inline int dw_log2(int p) {
+    int l = 0;
+    while ((1 << l) < p) ++l;
+    return l;
+}
+
+DwMap dw_plan(int cl, int64_t N, int64_t chans, int Hm, int Wm, int target_wgs) {
+    DwMap mp{};
+    mp.cl = cl;
+    mp.Hm = Hm;
+    mp.Wm = Wm;
+    mp.chans = chans;
+    mp.npix = N * Hm * Wm;
+    if (cl) {
+        const int tc = dw_pow2ceil(chans < 64 ? chans : 64);
+        mp.a_log = dw_log2(tc);
+        mp.slots = tc;
+        const int tpix = DW_THREADS / tc;
+        mp.units = (int)((mp.npix + tpix - 1) / tpix);
+    } else {
+        const int tw = dw_pow2ceil(Wm < 64 ? Wm : 64);
+        int th = dw_pow2ceil(Hm);
+        if (th > DW_THREADS / tw) th = DW_THREADS / tw;
+        mp.a_log = dw_log2(tw);
+        mp.b_log = dw_log2(th);
+        mp.slots = DW_THREADS / (tw * th);
+        mp.tiles_w = (Wm + tw - 1) / tw;
+        mp.tiles_h = (Hm + th - 1) / th;
+        mp.units = (int)(N * mp.tiles_h * mp.tiles_w);
+    }
+    mp.cgs = (chans + mp.slots - 1) / mp.slots;
+    int64_t s = (target_wgs + mp.cgs - 1) / mp.cgs;
+    if (s > mp.units) s = mp.units;
+    if (s < 1) s = 1;
+    mp.splits = (int)s;
+    return mp;
+}
+
+__device__ __forceinline__ int dw_slot(const DwMap& mp, int tid) {
+    return mp.cl ? (tid & (mp.slots - 1)) : (tid >> (mp.a_log + mp.b_log));
+}
+
+// position (n, h, w) that thread `tid` has in unit `u`; false when it lies outside the tensor
+__device__ __forceinline__ bool dw_pos(const DwMap& mp, int u, int tid, int& n, int& h, int& w) {
+    if (mp.cl) {
+        const int64_t pix = (int64_t)u * (DW_THREADS >> mp.a_log) + (tid >> mp.a_log);
+        if (pix >= mp.npix) return false;
+        const int p = (int)pix;
+        const int hw = mp.Hm * mp.Wm;
+        n = p / hw;
+        const int r = p - n * hw;
+        h = r / mp.Wm;
+        w = r - h * mp.Wm;
+        return true;
+    }
+    const int per = mp.tiles_h * mp.tiles_w;
+    n = u / per;
+    const int r = u - n * per;
+    const int th = r / mp.tiles_w;
+    const int tw = r - th * mp.tiles_w;
+    w = (tw << mp.a_log) + (tid & ((1 << mp.a_log) - 1));
+    h = (th << mp.b_log) + ((tid >> mp.a_log) & ((1 << mp.b_log) - 1));
+    return h < mp.Hm && w < mp.Wm;
+}
+
+__device__ __forceinline__ float dw_quant(int kind, float w) {
+    return kind == QT_DW_SIGN ? qt_safe_sign(w) : (kind == QT_DW_TERNARY ? qt_ternarize(w) : w);
+}
+
+// KH == 0: any kernel of up to 49 taps, tap coordinates divided out at run time; else the compile-time kernel
+template <int KH, int KW>
+struct DwTaps {
+    static constexpr bool GEN = KH == 0;
+    static constexpr int CAP = GEN ? DW_MAX_TAPS : KH * KW;
+    __device__ __forceinline__ static int kw(const DwGeom& g) { return GEN ? g.kw : KW; }
+    __device__ __forceinline__ static int kk(const DwGeom& g) { return GEN ? g.kh * g.kw : KH * KW; }
+};
+
+template <int KH, int KW>
+__global__ __launch_bounds__(DW_THREADS) void dw_forward_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                const float* __restrict__ bias, float* __restrict__ y, DwGeom g,
+                                                                DwStrides xs, DwStrides ys, DwMap mp, int kind) {
+    using T = DwTaps<KH, KW>;
+    const int tid = threadIdx.x;
+    const int64_t cg = blockIdx.x / mp.splits;
+    const int split = (int)(blockIdx.x - cg * mp.splits);
+    const int64_t co = cg * mp.slots + dw_slot(mp, tid);
+    if (co >= g.Cout) return;
+    const int kw = T::kw(g), kk = T::kk(g);
+    float wq[T::CAP];
+#pragma unroll
+    for (int t = 0; t < T::CAP; ++t) wq[t] = t < kk ? dw_quant(kind, w[co * kk + t]) : 0.0f;
+    const float b = bias ? bias[co] : 0.0f;
+    const int64_t c = co / g.m;
+    for (int u = split; u < mp.units; u += mp.splits) {
+        int n, ho, wo;
+        if (!dw_pos(mp, u, tid, n, ho, wo)) continue;
+        const float* xp = x + n * xs.n + c * xs.c;
+        const int h0 = ho * g.sh - g.ph, w0 = wo * g.sw - g.pw;
+        float acc = 0.0f;
+#pragma unroll
+        for (int t = 0; t < T::CAP; ++t) {
+            if (!T::GEN || t < kk) {
+                const int i = t / kw, j = t - i * kw;
+                const int hi = h0 + i * g.dh, wi = w0 + j * g.dw;
+                if (hi >= 0 && hi < g.H && wi >= 0 && wi < g.W) acc = acc + xp[hi * xs.h + wi * xs.w] * wq[t];
+            }
+        }
+        if (bias) acc = acc + b;
+        y[n * ys.n + co * ys.c + ho * ys.h + wo * ys.w] = acc;
+    }
+}
+
+// gather form: gx[n, c, h, w] = sum over j < m, taps (i, j') of go[n, c m + j, ho, wo] Q(w)[c m + j, i, j'] where
+// ho sh = h + ph - i dh and wo sw = w + pw - j' dw have a solution inside the output
+template <int KH, int KW>
+__global__ __launch_bounds__(DW_THREADS) void dw_grad_input_kernel(const float* __restrict__ go, const float* __restrict__ w,
+                                                                   float* __restrict__ gx, DwGeom g, DwStrides gs, DwStrides xs,
+                                                                   DwMap mp, int kind) {
+    using T = DwTaps<KH, KW>;
+    const int tid = threadIdx.x;
+    const int64_t cg = blockIdx.x / mp.splits;
+    const int split = (int)(blockIdx.x - cg * mp.splits);
+    const int64_t c = cg * mp.slots + dw_slot(mp, tid);
+    if (c >= g.C) return;
+    const int kw = T::kw(g), kk = T::kk(g);
+    const bool one = g.m == 1;            // the taps of the only output channel stay in registers
+    float wq[T::CAP];
+#pragma unroll
+    for (int t = 0; t < T::CAP; ++t) wq[t] = (one && t < kk) ? dw_quant(kind, w[c * kk + t]) : 0.0f;
+    for (int u = split; u < mp.units; u += mp.splits) {
+        int n, h, x0;
+        if (!dw_pos(mp, u, tid, n, h, x0)) continue;
+        float acc = 0.0f;
+        for (int j = 0; j < g.m; ++j) {
+            const int64_t co = c * g.m + j;
+            const float* gp = go + n * gs.n + co * gs.c;
+            const float* wp = w + co * kk;
+#pragma unroll
+            for (int t = 0; t < T::CAP; ++t) {
+                if (!T::GEN || t < kk) {
+                    const int i = t / kw, jj = t - i * kw;
+                    const int hh = h + g.ph - i * g.dh, ww = x0 + g.pw - jj * g.dw;
+                    if (hh >= 0 && ww >= 0) {
+                        const int ho = hh / g.sh, wo = ww / g.sw;
+                        if (ho * g.sh == hh && wo * g.sw == ww && ho < g.Ho && wo < g.Wo) {
+                            const float q = one ? wq[t] : dw_quant(kind, wp[t]);
+                            acc = acc + gp[ho * gs.h + wo * gs.w] * q;
+                        }
+                    }
+                }
+            }
+        }
+        gx[n * xs.n + c * xs.c + h * xs.h + x0 * xs.w] = acc;
+    }
+}
+
+// stage 1 of grad_weight: work[(split * Cout + co) * (kk + 1) + t] = this workgroup's share of sum go * x for tap t, and of
+// sum go for t == kk
+template <int KH, int KW>
+__global__ __launch_bounds__(DW_THREADS) void dw_grad_weight_kernel(const float* __restrict__ go, const float* __restrict__ x,
+                                                                    float* __restrict__ work, DwGeom g, DwStrides gs, DwStrides xs,
+                                                                    DwMap mp) {
+    using T = DwTaps<KH, KW>;
+    constexpr int CAP = T::CAP;
+    __shared__ float red[(CAP + 1) * DW_THREADS];
+    const int tid = threadIdx.x;
+    const int64_t cg = blockIdx.x / mp.splits;
+    const int split = (int)(blockIdx.x - cg * mp.splits);
+    const int64_t co = cg * mp.slots + dw_slot(mp, tid);
+    const bool live = co < g.Cout;
+    const int kw = T::kw(g), kk = T::kk(g);
+    const int64_t c = live ? co / g.m : 0;
+    float acc[CAP + 1];
+#pragma unroll
+    for (int t = 0; t <= CAP; ++t) acc[t] = 0.0f;
+    if (live) {
+        for (int u = split; u < mp.units; u += mp.splits) {
+            int n, ho, wo;
+            if (!dw_pos(mp, u, tid, n, ho, wo)) continue;
+            const float gv = go[n * gs.n + co * gs.c + ho * gs.h + wo * gs.w];
+            const float* xp = x + n * xs.n + c * xs.c;
+            const int h0 = ho * g.sh - g.ph, w0 = wo * g.sw - g.pw;
+            acc[CAP] = acc[CAP] + gv;
+#pragma unroll
+            for (int t = 0; t < CAP; ++t) {
+                if (!T::GEN || t < kk) {
+                    const int i = t / kw, j = t - i * kw;
+                    const int hi = h0 + i * g.dh, wi = w0 + j * g.dw;
+                    if (hi >= 0 && hi < g.H && wi >= 0 && wi < g.W) acc[t] = acc[t] + gv * xp[hi * xs.h + wi * xs.w];
+                }
+            }
+        }
+    }
+    // the lanes of a wave that share a channel: the low lane bits (NCHW map) or the bits from the channel lanes up (channels-last)
+    const int group = DW_THREADS / mp.slots;                       // NCHW: threads per channel slot
+    const int lo = mp.cl ? mp.slots : 1;
+    const int hi = mp.cl ? 64 : (group < 64 ? group : 64);
+#pragma unroll
+    for (int t = 0; t <= CAP; ++t) {
+        float v = acc[t];
+        for (int off = lo; off < hi; off <<= 1) v = v + __shfl_xor(v, off, 64);
+        red[t * DW_THREADS + tid] = v;
+    }
+    __syncthreads();
+    const int per = kk + 1;
+    for (int e = tid; e < mp.slots * per; e += DW_THREADS) {
+        const int q = e / per, t = e - q * per;
+        const float* r = red + (t == kk ? CAP : t) * DW_THREADS;
+        float s;
+        if (mp.cl) {
+            s = r[q];
+            for (int wv = 1; wv < DW_THREADS / 64; ++wv) s = s + r[wv * 64 + q];
+        } else {
+            s = r[q * group];
+            for (int wv = 1; wv < group / 64; ++wv) s = s + r[q * group + wv * 64];
+        }
+        const int64_t oc = cg * mp.slots + q;
+        if (oc < g.Cout) work[((int64_t)split * g.Cout + oc) * per + t] = s;
+    }
+}
+
+// stage 2: the splits in index order, the STE mask on the unquantised weight, the bias gradient
+__global__ __launch_bounds__(DW_THREADS) void dw_grad_weight_combine_kernel(const float* __restrict__ work, const float* __restrict__ w,
+                                                                            float* __restrict__ gw, float* __restrict__ gbias,
+                                                                            int64_t Cout, int kk, int splits, float thr) {
+    const int per = kk + 1;
+    const int64_t total = Cout * per;
+    for (int64_t e = (int64_t)blockIdx.x * DW_THREADS + threadIdx.x; e < total; e += (int64_t)gridDim.x * DW_THREADS) {
+        const int64_t co = e / per;
+        const int t = (int)(e - co * per);
+        float s = 0.0f;
+        for (int sp = 0; sp < splits; ++sp) s = s + work[((int64_t)sp * Cout + co) * per + t];
+        if (t < kk) {
+            if (thr > 0.0f && fabsf(w[co * kk + t]) > thr) s = 0.0f;
+            gw[co * kk + t] = s;
+        } else if (gbias) {
+            gbias[co] = s;
+        }
+    }
+}
+
+bool dw_aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+// 0 NCHW-contiguous, 1 channels-last, -1 neither, for a dense [N, C, H, W] tensor with these element strides
+int dw_layout(int64_t N, int64_t C, int64_t H, int64_t W, const DwStrides& s) {
+    if (s.w == 1 && s.h == W && s.c == H * W && s.n == C * H * W) return 0;
+    if (s.c == 1 && s.w == C && s.h == W * C && s.n == H * W * C) return 1;
+    return -1;
+}
+
+// validates the shape arguments and fills g; QT_OK with *empty set when there is nothing to compute
+int dw_geometry(int64_t N, int64_t C, int64_t m, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                int dw, DwGeom* g, bool* empty) {
+    *empty = false;
+    if (N < 0 || C < 0 || m < 1 || H < 0 || W < 0 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || ph < 0 || pw < 0 || dh < 1 || dw < 1)
+        return QT_ERR_INVALID_ARG;
+    if ((int64_t)kh * kw > DW_MAX_TAPS) return QT_ERR_UNSUPPORTED;
+    if (N == 0 || C == 0 || H == 0 || W == 0) {
+        *empty = true;
+        return QT_OK;
+    }
+    if (N >= DW_MAX_ELEMS || C >= DW_MAX_ELEMS || H >= DW_MAX_ELEMS || W >= DW_MAX_ELEMS || m >= DW_MAX_ELEMS || ph >= (1 << 24) ||
+        pw >= (1 << 24) || dh >= (1 << 24) || dw >= (1 << 24))
+        return QT_ERR_UNSUPPORTED;
+    if (H + 2 * (int64_t)ph >= DW_MAX_ELEMS || W + 2 * (int64_t)pw >= DW_MAX_ELEMS) return QT_ERR_UNSUPPORTED;     // tap coordinates are int
+    const int64_t eh = H + 2 * (int64_t)ph - (int64_t)dh * (kh - 1) - 1, ew = W + 2 * (int64_t)pw - (int64_t)dw * (kw - 1) - 1;
+    if (eh < 0 || ew < 0) return QT_ERR_INVALID_ARG;          // the kernel does not fit the padded image
+    const int64_t Ho = eh / sh + 1, Wo = ew / sw + 1;
+    const double in = (double)N * (double)C * (double)H * (double)W, out = (double)N * (double)C * (double)m * (double)Ho * (double)Wo;
+    if (in >= (double)DW_MAX_ELEMS || out >= (double)DW_MAX_ELEMS || (double)C * (double)m > (double)DW_MAX_CHANNELS)
+        return QT_ERR_UNSUPPORTED;
+    g->N = (int)N; g->C = (int)C; g->m = (int)m; g->H = (int)H; g->W = (int)W; g->Ho = (int)Ho; g->Wo = (int)Wo;
+    g->kh = kh; g->kw = kw; g->sh = sh; g->sw = sw; g->ph = ph; g->pw = pw; g->dh = dh; g->dw = dw;
+    g->Cout = C * m;
+    return QT_OK;
+}
+
+constexpr int DW_TARGET_STREAM = 2048;      // workgroups of a forward / grad_input launch: 8 per CU
+constexpr int DW_TARGET_REDUCE = 1024;      // ... of the grad_weight stage 1: each one leaves Cout-share x (taps + 1) partials
+
+#define DW_DISPATCH(KERNEL, g, ...)                                                                   \
+    do {                                                                                              \
+        if ((g).kh == 1 && (g).kw == 1) KERNEL<1, 1><<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);        \
+        else if ((g).kh == 3 && (g).kw == 3) KERNEL<3, 3><<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);   \
+        else if ((g).kh == 5 && (g).kw == 5) KERNEL<5, 5><<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);   \
+        else if ((g).kh == 7 && (g).kw == 7) KERNEL<7, 7><<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);   \
+        else KERNEL<0, 0><<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);                                   \
+    } while (0)
+
+inline int64_t dw_work_floats(const DwGeom& g, const DwMap& mp) { return (int64_t)mp.splits * g.Cout * (g.kh * g.kw + 1); }
+
+}  // namespace
+
+extern "C" int qt_dwconv2d_f32(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t C, int64_t m, int64_t H,
+                               int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t xs_n, int64_t xs_c,
+                               int64_t xs_h, int64_t xs_w, int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, int kind,
+                               qt_stream_t stream) {
+    DwGeom g{};
+    bool empty;
+    const int rc = dw_geometry(N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
+    if (rc != QT_OK || empty) return rc;
+    if (kind != QT_DW_RAW && kind != QT_DW_SIGN && kind != QT_DW_TERNARY) return QT_ERR_INVALID_ARG;
+    if (!x || !w || !y) return QT_ERR_INVALID_ARG;
+    const DwStrides xs{xs_n, xs_c, xs_h, xs_w}, ys{ys_n, ys_c, ys_h, ys_w};
+    const int ly = dw_layout(N, g.Cout, g.Ho, g.Wo, ys);
+    if (dw_layout(N, C, H, W, xs) < 0 || ly < 0) return QT_ERR_INVALID_ARG;
+    if (!dw_aligned4(x) || !dw_aligned4(w) || !dw_aligned4(y) || !dw_aligned4(bias)) return QT_ERR_ALIGNMENT;
+    const DwMap mp = dw_plan(ly, N, g.Cout, g.Ho, g.Wo, DW_TARGET_STREAM);
+    const unsigned grid = (unsigned)(mp.cgs * mp.splits);
+    hipStream_t s = (hipStream_t)stream;
+    DW_DISPATCH(dw_forward_kernel, g, x, w, bias, y, g, xs, ys, mp, kind);
+    return qt_check_launch();
+}
+
+extern "C" int qt_dwconv2d_grad_input_f32(const float* go, const float* w, float* gx, int64_t N, int64_t C, int64_t m, int64_t H,
+                                          int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n,
+                                          int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h,
+                                          int64_t xs_w, int kind, qt_stream_t stream) {
+    DwGeom g{};
+    bool empty;
+    const int rc = dw_geometry(N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
+    if (rc != QT_OK || empty) return rc;
+    if (kind != QT_DW_RAW && kind != QT_DW_SIGN && kind != QT_DW_TERNARY) return QT_ERR_INVALID_ARG;
+    if (!go || !w || !gx) return QT_ERR_INVALID_ARG;
+    const DwStrides gs{gs_n, gs_c, gs_h, gs_w}, xs{xs_n, xs_c, xs_h, xs_w};
+    const int lx = dw_layout(N, C, H, W, xs);
+    if (dw_layout(N, g.Cout, g.Ho, g.Wo, gs) < 0 || lx < 0) return QT_ERR_INVALID_ARG;
+    if (!dw_aligned4(go) || !dw_aligned4(w) || !dw_aligned4(gx)) return QT_ERR_ALIGNMENT;
+    const DwMap mp = dw_plan(lx, N, C, g.H, g.W, DW_TARGET_STREAM);
+    const unsigned grid = (unsigned)(mp.cgs * mp.splits);
+    hipStream_t s = (hipStream_t)stream;
+    DW_DISPATCH(dw_grad_input_kernel, g, go, w, gx, g, gs, xs, mp, kind);
+    return qt_check_launch();
+}
+
+extern "C" int64_t qt_dwconv2d_grad_weight_work_floats(int64_t N, int64_t C, int64_t m, int64_t H, int64_t W, int kh, int kw, int sh,
+                                                       int sw, int ph, int pw, int dh, int dw) {
+    DwGeom g{};
+    bool empty;
+    const int rc = dw_geometry(N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
+    if (rc != QT_OK) return rc;
+    if (empty) return 0;
+    // either layout of the gradient: the larger of the two plans
+    const int64_t a = dw_work_floats(g, dw_plan(0, N, g.Cout, g.Ho, g.Wo, DW_TARGET_REDUCE));
+    const int64_t b = dw_work_floats(g, dw_plan(1, N, g.Cout, g.Ho, g.Wo, DW_TARGET_REDUCE));
+    return a > b ? a : b;
+}
+
+extern "C" int qt_dwconv2d_grad_weight_f32(const float* go, const float* x, const float* w, float* gw, float* gbias, float* work,
+                                           int64_t work_floats, int64_t N, int64_t C, int64_t m, int64_t H, int64_t W, int kh, int kw,
+                                           int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n, int64_t gs_c, int64_t gs_h,
+                                           int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, float ste_threshold,
+                                           qt_stream_t stream) {
+    DwGeom g{};
+    bool empty;
+    const int rc = dw_geometry(N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
+    if (rc != QT_OK) return rc;
+    if (empty) return QT_OK;          // nothing is written: the caller owns the zero gradient of an empty batch
+    if (!gw || (ste_threshold > 0.0f && !w) || !(ste_threshold >= 0.0f)) return QT_ERR_INVALID_ARG;
+    if (!dw_aligned4(gw) || !dw_aligned4(gbias) || !dw_aligned4(w)) return QT_ERR_ALIGNMENT;
+    hipStream_t s = (hipStream_t)stream;
+    const int kk = kh * kw;
+    if (!go || !x || !work || work_floats < 0) return QT_ERR_INVALID_ARG;
+    const DwStrides gs{gs_n, gs_c, gs_h, gs_w}, xs{xs_n, xs_c, xs_h, xs_w};
+    const int lg = dw_layout(N, g.Cout, g.Ho, g.Wo, gs);
+    if (lg < 0 || dw_layout(N, C, H, W, xs) < 0) return QT_ERR_INVALID_ARG;
+    if (!dw_aligned4(go) || !dw_aligned4(x) || !dw_aligned4(work)) return QT_ERR_ALIGNMENT;
+    const DwMap mp = dw_plan(lg, N, g.Cout, g.Ho, g.Wo, DW_TARGET_REDUCE);
+    if (work_floats < dw_work_floats(g, mp)) return QT_ERR_INVALID_ARG;
+    const unsigned grid = (unsigned)(mp.cgs * mp.splits);
+    DW_DISPATCH(dw_grad_weight_kernel, g, go, x, work, g, gs, xs, mp);
+    int st = qt_check_launch();
+    if (st != QT_OK) return st;
+    dw_grad_weight_combine_kernel<<<qt_stream_grid((g.Cout * (kk + 1) + DW_THREADS - 1) / DW_THREADS), DW_THREADS, 0, s>>>(
+        work, w, gw, gbias, g.Cout, kk, mp.splits, ste_threshold);
+    return qt_check_launch();
+}

@@ -1937,6 +1937,55 @@ class LogLinConv2dFn(QtFunction):
         return grad_input, grad_weight, grad_bias, None, None
 
 
+# ---- depthwise convs (groups == in_channels) ---------------------------------------------------------------------------------------
+# K = kh * kw <= 49 is no matrix-core shape: one streaming launch forward, one per gradient (csrc/dwconv.hip, DESIGN.md "Depthwise
+# convs").  The kernels multiply whatever the activation holds, so nothing here asks whether it is +-1: no tag lookup, no detection,
+# no host synchronisation — the node can be captured in a hipGraph as it is.
+
+def depthwise_route(layer, input) -> bool:
+    """``layer`` (a Conv2d subclass with an fp32 weight) applied to ``input`` is a depthwise conv the HIP kernels take: a 4-D fp32
+    device tensor, ``groups == in_channels > 1``, padding mode "zeros" with numeric padding."""
+    return (isinstance(input, torch.Tensor) and input.is_cuda and input.dtype == torch.float32 and input.dim() == 4
+            and layer.weight.dtype == torch.float32 and layer.groups > 1 and layer.padding_mode == "zeros"
+            and ops.depthwise_applicable(input.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups))
+
+
+class DepthwiseConv2dFn(QtFunction):
+    """conv2d(x, Q(W), b, groups = C) with one input channel per group.  ``kind``: the quantiser the forward and grad_input kernels
+    apply to the taps ("binary" | "ternary" | "raw"); ``weight_q``: an image that replaces Q(W) (a saved stochastic draw, the stored
+    eval-mode image) — the kernels then run "raw" on it; ``ste``: threshold of the straight-through mask on the UNquantised
+    ``weight`` (0: none).  Forward one launch; backward grad_input and grad_weight (partials + combine inside one call), the bias
+    gradient being a by-product of the latter."""
+
+    @staticmethod
+    def forward(ctx, input, weight, bias, kind, weight_q, ste, conv_args):
+        stride, padding, dilation, _groups = conv_args
+        ctx.kind = kind if weight_q is None else "raw"
+        ctx.conv_args, ctx.ste, ctx.has_bias = conv_args, float(ste), bias is not None
+        input = _dense(input)
+        ctx.save_for_backward(input, weight, weight_q)
+        return ops.depthwise_conv2d(input, weight if weight_q is None else weight_q, bias, stride, padding, dilation, kind=ctx.kind)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        input, weight, weight_q = ctx.saved_tensors
+        stride, padding, dilation, _groups = ctx.conv_args
+        go = _dense(grad_output)
+        grad_input = grad_weight = grad_bias = None
+        if ctx.needs_input_grad[0]:
+            grad_input = ops.depthwise_conv2d_grad_input(input.shape, weight if weight_q is None else weight_q, go, stride, padding,
+                                                         dilation, kind=ctx.kind,
+                                                         channels_last=input.is_contiguous(memory_format=torch.channels_last)
+                                                         and not input.is_contiguous())
+        want_bias = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_bias:
+            grad_weight, grad_bias = ops.depthwise_conv2d_grad_weight(input, go, weight, stride, padding, dilation,
+                                                                      ste_threshold=ctx.ste, want_bias=want_bias)
+            if not ctx.needs_input_grad[1]:
+                grad_weight = None
+        return grad_input, grad_weight, grad_bias, None, None, None, None
+
+
 def grouped_quant_conv(layer, input, kind: str, quant_op):
     """BinConv2d / TerConv2d with ``groups`` > 1 (layers/binary_layers.py:59-60,103-106 hand ``groups`` to F.conv2d): group g is
     an independent conv of its channel slice with its rows of the weight, and the element-wise quantisers (safeSign, the fixed

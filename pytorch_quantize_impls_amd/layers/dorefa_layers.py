@@ -165,6 +165,11 @@ class DorefaConv2d(_DorefaLayer, torch.nn.Conv2d, QLayer):
         if self._eval_off_grid(input):
             _fused.note_library_path(input, "eval-mode weight off the quantiser's grid")
             return torch.nn.functional.conv2d(input, self.weight, self.bias, *args)
+        if _fused.depthwise_route(self, input):
+            # groups == in_channels, any bit_width: the streaming depthwise kernels on the quantised image, forward and both
+            # gradients; the gradient of the image flows on through weight_op's own backward, as on the RealConv2dFn route
+            w = self.weight_op.forward(self.weight) if self.training else self.weight
+            return _fused.DepthwiseConv2dFn.apply(input, w, self.bias, "raw", None, 0.0, args)
         if self._w1_route(input):
             if self.training:
                 return _fused.DorefaW1Conv2dFn.apply(input, self.weight, self.bias, args)

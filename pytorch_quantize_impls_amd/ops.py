@@ -4072,3 +4072,183 @@ def pack_weight_nib_into(weight: torch.Tensor, kind: str, planes: NibPlanes) -> 
     with _on(weight.device):
         _lib.call(entry, _p(w2), int(w2.stride(0) if rows > 1 else max(K, 1)), _p(words), int(words.shape[1]), rows, K,
                   _stream(weight.device))
+
+
+# ----------------------------------------------------------------------------------------------
+# depthwise conv2d (groups == in_channels): streaming kernels of csrc/dwconv.hip, forward and both gradients
+# ----------------------------------------------------------------------------------------------
+
+DW_KINDS = {"raw": _lib.DEFINES["QT_DW_RAW"], "binary": _lib.DEFINES["QT_DW_SIGN"], "ternary": _lib.DEFINES["QT_DW_TERNARY"]}
+DW_MAX_TAPS = _lib.DEFINES["QT_DW_MAX_TAPS"]
+DW_MAX_CHANNELS = _lib.DEFINES["QT_DW_MAX_CHANNELS"]
+
+
+def depthwise_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
+    """A conv2d of an [N, C, H, W] input with a [C * m, 1, kh, kw] weight and ``groups == C`` (one input channel per group,
+    m >= 1) that the depthwise entry points take: numeric padding, kh * kw <= 49, every tensor non-empty and below 2^31
+    elements, at most ``DW_MAX_CHANNELS`` output channels.  A pure function of the shapes."""
+    if len(x_shape) != 4 or len(w_shape) != 4 or isinstance(padding, str):
+        return False
+    N, C, H, W = (int(v) for v in x_shape)
+    Cout, cin_g, kh, kw = (int(v) for v in w_shape)
+    if int(groups) != C or C < 1 or cin_g != 1 or Cout < C or Cout % C != 0 or min(N, H, W, kh, kw) < 1:
+        return False
+    try:
+        (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
+    except (TypeError, IndexError, ValueError):
+        return False
+    if min(sh, sw, dh, dw) < 1 or min(ph, pw) < 0 or max(ph, pw, dh, dw) >= 1 << 24 or kh * kw > DW_MAX_TAPS or Cout > DW_MAX_CHANNELS:
+        return False
+    Ho, Wo = conv_out_hw(H, W, kh, kw, (sh, sw), (ph, pw), (dh, dw))
+    if Ho < 1 or Wo < 1 or H + 2 * ph >= 1 << 31 or W + 2 * pw >= 1 << 31:
+        return False
+    return N * C * H * W < 1 << 31 and N * Cout * Ho * Wo < 1 << 31
+
+
+def _dw_channels_last(t: torch.Tensor) -> bool:
+    return t.is_contiguous(memory_format=torch.channels_last) and not t.is_contiguous()
+
+
+def _dw_strides(shape, channels_last: bool):
+    """The element strides (n, c, h, w) the entry points accept for a dense tensor of ``shape`` (torch leaves the strides of
+    size-1 dimensions arbitrary)."""
+    _, C, H, W = (int(v) for v in shape)
+    return (H * W * C, 1, W * C, C) if channels_last else (C * H * W, H * W, W, 1)
+
+
+def _dw_operand(t: torch.Tensor, name: str, shape=None) -> torch.Tensor:
+    _require(t, name)
+    if t.dim() != 4 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{name}: expected a 4-D tensor" + (f" of shape {tuple(shape)}" if shape is not None else "") + f", got {tuple(t.shape)}")
+    return t if _storage_dense(t) else t.contiguous()
+
+
+def _dw_result(out: Optional[torch.Tensor], shape, like: torch.Tensor, name: str) -> torch.Tensor:
+    """``out`` checked (fp32, this shape, dense in NCHW or channels-last order, on ``like``'s device), or a new tensor of
+    ``shape`` in the layout of ``like``."""
+    if out is None:
+        fmt = torch.channels_last if _dw_channels_last(like) else torch.contiguous_format
+        return torch.empty(tuple(shape), dtype=torch.float32, device=like.device, memory_format=fmt)
+    _require(out, name)
+    if tuple(out.shape) != tuple(shape) or not _storage_dense(out) or out.device != like.device:
+        raise ValueError(f"{name}: expected a dense fp32 tensor of shape {tuple(shape)} on {like.device}, got {tuple(out.shape)} "
+                         f"with strides {out.stride()} on {out.device}")
+    return out
+
+
+def _dw_weight(weight: torch.Tensor, C: int):
+    _require(weight, "weight")
+    if weight.dim() != 4 or weight.shape[1] != 1 or C < 1 or weight.shape[0] % C != 0 or weight.shape[0] < C:
+        raise ValueError(f"weight: expected [C * m, 1, kh, kw] for C = {C}, got {tuple(weight.shape)}")
+    w = weight.detach()
+    return (w if w.is_contiguous() else w.contiguous()), int(weight.shape[0]) // C, int(weight.shape[2]), int(weight.shape[3])
+
+
+def _dw_geometry(x_shape, weight, stride, padding, dilation):
+    N, C, H, W = (int(v) for v in x_shape)
+    w, m, kh, kw = _dw_weight(weight, C)
+    if not depthwise_applicable(x_shape, weight.shape, stride, padding, dilation, C) and min(N, C, H, W) > 0:
+        raise ValueError(f"not a depthwise conv the HIP entry points take: input {tuple(x_shape)}, weight {tuple(weight.shape)}, "
+                         f"stride {stride}, padding {padding}, dilation {dilation}")
+    (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
+    Ho, Wo = (conv_out_hw(H, W, kh, kw, (sh, sw), (ph, pw), (dh, dw)) if min(H, W) > 0 else (0, 0))
+    return w, (N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw), (N, C * m, max(Ho, 0), max(Wo, 0))
+
+
+def depthwise_conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1,
+                     kind: str = "raw", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """F.conv2d(x, Q(weight), bias, stride, padding, dilation, groups = C) for x [N, C, H, W] fp32 (NCHW or channels-last) and
+    weight [C * m, 1, kh, kw]; Q = ``kind`` ("raw" | "binary" | "ternary") is applied to the taps inside the one launch
+    (qt_dwconv2d_f32).  The result has the layout of x, or is written into ``out``.  Bit-reproducible: +0 start, taps in row-major
+    order, one multiply and one add each, out-of-image taps skipped, bias last."""
+    x = _dw_operand(x, "input")
+    w, geom, y_shape = _dw_geometry(x.shape, weight, stride, padding, dilation)
+    bias = _check_bias(bias, y_shape[1], x.device)
+    y = _dw_result(out, y_shape, x, "out")
+    if y.numel() == 0 or x.numel() == 0:
+        return y
+    with _on(x.device):
+        _lib.call("qt_dwconv2d_f32", _p(x), _p(w), _p(bias), _p(y), *geom, *_dw_strides(x.shape, _dw_channels_last(x)),
+                  *_dw_strides(y.shape, _dw_channels_last(y)), DW_KINDS[kind], _stream(x.device))
+    return y
+
+
+def depthwise_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_output: torch.Tensor, stride=1, padding=0, dilation=1,
+                                kind: str = "raw", channels_last: Optional[bool] = None,
+                                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient of ``depthwise_conv2d`` with respect to x: a gather over the multiplier index (outermost) and the taps (row-major)
+    with the forward's arithmetic rules, no atomics (qt_dwconv2d_grad_input_f32).  The result has the layout of
+    ``grad_output`` unless ``channels_last`` says otherwise, or is written into ``out``."""
+    w, geom, y_shape = _dw_geometry(input_shape, weight, stride, padding, dilation)
+    go = _dw_operand(grad_output, "grad_output", y_shape)
+    if out is None:
+        cl = _dw_channels_last(go) if channels_last is None else bool(channels_last)
+        gx = torch.empty(tuple(input_shape), dtype=torch.float32, device=go.device,
+                         memory_format=torch.channels_last if cl else torch.contiguous_format)
+    else:
+        gx = _dw_result(out, input_shape, go, "out")
+    if gx.numel() == 0:
+        return gx
+    if go.numel() == 0:
+        return gx.zero_()
+    with _on(go.device):
+        _lib.call("qt_dwconv2d_grad_input_f32", _p(go), _p(w), _p(gx), *geom, *_dw_strides(go.shape, _dw_channels_last(go)),
+                  *_dw_strides(gx.shape, _dw_channels_last(gx)), DW_KINDS[kind], _stream(go.device))
+    return gx
+
+
+def depthwise_grad_weight_work_floats(input_shape, weight_shape, stride=1, padding=0, dilation=1) -> int:
+    """fp32 elements of workspace ``depthwise_conv2d_grad_weight`` needs (qt_dwconv2d_grad_weight_work_floats)."""
+    N, C, H, W = (int(v) for v in input_shape)
+    (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
+    n = int(_lib.load().qt_dwconv2d_grad_weight_work_floats(N, C, int(weight_shape[0]) // max(C, 1), H, W, int(weight_shape[2]),
+                                                            int(weight_shape[3]), sh, sw, ph, pw, dh, dw))
+    if n < 0:
+        raise _lib.QtStatusError(f"qt_dwconv2d_grad_weight_work_floats failed: {_lib.strerror(n)} (qt_status {n})")
+    return n
+
+
+def depthwise_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, weight: torch.Tensor, stride=1, padding=0, dilation=1,
+                                 ste_threshold: float = 0.0, want_bias: bool = False, out: Optional[torch.Tensor] = None,
+                                 out_bias: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """Gradient of ``depthwise_conv2d`` with respect to the weight, shaped like ``weight``, and — ``want_bias`` or ``out_bias`` —
+    the per-channel sum of ``grad_output`` from the same pass (else None): ``(grad_weight, grad_bias)``.  Two launches inside one
+    call, no atomics: partials per (split, channel, tap) into ``workspace`` (``depthwise_grad_weight_work_floats`` fp32 elements;
+    allocated when not given), then the splits in index order; equal inputs give equal bits.  ``ste_threshold`` > 0 zeroes the
+    entries where the UNquantised ``|weight|`` exceeds it (1.001 for the sign families)."""
+    x = _dw_operand(x, "input")
+    w, geom, y_shape = _dw_geometry(x.shape, weight, stride, padding, dilation)
+    go = _dw_operand(grad_output, "grad_output", y_shape)
+    if go.device != x.device:
+        raise ValueError("input and grad_output are on different devices")
+    Cout, kk = y_shape[1], geom[5] * geom[6]
+    if out is None:
+        gw = torch.empty(tuple(weight.shape), dtype=torch.float32, device=x.device)
+    else:
+        gw = _require(out, "out")
+        if tuple(gw.shape) != tuple(weight.shape) or not gw.is_contiguous() or gw.device != x.device:
+            raise ValueError(f"out: expected a contiguous fp32 tensor of shape {tuple(weight.shape)} on {x.device}")
+    gb = None
+    if out_bias is not None:
+        gb = _require(out_bias, "out_bias")
+        if tuple(gb.shape) != (Cout,) or not gb.is_contiguous() or gb.device != x.device:
+            raise ValueError(f"out_bias: expected a contiguous fp32 tensor of shape ({Cout},) on {x.device}")
+    elif want_bias:
+        gb = torch.empty((Cout,), dtype=torch.float32, device=x.device)
+    if gw.numel() == 0:
+        return gw, gb
+    if go.numel() == 0 or x.numel() == 0:
+        gw.zero_()
+        return gw, (gb.zero_() if gb is not None else None)
+    need = depthwise_grad_weight_work_floats(x.shape, weight.shape, stride, padding, dilation)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.float32, device=x.device)
+    else:
+        _require(workspace, "workspace")
+        if not workspace.is_contiguous() or workspace.device != x.device or workspace.numel() < need:
+            raise ValueError(f"workspace: expected at least {need} contiguous fp32 elements on {x.device}")
+    with _on(x.device):
+        _lib.call("qt_dwconv2d_grad_weight_f32", _p(go), _p(x), _p(w), _p(gw), _p(gb), _p(workspace), int(workspace.numel()), *geom,
+                  *_dw_strides(go.shape, _dw_channels_last(go)), *_dw_strides(x.shape, _dw_channels_last(x)), float(ste_threshold),
+                  _stream(x.device))
+    return gw, gb
