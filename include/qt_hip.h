@@ -1310,6 +1310,46 @@ int qt_dwconv2d_grad_weight_f32(const float* go, const float* x, const float* w,
                                 int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, float ste_threshold,
                                 qt_stream_t stream);
 
+/* Depthwise convolution on bit planes: the forward above inside the fused inference chain conv -> BatchNorm -> Hardtanh ->
+ * BinaryConnect -> next conv, reading and / or writing the planes a PackedActivation carries instead of fp32 tensors.  One
+ * launch each; no allocation, no synchronisation.
+ *
+ * The value y[n, c m + j, ho, wo] is EXACTLY what qt_dwconv2d_f32 stores for the same operands (accumulator +0, taps row-major,
+ * taps outside the image skipped, one fp32 multiply then one fp32 add per term, bias last; `kind` quantises the taps).
+ *
+ * Input forms (exactly one of x / x_plane is non-null):
+ *   x        fp32 [N, C, H, W], dense NCHW or channels-last, by its element strides xs_* as above;
+ *   x_plane  NHWC sign plane of a +-1 activation (ops.BitPlanes.sign): uint32 [N H W][ldx], bit (c & 31) of word (c >> 5) of
+ *            pixel row (n H + h) W + w is channel c, decoded as 1 -> -1.0f, 0 -> +1.0f and fed to the same arithmetic;
+ *            ldx >= max(4, ceil(C / 32) rounded up to 4) (ops.packed_ld(C)).
+ * Output forms:
+ *   qt_dwconv2d_sign      the threshold bit  bit = [ fl(fl(y alpha[co]) + beta[co]) < 0 ]  (two roundings, plain IEEE compare: a
+ *                         tie, -0.0 and NaN give 0) of every output, alpha / beta fp32 [C m], written as
+ *       sign_plane  uint32 [N Ho Wo][ldb], ldb >= ops.packed_ld(C m): bit (k & 31) of word (k >> 5) of a pixel row is channel
+ *                   k, 1 <=> negative; every bit and every word past C m is written as zero;
+ *       nib_plane   uint32 [N (Ho + 2 out_halo_h) (Wo + 2 out_halo_w)][ldn], ldn >= max(4, ceil(C m / 8) rounded up to 4)
+ *                   (ops.pixel_ld_nib(C m)) and ldn % 4 == 0, 16-byte aligned: element k in nibble (k & 7) of word (k >> 3),
+ *                   +1 = 0x2, -1 = 0xA; channels >= C m and the border pixels are zero words — the format of
+ *                   qt_pool_bits_nib / qt_bits_to_nib_pad.  The launch writes EVERY word of the plane, the border included.
+ *                   Either plane may be null (not wanted), not both.
+ *   qt_dwconv2d_bits_f32  y itself, fp32 [N, C m, Ho, Wo] by its element strides ys_* (for materialising a deferred depthwise conv
+ *                         whose input exists only as planes).
+ *
+ * Limits as above, unchanged (no C % 4 restriction); out_halo_* <= 64 and fewer than 2^31 pixel rows in nib_plane, beyond them
+ * QT_ERR_UNSUPPORTED.  Validation before anything is enqueued, in this order:
+ *   1. a negative halo, then step 1 above.   2. N, C, H or W zero: QT_OK, nothing is written.   3. the other limits.
+ *   4. an unknown `kind`, a null tensor (bias may be null), both or neither of x / x_plane, no output plane, a null alpha or beta,
+ *      strides that are no dense layout, ldx / ldb / ldn below the bounds above: QT_ERR_INVALID_ARG; then a pointer that is not
+ *      4-byte aligned, ldn % 4 != 0 or a nib_plane that is not 16-byte aligned: QT_ERR_ALIGNMENT. */
+int qt_dwconv2d_sign(const float* x, const uint32_t* x_plane, int64_t ldx, const float* w, const float* bias, const float* alpha,
+                     const float* beta, uint32_t* sign_plane, int64_t ldb, uint32_t* nib_plane, int64_t ldn, int64_t out_halo_h,
+                     int64_t out_halo_w, int64_t N, int64_t C, int64_t m, int64_t H, int64_t W, int kh, int kw, int sh, int sw,
+                     int ph, int pw, int dh, int dw, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, int kind,
+                     qt_stream_t stream);
+int qt_dwconv2d_bits_f32(const uint32_t* x_plane, int64_t ldx, const float* w, const float* bias, float* y, int64_t N, int64_t C,
+                         int64_t m, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                         int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, int kind, qt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,5 @@
-// Depthwise conv2d (groups == in_channels, out_channels = m * in_channels) in fp32: forward, grad_input, grad_weight.
+// Depthwise conv2d (groups == in_channels, out_channels = m * in_channels) in fp32: forward, grad_input, grad_weight — and the
+// forward on / into the bit planes of the fused inference chain (second half of the file).
 // include/qt_hip.h "Depthwise convolution" states the contract; DESIGN.md "Depthwise convs" the layout and the byte counts.
 //
 // These are streaming kernels: K = kh * kw <= 49 is no matrix-core shape.  One thread owns ONE channel for the whole launch and
@@ -341,7 +342,284 @@ constexpr int DW_TARGET_REDUCE = 1024;      // ... of the grad_weight stage 1: e
         else KERNEL<0, 0><<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);                                   \
     } while (0)
 
+// the same for a kernel template with one more (bool) parameter
+#define DW_DISPATCH_B(KERNEL, B, g, ...)                                                                 \
+    do {                                                                                                 \
+        if ((g).kh == 1 && (g).kw == 1) KERNEL<1, 1, B><<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);        \
+        else if ((g).kh == 3 && (g).kw == 3) KERNEL<3, 3, B><<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);   \
+        else if ((g).kh == 5 && (g).kw == 5) KERNEL<5, 5, B><<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);   \
+        else if ((g).kh == 7 && (g).kw == 7) KERNEL<7, 7, B><<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);   \
+        else KERNEL<0, 0, B><<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);                                   \
+    } while (0)
+
 inline int64_t dw_work_floats(const DwGeom& g, const DwMap& mp) { return (int64_t)mp.splits * g.Cout * (g.kh * g.kw + 1); }
+
+// ---- the forward on / into bit planes (include/qt_hip.h "Depthwise convolution on bit planes") -------------------------------------
+// dw_planes_kernel (sign-plane and channels-last fp32 inputs; also planes -> fp32): a HALF-wave (32 lanes) owns one 32-channel word
+// of one output pixel, a workgroup (plane word, split) walks 8 pixels per step, so every lane keeps ONE output channel — its taps,
+// bias, alpha and beta in registers — for the whole launch.  A plane input costs one word per tap and half-wave (the same address
+// in 32 lanes for m == 1), the lane picks its bit; a channels-last fp32 input is read in rows of 32 channels.  The threshold bits
+// of a wave come from one __ballot: its low word is the first pixel's, its high word the second's.
+// dw_planes_nchw_kernel (NCHW fp32 input): lanes along the pixels, the votes transposed through LDS (see there).
+// Either way one lane per (pixel, word) stores the word, the four nibble words made from it and — for the last word of a pixel —
+// the pad words of the row.  Nothing is read from an output buffer; the border pixels of a halo plane are zeroed by a walk of
+// the whole grid over the plane after the main loop.
+constexpr int DW_PIX_PER_STEP = DW_THREADS / 32;
+
+struct DwPlaneOut {
+    uint32_t* sign;      // [N Ho Wo][ldb] or null
+    uint32_t* nib;       // [N (Ho + 2 hy) (Wo + 2 hx)][ldn] or null
+    float* y;            // fp32 result by element strides, or null (then the planes are written)
+    int64_t ldb, ldn;
+    int hy, hx;
+};
+
+__device__ __forceinline__ uint32_t dw_spread8(uint32_t b) {
+    uint32_t t = b & 0xFFu;
+    t = (t | (t << 12)) & 0x000F000Fu;
+    t = (t | (t << 6)) & 0x03030303u;
+    t = (t | (t << 3)) & 0x11111111u;
+    return t;
+}
+
+__device__ __forceinline__ void dw_store_zero4(uint32_t* p) { *reinterpret_cast<uint4*>(p) = make_uint4(0, 0, 0, 0); }
+
+// the threshold bits of channels 32 wd ... 32 wd + 31 of output pixel pix = (n, ho, wo), bits of channels >= C m zero: the word of
+// the sign plane, its four nibble words, and — with the last live word of a pixel — the pad words of both rows
+__device__ __forceinline__ void dw_store_word(const DwPlaneOut& o, const DwGeom& g, int wd, int64_t pix, int n, int ho, int wo,
+                                              uint32_t word) {
+    const int nw = (int)((g.Cout + 31) >> 5);
+    if (o.sign) {
+        uint32_t* row = o.sign + pix * o.ldb;
+        row[wd] = word;
+        if (wd == nw - 1)
+            for (int64_t t = nw; t < o.ldb; ++t) row[t] = 0u;
+    }
+    if (o.nib) {
+        const int Hop = g.Ho + 2 * o.hy, Wop = g.Wo + 2 * o.hx;
+        const int64_t left = g.Cout - (int64_t)wd * 32;
+        const uint32_t mw = left >= 32 ? 0xFFFFFFFFu : ((1u << (int)left) - 1u);
+        uint4 q;
+        q.x = (dw_spread8(mw) << 1) | (dw_spread8(word) << 3);
+        q.y = (dw_spread8(mw >> 8) << 1) | (dw_spread8(word >> 8) << 3);
+        q.z = (dw_spread8(mw >> 16) << 1) | (dw_spread8(word >> 16) << 3);
+        q.w = (dw_spread8(mw >> 24) << 1) | (dw_spread8(word >> 24) << 3);
+        uint32_t* row = o.nib + (((int64_t)n * Hop + ho + o.hy) * Wop + wo + o.hx) * o.ldn;
+        *reinterpret_cast<uint4*>(row + wd * 4) = q;
+        if (wd == nw - 1)
+            for (int64_t t = (int64_t)nw * 4; t < o.ldn; t += 4) dw_store_zero4(row + t);
+    }
+}
+
+// the border pixels of a halo nibble plane, zeroed by a walk of the whole grid over the plane
+__device__ __forceinline__ void dw_zero_border(const DwPlaneOut& o, const DwGeom& g, int tid) {
+    if (!o.nib || !(o.hy || o.hx)) return;
+    const int Hop = g.Ho + 2 * o.hy, Wop = g.Wo + 2 * o.hx;
+    const int64_t groups = o.ldn / 4;
+    const int64_t total = (int64_t)g.N * Hop * Wop * groups;
+    for (int64_t e = (int64_t)blockIdx.x * DW_THREADS + tid; e < total; e += (int64_t)gridDim.x * DW_THREADS) {
+        const int64_t pix = e / groups;
+        const int rem = (int)(pix % ((int64_t)Hop * Wop));
+        const int r = rem / Wop - o.hy, q = rem % Wop - o.hx;
+        if ((unsigned)r >= (unsigned)g.Ho || (unsigned)q >= (unsigned)g.Wo) dw_store_zero4(o.nib + pix * o.ldn + (e - pix * groups) * 4);
+    }
+}
+
+// BITS_IN: x is the NHWC sign plane of a +-1 activation (ldx words per pixel; bit 1 -> -1.0f, bit 0 -> +1.0f), else fp32 by xs
+template <int KH, int KW, bool BITS_IN>
+__global__ __launch_bounds__(DW_THREADS) void dw_planes_kernel(const void* __restrict__ xv, int64_t ldx, const float* __restrict__ w,
+                                                               const float* __restrict__ bias, const float* __restrict__ alpha,
+                                                               const float* __restrict__ beta, DwPlaneOut o, DwGeom g, DwStrides xs,
+                                                               DwStrides ys, int units, int splits, int kind) {
+    using T = DwTaps<KH, KW>;
+    const int tid = threadIdx.x, lane = tid & 31;
+    const int wd = (int)(blockIdx.x / splits);
+    const int split = (int)(blockIdx.x - (unsigned)wd * splits);
+    const int64_t co = (int64_t)wd * 32 + lane;
+    const bool live = co < g.Cout;
+    const int kw = T::kw(g), kk = T::kk(g);
+    float wq[T::CAP];
+#pragma unroll
+    for (int t = 0; t < T::CAP; ++t) wq[t] = (live && t < kk) ? dw_quant(kind, w[co * kk + t]) : 0.0f;
+    const float b = (live && bias) ? bias[co] : 0.0f;
+    const float al = (live && alpha) ? alpha[co] : 0.0f, be = (live && beta) ? beta[co] : 0.0f;
+    const int64_t c = live ? co / g.m : 0;
+    const int hw = g.Ho * g.Wo;
+    const int64_t npix = (int64_t)g.N * hw;
+    const float* xf = static_cast<const float*>(xv);
+    const uint32_t* xb = static_cast<const uint32_t*>(xv);
+    for (int u = split; u < units; u += splits) {
+        const int64_t pix = (int64_t)u * DW_PIX_PER_STEP + (tid >> 5);
+        const bool in = pix < npix;
+        int n = 0, ho = 0, wo = 0;
+        if (in) {
+            const int p = (int)pix;
+            n = p / hw;
+            const int r = p - n * hw;
+            ho = r / g.Wo;
+            wo = r - ho * g.Wo;
+        }
+        float acc = 0.0f;
+        if (in && live) {
+            const int h0 = ho * g.sh - g.ph, w0 = wo * g.sw - g.pw;
+#pragma unroll
+            for (int t = 0; t < T::CAP; ++t) {
+                if (!T::GEN || t < kk) {
+                    const int i = t / kw, j = t - i * kw;
+                    const int hi = h0 + i * g.dh, wi = w0 + j * g.dw;
+                    if (hi >= 0 && hi < g.H && wi >= 0 && wi < g.W) {
+                        float v;
+                        if (BITS_IN) {
+                            const uint32_t word = xb[(((int64_t)n * g.H + hi) * g.W + wi) * ldx + (c >> 5)];
+                            v = ((word >> (c & 31)) & 1u) ? -1.0f : 1.0f;
+                        } else {
+                            v = xf[n * xs.n + c * xs.c + hi * xs.h + wi * xs.w];
+                        }
+                        acc = acc + v * wq[t];
+                    }
+                }
+            }
+            if (bias) acc = acc + b;
+        }
+        if (o.y) {                                   // uniform over the launch
+            if (in && live) o.y[n * ys.n + co * ys.c + ho * ys.h + wo * ys.w] = acc;
+            continue;
+        }
+        // two roundings (the build has -ffp-contract=off), as in pool_affine_sign_pack_kernel; dead lanes vote 0
+        const int neg = (in && live) ? (int)qt_neg_bit(acc * al + be) : 0;
+        const unsigned long long votes = __ballot(neg);
+        if (lane != 0 || !in) continue;
+        dw_store_word(o, g, wd, pix, n, ho, wo, (uint32_t)(votes >> (tid & 32)));
+    }
+    if (!o.y) dw_zero_border(o, g, tid);
+}
+
+// fp32 NCHW input -> planes.  The map above would read such an input with one image plane between neighbouring lanes, so here
+// the 64 lanes of a wave run along 64 consecutive output pixels (rows of x, coalesced) and a wave walks 8 of the workgroup's 32
+// channels with wave-uniform taps, bias, alpha and beta.  The votes of (channel, 64 pixels) go through 256 bytes of LDS and come
+// back as (pixel, 32 channels) words, which wave 0 stores as above.  Same arithmetic, same bits.
+template <int KH, int KW>
+__global__ __launch_bounds__(DW_THREADS) void dw_planes_nchw_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                    const float* __restrict__ bias, const float* __restrict__ alpha,
+                                                                    const float* __restrict__ beta, DwPlaneOut o, DwGeom g,
+                                                                    DwStrides xs, int units, int splits, int kind) {
+    using T = DwTaps<KH, KW>;
+    __shared__ unsigned long long votes[32];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wd = (int)(blockIdx.x / splits);
+    const int split = (int)(blockIdx.x - (unsigned)wd * splits);
+    const int kw = T::kw(g), kk = T::kk(g);
+    const int hw = g.Ho * g.Wo;
+    const int64_t npix = (int64_t)g.N * hw;
+    for (int u = split; u < units; u += splits) {
+        const int64_t pix = (int64_t)u * 64 + lane;
+        const bool in = pix < npix;
+        int n = 0, ho = 0, wo = 0;
+        if (in) {
+            const int p = (int)pix;
+            n = p / hw;
+            const int r = p - n * hw;
+            ho = r / g.Wo;
+            wo = r - ho * g.Wo;
+        }
+        const int h0 = ho * g.sh - g.ph, w0 = wo * g.sw - g.pw;
+        for (int q = 0; q < 8; ++q) {
+            const int cl = wave * 8 + q;
+            const int64_t co = (int64_t)wd * 32 + cl;             // wave-uniform
+            int neg = 0;
+            if (co < g.Cout && in) {
+                const float* xp = x + n * xs.n + (co / g.m) * xs.c;
+                const float* wp = w + co * kk;
+                float acc = 0.0f;
+                auto tap = [&](int t) {
+                    const int i = t / kw, j = t - i * kw;
+                    const int hi = h0 + i * g.dh, wi = w0 + j * g.dw;
+                    if (hi >= 0 && hi < g.H && wi >= 0 && wi < g.W) acc = acc + xp[hi * xs.h + wi * xs.w] * dw_quant(kind, wp[t]);
+                };
+                if (T::GEN) {               // the taps are read where they are used (wave-uniform): nothing to keep in registers
+                    for (int t = 0; t < kk; ++t) tap(t);
+                } else {
+#pragma unroll
+                    for (int t = 0; t < T::CAP; ++t) tap(t);
+                }
+                if (bias) acc = acc + bias[co];
+                neg = (int)qt_neg_bit(acc * alpha[co] + beta[co]);      // two roundings
+            }
+            const unsigned long long v = __ballot(neg);
+            if (lane == 0) votes[cl] = v;
+        }
+        __syncthreads();
+        if (tid < 64 && in) {
+            uint32_t word = 0;
+#pragma unroll
+            for (int cc = 0; cc < 32; ++cc) word |= (uint32_t)((votes[cc] >> lane) & 1ull) << cc;
+            dw_store_word(o, g, wd, pix, n, ho, wo, word);
+        }
+        __syncthreads();
+    }
+    dw_zero_border(o, g, tid);
+}
+
+inline int64_t dw_packed_ld(int64_t K) {
+    const int64_t kw = (K + 31) / 32;
+    return std::max<int64_t>(4, (kw + 3) / 4 * 4);
+}
+inline int64_t dw_pixel_ld_nib(int64_t K) { return std::max<int64_t>(4, ((K + 7) / 8 + 3) / 4 * 4); }
+bool dw_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+constexpr int DW_MAX_HALO = 64;
+
+// the shared body of the two plane entries: exactly one of (x, x_plane) is given; o.y, or at least one of o.sign / o.nib
+int dw_planes_launch(const float* x, const uint32_t* x_plane, int64_t ldx, const float* w, const float* bias, const float* alpha,
+                     const float* beta, DwPlaneOut o, int64_t halo_h, int64_t halo_w, int64_t N, int64_t C, int64_t m, int64_t H,
+                     int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, DwStrides xs, DwStrides ys, int kind,
+                     qt_stream_t stream) {
+    DwGeom g{};
+    bool empty;
+    if (halo_h < 0 || halo_w < 0) return QT_ERR_INVALID_ARG;
+    const int rc = dw_geometry(N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
+    if (rc != QT_OK || empty) return rc;
+    if (halo_h > DW_MAX_HALO || halo_w > DW_MAX_HALO) return QT_ERR_UNSUPPORTED;
+    if (o.nib && (double)N * (double)(g.Ho + 2 * halo_h) * (double)(g.Wo + 2 * halo_w) >= (double)DW_MAX_ELEMS) return QT_ERR_UNSUPPORTED;
+    if (kind != QT_DW_RAW && kind != QT_DW_SIGN && kind != QT_DW_TERNARY) return QT_ERR_INVALID_ARG;
+    if ((x == nullptr) == (x_plane == nullptr) || !w) return QT_ERR_INVALID_ARG;
+    if (o.y) {
+        if (dw_layout(N, g.Cout, g.Ho, g.Wo, ys) < 0) return QT_ERR_INVALID_ARG;
+    } else {
+        if ((!o.sign && !o.nib) || !alpha || !beta) return QT_ERR_INVALID_ARG;
+        if (o.sign && o.ldb < dw_packed_ld(g.Cout)) return QT_ERR_INVALID_ARG;
+        if (o.nib && o.ldn < dw_pixel_ld_nib(g.Cout)) return QT_ERR_INVALID_ARG;
+    }
+    if (x && dw_layout(N, C, H, W, xs) < 0) return QT_ERR_INVALID_ARG;
+    if (x_plane && ldx < dw_packed_ld(C)) return QT_ERR_INVALID_ARG;
+    if (!dw_aligned4(x) || !dw_aligned4(x_plane) || !dw_aligned4(w) || !dw_aligned4(bias) || !dw_aligned4(alpha) || !dw_aligned4(beta) ||
+        !dw_aligned4(o.y) || !dw_aligned4(o.sign))
+        return QT_ERR_ALIGNMENT;
+    if (o.nib && ((o.ldn & 3) || !dw_aligned16(o.nib))) return QT_ERR_ALIGNMENT;
+    o.hy = (int)halo_h;
+    o.hx = (int)halo_w;
+    const int64_t npix = (int64_t)g.N * g.Ho * g.Wo;
+    const int64_t nw = (g.Cout + 31) / 32;
+    const bool nchw = x && !o.y && dw_layout(N, C, H, W, xs) == 0;      // lanes along the pixels, 64 per step
+    const int per_step = nchw ? 64 : DW_PIX_PER_STEP;
+    const int units = (int)((npix + per_step - 1) / per_step);
+    int64_t sp = (DW_TARGET_STREAM + nw - 1) / nw;
+    if (sp > units) sp = units;
+    const int splits = (int)(sp < 1 ? 1 : sp);
+    const unsigned grid = (unsigned)(nw * splits);
+    hipStream_t s = (hipStream_t)stream;
+    if (nchw) {
+        DW_DISPATCH(dw_planes_nchw_kernel, g, x, w, bias, alpha, beta, o, g, xs, units, splits, kind);
+        return qt_check_launch();
+    }
+    const void* xv = x ? static_cast<const void*>(x) : static_cast<const void*>(x_plane);
+#define DW_PLANES_ARGS xv, ldx, w, bias, alpha, beta, o, g, xs, ys, units, splits, kind
+    if (x) DW_DISPATCH_B(dw_planes_kernel, false, g, DW_PLANES_ARGS);
+    else DW_DISPATCH_B(dw_planes_kernel, true, g, DW_PLANES_ARGS);
+#undef DW_PLANES_ARGS
+    return qt_check_launch();
+}
 
 }  // namespace
 
@@ -428,4 +706,32 @@ extern "C" int qt_dwconv2d_grad_weight_f32(const float* go, const float* x, cons
     dw_grad_weight_combine_kernel<<<qt_stream_grid((g.Cout * (kk + 1) + DW_THREADS - 1) / DW_THREADS), DW_THREADS, 0, s>>>(
         work, w, gw, gbias, g.Cout, kk, mp.splits, ste_threshold);
     return qt_check_launch();
+}
+
+extern "C" int qt_dwconv2d_sign(const float* x, const uint32_t* x_plane, int64_t ldx, const float* w, const float* bias,
+                                const float* alpha, const float* beta, uint32_t* sign_plane, int64_t ldb, uint32_t* nib_plane,
+                                int64_t ldn, int64_t out_halo_h, int64_t out_halo_w, int64_t N, int64_t C, int64_t m, int64_t H,
+                                int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t xs_n, int64_t xs_c,
+                                int64_t xs_h, int64_t xs_w, int kind, qt_stream_t stream) {
+    DwPlaneOut o{};
+    o.sign = sign_plane;
+    o.ldb = ldb;
+    o.nib = nib_plane;
+    o.ldn = ldn;
+    return dw_planes_launch(x, x_plane, ldx, w, bias, alpha, beta, o, out_halo_h, out_halo_w, N, C, m, H, W, kh, kw, sh, sw, ph, pw,
+                            dh, dw, DwStrides{xs_n, xs_c, xs_h, xs_w}, DwStrides{0, 0, 0, 0}, kind, stream);
+}
+
+extern "C" int qt_dwconv2d_bits_f32(const uint32_t* x_plane, int64_t ldx, const float* w, const float* bias, float* y, int64_t N,
+                                    int64_t C, int64_t m, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                                    int dw, int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, int kind, qt_stream_t stream) {
+    DwGeom g{};
+    bool empty;
+    const int rc = dw_geometry(N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
+    if (rc != QT_OK || empty) return rc;
+    if (!x_plane || !y) return QT_ERR_INVALID_ARG;
+    DwPlaneOut o{};
+    o.y = y;
+    return dw_planes_launch(nullptr, x_plane, ldx, w, bias, nullptr, nullptr, o, 0, 0, N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw,
+                            DwStrides{0, 0, 0, 0}, DwStrides{ys_n, ys_c, ys_h, ys_w}, kind, stream);
 }

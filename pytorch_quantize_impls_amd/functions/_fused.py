@@ -890,6 +890,21 @@ def packed_conv2d(layer, act, kind: str, epi=None):
     return y2.view(N, Ho, Wo, layer.weight.shape[0]).permute(0, 3, 1, 2)
 
 
+def packed_depthwise_conv2d(layer, act):
+    """Eval-mode BinConv2d / TerConv2d with ``groups == in_channels`` on a PackedActivation (NHWC bit planes): the fp32
+    [N, C * m, Ho, Wo] result in NCHW storage, bias added, from one launch on the planes (ops.depthwise_conv2d_from_bits) — what a
+    deferred depthwise conv whose input exists only as planes materialises to.  The stored eval image is multiplied as it is."""
+    if layer.training:
+        raise RuntimeError("PackedActivation inputs are an inference feature: call .eval() first")
+    if act.planes is None:
+        raise ValueError("a depthwise conv reads bit planes; this activation was produced as another conv's nibble operand")
+    if (layer.padding_mode != "zeros" or len(act.shape) != 4
+            or not ops.depthwise_applicable(act.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups)):
+        raise ValueError("packed depthwise conv needs groups == in_channels, numeric zero padding and a shape inside the kernels' limits")
+    return ops.depthwise_conv2d_from_bits(act.planes, act.shape, layer.weight.detach(), layer.bias, layer.stride, layer.padding,
+                                          layer.dilation, kind="raw")
+
+
 def packed_xnor_conv2d(layer, act, epi=None):
     """Eval-mode XNORConv2d on a PackedActivation: the per-tap scaled fp4 conv (ops.conv2d_nib_taps) on the activation's nibble
     plane — the producer's own (zero halo = this conv's padding, un-padded kernel) when its pixel stride is whole 32-byte taps,

@@ -729,6 +729,84 @@ class FusedConvPoolBnSign(torch.nn.Module):
         return out
 
 
+class FusedDepthwiseBnSign(torch.nn.Module):
+    """Depthwise BinConv2d / TerConv2d (``groups == in_channels``, eval) + [MaxPool2d(k, s)] + eval BatchNorm2d + [Hardtanh] +
+    BinaryConnect(det) -> PackedActivation: the depthwise sibling of ``FusedConvPoolBnSign``.  ONE launch (qt_dwconv2d_sign) reads the
+    input — an fp32 device tensor, or the bit planes of a PackedActivation — computes the conv in the pinned fp32 order of
+    ``ops.depthwise_conv2d`` and writes the bit [y * alpha + beta < 0] as bit planes or, with ``out_nib_halo`` set, as the consuming
+    conv's nibble pixel plane with its padding as a zero border.  A pool between conv and BatchNorm runs on the un-pooled bits."""
+
+    def __init__(self, conv, bn, pool=None, flatten_hwc=False, fold=None):
+        super().__init__()
+        from .binary_layers import BinConv2d
+        from .terner_layers import TerConv2d
+        if not isinstance(conv, (BinConv2d, TerConv2d)):
+            raise ValueError("FusedDepthwiseBnSign fuses depthwise BinConv2d / TerConv2d only")
+        if conv.groups != conv.in_channels or conv.groups <= 1 or conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+            raise ValueError("only groups == in_channels > 1, zero-padded convs with numeric padding can be fused")
+        kh, kw = conv.kernel_size
+        dh, dw = ops._pairs(conv.dilation)
+        fits = (1, conv.in_channels, dh * (kh - 1) + 1, dw * (kw - 1) + 1)       # the smallest image the kernel fits
+        if not ops.depthwise_applicable(fits, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups):
+            raise ValueError("a depthwise conv outside the limits of the HIP kernels (ops.depthwise_applicable)")
+        if not isinstance(bn, torch.nn.BatchNorm2d) or bn.num_features != conv.out_channels:
+            raise ValueError("BatchNorm2d over the conv's output channels expected")
+        self._pool = FusedPoolBnSign(bn, pool, fold=fold)           # validates the pooling geometry, owns the fold cache
+        self.fold = self._pool.fold
+        self.conv, self.bn = conv, bn
+        self.flatten_hwc = flatten_hwc
+        self._neg_alpha = None
+        self.out_nib_halo = None        # see FusedConvPoolBnSign.out_nib_halo
+
+    def refold(self):
+        self._pool.refold()
+        self._neg_alpha = None
+
+    def forward(self, x):
+        if self.bn.training or self.conv.training:
+            raise RuntimeError("FusedDepthwiseBnSign is an inference module: call .eval() first")
+        conv, fp = self.conv, self._pool
+        x = lazy.resolve(x)
+        if isinstance(x, packed.PackedActivation):
+            if x.planes is None:
+                raise ValueError("a depthwise block reads bit planes; its producer was linked to hand over a nibble operand")
+            src, shape, cl = x.planes, x.shape, _out_channels_last(x)
+        else:
+            if not (isinstance(x, torch.Tensor) and x.is_cuda):
+                raise TypeError("FusedDepthwiseBnSign runs on a HIP device only (use the un-fused modules on CPU)")
+            src, shape, cl = x, tuple(x.shape), ops._dw_channels_last(x)          # the depthwise result takes x's layout
+        if len(shape) != 4 or not ops.depthwise_applicable(shape, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups):
+            raise ValueError(f"not a depthwise conv the HIP kernels take: input {tuple(shape)}")
+        if not conv._eval_on_grid():
+            raise ValueError("the eval-mode weight is off the quantiser's grid")
+        dev = conv.weight.device
+        N, _, H, W = (int(v) for v in shape)
+        Ho, Wo = ops.conv_out_hw(H, W, conv.kernel_size[0], conv.kernel_size[1], conv.stride, conv.padding, conv.dilation)
+        prev = fp._folded
+        like = None
+        if self.fold == "device":
+            # the tensor the module graph would hand to F.batch_norm: this conv's output, pooled
+            like = ((N, conv.out_channels, (Ho - fp.pool_k) // fp.pool_s + 1, (Wo - fp.pool_k) // fp.pool_s + 1), cl)
+        alpha, beta = _folded_for(fp, "_folded", self.bn, dev, self.fold, like)
+        if fp._folded is not prev or self._neg_alpha is None:      # BatchNorm changed (or first call): derived data too
+            self._neg_alpha = ops.neg_alpha_words(alpha)
+        pooled = fp.pool_k != 1 or fp.pool_s != 1
+        nib_out = self.out_nib_halo is not None and not self.flatten_hwc
+        Cout = conv.out_channels
+        args = (src, conv.weight.detach(), conv.bias, alpha, beta, conv.stride, conv.padding, conv.dilation)
+        if nib_out and not pooled:
+            nib, _ = ops.depthwise_conv2d_sign(*args, kind="raw", shape=shape, out_halo=self.out_nib_halo)
+            return packed.PackedActivation(None, (N, Cout, Ho, Wo), nib=nib, halo=self.out_nib_halo)
+        planes, _ = ops.depthwise_conv2d_sign(*args, kind="raw", shape=shape)
+        if pooled and nib_out:
+            nib, (Ho, Wo) = ops.pool_bits_nib(planes, N, Ho, Wo, fp.pool_k, fp.pool_s, self._neg_alpha, self.out_nib_halo)
+            return packed.PackedActivation(None, (N, Cout, Ho, Wo), nib=nib, halo=self.out_nib_halo)
+        if pooled:
+            planes, (Ho, Wo) = ops.pool_bits(planes, N, Ho, Wo, fp.pool_k, fp.pool_s, self._neg_alpha)
+        act = packed.PackedActivation(planes, (N, Cout, Ho, Wo))
+        return act.flatten_hwc() if self.flatten_hwc else act
+
+
 #: real-valued 3x3 / stride-1 / padding-1 first layers of fused stacks run in the 2x2 output-blocked form
 D2S_FIRST_LAYER = True
 #: real-valued 3x3 / stride-1 / padding-1 first layers with <= 5 channels run on the direct kernel (bf16 triple planes);
@@ -964,7 +1042,8 @@ def fuse_sequential(seq: torch.nn.Sequential, fuse_conv: bool = False, packed_po
     """New nn.Sequential where every [MaxPool2d?, BatchNorm, Hardtanh?, BinaryConnect(det)] run is
     replaced by one FusedPoolBnSign (sharing the original BatchNorm's parameters).  With ``fuse_conv`` a
     BinConv2d / TerConv2d directly in front of such a run joins it (FusedConvPoolBnSign: the conv emits
-    threshold bits, no fp32 activation is written at all).  With ``packed_pool`` a MaxPool2d that directly follows a
+    threshold bits, no fp32 activation is written at all; a depthwise one, ``groups == in_channels``, becomes a
+    FusedDepthwiseBnSign).  With ``packed_pool`` a MaxPool2d that directly follows a
     fused block (pool AFTER the sign, VGG style) becomes a PackedMaxPool on the bit planes.  ``fold``: the BatchNorm
     fold of the fused blocks ("reference" | "device", module docstring; default DEFAULT_FOLD)."""
     from .binary_layers import BinConv2d
@@ -990,8 +1069,11 @@ def fuse_sequential(seq: torch.nn.Sequential, fuse_conv: bool = False, packed_po
                 j2 += 1
             if j2 < len(mods) and _is_det_binary_connect(mods[j2]):
                 try:
-                    out.append(FusedConvPoolBnSign(conv, bn, pool, fold=fold) if conv is not None
-                               else FusedPoolBnSign(bn, pool, pre_relu=pre_relu, fold=fold))
+                    if conv is not None and conv.groups == conv.in_channels > 1 and not isinstance(conv, XNORConv2d):
+                        out.append(FusedDepthwiseBnSign(conv, bn, pool, fold=fold))
+                    else:
+                        out.append(FusedConvPoolBnSign(conv, bn, pool, fold=fold) if conv is not None
+                                   else FusedPoolBnSign(bn, pool, pre_relu=pre_relu, fold=fold))
                     i = j2 + 1
                     if packed_pool and i < len(mods) and isinstance(mods[i], torch.nn.MaxPool2d) and (not bn.affine or bn.weight.dim() == 1) \
                             and isinstance(bn, torch.nn.BatchNorm2d):
@@ -1015,10 +1097,11 @@ def fuse_sequential(seq: torch.nn.Sequential, fuse_conv: bool = False, packed_po
 def link_nib_planes(mods) -> None:
     """Where a fused conv block directly consumes the output of another fused block (or of a PackedMaxPool), let the
     producer write the consumer's operand — the fp4 nibble pixel plane with the consumer's padding as a zero border —
-    instead of bit planes (saves the consumer's qt_bits_to_nib_pad pass: 10 % of the fused VGG-16 forward)."""
+    instead of bit planes (saves the consumer's qt_bits_to_nib_pad pass: 10 % of the fused VGG-16 forward).  A depthwise block
+    (FusedDepthwiseBnSign) is such a producer; as a consumer it reads bit planes, so its producer stays on them."""
     from ..functions import _fused
     for a, b in zip(mods, mods[1:]):
-        if isinstance(a, (FusedConvPoolBnSign, PackedMaxPool)):
+        if isinstance(a, (FusedConvPoolBnSign, PackedMaxPool, FusedDepthwiseBnSign)):
             a.out_nib_halo = None
             if (_fused._cfg("PAD_PLANES") and isinstance(b, FusedConvPoolBnSign) and not getattr(a, "flatten_hwc", False)):
                 a.out_nib_halo = tuple(int(v) for v in ops._pairs(b.conv.padding))

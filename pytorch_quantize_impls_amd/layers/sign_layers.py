@@ -214,6 +214,8 @@ class _SignConv2d(EvalSwapMixin, torch.nn.Conv2d, QLayer):
     def _forward_impl(self, input):
         kind = self.kind
         if isinstance(input, _PackedActivation):
+            if self.groups != 1:            # groups == in_channels on planes: a deferred depthwise conv that materialises
+                return _fused.packed_depthwise_conv2d(self, input)
             return _fused.packed_conv2d(self, input, kind)
         if _fused.half_route(input, self.weight):
             y = self._half_forward(input)         # bf16 / fp16 activation that is (treated as) +-1: the packed routes

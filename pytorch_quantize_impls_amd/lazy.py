@@ -35,8 +35,13 @@ BatchNorm2d -> [ReLU] -> nnQuant(lin | log) -> [MaxPool2d] -> [flatten] -> Quant
 arithmetic), ReLU and the quantiser in the conv's epilogue, which writes the next layer's one-term bf16 plane
 (``layers.fused.FusedLogLinConvBnQuant`` / ``LevelMaxPool`` / ``FusedBnLogLinQuant``).
 
-Nothing is deferred in training mode, with autograd enabled, on CPU tensors, for non-fp32 dtypes, grouped convs or
-non-zero padding modes.  ``lazy.ENABLED = False`` (or the ``eager()`` context manager) switches the mechanism off;
+Depthwise BinConv2d / TerConv2d (``groups == in_channels``) join the sign chain (``DEFER_DEPTHWISE``, on by default;
+``depthwise_deferred(False)`` switches it off): the layer takes its producer's bit planes and runs as ``layers.fused.FusedDepthwiseBnSign`` — one launch from planes to
+the next layer's planes or nibble operand — so a binarised pointwise / depthwise stack keeps every chain fused; a deferred
+depthwise conv on planes that must materialise computes its fp32 value from the planes (``_fused.packed_depthwise_conv2d``).
+
+Nothing is deferred in training mode, with autograd enabled, on CPU tensors, for non-fp32 dtypes, grouped convs other than
+those depthwise ones or non-zero padding modes.  ``lazy.ENABLED = False`` (or the ``eager()`` context manager) switches the mechanism off;
 ``lazy.STATS`` counts what happened (tests assert on it).
 """
 from __future__ import annotations
@@ -73,6 +78,12 @@ DEFER_DENSE = True
 #: layer's one-term bf16 plane (layers.fused.FusedLogLinConvBnQuant): no fp32 activation between two quantised layers.  Opt-in:
 #: False = the Lin / Log layers never defer and run call for call as without this mechanism (``levels_deferred()`` switches it on).
 DEFER_LEVELS = False
+#: depthwise BinConv2d / TerConv2d (``groups == in_channels``, shapes ``ops.depthwise_applicable`` takes) join the sign chain: the
+#: layer defers, asks its producer for bit planes and runs as ``layers.fused.FusedDepthwiseBnSign`` — one launch from planes (or a
+#: real-valued fp32 tensor) to the next layer's planes (measured: DESIGN.md "Depthwise convs").  False = every call runs exactly
+#: as without this mechanism — the depthwise layer returns fp32 and the chain in front of it materialises
+#: (``depthwise_deferred(False)`` switches it off for a block).
+DEFER_DEPTHWISE = True
 #: "deferred" convs that returned a LazyActivation, "fused" chains executed as fused blocks, "materialised" lazies that
 #: had to produce their fp32 value, "fallback:<func>" the functions that forced it
 STATS = collections.Counter()
@@ -135,6 +146,17 @@ def levels_deferred(on: bool = True):
         yield
     finally:
         DEFER_LEVELS = prev
+
+
+@contextlib.contextmanager
+def depthwise_deferred(on: bool = True):
+    """Defer depthwise sign convs (``DEFER_DEPTHWISE``) inside the block; process-wide, restores the previous setting."""
+    global DEFER_DEPTHWISE
+    prev, DEFER_DEPTHWISE = DEFER_DEPTHWISE, bool(on)
+    try:
+        yield
+    finally:
+        DEFER_DEPTHWISE = prev
 
 
 class _Node:
@@ -472,7 +494,7 @@ class _BnView1d(torch.nn.BatchNorm1d):
         _share_bn_tensors(self, rm, rv, w, b, eps)
 
 
-_BLOCKS = weakref.WeakKeyDictionary()      # conv layer -> OrderedDict(key -> FusedConvPoolBnSign)
+_BLOCKS = weakref.WeakKeyDictionary()      # conv layer -> OrderedDict(key -> FusedConvPoolBnSign | FusedDepthwiseBnSign | ...)
 _POOLS = {}
 _MAX_BLOCKS_PER_LAYER = 8
 
@@ -487,7 +509,8 @@ def _fused_block(layer, bn, pool, flatten: bool, halo):
     blk = per.get(key)
     if blk is None:
         pm = torch.nn.MaxPool2d(pool[0], pool[1]) if pool is not None else None
-        blk = fused.FusedConvPoolBnSign(layer, _BnView(rm, rv, w, b, eps), pm, flatten_hwc=flatten, fold="device")
+        make = fused.FusedDepthwiseBnSign if layer.groups != 1 else fused.FusedConvPoolBnSign
+        blk = make(layer, _BnView(rm, rv, w, b, eps), pm, flatten_hwc=flatten, fold="device")
         blk.out_nib_halo = halo
         per[key] = blk
         while len(per) > _MAX_BLOCKS_PER_LAYER:
@@ -1042,10 +1065,16 @@ def _untracked(*tensors) -> bool:
 
 
 def _conv_can_defer(layer, input) -> bool:
-    if layer.training or not _no_autograd(layer) or layer.groups != 1 or layer.padding_mode != "zeros" \
+    if layer.training or not _no_autograd(layer) or layer.padding_mode != "zeros" \
             or isinstance(layer.padding, str) or not getattr(layer, "_qt_can_defer", True):
         return False
     w = layer.weight
+    if layer.groups != 1:
+        # depthwise only (DEFER_DEPTHWISE), inside the limits of the depthwise kernels; every other grouped conv runs eagerly
+        if not (DEFER_DEPTHWISE and layer.groups == layer.in_channels and getattr(layer, "kind", None) in ("binary", "ternary")
+                and ops.depthwise_applicable(tuple(getattr(input, "shape", ())), tuple(w.shape), layer.stride, layer.padding,
+                                             layer.dilation, layer.groups)):
+            return False
     if not w.is_cuda or w.dtype != torch.float32:
         return False
     if isinstance(input, packed.PackedActivation):
@@ -1067,7 +1096,10 @@ def conv_forward(layer, input, kind: str):
         n = input._qt
         if n.signed and not n.flat and _conv_can_defer(layer, _ShapeOnly(n.shape)):
             from .functions import _fused
-            act = n.force(tuple(int(v) for v in ops._pairs(layer.padding)) if _fused._cfg("PAD_PLANES") else None)
+            if layer.groups != 1:
+                act = n.force(None)         # a depthwise consumer reads bit planes, never a halo plane
+            else:
+                act = n.force(tuple(int(v) for v in ops._pairs(layer.padding)) if _fused._cfg("PAD_PLANES") else None)
         input = act if act is not None else n.materialise()
     if enabled() and _conv_can_defer(layer, input):
         N, C, H, W = (int(v) for v in input.shape)

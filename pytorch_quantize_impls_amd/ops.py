@@ -4173,6 +4173,99 @@ def depthwise_conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
     return y
 
 
+def _dw_plane_input(planes: BitPlanes, shape):
+    """``planes`` checked as the sign-only NHWC pixel plane of a +-1 activation of logical ``shape`` (N, C, H, W)."""
+    if not isinstance(planes, BitPlanes):
+        raise TypeError(f"input: expected a device tensor or BitPlanes, got {type(planes)}")
+    if shape is None or len(shape) != 4:
+        raise ValueError("a BitPlanes input needs the logical (N, C, H, W) shape")
+    N, C, H, W = (int(v) for v in shape)
+    _require(planes.sign, "input planes", torch.int32)
+    if planes.mask is not None or planes.rows != N * H * W or planes.K != C or tuple(planes.sign.shape) != (N * H * W, planes.ld) \
+            or not planes.sign.is_contiguous() or planes.ld < packed_ld(C):
+        raise ValueError(f"input: expected the sign-only NHWC pixel plane of an {(N, C, H, W)} activation")
+    return (N, C, H, W)
+
+
+def _dw_plane_out(out: Optional[torch.Tensor], rows: int, ld: int, dev, name: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty((rows, ld), dtype=torch.int32, device=dev)
+    _require(out, name, torch.int32)
+    if out.dim() != 2 or int(out.shape[0]) != rows or int(out.shape[1]) < ld or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"{name}: expected a contiguous int32 tensor [{rows}, >= {ld}] on {dev}, got {tuple(out.shape)} on {out.device}")
+    return out
+
+
+def depthwise_conv2d_sign(x, weight: torch.Tensor, bias: Optional[torch.Tensor], alpha: torch.Tensor, beta: torch.Tensor, stride=1,
+                          padding=0, dilation=1, kind: str = "raw", shape=None, out_halo=None, with_bits: bool = False,
+                          out_sign: Optional[torch.Tensor] = None, out_nib: Optional[torch.Tensor] = None):
+    """The threshold bits [depthwise_conv2d(x) * alpha + beta < 0] (two fp32 roundings; a tie gives 0) written as planes by the one
+    launch that computes the conv (qt_dwconv2d_sign) — no fp32 activation exists.  ``x``: the fp32 device tensor [N, C, H, W] (NCHW
+    or channels-last), or the ``BitPlanes`` (sign-only NHWC pixel plane) of a +-1 activation with its logical ``shape``
+    (N, C, H, W); both give the bits of the pinned fp32 arithmetic of ``depthwise_conv2d``.  ``alpha`` / ``beta``: fp32 [C * m].
+    Returns ``(planes, (Ho, Wo))``: ``BitPlanes`` (rows = N*Ho*Wo, K = C*m) when ``out_halo`` is None, else the ``NibPlanes`` of
+    the consumer's operand — nibble pixel plane with a zero border of ``out_halo`` = (hy, hx) pixels, every word written — or,
+    ``with_bits``, the pair ``(BitPlanes, NibPlanes)`` from the same launch.  ``out_sign`` / ``out_nib``: existing contiguous
+    int32 [rows, ld] tensors the planes are written into (no prior content needed)."""
+    if isinstance(x, torch.Tensor):
+        x = _dw_operand(x, "input")
+        x_shape, dev = tuple(x.shape), x.device
+    else:
+        x_shape, dev = _dw_plane_input(x, shape), x.device
+    w, geom, y_shape = _dw_geometry(x_shape, weight, stride, padding, dilation)
+    if w.device != dev:
+        raise ValueError("input and weight are on different devices")
+    N, Cout, Ho, Wo = y_shape
+    bias = _check_bias(bias, Cout, dev)
+    alpha, beta, _ = epilogue_affine((alpha, beta), Cout, dev)
+    if alpha is None or beta is None:
+        raise TypeError("alpha and beta: expected fp32 device vectors")
+    hy, hx = (0, 0) if out_halo is None else (int(v) for v in _pairs(out_halo))
+    if hy < 0 or hx < 0:
+        raise ValueError("out_halo must not be negative")
+    bits = nib = None
+    if out_halo is None or with_bits:
+        bits = BitPlanes(sign=_dw_plane_out(out_sign, N * Ho * Wo, packed_ld(Cout), dev, "out_sign"), rows=N * Ho * Wo, K=Cout)
+    if out_halo is not None:
+        rows = N * (Ho + 2 * hy) * (Wo + 2 * hx)
+        nib = NibPlanes(words=_dw_plane_out(out_nib, rows, pixel_ld_nib(Cout), dev, "out_nib"), rows=rows, K=Cout)
+    if N * Cout * Ho * Wo > 0:
+        is_t = isinstance(x, torch.Tensor)
+        xs = _dw_strides(x_shape, _dw_channels_last(x)) if is_t else (0, 0, 0, 0)
+        with _on(dev):
+            _lib.call("qt_dwconv2d_sign", _p(x) if is_t else None, None if is_t else _p(x.sign), 0 if is_t else int(x.ld), _p(w),
+                      _p(bias), _p(alpha), _p(beta), _p(bits.sign) if bits is not None else None, bits.ld if bits is not None else 0,
+                      _p(nib.words) if nib is not None else None, nib.ld if nib is not None else 0, hy, hx, *geom, *xs,
+                      DW_KINDS[kind], _stream(dev))
+    out = bits if nib is None else ((bits, nib) if bits is not None else nib)
+    return out, (Ho, Wo)
+
+
+def depthwise_conv2d_from_bits(planes: BitPlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1,
+                               padding=0, dilation=1, kind: str = "raw", channels_last: bool = False,
+                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``depthwise_conv2d`` of the +-1 activation that exists only as ``planes`` (sign-only NHWC pixel plane, logical ``shape``
+    (N, C, H, W)): the fp32 result, bit for bit that of the fp32 +-1 image, in NCHW or ``channels_last`` storage or written into
+    ``out`` (qt_dwconv2d_bits_f32, one launch)."""
+    x_shape = _dw_plane_input(planes, shape)
+    dev = planes.device
+    w, geom, y_shape = _dw_geometry(x_shape, weight, stride, padding, dilation)
+    if w.device != dev:
+        raise ValueError("input and weight are on different devices")
+    bias = _check_bias(bias, y_shape[1], dev)
+    if out is None:
+        y = torch.empty(y_shape, dtype=torch.float32, device=dev,
+                        memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    else:
+        y = _dw_result(out, y_shape, w, "out")
+    if y.numel() == 0:
+        return y
+    with _on(dev):
+        _lib.call("qt_dwconv2d_bits_f32", _p(planes.sign), int(planes.ld), _p(w), _p(bias), _p(y), *geom,
+                  *_dw_strides(y.shape, _dw_channels_last(y)), DW_KINDS[kind], _stream(dev))
+    return y
+
+
 def depthwise_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_output: torch.Tensor, stride=1, padding=0, dilation=1,
                                 kind: str = "raw", channels_last: Optional[bool] = None,
                                 out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -1,0 +1,191 @@
+#!/usr/bin/env python
+"""The depthwise block pair of MobileNet-v1 at batch 256, un-modified modules, with and without the depthwise layer inside the fused
+inference chain: one JSON line and a markdown table.
+
+    dw 3x3 (padding 1) -> BatchNorm -> Hardtanh -> BinaryConnect -> pw 1x1 -> BatchNorm -> Hardtanh -> BinaryConnect
+
+on a +-1 fp32 input, eval mode, ``torch.no_grad()``, implicit hipGraphs off.  Two sides, the same modules and tensors:
+  deferred : ``lazy.depthwise_deferred(True)`` — the depthwise conv, its BatchNorm / Hardtanh / sign and the operand pack of the
+             pointwise conv are ONE launch (qt_dwconv2d_sign) that writes the pointwise conv's nibble plane;
+  eager    : ``lazy.depthwise_deferred(False)`` — how the pair runs without the switch: qt_dwconv2d_f32 writes fp32, BatchNorm,
+             Hardtanh and sign are three library passes, the pointwise conv packs the +-1 image again.
+Both sides end by asking the pair's result for the bit planes the next binarised layer would take (the pointwise chain runs fused
+on either side), and both are checked to give the same planes before anything is timed.
+
+Method (tools/bench_depthwise.py): every shape runs in a child process of its own under a time limit, nothing more is started after
+a child that fails or overruns; inside a child every side is warmed up, then the two sides take turns within each of ``--rounds``
+rounds; a round times ``steps`` forwards with the host clock around a run that ends in a device synchronise.  Reported per side:
+the median round and the range of the rounds.  ``bytes`` is what the depthwise part of the pair has to move on each side, from the
+shapes alone (|x| input, |y| depthwise output elements; the input is an fp32 tensor on both sides):
+  eager    : conv 4|x| + 4|y|, BatchNorm 8|y|, Hardtanh 8|y|, sign 8|y|, the consumer's pack 4|y|  =  4|x| + 32|y|
+  deferred : 4|x| + |y| / 2 (the nibble plane)
+``hbm_share`` = (bytes / 8 TB/s) / median time of the WHOLE pair on that side — the pointwise half is in the time and not in the
+bytes, so it is a lower bound of the depthwise part's own share.
+
+    python tools/bench_depthwise_chain.py [--rounds 9] [--out profiles/depthwise_chain_bench_line.json] [--docs]
+
+``--docs`` rewrites the table between the ``depthwise-chain-table`` markers of README.md and DESIGN.md.
+"""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+import time
+
+ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+sys.path.insert(0, ROOT)
+os.environ.setdefault("QT_AUTO_GRAPH", "0")
+
+BATCH = 256
+#: (channels, map, stride, pointwise output channels) of the depthwise / pointwise pairs of MobileNet-v1 at 224 x 224
+SHAPES = [(32, 112, 1, 64), (64, 112, 2, 128), (128, 56, 1, 128), (256, 28, 1, 256), (512, 14, 1, 512), (1024, 7, 1, 1024)]
+HBM_BYTES_PER_S = 8e12
+CHILD_LIMIT_S = 300
+STEPS = 20
+MARK = "depthwise-chain-table"
+
+
+def algorithmic_bytes(C, H, stride):
+    Ho = (H + 2 - 3) // stride + 1
+    x, y = BATCH * C * H * H, BATCH * C * Ho * Ho
+    return {"eager": 4 * x + 32 * y, "deferred": 4 * x + y // 2}
+
+
+def child(index, rounds):
+    import torch
+    import torch.nn as nn
+    from pytorch_quantize_impls_amd import _lib, lazy
+    from pytorch_quantize_impls_amd.functions import BinaryConnect
+    from pytorch_quantize_impls_amd.layers import BinConv2d
+
+    C, H, stride, Cpw = SHAPES[index]
+    dev = torch.device("cuda:0")
+    torch.manual_seed(index)
+    g = torch.Generator().manual_seed(index)
+
+    def run(c):
+        bn = nn.BatchNorm2d(c)
+        bn.running_mean.copy_(torch.randn(c, generator=g))
+        bn.running_var.copy_(torch.rand(c, generator=g) * 8 + 2)
+        gamma = torch.rand(c, generator=g) + 0.5
+        gamma[::3] *= -1
+        bn.weight.data.copy_(gamma)
+        bn.bias.data.copy_(torch.randn(c, generator=g) * 0.5)
+        return [bn, nn.Hardtanh(inplace=True), BinaryConnect()]
+
+    pair = nn.Sequential(BinConv2d(C, C, 3, stride=stride, padding=1, groups=C), *run(C), BinConv2d(C, Cpw, 1), *run(Cpw)).to(dev).eval()
+    pair[0].binary_input = pair[4].binary_input = True          # +-1 by construction: no side stops to ask the device
+    x = torch.where(torch.rand(BATCH, C, H, H, generator=g) < 0.5, -1.0, 1.0).to(dev)
+
+    def forward(on):
+        with torch.no_grad(), lazy.depthwise_deferred(on):
+            out = pair(x)
+            act = out._qt.force(None)          # the planes the next binarised layer would ask for
+            assert act is not None and act.planes is not None
+            return act.planes.sign
+
+    sides = {"deferred": lambda: forward(True), "eager": lambda: forward(False)}
+    calls = dict(_lib.call_counts)
+    a = sides["deferred"]()
+    used_on = {k: v - calls.get(k, 0) for k, v in _lib.call_counts.items() if v != calls.get(k, 0)}
+    calls = dict(_lib.call_counts)
+    b = sides["eager"]()
+    used_off = {k: v - calls.get(k, 0) for k, v in _lib.call_counts.items() if v != calls.get(k, 0)}
+    assert torch.equal(a, b), "the two sides disagree"
+    assert used_on.get("qt_dwconv2d_sign") == 1 and "qt_dwconv2d_f32" not in used_on, used_on
+    assert used_off.get("qt_dwconv2d_f32") == 1 and "qt_dwconv2d_sign" not in used_off, used_off
+
+    def run_us(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(STEPS):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6 / STEPS
+
+    for fn in sides.values():
+        for _ in range(3):
+            fn()
+    samples = {k: [] for k in sides}
+    for _ in range(rounds):
+        for k, fn in sides.items():
+            samples[k].append(run_us(fn))
+    nbytes = algorithmic_bytes(C, H, stride)
+    result = {"channels": C, "map": H, "stride": stride, "pointwise_out": Cpw, "bytes": nbytes,
+              "launches": {"deferred": used_on, "eager": used_off}}
+    for k, v in samples.items():
+        med = sorted(v)[len(v) // 2]
+        result[k] = {"median_us": round(med, 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1),
+                     "hbm_share": round(nbytes[k] / HBM_BYTES_PER_S / (med * 1e-6), 3)}
+    result["deferred_range_below_eager"] = result["deferred"]["max_us"] < result["eager"]["min_us"]
+    print(json.dumps(result))
+
+
+def table(shapes):
+    rows = ["| dw channels x map, stride | eager: median (range) us | deferred: median (range) us | eager MB, share of 8 TB/s | "
+            "deferred MB, share of 8 TB/s | deferred range below eager |",
+            "|---|---|---|---|---|---|"]
+    for s in shapes:
+        e, d = s["eager"], s["deferred"]
+        ok = "yes" if s["deferred_range_below_eager"] else "**no**"
+        rows.append(f"| {s['channels']} x {s['map']}², s{s['stride']} | {e['median_us']} ({e['min_us']}–{e['max_us']}) | "
+                    f"{d['median_us']} ({d['min_us']}–{d['max_us']}) | {s['bytes']['eager'] / 1e6:.1f}, {e['hbm_share']} | "
+                    f"{s['bytes']['deferred'] / 1e6:.1f}, {d['hbm_share']} | {ok} |")
+    return "\n".join(rows)
+
+
+def write_docs(text):
+    pat = re.compile(rf"(<!-- {MARK}:begin -->\n).*?(<!-- {MARK}:end -->)", re.S)
+    for name in ("README.md", "DESIGN.md"):
+        path = os.path.join(ROOT, name)
+        with open(path) as fh:
+            doc = fh.read()
+        if not pat.search(doc):
+            raise SystemExit(f"{name}: no {MARK} markers")
+        with open(path, "w") as fh:
+            fh.write(pat.sub(lambda m: m.group(1) + text + "\n" + m.group(2), doc))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "depthwise_chain_bench_line.json"))
+    ap.add_argument("--docs", action="store_true", help="rewrite the table in README.md and DESIGN.md")
+    ap.add_argument("--from-json", default=None, help="take the shapes from a recorded line instead of measuring (with --docs)")
+    ap.add_argument("--child", type=int, default=None)
+    a = ap.parse_args()
+    if a.child is not None:
+        return child(a.child, a.rounds)
+    if a.from_json:
+        with open(a.from_json) as fh:
+            line = json.loads(fh.read().strip().splitlines()[-1])
+        print(table(line["shapes"]))
+        if a.docs:
+            write_docs(table(line["shapes"]))
+        return
+    shapes = []
+    for i in range(len(SHAPES)):
+        # a child per shape, each under its own limit; the first failure ends the run
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(i), "--rounds", str(a.rounds)],
+                           stdout=subprocess.PIPE, text=True, timeout=CHILD_LIMIT_S)
+        if p.returncode != 0:
+            raise SystemExit(f"shape {SHAPES[i]}: the measuring process ended with status {p.returncode}; nothing more was started")
+        shapes.append(json.loads(p.stdout.strip().splitlines()[-1]))
+        print(json.dumps(shapes[-1]), file=sys.stderr)
+    line = {"bench": "depthwise_chain_mobilenet_v1", "batch": BATCH, "rounds": a.rounds, "steps": STEPS, "kernel": "3x3 pad 1",
+            "dtype": "float32 +-1 input", "layout": "NCHW", "hbm_bytes_per_s": HBM_BYTES_PER_S, "shapes": shapes,
+            "deferred_below_eager_at_every_shape": all(s["deferred_range_below_eager"] for s in shapes)}
+    text = json.dumps(line)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.write(text + "\n")
+    print(text)
+    print(table(shapes))
+    if a.docs:
+        write_docs(table(shapes))
+
+
+if __name__ == "__main__":
+    main()
