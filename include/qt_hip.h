@@ -1350,6 +1350,53 @@ int qt_dwconv2d_bits_f32(const uint32_t* x_plane, int64_t ldx, const float* w, c
                          int64_t m, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                          int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, int kind, qt_stream_t stream);
 
+/* Depthwise convolution on int8 code planes: the forward above inside the fused DoReFa inference chain conv -> BatchNorm -> [ReLU]
+ * -> nnDorefaQuant(k) -> next conv, reading the int8 code plane a CodeActivation carries and writing the next one.  One launch
+ * each; no allocation, no synchronisation.
+ *
+ * Input.  x_plane int8 NHWC [N][H + 2 in_halo_h][W + 2 in_halo_w][ldx_bytes]: byte c of pixel row (n (H + 2 hy) + h + hy)
+ * (W + 2 hx) + w + hx is the code q of channel c (ops.CodePlanes of a k-bit DoReFa activation, value = inv_n q), decoded as
+ * x = fl(inv_n * (float)q) — the fp32 image the quantiser writes — and fed to the arithmetic of qt_dwconv2d_f32.  ldx_bytes >= C
+ * rounded up to 16 (ops.code_ld_bytes(C, 16)) and a multiple of 16, the plane 16-byte aligned.  Taps outside the H x W image are
+ * SKIPPED: the halo of the input plane is never read, whatever in_halo_* and the padding are.
+ *
+ * The value y[n, c m + j, ho, wo] is EXACTLY what qt_dwconv2d_f32 stores for that fp32 image with kind = QT_DW_RAW (accumulator
+ * +0, taps row-major, taps outside the image skipped, one fp32 multiply then one fp32 add per term, bias last, nothing contracted);
+ * w [C m, kh kw] and bias [C m] (or NULL) as there.
+ *
+ * Output forms:
+ *   qt_dwconv2d_codes      the code epilogue of qt_affine_dorefa_codes_i8 without residuals (one helper, csrc/codes_epilogue.h):
+ *                          t = fl(fl(y alpha[co]) + beta[co]) (folded BatchNorm; bn_stats NULL), or
+ *                          t = fma(fl(fl(y - mean[co]) rs[co]), alpha[co], beta[co]) with bn_stats = fp32 [mean | rs] (2 C m values;
+ *                          alpha / beta then hold the BatchNorm weight / bias);  relu == 1: t = t < 0 ? 0 : t (relu in {0, 1});
+ *                          q = rint(fl((2^bit_width - 1) t)), half to even, unclamped: |q| > 127 or NaN stores code 0 and ORs
+ *                          *overflow with 1, or with 3 where some |q| > 2047 or NaN (the values of the other code epilogues).
+ *                          codes int8 [N][Ho + 2 out_halo_h][Wo + 2 out_halo_w][ldc_bytes], ldc_bytes >= C m rounded up to 16 and a
+ *                          multiple of 16, 16-byte aligned.  The launch writes EVERY byte of the plane — the pad bytes of each
+ *                          row, channels >= C m and the whole border as zero — with dword stores; nothing is read back.
+ *   qt_dwconv2d_codes_f32  y itself, fp32 [N, C m, Ho, Wo] by its element strides ys_* (dense NCHW or channels-last), for a deferred
+ *                          depthwise conv whose chain cannot run fused.  `overflow` (may be NULL) is the int8 range flag of the
+ *                          chain that produced x_plane, as in qt_codes_to_f32: if it is raised every output is NaN, decided on
+ *                          the device.
+ *
+ * Limits: those of the depthwise entries above (kh kw <= QT_DW_MAX_TAPS, C m <= QT_DW_MAX_CHANNELS, tensors below 2^31 elements; no
+ * C % 4 restriction), halos <= 64, fewer than 2^31 pixel rows in either plane; beyond them QT_ERR_UNSUPPORTED.  Validation before
+ * anything is enqueued, in this order:
+ *   1. a negative halo, then step 1 above.   2. N, C, H or W zero: QT_OK, nothing is written.   3. the other limits.
+ *   4. a null tensor (bias and bn_stats may be null; overflow only for the fp32 form), strides that are no dense layout, bit_width
+ *      outside 2 .. 8, relu outside {0, 1}, ldx_bytes / ldc_bytes below the bounds above: QT_ERR_INVALID_ARG; then a float or flag
+ *      pointer that is not 4-byte aligned, ldx_bytes % 16 or ldc_bytes % 16 != 0, a plane that is not 16-byte aligned:
+ *      QT_ERR_ALIGNMENT. */
+int qt_dwconv2d_codes(const int8_t* x_plane, int64_t ldx_bytes, int64_t in_halo_h, int64_t in_halo_w, float inv_n, const float* w,
+                      const float* bias, const float* alpha, const float* beta, const float* bn_stats, int relu, int bit_width,
+                      int8_t* codes, int64_t ldc_bytes, int64_t out_halo_h, int64_t out_halo_w, int32_t* overflow, int64_t N,
+                      int64_t C, int64_t m, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                      qt_stream_t stream);
+int qt_dwconv2d_codes_f32(const int8_t* x_plane, int64_t ldx_bytes, int64_t in_halo_h, int64_t in_halo_w, float inv_n,
+                          const float* w, const float* bias, const int32_t* overflow, float* y, int64_t N, int64_t C, int64_t m,
+                          int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t ys_n,
+                          int64_t ys_c, int64_t ys_h, int64_t ys_w, qt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

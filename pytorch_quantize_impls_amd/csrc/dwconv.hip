@@ -1,6 +1,6 @@
 // Depthwise conv2d (groups == in_channels, out_channels = m * in_channels) in fp32: forward, grad_input, grad_weight — and the
-// forward on / into the bit planes of the fused inference chain (second half of the file).
-// include/qt_hip.h "Depthwise convolution" states the contract; DESIGN.md "Depthwise convs" the layout and the byte counts.
+// forward on / into the bit planes of the fused sign chain and the int8 code planes of the fused DoReFa chain (second half of
+// the file).  include/qt_hip.h "Depthwise convolution" states the contract; DESIGN.md "Depthwise convs" the layout and the byte counts.
 //
 // These are streaming kernels: K = kh * kw <= 49 is no matrix-core shape.  One thread owns ONE channel for the whole launch and
 // keeps that channel's quantised taps in registers (the quantisers are the shared device helpers of qt_common.h); it then walks
@@ -18,6 +18,7 @@
 // the lanes that share a channel, the waves in index order, one partial per (split, channel, tap) in the workspace; a second launch
 // adds the splits in index order.  No atomics anywhere: equal inputs give equal bits.
 #include "qt_common.h"
+#include "codes_epilogue.h"
 
 namespace {
 
@@ -621,6 +622,219 @@ int dw_planes_launch(const float* x, const uint32_t* x_plane, int64_t ldx, const
     return qt_check_launch();
 }
 
+// ---- the forward on / into int8 code planes (include/qt_hip.h "Depthwise convolution on int8 code planes") -------------------------
+// dw_codes_kernel: a lane owns ONE DWORD of output channels (4 codes) for the whole launch — its 4 x taps, biases and BatchNorm
+// constants in registers — and the lanes of a workgroup run along the dwords of a pixel row first (`lanes` = the row's dwords
+// rounded up to a power of two, at most 64), then along 256 / lanes consecutive output pixels.  A workgroup is (dword group, split)
+// and walks pixel steps split, split + S, ...: the pixel advances by a constant, so (n, ho, wo) move by constant increments with
+// two carries (no division per element; the FIXED walk of affine_dorefa_codes is the model).  For m == 1 a tap is one 4-byte load
+// per lane, contiguous along the channels across the lanes; for m > 1 the four input bytes are read one by one.  Taps outside the
+// image are not added; their (discarded) load goes to the nearest pixel INSIDE the image, never to the halo.  The epilogue is
+// affine_codes_word of codes_epilogue.h; the dwords past C m of a row are written by lanes of their own as zero, the border pixels
+// of a halo plane by the same thread map after the main loop.  Nothing is read from the output.
+struct DwCodesMap {
+    int lanes_log;            // log2 of the lanes along the dwords of a pixel row
+    int slots;                // dwords per output pixel row that are written: ldc / 4, or ceil(C m / 4) for the fp32 form
+    int units, splits;        // pixel steps of 256 >> lanes_log pixels, workgroups per dword group
+    int d_n, d_ho, d_wo;      // splits * (256 >> lanes_log) pixels as (images, rows, columns)
+    int ihy, ihx, ohy, ohx;   // halos of the input and the output plane
+};
+
+struct DwCodesEpi {
+    const float* alpha;
+    const float* beta;
+    const float* bn_stats;
+    int relu;
+    float n;
+    int8_t* codes;
+    int64_t ldc;
+    int32_t* overflow;
+};
+
+struct DwF32Out {
+    float* y;
+    DwStrides ys;
+    const int32_t* overflow;
+    int vec;                  // channels-last, C m % 4 == 0, 16-byte aligned: one float4 store per lane
+};
+
+template <int KH, int KW, bool F32OUT>
+__global__ __launch_bounds__(DW_THREADS) void dw_codes_kernel(const int8_t* __restrict__ x, int64_t ldx, float inv_n,
+                                                              const float* __restrict__ w, const float* __restrict__ bias,
+                                                              DwCodesEpi ep, DwF32Out fo, DwGeom g, DwCodesMap mp) {
+    using T = DwTaps<KH, KW>;
+    const int tid = threadIdx.x;
+    const int lanes = 1 << mp.lanes_log, tpix = DW_THREADS >> mp.lanes_log;
+    const int sg = (int)(blockIdx.x / mp.splits);
+    const int split = (int)(blockIdx.x - (unsigned)sg * mp.splits);
+    const int slot = sg * lanes + (tid & (lanes - 1));
+    const int ps = tid >> mp.lanes_log;
+    const bool row_lane = slot < mp.slots;                     // this lane writes a dword of every pixel row
+    const int64_t co0 = (int64_t)slot * 4;
+    const int nvalid = (int)(g.Cout - co0 < 0 ? 0 : (g.Cout - co0 > 4 ? 4 : g.Cout - co0));
+    const int kw = T::kw(g), kk = T::kk(g);
+    const bool one = g.m == 1;
+    float wq[4][T::CAP], b[4];
+    int cin[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const bool live = e < nvalid;
+#pragma unroll
+        for (int t = 0; t < T::CAP; ++t) wq[e][t] = (live && t < kk) ? w[(co0 + e) * kk + t] : 0.0f;
+        b[e] = (live && bias) ? bias[co0 + e] : 0.0f;
+        cin[e] = live ? (int)((co0 + e) / g.m) : 0;
+    }
+    AffineConsts ac;
+    if (!F32OUT) affine_load_consts(ac, co0, g.Cout, ep.alpha, ep.beta, nullptr, nullptr, ep.bn_stats, nullptr);
+    const bool devbn = ep.bn_stats != nullptr;
+    const bool nan_all = F32OUT && fo.overflow != nullptr && *fo.overflow != 0;
+    const int Hp = g.H + 2 * mp.ihy, Wp = g.W + 2 * mp.ihx;
+    const int Hop = g.Ho + 2 * mp.ohy, Wop = g.Wo + 2 * mp.ohx;
+    const unsigned npix = (unsigned)g.N * (unsigned)(g.Ho * g.Wo);              // < 2^31: host check
+    int bad = 0;
+    // the first pixel of this thread, then constant increments
+    unsigned p = (unsigned)split * tpix + ps;
+    int n = (int)(p / (unsigned)(g.Ho * g.Wo));
+    int ho, wo;
+    {
+        const unsigned r = p - (unsigned)n * (unsigned)(g.Ho * g.Wo);
+        ho = (int)(r / (unsigned)g.Wo);
+        wo = (int)(r - (unsigned)ho * g.Wo);
+    }
+    for (int u = split; u < mp.units; u += mp.splits) {
+        if (p < npix && row_lane) {
+            float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (nvalid > 0) {
+                const int h0 = ho * g.sh - g.ph, w0 = wo * g.sw - g.pw;
+                int i = 0, j = 0;
+#pragma unroll
+                for (int t = 0; t < T::CAP; ++t) {
+                    if (!T::GEN || t < kk) {
+                        const int hi = h0 + i * g.dh, wi = w0 + j * g.dw;
+                        const bool ok = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
+                        const int hc = hi < 0 ? 0 : (hi >= g.H ? g.H - 1 : hi), wc = wi < 0 ? 0 : (wi >= g.W ? g.W - 1 : wi);
+                        const int8_t* px = x + (int64_t)((n * Hp + hc + mp.ihy) * Wp + wc + mp.ihx) * ldx;
+                        float v[4];
+                        if (one) {
+                            const uint32_t word = *reinterpret_cast<const uint32_t*>(px + co0);       // co0 + 3 < ldx: rows are 16-byte padded
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) v[e] = inv_n * (float)(int8_t)(word >> (8 * e));
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) v[e] = inv_n * (float)px[cin[e]];
+                        }
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) acc[e] = ok ? acc[e] + v[e] * wq[e][t] : acc[e];
+                    }
+                    if (++j == kw) { j = 0; ++i; }
+                }
+                if (bias) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[e] = acc[e] + b[e];
+                }
+            }
+            if (F32OUT) {
+                if (nan_all) acc[0] = acc[1] = acc[2] = acc[3] = __builtin_nanf("");
+                float* dst = fo.y + n * fo.ys.n + co0 * fo.ys.c + ho * fo.ys.h + wo * fo.ys.w;
+                if (fo.vec) {
+                    *reinterpret_cast<float4*>(dst) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (e < nvalid) dst[e * fo.ys.c] = acc[e];
+                }
+            } else {
+                const float r0[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                float q4[4];
+                const uint32_t word = affine_codes_word(acc, r0, 0u, ac, nvalid, devbn, false, false, false, false, 0.0f, ep.relu, ep.n, q4, bad);
+                *reinterpret_cast<uint32_t*>(ep.codes + (int64_t)((n * Hop + ho + mp.ohy) * Wop + wo + mp.ohx) * ep.ldc + co0) = word;
+            }
+        }
+        p += (unsigned)mp.splits * tpix;
+        wo += mp.d_wo;
+        const int c1 = wo >= g.Wo;
+        wo -= c1 ? g.Wo : 0;
+        ho += mp.d_ho + c1;
+        const int c2 = ho >= g.Ho;
+        ho -= c2 ? g.Ho : 0;
+        n += mp.d_n + c2;
+    }
+    if (F32OUT) return;
+    if ((mp.ohy | mp.ohx) && row_lane) {
+        // the border pixels of the output plane, enumerated alone: per image ohy rows on top, 2 ohx columns beside each of the
+        // Ho image rows, ohy rows below (the enumeration of halo_zero_border in codes_i8.hip); one dword per lane
+        const unsigned top = (unsigned)mp.ohy * Wop, side = 2u * mp.ohx * g.Ho, per_img = 2u * top + side;
+        const unsigned total = (unsigned)g.N * per_img;                        // < 2^31: host check on the plane's pixel rows
+        for (unsigned t = (unsigned)split * tpix + ps; t < total; t += (unsigned)mp.splits * tpix) {
+            const unsigned img = t / per_img, r = t - img * per_img;
+            unsigned h, c;
+            if (r < top) { h = r / Wop; c = r - h * Wop; }
+            else if (r < top + side) {
+                const unsigned q = r - top, row = q / (2u * mp.ohx), k = q - row * 2u * mp.ohx;
+                h = mp.ohy + row;
+                c = k < (unsigned)mp.ohx ? k : g.Wo + k;
+            } else { const unsigned q = r - top - side; h = mp.ohy + g.Ho + q / Wop; c = q % Wop; }
+            *reinterpret_cast<uint32_t*>(ep.codes + (int64_t)((img * Hop + h) * Wop + c) * ep.ldc + co0) = 0u;
+        }
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(ep.overflow, __any(bad & 2) ? 3 : 1);
+}
+
+inline int64_t dw_code_ld(int64_t K) { return std::max<int64_t>(16, (K + 15) / 16 * 16); }
+
+// the shared body of the two code-plane entries: ep.codes (code plane out) or fo.y (fp32 out)
+int dw_codes_launch(const int8_t* x_plane, int64_t ldx, int64_t ihy, int64_t ihx, float inv_n, const float* w, const float* bias,
+                    DwCodesEpi ep, int bit_width, int64_t ohy, int64_t ohx, DwF32Out fo, int64_t N, int64_t C, int64_t m, int64_t H,
+                    int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, bool f32, qt_stream_t stream) {
+    DwGeom g{};
+    bool empty;
+    if (ihy < 0 || ihx < 0 || ohy < 0 || ohx < 0) return QT_ERR_INVALID_ARG;
+    const int rc = dw_geometry(N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
+    if (rc != QT_OK || empty) return rc;
+    if (ihy > DW_MAX_HALO || ihx > DW_MAX_HALO || ohy > DW_MAX_HALO || ohx > DW_MAX_HALO) return QT_ERR_UNSUPPORTED;
+    if ((double)N * (double)(H + 2 * ihy) * (double)(W + 2 * ihx) >= (double)DW_MAX_ELEMS ||
+        (double)N * (double)(g.Ho + 2 * ohy) * (double)(g.Wo + 2 * ohx) >= (double)DW_MAX_ELEMS)
+        return QT_ERR_UNSUPPORTED;
+    if (!x_plane || !w) return QT_ERR_INVALID_ARG;
+    if (f32) {
+        if (!fo.y || dw_layout(N, g.Cout, g.Ho, g.Wo, fo.ys) < 0) return QT_ERR_INVALID_ARG;
+    } else {
+        if (bit_width < 2 || bit_width > 8 || ep.relu < 0 || ep.relu > 1) return QT_ERR_INVALID_ARG;
+        if (!ep.alpha || !ep.beta || !ep.codes || !ep.overflow) return QT_ERR_INVALID_ARG;
+        if (ep.ldc < dw_code_ld(g.Cout)) return QT_ERR_INVALID_ARG;
+        if (ep.ldc >= DW_MAX_ELEMS) return QT_ERR_UNSUPPORTED;
+    }
+    if (ldx < dw_code_ld(C)) return QT_ERR_INVALID_ARG;
+    if (!dw_aligned4(w) || !dw_aligned4(bias) || !dw_aligned4(ep.alpha) || !dw_aligned4(ep.beta) || !dw_aligned4(ep.bn_stats) ||
+        !dw_aligned4(ep.overflow) || !dw_aligned4(fo.overflow) || !dw_aligned4(fo.y))
+        return QT_ERR_ALIGNMENT;
+    if ((ldx & 15) || !dw_aligned16(x_plane) || (ep.ldc & 15) || !dw_aligned16(ep.codes)) return QT_ERR_ALIGNMENT;
+    ep.n = (float)((1 << (f32 ? 2 : bit_width)) - 1);
+    fo.vec = f32 && dw_layout(N, g.Cout, g.Ho, g.Wo, fo.ys) == 1 && fo.ys.c == 1 && (g.Cout & 3) == 0 && dw_aligned16(fo.y);
+    DwCodesMap mp{};
+    const int64_t slots = f32 ? (g.Cout + 3) / 4 : ep.ldc / 4;
+    const int lanes = dw_pow2ceil(slots < 64 ? slots : 64);
+    mp.lanes_log = dw_log2(lanes);
+    mp.slots = (int)slots;
+    const int tpix = DW_THREADS / lanes;
+    const int64_t npix = (int64_t)g.N * g.Ho * g.Wo;
+    mp.units = (int)((npix + tpix - 1) / tpix);
+    const int64_t groups = (slots + lanes - 1) / lanes;
+    int64_t sp = (DW_TARGET_STREAM + groups - 1) / groups;
+    if (sp > mp.units) sp = mp.units;
+    mp.splits = (int)(sp < 1 ? 1 : sp);
+    const int64_t step = (int64_t)mp.splits * tpix;
+    mp.d_wo = (int)(step % g.Wo);
+    mp.d_ho = (int)((step / g.Wo) % g.Ho);
+    mp.d_n = (int)(step / g.Wo / g.Ho);
+    mp.ihy = (int)ihy; mp.ihx = (int)ihx; mp.ohy = (int)ohy; mp.ohx = (int)ohx;
+    const unsigned grid = (unsigned)(groups * mp.splits);
+    hipStream_t s = (hipStream_t)stream;
+    if (f32) DW_DISPATCH_B(dw_codes_kernel, true, g, x_plane, ldx, inv_n, w, bias, ep, fo, g, mp);
+    else DW_DISPATCH_B(dw_codes_kernel, false, g, x_plane, ldx, inv_n, w, bias, ep, fo, g, mp);
+    return qt_check_launch();
+}
+
 }  // namespace
 
 extern "C" int qt_dwconv2d_f32(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t C, int64_t m, int64_t H,
@@ -734,4 +948,33 @@ extern "C" int qt_dwconv2d_bits_f32(const uint32_t* x_plane, int64_t ldx, const 
     o.y = y;
     return dw_planes_launch(nullptr, x_plane, ldx, w, bias, nullptr, nullptr, o, 0, 0, N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw,
                             DwStrides{0, 0, 0, 0}, DwStrides{ys_n, ys_c, ys_h, ys_w}, kind, stream);
+}
+
+extern "C" int qt_dwconv2d_codes(const int8_t* x_plane, int64_t ldx_bytes, int64_t in_halo_h, int64_t in_halo_w, float inv_n,
+                                 const float* w, const float* bias, const float* alpha, const float* beta, const float* bn_stats,
+                                 int relu, int bit_width, int8_t* codes, int64_t ldc_bytes, int64_t out_halo_h, int64_t out_halo_w,
+                                 int32_t* overflow, int64_t N, int64_t C, int64_t m, int64_t H, int64_t W, int kh, int kw, int sh,
+                                 int sw, int ph, int pw, int dh, int dw, qt_stream_t stream) {
+    DwCodesEpi ep{};
+    ep.alpha = alpha;
+    ep.beta = beta;
+    ep.bn_stats = bn_stats;
+    ep.relu = relu;
+    ep.codes = codes;
+    ep.ldc = ldc_bytes;
+    ep.overflow = overflow;
+    return dw_codes_launch(x_plane, ldx_bytes, in_halo_h, in_halo_w, inv_n, w, bias, ep, bit_width, out_halo_h, out_halo_w, DwF32Out{},
+                           N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw, false, stream);
+}
+
+extern "C" int qt_dwconv2d_codes_f32(const int8_t* x_plane, int64_t ldx_bytes, int64_t in_halo_h, int64_t in_halo_w, float inv_n,
+                                     const float* w, const float* bias, const int32_t* overflow, float* y, int64_t N, int64_t C,
+                                     int64_t m, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                                     int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, qt_stream_t stream) {
+    DwF32Out fo{};
+    fo.y = y;
+    fo.ys = DwStrides{ys_n, ys_c, ys_h, ys_w};
+    fo.overflow = overflow;
+    return dw_codes_launch(x_plane, ldx_bytes, in_halo_h, in_halo_w, inv_n, w, bias, DwCodesEpi{}, 0, 0, 0, fo, N, C, m, H, W, kh, kw,
+                           sh, sw, ph, pw, dh, dw, true, stream);
 }

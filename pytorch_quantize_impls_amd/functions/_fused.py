@@ -905,6 +905,22 @@ def packed_depthwise_conv2d(layer, act):
                                           layer.dilation, kind="raw")
 
 
+def codes_depthwise_conv2d(layer, act):
+    """Eval-mode DorefaConv2d with ``groups == in_channels`` (any weight bit_width) on a CodeActivation: the fp32 [N, C * m, Ho, Wo]
+    result in channels-last storage (the code tag of an NCHW fp32 tensor: NCHW, as the eager conv returns), bias added, from one launch
+    on the code plane (ops.depthwise_conv2d_from_codes) — what a
+    deferred depthwise DoReFa conv materialises to when its chain cannot run fused.  The stored eval image is multiplied as it is;
+    a raised int8 range flag of the activation's chain makes the result NaN on the device (as ``CodeActivation.float``)."""
+    if layer.training:
+        raise RuntimeError("CodeActivation inputs are an inference feature: call .eval() first")
+    if (layer.padding_mode != "zeros" or len(act.shape) != 4
+            or not ops.depthwise_applicable(act.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups)):
+        raise ValueError("depthwise conv on codes needs groups == in_channels, numeric zero padding and a shape inside the kernels' limits")
+    return ops.depthwise_conv2d_from_codes(act.codes, act.shape, layer.weight.detach(), layer.bias, layer.stride, layer.padding,
+                                           layer.dilation, in_halo=act.halo, channels_last=bool(act.source_channels_last),
+                                           flagged=not ops._cfg("ASSUME_CODES_FIT"))
+
+
 def packed_xnor_conv2d(layer, act, epi=None):
     """Eval-mode XNORConv2d on a PackedActivation: the per-tap scaled fp4 conv (ops.conv2d_nib_taps) on the activation's nibble
     plane — the producer's own (zero halo = this conv's padding, un-padded kernel) when its pixel stride is whole 32-byte taps,

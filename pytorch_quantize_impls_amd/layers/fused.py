@@ -452,6 +452,67 @@ class FusedDorefaConvBnQuant(torch.nn.Module):
                                              conv.padding_mode, scale=E, epi=epi)
 
 
+class FusedDepthwiseDorefaBnQuant(torch.nn.Module):
+    """Depthwise DorefaConv2d (``groups == in_channels``, eval, ANY weight bit_width whose eval image is on the quantiser's grid) ->
+    BatchNorm2d(eval) [-> ReLU] -> nnDorefaQuant(k): the depthwise sibling of ``FusedDorefaConvBnQuant``.  ONE launch
+    (qt_dwconv2d_codes) reads the int8 code plane of a CodeActivation (any halo: it is never read), computes the conv in the pinned
+    fp32 order of ``ops.depthwise_conv2d`` on the image fl(inv_n * code) with the stored weight image as it is, and writes the next
+    layer's code plane with ``out_halo`` as its zero border.  No residual, no ReLU in front of the BatchNorm.
+
+    ``fold="device"``: the BatchNorm probe has the layout the module graph's depthwise result has — channels-last for a code-plane
+    input, the tensor's own layout for the code tag of an fp32 tensor (``CodeActivation.source_channels_last``)."""
+
+    def __init__(self, conv, bn, bit_width: int, relu=True, out_halo=0, fold=None):
+        super().__init__()
+        from .dorefa_layers import DorefaConv2d
+        if not isinstance(conv, DorefaConv2d):
+            raise ValueError("FusedDepthwiseDorefaBnQuant fuses a depthwise DorefaConv2d only")
+        if conv.groups != conv.in_channels or conv.groups <= 1 or conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+            raise ValueError("only groups == in_channels > 1, zero-padded convs with numeric padding can be fused")
+        kh, kw = conv.kernel_size
+        dh, dw = ops._pairs(conv.dilation)
+        fits = (1, conv.in_channels, dh * (kh - 1) + 1, dw * (kw - 1) + 1)       # the smallest image the kernel fits
+        if not ops.depthwise_applicable(fits, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups):
+            raise ValueError("a depthwise conv outside the limits of the HIP kernels (ops.depthwise_applicable)")
+        if not isinstance(bn, torch.nn.BatchNorm2d) or bn.num_features != conv.out_channels:
+            raise ValueError("BatchNorm2d over the conv's output channels expected")
+        if not 2 <= int(bit_width) <= 8:
+            raise ValueError("code planes exist for 2 <= bit_width <= 8")
+        self.fold = fold or DEFAULT_FOLD
+        self.conv, self.bn, self.bit_width, self.relu = conv, bn, int(bit_width), ops.relu_mode(relu)
+        if self.relu == 2:
+            raise ValueError("the depthwise code epilogue has no ReLU in front of the BatchNorm (relu='pre')")
+        self.out_halo = (int(out_halo),) * 2 if isinstance(out_halo, int) else tuple(int(v) for v in out_halo)
+        self._folded = None
+
+    def refold(self):
+        self._folded = None
+
+    def forward(self, act, residual=None):
+        conv = self.conv
+        if conv.training or self.bn.training:
+            raise ValueError("FusedDepthwiseDorefaBnQuant is an inference form: call .eval() first")
+        if residual is not None:
+            raise ValueError("the depthwise code epilogue takes no residual")
+        if not isinstance(act, packed.CodeActivation):
+            raise TypeError("FusedDepthwiseDorefaBnQuant consumes a CodeActivation (a fused DoReFa block's output)")
+        shape = act.shape
+        if len(shape) != 4 or not ops.depthwise_applicable(shape, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups):
+            raise ValueError(f"not a depthwise conv the HIP kernels take: input {tuple(shape)}")
+        if not conv._eval_on_grid():
+            raise ValueError("the eval-mode weight is off the quantiser's grid")
+        N, _, H, W = shape
+        Ho, Wo = ops.conv_out_hw(H, W, conv.kernel_size[0], conv.kernel_size[1], conv.stride, conv.padding, conv.dilation)
+        # the tensor the module graph hands to F.batch_norm is this conv's fp32 output, which takes its input's layout
+        like = ((N, conv.out_channels, Ho, Wo), bool(act.source_channels_last)) if self.fold == "device" else None
+        folded = _code_fold_for(self, "_folded", self.bn, self.fold, like)
+        epi = ops.CodeEpilogue(folded[0], folded[1], self.bit_width, self.relu, out_halo=self.out_halo,
+                               bn_stats=folded[2] if len(folded) > 2 else None, overflow=act.codes.overflow)
+        out = ops.depthwise_conv2d_codes(act.codes, shape, conv.weight.detach(), conv.bias, epi, conv.stride, conv.padding,
+                                         conv.dilation, in_halo=act.halo)
+        return packed.CodeActivation(out, (N, conv.out_channels, Ho, Wo), halo=self.out_halo)
+
+
 class CodeMaxPool(torch.nn.Module):
     """MaxPool2d on a CodeActivation (the reference's DoReFa CNNs pool AFTER the quantiser,
     models/samples/AlexNet_Dorefa.py:38-41): the max of the int8 codes, bit-identical to pooling the fp32 image.

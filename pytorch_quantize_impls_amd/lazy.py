@@ -40,6 +40,13 @@ Depthwise BinConv2d / TerConv2d (``groups == in_channels``) join the sign chain 
 the next layer's planes or nibble operand — so a binarised pointwise / depthwise stack keeps every chain fused; a deferred
 depthwise conv on planes that must materialise computes its fp32 value from the planes (``_fused.packed_depthwise_conv2d``).
 
+Depthwise DorefaConv2d (``groups == in_channels``, any weight bit_width) joins the DoReFa code chain in the same way
+(``DEFER_DEPTHWISE_CODES``, together with ``DEFER_CODES``; ``depthwise_deferred()`` sets it with ``DEFER_DEPTHWISE``): the layer takes
+its producer's int8 code plane — whatever halo it has — and runs as ``layers.fused.FusedDepthwiseDorefaBnQuant``, one launch from
+codes to the next layer's codes, so a DoReFa pointwise / depthwise stack stays on code planes from the stem quantiser to the head.
+It takes no residual (an ``add`` behind its BatchNorm materialises); a deferred depthwise conv on codes that must materialise
+computes its fp32 value from the codes (``_fused.codes_depthwise_conv2d``).
+
 Nothing is deferred in training mode, with autograd enabled, on CPU tensors, for non-fp32 dtypes, grouped convs other than
 those depthwise ones or non-zero padding modes.  ``lazy.ENABLED = False`` (or the ``eager()`` context manager) switches the mechanism off;
 ``lazy.STATS`` counts what happened (tests assert on it).
@@ -84,6 +91,13 @@ DEFER_LEVELS = False
 #: as without this mechanism — the depthwise layer returns fp32 and the chain in front of it materialises
 #: (``depthwise_deferred(False)`` switches it off for a block).
 DEFER_DEPTHWISE = True
+#: depthwise DorefaConv2d (``groups == in_channels``, any weight bit_width with an on-grid eval image, shapes
+#: ``ops.depthwise_applicable`` takes) joins the DoReFa code chain — needs ``DEFER_CODES`` as well: the layer defers, reads its
+#: producer's int8 code plane and runs as ``layers.fused.FusedDepthwiseDorefaBnQuant``, one launch from codes to the next layer's
+#: codes (measured: DESIGN.md "Depthwise convs"; on by default by the acceptance rule stated there).  False = every call runs
+#: exactly as without this mechanism: the depthwise layer computes fp32 from the expanded image and the chain in front of it
+#: materialises (``depthwise_deferred(False)`` switches it off for a block).
+DEFER_DEPTHWISE_CODES = True
 #: "deferred" convs that returned a LazyActivation, "fused" chains executed as fused blocks, "materialised" lazies that
 #: had to produce their fp32 value, "fallback:<func>" the functions that forced it
 STATS = collections.Counter()
@@ -150,13 +164,15 @@ def levels_deferred(on: bool = True):
 
 @contextlib.contextmanager
 def depthwise_deferred(on: bool = True):
-    """Defer depthwise sign convs (``DEFER_DEPTHWISE``) inside the block; process-wide, restores the previous setting."""
-    global DEFER_DEPTHWISE
+    """Defer depthwise sign convs (``DEFER_DEPTHWISE``) and depthwise DoReFa convs (``DEFER_DEPTHWISE_CODES``) inside the block;
+    process-wide, restores both previous settings."""
+    global DEFER_DEPTHWISE, DEFER_DEPTHWISE_CODES
     prev, DEFER_DEPTHWISE = DEFER_DEPTHWISE, bool(on)
+    prev_codes, DEFER_DEPTHWISE_CODES = DEFER_DEPTHWISE_CODES, bool(on)
     try:
         yield
     finally:
-        DEFER_DEPTHWISE = prev
+        DEFER_DEPTHWISE, DEFER_DEPTHWISE_CODES = prev, prev_codes
 
 
 class _Node:
@@ -244,7 +260,12 @@ class _Node:
                 # the int8 codes, expanded; the chain's int8-range flag is applied on the device (NaN, no host sync)
                 y = codes.float()
             elif self.parent is None:
-                y = self.layer._forward_impl(self.input)
+                if self.kind == "dorefa" and self.layer.groups != 1 and isinstance(self.input, packed.CodeActivation):
+                    # a depthwise DoReFa conv on codes: its fp32 value from the code plane, one launch
+                    from .functions import _fused
+                    y = _fused.codes_depthwise_conv2d(self.layer, self.input)
+                else:
+                    y = self.layer._forward_impl(self.input)
             else:
                 x = self.parent.materialise()
                 tag = self.op[0]
@@ -333,6 +354,8 @@ def _force_codes(self, halo=None):
     try:
         with torch.no_grad():
             blk = _code_block(self.layer, self.bn, self.quant, self.relu, halo if self.pool2 is None else (0, 0))
+            if self.layer.groups != 1 and self.add is not None:
+                raise ValueError("the depthwise code epilogue takes no residual")
             res = res_bn = res_conv = None
             if self.add is not None:
                 other = self.add
@@ -367,7 +390,10 @@ def _force_codes(self, halo=None):
                         STATS["residual_as_codes"] += 1
                 if res is None and res_conv is None:
                     raise ValueError("residual cannot join the fused chain")
-            act = blk(self.input, residual=res, residual_bn=res_bn, residual_conv=res_conv)
+            if self.layer.groups != 1:
+                act = blk(self.input)
+            else:
+                act = blk(self.input, residual=res, residual_bn=res_bn, residual_conv=res_conv)
             if self.pool2 is not None:
                 act = fused.CodeMaxPool(torch.nn.MaxPool2d(self.pool2[0], self.pool2[1]), out_halo=halo)(act)
     except ValueError:
@@ -529,7 +555,8 @@ def _code_block(layer, bn, bit_width, relu, halo):
         per = _BLOCKS[layer] = collections.OrderedDict()
     blk = per.get(key)
     if blk is None:
-        blk = fused.FusedDorefaConvBnQuant(layer, _BnView(rm, rv, w, b, eps), bit_width, relu=relu, out_halo=halo, fold="device")
+        make = fused.FusedDepthwiseDorefaBnQuant if layer.groups != 1 else fused.FusedDorefaConvBnQuant
+        blk = make(layer, _BnView(rm, rv, w, b, eps), bit_width, relu=relu, out_halo=halo, fold="device")
         per[key] = blk
         while len(per) > _MAX_BLOCKS_PER_LAYER:
             per.popitem(last=False)
@@ -1115,10 +1142,18 @@ def conv_forward(layer, input, kind: str):
 
 
 def _dorefa_can_defer(layer, input) -> bool:
-    if (layer.training or not _no_autograd(layer) or layer.groups != 1 or layer.padding_mode != "zeros"
-            or isinstance(layer.padding, str) or layer.bit_width != 1):
+    if layer.training or not _no_autograd(layer) or layer.padding_mode != "zeros" or isinstance(layer.padding, str):
         return False
     w = layer.weight
+    if layer.groups != 1:
+        # depthwise only (DEFER_DEPTHWISE_CODES), any weight bit_width, inside the limits of the depthwise kernels; every other
+        # grouped conv runs eagerly
+        if not (DEFER_CODES and DEFER_DEPTHWISE_CODES and layer.groups == layer.in_channels
+                and ops.depthwise_applicable(tuple(getattr(input, "shape", ())), tuple(w.shape), layer.stride, layer.padding,
+                                             layer.dilation, layer.groups)):
+            return False
+    elif layer.bit_width != 1:
+        return False
     if not w.is_cuda or w.dtype != torch.float32 or not isinstance(input, packed.CodeActivation) or len(input.shape) != 4:
         return False
     if _untracked(w, layer.bias):
@@ -1127,13 +1162,18 @@ def _dorefa_can_defer(layer, input) -> bool:
 
 
 def dorefa_conv_forward(layer, input):
-    """forward() of DorefaConv2d: a 1-bit-weight conv in eval mode whose input carries int8 codes (the tag nnDorefaQuant
-    leaves on its result, a CodeActivation, or a deferred quantised chain) defers itself."""
+    """forward() of DorefaConv2d: a 1-bit-weight conv — or, under DEFER_DEPTHWISE_CODES, a depthwise conv of any weight bit_width —
+    in eval mode whose input carries int8 codes (the tag nnDorefaQuant leaves on its result, a CodeActivation, or a deferred
+    quantised chain) defers itself."""
     note_inference_call(layer, input)
     if isinstance(input, LazyActivation):
         n = input._qt
         act = None
-        if n.kind == "dorefa" and n.quant is not None and _dorefa_can_defer(layer, _CodeShapeOnly(n.shape)):
+        if layer.groups != 1:
+            if enabled() and n.kind == "dorefa" and n.quant is not None and _dorefa_can_defer(layer, _CodeShapeOnly(n.shape)):
+                # a depthwise consumer skips the taps outside the image itself: any plane already produced serves it, whatever its halo
+                act = n.force_any() if n.packed_cache else n.force((0, 0))
+        elif n.kind == "dorefa" and n.quant is not None and _dorefa_can_defer(layer, _CodeShapeOnly(n.shape)):
             pad = tuple(int(v) for v in ops._pairs(layer.padding))
             # a plane already produced for another consumer serves this one too if its zero border covers the padding
             # (the kernels read a halo plane at an offset of halo - padding pixels): e.g. the 1x1 shortcut conv of a
@@ -1149,18 +1189,20 @@ def dorefa_conv_forward(layer, input):
     defer = enabled() and DEFER_CODES
     if defer and not isinstance(input, packed.CodeActivation) and isinstance(input, torch.Tensor) and input.is_cuda \
             and input.dtype == torch.float32 and input.dim() == 4 and not torch.is_grad_enabled() and not layer.training \
-            and layer.bit_width == 1:
+            and (layer.bit_width == 1 if layer.groups == 1 else DEFER_DEPTHWISE_CODES):
         codes = packed.lookup_codes(input, packed.NHWC)
         N, C, H, W = (int(v) for v in input.shape)
         if codes is not None and codes.K == C and codes.rows == N * H * W:
             cand = packed.CodeActivation(codes, (N, C, H, W))
+            cand.source_channels_last = ops._dw_channels_last(input)      # (read by a depthwise consumer alone)
             if _dorefa_can_defer(layer, cand):
                 tagged, input = input, cand
     if defer and _dorefa_can_defer(layer, input):
         N, C, H, W = (int(v) for v in input.shape)
         kh, kw = layer.kernel_size
         Ho, Wo = ops.conv_out_hw(H, W, kh, kw, layer.stride, layer.padding, layer.dilation)
-        if Ho > 0 and Wo > 0 and 127 * kh * kw * int(input.codes.codes.shape[1]) < (1 << 24):
+        # (127 kh kw ld < 2^24 bounds the int8 conv's integer accumulator; the depthwise conv accumulates in fp32)
+        if Ho > 0 and Wo > 0 and (layer.groups != 1 or 127 * kh * kw * int(input.codes.codes.shape[1]) < (1 << 24)):
             STATS["deferred"] += 1
             node = _Node(None, None, (N, int(layer.out_channels), int(Ho), int(Wo)), layer=layer, kind="dorefa", input=input)
             node.stamp += _stamp(tagged)          # the fp32 tensor whose code tag is being used

@@ -4266,6 +4266,105 @@ def depthwise_conv2d_from_bits(planes: BitPlanes, shape, weight: torch.Tensor, b
     return y
 
 
+def _dw_code_input(codes: CodePlanes, shape, in_halo):
+    """``codes`` checked as the int8 NHWC pixel plane (16-byte rows, zero border of ``in_halo`` pixels) of a DoReFa activation of
+    logical ``shape`` (N, C, H, W); returns the shape and the halo as ints."""
+    if not isinstance(codes, CodePlanes):
+        raise TypeError(f"input: expected CodePlanes, got {type(codes)}")
+    if shape is None or len(shape) != 4:
+        raise ValueError("a CodePlanes input needs the logical (N, C, H, W) shape")
+    N, C, H, W = (int(v) for v in shape)
+    hy, hx = (int(v) for v in _pairs(in_halo))
+    _require(codes.codes, "input codes", torch.int8)
+    rows = N * (H + 2 * hy) * (W + 2 * hx)
+    ld = int(codes.codes.shape[1]) if codes.codes.dim() == 2 else 0
+    if (hy < 0 or hx < 0 or codes.rows != rows or codes.K != C or codes.codes.dim() != 2 or int(codes.codes.shape[0]) < rows
+            or not codes.codes.is_contiguous() or ld < code_ld_bytes(C, 16) or ld % 16):
+        raise ValueError(f"input: expected the int8 NHWC code plane (16-byte rows) of an {(N, C, H, W)} activation with halo {(hy, hx)}")
+    return (N, C, H, W), (hy, hx)
+
+
+def depthwise_conv2d_codes(codes: CodePlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor], epi: CodeEpilogue, stride=1,
+                           padding=0, dilation=1, in_halo=(0, 0), out: Optional[torch.Tensor] = None) -> CodePlanes:
+    """Depthwise conv (``depthwise_conv2d``'s pinned fp32 arithmetic on the image fl(inv_n * code)) -> BatchNorm -> [ReLU] -> k-bit
+    DoReFa quantiser, from the int8 code plane ``codes`` (logical ``shape`` (N, C, H, W), zero border of ``in_halo`` pixels that is
+    never read) to the next code plane in ONE launch (qt_dwconv2d_codes): no fp32 activation exists.  ``epi``: a ``CodeEpilogue``
+    without a residual — folded (alpha, beta), or the device form with ``bn_stats``; its ``out_halo`` is the zero border of the
+    produced plane [N*(Ho+2hy)*(Wo+2hx), code_ld_bytes(C*m, 16)], of which the launch writes every byte; ``overflow`` the chain's
+    int8 range flag (None: the input plane's, or a fresh one).  ``out``: an existing contiguous int8 [rows, ld] tensor the plane is
+    written into (no prior content needed)."""
+    x_shape, (ihy, ihx) = _dw_code_input(codes, shape, in_halo)
+    dev = codes.device
+    w, geom, y_shape = _dw_geometry(x_shape, weight, stride, padding, dilation)
+    if w.device != dev:
+        raise ValueError("input and weight are on different devices")
+    if not isinstance(epi, CodeEpilogue):
+        raise TypeError(f"epi: expected a CodeEpilogue, got {type(epi)}")
+    if epi.res_f32 is not None or epi.res_codes is not None or epi.res_affine is not None or any(epi.res_halo):
+        raise ValueError("the depthwise code epilogue takes no residual")
+    relu = relu_mode(epi.relu)
+    if relu == 2:
+        raise ValueError("the depthwise code epilogue has no ReLU in front of the BatchNorm (relu='pre')")
+    if not 2 <= int(epi.bit_width) <= 8:
+        raise ValueError("int8 code planes exist for 2 <= bit_width <= 8")
+    N, Cout, Ho, Wo = y_shape
+    bias = _check_bias(bias, Cout, dev)
+    alpha, beta = _check_bias(epi.alpha, Cout, dev, "alpha"), _check_bias(epi.beta, Cout, dev, "beta")
+    if alpha is None or beta is None:
+        raise TypeError("alpha and beta: expected fp32 device vectors")
+    stats = None
+    if epi.bn_stats is not None:
+        stats = _require(epi.bn_stats, "bn_stats").contiguous()
+        if stats.numel() != 2 * Cout or stats.device != dev:
+            raise ValueError("bn_stats must hold [mean | rs]: 2 * C * m values on the input's device")
+    ohy, ohx = (int(v) for v in _pairs(epi.out_halo))
+    if ohy < 0 or ohx < 0:
+        raise ValueError("out_halo must not be negative")
+    flag = epi.overflow if epi.overflow is not None else codes.overflow
+    if flag is None:
+        flag = torch.zeros((1,), dtype=torch.int32, device=dev)
+    _require(flag, "overflow", torch.int32)
+    rows, ldc = N * (Ho + 2 * ohy) * (Wo + 2 * ohx), code_ld_bytes(Cout, 16)
+    if out is None:
+        out = torch.empty((rows, ldc), dtype=torch.int8, device=dev)      # the launch writes every byte, halo border included
+    else:
+        _require(out, "out", torch.int8)
+        if tuple(out.shape) != (rows, ldc) or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out: expected a contiguous int8 tensor [{rows}, {ldc}] on {dev}, got {tuple(out.shape)} on {out.device}")
+    if N * Cout * Ho * Wo > 0:
+        with _on(dev):
+            _lib.call("qt_dwconv2d_codes", _p(codes.codes), int(codes.codes.shape[1]), ihy, ihx, float(codes.inv_n), _p(w), _p(bias),
+                      _p(alpha), _p(beta), _p(stats), relu, int(epi.bit_width), _p(out), ldc, ohy, ohx, _p(flag), *geom, _stream(dev))
+    return CodePlanes(codes=out, rows=rows, K=Cout, inv_n=inv_levels(epi.bit_width), bit_width=int(epi.bit_width), overflow=flag)
+
+
+def depthwise_conv2d_from_codes(codes: CodePlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1,
+                                padding=0, dilation=1, in_halo=(0, 0), channels_last: bool = True, out: Optional[torch.Tensor] = None,
+                                flagged: bool = True) -> torch.Tensor:
+    """``depthwise_conv2d`` of the DoReFa activation that exists only as the code plane ``codes`` (see ``depthwise_conv2d_codes``):
+    the fp32 result, bit for bit that of the fp32 image fl(inv_n * code), in ``channels_last`` or NCHW storage or written into ``out``
+    (qt_dwconv2d_codes_f32, one launch).  ``flagged``: a raised int8 range flag of the plane's chain makes every value NaN, on the
+    device."""
+    x_shape, (ihy, ihx) = _dw_code_input(codes, shape, in_halo)
+    dev = codes.device
+    w, geom, y_shape = _dw_geometry(x_shape, weight, stride, padding, dilation)
+    if w.device != dev:
+        raise ValueError("input and weight are on different devices")
+    bias = _check_bias(bias, y_shape[1], dev)
+    if out is None:
+        y = torch.empty(y_shape, dtype=torch.float32, device=dev,
+                        memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    else:
+        y = _dw_result(out, y_shape, w, "out")
+    if y.numel() == 0:
+        return y
+    flag = codes.overflow if flagged else None
+    with _on(dev):
+        _lib.call("qt_dwconv2d_codes_f32", _p(codes.codes), int(codes.codes.shape[1]), ihy, ihx, float(codes.inv_n), _p(w), _p(bias),
+                  _p(flag), _p(y), *geom, *_dw_strides(y.shape, _dw_channels_last(y)), _stream(dev))
+    return y
+
+
 def depthwise_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_output: torch.Tensor, stride=1, padding=0, dilation=1,
                                 kind: str = "raw", channels_last: Optional[bool] = None,
                                 out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -25,6 +25,23 @@ bytes, so it is a lower bound of the depthwise part's own share.
     python tools/bench_depthwise_chain.py [--rounds 9] [--out profiles/depthwise_chain_bench_line.json] [--docs]
 
 ``--docs`` rewrites the table between the ``depthwise-chain-table`` markers of README.md and DESIGN.md.
+
+``--family dorefa`` measures the DoReFa counterpart with the same shapes and the same protocol:
+
+    dw 3x3 (padding 1, bit_width 1) -> BatchNorm -> ReLU -> nnDorefaQuant(4) -> pw 1x1 DorefaConv2d(bit_width 1) -> BatchNorm -> ReLU
+    -> nnDorefaQuant(4)
+
+on a quantiser-tagged fp32 input (the channels-last result of nnDorefaQuant(4): an fp32 image that carries its int8 codes).
+  deferred : ``lazy.depthwise_deferred(True)`` — the depthwise layer reads the tag's code plane and writes the pointwise conv's code
+             plane in ONE launch (qt_dwconv2d_codes);
+  eager    : ``lazy.depthwise_deferred(False)`` — the path without ``lazy.DEFER_DEPTHWISE_CODES``: qt_dwconv2d_f32 on the fp32 image,
+             BatchNorm, ReLU and the quantiser as three passes over fp32 tensors, then the pointwise conv on the quantiser's codes.
+Both sides end by asking for the pair's int8 code plane and must agree on it.  ``bytes`` of the depthwise part, from the shapes:
+  eager    : conv 4|x| + 4|y|, BatchNorm 8|y|, ReLU 8|y|, quantiser 4|y| in + 4|y| image + |y| codes  =  4|x| + 29|y|
+  deferred : |x| + |y| (one code in, one code out)
+The line goes to profiles/depthwise_codes_chain_bench_line.json, the table between the ``depthwise-codes-chain-table`` markers.
+``--kernel-times`` adds the depthwise kernel's own time per shape (``kernel_us``) from one separate
+``rocprofv3 --kernel-trace --stats`` pass of each child, with no counters in that run.
 """
 import argparse
 import json
@@ -51,6 +68,119 @@ def algorithmic_bytes(C, H, stride):
     Ho = (H + 2 - 3) // stride + 1
     x, y = BATCH * C * H * H, BATCH * C * Ho * Ho
     return {"eager": 4 * x + 32 * y, "deferred": 4 * x + y // 2}
+
+
+FAMILIES = {"sign": {"mark": MARK, "out": "depthwise_chain_bench_line.json", "bench": "depthwise_chain_mobilenet_v1",
+                     "dtype": "float32 +-1 input", "layout": "NCHW", "kernel": "dw_planes"},
+            "dorefa": {"mark": "depthwise-codes-chain-table", "out": "depthwise_codes_chain_bench_line.json",
+                       "bench": "depthwise_codes_chain_mobilenet_v1", "dtype": "float32 image of 4-bit codes, code-tagged",
+                       "layout": "channels_last", "kernel": "dw_codes_kernel"}}
+
+
+def algorithmic_bytes_dorefa(C, H, stride):
+    Ho = (H + 2 - 3) // stride + 1
+    x, y = BATCH * C * H * H, BATCH * C * Ho * Ho
+    return {"eager": 4 * x + 29 * y, "deferred": x + y}
+
+
+def measure(sides, rounds):
+    """Warm every side up, then let the sides take turns within each round; {side: [us per forward, one per round]}."""
+    import torch
+
+    def run_us(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(STEPS):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6 / STEPS
+
+    for fn in sides.values():
+        for _ in range(3):
+            fn()
+    samples = {k: [] for k in sides}
+    for _ in range(rounds):
+        for k, fn in sides.items():
+            samples[k].append(run_us(fn))
+    return samples
+
+
+def child_dorefa(index, rounds):
+    import torch
+    import torch.nn as nn
+    from pytorch_quantize_impls_amd import _lib, lazy
+    from pytorch_quantize_impls_amd.functions import nnDorefaQuant
+    from pytorch_quantize_impls_amd.layers import DorefaConv2d
+
+    C, H, stride, Cpw = SHAPES[index]
+    dev = torch.device("cuda:0")
+    torch.manual_seed(index)
+    g = torch.Generator().manual_seed(index)
+
+    def run(c, fan):
+        # statistics sized for a sum of ``fan`` products of +-E and a 4-bit image: the codes stay far inside int8
+        bn = nn.BatchNorm2d(c)
+        bn.running_mean.copy_(torch.randn(c, generator=g) * 0.1)
+        bn.running_var.copy_((torch.rand(c, generator=g) + 0.5) * fan * 0.05)
+        gamma = torch.rand(c, generator=g) * 0.5 + 0.25
+        gamma[::3] *= -1
+        bn.weight.data.copy_(gamma)
+        bn.bias.data.copy_(torch.randn(c, generator=g) * 0.2 + 0.3)
+        return [bn, nn.ReLU(), nnDorefaQuant(4)]
+
+    pair = nn.Sequential(DorefaConv2d(C, C, 3, stride=stride, padding=1, groups=C, bit_width=1), *run(C, 9),
+                         DorefaConv2d(C, Cpw, 1, bit_width=1), *run(Cpw, C))
+    pair = pair.to(dev).to(memory_format=torch.channels_last).eval()
+    with torch.no_grad():
+        x = nnDorefaQuant(4)(torch.rand(BATCH, C, H, H, generator=g).to(dev).contiguous(memory_format=torch.channels_last))
+
+    def forward(on):
+        with torch.no_grad(), lazy.depthwise_deferred(on):
+            out = pair(x)
+            act = out._qt.force((0, 0))        # the code plane the next DoReFa layer would ask for
+            assert act is not None
+            return act.codes
+
+    sides = {"deferred": lambda: forward(True), "eager": lambda: forward(False)}
+    calls = dict(_lib.call_counts)
+    a = sides["deferred"]()
+    used_on = {k: v - calls.get(k, 0) for k, v in _lib.call_counts.items() if v != calls.get(k, 0)}
+    calls = dict(_lib.call_counts)
+    b = sides["eager"]()
+    used_off = {k: v - calls.get(k, 0) for k, v in _lib.call_counts.items() if v != calls.get(k, 0)}
+    assert torch.equal(a.codes, b.codes), "the two sides disagree"
+    assert int(a.overflow.item()) == 0 and int(b.overflow.item()) == 0 and int(a.codes.count_nonzero()) > 0
+    assert used_on.get("qt_dwconv2d_codes") == 1 and "qt_dwconv2d_f32" not in used_on, used_on
+    assert used_off.get("qt_dwconv2d_f32") == 1 and "qt_dwconv2d_codes" not in used_off, used_off
+
+    samples = measure(sides, rounds)
+    nbytes = algorithmic_bytes_dorefa(C, H, stride)
+    result = {"channels": C, "map": H, "stride": stride, "pointwise_out": Cpw, "bytes": nbytes,
+              "launches": {"deferred": used_on, "eager": used_off}}
+    for k, v in samples.items():
+        med = sorted(v)[len(v) // 2]
+        result[k] = {"median_us": round(med, 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1),
+                     "hbm_share": round(nbytes[k] / HBM_BYTES_PER_S / (med * 1e-6), 3)}
+    result["deferred_range_below_eager"] = result["deferred"]["max_us"] < result["eager"]["min_us"]
+    print(json.dumps(result))
+
+
+def kernel_time_us(index, family, workdir):
+    """Average duration of the family's depthwise chain kernel in one ``rocprofv3 --kernel-trace --stats`` pass of the child of shape
+    ``index`` (one round; no counters in the run)."""
+    import csv
+    import glob
+    out = os.path.join(workdir, f"kt_{family}_{index}")
+    p = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "-d", out, "-o", "dw", "--output-format", "csv", "--",
+                        sys.executable, os.path.abspath(__file__), "--child", str(index), "--rounds", "1", "--family", family],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=CHILD_LIMIT_S)
+    if p.returncode != 0:
+        raise SystemExit(f"shape {SHAPES[index]}: the profiled process ended with status {p.returncode}; nothing more was started")
+    path = sorted(glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True))[0]
+    with open(path) as fh:
+        rows = [r for r in csv.DictReader(fh) if FAMILIES[family]["kernel"] in r["Name"]]
+    calls = sum(int(r["Calls"]) for r in rows)
+    return round(sum(float(r["TotalDurationNs"]) for r in rows) / max(calls, 1) / 1e3, 1), calls
 
 
 def child(index, rounds):
@@ -124,26 +254,28 @@ def child(index, rounds):
 
 
 def table(shapes):
+    own = all("kernel_us" in s for s in shapes)
     rows = ["| dw channels x map, stride | eager: median (range) us | deferred: median (range) us | eager MB, share of 8 TB/s | "
-            "deferred MB, share of 8 TB/s | deferred range below eager |",
-            "|---|---|---|---|---|---|"]
+            "deferred MB, share of 8 TB/s | deferred range below eager |" + (" depthwise kernel alone, us |" if own else ""),
+            "|---|---|---|---|---|---|" + ("---|" if own else "")]
     for s in shapes:
         e, d = s["eager"], s["deferred"]
         ok = "yes" if s["deferred_range_below_eager"] else "**no**"
-        rows.append(f"| {s['channels']} x {s['map']}², s{s['stride']} | {e['median_us']} ({e['min_us']}–{e['max_us']}) | "
+        name = f"{s['channels']} x {s['map']}², s{s['stride']}"
+        rows.append(f"| {name if s['deferred_range_below_eager'] else '**' + name + '**'} | {e['median_us']} ({e['min_us']}–{e['max_us']}) | "
                     f"{d['median_us']} ({d['min_us']}–{d['max_us']}) | {s['bytes']['eager'] / 1e6:.1f}, {e['hbm_share']} | "
-                    f"{s['bytes']['deferred'] / 1e6:.1f}, {d['hbm_share']} | {ok} |")
+                    f"{s['bytes']['deferred'] / 1e6:.1f}, {d['hbm_share']} | {ok} |" + (f" {s['kernel_us']} |" if own else ""))
     return "\n".join(rows)
 
 
-def write_docs(text):
-    pat = re.compile(rf"(<!-- {MARK}:begin -->\n).*?(<!-- {MARK}:end -->)", re.S)
+def write_docs(text, mark=MARK):
+    pat = re.compile(rf"(<!-- {mark}:begin -->\n).*?(<!-- {mark}:end -->)", re.S)
     for name in ("README.md", "DESIGN.md"):
         path = os.path.join(ROOT, name)
         with open(path) as fh:
             doc = fh.read()
         if not pat.search(doc):
-            raise SystemExit(f"{name}: no {MARK} markers")
+            raise SystemExit(f"{name}: no {mark} markers")
         with open(path, "w") as fh:
             fh.write(pat.sub(lambda m: m.group(1) + text + "\n" + m.group(2), doc))
 
@@ -151,40 +283,50 @@ def write_docs(text):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "depthwise_chain_bench_line.json"))
+    ap.add_argument("--family", choices=sorted(FAMILIES), default="sign", help="sign: BinConv2d pair (default); dorefa: DorefaConv2d pair")
+    ap.add_argument("--out", default=None, help="default: profiles/depthwise_chain_bench_line.json (sign), "
+                                                "profiles/depthwise_codes_chain_bench_line.json (dorefa)")
+    ap.add_argument("--kernel-times", action="store_true", help="one more rocprofv3 --kernel-trace --stats pass per shape")
     ap.add_argument("--docs", action="store_true", help="rewrite the table in README.md and DESIGN.md")
     ap.add_argument("--from-json", default=None, help="take the shapes from a recorded line instead of measuring (with --docs)")
     ap.add_argument("--child", type=int, default=None)
     a = ap.parse_args()
+    fam = FAMILIES[a.family]
     if a.child is not None:
-        return child(a.child, a.rounds)
+        return child_dorefa(a.child, a.rounds) if a.family == "dorefa" else child(a.child, a.rounds)
     if a.from_json:
         with open(a.from_json) as fh:
             line = json.loads(fh.read().strip().splitlines()[-1])
         print(table(line["shapes"]))
         if a.docs:
-            write_docs(table(line["shapes"]))
+            write_docs(table(line["shapes"]), fam["mark"])
         return
+    out = a.out or os.path.join(ROOT, "profiles", fam["out"])
     shapes = []
     for i in range(len(SHAPES)):
         # a child per shape, each under its own limit; the first failure ends the run
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(i), "--rounds", str(a.rounds)],
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(i), "--rounds", str(a.rounds), "--family", a.family],
                            stdout=subprocess.PIPE, text=True, timeout=CHILD_LIMIT_S)
         if p.returncode != 0:
             raise SystemExit(f"shape {SHAPES[i]}: the measuring process ended with status {p.returncode}; nothing more was started")
         shapes.append(json.loads(p.stdout.strip().splitlines()[-1]))
         print(json.dumps(shapes[-1]), file=sys.stderr)
-    line = {"bench": "depthwise_chain_mobilenet_v1", "batch": BATCH, "rounds": a.rounds, "steps": STEPS, "kernel": "3x3 pad 1",
-            "dtype": "float32 +-1 input", "layout": "NCHW", "hbm_bytes_per_s": HBM_BYTES_PER_S, "shapes": shapes,
+    if a.kernel_times:
+        import tempfile
+        with tempfile.TemporaryDirectory() as work:
+            for i, s in enumerate(shapes):
+                s["kernel_us"], s["kernel_calls"] = kernel_time_us(i, a.family, work)
+    line = {"bench": fam["bench"], "batch": BATCH, "rounds": a.rounds, "steps": STEPS, "kernel": "3x3 pad 1",
+            "dtype": fam["dtype"], "layout": fam["layout"], "hbm_bytes_per_s": HBM_BYTES_PER_S, "shapes": shapes,
             "deferred_below_eager_at_every_shape": all(s["deferred_range_below_eager"] for s in shapes)}
     text = json.dumps(line)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as fh:
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
         fh.write(text + "\n")
     print(text)
     print(table(shapes))
     if a.docs:
-        write_docs(table(shapes))
+        write_docs(table(shapes), fam["mark"])
 
 
 if __name__ == "__main__":
