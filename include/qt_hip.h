@@ -1310,6 +1310,74 @@ int qt_dwconv2d_grad_weight_f32(const float* go, const float* x, const float* w,
                                 int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, float ste_threshold,
                                 qt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Grouped convolution: F.conv2d(x, Q(w), bias, stride, padding, dilation, groups = G) with a FEW input channels per group
+ * (1 <= cin_g <= QT_GC_MAX_CIN_G), fp32, forward and both gradients — the 3 x 3 of a ResNeXt block, ShuffleNet-style grouped
+ * layers as BinConv2d / TerConv2d / DorefaConv2d(groups = G).  Streaming kernels on the vector units, the siblings of the
+ * depthwise entries above (K = cin_g kh kw <= QT_GC_MAX_K is no matrix-core shape, and the block-diagonal operand would waste
+ * G times the tile): csrc/gconv.hip, DESIGN.md "Grouped convs".
+ *
+ * Operands.  x [N, G cin_g, H, W], y / go [N, G cout_g, Ho, Wo] (Ho, Wo as above), each DENSE in NCHW or in channels-last order
+ * and described by its four ELEMENT strides as above; the two tensors of a call need not share a layout.  w [G cout_g, cin_g,
+ * kh, kw] dense fp32 (row g cout_g + j: output channel j of group g, which reads input channels g cin_g ... g cin_g + cin_g - 1),
+ * bias [G cout_g] or NULL.  `kind` is QT_DW_RAW | QT_DW_SIGN | QT_DW_TERNARY, applied to every tap inside the kernel.  Zero
+ * padding, numeric; stride, padding and dilation per axis.
+ *
+ * Pinned arithmetic (fp32, one multiply then one add per term, nothing contracted), so that a float32 restatement on a CPU gives
+ * the same bits:
+ *   qt_gconv2d_f32            : y[n, g cout_g + j, ho, wo] = (sum of x[n, g cin_g + ci, ho sh - ph + i dh, wo sw - pw + j' dw]
+ *                               Q(w)[g cout_g + j, ci, i, j']) + bias.  The accumulator starts at +0; ci runs ascending
+ *                               (outermost), then the taps in row-major (i, j') order — the weight's own memory order; taps
+ *                               outside the image are skipped; the bias is added last (NULL: nothing is).
+ *   qt_gconv2d_grad_input_f32 : gather form, no atomics.  gx[n, g cin_g + ci, h, w] = sum of go[n, g cout_g + j, ho, wo]
+ *                               Q(w)[g cout_g + j, ci, i, j'] over j (outermost, ascending) and the taps (row-major), over those
+ *                               (ho, wo) inside the output with ho sh - ph + i dh == h and wo sw - pw + j' dw == w.  Same rules.
+ *                               gx is written in full.
+ *   qt_gconv2d_grad_weight_f32: gw[co, ci, i, j'] = sum over (n, ho, wo) of go[n, co, ho, wo] x[n, (co / cout_g) cin_g + ci, ...],
+ *                               L = N Ho Wo terms per element, in two stream-ordered launches with no atomics and no buffer that
+ *                               must be zero beforehand: one partial per (split, co, ci, tap) into `work` (a fixed walk per
+ *                               thread, a fixed butterfly over the lanes and the waves in index order), then the splits in index
+ *                               order.  The order depends on the shapes and the layout of go alone: equal inputs give equal
+ *                               bits.  gw is then ZERO where |w| > ste_threshold — w is the UNquantised weight; 0 for no mask
+ *                               (w may then be NULL).  gbias, when not NULL, receives sum of go per channel from the same pass.
+ *                               `work` holds at least qt_gconv2d_grad_weight_work_floats(...) floats (a bound for either layout
+ *                               of go; no initial content needed), `work_floats` states how many it holds.
+ * With cin_g == 1 the forward and grad_input give the bits of qt_dwconv2d_f32 / qt_dwconv2d_grad_input_f32 (G = C, cout_g = m).
+ *
+ * Limits: cin_g <= QT_GC_MAX_CIN_G; kh kw <= QT_DW_MAX_TAPS; cin_g kh kw <= QT_GC_MAX_K; every tensor below 2^31 elements;
+ * G cout_g <= QT_DW_MAX_CHANNELS (the grids are one-dimensional: channel blocks x splits, at most QT_DW_MAX_CHANNELS + 2048
+ * workgroups forward, 8 QT_DW_MAX_CHANNELS + 2048 for grad_input, QT_GC_MAX_CIN_G QT_DW_MAX_CHANNELS + 1024 for grad_weight);
+ * beyond them QT_ERR_UNSUPPORTED.
+ *
+ * Everything is validated before anything is enqueued, in the order of the depthwise entries; a non-zero status means nothing
+ * was launched:
+ *   1. negative sizes, cin_g or cout_g < 1, a kernel / stride / dilation below 1, negative padding: QT_ERR_INVALID_ARG;
+ *      kh kw > QT_DW_MAX_TAPS: QT_ERR_UNSUPPORTED.
+ *   2. N, G, H or W zero: QT_OK whatever the pointers are, nothing is written (the work-size query returns 0).
+ *   3. the other limits: QT_ERR_UNSUPPORTED; a kernel that does not fit the padded image: QT_ERR_INVALID_ARG.
+ *   4. an unknown `kind`, a negative or NaN ste_threshold, a null tensor (bias and gbias may be null), strides that are neither
+ *      dense layout, a workspace smaller than the query: QT_ERR_INVALID_ARG; a pointer that is not 4-byte aligned:
+ *      QT_ERR_ALIGNMENT.
+ * ---------------------------------------------------------------------------------------- */
+#define QT_GC_MAX_CIN_G    32
+#define QT_GC_MAX_K        512
+
+int qt_gconv2d_f32(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t G, int64_t cin_g,
+                   int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                   int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, int64_t ys_n, int64_t ys_c, int64_t ys_h,
+                   int64_t ys_w, int kind, qt_stream_t stream);
+int qt_gconv2d_grad_input_f32(const float* go, const float* w, float* gx, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g,
+                              int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n,
+                              int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w,
+                              int kind, qt_stream_t stream);
+int64_t qt_gconv2d_grad_weight_work_floats(int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh,
+                                           int kw, int sh, int sw, int ph, int pw, int dh, int dw);
+int qt_gconv2d_grad_weight_f32(const float* go, const float* x, const float* w, float* gw, float* gbias, float* work,
+                               int64_t work_floats, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W,
+                               int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n, int64_t gs_c,
+                               int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w,
+                               float ste_threshold, qt_stream_t stream);
+
 /* Depthwise convolution on bit planes: the forward above inside the fused inference chain conv -> BatchNorm -> Hardtanh ->
  * BinaryConnect -> next conv, reading and / or writing the planes a PackedActivation carries instead of fp32 tensors.  One
  * launch each; no allocation, no synchronisation.

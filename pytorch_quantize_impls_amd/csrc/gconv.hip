@@ -1,0 +1,630 @@
+// Grouped conv2d with a few channels per group (1 <= cin_g <= 32, K = cin_g * kh * kw <= 512) in fp32: forward, grad_input,
+// grad_weight.  include/qt_hip.h "Grouped convolution" states the contract; DESIGN.md "Grouped convs" the layout and the counts.
+//
+// Streaming kernels on the vector units, siblings of dwconv.hip: K is no matrix-core shape and the block-diagonal operand would
+// waste `groups` times the tile.  What separates them from cout_g depthwise passes is the register block: a lane owns ONE pixel
+// and CB channels of it (CB = 4, 8 or 16), so every input it loads feeds CB multiply-adds.
+//   forward    : a workgroup is (group, block of CB output channels of that group, split of the pixels).  It quantises its
+//                CB x K weights once into LDS as wl[k][CB] (k = ci * taps + t, the weight's own order), so the CB weights of a
+//                term are one wave-uniform 16 / 32 / 64-byte read (a broadcast, no bank conflict whatever the layout), then walks
+//                pixels split * 256 + tid, (split + S) * 256 + tid, ... of the flat (n, ho, wo) index: lanes run along W of an
+//                NCHW tensor (coalesced loads and stores) and along the pixels of a channels-last one (each lane reads the cin_g
+//                and writes the CB consecutive channels of its pixel).
+//   grad_input : the same with the roles turned: the block is CB input channels of the group, the terms run over the group's
+//                output channels j (outermost) and the taps; the weights wl[j][t][CB] are staged in chunks of j that fit 32 KiB.
+//   grad_weight: 1 x 1 and 3 x 3: a lane owns one output pixel and the partial sums of a COB x CIB block of (output, input)
+//                channels of one group in registers (gc_grad_weight_tile_kernel).  Any other kernel: the stage-1 reduction of
+//                dwconv.hip over "virtual channels" v = co * cin_g + ci (the thread map of dw_map.h, chosen by the layout of go;
+//                go is read cin_g times, from cache).  Either way one partial per (split, v, tap) in the workspace and one more
+//                per (split, co) for the bias gradient; a second launch adds the splits in index order.
+// The compile-time forms (1 x 1, 3 x 3) are branch-free: all loads of a channel go out together; the generic forms branch per tap.
+//
+// Arithmetic (the build has -ffp-contract=off): one fp32 multiply and one fp32 add per term, the accumulator starts at +0, terms
+// in the order stated above, taps outside the image skipped, bias last.  No atomics anywhere: equal inputs give equal bits.
+#include "qt_common.h"
+#include "dw_map.h"
+
+namespace {
+
+constexpr int GC_MAX_CIN_G = QT_GC_MAX_CIN_G;
+constexpr int GC_MAX_K = QT_GC_MAX_K;
+constexpr int GC_MAX_TAPS = QT_DW_MAX_TAPS;
+constexpr int GC_LDS_FLOATS = 16 * GC_MAX_K;                 // 32 KiB: the largest forward block, the chunk size of grad_input
+constexpr int64_t GC_MAX_ELEMS = (int64_t)1 << 31;
+constexpr int64_t GC_MAX_CHANNELS = QT_DW_MAX_CHANNELS;      // bounds the one-dimensional grid: channel blocks + the split target
+constexpr int GC_TARGET_STREAM = 2048;                       // workgroups of a forward / grad_input launch: 8 per CU
+constexpr int GC_TARGET_REDUCE = 1024;                       // ... of the grad_weight stage 1
+
+struct GcGeom {
+    int N, G, cin_g, cout_g, H, W, Ho, Wo;
+    int kh, kw, sh, sw, ph, pw, dh, dw;
+    int64_t Cin, Cout;
+};
+
+// (group, channel block) x split of the pixel units of 256 pixels
+struct GcPlan {
+    int cb;          // channels per block
+    int nblk;        // blocks per group
+    int units, splits;
+    int jc;          // grad_input: output channels of the group per LDS chunk
+};
+
+inline int gc_block(int chans) { return chans > 8 ? 16 : (chans > 4 ? 8 : 4); }
+
+GcPlan gc_plan(const GcGeom& g, int chans_g, int64_t npix, int other_g) {
+    GcPlan pl{};
+    pl.cb = gc_block(chans_g);
+    pl.nblk = (chans_g + pl.cb - 1) / pl.cb;
+    pl.units = (int)((npix + DW_THREADS - 1) / DW_THREADS);
+    const int64_t blocks = (int64_t)g.G * pl.nblk;
+    int64_t s = (GC_TARGET_STREAM + blocks - 1) / blocks;
+    if (s > pl.units) s = pl.units;
+    pl.splits = (int)(s < 1 ? 1 : s);
+    int jc = GC_LDS_FLOATS / (pl.cb * g.kh * g.kw);
+    pl.jc = jc > other_g ? other_g : jc;
+    return pl;
+}
+
+template <int KH, int KW, int CB>
+__global__ __launch_bounds__(DW_THREADS) void gc_forward_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                const float* __restrict__ bias, float* __restrict__ y, GcGeom g,
+                                                                DwStrides xs, DwStrides ys, GcPlan pl, int kind) {
+    constexpr bool GEN = KH == 0;
+    extern __shared__ float wl[];                                 // [K][CB]
+    const int taps = GEN ? g.kh * g.kw : KH * KW;
+    const int K = g.cin_g * taps;
+    const int tid = threadIdx.x;
+    const int blk = (int)(blockIdx.x / pl.splits);
+    const int split = (int)(blockIdx.x - (unsigned)blk * pl.splits);
+    const int grp = blk / pl.nblk;
+    const int j0 = (blk - grp * pl.nblk) * CB;
+    const int live = g.cout_g - j0 < CB ? g.cout_g - j0 : CB;
+    const int64_t co0 = (int64_t)grp * g.cout_g + j0;
+    for (int e = tid; e < CB * K; e += DW_THREADS) {
+        const int j = e / K, k = e - j * K;
+        wl[k * CB + j] = j < live ? dw_quant(kind, w[(co0 + j) * K + k]) : 0.0f;
+    }
+    __syncthreads();
+    const int hw = g.Ho * g.Wo;
+    const int64_t npix = (int64_t)g.N * hw;
+    for (int u = split; u < pl.units; u += pl.splits) {
+        const int64_t pix = (int64_t)u * DW_THREADS + tid;
+        if (pix >= npix) continue;
+        const int p = (int)pix;
+        const int n = p / hw;
+        const int r = p - n * hw;
+        const int ho = r / g.Wo, wo = r - ho * g.Wo;
+        const float* xp = x + n * xs.n + (int64_t)grp * g.cin_g * xs.c;
+        const int h0 = ho * g.sh - g.ph, w0 = wo * g.sw - g.pw;
+        float acc[CB];
+#pragma unroll
+        for (int j = 0; j < CB; ++j) acc[j] = 0.0f;
+        if (!GEN) {
+            // no branch per tap: the loads of a channel go out together (a tap outside the image reads element 0 of the plane
+            // instead) and a term outside the image is added as +0, which leaves the accumulator's bits as they are (it starts
+            // at +0 and a sum is -0 only when both terms are, so it never holds -0)
+            constexpr int T = GEN ? 1 : KH * KW;
+            int off[T];
+            bool ok[T];
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const int i = t / (GEN ? 1 : KW), jj = t - i * (GEN ? 1 : KW);
+                const int hi = h0 + i * g.dh, wi = w0 + jj * g.dw;
+                ok[t] = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
+                off[t] = ok[t] ? (int)(hi * xs.h + wi * xs.w) : 0;
+            }
+            constexpr int UNROLL = T == 1 ? 8 : 2;               // channels whose loads are in flight together
+#pragma unroll UNROLL
+            for (int ci = 0; ci < g.cin_g; ++ci) {
+                const float* xc = xp + ci * xs.c;
+                const float* wk = wl + ci * T * CB;
+                float v[T];
+#pragma unroll
+                for (int t = 0; t < T; ++t) v[t] = xc[off[t]];
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+#pragma unroll
+                    for (int j = 0; j < CB; ++j) {
+                        const float p = v[t] * wk[t * CB + j];
+                        acc[j] = acc[j] + (ok[t] ? p : 0.0f);
+                    }
+                }
+            }
+        } else {
+            for (int ci = 0; ci < g.cin_g; ++ci) {
+                const float* xc = xp + ci * xs.c;
+                const float* wk = wl + ci * taps * CB;
+                for (int i = 0; i < g.kh; ++i) {
+                    const int hi = h0 + i * g.dh;
+                    if (hi < 0 || hi >= g.H) continue;
+                    for (int jj = 0; jj < g.kw; ++jj) {
+                        const int wi = w0 + jj * g.dw;
+                        if (wi < 0 || wi >= g.W) continue;
+                        const float v = xc[hi * xs.h + wi * xs.w];
+                        const float* wt = wk + (i * g.kw + jj) * CB;
+#pragma unroll
+                        for (int j = 0; j < CB; ++j) acc[j] = acc[j] + v * wt[j];
+                    }
+                }
+            }
+        }
+        float* yp = y + n * ys.n + co0 * ys.c + ho * ys.h + wo * ys.w;
+#pragma unroll
+        for (int j = 0; j < CB; ++j) {
+            if (j < live) {
+                if (bias) acc[j] = acc[j] + bias[co0 + j];
+                yp[j * ys.c] = acc[j];
+            }
+        }
+    }
+}
+
+// gather form: gx[n, g cin_g + ci, h, w] = sum over j < cout_g (outermost), taps (i, j') row-major of
+// go[n, g cout_g + j, ho, wo] Q(w)[g cout_g + j, ci, i, j'] where ho sh = h + ph - i dh and wo sw = w + pw - j' dw have a solution
+// inside the output
+template <int KH, int KW, int CB>
+__global__ __launch_bounds__(DW_THREADS) void gc_grad_input_kernel(const float* __restrict__ go, const float* __restrict__ w,
+                                                                   float* __restrict__ gx, GcGeom g, DwStrides gs, DwStrides xs,
+                                                                   GcPlan pl, int kind) {
+    constexpr bool GEN = KH == 0;
+    extern __shared__ float wl[];                                 // [jc][taps][CB]
+    const int taps = GEN ? g.kh * g.kw : KH * KW;
+    const int tid = threadIdx.x;
+    const int blk = (int)(blockIdx.x / pl.splits);
+    const int split = (int)(blockIdx.x - (unsigned)blk * pl.splits);
+    const int grp = blk / pl.nblk;
+    const int c0 = (blk - grp * pl.nblk) * CB;
+    const int live = g.cin_g - c0 < CB ? g.cin_g - c0 : CB;
+    const int64_t ci0 = (int64_t)grp * g.cin_g + c0;
+    const int64_t cog = (int64_t)grp * g.cout_g;
+    const bool once = pl.jc >= g.cout_g;                          // the whole group's weights fit: staged once per workgroup
+    const int per = CB * taps;
+    auto stage = [&](int jb) {
+        for (int e = tid; e < pl.jc * per; e += DW_THREADS) {
+            const int jj = e / per, r = e - jj * per;
+            const int c = r / taps, t = r - c * taps;
+            const bool in = jb + jj < g.cout_g && c < live;
+            wl[(jj * taps + t) * CB + c] = in ? dw_quant(kind, w[((cog + jb + jj) * g.cin_g + c0 + c) * taps + t]) : 0.0f;
+        }
+    };
+    if (once) {
+        stage(0);
+        __syncthreads();
+    }
+    const int hw = g.H * g.W;
+    const int64_t npix = (int64_t)g.N * hw;
+    for (int u = split; u < pl.units; u += pl.splits) {           // uniform over the workgroup: the barriers below are too
+        const int64_t pix = (int64_t)u * DW_THREADS + tid;
+        const bool in = pix < npix;
+        const int p = in ? (int)pix : 0;
+        const int n = p / hw;
+        const int r = p - n * hw;
+        const int h = r / g.W, x0 = r - h * g.W;
+        constexpr int T = GEN ? 1 : KH * KW;
+        int off[T];
+        bool ok[T];
+        if (!GEN) {
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const int i = t / (GEN ? 1 : KW), jj = t - i * (GEN ? 1 : KW);
+                const int hh = h + g.ph - i * g.dh, ww = x0 + g.pw - jj * g.dw;
+                const int ho = g.sh == 1 ? hh : hh / g.sh, wo = g.sw == 1 ? ww : ww / g.sw;
+                ok[t] = in && hh >= 0 && ww >= 0 && ho * g.sh == hh && wo * g.sw == ww && ho < g.Ho && wo < g.Wo;
+                off[t] = ok[t] ? (int)(ho * gs.h + wo * gs.w) : 0;
+            }
+        }
+        float acc[CB];
+#pragma unroll
+        for (int c = 0; c < CB; ++c) acc[c] = 0.0f;
+        for (int jb = 0; jb < g.cout_g; jb += pl.jc) {
+            if (!once) {
+                __syncthreads();
+                stage(jb);
+                __syncthreads();
+            }
+            if (!in) continue;
+            const int jn = g.cout_g - jb < pl.jc ? g.cout_g - jb : pl.jc;
+            constexpr int UNROLL = GEN ? 1 : (KH * KW == 1 ? 8 : 2);
+#pragma unroll UNROLL
+            for (int jj = 0; jj < jn; ++jj) {
+                const float* gp = go + n * gs.n + (cog + jb + jj) * gs.c;
+                const float* wk = wl + jj * per;
+                if (!GEN) {                           // branch-free, as in the forward
+                    float v[T];
+#pragma unroll
+                    for (int t = 0; t < T; ++t) v[t] = gp[off[t]];
+#pragma unroll
+                    for (int t = 0; t < T; ++t) {
+#pragma unroll
+                        for (int c = 0; c < CB; ++c) {
+                            const float p = v[t] * wk[t * CB + c];
+                            acc[c] = acc[c] + (ok[t] ? p : 0.0f);
+                        }
+                    }
+                } else {
+                    for (int i = 0; i < g.kh; ++i) {
+                        const int hh = h + g.ph - i * g.dh;
+                        if (hh < 0) continue;
+                        const int ho = hh / g.sh;
+                        if (ho * g.sh != hh || ho >= g.Ho) continue;
+                        for (int t2 = 0; t2 < g.kw; ++t2) {
+                            const int ww = x0 + g.pw - t2 * g.dw;
+                            if (ww < 0) continue;
+                            const int wo = ww / g.sw;
+                            if (wo * g.sw != ww || wo >= g.Wo) continue;
+                            const float v = gp[ho * gs.h + wo * gs.w];
+                            const float* wt = wk + (i * g.kw + t2) * CB;
+#pragma unroll
+                            for (int c = 0; c < CB; ++c) acc[c] = acc[c] + v * wt[c];
+                        }
+                    }
+                }
+            }
+        }
+        if (in) {
+            float* xp = gx + n * xs.n + ci0 * xs.c + h * xs.h + x0 * xs.w;
+#pragma unroll
+            for (int c = 0; c < CB; ++c)
+                if (c < live) xp[c * xs.c] = acc[c];
+        }
+    }
+}
+
+// stage 1 of grad_weight for any kernel of up to 49 taps, over the virtual channels v = co * cin_g + ci: work[(split * Cv + v) * (kk + 1) + t] = this workgroup's
+// share of sum go[., co] * x[., g cin_g + ci] for tap t, and of sum go[., co] for t == kk
+__global__ __launch_bounds__(DW_THREADS) void gc_grad_weight_kernel(const float* __restrict__ go, const float* __restrict__ x,
+                                                                    float* __restrict__ work, GcGeom g, DwStrides gs, DwStrides xs,
+                                                                    DwMap mp) {
+    constexpr int CAP = GC_MAX_TAPS;
+    __shared__ float red[(CAP + 1) * DW_THREADS];
+    const int tid = threadIdx.x;
+    const int64_t cg = blockIdx.x / mp.splits;
+    const int split = (int)(blockIdx.x - cg * mp.splits);
+    const int64_t v = cg * mp.slots + dw_slot(mp, tid);
+    const bool live = v < mp.chans;
+    const int kw = g.kw, kk = g.kh * g.kw;
+    const int64_t co = live ? v / g.cin_g : 0;
+    const int64_t c = live ? (co / g.cout_g) * g.cin_g + (v - co * g.cin_g) : 0;
+    float acc[CAP + 1];
+#pragma unroll
+    for (int t = 0; t <= CAP; ++t) acc[t] = 0.0f;
+    if (live) {
+        for (int u = split; u < mp.units; u += mp.splits) {
+            int n, ho, wo;
+            if (!dw_pos(mp, u, tid, n, ho, wo)) continue;
+            const float gv = go[n * gs.n + co * gs.c + ho * gs.h + wo * gs.w];
+            const float* xp = x + n * xs.n + c * xs.c;
+            const int h0 = ho * g.sh - g.ph, w0 = wo * g.sw - g.pw;
+            acc[CAP] = acc[CAP] + gv;
+#pragma unroll
+            for (int t = 0; t < CAP; ++t) {
+                if (t < kk) {
+                    const int i = t / kw, j = t - i * kw;
+                    const int hi = h0 + i * g.dh, wi = w0 + j * g.dw;
+                    if (hi >= 0 && hi < g.H && wi >= 0 && wi < g.W) acc[t] = acc[t] + gv * xp[hi * xs.h + wi * xs.w];
+                }
+            }
+        }
+    }
+    // the lanes of a wave that share a channel: the low lane bits (NCHW map) or the bits from the channel lanes up (channels-last)
+    const int group = DW_THREADS / mp.slots;                       // NCHW: threads per channel slot
+    const int lo = mp.cl ? mp.slots : 1;
+    const int hi = mp.cl ? 64 : (group < 64 ? group : 64);
+#pragma unroll
+    for (int t = 0; t <= CAP; ++t) {
+        float s = acc[t];
+        for (int off = lo; off < hi; off <<= 1) s = s + __shfl_xor(s, off, 64);
+        red[t * DW_THREADS + tid] = s;
+    }
+    __syncthreads();
+    const int per = kk + 1;
+    for (int e = tid; e < mp.slots * per; e += DW_THREADS) {
+        const int q = e / per, t = e - q * per;
+        const float* r = red + (t == kk ? CAP : t) * DW_THREADS;
+        float s;
+        if (mp.cl) {
+            s = r[q];
+            for (int wv = 1; wv < DW_THREADS / 64; ++wv) s = s + r[wv * 64 + q];
+        } else {
+            s = r[q * group];
+            for (int wv = 1; wv < group / 64; ++wv) s = s + r[q * group + wv * 64];
+        }
+        const int64_t ov = cg * mp.slots + q;
+        if (ov < mp.chans) work[((int64_t)split * mp.chans + ov) * per + t] = s;
+    }
+}
+
+// stage 1 of grad_weight for the compile-time kernels (1 x 1, 3 x 3), register-tiled: a lane owns one output pixel and the
+// COB x CIB x taps partial sums of a block of COB output and CIB input channels of one group, so the COB gradient values and the
+// CIB x taps inputs it loads feed COB x CIB x taps multiply-adds (4 + 36 loads for 144 at 3 x 3).  A workgroup is (group, output
+// block, input block, split) and walks pixels split * 256 + tid, (split + S) * 256 + tid, ...; at the end a butterfly over the 64
+// lanes, then the four waves in index order through LDS.  Same workspace layout as the kernel above; the bias partial of an
+// output channel comes from the workgroup of input block 0.  Branch-free like the forward: a term outside the image adds +0.
+struct GcTilePlan {
+    int nco, nci;        // output / input channel blocks per group
+    int units, splits;
+};
+
+template <int KH, int KW, int COB, int CIB>
+__global__ __launch_bounds__(DW_THREADS) void gc_grad_weight_tile_kernel(const float* __restrict__ go, const float* __restrict__ x,
+                                                                         float* __restrict__ work, GcGeom g, DwStrides gs,
+                                                                         DwStrides xs, GcTilePlan tp) {
+    constexpr int T = KH * KW, A = COB * CIB * T, R = A + COB;
+    __shared__ float red[DW_THREADS / 64][R];
+    const int tid = threadIdx.x;
+    const int blk = (int)(blockIdx.x / tp.splits);
+    const int split = (int)(blockIdx.x - (unsigned)blk * tp.splits);
+    const int per_g = tp.nco * tp.nci;
+    const int grp = blk / per_g;
+    const int rb = blk - grp * per_g;
+    const int jb = rb / tp.nci, cb = rb - jb * tp.nci;
+    const int j0 = jb * COB, c0 = cb * CIB;
+    const int live_j = g.cout_g - j0 < COB ? g.cout_g - j0 : COB;
+    const int live_c = g.cin_g - c0 < CIB ? g.cin_g - c0 : CIB;
+    const int64_t co0 = (int64_t)grp * g.cout_g + j0, ci0 = (int64_t)grp * g.cin_g + c0;
+    float acc[A], gsum[COB];
+#pragma unroll
+    for (int a = 0; a < A; ++a) acc[a] = 0.0f;
+#pragma unroll
+    for (int j = 0; j < COB; ++j) gsum[j] = 0.0f;
+    const int hw = g.Ho * g.Wo;
+    const int64_t npix = (int64_t)g.N * hw;
+    for (int u = split; u < tp.units; u += tp.splits) {
+        const int64_t pix = (int64_t)u * DW_THREADS + tid;
+        if (pix >= npix) continue;
+        const int p = (int)pix;
+        const int n = p / hw;
+        const int r = p - n * hw;
+        const int ho = r / g.Wo, wo = r - ho * g.Wo;
+        const int h0 = ho * g.sh - g.ph, w0 = wo * g.sw - g.pw;
+        int off[T];
+        bool ok[T];
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const int i = t / KW, jj = t - i * KW;
+            const int hi = h0 + i * g.dh, wi = w0 + jj * g.dw;
+            ok[t] = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
+            off[t] = ok[t] ? (int)(hi * xs.h + wi * xs.w) : 0;
+        }
+        const float* gp = go + n * gs.n + co0 * gs.c + ho * gs.h + wo * gs.w;
+        float gv[COB];
+#pragma unroll
+        for (int j = 0; j < COB; ++j) {
+            gv[j] = j < live_j ? gp[j * gs.c] : 0.0f;
+            gsum[j] = gsum[j] + gv[j];
+        }
+        const float* xp = x + n * xs.n + ci0 * xs.c;
+#pragma unroll
+        for (int c = 0; c < CIB; ++c) {
+            if (c < live_c) {                                     // uniform over the workgroup
+                float xv[T];
+#pragma unroll
+                for (int t = 0; t < T; ++t) xv[t] = xp[c * xs.c + off[t]];
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+#pragma unroll
+                    for (int j = 0; j < COB; ++j) {
+                        const float pr = gv[j] * xv[t];
+                        acc[(j * CIB + c) * T + t] = acc[(j * CIB + c) * T + t] + (ok[t] ? pr : 0.0f);
+                    }
+                }
+            }
+        }
+    }
+    const int wave = tid >> 6;
+#pragma unroll
+    for (int a = 0; a < R; ++a) {
+        float v = a < A ? acc[a < A ? a : 0] : gsum[a < A ? 0 : a - A];
+        for (int o = 1; o < 64; o <<= 1) v = v + __shfl_xor(v, o, 64);
+        if ((tid & 63) == 0) red[wave][a] = v;
+    }
+    __syncthreads();
+    const int64_t Cv = g.Cout * g.cin_g;
+    for (int e = tid; e < R; e += DW_THREADS) {
+        float sum = red[0][e];
+        for (int wv = 1; wv < DW_THREADS / 64; ++wv) sum = sum + red[wv][e];
+        if (e < A) {
+            const int j = e / (CIB * T), r = e - j * CIB * T;
+            const int c = r / T, t = r - c * T;
+            if (j < live_j && c < live_c) work[((int64_t)split * Cv + (co0 + j) * g.cin_g + c0 + c) * (T + 1) + t] = sum;
+        } else {
+            const int j = e - A;
+            if (j < live_j && cb == 0) work[((int64_t)split * Cv + (co0 + j) * g.cin_g) * (T + 1) + T] = sum;
+        }
+    }
+}
+
+template <int COB, int CIB>
+GcTilePlan gc_tile_plan(const GcGeom& g) {
+    GcTilePlan tp{};
+    tp.nco = (g.cout_g + COB - 1) / COB;
+    tp.nci = (g.cin_g + CIB - 1) / CIB;
+    tp.units = (int)(((int64_t)g.N * g.Ho * g.Wo + DW_THREADS - 1) / DW_THREADS);
+    const int64_t blocks = (int64_t)g.G * tp.nco * tp.nci;
+    int64_t s = (GC_TARGET_REDUCE + blocks - 1) / blocks;
+    if (s > tp.units) s = tp.units;
+    tp.splits = (int)(s < 1 ? 1 : s);
+    return tp;
+}
+
+// register blocks of the tiled stage 1: 144 partial sums per lane at 3 x 3, 64 at 1 x 1
+constexpr int GC_T3_COB = 4, GC_T3_CIB = 4, GC_T1_COB = 8, GC_T1_CIB = 8;
+
+// stage 2: the splits in index order, the STE mask on the unquantised weight, the bias gradient from the ci == 0 channel
+__global__ __launch_bounds__(DW_THREADS) void gc_grad_weight_combine_kernel(const float* __restrict__ work, const float* __restrict__ w,
+                                                                            float* __restrict__ gw, float* __restrict__ gbias,
+                                                                            int64_t Cv, int cin_g, int kk, int splits, float thr) {
+    const int per = kk + 1;
+    const int64_t total = Cv * per;
+    for (int64_t e = (int64_t)blockIdx.x * DW_THREADS + threadIdx.x; e < total; e += (int64_t)gridDim.x * DW_THREADS) {
+        const int64_t v = e / per;
+        const int t = (int)(e - v * per);
+        if (t == kk && (!gbias || v % cin_g != 0)) continue;
+        float s = 0.0f;
+        for (int sp = 0; sp < splits; ++sp) s = s + work[((int64_t)sp * Cv + v) * per + t];
+        if (t < kk) {
+            if (thr > 0.0f && fabsf(w[v * kk + t]) > thr) s = 0.0f;
+            gw[v * kk + t] = s;
+        } else {
+            gbias[v / cin_g] = s;
+        }
+    }
+}
+
+// validates the shape arguments and fills g; QT_OK with *empty set when there is nothing to compute
+int gc_geometry(int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph,
+                int pw, int dh, int dw, GcGeom* g, bool* empty) {
+    *empty = false;
+    if (N < 0 || G < 0 || cin_g < 1 || cout_g < 1 || H < 0 || W < 0 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || ph < 0 || pw < 0 ||
+        dh < 1 || dw < 1)
+        return QT_ERR_INVALID_ARG;
+    if ((int64_t)kh * kw > GC_MAX_TAPS) return QT_ERR_UNSUPPORTED;
+    if (N == 0 || G == 0 || H == 0 || W == 0) {
+        *empty = true;
+        return QT_OK;
+    }
+    if (cin_g > GC_MAX_CIN_G || cin_g * kh * kw > GC_MAX_K) return QT_ERR_UNSUPPORTED;
+    if (N >= GC_MAX_ELEMS || G >= GC_MAX_ELEMS || H >= GC_MAX_ELEMS || W >= GC_MAX_ELEMS || cout_g >= GC_MAX_ELEMS || ph >= (1 << 24) ||
+        pw >= (1 << 24) || dh >= (1 << 24) || dw >= (1 << 24))
+        return QT_ERR_UNSUPPORTED;
+    if (H + 2 * (int64_t)ph >= GC_MAX_ELEMS || W + 2 * (int64_t)pw >= GC_MAX_ELEMS) return QT_ERR_UNSUPPORTED;     // tap coordinates are int
+    const int64_t eh = H + 2 * (int64_t)ph - (int64_t)dh * (kh - 1) - 1, ew = W + 2 * (int64_t)pw - (int64_t)dw * (kw - 1) - 1;
+    if (eh < 0 || ew < 0) return QT_ERR_INVALID_ARG;          // the kernel does not fit the padded image
+    const int64_t Ho = eh / sh + 1, Wo = ew / sw + 1;
+    const double cin = (double)G * (double)cin_g, cout = (double)G * (double)cout_g;
+    if ((double)N * cin * (double)H * (double)W >= (double)GC_MAX_ELEMS || (double)N * cout * (double)Ho * (double)Wo >= (double)GC_MAX_ELEMS ||
+        cout > (double)GC_MAX_CHANNELS)
+        return QT_ERR_UNSUPPORTED;
+    g->N = (int)N; g->G = (int)G; g->cin_g = (int)cin_g; g->cout_g = (int)cout_g; g->H = (int)H; g->W = (int)W; g->Ho = (int)Ho; g->Wo = (int)Wo;
+    g->kh = kh; g->kw = kw; g->sh = sh; g->sw = sw; g->ph = ph; g->pw = pw; g->dh = dh; g->dw = dw;
+    g->Cin = G * cin_g;
+    g->Cout = G * cout_g;
+    return QT_OK;
+}
+
+bool gc_kind_ok(int kind) { return kind == QT_DW_RAW || kind == QT_DW_SIGN || kind == QT_DW_TERNARY; }
+
+#define GC_LAUNCH_CB(KERNEL, KH, KW, pl, ...)                                                      \
+    do {                                                                                           \
+        if ((pl).cb == 16) KERNEL<KH, KW, 16><<<grid, DW_THREADS, lds, s>>>(__VA_ARGS__);          \
+        else if ((pl).cb == 8) KERNEL<KH, KW, 8><<<grid, DW_THREADS, lds, s>>>(__VA_ARGS__);       \
+        else KERNEL<KH, KW, 4><<<grid, DW_THREADS, lds, s>>>(__VA_ARGS__);                         \
+    } while (0)
+
+#define GC_DISPATCH(KERNEL, g, pl, ...)                                                            \
+    do {                                                                                           \
+        if ((g).kh == 1 && (g).kw == 1) GC_LAUNCH_CB(KERNEL, 1, 1, pl, __VA_ARGS__);               \
+        else if ((g).kh == 3 && (g).kw == 3) GC_LAUNCH_CB(KERNEL, 3, 3, pl, __VA_ARGS__);          \
+        else GC_LAUNCH_CB(KERNEL, 0, 0, pl, __VA_ARGS__);                                          \
+    } while (0)
+
+inline DwMap gc_reduce_plan(const GcGeom& g, int cl) { return dw_plan(cl, g.N, g.Cout * g.cin_g, g.Ho, g.Wo, GC_TARGET_REDUCE); }
+inline int64_t gc_work_floats(const GcGeom& g, int splits) { return (int64_t)splits * g.Cout * g.cin_g * (g.kh * g.kw + 1); }
+// 1: the 1 x 1 tile kernel, 3: the 3 x 3 one, 0: the virtual-channel kernel
+inline int gc_tiled(const GcGeom& g) { return g.kh == 1 && g.kw == 1 ? 1 : (g.kh == 3 && g.kw == 3 ? 3 : 0); }
+// splits of the stage 1 that runs for this geometry and layout of go
+inline int gc_reduce_splits(const GcGeom& g, int cl) {
+    const int tiled = gc_tiled(g);
+    if (tiled == 1) return gc_tile_plan<GC_T1_COB, GC_T1_CIB>(g).splits;
+    if (tiled == 3) return gc_tile_plan<GC_T3_COB, GC_T3_CIB>(g).splits;
+    return gc_reduce_plan(g, cl).splits;
+}
+
+}  // namespace
+
+extern "C" int qt_gconv2d_f32(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t G, int64_t cin_g,
+                              int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                              int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, int64_t ys_n, int64_t ys_c, int64_t ys_h,
+                              int64_t ys_w, int kind, qt_stream_t stream) {
+    GcGeom g{};
+    bool empty;
+    const int rc = gc_geometry(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
+    if (rc != QT_OK || empty) return rc;
+    if (!gc_kind_ok(kind)) return QT_ERR_INVALID_ARG;
+    if (!x || !w || !y) return QT_ERR_INVALID_ARG;
+    const DwStrides xs{xs_n, xs_c, xs_h, xs_w}, ys{ys_n, ys_c, ys_h, ys_w};
+    if (dw_layout(N, g.Cin, H, W, xs) < 0 || dw_layout(N, g.Cout, g.Ho, g.Wo, ys) < 0) return QT_ERR_INVALID_ARG;
+    if (!dw_aligned4(x) || !dw_aligned4(w) || !dw_aligned4(y) || !dw_aligned4(bias)) return QT_ERR_ALIGNMENT;
+    const GcPlan pl = gc_plan(g, g.cout_g, (int64_t)g.N * g.Ho * g.Wo, g.cin_g);
+    const unsigned grid = (unsigned)((int64_t)g.G * pl.nblk * pl.splits);
+    const size_t lds = sizeof(float) * pl.cb * g.cin_g * kh * kw;
+    hipStream_t s = (hipStream_t)stream;
+    GC_DISPATCH(gc_forward_kernel, g, pl, x, w, bias, y, g, xs, ys, pl, kind);
+    return qt_check_launch();
+}
+
+extern "C" int qt_gconv2d_grad_input_f32(const float* go, const float* w, float* gx, int64_t N, int64_t G, int64_t cin_g,
+                                         int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                                         int dw, int64_t gs_n, int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c,
+                                         int64_t xs_h, int64_t xs_w, int kind, qt_stream_t stream) {
+    GcGeom g{};
+    bool empty;
+    const int rc = gc_geometry(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
+    if (rc != QT_OK || empty) return rc;
+    if (!gc_kind_ok(kind)) return QT_ERR_INVALID_ARG;
+    if (!go || !w || !gx) return QT_ERR_INVALID_ARG;
+    const DwStrides gs{gs_n, gs_c, gs_h, gs_w}, xs{xs_n, xs_c, xs_h, xs_w};
+    if (dw_layout(N, g.Cout, g.Ho, g.Wo, gs) < 0 || dw_layout(N, g.Cin, H, W, xs) < 0) return QT_ERR_INVALID_ARG;
+    if (!dw_aligned4(go) || !dw_aligned4(w) || !dw_aligned4(gx)) return QT_ERR_ALIGNMENT;
+    const GcPlan pl = gc_plan(g, g.cin_g, (int64_t)g.N * g.H * g.W, g.cout_g);
+    const unsigned grid = (unsigned)((int64_t)g.G * pl.nblk * pl.splits);
+    const size_t lds = sizeof(float) * pl.jc * pl.cb * kh * kw;
+    hipStream_t s = (hipStream_t)stream;
+    GC_DISPATCH(gc_grad_input_kernel, g, pl, go, w, gx, g, gs, xs, pl, kind);
+    return qt_check_launch();
+}
+
+extern "C" int64_t qt_gconv2d_grad_weight_work_floats(int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W,
+                                                      int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw) {
+    GcGeom g{};
+    bool empty;
+    const int rc = gc_geometry(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
+    if (rc != QT_OK) return rc;
+    if (empty) return 0;
+    // either layout of the gradient: the larger of the two plans
+    const int64_t a = gc_work_floats(g, gc_reduce_splits(g, 0)), b = gc_work_floats(g, gc_reduce_splits(g, 1));
+    return a > b ? a : b;
+}
+
+extern "C" int qt_gconv2d_grad_weight_f32(const float* go, const float* x, const float* w, float* gw, float* gbias, float* work,
+                                          int64_t work_floats, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H,
+                                          int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n,
+                                          int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h,
+                                          int64_t xs_w, float ste_threshold, qt_stream_t stream) {
+    GcGeom g{};
+    bool empty;
+    const int rc = gc_geometry(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
+    if (rc != QT_OK) return rc;
+    if (empty) return QT_OK;          // nothing is written: the caller owns the zero gradient of an empty batch
+    if (!gw || (ste_threshold > 0.0f && !w) || !(ste_threshold >= 0.0f)) return QT_ERR_INVALID_ARG;
+    if (!go || !x || !work || work_floats < 0) return QT_ERR_INVALID_ARG;
+    const DwStrides gs{gs_n, gs_c, gs_h, gs_w}, xs{xs_n, xs_c, xs_h, xs_w};
+    const int lg = dw_layout(N, g.Cout, g.Ho, g.Wo, gs);
+    if (lg < 0 || dw_layout(N, g.Cin, H, W, xs) < 0) return QT_ERR_INVALID_ARG;
+    const int splits = gc_reduce_splits(g, lg);
+    if (work_floats < gc_work_floats(g, splits)) return QT_ERR_INVALID_ARG;
+    if (!dw_aligned4(gw) || !dw_aligned4(gbias) || !dw_aligned4(w) || !dw_aligned4(go) || !dw_aligned4(x) || !dw_aligned4(work))
+        return QT_ERR_ALIGNMENT;
+    hipStream_t s = (hipStream_t)stream;
+    const int kk = kh * kw;
+    const int64_t Cv = g.Cout * g.cin_g;
+    const int tiled = gc_tiled(g);
+    if (tiled == 1) {
+        const GcTilePlan tp = gc_tile_plan<GC_T1_COB, GC_T1_CIB>(g);
+        const unsigned grid = (unsigned)((int64_t)g.G * tp.nco * tp.nci * tp.splits);
+        gc_grad_weight_tile_kernel<1, 1, GC_T1_COB, GC_T1_CIB><<<grid, DW_THREADS, 0, s>>>(go, x, work, g, gs, xs, tp);
+    } else if (tiled == 3) {
+        const GcTilePlan tp = gc_tile_plan<GC_T3_COB, GC_T3_CIB>(g);
+        const unsigned grid = (unsigned)((int64_t)g.G * tp.nco * tp.nci * tp.splits);
+        gc_grad_weight_tile_kernel<3, 3, GC_T3_COB, GC_T3_CIB><<<grid, DW_THREADS, 0, s>>>(go, x, work, g, gs, xs, tp);
+    } else {
+        const DwMap mp = gc_reduce_plan(g, lg);
+        const unsigned grid = (unsigned)(mp.cgs * mp.splits);
+        gc_grad_weight_kernel<<<grid, DW_THREADS, 0, s>>>(go, x, work, g, gs, xs, mp);
+    }
+    const int st = qt_check_launch();
+    if (st != QT_OK) return st;
+    gc_grad_weight_combine_kernel<<<qt_stream_grid((Cv * (kk + 1) + DW_THREADS - 1) / DW_THREADS), DW_THREADS, 0, s>>>(
+        work, w, gw, gbias, Cv, g.cin_g, kk, splits, ste_threshold);
+    return qt_check_launch();
+}

@@ -2017,6 +2017,63 @@ class DepthwiseConv2dFn(QtFunction):
         return grad_input, grad_weight, grad_bias, None, None, None, None
 
 
+# ---- grouped convs with a few channels per group -----------------------------------------------------------------------------------
+# K = cin_g * kh * kw <= 512 on a block-diagonal operand is no matrix-core shape either: one streaming launch forward, one per
+# gradient (csrc/gconv.hip, DESIGN.md "Grouped convs"), instead of one conv per group on copied slices.  As above, nothing asks
+# whether the activation is +-1.
+
+#: fewer groups keep the per-group loop: it is short and its tiles are reasonably full
+GROUPED_MIN_GROUPS = 4
+#: most input channels per group that take the grouped kernels; set from tools/bench_grouped.py by the rule of DESIGN.md "Grouped
+#: convs" (the largest measured cin_g of 4, 8, 16, 24 up to which a training step beats both the loop and the dense library and
+#: the forward is not behind the better of the two), never above 31.  Measured: 4 and 8 pass; at 16 the library wins the forward.
+GROUPED_MAX_CIN_G = 8
+
+
+def grouped_route(layer, input) -> bool:
+    """``layer`` (a Conv2d subclass with an fp32 weight) applied to ``input`` is a grouped conv the HIP kernels take: a 4-D fp32
+    device tensor, ``groups >= GROUPED_MIN_GROUPS`` with 2 ... ``GROUPED_MAX_CIN_G`` input channels each, padding mode "zeros"
+    with numeric padding."""
+    return (isinstance(input, torch.Tensor) and input.is_cuda and input.dtype == torch.float32 and input.dim() == 4
+            and layer.weight.dtype == torch.float32 and layer.groups >= GROUPED_MIN_GROUPS and layer.padding_mode == "zeros"
+            and 2 <= int(layer.weight.shape[1]) <= GROUPED_MAX_CIN_G
+            and ops.grouped_applicable(input.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups))
+
+
+class GroupedConv2dFn(QtFunction):
+    """conv2d(x, Q(W), b, groups = G) with a few input channels per group: the sibling of ``DepthwiseConv2dFn``, same arguments.
+    Forward one launch; backward grad_input and grad_weight (partials + combine inside one call), the bias gradient being a
+    by-product of the latter."""
+
+    @staticmethod
+    def forward(ctx, input, weight, bias, kind, weight_q, ste, conv_args):
+        stride, padding, dilation, groups = conv_args
+        ctx.kind = kind if weight_q is None else "raw"
+        ctx.conv_args, ctx.ste, ctx.has_bias = conv_args, float(ste), bias is not None
+        input = _dense(input)
+        ctx.save_for_backward(input, weight, weight_q)
+        return ops.grouped_conv2d(input, weight if weight_q is None else weight_q, bias, stride, padding, dilation, groups, kind=ctx.kind)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        input, weight, weight_q = ctx.saved_tensors
+        stride, padding, dilation, groups = ctx.conv_args
+        go = _dense(grad_output)
+        grad_input = grad_weight = grad_bias = None
+        if ctx.needs_input_grad[0]:
+            grad_input = ops.grouped_conv2d_grad_input(input.shape, weight if weight_q is None else weight_q, go, stride, padding,
+                                                       dilation, groups, kind=ctx.kind,
+                                                       channels_last=input.is_contiguous(memory_format=torch.channels_last)
+                                                       and not input.is_contiguous())
+        want_bias = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_bias:
+            grad_weight, grad_bias = ops.grouped_conv2d_grad_weight(input, go, weight, stride, padding, dilation, groups,
+                                                                    ste_threshold=ctx.ste, want_bias=want_bias)
+            if not ctx.needs_input_grad[1]:
+                grad_weight = None
+        return grad_input, grad_weight, grad_bias, None, None, None, None
+
+
 def grouped_quant_conv(layer, input, kind: str, quant_op):
     """BinConv2d / TerConv2d with ``groups`` > 1 (layers/binary_layers.py:59-60,103-106 hand ``groups`` to F.conv2d): group g is
     an independent conv of its channel slice with its rows of the weight, and the element-wise quantisers (safeSign, the fixed

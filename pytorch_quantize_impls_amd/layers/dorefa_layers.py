@@ -170,6 +170,10 @@ class DorefaConv2d(_DorefaLayer, torch.nn.Conv2d, QLayer):
             # gradients; the gradient of the image flows on through weight_op's own backward, as on the RealConv2dFn route
             w = self.weight_op.forward(self.weight) if self.training else self.weight
             return _fused.DepthwiseConv2dFn.apply(input, w, self.bias, "raw", None, 0.0, args)
+        if _fused.grouped_route(self, input):
+            # at least GROUPED_MIN_GROUPS groups of a few input channels, any bit_width: the grouped kernels in the same way
+            w = self.weight_op.forward(self.weight) if self.training else self.weight
+            return _fused.GroupedConv2dFn.apply(input, w, self.bias, "raw", None, 0.0, args)
         if self._w1_route(input):
             if self.training:
                 return _fused.DorefaW1Conv2dFn.apply(input, self.weight, self.bias, args)

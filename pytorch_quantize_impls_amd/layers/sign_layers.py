@@ -190,20 +190,25 @@ class _SignConv2d(EvalSwapMixin, torch.nn.Conv2d, QLayer):
         return _fused.quant_conv2d_forward(input, self.weight, self.bias, *args, kind, weight_q=self.weight, weight_planes=wp,
                                            binary_input=pm1, padding_mode=self.padding_mode, half_ok=True)
 
-    def _depthwise_forward(self, input):
-        """``groups == in_channels`` on a device fp32 input (``_fused.depthwise_route``): the depthwise kernels, which quantise the
-        taps themselves — training with the layer's quantiser and its STE mask (a stochastic layer draws once for the whole
-        weight and hands the draw over), eval on the stored image; None for everything else, an off-grid eval weight included
-        (it keeps the counted library expression)."""
-        if not _fused.depthwise_route(self, input):
+    def _streaming_forward(self, input):
+        """``groups == in_channels`` (``_fused.depthwise_route``) or at least ``_fused.GROUPED_MIN_GROUPS`` groups of a few input
+        channels (``_fused.grouped_route``) on a device fp32 input: the depthwise / grouped kernels, which quantise the taps
+        themselves — training with the layer's quantiser and its STE mask (a stochastic layer draws once for the whole weight and
+        hands the draw over), eval on the stored image; None for everything else, an off-grid eval weight included (it keeps the
+        counted library expression)."""
+        if _fused.depthwise_route(self, input):
+            fn = _fused.DepthwiseConv2dFn
+        elif _fused.grouped_route(self, input):
+            fn = _fused.GroupedConv2dFn
+        else:
             return None
         args = (self.stride, self.padding, self.dilation, self.groups)
         if self.training:
             wq = None if self.deterministic else self._op.apply(self.weight.detach())
-            return _fused.DepthwiseConv2dFn.apply(input, self.weight, self.bias, self.kind, wq, _fused.ops.STE_THRESHOLD, args)
+            return fn.apply(input, self.weight, self.bias, self.kind, wq, _fused.ops.STE_THRESHOLD, args)
         if not self._eval_on_grid():
             return None
-        return _fused.DepthwiseConv2dFn.apply(input, self.weight, self.bias, "raw", self.weight.detach(), _fused.ops.STE_THRESHOLD, args)
+        return fn.apply(input, self.weight, self.bias, "raw", self.weight.detach(), _fused.ops.STE_THRESHOLD, args)
 
     def forward(self, input):
         """Eval mode without autograd on a HIP device: returns a deferred activation (``lazy.LazyActivation``: a Tensor
@@ -227,7 +232,7 @@ class _SignConv2d(EvalSwapMixin, torch.nn.Conv2d, QLayer):
             return torch.nn.functional.conv2d(input, w, self.bias, self.stride, self.padding,
                                               self.dilation, self.groups)
         if self.groups > 1 and self.padding_mode == "zeros" and input.dim() == 4 and not isinstance(self.padding, str):
-            y = self._depthwise_forward(input)                             # groups == in_channels: one streaming launch
+            y = self._streaming_forward(input)                             # depthwise / few channels per group: one streaming launch
             if y is None:
                 y = _fused.grouped_quant_conv(self, input, kind, self._op)     # every group on the groups == 1 routes
             if y is not None:

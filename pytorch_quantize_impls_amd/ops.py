@@ -4444,3 +4444,157 @@ def depthwise_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, wei
                   *_dw_strides(go.shape, _dw_channels_last(go)), *_dw_strides(x.shape, _dw_channels_last(x)), float(ste_threshold),
                   _stream(x.device))
     return gw, gb
+
+
+# ----------------------------------------------------------------------------------------------
+# grouped conv2d with a few channels per group: streaming kernels of csrc/gconv.hip, forward and both gradients
+# ----------------------------------------------------------------------------------------------
+
+GC_MAX_CIN_G = _lib.DEFINES["QT_GC_MAX_CIN_G"]
+GC_MAX_K = _lib.DEFINES["QT_GC_MAX_K"]
+
+
+def grouped_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
+    """A conv2d of an [N, G * cin_g, H, W] input with a [G * cout_g, cin_g, kh, kw] weight and ``groups == G`` that the grouped
+    entry points take: numeric padding, 1 <= cin_g <= ``GC_MAX_CIN_G``, kh * kw <= ``DW_MAX_TAPS``, cin_g * kh * kw <=
+    ``GC_MAX_K``, every tensor non-empty and below 2^31 elements, at most ``DW_MAX_CHANNELS`` output channels.  A pure function of
+    the shapes."""
+    if len(x_shape) != 4 or len(w_shape) != 4 or isinstance(padding, str):
+        return False
+    N, C, H, W = (int(v) for v in x_shape)
+    Cout, cin_g, kh, kw = (int(v) for v in w_shape)
+    G = int(groups)
+    if G < 1 or cin_g < 1 or C != G * cin_g or Cout < G or Cout % G != 0 or min(N, H, W, kh, kw) < 1:
+        return False
+    try:
+        (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
+    except (TypeError, IndexError, ValueError):
+        return False
+    if min(sh, sw, dh, dw) < 1 or min(ph, pw) < 0 or max(ph, pw, dh, dw) >= 1 << 24 or Cout > DW_MAX_CHANNELS:
+        return False
+    if cin_g > GC_MAX_CIN_G or kh * kw > DW_MAX_TAPS or cin_g * kh * kw > GC_MAX_K:
+        return False
+    Ho, Wo = conv_out_hw(H, W, kh, kw, (sh, sw), (ph, pw), (dh, dw))
+    if Ho < 1 or Wo < 1 or H + 2 * ph >= 1 << 31 or W + 2 * pw >= 1 << 31:
+        return False
+    return N * C * H * W < 1 << 31 and N * Cout * Ho * Wo < 1 << 31
+
+
+def _gc_geometry(x_shape, weight, stride, padding, dilation, groups):
+    _require(weight, "weight")
+    N, C, H, W = (int(v) for v in x_shape)
+    G = int(groups)
+    if weight.dim() != 4 or G < 1 or C != G * int(weight.shape[1]) or weight.shape[0] % G != 0 or weight.shape[0] < G:
+        raise ValueError(f"weight: expected [G * cout_g, C / G, kh, kw] for C = {C}, G = {G}, got {tuple(weight.shape)}")
+    if not grouped_applicable(x_shape, weight.shape, stride, padding, dilation, G) and min(N, C, H, W) > 0:
+        raise ValueError(f"not a grouped conv the HIP entry points take: input {tuple(x_shape)}, weight {tuple(weight.shape)}, "
+                         f"groups {G}, stride {stride}, padding {padding}, dilation {dilation}")
+    w = weight.detach()
+    w = w if w.is_contiguous() else w.contiguous()
+    Cout, cin_g, kh, kw = (int(v) for v in weight.shape)
+    (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
+    Ho, Wo = (conv_out_hw(H, W, kh, kw, (sh, sw), (ph, pw), (dh, dw)) if min(H, W) > 0 else (0, 0))
+    return w, (N, G, cin_g, Cout // G, H, W, kh, kw, sh, sw, ph, pw, dh, dw), (N, Cout, max(Ho, 0), max(Wo, 0))
+
+
+def grouped_conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1,
+                   groups: int = 1, kind: str = "raw", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """F.conv2d(x, Q(weight), bias, stride, padding, dilation, groups) for x [N, G * cin_g, H, W] fp32 (NCHW or channels-last) and
+    weight [G * cout_g, cin_g, kh, kw]; Q = ``kind`` ("raw" | "binary" | "ternary") is applied to the taps inside the one launch
+    (qt_gconv2d_f32).  The result has the layout of x, or is written into ``out``.  Bit-reproducible: +0 start, the group's input
+    channels ascending and the taps in row-major order inside each, one multiply and one add per term, out-of-image taps skipped,
+    bias last."""
+    x = _dw_operand(x, "input")
+    w, geom, y_shape = _gc_geometry(x.shape, weight, stride, padding, dilation, groups)
+    bias = _check_bias(bias, y_shape[1], x.device)
+    y = _dw_result(out, y_shape, x, "out")
+    if y.numel() == 0 or x.numel() == 0:
+        return y
+    with _on(x.device):
+        _lib.call("qt_gconv2d_f32", _p(x), _p(w), _p(bias), _p(y), *geom, *_dw_strides(x.shape, _dw_channels_last(x)),
+                  *_dw_strides(y.shape, _dw_channels_last(y)), DW_KINDS[kind], _stream(x.device))
+    return y
+
+
+def grouped_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_output: torch.Tensor, stride=1, padding=0, dilation=1,
+                              groups: int = 1, kind: str = "raw", channels_last: Optional[bool] = None,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient of ``grouped_conv2d`` with respect to x: a gather over the group's output channels (outermost) and the taps
+    (row-major) with the forward's arithmetic rules, no atomics (qt_gconv2d_grad_input_f32).  The result has the layout of
+    ``grad_output`` unless ``channels_last`` says otherwise, or is written into ``out``."""
+    w, geom, y_shape = _gc_geometry(input_shape, weight, stride, padding, dilation, groups)
+    go = _dw_operand(grad_output, "grad_output", y_shape)
+    if out is None:
+        cl = _dw_channels_last(go) if channels_last is None else bool(channels_last)
+        gx = torch.empty(tuple(input_shape), dtype=torch.float32, device=go.device,
+                         memory_format=torch.channels_last if cl else torch.contiguous_format)
+    else:
+        gx = _dw_result(out, input_shape, go, "out")
+    if gx.numel() == 0:
+        return gx
+    if go.numel() == 0:
+        return gx.zero_()
+    with _on(go.device):
+        _lib.call("qt_gconv2d_grad_input_f32", _p(go), _p(w), _p(gx), *geom, *_dw_strides(go.shape, _dw_channels_last(go)),
+                  *_dw_strides(gx.shape, _dw_channels_last(gx)), DW_KINDS[kind], _stream(go.device))
+    return gx
+
+
+def grouped_grad_weight_work_floats(input_shape, weight_shape, stride=1, padding=0, dilation=1, groups: int = 1) -> int:
+    """fp32 elements of workspace ``grouped_conv2d_grad_weight`` needs (qt_gconv2d_grad_weight_work_floats)."""
+    N, _C, H, W = (int(v) for v in input_shape)
+    G = int(groups)
+    (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
+    n = int(_lib.load().qt_gconv2d_grad_weight_work_floats(N, G, int(weight_shape[1]), int(weight_shape[0]) // max(G, 1), H, W,
+                                                           int(weight_shape[2]), int(weight_shape[3]), sh, sw, ph, pw, dh, dw))
+    if n < 0:
+        raise _lib.QtStatusError(f"qt_gconv2d_grad_weight_work_floats failed: {_lib.strerror(n)} (qt_status {n})")
+    return n
+
+
+def grouped_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, weight: torch.Tensor, stride=1, padding=0, dilation=1,
+                               groups: int = 1, ste_threshold: float = 0.0, want_bias: bool = False,
+                               out: Optional[torch.Tensor] = None, out_bias: Optional[torch.Tensor] = None,
+                               workspace: Optional[torch.Tensor] = None):
+    """Gradient of ``grouped_conv2d`` with respect to the weight, shaped like ``weight``, and — ``want_bias`` or ``out_bias`` — the
+    per-channel sum of ``grad_output`` from the same pass (else None): ``(grad_weight, grad_bias)``.  Two launches inside one call,
+    no atomics: partials per (split, output channel, input channel of the group, tap) into ``workspace``
+    (``grouped_grad_weight_work_floats`` fp32 elements; allocated when not given), then the splits in index order; equal inputs
+    give equal bits.  ``ste_threshold`` > 0 zeroes the entries where the UNquantised ``|weight|`` exceeds it (1.001 for the sign
+    families)."""
+    x = _dw_operand(x, "input")
+    w, geom, y_shape = _gc_geometry(x.shape, weight, stride, padding, dilation, groups)
+    go = _dw_operand(grad_output, "grad_output", y_shape)
+    if go.device != x.device:
+        raise ValueError("input and grad_output are on different devices")
+    Cout = y_shape[1]
+    if out is None:
+        gw = torch.empty(tuple(weight.shape), dtype=torch.float32, device=x.device)
+    else:
+        gw = _require(out, "out")
+        if tuple(gw.shape) != tuple(weight.shape) or not gw.is_contiguous() or gw.device != x.device:
+            raise ValueError(f"out: expected a contiguous fp32 tensor of shape {tuple(weight.shape)} on {x.device}")
+    gb = None
+    if out_bias is not None:
+        gb = _require(out_bias, "out_bias")
+        if tuple(gb.shape) != (Cout,) or not gb.is_contiguous() or gb.device != x.device:
+            raise ValueError(f"out_bias: expected a contiguous fp32 tensor of shape ({Cout},) on {x.device}")
+    elif want_bias:
+        gb = torch.empty((Cout,), dtype=torch.float32, device=x.device)
+    if gw.numel() == 0:
+        return gw, gb
+    if go.numel() == 0 or x.numel() == 0:
+        gw.zero_()
+        return gw, (gb.zero_() if gb is not None else None)
+    need = grouped_grad_weight_work_floats(x.shape, weight.shape, stride, padding, dilation, groups)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.float32, device=x.device)
+    else:
+        _require(workspace, "workspace")
+        if not workspace.is_contiguous() or workspace.device != x.device or workspace.numel() < need:
+            raise ValueError(f"workspace: expected at least {need} contiguous fp32 elements on {x.device}")
+    with _on(x.device):
+        _lib.call("qt_gconv2d_grad_weight_f32", _p(go), _p(x), _p(w), _p(gw), _p(gb), _p(workspace), int(workspace.numel()), *geom,
+                  *_dw_strides(go.shape, _dw_channels_last(go)), *_dw_strides(x.shape, _dw_channels_last(x)), float(ste_threshold),
+                  _stream(x.device))
+    return gw, gb
