@@ -1418,6 +1418,51 @@ int qt_dwconv2d_bits_f32(const uint32_t* x_plane, int64_t ldx, const float* w, c
                          int64_t m, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                          int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, int kind, qt_stream_t stream);
 
+/* Grouped convolution on bit planes: the grouped forward (qt_gconv2d_f32) inside the same fused inference chain, for groups of 2, 4
+ * or 8 input channels.  One launch each; no allocation, no synchronisation; csrc/gconv.hip, DESIGN.md "Grouped convs".
+ *
+ * Input.  x_plane is the NHWC sign plane of qt_dwconv2d_sign above over C = G cin_g channels (bit 1 <=> -1), ldx >=
+ * ops.packed_ld(G cin_g).  w fp32 [G cout_g, cin_g, kh, kw] and bias [G cout_g] or NULL as for qt_gconv2d_f32.  cin_g must be 2, 4 or
+ * 8, so that the cin_g operands of a group at one tap are a bit field of ONE plane word; cout_g >= 1 is free.
+ *
+ * Taps.  Every tap is classified to -1 / 0 / +1 inside the launch, from the fp32 image (no packed weight exists): `kind`
+ * QT_DW_SIGN and QT_DW_TERNARY apply the quantisers above and classify their result; QT_DW_RAW reads w > 0 -> +1, w < 0 -> -1,
+ * anything else (+-0, NaN) -> 0.
+ *
+ * Value.  With nz_t / neg_t the cin_g-bit masks "tap t of input channel ci is non-zero / negative" of an output channel and x_field
+ * the group's bits of the input pixel under tap t:
+ *   S = sum over the taps inside the image of ( popc(nz_t) - 2 popc((x_field ^ neg_t) & nz_t) ),   an integer, |S| <= 8 * 49;
+ *   y = fl((float)S + bias[co]),  or (float)S when bias is NULL (S == 0 gives +0).
+ * For weights ON the grid {-1, 0, +1} (with QT_DW_RAW; or any weight with QT_DW_SIGN / QT_DW_TERNARY), y equals BIT FOR BIT what
+ * qt_gconv2d_f32 stores for the decoded +-1 image with the same `kind`: every product there is -1, +-0 or +1 and every partial sum
+ * an integer below 2^24, so its fp32 additions are exact in any order.  For QT_DW_RAW weights off the grid only the
+ * classification above is promised.
+ *
+ * Output forms — exactly those of the depthwise plane entries:
+ *   qt_gconv2d_sign      the threshold bit [ fl(fl(y alpha[co]) + beta[co]) < 0 ] (two roundings; a tie, -0.0 and NaN give 0),
+ *                        alpha / beta fp32 [G cout_g], as sign_plane [N Ho Wo][ldb] and / or nib_plane [N (Ho + 2 out_halo_h)
+ *                        (Wo + 2 out_halo_w)][ldn] in the formats and with the bounds stated there (C m = G cout_g).  The launch
+ *                        writes EVERY word of every plane — channels past G cout_g, pad words, border pixels — and reads nothing
+ *                        back.  Either plane may be null, not both.
+ *   qt_gconv2d_bits_f32  y itself, fp32 [N, G cout_g, Ho, Wo] by its element strides ys_* (dense NCHW or channels-last), for a
+ *                        deferred grouped conv whose input exists only as planes.
+ *
+ * Limits: those of the grouped entries above, cin_g in {2, 4, 8}, out_halo_* <= 64 and fewer than 2^31 pixel rows in nib_plane;
+ * beyond them QT_ERR_UNSUPPORTED.  Validation before anything is enqueued, in this order:
+ *   1. a negative halo, then step 1 of the grouped entries.
+ *   2. for a problem that is not empty step 3 of the grouped entries; then cin_g outside {2, 4, 8}: QT_ERR_UNSUPPORTED.
+ *   3. N, G, H or W zero: QT_OK, nothing is written.   4. a halo above 64, too many pixel rows: QT_ERR_UNSUPPORTED.
+ *   5. an unknown `kind`, a null tensor (bias may be null), no output plane, a null alpha or beta, strides that are no dense layout,
+ *      ldx / ldb / ldn below the bounds: QT_ERR_INVALID_ARG; then a pointer that is not 4-byte aligned, ldn % 4 != 0 or a nib_plane
+ *      that is not 16-byte aligned: QT_ERR_ALIGNMENT. */
+int qt_gconv2d_sign(const uint32_t* x_plane, int64_t ldx, const float* w, const float* bias, const float* alpha, const float* beta,
+                    uint32_t* sign_plane, int64_t ldb, uint32_t* nib_plane, int64_t ldn, int64_t out_halo_h, int64_t out_halo_w,
+                    int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw,
+                    int ph, int pw, int dh, int dw, int kind, qt_stream_t stream);
+int qt_gconv2d_bits_f32(const uint32_t* x_plane, int64_t ldx, const float* w, const float* bias, float* y, int64_t N, int64_t G,
+                        int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                        int dw, int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, int kind, qt_stream_t stream);
+
 /* Depthwise convolution on int8 code planes: the forward above inside the fused DoReFa inference chain conv -> BatchNorm -> [ReLU]
  * -> nnDorefaQuant(k) -> next conv, reading the int8 code plane a CodeActivation carries and writing the next one.  One launch
  * each; no allocation, no synchronisation.

@@ -1,5 +1,6 @@
 // Grouped conv2d with a few channels per group (1 <= cin_g <= 32, K = cin_g * kh * kw <= 512) in fp32: forward, grad_input,
-// grad_weight.  include/qt_hip.h "Grouped convolution" states the contract; DESIGN.md "Grouped convs" the layout and the counts.
+// grad_weight — and the forward on / into the bit planes of the fused sign chain (gc_planes_kernel, further down).
+// include/qt_hip.h "Grouped convolution" states the contract; DESIGN.md "Grouped convs" the layout and the counts.
 //
 // Streaming kernels on the vector units, siblings of dwconv.hip: K is no matrix-core shape and the block-diagonal operand would
 // waste `groups` times the tile.  What separates them from cout_g depthwise passes is the register block: a lane owns ONE pixel
@@ -23,6 +24,7 @@
 // in the order stated above, taps outside the image skipped, bias last.  No atomics anywhere: equal inputs give equal bits.
 #include "qt_common.h"
 #include "dw_map.h"
+#include "dw_planes.h"
 
 namespace {
 
@@ -518,6 +520,187 @@ bool gc_kind_ok(int kind) { return kind == QT_DW_RAW || kind == QT_DW_SIGN || ki
         else GC_LAUNCH_CB(KERNEL, 0, 0, pl, __VA_ARGS__);                                          \
     } while (0)
 
+// ---- the forward on / into bit planes (include/qt_hip.h "Grouped convolution on bit planes") ---------------------------------------
+// The input is the NHWC sign plane of a +-1 activation and every tap is classified to -1 / 0 / +1, so the cin_g operands of a group
+// at one tap are a cin_g-bit FIELD of one plane word (cin_g in {2, 4, 8}: a field never straddles a word) and the group's dot
+// product at that tap is  popc(nz) - 2 popc((field ^ neg) & nz)  with the tap's masks nz (weight != 0) and neg (weight < 0): one
+// XOR, one AND and a popcount instead of cin_g multiply-adds.  The sum S over the taps inside the image is an integer of magnitude
+// <= 8 * 49, so (float)S is what any order of fp32 additions of the +-1 products gives, and fl((float)S + bias) has the bits
+// qt_gconv2d_f32 stores for the decoded image.
+// The map is that of dw_planes_kernel: a HALF-wave owns one 32-channel output word of one pixel, a workgroup (plane word, split)
+// walks 8 pixels per step, so a lane keeps ONE output channel for the whole launch — its (neg, nz) masks of all taps (two taps per
+// register: at most 25), bias, alpha and beta.  Lane co reads input word (g cin_g) >> 5 at shift (g cin_g) & 31, g = co / cout_g.
+// The 1 x 1 and 3 x 3 forms are branch-free: all tap loads go out together, a tap outside the image loads the nearest pixel inside
+// and contributes through a select on its nz mask; dead lanes and pixels past the end compute on pixel 0 and are not stored.  The
+// writing stage is dw_planes.h.  (Tried: a whole wave per pixel, so that the tap coordinates and row addresses run on the scalar
+// unit — slower at every measured shape, DESIGN.md "Grouped convs", "Tried".)
+
+template <int KH, int KW>
+__global__ __launch_bounds__(DW_THREADS) void gc_planes_kernel(const uint32_t* __restrict__ xb, int64_t ldx, const float* __restrict__ w,
+                                                               const float* __restrict__ bias, const float* __restrict__ alpha,
+                                                               const float* __restrict__ beta, DwPlaneOut o, DwGeom g, int cin_g,
+                                                               int cout_g, DwStrides ys, int units, int splits, int d_n, int d_ho, int d_wo,
+                                                               int kind) {
+    constexpr bool GEN = KH == 0;
+    constexpr int CAP = GEN ? GC_MAX_TAPS : KH * KW;
+    const int tid = threadIdx.x, lane = tid & 31;
+    const int wd = (int)(blockIdx.x / splits);
+    const int split = (int)(blockIdx.x - (unsigned)wd * splits);
+    const int64_t co = (int64_t)wd * 32 + lane;
+    const bool live = co < g.Cout;
+    const int kw = GEN ? g.kw : KW, kk = GEN ? g.kh * g.kw : KH * KW;
+    // tap t: nz in bits 0 .. 7 and neg in bits 8 .. 15 of half (t & 1) of pk[t >> 1]
+    uint32_t pk[(CAP + 1) / 2];
+#pragma unroll
+    for (int r = 0; r < (CAP + 1) / 2; ++r) pk[r] = 0u;
+    if (live) {
+        for (int ci = 0; ci < cin_g; ++ci) {
+            const float* wp = w + (co * cin_g + ci) * kk;
+            float wv[CAP];                                       // the loads of a channel go out together, then the (branching) quantiser
+#pragma unroll
+            for (int t = 0; t < CAP; ++t) wv[t] = (!GEN || t < kk) ? wp[t] : 0.0f;
+#pragma unroll
+            for (int t = 0; t < CAP; ++t) {
+                if (!GEN || t < kk) {
+                    const float q = dw_quant(kind, wv[t]);
+                    const uint32_t cls = ((q > 0.0f || q < 0.0f) ? 1u : 0u) | (q < 0.0f ? 0x100u : 0u);
+                    pk[t >> 1] |= cls << (ci + 16 * (t & 1));
+                }
+            }
+        }
+    }
+    const float b = (live && bias) ? bias[co] : 0.0f;
+    const float al = (live && alpha) ? alpha[co] : 0.0f, be = (live && beta) ? beta[co] : 0.0f;
+    const int c0 = live ? (int)(co / cout_g) * cin_g : 0;          // first input channel of the lane's group
+    const int xw = c0 >> 5, xsh = c0 & 31;
+    const int hw = g.Ho * g.Wo;
+    const int64_t npix = (int64_t)g.N * hw;
+    // the first pixel of this half-wave is divided out once; a step advances it by splits * 8 pixels = (d_n, d_ho, d_wo) images,
+    // rows and columns with two carries (the walk of dw_codes_kernel): no division per output
+    int64_t next = (int64_t)split * DW_PIX_PER_STEP + (tid >> 5);
+    int rn = 0, rho = 0, rwo = 0;
+    if (next < npix) {
+        const int p = (int)next;
+        rn = p / hw;
+        const int r = p - rn * hw;
+        rho = r / g.Wo;
+        rwo = r - rho * g.Wo;
+    }
+    for (int u = split; u < units; u += splits) {
+        const int64_t pix = next;
+        const bool in = pix < npix;
+        const int n = in ? rn : 0, ho = in ? rho : 0, wo = in ? rwo : 0;
+        next += (int64_t)splits * DW_PIX_PER_STEP;
+        rwo += d_wo;
+        const int c1 = rwo >= g.Wo;
+        rwo -= c1 ? g.Wo : 0;
+        rho += d_ho + c1;
+        const int c2 = rho >= g.Ho;
+        rho -= c2 ? g.Ho : 0;
+        rn += d_n + c2;
+        const int h0 = ho * g.sh - g.ph, w0 = wo * g.sw - g.pw;
+        const uint32_t* xn = xb + (int64_t)n * g.H * g.W * ldx + xw;
+        int S = 0;
+        if (!GEN) {
+            uint32_t word[CAP];
+            bool ok[CAP];
+#pragma unroll
+            for (int t = 0; t < CAP; ++t) {
+                const int i = t / (GEN ? 1 : KW), j = t - i * (GEN ? 1 : KW);
+                const int hi = h0 + i * g.dh, wi = w0 + j * g.dw;
+                ok[t] = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
+                const int hc = hi < 0 ? 0 : (hi >= g.H ? g.H - 1 : hi), wc = wi < 0 ? 0 : (wi >= g.W ? g.W - 1 : wi);
+                word[t] = xn[((int64_t)hc * g.W + wc) * ldx];
+            }
+#pragma unroll
+            for (int t = 0; t < CAP; ++t) {
+                const uint32_t m = pk[t >> 1] >> (16 * (t & 1));
+                const uint32_t nz = ok[t] ? (m & 0xFFu) : 0u;
+                S += __popc(nz) - 2 * __popc(((word[t] >> xsh) ^ (m >> 8)) & nz);
+            }
+        } else {
+            int i = 0, j = 0;
+#pragma unroll
+            for (int t = 0; t < CAP; ++t) {
+                if (t < kk) {
+                    const int hi = h0 + i * g.dh, wi = w0 + j * g.dw;
+                    const bool ok = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
+                    const int hc = hi < 0 ? 0 : (hi >= g.H ? g.H - 1 : hi), wc = wi < 0 ? 0 : (wi >= g.W ? g.W - 1 : wi);
+                    const uint32_t word = xn[((int64_t)hc * g.W + wc) * ldx];
+                    const uint32_t m = pk[t >> 1] >> (16 * (t & 1));
+                    const uint32_t nz = ok ? (m & 0xFFu) : 0u;
+                    S += __popc(nz) - 2 * __popc(((word >> xsh) ^ (m >> 8)) & nz);
+                    if (++j == kw) { j = 0; ++i; }
+                }
+            }
+        }
+        float acc = (float)S;
+        if (bias) acc = acc + b;
+        if (o.y) {                                   // uniform over the launch
+            if (in && live) o.y[n * ys.n + co * ys.c + ho * ys.h + wo * ys.w] = acc;
+            continue;
+        }
+        // two roundings (the build has -ffp-contract=off), as in dw_planes_kernel; dead lanes vote 0
+        const int neg = (in && live) ? (int)qt_neg_bit(acc * al + be) : 0;
+        const unsigned long long votes = __ballot(neg);
+        if (lane != 0 || !in) continue;
+        dw_store_word(o, g, wd, pix, n, ho, wo, (uint32_t)(votes >> (tid & 32)));
+    }
+    if (!o.y) dw_zero_border(o, g, tid);
+}
+
+// the shared body of the two plane entries: o.y, or at least one of o.sign / o.nib
+int gc_planes_launch(const uint32_t* x_plane, int64_t ldx, const float* w, const float* bias, const float* alpha, const float* beta,
+                     DwPlaneOut o, bool f32, int64_t halo_h, int64_t halo_w, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H,
+                     int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, DwStrides ys, int kind,
+                     qt_stream_t stream) {
+    GcGeom gg{};
+    bool empty;
+    if (halo_h < 0 || halo_w < 0) return QT_ERR_INVALID_ARG;
+    const int rc = gc_geometry(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &gg, &empty);
+    if (rc != QT_OK) return rc;
+    if (cin_g != 2 && cin_g != 4 && cin_g != 8) return QT_ERR_UNSUPPORTED;      // a group's field must not straddle a plane word
+    if (empty) return QT_OK;
+    if (halo_h > DW_MAX_HALO || halo_w > DW_MAX_HALO) return QT_ERR_UNSUPPORTED;
+    if (o.nib && (double)N * (double)(gg.Ho + 2 * halo_h) * (double)(gg.Wo + 2 * halo_w) >= (double)GC_MAX_ELEMS) return QT_ERR_UNSUPPORTED;
+    if (!gc_kind_ok(kind)) return QT_ERR_INVALID_ARG;
+    if (!x_plane || !w) return QT_ERR_INVALID_ARG;
+    if (f32) {
+        if (!o.y || dw_layout(N, gg.Cout, gg.Ho, gg.Wo, ys) < 0) return QT_ERR_INVALID_ARG;
+    } else {
+        if ((!o.sign && !o.nib) || !alpha || !beta) return QT_ERR_INVALID_ARG;
+        if (o.sign && o.ldb < dw_packed_ld(gg.Cout)) return QT_ERR_INVALID_ARG;
+        if (o.nib && o.ldn < dw_pixel_ld_nib(gg.Cout)) return QT_ERR_INVALID_ARG;
+    }
+    if (ldx < dw_packed_ld(gg.Cin)) return QT_ERR_INVALID_ARG;
+    if (!dw_aligned4(x_plane) || !dw_aligned4(w) || !dw_aligned4(bias) || !dw_aligned4(alpha) || !dw_aligned4(beta) || !dw_aligned4(o.y) ||
+        !dw_aligned4(o.sign))
+        return QT_ERR_ALIGNMENT;
+    if (o.nib && ((o.ldn & 3) || !dw_aligned16(o.nib))) return QT_ERR_ALIGNMENT;
+    o.hy = (int)halo_h;
+    o.hx = (int)halo_w;
+    DwGeom g{};                                     // the record the writing stage reads; m is not used
+    g.N = gg.N; g.C = (int)gg.Cin; g.H = gg.H; g.W = gg.W; g.Ho = gg.Ho; g.Wo = gg.Wo;
+    g.kh = kh; g.kw = kw; g.sh = sh; g.sw = sw; g.ph = ph; g.pw = pw; g.dh = dh; g.dw = dw;
+    g.Cout = gg.Cout;
+    const int64_t npix = (int64_t)g.N * g.Ho * g.Wo;
+    const int64_t nw = (g.Cout + 31) / 32;
+    const int units = (int)((npix + DW_PIX_PER_STEP - 1) / DW_PIX_PER_STEP);
+    int64_t sp = (GC_TARGET_STREAM + nw - 1) / nw;
+    if (sp > units) sp = units;
+    const int splits = (int)(sp < 1 ? 1 : sp);
+    const unsigned grid = (unsigned)(nw * splits);
+    const int64_t step = (int64_t)splits * DW_PIX_PER_STEP;
+    const int d_wo = (int)(step % g.Wo), d_ho = (int)((step / g.Wo) % g.Ho), d_n = (int)(step / g.Wo / g.Ho);
+    hipStream_t s = (hipStream_t)stream;
+#define GC_PLANES_ARGS x_plane, ldx, w, bias, alpha, beta, o, g, gg.cin_g, gg.cout_g, ys, units, splits, d_n, d_ho, d_wo, kind
+    if (kh == 1 && kw == 1) gc_planes_kernel<1, 1><<<grid, DW_THREADS, 0, s>>>(GC_PLANES_ARGS);
+    else if (kh == 3 && kw == 3) gc_planes_kernel<3, 3><<<grid, DW_THREADS, 0, s>>>(GC_PLANES_ARGS);
+    else gc_planes_kernel<0, 0><<<grid, DW_THREADS, 0, s>>>(GC_PLANES_ARGS);
+#undef GC_PLANES_ARGS
+    return qt_check_launch();
+}
+
 inline DwMap gc_reduce_plan(const GcGeom& g, int cl) { return dw_plan(cl, g.N, g.Cout * g.cin_g, g.Ho, g.Wo, GC_TARGET_REDUCE); }
 inline int64_t gc_work_floats(const GcGeom& g, int splits) { return (int64_t)splits * g.Cout * g.cin_g * (g.kh * g.kw + 1); }
 // 1: the 1 x 1 tile kernel, 3: the 3 x 3 one, 0: the virtual-channel kernel
@@ -627,4 +810,28 @@ extern "C" int qt_gconv2d_grad_weight_f32(const float* go, const float* x, const
     gc_grad_weight_combine_kernel<<<qt_stream_grid((Cv * (kk + 1) + DW_THREADS - 1) / DW_THREADS), DW_THREADS, 0, s>>>(
         work, w, gw, gbias, Cv, g.cin_g, kk, splits, ste_threshold);
     return qt_check_launch();
+}
+
+extern "C" int qt_gconv2d_sign(const uint32_t* x_plane, int64_t ldx, const float* w, const float* bias, const float* alpha,
+                               const float* beta, uint32_t* sign_plane, int64_t ldb, uint32_t* nib_plane, int64_t ldn,
+                               int64_t out_halo_h, int64_t out_halo_w, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H,
+                               int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int kind,
+                               qt_stream_t stream) {
+    DwPlaneOut o{};
+    o.sign = sign_plane;
+    o.ldb = ldb;
+    o.nib = nib_plane;
+    o.ldn = ldn;
+    return gc_planes_launch(x_plane, ldx, w, bias, alpha, beta, o, false, out_halo_h, out_halo_w, N, G, cin_g, cout_g, H, W, kh, kw, sh,
+                            sw, ph, pw, dh, dw, DwStrides{0, 0, 0, 0}, kind, stream);
+}
+
+extern "C" int qt_gconv2d_bits_f32(const uint32_t* x_plane, int64_t ldx, const float* w, const float* bias, float* y, int64_t N,
+                                   int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw,
+                                   int ph, int pw, int dh, int dw, int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, int kind,
+                                   qt_stream_t stream) {
+    DwPlaneOut o{};
+    o.y = y;
+    return gc_planes_launch(x_plane, ldx, w, bias, nullptr, nullptr, o, true, 0, 0, N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh,
+                            dw, DwStrides{ys_n, ys_c, ys_h, ys_w}, kind, stream);
 }

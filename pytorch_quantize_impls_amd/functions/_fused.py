@@ -921,6 +921,24 @@ def codes_depthwise_conv2d(layer, act):
                                            flagged=not ops._cfg("ASSUME_CODES_FIT"))
 
 
+def packed_grouped_conv2d(layer, act):
+    """Eval-mode BinConv2d / TerConv2d with ``1 < groups < in_channels`` on a PackedActivation (NHWC bit planes): the fp32
+    [N, G * cout_g, Ho, Wo] result in NCHW storage, bias added, from one launch on the planes (ops.grouped_conv2d_from_bits) — what a
+    deferred grouped conv whose input exists only as planes materialises to.  The stored eval image is classified by its sign."""
+    if layer.training:
+        raise RuntimeError("PackedActivation inputs are an inference feature: call .eval() first")
+    if act.planes is None:
+        raise ValueError("a grouped conv reads bit planes; this activation was produced as another conv's nibble operand")
+    if (layer.padding_mode != "zeros" or len(act.shape) != 4 or layer.groups < GROUPED_MIN_GROUPS
+            or not ops.grouped_planes_applicable(act.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups)):
+        raise ValueError(f"packed grouped conv needs at least {GROUPED_MIN_GROUPS} groups of 2, 4 or 8 input channels, numeric zero "
+                         "padding and a shape inside the kernels' limits")
+    if not layer._eval_on_grid():
+        raise ValueError("packed grouped conv needs an eval-mode weight on the quantiser's grid")
+    return ops.grouped_conv2d_from_bits(act.planes, act.shape, layer.weight.detach(), layer.bias, layer.stride, layer.padding,
+                                        layer.dilation, layer.groups, kind="raw")
+
+
 def packed_xnor_conv2d(layer, act, epi=None):
     """Eval-mode XNORConv2d on a PackedActivation: the per-tap scaled fp4 conv (ops.conv2d_nib_taps) on the activation's nibble
     plane — the producer's own (zero halo = this conv's padding, un-padded kernel) when its pixel stride is whole 32-byte taps,

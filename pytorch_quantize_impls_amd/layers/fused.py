@@ -868,6 +868,89 @@ class FusedDepthwiseBnSign(torch.nn.Module):
         return act.flatten_hwc() if self.flatten_hwc else act
 
 
+class FusedGroupedBnSign(torch.nn.Module):
+    """Grouped BinConv2d / TerConv2d (eval; at least ``_fused.GROUPED_MIN_GROUPS`` groups of 2, 4 or 8 input channels, not depthwise)
+    + [MaxPool2d(k, s)] + eval BatchNorm2d + [Hardtanh] + BinaryConnect(det) -> PackedActivation: the grouped sibling of
+    ``FusedDepthwiseBnSign``.  ONE launch (qt_gconv2d_sign) reads the bit planes of a PackedActivation — a group's operand at a tap is
+    a bit field of one plane word, its dot product one XOR, AND and popcount — and writes the bit [y * alpha + beta < 0] as bit planes
+    or, with ``out_nib_halo`` set, as the consuming conv's nibble pixel plane with its padding as a zero border; y has the bits of
+    ``ops.grouped_conv2d`` on the decoded image.  A pool between conv and BatchNorm runs on the un-pooled bits.  There is no fp32
+    input form: an fp32 tensor is a TypeError (the un-fused layer runs it)."""
+
+    def __init__(self, conv, bn, pool=None, flatten_hwc=False, fold=None):
+        super().__init__()
+        from ..functions import _fused
+        from .binary_layers import BinConv2d
+        from .terner_layers import TerConv2d
+        if not isinstance(conv, (BinConv2d, TerConv2d)):
+            raise ValueError("FusedGroupedBnSign fuses grouped BinConv2d / TerConv2d only")
+        if conv.groups < _fused.GROUPED_MIN_GROUPS or conv.groups == conv.in_channels or conv.padding_mode != "zeros" \
+                or isinstance(conv.padding, str):
+            raise ValueError(f"only zero-padded convs with numeric padding and at least {_fused.GROUPED_MIN_GROUPS} groups of more than "
+                             "one input channel can be fused")
+        kh, kw = conv.kernel_size
+        dh, dw = ops._pairs(conv.dilation)
+        fits = (1, conv.in_channels, dh * (kh - 1) + 1, dw * (kw - 1) + 1)       # the smallest image the kernel fits
+        if not ops.grouped_planes_applicable(fits, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups):
+            raise ValueError("a grouped conv outside the limits of the plane kernel (ops.grouped_planes_applicable: 2, 4 or 8 input "
+                             "channels per group)")
+        if not isinstance(bn, torch.nn.BatchNorm2d) or bn.num_features != conv.out_channels:
+            raise ValueError("BatchNorm2d over the conv's output channels expected")
+        self._pool = FusedPoolBnSign(bn, pool, fold=fold)           # validates the pooling geometry, owns the fold cache
+        self.fold = self._pool.fold
+        self.conv, self.bn = conv, bn
+        self.flatten_hwc = flatten_hwc
+        self._neg_alpha = None
+        self.out_nib_halo = None        # see FusedConvPoolBnSign.out_nib_halo
+
+    def refold(self):
+        self._pool.refold()
+        self._neg_alpha = None
+
+    def forward(self, x):
+        if self.bn.training or self.conv.training:
+            raise RuntimeError("FusedGroupedBnSign is an inference module: call .eval() first")
+        conv, fp = self.conv, self._pool
+        x = lazy.resolve(x)
+        if not isinstance(x, packed.PackedActivation):
+            raise TypeError("FusedGroupedBnSign reads the bit planes of a PackedActivation only (the un-fused layer takes fp32 tensors)")
+        if x.planes is None:
+            raise ValueError("a grouped block reads bit planes; its producer was linked to hand over a nibble operand")
+        shape = x.shape
+        if len(shape) != 4 or not ops.grouped_planes_applicable(shape, conv.weight.shape, conv.stride, conv.padding, conv.dilation,
+                                                                conv.groups):
+            raise ValueError(f"not a grouped conv the plane kernel takes: input {tuple(shape)}")
+        if not conv._eval_on_grid():
+            raise ValueError("the eval-mode weight is off the quantiser's grid")
+        dev = conv.weight.device
+        N, _, H, W = (int(v) for v in shape)
+        Ho, Wo = ops.conv_out_hw(H, W, conv.kernel_size[0], conv.kernel_size[1], conv.stride, conv.padding, conv.dilation)
+        prev = fp._folded
+        like = None
+        if self.fold == "device":
+            # the tensor the module graph would hand to F.batch_norm: the grouped result — which takes the layout of the conv's
+            # fp32 input, here the +-1 tensor the planes stand for — pooled
+            like = ((N, conv.out_channels, (Ho - fp.pool_k) // fp.pool_s + 1, (Wo - fp.pool_k) // fp.pool_s + 1), _out_channels_last(x))
+        alpha, beta = _folded_for(fp, "_folded", self.bn, dev, self.fold, like)
+        if fp._folded is not prev or self._neg_alpha is None:      # BatchNorm changed (or first call): derived data too
+            self._neg_alpha = ops.neg_alpha_words(alpha)
+        pooled = fp.pool_k != 1 or fp.pool_s != 1
+        nib_out = self.out_nib_halo is not None and not self.flatten_hwc
+        Cout = conv.out_channels
+        args = (x.planes, conv.weight.detach(), conv.bias, alpha, beta, conv.stride, conv.padding, conv.dilation, conv.groups)
+        if nib_out and not pooled:
+            nib, _ = ops.grouped_conv2d_sign(*args, kind="raw", shape=shape, out_halo=self.out_nib_halo)
+            return packed.PackedActivation(None, (N, Cout, Ho, Wo), nib=nib, halo=self.out_nib_halo)
+        planes, _ = ops.grouped_conv2d_sign(*args, kind="raw", shape=shape)
+        if pooled and nib_out:
+            nib, (Ho, Wo) = ops.pool_bits_nib(planes, N, Ho, Wo, fp.pool_k, fp.pool_s, self._neg_alpha, self.out_nib_halo)
+            return packed.PackedActivation(None, (N, Cout, Ho, Wo), nib=nib, halo=self.out_nib_halo)
+        if pooled:
+            planes, (Ho, Wo) = ops.pool_bits(planes, N, Ho, Wo, fp.pool_k, fp.pool_s, self._neg_alpha)
+        act = packed.PackedActivation(planes, (N, Cout, Ho, Wo))
+        return act.flatten_hwc() if self.flatten_hwc else act
+
+
 #: real-valued 3x3 / stride-1 / padding-1 first layers of fused stacks run in the 2x2 output-blocked form
 D2S_FIRST_LAYER = True
 #: real-valued 3x3 / stride-1 / padding-1 first layers with <= 5 channels run on the direct kernel (bf16 triple planes);
@@ -1095,6 +1178,10 @@ def fuse_sequential_training(seq: torch.nn.Sequential) -> torch.nn.Sequential:
     return torch.nn.Sequential(*out)
 
 
+#: the fused modules whose PackedActivation carries bit planes (or, linked, the consumer's nibble operand)
+_PLANE_PRODUCERS = (FusedConvPoolBnSign, PackedMaxPool, FusedDepthwiseBnSign, FusedGroupedBnSign)
+
+
 def _is_det_binary_connect(m):
     return isinstance(m, _FunctionModule) and m.core is BinaryConnectDeterministic
 
@@ -1104,7 +1191,9 @@ def fuse_sequential(seq: torch.nn.Sequential, fuse_conv: bool = False, packed_po
     replaced by one FusedPoolBnSign (sharing the original BatchNorm's parameters).  With ``fuse_conv`` a
     BinConv2d / TerConv2d directly in front of such a run joins it (FusedConvPoolBnSign: the conv emits
     threshold bits, no fp32 activation is written at all; a depthwise one, ``groups == in_channels``, becomes a
-    FusedDepthwiseBnSign).  With ``packed_pool`` a MaxPool2d that directly follows a
+    FusedDepthwiseBnSign; a grouped one that ``FusedGroupedBnSign`` takes becomes that block when the module emitted just before
+    it produces bit planes — FusedConvPoolBnSign, PackedMaxPool, FusedDepthwiseBnSign, FusedGroupedBnSign — and stays the
+    un-fused layer otherwise).  With ``packed_pool`` a MaxPool2d that directly follows a
     fused block (pool AFTER the sign, VGG style) becomes a PackedMaxPool on the bit planes.  ``fold``: the BatchNorm
     fold of the fused blocks ("reference" | "device", module docstring; default DEFAULT_FOLD)."""
     from .binary_layers import BinConv2d
@@ -1132,6 +1221,9 @@ def fuse_sequential(seq: torch.nn.Sequential, fuse_conv: bool = False, packed_po
                 try:
                     if conv is not None and conv.groups == conv.in_channels > 1 and not isinstance(conv, XNORConv2d):
                         out.append(FusedDepthwiseBnSign(conv, bn, pool, fold=fold))
+                    elif (conv is not None and 1 < conv.groups < conv.in_channels and not isinstance(conv, XNORConv2d)
+                          and out and isinstance(out[-1], _PLANE_PRODUCERS) and not getattr(out[-1], "flatten_hwc", False)):
+                        out.append(FusedGroupedBnSign(conv, bn, pool, fold=fold))       # reads planes only: never at the head
                     else:
                         out.append(FusedConvPoolBnSign(conv, bn, pool, fold=fold) if conv is not None
                                    else FusedPoolBnSign(bn, pool, pre_relu=pre_relu, fold=fold))
@@ -1159,10 +1251,11 @@ def link_nib_planes(mods) -> None:
     """Where a fused conv block directly consumes the output of another fused block (or of a PackedMaxPool), let the
     producer write the consumer's operand — the fp4 nibble pixel plane with the consumer's padding as a zero border —
     instead of bit planes (saves the consumer's qt_bits_to_nib_pad pass: 10 % of the fused VGG-16 forward).  A depthwise block
-    (FusedDepthwiseBnSign) is such a producer; as a consumer it reads bit planes, so its producer stays on them."""
+    or a grouped block (FusedDepthwiseBnSign, FusedGroupedBnSign) is such a producer; as a consumer it reads bit planes, so its
+    producer stays on them."""
     from ..functions import _fused
     for a, b in zip(mods, mods[1:]):
-        if isinstance(a, (FusedConvPoolBnSign, PackedMaxPool, FusedDepthwiseBnSign)):
+        if isinstance(a, _PLANE_PRODUCERS):
             a.out_nib_halo = None
             if (_fused._cfg("PAD_PLANES") and isinstance(b, FusedConvPoolBnSign) and not getattr(a, "flatten_hwc", False)):
                 a.out_nib_halo = tuple(int(v) for v in ops._pairs(b.conv.padding))

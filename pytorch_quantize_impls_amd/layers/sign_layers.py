@@ -219,6 +219,8 @@ class _SignConv2d(EvalSwapMixin, torch.nn.Conv2d, QLayer):
     def _forward_impl(self, input):
         kind = self.kind
         if isinstance(input, _PackedActivation):
+            if 1 < self.groups < self.in_channels:      # a deferred grouped conv on planes that materialises
+                return _fused.packed_grouped_conv2d(self, input)
             if self.groups != 1:            # groups == in_channels on planes: a deferred depthwise conv that materialises
                 return _fused.packed_depthwise_conv2d(self, input)
             return _fused.packed_conv2d(self, input, kind)

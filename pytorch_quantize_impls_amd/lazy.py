@@ -47,8 +47,14 @@ codes to the next layer's codes, so a DoReFa pointwise / depthwise stack stays o
 It takes no residual (an ``add`` behind its BatchNorm materialises); a deferred depthwise conv on codes that must materialise
 computes its fp32 value from the codes (``_fused.codes_depthwise_conv2d``).
 
+Grouped BinConv2d / TerConv2d with at least ``_fused.GROUPED_MIN_GROUPS`` groups of 2, 4 or 8 input channels join the sign chain
+behind a producer of bit planes (``DEFER_GROUPED``, on by default; ``grouped_deferred(False)`` switches it off): the layer takes
+its producer's bit planes and runs as ``layers.fused.FusedGroupedBnSign`` — one launch (qt_gconv2d_sign) from planes to the next
+layer's planes or nibble operand; a deferred grouped conv on planes that must materialise computes its fp32 value from the planes
+(``_fused.packed_grouped_conv2d``).  On an fp32 tensor — at the head of a chain — a grouped layer never defers.
+
 Nothing is deferred in training mode, with autograd enabled, on CPU tensors, for non-fp32 dtypes, grouped convs other than
-those depthwise ones or non-zero padding modes.  ``lazy.ENABLED = False`` (or the ``eager()`` context manager) switches the mechanism off;
+those depthwise and few-channel ones or non-zero padding modes.  ``lazy.ENABLED = False`` (or the ``eager()`` context manager) switches the mechanism off;
 ``lazy.STATS`` counts what happened (tests assert on it).
 """
 from __future__ import annotations
@@ -98,6 +104,13 @@ DEFER_DEPTHWISE = True
 #: exactly as without this mechanism: the depthwise layer computes fp32 from the expanded image and the chain in front of it
 #: materialises (``depthwise_deferred(False)`` switches it off for a block).
 DEFER_DEPTHWISE_CODES = True
+#: grouped BinConv2d / TerConv2d (``groups >= _fused.GROUPED_MIN_GROUPS``, 2, 4 or 8 input channels per group, shapes
+#: ``ops.grouped_planes_applicable`` takes) join the sign chain when their input is a deferred +-1 activation: the layer asks its
+#: producer for bit planes and runs as ``layers.fused.FusedGroupedBnSign`` — one launch from planes to the next layer's planes
+#: (DESIGN.md "Grouped convs", "Inside the fused inference chain", says what was measured and why the default is what it is).
+#: False = every call runs exactly as without this mechanism: the grouped layer returns fp32 from qt_gconv2d_f32 and the chain in
+#: front of it materialises (``grouped_deferred()`` switches it for a block).
+DEFER_GROUPED = True
 #: "deferred" convs that returned a LazyActivation, "fused" chains executed as fused blocks, "materialised" lazies that
 #: had to produce their fp32 value, "fallback:<func>" the functions that forced it
 STATS = collections.Counter()
@@ -173,6 +186,17 @@ def depthwise_deferred(on: bool = True):
         yield
     finally:
         DEFER_DEPTHWISE, DEFER_DEPTHWISE_CODES = prev, prev_codes
+
+
+@contextlib.contextmanager
+def grouped_deferred(on: bool = True):
+    """Defer grouped sign convs (``DEFER_GROUPED``) inside the block; process-wide, restores the previous setting."""
+    global DEFER_GROUPED
+    prev, DEFER_GROUPED = DEFER_GROUPED, bool(on)
+    try:
+        yield
+    finally:
+        DEFER_GROUPED = prev
 
 
 class _Node:
@@ -535,7 +559,8 @@ def _fused_block(layer, bn, pool, flatten: bool, halo):
     blk = per.get(key)
     if blk is None:
         pm = torch.nn.MaxPool2d(pool[0], pool[1]) if pool is not None else None
-        make = fused.FusedDepthwiseBnSign if layer.groups != 1 else fused.FusedConvPoolBnSign
+        make = (fused.FusedConvPoolBnSign if layer.groups == 1 else
+                fused.FusedDepthwiseBnSign if layer.groups == layer.in_channels else fused.FusedGroupedBnSign)
         blk = make(layer, _BnView(rm, rv, w, b, eps), pm, flatten_hwc=flatten, fold="device")
         blk.out_nib_halo = halo
         per[key] = blk
@@ -1097,11 +1122,22 @@ def _conv_can_defer(layer, input) -> bool:
         return False
     w = layer.weight
     if layer.groups != 1:
-        # depthwise only (DEFER_DEPTHWISE), inside the limits of the depthwise kernels; every other grouped conv runs eagerly
-        if not (DEFER_DEPTHWISE and layer.groups == layer.in_channels and getattr(layer, "kind", None) in ("binary", "ternary")
-                and ops.depthwise_applicable(tuple(getattr(input, "shape", ())), tuple(w.shape), layer.stride, layer.padding,
-                                             layer.dilation, layer.groups)):
+        # depthwise (DEFER_DEPTHWISE) inside the limits of the depthwise kernels, or a few channels per group (DEFER_GROUPED) on the
+        # planes of a +-1 activation — never on an fp32 tensor — inside those of the grouped plane kernel; every other grouped
+        # conv runs eagerly
+        if getattr(layer, "kind", None) not in ("binary", "ternary"):
             return False
+        shape = tuple(getattr(input, "shape", ()))
+        if layer.groups == layer.in_channels:
+            if not (DEFER_DEPTHWISE and ops.depthwise_applicable(shape, tuple(w.shape), layer.stride, layer.padding, layer.dilation,
+                                                                 layer.groups)):
+                return False
+        else:
+            from .functions import _fused
+            if not (DEFER_GROUPED and layer.groups >= _fused.GROUPED_MIN_GROUPS and isinstance(input, packed.PackedActivation)
+                    and (isinstance(input, _ShapeOnly) or input.planes is not None)
+                    and ops.grouped_planes_applicable(shape, tuple(w.shape), layer.stride, layer.padding, layer.dilation, layer.groups)):
+                return False
     if not w.is_cuda or w.dtype != torch.float32:
         return False
     if isinstance(input, packed.PackedActivation):
@@ -1124,7 +1160,7 @@ def conv_forward(layer, input, kind: str):
         if n.signed and not n.flat and _conv_can_defer(layer, _ShapeOnly(n.shape)):
             from .functions import _fused
             if layer.groups != 1:
-                act = n.force(None)         # a depthwise consumer reads bit planes, never a halo plane
+                act = n.force(None)         # a depthwise / grouped consumer reads bit planes, never a halo plane
             else:
                 act = n.force(tuple(int(v) for v in ops._pairs(layer.padding)) if _fused._cfg("PAD_PLANES") else None)
         input = act if act is not None else n.materialise()

@@ -4516,6 +4516,83 @@ def grouped_conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
     return y
 
 
+#: input channels per group the grouped plane kernel takes: a group's operand at one tap is a bit field of ONE plane word
+GC_PLANE_CIN_G = (2, 4, 8)
+
+
+def grouped_planes_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
+    """``grouped_applicable`` and 2, 4 or 8 input channels per group: the grouped convs that run on the bit planes of a +-1
+    activation (``grouped_conv2d_sign`` / ``grouped_conv2d_from_bits``).  A pure function of the shapes."""
+    return (grouped_applicable(x_shape, w_shape, stride, padding, dilation, groups) and int(w_shape[1]) in GC_PLANE_CIN_G)
+
+
+def _gc_planes_geometry(planes, shape, weight, stride, padding, dilation, groups):
+    x_shape = _dw_plane_input(planes, shape)
+    w, geom, y_shape = _gc_geometry(x_shape, weight, stride, padding, dilation, groups)
+    if geom[2] not in GC_PLANE_CIN_G:
+        raise ValueError(f"the grouped plane kernel takes 2, 4 or 8 input channels per group, got {geom[2]}")
+    if w.device != planes.device:
+        raise ValueError("input and weight are on different devices")
+    return w, geom, y_shape
+
+
+def grouped_conv2d_sign(planes: BitPlanes, weight: torch.Tensor, bias: Optional[torch.Tensor], alpha: torch.Tensor, beta: torch.Tensor,
+                        stride=1, padding=0, dilation=1, groups: int = 1, kind: str = "raw", shape=None, out_halo=None,
+                        with_bits: bool = False, out_sign: Optional[torch.Tensor] = None, out_nib: Optional[torch.Tensor] = None):
+    """The threshold bits [grouped_conv2d(x) * alpha + beta < 0] (two fp32 roundings; a tie gives 0) of the +-1 activation x that
+    exists as ``planes`` (sign-only NHWC pixel plane, logical ``shape`` (N, G * cin_g, H, W)), written as planes by the one launch
+    that computes the conv (qt_gconv2d_sign): per tap one XOR, one AND and one popcount on the group's bit field, with the taps
+    classified to -1 / 0 / +1 (``kind``; "raw": by their sign).  For an on-grid weight the bits are those of the pinned fp32
+    arithmetic of ``grouped_conv2d`` on the decoded image.  cin_g in {2, 4, 8} (``grouped_planes_applicable``).  Returns and the
+    ``out_*`` arguments as ``depthwise_conv2d_sign``."""
+    w, geom, y_shape = _gc_planes_geometry(planes, shape, weight, stride, padding, dilation, groups)
+    dev = planes.device
+    N, Cout, Ho, Wo = y_shape
+    bias = _check_bias(bias, Cout, dev)
+    alpha, beta, _ = epilogue_affine((alpha, beta), Cout, dev)
+    if alpha is None or beta is None:
+        raise TypeError("alpha and beta: expected fp32 device vectors")
+    hy, hx = (0, 0) if out_halo is None else (int(v) for v in _pairs(out_halo))
+    if hy < 0 or hx < 0:
+        raise ValueError("out_halo must not be negative")
+    bits = nib = None
+    if out_halo is None or with_bits:
+        bits = BitPlanes(sign=_dw_plane_out(out_sign, N * Ho * Wo, packed_ld(Cout), dev, "out_sign"), rows=N * Ho * Wo, K=Cout)
+    if out_halo is not None:
+        rows = N * (Ho + 2 * hy) * (Wo + 2 * hx)
+        nib = NibPlanes(words=_dw_plane_out(out_nib, rows, pixel_ld_nib(Cout), dev, "out_nib"), rows=rows, K=Cout)
+    if N * Cout * Ho * Wo > 0:
+        with _on(dev):
+            _lib.call("qt_gconv2d_sign", _p(planes.sign), int(planes.ld), _p(w), _p(bias), _p(alpha), _p(beta),
+                      _p(bits.sign) if bits is not None else None, bits.ld if bits is not None else 0,
+                      _p(nib.words) if nib is not None else None, nib.ld if nib is not None else 0, hy, hx, *geom, DW_KINDS[kind],
+                      _stream(dev))
+    out = bits if nib is None else ((bits, nib) if bits is not None else nib)
+    return out, (Ho, Wo)
+
+
+def grouped_conv2d_from_bits(planes: BitPlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1, padding=0,
+                             dilation=1, groups: int = 1, kind: str = "raw", channels_last: bool = False,
+                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``grouped_conv2d`` of the +-1 activation that exists only as ``planes`` (sign-only NHWC pixel plane, logical ``shape``
+    (N, G * cin_g, H, W)), cin_g in {2, 4, 8}: the fp32 result — for an on-grid weight bit for bit that of the fp32 +-1 image — in
+    NCHW or ``channels_last`` storage or written into ``out`` (qt_gconv2d_bits_f32, one launch)."""
+    w, geom, y_shape = _gc_planes_geometry(planes, shape, weight, stride, padding, dilation, groups)
+    dev = planes.device
+    bias = _check_bias(bias, y_shape[1], dev)
+    if out is None:
+        y = torch.empty(y_shape, dtype=torch.float32, device=dev,
+                        memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    else:
+        y = _dw_result(out, y_shape, w, "out")
+    if y.numel() == 0:
+        return y
+    with _on(dev):
+        _lib.call("qt_gconv2d_bits_f32", _p(planes.sign), int(planes.ld), _p(w), _p(bias), _p(y), *geom,
+                  *_dw_strides(y.shape, _dw_channels_last(y)), DW_KINDS[kind], _stream(dev))
+    return y
+
+
 def grouped_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_output: torch.Tensor, stride=1, padding=0, dilation=1,
                               groups: int = 1, kind: str = "raw", channels_last: Optional[bool] = None,
                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
