@@ -197,9 +197,35 @@ def _folded_for(owner, attr, bn, device=None, fold="reference", like=None):
         raise ValueError(f"fold must be 'reference' or 'device', got {fold!r}")
     cur = getattr(owner, attr, None)
     if cur is None or cur[0] != key or (device is not None and cur[1][0].device != device):
-        cur = (key, device_sign_fold(bn, *like) if fold == "device" else fold_batchnorm(bn))
+        kept = _kept_folds(owner, attr, bn, device, cur is None)
+        cur = kept.get(key)
+        if cur is None:
+            cur = kept[key] = (key, device_sign_fold(bn, *like) if fold == "device" else fold_batchnorm(bn), {})
         setattr(owner, attr, cur)
     return cur[1]
+
+
+def _kept_folds(owner, attr, bn, device, fresh: bool) -> dict:
+    """{key: fold entry} of ``owner`` for the PRESENT state of ``bn``.  A device fold is made per probe signature (batch extent 1
+    or more, memory format): a forward with another signature must not FREE the tensors of the one before — a hipGraph captured
+    for that signature has their addresses baked in and would read whatever the allocator puts there next (an implicit graph per
+    input signature; batch 1 beside batch N, or NCHW beside channels-last, is all it takes).  So the entries of one BatchNorm
+    state live side by side, each with the data derived from it (``entry[2]``: negative-slope words, integer thresholds); a
+    written BatchNorm — which drops the graphs as well — or ``refold()`` (``fresh``) starts over."""
+    state = (_bn_key(bn), device)
+    kept = owner.__dict__.get(attr + "_kept")
+    if fresh or kept is None or kept[0] != state:
+        kept = (state, {})
+        owner.__dict__[attr + "_kept"] = kept
+    return kept[1]
+
+
+def _derived(entry, name, make):
+    """Data derived from a fold entry, made once and kept with it (see ``_kept_folds``)."""
+    d = entry[2]
+    if name not in d:
+        d[name] = make()
+    return d[name]
 
 
 def _code_fold_for(owner, attr, bn, fold, like):
@@ -211,7 +237,10 @@ def _code_fold_for(owner, attr, bn, fold, like):
     key = _bn_key(bn) + (("codes", len(shape), bool(cl)),)
     cur = getattr(owner, attr, None)
     if cur is None or cur[0] != key:
-        cur = (key, device_bn_fold(bn, shape, cl))
+        kept = _kept_folds(owner, attr, bn, None, cur is None)      # (the other memory format's fold stays alive: _kept_folds)
+        cur = kept.get(key)
+        if cur is None:
+            cur = kept[key] = (key, device_bn_fold(bn, shape, cl), {})
         setattr(owner, attr, cur)
     return cur[1]
 
@@ -720,9 +749,9 @@ class FusedConvPoolBnSign(torch.nn.Module):
             like = ((N, conv.out_channels, (Ho - fp.pool_k) // fp.pool_s + 1, (Wo - fp.pool_k) // fp.pool_s + 1),
                     _out_channels_last(x))
         epi = _folded_for(fp, "_folded", self.bn, dev, self.fold, like)
-        if fp._folded is not prev or self._neg_alpha is None:      # BatchNorm changed (or first call): derived data too
-            self._neg_alpha = ops.neg_alpha_words(epi[0])
-            self._thr = None
+        if fp._folded is not prev or self._neg_alpha is None:      # BatchNorm / probe signature changed (or first call): derived data too
+            self._neg_alpha = _derived(fp._folded, "neg_alpha", lambda: ops.neg_alpha_words(epi[0]))
+            self._thr = fp._folded[2].get("thr")
         pooled = fp.pool_k != 1 or fp.pool_s != 1
         nib_out = self.out_nib_halo is not None and not self.flatten_hwc
         if isinstance(x, packed.PackedActivation):
@@ -732,7 +761,7 @@ class FusedConvPoolBnSign(torch.nn.Module):
             int_thr = INTEGER_THRESHOLDS and self.kind != "xnor"
             if int_thr and (self._thr is None or self._thr[0] != bkey or self._thr[1].device != dev):
                 kmax = conv.in_channels * conv.kernel_size[0] * conv.kernel_size[1]
-                self._thr = (bkey, ops.integer_thresholds(conv.bias, epi[0], epi[1], kmax))
+                self._thr = fp._folded[2]["thr"] = (bkey, ops.integer_thresholds(conv.bias, epi[0], epi[1], kmax))
             thr = self._thr[1] if int_thr else None
             epi = (epi[0], epi[1], thr)
             if nib_out and not pooled:
@@ -849,8 +878,8 @@ class FusedDepthwiseBnSign(torch.nn.Module):
             # the tensor the module graph would hand to F.batch_norm: this conv's output, pooled
             like = ((N, conv.out_channels, (Ho - fp.pool_k) // fp.pool_s + 1, (Wo - fp.pool_k) // fp.pool_s + 1), cl)
         alpha, beta = _folded_for(fp, "_folded", self.bn, dev, self.fold, like)
-        if fp._folded is not prev or self._neg_alpha is None:      # BatchNorm changed (or first call): derived data too
-            self._neg_alpha = ops.neg_alpha_words(alpha)
+        if fp._folded is not prev or self._neg_alpha is None:      # BatchNorm / probe signature changed (or first call): derived data too
+            self._neg_alpha = _derived(fp._folded, "neg_alpha", lambda: ops.neg_alpha_words(alpha))
         pooled = fp.pool_k != 1 or fp.pool_s != 1
         nib_out = self.out_nib_halo is not None and not self.flatten_hwc
         Cout = conv.out_channels
@@ -932,8 +961,8 @@ class FusedGroupedBnSign(torch.nn.Module):
             # fp32 input, here the +-1 tensor the planes stand for — pooled
             like = ((N, conv.out_channels, (Ho - fp.pool_k) // fp.pool_s + 1, (Wo - fp.pool_k) // fp.pool_s + 1), _out_channels_last(x))
         alpha, beta = _folded_for(fp, "_folded", self.bn, dev, self.fold, like)
-        if fp._folded is not prev or self._neg_alpha is None:      # BatchNorm changed (or first call): derived data too
-            self._neg_alpha = ops.neg_alpha_words(alpha)
+        if fp._folded is not prev or self._neg_alpha is None:      # BatchNorm / probe signature changed (or first call): derived data too
+            self._neg_alpha = _derived(fp._folded, "neg_alpha", lambda: ops.neg_alpha_words(alpha))
         pooled = fp.pool_k != 1 or fp.pool_s != 1
         nib_out = self.out_nib_halo is not None and not self.flatten_hwc
         Cout = conv.out_channels

@@ -2020,6 +2020,14 @@ class TriplePlanes:
 _ABS_MEAN_WORK = {}      # (device index, stream handle) -> zero-initialised ticket / partial buffer (the kernel leaves it zero)
 
 
+def _abs_mean_work(dev) -> torch.Tensor:
+    """A zeroed, 8-byte aligned work buffer of qt_abs_mean_f32 (ticket counter + partials)."""
+    words = int(_lib.load().qt_abs_mean_work_words())
+    with _on(dev):
+        work = torch.zeros((words + 2,), dtype=torch.int32, device=dev)
+    return work[1:] if work.data_ptr() % 8 else work
+
+
 def abs_mean(x: torch.Tensor) -> torch.Tensor:
     """mean|x| as a 0-dim tensor: ``torch.mean(torch.abs(x))`` (functions/dorefa_connect.py:100, DoReFa's E).  Dense fp32 device
     tensors: one launch (qt_abs_mean_f32: double-precision, order-fixed fold) instead of torch's abs + mean (+ fill); every
@@ -2029,17 +2037,20 @@ def abs_mean(x: torch.Tensor) -> torch.Tensor:
         return torch.mean(torch.abs(x))
     dev = x.device
     st = _stream(dev)
-    key = (dev.index, int(st) if st is not None else 0)
-    work = _ABS_MEAN_WORK.get(key)
-    if work is None:
-        if len(_ABS_MEAN_WORK) > 64:
-            _ABS_MEAN_WORK.clear()
-        words = int(_lib.load().qt_abs_mean_work_words())
-        with _on(dev):
-            work = torch.zeros((words + 2,), dtype=torch.int32, device=dev)
-        if work.data_ptr() % 8:
-            work = work[1:]
-        _ABS_MEAN_WORK[key] = work
+    with _on(dev):                                  # (the question is about the current stream of x's device)
+        capturing = torch.cuda.is_current_stream_capturing()
+    if capturing:
+        # inside a stream capture ``torch.zeros`` is only RECORDED and its memory belongs to the graph's private pool: such a buffer
+        # must not outlive the capture in the cache (a later eager call on this stream handle would start from a ticket nobody
+        # zeroed, and the kernel would never write ``out``).  A fresh buffer per call, zeroed by the graph itself on every replay.
+        work = _abs_mean_work(dev)
+    else:
+        key = (dev.index, int(st) if st is not None else 0)
+        work = _ABS_MEAN_WORK.get(key)
+        if work is None:
+            if len(_ABS_MEAN_WORK) > 64:
+                _ABS_MEAN_WORK.clear()
+            work = _ABS_MEAN_WORK[key] = _abs_mean_work(dev)
     out = torch.empty((), dtype=torch.float32, device=dev)
     with _on(dev):
         _lib.call("qt_abs_mean_f32", _p(x), int(x.numel()), _p(work), _p(out), st)

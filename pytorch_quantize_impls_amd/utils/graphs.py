@@ -121,6 +121,8 @@ class AutoGraphed(torch.nn.Module):
         self.capture_after, self.max_graphs, self.clone_output = int(capture_after), int(max_graphs), bool(clone_output)
         self._graphs, self._seen, self._state = {}, {}, None
         self.replays = self.eager_calls = 0
+        #: stream captures started (kept or not): grows with every signature and every write to a parameter / buffer, not with calls
+        self.captures = 0
         #: captures that failed, by reason ("ExceptionType: message" -> count): such a signature stays eager — VISIBLY (a genuine
         #: bug inside a captured forward must not turn into a silent performance regression); ``strict=True`` re-raises instead
         self.capture_failures = {}
@@ -159,6 +161,7 @@ class AutoGraphed(torch.nn.Module):
             if n <= self.capture_after or len(self._graphs) >= self.max_graphs:
                 self.eager_calls += 1
                 return self._call(x)
+            self.captures += 1
             try:
                 g = GraphedModule(self.module, x, warmup=1, call=None if self._call is self.module else self._call)
                 if self.refuse_lazy_outputs and g.lazy_output:

@@ -13,8 +13,8 @@ process-wide module hook would say the same, but costs 3.6 us on EVERY module ca
 
   * has every module of its tree in eval mode, autograd is off,
   * was called with ONE positional fp32 device tensor and no keyword argument, outside any stream capture,
-  * carries no forward / backward hooks anywhere in its tree (user instrumentation must keep seeing every call), and is not a
-    ``torch.nn.parallel`` / graph wrapper,
+  * carries no forward / backward hooks anywhere in its tree, nor are there process-wide module hooks (user instrumentation must
+    keep seeing every call), and is not a ``torch.nn.parallel`` / graph wrapper,
 
 the root gets an INSTANCE attribute ``forward`` — an
 ``_ImplicitForward`` around its original forward — which from then on is ``utils.AutoGraphed`` in all but name: captured per input
@@ -24,6 +24,19 @@ Two safety nets on top of the opt-in wrapper: the captured replay must reproduce
 (a forward whose value depends on anything but its input and the tree's tensors is left eager), and the replay must be faster
 than the eager forward (timed once at capture, which synchronises anyway: a device-bound forward keeps its eager path and the
 graph's private memory pool is released).
+
+Hooks are looked for again before EVERY replay, not only when the root is wrapped: while a hook registered later sits anywhere in
+the tree (or on the root, or process-wide) the call runs the original forward, so the hook fires; the captured graphs are kept and
+replay again once it is removed (``hooked_calls`` in the stats).  The signatures that are eager anyway run the original forward
+and need no such walk.
+
+A root whose eval forward WRITES a parameter / buffer of its own tree (a call counter, an observer) is found out at the first
+verification — the state signature differs before and after that eager forward — and is then left eager for good
+(``left_eager`` in the stats says why; ``captures`` stays at 1): a replay would repeat the captured write without its Python side,
+and every call would otherwise drop the graphs and capture again.  Until that verdict such a root has seen, besides one forward
+per user call, the forwards of one capture: 1 warm-up, 1 verification and — with the timing verdict on (``KEEP_IF_FASTER`` > 0) —
+3 timed replays and 3 timed eager forwards; the forward recorded by the capture itself runs in Python only, its launches execute
+as the user's replay.  With the timing verdict off that is 2 extra forwards, all in the third call.
 
 What a replay cannot preserve: Python side effects of a user-defined ``forward`` (counters, prints, appended lists) happen in
 the eager calls only.  Opt out: ``QT_AUTO_GRAPH=0`` in the environment, ``utils.implicit_graphs(False)`` (process-wide; also a
@@ -99,8 +112,13 @@ def implicit_graph_stats(model: torch.nn.Module) -> dict:
         e = fw.engine
         return {"wrapped": True, "replays": e.replays, "eager_calls": e.eager_calls, "graphs": sum(g is not None for g in e._graphs.values()),
                 "capture_failures": dict(e.capture_failures), "not_faster": e.not_faster, "value_mismatch": fw.value_mismatch,
-                "eager_signatures": len(fw.eager_keys)}
+                "eager_signatures": len(fw.eager_keys), "captures": e.captures, "hooked_calls": fw.hooked_calls,
+                "left_eager": fw.left_eager}
     return {"wrapped": False, "opted_out": model in _OPTED_OUT, "why": _PENDING.get(model)}
+
+
+_nn_module = torch.nn.modules.module
+_GLOBAL_HOOKS = ("_global_forward_hooks", "_global_forward_pre_hooks", "_global_backward_hooks", "_global_backward_pre_hooks")
 
 
 def _has_quantised_layer(module) -> bool:
@@ -109,9 +127,23 @@ def _has_quantised_layer(module) -> bool:
 
 
 def _hooked(module) -> bool:
-    for m in module.modules():
-        if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, "_backward_pre_hooks", None):
+    """A forward / backward hook anywhere in the tree.  Asked when a root is about to be wrapped and again before every replay (a
+    hook may arrive later): one pass over the modules, four attribute reads each."""
+    if any(getattr(_nn_module, name, None) for name in _GLOBAL_HOOKS):          # torch's process-wide module hooks
+        return True
+    # (the tree by its ``_modules`` dictionaries: ``module.modules()`` builds a dotted name and a memo entry per module on the way,
+    # 5 x the time.  A module reachable twice is looked at twice.)  Measured on the 101 modules of DoReFa ResNet-18: 12 us per call
+    # on the MI355X host, next to a replay of 570 us.
+    todo = [module]
+    for m in todo:
+        if m is None:
+            continue
+        d = m.__dict__
+        if d["_forward_hooks"] or d["_forward_pre_hooks"] or d["_backward_hooks"] or d.get("_backward_pre_hooks"):
             return True
+        children = d["_modules"]
+        if children:
+            todo.extend(children.values())
     return False
 
 
@@ -136,6 +168,8 @@ class _ImplicitForward:
         # the engine must not register `module` as a child of itself as an attribute cycle that state_dict() walks: it is an
         # nn.Module that is never called as one and never appears in the root's tree (held here, not on the root's _modules)
         self.value_mismatch = 0
+        self.hooked_calls = 0               # calls that ran the original forward because a hook sat in the tree
+        self.left_eager = None              # why this root is never replayed again (a forward that writes its own state), or None
         self.busy = threading.Lock()
         self._checked = set()
         self.eager_keys = set()
@@ -146,7 +180,8 @@ class _ImplicitForward:
 
     def __call__(self, *args, **kwargs):
         # (inside `with lazy.eager():` the caller asks for the module-by-module execution: it gets it)
-        if kwargs or len(args) != 1 or not enabled() or not _lazy.enabled() or not self.busy.acquire(blocking=False):
+        if (kwargs or len(args) != 1 or self.left_eager is not None or not enabled() or not _lazy.enabled()
+                or not self.busy.acquire(blocking=False)):
             with _thread_off():
                 return self.original(*args, **kwargs)
         try:
@@ -156,8 +191,17 @@ class _ImplicitForward:
             if key in self.eager_keys:
                 # this signature was measured (replay not faster: a device-bound forward) or could not be captured: the original
                 # forward, without the per-call state signature / training-mode walk of the engine (a 16-launch AlexNet forward
-                # at batch 256 is close enough to host-bound for those 60 us to show: 313 k -> 294 k img/s)
+                # at batch 256 is close enough to host-bound for those 60 us to show: 313 k -> 294 k img/s) — and without the hook
+                # walk below: the original forward runs every module, so hooks fire by themselves
                 return self.original(x)
+            module = self.module_ref()
+            if module is not None and _hooked(module):
+                # a hook registered AFTER the root was wrapped: a replay never enters the submodules, so it would be skipped.  The
+                # original forward while the hook is there; the graphs stay (nothing they baked in has changed) and replay again
+                # once it is removed.  One more walk over the tree next to the two the engine does per replay (parameters /
+                # buffers for the state signature, modules for the training flags).
+                self.hooked_calls += 1
+                return self._eager(x)
             before, state_before = eng.replays, eng._state
             out = eng(x)
             if eng._state is not state_before:
@@ -169,6 +213,16 @@ class _ImplicitForward:
                     # first replay of this capture: it must reproduce the eager value of the same input bit for bit
                     self._checked.add(key)
                     ref = self._eager(x)
+                    if eng._state_sig() != eng._state:
+                        # the forward WRITES a parameter / buffer of its own tree (a call counter, an observer): every call would
+                        # change the state signature, drop the graphs and capture again — and a replay repeats the captured write
+                        # without its Python side.  Such a root is left eager for good; the verdict costs it the forwards of ONE
+                        # capture (see the module docstring)
+                        self.left_eager = "the forward writes a parameter / buffer of its own tree"
+                        eng.reset()
+                        self.eager_keys.clear()
+                        self._checked.clear()
+                        return ref
                     if not _same(out, ref):
                         self.value_mismatch += 1
                         eng._graphs[key] = None                     # this signature stays eager
