@@ -1510,6 +1510,55 @@ int qt_dwconv2d_codes_f32(const int8_t* x_plane, int64_t ldx_bytes, int64_t in_h
                           int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t ys_n,
                           int64_t ys_c, int64_t ys_h, int64_t ys_w, qt_stream_t stream);
 
+/* Grouped convolution on int8 code planes: the grouped forward (qt_gconv2d_f32) inside the same fused DoReFa inference chain, reading
+ * the int8 code plane a CodeActivation carries and writing the next one.  One launch each; no allocation, no synchronisation;
+ * csrc/gconv.hip, DESIGN.md "Grouped convs".
+ *
+ * Input.  x_plane int8 NHWC [N][H + 2 in_halo_h][W + 2 in_halo_w][ldx_bytes] over C = G cin_g channels, in the format of
+ * qt_dwconv2d_codes above: a code q is decoded as x = fl(inv_n * (float)q).  ldx_bytes >= G cin_g rounded up to 16
+ * (ops.code_ld_bytes(G cin_g, 16)) and a multiple of 16, the plane 16-byte aligned.  Taps outside the H x W image are SKIPPED: the
+ * halo of the input plane is never read, whatever in_halo_* and the padding are.  w fp32 [G cout_g, cin_g, kh, kw] and bias
+ * [G cout_g] or NULL as for qt_gconv2d_f32; the weight image is multiplied as it is (no quantiser inside the launch).
+ *
+ * The value y[n, g cout_g + j, ho, wo] is EXACTLY what qt_gconv2d_f32 stores for that fp32 image with kind = QT_DW_RAW: accumulator
+ * +0; the group's input channel ascending, outermost; then the taps row-major; taps outside the image skipped; one fp32 multiply
+ * then one fp32 add per term; bias last; nothing contracted.  No integer arithmetic stands in for it: bit identity with the
+ * module-by-module graph rests on this order.  With cin_g == 1 both entries give the bytes of qt_dwconv2d_codes /
+ * qt_dwconv2d_codes_f32 (C = G, m = cout_g).
+ *
+ * Output forms — exactly those of the depthwise code entries:
+ *   qt_gconv2d_codes      the code epilogue stated at qt_dwconv2d_codes (one helper, csrc/codes_epilogue.h): folded BatchNorm
+ *                         (bn_stats NULL) or the device form (bn_stats = fp32 [mean | rs], 2 G cout_g values), relu in {0, 1},
+ *                         q = rint(fl((2^bit_width - 1) t)) unclamped; |q| > 127 or NaN stores code 0 and ORs *overflow with 1, or
+ *                         with 3 where some |q| > 2047 or NaN.  codes int8 [N][Ho + 2 out_halo_h][Wo + 2 out_halo_w][ldc_bytes],
+ *                         ldc_bytes >= G cout_g rounded up to 16 and a multiple of 16, 16-byte aligned.  The launch writes EVERY
+ *                         byte of the plane — the pad bytes of each row, channels >= G cout_g and the whole border as zero — with
+ *                         dword stores; nothing is read back.
+ *   qt_gconv2d_codes_f32  y itself, fp32 [N, G cout_g, Ho, Wo] by its element strides ys_* (dense NCHW or channels-last), for a
+ *                         deferred grouped conv whose chain cannot run fused.  `overflow` (may be NULL) is the int8 range flag of
+ *                         the chain that produced x_plane: if it is raised every output is NaN, decided on the device.
+ *
+ * Limits: those of the grouped entries above (cin_g <= QT_GC_MAX_CIN_G, kh kw <= QT_DW_MAX_TAPS, cin_g kh kw <= QT_GC_MAX_K,
+ * G cout_g <= QT_DW_MAX_CHANNELS, tensors below 2^31 elements; any cout_g >= 1, no restriction on cin_g beyond those), halos <= 64,
+ * fewer than 2^31 pixel rows in either plane, ldc_bytes < 2^31; beyond them QT_ERR_UNSUPPORTED.  Validation before anything is
+ * enqueued, in this order:
+ *   1. a negative halo, then step 1 of the grouped entries.
+ *   2. N, G, H or W zero: QT_OK, nothing is written.
+ *   3. step 3 of the grouped entries; then a halo above 64, too many pixel rows, ldc_bytes >= 2^31: QT_ERR_UNSUPPORTED.
+ *   4. a null tensor (bias and bn_stats may be null; overflow only for the fp32 form), strides that are no dense layout, bit_width
+ *      outside 2 .. 8, relu outside {0, 1}, ldx_bytes / ldc_bytes below the bounds above: QT_ERR_INVALID_ARG; then a float or flag
+ *      pointer that is not 4-byte aligned, ldx_bytes % 16 or ldc_bytes % 16 != 0, a plane that is not 16-byte aligned:
+ *      QT_ERR_ALIGNMENT. */
+int qt_gconv2d_codes(const int8_t* x_plane, int64_t ldx_bytes, int64_t in_halo_h, int64_t in_halo_w, float inv_n, const float* w,
+                     const float* bias, const float* alpha, const float* beta, const float* bn_stats, int relu, int bit_width,
+                     int8_t* codes, int64_t ldc_bytes, int64_t out_halo_h, int64_t out_halo_w, int32_t* overflow, int64_t N,
+                     int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw,
+                     int dh, int dw, qt_stream_t stream);
+int qt_gconv2d_codes_f32(const int8_t* x_plane, int64_t ldx_bytes, int64_t in_halo_h, int64_t in_halo_w, float inv_n,
+                         const float* w, const float* bias, const int32_t* overflow, float* y, int64_t N, int64_t G, int64_t cin_g,
+                         int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                         int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, qt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

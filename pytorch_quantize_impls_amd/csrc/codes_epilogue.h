@@ -1,5 +1,6 @@
-// The code epilogue of the DoReFa inference chain, shared by the elementwise pass (codes_i8.hip) and the depthwise conv on code
-// planes (dwconv.hip): per-channel constants of one output dword and the arithmetic that turns four fp32 values into four int8 codes.
+// The code epilogue of the DoReFa inference chain, shared by the elementwise pass (codes_i8.hip) and the depthwise and grouped convs
+// on code planes (dwconv.hip, gconv.hip): per-channel constants of one output dword and the arithmetic that turns four fp32 values
+// into four int8 codes.
 #pragma once
 #include "qt_common.h"
 

@@ -1,5 +1,6 @@
 // Grouped conv2d with a few channels per group (1 <= cin_g <= 32, K = cin_g * kh * kw <= 512) in fp32: forward, grad_input,
-// grad_weight — and the forward on / into the bit planes of the fused sign chain (gc_planes_kernel, further down).
+// grad_weight — and the forward on / into the bit planes of the fused sign chain (gc_planes_kernel) and the int8 code planes of the
+// fused DoReFa chain (gc_codes_kernel), both further down.
 // include/qt_hip.h "Grouped convolution" states the contract; DESIGN.md "Grouped convs" the layout and the counts.
 //
 // Streaming kernels on the vector units, siblings of dwconv.hip: K is no matrix-core shape and the block-diagonal operand would
@@ -25,6 +26,7 @@
 #include "qt_common.h"
 #include "dw_map.h"
 #include "dw_planes.h"
+#include "codes_epilogue.h"
 
 namespace {
 
@@ -701,6 +703,306 @@ int gc_planes_launch(const uint32_t* x_plane, int64_t ldx, const float* w, const
     return qt_check_launch();
 }
 
+// ---- the forward on / into int8 code planes (include/qt_hip.h "Grouped convolution on int8 code planes") ----------------------------
+// gc_codes_kernel: the thread map of dw_codes_kernel (dwconv.hip) — a lane owns ONE DWORD of output channels (4 codes) for the whole
+// launch, the lanes of a workgroup run along the dwords of a pixel row first (`lanes`, a power of two), then along 256 / lanes
+// consecutive output pixels; a workgroup is (dword group, split) and walks pixel steps split, split + S, ... with constant
+// increments and two carries.  What differs is the inner product: cin_g x taps terms per output instead of taps.
+//   weights : 4 x K per lane (K = cin_g taps) do not fit registers beyond 1 x 1, so the workgroup stages the weights of its `lanes`
+//             dwords once into LDS as wl[k][lane] float4 (k = ci * taps + t, the weight's own order): lanes on consecutive dwords
+//             read consecutive 16 bytes, lanes on other pixels the same address (a broadcast).  The host caps `lanes` at 2048 / K,
+//             so the block is at most 32 KiB whatever K <= 512 is.  The 1 x 1 forms keep their 4 x cin_g weights in registers.
+//   forms   : CING in {2, 4, 8} with cout_g % 4 == 0 and a 1 x 1 or 3 x 3 kernel are compile-time forms: the lane's four channels
+//             share one group, whose cin_g input bytes of a tap are ONE aligned 2- / 4- / 8-byte load at byte g cin_g of the pixel
+//             row; all tap loads go out together (a tap outside the image loads the nearest pixel inside it, never the halo) and a
+//             term outside the image is added as +0 — a select on the product, which leaves the accumulator's bits as they are (it
+//             never holds -0, see gc_forward_kernel).  Everything else (CING == 0) is the generic form: per channel of the dword,
+//             per input channel, per tap one byte load under a branch; correct for a dword that straddles groups, not fast.
+// The order of every output's sum is that of gc_forward_kernel: +0, input channel ascending (outermost), taps row-major, one fp32
+// multiply then one fp32 add per term on x = fl(inv_n * (float)q), bias last.  The epilogue is affine_codes_word of
+// codes_epilogue.h; dwords past G cout_g are written by lanes of their own as zero, the border of a halo plane by the same map.
+struct GcCodesMap {
+    int lanes_log;            // log2 of the lanes along the dwords of a pixel row
+    int slots;                // dwords per output pixel row that are written: ldc / 4, or ceil(G cout_g / 4) for the fp32 form
+    int units, splits;        // pixel steps of 256 >> lanes_log pixels, workgroups per dword group
+    int d_n, d_ho, d_wo;      // splits * (256 >> lanes_log) pixels as (images, rows, columns)
+    int ihy, ihx, ohy, ohx;   // halos of the input and the output plane
+};
+
+struct GcCodesEpi {
+    const float* alpha;
+    const float* beta;
+    const float* bn_stats;
+    int relu;
+    float n;
+    int8_t* codes;
+    int64_t ldc;
+    int32_t* overflow;
+};
+
+struct GcF32Out {
+    float* y;
+    DwStrides ys;
+    const int32_t* overflow;
+    int vec;                  // channels-last, G cout_g % 4 == 0, 16-byte aligned: one float4 store per lane
+};
+
+template <int KH, int KW, int CING, bool F32OUT>
+__global__ __launch_bounds__(DW_THREADS) void gc_codes_kernel(const int8_t* __restrict__ x, int64_t ldx, float inv_n,
+                                                              const float* __restrict__ w, const float* __restrict__ bias,
+                                                              GcCodesEpi ep, GcF32Out fo, GcGeom g, GcCodesMap mp) {
+    constexpr bool GEN = CING == 0;
+    constexpr int T = GEN ? 1 : KH * KW;
+    constexpr bool REGW = !GEN && T == 1;                       // the weights stay in registers
+    extern __shared__ float4 wl4[];                             // [K][lanes]
+    const int tid = threadIdx.x;
+    const int lanes = 1 << mp.lanes_log, tpix = DW_THREADS >> mp.lanes_log;
+    const int sg = (int)(blockIdx.x / mp.splits);
+    const int split = (int)(blockIdx.x - (unsigned)sg * mp.splits);
+    const int ln = tid & (lanes - 1);
+    const int slot = sg * lanes + ln;
+    const int ps = tid >> mp.lanes_log;
+    const bool row_lane = slot < mp.slots;                     // this lane writes a dword of every pixel row
+    const int64_t co0 = (int64_t)slot * 4;
+    const int nvalid = (int)(g.Cout - co0 < 0 ? 0 : (g.Cout - co0 > 4 ? 4 : g.Cout - co0));
+    const int taps = GEN ? g.kh * g.kw : T;
+    const int K = g.cin_g * taps;
+    float4 wr[REGW ? CING : 1];
+    if (REGW) {
+#pragma unroll
+        for (int ci = 0; ci < (REGW ? CING : 1); ++ci) {
+            float we[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) we[e] = e < nvalid ? w[(co0 + e) * K + ci] : 0.0f;
+            wr[ci] = make_float4(we[0], we[1], we[2], we[3]);
+        }
+    } else {
+        float* wl = reinterpret_cast<float*>(wl4);
+        const int64_t cb = (int64_t)sg * lanes * 4;             // first channel of this workgroup's dwords
+        for (int e = tid; e < lanes * 4 * K; e += DW_THREADS) {
+            const int j = e / K, k = e - j * K;
+            wl[(k * lanes + (j >> 2)) * 4 + (j & 3)] = cb + j < g.Cout ? w[(cb + j) * K + k] : 0.0f;
+        }
+        __syncthreads();
+    }
+    float b[4];
+    int cbase[4];                                               // first input channel of each channel's group
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const bool live = e < nvalid;
+        b[e] = (live && bias) ? bias[co0 + e] : 0.0f;
+        cbase[e] = live ? (int)((co0 + e) / g.cout_g) * g.cin_g : 0;
+    }
+    AffineConsts ac;
+    if (!F32OUT) affine_load_consts(ac, co0, g.Cout, ep.alpha, ep.beta, nullptr, nullptr, ep.bn_stats, nullptr);
+    const bool devbn = ep.bn_stats != nullptr;
+    const bool nan_all = F32OUT && fo.overflow != nullptr && *fo.overflow != 0;
+    const int Hp = g.H + 2 * mp.ihy, Wp = g.W + 2 * mp.ihx;
+    const int Hop = g.Ho + 2 * mp.ohy, Wop = g.Wo + 2 * mp.ohx;
+    const unsigned npix = (unsigned)g.N * (unsigned)(g.Ho * g.Wo);              // < 2^31: host check
+    int bad = 0;
+    // the first pixel of this thread, then constant increments
+    unsigned p = (unsigned)split * tpix + ps;
+    int n = (int)(p / (unsigned)(g.Ho * g.Wo));
+    int ho, wo;
+    {
+        const unsigned r = p - (unsigned)n * (unsigned)(g.Ho * g.Wo);
+        ho = (int)(r / (unsigned)g.Wo);
+        wo = (int)(r - (unsigned)ho * g.Wo);
+    }
+    for (int u = split; u < mp.units; u += mp.splits) {
+        if (p < npix && row_lane) {
+            float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (nvalid > 0) {
+                const int h0 = ho * g.sh - g.ph, w0 = wo * g.sw - g.pw;
+                if (!GEN) {
+                    constexpr int NW = CING == 8 ? 2 : 1;
+                    uint32_t raw[T][NW];
+                    bool ok[T];
+#pragma unroll
+                    for (int t = 0; t < T; ++t) {
+                        const int i = t / (GEN ? 1 : KW), j = t - i * (GEN ? 1 : KW);
+                        const int hi = h0 + i * g.dh, wi = w0 + j * g.dw;
+                        ok[t] = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
+                        const int hc = hi < 0 ? 0 : (hi >= g.H ? g.H - 1 : hi), wc = wi < 0 ? 0 : (wi >= g.W ? g.W - 1 : wi);
+                        const int8_t* px = x + (int64_t)((n * Hp + hc + mp.ihy) * Wp + wc + mp.ihx) * ldx + cbase[0];
+                        if (CING == 8) {
+                            const uint2 v2 = *reinterpret_cast<const uint2*>(px);
+                            raw[t][0] = v2.x;
+                            raw[t][NW - 1] = v2.y;
+                        } else if (CING == 4) {
+                            raw[t][0] = *reinterpret_cast<const uint32_t*>(px);
+                        } else {
+                            raw[t][0] = *reinterpret_cast<const uint16_t*>(px);
+                        }
+                    }
+#pragma unroll
+                    for (int ci = 0; ci < (GEN ? 1 : CING); ++ci) {
+#pragma unroll
+                        for (int t = 0; t < T; ++t) {
+                            const float v = inv_n * (float)(int8_t)(raw[t][ci >> 2] >> (8 * (ci & 3)));
+                            const float4 wv = REGW ? wr[REGW ? ci : 0] : wl4[(ci * T + t) * lanes + ln];
+                            const float p0 = v * wv.x, p1 = v * wv.y, p2 = v * wv.z, p3 = v * wv.w;
+                            acc[0] = acc[0] + (ok[t] ? p0 : 0.0f);
+                            acc[1] = acc[1] + (ok[t] ? p1 : 0.0f);
+                            acc[2] = acc[2] + (ok[t] ? p2 : 0.0f);
+                            acc[3] = acc[3] + (ok[t] ? p3 : 0.0f);
+                        }
+                    }
+                } else {
+                    const float* wl = reinterpret_cast<const float*>(wl4);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if (e < nvalid) {
+                            float a = 0.0f;
+                            for (int ci = 0; ci < g.cin_g; ++ci) {
+                                for (int i = 0; i < g.kh; ++i) {
+                                    const int hi = h0 + i * g.dh;
+                                    if (hi < 0 || hi >= g.H) continue;
+                                    for (int j = 0; j < g.kw; ++j) {
+                                        const int wi = w0 + j * g.dw;
+                                        if (wi < 0 || wi >= g.W) continue;
+                                        const int8_t q = x[(int64_t)((n * Hp + hi + mp.ihy) * Wp + wi + mp.ihx) * ldx + cbase[e] + ci];
+                                        const float v = inv_n * (float)q;
+                                        a = a + v * wl[(((ci * g.kh + i) * g.kw + j) * lanes + ln) * 4 + e];
+                                    }
+                                }
+                            }
+                            acc[e] = a;
+                        }
+                    }
+                }
+                if (bias) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[e] = acc[e] + b[e];
+                }
+            }
+            if (F32OUT) {
+                if (nan_all) acc[0] = acc[1] = acc[2] = acc[3] = __builtin_nanf("");
+                float* dst = fo.y + n * fo.ys.n + co0 * fo.ys.c + ho * fo.ys.h + wo * fo.ys.w;
+                if (fo.vec) {
+                    *reinterpret_cast<float4*>(dst) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (e < nvalid) dst[e * fo.ys.c] = acc[e];
+                }
+            } else {
+                const float r0[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                float q4[4];
+                const uint32_t word = affine_codes_word(acc, r0, 0u, ac, nvalid, devbn, false, false, false, false, 0.0f, ep.relu, ep.n, q4, bad);
+                *reinterpret_cast<uint32_t*>(ep.codes + (int64_t)((n * Hop + ho + mp.ohy) * Wop + wo + mp.ohx) * ep.ldc + co0) = word;
+            }
+        }
+        p += (unsigned)mp.splits * tpix;
+        wo += mp.d_wo;
+        const int c1 = wo >= g.Wo;
+        wo -= c1 ? g.Wo : 0;
+        ho += mp.d_ho + c1;
+        const int c2 = ho >= g.Ho;
+        ho -= c2 ? g.Ho : 0;
+        n += mp.d_n + c2;
+    }
+    if (F32OUT) return;
+    if ((mp.ohy | mp.ohx) && row_lane) {
+        // the border pixels of the output plane, enumerated alone as in dw_codes_kernel: per image ohy rows on top, 2 ohx columns
+        // beside each of the Ho image rows, ohy rows below; one dword per lane
+        const unsigned top = (unsigned)mp.ohy * Wop, side = 2u * mp.ohx * g.Ho, per_img = 2u * top + side;
+        const unsigned total = (unsigned)g.N * per_img;                        // < 2^31: host check on the plane's pixel rows
+        for (unsigned t = (unsigned)split * tpix + ps; t < total; t += (unsigned)mp.splits * tpix) {
+            const unsigned img = t / per_img, r = t - img * per_img;
+            unsigned h, c;
+            if (r < top) { h = r / Wop; c = r - h * Wop; }
+            else if (r < top + side) {
+                const unsigned q = r - top, row = q / (2u * mp.ohx), k = q - row * 2u * mp.ohx;
+                h = mp.ohy + row;
+                c = k < (unsigned)mp.ohx ? k : g.Wo + k;
+            } else { const unsigned q = r - top - side; h = mp.ohy + g.Ho + q / Wop; c = q % Wop; }
+            *reinterpret_cast<uint32_t*>(ep.codes + (int64_t)((img * Hop + h) * Wop + c) * ep.ldc + co0) = 0u;
+        }
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(ep.overflow, __any(bad & 2) ? 3 : 1);
+}
+
+inline int64_t gc_code_ld(int64_t K) { return std::max<int64_t>(16, (K + 15) / 16 * 16); }
+
+// the shared body of the two code-plane entries: ep.codes (code plane out) or fo.y (fp32 out)
+int gc_codes_launch(const int8_t* x_plane, int64_t ldx, int64_t ihy, int64_t ihx, float inv_n, const float* w, const float* bias,
+                    GcCodesEpi ep, int bit_width, int64_t ohy, int64_t ohx, GcF32Out fo, int64_t N, int64_t G, int64_t cin_g,
+                    int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, bool f32,
+                    qt_stream_t stream) {
+    GcGeom g{};
+    bool empty;
+    if (ihy < 0 || ihx < 0 || ohy < 0 || ohx < 0) return QT_ERR_INVALID_ARG;
+    const int rc = gc_geometry(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
+    if (rc != QT_OK || empty) return rc;
+    if (ihy > DW_MAX_HALO || ihx > DW_MAX_HALO || ohy > DW_MAX_HALO || ohx > DW_MAX_HALO) return QT_ERR_UNSUPPORTED;
+    if ((double)N * (double)(H + 2 * ihy) * (double)(W + 2 * ihx) >= (double)GC_MAX_ELEMS ||
+        (double)N * (double)(g.Ho + 2 * ohy) * (double)(g.Wo + 2 * ohx) >= (double)GC_MAX_ELEMS)
+        return QT_ERR_UNSUPPORTED;
+    if (!f32 && ep.ldc >= GC_MAX_ELEMS) return QT_ERR_UNSUPPORTED;
+    if (!x_plane || !w) return QT_ERR_INVALID_ARG;
+    if (f32) {
+        if (!fo.y || dw_layout(N, g.Cout, g.Ho, g.Wo, fo.ys) < 0) return QT_ERR_INVALID_ARG;
+    } else {
+        if (bit_width < 2 || bit_width > 8 || ep.relu < 0 || ep.relu > 1) return QT_ERR_INVALID_ARG;
+        if (!ep.alpha || !ep.beta || !ep.codes || !ep.overflow) return QT_ERR_INVALID_ARG;
+        if (ep.ldc < gc_code_ld(g.Cout)) return QT_ERR_INVALID_ARG;
+    }
+    if (ldx < gc_code_ld(g.Cin)) return QT_ERR_INVALID_ARG;
+    if (!dw_aligned4(w) || !dw_aligned4(bias) || !dw_aligned4(ep.alpha) || !dw_aligned4(ep.beta) || !dw_aligned4(ep.bn_stats) ||
+        !dw_aligned4(ep.overflow) || !dw_aligned4(fo.overflow) || !dw_aligned4(fo.y))
+        return QT_ERR_ALIGNMENT;
+    if ((ldx & 15) || !dw_aligned16(x_plane) || (ep.ldc & 15) || !dw_aligned16(ep.codes)) return QT_ERR_ALIGNMENT;
+    ep.n = (float)((1 << (f32 ? 2 : bit_width)) - 1);
+    fo.vec = f32 && dw_layout(N, g.Cout, g.Ho, g.Wo, fo.ys) == 1 && fo.ys.c == 1 && (g.Cout & 3) == 0 && dw_aligned16(fo.y);
+    const bool fixed = (g.cout_g & 3) == 0 && (g.cin_g == 2 || g.cin_g == 4 || g.cin_g == 8) &&
+                       ((kh == 1 && kw == 1) || (kh == 3 && kw == 3));
+    const int K = g.cin_g * kh * kw;
+    const bool regw = fixed && kh == 1;
+    GcCodesMap mp{};
+    const int64_t slots = f32 ? (g.Cout + 3) / 4 : ep.ldc / 4;
+    int lanes = dw_pow2ceil(slots < 64 ? slots : 64);
+    // the staged block wl[K][lanes] float4 stays within GC_LDS_FLOATS (K <= 512: at least 4 lanes)
+    while (!regw && lanes > 1 && (int64_t)lanes * K * 4 > GC_LDS_FLOATS) lanes >>= 1;
+    mp.lanes_log = dw_log2(lanes);
+    mp.slots = (int)slots;
+    const int tpix = DW_THREADS / lanes;
+    const int64_t npix = (int64_t)g.N * g.Ho * g.Wo;
+    mp.units = (int)((npix + tpix - 1) / tpix);
+    const int64_t groups = (slots + lanes - 1) / lanes;
+    int64_t sp = (GC_TARGET_STREAM + groups - 1) / groups;
+    if (sp > mp.units) sp = mp.units;
+    mp.splits = (int)(sp < 1 ? 1 : sp);
+    const int64_t step = (int64_t)mp.splits * tpix;
+    mp.d_wo = (int)(step % g.Wo);
+    mp.d_ho = (int)((step / g.Wo) % g.Ho);
+    mp.d_n = (int)(step / g.Wo / g.Ho);
+    mp.ihy = (int)ihy; mp.ihx = (int)ihx; mp.ohy = (int)ohy; mp.ohx = (int)ohx;
+    const unsigned grid = (unsigned)(groups * mp.splits);
+    const size_t lds = regw ? 0 : sizeof(float) * 4 * lanes * K;
+    hipStream_t s = (hipStream_t)stream;
+#define GC_CODES_ARGS x_plane, ldx, inv_n, w, bias, ep, fo, g, mp
+#define GC_CODES_LAUNCH(KH, KW, CING)                                                                                  \
+    do {                                                                                                               \
+        if (f32) gc_codes_kernel<KH, KW, CING, true><<<grid, DW_THREADS, lds, s>>>(GC_CODES_ARGS);                     \
+        else gc_codes_kernel<KH, KW, CING, false><<<grid, DW_THREADS, lds, s>>>(GC_CODES_ARGS);                        \
+    } while (0)
+#define GC_CODES_CING(KH, KW)                                                                                          \
+    do {                                                                                                               \
+        if (g.cin_g == 2) GC_CODES_LAUNCH(KH, KW, 2);                                                                  \
+        else if (g.cin_g == 4) GC_CODES_LAUNCH(KH, KW, 4);                                                             \
+        else GC_CODES_LAUNCH(KH, KW, 8);                                                                               \
+    } while (0)
+    if (!fixed) GC_CODES_LAUNCH(0, 0, 0);
+    else if (kh == 1) GC_CODES_CING(1, 1);
+    else GC_CODES_CING(3, 3);
+#undef GC_CODES_CING
+#undef GC_CODES_LAUNCH
+#undef GC_CODES_ARGS
+    return qt_check_launch();
+}
+
 inline DwMap gc_reduce_plan(const GcGeom& g, int cl) { return dw_plan(cl, g.N, g.Cout * g.cin_g, g.Ho, g.Wo, GC_TARGET_REDUCE); }
 inline int64_t gc_work_floats(const GcGeom& g, int splits) { return (int64_t)splits * g.Cout * g.cin_g * (g.kh * g.kw + 1); }
 // 1: the 1 x 1 tile kernel, 3: the 3 x 3 one, 0: the virtual-channel kernel
@@ -834,4 +1136,34 @@ extern "C" int qt_gconv2d_bits_f32(const uint32_t* x_plane, int64_t ldx, const f
     o.y = y;
     return gc_planes_launch(x_plane, ldx, w, bias, nullptr, nullptr, o, true, 0, 0, N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh,
                             dw, DwStrides{ys_n, ys_c, ys_h, ys_w}, kind, stream);
+}
+
+extern "C" int qt_gconv2d_codes(const int8_t* x_plane, int64_t ldx_bytes, int64_t in_halo_h, int64_t in_halo_w, float inv_n,
+                                const float* w, const float* bias, const float* alpha, const float* beta, const float* bn_stats,
+                                int relu, int bit_width, int8_t* codes, int64_t ldc_bytes, int64_t out_halo_h, int64_t out_halo_w,
+                                int32_t* overflow, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh,
+                                int kw, int sh, int sw, int ph, int pw, int dh, int dw, qt_stream_t stream) {
+    GcCodesEpi ep{};
+    ep.alpha = alpha;
+    ep.beta = beta;
+    ep.bn_stats = bn_stats;
+    ep.relu = relu;
+    ep.codes = codes;
+    ep.ldc = ldc_bytes;
+    ep.overflow = overflow;
+    return gc_codes_launch(x_plane, ldx_bytes, in_halo_h, in_halo_w, inv_n, w, bias, ep, bit_width, out_halo_h, out_halo_w, GcF32Out{},
+                           N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, false, stream);
+}
+
+extern "C" int qt_gconv2d_codes_f32(const int8_t* x_plane, int64_t ldx_bytes, int64_t in_halo_h, int64_t in_halo_w, float inv_n,
+                                    const float* w, const float* bias, const int32_t* overflow, float* y, int64_t N, int64_t G,
+                                    int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph,
+                                    int pw, int dh, int dw, int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w,
+                                    qt_stream_t stream) {
+    GcF32Out fo{};
+    fo.y = y;
+    fo.ys = DwStrides{ys_n, ys_c, ys_h, ys_w};
+    fo.overflow = overflow;
+    return gc_codes_launch(x_plane, ldx_bytes, in_halo_h, in_halo_w, inv_n, w, bias, GcCodesEpi{}, 0, 0, 0, fo, N, G, cin_g, cout_g, H,
+                           W, kh, kw, sh, sw, ph, pw, dh, dw, true, stream);
 }

@@ -939,6 +939,24 @@ def packed_grouped_conv2d(layer, act):
                                         layer.dilation, layer.groups, kind="raw")
 
 
+def codes_grouped_conv2d(layer, act):
+    """Eval-mode DorefaConv2d with ``1 < groups < in_channels`` (any weight bit_width) on a CodeActivation: the sibling of
+    ``codes_depthwise_conv2d`` — the fp32 [N, G * cout_g, Ho, Wo] result in the layout the module graph's conv result has
+    (``CodeActivation.source_channels_last``), bias added, from one launch on the code plane (ops.grouped_conv2d_from_codes); what a
+    deferred grouped DoReFa conv materialises to when its chain cannot run fused.  The stored eval image is multiplied as it is; a
+    raised int8 range flag of the activation's chain makes the result NaN on the device."""
+    if layer.training:
+        raise RuntimeError("CodeActivation inputs are an inference feature: call .eval() first")
+    cin_g = int(layer.weight.shape[1])
+    if (layer.padding_mode != "zeros" or len(act.shape) != 4 or layer.groups < GROUPED_MIN_GROUPS or not 2 <= cin_g <= GROUPED_MAX_CIN_G
+            or not ops.grouped_codes_applicable(act.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups)):
+        raise ValueError(f"grouped conv on codes needs at least {GROUPED_MIN_GROUPS} groups of 2 ... {GROUPED_MAX_CIN_G} input channels, "
+                         "numeric zero padding and a shape inside the kernels' limits")
+    return ops.grouped_conv2d_from_codes(act.codes, act.shape, layer.weight.detach(), layer.bias, layer.stride, layer.padding,
+                                         layer.dilation, layer.groups, in_halo=act.halo,
+                                         channels_last=bool(act.source_channels_last), flagged=not ops._cfg("ASSUME_CODES_FIT"))
+
+
 def packed_xnor_conv2d(layer, act, epi=None):
     """Eval-mode XNORConv2d on a PackedActivation: the per-tap scaled fp4 conv (ops.conv2d_nib_taps) on the activation's nibble
     plane — the producer's own (zero halo = this conv's padding, un-padded kernel) when its pixel stride is whole 32-byte taps,

@@ -10,4 +10,4 @@ from .WQR_layers import LinearQuantWLin, LinearQuantWLog, QuantConv2dWLin, Quant
 from .common import QLayer
 from .fused import (FusedTrainPoolBnSign, FusedTrainBnActQuant, fuse_sequential_training, CodeMaxPool, FusedBnDorefaQuant, FusedDorefaConvBnQuant, FusedPoolBnSign, FusedConvPoolBnSign, FusedFeatureClassifier, PackedMaxPool, fuse_sequential, fold_batchnorm,
                     permute_fc_weight_hwc, FusedLogLinConvBnQuant, LevelMaxPool, FusedBnLogLinQuant, FusedDepthwiseBnSign, FusedGroupedBnSign,
-                    FusedDepthwiseDorefaBnQuant)
+                    FusedDepthwiseDorefaBnQuant, FusedGroupedDorefaBnQuant)

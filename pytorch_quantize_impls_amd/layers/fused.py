@@ -542,6 +542,71 @@ class FusedDepthwiseDorefaBnQuant(torch.nn.Module):
         return packed.CodeActivation(out, (N, conv.out_channels, Ho, Wo), halo=self.out_halo)
 
 
+class FusedGroupedDorefaBnQuant(torch.nn.Module):
+    """Grouped DorefaConv2d (eval; at least ``_fused.GROUPED_MIN_GROUPS`` groups of 2 ... ``_fused.GROUPED_MAX_CIN_G`` input
+    channels, not depthwise; ANY weight bit_width whose eval image is on the quantiser's grid) -> BatchNorm2d(eval) [-> ReLU] ->
+    nnDorefaQuant(k): the grouped sibling of ``FusedDepthwiseDorefaBnQuant``.  ONE launch (qt_gconv2d_codes) reads the int8 code plane
+    of a CodeActivation (any halo: it is never read), computes the conv in the pinned fp32 order of ``ops.grouped_conv2d`` on the
+    image fl(inv_n * code) with the stored weight image as it is, and writes the next layer's code plane with ``out_halo`` as its
+    zero border.  No residual, no ReLU in front of the BatchNorm.  ``fold="device"`` as in the depthwise sibling."""
+
+    def __init__(self, conv, bn, bit_width: int, relu=True, out_halo=(0, 0), fold=None):
+        super().__init__()
+        from .dorefa_layers import DorefaConv2d
+        from ..functions import _fused
+        if not isinstance(conv, DorefaConv2d):
+            raise ValueError("FusedGroupedDorefaBnQuant fuses a grouped DorefaConv2d only")
+        if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+            raise ValueError("only zero-padded convs with numeric padding can be fused")
+        cin_g = int(conv.weight.shape[1])
+        if conv.groups < _fused.GROUPED_MIN_GROUPS or conv.groups == conv.in_channels or not 2 <= cin_g <= _fused.GROUPED_MAX_CIN_G:
+            raise ValueError(f"only convs with at least {_fused.GROUPED_MIN_GROUPS} groups of 2 ... {_fused.GROUPED_MAX_CIN_G} input "
+                             "channels can be fused (depthwise: FusedDepthwiseDorefaBnQuant; ungrouped: FusedDorefaConvBnQuant)")
+        kh, kw = conv.kernel_size
+        dh, dw = ops._pairs(conv.dilation)
+        fits = (1, conv.in_channels, dh * (kh - 1) + 1, dw * (kw - 1) + 1)       # the smallest image the kernel fits
+        if not ops.grouped_codes_applicable(fits, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups):
+            raise ValueError("a grouped conv outside the limits of the HIP kernels (ops.grouped_codes_applicable)")
+        if not isinstance(bn, torch.nn.BatchNorm2d) or bn.num_features != conv.out_channels:
+            raise ValueError("BatchNorm2d over the conv's output channels expected")
+        if not 2 <= int(bit_width) <= 8:
+            raise ValueError("code planes exist for 2 <= bit_width <= 8")
+        self.fold = fold or DEFAULT_FOLD
+        self.conv, self.bn, self.bit_width, self.relu = conv, bn, int(bit_width), ops.relu_mode(relu)
+        if self.relu == 2:
+            raise ValueError("the grouped code epilogue has no ReLU in front of the BatchNorm (relu='pre')")
+        self.out_halo = (int(out_halo),) * 2 if isinstance(out_halo, int) else tuple(int(v) for v in out_halo)
+        self._folded = None
+
+    def refold(self):
+        self._folded = None
+
+    def forward(self, act, residual=None):
+        conv = self.conv
+        if conv.training or self.bn.training:
+            raise ValueError("FusedGroupedDorefaBnQuant is an inference form: call .eval() first")
+        if residual is not None:
+            raise ValueError("the grouped code epilogue takes no residual")
+        if not isinstance(act, packed.CodeActivation):
+            raise TypeError("FusedGroupedDorefaBnQuant consumes a CodeActivation (a fused DoReFa block's output)")
+        shape = act.shape
+        if len(shape) != 4 or not ops.grouped_codes_applicable(shape, conv.weight.shape, conv.stride, conv.padding, conv.dilation,
+                                                               conv.groups):
+            raise ValueError(f"not a grouped conv the HIP kernels take: input {tuple(shape)}")
+        if not conv._eval_on_grid():
+            raise ValueError("the eval-mode weight is off the quantiser's grid")
+        N, _, H, W = shape
+        Ho, Wo = ops.conv_out_hw(H, W, conv.kernel_size[0], conv.kernel_size[1], conv.stride, conv.padding, conv.dilation)
+        # the tensor the module graph hands to F.batch_norm is this conv's fp32 output, which takes its input's layout
+        like = ((N, conv.out_channels, Ho, Wo), bool(act.source_channels_last)) if self.fold == "device" else None
+        folded = _code_fold_for(self, "_folded", self.bn, self.fold, like)
+        epi = ops.CodeEpilogue(folded[0], folded[1], self.bit_width, self.relu, out_halo=self.out_halo,
+                               bn_stats=folded[2] if len(folded) > 2 else None, overflow=act.codes.overflow)
+        out = ops.grouped_conv2d_codes(act.codes, shape, conv.weight.detach(), conv.bias, epi, conv.stride, conv.padding,
+                                       conv.dilation, conv.groups, in_halo=act.halo)
+        return packed.CodeActivation(out, (N, conv.out_channels, Ho, Wo), halo=self.out_halo)
+
+
 class CodeMaxPool(torch.nn.Module):
     """MaxPool2d on a CodeActivation (the reference's DoReFa CNNs pool AFTER the quantiser,
     models/samples/AlexNet_Dorefa.py:38-41): the max of the int8 codes, bit-identical to pooling the fp32 image.

@@ -53,6 +53,14 @@ its producer's bit planes and runs as ``layers.fused.FusedGroupedBnSign`` — on
 layer's planes or nibble operand; a deferred grouped conv on planes that must materialise computes its fp32 value from the planes
 (``_fused.packed_grouped_conv2d``).  On an fp32 tensor — at the head of a chain — a grouped layer never defers.
 
+Grouped DorefaConv2d with at least ``_fused.GROUPED_MIN_GROUPS`` groups of 2 ... ``_fused.GROUPED_MAX_CIN_G`` input channels (any
+weight bit_width) joins the DoReFa code chain as its depthwise sibling does (``DEFER_GROUPED_CODES``, together with ``DEFER_CODES``;
+``grouped_deferred()`` sets it with ``DEFER_GROUPED``): the layer takes its producer's int8 code plane — whatever halo it has — and
+runs as ``layers.fused.FusedGroupedDorefaBnQuant``, one launch (qt_gconv2d_codes) from codes to the next layer's codes.  It takes
+no residual (an ``add`` behind its BatchNorm materialises); a deferred grouped conv on codes that must materialise computes its
+fp32 value from the codes (``_fused.codes_grouped_conv2d``).  Two or three groups and more than ``GROUPED_MAX_CIN_G`` channels per
+group keep their module-by-module path.
+
 Nothing is deferred in training mode, with autograd enabled, on CPU tensors, for non-fp32 dtypes, grouped convs other than
 those depthwise and few-channel ones or non-zero padding modes.  ``lazy.ENABLED = False`` (or the ``eager()`` context manager) switches the mechanism off;
 ``lazy.STATS`` counts what happened (tests assert on it).
@@ -111,6 +119,14 @@ DEFER_DEPTHWISE_CODES = True
 #: False = every call runs exactly as without this mechanism: the grouped layer returns fp32 from qt_gconv2d_f32 and the chain in
 #: front of it materialises (``grouped_deferred()`` switches it for a block).
 DEFER_GROUPED = True
+#: grouped DorefaConv2d (``groups >= _fused.GROUPED_MIN_GROUPS``, 2 ... ``_fused.GROUPED_MAX_CIN_G`` input channels per group, any
+#: weight bit_width with an on-grid eval image, shapes ``ops.grouped_codes_applicable`` takes — the layers ``_fused.grouped_route``
+#: sends to qt_gconv2d_f32) joins the DoReFa code chain — needs ``DEFER_CODES`` as well: the layer defers, reads its producer's int8
+#: code plane and runs as ``layers.fused.FusedGroupedDorefaBnQuant``, one launch from codes to the next layer's codes (DESIGN.md
+#: "Grouped convs", "Inside the fused int8 code chain", says what was measured and why the default is what it is).  False = every
+#: call runs exactly as without this mechanism: the grouped layer computes fp32 from the expanded image and the chain in front of
+#: it materialises (``grouped_deferred()`` switches it for a block).
+DEFER_GROUPED_CODES = True
 #: "deferred" convs that returned a LazyActivation, "fused" chains executed as fused blocks, "materialised" lazies that
 #: had to produce their fp32 value, "fallback:<func>" the functions that forced it
 STATS = collections.Counter()
@@ -190,13 +206,15 @@ def depthwise_deferred(on: bool = True):
 
 @contextlib.contextmanager
 def grouped_deferred(on: bool = True):
-    """Defer grouped sign convs (``DEFER_GROUPED``) inside the block; process-wide, restores the previous setting."""
-    global DEFER_GROUPED
+    """Defer grouped sign convs (``DEFER_GROUPED``) and grouped DoReFa convs (``DEFER_GROUPED_CODES``) inside the block;
+    process-wide, restores both previous settings."""
+    global DEFER_GROUPED, DEFER_GROUPED_CODES
     prev, DEFER_GROUPED = DEFER_GROUPED, bool(on)
+    prev_codes, DEFER_GROUPED_CODES = DEFER_GROUPED_CODES, bool(on)
     try:
         yield
     finally:
-        DEFER_GROUPED = prev
+        DEFER_GROUPED, DEFER_GROUPED_CODES = prev, prev_codes
 
 
 class _Node:
@@ -285,9 +303,12 @@ class _Node:
                 y = codes.float()
             elif self.parent is None:
                 if self.kind == "dorefa" and self.layer.groups != 1 and isinstance(self.input, packed.CodeActivation):
-                    # a depthwise DoReFa conv on codes: its fp32 value from the code plane, one launch
+                    # a depthwise or grouped DoReFa conv on codes: its fp32 value from the code plane, one launch
                     from .functions import _fused
-                    y = _fused.codes_depthwise_conv2d(self.layer, self.input)
+                    if self.layer.groups == self.layer.in_channels:
+                        y = _fused.codes_depthwise_conv2d(self.layer, self.input)
+                    else:
+                        y = _fused.codes_grouped_conv2d(self.layer, self.input)
                 else:
                     y = self.layer._forward_impl(self.input)
             else:
@@ -379,7 +400,7 @@ def _force_codes(self, halo=None):
         with torch.no_grad():
             blk = _code_block(self.layer, self.bn, self.quant, self.relu, halo if self.pool2 is None else (0, 0))
             if self.layer.groups != 1 and self.add is not None:
-                raise ValueError("the depthwise code epilogue takes no residual")
+                raise ValueError("the depthwise and grouped code epilogues take no residual")
             res = res_bn = res_conv = None
             if self.add is not None:
                 other = self.add
@@ -580,7 +601,8 @@ def _code_block(layer, bn, bit_width, relu, halo):
         per = _BLOCKS[layer] = collections.OrderedDict()
     blk = per.get(key)
     if blk is None:
-        make = fused.FusedDepthwiseDorefaBnQuant if layer.groups != 1 else fused.FusedDorefaConvBnQuant
+        make = (fused.FusedDorefaConvBnQuant if layer.groups == 1 else
+                fused.FusedDepthwiseDorefaBnQuant if layer.groups == layer.in_channels else fused.FusedGroupedDorefaBnQuant)
         blk = make(layer, _BnView(rm, rv, w, b, eps), bit_width, relu=relu, out_halo=halo, fold="device")
         per[key] = blk
         while len(per) > _MAX_BLOCKS_PER_LAYER:
@@ -1182,12 +1204,23 @@ def _dorefa_can_defer(layer, input) -> bool:
         return False
     w = layer.weight
     if layer.groups != 1:
-        # depthwise only (DEFER_DEPTHWISE_CODES), any weight bit_width, inside the limits of the depthwise kernels; every other
-        # grouped conv runs eagerly
-        if not (DEFER_CODES and DEFER_DEPTHWISE_CODES and layer.groups == layer.in_channels
-                and ops.depthwise_applicable(tuple(getattr(input, "shape", ())), tuple(w.shape), layer.stride, layer.padding,
-                                             layer.dilation, layer.groups)):
+        # any weight bit_width.  Depthwise (DEFER_DEPTHWISE_CODES): inside the limits of the depthwise kernels.  Otherwise
+        # (DEFER_GROUPED_CODES): the layers _fused.grouped_route sends to qt_gconv2d_f32 — at least GROUPED_MIN_GROUPS groups of
+        # 2 ... GROUPED_MAX_CIN_G input channels — so the deferred value has the eager one's arithmetic.  Every other grouped conv
+        # runs eagerly
+        shape = tuple(getattr(input, "shape", ()))
+        if not DEFER_CODES:
             return False
+        if layer.groups == layer.in_channels:
+            if not (DEFER_DEPTHWISE_CODES
+                    and ops.depthwise_applicable(shape, tuple(w.shape), layer.stride, layer.padding, layer.dilation, layer.groups)):
+                return False
+        else:
+            from .functions import _fused
+            if not (DEFER_GROUPED_CODES and layer.groups >= _fused.GROUPED_MIN_GROUPS
+                    and 2 <= int(w.shape[1]) <= _fused.GROUPED_MAX_CIN_G
+                    and ops.grouped_codes_applicable(shape, tuple(w.shape), layer.stride, layer.padding, layer.dilation, layer.groups)):
+                return False
     elif layer.bit_width != 1:
         return False
     if not w.is_cuda or w.dtype != torch.float32 or not isinstance(input, packed.CodeActivation) or len(input.shape) != 4:
@@ -1198,8 +1231,8 @@ def _dorefa_can_defer(layer, input) -> bool:
 
 
 def dorefa_conv_forward(layer, input):
-    """forward() of DorefaConv2d: a 1-bit-weight conv — or, under DEFER_DEPTHWISE_CODES, a depthwise conv of any weight bit_width —
-    in eval mode whose input carries int8 codes (the tag nnDorefaQuant leaves on its result, a CodeActivation, or a deferred
+    """forward() of DorefaConv2d: a 1-bit-weight conv — or, under DEFER_DEPTHWISE_CODES / DEFER_GROUPED_CODES, a depthwise / grouped
+    conv of any weight bit_width — in eval mode whose input carries int8 codes (the tag nnDorefaQuant leaves on its result, a CodeActivation, or a deferred
     quantised chain) defers itself."""
     note_inference_call(layer, input)
     if isinstance(input, LazyActivation):
@@ -1207,7 +1240,8 @@ def dorefa_conv_forward(layer, input):
         act = None
         if layer.groups != 1:
             if enabled() and n.kind == "dorefa" and n.quant is not None and _dorefa_can_defer(layer, _CodeShapeOnly(n.shape)):
-                # a depthwise consumer skips the taps outside the image itself: any plane already produced serves it, whatever its halo
+                # a depthwise or grouped consumer skips the taps outside the image itself: any plane already produced serves it,
+                # whatever its halo
                 act = n.force_any() if n.packed_cache else n.force((0, 0))
         elif n.kind == "dorefa" and n.quant is not None and _dorefa_can_defer(layer, _CodeShapeOnly(n.shape)):
             pad = tuple(int(v) for v in ops._pairs(layer.padding))
@@ -1225,19 +1259,20 @@ def dorefa_conv_forward(layer, input):
     defer = enabled() and DEFER_CODES
     if defer and not isinstance(input, packed.CodeActivation) and isinstance(input, torch.Tensor) and input.is_cuda \
             and input.dtype == torch.float32 and input.dim() == 4 and not torch.is_grad_enabled() and not layer.training \
-            and (layer.bit_width == 1 if layer.groups == 1 else DEFER_DEPTHWISE_CODES):
+            and (layer.bit_width == 1 if layer.groups == 1 else
+                 DEFER_DEPTHWISE_CODES if layer.groups == layer.in_channels else DEFER_GROUPED_CODES):
         codes = packed.lookup_codes(input, packed.NHWC)
         N, C, H, W = (int(v) for v in input.shape)
         if codes is not None and codes.K == C and codes.rows == N * H * W:
             cand = packed.CodeActivation(codes, (N, C, H, W))
-            cand.source_channels_last = ops._dw_channels_last(input)      # (read by a depthwise consumer alone)
+            cand.source_channels_last = ops._dw_channels_last(input)      # (read by a depthwise or grouped consumer alone)
             if _dorefa_can_defer(layer, cand):
                 tagged, input = input, cand
     if defer and _dorefa_can_defer(layer, input):
         N, C, H, W = (int(v) for v in input.shape)
         kh, kw = layer.kernel_size
         Ho, Wo = ops.conv_out_hw(H, W, kh, kw, layer.stride, layer.padding, layer.dilation)
-        # (127 kh kw ld < 2^24 bounds the int8 conv's integer accumulator; the depthwise conv accumulates in fp32)
+        # (127 kh kw ld < 2^24 bounds the int8 conv's integer accumulator; the depthwise and grouped convs accumulate in fp32)
         if Ho > 0 and Wo > 0 and (layer.groups != 1 or 127 * kh * kw * int(input.codes.codes.shape[1]) < (1 << 24)):
             STATS["deferred"] += 1
             node = _Node(None, None, (N, int(layer.out_channels), int(Ho), int(Wo)), layer=layer, kind="dorefa", input=input)

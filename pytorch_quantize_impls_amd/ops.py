@@ -4604,6 +4604,96 @@ def grouped_conv2d_from_bits(planes: BitPlanes, shape, weight: torch.Tensor, bia
     return y
 
 
+def grouped_codes_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
+    """The grouped convs that run on the int8 code plane of a DoReFa activation (``grouped_conv2d_codes`` /
+    ``grouped_conv2d_from_codes``): those ``grouped_applicable`` takes — any cin_g the fp32 entry takes, any cout_g; the pixel rows of
+    the un-bordered planes are bounded by the tensors' elements.  A pure function of the shapes: it does not know the halos, so a
+    plane whose border (up to 64 pixels a side) brings it to 2^31 pixel rows or more passes here and is refused by the entry
+    (QT_ERR_UNSUPPORTED, raised by the wrapper) — as with ``depthwise_applicable`` and the depthwise code entries."""
+    return grouped_applicable(x_shape, w_shape, stride, padding, dilation, groups)
+
+
+def _gc_codes_geometry(codes, shape, in_halo, weight, stride, padding, dilation, groups):
+    x_shape, halo = _dw_code_input(codes, shape, in_halo)
+    w, geom, y_shape = _gc_geometry(x_shape, weight, stride, padding, dilation, groups)
+    if w.device != codes.device:
+        raise ValueError("input and weight are on different devices")
+    return w, geom, y_shape, halo
+
+
+def grouped_conv2d_codes(codes: CodePlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor], epi: CodeEpilogue, stride=1,
+                         padding=0, dilation=1, groups: int = 1, in_halo=(0, 0), out: Optional[torch.Tensor] = None) -> CodePlanes:
+    """Grouped conv (``grouped_conv2d``'s pinned fp32 arithmetic on the image fl(inv_n * code)) -> BatchNorm -> [ReLU] -> k-bit
+    DoReFa quantiser, from the int8 code plane ``codes`` (logical ``shape`` (N, G * cin_g, H, W), zero border of ``in_halo`` pixels
+    that is never read) to the next code plane in ONE launch (qt_gconv2d_codes): no fp32 activation exists.  ``epi``, ``out`` and the
+    result as ``depthwise_conv2d_codes``: a ``CodeEpilogue`` without a residual, whose ``out_halo`` is the zero border of the
+    produced plane [N*(Ho+2hy)*(Wo+2hx), code_ld_bytes(G*cout_g, 16)], of which the launch writes every byte."""
+    w, geom, y_shape, (ihy, ihx) = _gc_codes_geometry(codes, shape, in_halo, weight, stride, padding, dilation, groups)
+    dev = codes.device
+    if not isinstance(epi, CodeEpilogue):
+        raise TypeError(f"epi: expected a CodeEpilogue, got {type(epi)}")
+    if epi.res_f32 is not None or epi.res_codes is not None or epi.res_affine is not None or any(epi.res_halo):
+        raise ValueError("the grouped code epilogue takes no residual")
+    relu = relu_mode(epi.relu)
+    if relu == 2:
+        raise ValueError("the grouped code epilogue has no ReLU in front of the BatchNorm (relu='pre')")
+    if not 2 <= int(epi.bit_width) <= 8:
+        raise ValueError("int8 code planes exist for 2 <= bit_width <= 8")
+    N, Cout, Ho, Wo = y_shape
+    bias = _check_bias(bias, Cout, dev)
+    alpha, beta = _check_bias(epi.alpha, Cout, dev, "alpha"), _check_bias(epi.beta, Cout, dev, "beta")
+    if alpha is None or beta is None:
+        raise TypeError("alpha and beta: expected fp32 device vectors")
+    stats = None
+    if epi.bn_stats is not None:
+        stats = _require(epi.bn_stats, "bn_stats").contiguous()
+        if stats.numel() != 2 * Cout or stats.device != dev:
+            raise ValueError("bn_stats must hold [mean | rs]: 2 * G * cout_g values on the input's device")
+    ohy, ohx = (int(v) for v in _pairs(epi.out_halo))
+    if ohy < 0 or ohx < 0:
+        raise ValueError("out_halo must not be negative")
+    flag = epi.overflow if epi.overflow is not None else codes.overflow
+    if flag is None:
+        flag = torch.zeros((1,), dtype=torch.int32, device=dev)
+    _require(flag, "overflow", torch.int32)
+    rows, ldc = N * (Ho + 2 * ohy) * (Wo + 2 * ohx), code_ld_bytes(Cout, 16)
+    if out is None:
+        out = torch.empty((rows, ldc), dtype=torch.int8, device=dev)      # the launch writes every byte, halo border included
+    else:
+        _require(out, "out", torch.int8)
+        if tuple(out.shape) != (rows, ldc) or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out: expected a contiguous int8 tensor [{rows}, {ldc}] on {dev}, got {tuple(out.shape)} on {out.device}")
+    if N * Cout * Ho * Wo > 0:
+        with _on(dev):
+            _lib.call("qt_gconv2d_codes", _p(codes.codes), int(codes.codes.shape[1]), ihy, ihx, float(codes.inv_n), _p(w), _p(bias),
+                      _p(alpha), _p(beta), _p(stats), relu, int(epi.bit_width), _p(out), ldc, ohy, ohx, _p(flag), *geom, _stream(dev))
+    return CodePlanes(codes=out, rows=rows, K=Cout, inv_n=inv_levels(epi.bit_width), bit_width=int(epi.bit_width), overflow=flag)
+
+
+def grouped_conv2d_from_codes(codes: CodePlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1,
+                              padding=0, dilation=1, groups: int = 1, in_halo=(0, 0), channels_last: bool = True,
+                              out: Optional[torch.Tensor] = None, flagged: bool = True) -> torch.Tensor:
+    """``grouped_conv2d`` of the DoReFa activation that exists only as the code plane ``codes`` (see ``grouped_conv2d_codes``): the
+    fp32 result, bit for bit that of the fp32 image fl(inv_n * code), in ``channels_last`` or NCHW storage or written into ``out``
+    (qt_gconv2d_codes_f32, one launch).  ``flagged``: a raised int8 range flag of the plane's chain makes every value NaN, on the
+    device."""
+    w, geom, y_shape, (ihy, ihx) = _gc_codes_geometry(codes, shape, in_halo, weight, stride, padding, dilation, groups)
+    dev = codes.device
+    bias = _check_bias(bias, y_shape[1], dev)
+    if out is None:
+        y = torch.empty(y_shape, dtype=torch.float32, device=dev,
+                        memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    else:
+        y = _dw_result(out, y_shape, w, "out")
+    if y.numel() == 0:
+        return y
+    flag = codes.overflow if flagged else None
+    with _on(dev):
+        _lib.call("qt_gconv2d_codes_f32", _p(codes.codes), int(codes.codes.shape[1]), ihy, ihx, float(codes.inv_n), _p(w), _p(bias),
+                  _p(flag), _p(y), *geom, *_dw_strides(y.shape, _dw_channels_last(y)), _stream(dev))
+    return y
+
+
 def grouped_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_output: torch.Tensor, stride=1, padding=0, dilation=1,
                               groups: int = 1, kind: str = "raw", channels_last: Optional[bool] = None,
                               out: Optional[torch.Tensor] = None) -> torch.Tensor:

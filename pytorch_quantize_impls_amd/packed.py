@@ -145,7 +145,8 @@ class CodeActivation:
         # rows = N*(H + 2hy)*(W + 2hx): the next conv's zero padding is then physical (un-padded kernels)
         self.halo = tuple(int(v) for v in halo)
         # memory format of the fp32 tensor the module graph has in this activation's place: channels-last for the output of a fused
-        # block; lazy.py clears it for the code tag of an NCHW fp32 tensor (a depthwise consumer's result takes its input's layout)
+        # block; lazy.py clears it for the code tag of an NCHW fp32 tensor (a depthwise or grouped consumer's result takes its input's
+        # layout)
         self.source_channels_last = True
         if any(self.halo) and len(self.shape) != 4:
             raise ValueError("only (N, C, H, W) activations carry a halo")

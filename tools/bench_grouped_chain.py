@@ -30,6 +30,24 @@ bytes, so it is a lower bound of the grouped part's own share.
 ``--docs`` rewrites the table between the ``grouped-chain-table`` markers of README.md and DESIGN.md.  ``--kernel-times`` adds the
 grouped plane kernel's own time per shape (``kernel_us``) from one separate ``rocprofv3 --kernel-trace --stats`` pass of each child,
 with no counters in that run.
+
+``--family dorefa`` measures the DoReFa counterpart with the same shapes and the same protocol:
+
+    pw 1x1 (bit_width 1) -> run -> grouped k x k (bit_width 1) -> run -> pw 1x1 (bit_width 1) -> run
+                                                                              run = BatchNorm -> ReLU -> nnDorefaQuant(4)
+
+on a quantiser-tagged fp32 input (the channels-last result of nnDorefaQuant(4): an fp32 image that carries its int8 codes).
+  deferred : ``lazy.grouped_deferred(True)`` — the grouped layer reads the first pointwise chain's code plane and writes the second
+             pointwise conv's code plane in ONE launch (qt_gconv2d_codes);
+  eager    : ``lazy.grouped_deferred(False)`` — the path without ``lazy.DEFER_GROUPED_CODES`` (that of the commit before it): the
+             producer's codes are expanded to fp32, qt_gconv2d_f32 reads that image and writes fp32, BatchNorm, ReLU and the quantiser
+             are three passes over fp32 tensors, then the second pointwise conv runs on the quantiser's codes.
+Both sides end by asking for the triple's int8 code plane and must agree on it.  ``bytes`` of the grouped part, from the shapes, by
+the count of tools/bench_depthwise_chain.py:
+  eager    : conv 4|x| + 4|y|, BatchNorm 8|y|, ReLU 8|y|, quantiser 4|y| in + 4|y| image + |y| codes  =  4|x| + 29|y|
+  deferred : |x| + |y| (one code in, one code out)
+The line goes to profiles/grouped_codes_chain_bench_line.json, the table between the ``grouped-codes-chain-table`` markers;
+``--kernel-times`` then times gc_codes_kernel.
 """
 import argparse
 import json
@@ -51,6 +69,8 @@ CHILD_LIMIT_S = 300
 STEPS = 20
 MARK = "grouped-chain-table"
 KERNEL = "gc_planes_kernel"
+FAMILIES = {"sign": {"mark": MARK, "out": "grouped_chain_bench_line.json", "kernel": KERNEL},
+            "dorefa": {"mark": "grouped-codes-chain-table", "out": "grouped_codes_chain_bench_line.json", "kernel": "gc_codes_kernel"}}
 
 
 def algorithmic_bytes(C, H, stride, k):
@@ -59,20 +79,26 @@ def algorithmic_bytes(C, H, stride, k):
     return {"eager": 32 * x + 32 * y, "deferred": x // 4 + y // 2}
 
 
-def kernel_time_us(index, workdir):
-    """Average duration of the grouped plane kernel in one ``rocprofv3 --kernel-trace --stats`` pass of the child of shape ``index``
+def algorithmic_bytes_dorefa(C, H, stride, k):
+    Ho = (H + 2 * (k // 2) - k) // stride + 1
+    x, y = BATCH * C * H * H, BATCH * C * Ho * Ho
+    return {"eager": 4 * x + 29 * y, "deferred": x + y}
+
+
+def kernel_time_us(index, workdir, family="sign"):
+    """Average duration of the family's grouped chain kernel in one ``rocprofv3 --kernel-trace --stats`` pass of the child of shape ``index``
     (one round; no counters in the run)."""
     import csv
     import glob
-    out = os.path.join(workdir, f"kt_{index}")
+    out = os.path.join(workdir, f"kt_{family}_{index}")
     p = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "-d", out, "-o", "gc", "--output-format", "csv", "--",
-                        sys.executable, os.path.abspath(__file__), "--child", str(index), "--rounds", "1"],
+                        sys.executable, os.path.abspath(__file__), "--child", str(index), "--rounds", "1", "--family", family],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=CHILD_LIMIT_S)
     if p.returncode != 0:
         raise SystemExit(f"shape {SHAPES[index]}: the profiled process ended with status {p.returncode}; nothing more was started")
     path = sorted(glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True))[0]
     with open(path) as fh:
-        rows = [r for r in csv.DictReader(fh) if KERNEL in r["Name"]]
+        rows = [r for r in csv.DictReader(fh) if FAMILIES[family]["kernel"] in r["Name"]]
     calls = sum(int(r["Calls"]) for r in rows)
     return round(sum(float(r["TotalDurationNs"]) for r in rows) / max(calls, 1) / 1e3, 1), calls
 
@@ -149,11 +175,86 @@ def child(index, rounds):
     print(json.dumps(result))
 
 
-def table(shapes):
+def child_dorefa(index, rounds):
+    import torch
+    import torch.nn as nn
+    from pytorch_quantize_impls_amd import _lib, lazy
+    from pytorch_quantize_impls_amd.functions import nnDorefaQuant
+    from pytorch_quantize_impls_amd.layers import DorefaConv2d
+
+    C, H, stride, G, k = SHAPES[index]
+    dev = torch.device("cuda:0")
+    torch.manual_seed(index)
+    g = torch.Generator().manual_seed(index)
+
+    def run(c, fan):
+        # statistics sized for a sum of ``fan`` products of +-E and a 4-bit image: the codes stay far inside int8
+        bn = nn.BatchNorm2d(c)
+        bn.running_mean.copy_(torch.randn(c, generator=g) * 0.1)
+        bn.running_var.copy_((torch.rand(c, generator=g) + 0.5) * fan * 0.05)
+        gamma = torch.rand(c, generator=g) * 0.5 + 0.25
+        gamma[::3] *= -1
+        bn.weight.data.copy_(gamma)
+        bn.bias.data.copy_(torch.randn(c, generator=g) * 0.2 + 0.3)
+        return [bn, nn.ReLU(), nnDorefaQuant(4)]
+
+    triple = nn.Sequential(DorefaConv2d(C, C, 1, bit_width=1), *run(C, C),
+                           DorefaConv2d(C, C, k, stride=stride, padding=k // 2, groups=G, bit_width=1), *run(C, C // G * k * k),
+                           DorefaConv2d(C, C, 1, bit_width=1), *run(C, C))
+    triple = triple.to(dev).to(memory_format=torch.channels_last).eval()
+    with torch.no_grad():
+        x = nnDorefaQuant(4)(torch.rand(BATCH, C, H, H, generator=g).to(dev).contiguous(memory_format=torch.channels_last))
+
+    def forward(on):
+        with torch.no_grad(), lazy.grouped_deferred(on):
+            out = triple(x)
+            act = out._qt.force((0, 0))        # the code plane the next DoReFa layer would ask for
+            assert act is not None
+            return act.codes
+
+    sides = {"deferred": lambda: forward(True), "eager": lambda: forward(False)}
+    calls = dict(_lib.call_counts)
+    a = sides["deferred"]()
+    used_on = {k_: v - calls.get(k_, 0) for k_, v in _lib.call_counts.items() if v != calls.get(k_, 0)}
+    calls = dict(_lib.call_counts)
+    b = sides["eager"]()
+    used_off = {k_: v - calls.get(k_, 0) for k_, v in _lib.call_counts.items() if v != calls.get(k_, 0)}
+    assert torch.equal(a.codes, b.codes), "the two sides disagree"
+    assert int(a.overflow.item()) == 0 and int(b.overflow.item()) == 0 and int(a.codes.count_nonzero()) > 0
+    assert used_on.get("qt_gconv2d_codes") == 1 and "qt_gconv2d_f32" not in used_on, used_on
+    assert used_off.get("qt_gconv2d_f32") == 1 and "qt_gconv2d_codes" not in used_off, used_off
+
+    def run_us(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(STEPS):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6 / STEPS
+
+    for fn in sides.values():
+        for _ in range(3):
+            fn()
+    samples = {s: [] for s in sides}
+    for _ in range(rounds):
+        for s, fn in sides.items():
+            samples[s].append(run_us(fn))
+    nbytes = algorithmic_bytes_dorefa(C, H, stride, k)
+    result = {"channels": C, "map": H, "stride": stride, "groups": G, "kernel": k, "bytes": nbytes,
+              "launches": {"deferred": used_on, "eager": used_off}}
+    for s, v in samples.items():
+        med = sorted(v)[len(v) // 2]
+        result[s] = {"median_us": round(med, 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1),
+                     "hbm_share": round(nbytes[s] / HBM_BYTES_PER_S / (med * 1e-6), 3)}
+    result["deferred_range_below_eager"] = result["deferred"]["max_us"] < result["eager"]["min_us"]
+    print(json.dumps(result))
+
+
+def table(shapes, kernel_name="grouped plane kernel"):
     own = all("kernel_us" in s for s in shapes)
     rows = ["| grouped channels x map, groups, kernel, stride | eager: median (range) us | deferred: median (range) us | "
             "eager MB, share of 8 TB/s | deferred MB, share of 8 TB/s | deferred range below eager |"
-            + (" grouped plane kernel alone, us |" if own else ""),
+            + (f" {kernel_name} alone, us |" if own else ""),
             "|---|---|---|---|---|---|" + ("---|" if own else "")]
     for s in shapes:
         e, d = s["eager"], s["deferred"]
@@ -180,25 +281,32 @@ def write_docs(text, mark=MARK):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grouped_chain_bench_line.json"))
+    ap.add_argument("--family", choices=sorted(FAMILIES), default="sign", help="sign: BinConv2d triple (default); dorefa: DorefaConv2d triple")
+    ap.add_argument("--out", default=None, help="default: profiles/grouped_chain_bench_line.json (sign), "
+                                                "profiles/grouped_codes_chain_bench_line.json (dorefa)")
     ap.add_argument("--kernel-times", action="store_true", help="one more rocprofv3 --kernel-trace --stats pass per shape")
     ap.add_argument("--docs", action="store_true", help="rewrite the table in README.md and DESIGN.md")
     ap.add_argument("--from-json", default=None, help="take the shapes from a recorded line instead of measuring (with --docs)")
     ap.add_argument("--child", type=int, default=None)
     a = ap.parse_args()
+    fam = FAMILIES[a.family]
+    dorefa = a.family == "dorefa"
+    kernel_name = "grouped code kernel" if dorefa else "grouped plane kernel"
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", fam["out"])
     if a.child is not None:
-        return child(a.child, a.rounds)
+        return child_dorefa(a.child, a.rounds) if dorefa else child(a.child, a.rounds)
     if a.from_json:
         with open(a.from_json) as fh:
             line = json.loads(fh.read().strip().splitlines()[-1])
-        print(table(line["shapes"]))
+        print(table(line["shapes"], kernel_name))
         if a.docs:
-            write_docs(table(line["shapes"]))
+            write_docs(table(line["shapes"], kernel_name), fam["mark"])
         return
     shapes = []
     for i in range(len(SHAPES)):
         # a child per shape, each under its own limit; the first failure ends the run
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(i), "--rounds", str(a.rounds)],
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(i), "--rounds", str(a.rounds), "--family", a.family],
                            stdout=subprocess.PIPE, text=True, timeout=CHILD_LIMIT_S)
         if p.returncode != 0:
             raise SystemExit(f"shape {SHAPES[i]}: the measuring process ended with status {p.returncode}; nothing more was started")
@@ -208,20 +316,24 @@ def main():
         import tempfile
         with tempfile.TemporaryDirectory() as work:
             for i, s in enumerate(shapes):
-                s["kernel_us"], s["kernel_calls"] = kernel_time_us(i, work)
+                s["kernel_us"], s["kernel_calls"] = kernel_time_us(i, work, a.family)
     from pytorch_quantize_impls_amd import lazy
     line = {"bench": "grouped_chain_resnext", "batch": BATCH, "rounds": a.rounds, "steps": STEPS, "dtype": "float32 +-1 input",
             "layout": "NCHW", "hbm_bytes_per_s": HBM_BYTES_PER_S, "shapes": shapes,
             "deferred_below_eager_at_every_shape": all(s["deferred_range_below_eager"] for s in shapes),
             "defer_grouped_shipped": bool(lazy.DEFER_GROUPED)}
+    if dorefa:
+        line.update({"bench": "grouped_codes_chain_resnext", "dtype": "float32 image of 4-bit codes, code-tagged", "layout": "channels_last"})
+        del line["defer_grouped_shipped"]
+        line["defer_grouped_codes_shipped"] = bool(lazy.DEFER_GROUPED_CODES)
     text = json.dumps(line)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh:
         fh.write(text + "\n")
     print(text)
-    print(table(shapes))
+    print(table(shapes, kernel_name))
     if a.docs:
-        write_docs(table(shapes))
+        write_docs(table(shapes, kernel_name), fam["mark"])
 
 
 if __name__ == "__main__":
