@@ -1559,6 +1559,49 @@ int qt_gconv2d_codes_f32(const int8_t* x_plane, int64_t ldx_bytes, int64_t in_ha
                          int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                          int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, qt_stream_t stream);
 
+/* BatchNorm + shortcut + sign: the activation between two binarised convs of a residual block,
+ *   s = BatchNorm(conv) + shortcut;  next conv input = sign([Hardtanh](s));  next shortcut = s
+ * in ONE streaming pass over the fp32 conv result.  One launch; no allocation, no synchronisation, no atomics; capturable;
+ * csrc/resid_sign.hip, DESIGN.md "Residual blocks in the sign chain".
+ *
+ * x is the conv result as NHWC rows: fp32 [rows = N Ho Wo][ldx], ldx >= C, channel c of pixel row (n Ho + ho) Wo + wo at column c.
+ * Per element, every step ONE fp32 rounding and the multiply-add a fused one (nothing else is contracted):
+ *   t = fma(fl(fl(x - mean[c]) * rs[c]), weight[c], bias[c])        bn_stats = fp32 [mean | rs], 2 C values: the expression of
+ *                                                                   qt_bn_eval_device_f32;  weight, bias fp32 [C]
+ *   s = fl(t + r)
+ *   v = s < lo ? lo : (s > hi ? hi : s)  when hardtanh == 1 (torch's hardtanh: NaN stays NaN), v = s when hardtanh == 0
+ *   bit = [v < 0]                                                   plain IEEE compare: -0.0, a tie and NaN give 0
+ * r is the shortcut, fp32 [N, C, Ho, Wo] by its element strides rs_n, rs_c, rs_h, rs_w: dense NCHW (rs_w = 1, rs_h = Wo, rs_c = Ho Wo,
+ * rs_n = C Ho Wo) or channels-last with a row pitch (rs_c = 1, rs_w = P >= C, rs_h = Wo P, rs_n = Ho Wo P) — the `sum` of an earlier
+ * launch is such a tensor.  An NCHW shortcut is read with the lanes along the pixels through an LDS tile, never Ho Wo floats apart.
+ *
+ * Outputs, each may be null, not all three:
+ *   sum         fp32 [N, C, Ho, Wo] holding v, by its element strides ss_n, ss_c, ss_h, ss_w, in one of the two forms of r: NHWC rows
+ *               with a pitch lds = ss_w >= C — these may be x itself (same pointer AND lds == ldx: in place) — or dense NCHW, the
+ *               storage the module graph's own sum has behind an NCHW input (written with the lanes along the pixels through the
+ *               LDS tile, never Ho Wo floats apart).  Any overlap with x other than "in place" is refused.  Where both forms
+ *               describe the same memory (Ho Wo == 1) the strides are read as rows.
+ *   sign_plane  uint32 [rows][ldb], the sign plane of qt_dwconv2d_sign with its bound ldb >= ops.packed_ld(C): bit 1 <=> negative;
+ *               every bit and every word past C is written as zero.
+ *   nib_plane   uint32 [N (Ho + 2 out_halo_h) (Wo + 2 out_halo_w)][ldn], the nibble plane of qt_dwconv2d_sign / the operand of
+ *               qt_conv2d_implicit_nib: +1 = 0x2, -1 = 0xA, channels >= C and the border pixels zero words; ldn >=
+ *               ops.pixel_ld_nib(C), ldn % 4 == 0, 16-byte aligned.  The launch writes EVERY word of the plane.
+ * Any C >= 1.  x, a sum in rows and a channels-last r move as 16-byte vectors when C % 4 == 0, the pitches are multiples of 4 and the pointers
+ * 16-byte aligned; otherwise element by element (same values).
+ *
+ * Validation before anything is enqueued, in this order; a non-zero status means nothing was launched:
+ *   1. a negative size or halo: QT_ERR_INVALID_ARG.      2. N, C, Ho or Wo zero: QT_OK, nothing is written.
+ *   3. out_halo_* > 64, 2^31 or more pixel rows in the (haloed) plane: QT_ERR_UNSUPPORTED.
+ *   4. a null x, weight, bias, bn_stats or r; no output at all; hardtanh outside {0, 1}, or 1 with lo <= hi false (NaN included);
+ *      ldx < C; strides of r, or of a non-null sum, that are neither form above (a pitch below C included); ldb / ldn below their
+ *      bounds; a sum that overlaps x without being x in place: QT_ERR_INVALID_ARG.
+ *   5. a pointer that is not 4-byte aligned, ldn % 4 != 0 or a nib_plane that is not 16-byte aligned: QT_ERR_ALIGNMENT. */
+int qt_bn_add_sign_f32(const float* x, int64_t ldx, const float* weight, const float* bias, const float* bn_stats, const float* r,
+                       int64_t rs_n, int64_t rs_c, int64_t rs_h, int64_t rs_w, int hardtanh, float lo, float hi, float* sum,
+                       int64_t ss_n, int64_t ss_c, int64_t ss_h, int64_t ss_w, uint32_t* sign_plane, int64_t ldb, uint32_t* nib_plane,
+                       int64_t ldn, int64_t out_halo_h, int64_t out_halo_w, int64_t N, int64_t C, int64_t Ho, int64_t Wo,
+                       qt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

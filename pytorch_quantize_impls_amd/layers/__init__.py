@@ -9,5 +9,5 @@ from .elastic_layers import LinearQuantLin, LinearQuantLog, QuantConv2dLin, Quan
 from .WQR_layers import LinearQuantWLin, LinearQuantWLog, QuantConv2dWLin, QuantConv2dWLog
 from .common import QLayer
 from .fused import (FusedTrainPoolBnSign, FusedTrainBnActQuant, fuse_sequential_training, CodeMaxPool, FusedBnDorefaQuant, FusedDorefaConvBnQuant, FusedPoolBnSign, FusedConvPoolBnSign, FusedFeatureClassifier, PackedMaxPool, fuse_sequential, fold_batchnorm,
-                    permute_fc_weight_hwc, FusedLogLinConvBnQuant, LevelMaxPool, FusedBnLogLinQuant, FusedDepthwiseBnSign, FusedGroupedBnSign,
+                    permute_fc_weight_hwc, FusedLogLinConvBnQuant, LevelMaxPool, FusedBnLogLinQuant, FusedDepthwiseBnSign, FusedGroupedBnSign, FusedConvBnAddSign,
                     FusedDepthwiseDorefaBnQuant, FusedGroupedDorefaBnQuant)

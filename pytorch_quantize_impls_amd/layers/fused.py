@@ -1045,6 +1045,107 @@ class FusedGroupedBnSign(torch.nn.Module):
         return act.flatten_hwc() if self.flatten_hwc else act
 
 
+class FusedConvBnAddSign(torch.nn.Module):
+    """The residual block of a binarised ResNet (Bi-Real-Net style), eval only:
+
+        s = BatchNorm2d(conv(x)) + residual;   next conv's input = BinaryConnect(det)([Hardtanh](s));   next shortcut = [Hardtanh](s)
+
+    ``forward(x, residual) -> (PackedActivation, sum)``.  The conv — BinConv2d / TerConv2d, deterministic; ``groups == 1``, or the
+    depthwise / grouped layers the sign chain takes — computes exactly the fp32 value its eval path yields for ``x`` (a
+    PackedActivation or a device fp32 tensor: ``conv._forward_impl``).  ONE streaming launch (ops.bn_add_sign, qt_bn_add_sign_f32)
+    then turns that buffer, in place, into the sum and writes the bits: BatchNorm in this device's own arithmetic
+    (``device_bn_fold``, verified on a probe; a mismatch is a ValueError), one fp32 add, Hardtanh, sign.  A conv result in NCHW
+    storage (an NCHW fp32 input; the depthwise and grouped convs on planes) is first copied to NHWC rows.  Where the module graph
+    works in NCHW storage — an NCHW-contiguous fp32 input, or a PackedActivation whose ``source_channels_last`` is False, which this
+    block sets on its own output — the sum is written as an NCHW-contiguous tensor by the same launch instead of in place: what the
+    caller does with it (a real-valued ``nn.Conv2d`` shortcut branch, a pooling head) then sees the operand layout, and so the
+    library kernels and roundings, of the module graph.  The thresholds of
+    ``device_sign_fold`` cannot express this block: the sign of bn(acc) + r depends on a per-element real r.
+
+    ``sum`` is the fp32 [N, C, Ho, Wo] tensor the module graph's ``+`` returns (after the Hardtanh when one is given, as
+    ``nn.Hardtanh`` between the add and the sign leaves it): a channels-last view of the conv's buffer, or the NCHW tensor above.  ``out_nib_halo`` as on
+    ``FusedConvPoolBnSign``: (ph, pw) of the conv that consumes the activation — the launch then writes that conv's nibble operand
+    with the padding as a zero border instead of bit planes.  ``fold`` is accepted for symmetry; the arithmetic is always the
+    device's ("device")."""
+
+    def __init__(self, conv, bn, hardtanh=None, fold=None):
+        super().__init__()
+        from .binary_layers import BinConv2d
+        from .terner_layers import TerConv2d
+        if not isinstance(conv, (BinConv2d, TerConv2d)):
+            raise ValueError("FusedConvBnAddSign fuses BinConv2d / TerConv2d only (XNOR, Lin / Log and DoReFa convs have other chains)")
+        if not conv.deterministic:
+            raise ValueError("FusedConvBnAddSign takes the deterministic quantiser only")
+        if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+            raise ValueError("only zero-padded convs with numeric padding can be fused")
+        if isinstance(bn, (torch.nn.MaxPool2d, torch.nn.AvgPool2d)):
+            raise ValueError("a pool in front of the BatchNorm cannot be fused into a residual block")
+        if not isinstance(bn, torch.nn.BatchNorm2d) or bn.num_features != conv.out_channels:
+            raise ValueError("BatchNorm2d over the conv's output channels expected")
+        if conv.weight.dtype != torch.float32 or (bn.running_mean is not None and bn.running_mean.dtype != torch.float32):
+            raise ValueError("FusedConvBnAddSign is an fp32 form (half dtypes keep the module graph)")
+        if bn.running_mean is None or bn.running_var is None:
+            raise ValueError("a BatchNorm2d that tracks running statistics expected")
+        if fold not in (None, "device"):
+            raise ValueError("FusedConvBnAddSign evaluates BatchNorm in the device's arithmetic: fold must be None or 'device'")
+        if hardtanh is not None:
+            if isinstance(hardtanh, torch.nn.Hardtanh):
+                hardtanh = (float(hardtanh.min_val), float(hardtanh.max_val))
+            hardtanh = (float(hardtanh[0]), float(hardtanh[1]))
+            if not hardtanh[0] < 0.0 < hardtanh[1]:
+                raise ValueError("Hardtanh(min_val < 0 < max_val) expected")
+        self.conv, self.bn, self.hardtanh = conv, bn, hardtanh
+        self.fold = "device"
+        self.out_nib_halo = None        # see FusedConvPoolBnSign.out_nib_halo
+        self._folded = None
+
+    def refold(self):
+        self._folded = None
+
+    def forward(self, x, residual):
+        conv = self.conv
+        if self.bn.training or conv.training:
+            raise RuntimeError("FusedConvBnAddSign is an inference module: call .eval() first")
+        x, residual = lazy.resolve(x), lazy.resolve(residual)
+        if isinstance(x, packed.PackedActivation):
+            if len(x.shape) != 4:
+                raise ValueError("a flattened activation cannot enter a residual block")
+            cl = bool(getattr(x, "source_channels_last", True))          # the storage the module graph works in
+        else:
+            if not (isinstance(x, torch.Tensor) and x.is_cuda):
+                raise TypeError("FusedConvBnAddSign runs on a HIP device only (use the un-fused modules on CPU)")
+            if x.dtype != torch.float32 or x.dim() != 4:
+                raise ValueError("FusedConvBnAddSign takes 4-D fp32 inputs (half dtypes keep the module graph)")
+            cl = _out_channels_last(x)
+        if not conv._eval_on_grid():
+            raise ValueError("the eval-mode weight is off the quantiser's grid")
+        if not (isinstance(residual, torch.Tensor) and residual.is_cuda and residual.dtype == torch.float32 and residual.dim() == 4):
+            raise ValueError("residual: a 4-D fp32 device tensor expected")
+        with torch.no_grad():
+            y = conv._forward_impl(x)
+            if y.dtype != torch.float32 or y.dim() != 4:
+                raise ValueError("the conv did not yield an fp32 activation")
+            N, C, Ho, Wo = (int(v) for v in y.shape)
+            if tuple(residual.shape) != (N, C, Ho, Wo):
+                raise ValueError(f"residual {tuple(residual.shape)} does not cover this conv's output {(N, C, Ho, Wo)}")
+            w, b, stats = _code_fold_for(self, "_folded", self.bn, "device", ((N, C, Ho, Wo), cl))
+            rows = y.permute(0, 2, 3, 1)
+            if not rows.is_contiguous():
+                rows = rows.contiguous()
+            x2 = rows.view(N * Ho * Wo, C)
+            nib_out = self.out_nib_halo is not None
+            s2, bits, nib = ops.bn_add_sign(x2, (N, C, Ho, Wo), w, b, stats, residual.detach(), hardtanh=self.hardtanh,
+                                            sum_out="inplace" if cl else "nchw", want_sign=not nib_out,
+                                            out_halo=self.out_nib_halo if nib_out else None)
+            total = s2.view(N, Ho, Wo, C).permute(0, 3, 1, 2) if cl else s2
+        if nib_out:
+            act = packed.PackedActivation(None, (N, C, Ho, Wo), nib=nib, halo=tuple(self.out_nib_halo))
+        else:
+            act = packed.PackedActivation(bits, (N, C, Ho, Wo))
+        act.source_channels_last = cl
+        return act, total
+
+
 #: real-valued 3x3 / stride-1 / padding-1 first layers of fused stacks run in the 2x2 output-blocked form
 D2S_FIRST_LAYER = True
 #: real-valued 3x3 / stride-1 / padding-1 first layers with <= 5 channels run on the direct kernel (bf16 triple planes);

@@ -61,6 +61,16 @@ no residual (an ``add`` behind its BatchNorm materialises); a deferred grouped c
 fp32 value from the codes (``_fused.codes_grouped_conv2d``).  Two or three groups and more than ``GROUPED_MAX_CIN_G`` channels per
 group keep their module-by-module path.
 
+Residual blocks of binarised ResNets (Bi-Real-Net style: ``s = bn(conv(sign(x))) + shortcut``, next conv input ``sign([Hardtanh](s))``,
+next shortcut ``s``) stay in the sign chain (``DEFER_RESIDUAL_SIGN``, on by default; ``residual_deferred(False)`` switches it off): ``+`` / ``+=`` on
+a recorded BinConv2d / TerConv2d -> BatchNorm2d chain is RECORDED with its other operand — an fp32 device tensor, or another deferred
+sign-kind activation — and the chain runs as ``layers.fused.FusedConvBnAddSign``: the conv to fp32, then ONE pass (qt_bn_add_sign_f32)
+that evaluates BatchNorm in this device's own arithmetic (verified on a probe, as for the DoReFa chains), adds the shortcut, applies
+the Hardtanh and writes the next conv's operand AND the fp32 sum.  The sum becomes the value of the activation the sign was applied to:
+when the next block says ``bn(conv(sign(s))) + s`` it is already there, nothing materialises and no conv runs twice.  False = ``+`` on
+a sign chain returns NotImplemented as without this mechanism and the chain materialises (DESIGN.md "Residual blocks in the sign
+chain" has the grammar, the exactness argument and what was measured).
+
 Nothing is deferred in training mode, with autograd enabled, on CPU tensors, for non-fp32 dtypes, grouped convs other than
 those depthwise and few-channel ones or non-zero padding modes.  ``lazy.ENABLED = False`` (or the ``eager()`` context manager) switches the mechanism off;
 ``lazy.STATS`` counts what happened (tests assert on it).
@@ -127,6 +137,12 @@ DEFER_GROUPED = True
 #: call runs exactly as without this mechanism: the grouped layer computes fp32 from the expanded image and the chain in front of
 #: it materialises (``grouped_deferred()`` switches it for a block).
 DEFER_GROUPED_CODES = True
+#: ``bn(conv(...)) + shortcut`` on a BinConv2d / TerConv2d chain (the residual block of a binarised ResNet) is recorded and runs as
+#: ``layers.fused.FusedConvBnAddSign``: conv to fp32, then one launch (qt_bn_add_sign_f32) for BatchNorm (device arithmetic, verified on
+#: a probe) + shortcut + [Hardtanh] + sign that writes the next conv's operand and the fp32 sum — the next block's shortcut (DESIGN.md
+#: "Residual blocks in the sign chain" says what was measured and why the default is what it is).  False = every call runs exactly as
+#: without this mechanism: the add returns NotImplemented and the chain materialises (``residual_deferred()`` switches it for a block).
+DEFER_RESIDUAL_SIGN = True
 #: "deferred" convs that returned a LazyActivation, "fused" chains executed as fused blocks, "materialised" lazies that
 #: had to produce their fp32 value, "fallback:<func>" the functions that forced it
 STATS = collections.Counter()
@@ -215,6 +231,18 @@ def grouped_deferred(on: bool = True):
         yield
     finally:
         DEFER_GROUPED, DEFER_GROUPED_CODES = prev, prev_codes
+
+
+@contextlib.contextmanager
+def residual_deferred(on: bool = True):
+    """Keep residual blocks of the sign chain deferred (``DEFER_RESIDUAL_SIGN``) inside the block; process-wide, restores the previous
+    setting."""
+    global DEFER_RESIDUAL_SIGN
+    prev, DEFER_RESIDUAL_SIGN = DEFER_RESIDUAL_SIGN, bool(on)
+    try:
+        yield
+    finally:
+        DEFER_RESIDUAL_SIGN = prev
 
 
 class _Node:
@@ -353,6 +381,8 @@ class _Node:
             return self._force_ldense()
         if not self.signed or self.bn is None:
             return None
+        if self.add is not None:
+            return self._force_residual(halo)
         if self.flat:
             halo = None
         key = halo
@@ -374,8 +404,60 @@ class _Node:
             act = None
         if act is not None:
             STATS["fused"] += 1
+            act.source_channels_last = _graph_channels_last(self.input)
         self.packed_cache[key] = act
         return act
+
+
+def _graph_channels_last(x) -> bool:
+    """The storage the module-by-module graph works in behind the chain input ``x``: NCHW (False) behind an NCHW-contiguous tensor."""
+    if isinstance(x, packed.PackedActivation):
+        return bool(getattr(x, "source_channels_last", True))
+    return not (x.is_contiguous() and not x.is_contiguous(memory_format=torch.channels_last))
+
+
+def _force_residual(self, halo=None):
+    """PackedActivation of a signed chain with a recorded ``+ shortcut`` (conv -> BatchNorm -> add -> [Hardtanh] -> sign -> [MaxPool]):
+    layers.fused.FusedConvBnAddSign on the resolved shortcut.  The fp32 sum the launch emits becomes the value of the node the sign was
+    applied to — the activation the caller still holds and may use as the next shortcut.  None when the chain cannot run fused; also
+    when that sum already exists (another operand form was produced before, or the caller read it): the sign is then taken from the
+    stored sum by the ordinary replay and no conv runs a second time."""
+    if self.flat or self.pool is not None:
+        return None
+    key = halo
+    if self.packed_cache is None:
+        self.packed_cache = {}
+    if key in self.packed_cache:
+        return self.packed_cache[key]
+    signed = self
+    while signed.op[0] != "sign":
+        signed = signed.parent
+    target = signed.parent
+    root = target
+    while root.parent is not None:
+        root = root.parent
+    act = None
+    if target.value is None and root.value is None:
+        self.check_unmodified()
+        try:
+            with torch.no_grad():
+                blk = _residual_block(self.layer, self.bn, self.hardtanh, halo if self.pool2 is None else None)
+                act, total = blk(self.input, resolve(self.add))
+                target.value = total
+                if self.pool2 is not None:
+                    cl = act.source_channels_last
+                    act = _packed_pool(self.pool2, halo)(act)
+                    act.source_channels_last = cl
+        except ValueError:
+            act = None
+    if act is not None:
+        STATS["fused"] += 1
+        STATS["residual_sign_fused"] += 1
+    self.packed_cache[key] = act
+    return act
+
+
+_Node._force_residual = _force_residual
 
 
 def _stamp(*tensors):
@@ -583,6 +665,25 @@ def _fused_block(layer, bn, pool, flatten: bool, halo):
         make = (fused.FusedConvPoolBnSign if layer.groups == 1 else
                 fused.FusedDepthwiseBnSign if layer.groups == layer.in_channels else fused.FusedGroupedBnSign)
         blk = make(layer, _BnView(rm, rv, w, b, eps), pm, flatten_hwc=flatten, fold="device")
+        blk.out_nib_halo = halo
+        per[key] = blk
+        while len(per) > _MAX_BLOCKS_PER_LAYER:
+            per.popitem(last=False)
+    else:
+        per.move_to_end(key)
+    return blk
+
+
+def _residual_block(layer, bn, hardtanh, halo):
+    from .layers import fused
+    rm, rv, w, b, eps = bn
+    key = (id(rm), id(rv), id(w), id(b), eps, "residual", hardtanh, halo)
+    per = _BLOCKS.get(layer)
+    if per is None:
+        per = _BLOCKS[layer] = collections.OrderedDict()
+    blk = per.get(key)
+    if blk is None:
+        blk = fused.FusedConvBnAddSign(layer, _BnView(rm, rv, w, b, eps), hardtanh=hardtanh, fold="device")
         blk.out_nib_halo = halo
         per[key] = blk
         while len(per) > _MAX_BLOCKS_PER_LAYER:
@@ -982,14 +1083,41 @@ def _mainline(n: _Node) -> bool:
             and len(n.shape) == 4)
 
 
+_SIGN_KINDS = ("binary", "ternary")
+
+
+def _sign_mainline(n: _Node) -> bool:
+    """Exactly conv -> BatchNorm2d of a sign-kind chain, nothing else recorded, nothing computed yet (DEFER_RESIDUAL_SIGN)."""
+    return (DEFER_RESIDUAL_SIGN and n.kind in _SIGN_KINDS and n.parent is not None and n.parent.parent is None and n.op[0] == "bn"
+            and n.add is None and n.hardtanh is None and not n.signed and not n.flat and n.pool is None and n.pool2 is None
+            and len(n.shape) == 4 and n.value is None and n.parent.value is None)
+
+
+def _sign_residual_ok(main: _Node, other) -> bool:
+    if isinstance(other, LazyActivation):
+        o = other._qt
+        return o.kind in _SIGN_KINDS and o.shape == main.shape and not o.signed and not o.flat
+    return (type(other) is torch.Tensor and other.device == main.device and other.dtype == torch.float32
+            and tuple(other.shape) == main.shape and not other.requires_grad and not other.is_inference()
+            and (other.is_contiguous() or other.is_contiguous(memory_format=torch.channels_last)))
+
+
+def _add_candidate(x, other) -> bool:
+    if not isinstance(x, LazyActivation):
+        return False
+    n = x._qt
+    return (_mainline(n) and _residual_ok(n, other)) or (_sign_mainline(n) and _sign_residual_ok(n, other))
+
+
 def _h_add(a, b, *, alpha=1, out=None, _inplace=False):
-    """bn(conv(x)) + shortcut: the residual add of a DoReFa ResNet block, folded into the conv's code epilogue."""
+    """bn(conv(x)) + shortcut: the residual add of a DoReFa ResNet block, folded into the conv's code epilogue; of a binarised
+    ResNet block (DEFER_RESIDUAL_SIGN), recorded for the one pass behind the conv (layers.fused.FusedConvBnAddSign)."""
     if alpha != 1 or out is not None:
         return NotImplemented
     cands = []
-    if isinstance(a, LazyActivation) and _mainline(a._qt) and _residual_ok(a._qt, b):
+    if _add_candidate(a, b):
         cands.append((a, b))
-    if not _inplace and isinstance(b, LazyActivation) and _mainline(b._qt) and _residual_ok(b._qt, a):
+    if not _inplace and _add_candidate(b, a):
         cands.append((b, a))
     if not cands:
         return NotImplemented

@@ -4776,3 +4776,89 @@ def grouped_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, weigh
                   *_dw_strides(go.shape, _dw_channels_last(go)), *_dw_strides(x.shape, _dw_channels_last(x)), float(ste_threshold),
                   _stream(x.device))
     return gw, gb
+
+
+# ---- residual blocks of the sign chain ---------------------------------------------------------------------------------------------
+
+def _residual_strides(r: torch.Tensor, shape):
+    """``r`` (or a dense copy of it) and the element strides (n, c, h, w) qt_bn_add_sign_f32 takes for it: dense NCHW, or
+    channels-last with a row pitch of at least C floats (torch leaves the strides of size-1 dimensions arbitrary, so the canonical
+    ones are passed for the two dense forms)."""
+    N, C, H, W = shape
+    if r.is_contiguous():
+        return r, (C * H * W, H * W, W, 1)
+    if r.is_contiguous(memory_format=torch.channels_last):
+        return r, (H * W * C, 1, W * C, C)
+    sn, sc, sh, sw = (int(v) for v in r.stride())
+    if sc == 1 and sw >= C and sh == W * sw and sn == H * sh and C > 1 and W > 1 and H > 1 and N > 1:
+        return r, (sn, 1, sh, sw)
+    return r.contiguous(), (C * H * W, H * W, W, 1)
+
+
+def bn_add_sign(x2: torch.Tensor, shape, weight: torch.Tensor, bias: torch.Tensor, bn_stats: torch.Tensor, residual: torch.Tensor,
+                hardtanh=None, sum_out="inplace", want_sign: bool = True, out_halo=None):
+    """The activation between two binarised convs of a residual block in one pass (qt_bn_add_sign_f32):
+
+        s = fma(fl(fl(x - mean) * rs), weight, bias) + residual;   v = hardtanh(s) or s;   bit = [v < 0]
+
+    ``x2``: the conv result as fp32 NHWC rows [N*Ho*Wo, >= C] with unit channel stride, logical ``shape`` (N, C, Ho, Wo);
+    ``weight`` / ``bias`` / ``bn_stats`` = [mean | rs]: layers.fused.device_bn_fold; ``residual``: fp32 [N, C, Ho, Wo], dense NCHW or
+    channels-last (anything else is copied); ``hardtanh``: None or (lo, hi).  ``sum_out``: "inplace" (v overwrites x2), "new" (a fresh
+    [rows, C] matrix), "nchw" (a fresh NCHW-contiguous [N, C, Ho, Wo] tensor: the storage the module graph's sum has behind an NCHW
+    input), None (not written) or an fp32 [rows, C] matrix.  Returns ``(sum or None, BitPlanes or None, NibPlanes or None)``: the sign plane when ``want_sign``, the consumer's nibble operand with a zero border of ``out_halo`` pixels when that is
+    given; at least one of the three must be asked for."""
+    _require(x2, "input")
+    N, C, Ho, Wo = (int(v) for v in shape)
+    rows, dev = N * Ho * Wo, x2.device
+    if x2.dim() != 2 or int(x2.shape[0]) != rows or int(x2.shape[1]) != C or (C > 1 and x2.stride(1) != 1):
+        raise ValueError(f"input: expected the fp32 NHWC rows [{rows}, {C}] of a {tuple(shape)} conv result, got {tuple(x2.shape)}")
+    ldx = int(x2.stride(0)) if rows > 1 else max(C, 1)
+    for name, t, n in (("weight", weight, C), ("bias", bias, C), ("bn_stats", bn_stats, 2 * C)):
+        _require(t, name)
+        if t.dim() != 1 or int(t.numel()) != n or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name}: expected a contiguous fp32 vector of {n} values on {dev}")
+    _require(residual, "residual")
+    if tuple(residual.shape) != (N, C, Ho, Wo) or residual.device != dev:
+        raise ValueError(f"residual: expected an fp32 tensor {(N, C, Ho, Wo)} on {dev}, got {tuple(residual.shape)} on {residual.device}")
+    residual, rs = _residual_strides(residual, (N, C, Ho, Wo))
+    if hardtanh is None:
+        ht, lo, hi = 0, 0.0, 0.0
+    else:
+        ht, lo, hi = 1, float(hardtanh[0]), float(hardtanh[1])
+        if not lo <= hi:
+            raise ValueError("hardtanh: min_val must not exceed max_val")
+    if isinstance(sum_out, str):
+        if sum_out not in ("inplace", "new", "nchw"):
+            raise ValueError("sum_out: 'inplace', 'new', 'nchw', None or an fp32 matrix")
+        s2 = (x2 if sum_out == "inplace" else torch.empty((rows, C), dtype=torch.float32, device=dev) if sum_out == "new"
+              else torch.empty((N, C, Ho, Wo), dtype=torch.float32, device=dev))
+    else:
+        s2 = sum_out
+        if s2 is not None:
+            _require(s2, "sum_out")
+            if s2.dim() != 2 or tuple(s2.shape) != (rows, C) or (C > 1 and s2.stride(1) != 1) or s2.device != dev:
+                raise ValueError(f"sum_out: expected fp32 rows [{rows}, {C}] with unit channel stride on {dev}")
+    if s2 is None:
+        ss = (0, 0, 0, 0)
+    elif s2.dim() == 4:
+        ss = (C * Ho * Wo, Ho * Wo, Wo, 1)
+    else:
+        lds = int(s2.stride(0)) if rows > 1 else max(C, 1)
+        ss = (Ho * Wo * lds, 1, Wo * lds, lds)
+    hy, hx = (0, 0) if out_halo is None else (int(v) for v in _pairs(out_halo))
+    if hy < 0 or hx < 0:
+        raise ValueError("out_halo must not be negative")
+    if s2 is None and not want_sign and out_halo is None:
+        raise ValueError("bn_add_sign: nothing to write (no sum, no sign plane, no nibble plane)")
+    bits = nib = None
+    if want_sign:
+        bits = BitPlanes(sign=torch.empty((rows, packed_ld(C)), dtype=torch.int32, device=dev), rows=rows, K=C)
+    if out_halo is not None:
+        prow = N * (Ho + 2 * hy) * (Wo + 2 * hx)
+        nib = NibPlanes(words=torch.empty((prow, pixel_ld_nib(C)), dtype=torch.int32, device=dev), rows=prow, K=C)
+    if rows * C > 0:
+        with _on(dev):
+            _lib.call("qt_bn_add_sign_f32", _p(x2), ldx, _p(weight), _p(bias), _p(bn_stats), _p(residual), *rs, ht, lo, hi, _p(s2), *ss,
+                      _p(bits.sign) if bits is not None else None, bits.ld if bits is not None else 0,
+                      _p(nib.words) if nib is not None else None, nib.ld if nib is not None else 0, hy, hx, N, C, Ho, Wo, _stream(dev))
+    return s2, bits, nib

@@ -100,6 +100,9 @@ class PackedActivation:
         self.halo = tuple(int(v) for v in halo)
         self.shape = tuple(int(v) for v in shape)
         self.hwc = None               # (C, H, W) when the rows are a feature map flattened in (h, w, c) order (flatten_hwc)
+        # the storage the module-by-module graph works in at this point (False: NCHW): a producer that also hands out an fp32
+        # tensor (layers.fused.FusedConvBnAddSign's sum) gives it that storage
+        self.source_channels_last = True
 
     @property
     def device(self):
