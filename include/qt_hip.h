@@ -1378,6 +1378,62 @@ int qt_gconv2d_grad_weight_f32(const float* go, const float* x, const float* w, 
                                int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w,
                                float ste_threshold, qt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Depthwise and grouped convolution on half-precision operands: the six entries above for bf16 / fp16 models
+ * (model.bfloat16(), model.half(), fp32 models under torch.autocast), named by the "_h" convention of "Half-precision operands".
+ *
+ * Operands.  The activation-side tensors (x, y, go, gx) are 2-byte elements of ONE type, `dtype` = QT_DTYPE_BF16 | QT_DTYPE_F16.
+ * The weight side (w, and gw / gbias of grad_weight) has its own `w_dtype`: `dtype`, or QT_DTYPE_F32 (an fp32 model under
+ * autocast).  bias stays an fp32 vector, the workspace stays fp32 and the *_work_floats queries above serve both forms.  Strides
+ * are in elements.  A pointer to 2-byte elements needs 2-byte alignment only (a view at an odd element offset is fine); fp32
+ * pointers (an fp32 w / gw / gbias, bias, work) need 4.  Shapes, layouts, `kind`, ste_threshold and the limits are those of the
+ * "_f32" entries.
+ *
+ * Pinned arithmetic — this is the whole contract:
+ *   accumulation : every element is upcast EXACTLY to fp32; the kernels are the "_f32" kernels instantiated on the element type,
+ *                  so the fp32 operations, their order and the thread maps are those stated above (nothing contracted).
+ *   rounding     : the fp32 result is rounded ONCE, to nearest even, into the output element type: the sum plus bias for y, the
+ *                  gathered sum for gx, the combined splits after the STE mask for gw / gbias (type `w_dtype`).
+ *   consequence  : a "_h" result is, bit for bit, RNE(the "_f32" result on the upcast operands); the float32 CPU restatement of
+ *                  the "_f32" entry followed by one rounding is the reference.  With w_dtype == QT_DTYPE_F32 the gw / gbias bits
+ *                  are those of the "_f32" entry on the upcast activations.
+ *   specials     : NaN stays NaN (some quiet pattern), inf stays inf, overflow rounds to inf; fp16 subnormal inputs are not
+ *                  flushed and fp16 subnormal results are rounded gradually (so are the fp32 subnormals a bf16 result comes from).
+ *   quantiser    : `kind` is applied to the exact upcast of a half tap, which gives the classes of the bit-pattern rule of
+ *                  "Half-precision operands" (safeSign: -0.0, NaN -> +1, a negative subnormal -> -1; ternary: 0.5 is exact).
+ *   STE mask     : |float(w)| > ste_threshold, compared in fp32.
+ *
+ * Validation: an unknown `dtype`, or a `w_dtype` that is neither `dtype` nor QT_DTYPE_F32: QT_ERR_INVALID_ARG, before anything
+ * else; then the order of the "_f32" entries with the alignment rule above.  A non-zero status means nothing was launched.
+ * ---------------------------------------------------------------------------------------- */
+int qt_dwconv2d_h(const void* x, int dtype, const void* w, int w_dtype, const float* bias, void* y, int64_t N, int64_t C,
+                  int64_t m, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t xs_n,
+                  int64_t xs_c, int64_t xs_h, int64_t xs_w, int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, int kind,
+                  qt_stream_t stream);
+int qt_dwconv2d_grad_input_h(const void* go, int dtype, const void* w, int w_dtype, void* gx, int64_t N, int64_t C, int64_t m,
+                             int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n,
+                             int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w,
+                             int kind, qt_stream_t stream);
+/* go and x share `dtype`; w, gw and gbias share `w_dtype` */
+int qt_dwconv2d_grad_weight_h(const void* go, const void* x, int dtype, const void* w, void* gw, void* gbias, int w_dtype,
+                              float* work, int64_t work_floats, int64_t N, int64_t C, int64_t m, int64_t H, int64_t W, int kh,
+                              int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n, int64_t gs_c, int64_t gs_h,
+                              int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, float ste_threshold,
+                              qt_stream_t stream);
+int qt_gconv2d_h(const void* x, int dtype, const void* w, int w_dtype, const float* bias, void* y, int64_t N, int64_t G,
+                 int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                 int dw, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, int64_t ys_n, int64_t ys_c, int64_t ys_h,
+                 int64_t ys_w, int kind, qt_stream_t stream);
+int qt_gconv2d_grad_input_h(const void* go, int dtype, const void* w, int w_dtype, void* gx, int64_t N, int64_t G, int64_t cin_g,
+                            int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                            int64_t gs_n, int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h,
+                            int64_t xs_w, int kind, qt_stream_t stream);
+int qt_gconv2d_grad_weight_h(const void* go, const void* x, int dtype, const void* w, void* gw, void* gbias, int w_dtype,
+                             float* work, int64_t work_floats, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H,
+                             int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n,
+                             int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w,
+                             float ste_threshold, qt_stream_t stream);
+
 /* Depthwise convolution on bit planes: the forward above inside the fused inference chain conv -> BatchNorm -> Hardtanh ->
  * BinaryConnect -> next conv, reading and / or writing the planes a PackedActivation carries instead of fp32 tensors.  One
  * launch each; no allocation, no synchronisation.

@@ -37,9 +37,10 @@ struct DwTaps {
     __device__ __forceinline__ static int kk(const DwGeom& g) { return GEN ? g.kh * g.kw : KH * KW; }
 };
 
-template <int KH, int KW>
-__global__ __launch_bounds__(DW_THREADS) void dw_forward_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                                const float* __restrict__ bias, float* __restrict__ y, DwGeom g,
+// XT: element type of x and y, WT: of w (dw_map.h: float, DwBf16, DwF16); the accumulator and the bias are fp32 for all of them
+template <int KH, int KW, typename XT = float, typename WT = float>
+__global__ __launch_bounds__(DW_THREADS) void dw_forward_kernel(const XT* __restrict__ x, const WT* __restrict__ w,
+                                                                const float* __restrict__ bias, XT* __restrict__ y, DwGeom g,
                                                                 DwStrides xs, DwStrides ys, DwMap mp, int kind) {
     using T = DwTaps<KH, KW>;
     const int tid = threadIdx.x;
@@ -50,13 +51,13 @@ __global__ __launch_bounds__(DW_THREADS) void dw_forward_kernel(const float* __r
     const int kw = T::kw(g), kk = T::kk(g);
     float wq[T::CAP];
 #pragma unroll
-    for (int t = 0; t < T::CAP; ++t) wq[t] = t < kk ? dw_quant(kind, w[co * kk + t]) : 0.0f;
+    for (int t = 0; t < T::CAP; ++t) wq[t] = t < kk ? dw_quant(kind, dw_ld(w[co * kk + t])) : 0.0f;
     const float b = bias ? bias[co] : 0.0f;
     const int64_t c = co / g.m;
     for (int u = split; u < mp.units; u += mp.splits) {
         int n, ho, wo;
         if (!dw_pos(mp, u, tid, n, ho, wo)) continue;
-        const float* xp = x + n * xs.n + c * xs.c;
+        const XT* xp = x + n * xs.n + c * xs.c;
         const int h0 = ho * g.sh - g.ph, w0 = wo * g.sw - g.pw;
         float acc = 0.0f;
 #pragma unroll
@@ -64,19 +65,19 @@ __global__ __launch_bounds__(DW_THREADS) void dw_forward_kernel(const float* __r
             if (!T::GEN || t < kk) {
                 const int i = t / kw, j = t - i * kw;
                 const int hi = h0 + i * g.dh, wi = w0 + j * g.dw;
-                if (hi >= 0 && hi < g.H && wi >= 0 && wi < g.W) acc = acc + xp[hi * xs.h + wi * xs.w] * wq[t];
+                if (hi >= 0 && hi < g.H && wi >= 0 && wi < g.W) acc = acc + dw_ld(xp[hi * xs.h + wi * xs.w]) * wq[t];
             }
         }
         if (bias) acc = acc + b;
-        y[n * ys.n + co * ys.c + ho * ys.h + wo * ys.w] = acc;
+        dw_st(&y[n * ys.n + co * ys.c + ho * ys.h + wo * ys.w], acc);
     }
 }
 
 // gather form: gx[n, c, h, w] = sum over j < m, taps (i, j') of go[n, c m + j, ho, wo] Q(w)[c m + j, i, j'] where
 // ho sh = h + ph - i dh and wo sw = w + pw - j' dw have a solution inside the output
-template <int KH, int KW>
-__global__ __launch_bounds__(DW_THREADS) void dw_grad_input_kernel(const float* __restrict__ go, const float* __restrict__ w,
-                                                                   float* __restrict__ gx, DwGeom g, DwStrides gs, DwStrides xs,
+template <int KH, int KW, typename XT = float, typename WT = float>
+__global__ __launch_bounds__(DW_THREADS) void dw_grad_input_kernel(const XT* __restrict__ go, const WT* __restrict__ w,
+                                                                   XT* __restrict__ gx, DwGeom g, DwStrides gs, DwStrides xs,
                                                                    DwMap mp, int kind) {
     using T = DwTaps<KH, KW>;
     const int tid = threadIdx.x;
@@ -88,15 +89,15 @@ __global__ __launch_bounds__(DW_THREADS) void dw_grad_input_kernel(const float* 
     const bool one = g.m == 1;            // the taps of the only output channel stay in registers
     float wq[T::CAP];
 #pragma unroll
-    for (int t = 0; t < T::CAP; ++t) wq[t] = (one && t < kk) ? dw_quant(kind, w[c * kk + t]) : 0.0f;
+    for (int t = 0; t < T::CAP; ++t) wq[t] = (one && t < kk) ? dw_quant(kind, dw_ld(w[c * kk + t])) : 0.0f;
     for (int u = split; u < mp.units; u += mp.splits) {
         int n, h, x0;
         if (!dw_pos(mp, u, tid, n, h, x0)) continue;
         float acc = 0.0f;
         for (int j = 0; j < g.m; ++j) {
             const int64_t co = c * g.m + j;
-            const float* gp = go + n * gs.n + co * gs.c;
-            const float* wp = w + co * kk;
+            const XT* gp = go + n * gs.n + co * gs.c;
+            const WT* wp = w + co * kk;
 #pragma unroll
             for (int t = 0; t < T::CAP; ++t) {
                 if (!T::GEN || t < kk) {
@@ -105,21 +106,22 @@ __global__ __launch_bounds__(DW_THREADS) void dw_grad_input_kernel(const float* 
                     if (hh >= 0 && ww >= 0) {
                         const int ho = hh / g.sh, wo = ww / g.sw;
                         if (ho * g.sh == hh && wo * g.sw == ww && ho < g.Ho && wo < g.Wo) {
-                            const float q = one ? wq[t] : dw_quant(kind, wp[t]);
-                            acc = acc + gp[ho * gs.h + wo * gs.w] * q;
+                            const float q = one ? wq[t] : dw_quant(kind, dw_ld(wp[t]));
+                            acc = acc + dw_ld(gp[ho * gs.h + wo * gs.w]) * q;
                         }
                     }
                 }
             }
         }
-        gx[n * xs.n + c * xs.c + h * xs.h + x0 * xs.w] = acc;
+        dw_st(&gx[n * xs.n + c * xs.c + h * xs.h + x0 * xs.w], acc);
     }
 }
 
 // stage 1 of grad_weight: work[(split * Cout + co) * (kk + 1) + t] = this workgroup's share of sum go * x for tap t, and of
 // sum go for t == kk
-template <int KH, int KW>
-__global__ __launch_bounds__(DW_THREADS) void dw_grad_weight_kernel(const float* __restrict__ go, const float* __restrict__ x,
+// (two type parameters like its siblings, so that one dispatch macro serves all three; go and x share XT)
+template <int KH, int KW, typename XT = float, typename = XT>
+__global__ __launch_bounds__(DW_THREADS) void dw_grad_weight_kernel(const XT* __restrict__ go, const XT* __restrict__ x,
                                                                     float* __restrict__ work, DwGeom g, DwStrides gs, DwStrides xs,
                                                                     DwMap mp) {
     using T = DwTaps<KH, KW>;
@@ -139,8 +141,8 @@ __global__ __launch_bounds__(DW_THREADS) void dw_grad_weight_kernel(const float*
         for (int u = split; u < mp.units; u += mp.splits) {
             int n, ho, wo;
             if (!dw_pos(mp, u, tid, n, ho, wo)) continue;
-            const float gv = go[n * gs.n + co * gs.c + ho * gs.h + wo * gs.w];
-            const float* xp = x + n * xs.n + c * xs.c;
+            const float gv = dw_ld(go[n * gs.n + co * gs.c + ho * gs.h + wo * gs.w]);
+            const XT* xp = x + n * xs.n + c * xs.c;
             const int h0 = ho * g.sh - g.ph, w0 = wo * g.sw - g.pw;
             acc[CAP] = acc[CAP] + gv;
 #pragma unroll
@@ -148,7 +150,7 @@ __global__ __launch_bounds__(DW_THREADS) void dw_grad_weight_kernel(const float*
                 if (!T::GEN || t < kk) {
                     const int i = t / kw, j = t - i * kw;
                     const int hi = h0 + i * g.dh, wi = w0 + j * g.dw;
-                    if (hi >= 0 && hi < g.H && wi >= 0 && wi < g.W) acc[t] = acc[t] + gv * xp[hi * xs.h + wi * xs.w];
+                    if (hi >= 0 && hi < g.H && wi >= 0 && wi < g.W) acc[t] = acc[t] + gv * dw_ld(xp[hi * xs.h + wi * xs.w]);
                 }
             }
         }
@@ -181,9 +183,10 @@ __global__ __launch_bounds__(DW_THREADS) void dw_grad_weight_kernel(const float*
     }
 }
 
-// stage 2: the splits in index order, the STE mask on the unquantised weight, the bias gradient
-__global__ __launch_bounds__(DW_THREADS) void dw_grad_weight_combine_kernel(const float* __restrict__ work, const float* __restrict__ w,
-                                                                            float* __restrict__ gw, float* __restrict__ gbias,
+// stage 2: the splits in index order, the STE mask on the unquantised weight, the bias gradient; WT: element type of w, gw, gbias
+template <typename WT = float>
+__global__ __launch_bounds__(DW_THREADS) void dw_grad_weight_combine_kernel(const float* __restrict__ work, const WT* __restrict__ w,
+                                                                            WT* __restrict__ gw, WT* __restrict__ gbias,
                                                                             int64_t Cout, int kk, int splits, float thr) {
     const int per = kk + 1;
     const int64_t total = Cout * per;
@@ -193,10 +196,10 @@ __global__ __launch_bounds__(DW_THREADS) void dw_grad_weight_combine_kernel(cons
         float s = 0.0f;
         for (int sp = 0; sp < splits; ++sp) s = s + work[((int64_t)sp * Cout + co) * per + t];
         if (t < kk) {
-            if (thr > 0.0f && fabsf(w[co * kk + t]) > thr) s = 0.0f;
-            gw[co * kk + t] = s;
+            if (thr > 0.0f && fabsf(dw_ld(w[co * kk + t])) > thr) s = 0.0f;
+            dw_st(&gw[co * kk + t], s);
         } else if (gbias) {
-            gbias[co] = s;
+            dw_st(&gbias[co], s);
         }
     }
 }
@@ -238,6 +241,16 @@ constexpr int DW_TARGET_REDUCE = 1024;      // ... of the grad_weight stage 1: e
         else if ((g).kh == 5 && (g).kw == 5) KERNEL<5, 5><<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);   \
         else if ((g).kh == 7 && (g).kw == 7) KERNEL<7, 7><<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);   \
         else KERNEL<0, 0><<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);                                   \
+    } while (0)
+
+// the same for the kernel templates with two element types
+#define DW_DISPATCH_T(KERNEL, TA, TB, g, ...)                                                                   \
+    do {                                                                                                        \
+        if ((g).kh == 1 && (g).kw == 1) KERNEL<1, 1, TA, TB>   <<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);        \
+        else if ((g).kh == 3 && (g).kw == 3) KERNEL<3, 3, TA, TB>   <<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);   \
+        else if ((g).kh == 5 && (g).kw == 5) KERNEL<5, 5, TA, TB>   <<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);   \
+        else if ((g).kh == 7 && (g).kw == 7) KERNEL<7, 7, TA, TB>   <<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);   \
+        else KERNEL<0, 0, TA, TB>   <<<grid, DW_THREADS, 0, s>>>(__VA_ARGS__);                                   \
     } while (0)
 
 // the same for a kernel template with one more (bool) parameter
@@ -663,48 +676,118 @@ int dw_codes_launch(const int8_t* x_plane, int64_t ldx, int64_t ihy, int64_t ihx
     return qt_check_launch();
 }
 
-}  // namespace
-
-extern "C" int qt_dwconv2d_f32(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t C, int64_t m, int64_t H,
-                               int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t xs_n, int64_t xs_c,
-                               int64_t xs_h, int64_t xs_w, int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, int kind,
-                               qt_stream_t stream) {
+// The bodies of the three entries for any element types (the "_f32" entries: all float).  Validation order: qt_hip.h.
+template <typename XT, typename WT>
+int dw_forward_entry(const XT* x, const WT* w, const float* bias, XT* y, int64_t N, int64_t C, int64_t m, int64_t H, int64_t W, int kh,
+                     int kw, int sh, int sw, int ph, int pw, int dh, int dw, const DwStrides& xs, const DwStrides& ys, int kind,
+                     qt_stream_t stream) {
     DwGeom g{};
     bool empty;
     const int rc = dw_geometry(N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
     if (rc != QT_OK || empty) return rc;
     if (kind != QT_DW_RAW && kind != QT_DW_SIGN && kind != QT_DW_TERNARY) return QT_ERR_INVALID_ARG;
     if (!x || !w || !y) return QT_ERR_INVALID_ARG;
-    const DwStrides xs{xs_n, xs_c, xs_h, xs_w}, ys{ys_n, ys_c, ys_h, ys_w};
     const int ly = dw_layout(N, g.Cout, g.Ho, g.Wo, ys);
     if (dw_layout(N, C, H, W, xs) < 0 || ly < 0) return QT_ERR_INVALID_ARG;
-    if (!dw_aligned4(x) || !dw_aligned4(w) || !dw_aligned4(y) || !dw_aligned4(bias)) return QT_ERR_ALIGNMENT;
+    if (!dw_aligned_elt(x) || !dw_aligned_elt(w) || !dw_aligned_elt(y) || !dw_aligned4(bias)) return QT_ERR_ALIGNMENT;
     const DwMap mp = dw_plan(ly, N, g.Cout, g.Ho, g.Wo, DW_TARGET_STREAM);
     const unsigned grid = (unsigned)(mp.cgs * mp.splits);
     hipStream_t s = (hipStream_t)stream;
-    DW_DISPATCH(dw_forward_kernel, g, x, w, bias, y, g, xs, ys, mp, kind);
+    DW_DISPATCH_T(dw_forward_kernel, XT, WT, g, x, w, bias, y, g, xs, ys, mp, kind);
     return qt_check_launch();
 }
 
-extern "C" int qt_dwconv2d_grad_input_f32(const float* go, const float* w, float* gx, int64_t N, int64_t C, int64_t m, int64_t H,
-                                          int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n,
-                                          int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h,
-                                          int64_t xs_w, int kind, qt_stream_t stream) {
+template <typename XT, typename WT>
+int dw_grad_input_entry(const XT* go, const WT* w, XT* gx, int64_t N, int64_t C, int64_t m, int64_t H, int64_t W, int kh, int kw, int sh,
+                        int sw, int ph, int pw, int dh, int dw, const DwStrides& gs, const DwStrides& xs, int kind, qt_stream_t stream) {
     DwGeom g{};
     bool empty;
     const int rc = dw_geometry(N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
     if (rc != QT_OK || empty) return rc;
     if (kind != QT_DW_RAW && kind != QT_DW_SIGN && kind != QT_DW_TERNARY) return QT_ERR_INVALID_ARG;
     if (!go || !w || !gx) return QT_ERR_INVALID_ARG;
-    const DwStrides gs{gs_n, gs_c, gs_h, gs_w}, xs{xs_n, xs_c, xs_h, xs_w};
     const int lx = dw_layout(N, C, H, W, xs);
     if (dw_layout(N, g.Cout, g.Ho, g.Wo, gs) < 0 || lx < 0) return QT_ERR_INVALID_ARG;
-    if (!dw_aligned4(go) || !dw_aligned4(w) || !dw_aligned4(gx)) return QT_ERR_ALIGNMENT;
+    if (!dw_aligned_elt(go) || !dw_aligned_elt(w) || !dw_aligned_elt(gx)) return QT_ERR_ALIGNMENT;
     const DwMap mp = dw_plan(lx, N, C, g.H, g.W, DW_TARGET_STREAM);
     const unsigned grid = (unsigned)(mp.cgs * mp.splits);
     hipStream_t s = (hipStream_t)stream;
-    DW_DISPATCH(dw_grad_input_kernel, g, go, w, gx, g, gs, xs, mp, kind);
+    DW_DISPATCH_T(dw_grad_input_kernel, XT, WT, g, go, w, gx, g, gs, xs, mp, kind);
     return qt_check_launch();
+}
+
+template <typename XT, typename WT>
+int dw_grad_weight_entry(const XT* go, const XT* x, const WT* w, WT* gw, WT* gbias, float* work, int64_t work_floats, int64_t N,
+                         int64_t C, int64_t m, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                         const DwStrides& gs, const DwStrides& xs, float ste_threshold, qt_stream_t stream) {
+    DwGeom g{};
+    bool empty;
+    const int rc = dw_geometry(N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
+    if (rc != QT_OK) return rc;
+    if (empty) return QT_OK;          // nothing is written: the caller owns the zero gradient of an empty batch
+    if (!gw || (ste_threshold > 0.0f && !w) || !(ste_threshold >= 0.0f)) return QT_ERR_INVALID_ARG;
+    if (!dw_aligned_elt(gw) || !dw_aligned_elt(gbias) || !dw_aligned_elt(w)) return QT_ERR_ALIGNMENT;
+    hipStream_t s = (hipStream_t)stream;
+    const int kk = kh * kw;
+    if (!go || !x || !work || work_floats < 0) return QT_ERR_INVALID_ARG;
+    const int lg = dw_layout(N, g.Cout, g.Ho, g.Wo, gs);
+    if (lg < 0 || dw_layout(N, C, H, W, xs) < 0) return QT_ERR_INVALID_ARG;
+    if (!dw_aligned_elt(go) || !dw_aligned_elt(x) || !dw_aligned4(work)) return QT_ERR_ALIGNMENT;
+    const DwMap mp = dw_plan(lg, N, g.Cout, g.Ho, g.Wo, DW_TARGET_REDUCE);
+    if (work_floats < dw_work_floats(g, mp)) return QT_ERR_INVALID_ARG;
+    const unsigned grid = (unsigned)(mp.cgs * mp.splits);
+    DW_DISPATCH_T(dw_grad_weight_kernel, XT, XT, g, go, x, work, g, gs, xs, mp);
+    int st = qt_check_launch();
+    if (st != QT_OK) return st;
+    dw_grad_weight_combine_kernel<WT><<<qt_stream_grid((g.Cout * (kk + 1) + DW_THREADS - 1) / DW_THREADS), DW_THREADS, 0, s>>>(
+        work, w, gw, gbias, g.Cout, kk, mp.splits, ste_threshold);
+    return qt_check_launch();
+}
+
+}  // namespace
+
+extern "C" int qt_dwconv2d_f32(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t C, int64_t m, int64_t H,
+                               int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t xs_n, int64_t xs_c,
+                               int64_t xs_h, int64_t xs_w, int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, int kind,
+                               qt_stream_t stream) {
+    return dw_forward_entry(x, w, bias, y, N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw, DwStrides{xs_n, xs_c, xs_h, xs_w},
+                            DwStrides{ys_n, ys_c, ys_h, ys_w}, kind, stream);
+}
+
+extern "C" int qt_dwconv2d_h(const void* x, int dtype, const void* w, int w_dtype, const float* bias, void* y, int64_t N, int64_t C,
+                             int64_t m, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                             int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, int64_t ys_n, int64_t ys_c, int64_t ys_h,
+                             int64_t ys_w, int kind, qt_stream_t stream) {
+    int rc = QT_ERR_INVALID_ARG;
+    dw_half_types(dtype, w_dtype, [&](auto* xt, auto* wt) {
+        using XT = std::remove_pointer_t<decltype(xt)>;
+        using WT = std::remove_pointer_t<decltype(wt)>;
+        rc = dw_forward_entry(static_cast<const XT*>(x), static_cast<const WT*>(w), bias, static_cast<XT*>(y), N, C, m, H, W, kh, kw, sh,
+                              sw, ph, pw, dh, dw, DwStrides{xs_n, xs_c, xs_h, xs_w}, DwStrides{ys_n, ys_c, ys_h, ys_w}, kind, stream);
+    });
+    return rc;
+}
+
+extern "C" int qt_dwconv2d_grad_input_f32(const float* go, const float* w, float* gx, int64_t N, int64_t C, int64_t m, int64_t H,
+                                          int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n,
+                                          int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h,
+                                          int64_t xs_w, int kind, qt_stream_t stream) {
+    return dw_grad_input_entry(go, w, gx, N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw, DwStrides{gs_n, gs_c, gs_h, gs_w},
+                               DwStrides{xs_n, xs_c, xs_h, xs_w}, kind, stream);
+}
+
+extern "C" int qt_dwconv2d_grad_input_h(const void* go, int dtype, const void* w, int w_dtype, void* gx, int64_t N, int64_t C, int64_t m,
+                                        int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                                        int64_t gs_n, int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c,
+                                        int64_t xs_h, int64_t xs_w, int kind, qt_stream_t stream) {
+    int rc = QT_ERR_INVALID_ARG;
+    dw_half_types(dtype, w_dtype, [&](auto* xt, auto* wt) {
+        using XT = std::remove_pointer_t<decltype(xt)>;
+        using WT = std::remove_pointer_t<decltype(wt)>;
+        rc = dw_grad_input_entry(static_cast<const XT*>(go), static_cast<const WT*>(w), static_cast<XT*>(gx), N, C, m, H, W, kh, kw, sh,
+                                 sw, ph, pw, dh, dw, DwStrides{gs_n, gs_c, gs_h, gs_w}, DwStrides{xs_n, xs_c, xs_h, xs_w}, kind, stream);
+    });
+    return rc;
 }
 
 extern "C" int64_t qt_dwconv2d_grad_weight_work_floats(int64_t N, int64_t C, int64_t m, int64_t H, int64_t W, int kh, int kw, int sh,
@@ -725,29 +808,24 @@ extern "C" int qt_dwconv2d_grad_weight_f32(const float* go, const float* x, cons
                                            int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n, int64_t gs_c, int64_t gs_h,
                                            int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, float ste_threshold,
                                            qt_stream_t stream) {
-    DwGeom g{};
-    bool empty;
-    const int rc = dw_geometry(N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
-    if (rc != QT_OK) return rc;
-    if (empty) return QT_OK;          // nothing is written: the caller owns the zero gradient of an empty batch
-    if (!gw || (ste_threshold > 0.0f && !w) || !(ste_threshold >= 0.0f)) return QT_ERR_INVALID_ARG;
-    if (!dw_aligned4(gw) || !dw_aligned4(gbias) || !dw_aligned4(w)) return QT_ERR_ALIGNMENT;
-    hipStream_t s = (hipStream_t)stream;
-    const int kk = kh * kw;
-    if (!go || !x || !work || work_floats < 0) return QT_ERR_INVALID_ARG;
-    const DwStrides gs{gs_n, gs_c, gs_h, gs_w}, xs{xs_n, xs_c, xs_h, xs_w};
-    const int lg = dw_layout(N, g.Cout, g.Ho, g.Wo, gs);
-    if (lg < 0 || dw_layout(N, C, H, W, xs) < 0) return QT_ERR_INVALID_ARG;
-    if (!dw_aligned4(go) || !dw_aligned4(x) || !dw_aligned4(work)) return QT_ERR_ALIGNMENT;
-    const DwMap mp = dw_plan(lg, N, g.Cout, g.Ho, g.Wo, DW_TARGET_REDUCE);
-    if (work_floats < dw_work_floats(g, mp)) return QT_ERR_INVALID_ARG;
-    const unsigned grid = (unsigned)(mp.cgs * mp.splits);
-    DW_DISPATCH(dw_grad_weight_kernel, g, go, x, work, g, gs, xs, mp);
-    int st = qt_check_launch();
-    if (st != QT_OK) return st;
-    dw_grad_weight_combine_kernel<<<qt_stream_grid((g.Cout * (kk + 1) + DW_THREADS - 1) / DW_THREADS), DW_THREADS, 0, s>>>(
-        work, w, gw, gbias, g.Cout, kk, mp.splits, ste_threshold);
-    return qt_check_launch();
+    return dw_grad_weight_entry(go, x, w, gw, gbias, work, work_floats, N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw,
+                                DwStrides{gs_n, gs_c, gs_h, gs_w}, DwStrides{xs_n, xs_c, xs_h, xs_w}, ste_threshold, stream);
+}
+
+extern "C" int qt_dwconv2d_grad_weight_h(const void* go, const void* x, int dtype, const void* w, void* gw, void* gbias, int w_dtype,
+                                         float* work, int64_t work_floats, int64_t N, int64_t C, int64_t m, int64_t H, int64_t W, int kh,
+                                         int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n, int64_t gs_c,
+                                         int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w,
+                                         float ste_threshold, qt_stream_t stream) {
+    int rc = QT_ERR_INVALID_ARG;
+    dw_half_types(dtype, w_dtype, [&](auto* xt, auto* wt) {
+        using XT = std::remove_pointer_t<decltype(xt)>;
+        using WT = std::remove_pointer_t<decltype(wt)>;
+        rc = dw_grad_weight_entry(static_cast<const XT*>(go), static_cast<const XT*>(x), static_cast<const WT*>(w), static_cast<WT*>(gw),
+                                  static_cast<WT*>(gbias), work, work_floats, N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw,
+                                  DwStrides{gs_n, gs_c, gs_h, gs_w}, DwStrides{xs_n, xs_c, xs_h, xs_w}, ste_threshold, stream);
+    });
+    return rc;
 }
 
 extern "C" int qt_dwconv2d_sign(const float* x, const uint32_t* x_plane, int64_t ldx, const float* w, const float* bias,

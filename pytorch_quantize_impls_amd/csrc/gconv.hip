@@ -69,9 +69,10 @@ GcPlan gc_plan(const GcGeom& g, int chans_g, int64_t npix, int other_g) {
     return pl;
 }
 
-template <int KH, int KW, int CB>
-__global__ __launch_bounds__(DW_THREADS) void gc_forward_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                                const float* __restrict__ bias, float* __restrict__ y, GcGeom g,
+// XT: element type of x and y, WT: of w (dw_map.h: float, DwBf16, DwF16); LDS weights, accumulators and the bias are fp32 for all
+template <int KH, int KW, int CB, typename XT = float, typename WT = float>
+__global__ __launch_bounds__(DW_THREADS) void gc_forward_kernel(const XT* __restrict__ x, const WT* __restrict__ w,
+                                                                const float* __restrict__ bias, XT* __restrict__ y, GcGeom g,
                                                                 DwStrides xs, DwStrides ys, GcPlan pl, int kind) {
     constexpr bool GEN = KH == 0;
     extern __shared__ float wl[];                                 // [K][CB]
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(DW_THREADS) void gc_forward_kernel(const float* __r
     const int64_t co0 = (int64_t)grp * g.cout_g + j0;
     for (int e = tid; e < CB * K; e += DW_THREADS) {
         const int j = e / K, k = e - j * K;
-        wl[k * CB + j] = j < live ? dw_quant(kind, w[(co0 + j) * K + k]) : 0.0f;
+        wl[k * CB + j] = j < live ? dw_quant(kind, dw_ld(w[(co0 + j) * K + k])) : 0.0f;
     }
     __syncthreads();
     const int hw = g.Ho * g.Wo;
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(DW_THREADS) void gc_forward_kernel(const float* __r
         const int n = p / hw;
         const int r = p - n * hw;
         const int ho = r / g.Wo, wo = r - ho * g.Wo;
-        const float* xp = x + n * xs.n + (int64_t)grp * g.cin_g * xs.c;
+        const XT* xp = x + n * xs.n + (int64_t)grp * g.cin_g * xs.c;
         const int h0 = ho * g.sh - g.ph, w0 = wo * g.sw - g.pw;
         float acc[CB];
 #pragma unroll
@@ -120,11 +121,15 @@ __global__ __launch_bounds__(DW_THREADS) void gc_forward_kernel(const float* __r
             constexpr int UNROLL = T == 1 ? 8 : 2;               // channels whose loads are in flight together
 #pragma unroll UNROLL
             for (int ci = 0; ci < g.cin_g; ++ci) {
-                const float* xc = xp + ci * xs.c;
+                const XT* xc = xp + ci * xs.c;
                 const float* wk = wl + ci * T * CB;
+                XT raw[T];
                 float v[T];
 #pragma unroll
-                for (int t = 0; t < T; ++t) v[t] = xc[off[t]];
+                for (int t = 0; t < T; ++t) raw[t] = xc[off[t]];
+                dw_loads_issued<XT, T>();
+#pragma unroll
+                for (int t = 0; t < T; ++t) v[t] = dw_ld(raw[t]);
 #pragma unroll
                 for (int t = 0; t < T; ++t) {
 #pragma unroll
@@ -136,7 +141,7 @@ __global__ __launch_bounds__(DW_THREADS) void gc_forward_kernel(const float* __r
             }
         } else {
             for (int ci = 0; ci < g.cin_g; ++ci) {
-                const float* xc = xp + ci * xs.c;
+                const XT* xc = xp + ci * xs.c;
                 const float* wk = wl + ci * taps * CB;
                 for (int i = 0; i < g.kh; ++i) {
                     const int hi = h0 + i * g.dh;
@@ -144,7 +149,7 @@ __global__ __launch_bounds__(DW_THREADS) void gc_forward_kernel(const float* __r
                     for (int jj = 0; jj < g.kw; ++jj) {
                         const int wi = w0 + jj * g.dw;
                         if (wi < 0 || wi >= g.W) continue;
-                        const float v = xc[hi * xs.h + wi * xs.w];
+                        const float v = dw_ld(xc[hi * xs.h + wi * xs.w]);
                         const float* wt = wk + (i * g.kw + jj) * CB;
 #pragma unroll
                         for (int j = 0; j < CB; ++j) acc[j] = acc[j] + v * wt[j];
@@ -152,12 +157,12 @@ __global__ __launch_bounds__(DW_THREADS) void gc_forward_kernel(const float* __r
                 }
             }
         }
-        float* yp = y + n * ys.n + co0 * ys.c + ho * ys.h + wo * ys.w;
+        XT* yp = y + n * ys.n + co0 * ys.c + ho * ys.h + wo * ys.w;
 #pragma unroll
         for (int j = 0; j < CB; ++j) {
             if (j < live) {
                 if (bias) acc[j] = acc[j] + bias[co0 + j];
-                yp[j * ys.c] = acc[j];
+                dw_st(&yp[j * ys.c], acc[j]);
             }
         }
     }
@@ -166,9 +171,9 @@ __global__ __launch_bounds__(DW_THREADS) void gc_forward_kernel(const float* __r
 // gather form: gx[n, g cin_g + ci, h, w] = sum over j < cout_g (outermost), taps (i, j') row-major of
 // go[n, g cout_g + j, ho, wo] Q(w)[g cout_g + j, ci, i, j'] where ho sh = h + ph - i dh and wo sw = w + pw - j' dw have a solution
 // inside the output
-template <int KH, int KW, int CB>
-__global__ __launch_bounds__(DW_THREADS) void gc_grad_input_kernel(const float* __restrict__ go, const float* __restrict__ w,
-                                                                   float* __restrict__ gx, GcGeom g, DwStrides gs, DwStrides xs,
+template <int KH, int KW, int CB, typename XT = float, typename WT = float>
+__global__ __launch_bounds__(DW_THREADS) void gc_grad_input_kernel(const XT* __restrict__ go, const WT* __restrict__ w,
+                                                                   XT* __restrict__ gx, GcGeom g, DwStrides gs, DwStrides xs,
                                                                    GcPlan pl, int kind) {
     constexpr bool GEN = KH == 0;
     extern __shared__ float wl[];                                 // [jc][taps][CB]
@@ -188,7 +193,7 @@ __global__ __launch_bounds__(DW_THREADS) void gc_grad_input_kernel(const float* 
             const int jj = e / per, r = e - jj * per;
             const int c = r / taps, t = r - c * taps;
             const bool in = jb + jj < g.cout_g && c < live;
-            wl[(jj * taps + t) * CB + c] = in ? dw_quant(kind, w[((cog + jb + jj) * g.cin_g + c0 + c) * taps + t]) : 0.0f;
+            wl[(jj * taps + t) * CB + c] = in ? dw_quant(kind, dw_ld(w[((cog + jb + jj) * g.cin_g + c0 + c) * taps + t])) : 0.0f;
         }
     };
     if (once) {
@@ -231,12 +236,16 @@ __global__ __launch_bounds__(DW_THREADS) void gc_grad_input_kernel(const float* 
             constexpr int UNROLL = GEN ? 1 : (KH * KW == 1 ? 8 : 2);
 #pragma unroll UNROLL
             for (int jj = 0; jj < jn; ++jj) {
-                const float* gp = go + n * gs.n + (cog + jb + jj) * gs.c;
+                const XT* gp = go + n * gs.n + (cog + jb + jj) * gs.c;
                 const float* wk = wl + jj * per;
                 if (!GEN) {                           // branch-free, as in the forward
+                    XT raw[T];
                     float v[T];
 #pragma unroll
-                    for (int t = 0; t < T; ++t) v[t] = gp[off[t]];
+                    for (int t = 0; t < T; ++t) raw[t] = gp[off[t]];
+                    dw_loads_issued<XT, T>();
+#pragma unroll
+                    for (int t = 0; t < T; ++t) v[t] = dw_ld(raw[t]);
 #pragma unroll
                     for (int t = 0; t < T; ++t) {
 #pragma unroll
@@ -256,7 +265,7 @@ __global__ __launch_bounds__(DW_THREADS) void gc_grad_input_kernel(const float* 
                             if (ww < 0) continue;
                             const int wo = ww / g.sw;
                             if (wo * g.sw != ww || wo >= g.Wo) continue;
-                            const float v = gp[ho * gs.h + wo * gs.w];
+                            const float v = dw_ld(gp[ho * gs.h + wo * gs.w]);
                             const float* wt = wk + (i * g.kw + t2) * CB;
 #pragma unroll
                             for (int c = 0; c < CB; ++c) acc[c] = acc[c] + v * wt[c];
@@ -266,17 +275,18 @@ __global__ __launch_bounds__(DW_THREADS) void gc_grad_input_kernel(const float* 
             }
         }
         if (in) {
-            float* xp = gx + n * xs.n + ci0 * xs.c + h * xs.h + x0 * xs.w;
+            XT* xp = gx + n * xs.n + ci0 * xs.c + h * xs.h + x0 * xs.w;
 #pragma unroll
             for (int c = 0; c < CB; ++c)
-                if (c < live) xp[c * xs.c] = acc[c];
+                if (c < live) dw_st(&xp[c * xs.c], acc[c]);
         }
     }
 }
 
 // stage 1 of grad_weight for any kernel of up to 49 taps, over the virtual channels v = co * cin_g + ci: work[(split * Cv + v) * (kk + 1) + t] = this workgroup's
 // share of sum go[., co] * x[., g cin_g + ci] for tap t, and of sum go[., co] for t == kk
-__global__ __launch_bounds__(DW_THREADS) void gc_grad_weight_kernel(const float* __restrict__ go, const float* __restrict__ x,
+template <typename XT = float>
+__global__ __launch_bounds__(DW_THREADS) void gc_grad_weight_kernel(const XT* __restrict__ go, const XT* __restrict__ x,
                                                                     float* __restrict__ work, GcGeom g, DwStrides gs, DwStrides xs,
                                                                     DwMap mp) {
     constexpr int CAP = GC_MAX_TAPS;
@@ -296,8 +306,8 @@ __global__ __launch_bounds__(DW_THREADS) void gc_grad_weight_kernel(const float*
         for (int u = split; u < mp.units; u += mp.splits) {
             int n, ho, wo;
             if (!dw_pos(mp, u, tid, n, ho, wo)) continue;
-            const float gv = go[n * gs.n + co * gs.c + ho * gs.h + wo * gs.w];
-            const float* xp = x + n * xs.n + c * xs.c;
+            const float gv = dw_ld(go[n * gs.n + co * gs.c + ho * gs.h + wo * gs.w]);
+            const XT* xp = x + n * xs.n + c * xs.c;
             const int h0 = ho * g.sh - g.ph, w0 = wo * g.sw - g.pw;
             acc[CAP] = acc[CAP] + gv;
 #pragma unroll
@@ -305,7 +315,7 @@ __global__ __launch_bounds__(DW_THREADS) void gc_grad_weight_kernel(const float*
                 if (t < kk) {
                     const int i = t / kw, j = t - i * kw;
                     const int hi = h0 + i * g.dh, wi = w0 + j * g.dw;
-                    if (hi >= 0 && hi < g.H && wi >= 0 && wi < g.W) acc[t] = acc[t] + gv * xp[hi * xs.h + wi * xs.w];
+                    if (hi >= 0 && hi < g.H && wi >= 0 && wi < g.W) acc[t] = acc[t] + gv * dw_ld(xp[hi * xs.h + wi * xs.w]);
                 }
             }
         }
@@ -349,8 +359,8 @@ struct GcTilePlan {
     int units, splits;
 };
 
-template <int KH, int KW, int COB, int CIB>
-__global__ __launch_bounds__(DW_THREADS) void gc_grad_weight_tile_kernel(const float* __restrict__ go, const float* __restrict__ x,
+template <int KH, int KW, int COB, int CIB, typename XT = float>
+__global__ __launch_bounds__(DW_THREADS) void gc_grad_weight_tile_kernel(const XT* __restrict__ go, const XT* __restrict__ x,
                                                                          float* __restrict__ work, GcGeom g, DwStrides gs,
                                                                          DwStrides xs, GcTilePlan tp) {
     constexpr int T = KH * KW, A = COB * CIB * T, R = A + COB;
@@ -390,20 +400,24 @@ __global__ __launch_bounds__(DW_THREADS) void gc_grad_weight_tile_kernel(const f
             ok[t] = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
             off[t] = ok[t] ? (int)(hi * xs.h + wi * xs.w) : 0;
         }
-        const float* gp = go + n * gs.n + co0 * gs.c + ho * gs.h + wo * gs.w;
+        const XT* gp = go + n * gs.n + co0 * gs.c + ho * gs.h + wo * gs.w;
         float gv[COB];
 #pragma unroll
         for (int j = 0; j < COB; ++j) {
-            gv[j] = j < live_j ? gp[j * gs.c] : 0.0f;
+            gv[j] = j < live_j ? dw_ld(gp[j * gs.c]) : 0.0f;
             gsum[j] = gsum[j] + gv[j];
         }
-        const float* xp = x + n * xs.n + ci0 * xs.c;
+        const XT* xp = x + n * xs.n + ci0 * xs.c;
 #pragma unroll
         for (int c = 0; c < CIB; ++c) {
             if (c < live_c) {                                     // uniform over the workgroup
+                XT raw[T];
                 float xv[T];
 #pragma unroll
-                for (int t = 0; t < T; ++t) xv[t] = xp[c * xs.c + off[t]];
+                for (int t = 0; t < T; ++t) raw[t] = xp[c * xs.c + off[t]];
+                dw_loads_issued<XT, T>();
+#pragma unroll
+                for (int t = 0; t < T; ++t) xv[t] = dw_ld(raw[t]);
 #pragma unroll
                 for (int t = 0; t < T; ++t) {
 #pragma unroll
@@ -454,9 +468,11 @@ GcTilePlan gc_tile_plan(const GcGeom& g) {
 // register blocks of the tiled stage 1: 144 partial sums per lane at 3 x 3, 64 at 1 x 1
 constexpr int GC_T3_COB = 4, GC_T3_CIB = 4, GC_T1_COB = 8, GC_T1_CIB = 8;
 
-// stage 2: the splits in index order, the STE mask on the unquantised weight, the bias gradient from the ci == 0 channel
-__global__ __launch_bounds__(DW_THREADS) void gc_grad_weight_combine_kernel(const float* __restrict__ work, const float* __restrict__ w,
-                                                                            float* __restrict__ gw, float* __restrict__ gbias,
+// stage 2: the splits in index order, the STE mask on the unquantised weight, the bias gradient from the ci == 0 channel;
+// WT: element type of w, gw and gbias
+template <typename WT = float>
+__global__ __launch_bounds__(DW_THREADS) void gc_grad_weight_combine_kernel(const float* __restrict__ work, const WT* __restrict__ w,
+                                                                            WT* __restrict__ gw, WT* __restrict__ gbias,
                                                                             int64_t Cv, int cin_g, int kk, int splits, float thr) {
     const int per = kk + 1;
     const int64_t total = Cv * per;
@@ -467,10 +483,10 @@ __global__ __launch_bounds__(DW_THREADS) void gc_grad_weight_combine_kernel(cons
         float s = 0.0f;
         for (int sp = 0; sp < splits; ++sp) s = s + work[((int64_t)sp * Cv + v) * per + t];
         if (t < kk) {
-            if (thr > 0.0f && fabsf(w[v * kk + t]) > thr) s = 0.0f;
-            gw[v * kk + t] = s;
+            if (thr > 0.0f && fabsf(dw_ld(w[v * kk + t])) > thr) s = 0.0f;
+            dw_st(&gw[v * kk + t], s);
         } else {
-            gbias[v / cin_g] = s;
+            dw_st(&gbias[v / cin_g], s);
         }
     }
 }
@@ -508,18 +524,19 @@ int gc_geometry(int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, 
 
 bool gc_kind_ok(int kind) { return kind == QT_DW_RAW || kind == QT_DW_SIGN || kind == QT_DW_TERNARY; }
 
-#define GC_LAUNCH_CB(KERNEL, KH, KW, pl, ...)                                                      \
+// TA, TB: the two element types of the kernel template
+#define GC_LAUNCH_CB(KERNEL, KH, KW, TA, TB, pl, ...)                                              \
     do {                                                                                           \
-        if ((pl).cb == 16) KERNEL<KH, KW, 16><<<grid, DW_THREADS, lds, s>>>(__VA_ARGS__);          \
-        else if ((pl).cb == 8) KERNEL<KH, KW, 8><<<grid, DW_THREADS, lds, s>>>(__VA_ARGS__);       \
-        else KERNEL<KH, KW, 4><<<grid, DW_THREADS, lds, s>>>(__VA_ARGS__);                         \
+        if ((pl).cb == 16) KERNEL<KH, KW, 16, TA, TB><<<grid, DW_THREADS, lds, s>>>(__VA_ARGS__);  \
+        else if ((pl).cb == 8) KERNEL<KH, KW, 8, TA, TB><<<grid, DW_THREADS, lds, s>>>(__VA_ARGS__); \
+        else KERNEL<KH, KW, 4, TA, TB><<<grid, DW_THREADS, lds, s>>>(__VA_ARGS__);                 \
     } while (0)
 
-#define GC_DISPATCH(KERNEL, g, pl, ...)                                                            \
+#define GC_DISPATCH(KERNEL, TA, TB, g, pl, ...)                                                    \
     do {                                                                                           \
-        if ((g).kh == 1 && (g).kw == 1) GC_LAUNCH_CB(KERNEL, 1, 1, pl, __VA_ARGS__);               \
-        else if ((g).kh == 3 && (g).kw == 3) GC_LAUNCH_CB(KERNEL, 3, 3, pl, __VA_ARGS__);          \
-        else GC_LAUNCH_CB(KERNEL, 0, 0, pl, __VA_ARGS__);                                          \
+        if ((g).kh == 1 && (g).kw == 1) GC_LAUNCH_CB(KERNEL, 1, 1, TA, TB, pl, __VA_ARGS__);       \
+        else if ((g).kh == 3 && (g).kw == 3) GC_LAUNCH_CB(KERNEL, 3, 3, TA, TB, pl, __VA_ARGS__);  \
+        else GC_LAUNCH_CB(KERNEL, 0, 0, TA, TB, pl, __VA_ARGS__);                                  \
     } while (0)
 
 // ---- the forward on / into bit planes (include/qt_hip.h "Grouped convolution on bit planes") ---------------------------------------
@@ -1015,48 +1032,135 @@ inline int gc_reduce_splits(const GcGeom& g, int cl) {
     return gc_reduce_plan(g, cl).splits;
 }
 
-}  // namespace
-
-extern "C" int qt_gconv2d_f32(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t G, int64_t cin_g,
-                              int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
-                              int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, int64_t ys_n, int64_t ys_c, int64_t ys_h,
-                              int64_t ys_w, int kind, qt_stream_t stream) {
+// The bodies of the three entries for any element types (the "_f32" entries: all float).  Validation order: qt_hip.h.
+template <typename XT, typename WT>
+int gc_forward_entry(const XT* x, const WT* w, const float* bias, XT* y, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H,
+                     int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, const DwStrides& xs, const DwStrides& ys,
+                     int kind, qt_stream_t stream) {
     GcGeom g{};
     bool empty;
     const int rc = gc_geometry(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
     if (rc != QT_OK || empty) return rc;
     if (!gc_kind_ok(kind)) return QT_ERR_INVALID_ARG;
     if (!x || !w || !y) return QT_ERR_INVALID_ARG;
-    const DwStrides xs{xs_n, xs_c, xs_h, xs_w}, ys{ys_n, ys_c, ys_h, ys_w};
     if (dw_layout(N, g.Cin, H, W, xs) < 0 || dw_layout(N, g.Cout, g.Ho, g.Wo, ys) < 0) return QT_ERR_INVALID_ARG;
-    if (!dw_aligned4(x) || !dw_aligned4(w) || !dw_aligned4(y) || !dw_aligned4(bias)) return QT_ERR_ALIGNMENT;
+    if (!dw_aligned_elt(x) || !dw_aligned_elt(w) || !dw_aligned_elt(y) || !dw_aligned4(bias)) return QT_ERR_ALIGNMENT;
     const GcPlan pl = gc_plan(g, g.cout_g, (int64_t)g.N * g.Ho * g.Wo, g.cin_g);
     const unsigned grid = (unsigned)((int64_t)g.G * pl.nblk * pl.splits);
     const size_t lds = sizeof(float) * pl.cb * g.cin_g * kh * kw;
     hipStream_t s = (hipStream_t)stream;
-    GC_DISPATCH(gc_forward_kernel, g, pl, x, w, bias, y, g, xs, ys, pl, kind);
+    GC_DISPATCH(gc_forward_kernel, XT, WT, g, pl, x, w, bias, y, g, xs, ys, pl, kind);
     return qt_check_launch();
 }
 
-extern "C" int qt_gconv2d_grad_input_f32(const float* go, const float* w, float* gx, int64_t N, int64_t G, int64_t cin_g,
-                                         int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
-                                         int dw, int64_t gs_n, int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c,
-                                         int64_t xs_h, int64_t xs_w, int kind, qt_stream_t stream) {
+template <typename XT, typename WT>
+int gc_grad_input_entry(const XT* go, const WT* w, XT* gx, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W,
+                        int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, const DwStrides& gs, const DwStrides& xs,
+                        int kind, qt_stream_t stream) {
     GcGeom g{};
     bool empty;
     const int rc = gc_geometry(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
     if (rc != QT_OK || empty) return rc;
     if (!gc_kind_ok(kind)) return QT_ERR_INVALID_ARG;
     if (!go || !w || !gx) return QT_ERR_INVALID_ARG;
-    const DwStrides gs{gs_n, gs_c, gs_h, gs_w}, xs{xs_n, xs_c, xs_h, xs_w};
     if (dw_layout(N, g.Cout, g.Ho, g.Wo, gs) < 0 || dw_layout(N, g.Cin, H, W, xs) < 0) return QT_ERR_INVALID_ARG;
-    if (!dw_aligned4(go) || !dw_aligned4(w) || !dw_aligned4(gx)) return QT_ERR_ALIGNMENT;
+    if (!dw_aligned_elt(go) || !dw_aligned_elt(w) || !dw_aligned_elt(gx)) return QT_ERR_ALIGNMENT;
     const GcPlan pl = gc_plan(g, g.cin_g, (int64_t)g.N * g.H * g.W, g.cout_g);
     const unsigned grid = (unsigned)((int64_t)g.G * pl.nblk * pl.splits);
     const size_t lds = sizeof(float) * pl.jc * pl.cb * kh * kw;
     hipStream_t s = (hipStream_t)stream;
-    GC_DISPATCH(gc_grad_input_kernel, g, pl, go, w, gx, g, gs, xs, pl, kind);
+    GC_DISPATCH(gc_grad_input_kernel, XT, WT, g, pl, go, w, gx, g, gs, xs, pl, kind);
     return qt_check_launch();
+}
+
+template <typename XT, typename WT>
+int gc_grad_weight_entry(const XT* go, const XT* x, const WT* w, WT* gw, WT* gbias, float* work, int64_t work_floats, int64_t N,
+                         int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw,
+                         int dh, int dw, const DwStrides& gs, const DwStrides& xs, float ste_threshold, qt_stream_t stream) {
+    GcGeom g{};
+    bool empty;
+    const int rc = gc_geometry(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
+    if (rc != QT_OK) return rc;
+    if (empty) return QT_OK;          // nothing is written: the caller owns the zero gradient of an empty batch
+    if (!gw || (ste_threshold > 0.0f && !w) || !(ste_threshold >= 0.0f)) return QT_ERR_INVALID_ARG;
+    if (!go || !x || !work || work_floats < 0) return QT_ERR_INVALID_ARG;
+    const int lg = dw_layout(N, g.Cout, g.Ho, g.Wo, gs);
+    if (lg < 0 || dw_layout(N, g.Cin, H, W, xs) < 0) return QT_ERR_INVALID_ARG;
+    const int splits = gc_reduce_splits(g, lg);
+    if (work_floats < gc_work_floats(g, splits)) return QT_ERR_INVALID_ARG;
+    if (!dw_aligned_elt(gw) || !dw_aligned_elt(gbias) || !dw_aligned_elt(w) || !dw_aligned_elt(go) || !dw_aligned_elt(x) ||
+        !dw_aligned4(work))
+        return QT_ERR_ALIGNMENT;
+    hipStream_t s = (hipStream_t)stream;
+    const int kk = kh * kw;
+    const int64_t Cv = g.Cout * g.cin_g;
+    const int tiled = gc_tiled(g);
+    if (tiled == 1) {
+        const GcTilePlan tp = gc_tile_plan<GC_T1_COB, GC_T1_CIB>(g);
+        const unsigned grid = (unsigned)((int64_t)g.G * tp.nco * tp.nci * tp.splits);
+        gc_grad_weight_tile_kernel<1, 1, GC_T1_COB, GC_T1_CIB, XT><<<grid, DW_THREADS, 0, s>>>(go, x, work, g, gs, xs, tp);
+    } else if (tiled == 3) {
+        const GcTilePlan tp = gc_tile_plan<GC_T3_COB, GC_T3_CIB>(g);
+        const unsigned grid = (unsigned)((int64_t)g.G * tp.nco * tp.nci * tp.splits);
+        gc_grad_weight_tile_kernel<3, 3, GC_T3_COB, GC_T3_CIB, XT><<<grid, DW_THREADS, 0, s>>>(go, x, work, g, gs, xs, tp);
+    } else {
+        const DwMap mp = gc_reduce_plan(g, lg);
+        const unsigned grid = (unsigned)(mp.cgs * mp.splits);
+        gc_grad_weight_kernel<XT><<<grid, DW_THREADS, 0, s>>>(go, x, work, g, gs, xs, mp);
+    }
+    const int st = qt_check_launch();
+    if (st != QT_OK) return st;
+    gc_grad_weight_combine_kernel<WT><<<qt_stream_grid((Cv * (kk + 1) + DW_THREADS - 1) / DW_THREADS), DW_THREADS, 0, s>>>(
+        work, w, gw, gbias, Cv, g.cin_g, kk, splits, ste_threshold);
+    return qt_check_launch();
+}
+
+}  // namespace
+
+extern "C" int qt_gconv2d_f32(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t G, int64_t cin_g,
+                              int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                              int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, int64_t ys_n, int64_t ys_c, int64_t ys_h,
+                              int64_t ys_w, int kind, qt_stream_t stream) {
+    return gc_forward_entry(x, w, bias, y, N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, DwStrides{xs_n, xs_c, xs_h, xs_w},
+                            DwStrides{ys_n, ys_c, ys_h, ys_w}, kind, stream);
+}
+
+extern "C" int qt_gconv2d_h(const void* x, int dtype, const void* w, int w_dtype, const float* bias, void* y, int64_t N, int64_t G,
+                            int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                            int dw, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, int64_t ys_n, int64_t ys_c, int64_t ys_h,
+                            int64_t ys_w, int kind, qt_stream_t stream) {
+    int rc = QT_ERR_INVALID_ARG;
+    dw_half_types(dtype, w_dtype, [&](auto* xt, auto* wt) {
+        using XT = std::remove_pointer_t<decltype(xt)>;
+        using WT = std::remove_pointer_t<decltype(wt)>;
+        rc = gc_forward_entry(static_cast<const XT*>(x), static_cast<const WT*>(w), bias, static_cast<XT*>(y), N, G, cin_g, cout_g, H, W,
+                              kh, kw, sh, sw, ph, pw, dh, dw, DwStrides{xs_n, xs_c, xs_h, xs_w}, DwStrides{ys_n, ys_c, ys_h, ys_w}, kind,
+                              stream);
+    });
+    return rc;
+}
+
+extern "C" int qt_gconv2d_grad_input_f32(const float* go, const float* w, float* gx, int64_t N, int64_t G, int64_t cin_g,
+                                         int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                                         int dw, int64_t gs_n, int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c,
+                                         int64_t xs_h, int64_t xs_w, int kind, qt_stream_t stream) {
+    return gc_grad_input_entry(go, w, gx, N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, DwStrides{gs_n, gs_c, gs_h, gs_w},
+                               DwStrides{xs_n, xs_c, xs_h, xs_w}, kind, stream);
+}
+
+extern "C" int qt_gconv2d_grad_input_h(const void* go, int dtype, const void* w, int w_dtype, void* gx, int64_t N, int64_t G,
+                                       int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph,
+                                       int pw, int dh, int dw, int64_t gs_n, int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n,
+                                       int64_t xs_c, int64_t xs_h, int64_t xs_w, int kind, qt_stream_t stream) {
+    int rc = QT_ERR_INVALID_ARG;
+    dw_half_types(dtype, w_dtype, [&](auto* xt, auto* wt) {
+        using XT = std::remove_pointer_t<decltype(xt)>;
+        using WT = std::remove_pointer_t<decltype(wt)>;
+        rc = gc_grad_input_entry(static_cast<const XT*>(go), static_cast<const WT*>(w), static_cast<XT*>(gx), N, G, cin_g, cout_g, H, W,
+                                 kh, kw, sh, sw, ph, pw, dh, dw, DwStrides{gs_n, gs_c, gs_h, gs_w}, DwStrides{xs_n, xs_c, xs_h, xs_w},
+                                 kind, stream);
+    });
+    return rc;
 }
 
 extern "C" int64_t qt_gconv2d_grad_weight_work_floats(int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W,
@@ -1076,42 +1180,24 @@ extern "C" int qt_gconv2d_grad_weight_f32(const float* go, const float* x, const
                                           int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n,
                                           int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h,
                                           int64_t xs_w, float ste_threshold, qt_stream_t stream) {
-    GcGeom g{};
-    bool empty;
-    const int rc = gc_geometry(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, &g, &empty);
-    if (rc != QT_OK) return rc;
-    if (empty) return QT_OK;          // nothing is written: the caller owns the zero gradient of an empty batch
-    if (!gw || (ste_threshold > 0.0f && !w) || !(ste_threshold >= 0.0f)) return QT_ERR_INVALID_ARG;
-    if (!go || !x || !work || work_floats < 0) return QT_ERR_INVALID_ARG;
-    const DwStrides gs{gs_n, gs_c, gs_h, gs_w}, xs{xs_n, xs_c, xs_h, xs_w};
-    const int lg = dw_layout(N, g.Cout, g.Ho, g.Wo, gs);
-    if (lg < 0 || dw_layout(N, g.Cin, H, W, xs) < 0) return QT_ERR_INVALID_ARG;
-    const int splits = gc_reduce_splits(g, lg);
-    if (work_floats < gc_work_floats(g, splits)) return QT_ERR_INVALID_ARG;
-    if (!dw_aligned4(gw) || !dw_aligned4(gbias) || !dw_aligned4(w) || !dw_aligned4(go) || !dw_aligned4(x) || !dw_aligned4(work))
-        return QT_ERR_ALIGNMENT;
-    hipStream_t s = (hipStream_t)stream;
-    const int kk = kh * kw;
-    const int64_t Cv = g.Cout * g.cin_g;
-    const int tiled = gc_tiled(g);
-    if (tiled == 1) {
-        const GcTilePlan tp = gc_tile_plan<GC_T1_COB, GC_T1_CIB>(g);
-        const unsigned grid = (unsigned)((int64_t)g.G * tp.nco * tp.nci * tp.splits);
-        gc_grad_weight_tile_kernel<1, 1, GC_T1_COB, GC_T1_CIB><<<grid, DW_THREADS, 0, s>>>(go, x, work, g, gs, xs, tp);
-    } else if (tiled == 3) {
-        const GcTilePlan tp = gc_tile_plan<GC_T3_COB, GC_T3_CIB>(g);
-        const unsigned grid = (unsigned)((int64_t)g.G * tp.nco * tp.nci * tp.splits);
-        gc_grad_weight_tile_kernel<3, 3, GC_T3_COB, GC_T3_CIB><<<grid, DW_THREADS, 0, s>>>(go, x, work, g, gs, xs, tp);
-    } else {
-        const DwMap mp = gc_reduce_plan(g, lg);
-        const unsigned grid = (unsigned)(mp.cgs * mp.splits);
-        gc_grad_weight_kernel<<<grid, DW_THREADS, 0, s>>>(go, x, work, g, gs, xs, mp);
-    }
-    const int st = qt_check_launch();
-    if (st != QT_OK) return st;
-    gc_grad_weight_combine_kernel<<<qt_stream_grid((Cv * (kk + 1) + DW_THREADS - 1) / DW_THREADS), DW_THREADS, 0, s>>>(
-        work, w, gw, gbias, Cv, g.cin_g, kk, splits, ste_threshold);
-    return qt_check_launch();
+    return gc_grad_weight_entry(go, x, w, gw, gbias, work, work_floats, N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw,
+                                DwStrides{gs_n, gs_c, gs_h, gs_w}, DwStrides{xs_n, xs_c, xs_h, xs_w}, ste_threshold, stream);
+}
+
+extern "C" int qt_gconv2d_grad_weight_h(const void* go, const void* x, int dtype, const void* w, void* gw, void* gbias, int w_dtype,
+                                        float* work, int64_t work_floats, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g,
+                                        int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                                        int64_t gs_n, int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c,
+                                        int64_t xs_h, int64_t xs_w, float ste_threshold, qt_stream_t stream) {
+    int rc = QT_ERR_INVALID_ARG;
+    dw_half_types(dtype, w_dtype, [&](auto* xt, auto* wt) {
+        using XT = std::remove_pointer_t<decltype(xt)>;
+        using WT = std::remove_pointer_t<decltype(wt)>;
+        rc = gc_grad_weight_entry(static_cast<const XT*>(go), static_cast<const XT*>(x), static_cast<const WT*>(w), static_cast<WT*>(gw),
+                                  static_cast<WT*>(gbias), work, work_floats, N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw,
+                                  DwStrides{gs_n, gs_c, gs_h, gs_w}, DwStrides{xs_n, xs_c, xs_h, xs_w}, ste_threshold, stream);
+    });
+    return rc;
 }
 
 extern "C" int qt_gconv2d_sign(const uint32_t* x_plane, int64_t ldx, const float* w, const float* bias, const float* alpha,

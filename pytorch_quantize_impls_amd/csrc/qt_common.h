@@ -5,7 +5,7 @@
 #include <atomic>
 #include "../../include/qt_hip.h"
 
-#define QT_VERSION_INT 301 /* 0.3.1: tile describe entry points (0.3.0: flags argument of qt_conv2d_implicit_bits / _nib / _codes; 0.2.0: half-precision operands) */
+#define QT_VERSION_INT 302 /* 0.3.2: depthwise / grouped "_h" entries (0.3.1: tile describe entry points; 0.3.0: flags argument of qt_conv2d_implicit_bits / _nib / _codes; 0.2.0: half-precision operands) */
 
 static inline int qt_check_launch() {
     hipError_t e = hipGetLastError();

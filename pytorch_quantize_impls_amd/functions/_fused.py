@@ -2009,6 +2009,52 @@ class LogLinConv2dFn(QtFunction):
 # convs").  The kernels multiply whatever the activation holds, so nothing here asks whether it is +-1: no tag lookup, no detection,
 # no host synchronisation — the node can be captured in a hipGraph as it is.
 
+def _streaming_grad_output(grad_output: torch.Tensor, input: torch.Tensor) -> torch.Tensor:
+    """The incoming gradient as the streaming kernels read it: dense, and of the activation's dtype (the gradient entries take one
+    element type for the activation side; it already has it unless something between the layers changed the dtype)."""
+    go = _dense(grad_output)
+    return go if go.dtype == input.dtype else go.to(input.dtype)
+
+
+#: routes taken by ``depthwise_half_route`` / ``grouped_half_route`` layers, by family ("depthwise" | "grouped"); the tests read it
+STREAMING_HALF_STATS: Counter = Counter()
+
+#: depthwise BinConv2d / TerConv2d on bf16 / fp16 activations run the "_h" streaming kernels (False: the dense library's half conv,
+#: counted in LIBRARY_PATHS).  Set from tools/bench_half_streaming.py by the rule of DESIGN.md "Half-precision streaming convs":
+#: True iff for both dtypes and all six MobileNet-v1 shapes the forward+backward round range lies entirely below the library's.
+#: Measured (profiles/half_streaming_bench_line.json): it does on all twelve rows, 1.5x - 7x; the forward alone is level with the
+#: library (0.5x - 1.1x of its time; behind it by 9 - 11 % at 256 channels, 28 x 28).
+DEPTHWISE_HALF = True
+#: most input channels per group that take the grouped "_h" kernels (0: off; never above GROUPED_MAX_CIN_G): the largest measured
+#: value of 4, 8 up to which, for both dtypes, the training-step round range lies below the library's and the forward median is not
+#: above the library's.  Measured: 4 and 8 both pass in both dtypes (step 2.0x - 14x, forward 1.5x - 7.6x; the closest row is
+#: 256 x 28 x 28 with 8 channels per group in fp16: forward 319 against 488 us, step 1603 - 1627 against 3149 - 3157 us).
+GROUPED_HALF_MAX_CIN_G = 8
+
+
+def _streaming_half_common(layer, input) -> bool:
+    """What both half routes ask: ``half_route`` holds (same half dtype, or an fp32 weight under autocast to the activation's
+    dtype), a 4-D device activation, padding mode "zeros" with numeric padding."""
+    return (half_route(input, layer.weight) and input.dim() == 4 and layer.padding_mode == "zeros"
+            and not isinstance(layer.padding, str))
+
+
+def depthwise_half_route(layer, input) -> bool:
+    """``depthwise_route`` for a bf16 / fp16 activation: the "_h" streaming kernels, switched by ``DEPTHWISE_HALF``.  As on fp32
+    nothing asks whether the activation is +-1."""
+    return (bool(DEPTHWISE_HALF) and _streaming_half_common(layer, input) and layer.groups > 1
+            and ops.depthwise_applicable(input.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups))
+
+
+def grouped_half_route(layer, input) -> bool:
+    """``grouped_route`` for a bf16 / fp16 activation: at least ``GROUPED_MIN_GROUPS`` groups of 2 ... ``GROUPED_HALF_MAX_CIN_G``
+    (capped by ``GROUPED_MAX_CIN_G``) input channels each."""
+    top = min(int(GROUPED_HALF_MAX_CIN_G), GROUPED_MAX_CIN_G)
+    return (_streaming_half_common(layer, input) and layer.groups >= GROUPED_MIN_GROUPS
+            and 2 <= int(layer.weight.shape[1]) <= top
+            and ops.grouped_applicable(input.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups))
+
+
 def depthwise_route(layer, input) -> bool:
     """``layer`` (a Conv2d subclass with an fp32 weight) applied to ``input`` is a depthwise conv the HIP kernels take: a 4-D fp32
     device tensor, ``groups == in_channels > 1``, padding mode "zeros" with numeric padding."""
@@ -2029,15 +2075,18 @@ class DepthwiseConv2dFn(QtFunction):
         stride, padding, dilation, _groups = conv_args
         ctx.kind = kind if weight_q is None else "raw"
         ctx.conv_args, ctx.ste, ctx.has_bias = conv_args, float(ste), bias is not None
+        ctx.bias_dtype = bias.dtype if bias is not None else None
         input = _dense(input)
         ctx.save_for_backward(input, weight, weight_q)
+        if input.dtype in ops.HALF_DTYPES:      # the "_h" entries add an fp32 bias vector before their one rounding
+            bias = half_bias(bias, input.dtype)
         return ops.depthwise_conv2d(input, weight if weight_q is None else weight_q, bias, stride, padding, dilation, kind=ctx.kind)
 
     @staticmethod
     def backward(ctx, grad_output):
         input, weight, weight_q = ctx.saved_tensors
         stride, padding, dilation, _groups = ctx.conv_args
-        go = _dense(grad_output)
+        go = _streaming_grad_output(grad_output, input)
         grad_input = grad_weight = grad_bias = None
         if ctx.needs_input_grad[0]:
             grad_input = ops.depthwise_conv2d_grad_input(input.shape, weight if weight_q is None else weight_q, go, stride, padding,
@@ -2050,6 +2099,8 @@ class DepthwiseConv2dFn(QtFunction):
                                                                       ste_threshold=ctx.ste, want_bias=want_bias)
             if not ctx.needs_input_grad[1]:
                 grad_weight = None
+        if grad_bias is not None and grad_bias.dtype != ctx.bias_dtype:
+            grad_bias = grad_bias.to(ctx.bias_dtype)
         return grad_input, grad_weight, grad_bias, None, None, None, None
 
 
@@ -2086,15 +2137,18 @@ class GroupedConv2dFn(QtFunction):
         stride, padding, dilation, groups = conv_args
         ctx.kind = kind if weight_q is None else "raw"
         ctx.conv_args, ctx.ste, ctx.has_bias = conv_args, float(ste), bias is not None
+        ctx.bias_dtype = bias.dtype if bias is not None else None
         input = _dense(input)
         ctx.save_for_backward(input, weight, weight_q)
+        if input.dtype in ops.HALF_DTYPES:      # the "_h" entries add an fp32 bias vector before their one rounding
+            bias = half_bias(bias, input.dtype)
         return ops.grouped_conv2d(input, weight if weight_q is None else weight_q, bias, stride, padding, dilation, groups, kind=ctx.kind)
 
     @staticmethod
     def backward(ctx, grad_output):
         input, weight, weight_q = ctx.saved_tensors
         stride, padding, dilation, groups = ctx.conv_args
-        go = _dense(grad_output)
+        go = _streaming_grad_output(grad_output, input)
         grad_input = grad_weight = grad_bias = None
         if ctx.needs_input_grad[0]:
             grad_input = ops.grouped_conv2d_grad_input(input.shape, weight if weight_q is None else weight_q, go, stride, padding,
@@ -2107,6 +2161,8 @@ class GroupedConv2dFn(QtFunction):
                                                                     ste_threshold=ctx.ste, want_bias=want_bias)
             if not ctx.needs_input_grad[1]:
                 grad_weight = None
+        if grad_bias is not None and grad_bias.dtype != ctx.bias_dtype:
+            grad_bias = grad_bias.to(ctx.bias_dtype)
         return grad_input, grad_weight, grad_bias, None, None, None, None
 
 

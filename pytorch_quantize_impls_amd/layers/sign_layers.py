@@ -169,8 +169,8 @@ class _SignConv2d(EvalSwapMixin, torch.nn.Conv2d, QLayer):
     def _half_forward(self, input):
         """bf16 / fp16 device activation (``_fused.half_route``) that is tagged, hinted or detected as +-1: the implicit-GEMM conv
         on fp4 planes with the result in the activation's dtype (the exact sum + bias rounded once); None for everything the
-        packed conv does not take (real-valued activations, grouped convs, non-zero padding modes, off-grid eval weights), which
-        keeps the counted torch expression below.  Never deferred: the modules between the layers stay torch ops in half."""
+        packed conv does not take (real-valued activations, grouped convs, non-zero padding modes, off-grid eval weights): a grouped
+        conv goes on to ``_streaming_half_forward``, the rest keeps the counted torch expression below.  Never deferred: the modules between the layers stay torch ops in half."""
         from ..packed import NHWC
         if self.groups != 1 or self.padding_mode != "zeros" or input.dim() != 4 or isinstance(self.padding, str):
             return None
@@ -210,6 +210,27 @@ class _SignConv2d(EvalSwapMixin, torch.nn.Conv2d, QLayer):
             return None
         return fn.apply(input, self.weight, self.bias, "raw", self.weight.detach(), _fused.ops.STE_THRESHOLD, args)
 
+    def _streaming_half_forward(self, input):
+        """``_streaming_forward`` for a bf16 / fp16 activation (``_fused.depthwise_half_route`` / ``grouped_half_route``): the same
+        autograd nodes on the "_h" entries — results rounded once into the activation's dtype, the weight gradient in the weight's
+        dtype.  Real-valued activations take it too (nothing asks for +-1); never deferred.  None: the counted library expression."""
+        if _fused.depthwise_half_route(self, input):
+            fn, fam = _fused.DepthwiseConv2dFn, "depthwise"
+        elif _fused.grouped_half_route(self, input):
+            fn, fam = _fused.GroupedConv2dFn, "grouped"
+        else:
+            return None
+        args = (self.stride, self.padding, self.dilation, self.groups)
+        if self.training:
+            wq = None if self.deterministic else self._op.apply(self.weight.detach())
+            y = fn.apply(input, self.weight, self.bias, self.kind, wq, _fused.ops.STE_THRESHOLD, args)
+        elif not self._eval_on_grid():
+            return None
+        else:
+            y = fn.apply(input, self.weight, self.bias, "raw", self.weight.detach(), _fused.ops.STE_THRESHOLD, args)
+        _fused.STREAMING_HALF_STATS[fam] += 1
+        return y
+
     def forward(self, input):
         """Eval mode without autograd on a HIP device: returns a deferred activation (``lazy.LazyActivation``: a Tensor
         that runs this conv fused with the BatchNorm / pooling / Hardtanh / BinaryConnect modules that follow it, or
@@ -226,6 +247,8 @@ class _SignConv2d(EvalSwapMixin, torch.nn.Conv2d, QLayer):
             return _fused.packed_conv2d(self, input, kind)
         if _fused.half_route(input, self.weight):
             y = self._half_forward(input)         # bf16 / fp16 activation that is (treated as) +-1: the packed routes
+            if y is None and self.groups > 1:
+                y = self._streaming_half_forward(input)       # depthwise / few channels per group: the "_h" streaming kernels
             if y is not None:
                 return y
         if not input.is_cuda or input.dtype != torch.float32 or self.weight.dtype != torch.float32:

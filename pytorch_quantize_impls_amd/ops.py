@@ -4127,37 +4127,54 @@ def _dw_strides(shape, channels_last: bool):
     return (H * W * C, 1, W * C, C) if channels_last else (C * H * W, H * W, W, 1)
 
 
-def _dw_operand(t: torch.Tensor, name: str, shape=None) -> torch.Tensor:
-    _require(t, name)
+def _dw_operand(t: torch.Tensor, name: str, shape=None, half: bool = False) -> torch.Tensor:
+    """``half``: bf16 / fp16 are taken too (the streaming forward and gradients, which have "_h" entries)."""
+    _require_packable(t, name) if half else _require(t, name)
     if t.dim() != 4 or (shape is not None and tuple(t.shape) != tuple(shape)):
         raise ValueError(f"{name}: expected a 4-D tensor" + (f" of shape {tuple(shape)}" if shape is not None else "") + f", got {tuple(t.shape)}")
     return t if _storage_dense(t) else t.contiguous()
 
 
-def _dw_result(out: Optional[torch.Tensor], shape, like: torch.Tensor, name: str) -> torch.Tensor:
-    """``out`` checked (fp32, this shape, dense in NCHW or channels-last order, on ``like``'s device), or a new tensor of
+def _dw_result(out: Optional[torch.Tensor], shape, like: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
+    """``out`` checked (``dtype``, this shape, dense in NCHW or channels-last order, on ``like``'s device), or a new tensor of
     ``shape`` in the layout of ``like``."""
     if out is None:
         fmt = torch.channels_last if _dw_channels_last(like) else torch.contiguous_format
-        return torch.empty(tuple(shape), dtype=torch.float32, device=like.device, memory_format=fmt)
-    _require(out, name)
+        return torch.empty(tuple(shape), dtype=dtype, device=like.device, memory_format=fmt)
+    _require(out, name, dtype)
     if tuple(out.shape) != tuple(shape) or not _storage_dense(out) or out.device != like.device:
-        raise ValueError(f"{name}: expected a dense fp32 tensor of shape {tuple(shape)} on {like.device}, got {tuple(out.shape)} "
+        raise ValueError(f"{name}: expected a dense {dtype} tensor of shape {tuple(shape)} on {like.device}, got {tuple(out.shape)} "
                          f"with strides {out.stride()} on {out.device}")
     return out
 
 
-def _dw_weight(weight: torch.Tensor, C: int):
-    _require(weight, "weight")
+def _dw_half_codes(act: torch.Tensor, weight: torch.Tensor, *more):
+    """The dtype rule of the streaming convs.  None: everything is fp32 (the "_f32" entries).  (dtype, w_dtype) codes of the "_h"
+    entries: the activation-side tensors (``act`` and ``more``) share ONE half dtype and the weight has that dtype or is fp32
+    (an fp32 model under autocast).  Anything else is a TypeError."""
+    for t in more:
+        if t.dtype != act.dtype:
+            raise TypeError(f"the activation-side tensors must share a dtype, got {act.dtype} and {t.dtype}")
+    if act.dtype == torch.float32:
+        if weight.dtype != torch.float32:
+            raise TypeError(f"weight: expected dtype torch.float32 for an fp32 activation, got {weight.dtype}")
+        return None
+    if weight.dtype != act.dtype and weight.dtype != torch.float32:
+        raise TypeError(f"weight: expected dtype {act.dtype} or torch.float32 for a {act.dtype} activation, got {weight.dtype}")
+    return _DTYPE_CODE[act.dtype], _DTYPE_CODE.get(weight.dtype, _lib.DEFINES["QT_DTYPE_F32"])
+
+
+def _dw_weight(weight: torch.Tensor, C: int, half: bool = False):
+    _require_packable(weight, "weight") if half else _require(weight, "weight")
     if weight.dim() != 4 or weight.shape[1] != 1 or C < 1 or weight.shape[0] % C != 0 or weight.shape[0] < C:
         raise ValueError(f"weight: expected [C * m, 1, kh, kw] for C = {C}, got {tuple(weight.shape)}")
     w = weight.detach()
     return (w if w.is_contiguous() else w.contiguous()), int(weight.shape[0]) // C, int(weight.shape[2]), int(weight.shape[3])
 
 
-def _dw_geometry(x_shape, weight, stride, padding, dilation):
+def _dw_geometry(x_shape, weight, stride, padding, dilation, half: bool = False):
     N, C, H, W = (int(v) for v in x_shape)
-    w, m, kh, kw = _dw_weight(weight, C)
+    w, m, kh, kw = _dw_weight(weight, C, half)
     if not depthwise_applicable(x_shape, weight.shape, stride, padding, dilation, C) and min(N, C, H, W) > 0:
         raise ValueError(f"not a depthwise conv the HIP entry points take: input {tuple(x_shape)}, weight {tuple(weight.shape)}, "
                          f"stride {stride}, padding {padding}, dilation {dilation}")
@@ -4171,16 +4188,23 @@ def depthwise_conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
     """F.conv2d(x, Q(weight), bias, stride, padding, dilation, groups = C) for x [N, C, H, W] fp32 (NCHW or channels-last) and
     weight [C * m, 1, kh, kw]; Q = ``kind`` ("raw" | "binary" | "ternary") is applied to the taps inside the one launch
     (qt_dwconv2d_f32).  The result has the layout of x, or is written into ``out``.  Bit-reproducible: +0 start, taps in row-major
-    order, one multiply and one add each, out-of-image taps skipped, bias last."""
-    x = _dw_operand(x, "input")
-    w, geom, y_shape = _dw_geometry(x.shape, weight, stride, padding, dilation)
+    order, one multiply and one add each, out-of-image taps skipped, bias last.  A bf16 / fp16 ``x`` (with a weight of the same dtype,
+    or fp32 as under autocast; ``bias`` stays an fp32 vector) runs qt_dwconv2d_h: the same fp32 arithmetic on the exactly upcast
+    elements, rounded once to nearest even into a result of x's dtype."""
+    x = _dw_operand(x, "input", half=True)
+    w, geom, y_shape = _dw_geometry(x.shape, weight, stride, padding, dilation, half=True)
+    codes = _dw_half_codes(x, w)
     bias = _check_bias(bias, y_shape[1], x.device)
-    y = _dw_result(out, y_shape, x, "out")
+    y = _dw_result(out, y_shape, x, "out", x.dtype)
     if y.numel() == 0 or x.numel() == 0:
         return y
+    tail = (*geom, *_dw_strides(x.shape, _dw_channels_last(x)), *_dw_strides(y.shape, _dw_channels_last(y)), DW_KINDS[kind],
+            _stream(x.device))
     with _on(x.device):
-        _lib.call("qt_dwconv2d_f32", _p(x), _p(w), _p(bias), _p(y), *geom, *_dw_strides(x.shape, _dw_channels_last(x)),
-                  *_dw_strides(y.shape, _dw_channels_last(y)), DW_KINDS[kind], _stream(x.device))
+        if codes is None:
+            _lib.call("qt_dwconv2d_f32", _p(x), _p(w), _p(bias), _p(y), *tail)
+        else:
+            _lib.call("qt_dwconv2d_h", _p(x), codes[0], _p(w), codes[1], _p(bias), _p(y), *tail)
     return y
 
 
@@ -4380,23 +4404,29 @@ def depthwise_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_output: 
                                 kind: str = "raw", channels_last: Optional[bool] = None,
                                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Gradient of ``depthwise_conv2d`` with respect to x: a gather over the multiplier index (outermost) and the taps (row-major)
-    with the forward's arithmetic rules, no atomics (qt_dwconv2d_grad_input_f32).  The result has the layout of
-    ``grad_output`` unless ``channels_last`` says otherwise, or is written into ``out``."""
-    w, geom, y_shape = _dw_geometry(input_shape, weight, stride, padding, dilation)
-    go = _dw_operand(grad_output, "grad_output", y_shape)
+    with the forward's arithmetic rules, no atomics (qt_dwconv2d_grad_input_f32; qt_dwconv2d_grad_input_h for a bf16 / fp16
+    ``grad_output``, whose dtype the result then has).  The result has the layout of ``grad_output`` unless ``channels_last`` says
+    otherwise, or is written into ``out``."""
+    w, geom, y_shape = _dw_geometry(input_shape, weight, stride, padding, dilation, half=True)
+    go = _dw_operand(grad_output, "grad_output", y_shape, half=True)
+    codes = _dw_half_codes(go, w)
     if out is None:
         cl = _dw_channels_last(go) if channels_last is None else bool(channels_last)
-        gx = torch.empty(tuple(input_shape), dtype=torch.float32, device=go.device,
+        gx = torch.empty(tuple(input_shape), dtype=go.dtype, device=go.device,
                          memory_format=torch.channels_last if cl else torch.contiguous_format)
     else:
-        gx = _dw_result(out, input_shape, go, "out")
+        gx = _dw_result(out, input_shape, go, "out", go.dtype)
     if gx.numel() == 0:
         return gx
     if go.numel() == 0:
         return gx.zero_()
+    tail = (*geom, *_dw_strides(go.shape, _dw_channels_last(go)), *_dw_strides(gx.shape, _dw_channels_last(gx)), DW_KINDS[kind],
+            _stream(go.device))
     with _on(go.device):
-        _lib.call("qt_dwconv2d_grad_input_f32", _p(go), _p(w), _p(gx), *geom, *_dw_strides(go.shape, _dw_channels_last(go)),
-                  *_dw_strides(gx.shape, _dw_channels_last(gx)), DW_KINDS[kind], _stream(go.device))
+        if codes is None:
+            _lib.call("qt_dwconv2d_grad_input_f32", _p(go), _p(w), _p(gx), *tail)
+        else:
+            _lib.call("qt_dwconv2d_grad_input_h", _p(go), codes[0], _p(w), codes[1], _p(gx), *tail)
     return gx
 
 
@@ -4418,26 +4448,28 @@ def depthwise_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, wei
     the per-channel sum of ``grad_output`` from the same pass (else None): ``(grad_weight, grad_bias)``.  Two launches inside one
     call, no atomics: partials per (split, channel, tap) into ``workspace`` (``depthwise_grad_weight_work_floats`` fp32 elements;
     allocated when not given), then the splits in index order; equal inputs give equal bits.  ``ste_threshold`` > 0 zeroes the
-    entries where the UNquantised ``|weight|`` exceeds it (1.001 for the sign families)."""
-    x = _dw_operand(x, "input")
-    w, geom, y_shape = _dw_geometry(x.shape, weight, stride, padding, dilation)
-    go = _dw_operand(grad_output, "grad_output", y_shape)
+    entries where the UNquantised ``|weight|`` exceeds it (1.001 for the sign families).  bf16 / fp16 ``x`` and ``grad_output`` (one
+    dtype) run qt_dwconv2d_grad_weight_h; both gradients have the WEIGHT's dtype (fp32 under autocast), rounded once from fp32."""
+    x = _dw_operand(x, "input", half=True)
+    w, geom, y_shape = _dw_geometry(x.shape, weight, stride, padding, dilation, half=True)
+    go = _dw_operand(grad_output, "grad_output", y_shape, half=True)
     if go.device != x.device:
         raise ValueError("input and grad_output are on different devices")
+    codes = _dw_half_codes(x, w, go)
     Cout, kk = y_shape[1], geom[5] * geom[6]
     if out is None:
-        gw = torch.empty(tuple(weight.shape), dtype=torch.float32, device=x.device)
+        gw = torch.empty(tuple(weight.shape), dtype=w.dtype, device=x.device)
     else:
-        gw = _require(out, "out")
+        gw = _require(out, "out", w.dtype)
         if tuple(gw.shape) != tuple(weight.shape) or not gw.is_contiguous() or gw.device != x.device:
-            raise ValueError(f"out: expected a contiguous fp32 tensor of shape {tuple(weight.shape)} on {x.device}")
+            raise ValueError(f"out: expected a contiguous {w.dtype} tensor of shape {tuple(weight.shape)} on {x.device}")
     gb = None
     if out_bias is not None:
-        gb = _require(out_bias, "out_bias")
+        gb = _require(out_bias, "out_bias", w.dtype)
         if tuple(gb.shape) != (Cout,) or not gb.is_contiguous() or gb.device != x.device:
-            raise ValueError(f"out_bias: expected a contiguous fp32 tensor of shape ({Cout},) on {x.device}")
+            raise ValueError(f"out_bias: expected a contiguous {w.dtype} tensor of shape ({Cout},) on {x.device}")
     elif want_bias:
-        gb = torch.empty((Cout,), dtype=torch.float32, device=x.device)
+        gb = torch.empty((Cout,), dtype=w.dtype, device=x.device)
     if gw.numel() == 0:
         return gw, gb
     if go.numel() == 0 or x.numel() == 0:
@@ -4450,10 +4482,13 @@ def depthwise_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, wei
         _require(workspace, "workspace")
         if not workspace.is_contiguous() or workspace.device != x.device or workspace.numel() < need:
             raise ValueError(f"workspace: expected at least {need} contiguous fp32 elements on {x.device}")
+    tail = (_p(workspace), int(workspace.numel()), *geom, *_dw_strides(go.shape, _dw_channels_last(go)),
+            *_dw_strides(x.shape, _dw_channels_last(x)), float(ste_threshold), _stream(x.device))
     with _on(x.device):
-        _lib.call("qt_dwconv2d_grad_weight_f32", _p(go), _p(x), _p(w), _p(gw), _p(gb), _p(workspace), int(workspace.numel()), *geom,
-                  *_dw_strides(go.shape, _dw_channels_last(go)), *_dw_strides(x.shape, _dw_channels_last(x)), float(ste_threshold),
-                  _stream(x.device))
+        if codes is None:
+            _lib.call("qt_dwconv2d_grad_weight_f32", _p(go), _p(x), _p(w), _p(gw), _p(gb), *tail)
+        else:
+            _lib.call("qt_dwconv2d_grad_weight_h", _p(go), _p(x), codes[0], _p(w), _p(gw), _p(gb), codes[1], *tail)
     return gw, gb
 
 
@@ -4491,8 +4526,8 @@ def grouped_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> b
     return N * C * H * W < 1 << 31 and N * Cout * Ho * Wo < 1 << 31
 
 
-def _gc_geometry(x_shape, weight, stride, padding, dilation, groups):
-    _require(weight, "weight")
+def _gc_geometry(x_shape, weight, stride, padding, dilation, groups, half: bool = False):
+    _require_packable(weight, "weight") if half else _require(weight, "weight")
     N, C, H, W = (int(v) for v in x_shape)
     G = int(groups)
     if weight.dim() != 4 or G < 1 or C != G * int(weight.shape[1]) or weight.shape[0] % G != 0 or weight.shape[0] < G:
@@ -4514,16 +4549,22 @@ def grouped_conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
     weight [G * cout_g, cin_g, kh, kw]; Q = ``kind`` ("raw" | "binary" | "ternary") is applied to the taps inside the one launch
     (qt_gconv2d_f32).  The result has the layout of x, or is written into ``out``.  Bit-reproducible: +0 start, the group's input
     channels ascending and the taps in row-major order inside each, one multiply and one add per term, out-of-image taps skipped,
-    bias last."""
-    x = _dw_operand(x, "input")
-    w, geom, y_shape = _gc_geometry(x.shape, weight, stride, padding, dilation, groups)
+    bias last.  A bf16 / fp16 ``x`` (with a weight of the same dtype, or fp32 as under autocast; ``bias`` stays an fp32 vector) runs
+    qt_gconv2d_h: the same fp32 arithmetic on the exactly upcast elements, rounded once to nearest even into a result of x's dtype."""
+    x = _dw_operand(x, "input", half=True)
+    w, geom, y_shape = _gc_geometry(x.shape, weight, stride, padding, dilation, groups, half=True)
+    codes = _dw_half_codes(x, w)
     bias = _check_bias(bias, y_shape[1], x.device)
-    y = _dw_result(out, y_shape, x, "out")
+    y = _dw_result(out, y_shape, x, "out", x.dtype)
     if y.numel() == 0 or x.numel() == 0:
         return y
+    tail = (*geom, *_dw_strides(x.shape, _dw_channels_last(x)), *_dw_strides(y.shape, _dw_channels_last(y)), DW_KINDS[kind],
+            _stream(x.device))
     with _on(x.device):
-        _lib.call("qt_gconv2d_f32", _p(x), _p(w), _p(bias), _p(y), *geom, *_dw_strides(x.shape, _dw_channels_last(x)),
-                  *_dw_strides(y.shape, _dw_channels_last(y)), DW_KINDS[kind], _stream(x.device))
+        if codes is None:
+            _lib.call("qt_gconv2d_f32", _p(x), _p(w), _p(bias), _p(y), *tail)
+        else:
+            _lib.call("qt_gconv2d_h", _p(x), codes[0], _p(w), codes[1], _p(bias), _p(y), *tail)
     return y
 
 
@@ -4698,23 +4739,29 @@ def grouped_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_output: to
                               groups: int = 1, kind: str = "raw", channels_last: Optional[bool] = None,
                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Gradient of ``grouped_conv2d`` with respect to x: a gather over the group's output channels (outermost) and the taps
-    (row-major) with the forward's arithmetic rules, no atomics (qt_gconv2d_grad_input_f32).  The result has the layout of
-    ``grad_output`` unless ``channels_last`` says otherwise, or is written into ``out``."""
-    w, geom, y_shape = _gc_geometry(input_shape, weight, stride, padding, dilation, groups)
-    go = _dw_operand(grad_output, "grad_output", y_shape)
+    (row-major) with the forward's arithmetic rules, no atomics (qt_gconv2d_grad_input_f32; qt_gconv2d_grad_input_h for a bf16 /
+    fp16 ``grad_output``, whose dtype the result then has).  The result has the layout of ``grad_output`` unless ``channels_last``
+    says otherwise, or is written into ``out``."""
+    w, geom, y_shape = _gc_geometry(input_shape, weight, stride, padding, dilation, groups, half=True)
+    go = _dw_operand(grad_output, "grad_output", y_shape, half=True)
+    codes = _dw_half_codes(go, w)
     if out is None:
         cl = _dw_channels_last(go) if channels_last is None else bool(channels_last)
-        gx = torch.empty(tuple(input_shape), dtype=torch.float32, device=go.device,
+        gx = torch.empty(tuple(input_shape), dtype=go.dtype, device=go.device,
                          memory_format=torch.channels_last if cl else torch.contiguous_format)
     else:
-        gx = _dw_result(out, input_shape, go, "out")
+        gx = _dw_result(out, input_shape, go, "out", go.dtype)
     if gx.numel() == 0:
         return gx
     if go.numel() == 0:
         return gx.zero_()
+    tail = (*geom, *_dw_strides(go.shape, _dw_channels_last(go)), *_dw_strides(gx.shape, _dw_channels_last(gx)), DW_KINDS[kind],
+            _stream(go.device))
     with _on(go.device):
-        _lib.call("qt_gconv2d_grad_input_f32", _p(go), _p(w), _p(gx), *geom, *_dw_strides(go.shape, _dw_channels_last(go)),
-                  *_dw_strides(gx.shape, _dw_channels_last(gx)), DW_KINDS[kind], _stream(go.device))
+        if codes is None:
+            _lib.call("qt_gconv2d_grad_input_f32", _p(go), _p(w), _p(gx), *tail)
+        else:
+            _lib.call("qt_gconv2d_grad_input_h", _p(go), codes[0], _p(w), codes[1], _p(gx), *tail)
     return gx
 
 
@@ -4739,26 +4786,28 @@ def grouped_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, weigh
     no atomics: partials per (split, output channel, input channel of the group, tap) into ``workspace``
     (``grouped_grad_weight_work_floats`` fp32 elements; allocated when not given), then the splits in index order; equal inputs
     give equal bits.  ``ste_threshold`` > 0 zeroes the entries where the UNquantised ``|weight|`` exceeds it (1.001 for the sign
-    families)."""
-    x = _dw_operand(x, "input")
-    w, geom, y_shape = _gc_geometry(x.shape, weight, stride, padding, dilation, groups)
-    go = _dw_operand(grad_output, "grad_output", y_shape)
+    families).  bf16 / fp16 ``x`` and ``grad_output`` (one dtype) run qt_gconv2d_grad_weight_h; both gradients have the WEIGHT's
+    dtype (fp32 under autocast), rounded once from fp32."""
+    x = _dw_operand(x, "input", half=True)
+    w, geom, y_shape = _gc_geometry(x.shape, weight, stride, padding, dilation, groups, half=True)
+    go = _dw_operand(grad_output, "grad_output", y_shape, half=True)
     if go.device != x.device:
         raise ValueError("input and grad_output are on different devices")
+    codes = _dw_half_codes(x, w, go)
     Cout = y_shape[1]
     if out is None:
-        gw = torch.empty(tuple(weight.shape), dtype=torch.float32, device=x.device)
+        gw = torch.empty(tuple(weight.shape), dtype=w.dtype, device=x.device)
     else:
-        gw = _require(out, "out")
+        gw = _require(out, "out", w.dtype)
         if tuple(gw.shape) != tuple(weight.shape) or not gw.is_contiguous() or gw.device != x.device:
-            raise ValueError(f"out: expected a contiguous fp32 tensor of shape {tuple(weight.shape)} on {x.device}")
+            raise ValueError(f"out: expected a contiguous {w.dtype} tensor of shape {tuple(weight.shape)} on {x.device}")
     gb = None
     if out_bias is not None:
-        gb = _require(out_bias, "out_bias")
+        gb = _require(out_bias, "out_bias", w.dtype)
         if tuple(gb.shape) != (Cout,) or not gb.is_contiguous() or gb.device != x.device:
-            raise ValueError(f"out_bias: expected a contiguous fp32 tensor of shape ({Cout},) on {x.device}")
+            raise ValueError(f"out_bias: expected a contiguous {w.dtype} tensor of shape ({Cout},) on {x.device}")
     elif want_bias:
-        gb = torch.empty((Cout,), dtype=torch.float32, device=x.device)
+        gb = torch.empty((Cout,), dtype=w.dtype, device=x.device)
     if gw.numel() == 0:
         return gw, gb
     if go.numel() == 0 or x.numel() == 0:
@@ -4771,10 +4820,13 @@ def grouped_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, weigh
         _require(workspace, "workspace")
         if not workspace.is_contiguous() or workspace.device != x.device or workspace.numel() < need:
             raise ValueError(f"workspace: expected at least {need} contiguous fp32 elements on {x.device}")
+    tail = (_p(workspace), int(workspace.numel()), *geom, *_dw_strides(go.shape, _dw_channels_last(go)),
+            *_dw_strides(x.shape, _dw_channels_last(x)), float(ste_threshold), _stream(x.device))
     with _on(x.device):
-        _lib.call("qt_gconv2d_grad_weight_f32", _p(go), _p(x), _p(w), _p(gw), _p(gb), _p(workspace), int(workspace.numel()), *geom,
-                  *_dw_strides(go.shape, _dw_channels_last(go)), *_dw_strides(x.shape, _dw_channels_last(x)), float(ste_threshold),
-                  _stream(x.device))
+        if codes is None:
+            _lib.call("qt_gconv2d_grad_weight_f32", _p(go), _p(x), _p(w), _p(gw), _p(gb), *tail)
+        else:
+            _lib.call("qt_gconv2d_grad_weight_h", _p(go), _p(x), codes[0], _p(w), _p(gw), _p(gb), codes[1], *tail)
     return gw, gb
 
 
