@@ -18,7 +18,7 @@ import contextlib
 import threading
 import weakref
 from collections import Counter
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
@@ -894,15 +894,51 @@ def packed_depthwise_conv2d(layer, act):
     """Eval-mode BinConv2d / TerConv2d with ``groups == in_channels`` on a PackedActivation (NHWC bit planes): the fp32
     [N, C * m, Ho, Wo] result in NCHW storage, bias added, from one launch on the planes (ops.depthwise_conv2d_from_bits) — what a
     deferred depthwise conv whose input exists only as planes materialises to.  The stored eval image is multiplied as it is."""
+    return _packed_streaming_conv2d(_DEPTHWISE, layer, act)
+
+
+def _depthwise_admission(layer, act, what: str) -> None:
+    if (layer.padding_mode != "zeros" or len(act.shape) != 4
+            or not ops.depthwise_applicable(act.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups)):
+        raise ValueError(f"{what} needs groups == in_channels, numeric zero padding and a shape inside the kernels' limits")
+
+
+def _grouped_planes_admission(layer, act, what: str) -> None:
+    if (layer.padding_mode != "zeros" or len(act.shape) != 4 or layer.groups < GROUPED_MIN_GROUPS
+            or not ops.grouped_planes_applicable(act.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups)):
+        raise ValueError(f"{what} needs at least {GROUPED_MIN_GROUPS} groups of 2, 4 or 8 input channels, numeric zero "
+                         "padding and a shape inside the kernels' limits")
+    if not layer._eval_on_grid():
+        raise ValueError(f"{what} needs an eval-mode weight on the quantiser's grid")
+
+
+def _grouped_codes_admission(layer, act, what: str) -> None:
+    cin_g = int(layer.weight.shape[1])
+    if (layer.padding_mode != "zeros" or len(act.shape) != 4 or layer.groups < GROUPED_MIN_GROUPS or not 2 <= cin_g <= GROUPED_MAX_CIN_G
+            or not ops.grouped_codes_applicable(act.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups)):
+        raise ValueError(f"{what} needs at least {GROUPED_MIN_GROUPS} groups of 2 ... {GROUPED_MAX_CIN_G} input channels, "
+                         "numeric zero padding and a shape inside the kernels' limits")
+
+
+def _packed_streaming_conv2d(fam, layer, act):
+    """A deferred streaming conv (``fam``: ``_DEPTHWISE`` | ``_GROUPED``) materialised from the bit planes of its input."""
     if layer.training:
         raise RuntimeError("PackedActivation inputs are an inference feature: call .eval() first")
     if act.planes is None:
-        raise ValueError("a depthwise conv reads bit planes; this activation was produced as another conv's nibble operand")
-    if (layer.padding_mode != "zeros" or len(act.shape) != 4
-            or not ops.depthwise_applicable(act.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups)):
-        raise ValueError("packed depthwise conv needs groups == in_channels, numeric zero padding and a shape inside the kernels' limits")
-    return ops.depthwise_conv2d_from_bits(act.planes, act.shape, layer.weight.detach(), layer.bias, layer.stride, layer.padding,
-                                          layer.dilation, kind="raw")
+        raise ValueError(f"a {fam.ops_family.noun} conv reads bit planes; this activation was produced as another conv's nibble operand")
+    fam.planes_admission(layer, act, f"packed {fam.ops_family.noun} conv")
+    return ops._streaming_conv2d_from_bits(fam.ops_family, act.planes, act.shape, layer.weight.detach(), layer.bias, layer.stride,
+                                           layer.padding, layer.dilation, layer.groups, "raw")
+
+
+def _codes_streaming_conv2d(fam, layer, act):
+    """A deferred streaming DoReFa conv materialised from the code plane of its input."""
+    if layer.training:
+        raise RuntimeError("CodeActivation inputs are an inference feature: call .eval() first")
+    fam.codes_admission(layer, act, f"{fam.ops_family.noun} conv on codes")
+    return ops._streaming_conv2d_from_codes(fam.ops_family, act.codes, act.shape, layer.weight.detach(), layer.bias, layer.stride,
+                                            layer.padding, layer.dilation, layer.groups, in_halo=act.halo,
+                                            channels_last=bool(act.source_channels_last), flagged=not ops._cfg("ASSUME_CODES_FIT"))
 
 
 def codes_depthwise_conv2d(layer, act):
@@ -911,32 +947,14 @@ def codes_depthwise_conv2d(layer, act):
     on the code plane (ops.depthwise_conv2d_from_codes) — what a
     deferred depthwise DoReFa conv materialises to when its chain cannot run fused.  The stored eval image is multiplied as it is;
     a raised int8 range flag of the activation's chain makes the result NaN on the device (as ``CodeActivation.float``)."""
-    if layer.training:
-        raise RuntimeError("CodeActivation inputs are an inference feature: call .eval() first")
-    if (layer.padding_mode != "zeros" or len(act.shape) != 4
-            or not ops.depthwise_applicable(act.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups)):
-        raise ValueError("depthwise conv on codes needs groups == in_channels, numeric zero padding and a shape inside the kernels' limits")
-    return ops.depthwise_conv2d_from_codes(act.codes, act.shape, layer.weight.detach(), layer.bias, layer.stride, layer.padding,
-                                           layer.dilation, in_halo=act.halo, channels_last=bool(act.source_channels_last),
-                                           flagged=not ops._cfg("ASSUME_CODES_FIT"))
+    return _codes_streaming_conv2d(_DEPTHWISE, layer, act)
 
 
 def packed_grouped_conv2d(layer, act):
     """Eval-mode BinConv2d / TerConv2d with ``1 < groups < in_channels`` on a PackedActivation (NHWC bit planes): the fp32
     [N, G * cout_g, Ho, Wo] result in NCHW storage, bias added, from one launch on the planes (ops.grouped_conv2d_from_bits) — what a
     deferred grouped conv whose input exists only as planes materialises to.  The stored eval image is classified by its sign."""
-    if layer.training:
-        raise RuntimeError("PackedActivation inputs are an inference feature: call .eval() first")
-    if act.planes is None:
-        raise ValueError("a grouped conv reads bit planes; this activation was produced as another conv's nibble operand")
-    if (layer.padding_mode != "zeros" or len(act.shape) != 4 or layer.groups < GROUPED_MIN_GROUPS
-            or not ops.grouped_planes_applicable(act.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups)):
-        raise ValueError(f"packed grouped conv needs at least {GROUPED_MIN_GROUPS} groups of 2, 4 or 8 input channels, numeric zero "
-                         "padding and a shape inside the kernels' limits")
-    if not layer._eval_on_grid():
-        raise ValueError("packed grouped conv needs an eval-mode weight on the quantiser's grid")
-    return ops.grouped_conv2d_from_bits(act.planes, act.shape, layer.weight.detach(), layer.bias, layer.stride, layer.padding,
-                                        layer.dilation, layer.groups, kind="raw")
+    return _packed_streaming_conv2d(_GROUPED, layer, act)
 
 
 def codes_grouped_conv2d(layer, act):
@@ -945,16 +963,7 @@ def codes_grouped_conv2d(layer, act):
     (``CodeActivation.source_channels_last``), bias added, from one launch on the code plane (ops.grouped_conv2d_from_codes); what a
     deferred grouped DoReFa conv materialises to when its chain cannot run fused.  The stored eval image is multiplied as it is; a
     raised int8 range flag of the activation's chain makes the result NaN on the device."""
-    if layer.training:
-        raise RuntimeError("CodeActivation inputs are an inference feature: call .eval() first")
-    cin_g = int(layer.weight.shape[1])
-    if (layer.padding_mode != "zeros" or len(act.shape) != 4 or layer.groups < GROUPED_MIN_GROUPS or not 2 <= cin_g <= GROUPED_MAX_CIN_G
-            or not ops.grouped_codes_applicable(act.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups)):
-        raise ValueError(f"grouped conv on codes needs at least {GROUPED_MIN_GROUPS} groups of 2 ... {GROUPED_MAX_CIN_G} input channels, "
-                         "numeric zero padding and a shape inside the kernels' limits")
-    return ops.grouped_conv2d_from_codes(act.codes, act.shape, layer.weight.detach(), layer.bias, layer.stride, layer.padding,
-                                         layer.dilation, layer.groups, in_halo=act.halo,
-                                         channels_last=bool(act.source_channels_last), flagged=not ops._cfg("ASSUME_CODES_FIT"))
+    return _codes_streaming_conv2d(_GROUPED, layer, act)
 
 
 def packed_xnor_conv2d(layer, act, epi=None):
@@ -2016,6 +2025,53 @@ def _streaming_grad_output(grad_output: torch.Tensor, input: torch.Tensor) -> to
     return go if go.dtype == input.dtype else go.to(input.dtype)
 
 
+class _StreamingFamily(NamedTuple):
+    """One family of streaming convs as this module uses it: the descriptor the shared bodies of ``ops`` take (they are called
+    directly, with ``groups`` in its place: the depthwise family does not look at it), and what admits a layer to the
+    materialising helpers (``(layer, act, what)``: raises the family's ValueError).  The autograd bodies, the two helpers' bodies
+    and these two instances are all there is per family here: a new operation is written once."""
+    ops_family: ops._Streaming
+    planes_admission: Callable
+    codes_admission: Callable
+
+
+_DEPTHWISE = _StreamingFamily(ops._DW, _depthwise_admission, _depthwise_admission)
+_GROUPED = _StreamingFamily(ops._GC, _grouped_planes_admission, _grouped_codes_admission)
+
+
+def _streaming_forward(fam: _StreamingFamily, ctx, input, weight, bias, kind, weight_q, ste, conv_args):
+    stride, padding, dilation, groups = conv_args
+    ctx.kind = kind if weight_q is None else "raw"
+    ctx.conv_args, ctx.ste, ctx.has_bias = conv_args, float(ste), bias is not None
+    ctx.bias_dtype = bias.dtype if bias is not None else None
+    input = _dense(input)
+    ctx.save_for_backward(input, weight, weight_q)
+    if input.dtype in ops.HALF_DTYPES:      # the "_h" entries add an fp32 bias vector before their one rounding
+        bias = half_bias(bias, input.dtype)
+    return ops._streaming_conv2d(fam.ops_family, input, weight if weight_q is None else weight_q, bias, stride, padding, dilation, groups,
+                                 ctx.kind)
+
+
+def _streaming_backward(fam: _StreamingFamily, ctx, grad_output):
+    input, weight, weight_q = ctx.saved_tensors
+    stride, padding, dilation, groups = ctx.conv_args
+    go = _streaming_grad_output(grad_output, input)
+    grad_input = grad_weight = grad_bias = None
+    if ctx.needs_input_grad[0]:
+        grad_input = ops._streaming_conv2d_grad_input(
+            fam.ops_family, input.shape, weight if weight_q is None else weight_q, go, stride, padding, dilation, groups, ctx.kind,
+            input.is_contiguous(memory_format=torch.channels_last) and not input.is_contiguous())          # channels_last
+    want_bias = ctx.has_bias and ctx.needs_input_grad[2]
+    if ctx.needs_input_grad[1] or want_bias:
+        grad_weight, grad_bias = ops._streaming_conv2d_grad_weight(fam.ops_family, input, go, weight, stride, padding, dilation, groups,
+                                                                   ctx.ste, want_bias)
+        if not ctx.needs_input_grad[1]:
+            grad_weight = None
+    if grad_bias is not None and grad_bias.dtype != ctx.bias_dtype:
+        grad_bias = grad_bias.to(ctx.bias_dtype)
+    return grad_input, grad_weight, grad_bias, None, None, None, None
+
+
 #: routes taken by ``depthwise_half_route`` / ``grouped_half_route`` layers, by family ("depthwise" | "grouped"); the tests read it
 STREAMING_HALF_STATS: Counter = Counter()
 
@@ -2039,6 +2095,12 @@ def _streaming_half_common(layer, input) -> bool:
             and not isinstance(layer.padding, str))
 
 
+def _streaming_f32_common(layer, input) -> bool:
+    """What both fp32 routes ask: a 4-D fp32 device tensor, an fp32 weight, padding mode "zeros"."""
+    return (isinstance(input, torch.Tensor) and input.is_cuda and input.dtype == torch.float32 and input.dim() == 4
+            and layer.weight.dtype == torch.float32 and layer.padding_mode == "zeros")
+
+
 def depthwise_half_route(layer, input) -> bool:
     """``depthwise_route`` for a bf16 / fp16 activation: the "_h" streaming kernels, switched by ``DEPTHWISE_HALF``.  As on fp32
     nothing asks whether the activation is +-1."""
@@ -2058,8 +2120,7 @@ def grouped_half_route(layer, input) -> bool:
 def depthwise_route(layer, input) -> bool:
     """``layer`` (a Conv2d subclass with an fp32 weight) applied to ``input`` is a depthwise conv the HIP kernels take: a 4-D fp32
     device tensor, ``groups == in_channels > 1``, padding mode "zeros" with numeric padding."""
-    return (isinstance(input, torch.Tensor) and input.is_cuda and input.dtype == torch.float32 and input.dim() == 4
-            and layer.weight.dtype == torch.float32 and layer.groups > 1 and layer.padding_mode == "zeros"
+    return (_streaming_f32_common(layer, input) and layer.groups > 1
             and ops.depthwise_applicable(input.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups))
 
 
@@ -2072,36 +2133,11 @@ class DepthwiseConv2dFn(QtFunction):
 
     @staticmethod
     def forward(ctx, input, weight, bias, kind, weight_q, ste, conv_args):
-        stride, padding, dilation, _groups = conv_args
-        ctx.kind = kind if weight_q is None else "raw"
-        ctx.conv_args, ctx.ste, ctx.has_bias = conv_args, float(ste), bias is not None
-        ctx.bias_dtype = bias.dtype if bias is not None else None
-        input = _dense(input)
-        ctx.save_for_backward(input, weight, weight_q)
-        if input.dtype in ops.HALF_DTYPES:      # the "_h" entries add an fp32 bias vector before their one rounding
-            bias = half_bias(bias, input.dtype)
-        return ops.depthwise_conv2d(input, weight if weight_q is None else weight_q, bias, stride, padding, dilation, kind=ctx.kind)
+        return _streaming_forward(_DEPTHWISE, ctx, input, weight, bias, kind, weight_q, ste, conv_args)
 
     @staticmethod
     def backward(ctx, grad_output):
-        input, weight, weight_q = ctx.saved_tensors
-        stride, padding, dilation, _groups = ctx.conv_args
-        go = _streaming_grad_output(grad_output, input)
-        grad_input = grad_weight = grad_bias = None
-        if ctx.needs_input_grad[0]:
-            grad_input = ops.depthwise_conv2d_grad_input(input.shape, weight if weight_q is None else weight_q, go, stride, padding,
-                                                         dilation, kind=ctx.kind,
-                                                         channels_last=input.is_contiguous(memory_format=torch.channels_last)
-                                                         and not input.is_contiguous())
-        want_bias = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1] or want_bias:
-            grad_weight, grad_bias = ops.depthwise_conv2d_grad_weight(input, go, weight, stride, padding, dilation,
-                                                                      ste_threshold=ctx.ste, want_bias=want_bias)
-            if not ctx.needs_input_grad[1]:
-                grad_weight = None
-        if grad_bias is not None and grad_bias.dtype != ctx.bias_dtype:
-            grad_bias = grad_bias.to(ctx.bias_dtype)
-        return grad_input, grad_weight, grad_bias, None, None, None, None
+        return _streaming_backward(_DEPTHWISE, ctx, grad_output)
 
 
 # ---- grouped convs with a few channels per group -----------------------------------------------------------------------------------
@@ -2121,8 +2157,7 @@ def grouped_route(layer, input) -> bool:
     """``layer`` (a Conv2d subclass with an fp32 weight) applied to ``input`` is a grouped conv the HIP kernels take: a 4-D fp32
     device tensor, ``groups >= GROUPED_MIN_GROUPS`` with 2 ... ``GROUPED_MAX_CIN_G`` input channels each, padding mode "zeros"
     with numeric padding."""
-    return (isinstance(input, torch.Tensor) and input.is_cuda and input.dtype == torch.float32 and input.dim() == 4
-            and layer.weight.dtype == torch.float32 and layer.groups >= GROUPED_MIN_GROUPS and layer.padding_mode == "zeros"
+    return (_streaming_f32_common(layer, input) and layer.groups >= GROUPED_MIN_GROUPS
             and 2 <= int(layer.weight.shape[1]) <= GROUPED_MAX_CIN_G
             and ops.grouped_applicable(input.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups))
 
@@ -2134,36 +2169,11 @@ class GroupedConv2dFn(QtFunction):
 
     @staticmethod
     def forward(ctx, input, weight, bias, kind, weight_q, ste, conv_args):
-        stride, padding, dilation, groups = conv_args
-        ctx.kind = kind if weight_q is None else "raw"
-        ctx.conv_args, ctx.ste, ctx.has_bias = conv_args, float(ste), bias is not None
-        ctx.bias_dtype = bias.dtype if bias is not None else None
-        input = _dense(input)
-        ctx.save_for_backward(input, weight, weight_q)
-        if input.dtype in ops.HALF_DTYPES:      # the "_h" entries add an fp32 bias vector before their one rounding
-            bias = half_bias(bias, input.dtype)
-        return ops.grouped_conv2d(input, weight if weight_q is None else weight_q, bias, stride, padding, dilation, groups, kind=ctx.kind)
+        return _streaming_forward(_GROUPED, ctx, input, weight, bias, kind, weight_q, ste, conv_args)
 
     @staticmethod
     def backward(ctx, grad_output):
-        input, weight, weight_q = ctx.saved_tensors
-        stride, padding, dilation, groups = ctx.conv_args
-        go = _streaming_grad_output(grad_output, input)
-        grad_input = grad_weight = grad_bias = None
-        if ctx.needs_input_grad[0]:
-            grad_input = ops.grouped_conv2d_grad_input(input.shape, weight if weight_q is None else weight_q, go, stride, padding,
-                                                       dilation, groups, kind=ctx.kind,
-                                                       channels_last=input.is_contiguous(memory_format=torch.channels_last)
-                                                       and not input.is_contiguous())
-        want_bias = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1] or want_bias:
-            grad_weight, grad_bias = ops.grouped_conv2d_grad_weight(input, go, weight, stride, padding, dilation, groups,
-                                                                    ste_threshold=ctx.ste, want_bias=want_bias)
-            if not ctx.needs_input_grad[1]:
-                grad_weight = None
-        if grad_bias is not None and grad_bias.dtype != ctx.bias_dtype:
-            grad_bias = grad_bias.to(ctx.bias_dtype)
-        return grad_input, grad_weight, grad_bias, None, None, None, None
+        return _streaming_backward(_GROUPED, ctx, grad_output)
 
 
 def grouped_quant_conv(layer, input, kind: str, quant_op):

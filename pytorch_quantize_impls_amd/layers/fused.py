@@ -481,7 +481,69 @@ class FusedDorefaConvBnQuant(torch.nn.Module):
                                              conv.padding_mode, scale=E, epi=epi)
 
 
-class FusedDepthwiseDorefaBnQuant(torch.nn.Module):
+def _admit_depthwise(conv) -> None:
+    """What both fused depthwise blocks ask of their conv."""
+    if conv.groups != conv.in_channels or conv.groups <= 1 or conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+        raise ValueError("only groups == in_channels > 1, zero-padded convs with numeric padding can be fused")
+
+
+class _FusedStreamingDorefaBnQuant(torch.nn.Module):
+    """What ``FusedDepthwiseDorefaBnQuant`` and ``FusedGroupedDorefaBnQuant`` share — all but which convs they admit and which
+    ``ops`` entry runs them.  A subclass supplies ``_noun`` (its name in the messages), ``_admit(conv)`` (raises ValueError for a conv
+    that is not the family's), ``_applicable`` (the shape predicate of ``ops``), ``_conv2d_codes`` (the ``ops`` wrapper) and
+    ``_takes_groups`` (that wrapper has a ``groups`` argument behind ``dilation``)."""
+
+    def __init__(self, conv, bn, bit_width: int, relu=True, out_halo=0, fold=None):
+        super().__init__()
+        from .dorefa_layers import DorefaConv2d
+        if not isinstance(conv, DorefaConv2d):
+            raise ValueError(f"{type(self).__name__} fuses a {self._noun} DorefaConv2d only")
+        self._admit(conv)
+        kh, kw = conv.kernel_size
+        dh, dw = ops._pairs(conv.dilation)
+        fits = (1, conv.in_channels, dh * (kh - 1) + 1, dw * (kw - 1) + 1)       # the smallest image the kernel fits
+        if not self._applicable(fits, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups):
+            raise ValueError(f"a {self._noun} conv outside the limits of the HIP kernels (ops.{self._applicable.__name__})")
+        if not isinstance(bn, torch.nn.BatchNorm2d) or bn.num_features != conv.out_channels:
+            raise ValueError("BatchNorm2d over the conv's output channels expected")
+        if not 2 <= int(bit_width) <= 8:
+            raise ValueError("code planes exist for 2 <= bit_width <= 8")
+        self.fold = fold or DEFAULT_FOLD
+        self.conv, self.bn, self.bit_width, self.relu = conv, bn, int(bit_width), ops.relu_mode(relu)
+        if self.relu == 2:
+            raise ValueError(f"the {self._noun} code epilogue has no ReLU in front of the BatchNorm (relu='pre')")
+        self.out_halo = (int(out_halo),) * 2 if isinstance(out_halo, int) else tuple(int(v) for v in out_halo)
+        self._folded = None
+
+    def refold(self):
+        self._folded = None
+
+    def forward(self, act, residual=None):
+        conv, name = self.conv, type(self).__name__
+        if conv.training or self.bn.training:
+            raise ValueError(f"{name} is an inference form: call .eval() first")
+        if residual is not None:
+            raise ValueError(f"the {self._noun} code epilogue takes no residual")
+        if not isinstance(act, packed.CodeActivation):
+            raise TypeError(f"{name} consumes a CodeActivation (a fused DoReFa block's output)")
+        shape = act.shape
+        if len(shape) != 4 or not self._applicable(shape, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups):
+            raise ValueError(f"not a {self._noun} conv the HIP kernels take: input {tuple(shape)}")
+        if not conv._eval_on_grid():
+            raise ValueError("the eval-mode weight is off the quantiser's grid")
+        N, _, H, W = shape
+        Ho, Wo = ops.conv_out_hw(H, W, conv.kernel_size[0], conv.kernel_size[1], conv.stride, conv.padding, conv.dilation)
+        # the tensor the module graph hands to F.batch_norm is this conv's fp32 output, which takes its input's layout
+        like = ((N, conv.out_channels, Ho, Wo), bool(act.source_channels_last)) if self.fold == "device" else None
+        folded = _code_fold_for(self, "_folded", self.bn, self.fold, like)
+        epi = ops.CodeEpilogue(folded[0], folded[1], self.bit_width, self.relu, out_halo=self.out_halo,
+                               bn_stats=folded[2] if len(folded) > 2 else None, overflow=act.codes.overflow)
+        out = self._conv2d_codes(act.codes, shape, conv.weight.detach(), conv.bias, epi, conv.stride, conv.padding, conv.dilation,
+                                 *((conv.groups,) if self._takes_groups else ()), in_halo=act.halo)
+        return packed.CodeActivation(out, (N, conv.out_channels, Ho, Wo), halo=self.out_halo)
+
+
+class FusedDepthwiseDorefaBnQuant(_FusedStreamingDorefaBnQuant):
     """Depthwise DorefaConv2d (``groups == in_channels``, eval, ANY weight bit_width whose eval image is on the quantiser's grid) ->
     BatchNorm2d(eval) [-> ReLU] -> nnDorefaQuant(k): the depthwise sibling of ``FusedDorefaConvBnQuant``.  ONE launch
     (qt_dwconv2d_codes) reads the int8 code plane of a CodeActivation (any halo: it is never read), computes the conv in the pinned
@@ -490,121 +552,33 @@ class FusedDepthwiseDorefaBnQuant(torch.nn.Module):
 
     ``fold="device"``: the BatchNorm probe has the layout the module graph's depthwise result has — channels-last for a code-plane
     input, the tensor's own layout for the code tag of an fp32 tensor (``CodeActivation.source_channels_last``)."""
-
-    def __init__(self, conv, bn, bit_width: int, relu=True, out_halo=0, fold=None):
-        super().__init__()
-        from .dorefa_layers import DorefaConv2d
-        if not isinstance(conv, DorefaConv2d):
-            raise ValueError("FusedDepthwiseDorefaBnQuant fuses a depthwise DorefaConv2d only")
-        if conv.groups != conv.in_channels or conv.groups <= 1 or conv.padding_mode != "zeros" or isinstance(conv.padding, str):
-            raise ValueError("only groups == in_channels > 1, zero-padded convs with numeric padding can be fused")
-        kh, kw = conv.kernel_size
-        dh, dw = ops._pairs(conv.dilation)
-        fits = (1, conv.in_channels, dh * (kh - 1) + 1, dw * (kw - 1) + 1)       # the smallest image the kernel fits
-        if not ops.depthwise_applicable(fits, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups):
-            raise ValueError("a depthwise conv outside the limits of the HIP kernels (ops.depthwise_applicable)")
-        if not isinstance(bn, torch.nn.BatchNorm2d) or bn.num_features != conv.out_channels:
-            raise ValueError("BatchNorm2d over the conv's output channels expected")
-        if not 2 <= int(bit_width) <= 8:
-            raise ValueError("code planes exist for 2 <= bit_width <= 8")
-        self.fold = fold or DEFAULT_FOLD
-        self.conv, self.bn, self.bit_width, self.relu = conv, bn, int(bit_width), ops.relu_mode(relu)
-        if self.relu == 2:
-            raise ValueError("the depthwise code epilogue has no ReLU in front of the BatchNorm (relu='pre')")
-        self.out_halo = (int(out_halo),) * 2 if isinstance(out_halo, int) else tuple(int(v) for v in out_halo)
-        self._folded = None
-
-    def refold(self):
-        self._folded = None
-
-    def forward(self, act, residual=None):
-        conv = self.conv
-        if conv.training or self.bn.training:
-            raise ValueError("FusedDepthwiseDorefaBnQuant is an inference form: call .eval() first")
-        if residual is not None:
-            raise ValueError("the depthwise code epilogue takes no residual")
-        if not isinstance(act, packed.CodeActivation):
-            raise TypeError("FusedDepthwiseDorefaBnQuant consumes a CodeActivation (a fused DoReFa block's output)")
-        shape = act.shape
-        if len(shape) != 4 or not ops.depthwise_applicable(shape, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups):
-            raise ValueError(f"not a depthwise conv the HIP kernels take: input {tuple(shape)}")
-        if not conv._eval_on_grid():
-            raise ValueError("the eval-mode weight is off the quantiser's grid")
-        N, _, H, W = shape
-        Ho, Wo = ops.conv_out_hw(H, W, conv.kernel_size[0], conv.kernel_size[1], conv.stride, conv.padding, conv.dilation)
-        # the tensor the module graph hands to F.batch_norm is this conv's fp32 output, which takes its input's layout
-        like = ((N, conv.out_channels, Ho, Wo), bool(act.source_channels_last)) if self.fold == "device" else None
-        folded = _code_fold_for(self, "_folded", self.bn, self.fold, like)
-        epi = ops.CodeEpilogue(folded[0], folded[1], self.bit_width, self.relu, out_halo=self.out_halo,
-                               bn_stats=folded[2] if len(folded) > 2 else None, overflow=act.codes.overflow)
-        out = ops.depthwise_conv2d_codes(act.codes, shape, conv.weight.detach(), conv.bias, epi, conv.stride, conv.padding,
-                                         conv.dilation, in_halo=act.halo)
-        return packed.CodeActivation(out, (N, conv.out_channels, Ho, Wo), halo=self.out_halo)
+    _noun, _takes_groups = "depthwise", False
+    _applicable, _conv2d_codes = staticmethod(ops.depthwise_applicable), staticmethod(ops.depthwise_conv2d_codes)
+    _admit = staticmethod(_admit_depthwise)
 
 
-class FusedGroupedDorefaBnQuant(torch.nn.Module):
+class FusedGroupedDorefaBnQuant(_FusedStreamingDorefaBnQuant):
     """Grouped DorefaConv2d (eval; at least ``_fused.GROUPED_MIN_GROUPS`` groups of 2 ... ``_fused.GROUPED_MAX_CIN_G`` input
     channels, not depthwise; ANY weight bit_width whose eval image is on the quantiser's grid) -> BatchNorm2d(eval) [-> ReLU] ->
     nnDorefaQuant(k): the grouped sibling of ``FusedDepthwiseDorefaBnQuant``.  ONE launch (qt_gconv2d_codes) reads the int8 code plane
     of a CodeActivation (any halo: it is never read), computes the conv in the pinned fp32 order of ``ops.grouped_conv2d`` on the
     image fl(inv_n * code) with the stored weight image as it is, and writes the next layer's code plane with ``out_halo`` as its
     zero border.  No residual, no ReLU in front of the BatchNorm.  ``fold="device"`` as in the depthwise sibling."""
+    _noun, _takes_groups = "grouped", True
+    _applicable, _conv2d_codes = staticmethod(ops.grouped_codes_applicable), staticmethod(ops.grouped_conv2d_codes)
 
     def __init__(self, conv, bn, bit_width: int, relu=True, out_halo=(0, 0), fold=None):
-        super().__init__()
-        from .dorefa_layers import DorefaConv2d
+        super().__init__(conv, bn, bit_width, relu, out_halo, fold)
+
+    @staticmethod
+    def _admit(conv):
         from ..functions import _fused
-        if not isinstance(conv, DorefaConv2d):
-            raise ValueError("FusedGroupedDorefaBnQuant fuses a grouped DorefaConv2d only")
         if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
             raise ValueError("only zero-padded convs with numeric padding can be fused")
         cin_g = int(conv.weight.shape[1])
         if conv.groups < _fused.GROUPED_MIN_GROUPS or conv.groups == conv.in_channels or not 2 <= cin_g <= _fused.GROUPED_MAX_CIN_G:
             raise ValueError(f"only convs with at least {_fused.GROUPED_MIN_GROUPS} groups of 2 ... {_fused.GROUPED_MAX_CIN_G} input "
                              "channels can be fused (depthwise: FusedDepthwiseDorefaBnQuant; ungrouped: FusedDorefaConvBnQuant)")
-        kh, kw = conv.kernel_size
-        dh, dw = ops._pairs(conv.dilation)
-        fits = (1, conv.in_channels, dh * (kh - 1) + 1, dw * (kw - 1) + 1)       # the smallest image the kernel fits
-        if not ops.grouped_codes_applicable(fits, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups):
-            raise ValueError("a grouped conv outside the limits of the HIP kernels (ops.grouped_codes_applicable)")
-        if not isinstance(bn, torch.nn.BatchNorm2d) or bn.num_features != conv.out_channels:
-            raise ValueError("BatchNorm2d over the conv's output channels expected")
-        if not 2 <= int(bit_width) <= 8:
-            raise ValueError("code planes exist for 2 <= bit_width <= 8")
-        self.fold = fold or DEFAULT_FOLD
-        self.conv, self.bn, self.bit_width, self.relu = conv, bn, int(bit_width), ops.relu_mode(relu)
-        if self.relu == 2:
-            raise ValueError("the grouped code epilogue has no ReLU in front of the BatchNorm (relu='pre')")
-        self.out_halo = (int(out_halo),) * 2 if isinstance(out_halo, int) else tuple(int(v) for v in out_halo)
-        self._folded = None
-
-    def refold(self):
-        self._folded = None
-
-    def forward(self, act, residual=None):
-        conv = self.conv
-        if conv.training or self.bn.training:
-            raise ValueError("FusedGroupedDorefaBnQuant is an inference form: call .eval() first")
-        if residual is not None:
-            raise ValueError("the grouped code epilogue takes no residual")
-        if not isinstance(act, packed.CodeActivation):
-            raise TypeError("FusedGroupedDorefaBnQuant consumes a CodeActivation (a fused DoReFa block's output)")
-        shape = act.shape
-        if len(shape) != 4 or not ops.grouped_codes_applicable(shape, conv.weight.shape, conv.stride, conv.padding, conv.dilation,
-                                                               conv.groups):
-            raise ValueError(f"not a grouped conv the HIP kernels take: input {tuple(shape)}")
-        if not conv._eval_on_grid():
-            raise ValueError("the eval-mode weight is off the quantiser's grid")
-        N, _, H, W = shape
-        Ho, Wo = ops.conv_out_hw(H, W, conv.kernel_size[0], conv.kernel_size[1], conv.stride, conv.padding, conv.dilation)
-        # the tensor the module graph hands to F.batch_norm is this conv's fp32 output, which takes its input's layout
-        like = ((N, conv.out_channels, Ho, Wo), bool(act.source_channels_last)) if self.fold == "device" else None
-        folded = _code_fold_for(self, "_folded", self.bn, self.fold, like)
-        epi = ops.CodeEpilogue(folded[0], folded[1], self.bit_width, self.relu, out_halo=self.out_halo,
-                               bn_stats=folded[2] if len(folded) > 2 else None, overflow=act.codes.overflow)
-        out = ops.grouped_conv2d_codes(act.codes, shape, conv.weight.detach(), conv.bias, epi, conv.stride, conv.padding,
-                                       conv.dilation, conv.groups, in_halo=act.halo)
-        return packed.CodeActivation(out, (N, conv.out_channels, Ho, Wo), halo=self.out_halo)
 
 
 class CodeMaxPool(torch.nn.Module):
@@ -884,26 +858,25 @@ class FusedConvPoolBnSign(torch.nn.Module):
         return out
 
 
-class FusedDepthwiseBnSign(torch.nn.Module):
-    """Depthwise BinConv2d / TerConv2d (``groups == in_channels``, eval) + [MaxPool2d(k, s)] + eval BatchNorm2d + [Hardtanh] +
-    BinaryConnect(det) -> PackedActivation: the depthwise sibling of ``FusedConvPoolBnSign``.  ONE launch (qt_dwconv2d_sign) reads the
-    input — an fp32 device tensor, or the bit planes of a PackedActivation — computes the conv in the pinned fp32 order of
-    ``ops.depthwise_conv2d`` and writes the bit [y * alpha + beta < 0] as bit planes or, with ``out_nib_halo`` set, as the consuming
-    conv's nibble pixel plane with its padding as a zero border.  A pool between conv and BatchNorm runs on the un-pooled bits."""
+class _FusedStreamingBnSign(torch.nn.Module):
+    """What ``FusedDepthwiseBnSign`` and ``FusedGroupedBnSign`` share — all but which convs they admit, which ``ops`` entry runs them
+    and whether an fp32 tensor is an input.  A subclass supplies ``_noun``, ``_admit(conv)`` (raises ValueError for a conv that is not
+    the family's), ``_applicable`` (the shape predicate of ``ops``) with ``_outside`` / ``_not_taken`` (the texts for a conv and an
+    input it refuses), ``_conv2d_sign`` (the ``ops`` wrapper), ``_takes_groups`` (that wrapper has a ``groups`` argument behind
+    ``dilation``) and ``_tensor_input(x)``: ``(x, shape, channels_last)`` of an input that is no PackedActivation, or a TypeError."""
 
     def __init__(self, conv, bn, pool=None, flatten_hwc=False, fold=None):
         super().__init__()
         from .binary_layers import BinConv2d
         from .terner_layers import TerConv2d
         if not isinstance(conv, (BinConv2d, TerConv2d)):
-            raise ValueError("FusedDepthwiseBnSign fuses depthwise BinConv2d / TerConv2d only")
-        if conv.groups != conv.in_channels or conv.groups <= 1 or conv.padding_mode != "zeros" or isinstance(conv.padding, str):
-            raise ValueError("only groups == in_channels > 1, zero-padded convs with numeric padding can be fused")
+            raise ValueError(f"{type(self).__name__} fuses {self._noun} BinConv2d / TerConv2d only")
+        self._admit(conv)
         kh, kw = conv.kernel_size
         dh, dw = ops._pairs(conv.dilation)
         fits = (1, conv.in_channels, dh * (kh - 1) + 1, dw * (kw - 1) + 1)       # the smallest image the kernel fits
-        if not ops.depthwise_applicable(fits, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups):
-            raise ValueError("a depthwise conv outside the limits of the HIP kernels (ops.depthwise_applicable)")
+        if not self._applicable(fits, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups):
+            raise ValueError(self._outside)
         if not isinstance(bn, torch.nn.BatchNorm2d) or bn.num_features != conv.out_channels:
             raise ValueError("BatchNorm2d over the conv's output channels expected")
         self._pool = FusedPoolBnSign(bn, pool, fold=fold)           # validates the pooling geometry, owns the fold cache
@@ -919,19 +892,18 @@ class FusedDepthwiseBnSign(torch.nn.Module):
 
     def forward(self, x):
         if self.bn.training or self.conv.training:
-            raise RuntimeError("FusedDepthwiseBnSign is an inference module: call .eval() first")
+            raise RuntimeError(f"{type(self).__name__} is an inference module: call .eval() first")
         conv, fp = self.conv, self._pool
         x = lazy.resolve(x)
         if isinstance(x, packed.PackedActivation):
             if x.planes is None:
-                raise ValueError("a depthwise block reads bit planes; its producer was linked to hand over a nibble operand")
+                raise ValueError(f"a {self._noun} block reads bit planes; its producer was linked to hand over a nibble operand")
+            # the result takes the layout of the conv's fp32 input, here the +-1 tensor the planes stand for
             src, shape, cl = x.planes, x.shape, _out_channels_last(x)
         else:
-            if not (isinstance(x, torch.Tensor) and x.is_cuda):
-                raise TypeError("FusedDepthwiseBnSign runs on a HIP device only (use the un-fused modules on CPU)")
-            src, shape, cl = x, tuple(x.shape), ops._dw_channels_last(x)          # the depthwise result takes x's layout
-        if len(shape) != 4 or not ops.depthwise_applicable(shape, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups):
-            raise ValueError(f"not a depthwise conv the HIP kernels take: input {tuple(shape)}")
+            src, shape, cl = self._tensor_input(x)
+        if len(shape) != 4 or not self._applicable(shape, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups):
+            raise ValueError(f"{self._not_taken}: input {tuple(shape)}")
         if not conv._eval_on_grid():
             raise ValueError("the eval-mode weight is off the quantiser's grid")
         dev = conv.weight.device
@@ -948,11 +920,12 @@ class FusedDepthwiseBnSign(torch.nn.Module):
         pooled = fp.pool_k != 1 or fp.pool_s != 1
         nib_out = self.out_nib_halo is not None and not self.flatten_hwc
         Cout = conv.out_channels
-        args = (src, conv.weight.detach(), conv.bias, alpha, beta, conv.stride, conv.padding, conv.dilation)
+        args = (src, conv.weight.detach(), conv.bias, alpha, beta, conv.stride, conv.padding, conv.dilation,
+                *((conv.groups,) if self._takes_groups else ()))
         if nib_out and not pooled:
-            nib, _ = ops.depthwise_conv2d_sign(*args, kind="raw", shape=shape, out_halo=self.out_nib_halo)
+            nib, _ = self._conv2d_sign(*args, kind="raw", shape=shape, out_halo=self.out_nib_halo)
             return packed.PackedActivation(None, (N, Cout, Ho, Wo), nib=nib, halo=self.out_nib_halo)
-        planes, _ = ops.depthwise_conv2d_sign(*args, kind="raw", shape=shape)
+        planes, _ = self._conv2d_sign(*args, kind="raw", shape=shape)
         if pooled and nib_out:
             nib, (Ho, Wo) = ops.pool_bits_nib(planes, N, Ho, Wo, fp.pool_k, fp.pool_s, self._neg_alpha, self.out_nib_halo)
             return packed.PackedActivation(None, (N, Cout, Ho, Wo), nib=nib, halo=self.out_nib_halo)
@@ -962,7 +935,26 @@ class FusedDepthwiseBnSign(torch.nn.Module):
         return act.flatten_hwc() if self.flatten_hwc else act
 
 
-class FusedGroupedBnSign(torch.nn.Module):
+class FusedDepthwiseBnSign(_FusedStreamingBnSign):
+    """Depthwise BinConv2d / TerConv2d (``groups == in_channels``, eval) + [MaxPool2d(k, s)] + eval BatchNorm2d + [Hardtanh] +
+    BinaryConnect(det) -> PackedActivation: the depthwise sibling of ``FusedConvPoolBnSign``.  ONE launch (qt_dwconv2d_sign) reads the
+    input — an fp32 device tensor, or the bit planes of a PackedActivation — computes the conv in the pinned fp32 order of
+    ``ops.depthwise_conv2d`` and writes the bit [y * alpha + beta < 0] as bit planes or, with ``out_nib_halo`` set, as the consuming
+    conv's nibble pixel plane with its padding as a zero border.  A pool between conv and BatchNorm runs on the un-pooled bits."""
+    _noun, _takes_groups = "depthwise", False
+    _applicable, _conv2d_sign = staticmethod(ops.depthwise_applicable), staticmethod(ops.depthwise_conv2d_sign)
+    _outside = "a depthwise conv outside the limits of the HIP kernels (ops.depthwise_applicable)"
+    _not_taken = "not a depthwise conv the HIP kernels take"
+    _admit = staticmethod(_admit_depthwise)
+
+    @staticmethod
+    def _tensor_input(x):
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            raise TypeError("FusedDepthwiseBnSign runs on a HIP device only (use the un-fused modules on CPU)")
+        return x, tuple(x.shape), ops._dw_channels_last(x)          # the depthwise result takes x's layout
+
+
+class FusedGroupedBnSign(_FusedStreamingBnSign):
     """Grouped BinConv2d / TerConv2d (eval; at least ``_fused.GROUPED_MIN_GROUPS`` groups of 2, 4 or 8 input channels, not depthwise)
     + [MaxPool2d(k, s)] + eval BatchNorm2d + [Hardtanh] + BinaryConnect(det) -> PackedActivation: the grouped sibling of
     ``FusedDepthwiseBnSign``.  ONE launch (qt_gconv2d_sign) reads the bit planes of a PackedActivation — a group's operand at a tap is
@@ -970,79 +962,23 @@ class FusedGroupedBnSign(torch.nn.Module):
     or, with ``out_nib_halo`` set, as the consuming conv's nibble pixel plane with its padding as a zero border; y has the bits of
     ``ops.grouped_conv2d`` on the decoded image.  A pool between conv and BatchNorm runs on the un-pooled bits.  There is no fp32
     input form: an fp32 tensor is a TypeError (the un-fused layer runs it)."""
+    _noun, _takes_groups = "grouped", True
+    _applicable, _conv2d_sign = staticmethod(ops.grouped_planes_applicable), staticmethod(ops.grouped_conv2d_sign)
+    _outside = ("a grouped conv outside the limits of the plane kernel (ops.grouped_planes_applicable: 2, 4 or 8 input "
+                "channels per group)")
+    _not_taken = "not a grouped conv the plane kernel takes"
 
-    def __init__(self, conv, bn, pool=None, flatten_hwc=False, fold=None):
-        super().__init__()
+    @staticmethod
+    def _admit(conv):
         from ..functions import _fused
-        from .binary_layers import BinConv2d
-        from .terner_layers import TerConv2d
-        if not isinstance(conv, (BinConv2d, TerConv2d)):
-            raise ValueError("FusedGroupedBnSign fuses grouped BinConv2d / TerConv2d only")
         if conv.groups < _fused.GROUPED_MIN_GROUPS or conv.groups == conv.in_channels or conv.padding_mode != "zeros" \
                 or isinstance(conv.padding, str):
             raise ValueError(f"only zero-padded convs with numeric padding and at least {_fused.GROUPED_MIN_GROUPS} groups of more than "
                              "one input channel can be fused")
-        kh, kw = conv.kernel_size
-        dh, dw = ops._pairs(conv.dilation)
-        fits = (1, conv.in_channels, dh * (kh - 1) + 1, dw * (kw - 1) + 1)       # the smallest image the kernel fits
-        if not ops.grouped_planes_applicable(fits, conv.weight.shape, conv.stride, conv.padding, conv.dilation, conv.groups):
-            raise ValueError("a grouped conv outside the limits of the plane kernel (ops.grouped_planes_applicable: 2, 4 or 8 input "
-                             "channels per group)")
-        if not isinstance(bn, torch.nn.BatchNorm2d) or bn.num_features != conv.out_channels:
-            raise ValueError("BatchNorm2d over the conv's output channels expected")
-        self._pool = FusedPoolBnSign(bn, pool, fold=fold)           # validates the pooling geometry, owns the fold cache
-        self.fold = self._pool.fold
-        self.conv, self.bn = conv, bn
-        self.flatten_hwc = flatten_hwc
-        self._neg_alpha = None
-        self.out_nib_halo = None        # see FusedConvPoolBnSign.out_nib_halo
 
-    def refold(self):
-        self._pool.refold()
-        self._neg_alpha = None
-
-    def forward(self, x):
-        if self.bn.training or self.conv.training:
-            raise RuntimeError("FusedGroupedBnSign is an inference module: call .eval() first")
-        conv, fp = self.conv, self._pool
-        x = lazy.resolve(x)
-        if not isinstance(x, packed.PackedActivation):
-            raise TypeError("FusedGroupedBnSign reads the bit planes of a PackedActivation only (the un-fused layer takes fp32 tensors)")
-        if x.planes is None:
-            raise ValueError("a grouped block reads bit planes; its producer was linked to hand over a nibble operand")
-        shape = x.shape
-        if len(shape) != 4 or not ops.grouped_planes_applicable(shape, conv.weight.shape, conv.stride, conv.padding, conv.dilation,
-                                                                conv.groups):
-            raise ValueError(f"not a grouped conv the plane kernel takes: input {tuple(shape)}")
-        if not conv._eval_on_grid():
-            raise ValueError("the eval-mode weight is off the quantiser's grid")
-        dev = conv.weight.device
-        N, _, H, W = (int(v) for v in shape)
-        Ho, Wo = ops.conv_out_hw(H, W, conv.kernel_size[0], conv.kernel_size[1], conv.stride, conv.padding, conv.dilation)
-        prev = fp._folded
-        like = None
-        if self.fold == "device":
-            # the tensor the module graph would hand to F.batch_norm: the grouped result — which takes the layout of the conv's
-            # fp32 input, here the +-1 tensor the planes stand for — pooled
-            like = ((N, conv.out_channels, (Ho - fp.pool_k) // fp.pool_s + 1, (Wo - fp.pool_k) // fp.pool_s + 1), _out_channels_last(x))
-        alpha, beta = _folded_for(fp, "_folded", self.bn, dev, self.fold, like)
-        if fp._folded is not prev or self._neg_alpha is None:      # BatchNorm / probe signature changed (or first call): derived data too
-            self._neg_alpha = _derived(fp._folded, "neg_alpha", lambda: ops.neg_alpha_words(alpha))
-        pooled = fp.pool_k != 1 or fp.pool_s != 1
-        nib_out = self.out_nib_halo is not None and not self.flatten_hwc
-        Cout = conv.out_channels
-        args = (x.planes, conv.weight.detach(), conv.bias, alpha, beta, conv.stride, conv.padding, conv.dilation, conv.groups)
-        if nib_out and not pooled:
-            nib, _ = ops.grouped_conv2d_sign(*args, kind="raw", shape=shape, out_halo=self.out_nib_halo)
-            return packed.PackedActivation(None, (N, Cout, Ho, Wo), nib=nib, halo=self.out_nib_halo)
-        planes, _ = ops.grouped_conv2d_sign(*args, kind="raw", shape=shape)
-        if pooled and nib_out:
-            nib, (Ho, Wo) = ops.pool_bits_nib(planes, N, Ho, Wo, fp.pool_k, fp.pool_s, self._neg_alpha, self.out_nib_halo)
-            return packed.PackedActivation(None, (N, Cout, Ho, Wo), nib=nib, halo=self.out_nib_halo)
-        if pooled:
-            planes, (Ho, Wo) = ops.pool_bits(planes, N, Ho, Wo, fp.pool_k, fp.pool_s, self._neg_alpha)
-        act = packed.PackedActivation(planes, (N, Cout, Ho, Wo))
-        return act.flatten_hwc() if self.flatten_hwc else act
+    @staticmethod
+    def _tensor_input(x):
+        raise TypeError("FusedGroupedBnSign reads the bit planes of a PackedActivation only (the un-fused layer takes fp32 tensors)")
 
 
 class FusedConvBnAddSign(torch.nn.Module):

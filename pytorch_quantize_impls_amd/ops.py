@@ -12,7 +12,7 @@ import ctypes as _ct
 import threading
 import functools
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -4086,23 +4086,32 @@ def pack_weight_nib_into(weight: torch.Tensor, kind: str, planes: NibPlanes) -> 
 
 
 # ----------------------------------------------------------------------------------------------
-# depthwise conv2d (groups == in_channels): streaming kernels of csrc/dwconv.hip, forward and both gradients
+# streaming conv2d, forward and both gradients, on tensors, bit planes and code planes: the depthwise family (groups ==
+# in_channels, csrc/dwconv.hip, "qt_dwconv2d_*") and the grouped family (a few channels per group, csrc/gconv.hip, "qt_gconv2d_*").
+# The kernels differ; the host side does not: ONE private body per operation (_streaming_*), which a ``_Streaming`` descriptor
+# tells the entry prefix, the noun of the messages and the geometry tuple of the C call, and two public wrappers that pick the
+# family.  A new operation is written once; a new family is a descriptor, its geometry function and its wrappers.
 # ----------------------------------------------------------------------------------------------
 
 DW_KINDS = {"raw": _lib.DEFINES["QT_DW_RAW"], "binary": _lib.DEFINES["QT_DW_SIGN"], "ternary": _lib.DEFINES["QT_DW_TERNARY"]}
 DW_MAX_TAPS = _lib.DEFINES["QT_DW_MAX_TAPS"]
 DW_MAX_CHANNELS = _lib.DEFINES["QT_DW_MAX_CHANNELS"]
+GC_MAX_CIN_G = _lib.DEFINES["QT_GC_MAX_CIN_G"]
+GC_MAX_K = _lib.DEFINES["QT_GC_MAX_K"]
+#: input channels per group the grouped plane kernel takes: a group's operand at one tap is a bit field of ONE plane word
+GC_PLANE_CIN_G = (2, 4, 8)
 
 
-def depthwise_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
-    """A conv2d of an [N, C, H, W] input with a [C * m, 1, kh, kw] weight and ``groups == C`` (one input channel per group,
-    m >= 1) that the depthwise entry points take: numeric padding, kh * kw <= 49, every tensor non-empty and below 2^31
-    elements, at most ``DW_MAX_CHANNELS`` output channels.  A pure function of the shapes."""
+def _streaming_limits(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
+    """What both families ask of a conv2d of an [N, G * cin_g, H, W] input with a [G * cout_g, cin_g, kh, kw] weight and ``groups
+    == G``: numeric padding, kh * kw <= ``DW_MAX_TAPS``, every tensor non-empty and below 2^31 elements, at most
+    ``DW_MAX_CHANNELS`` output channels."""
     if len(x_shape) != 4 or len(w_shape) != 4 or isinstance(padding, str):
         return False
-    N, C, H, W = (int(v) for v in x_shape)
-    Cout, cin_g, kh, kw = (int(v) for v in w_shape)
-    if int(groups) != C or C < 1 or cin_g != 1 or Cout < C or Cout % C != 0 or min(N, H, W, kh, kw) < 1:
+    N, C, H, W = map(int, x_shape)
+    Cout, cin_g, kh, kw = map(int, w_shape)
+    G = int(groups)
+    if G < 1 or cin_g < 1 or C != G * cin_g or Cout < G or Cout % G != 0 or min(N, H, W, kh, kw) < 1:
         return False
     try:
         (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
@@ -4116,6 +4125,39 @@ def depthwise_applicable(x_shape, w_shape, stride, padding, dilation, groups) ->
     return N * C * H * W < 1 << 31 and N * Cout * Ho * Wo < 1 << 31
 
 
+def depthwise_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
+    """A conv2d of an [N, C, H, W] input with a [C * m, 1, kh, kw] weight and ``groups == C`` (one input channel per group,
+    m >= 1) that the depthwise entry points take: numeric padding, kh * kw <= 49, every tensor non-empty and below 2^31
+    elements, at most ``DW_MAX_CHANNELS`` output channels.  A pure function of the shapes."""
+    return _streaming_limits(x_shape, w_shape, stride, padding, dilation, groups) and int(w_shape[1]) == 1
+
+
+def grouped_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
+    """A conv2d of an [N, G * cin_g, H, W] input with a [G * cout_g, cin_g, kh, kw] weight and ``groups == G`` that the grouped
+    entry points take: numeric padding, 1 <= cin_g <= ``GC_MAX_CIN_G``, kh * kw <= ``DW_MAX_TAPS``, cin_g * kh * kw <=
+    ``GC_MAX_K``, every tensor non-empty and below 2^31 elements, at most ``DW_MAX_CHANNELS`` output channels.  A pure function of
+    the shapes."""
+    if not _streaming_limits(x_shape, w_shape, stride, padding, dilation, groups):
+        return False
+    cin_g = int(w_shape[1])
+    return cin_g <= GC_MAX_CIN_G and cin_g * int(w_shape[2]) * int(w_shape[3]) <= GC_MAX_K
+
+
+def grouped_planes_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
+    """``grouped_applicable`` and 2, 4 or 8 input channels per group: the grouped convs that run on the bit planes of a +-1
+    activation (``grouped_conv2d_sign`` / ``grouped_conv2d_from_bits``).  A pure function of the shapes."""
+    return (grouped_applicable(x_shape, w_shape, stride, padding, dilation, groups) and int(w_shape[1]) in GC_PLANE_CIN_G)
+
+
+def grouped_codes_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
+    """The grouped convs that run on the int8 code plane of a DoReFa activation (``grouped_conv2d_codes`` /
+    ``grouped_conv2d_from_codes``): those ``grouped_applicable`` takes — any cin_g the fp32 entry takes, any cout_g; the pixel rows of
+    the un-bordered planes are bounded by the tensors' elements.  A pure function of the shapes: it does not know the halos, so a
+    plane whose border (up to 64 pixels a side) brings it to 2^31 pixel rows or more passes here and is refused by the entry
+    (QT_ERR_UNSUPPORTED, raised by the wrapper) — as with ``depthwise_applicable`` and the depthwise code entries."""
+    return grouped_applicable(x_shape, w_shape, stride, padding, dilation, groups)
+
+
 def _dw_channels_last(t: torch.Tensor) -> bool:
     return t.is_contiguous(memory_format=torch.channels_last) and not t.is_contiguous()
 
@@ -4123,7 +4165,7 @@ def _dw_channels_last(t: torch.Tensor) -> bool:
 def _dw_strides(shape, channels_last: bool):
     """The element strides (n, c, h, w) the entry points accept for a dense tensor of ``shape`` (torch leaves the strides of
     size-1 dimensions arbitrary)."""
-    _, C, H, W = (int(v) for v in shape)
+    _, C, H, W = map(int, shape)
     return (H * W * C, 1, W * C, C) if channels_last else (C * H * W, H * W, W, 1)
 
 
@@ -4172,15 +4214,80 @@ def _dw_weight(weight: torch.Tensor, C: int, half: bool = False):
     return (w if w.is_contiguous() else w.contiguous()), int(weight.shape[0]) // C, int(weight.shape[2]), int(weight.shape[3])
 
 
-def _dw_geometry(x_shape, weight, stride, padding, dilation, half: bool = False):
-    N, C, H, W = (int(v) for v in x_shape)
+def _dw_geometry(x_shape, weight, stride, padding, dilation, groups=None, half: bool = False):
+    """``groups`` is not looked at: it is C."""
+    N, C, H, W = map(int, x_shape)
     w, m, kh, kw = _dw_weight(weight, C, half)
-    if not depthwise_applicable(x_shape, weight.shape, stride, padding, dilation, C) and min(N, C, H, W) > 0:
+    # depthwise_applicable, whose one-channel-per-group test _dw_weight has just made
+    if not _streaming_limits(x_shape, weight.shape, stride, padding, dilation, C) and min(N, C, H, W) > 0:
         raise ValueError(f"not a depthwise conv the HIP entry points take: input {tuple(x_shape)}, weight {tuple(weight.shape)}, "
                          f"stride {stride}, padding {padding}, dilation {dilation}")
     (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
     Ho, Wo = (conv_out_hw(H, W, kh, kw, (sh, sw), (ph, pw), (dh, dw)) if min(H, W) > 0 else (0, 0))
     return w, (N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw), (N, C * m, max(Ho, 0), max(Wo, 0))
+
+
+def _gc_geometry(x_shape, weight, stride, padding, dilation, groups, half: bool = False):
+    _require_packable(weight, "weight") if half else _require(weight, "weight")
+    N, C, H, W = map(int, x_shape)
+    G = int(groups)
+    if weight.dim() != 4 or G < 1 or C != G * int(weight.shape[1]) or weight.shape[0] % G != 0 or weight.shape[0] < G:
+        raise ValueError(f"weight: expected [G * cout_g, C / G, kh, kw] for C = {C}, G = {G}, got {tuple(weight.shape)}")
+    if not grouped_applicable(x_shape, weight.shape, stride, padding, dilation, G) and min(N, C, H, W) > 0:
+        raise ValueError(f"not a grouped conv the HIP entry points take: input {tuple(x_shape)}, weight {tuple(weight.shape)}, "
+                         f"groups {G}, stride {stride}, padding {padding}, dilation {dilation}")
+    w = weight.detach()
+    w = w if w.is_contiguous() else w.contiguous()
+    Cout, cin_g, kh, kw = map(int, weight.shape)
+    (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
+    Ho, Wo = (conv_out_hw(H, W, kh, kw, (sh, sw), (ph, pw), (dh, dw)) if min(H, W) > 0 else (0, 0))
+    return w, (N, G, cin_g, Cout // G, H, W, kh, kw, sh, sw, ph, pw, dh, dw), (N, Cout, max(Ho, 0), max(Wo, 0))
+
+
+def _gc_planes_geometry(x_shape, weight, stride, padding, dilation, groups):
+    w, geom, y_shape = _gc_geometry(x_shape, weight, stride, padding, dilation, groups)
+    if geom[2] not in GC_PLANE_CIN_G:
+        raise ValueError(f"the grouped plane kernel takes 2, 4 or 8 input channels per group, got {geom[2]}")
+    return w, geom, y_shape
+
+
+class _Streaming(NamedTuple):
+    """One family of streaming convs, as the shared bodies below see it."""
+    entry: dict                 # suffix -> name of the entry point ("f32" -> "qt_dwconv2d_f32"), spelled once, not per call
+    noun: str                  # the family's name in the messages
+    cout: str                   # its output channel count, as the messages spell it
+    #: (x_shape, weight, stride, padding, dilation, groups[, half]) -> (dense detached weight, the geometry arguments of the C
+    #: calls, y_shape); refuses a weight that is not the family's, then a conv outside the limits — an empty tensor passes
+    geometry: Callable
+    planes_geometry: Callable   # ``geometry`` of the entries that read bit planes (fp32 weight)
+    tensor_sign: bool           # the "sign" entry reads an fp32 tensor too: an (x, plane, ldx) head and x's strides in its arguments
+
+
+def _streaming_entries(prefix: str) -> dict:
+    return {s: f"{prefix}_{s}" for s in ("f32", "h", "sign", "bits_f32", "codes", "codes_f32", "grad_input_f32", "grad_input_h",
+                                         "grad_weight_f32", "grad_weight_h", "grad_weight_work_floats")}
+
+
+_DW = _Streaming(_streaming_entries("qt_dwconv2d"), "depthwise", "C * m", _dw_geometry, _dw_geometry, True)
+_GC = _Streaming(_streaming_entries("qt_gconv2d"), "grouped", "G * cout_g", _gc_geometry, _gc_planes_geometry, False)
+
+
+def _streaming_conv2d(fam: _Streaming, x, weight, bias, stride, padding, dilation, groups, kind="raw", out=None):
+    x = _dw_operand(x, "input", half=True)
+    w, geom, y_shape = fam.geometry(x.shape, weight, stride, padding, dilation, groups, True)
+    codes = _dw_half_codes(x, w)
+    bias = _check_bias(bias, y_shape[1], x.device)
+    y = _dw_result(out, y_shape, x, "out", x.dtype)
+    if y.numel() == 0 or x.numel() == 0:
+        return y
+    tail = (*geom, *_dw_strides(x.shape, _dw_channels_last(x)), *_dw_strides(y.shape, _dw_channels_last(y)), DW_KINDS[kind],
+            _stream(x.device))
+    with _on(x.device):
+        if codes is None:
+            _lib.call(fam.entry["f32"], _p(x), _p(w), _p(bias), _p(y), *tail)
+        else:
+            _lib.call(fam.entry["h"], _p(x), codes[0], _p(w), codes[1], _p(bias), _p(y), *tail)
+    return y
 
 
 def depthwise_conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1,
@@ -4191,21 +4298,18 @@ def depthwise_conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
     order, one multiply and one add each, out-of-image taps skipped, bias last.  A bf16 / fp16 ``x`` (with a weight of the same dtype,
     or fp32 as under autocast; ``bias`` stays an fp32 vector) runs qt_dwconv2d_h: the same fp32 arithmetic on the exactly upcast
     elements, rounded once to nearest even into a result of x's dtype."""
-    x = _dw_operand(x, "input", half=True)
-    w, geom, y_shape = _dw_geometry(x.shape, weight, stride, padding, dilation, half=True)
-    codes = _dw_half_codes(x, w)
-    bias = _check_bias(bias, y_shape[1], x.device)
-    y = _dw_result(out, y_shape, x, "out", x.dtype)
-    if y.numel() == 0 or x.numel() == 0:
-        return y
-    tail = (*geom, *_dw_strides(x.shape, _dw_channels_last(x)), *_dw_strides(y.shape, _dw_channels_last(y)), DW_KINDS[kind],
-            _stream(x.device))
-    with _on(x.device):
-        if codes is None:
-            _lib.call("qt_dwconv2d_f32", _p(x), _p(w), _p(bias), _p(y), *tail)
-        else:
-            _lib.call("qt_dwconv2d_h", _p(x), codes[0], _p(w), codes[1], _p(bias), _p(y), *tail)
-    return y
+    return _streaming_conv2d(_DW, x, weight, bias, stride, padding, dilation, None, kind, out)
+
+
+def grouped_conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1,
+                   groups: int = 1, kind: str = "raw", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """F.conv2d(x, Q(weight), bias, stride, padding, dilation, groups) for x [N, G * cin_g, H, W] fp32 (NCHW or channels-last) and
+    weight [G * cout_g, cin_g, kh, kw]; Q = ``kind`` ("raw" | "binary" | "ternary") is applied to the taps inside the one launch
+    (qt_gconv2d_f32).  The result has the layout of x, or is written into ``out``.  Bit-reproducible: +0 start, the group's input
+    channels ascending and the taps in row-major order inside each, one multiply and one add per term, out-of-image taps skipped,
+    bias last.  A bf16 / fp16 ``x`` (with a weight of the same dtype, or fp32 as under autocast; ``bias`` stays an fp32 vector) runs
+    qt_gconv2d_h: the same fp32 arithmetic on the exactly upcast elements, rounded once to nearest even into a result of x's dtype."""
+    return _streaming_conv2d(_GC, x, weight, bias, stride, padding, dilation, groups, kind, out)
 
 
 def _dw_plane_input(planes: BitPlanes, shape):
@@ -4214,7 +4318,7 @@ def _dw_plane_input(planes: BitPlanes, shape):
         raise TypeError(f"input: expected a device tensor or BitPlanes, got {type(planes)}")
     if shape is None or len(shape) != 4:
         raise ValueError("a BitPlanes input needs the logical (N, C, H, W) shape")
-    N, C, H, W = (int(v) for v in shape)
+    N, C, H, W = map(int, shape)
     _require(planes.sign, "input planes", torch.int32)
     if planes.mask is not None or planes.rows != N * H * W or planes.K != C or tuple(planes.sign.shape) != (N * H * W, planes.ld) \
             or not planes.sign.is_contiguous() or planes.ld < packed_ld(C):
@@ -4231,6 +4335,59 @@ def _dw_plane_out(out: Optional[torch.Tensor], rows: int, ld: int, dev, name: st
     return out
 
 
+def _sign_planes_out(N: int, C: int, Ho: int, Wo: int, dev, want_bits: bool, halo, out_sign=None, out_nib=None):
+    """The planes a threshold-bit launch writes for an (N, C, Ho, Wo) result: ``(BitPlanes or None, NibPlanes or None)`` — the
+    sign plane when ``want_bits``, the nibble pixel plane with a zero border of ``halo`` = (hy, hx) pixels unless that is None —
+    in new tensors, or in ``out_sign`` / ``out_nib`` (checked)."""
+    bits = nib = None
+    if want_bits:
+        bits = BitPlanes(sign=_dw_plane_out(out_sign, N * Ho * Wo, packed_ld(C), dev, "out_sign"), rows=N * Ho * Wo, K=C)
+    if halo is not None:
+        rows = N * (Ho + 2 * halo[0]) * (Wo + 2 * halo[1])
+        nib = NibPlanes(words=_dw_plane_out(out_nib, rows, pixel_ld_nib(C), dev, "out_nib"), rows=rows, K=C)
+    return bits, nib
+
+
+def _streaming_conv2d_sign(fam: _Streaming, x, weight, bias, alpha, beta, stride, padding, dilation, groups, kind, shape, out_halo,
+                           with_bits, out_sign, out_nib):
+    is_t = fam.tensor_sign and isinstance(x, torch.Tensor)
+    if is_t:
+        x = _dw_operand(x, "input")
+        x_shape = tuple(x.shape)
+    else:
+        x_shape = _dw_plane_input(x, shape)
+    dev = x.device
+    w, geom, y_shape = fam.planes_geometry(x_shape, weight, stride, padding, dilation, groups)
+    if w.device != dev:
+        raise ValueError("input and weight are on different devices")
+    N, Cout, Ho, Wo = y_shape
+    bias = _check_bias(bias, Cout, dev)
+    alpha, beta, _ = epilogue_affine((alpha, beta), Cout, dev)
+    if alpha is None or beta is None:
+        raise TypeError("alpha and beta: expected fp32 device vectors")
+    hy, hx = (0, 0) if out_halo is None else _pairs(out_halo)
+    if hy < 0 or hx < 0:
+        raise ValueError("out_halo must not be negative")
+    bits, nib = _sign_planes_out(N, Cout, Ho, Wo, dev, out_halo is None or with_bits, None if out_halo is None else (hy, hx),
+                                 out_sign, out_nib)
+    if N * Cout * Ho * Wo > 0:
+        # the two argument lists differ in their head and in x's strides; written out, not assembled, to cost the host nothing
+        with _on(dev):
+            if fam.tensor_sign:         # (x, plane, ldx) in front, x's strides (zeros for a plane) behind the geometry
+                xs = _dw_strides(x_shape, _dw_channels_last(x)) if is_t else (0, 0, 0, 0)
+                _lib.call(fam.entry["sign"], _p(x) if is_t else None, None if is_t else _p(x.sign), 0 if is_t else int(x.ld), _p(w),
+                          _p(bias), _p(alpha), _p(beta), _p(bits.sign) if bits is not None else None, bits.ld if bits is not None else 0,
+                          _p(nib.words) if nib is not None else None, nib.ld if nib is not None else 0, hy, hx, *geom, *xs,
+                          DW_KINDS[kind], _stream(dev))
+            else:                       # the plane and its row stride in front
+                _lib.call(fam.entry["sign"], _p(x.sign), int(x.ld), _p(w), _p(bias), _p(alpha), _p(beta),
+                          _p(bits.sign) if bits is not None else None, bits.ld if bits is not None else 0,
+                          _p(nib.words) if nib is not None else None, nib.ld if nib is not None else 0, hy, hx, *geom, DW_KINDS[kind],
+                          _stream(dev))
+    out = bits if nib is None else ((bits, nib) if bits is not None else nib)
+    return out, (Ho, Wo)
+
+
 def depthwise_conv2d_sign(x, weight: torch.Tensor, bias: Optional[torch.Tensor], alpha: torch.Tensor, beta: torch.Tensor, stride=1,
                           padding=0, dilation=1, kind: str = "raw", shape=None, out_halo=None, with_bits: bool = False,
                           out_sign: Optional[torch.Tensor] = None, out_nib: Optional[torch.Tensor] = None):
@@ -4242,350 +4399,8 @@ def depthwise_conv2d_sign(x, weight: torch.Tensor, bias: Optional[torch.Tensor],
     the consumer's operand — nibble pixel plane with a zero border of ``out_halo`` = (hy, hx) pixels, every word written — or,
     ``with_bits``, the pair ``(BitPlanes, NibPlanes)`` from the same launch.  ``out_sign`` / ``out_nib``: existing contiguous
     int32 [rows, ld] tensors the planes are written into (no prior content needed)."""
-    if isinstance(x, torch.Tensor):
-        x = _dw_operand(x, "input")
-        x_shape, dev = tuple(x.shape), x.device
-    else:
-        x_shape, dev = _dw_plane_input(x, shape), x.device
-    w, geom, y_shape = _dw_geometry(x_shape, weight, stride, padding, dilation)
-    if w.device != dev:
-        raise ValueError("input and weight are on different devices")
-    N, Cout, Ho, Wo = y_shape
-    bias = _check_bias(bias, Cout, dev)
-    alpha, beta, _ = epilogue_affine((alpha, beta), Cout, dev)
-    if alpha is None or beta is None:
-        raise TypeError("alpha and beta: expected fp32 device vectors")
-    hy, hx = (0, 0) if out_halo is None else (int(v) for v in _pairs(out_halo))
-    if hy < 0 or hx < 0:
-        raise ValueError("out_halo must not be negative")
-    bits = nib = None
-    if out_halo is None or with_bits:
-        bits = BitPlanes(sign=_dw_plane_out(out_sign, N * Ho * Wo, packed_ld(Cout), dev, "out_sign"), rows=N * Ho * Wo, K=Cout)
-    if out_halo is not None:
-        rows = N * (Ho + 2 * hy) * (Wo + 2 * hx)
-        nib = NibPlanes(words=_dw_plane_out(out_nib, rows, pixel_ld_nib(Cout), dev, "out_nib"), rows=rows, K=Cout)
-    if N * Cout * Ho * Wo > 0:
-        is_t = isinstance(x, torch.Tensor)
-        xs = _dw_strides(x_shape, _dw_channels_last(x)) if is_t else (0, 0, 0, 0)
-        with _on(dev):
-            _lib.call("qt_dwconv2d_sign", _p(x) if is_t else None, None if is_t else _p(x.sign), 0 if is_t else int(x.ld), _p(w),
-                      _p(bias), _p(alpha), _p(beta), _p(bits.sign) if bits is not None else None, bits.ld if bits is not None else 0,
-                      _p(nib.words) if nib is not None else None, nib.ld if nib is not None else 0, hy, hx, *geom, *xs,
-                      DW_KINDS[kind], _stream(dev))
-    out = bits if nib is None else ((bits, nib) if bits is not None else nib)
-    return out, (Ho, Wo)
-
-
-def depthwise_conv2d_from_bits(planes: BitPlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1,
-                               padding=0, dilation=1, kind: str = "raw", channels_last: bool = False,
-                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``depthwise_conv2d`` of the +-1 activation that exists only as ``planes`` (sign-only NHWC pixel plane, logical ``shape``
-    (N, C, H, W)): the fp32 result, bit for bit that of the fp32 +-1 image, in NCHW or ``channels_last`` storage or written into
-    ``out`` (qt_dwconv2d_bits_f32, one launch)."""
-    x_shape = _dw_plane_input(planes, shape)
-    dev = planes.device
-    w, geom, y_shape = _dw_geometry(x_shape, weight, stride, padding, dilation)
-    if w.device != dev:
-        raise ValueError("input and weight are on different devices")
-    bias = _check_bias(bias, y_shape[1], dev)
-    if out is None:
-        y = torch.empty(y_shape, dtype=torch.float32, device=dev,
-                        memory_format=torch.channels_last if channels_last else torch.contiguous_format)
-    else:
-        y = _dw_result(out, y_shape, w, "out")
-    if y.numel() == 0:
-        return y
-    with _on(dev):
-        _lib.call("qt_dwconv2d_bits_f32", _p(planes.sign), int(planes.ld), _p(w), _p(bias), _p(y), *geom,
-                  *_dw_strides(y.shape, _dw_channels_last(y)), DW_KINDS[kind], _stream(dev))
-    return y
-
-
-def _dw_code_input(codes: CodePlanes, shape, in_halo):
-    """``codes`` checked as the int8 NHWC pixel plane (16-byte rows, zero border of ``in_halo`` pixels) of a DoReFa activation of
-    logical ``shape`` (N, C, H, W); returns the shape and the halo as ints."""
-    if not isinstance(codes, CodePlanes):
-        raise TypeError(f"input: expected CodePlanes, got {type(codes)}")
-    if shape is None or len(shape) != 4:
-        raise ValueError("a CodePlanes input needs the logical (N, C, H, W) shape")
-    N, C, H, W = (int(v) for v in shape)
-    hy, hx = (int(v) for v in _pairs(in_halo))
-    _require(codes.codes, "input codes", torch.int8)
-    rows = N * (H + 2 * hy) * (W + 2 * hx)
-    ld = int(codes.codes.shape[1]) if codes.codes.dim() == 2 else 0
-    if (hy < 0 or hx < 0 or codes.rows != rows or codes.K != C or codes.codes.dim() != 2 or int(codes.codes.shape[0]) < rows
-            or not codes.codes.is_contiguous() or ld < code_ld_bytes(C, 16) or ld % 16):
-        raise ValueError(f"input: expected the int8 NHWC code plane (16-byte rows) of an {(N, C, H, W)} activation with halo {(hy, hx)}")
-    return (N, C, H, W), (hy, hx)
-
-
-def depthwise_conv2d_codes(codes: CodePlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor], epi: CodeEpilogue, stride=1,
-                           padding=0, dilation=1, in_halo=(0, 0), out: Optional[torch.Tensor] = None) -> CodePlanes:
-    """Depthwise conv (``depthwise_conv2d``'s pinned fp32 arithmetic on the image fl(inv_n * code)) -> BatchNorm -> [ReLU] -> k-bit
-    DoReFa quantiser, from the int8 code plane ``codes`` (logical ``shape`` (N, C, H, W), zero border of ``in_halo`` pixels that is
-    never read) to the next code plane in ONE launch (qt_dwconv2d_codes): no fp32 activation exists.  ``epi``: a ``CodeEpilogue``
-    without a residual — folded (alpha, beta), or the device form with ``bn_stats``; its ``out_halo`` is the zero border of the
-    produced plane [N*(Ho+2hy)*(Wo+2hx), code_ld_bytes(C*m, 16)], of which the launch writes every byte; ``overflow`` the chain's
-    int8 range flag (None: the input plane's, or a fresh one).  ``out``: an existing contiguous int8 [rows, ld] tensor the plane is
-    written into (no prior content needed)."""
-    x_shape, (ihy, ihx) = _dw_code_input(codes, shape, in_halo)
-    dev = codes.device
-    w, geom, y_shape = _dw_geometry(x_shape, weight, stride, padding, dilation)
-    if w.device != dev:
-        raise ValueError("input and weight are on different devices")
-    if not isinstance(epi, CodeEpilogue):
-        raise TypeError(f"epi: expected a CodeEpilogue, got {type(epi)}")
-    if epi.res_f32 is not None or epi.res_codes is not None or epi.res_affine is not None or any(epi.res_halo):
-        raise ValueError("the depthwise code epilogue takes no residual")
-    relu = relu_mode(epi.relu)
-    if relu == 2:
-        raise ValueError("the depthwise code epilogue has no ReLU in front of the BatchNorm (relu='pre')")
-    if not 2 <= int(epi.bit_width) <= 8:
-        raise ValueError("int8 code planes exist for 2 <= bit_width <= 8")
-    N, Cout, Ho, Wo = y_shape
-    bias = _check_bias(bias, Cout, dev)
-    alpha, beta = _check_bias(epi.alpha, Cout, dev, "alpha"), _check_bias(epi.beta, Cout, dev, "beta")
-    if alpha is None or beta is None:
-        raise TypeError("alpha and beta: expected fp32 device vectors")
-    stats = None
-    if epi.bn_stats is not None:
-        stats = _require(epi.bn_stats, "bn_stats").contiguous()
-        if stats.numel() != 2 * Cout or stats.device != dev:
-            raise ValueError("bn_stats must hold [mean | rs]: 2 * C * m values on the input's device")
-    ohy, ohx = (int(v) for v in _pairs(epi.out_halo))
-    if ohy < 0 or ohx < 0:
-        raise ValueError("out_halo must not be negative")
-    flag = epi.overflow if epi.overflow is not None else codes.overflow
-    if flag is None:
-        flag = torch.zeros((1,), dtype=torch.int32, device=dev)
-    _require(flag, "overflow", torch.int32)
-    rows, ldc = N * (Ho + 2 * ohy) * (Wo + 2 * ohx), code_ld_bytes(Cout, 16)
-    if out is None:
-        out = torch.empty((rows, ldc), dtype=torch.int8, device=dev)      # the launch writes every byte, halo border included
-    else:
-        _require(out, "out", torch.int8)
-        if tuple(out.shape) != (rows, ldc) or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out: expected a contiguous int8 tensor [{rows}, {ldc}] on {dev}, got {tuple(out.shape)} on {out.device}")
-    if N * Cout * Ho * Wo > 0:
-        with _on(dev):
-            _lib.call("qt_dwconv2d_codes", _p(codes.codes), int(codes.codes.shape[1]), ihy, ihx, float(codes.inv_n), _p(w), _p(bias),
-                      _p(alpha), _p(beta), _p(stats), relu, int(epi.bit_width), _p(out), ldc, ohy, ohx, _p(flag), *geom, _stream(dev))
-    return CodePlanes(codes=out, rows=rows, K=Cout, inv_n=inv_levels(epi.bit_width), bit_width=int(epi.bit_width), overflow=flag)
-
-
-def depthwise_conv2d_from_codes(codes: CodePlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1,
-                                padding=0, dilation=1, in_halo=(0, 0), channels_last: bool = True, out: Optional[torch.Tensor] = None,
-                                flagged: bool = True) -> torch.Tensor:
-    """``depthwise_conv2d`` of the DoReFa activation that exists only as the code plane ``codes`` (see ``depthwise_conv2d_codes``):
-    the fp32 result, bit for bit that of the fp32 image fl(inv_n * code), in ``channels_last`` or NCHW storage or written into ``out``
-    (qt_dwconv2d_codes_f32, one launch).  ``flagged``: a raised int8 range flag of the plane's chain makes every value NaN, on the
-    device."""
-    x_shape, (ihy, ihx) = _dw_code_input(codes, shape, in_halo)
-    dev = codes.device
-    w, geom, y_shape = _dw_geometry(x_shape, weight, stride, padding, dilation)
-    if w.device != dev:
-        raise ValueError("input and weight are on different devices")
-    bias = _check_bias(bias, y_shape[1], dev)
-    if out is None:
-        y = torch.empty(y_shape, dtype=torch.float32, device=dev,
-                        memory_format=torch.channels_last if channels_last else torch.contiguous_format)
-    else:
-        y = _dw_result(out, y_shape, w, "out")
-    if y.numel() == 0:
-        return y
-    flag = codes.overflow if flagged else None
-    with _on(dev):
-        _lib.call("qt_dwconv2d_codes_f32", _p(codes.codes), int(codes.codes.shape[1]), ihy, ihx, float(codes.inv_n), _p(w), _p(bias),
-                  _p(flag), _p(y), *geom, *_dw_strides(y.shape, _dw_channels_last(y)), _stream(dev))
-    return y
-
-
-def depthwise_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_output: torch.Tensor, stride=1, padding=0, dilation=1,
-                                kind: str = "raw", channels_last: Optional[bool] = None,
-                                out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Gradient of ``depthwise_conv2d`` with respect to x: a gather over the multiplier index (outermost) and the taps (row-major)
-    with the forward's arithmetic rules, no atomics (qt_dwconv2d_grad_input_f32; qt_dwconv2d_grad_input_h for a bf16 / fp16
-    ``grad_output``, whose dtype the result then has).  The result has the layout of ``grad_output`` unless ``channels_last`` says
-    otherwise, or is written into ``out``."""
-    w, geom, y_shape = _dw_geometry(input_shape, weight, stride, padding, dilation, half=True)
-    go = _dw_operand(grad_output, "grad_output", y_shape, half=True)
-    codes = _dw_half_codes(go, w)
-    if out is None:
-        cl = _dw_channels_last(go) if channels_last is None else bool(channels_last)
-        gx = torch.empty(tuple(input_shape), dtype=go.dtype, device=go.device,
-                         memory_format=torch.channels_last if cl else torch.contiguous_format)
-    else:
-        gx = _dw_result(out, input_shape, go, "out", go.dtype)
-    if gx.numel() == 0:
-        return gx
-    if go.numel() == 0:
-        return gx.zero_()
-    tail = (*geom, *_dw_strides(go.shape, _dw_channels_last(go)), *_dw_strides(gx.shape, _dw_channels_last(gx)), DW_KINDS[kind],
-            _stream(go.device))
-    with _on(go.device):
-        if codes is None:
-            _lib.call("qt_dwconv2d_grad_input_f32", _p(go), _p(w), _p(gx), *tail)
-        else:
-            _lib.call("qt_dwconv2d_grad_input_h", _p(go), codes[0], _p(w), codes[1], _p(gx), *tail)
-    return gx
-
-
-def depthwise_grad_weight_work_floats(input_shape, weight_shape, stride=1, padding=0, dilation=1) -> int:
-    """fp32 elements of workspace ``depthwise_conv2d_grad_weight`` needs (qt_dwconv2d_grad_weight_work_floats)."""
-    N, C, H, W = (int(v) for v in input_shape)
-    (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
-    n = int(_lib.load().qt_dwconv2d_grad_weight_work_floats(N, C, int(weight_shape[0]) // max(C, 1), H, W, int(weight_shape[2]),
-                                                            int(weight_shape[3]), sh, sw, ph, pw, dh, dw))
-    if n < 0:
-        raise _lib.QtStatusError(f"qt_dwconv2d_grad_weight_work_floats failed: {_lib.strerror(n)} (qt_status {n})")
-    return n
-
-
-def depthwise_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, weight: torch.Tensor, stride=1, padding=0, dilation=1,
-                                 ste_threshold: float = 0.0, want_bias: bool = False, out: Optional[torch.Tensor] = None,
-                                 out_bias: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
-    """Gradient of ``depthwise_conv2d`` with respect to the weight, shaped like ``weight``, and — ``want_bias`` or ``out_bias`` —
-    the per-channel sum of ``grad_output`` from the same pass (else None): ``(grad_weight, grad_bias)``.  Two launches inside one
-    call, no atomics: partials per (split, channel, tap) into ``workspace`` (``depthwise_grad_weight_work_floats`` fp32 elements;
-    allocated when not given), then the splits in index order; equal inputs give equal bits.  ``ste_threshold`` > 0 zeroes the
-    entries where the UNquantised ``|weight|`` exceeds it (1.001 for the sign families).  bf16 / fp16 ``x`` and ``grad_output`` (one
-    dtype) run qt_dwconv2d_grad_weight_h; both gradients have the WEIGHT's dtype (fp32 under autocast), rounded once from fp32."""
-    x = _dw_operand(x, "input", half=True)
-    w, geom, y_shape = _dw_geometry(x.shape, weight, stride, padding, dilation, half=True)
-    go = _dw_operand(grad_output, "grad_output", y_shape, half=True)
-    if go.device != x.device:
-        raise ValueError("input and grad_output are on different devices")
-    codes = _dw_half_codes(x, w, go)
-    Cout, kk = y_shape[1], geom[5] * geom[6]
-    if out is None:
-        gw = torch.empty(tuple(weight.shape), dtype=w.dtype, device=x.device)
-    else:
-        gw = _require(out, "out", w.dtype)
-        if tuple(gw.shape) != tuple(weight.shape) or not gw.is_contiguous() or gw.device != x.device:
-            raise ValueError(f"out: expected a contiguous {w.dtype} tensor of shape {tuple(weight.shape)} on {x.device}")
-    gb = None
-    if out_bias is not None:
-        gb = _require(out_bias, "out_bias", w.dtype)
-        if tuple(gb.shape) != (Cout,) or not gb.is_contiguous() or gb.device != x.device:
-            raise ValueError(f"out_bias: expected a contiguous {w.dtype} tensor of shape ({Cout},) on {x.device}")
-    elif want_bias:
-        gb = torch.empty((Cout,), dtype=w.dtype, device=x.device)
-    if gw.numel() == 0:
-        return gw, gb
-    if go.numel() == 0 or x.numel() == 0:
-        gw.zero_()
-        return gw, (gb.zero_() if gb is not None else None)
-    need = depthwise_grad_weight_work_floats(x.shape, weight.shape, stride, padding, dilation)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.float32, device=x.device)
-    else:
-        _require(workspace, "workspace")
-        if not workspace.is_contiguous() or workspace.device != x.device or workspace.numel() < need:
-            raise ValueError(f"workspace: expected at least {need} contiguous fp32 elements on {x.device}")
-    tail = (_p(workspace), int(workspace.numel()), *geom, *_dw_strides(go.shape, _dw_channels_last(go)),
-            *_dw_strides(x.shape, _dw_channels_last(x)), float(ste_threshold), _stream(x.device))
-    with _on(x.device):
-        if codes is None:
-            _lib.call("qt_dwconv2d_grad_weight_f32", _p(go), _p(x), _p(w), _p(gw), _p(gb), *tail)
-        else:
-            _lib.call("qt_dwconv2d_grad_weight_h", _p(go), _p(x), codes[0], _p(w), _p(gw), _p(gb), codes[1], *tail)
-    return gw, gb
-
-
-# ----------------------------------------------------------------------------------------------
-# grouped conv2d with a few channels per group: streaming kernels of csrc/gconv.hip, forward and both gradients
-# ----------------------------------------------------------------------------------------------
-
-GC_MAX_CIN_G = _lib.DEFINES["QT_GC_MAX_CIN_G"]
-GC_MAX_K = _lib.DEFINES["QT_GC_MAX_K"]
-
-
-def grouped_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
-    """A conv2d of an [N, G * cin_g, H, W] input with a [G * cout_g, cin_g, kh, kw] weight and ``groups == G`` that the grouped
-    entry points take: numeric padding, 1 <= cin_g <= ``GC_MAX_CIN_G``, kh * kw <= ``DW_MAX_TAPS``, cin_g * kh * kw <=
-    ``GC_MAX_K``, every tensor non-empty and below 2^31 elements, at most ``DW_MAX_CHANNELS`` output channels.  A pure function of
-    the shapes."""
-    if len(x_shape) != 4 or len(w_shape) != 4 or isinstance(padding, str):
-        return False
-    N, C, H, W = (int(v) for v in x_shape)
-    Cout, cin_g, kh, kw = (int(v) for v in w_shape)
-    G = int(groups)
-    if G < 1 or cin_g < 1 or C != G * cin_g or Cout < G or Cout % G != 0 or min(N, H, W, kh, kw) < 1:
-        return False
-    try:
-        (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
-    except (TypeError, IndexError, ValueError):
-        return False
-    if min(sh, sw, dh, dw) < 1 or min(ph, pw) < 0 or max(ph, pw, dh, dw) >= 1 << 24 or Cout > DW_MAX_CHANNELS:
-        return False
-    if cin_g > GC_MAX_CIN_G or kh * kw > DW_MAX_TAPS or cin_g * kh * kw > GC_MAX_K:
-        return False
-    Ho, Wo = conv_out_hw(H, W, kh, kw, (sh, sw), (ph, pw), (dh, dw))
-    if Ho < 1 or Wo < 1 or H + 2 * ph >= 1 << 31 or W + 2 * pw >= 1 << 31:
-        return False
-    return N * C * H * W < 1 << 31 and N * Cout * Ho * Wo < 1 << 31
-
-
-def _gc_geometry(x_shape, weight, stride, padding, dilation, groups, half: bool = False):
-    _require_packable(weight, "weight") if half else _require(weight, "weight")
-    N, C, H, W = (int(v) for v in x_shape)
-    G = int(groups)
-    if weight.dim() != 4 or G < 1 or C != G * int(weight.shape[1]) or weight.shape[0] % G != 0 or weight.shape[0] < G:
-        raise ValueError(f"weight: expected [G * cout_g, C / G, kh, kw] for C = {C}, G = {G}, got {tuple(weight.shape)}")
-    if not grouped_applicable(x_shape, weight.shape, stride, padding, dilation, G) and min(N, C, H, W) > 0:
-        raise ValueError(f"not a grouped conv the HIP entry points take: input {tuple(x_shape)}, weight {tuple(weight.shape)}, "
-                         f"groups {G}, stride {stride}, padding {padding}, dilation {dilation}")
-    w = weight.detach()
-    w = w if w.is_contiguous() else w.contiguous()
-    Cout, cin_g, kh, kw = (int(v) for v in weight.shape)
-    (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
-    Ho, Wo = (conv_out_hw(H, W, kh, kw, (sh, sw), (ph, pw), (dh, dw)) if min(H, W) > 0 else (0, 0))
-    return w, (N, G, cin_g, Cout // G, H, W, kh, kw, sh, sw, ph, pw, dh, dw), (N, Cout, max(Ho, 0), max(Wo, 0))
-
-
-def grouped_conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1,
-                   groups: int = 1, kind: str = "raw", out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """F.conv2d(x, Q(weight), bias, stride, padding, dilation, groups) for x [N, G * cin_g, H, W] fp32 (NCHW or channels-last) and
-    weight [G * cout_g, cin_g, kh, kw]; Q = ``kind`` ("raw" | "binary" | "ternary") is applied to the taps inside the one launch
-    (qt_gconv2d_f32).  The result has the layout of x, or is written into ``out``.  Bit-reproducible: +0 start, the group's input
-    channels ascending and the taps in row-major order inside each, one multiply and one add per term, out-of-image taps skipped,
-    bias last.  A bf16 / fp16 ``x`` (with a weight of the same dtype, or fp32 as under autocast; ``bias`` stays an fp32 vector) runs
-    qt_gconv2d_h: the same fp32 arithmetic on the exactly upcast elements, rounded once to nearest even into a result of x's dtype."""
-    x = _dw_operand(x, "input", half=True)
-    w, geom, y_shape = _gc_geometry(x.shape, weight, stride, padding, dilation, groups, half=True)
-    codes = _dw_half_codes(x, w)
-    bias = _check_bias(bias, y_shape[1], x.device)
-    y = _dw_result(out, y_shape, x, "out", x.dtype)
-    if y.numel() == 0 or x.numel() == 0:
-        return y
-    tail = (*geom, *_dw_strides(x.shape, _dw_channels_last(x)), *_dw_strides(y.shape, _dw_channels_last(y)), DW_KINDS[kind],
-            _stream(x.device))
-    with _on(x.device):
-        if codes is None:
-            _lib.call("qt_gconv2d_f32", _p(x), _p(w), _p(bias), _p(y), *tail)
-        else:
-            _lib.call("qt_gconv2d_h", _p(x), codes[0], _p(w), codes[1], _p(bias), _p(y), *tail)
-    return y
-
-
-#: input channels per group the grouped plane kernel takes: a group's operand at one tap is a bit field of ONE plane word
-GC_PLANE_CIN_G = (2, 4, 8)
-
-
-def grouped_planes_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
-    """``grouped_applicable`` and 2, 4 or 8 input channels per group: the grouped convs that run on the bit planes of a +-1
-    activation (``grouped_conv2d_sign`` / ``grouped_conv2d_from_bits``).  A pure function of the shapes."""
-    return (grouped_applicable(x_shape, w_shape, stride, padding, dilation, groups) and int(w_shape[1]) in GC_PLANE_CIN_G)
-
-
-def _gc_planes_geometry(planes, shape, weight, stride, padding, dilation, groups):
-    x_shape = _dw_plane_input(planes, shape)
-    w, geom, y_shape = _gc_geometry(x_shape, weight, stride, padding, dilation, groups)
-    if geom[2] not in GC_PLANE_CIN_G:
-        raise ValueError(f"the grouped plane kernel takes 2, 4 or 8 input channels per group, got {geom[2]}")
-    if w.device != planes.device:
-        raise ValueError("input and weight are on different devices")
-    return w, geom, y_shape
+    return _streaming_conv2d_sign(_DW, x, weight, bias, alpha, beta, stride, padding, dilation, None, kind, shape, out_halo, with_bits,
+                                  out_sign, out_nib)
 
 
 def grouped_conv2d_sign(planes: BitPlanes, weight: torch.Tensor, bias: Optional[torch.Tensor], alpha: torch.Tensor, beta: torch.Tensor,
@@ -4597,30 +4412,42 @@ def grouped_conv2d_sign(planes: BitPlanes, weight: torch.Tensor, bias: Optional[
     classified to -1 / 0 / +1 (``kind``; "raw": by their sign).  For an on-grid weight the bits are those of the pinned fp32
     arithmetic of ``grouped_conv2d`` on the decoded image.  cin_g in {2, 4, 8} (``grouped_planes_applicable``).  Returns and the
     ``out_*`` arguments as ``depthwise_conv2d_sign``."""
-    w, geom, y_shape = _gc_planes_geometry(planes, shape, weight, stride, padding, dilation, groups)
+    return _streaming_conv2d_sign(_GC, planes, weight, bias, alpha, beta, stride, padding, dilation, groups, kind, shape, out_halo,
+                                  with_bits, out_sign, out_nib)
+
+
+def _streaming_result(out: Optional[torch.Tensor], y_shape, channels_last: bool, w: torch.Tensor) -> torch.Tensor:
+    """The fp32 result of an entry that reads a plane: ``out`` checked, or a new tensor in NCHW or ``channels_last`` storage."""
+    if out is not None:
+        return _dw_result(out, y_shape, w, "out")
+    return torch.empty(y_shape, dtype=torch.float32, device=w.device,
+                       memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+
+
+def _streaming_conv2d_from_bits(fam: _Streaming, planes, shape, weight, bias, stride, padding, dilation, groups, kind="raw",
+                                channels_last=False, out=None):
+    x_shape = _dw_plane_input(planes, shape)
     dev = planes.device
-    N, Cout, Ho, Wo = y_shape
-    bias = _check_bias(bias, Cout, dev)
-    alpha, beta, _ = epilogue_affine((alpha, beta), Cout, dev)
-    if alpha is None or beta is None:
-        raise TypeError("alpha and beta: expected fp32 device vectors")
-    hy, hx = (0, 0) if out_halo is None else (int(v) for v in _pairs(out_halo))
-    if hy < 0 or hx < 0:
-        raise ValueError("out_halo must not be negative")
-    bits = nib = None
-    if out_halo is None or with_bits:
-        bits = BitPlanes(sign=_dw_plane_out(out_sign, N * Ho * Wo, packed_ld(Cout), dev, "out_sign"), rows=N * Ho * Wo, K=Cout)
-    if out_halo is not None:
-        rows = N * (Ho + 2 * hy) * (Wo + 2 * hx)
-        nib = NibPlanes(words=_dw_plane_out(out_nib, rows, pixel_ld_nib(Cout), dev, "out_nib"), rows=rows, K=Cout)
-    if N * Cout * Ho * Wo > 0:
-        with _on(dev):
-            _lib.call("qt_gconv2d_sign", _p(planes.sign), int(planes.ld), _p(w), _p(bias), _p(alpha), _p(beta),
-                      _p(bits.sign) if bits is not None else None, bits.ld if bits is not None else 0,
-                      _p(nib.words) if nib is not None else None, nib.ld if nib is not None else 0, hy, hx, *geom, DW_KINDS[kind],
-                      _stream(dev))
-    out = bits if nib is None else ((bits, nib) if bits is not None else nib)
-    return out, (Ho, Wo)
+    w, geom, y_shape = fam.planes_geometry(x_shape, weight, stride, padding, dilation, groups)
+    if w.device != dev:
+        raise ValueError("input and weight are on different devices")
+    bias = _check_bias(bias, y_shape[1], dev)
+    y = _streaming_result(out, y_shape, channels_last, w)
+    if y.numel() == 0:
+        return y
+    with _on(dev):
+        _lib.call(fam.entry["bits_f32"], _p(planes.sign), int(planes.ld), _p(w), _p(bias), _p(y), *geom,
+                  *_dw_strides(y.shape, _dw_channels_last(y)), DW_KINDS[kind], _stream(dev))
+    return y
+
+
+def depthwise_conv2d_from_bits(planes: BitPlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1,
+                               padding=0, dilation=1, kind: str = "raw", channels_last: bool = False,
+                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``depthwise_conv2d`` of the +-1 activation that exists only as ``planes`` (sign-only NHWC pixel plane, logical ``shape``
+    (N, C, H, W)): the fp32 result, bit for bit that of the fp32 +-1 image, in NCHW or ``channels_last`` storage or written into
+    ``out`` (qt_dwconv2d_bits_f32, one launch)."""
+    return _streaming_conv2d_from_bits(_DW, planes, shape, weight, bias, stride, padding, dilation, None, kind, channels_last, out)
 
 
 def grouped_conv2d_from_bits(planes: BitPlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1, padding=0,
@@ -4629,55 +4456,38 @@ def grouped_conv2d_from_bits(planes: BitPlanes, shape, weight: torch.Tensor, bia
     """``grouped_conv2d`` of the +-1 activation that exists only as ``planes`` (sign-only NHWC pixel plane, logical ``shape``
     (N, G * cin_g, H, W)), cin_g in {2, 4, 8}: the fp32 result — for an on-grid weight bit for bit that of the fp32 +-1 image — in
     NCHW or ``channels_last`` storage or written into ``out`` (qt_gconv2d_bits_f32, one launch)."""
-    w, geom, y_shape = _gc_planes_geometry(planes, shape, weight, stride, padding, dilation, groups)
-    dev = planes.device
-    bias = _check_bias(bias, y_shape[1], dev)
-    if out is None:
-        y = torch.empty(y_shape, dtype=torch.float32, device=dev,
-                        memory_format=torch.channels_last if channels_last else torch.contiguous_format)
-    else:
-        y = _dw_result(out, y_shape, w, "out")
-    if y.numel() == 0:
-        return y
-    with _on(dev):
-        _lib.call("qt_gconv2d_bits_f32", _p(planes.sign), int(planes.ld), _p(w), _p(bias), _p(y), *geom,
-                  *_dw_strides(y.shape, _dw_channels_last(y)), DW_KINDS[kind], _stream(dev))
-    return y
+    return _streaming_conv2d_from_bits(_GC, planes, shape, weight, bias, stride, padding, dilation, groups, kind, channels_last, out)
 
 
-def grouped_codes_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
-    """The grouped convs that run on the int8 code plane of a DoReFa activation (``grouped_conv2d_codes`` /
-    ``grouped_conv2d_from_codes``): those ``grouped_applicable`` takes — any cin_g the fp32 entry takes, any cout_g; the pixel rows of
-    the un-bordered planes are bounded by the tensors' elements.  A pure function of the shapes: it does not know the halos, so a
-    plane whose border (up to 64 pixels a side) brings it to 2^31 pixel rows or more passes here and is refused by the entry
-    (QT_ERR_UNSUPPORTED, raised by the wrapper) — as with ``depthwise_applicable`` and the depthwise code entries."""
-    return grouped_applicable(x_shape, w_shape, stride, padding, dilation, groups)
+def _dw_code_input(codes: CodePlanes, shape, in_halo):
+    """``codes`` checked as the int8 NHWC pixel plane (16-byte rows, zero border of ``in_halo`` pixels) of a DoReFa activation of
+    logical ``shape`` (N, C, H, W); returns the shape and the halo as ints."""
+    if not isinstance(codes, CodePlanes):
+        raise TypeError(f"input: expected CodePlanes, got {type(codes)}")
+    if shape is None or len(shape) != 4:
+        raise ValueError("a CodePlanes input needs the logical (N, C, H, W) shape")
+    N, C, H, W = map(int, shape)
+    hy, hx = _pairs(in_halo)
+    _require(codes.codes, "input codes", torch.int8)
+    rows = N * (H + 2 * hy) * (W + 2 * hx)
+    ld = int(codes.codes.shape[1]) if codes.codes.dim() == 2 else 0
+    if (hy < 0 or hx < 0 or codes.rows != rows or codes.K != C or codes.codes.dim() != 2 or int(codes.codes.shape[0]) < rows
+            or not codes.codes.is_contiguous() or ld < code_ld_bytes(C, 16) or ld % 16):
+        raise ValueError(f"input: expected the int8 NHWC code plane (16-byte rows) of an {(N, C, H, W)} activation with halo {(hy, hx)}")
+    return (N, C, H, W), (hy, hx)
 
 
-def _gc_codes_geometry(codes, shape, in_halo, weight, stride, padding, dilation, groups):
-    x_shape, halo = _dw_code_input(codes, shape, in_halo)
-    w, geom, y_shape = _gc_geometry(x_shape, weight, stride, padding, dilation, groups)
-    if w.device != codes.device:
-        raise ValueError("input and weight are on different devices")
-    return w, geom, y_shape, halo
-
-
-def grouped_conv2d_codes(codes: CodePlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor], epi: CodeEpilogue, stride=1,
-                         padding=0, dilation=1, groups: int = 1, in_halo=(0, 0), out: Optional[torch.Tensor] = None) -> CodePlanes:
-    """Grouped conv (``grouped_conv2d``'s pinned fp32 arithmetic on the image fl(inv_n * code)) -> BatchNorm -> [ReLU] -> k-bit
-    DoReFa quantiser, from the int8 code plane ``codes`` (logical ``shape`` (N, G * cin_g, H, W), zero border of ``in_halo`` pixels
-    that is never read) to the next code plane in ONE launch (qt_gconv2d_codes): no fp32 activation exists.  ``epi``, ``out`` and the
-    result as ``depthwise_conv2d_codes``: a ``CodeEpilogue`` without a residual, whose ``out_halo`` is the zero border of the
-    produced plane [N*(Ho+2hy)*(Wo+2hx), code_ld_bytes(G*cout_g, 16)], of which the launch writes every byte."""
-    w, geom, y_shape, (ihy, ihx) = _gc_codes_geometry(codes, shape, in_halo, weight, stride, padding, dilation, groups)
-    dev = codes.device
+def _streaming_code_epilogue(fam: _Streaming, epi, codes: CodePlanes, bias, y_shape, dev, out):
+    """``epi`` checked as the code epilogue of a streaming conv with the result ``y_shape`` — no residual, no ReLU in front of the
+    BatchNorm —, with ``bias`` and the ``out`` plane: ``(bias, relu, alpha, beta, stats, (ohy, ohx), flag, out, rows, ldc)``, the
+    flag being the epilogue's, the input plane's or a fresh one and ``out`` a new [rows, ldc] int8 tensor when not given."""
     if not isinstance(epi, CodeEpilogue):
         raise TypeError(f"epi: expected a CodeEpilogue, got {type(epi)}")
     if epi.res_f32 is not None or epi.res_codes is not None or epi.res_affine is not None or any(epi.res_halo):
-        raise ValueError("the grouped code epilogue takes no residual")
+        raise ValueError(f"the {fam.noun} code epilogue takes no residual")
     relu = relu_mode(epi.relu)
     if relu == 2:
-        raise ValueError("the grouped code epilogue has no ReLU in front of the BatchNorm (relu='pre')")
+        raise ValueError(f"the {fam.noun} code epilogue has no ReLU in front of the BatchNorm (relu='pre')")
     if not 2 <= int(epi.bit_width) <= 8:
         raise ValueError("int8 code planes exist for 2 <= bit_width <= 8")
     N, Cout, Ho, Wo = y_shape
@@ -4689,8 +4499,8 @@ def grouped_conv2d_codes(codes: CodePlanes, shape, weight: torch.Tensor, bias: O
     if epi.bn_stats is not None:
         stats = _require(epi.bn_stats, "bn_stats").contiguous()
         if stats.numel() != 2 * Cout or stats.device != dev:
-            raise ValueError("bn_stats must hold [mean | rs]: 2 * G * cout_g values on the input's device")
-    ohy, ohx = (int(v) for v in _pairs(epi.out_halo))
+            raise ValueError(f"bn_stats must hold [mean | rs]: 2 * {fam.cout} values on the input's device")
+    ohy, ohx = _pairs(epi.out_halo)
     if ohy < 0 or ohx < 0:
         raise ValueError("out_halo must not be negative")
     flag = epi.overflow if epi.overflow is not None else codes.overflow
@@ -4704,11 +4514,73 @@ def grouped_conv2d_codes(codes: CodePlanes, shape, weight: torch.Tensor, bias: O
         _require(out, "out", torch.int8)
         if tuple(out.shape) != (rows, ldc) or not out.is_contiguous() or out.device != dev:
             raise ValueError(f"out: expected a contiguous int8 tensor [{rows}, {ldc}] on {dev}, got {tuple(out.shape)} on {out.device}")
+    return bias, relu, alpha, beta, stats, (ohy, ohx), flag, out, rows, ldc
+
+
+def _streaming_conv2d_codes(fam: _Streaming, codes, shape, weight, bias, epi, stride, padding, dilation, groups, in_halo, out):
+    x_shape, (ihy, ihx) = _dw_code_input(codes, shape, in_halo)
+    dev = codes.device
+    w, geom, y_shape = fam.geometry(x_shape, weight, stride, padding, dilation, groups)
+    if w.device != dev:
+        raise ValueError("input and weight are on different devices")
+    bias, relu, alpha, beta, stats, (ohy, ohx), flag, out, rows, ldc = _streaming_code_epilogue(fam, epi, codes, bias, y_shape, dev, out)
+    N, Cout, Ho, Wo = y_shape
     if N * Cout * Ho * Wo > 0:
         with _on(dev):
-            _lib.call("qt_gconv2d_codes", _p(codes.codes), int(codes.codes.shape[1]), ihy, ihx, float(codes.inv_n), _p(w), _p(bias),
+            _lib.call(fam.entry["codes"], _p(codes.codes), int(codes.codes.shape[1]), ihy, ihx, float(codes.inv_n), _p(w), _p(bias),
                       _p(alpha), _p(beta), _p(stats), relu, int(epi.bit_width), _p(out), ldc, ohy, ohx, _p(flag), *geom, _stream(dev))
     return CodePlanes(codes=out, rows=rows, K=Cout, inv_n=inv_levels(epi.bit_width), bit_width=int(epi.bit_width), overflow=flag)
+
+
+def depthwise_conv2d_codes(codes: CodePlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor], epi: CodeEpilogue, stride=1,
+                           padding=0, dilation=1, in_halo=(0, 0), out: Optional[torch.Tensor] = None) -> CodePlanes:
+    """Depthwise conv (``depthwise_conv2d``'s pinned fp32 arithmetic on the image fl(inv_n * code)) -> BatchNorm -> [ReLU] -> k-bit
+    DoReFa quantiser, from the int8 code plane ``codes`` (logical ``shape`` (N, C, H, W), zero border of ``in_halo`` pixels that is
+    never read) to the next code plane in ONE launch (qt_dwconv2d_codes): no fp32 activation exists.  ``epi``: a ``CodeEpilogue``
+    without a residual — folded (alpha, beta), or the device form with ``bn_stats``; its ``out_halo`` is the zero border of the
+    produced plane [N*(Ho+2hy)*(Wo+2hx), code_ld_bytes(C*m, 16)], of which the launch writes every byte; ``overflow`` the chain's
+    int8 range flag (None: the input plane's, or a fresh one).  ``out``: an existing contiguous int8 [rows, ld] tensor the plane is
+    written into (no prior content needed)."""
+    return _streaming_conv2d_codes(_DW, codes, shape, weight, bias, epi, stride, padding, dilation, None, in_halo, out)
+
+
+def grouped_conv2d_codes(codes: CodePlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor], epi: CodeEpilogue, stride=1,
+                         padding=0, dilation=1, groups: int = 1, in_halo=(0, 0), out: Optional[torch.Tensor] = None) -> CodePlanes:
+    """Grouped conv (``grouped_conv2d``'s pinned fp32 arithmetic on the image fl(inv_n * code)) -> BatchNorm -> [ReLU] -> k-bit
+    DoReFa quantiser, from the int8 code plane ``codes`` (logical ``shape`` (N, G * cin_g, H, W), zero border of ``in_halo`` pixels
+    that is never read) to the next code plane in ONE launch (qt_gconv2d_codes): no fp32 activation exists.  ``epi``, ``out`` and the
+    result as ``depthwise_conv2d_codes``: a ``CodeEpilogue`` without a residual, whose ``out_halo`` is the zero border of the
+    produced plane [N*(Ho+2hy)*(Wo+2hx), code_ld_bytes(G*cout_g, 16)], of which the launch writes every byte."""
+    return _streaming_conv2d_codes(_GC, codes, shape, weight, bias, epi, stride, padding, dilation, groups, in_halo, out)
+
+
+def _streaming_conv2d_from_codes(fam: _Streaming, codes, shape, weight, bias, stride, padding, dilation, groups, in_halo=(0, 0),
+                                 channels_last=True, out=None, flagged=True):
+    x_shape, (ihy, ihx) = _dw_code_input(codes, shape, in_halo)
+    dev = codes.device
+    w, geom, y_shape = fam.geometry(x_shape, weight, stride, padding, dilation, groups)
+    if w.device != dev:
+        raise ValueError("input and weight are on different devices")
+    bias = _check_bias(bias, y_shape[1], dev)
+    y = _streaming_result(out, y_shape, channels_last, w)
+    if y.numel() == 0:
+        return y
+    flag = codes.overflow if flagged else None
+    with _on(dev):
+        _lib.call(fam.entry["codes_f32"], _p(codes.codes), int(codes.codes.shape[1]), ihy, ihx, float(codes.inv_n), _p(w), _p(bias),
+                  _p(flag), _p(y), *geom, *_dw_strides(y.shape, _dw_channels_last(y)), _stream(dev))
+    return y
+
+
+def depthwise_conv2d_from_codes(codes: CodePlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1,
+                                padding=0, dilation=1, in_halo=(0, 0), channels_last: bool = True, out: Optional[torch.Tensor] = None,
+                                flagged: bool = True) -> torch.Tensor:
+    """``depthwise_conv2d`` of the DoReFa activation that exists only as the code plane ``codes`` (see ``depthwise_conv2d_codes``):
+    the fp32 result, bit for bit that of the fp32 image fl(inv_n * code), in ``channels_last`` or NCHW storage or written into ``out``
+    (qt_dwconv2d_codes_f32, one launch).  ``flagged``: a raised int8 range flag of the plane's chain makes every value NaN, on the
+    device."""
+    return _streaming_conv2d_from_codes(_DW, codes, shape, weight, bias, stride, padding, dilation, None, in_halo, channels_last, out,
+                                        flagged)
 
 
 def grouped_conv2d_from_codes(codes: CodePlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1,
@@ -4718,31 +4590,13 @@ def grouped_conv2d_from_codes(codes: CodePlanes, shape, weight: torch.Tensor, bi
     fp32 result, bit for bit that of the fp32 image fl(inv_n * code), in ``channels_last`` or NCHW storage or written into ``out``
     (qt_gconv2d_codes_f32, one launch).  ``flagged``: a raised int8 range flag of the plane's chain makes every value NaN, on the
     device."""
-    w, geom, y_shape, (ihy, ihx) = _gc_codes_geometry(codes, shape, in_halo, weight, stride, padding, dilation, groups)
-    dev = codes.device
-    bias = _check_bias(bias, y_shape[1], dev)
-    if out is None:
-        y = torch.empty(y_shape, dtype=torch.float32, device=dev,
-                        memory_format=torch.channels_last if channels_last else torch.contiguous_format)
-    else:
-        y = _dw_result(out, y_shape, w, "out")
-    if y.numel() == 0:
-        return y
-    flag = codes.overflow if flagged else None
-    with _on(dev):
-        _lib.call("qt_gconv2d_codes_f32", _p(codes.codes), int(codes.codes.shape[1]), ihy, ihx, float(codes.inv_n), _p(w), _p(bias),
-                  _p(flag), _p(y), *geom, *_dw_strides(y.shape, _dw_channels_last(y)), _stream(dev))
-    return y
+    return _streaming_conv2d_from_codes(_GC, codes, shape, weight, bias, stride, padding, dilation, groups, in_halo, channels_last, out,
+                                        flagged)
 
 
-def grouped_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_output: torch.Tensor, stride=1, padding=0, dilation=1,
-                              groups: int = 1, kind: str = "raw", channels_last: Optional[bool] = None,
-                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Gradient of ``grouped_conv2d`` with respect to x: a gather over the group's output channels (outermost) and the taps
-    (row-major) with the forward's arithmetic rules, no atomics (qt_gconv2d_grad_input_f32; qt_gconv2d_grad_input_h for a bf16 /
-    fp16 ``grad_output``, whose dtype the result then has).  The result has the layout of ``grad_output`` unless ``channels_last``
-    says otherwise, or is written into ``out``."""
-    w, geom, y_shape = _gc_geometry(input_shape, weight, stride, padding, dilation, groups, half=True)
+def _streaming_conv2d_grad_input(fam: _Streaming, input_shape, weight, grad_output, stride, padding, dilation, groups, kind="raw",
+                                 channels_last=None, out=None):
+    w, geom, y_shape = fam.geometry(input_shape, weight, stride, padding, dilation, groups, True)
     go = _dw_operand(grad_output, "grad_output", y_shape, half=True)
     codes = _dw_half_codes(go, w)
     if out is None:
@@ -4759,37 +4613,62 @@ def grouped_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_output: to
             _stream(go.device))
     with _on(go.device):
         if codes is None:
-            _lib.call("qt_gconv2d_grad_input_f32", _p(go), _p(w), _p(gx), *tail)
+            _lib.call(fam.entry["grad_input_f32"], _p(go), _p(w), _p(gx), *tail)
         else:
-            _lib.call("qt_gconv2d_grad_input_h", _p(go), codes[0], _p(w), codes[1], _p(gx), *tail)
+            _lib.call(fam.entry["grad_input_h"], _p(go), codes[0], _p(w), codes[1], _p(gx), *tail)
     return gx
+
+
+def depthwise_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_output: torch.Tensor, stride=1, padding=0, dilation=1,
+                                kind: str = "raw", channels_last: Optional[bool] = None,
+                                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient of ``depthwise_conv2d`` with respect to x: a gather over the multiplier index (outermost) and the taps (row-major)
+    with the forward's arithmetic rules, no atomics (qt_dwconv2d_grad_input_f32; qt_dwconv2d_grad_input_h for a bf16 / fp16
+    ``grad_output``, whose dtype the result then has).  The result has the layout of ``grad_output`` unless ``channels_last`` says
+    otherwise, or is written into ``out``."""
+    return _streaming_conv2d_grad_input(_DW, input_shape, weight, grad_output, stride, padding, dilation, None, kind, channels_last, out)
+
+
+def grouped_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_output: torch.Tensor, stride=1, padding=0, dilation=1,
+                              groups: int = 1, kind: str = "raw", channels_last: Optional[bool] = None,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient of ``grouped_conv2d`` with respect to x: a gather over the group's output channels (outermost) and the taps
+    (row-major) with the forward's arithmetic rules, no atomics (qt_gconv2d_grad_input_f32; qt_gconv2d_grad_input_h for a bf16 /
+    fp16 ``grad_output``, whose dtype the result then has).  The result has the layout of ``grad_output`` unless ``channels_last``
+    says otherwise, or is written into ``out``."""
+    return _streaming_conv2d_grad_input(_GC, input_shape, weight, grad_output, stride, padding, dilation, groups, kind, channels_last,
+                                        out)
+
+
+def _streaming_grad_weight_work_floats(fam: _Streaming, geom) -> int:
+    """``geom``: the geometry arguments of the family's C calls, unchecked (the entry validates)."""
+    entry = fam.entry["grad_weight_work_floats"]
+    n = int(getattr(_lib.load(), entry)(*geom))
+    if n < 0:
+        raise _lib.QtStatusError(f"{entry} failed: {_lib.strerror(n)} (qt_status {n})")
+    return n
+
+
+def depthwise_grad_weight_work_floats(input_shape, weight_shape, stride=1, padding=0, dilation=1) -> int:
+    """fp32 elements of workspace ``depthwise_conv2d_grad_weight`` needs (qt_dwconv2d_grad_weight_work_floats)."""
+    N, C, H, W = (int(v) for v in input_shape)
+    return _streaming_grad_weight_work_floats(_DW, (N, C, int(weight_shape[0]) // max(C, 1), H, W, int(weight_shape[2]),
+                                                    int(weight_shape[3]), *_pairs(stride), *_pairs(padding), *_pairs(dilation)))
 
 
 def grouped_grad_weight_work_floats(input_shape, weight_shape, stride=1, padding=0, dilation=1, groups: int = 1) -> int:
     """fp32 elements of workspace ``grouped_conv2d_grad_weight`` needs (qt_gconv2d_grad_weight_work_floats)."""
     N, _C, H, W = (int(v) for v in input_shape)
     G = int(groups)
-    (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
-    n = int(_lib.load().qt_gconv2d_grad_weight_work_floats(N, G, int(weight_shape[1]), int(weight_shape[0]) // max(G, 1), H, W,
-                                                           int(weight_shape[2]), int(weight_shape[3]), sh, sw, ph, pw, dh, dw))
-    if n < 0:
-        raise _lib.QtStatusError(f"qt_gconv2d_grad_weight_work_floats failed: {_lib.strerror(n)} (qt_status {n})")
-    return n
+    return _streaming_grad_weight_work_floats(_GC, (N, G, int(weight_shape[1]), int(weight_shape[0]) // max(G, 1), H, W,
+                                                    int(weight_shape[2]), int(weight_shape[3]), *_pairs(stride), *_pairs(padding),
+                                                    *_pairs(dilation)))
 
 
-def grouped_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, weight: torch.Tensor, stride=1, padding=0, dilation=1,
-                               groups: int = 1, ste_threshold: float = 0.0, want_bias: bool = False,
-                               out: Optional[torch.Tensor] = None, out_bias: Optional[torch.Tensor] = None,
-                               workspace: Optional[torch.Tensor] = None):
-    """Gradient of ``grouped_conv2d`` with respect to the weight, shaped like ``weight``, and — ``want_bias`` or ``out_bias`` — the
-    per-channel sum of ``grad_output`` from the same pass (else None): ``(grad_weight, grad_bias)``.  Two launches inside one call,
-    no atomics: partials per (split, output channel, input channel of the group, tap) into ``workspace``
-    (``grouped_grad_weight_work_floats`` fp32 elements; allocated when not given), then the splits in index order; equal inputs
-    give equal bits.  ``ste_threshold`` > 0 zeroes the entries where the UNquantised ``|weight|`` exceeds it (1.001 for the sign
-    families).  bf16 / fp16 ``x`` and ``grad_output`` (one dtype) run qt_gconv2d_grad_weight_h; both gradients have the WEIGHT's
-    dtype (fp32 under autocast), rounded once from fp32."""
+def _streaming_conv2d_grad_weight(fam: _Streaming, x, grad_output, weight, stride, padding, dilation, groups, ste_threshold=0.0,
+                                  want_bias=False, out=None, out_bias=None, workspace=None):
     x = _dw_operand(x, "input", half=True)
-    w, geom, y_shape = _gc_geometry(x.shape, weight, stride, padding, dilation, groups, half=True)
+    w, geom, y_shape = fam.geometry(x.shape, weight, stride, padding, dilation, groups, True)
     go = _dw_operand(grad_output, "grad_output", y_shape, half=True)
     if go.device != x.device:
         raise ValueError("input and grad_output are on different devices")
@@ -4813,7 +4692,7 @@ def grouped_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, weigh
     if go.numel() == 0 or x.numel() == 0:
         gw.zero_()
         return gw, (gb.zero_() if gb is not None else None)
-    need = grouped_grad_weight_work_floats(x.shape, weight.shape, stride, padding, dilation, groups)
+    need = _streaming_grad_weight_work_floats(fam, geom)
     if workspace is None:
         workspace = torch.empty((need,), dtype=torch.float32, device=x.device)
     else:
@@ -4824,10 +4703,38 @@ def grouped_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, weigh
             *_dw_strides(x.shape, _dw_channels_last(x)), float(ste_threshold), _stream(x.device))
     with _on(x.device):
         if codes is None:
-            _lib.call("qt_gconv2d_grad_weight_f32", _p(go), _p(x), _p(w), _p(gw), _p(gb), *tail)
+            _lib.call(fam.entry["grad_weight_f32"], _p(go), _p(x), _p(w), _p(gw), _p(gb), *tail)
         else:
-            _lib.call("qt_gconv2d_grad_weight_h", _p(go), _p(x), codes[0], _p(w), _p(gw), _p(gb), codes[1], *tail)
+            _lib.call(fam.entry["grad_weight_h"], _p(go), _p(x), codes[0], _p(w), _p(gw), _p(gb), codes[1], *tail)
     return gw, gb
+
+
+def depthwise_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, weight: torch.Tensor, stride=1, padding=0, dilation=1,
+                                 ste_threshold: float = 0.0, want_bias: bool = False, out: Optional[torch.Tensor] = None,
+                                 out_bias: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """Gradient of ``depthwise_conv2d`` with respect to the weight, shaped like ``weight``, and — ``want_bias`` or ``out_bias`` —
+    the per-channel sum of ``grad_output`` from the same pass (else None): ``(grad_weight, grad_bias)``.  Two launches inside one
+    call, no atomics: partials per (split, channel, tap) into ``workspace`` (``depthwise_grad_weight_work_floats`` fp32 elements;
+    allocated when not given), then the splits in index order; equal inputs give equal bits.  ``ste_threshold`` > 0 zeroes the
+    entries where the UNquantised ``|weight|`` exceeds it (1.001 for the sign families).  bf16 / fp16 ``x`` and ``grad_output`` (one
+    dtype) run qt_dwconv2d_grad_weight_h; both gradients have the WEIGHT's dtype (fp32 under autocast), rounded once from fp32."""
+    return _streaming_conv2d_grad_weight(_DW, x, grad_output, weight, stride, padding, dilation, None, ste_threshold, want_bias, out,
+                                         out_bias, workspace)
+
+
+def grouped_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, weight: torch.Tensor, stride=1, padding=0, dilation=1,
+                               groups: int = 1, ste_threshold: float = 0.0, want_bias: bool = False,
+                               out: Optional[torch.Tensor] = None, out_bias: Optional[torch.Tensor] = None,
+                               workspace: Optional[torch.Tensor] = None):
+    """Gradient of ``grouped_conv2d`` with respect to the weight, shaped like ``weight``, and — ``want_bias`` or ``out_bias`` — the
+    per-channel sum of ``grad_output`` from the same pass (else None): ``(grad_weight, grad_bias)``.  Two launches inside one call,
+    no atomics: partials per (split, output channel, input channel of the group, tap) into ``workspace``
+    (``grouped_grad_weight_work_floats`` fp32 elements; allocated when not given), then the splits in index order; equal inputs
+    give equal bits.  ``ste_threshold`` > 0 zeroes the entries where the UNquantised ``|weight|`` exceeds it (1.001 for the sign
+    families).  bf16 / fp16 ``x`` and ``grad_output`` (one dtype) run qt_gconv2d_grad_weight_h; both gradients have the WEIGHT's
+    dtype (fp32 under autocast), rounded once from fp32."""
+    return _streaming_conv2d_grad_weight(_GC, x, grad_output, weight, stride, padding, dilation, groups, ste_threshold, want_bias, out,
+                                         out_bias, workspace)
 
 
 # ---- residual blocks of the sign chain ---------------------------------------------------------------------------------------------
@@ -4902,12 +4809,7 @@ def bn_add_sign(x2: torch.Tensor, shape, weight: torch.Tensor, bias: torch.Tenso
         raise ValueError("out_halo must not be negative")
     if s2 is None and not want_sign and out_halo is None:
         raise ValueError("bn_add_sign: nothing to write (no sum, no sign plane, no nibble plane)")
-    bits = nib = None
-    if want_sign:
-        bits = BitPlanes(sign=torch.empty((rows, packed_ld(C)), dtype=torch.int32, device=dev), rows=rows, K=C)
-    if out_halo is not None:
-        prow = N * (Ho + 2 * hy) * (Wo + 2 * hx)
-        nib = NibPlanes(words=torch.empty((prow, pixel_ld_nib(C)), dtype=torch.int32, device=dev), rows=prow, K=C)
+    bits, nib = _sign_planes_out(N, C, Ho, Wo, dev, want_sign, None if out_halo is None else (hy, hx))
     if rows * C > 0:
         with _on(dev):
             _lib.call("qt_bn_add_sign_f32", _p(x2), ldx, _p(weight), _p(bias), _p(bn_stats), _p(residual), *rs, ht, lo, hi, _p(s2), *ss,
