@@ -95,15 +95,17 @@ def nib_to_bits(nib: torch.Tensor) -> torch.Tensor:
     return nib == NIB_NEG
 
 
-def conv64(x: torch.Tensor, w: torch.Tensor, stride=1, padding=0) -> torch.Tensor:
-    """conv2d [n, C, H, W] x [Cout, C, kh, kw] -> [n, Cout, Ho, Wo] in float64 via unfold + matmul, no bias."""
+def conv64(x: torch.Tensor, w: torch.Tensor, stride=1, padding=0, dilation=1) -> torch.Tensor:
+    """conv2d [n, C, H, W] x [Cout, C, kh, kw] -> [n, Cout, Ho, Wo] in float64 via unfold + matmul, no bias.  ``stride``,
+    ``padding`` and ``dilation``: an int or an (h, w) pair each; the kernel need not be square."""
     n, C, H, W = (int(v) for v in x.shape)
     Cout, Cw, kh, kw = (int(v) for v in w.shape)
     assert Cw == C
     sh, sw = (stride, stride) if isinstance(stride, int) else stride
     ph, pw = (padding, padding) if isinstance(padding, int) else padding
-    Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
-    cols = F.unfold(x.to(torch.float64), (kh, kw), padding=(ph, pw), stride=(sh, sw))       # [n, C*kh*kw, Ho*Wo]
+    dh, dw = (dilation, dilation) if isinstance(dilation, int) else dilation
+    Ho, Wo = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    cols = F.unfold(x.to(torch.float64), (kh, kw), dilation=(dh, dw), padding=(ph, pw), stride=(sh, sw))       # [n, C*kh*kw, Ho*Wo]
     return torch.matmul(w.to(torch.float64).reshape(Cout, C * kh * kw), cols).reshape(n, Cout, Ho, Wo)
 
 

@@ -124,9 +124,13 @@ def switches(sw):
             setattr(homes[k], k, v)
 
 
-def operands(kind, geom, batch, dev, exact=False):
+def operands(kind, geom, batch, dev, exact=False, given=None):
     """(image, weight, bias, alpha, beta) from fixed seeds; ``exact``: an image of multiples of 1/8, whose partial sums against
-    +-1 / 0 weights are exact in fp32 whatever the order of the accumulation."""
+    +-1 / 0 weights are exact in fp32 whatever the order of the accumulation.  ``given``: the caller's own device operands
+    (image, weight, bias, alpha, beta[, BatchNorm (running_mean, running_var, weight, bias) of a block]) instead, as they are
+    (tests/test_gpu_first_layer_exact.py: designed operands in the storage order under test)."""
+    if given is not None:
+        return tuple(given[:5])
     C, Cout, k = geom[:3]
     H, W = geom[6:]
     img = synth.normal(71, (batch, C, H, W))
@@ -138,7 +142,7 @@ def operands(kind, geom, batch, dev, exact=False):
     return x, w, b, alpha, beta
 
 
-def make_block(kind, geom, form, dev, w, b):
+def make_block(kind, geom, form, dev, w, b, bn_stats=None):
     C, Cout, k, st, pd, dl = geom[:6]
     cls = {"binary": BinConv2d, "ternary": TerConv2d, "xnor": XNORConv2d}[kind]
     conv = cls(C, Cout, k, stride=st, padding=pd, dilation=dl).to(dev)
@@ -147,10 +151,12 @@ def make_block(kind, geom, form, dev, w, b):
     conv.binary_input = False
     conv.eval()
     bn = torch.nn.BatchNorm2d(Cout).to(dev).eval()
-    bn.running_mean.copy_(g(synth.normal(76, (Cout,)), dev))
-    bn.running_var.copy_(g(synth.uniform(77, (Cout,), 0.5, 4), dev))
-    bn.weight.data.copy_(g(synth.normal(78, (Cout,)), dev))
-    bn.bias.data.copy_(g(synth.normal(79, (Cout,)), dev))
+    mean, var, gamma, shift = bn_stats if bn_stats is not None else (g(synth.normal(76, (Cout,)), dev), g(synth.uniform(77, (Cout,), 0.5, 4), dev),
+                                                                     g(synth.normal(78, (Cout,)), dev), g(synth.normal(79, (Cout,)), dev))
+    bn.running_mean.copy_(mean)
+    bn.running_var.copy_(var)
+    bn.weight.data.copy_(gamma)
+    bn.bias.data.copy_(shift)
     blk = FusedConvPoolBnSign(conv, bn, torch.nn.MaxPool2d(2, 2) if form == "pool" else None)
     blk.out_nib_halo = {"nib11": (1, 1), "nib22": (2, 2)}.get(form)
     return blk
@@ -164,13 +170,13 @@ def forward_epi(form, alpha, beta):
     return ops.NibEpilogue(alpha, beta, {"nib11": (1, 1), "nib22": (2, 2)}[form])
 
 
-def run_case(case, dev, exact=False):
-    """Runs one case; returns (result tensor whose bytes are digested, {entry point: calls of the forward})."""
+def run_case(case, dev, exact=False, given=None):
+    """Runs one case; returns (result tensor whose bytes are digested, {entry point: calls of the forward}).  ``given``: see ``operands``."""
     _, _, entry, kind, geom, batch, form, sw = case
     st, pd, dl = geom[3:6]
-    x, w, b, alpha, beta = operands(kind, geom, batch, dev, exact)
+    x, w, b, alpha, beta = operands(kind, geom, batch, dev, exact, given)
     with switches(sw), torch.no_grad():
-        blk = make_block(kind, geom, form, dev, w, b) if entry == "block" else None
+        blk = make_block(kind, geom, form, dev, w, b, given[5] if given is not None and len(given) > 5 else None) if entry == "block" else None
         torch.cuda.synchronize()
         before = dict(_lib.call_counts)
         if entry == "forward":
