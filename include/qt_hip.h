@@ -768,6 +768,10 @@ int qt_bn_relu_linlog_bf16_f32(const float* x, int64_t ldx, const float* weight,
                                int64_t ld_bytes, int64_t rows, int64_t C, qt_stream_t stream);
 int qt_f16_gemm(const uint32_t* Xh, int64_t ldxp, const uint32_t* Wh, int64_t ldwp, const float* bias, float scale,
                 const float* scale_dev, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, qt_stream_t stream);
+/* qt_f16_gemm on an explicit tile configuration (tests / A/B runs): variant 0 = automatic, 20 = the 256x256 ping-pong tile
+ * (qt_nib_gemm_variant's number); any other variant is QT_ERR_UNSUPPORTED, a stride the tile cannot take QT_ERR_ALIGNMENT. */
+int qt_f16_gemm_variant(int variant, const uint32_t* Xh, int64_t ldxp, const uint32_t* Wh, int64_t ldwp, const float* bias, float scale,
+                        const float* scale_dev, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, qt_stream_t stream);
 
 /* ---- training-mode chain between two binarised layers (csrc/train_chain.hip, round 3) -------------------------------------
  * [MaxPool2d(k, s)] -> BatchNorm (BATCH statistics) -> [Hardtanh(lo, hi)] -> BinaryConnectDeterministic, forward and backward:

@@ -580,6 +580,16 @@ int qt_f16_gemm(const uint32_t* Xh, int64_t ldxp, const uint32_t* Wh, int64_t ld
     return dispatch_gemm<ElemF16>(0, Xh, ldxp, Wh, ldwp, bias, scale, scale_dev, Y, ldy, M, N, K, stream);
 }
 
+int qt_f16_gemm_variant(int variant, const uint32_t* Xh, int64_t ldxp, const uint32_t* Wh, int64_t ldwp, const float* bias, float scale,
+                        const float* scale_dev, float* Y, int64_t ldy, int64_t M, int64_t N, int64_t K, qt_stream_t stream) {
+    if (variant == 0) return qt_f16_gemm(Xh, ldxp, Wh, ldwp, bias, scale, scale_dev, Y, ldy, M, N, K, stream);
+    if (variant != 20) return QT_ERR_UNSUPPORTED;      // the one explicit tile of this element: the kernel the automatic rule launches
+    const int rc = check_common(Xh, ldxp, Wh, ldwp, Y, ldy, M, N, K, (K + 1) / 2);
+    if (rc != QT_OK) return rc > 0 ? QT_OK : rc;
+    if (!gemm_pipe_ok(M, N, ldxp, ldwp)) return QT_ERR_ALIGNMENT;
+    return launch_cfg<PP256<ElemF16>>(Xh, ldxp, Wh, ldwp, bias, scale, scale_dev, Y, ldy, M, N, K, stream);
+}
+
 int qt_bf16_gemm_taps(const uint32_t* Xh, int64_t ldxp, const uint32_t* Wh, int64_t ldwp, float* Y, int64_t ldy,
                       int64_t M, int64_t N, int64_t K, int64_t tap_rows, int64_t tap_cols, int64_t nslice,
                       int64_t w_copy_bytes, int64_t w_row_bytes, int64_t y_stride, qt_stream_t stream) {

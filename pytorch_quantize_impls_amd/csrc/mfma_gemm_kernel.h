@@ -316,6 +316,12 @@ struct GemmCfg {
     // OCC_ workgroups per CU the register budget is sized for (small-accumulator tiles: 2 workgroups overlap each
     // other's prologue latency, which dominates convs whose K is only a few stages)
     static constexpr int WAVES_PER_SIMD = OCC_ * ((NWAVES + 3) / 4);
+    // the plain fp32 epilogue stores whole rows of the wave tile (256 contiguous bytes, "row-wide stores" in the kernel): the 256x256
+    // ping-pong GEMM (PP256) only.  Derived, not a parameter: the configurations' template arguments are what profilers and the
+    // route tests read, and every other configuration, the convs included, compiles its epilogue as before.
+    // The condition spells out PP256's whole shape, so that another ping-pong GEMM tile does not pick the path up unasked.
+    static constexpr bool ROW_STORES = CONV_ == 0 && PIPE_ == 2 && WM_ == 2 && WN_ == 4 && TMW_ == 4 && TNW_ == 2 && SB_ == 64 && OCC_ == 1;
+    static_assert(!ROW_STORES || NWAVES * 8192 <= NBUF * BUF, "row-wide stores: 8 KiB of dead stage buffer per wave");
     static_assert(TM % (ROWS_PER_PIECE * NWAVES) == 0 && (TN % (ROWS_PER_PIECE * NWAVES) == 0 || PIPE_ >= 1),
                   "DMA pieces divide evenly over the waves (asm-DMA pipelines: W pieces may wrap)");
 };
@@ -1427,6 +1433,48 @@ __global__ __launch_bounds__(C::NTHREADS, C::WAVES_PER_SIMD) void mfma_gemm_kern
                     for (int wc = (n0 + C::TN) >> 5; wc < ldy; ++wc) B[(int64_t)m * ldy + wc] = 0u;
             }
         }
+    } else if (C::ROW_STORES && OD == 0 && wide && m0 + C::TM <= M && n0 + C::TN <= N) {
+        // ---- row-wide stores (whole tiles; ragged tiles and unaligned Y / ldy take the guarded branches below) ----
+        // The wave owns 64 consecutive columns = 256 contiguous bytes of each of its rows.  Both 32x32 blocks of a 32-row band
+        // are transposed through a wave-private patch of 32 rows x 64 columns (8 KiB; the eight patches lie inside the dead
+        // stage buffers) and the band leaves as 8 dwordx4 wave-stores of 4 rows x 256 contiguous bytes each, where the
+        // block-by-block form below writes 8 rows x 128 bytes per store and starts a band's second half only after the whole
+        // first column of blocks.  Same values, same instruction counts: only the shape of a store changes.
+        // Patch columns of rows with bit 2 set (the lhalf = 1 lanes of a transposing write) are swapped in halves of 32, so the
+        // two half-waves of one ds_write_b32 fall into different banks of a 64-bank LDS.
+        if constexpr (C::ROW_STORES && OD == 0) {
+            float* T = reinterpret_cast<float*>(smem) + wave * 2048;
+            const bool stream_out = (int64_t)M * N >= (int64_t)(8 << 20);     // as below: a result the eight L2s do not hold
+            const int nb = n0 + wave_n * 64;
+            const float bv0 = bias ? bias[nb + lrow] : 0.0f, bv1 = bias ? bias[nb + 32 + lrow] : 0.0f;
+#pragma unroll
+            for (int a = 0; a < C::TMW; ++a) {
+                const int mb = m0 + (wave_m * C::TMW + a) * 32;
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        T[((r & 3) + 8 * (r >> 2) + 4 * lhalf) * 64 + ((b ^ lhalf) * 32 + lrow)] = E::out(acc[a][b][r], scale, b ? bv1 : bv0);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const int row = i * 4 + (lane >> 4), c4 = (lane & 15) * 4;      // bit 2 of row = i & 1
+                    const float4 v = *reinterpret_cast<const float4*>(T + row * 64 + (c4 ^ ((i & 1) * 32)));
+                    float* dst = Y + (int64_t)(mb + row) * ldy + nb + c4;
+                    if (stream_out) {      // write-through, s_nop: see the block-by-block form below
+                        typedef float epi_v4f __attribute__((ext_vector_type(4)));
+                        const epi_v4f ev = {v.x, v.y, v.z, v.w};
+                        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(dst), "v"(ev) : "memory");
+                    } else {
+                        *reinterpret_cast<float4*>(dst) = v;
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
     } else if (wide) {
         float* T = reinterpret_cast<float*>(smem) + wave * 1024;
         const bool stream_out = (int64_t)M * N >= (int64_t)((OD ? 16 : 8) << 20);     // >= 32 MiB of result: more than the eight L2s hold
@@ -1566,7 +1614,7 @@ template <class E> using CfgSkinny = GemmCfg<E, 4, 2, 1, 1, 1, 0, 256>;
 template <class E> using CfgSkinny512 = GemmCfg<E, 2, 2, 1, 1, 1, 0, 512>;   // 64x64 tiles, 512-byte stages, 4 waves   // 256x192 (wave 64x96): N = 576, 1152, ...
 
 // ping-pong configurations (64-byte stages, ring of 4)
-template <class E, int ABL = 0> using PP256 = GemmCfg<E, 2, 4, 4, 2, 2, ABL, 64, false>;
+template <class E, int ABL = 0> using PP256 = GemmCfg<E, 2, 4, 4, 2, 2, ABL, 64, false>;   // (GemmCfg::ROW_STORES)
 template <class E> using PP128 = GemmCfg<E, 2, 4, 4, 1, 2, 0, 64, false>;
 template <class E> using PP192 = GemmCfg<E, 4, 2, 2, 3, 2, 0, 64, false>;
 template <class E> using PP384x192 = GemmCfg<E, 4, 2, 3, 3, 2, 0, 64, false>;   // wave tile 96x96: 6 fragment reads per 9 MFMAs

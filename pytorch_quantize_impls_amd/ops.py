@@ -2136,9 +2136,12 @@ def weight_bf16x3(w2d: torch.Tensor, kind: str, ld_bytes: Optional[int] = None, 
 
 
 def bf16_gemm(x: TriplePlanes, w: TriplePlanes, bias: Optional[torch.Tensor] = None,
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+              out: Optional[torch.Tensor] = None, variant: Optional[int] = None) -> torch.Tensor:
+    """``variant`` (two-term planes only; tests / A/B runs): 20 = the 256x256 ping-pong tile whatever the shape (qt_f16_gemm_variant)."""
     if x.K != w.K:
         raise ValueError(f"K mismatch: activations {x.K} vs weights {w.K}")
+    if variant is not None and x.terms != 2:
+        raise ValueError("explicit kernel variants exist for the two-term fp16 planes only")
     M, N = x.rows, w.rows
     dev = x.device
     bias = _check_bias(bias, N, dev)
@@ -2148,9 +2151,13 @@ def bf16_gemm(x: TriplePlanes, w: TriplePlanes, bias: Optional[torch.Tensor] = N
         raise ValueError(f"operand planes disagree: {x.terms}-term activation vs {w.terms}-term weight")
     with _on(dev):
         if x.terms == 2:
-            _lib.call("qt_f16_gemm", _p(x.data), int(x.ld_words), _p(w.data), int(w.ld_words), _p(bias), 1.0,
-                      _p(x.scale[0:1] if x.scale is not None else None), _p(out),
-                      int(out.stride(0) if M > 1 else max(N, 1)), int(M), int(N), int(2 * x.K), _stream(dev))
+            args = (_p(x.data), int(x.ld_words), _p(w.data), int(w.ld_words), _p(bias), 1.0,
+                    _p(x.scale[0:1] if x.scale is not None else None), _p(out),
+                    int(out.stride(0) if M > 1 else max(N, 1)), int(M), int(N), int(2 * x.K), _stream(dev))
+            if variant is None:
+                _lib.call("qt_f16_gemm", *args)
+            else:
+                _lib.call("qt_f16_gemm_variant", int(variant), *args)
         else:
             _lib.call("qt_bf16_gemm", _p(x.data), int(x.ld_words), _p(w.data), int(w.ld_words),
                       _p(bias), _p(out), int(out.stride(0) if M > 1 else max(N, 1)), int(M),
