@@ -1318,8 +1318,9 @@ int qt_dwconv2d_grad_weight_f32(const float* go, const float* x, const float* w,
  * Grouped convolution: F.conv2d(x, Q(w), bias, stride, padding, dilation, groups = G) with a FEW input channels per group
  * (1 <= cin_g <= QT_GC_MAX_CIN_G), fp32, forward and both gradients — the 3 x 3 of a ResNeXt block, ShuffleNet-style grouped
  * layers as BinConv2d / TerConv2d / DorefaConv2d(groups = G).  Streaming kernels on the vector units, the siblings of the
- * depthwise entries above (K = cin_g kh kw <= QT_GC_MAX_K is no matrix-core shape, and the block-diagonal operand would waste
- * G times the tile): csrc/gconv.hip, DESIGN.md "Grouped convs".
+ * depthwise entries above (with a few channels per group K = cin_g kh kw is no matrix-core shape, and the block-diagonal operand
+ * would waste G times the tile; 16, 24 and 32 channels per group have matrix-core entries of their own further down):
+ * csrc/gconv.hip, DESIGN.md "Grouped convs".
  *
  * Operands.  x [N, G cin_g, H, W], y / go [N, G cout_g, Ho, Wo] (Ho, Wo as above), each DENSE in NCHW or in channels-last order
  * and described by its four ELEMENT strides as above; the two tensors of a call need not share a layout.  w [G cout_g, cin_g,
@@ -1381,6 +1382,51 @@ int qt_gconv2d_grad_weight_f32(const float* go, const float* x, const float* w, 
                                int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n, int64_t gs_c,
                                int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w,
                                float ste_threshold, qt_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Grouped convolution on the matrix cores: forward and grad_input of F.conv2d(x, Q(w), bias, stride, padding, 1, groups = G) with
+ * 16, 24 or 32 input channels per group — the grouped 3 x 3 of the last ResNeXt stages as BinConv2d / TerConv2d(groups = G) —
+ * where the streaming kernels above are compute-bound.  A workgroup works inside ONE group, so the block-diagonal operand costs
+ * nothing: csrc/gconv_mfma.hip, DESIGN.md "Grouped convs on the matrix cores".  The weight gradient of these layers is
+ * qt_gconv2d_grad_weight_f32 above, which takes them as they are.
+ *
+ * Operands, layouts, strides and `kind` as for qt_gconv2d_f32 / qt_gconv2d_grad_input_f32 (fp32, each tensor dense NCHW or
+ * channels-last, the two of a call need not share a layout).  x and go may hold ANY value: nothing asks whether they are +-1.
+ *
+ * Arithmetic (that of qt_float_gemm_bf16 with three terms): every element v of the real operand (x forward, go backward) is split
+ * EXACTLY into hi = bf16_rn(v), mid = bf16_rn(v - hi), lo = bf16_rn((v - hi) - mid) inside the launch — no operand plane is written
+ * to memory — Q(w) in {-1, 0, +1} is exact in bf16 (a QT_DW_RAW weight that is not is rounded to nearest even), the products are
+ * exact and are accumulated in fp32 inside v_mfma_f32_16x16x32_bf16, in an order that depends on the shapes alone (no atomics: equal
+ * inputs give equal bits); the bias is added once in fp32 at the end.  grad_input is the gather form of
+ * qt_gconv2d_grad_input_f32; gx is written in full.  For finite inputs of normal range the result is the exact sum up to fp32
+ * accumulation order: |result - exact| <= (3 Kp + 1) 2^-23 (sum |x q| + |bias|) with Kp the reduction length (cin_g kh kw forward,
+ * cout_g kh kw backward) padded to a multiple of 32; where the sum of |terms| stays below 2^24 units of a common power of two
+ * (integers, say) it IS the exact sum.  Not pinned: an inf or NaN element makes every output whose window holds it NaN, also
+ * through a zero weight; an element above the largest bf16 (about 3.39e38) overflows to inf in `hi`; terms below the smallest fp32
+ * subnormal times 2^16 lose their low bits.
+ *
+ * Limits (beyond them QT_ERR_UNSUPPORTED): cin_g in {16, 24, 32}; cout_g a multiple of 16, at most QT_GM_MAX_COUT_G; a 1 x 1 or
+ * 3 x 3 kernel; stride 1 or 2, equal on both axes; dilation 1; padding 0 or 1 per axis; every tensor below 2^31 elements;
+ * G cout_g <= QT_DW_MAX_CHANNELS.  The grid is G x splits (at most G + 1024 workgroups); dynamic LDS at most 64 KiB.
+ *
+ * Validated before anything is enqueued, in the order of the grouped entries above; a non-zero status means nothing was launched:
+ *   1. negative sizes, cin_g or cout_g < 1, a kernel / stride / dilation below 1, negative padding: QT_ERR_INVALID_ARG;
+ *      kh kw > QT_DW_MAX_TAPS: QT_ERR_UNSUPPORTED.
+ *   2. N, G, H or W zero: QT_OK whatever the pointers are, nothing is written.
+ *   3. the limits: QT_ERR_UNSUPPORTED; a kernel that does not fit the padded image: QT_ERR_INVALID_ARG.
+ *   4. an unknown `kind`, a null tensor (bias may be null), strides that are neither dense layout: QT_ERR_INVALID_ARG; a pointer
+ *      that is not 4-byte aligned: QT_ERR_ALIGNMENT.
+ * ---------------------------------------------------------------------------------------- */
+#define QT_GM_MAX_COUT_G   48
+
+int qt_gmconv2d_f32(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t G, int64_t cin_g,
+                    int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                    int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, int64_t ys_n, int64_t ys_c, int64_t ys_h,
+                    int64_t ys_w, int kind, qt_stream_t stream);
+int qt_gmconv2d_grad_input_f32(const float* go, const float* w, float* gx, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g,
+                               int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n,
+                               int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w,
+                               int kind, qt_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Depthwise and grouped convolution on half-precision operands: the six entries above for bf16 / fp16 models

@@ -1,0 +1,360 @@
+// Grouped conv2d with 16, 24 or 32 input channels per group on the bf16 matrix cores: forward and grad_input of
+// conv2d(x, Q(w), bias, groups = G) for fp32 tensors of ANY value.  include/qt_hip.h "Grouped convolution on the matrix cores"
+// states the contract; DESIGN.md "Grouped convs on the matrix cores" the layout, the counts and the measurements.
+//
+// At this size a group stops being "no matrix-core shape": its output channels are one to three 16-wide MFMA column tiles and a
+// K chunk of 32 is two taps of 16 channels or one tap of 32, so a workgroup that works inside ONE group wastes nothing on the
+// block-diagonal zeros.  One kernel template serves both directions as a gather
+//     dst[n, g NO + oc, r, c] = sum over taps t and k < KC of  src[n, g KC + k, sr(r, t), sc(c, t)] * Wq[oc, k, t]   (+ bias[oc])
+//   forward    : src = x, dst = y, KC = cin_g, NO = cout_g, sr = r s - p + i
+//   grad_input : src = go, dst = gx, KC = cout_g, NO = cin_g, sr = (r + p - i) / s where that division is exact (a (pixel, tap)
+//                pair without a source contributes a zero fragment: no atomics, gx written in full)
+// with the real operand split EXACTLY into three bf16 terms (hi = bf16_rn(v), mid = bf16_rn(v - hi), lo = bf16_rn(v - hi - mid))
+// inside the launch, the quantised weight exact in bf16, and fp32 accumulation inside v_mfma_f32_16x16x32_bf16.
+//
+// Work split.  A workgroup (4 waves) owns ONE group and walks tiles split, split + S, ... of the flat (n, tile) index; a tile is
+// TR x TC destination pixels (at most 128, balanced over the map).  Once per workgroup: the group's weights, quantised (`kind`),
+// into LDS as bf16 B fragments wl[pair][oc][8] (pair = (tap, block of 8 reduction channels), padded with zero pairs to a multiple
+// of four; oc padded with zero columns to a multiple of 16).  Per tile:
+//   stage   : the bounding box of the source pixels the tile reads, clipped to the image, is read ONCE from HBM — a thread owns
+//             (source pixel, block of 8 channels): lanes run along W for NCHW (coalesced row segments), along the channel blocks
+//             of a pixel for channels-last (two 16-byte loads when the tensor is 16-byte aligned) — split once and stored as
+//             three 16-byte LDS writes into patch[term][pixel][KC (+ pad)].  Pixel `npmax` of every term is a ZERO pixel.
+//   tables  : offs[tap][q] = byte offset of the source pixel of destination pixel q under that tap, or of the zero pixel where it
+//             lies outside the image / has no source (stride 2 backward) / q is past the tile; outq[q] = q's offset in dst or -1.
+//             So the main loop has no branch and no coordinate arithmetic.
+//   compute : a wave takes (pair of 16-pixel row tiles, 16-channel column tile) items round-robin.  Per K chunk of 32 a lane
+//             (row = lane & 15, k block = lane >> 4) reads one table word, its B fragment (16 bytes) and per row tile and term
+//             one A fragment (16 bytes at offs + term plane + channel block): 6 MFMAs per 7 fragment reads.  Pixels are the MFMA
+//             rows, so a lane's accumulator quad is 4 consecutive pixels of one channel; the bias is added once in fp32.
+// LDS strides: a pixel is KC * 2 bytes padded to an ODD number of 16-byte slots, so the 16 lanes of a fragment read (consecutive
+// pixels) fall into 16 different slots of the 256-byte bank row; the B fragments of 16 lanes are 256 contiguous bytes.
+//
+// Non-finite inputs: an inf / NaN element poisons (NaN) every output whose window holds it — also through a ZERO weight
+// (0 * inf), unlike the streaming kernels; elements of magnitude above ~3.39e38 overflow in the bf16 rounding of `hi`.
+#include "qt_common.h"
+#include "dw_map.h"
+
+namespace {
+
+typedef __bf16 gm_bf8 __attribute__((ext_vector_type(8)));
+typedef float gm_f4 __attribute__((ext_vector_type(4)));
+
+constexpr int GM_TILE_PIX = 128;                 // destination pixels of a tile: 8 row tiles of 16
+constexpr int GM_TILE_COLS = 32;
+constexpr int GM_LDS_BYTES = 64 * 1024;          // weights + tables + patch: two workgroups per CU at the worst
+constexpr int GM_TARGET_WGS = 1024;
+constexpr int GM_MAX_COUT_G = QT_GM_MAX_COUT_G;
+constexpr int64_t GM_MAX_ELEMS = (int64_t)1 << 31;
+
+struct GmGeom {
+    int N, G;
+    int KC, NO;              // reduction / result channels per group
+    int Hs, Ws, Hd, Wd;      // source and destination maps
+    int s, ph, pw;
+    int bwd;                 // 0: forward (src = x), 1: grad_input (src = go)
+    int vec;                 // channels-last source, 16-byte aligned: float4 loads
+};
+
+struct GmPlan {
+    int TR, TC, tiles_r, tiles_c;
+    int splits;
+    int npmax;               // patch pixels per term; pixel npmax is the zero pixel
+    int nopad;               // NO padded to the column tile
+    int w_bytes, lds_bytes;
+};
+
+// bytes of a patch pixel: NCB blocks of 8 bf16, padded to an odd number of 16-byte slots
+constexpr int gm_ps(int ncb) { return 16 * (ncb | 1); }
+
+__host__ __device__ inline int gm_min(int a, int b) { return a < b ? a : b; }
+
+// the source rows (columns) a run [d0, d1) of destination rows reads along one axis, clipped to the source: first and count
+__device__ __forceinline__ void gm_span(int bwd, int d0, int d1, int s, int p, int k, int S, int& lo, int& cnt) {
+    int hi;
+    if (!bwd) {
+        lo = d0 * s - p;
+        hi = (d1 - 1) * s - p + k - 1;
+    } else {
+        const int a = d0 + p - (k - 1);
+        lo = a <= 0 ? 0 : (a + s - 1) / s;
+        hi = (d1 - 1 + p) / s;
+    }
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > S - 1 ? S - 1 : hi;
+    cnt = hi >= lo ? hi - lo + 1 : 0;
+}
+
+// the most gm_span can return for a run of T destination rows
+inline int gm_span_cap(int bwd, int T, int s, int k, int S) {
+    const int cap = bwd ? (T + k - 2) / s + 1 : (T - 1) * s + k;
+    return cap < S ? cap : S;
+}
+
+__device__ __forceinline__ uint32_t gm_bf16_rn(float f) {          // round to nearest even, NaN kept quiet (split_bf16.hip)
+    uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return u >> 16;
+}
+
+// v = hi + mid + lo exactly (each subtraction is exact in fp32): the three terms of element e of a block of 8 into halves of t[]
+__device__ __forceinline__ void gm_split(float v, int e, uint32_t (&hi)[4], uint32_t (&mid)[4], uint32_t (&lo)[4]) {
+    const uint32_t a = gm_bf16_rn(v);
+    const float r1 = v - __uint_as_float(a << 16);
+    const uint32_t b = gm_bf16_rn(r1);
+    const float r2 = r1 - __uint_as_float(b << 16);
+    const uint32_t c = gm_bf16_rn(r2);
+    const int sh = 16 * (e & 1);
+    hi[e >> 1] |= a << sh;
+    mid[e >> 1] |= b << sh;
+    lo[e >> 1] |= c << sh;
+}
+
+template <int TAPS, int NCB>
+__global__ __launch_bounds__(DW_THREADS) void gm_kernel(const float* __restrict__ src, const float* __restrict__ w,
+                                                        const float* __restrict__ bias, float* __restrict__ dst, GmGeom g,
+                                                        DwStrides ss, DwStrides ds, GmPlan pl, int kind) {
+    constexpr int KC = NCB * 8, PAIRS = TAPS * NCB, NCHUNK = (PAIRS + 3) / 4, PS = gm_ps(NCB);
+    constexpr int KS = TAPS == 9 ? 3 : 1;                            // kernel side
+    extern __shared__ __attribute__((aligned(16))) unsigned char gm_smem[];
+    uint4* wl = reinterpret_cast<uint4*>(gm_smem);                   // [NCHUNK * 4][nopad]
+    int* offs = reinterpret_cast<int*>(gm_smem + pl.w_bytes);        // [TAPS][128]
+    int* outq = offs + TAPS * GM_TILE_PIX;                           // [128]
+    unsigned char* patch = reinterpret_cast<unsigned char*>(outq + GM_TILE_PIX);          // [3][npmax + 1][PS]
+    const int TS = (pl.npmax + 1) * PS, zero_off = pl.npmax * PS;
+    const int tid = threadIdx.x;
+    const int grp = (int)(blockIdx.x / pl.splits);
+    const int split = (int)(blockIdx.x - (unsigned)grp * pl.splits);
+
+    // once: the group's weights as B fragments, the zero pixel of every term
+    for (int e = tid; e < NCHUNK * 4 * pl.nopad; e += DW_THREADS) {
+        const int p = e / pl.nopad, oc = e - p * pl.nopad;
+        const int t = p / NCB, cb = p - t * NCB;
+        uint32_t h[4] = {0u, 0u, 0u, 0u};
+        if (p < PAIRS && oc < g.NO) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int kc = cb * 8 + k;
+                const int64_t idx = g.bwd ? (((int64_t)grp * KC + kc) * g.NO + oc) * TAPS + t
+                                          : (((int64_t)grp * g.NO + oc) * KC + kc) * TAPS + t;
+                h[k >> 1] |= gm_bf16_rn(dw_quant(kind, w[idx])) << (16 * (k & 1));
+            }
+        }
+        wl[e] = make_uint4(h[0], h[1], h[2], h[3]);
+    }
+    for (int e = tid; e < 3 * (PS / 16); e += DW_THREADS) {
+        const int term = e / (PS / 16), sl = e - term * (PS / 16);
+        *reinterpret_cast<uint4*>(patch + term * TS + zero_off + sl * 16) = make_uint4(0u, 0u, 0u, 0u);
+    }
+
+    const int wave = tid >> 6, lane = tid & 63, lrow = lane & 15, kb = lane >> 4;
+    const int tiles = pl.tiles_r * pl.tiles_c;
+    const int units = g.N * tiles;
+    for (int u = split; u < units; u += pl.splits) {                 // uniform over the workgroup: so are the barriers
+        const int n = u / tiles, tt = u - n * tiles;
+        const int tr = tt / pl.tiles_c, tc = tt - tr * pl.tiles_c;
+        const int r0 = tr * pl.TR, c0 = tc * pl.TC;
+        const int TRa = gm_min(pl.TR, g.Hd - r0), TCa = gm_min(pl.TC, g.Wd - c0);
+        const int npix = TRa * TCa;
+        int lo_r, PH, lo_c, PW;
+        gm_span(g.bwd, r0, r0 + TRa, g.s, g.ph, KS, g.Hs, lo_r, PH);
+        gm_span(g.bwd, c0, c0 + TCa, g.s, g.pw, KS, g.Ws, lo_c, PW);
+        const int np = PH * PW;
+        __syncthreads();                                              // the previous tile has been read (first tile: wl is written)
+        const float* sbase = src + n * ss.n + (int64_t)grp * KC * ss.c + lo_r * ss.h + lo_c * ss.w;
+        for (int e = tid; e < np * NCB; e += DW_THREADS) {
+            int cb, pp;
+            if (ss.c == 1) {                                          // channels-last: the blocks of a pixel on consecutive lanes
+                pp = e / NCB;
+                cb = e - pp * NCB;
+            } else {                                                  // NCHW: consecutive lanes along W
+                cb = e / np;
+                pp = e - cb * np;
+            }
+            const int row = pp / PW, col = pp - row * PW;
+            const float* sp = sbase + row * ss.h + col * ss.w + cb * 8 * ss.c;
+            float v[8];
+            if (g.vec) {
+                const float4 a = *reinterpret_cast<const float4*>(sp), b = *reinterpret_cast<const float4*>(sp + 4);
+                v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = sp[k * ss.c];
+            }
+            uint32_t hi[4] = {0u, 0u, 0u, 0u}, mid[4] = {0u, 0u, 0u, 0u}, lo[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int k = 0; k < 8; ++k) gm_split(v[k], k, hi, mid, lo);
+            unsigned char* pd = patch + pp * PS + cb * 16;
+            *reinterpret_cast<uint4*>(pd) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+            *reinterpret_cast<uint4*>(pd + TS) = make_uint4(mid[0], mid[1], mid[2], mid[3]);
+            *reinterpret_cast<uint4*>(pd + 2 * TS) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+        }
+        for (int e = tid; e < (TAPS + 1) * GM_TILE_PIX; e += DW_THREADS) {
+            const int t = e / GM_TILE_PIX, q = e - t * GM_TILE_PIX;
+            const bool in = q < npix;
+            const int qr = in ? q / TCa : 0;
+            const int r = r0 + qr, c = c0 + (in ? q - qr * TCa : 0);
+            if (t == TAPS) {
+                outq[q] = in ? (int)(r * ds.h + c * ds.w) : -1;
+                continue;
+            }
+            const int i = t / KS, j = t - i * KS;
+            int sr, sc;
+            bool ok = in;
+            if (!g.bwd) {
+                sr = r * g.s - g.ph + i;
+                sc = c * g.s - g.pw + j;
+            } else {
+                const int hh = r + g.ph - i, ww = c + g.pw - j;
+                ok = ok && hh >= 0 && ww >= 0;
+                sr = (hh < 0 ? 0 : hh) / g.s;
+                sc = (ww < 0 ? 0 : ww) / g.s;
+                ok = ok && sr * g.s == hh && sc * g.s == ww;
+            }
+            ok = ok && (unsigned)(sr - lo_r) < (unsigned)PH && (unsigned)(sc - lo_c) < (unsigned)PW;   // inside the image: inside the box
+            offs[e] = ok ? ((sr - lo_r) * PW + (sc - lo_c)) * PS : zero_off;
+        }
+        __syncthreads();
+
+        const int npp = (npix + 31) >> 5;
+        const int items = npp * (pl.nopad >> 4);
+        for (int it = wave; it < items; it += DW_THREADS / 64) {
+            const int nt = it / npp, pp = it - nt * npp;
+            const int q0 = pp * 32 + lrow;
+            gm_f4 acc0 = {0.0f, 0.0f, 0.0f, 0.0f}, acc1 = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int ch = 0; ch < NCHUNK; ++ch) {
+                const int p = 4 * ch + kb;                            // the lane's pair of this chunk
+                const int t = p / NCB, cb = p - t * NCB;
+                const bool live = p < PAIRS;                          // a padding pair reads the zero pixel (its weights are zero too)
+                const int ti = live ? t * GM_TILE_PIX : 0;
+                const int o0 = (live ? offs[ti + q0] : zero_off) + cb * 16;
+                const int o1 = (live ? offs[ti + q0 + 16] : zero_off) + cb * 16;
+                gm_bf8 b;
+                const uint4 bw = wl[p * pl.nopad + nt * 16 + lrow];
+                __builtin_memcpy(&b, &bw, 16);
+#pragma unroll
+                for (int term = 0; term < 3; ++term) {
+                    const gm_bf8 a0 = *reinterpret_cast<const gm_bf8*>(patch + term * TS + o0);
+                    const gm_bf8 a1 = *reinterpret_cast<const gm_bf8*>(patch + term * TS + o1);
+                    acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b, acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b, acc1, 0, 0, 0);
+                }
+            }
+            // D[row = 4 kb + i][col = lrow]: 4 consecutive pixels of output channel nt * 16 + lrow
+            const int oc = nt * 16 + lrow;
+            if (oc < g.NO) {
+                const int64_t ch = (int64_t)grp * g.NO + oc;
+                float* dp = dst + n * ds.n + ch * ds.c;
+                const float bv = bias ? bias[ch] : 0.0f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int oa = outq[pp * 32 + kb * 4 + i], ob = outq[pp * 32 + 16 + kb * 4 + i];
+                    if (oa >= 0) dp[oa] = bias ? acc0[i] + bv : acc0[i];
+                    if (ob >= 0) dp[ob] = bias ? acc1[i] + bv : acc1[i];
+                }
+            }
+        }
+    }
+}
+
+// the tile of the destination map and the LDS it needs: at most 128 pixels, at most 32 columns, the patch inside the budget, then
+// balanced over the map (which only shrinks it)
+GmPlan gm_plan(const GmGeom& g, int taps, int ncb) {
+    GmPlan pl{};
+    const int ks = taps == 9 ? 3 : 1, ps = gm_ps(ncb);
+    pl.nopad = (g.NO + 15) & ~15;
+    pl.w_bytes = (taps * ncb + 3) / 4 * 4 * pl.nopad * 16;
+    const int fixed = pl.w_bytes + (taps + 1) * GM_TILE_PIX * 4;
+    const int budget = (GM_LDS_BYTES - fixed) / (3 * ps) - 1;         // patch pixels per term, the zero pixel aside
+    auto need = [&](int tr, int tc) { return gm_span_cap(g.bwd, tr, g.s, ks, g.Hs) * gm_span_cap(g.bwd, tc, g.s, ks, g.Ws); };
+    int tc = gm_min(g.Wd, GM_TILE_COLS);
+    pl.tiles_c = (g.Wd + tc - 1) / tc;
+    tc = (g.Wd + pl.tiles_c - 1) / pl.tiles_c;
+    int tr = gm_min(g.Hd, GM_TILE_PIX / tc);
+    while (need(tr, tc) > budget) {                                   // a 1 x 1 tile needs 9 pixels: this ends
+        if (tr > 1) --tr;
+        else --tc;
+    }
+    pl.tiles_c = (g.Wd + tc - 1) / tc;
+    pl.tiles_r = (g.Hd + tr - 1) / tr;
+    pl.TR = (g.Hd + pl.tiles_r - 1) / pl.tiles_r;
+    pl.TC = (g.Wd + pl.tiles_c - 1) / pl.tiles_c;
+    pl.npmax = need(pl.TR, pl.TC);
+    pl.lds_bytes = fixed + 3 * (pl.npmax + 1) * ps;
+    const int64_t units = (int64_t)g.N * pl.tiles_r * pl.tiles_c;
+    int64_t s = (GM_TARGET_WGS + g.G - 1) / g.G;
+    if (s > units) s = units;
+    pl.splits = (int)(s < 1 ? 1 : s);
+    return pl;
+}
+
+template <int TAPS>
+int gm_launch(int ncb, const float* src, const float* w, const float* bias, float* dst, const GmGeom& g, const DwStrides& ss,
+              const DwStrides& ds, int kind, hipStream_t s) {
+    const GmPlan pl = gm_plan(g, TAPS, ncb);
+    const unsigned grid = (unsigned)((int64_t)g.G * pl.splits);
+#define GM_GO(NCB) gm_kernel<TAPS, NCB><<<grid, DW_THREADS, (size_t)pl.lds_bytes, s>>>(src, w, bias, dst, g, ss, ds, pl, kind)
+    if (ncb == 2) GM_GO(2);
+    else if (ncb == 3) GM_GO(3);
+    else if (ncb == 4) GM_GO(4);
+    else GM_GO(6);
+#undef GM_GO
+    return qt_check_launch();
+}
+
+// The validation both entries share, in the documented order.  in / out: the tensor read (x, go) and the one written (y, gx).
+int gm_entry(bool bwd, const float* in, const float* w, const float* bias, float* out, int64_t N, int64_t G, int64_t cin_g,
+             int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, const DwStrides& is,
+             const DwStrides& os, int kind, qt_stream_t stream) {
+    if (N < 0 || G < 0 || cin_g < 1 || cout_g < 1 || H < 0 || W < 0 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || ph < 0 || pw < 0 ||
+        dh < 1 || dw < 1)
+        return QT_ERR_INVALID_ARG;
+    if ((int64_t)kh * kw > QT_DW_MAX_TAPS) return QT_ERR_UNSUPPORTED;
+    if (N == 0 || G == 0 || H == 0 || W == 0) return QT_OK;
+    if ((cin_g != 16 && cin_g != 24 && cin_g != 32) || (cout_g & 15) || cout_g > GM_MAX_COUT_G) return QT_ERR_UNSUPPORTED;
+    if (!((kh == 1 && kw == 1) || (kh == 3 && kw == 3)) || sh != sw || sh > 2 || dh != 1 || dw != 1 || ph > 1 || pw > 1)
+        return QT_ERR_UNSUPPORTED;
+    if (N >= GM_MAX_ELEMS || G >= GM_MAX_ELEMS || H >= GM_MAX_ELEMS || W >= GM_MAX_ELEMS) return QT_ERR_UNSUPPORTED;
+    const int64_t eh = H + 2 * (int64_t)ph - kh, ew = W + 2 * (int64_t)pw - kw;
+    if (eh < 0 || ew < 0) return QT_ERR_INVALID_ARG;              // the kernel does not fit the padded image
+    const int64_t Ho = eh / sh + 1, Wo = ew / sw + 1;
+    const int64_t Cin = G * cin_g, Cout = G * cout_g;
+    if ((double)N * (double)Cin * (double)H * (double)W >= (double)GM_MAX_ELEMS ||
+        (double)N * (double)Cout * (double)Ho * (double)Wo >= (double)GM_MAX_ELEMS || (double)Cout > (double)QT_DW_MAX_CHANNELS)
+        return QT_ERR_UNSUPPORTED;
+    if (kind != QT_DW_RAW && kind != QT_DW_SIGN && kind != QT_DW_TERNARY) return QT_ERR_INVALID_ARG;
+    if (!in || !w || !out) return QT_ERR_INVALID_ARG;
+    const DwStrides& xs = bwd ? os : is;
+    const DwStrides& ys = bwd ? is : os;
+    if (dw_layout(N, Cin, H, W, xs) < 0 || dw_layout(N, Cout, Ho, Wo, ys) < 0) return QT_ERR_INVALID_ARG;
+    if (!dw_aligned4(in) || !dw_aligned4(w) || !dw_aligned4(out) || !dw_aligned4(bias)) return QT_ERR_ALIGNMENT;
+    GmGeom g{};
+    g.N = (int)N; g.G = (int)G;
+    g.KC = (int)(bwd ? cout_g : cin_g); g.NO = (int)(bwd ? cin_g : cout_g);
+    g.Hs = (int)(bwd ? Ho : H); g.Ws = (int)(bwd ? Wo : W); g.Hd = (int)(bwd ? H : Ho); g.Wd = (int)(bwd ? W : Wo);
+    g.s = sh; g.ph = ph; g.pw = pw; g.bwd = bwd ? 1 : 0;
+    g.vec = is.c == 1 && qt_aligned16(in) ? 1 : 0;                 // every pixel's group block then starts on 32 bytes
+    hipStream_t s = (hipStream_t)stream;
+    return kh == 3 ? gm_launch<9>(g.KC / 8, in, w, bias, out, g, is, os, kind, s)
+                   : gm_launch<1>(g.KC / 8, in, w, bias, out, g, is, os, kind, s);
+}
+
+}  // namespace
+
+extern "C" int qt_gmconv2d_f32(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t G, int64_t cin_g,
+                               int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                               int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, int64_t ys_n, int64_t ys_c, int64_t ys_h,
+                               int64_t ys_w, int kind, qt_stream_t stream) {
+    return gm_entry(false, x, w, bias, y, N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw,
+                    DwStrides{xs_n, xs_c, xs_h, xs_w}, DwStrides{ys_n, ys_c, ys_h, ys_w}, kind, stream);
+}
+
+extern "C" int qt_gmconv2d_grad_input_f32(const float* go, const float* w, float* gx, int64_t N, int64_t G, int64_t cin_g,
+                                          int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                                          int dw, int64_t gs_n, int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c,
+                                          int64_t xs_h, int64_t xs_w, int kind, qt_stream_t stream) {
+    return gm_entry(true, go, w, nullptr, gx, N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw,
+                    DwStrides{gs_n, gs_c, gs_h, gs_w}, DwStrides{xs_n, xs_c, xs_h, xs_w}, kind, stream);
+}

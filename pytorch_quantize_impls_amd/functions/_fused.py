@@ -2141,7 +2141,8 @@ class DepthwiseConv2dFn(QtFunction):
 
 
 # ---- grouped convs with a few channels per group -----------------------------------------------------------------------------------
-# K = cin_g * kh * kw <= 512 on a block-diagonal operand is no matrix-core shape either: one streaming launch forward, one per
+# K = cin_g * kh * kw on a block-diagonal operand is no matrix-core shape either while a group has a few channels (from 16 per
+# group on it is one: "grouped convs with 16 ... 32 channels per group" below): one streaming launch forward, one per
 # gradient (csrc/gconv.hip, DESIGN.md "Grouped convs"), instead of one conv per group on copied slices.  As above, nothing asks
 # whether the activation is +-1.
 
@@ -2174,6 +2175,45 @@ class GroupedConv2dFn(QtFunction):
     @staticmethod
     def backward(ctx, grad_output):
         return _streaming_backward(_GROUPED, ctx, grad_output)
+
+
+# ---- grouped convs with 16 ... 32 channels per group -------------------------------------------------------------------------------
+# Here a group IS a matrix-core shape once a workgroup works inside one group: its output channels are one to three MFMA column
+# tiles, a K chunk of 32 is two taps of 16 channels or one tap of 32 (csrc/gconv_mfma.hip, DESIGN.md "Grouped convs on the matrix
+# cores").  Forward and grad_input each one launch on three exact bf16 terms of the real operand; the weight gradient (and the bias
+# gradient with it) is the grouped family's streaming kernel.  As above nothing asks whether the activation is +-1.
+
+#: fewer groups keep the per-group loop (tests/test_gpu_gconv.py pins four groups of 32 channels on it)
+GROUPED_MFMA_MIN_GROUPS = 8
+#: BinConv2d / TerConv2d layers inside the window take ``GroupedMfmaConv2dFn`` (False: the per-group loop, as before).  Set from
+#: tools/bench_grouped_mfma.py by the rule of DESIGN.md "Grouped convs on the matrix cores": True iff on every measured row the
+#: node's round range lies wholly below the per-group loop's, forward and forward + backward.  Measured
+#: (profiles/grouped_mfma_bench_line.json): it does on all five rows the route takes, 6.8x - 32x forward and 2.9x - 25x a step.
+GROUPED_MFMA = True
+
+_GROUPED_MFMA = _StreamingFamily(ops._GM, None, None)          # no plane or code form: the deferred chains decline these layers
+
+
+def grouped_mfma_route(layer, input) -> bool:
+    """``layer`` (a Conv2d subclass with an fp32 weight) applied to ``input`` is a grouped conv the matrix-core kernels take and
+    ``GROUPED_MFMA`` is on: a 4-D fp32 device tensor, ``groups >= GROUPED_MFMA_MIN_GROUPS`` with 16, 24 or 32 input channels each,
+    padding mode "zeros" and the shapes of ``ops.grouped_mfma_applicable``."""
+    return (bool(GROUPED_MFMA) and _streaming_f32_common(layer, input) and layer.groups >= GROUPED_MFMA_MIN_GROUPS
+            and ops.grouped_mfma_applicable(input.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups))
+
+
+class GroupedMfmaConv2dFn(QtFunction):
+    """conv2d(x, Q(W), b, groups = G) with 16, 24 or 32 input channels per group on the matrix cores: the sibling of
+    ``GroupedConv2dFn``, same arguments.  Forward qt_gmconv2d_f32, backward qt_gmconv2d_grad_input_f32 and the grouped family's
+    grad_weight (partials + combine inside one call), the bias gradient being a by-product of the latter."""
+
+    @staticmethod
+    def forward(ctx, input, weight, bias, kind, weight_q, ste, conv_args):
+        return _streaming_forward(_GROUPED_MFMA, ctx, input, weight, bias, kind, weight_q, ste, conv_args)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return _streaming_backward(_GROUPED_MFMA, ctx, grad_output)
 
 
 def grouped_quant_conv(layer, input, kind: str, quant_op):

@@ -4165,6 +4165,25 @@ def grouped_codes_applicable(x_shape, w_shape, stride, padding, dilation, groups
     return grouped_applicable(x_shape, w_shape, stride, padding, dilation, groups)
 
 
+#: input channels per group the matrix-core grouped kernels take (csrc/gconv_mfma.hip), and their most output channels per group
+GM_CIN_G = (16, 24, 32)
+GM_MAX_COUT_G = _lib.DEFINES["QT_GM_MAX_COUT_G"]
+
+
+def grouped_mfma_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
+    """A conv2d of an [N, G * cin_g, H, W] input with a [G * cout_g, cin_g, kh, kw] weight and ``groups == G`` that the matrix-core
+    grouped entries take (``grouped_mfma_conv2d`` / ``grouped_mfma_conv2d_grad_input``): cin_g in ``GM_CIN_G``, cout_g a multiple
+    of 16 up to ``GM_MAX_COUT_G``, a 1 x 1 or 3 x 3 kernel, stride 1 or 2 (equal on both axes), dilation 1, numeric padding 0 or
+    1 per axis, every tensor non-empty and below 2^31 elements.  A pure function of the shapes."""
+    if not _streaming_limits(x_shape, w_shape, stride, padding, dilation, groups):
+        return False
+    Cout, cin_g, kh, kw = map(int, w_shape)
+    cout_g = Cout // int(groups)
+    (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
+    return (cin_g in GM_CIN_G and cout_g % 16 == 0 and cout_g <= GM_MAX_COUT_G and (kh, kw) in ((1, 1), (3, 3))
+            and sh == sw and sh <= 2 and (dh, dw) == (1, 1) and max(ph, pw) <= 1)
+
+
 def _dw_channels_last(t: torch.Tensor) -> bool:
     return t.is_contiguous(memory_format=torch.channels_last) and not t.is_contiguous()
 
@@ -4258,6 +4277,16 @@ def _gc_planes_geometry(x_shape, weight, stride, padding, dilation, groups):
     return w, geom, y_shape
 
 
+def _gm_geometry(x_shape, weight, stride, padding, dilation, groups, half: bool = False):
+    """``_gc_geometry`` inside the window of ``grouped_mfma_applicable``; fp32 only, whatever ``half`` says."""
+    _require(weight, "weight")
+    if (len(x_shape) == 4 and weight.dim() == 4 and min(map(int, x_shape)) > 0
+            and not grouped_mfma_applicable(x_shape, weight.shape, stride, padding, dilation, groups)):
+        raise ValueError(f"not a grouped conv the matrix-core entry points take: input {tuple(x_shape)}, weight {tuple(weight.shape)}, "
+                         f"groups {groups}, stride {stride}, padding {padding}, dilation {dilation}")
+    return _gc_geometry(x_shape, weight, stride, padding, dilation, groups)
+
+
 class _Streaming(NamedTuple):
     """One family of streaming convs, as the shared bodies below see it."""
     entry: dict                 # suffix -> name of the entry point ("f32" -> "qt_dwconv2d_f32"), spelled once, not per call
@@ -4277,6 +4306,11 @@ def _streaming_entries(prefix: str) -> dict:
 
 _DW = _Streaming(_streaming_entries("qt_dwconv2d"), "depthwise", "C * m", _dw_geometry, _dw_geometry, True)
 _GC = _Streaming(_streaming_entries("qt_gconv2d"), "grouped", "G * cout_g", _gc_geometry, _gc_planes_geometry, False)
+#: 16 ... 32 input channels per group on the matrix cores (csrc/gconv_mfma.hip): fp32 forward and grad_input of its own, the weight
+#: gradient of the grouped family (whose entry takes up to 32 channels per group); no plane, code or "_h" entries
+_GM = _Streaming({"f32": "qt_gmconv2d_f32", "grad_input_f32": "qt_gmconv2d_grad_input_f32",
+                  "grad_weight_f32": _GC.entry["grad_weight_f32"], "grad_weight_work_floats": _GC.entry["grad_weight_work_floats"]},
+                 "matrix-core grouped", "G * cout_g", _gm_geometry, _gm_geometry, False)
 
 
 def _streaming_conv2d(fam: _Streaming, x, weight, bias, stride, padding, dilation, groups, kind="raw", out=None):
@@ -4317,6 +4351,18 @@ def grouped_conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
     bias last.  A bf16 / fp16 ``x`` (with a weight of the same dtype, or fp32 as under autocast; ``bias`` stays an fp32 vector) runs
     qt_gconv2d_h: the same fp32 arithmetic on the exactly upcast elements, rounded once to nearest even into a result of x's dtype."""
     return _streaming_conv2d(_GC, x, weight, bias, stride, padding, dilation, groups, kind, out)
+
+
+def grouped_mfma_conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1,
+                        groups: int = 1, kind: str = "raw", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``grouped_conv2d`` for the shapes of ``grouped_mfma_applicable`` (16, 24 or 32 input channels per group) on the bf16 matrix
+    cores, one launch (qt_gmconv2d_f32): fp32 ``x`` of ANY value is split exactly into three bf16 terms inside the launch, Q(weight)
+    is exact in bf16, accumulation is fp32 inside the MFMA, the bias is added once at the end — the arithmetic of
+    ``float_linear(..., "sign", terms=3)``: the exact sum up to fp32 accumulation order, THE exact sum for integer data below
+    2^24.  No detection, no host synchronisation, no allocation beyond the result.  The result has the layout of x, or is written
+    into ``out``."""
+    _require(x, "input")
+    return _streaming_conv2d(_GM, x, weight, bias, stride, padding, dilation, groups, kind, out)
 
 
 def _dw_plane_input(planes: BitPlanes, shape):
@@ -4644,6 +4690,17 @@ def grouped_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_output: to
     fp16 ``grad_output``, whose dtype the result then has).  The result has the layout of ``grad_output`` unless ``channels_last``
     says otherwise, or is written into ``out``."""
     return _streaming_conv2d_grad_input(_GC, input_shape, weight, grad_output, stride, padding, dilation, groups, kind, channels_last,
+                                        out)
+
+
+def grouped_mfma_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_output: torch.Tensor, stride=1, padding=0, dilation=1,
+                                   groups: int = 1, kind: str = "raw", channels_last: Optional[bool] = None,
+                                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient of ``grouped_mfma_conv2d`` with respect to x on the matrix cores (qt_gmconv2d_grad_input_f32): the gather of
+    ``grouped_conv2d_grad_input`` with ``grad_output`` split into three bf16 terms inside the launch; no atomics, the result
+    written in full.  Layout rules as there."""
+    _require(grad_output, "grad_output")
+    return _streaming_conv2d_grad_input(_GM, input_shape, weight, grad_output, stride, padding, dilation, groups, kind, channels_last,
                                         out)
 
 

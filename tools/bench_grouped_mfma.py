@@ -1,0 +1,162 @@
+#!/usr/bin/env python
+"""The grouped layers with 16 ... 32 channels per group (ResNeXt-50 stages 3 and 4, a wide 24-channel layer, the strided layer that
+opens stage 3, a grouped 1 x 1) at batch 256 as BinConv2d(C, Cout, k, stride, padding, groups=G) on +-1 activations, NCHW, one GPU:
+one JSON line.  The protocol, the counts and the constants are those of tools/bench_grouped.py (imported): a child process per
+shape under a time limit, nothing started after a failing child, the routes taking turns inside each of ``--rounds`` rounds, us per
+call as the median and the range of the rounds, forward and forward + backward.  The byte and MAC counts are those of
+``bench_grouped.counts`` for a layer whose output channels may differ from its input channels.
+
+Routes:
+  mfma   : ``_fused.GroupedMfmaConv2dFn`` called directly (csrc/gconv_mfma.hip; so the measurement does not depend on the switch
+           ``_fused.GROUPED_MFMA``, which is set FROM it);
+  loop   : ``_fused.grouped_quant_conv`` with ``binary_input = True``: what these layers run with the switch off;
+  torch  : F.conv2d(x, sign(W), b, groups=G) through torch (MIOpen);
+  stream : ``_fused.GroupedConv2dFn`` called directly (the streaming kernels of csrc/gconv.hip, not routed at this size).
+``hbm_share`` = (4 (|x| + |y|) (x 3 for a step) / 8 TB/s) / the mfma median; ``mfma_share`` = (2 macs x 3 bf16 terms / 2.5 PFLOP/s)
+/ the same.  ``grouped_mfma_by_rule`` is the value ``_fused.GROUPED_MFMA`` has to ship with: True iff on every row the route takes the mfma round
+range lies wholly below the loop's, forward and forward + backward.  The library and the streaming kernels are reported, not gated.
+
+    python tools/bench_grouped_mfma.py [--rounds 9] [--out profiles/grouped_mfma_bench_line.json]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import bench_grouped as B
+
+sys.path.insert(0, B.ROOT)
+
+#: (channels, map, stride, groups, kernel, output channels).  768 -> 768 at 32 groups has 24 OUTPUT channels per group, no multiple
+#: of 16: the matrix-core route declines it (the row keeps its other three routes); 768 -> 1536 is the 24-channel row it takes.
+SHAPES = [(512, 14, 1, 32, 3, 512), (768, 14, 1, 32, 3, 768), (768, 14, 1, 32, 3, 1536), (1024, 7, 1, 32, 3, 1024),
+          (512, 28, 2, 32, 3, 512), (256, 14, 1, 16, 1, 256)]
+BF16_FLOPS = 2.5e15
+
+
+def child(index, rounds):
+    import torch
+    import torch.nn.functional as F
+    from pytorch_quantize_impls_amd import _lib, ops
+    from pytorch_quantize_impls_amd.functions import _fused
+    from pytorch_quantize_impls_amd.layers import BinConv2d
+
+    C, H, stride, G, k, Cout = SHAPES[index]
+    pad = k // 2
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(index)
+    layer = BinConv2d(C, Cout, k, stride=stride, padding=pad, groups=G).to(dev)
+    layer.weight.data.uniform_(-1.2, 1.2)
+    layer.binary_input = True
+    args = (layer.stride, layer.padding, layer.dilation, G)
+    x = torch.where(torch.rand(B.BATCH, C, H, H, generator=g) < 0.5, -1.0, 1.0).to(dev)
+    xg = x.clone().requires_grad_(True)
+
+    def node(fn):
+        return lambda inp: fn.apply(inp, layer.weight, layer.bias, "binary", None, ops.STE_THRESHOLD, args)
+
+    def library(inp):                                       # in a step the library computes the weight gradient too
+        wq = torch.where(layer.weight.detach() < 0, -1.0, 1.0).requires_grad_(inp.requires_grad)
+        return F.conv2d(inp, wq, layer.bias, stride, pad, 1, G)
+
+    forward = {"mfma": node(_fused.GroupedMfmaConv2dFn), "loop": lambda inp: _fused.grouped_quant_conv(layer, inp, "binary", layer._op),
+               "torch": library,
+               "stream": node(_fused.GroupedConv2dFn)}
+    taken = ops.grouped_mfma_applicable(x.shape, layer.weight.shape, *args)
+    if not taken:
+        del forward["mfma"]
+    with torch.no_grad():
+        want = forward["loop"](x)
+        go = torch.randn(want.shape, generator=g).to(dev)
+        for r in set(forward) - {"loop", "torch"}:         # integer sums plus the bias: the same bits on every route of ours
+            assert torch.equal(forward[r](x), want), r
+    if taken:
+        calls = dict(_lib.call_counts)
+        forward["mfma"](xg).backward(go)
+        used = {k_: v - calls.get(k_, 0) for k_, v in _lib.call_counts.items() if v != calls.get(k_, 0)}
+        assert used == {"qt_gmconv2d_f32": 1, "qt_gmconv2d_grad_input_f32": 1, "qt_gconv2d_grad_weight_f32": 1}, used
+
+    def fwd(r):
+        def run():
+            with torch.no_grad():
+                forward[r](x)
+        return run
+
+    def step(r):
+        def run():
+            forward[r](xg).backward(go)
+            xg.grad = None
+            layer.zero_grad(set_to_none=True)
+        return run
+
+    def run_us(fn, steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6 / steps
+
+    x_b, y_b, m = 4 * x.numel(), 4 * want.numel(), want.numel() * (C // G) * k * k
+    nbytes, macs = {"fwd": x_b + y_b, "fwd_bwd": 3 * (x_b + y_b)}, {"fwd": m, "fwd_bwd": 3 * m}
+    result = {"channels": C, "out_channels": Cout, "map": H, "stride": stride, "groups": G, "cin_g": C // G, "cout_g": Cout // G,
+              "kernel": k, "bytes": nbytes, "macs": macs, "mfma_takes_it": taken}
+    for mode, make in (("fwd", fwd), ("fwd_bwd", step)):
+        fns = {r: make(r) for r in forward}
+        steps = {r: (2 if r == "loop" else 10) for r in fns}
+        for fn in fns.values():
+            for _ in range(2):
+                fn()
+        samples = {r: [] for r in fns}
+        for _ in range(rounds):
+            for r, fn in fns.items():
+                samples[r].append(run_us(fn, steps[r]))
+        result[mode] = {r: {"median_us": round(sorted(v)[len(v) // 2], 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1)}
+                        for r, v in samples.items()}
+        if not taken:
+            continue
+        t = result[mode]["mfma"]["median_us"] * 1e-6
+        result[mode]["mfma"].update(hbm_share=round(nbytes[mode] / B.HBM_BYTES_PER_S / t, 3),
+                                    mfma_share=round(6 * macs[mode] / BF16_FLOPS / t, 3))
+    print(json.dumps(result))
+
+
+def shape_passes(s):
+    """None: the route declines the row (it keeps the loop whatever the switch says)."""
+    if not s["mfma_takes_it"]:
+        return None
+    return all(s[m]["mfma"]["max_us"] < s[m]["loop"]["min_us"] for m in ("fwd", "fwd_bwd"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--out", default=os.path.join(B.ROOT, "profiles", "grouped_mfma_bench_line.json"))
+    ap.add_argument("--child", type=int, default=None)
+    a = ap.parse_args()
+    if a.child is not None:
+        return child(a.child, a.rounds)
+    shapes = []
+    for i in range(len(SHAPES)):
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(i), "--rounds", str(a.rounds)],
+                           stdout=subprocess.PIPE, text=True, timeout=B.CHILD_LIMIT_S)
+        if p.returncode != 0:
+            raise SystemExit(f"shape {SHAPES[i]}: the measuring process ended with status {p.returncode}; nothing more was started")
+        shapes.append(json.loads(p.stdout.strip().splitlines()[-1]))
+        print(json.dumps(shapes[-1]), file=sys.stderr)
+    from pytorch_quantize_impls_amd.functions import _fused
+    line = {"bench": "grouped_mfma", "batch": B.BATCH, "rounds": a.rounds, "dtype": "float32", "layout": "NCHW",
+            "hbm_bytes_per_s": B.HBM_BYTES_PER_S, "bf16_flops": BF16_FLOPS, "shapes": shapes,
+            "shape_passes_rule": [shape_passes(s) for s in shapes], "grouped_mfma_by_rule": all(shape_passes(s) is not False for s in shapes),
+            "grouped_mfma_shipped": bool(_fused.GROUPED_MFMA)}
+    text = json.dumps(line)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.write(text + "\n")
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
