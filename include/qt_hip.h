@@ -1388,7 +1388,8 @@ int qt_gconv2d_grad_weight_f32(const float* go, const float* x, const float* w, 
  * 16, 24 or 32 input channels per group — the grouped 3 x 3 of the last ResNeXt stages as BinConv2d / TerConv2d(groups = G) —
  * where the streaming kernels above are compute-bound.  A workgroup works inside ONE group, so the block-diagonal operand costs
  * nothing: csrc/gconv_mfma.hip, DESIGN.md "Grouped convs on the matrix cores".  The weight gradient of these layers is
- * qt_gconv2d_grad_weight_f32 above, which takes them as they are.
+ * qt_gmconv2d_grad_weight_f32 below (six bf16 products per real x real term, same launch shape); qt_gconv2d_grad_weight_f32 above
+ * takes them as they are too, in plain fp32.
  *
  * Operands, layouts, strides and `kind` as for qt_gconv2d_f32 / qt_gconv2d_grad_input_f32 (fp32, each tensor dense NCHW or
  * channels-last, the two of a call need not share a layout).  x and go may hold ANY value: nothing asks whether they are +-1.
@@ -1427,6 +1428,37 @@ int qt_gmconv2d_grad_input_f32(const float* go, const float* w, float* gx, int64
                                int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n,
                                int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w,
                                int kind, qt_stream_t stream);
+
+/* The weight gradient of the same layers on the matrix cores (and the bias gradient from the same pass), inside the window above:
+ *   gw[g cout_g + oc, ci, i, j] = sum over (n, ho, wo) of go[n, g cout_g + oc, ho, wo] x[n, g cin_g + ci, ho s - p + i, wo s - p + j]
+ *   gbias[c] = sum over (n, ho, wo) of go[n, c, ho, wo]
+ * Arguments, layouts and the two launches (partials, then the splits in index order with the STE mask: gw is zeroed where
+ * |w| > ste_threshold > 0) are those of qt_gconv2d_grad_weight_f32; `w` may be null when ste_threshold is 0, `gbias` may be null.
+ * `work` holds qt_gmconv2d_grad_weight_work_floats(...) floats (splits x G x (kh kw cout_g cin_g + cout_g); one value for both
+ * layouts), need not be zero and must be 16-byte aligned.  Splits per group: at most QT_GM_WGRAD_MAX_SPLITS.
+ *
+ * Arithmetic: BOTH operands are real, so each element of go and of x is split EXACTLY into three bf16 terms as above
+ * (g = gh + gm + gl, x = xh + xm + xl) and the six products of the real x real convention (qt_bf16x6_pack_f32) are kept:
+ * gh xh, gh xm, gh xl, gm xh, gm xm, gl xh; the three dropped ones (gm xl, gl xm, gl xl) are below 2^-23 |g x| together.  Each
+ * product is exact; they are accumulated in fp32 inside v_mfma_f32_16x16x32_bf16 and across the splits in an order fixed by the
+ * shapes and the layouts alone (no atomics: equal inputs give equal bits).  For finite inputs of normal range, with L = N Ho Wo:
+ *   |gw - exact| <= (6 L + QT_GM_WGRAD_MAX_SPLITS + 2) 2^-23 sum |go x|,   |gbias - exact| <= (3 L + QT_GM_WGRAD_MAX_SPLITS + 1) 2^-23 sum |go|.
+ * Where both operands have at most 16 significant bits (or one has 24 and the other 8: every dropped product is then zero) and
+ * sum |go x| stays below 2^24 units of a common power of two, the results ARE the exact sums.  Non-finite elements: as above.
+ *
+ * Validation, before anything is enqueued: steps 1 - 3 above; then a null go, x, gw or work, a null w with ste_threshold > 0, a
+ * negative or NaN ste_threshold, strides that are neither dense layout, work_floats below the need: QT_ERR_INVALID_ARG; a pointer
+ * that is not 4-byte aligned, `work` not 16-byte aligned: QT_ERR_ALIGNMENT.  An empty problem (step 2) writes nothing and needs 0
+ * floats; qt_gmconv2d_grad_weight_work_floats returns the negative status where the shape is refused. */
+#define QT_GM_WGRAD_MAX_SPLITS   128
+
+int64_t qt_gmconv2d_grad_weight_work_floats(int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw,
+                                            int sh, int sw, int ph, int pw, int dh, int dw);
+int qt_gmconv2d_grad_weight_f32(const float* go, const float* x, const float* w, float* gw, float* gbias, float* work,
+                                int64_t work_floats, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W,
+                                int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n, int64_t gs_c,
+                                int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w,
+                                float ste_threshold, qt_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Depthwise and grouped convolution on half-precision operands: the six entries above for bf16 / fp16 models

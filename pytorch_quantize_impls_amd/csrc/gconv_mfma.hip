@@ -304,26 +304,44 @@ int gm_launch(int ncb, const float* src, const float* w, const float* bias, floa
     return qt_check_launch();
 }
 
-// The validation both entries share, in the documented order.  in / out: the tensor read (x, go) and the one written (y, gx).
+// Steps 1 to 3 of the documented validation order, shared by every entry: the sizes, the empty problem, the limits.  False: the
+// call ends with `rc`; true: Ho x Wo is the output map of a problem inside the window.
+bool gm_shape(int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw,
+              int dh, int dw, int64_t& Ho, int64_t& Wo, int& rc) {
+    rc = QT_ERR_INVALID_ARG;
+    if (N < 0 || G < 0 || cin_g < 1 || cout_g < 1 || H < 0 || W < 0 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || ph < 0 || pw < 0 ||
+        dh < 1 || dw < 1)
+        return false;
+    rc = QT_ERR_UNSUPPORTED;
+    if ((int64_t)kh * kw > QT_DW_MAX_TAPS) return false;
+    if (N == 0 || G == 0 || H == 0 || W == 0) {
+        rc = QT_OK;
+        return false;
+    }
+    if ((cin_g != 16 && cin_g != 24 && cin_g != 32) || (cout_g & 15) || cout_g > GM_MAX_COUT_G) return false;
+    if (!((kh == 1 && kw == 1) || (kh == 3 && kw == 3)) || sh != sw || sh > 2 || dh != 1 || dw != 1 || ph > 1 || pw > 1) return false;
+    if (N >= GM_MAX_ELEMS || G >= GM_MAX_ELEMS || H >= GM_MAX_ELEMS || W >= GM_MAX_ELEMS) return false;
+    const int64_t eh = H + 2 * (int64_t)ph - kh, ew = W + 2 * (int64_t)pw - kw;
+    if (eh < 0 || ew < 0) {                                       // the kernel does not fit the padded image
+        rc = QT_ERR_INVALID_ARG;
+        return false;
+    }
+    Ho = eh / sh + 1;
+    Wo = ew / sw + 1;
+    return (double)N * (double)(G * cin_g) * (double)H * (double)W < (double)GM_MAX_ELEMS &&
+           (double)N * (double)(G * cout_g) * (double)Ho * (double)Wo < (double)GM_MAX_ELEMS &&
+           (double)(G * cout_g) <= (double)QT_DW_MAX_CHANNELS;
+}
+
+// The validation of the forward and grad_input entries, in the documented order.  in / out: the tensor read (x, go) and the one
+// written (y, gx).
 int gm_entry(bool bwd, const float* in, const float* w, const float* bias, float* out, int64_t N, int64_t G, int64_t cin_g,
              int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, const DwStrides& is,
              const DwStrides& os, int kind, qt_stream_t stream) {
-    if (N < 0 || G < 0 || cin_g < 1 || cout_g < 1 || H < 0 || W < 0 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || ph < 0 || pw < 0 ||
-        dh < 1 || dw < 1)
-        return QT_ERR_INVALID_ARG;
-    if ((int64_t)kh * kw > QT_DW_MAX_TAPS) return QT_ERR_UNSUPPORTED;
-    if (N == 0 || G == 0 || H == 0 || W == 0) return QT_OK;
-    if ((cin_g != 16 && cin_g != 24 && cin_g != 32) || (cout_g & 15) || cout_g > GM_MAX_COUT_G) return QT_ERR_UNSUPPORTED;
-    if (!((kh == 1 && kw == 1) || (kh == 3 && kw == 3)) || sh != sw || sh > 2 || dh != 1 || dw != 1 || ph > 1 || pw > 1)
-        return QT_ERR_UNSUPPORTED;
-    if (N >= GM_MAX_ELEMS || G >= GM_MAX_ELEMS || H >= GM_MAX_ELEMS || W >= GM_MAX_ELEMS) return QT_ERR_UNSUPPORTED;
-    const int64_t eh = H + 2 * (int64_t)ph - kh, ew = W + 2 * (int64_t)pw - kw;
-    if (eh < 0 || ew < 0) return QT_ERR_INVALID_ARG;              // the kernel does not fit the padded image
-    const int64_t Ho = eh / sh + 1, Wo = ew / sw + 1;
+    int64_t Ho, Wo;
+    int rc;
+    if (!gm_shape(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, Ho, Wo, rc)) return rc;
     const int64_t Cin = G * cin_g, Cout = G * cout_g;
-    if ((double)N * (double)Cin * (double)H * (double)W >= (double)GM_MAX_ELEMS ||
-        (double)N * (double)Cout * (double)Ho * (double)Wo >= (double)GM_MAX_ELEMS || (double)Cout > (double)QT_DW_MAX_CHANNELS)
-        return QT_ERR_UNSUPPORTED;
     if (kind != QT_DW_RAW && kind != QT_DW_SIGN && kind != QT_DW_TERNARY) return QT_ERR_INVALID_ARG;
     if (!in || !w || !out) return QT_ERR_INVALID_ARG;
     const DwStrides& xs = bwd ? os : is;
@@ -341,7 +359,357 @@ int gm_entry(bool bwd, const float* in, const float* w, const float* bias, float
                    : gm_launch<1>(g.KC / 8, in, w, bias, out, g, is, os, kind, s);
 }
 
+// ---- the weight gradient ------------------------------------------------------------------------------------------------------------
+//     gw[g cout_g + oc, ci, i, j] = sum over (n, ho, wo) of  go[n, g cout_g + oc, ho, wo] * x[n, g cin_g + ci, ho s - p + i, wo s - p + j]
+// is per group a dense [cin_g taps x L] . [L x cout_g] product whose reduction runs over the L = N Ho Wo output PIXELS; both
+// operands are real, so both are split exactly into three bf16 terms and the six products of the project's real x real convention
+// (gh xh, gh xm, gh xl, gm xh, gm xm, gl xh) go into one fp32 accumulator.
+//
+// Work split: as above, grid = G x splits, a workgroup owns one group and walks tiles split, split + S, ... of the flat (n, tile of
+// output pixels) index with its accumulators in registers; at the end it writes ONE partial [split][g][tap][oc][ci] (+ [oc] for the
+// bias gradient) with float4 stores.  gmw_reduce_kernel sums the splits in index order, masks and writes gw / gbias.
+// Per tile: the go tile (TR x TC output pixels, zero-filled up to a multiple of 32) and the x patch (the bounding box the tile's taps
+// read, clipped to the image; pixel npmax is a ZERO pixel) are staged once each, split, pixel-major [term][pixel][channels (+ pad)]
+// like the forward's patch; offs[tap][q] is the patch offset of output pixel q's source under that tap, or the zero pixel's.
+// Fragments: v_mfma_f32_16x16x32_bf16 wants 8 consecutive k (here: pixels) of one channel per lane.  ds_read_b64_tr_b16 makes
+// them out of the pixel-major tiles: in a 16-lane group lane q gives the address of 4 channels (q & 3) of pixel row (q >> 2) and
+// lane i receives channel i of the four rows; two reads per fragment.  Every lane supplies its own row address, so the x rows come
+// straight from the offset table: no branch, no coordinate arithmetic in the main loop.
+// Roles: x is the MFMA's A operand (rows = ci), go its B operand (columns = oc), so a lane's accumulator quad is 4 consecutive ci
+// of one oc: one float4 of the partial.  Items are (row tile of 16 oc, column tile of 16 ci, tap) plus one "bias" item per row tile
+// (go against a register fragment of ones: gbias from the same pass); the four waves take contiguous, balanced runs of them, so a
+// wave's go fragments of a 32-pixel chunk are reused across its taps.  cin_g = 24 reads 8 channels past the pixel in its second
+// column tile (the neighbour's, or the 16 bytes of slack after the last): MFMA rows are independent and those rows are never stored.
+
+constexpr int GMW_MAX_SPLITS = QT_GM_WGRAD_MAX_SPLITS;
+
+struct GmwPlan {
+    int TR, TC, tiles_r, tiles_c;
+    int splits;
+    int npmax;               // x patch pixels per term; pixel npmax is the zero pixel
+    int gpix;                // go tile pixels per term: TR * TC rounded up to the chunk of 32
+    int gvec;                // go is channels-last and 16-byte aligned (GmGeom::vec says so for x)
+    int lds_bytes;
+};
+
+typedef short gm_s4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) gm_s4 gm_lds_s4;
+
+// the fragment of the two transposing reads at LDS bytes a and b: elements 0-3 from a, 4-7 from b
+__device__ __forceinline__ gm_bf8 gmw_frag(const unsigned char* a, const unsigned char* b) {
+    const gm_s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((gm_lds_s4*)a);
+    const gm_s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((gm_lds_s4*)b);
+    gm_bf8 f;
+    __builtin_memcpy(&f, &lo, 8);
+    __builtin_memcpy(reinterpret_cast<unsigned char*>(&f) + 8, &hi, 8);
+    return f;
+}
+
+// Stage pixels [0, nfill) of a PW-wide box at `base` (8 NCB channels from there) into dst[term][pixel][PS]: pixels below np are read,
+// split into three terms and stored as three 16-byte writes, the others are zero.  Lanes as in the forward's stage.
+template <int NCB>
+__device__ __forceinline__ void gmw_stage(const float* __restrict__ base, const DwStrides& st, int vec, int PW, int np, int nfill,
+                                          unsigned char* dst, int TS, int tid) {
+    constexpr int PS = gm_ps(NCB);
+    for (int e = tid; e < nfill * NCB; e += DW_THREADS) {
+        int cb, pp;
+        if (st.c == 1) {
+            pp = e / NCB;
+            cb = e - pp * NCB;
+        } else {
+            cb = e / nfill;
+            pp = e - cb * nfill;
+        }
+        uint32_t hi[4] = {0u, 0u, 0u, 0u}, mid[4] = {0u, 0u, 0u, 0u}, lo[4] = {0u, 0u, 0u, 0u};
+        if (pp < np) {
+            const int row = pp / PW, col = pp - row * PW;
+            const float* sp = base + row * st.h + col * st.w + cb * 8 * st.c;
+            float v[8];
+            if (vec) {
+                const float4 a = *reinterpret_cast<const float4*>(sp), b = *reinterpret_cast<const float4*>(sp + 4);
+                v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = sp[k * st.c];
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) gm_split(v[k], k, hi, mid, lo);
+        }
+        unsigned char* pd = dst + pp * PS + cb * 16;
+        *reinterpret_cast<uint4*>(pd) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+        *reinterpret_cast<uint4*>(pd + TS) = make_uint4(mid[0], mid[1], mid[2], mid[3]);
+        *reinterpret_cast<uint4*>(pd + 2 * TS) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+    }
+}
+
+// floats of one (split, group) block of the partials: [tap][oc][ci], then the bias gradient [oc]
+__host__ __device__ inline int64_t gmw_block(int taps, int cout_g, int cin_g) { return (int64_t)taps * cout_g * cin_g + cout_g; }
+
+// NCBX: blocks of 8 input channels of a group (2, 3, 4); RT: row tiles of 16 output channels (1, 2, 3)
+template <int TAPS, int NCBX, int RT>
+__global__ __launch_bounds__(DW_THREADS) void gmw_kernel(const float* __restrict__ go, const float* __restrict__ x,
+                                                         float* __restrict__ work, GmGeom g, DwStrides gs, DwStrides xs, GmwPlan pl) {
+    constexpr int CIN = NCBX * 8, COUT = RT * 16, CT = (NCBX + 1) / 2, NCBG = RT * 2, PSX = gm_ps(NCBX), PSG = gm_ps(NCBG);
+    constexpr int KS = TAPS == 9 ? 3 : 1;
+    constexpr int CONV = RT * CT * TAPS, ITEMS = CONV + RT, IPW = (ITEMS + 3) / 4;         // the bias items come last
+    extern __shared__ __attribute__((aligned(16))) unsigned char gm_smem[];
+    int* offs = reinterpret_cast<int*>(gm_smem);                                            // [TAPS][128]
+    unsigned char* gt = gm_smem + TAPS * GM_TILE_PIX * 4;                                   // [3][gpix][PSG]
+    const int TSG = pl.gpix * PSG, TSX = (pl.npmax + 1) * PSX, zero_off = pl.npmax * PSX;
+    unsigned char* patch = gt + 3 * TSG;                                                    // [3][npmax + 1][PSX] (+ 16 bytes)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int grp = (int)(blockIdx.x / pl.splits);
+    const int split = (int)(blockIdx.x - (unsigned)grp * pl.splits);
+
+    for (int e = tid; e < 3 * (PSX / 16); e += DW_THREADS) {                                // the zero pixel of every term
+        const int term = e / (PSX / 16), sl = e - term * (PSX / 16);
+        *reinterpret_cast<uint4*>(patch + term * TSX + zero_off + sl * 16) = make_uint4(0u, 0u, 0u, 0u);
+    }
+
+    // this wave's items it0 <= it < it1, decoded once: the row tile, and for a conv item the tap's table and the column tile's bytes
+    const int it0 = (wave * ITEMS) >> 2, it1 = ((wave + 1) * ITEMS) >> 2;
+    int irt[IPW], itab[IPW], icol[IPW];
+    gm_f4 acc[IPW];
+#pragma unroll
+    for (int j = 0; j < IPW; ++j) {
+        const int it = it0 + j;
+        const int rt = it / (CT * TAPS), rem = it - rt * (CT * TAPS);
+        const int ct = rem / TAPS;
+        irt[j] = it < CONV ? rt : it - CONV;
+        itab[j] = (rem - ct * TAPS) * GM_TILE_PIX;
+        icol[j] = ct * 32;
+        acc[j] = gm_f4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+    // lane l of a transposing read: pixel row 8 (l >> 4) + ((l & 15) >> 2) of the chunk (+ 4 for the second read), channels 4 (l & 3)
+    const int prow = 8 * (lane >> 4) + ((lane & 15) >> 2), csub = (lane & 3) * 8;
+    gm_bf8 ones, none;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        ones[k] = (__bf16)1.0f;
+        none[k] = (__bf16)0.0f;
+    }
+
+    const int tiles = pl.tiles_r * pl.tiles_c;
+    const int units = g.N * tiles;
+    for (int u = split; u < units; u += pl.splits) {                 // uniform over the workgroup: so are the barriers
+        const int n = u / tiles, tt = u - n * tiles;
+        const int tr = tt / pl.tiles_c, tc = tt - tr * pl.tiles_c;
+        const int r0 = tr * pl.TR, c0 = tc * pl.TC;
+        const int TRa = gm_min(pl.TR, g.Hd - r0), TCa = gm_min(pl.TC, g.Wd - c0);
+        const int npix = TRa * TCa;
+        int lo_r, PH, lo_c, PW;
+        gm_span(0, r0, r0 + TRa, g.s, g.ph, KS, g.Hs, lo_r, PH);
+        gm_span(0, c0, c0 + TCa, g.s, g.pw, KS, g.Ws, lo_c, PW);
+        __syncthreads();                                              // the previous tile has been read
+        gmw_stage<NCBG>(go + n * gs.n + (int64_t)grp * COUT * gs.c + r0 * gs.h + c0 * gs.w, gs, pl.gvec, TCa, npix, pl.gpix, gt, TSG, tid);
+        gmw_stage<NCBX>(x + n * xs.n + (int64_t)grp * CIN * xs.c + lo_r * xs.h + lo_c * xs.w, xs, g.vec, PW, PH * PW, PH * PW, patch, TSX,
+                        tid);
+        for (int e = tid; e < TAPS * GM_TILE_PIX; e += DW_THREADS) {
+            const int t = e / GM_TILE_PIX, q = e - t * GM_TILE_PIX;
+            const bool in = q < npix;
+            const int qr = in ? q / TCa : 0;
+            const int sr = (r0 + qr) * g.s - g.ph + t / KS, sc = (c0 + (in ? q - qr * TCa : 0)) * g.s - g.pw + (t - t / KS * KS);
+            const bool ok = in && (unsigned)(sr - lo_r) < (unsigned)PH && (unsigned)(sc - lo_c) < (unsigned)PW;   // inside the image
+            offs[e] = ok ? ((sr - lo_r) * PW + (sc - lo_c)) * PSX : zero_off;
+        }
+        __syncthreads();
+
+        const int nch = (npix + 31) >> 5;
+        for (int ch = 0; ch < nch; ++ch) {
+            const int q = ch * 32 + prow;
+            const unsigned char* ga = gt + q * PSG + csub;
+            int prt = -1;
+            gm_bf8 gh = none, gmid = none, gl = none;
+#pragma unroll
+            for (int j = 0; j < IPW; ++j) {
+                if (it0 + j < it1) {                                  // wave-uniform, like every test on irt[]
+                    if (irt[j] != prt) {
+                        prt = irt[j];
+                        const unsigned char* gp = ga + prt * 32;
+                        gh = gmw_frag(gp, gp + 4 * PSG);
+                        gmid = gmw_frag(gp + TSG, gp + TSG + 4 * PSG);
+                        gl = gmw_frag(gp + 2 * TSG, gp + 2 * TSG + 4 * PSG);
+                    }
+                    gm_bf8 xh = ones, xm = none, xl = none;
+                    if (it0 + j < CONV) {
+                        const unsigned char* xa = patch + offs[itab[j] + q] + icol[j] + csub;
+                        const unsigned char* xb = patch + offs[itab[j] + q + 4] + icol[j] + csub;
+                        xh = gmw_frag(xa, xb);
+                        xm = gmw_frag(xa + TSX, xb + TSX);
+                        xl = gmw_frag(xa + 2 * TSX, xb + 2 * TSX);
+                    }
+                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, gh, acc[j], 0, 0, 0);
+                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xm, gh, acc[j], 0, 0, 0);
+                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl, gh, acc[j], 0, 0, 0);
+                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, gmid, acc[j], 0, 0, 0);
+                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xm, gmid, acc[j], 0, 0, 0);
+                    acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, gl, acc[j], 0, 0, 0);
+                }
+            }
+        }
+    }
+
+    // D[row = 4 (lane >> 4) + i][col = lane & 15]: 4 consecutive ci of output channel irt * 16 + (lane & 15)
+    float* part = work + ((int64_t)split * g.G + grp) * gmw_block(TAPS, COUT, CIN);
+#pragma unroll
+    for (int j = 0; j < IPW; ++j) {
+        if (it0 + j >= it1) continue;
+        const int oc = irt[j] * 16 + (lane & 15);
+        if (it0 + j < CONV) {
+            const int ci = (icol[j] >> 1) + 4 * (lane >> 4);
+            if (ci < CIN)                                             // the padded columns of cin_g = 24 are dropped here
+                *reinterpret_cast<float4*>(part + ((int64_t)(itab[j] / GM_TILE_PIX) * COUT + oc) * CIN + ci) =
+                    make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+        } else if (lane < 16) {                                       // every row of a bias item holds the same sums
+            part[TAPS * COUT * CIN + oc] = acc[j][0];
+        }
+    }
+}
+
+// second launch: the splits in index order, the STE mask on the unquantised weight (the rule of gc_grad_weight_combine_kernel), gw
+// in the weight's own [G cout_g, cin_g, kh, kw] order, then gbias
+__global__ __launch_bounds__(DW_THREADS) void gmw_reduce_kernel(const float* __restrict__ work, const float* __restrict__ w,
+                                                                float* __restrict__ gw, float* __restrict__ gbias, int G, int cout_g,
+                                                                int cin_g, int taps, int splits, float thr) {
+    const int64_t blk = gmw_block(taps, cout_g, cin_g);
+    const int64_t nw = (int64_t)G * cout_g * cin_g * taps, total = nw + (gbias ? (int64_t)G * cout_g : 0);
+    for (int64_t e = (int64_t)blockIdx.x * DW_THREADS + threadIdx.x; e < total; e += (int64_t)gridDim.x * DW_THREADS) {
+        int64_t co, at;                                               // the output channel and the element's place in a block
+        if (e < nw) {
+            co = e / (cin_g * taps);
+            const int rem = (int)(e - co * (cin_g * taps)), ci = rem / taps, t = rem - ci * taps;
+            at = ((int64_t)t * cout_g + co % cout_g) * cin_g + ci;
+        } else {
+            co = e - nw;
+            at = (int64_t)taps * cout_g * cin_g + co % cout_g;
+        }
+        const float* p = work + (co / cout_g) * blk + at;
+        const int64_t step = (int64_t)G * blk;
+        float s = 0.0f;
+        int sp = 0;
+        for (; sp + 8 <= splits; sp += 8) {                           // eight loads in flight, added in index order all the same
+            float v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = p[(sp + k) * step];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s = s + v[k];
+        }
+        for (; sp < splits; ++sp) s = s + p[sp * step];
+        if (e >= nw) {
+            gbias[co] = s;
+        } else {
+            if (thr > 0.0f && fabsf(w[e]) > thr) s = 0.0f;
+            gw[e] = s;
+        }
+    }
+}
+
+// the tile of the output map and the LDS it needs: as gm_plan, with the go tile beside the x patch and no weights
+GmwPlan gmw_plan(const GmGeom& g, int taps, int ncbx, int rt) {
+    GmwPlan pl{};
+    const int ks = taps == 9 ? 3 : 1, psx = gm_ps(ncbx), psg = gm_ps(2 * rt);
+    auto need = [&](int tr, int tc) { return gm_span_cap(0, tr, g.s, ks, g.Hs) * gm_span_cap(0, tc, g.s, ks, g.Ws); };
+    auto bytes = [&](int tr, int tc) {
+        return taps * GM_TILE_PIX * 4 + 3 * ((tr * tc + 31) & ~31) * psg + 3 * (need(tr, tc) + 1) * psx + 16;
+    };
+    int tc = gm_min(g.Wd, GM_TILE_COLS);
+    pl.tiles_c = (g.Wd + tc - 1) / tc;
+    tc = (g.Wd + pl.tiles_c - 1) / pl.tiles_c;
+    int tr = gm_min(g.Hd, GM_TILE_PIX / tc);
+    while (bytes(tr, tc) > GM_LDS_BYTES) {                            // a 1 x 1 tile needs under 20 KiB: this ends
+        if (tr > 1) --tr;
+        else --tc;
+    }
+    pl.tiles_c = (g.Wd + tc - 1) / tc;
+    pl.tiles_r = (g.Hd + tr - 1) / tr;
+    pl.TR = (g.Hd + pl.tiles_r - 1) / pl.tiles_r;
+    pl.TC = (g.Wd + pl.tiles_c - 1) / pl.tiles_c;
+    pl.npmax = need(pl.TR, pl.TC);
+    pl.gpix = (pl.TR * pl.TC + 31) & ~31;
+    pl.lds_bytes = bytes(pl.TR, pl.TC);
+    const int64_t units = (int64_t)g.N * pl.tiles_r * pl.tiles_c;
+    int64_t s = (GM_TARGET_WGS + g.G - 1) / g.G;
+    if (s > GMW_MAX_SPLITS) s = GMW_MAX_SPLITS;
+    if (s > units) s = units;
+    pl.splits = (int)s;
+    return pl;
+}
+
+GmGeom gmw_geom(int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int64_t Ho, int64_t Wo, int s, int ph,
+                int pw) {
+    GmGeom g{};
+    g.N = (int)N; g.G = (int)G; g.KC = (int)cin_g; g.NO = (int)cout_g;
+    g.Hs = (int)H; g.Ws = (int)W; g.Hd = (int)Ho; g.Wd = (int)Wo;
+    g.s = s; g.ph = ph; g.pw = pw;
+    return g;
+}
+
+template <int TAPS, int NCBX>
+void gmw_launch(int rt, unsigned grid, hipStream_t s, const float* go, const float* x, float* work, const GmGeom& g, const DwStrides& gs,
+                const DwStrides& xs, const GmwPlan& pl) {
+#define GMW_GO(RT) gmw_kernel<TAPS, NCBX, RT><<<grid, DW_THREADS, (size_t)pl.lds_bytes, s>>>(go, x, work, g, gs, xs, pl)
+    if (rt == 1) GMW_GO(1);
+    else if (rt == 2) GMW_GO(2);
+    else GMW_GO(3);
+#undef GMW_GO
+}
+
+int gmw_entry(const float* go, const float* x, const float* w, float* gw, float* gbias, float* work, int64_t work_floats, int64_t N,
+              int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+              int dw, const DwStrides& gs, const DwStrides& xs, float ste_threshold, qt_stream_t stream) {
+    int64_t Ho, Wo;
+    int rc;
+    if (!gm_shape(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, Ho, Wo, rc)) return rc;
+    if (!gw || (ste_threshold > 0.0f && !w) || !(ste_threshold >= 0.0f)) return QT_ERR_INVALID_ARG;
+    if (!go || !x || !work || work_floats < 0) return QT_ERR_INVALID_ARG;
+    if (dw_layout(N, G * cout_g, Ho, Wo, gs) < 0 || dw_layout(N, G * cin_g, H, W, xs) < 0) return QT_ERR_INVALID_ARG;
+    GmGeom g = gmw_geom(N, G, cin_g, cout_g, H, W, Ho, Wo, sh, ph, pw);
+    const int taps = kh * kw, ncbx = (int)cin_g / 8, rt = (int)cout_g / 16;
+    GmwPlan pl = gmw_plan(g, taps, ncbx, rt);
+    if (work_floats < (int64_t)pl.splits * G * gmw_block(taps, (int)cout_g, (int)cin_g)) return QT_ERR_INVALID_ARG;
+    if (!dw_aligned4(gw) || !dw_aligned4(gbias) || !dw_aligned4(w) || !dw_aligned4(go) || !dw_aligned4(x) || !qt_aligned16(work))
+        return QT_ERR_ALIGNMENT;                                      // the partials are written as float4
+    g.vec = xs.c == 1 && qt_aligned16(x) ? 1 : 0;
+    pl.gvec = gs.c == 1 && qt_aligned16(go) ? 1 : 0;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned grid = (unsigned)(G * pl.splits);
+    if (taps == 9) {
+        if (ncbx == 2) gmw_launch<9, 2>(rt, grid, s, go, x, work, g, gs, xs, pl);
+        else if (ncbx == 3) gmw_launch<9, 3>(rt, grid, s, go, x, work, g, gs, xs, pl);
+        else gmw_launch<9, 4>(rt, grid, s, go, x, work, g, gs, xs, pl);
+    } else {
+        if (ncbx == 2) gmw_launch<1, 2>(rt, grid, s, go, x, work, g, gs, xs, pl);
+        else if (ncbx == 3) gmw_launch<1, 3>(rt, grid, s, go, x, work, g, gs, xs, pl);
+        else gmw_launch<1, 4>(rt, grid, s, go, x, work, g, gs, xs, pl);
+    }
+    const int st = qt_check_launch();
+    if (st != QT_OK) return st;
+    const int64_t total = G * cout_g * (cin_g * taps + 1);
+    gmw_reduce_kernel<<<qt_stream_grid((total + DW_THREADS - 1) / DW_THREADS), DW_THREADS, 0, s>>>(
+        work, w, gw, gbias, (int)G, (int)cout_g, (int)cin_g, taps, pl.splits, ste_threshold);
+    return qt_check_launch();
+}
+
 }  // namespace
+
+extern "C" int64_t qt_gmconv2d_grad_weight_work_floats(int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W,
+                                                       int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw) {
+    int64_t Ho, Wo;
+    int rc;
+    if (!gm_shape(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, Ho, Wo, rc)) return rc;      // an empty problem: 0
+    const GmwPlan pl = gmw_plan(gmw_geom(N, G, cin_g, cout_g, H, W, Ho, Wo, sh, ph, pw), kh * kw, (int)cin_g / 8, (int)cout_g / 16);
+    return (int64_t)pl.splits * G * gmw_block(kh * kw, (int)cout_g, (int)cin_g);
+}
+
+extern "C" int qt_gmconv2d_grad_weight_f32(const float* go, const float* x, const float* w, float* gw, float* gbias, float* work,
+                                           int64_t work_floats, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H,
+                                           int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n,
+                                           int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h,
+                                           int64_t xs_w, float ste_threshold, qt_stream_t stream) {
+    return gmw_entry(go, x, w, gw, gbias, work, work_floats, N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw,
+                     DwStrides{gs_n, gs_c, gs_h, gs_w}, DwStrides{xs_n, xs_c, xs_h, xs_w}, ste_threshold, stream);
+}
 
 extern "C" int qt_gmconv2d_f32(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t G, int64_t cin_g,
                                int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,

@@ -2181,7 +2181,8 @@ class GroupedConv2dFn(QtFunction):
 # Here a group IS a matrix-core shape once a workgroup works inside one group: its output channels are one to three MFMA column
 # tiles, a K chunk of 32 is two taps of 16 channels or one tap of 32 (csrc/gconv_mfma.hip, DESIGN.md "Grouped convs on the matrix
 # cores").  Forward and grad_input each one launch on three exact bf16 terms of the real operand; the weight gradient (and the bias
-# gradient with it) is the grouped family's streaming kernel.  As above nothing asks whether the activation is +-1.
+# gradient with it) is the grouped family's streaming kernel, or — behind GROUPED_MFMA_WGRAD — six bf16 products of both operands'
+# terms on the matrix cores.  As above nothing asks whether the activation is +-1.
 
 #: fewer groups keep the per-group loop (tests/test_gpu_gconv.py pins four groups of 32 channels on it)
 GROUPED_MFMA_MIN_GROUPS = 8
@@ -2191,7 +2192,27 @@ GROUPED_MFMA_MIN_GROUPS = 8
 #: (profiles/grouped_mfma_bench_line.json): it does on all five rows the route takes, 6.8x - 32x forward and 2.9x - 25x a step.
 GROUPED_MFMA = True
 
+#: the backward of ``GroupedMfmaConv2dFn`` takes the weight gradient on the matrix cores too (qt_gmconv2d_grad_weight_f32) when the
+#: reduction is long enough (False: the grouped family's streaming kernel, as before).  Set from tools/bench_grouped_mfma.py by the
+#: rule of DESIGN.md "Grouped convs on the matrix cores": True iff on every row the route takes the step's round range with it on
+#: lies wholly below the range with it off.  Measured (profiles/grouped_mfma_wgrad_bench_line.json): 1.2x - 2.5x faster steps on
+#: the four 3 x 3 rows, level on the 1 x 1 row (221 against 216 us, overlapping ranges): off by the rule.
+GROUPED_MFMA_WGRAD = False
+#: fewest output pixels L = N Ho Wo per channel for it.  Below 1024 a group has fewer than eight 128-pixel tiles: even 32 groups
+#: then leave most of the 256 CUs without one and the split pass is pure overhead.  NOT tuned: nothing between this floor and the
+#: smallest benchmarked shape (L = 12544) has been measured.
+GROUPED_MFMA_WGRAD_MIN_L = 1024
+
 _GROUPED_MFMA = _StreamingFamily(ops._GM, None, None)          # no plane or code form: the deferred chains decline these layers
+_GROUPED_MFMA_WGRAD = _StreamingFamily(ops._GMW, None, None)
+
+
+def grouped_mfma_wgrad_route(grad_output_shape) -> bool:
+    """The backward of a ``GroupedMfmaConv2dFn`` node whose incoming gradient has this [N, Cout, Ho, Wo] shape takes the
+    matrix-core weight gradient: ``GROUPED_MFMA_WGRAD`` is on and N Ho Wo >= ``GROUPED_MFMA_WGRAD_MIN_L``.  A pure function of
+    the switch and the shape (the node is inside the entry's window already)."""
+    N, _C, Ho, Wo = (int(v) for v in grad_output_shape)
+    return bool(GROUPED_MFMA_WGRAD) and N * Ho * Wo >= GROUPED_MFMA_WGRAD_MIN_L
 
 
 def grouped_mfma_route(layer, input) -> bool:
@@ -2204,8 +2225,9 @@ def grouped_mfma_route(layer, input) -> bool:
 
 class GroupedMfmaConv2dFn(QtFunction):
     """conv2d(x, Q(W), b, groups = G) with 16, 24 or 32 input channels per group on the matrix cores: the sibling of
-    ``GroupedConv2dFn``, same arguments.  Forward qt_gmconv2d_f32, backward qt_gmconv2d_grad_input_f32 and the grouped family's
-    grad_weight (partials + combine inside one call), the bias gradient being a by-product of the latter."""
+    ``GroupedConv2dFn``, same arguments.  Forward qt_gmconv2d_f32, backward qt_gmconv2d_grad_input_f32 and a grad_weight (partials
+    + combine inside one call, the bias gradient being a by-product): qt_gmconv2d_grad_weight_f32 where
+    ``grouped_mfma_wgrad_route`` says so, else the grouped family's streaming kernel."""
 
     @staticmethod
     def forward(ctx, input, weight, bias, kind, weight_q, ste, conv_args):
@@ -2213,7 +2235,8 @@ class GroupedMfmaConv2dFn(QtFunction):
 
     @staticmethod
     def backward(ctx, grad_output):
-        return _streaming_backward(_GROUPED_MFMA, ctx, grad_output)
+        return _streaming_backward(_GROUPED_MFMA_WGRAD if grouped_mfma_wgrad_route(grad_output.shape) else _GROUPED_MFMA, ctx,
+                                   grad_output)
 
 
 def grouped_quant_conv(layer, input, kind: str, quant_op):

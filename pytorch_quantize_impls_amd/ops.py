@@ -4311,6 +4311,11 @@ _GC = _Streaming(_streaming_entries("qt_gconv2d"), "grouped", "G * cout_g", _gc_
 _GM = _Streaming({"f32": "qt_gmconv2d_f32", "grad_input_f32": "qt_gmconv2d_grad_input_f32",
                   "grad_weight_f32": _GC.entry["grad_weight_f32"], "grad_weight_work_floats": _GC.entry["grad_weight_work_floats"]},
                  "matrix-core grouped", "G * cout_g", _gm_geometry, _gm_geometry, False)
+#: the same family with the weight gradient on the matrix cores too (qt_gmconv2d_grad_weight_f32: six bf16 products per term)
+_GMW = _GM._replace(entry={**_GM.entry, "grad_weight_f32": "qt_gmconv2d_grad_weight_f32",
+                           "grad_weight_work_floats": "qt_gmconv2d_grad_weight_work_floats"})
+#: most splits per group of that entry: the S_max of its error bound
+GM_WGRAD_MAX_SPLITS = _lib.DEFINES["QT_GM_WGRAD_MAX_SPLITS"]
 
 
 def _streaming_conv2d(fam: _Streaming, x, weight, bias, stride, padding, dilation, groups, kind="raw", out=None):
@@ -4798,6 +4803,31 @@ def grouped_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, weigh
     families).  bf16 / fp16 ``x`` and ``grad_output`` (one dtype) run qt_gconv2d_grad_weight_h; both gradients have the WEIGHT's
     dtype (fp32 under autocast), rounded once from fp32."""
     return _streaming_conv2d_grad_weight(_GC, x, grad_output, weight, stride, padding, dilation, groups, ste_threshold, want_bias, out,
+                                         out_bias, workspace)
+
+
+def grouped_mfma_grad_weight_work_floats(input_shape, weight_shape, stride=1, padding=0, dilation=1, groups: int = 1) -> int:
+    """fp32 elements of workspace ``grouped_mfma_conv2d_grad_weight`` needs (qt_gmconv2d_grad_weight_work_floats)."""
+    N, _C, H, W = (int(v) for v in input_shape)
+    G = int(groups)
+    return _streaming_grad_weight_work_floats(_GMW, (N, G, int(weight_shape[1]), int(weight_shape[0]) // max(G, 1), H, W,
+                                                     int(weight_shape[2]), int(weight_shape[3]), *_pairs(stride), *_pairs(padding),
+                                                     *_pairs(dilation)))
+
+
+def grouped_mfma_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, weight: torch.Tensor, stride=1, padding=0, dilation=1,
+                                    groups: int = 1, ste_threshold: float = 0.0, want_bias: bool = False,
+                                    out: Optional[torch.Tensor] = None, out_bias: Optional[torch.Tensor] = None,
+                                    workspace: Optional[torch.Tensor] = None):
+    """``grouped_conv2d_grad_weight`` for the shapes of ``grouped_mfma_applicable`` on the bf16 matrix cores
+    (qt_gmconv2d_grad_weight_f32), fp32 only: ``x`` and ``grad_output`` of ANY value are each split exactly into three bf16 terms
+    inside the launch and six of the nine cross products are kept (the dropped ones are below 2^-23 of the term), accumulated in
+    fp32 over the N Ho Wo output pixels — within (6 L + ``GM_WGRAD_MAX_SPLITS`` + 2) 2^-23 sum |go x| of the exact sum, THE exact sum
+    for integers of up to 16 bits whose sums of magnitudes stay below 2^24.  Same two launches, arguments and return; the
+    workspace is ``grouped_mfma_grad_weight_work_floats`` fp32 elements, 16-byte aligned."""
+    _require(x, "input")
+    _require(grad_output, "grad_output")
+    return _streaming_conv2d_grad_weight(_GMW, x, grad_output, weight, stride, padding, dilation, groups, ste_threshold, want_bias, out,
                                          out_bias, workspace)
 
 

@@ -8,15 +8,21 @@ call as the median and the range of the rounds, forward and forward + backward. 
 
 Routes:
   mfma   : ``_fused.GroupedMfmaConv2dFn`` called directly (csrc/gconv_mfma.hip; so the measurement does not depend on the switch
-           ``_fused.GROUPED_MFMA``, which is set FROM it);
+           ``_fused.GROUPED_MFMA``, which is set FROM it), with ``_fused.GROUPED_MFMA_WGRAD`` off: the streaming weight gradient;
+  mfma_wgrad : the same node with ``_fused.GROUPED_MFMA_WGRAD`` on (a step only: the forward is the same launch);
   loop   : ``_fused.grouped_quant_conv`` with ``binary_input = True``: what these layers run with the switch off;
   torch  : F.conv2d(x, sign(W), b, groups=G) through torch (MIOpen);
   stream : ``_fused.GroupedConv2dFn`` called directly (the streaming kernels of csrc/gconv.hip, not routed at this size).
 ``hbm_share`` = (4 (|x| + |y|) (x 3 for a step) / 8 TB/s) / the mfma median; ``mfma_share`` = (2 macs x 3 bf16 terms / 2.5 PFLOP/s)
 / the same.  ``grouped_mfma_by_rule`` is the value ``_fused.GROUPED_MFMA`` has to ship with: True iff on every row the route takes the mfma round
 range lies wholly below the loop's, forward and forward + backward.  The library and the streaming kernels are reported, not gated.
+``grouped_mfma_wgrad_by_rule`` is the value of ``_fused.GROUPED_MFMA_WGRAD``: True iff on every row the route takes the step's round
+range with the switch on lies wholly below the range with it off; ``step_beats_torch`` says row by row whether the step with the
+switch on lies wholly below the library's.  ``wgrad`` times the weight gradient alone (its two launches through ``ops``), streaming
+against matrix cores, with ``hbm_share`` = 4 (|x| + |go|) / 8 TB/s and ``mfma_share`` = 2 macs x 6 bf16 products / 2.5 PFLOP/s over
+the matrix-core median.
 
-    python tools/bench_grouped_mfma.py [--rounds 9] [--out profiles/grouped_mfma_bench_line.json]
+    python tools/bench_grouped_mfma.py [--rounds 9] [--out profiles/grouped_mfma_wgrad_bench_line.json]
 """
 import argparse
 import json
@@ -72,11 +78,17 @@ def child(index, rounds):
         go = torch.randn(want.shape, generator=g).to(dev)
         for r in set(forward) - {"loop", "torch"}:         # integer sums plus the bias: the same bits on every route of ours
             assert torch.equal(forward[r](x), want), r
-    if taken:
+    def switched(fn, on):                                   # the backward reads the switch when it runs
+        def run(*a):
+            _fused.GROUPED_MFMA_WGRAD = on
+            return fn(*a)
+        return run
+
+    for on, gwt in ((False, "qt_gconv2d_grad_weight_f32"), (True, "qt_gmconv2d_grad_weight_f32")) if taken else ():
         calls = dict(_lib.call_counts)
-        forward["mfma"](xg).backward(go)
+        switched(lambda: forward["mfma"](xg).backward(go), on)()
         used = {k_: v - calls.get(k_, 0) for k_, v in _lib.call_counts.items() if v != calls.get(k_, 0)}
-        assert used == {"qt_gmconv2d_f32": 1, "qt_gmconv2d_grad_input_f32": 1, "qt_gconv2d_grad_weight_f32": 1}, used
+        assert used == {"qt_gmconv2d_f32": 1, "qt_gmconv2d_grad_input_f32": 1, gwt: 1}, used
 
     def fwd(r):
         def run():
@@ -86,7 +98,7 @@ def child(index, rounds):
 
     def step(r):
         def run():
-            forward[r](xg).backward(go)
+            forward["mfma" if r == "mfma_wgrad" else r](xg).backward(go)
             xg.grad = None
             layer.zero_grad(set_to_none=True)
         return run
@@ -103,8 +115,15 @@ def child(index, rounds):
     nbytes, macs = {"fwd": x_b + y_b, "fwd_bwd": 3 * (x_b + y_b)}, {"fwd": m, "fwd_bwd": 3 * m}
     result = {"channels": C, "out_channels": Cout, "map": H, "stride": stride, "groups": G, "cin_g": C // G, "cout_g": Cout // G,
               "kernel": k, "bytes": nbytes, "macs": macs, "mfma_takes_it": taken}
-    for mode, make in (("fwd", fwd), ("fwd_bwd", step)):
-        fns = {r: make(r) for r in forward}
+    def wgrad(r):
+        op = ops.grouped_mfma_conv2d_grad_weight if r == "mfma" else ops.grouped_conv2d_grad_weight
+        return lambda: op(x, go, layer.weight, *args, ops.STE_THRESHOLD, True)
+
+    for mode, make in (("fwd", fwd), ("fwd_bwd", step), ("wgrad", wgrad)):
+        routes = [r for r in forward if mode != "wgrad" or r in ("stream", "mfma")]
+        fns = {r: switched(make(r), False) for r in routes}
+        if taken and mode == "fwd_bwd":
+            fns["mfma_wgrad"] = switched(make("mfma_wgrad"), True)
         steps = {r: (2 if r == "loop" else 10) for r in fns}
         for fn in fns.values():
             for _ in range(2):
@@ -118,9 +137,37 @@ def child(index, rounds):
         if not taken:
             continue
         t = result[mode]["mfma"]["median_us"] * 1e-6
+        if mode == "wgrad":                                 # both operands real: six bf16 products per MAC, 2 flops each
+            result[mode]["mfma"].update(hbm_share=round((x_b + y_b) / B.HBM_BYTES_PER_S / t, 3),
+                                        mfma_share=round(12 * m / BF16_FLOPS / t, 3))
+            continue
         result[mode]["mfma"].update(hbm_share=round(nbytes[mode] / B.HBM_BYTES_PER_S / t, 3),
                                     mfma_share=round(6 * macs[mode] / BF16_FLOPS / t, 3))
     print(json.dumps(result))
+
+
+def trace_steps(steps):
+    """For ``rocprofv3 --kernel-trace --stats -- python tools/bench_grouped_mfma.py --trace-steps 3``: every row the route takes, in
+    one process, ``steps`` training steps with the weight-gradient switch off and then on.  Kernel times instead of wall-time
+    differences: the rows differ in their grids, the two sides in the grad_weight kernels' names."""
+    import torch
+    from pytorch_quantize_impls_amd import ops
+    from pytorch_quantize_impls_amd.functions import _fused
+    from pytorch_quantize_impls_amd.layers import BinConv2d
+
+    dev = torch.device("cuda:0")
+    for C, H, stride, G, k, Cout in SHAPES:
+        layer = BinConv2d(C, Cout, k, stride=stride, padding=k // 2, groups=G).to(dev)
+        args = (layer.stride, layer.padding, layer.dilation, G)
+        xg = torch.where(torch.rand(B.BATCH, C, H, H) < 0.5, -1.0, 1.0).to(dev).requires_grad_(True)
+        if not ops.grouped_mfma_applicable(xg.shape, layer.weight.shape, *args):
+            continue
+        for on in (False, True):
+            _fused.GROUPED_MFMA_WGRAD = on
+            for _ in range(steps):
+                y = _fused.GroupedMfmaConv2dFn.apply(xg, layer.weight, layer.bias, "binary", None, ops.STE_THRESHOLD, args)
+                y.backward(torch.ones_like(y))
+        torch.cuda.synchronize()
 
 
 def shape_passes(s):
@@ -130,12 +177,22 @@ def shape_passes(s):
     return all(s[m]["mfma"]["max_us"] < s[m]["loop"]["min_us"] for m in ("fwd", "fwd_bwd"))
 
 
+def wgrad_passes(s, against="mfma"):
+    """The step with the matrix-core weight gradient lies wholly below the step of ``against``; None: the route declines the row."""
+    if not s["mfma_takes_it"]:
+        return None
+    return s["fwd_bwd"]["mfma_wgrad"]["max_us"] < s["fwd_bwd"][against]["min_us"]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
-    ap.add_argument("--out", default=os.path.join(B.ROOT, "profiles", "grouped_mfma_bench_line.json"))
+    ap.add_argument("--out", default=os.path.join(B.ROOT, "profiles", "grouped_mfma_wgrad_bench_line.json"))
     ap.add_argument("--child", type=int, default=None)
+    ap.add_argument("--trace-steps", type=int, default=None)
     a = ap.parse_args()
+    if a.trace_steps is not None:
+        return trace_steps(a.trace_steps)
     if a.child is not None:
         return child(a.child, a.rounds)
     shapes = []
@@ -150,7 +207,10 @@ def main():
     line = {"bench": "grouped_mfma", "batch": B.BATCH, "rounds": a.rounds, "dtype": "float32", "layout": "NCHW",
             "hbm_bytes_per_s": B.HBM_BYTES_PER_S, "bf16_flops": BF16_FLOPS, "shapes": shapes,
             "shape_passes_rule": [shape_passes(s) for s in shapes], "grouped_mfma_by_rule": all(shape_passes(s) is not False for s in shapes),
-            "grouped_mfma_shipped": bool(_fused.GROUPED_MFMA)}
+            "grouped_mfma_shipped": bool(_fused.GROUPED_MFMA),
+            "wgrad_passes_rule": [wgrad_passes(s) for s in shapes], "step_beats_torch": [wgrad_passes(s, "torch") for s in shapes],
+            "grouped_mfma_wgrad_by_rule": all(wgrad_passes(s) is not False for s in shapes),
+            "grouped_mfma_wgrad_shipped": bool(_fused.GROUPED_MFMA_WGRAD)}
     text = json.dumps(line)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh:
