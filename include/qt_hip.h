@@ -1460,6 +1460,44 @@ int qt_gmconv2d_grad_weight_f32(const float* go, const float* x, const float* w,
                                 int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w,
                                 float ste_threshold, qt_stream_t stream);
 
+/* Grouped convolution on bit planes, on the matrix cores: the forward above inside the fused sign chain, for groups of 16 or 32
+ * input channels whose input exists as the sign plane of a +-1 activation — the matrix-core sibling of qt_gconv2d_sign /
+ * qt_gconv2d_bits_f32 below ("Grouped convolution on bit planes"), whose formats, output forms and argument lists these two entries
+ * share.  One launch each on the caller's stream; no allocation, no synchronisation, no environment read;
+ * csrc/gconv_planes_mfma.hip, DESIGN.md "Grouped convs on bit planes, on the matrix cores".
+ *
+ * Input: x_plane, the NHWC sign plane over C = G cin_g channels (bit 1 <=> -1), ldx >= ops.packed_ld(G cin_g); w fp32
+ * [G cout_g, cin_g, kh, kw]; bias [G cout_g] or NULL.  Every tap is classified to -1 / 0 / +1 inside the launch as stated there
+ * (`kind`), the +-1 input and the taps are int8 operands of v_mfma_i32_16x16x64_i8, and
+ *   S = the exact integer sum over the taps inside the image, |S| <= cin_g kh kw <= 288;   y = fl((float)S + bias[co]) ((float)S
+ *   when bias is NULL): the bits qt_gconv2d_f32 / qt_gmconv2d_f32 store for the decoded image and an on-grid weight.
+ *   qt_gmconv2d_sign      the threshold bit [ fl(fl(y alpha[co]) + beta[co]) < 0 ] (a tie, -0.0, alpha == beta == 0 give 0) as
+ *                         sign_plane and / or nib_plane with a zero border of out_halo_* pixels: EVERY word of every plane is
+ *                         written — bits past G cout_g, pad words, border pixels — and nothing is read back.  Either plane may be
+ *                         null, not both.
+ *   qt_gmconv2d_bits_f32  y itself, fp32 [N, G cout_g, Ho, Wo] by its element strides (dense NCHW or channels-last).
+ *
+ * Limits (beyond them QT_ERR_UNSUPPORTED): cin_g in {16, 32} (a 24-bit field would straddle plane words); cout_g in {16, 32, 48};
+ * a 1 x 1 or 3 x 3 kernel; stride 1 or 2, equal on both axes; dilation 1; padding 0 or 1 per axis; any G >= 1 with G cout_g <=
+ * QT_DW_MAX_CHANNELS; out_halo_* <= 64; fewer than 2^31 pixel rows in every plane and fewer than 2^31 elements in y.  The grid is
+ * one-dimensional, at most max(1024, G / 4 + 1) workgroups.
+ *
+ * Validated before anything is enqueued, in this order; a non-zero status means nothing was launched:
+ *   1. a negative halo, negative sizes, cin_g or cout_g < 1, a kernel / stride / dilation below 1, negative padding:
+ *      QT_ERR_INVALID_ARG; kh kw > QT_DW_MAX_TAPS: QT_ERR_UNSUPPORTED.
+ *   2. N, G, H or W zero: QT_OK whatever the pointers are, nothing is written.
+ *   3. the limits: QT_ERR_UNSUPPORTED; a kernel that does not fit the padded image: QT_ERR_INVALID_ARG.
+ *   4. an unknown `kind`, a null tensor (bias may be null), no output plane, a null alpha or beta, strides that are no dense
+ *      layout, ldx / ldb / ldn below the bounds: QT_ERR_INVALID_ARG; then a pointer that is not 4-byte aligned, ldn % 4 != 0 or a
+ *      nib_plane that is not 16-byte aligned: QT_ERR_ALIGNMENT. */
+int qt_gmconv2d_sign(const uint32_t* x_plane, int64_t ldx, const float* w, const float* bias, const float* alpha, const float* beta,
+                     uint32_t* sign_plane, int64_t ldb, uint32_t* nib_plane, int64_t ldn, int64_t out_halo_h, int64_t out_halo_w,
+                     int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw,
+                     int ph, int pw, int dh, int dw, int kind, qt_stream_t stream);
+int qt_gmconv2d_bits_f32(const uint32_t* x_plane, int64_t ldx, const float* w, const float* bias, float* y, int64_t N, int64_t G,
+                         int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                         int dw, int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, int kind, qt_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Depthwise and grouped convolution on half-precision operands: the six entries above for bf16 / fp16 models
  * (model.bfloat16(), model.half(), fp32 models under torch.autocast), named by the "_h" convention of "Half-precision operands".

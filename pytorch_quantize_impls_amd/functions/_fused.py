@@ -912,6 +912,21 @@ def _grouped_planes_admission(layer, act, what: str) -> None:
         raise ValueError(f"{what} needs an eval-mode weight on the quantiser's grid")
 
 
+def _grouped_mfma_planes_window(layer, shape) -> bool:
+    """``layer`` on a +-1 activation of ``shape`` is a grouped conv the matrix-core plane kernel takes: at least
+    ``GROUPED_MFMA_MIN_GROUPS`` groups of 16 or 32 input channels inside ``ops.grouped_mfma_planes_applicable``."""
+    return (layer.padding_mode == "zeros" and len(shape) == 4 and layer.groups >= GROUPED_MFMA_MIN_GROUPS
+            and ops.grouped_mfma_planes_applicable(shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups))
+
+
+def _grouped_mfma_planes_admission(layer, act, what: str) -> None:
+    if not _grouped_mfma_planes_window(layer, act.shape):
+        raise ValueError(f"{what} needs at least {GROUPED_MFMA_MIN_GROUPS} groups of 16 or 32 input channels, numeric zero "
+                         "padding and a shape inside the kernel's window (ops.grouped_mfma_planes_applicable)")
+    if not layer._eval_on_grid():
+        raise ValueError(f"{what} needs an eval-mode weight on the quantiser's grid")
+
+
 def _grouped_codes_admission(layer, act, what: str) -> None:
     cin_g = int(layer.weight.shape[1])
     if (layer.padding_mode != "zeros" or len(act.shape) != 4 or layer.groups < GROUPED_MIN_GROUPS or not 2 <= cin_g <= GROUPED_MAX_CIN_G
@@ -953,8 +968,9 @@ def codes_depthwise_conv2d(layer, act):
 def packed_grouped_conv2d(layer, act):
     """Eval-mode BinConv2d / TerConv2d with ``1 < groups < in_channels`` on a PackedActivation (NHWC bit planes): the fp32
     [N, G * cout_g, Ho, Wo] result in NCHW storage, bias added, from one launch on the planes (ops.grouped_conv2d_from_bits) — what a
-    deferred grouped conv whose input exists only as planes materialises to.  The stored eval image is classified by its sign."""
-    return _packed_streaming_conv2d(_GROUPED, layer, act)
+    deferred grouped conv whose input exists only as planes materialises to.  The stored eval image is classified by its sign.
+    Groups of 16 or 32 channels inside the matrix-core plane window take ops.grouped_mfma_conv2d_from_bits (qt_gmconv2d_bits_f32)."""
+    return _packed_streaming_conv2d(_GROUPED_MFMA_PLANES if _grouped_mfma_planes_window(layer, act.shape) else _GROUPED, layer, act)
 
 
 def codes_grouped_conv2d(layer, act):
@@ -2203,8 +2219,10 @@ GROUPED_MFMA_WGRAD = False
 #: smallest benchmarked shape (L = 12544) has been measured.
 GROUPED_MFMA_WGRAD_MIN_L = 1024
 
-_GROUPED_MFMA = _StreamingFamily(ops._GM, None, None)          # no plane or code form: the deferred chains decline these layers
+_GROUPED_MFMA = _StreamingFamily(ops._GM, None, None)          # the fp32 tensors' form; no code form
 _GROUPED_MFMA_WGRAD = _StreamingFamily(ops._GMW, None, None)
+#: the same layers on the bit planes of a +-1 activation (csrc/gconv_planes_mfma.hip): the sign chain's form of them
+_GROUPED_MFMA_PLANES = _StreamingFamily(ops._GMP, _grouped_mfma_planes_admission, None)
 
 
 def grouped_mfma_wgrad_route(grad_output_shape) -> bool:

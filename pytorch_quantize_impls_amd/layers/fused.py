@@ -981,6 +981,29 @@ class FusedGroupedBnSign(_FusedStreamingBnSign):
         raise TypeError("FusedGroupedBnSign reads the bit planes of a PackedActivation only (the un-fused layer takes fp32 tensors)")
 
 
+class FusedGroupedMfmaBnSign(FusedGroupedBnSign):
+    """``FusedGroupedBnSign`` for at least ``_fused.GROUPED_MFMA_MIN_GROUPS`` groups of 16 or 32 input channels (16, 32 or 48 output
+    channels each; ``ops.grouped_mfma_planes_applicable``): ONE launch on the int8 matrix cores (qt_gmconv2d_sign) reads the bit
+    planes of a PackedActivation — a group's tap is an aligned 16- / 32-bit field of a plane row, expanded to +-1 bytes in
+    registers — and writes the threshold bits as bit planes or the consuming conv's nibble pixel plane.  Fold cache, ``refold()``,
+    ``out_nib_halo``, pooling on bits and the ValueError / TypeError rules are the base class's."""
+    _applicable, _conv2d_sign = staticmethod(ops.grouped_mfma_planes_applicable), staticmethod(ops.grouped_mfma_conv2d_sign)
+    _outside = ("a grouped conv outside the window of the matrix-core plane kernel (ops.grouped_mfma_planes_applicable: 16 or 32 "
+                "input channels per group)")
+    _not_taken = "not a grouped conv the matrix-core plane kernel takes"
+
+    @staticmethod
+    def _admit(conv):
+        from ..functions import _fused
+        if conv.groups < _fused.GROUPED_MFMA_MIN_GROUPS or conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+            raise ValueError(f"only zero-padded convs with numeric padding and at least {_fused.GROUPED_MFMA_MIN_GROUPS} groups can be "
+                             "fused on the matrix cores")
+
+    @staticmethod
+    def _tensor_input(x):
+        raise TypeError("FusedGroupedMfmaBnSign reads the bit planes of a PackedActivation only (the un-fused layer takes fp32 tensors)")
+
+
 class FusedConvBnAddSign(torch.nn.Module):
     """The residual block of a binarised ResNet (Bi-Real-Net style), eval only:
 
@@ -1310,7 +1333,7 @@ def fuse_sequential_training(seq: torch.nn.Sequential) -> torch.nn.Sequential:
 
 
 #: the fused modules whose PackedActivation carries bit planes (or, linked, the consumer's nibble operand)
-_PLANE_PRODUCERS = (FusedConvPoolBnSign, PackedMaxPool, FusedDepthwiseBnSign, FusedGroupedBnSign)
+_PLANE_PRODUCERS = (FusedConvPoolBnSign, PackedMaxPool, FusedDepthwiseBnSign, FusedGroupedBnSign)     # subclasses included
 
 
 def _is_det_binary_connect(m):
@@ -1324,7 +1347,7 @@ def fuse_sequential(seq: torch.nn.Sequential, fuse_conv: bool = False, packed_po
     threshold bits, no fp32 activation is written at all; a depthwise one, ``groups == in_channels``, becomes a
     FusedDepthwiseBnSign; a grouped one that ``FusedGroupedBnSign`` takes becomes that block when the module emitted just before
     it produces bit planes — FusedConvPoolBnSign, PackedMaxPool, FusedDepthwiseBnSign, FusedGroupedBnSign — and stays the
-    un-fused layer otherwise).  With ``packed_pool`` a MaxPool2d that directly follows a
+    un-fused layer otherwise; with 16 or 32 input channels per group it is a ``FusedGroupedMfmaBnSign``).  With ``packed_pool`` a MaxPool2d that directly follows a
     fused block (pool AFTER the sign, VGG style) becomes a PackedMaxPool on the bit planes.  ``fold``: the BatchNorm
     fold of the fused blocks ("reference" | "device", module docstring; default DEFAULT_FOLD)."""
     from .binary_layers import BinConv2d
@@ -1354,7 +1377,9 @@ def fuse_sequential(seq: torch.nn.Sequential, fuse_conv: bool = False, packed_po
                         out.append(FusedDepthwiseBnSign(conv, bn, pool, fold=fold))
                     elif (conv is not None and 1 < conv.groups < conv.in_channels and not isinstance(conv, XNORConv2d)
                           and out and isinstance(out[-1], _PLANE_PRODUCERS) and not getattr(out[-1], "flatten_hwc", False)):
-                        out.append(FusedGroupedBnSign(conv, bn, pool, fold=fold))       # reads planes only: never at the head
+                        # reads planes only: never at the head; 16 / 32 channels per group on the matrix cores
+                        wide = int(conv.weight.shape[1]) in ops.GMP_CIN_G
+                        out.append((FusedGroupedMfmaBnSign if wide else FusedGroupedBnSign)(conv, bn, pool, fold=fold))
                     else:
                         out.append(FusedConvPoolBnSign(conv, bn, pool, fold=fold) if conv is not None
                                    else FusedPoolBnSign(bn, pool, pre_relu=pre_relu, fold=fold))
@@ -1382,7 +1407,7 @@ def link_nib_planes(mods) -> None:
     """Where a fused conv block directly consumes the output of another fused block (or of a PackedMaxPool), let the
     producer write the consumer's operand — the fp4 nibble pixel plane with the consumer's padding as a zero border —
     instead of bit planes (saves the consumer's qt_bits_to_nib_pad pass: 10 % of the fused VGG-16 forward).  A depthwise block
-    or a grouped block (FusedDepthwiseBnSign, FusedGroupedBnSign) is such a producer; as a consumer it reads bit planes, so its
+    or a grouped block (FusedDepthwiseBnSign, FusedGroupedBnSign, FusedGroupedMfmaBnSign) is such a producer; as a consumer it reads bit planes, so its
     producer stays on them."""
     from ..functions import _fused
     for a, b in zip(mods, mods[1:]):

@@ -53,6 +53,12 @@ its producer's bit planes and runs as ``layers.fused.FusedGroupedBnSign`` — on
 layer's planes or nibble operand; a deferred grouped conv on planes that must materialise computes its fp32 value from the planes
 (``_fused.packed_grouped_conv2d``).  On an fp32 tensor — at the head of a chain — a grouped layer never defers.
 
+Grouped BinConv2d / TerConv2d with at least ``_fused.GROUPED_MFMA_MIN_GROUPS`` groups of 16 or 32 input channels (16, 32 or 48
+output channels each, 1 x 1 or 3 x 3, ``ops.grouped_mfma_planes_applicable``) join it the same way behind ``DEFER_GROUPED_MFMA``
+(``grouped_mfma_deferred()``): the layer runs as ``layers.fused.FusedGroupedMfmaBnSign`` — one launch on the int8 matrix cores
+(qt_gmconv2d_sign) — and materialises, where it must, from the planes (qt_gmconv2d_bits_f32).  24 channels per group, other
+output widths and a layer at the head of a chain keep qt_gmconv2d_f32 on the materialised fp32 activation.
+
 Grouped DorefaConv2d with at least ``_fused.GROUPED_MIN_GROUPS`` groups of 2 ... ``_fused.GROUPED_MAX_CIN_G`` input channels (any
 weight bit_width) joins the DoReFa code chain as its depthwise sibling does (``DEFER_GROUPED_CODES``, together with ``DEFER_CODES``;
 ``grouped_deferred()`` sets it with ``DEFER_GROUPED``): the layer takes its producer's int8 code plane — whatever halo it has — and
@@ -72,7 +78,7 @@ a sign chain returns NotImplemented as without this mechanism and the chain mate
 chain" has the grammar, the exactness argument and what was measured).
 
 Nothing is deferred in training mode, with autograd enabled, on CPU tensors, for non-fp32 dtypes, grouped convs other than
-those depthwise and few-channel ones or non-zero padding modes.  ``lazy.ENABLED = False`` (or the ``eager()`` context manager) switches the mechanism off;
+those depthwise, few-channel and 16- / 32-channel ones or non-zero padding modes.  ``lazy.ENABLED = False`` (or the ``eager()`` context manager) switches the mechanism off;
 ``lazy.STATS`` counts what happened (tests assert on it).
 """
 from __future__ import annotations
@@ -137,6 +143,15 @@ DEFER_GROUPED = True
 #: call runs exactly as without this mechanism: the grouped layer computes fp32 from the expanded image and the chain in front of
 #: it materialises (``grouped_deferred()`` switches it for a block).
 DEFER_GROUPED_CODES = True
+#: grouped BinConv2d / TerConv2d with ``groups >= _fused.GROUPED_MFMA_MIN_GROUPS`` and 16 or 32 input channels per group (shapes
+#: ``ops.grouped_mfma_planes_applicable`` takes) join the sign chain when their input is a deferred +-1 activation: the layer asks
+#: its producer for bit planes and runs as ``layers.fused.FusedGroupedMfmaBnSign`` — one launch on the int8 matrix cores
+#: (qt_gmconv2d_sign) from planes to the next layer's planes; on an fp32 tensor the layer keeps qt_gmconv2d_f32.  Set by the
+#: shipping rule of DESIGN.md "Grouped convs on bit planes, on the matrix cores": on every measured row the deferred triple's round
+#: range lies below the eager one's (3.8x - 7.0x at 3 x 3, 2.7x at 1 x 1; profiles/grouped_mfma_chain_bench_line.json) and the
+#: existing suites pass with it on.  False = every call runs exactly as without this mechanism (``grouped_mfma_deferred()`` switches
+#: it for a block).
+DEFER_GROUPED_MFMA = True
 #: ``bn(conv(...)) + shortcut`` on a BinConv2d / TerConv2d chain (the residual block of a binarised ResNet) is recorded and runs as
 #: ``layers.fused.FusedConvBnAddSign``: conv to fp32, then one launch (qt_bn_add_sign_f32) for BatchNorm (device arithmetic, verified on
 #: a probe) + shortcut + [Hardtanh] + sign that writes the next conv's operand and the fp32 sum — the next block's shortcut (DESIGN.md
@@ -231,6 +246,18 @@ def grouped_deferred(on: bool = True):
         yield
     finally:
         DEFER_GROUPED, DEFER_GROUPED_CODES = prev, prev_codes
+
+
+@contextlib.contextmanager
+def grouped_mfma_deferred(on: bool = True):
+    """Defer grouped sign convs with 16 or 32 input channels per group (``DEFER_GROUPED_MFMA``) inside the block; process-wide,
+    restores the previous setting."""
+    global DEFER_GROUPED_MFMA
+    prev, DEFER_GROUPED_MFMA = DEFER_GROUPED_MFMA, bool(on)
+    try:
+        yield
+    finally:
+        DEFER_GROUPED_MFMA = prev
 
 
 @contextlib.contextmanager
@@ -663,7 +690,8 @@ def _fused_block(layer, bn, pool, flatten: bool, halo):
     if blk is None:
         pm = torch.nn.MaxPool2d(pool[0], pool[1]) if pool is not None else None
         make = (fused.FusedConvPoolBnSign if layer.groups == 1 else
-                fused.FusedDepthwiseBnSign if layer.groups == layer.in_channels else fused.FusedGroupedBnSign)
+                fused.FusedDepthwiseBnSign if layer.groups == layer.in_channels else
+                fused.FusedGroupedMfmaBnSign if int(layer.weight.shape[1]) in ops.GMP_CIN_G else fused.FusedGroupedBnSign)
         blk = make(layer, _BnView(rm, rv, w, b, eps), pm, flatten_hwc=flatten, fold="device")
         blk.out_nib_halo = halo
         per[key] = blk
@@ -1273,8 +1301,8 @@ def _conv_can_defer(layer, input) -> bool:
     w = layer.weight
     if layer.groups != 1:
         # depthwise (DEFER_DEPTHWISE) inside the limits of the depthwise kernels, or a few channels per group (DEFER_GROUPED) on the
-        # planes of a +-1 activation — never on an fp32 tensor — inside those of the grouped plane kernel; every other grouped
-        # conv runs eagerly
+        # planes of a +-1 activation — never on an fp32 tensor — inside those of the grouped plane kernel, or 16 / 32 channels per
+        # group (DEFER_GROUPED_MFMA) inside the window of the matrix-core plane kernel; every other grouped conv runs eagerly
         if getattr(layer, "kind", None) not in ("binary", "ternary"):
             return False
         shape = tuple(getattr(input, "shape", ()))
@@ -1284,9 +1312,11 @@ def _conv_can_defer(layer, input) -> bool:
                 return False
         else:
             from .functions import _fused
-            if not (DEFER_GROUPED and layer.groups >= _fused.GROUPED_MIN_GROUPS and isinstance(input, packed.PackedActivation)
-                    and (isinstance(input, _ShapeOnly) or input.planes is not None)
-                    and ops.grouped_planes_applicable(shape, tuple(w.shape), layer.stride, layer.padding, layer.dilation, layer.groups)):
+            if not (isinstance(input, packed.PackedActivation) and (isinstance(input, _ShapeOnly) or input.planes is not None)):
+                return False
+            if not ((DEFER_GROUPED and layer.groups >= _fused.GROUPED_MIN_GROUPS
+                     and ops.grouped_planes_applicable(shape, tuple(w.shape), layer.stride, layer.padding, layer.dilation, layer.groups))
+                    or (DEFER_GROUPED_MFMA and _fused._grouped_mfma_planes_window(layer, shape))):
                 return False
     if not w.is_cuda or w.dtype != torch.float32:
         return False

@@ -4184,6 +4184,20 @@ def grouped_mfma_applicable(x_shape, w_shape, stride, padding, dilation, groups)
             and sh == sw and sh <= 2 and (dh, dw) == (1, 1) and max(ph, pw) <= 1)
 
 
+#: input channels per group the matrix-core grouped PLANE kernel takes (csrc/gconv_planes_mfma.hip): a 24-bit field would straddle
+#: plane words; and its output channels per group
+GMP_CIN_G = (16, 32)
+GMP_COUT_G = (16, 32, 48)
+
+
+def grouped_mfma_planes_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
+    """``grouped_mfma_applicable`` with cin_g in ``GMP_CIN_G`` and fewer than 2^31 pixel rows: the grouped convs that run on the bit
+    planes of a +-1 activation on the int8 matrix cores (``grouped_mfma_conv2d_sign`` / ``grouped_mfma_conv2d_from_bits``).
+    Disjoint from ``grouped_planes_applicable`` (2, 4 or 8 channels per group).  A pure function of the shapes."""
+    return (grouped_mfma_applicable(x_shape, w_shape, stride, padding, dilation, groups) and int(w_shape[1]) in GMP_CIN_G
+            and int(w_shape[0]) // int(groups) in GMP_COUT_G)
+
+
 def _dw_channels_last(t: torch.Tensor) -> bool:
     return t.is_contiguous(memory_format=torch.channels_last) and not t.is_contiguous()
 
@@ -4287,6 +4301,16 @@ def _gm_geometry(x_shape, weight, stride, padding, dilation, groups, half: bool 
     return _gc_geometry(x_shape, weight, stride, padding, dilation, groups)
 
 
+def _gmp_geometry(x_shape, weight, stride, padding, dilation, groups):
+    """``_gc_geometry`` inside the window of ``grouped_mfma_planes_applicable``."""
+    _require(weight, "weight")
+    if (len(x_shape) == 4 and weight.dim() == 4 and min(map(int, x_shape)) > 0
+            and not grouped_mfma_planes_applicable(x_shape, weight.shape, stride, padding, dilation, groups)):
+        raise ValueError(f"not a grouped conv the matrix-core plane kernel takes: input {tuple(x_shape)}, weight {tuple(weight.shape)}, "
+                         f"groups {groups}, stride {stride}, padding {padding}, dilation {dilation}")
+    return _gc_geometry(x_shape, weight, stride, padding, dilation, groups)
+
+
 class _Streaming(NamedTuple):
     """One family of streaming convs, as the shared bodies below see it."""
     entry: dict                 # suffix -> name of the entry point ("f32" -> "qt_dwconv2d_f32"), spelled once, not per call
@@ -4314,6 +4338,10 @@ _GM = _Streaming({"f32": "qt_gmconv2d_f32", "grad_input_f32": "qt_gmconv2d_grad_
 #: the same family with the weight gradient on the matrix cores too (qt_gmconv2d_grad_weight_f32: six bf16 products per term)
 _GMW = _GM._replace(entry={**_GM.entry, "grad_weight_f32": "qt_gmconv2d_grad_weight_f32",
                            "grad_weight_work_floats": "qt_gmconv2d_grad_weight_work_floats"})
+#: 16 or 32 input channels per group on the bit planes of a +-1 activation, on the int8 matrix cores (csrc/gconv_planes_mfma.hip):
+#: the two plane entries alone
+_GMP = _Streaming({"sign": "qt_gmconv2d_sign", "bits_f32": "qt_gmconv2d_bits_f32"}, "matrix-core grouped", "G * cout_g",
+                  _gm_geometry, _gmp_geometry, False)
 #: most splits per group of that entry: the S_max of its error bound
 GM_WGRAD_MAX_SPLITS = _lib.DEFINES["QT_GM_WGRAD_MAX_SPLITS"]
 
@@ -4474,6 +4502,18 @@ def grouped_conv2d_sign(planes: BitPlanes, weight: torch.Tensor, bias: Optional[
                                   with_bits, out_sign, out_nib)
 
 
+def grouped_mfma_conv2d_sign(planes: BitPlanes, weight: torch.Tensor, bias: Optional[torch.Tensor], alpha: torch.Tensor,
+                             beta: torch.Tensor, stride=1, padding=0, dilation=1, groups: int = 1, kind: str = "raw", shape=None,
+                             out_halo=None, with_bits: bool = False, out_sign: Optional[torch.Tensor] = None,
+                             out_nib: Optional[torch.Tensor] = None):
+    """``grouped_conv2d_sign`` for 16 or 32 input channels per group (``grouped_mfma_planes_applicable``), one launch on the int8
+    matrix cores (qt_gmconv2d_sign): a group's tap is an aligned 16- / 32-bit field of the sign plane, expanded to +-1 bytes in
+    registers; the classified taps (``kind``) are the other operand; the sums are exact integers.  Arguments, returns and the
+    ``out_*`` tensors as ``grouped_conv2d_sign``."""
+    return _streaming_conv2d_sign(_GMP, planes, weight, bias, alpha, beta, stride, padding, dilation, groups, kind, shape, out_halo,
+                                  with_bits, out_sign, out_nib)
+
+
 def _streaming_result(out: Optional[torch.Tensor], y_shape, channels_last: bool, w: torch.Tensor) -> torch.Tensor:
     """The fp32 result of an entry that reads a plane: ``out`` checked, or a new tensor in NCHW or ``channels_last`` storage."""
     if out is not None:
@@ -4515,6 +4555,15 @@ def grouped_conv2d_from_bits(planes: BitPlanes, shape, weight: torch.Tensor, bia
     (N, G * cin_g, H, W)), cin_g in {2, 4, 8}: the fp32 result — for an on-grid weight bit for bit that of the fp32 +-1 image — in
     NCHW or ``channels_last`` storage or written into ``out`` (qt_gconv2d_bits_f32, one launch)."""
     return _streaming_conv2d_from_bits(_GC, planes, shape, weight, bias, stride, padding, dilation, groups, kind, channels_last, out)
+
+
+def grouped_mfma_conv2d_from_bits(planes: BitPlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1,
+                                  padding=0, dilation=1, groups: int = 1, kind: str = "raw", channels_last: bool = False,
+                                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``grouped_conv2d_from_bits`` for 16 or 32 input channels per group (``grouped_mfma_planes_applicable``): the fp32 result —
+    for an on-grid weight bit for bit that of ``grouped_mfma_conv2d`` on the fp32 +-1 image — from one launch on the planes
+    (qt_gmconv2d_bits_f32)."""
+    return _streaming_conv2d_from_bits(_GMP, planes, shape, weight, bias, stride, padding, dilation, groups, kind, channels_last, out)
 
 
 def _dw_code_input(codes: CodePlanes, shape, in_halo):

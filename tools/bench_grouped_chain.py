@@ -48,6 +48,15 @@ the count of tools/bench_depthwise_chain.py:
   deferred : |x| + |y| (one code in, one code out)
 The line goes to profiles/grouped_codes_chain_bench_line.json, the table between the ``grouped-codes-chain-table`` markers;
 ``--kernel-times`` then times gc_codes_kernel.
+
+``--family mfma`` measures the sign triple around the grouped layers with 16 or 32 input channels per group (the layers of
+profiles/grouped_mfma_bench_line.json inside ``ops.grouped_mfma_planes_applicable``), same protocol:
+  deferred : ``lazy.grouped_mfma_deferred(True)`` — ONE launch on the int8 matrix cores (qt_gmconv2d_sign) from the first pointwise
+             chain's bit planes to the second pointwise conv's operand;
+  eager    : ``lazy.grouped_mfma_deferred(False)`` — the path of the commit before the switch: the first chain materialises fp32,
+             qt_gmconv2d_f32 reads it, three library passes and a pack follow.
+``bytes`` as for the sign family.  The line goes to profiles/grouped_mfma_chain_bench_line.json, the table between the
+``grouped-mfma-chain-table`` markers; ``--kernel-times`` then times gp_kernel.
 """
 import argparse
 import json
@@ -69,13 +78,22 @@ CHILD_LIMIT_S = 300
 STEPS = 20
 MARK = "grouped-chain-table"
 KERNEL = "gc_planes_kernel"
-FAMILIES = {"sign": {"mark": MARK, "out": "grouped_chain_bench_line.json", "kernel": KERNEL},
-            "dorefa": {"mark": "grouped-codes-chain-table", "out": "grouped_codes_chain_bench_line.json", "kernel": "gc_codes_kernel"}}
+#: (channels, map, stride, groups, kernel, output channels): the grouped layers of tools/bench_grouped_mfma.py with 16 or 32 input
+#: channels per group.  Its 768 -> 1536 row has 24 per group, which the plane window declines (both sides would run the same
+#: launches); 1024 -> 1536 stands in for it: 32 -> 48 channels per group, the kernel's largest form
+SHAPES_MFMA = [(512, 14, 1, 32, 3, 512), (1024, 7, 1, 32, 3, 1024), (512, 28, 2, 32, 3, 512), (256, 14, 1, 16, 1, 256),
+               (1024, 14, 1, 32, 3, 1536)]
+FAMILIES = {"sign": {"mark": MARK, "out": "grouped_chain_bench_line.json", "kernel": KERNEL, "shapes": SHAPES,
+                     "entries": ("qt_gconv2d_sign", "qt_gconv2d_f32"), "switch": "grouped_deferred"},
+            "dorefa": {"mark": "grouped-codes-chain-table", "out": "grouped_codes_chain_bench_line.json", "kernel": "gc_codes_kernel",
+                       "shapes": SHAPES},
+            "mfma": {"mark": "grouped-mfma-chain-table", "out": "grouped_mfma_chain_bench_line.json", "kernel": "gp_kernel",
+                     "shapes": SHAPES_MFMA, "entries": ("qt_gmconv2d_sign", "qt_gmconv2d_f32"), "switch": "grouped_mfma_deferred"}}
 
 
-def algorithmic_bytes(C, H, stride, k):
+def algorithmic_bytes(C, H, stride, k, Co=None):
     Ho = (H + 2 * (k // 2) - k) // stride + 1
-    x, y = BATCH * C * H * H, BATCH * C * Ho * Ho
+    x, y = BATCH * C * H * H, BATCH * (Co or C) * Ho * Ho
     return {"eager": 32 * x + 32 * y, "deferred": x // 4 + y // 2}
 
 
@@ -95,7 +113,7 @@ def kernel_time_us(index, workdir, family="sign"):
                         sys.executable, os.path.abspath(__file__), "--child", str(index), "--rounds", "1", "--family", family],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=CHILD_LIMIT_S)
     if p.returncode != 0:
-        raise SystemExit(f"shape {SHAPES[index]}: the profiled process ended with status {p.returncode}; nothing more was started")
+        raise SystemExit(f"shape {FAMILIES[family]['shapes'][index]}: the profiled process ended with status {p.returncode}; nothing more was started")
     path = sorted(glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True))[0]
     with open(path) as fh:
         rows = [r for r in csv.DictReader(fh) if FAMILIES[family]["kernel"] in r["Name"]]
@@ -103,14 +121,18 @@ def kernel_time_us(index, workdir, family="sign"):
     return round(sum(float(r["TotalDurationNs"]) for r in rows) / max(calls, 1) / 1e3, 1), calls
 
 
-def child(index, rounds):
+def child(index, rounds, family="sign"):
     import torch
     import torch.nn as nn
     from pytorch_quantize_impls_amd import _lib, lazy
     from pytorch_quantize_impls_amd.functions import BinaryConnect
     from pytorch_quantize_impls_amd.layers import BinConv2d
 
-    C, H, stride, G, k = SHAPES[index]
+    fam = FAMILIES[family]
+    C, H, stride, G, k = fam["shapes"][index][:5]
+    Co = (fam["shapes"][index] + (C,))[5]          # output channels of the grouped layer: C unless the shape names them
+    sign_entry, eager_entry = fam["entries"]
+    switch = getattr(lazy, fam["switch"])
     dev = torch.device("cuda:0")
     torch.manual_seed(index)
     g = torch.Generator().manual_seed(index)
@@ -125,14 +147,14 @@ def child(index, rounds):
         bn.bias.data.copy_(torch.randn(c, generator=g) * 0.5)
         return [bn, nn.Hardtanh(inplace=True), BinaryConnect()]
 
-    triple = nn.Sequential(BinConv2d(C, C, 1), *run(C), BinConv2d(C, C, k, stride=stride, padding=k // 2, groups=G), *run(C),
-                           BinConv2d(C, C, 1), *run(C)).to(dev).eval()
+    triple = nn.Sequential(BinConv2d(C, C, 1), *run(C), BinConv2d(C, Co, k, stride=stride, padding=k // 2, groups=G), *run(Co),
+                           BinConv2d(Co, Co, 1), *run(Co)).to(dev).eval()
     for i in (0, 4, 8):
         triple[i].binary_input = True          # +-1 by construction: no side stops to ask the device
     x = torch.where(torch.rand(BATCH, C, H, H, generator=g) < 0.5, -1.0, 1.0).to(dev)
 
     def forward(on):
-        with torch.no_grad(), lazy.grouped_deferred(on):
+        with torch.no_grad(), switch(on):
             out = triple(x)
             act = out._qt.force(None)          # the planes the next binarised layer would ask for
             assert act is not None and act.planes is not None
@@ -146,8 +168,8 @@ def child(index, rounds):
     b = sides["eager"]()
     used_off = {k_: v - calls.get(k_, 0) for k_, v in _lib.call_counts.items() if v != calls.get(k_, 0)}
     assert torch.equal(a, b), "the two sides disagree"
-    assert used_on.get("qt_gconv2d_sign") == 1 and "qt_gconv2d_f32" not in used_on, used_on
-    assert used_off.get("qt_gconv2d_f32") == 1 and "qt_gconv2d_sign" not in used_off, used_off
+    assert used_on.get(sign_entry) == 1 and eager_entry not in used_on, used_on
+    assert used_off.get(eager_entry) == 1 and sign_entry not in used_off, used_off
 
     def run_us(fn):
         torch.cuda.synchronize()
@@ -164,8 +186,8 @@ def child(index, rounds):
     for _ in range(rounds):
         for s, fn in sides.items():
             samples[s].append(run_us(fn))
-    nbytes = algorithmic_bytes(C, H, stride, k)
-    result = {"channels": C, "map": H, "stride": stride, "groups": G, "kernel": k, "bytes": nbytes,
+    nbytes = algorithmic_bytes(C, H, stride, k, Co)
+    result = {"channels": C, "out_channels": Co, "map": H, "stride": stride, "groups": G, "kernel": k, "bytes": nbytes,
               "launches": {"deferred": used_on, "eager": used_off}}
     for s, v in samples.items():
         med = sorted(v)[len(v) // 2]
@@ -259,7 +281,8 @@ def table(shapes, kernel_name="grouped plane kernel"):
     for s in shapes:
         e, d = s["eager"], s["deferred"]
         ok = "yes" if s["deferred_range_below_eager"] else "**no**"
-        name = f"{s['channels']} x {s['map']}², g{s['groups']}, {s['kernel']}x{s['kernel']}, s{s['stride']}"
+        wide = f" → {s['out_channels']}" if s.get("out_channels", s["channels"]) != s["channels"] else ""
+        name = f"{s['channels']}{wide} x {s['map']}², g{s['groups']}, {s['kernel']}x{s['kernel']}, s{s['stride']}"
         rows.append(f"| {name if s['deferred_range_below_eager'] else '**' + name + '**'} | {e['median_us']} ({e['min_us']}–{e['max_us']}) | "
                     f"{d['median_us']} ({d['min_us']}–{d['max_us']}) | {s['bytes']['eager'] / 1e6:.1f}, {e['hbm_share']} | "
                     f"{s['bytes']['deferred'] / 1e6:.1f}, {d['hbm_share']} | {ok} |" + (f" {s['kernel_us']} |" if own else ""))
@@ -281,7 +304,7 @@ def write_docs(text, mark=MARK):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
-    ap.add_argument("--family", choices=sorted(FAMILIES), default="sign", help="sign: BinConv2d triple (default); dorefa: DorefaConv2d triple")
+    ap.add_argument("--family", choices=sorted(FAMILIES), default="sign", help="sign: BinConv2d triple (default); dorefa: DorefaConv2d triple; mfma: BinConv2d triple, 16 / 32 channels per group")
     ap.add_argument("--out", default=None, help="default: profiles/grouped_chain_bench_line.json (sign), "
                                                 "profiles/grouped_codes_chain_bench_line.json (dorefa)")
     ap.add_argument("--kernel-times", action="store_true", help="one more rocprofv3 --kernel-trace --stats pass per shape")
@@ -291,11 +314,11 @@ def main():
     a = ap.parse_args()
     fam = FAMILIES[a.family]
     dorefa = a.family == "dorefa"
-    kernel_name = "grouped code kernel" if dorefa else "grouped plane kernel"
+    kernel_name = "grouped code kernel" if dorefa else ("matrix-core plane kernel" if a.family == "mfma" else "grouped plane kernel")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", fam["out"])
     if a.child is not None:
-        return child_dorefa(a.child, a.rounds) if dorefa else child(a.child, a.rounds)
+        return child_dorefa(a.child, a.rounds) if dorefa else child(a.child, a.rounds, a.family)
     if a.from_json:
         with open(a.from_json) as fh:
             line = json.loads(fh.read().strip().splitlines()[-1])
@@ -304,12 +327,12 @@ def main():
             write_docs(table(line["shapes"], kernel_name), fam["mark"])
         return
     shapes = []
-    for i in range(len(SHAPES)):
+    for i in range(len(fam["shapes"])):
         # a child per shape, each under its own limit; the first failure ends the run
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(i), "--rounds", str(a.rounds), "--family", a.family],
                            stdout=subprocess.PIPE, text=True, timeout=CHILD_LIMIT_S)
         if p.returncode != 0:
-            raise SystemExit(f"shape {SHAPES[i]}: the measuring process ended with status {p.returncode}; nothing more was started")
+            raise SystemExit(f"shape {fam['shapes'][i]}: the measuring process ended with status {p.returncode}; nothing more was started")
         shapes.append(json.loads(p.stdout.strip().splitlines()[-1]))
         print(json.dumps(shapes[-1]), file=sys.stderr)
     if a.kernel_times:
@@ -326,6 +349,10 @@ def main():
         line.update({"bench": "grouped_codes_chain_resnext", "dtype": "float32 image of 4-bit codes, code-tagged", "layout": "channels_last"})
         del line["defer_grouped_shipped"]
         line["defer_grouped_codes_shipped"] = bool(lazy.DEFER_GROUPED_CODES)
+    if a.family == "mfma":
+        line["bench"] = "grouped_mfma_chain_resnext"
+        del line["defer_grouped_shipped"]
+        line["defer_grouped_mfma_shipped"] = bool(lazy.DEFER_GROUPED_MFMA)
     text = json.dumps(line)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh:
