@@ -1498,6 +1498,26 @@ int qt_gmconv2d_bits_f32(const uint32_t* x_plane, int64_t ldx, const float* w, c
                          int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
                          int dw, int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, int kind, qt_stream_t stream);
 
+/* How a matrix-core grouped conv would launch, without launching it: host arithmetic only, no device call, usable on a machine
+ * without a GPU.  `op` says which entry is meant and the other numbers are that entry's geometry arguments; the status is what
+ * that entry returns for them up to its pointer checks (steps 1 to 3 of its validation), QT_OK with an empty text where there is
+ * nothing to do; a null `out`, cap < 2 or an unknown `op`: QT_ERR_INVALID_ARG.  The text in out[cap] is a list of `name=value`
+ * words, worked out by the functions the launch itself calls (csrc/gconv_mfma.hip gm_plan / gmw_plan, csrc/gconv_planes_mfma.hip
+ * gp_walk), so it is the launch:
+ *   FORWARD, GRAD_INPUT, GRAD_WEIGHT   kernel (the template instantiation), TR TC (destination pixels of a tile), tiles_r tiles_c
+ *                  (tiles of a map), units (N tiles_r tiles_c: the flat index a workgroup walks), splits (workgroups per group),
+ *                  npmax (source pixels of the LDS patch, the zero pixel aside), lds_bytes, tr_shrunk tc_shrunk (rows / columns the
+ *                  LDS budget took from the first tile), grid, block; GRAD_WEIGHT also gpix (go pixels of a tile).
+ *   PLANES         qt_gmconv2d_sign with no output halo (qt_gmconv2d_bits_f32 walks alike): kernel, units (16-pixel tiles of the
+ *                  flat (n, ho, wo) index), splits (waves per group), d_n d_ho d_wo (what one step of splits * 16 pixels adds to
+ *                  a lane's coordinates, before the two carries), grid, block. */
+#define QT_GM_OP_FORWARD     0     /* qt_gmconv2d_f32 */
+#define QT_GM_OP_GRAD_INPUT  1     /* qt_gmconv2d_grad_input_f32 */
+#define QT_GM_OP_GRAD_WEIGHT 2     /* qt_gmconv2d_grad_weight_f32 */
+#define QT_GM_OP_PLANES      3     /* qt_gmconv2d_sign, qt_gmconv2d_bits_f32 */
+int qt_gmconv2d_describe(int op, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh,
+                         int sw, int ph, int pw, int dh, int dw, char* out, int cap);
+
 /* ------------------------------------------------------------------------------------------
  * Depthwise and grouped convolution on half-precision operands: the six entries above for bf16 / fp16 models
  * (model.bfloat16(), model.half(), fp32 models under torch.autocast), named by the "_h" convention of "Half-precision operands".

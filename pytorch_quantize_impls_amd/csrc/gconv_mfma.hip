@@ -32,8 +32,11 @@
 //
 // Non-finite inputs: an inf / NaN element poisons (NaN) every output whose window holds it — also through a ZERO weight
 // (0 * inf), unlike the streaming kernels; elements of magnitude above ~3.39e38 overflow in the bf16 rounding of `hi`.
+#include <cstdio>
+
 #include "qt_common.h"
 #include "dw_map.h"
+#include "gm_describe.h"
 
 namespace {
 
@@ -260,8 +263,8 @@ __global__ __launch_bounds__(DW_THREADS) void gm_kernel(const float* __restrict_
 }
 
 // the tile of the destination map and the LDS it needs: at most 128 pixels, at most 32 columns, the patch inside the budget, then
-// balanced over the map (which only shrinks it)
-GmPlan gm_plan(const GmGeom& g, int taps, int ncb) {
+// balanced over the map (which only shrinks it).  shrunk (qt_gmconv2d_describe): how often the budget loop took a row, a column.
+GmPlan gm_plan(const GmGeom& g, int taps, int ncb, int* shrunk = nullptr) {
     GmPlan pl{};
     const int ks = taps == 9 ? 3 : 1, ps = gm_ps(ncb);
     pl.nopad = (g.NO + 15) & ~15;
@@ -273,10 +276,12 @@ GmPlan gm_plan(const GmGeom& g, int taps, int ncb) {
     pl.tiles_c = (g.Wd + tc - 1) / tc;
     tc = (g.Wd + pl.tiles_c - 1) / pl.tiles_c;
     int tr = gm_min(g.Hd, GM_TILE_PIX / tc);
+    int dec[2] = {0, 0};
     while (need(tr, tc) > budget) {                                   // a 1 x 1 tile needs 9 pixels: this ends
-        if (tr > 1) --tr;
-        else --tc;
+        if (tr > 1) --tr, ++dec[0];
+        else --tc, ++dec[1];
     }
+    if (shrunk) shrunk[0] = dec[0], shrunk[1] = dec[1];
     pl.tiles_c = (g.Wd + tc - 1) / tc;
     pl.tiles_r = (g.Hd + tr - 1) / tr;
     pl.TR = (g.Hd + pl.tiles_r - 1) / pl.tiles_r;
@@ -333,6 +338,17 @@ bool gm_shape(int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, in
            (double)(G * cout_g) <= (double)QT_DW_MAX_CHANNELS;
 }
 
+// the gather's record of a problem gm_shape took: the source is x (forward) or go (grad_input); vec is the caller's to set
+GmGeom gm_geom(bool bwd, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int64_t Ho, int64_t Wo, int s, int ph,
+               int pw) {
+    GmGeom g{};
+    g.N = (int)N; g.G = (int)G;
+    g.KC = (int)(bwd ? cout_g : cin_g); g.NO = (int)(bwd ? cin_g : cout_g);
+    g.Hs = (int)(bwd ? Ho : H); g.Ws = (int)(bwd ? Wo : W); g.Hd = (int)(bwd ? H : Ho); g.Wd = (int)(bwd ? W : Wo);
+    g.s = s; g.ph = ph; g.pw = pw; g.bwd = bwd ? 1 : 0;
+    return g;
+}
+
 // The validation of the forward and grad_input entries, in the documented order.  in / out: the tensor read (x, go) and the one
 // written (y, gx).
 int gm_entry(bool bwd, const float* in, const float* w, const float* bias, float* out, int64_t N, int64_t G, int64_t cin_g,
@@ -348,11 +364,7 @@ int gm_entry(bool bwd, const float* in, const float* w, const float* bias, float
     const DwStrides& ys = bwd ? is : os;
     if (dw_layout(N, Cin, H, W, xs) < 0 || dw_layout(N, Cout, Ho, Wo, ys) < 0) return QT_ERR_INVALID_ARG;
     if (!dw_aligned4(in) || !dw_aligned4(w) || !dw_aligned4(out) || !dw_aligned4(bias)) return QT_ERR_ALIGNMENT;
-    GmGeom g{};
-    g.N = (int)N; g.G = (int)G;
-    g.KC = (int)(bwd ? cout_g : cin_g); g.NO = (int)(bwd ? cin_g : cout_g);
-    g.Hs = (int)(bwd ? Ho : H); g.Ws = (int)(bwd ? Wo : W); g.Hd = (int)(bwd ? H : Ho); g.Wd = (int)(bwd ? W : Wo);
-    g.s = sh; g.ph = ph; g.pw = pw; g.bwd = bwd ? 1 : 0;
+    GmGeom g = gm_geom(bwd, N, G, cin_g, cout_g, H, W, Ho, Wo, sh, ph, pw);
     g.vec = is.c == 1 && qt_aligned16(in) ? 1 : 0;                 // every pixel's group block then starts on 32 bytes
     hipStream_t s = (hipStream_t)stream;
     return kh == 3 ? gm_launch<9>(g.KC / 8, in, w, bias, out, g, is, os, kind, s)
@@ -606,7 +618,7 @@ __global__ __launch_bounds__(DW_THREADS) void gmw_reduce_kernel(const float* __r
 }
 
 // the tile of the output map and the LDS it needs: as gm_plan, with the go tile beside the x patch and no weights
-GmwPlan gmw_plan(const GmGeom& g, int taps, int ncbx, int rt) {
+GmwPlan gmw_plan(const GmGeom& g, int taps, int ncbx, int rt, int* shrunk = nullptr) {
     GmwPlan pl{};
     const int ks = taps == 9 ? 3 : 1, psx = gm_ps(ncbx), psg = gm_ps(2 * rt);
     auto need = [&](int tr, int tc) { return gm_span_cap(0, tr, g.s, ks, g.Hs) * gm_span_cap(0, tc, g.s, ks, g.Ws); };
@@ -617,10 +629,12 @@ GmwPlan gmw_plan(const GmGeom& g, int taps, int ncbx, int rt) {
     pl.tiles_c = (g.Wd + tc - 1) / tc;
     tc = (g.Wd + pl.tiles_c - 1) / pl.tiles_c;
     int tr = gm_min(g.Hd, GM_TILE_PIX / tc);
+    int dec[2] = {0, 0};
     while (bytes(tr, tc) > GM_LDS_BYTES) {                            // a 1 x 1 tile needs under 20 KiB: this ends
-        if (tr > 1) --tr;
-        else --tc;
+        if (tr > 1) --tr, ++dec[0];
+        else --tc, ++dec[1];
     }
+    if (shrunk) shrunk[0] = dec[0], shrunk[1] = dec[1];
     pl.tiles_c = (g.Wd + tc - 1) / tc;
     pl.tiles_r = (g.Hd + tr - 1) / tr;
     pl.TR = (g.Hd + pl.tiles_r - 1) / pl.tiles_r;
@@ -700,6 +714,39 @@ extern "C" int64_t qt_gmconv2d_grad_weight_work_floats(int64_t N, int64_t G, int
     if (!gm_shape(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, Ho, Wo, rc)) return rc;      // an empty problem: 0
     const GmwPlan pl = gmw_plan(gmw_geom(N, G, cin_g, cout_g, H, W, Ho, Wo, sh, ph, pw), kh * kw, (int)cin_g / 8, (int)cout_g / 16);
     return (int64_t)pl.splits * G * gmw_block(kh * kw, (int)cout_g, (int)cin_g);
+}
+
+// What the launch of `op` would run for these numbers: the entry's steps 1 to 3 (gm_shape), then the plan functions the launches
+// call.  The planes walk is reported by gp_describe (gconv_planes_mfma.hip).  No device call.
+extern "C" int qt_gmconv2d_describe(int op, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw,
+                                    int sh, int sw, int ph, int pw, int dh, int dw, char* out, int cap) {
+    if (!out || cap < 2) return QT_ERR_INVALID_ARG;
+    out[0] = 0;
+    if (op == QT_GM_OP_PLANES) return gp_describe(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, out, cap);
+    if (op != QT_GM_OP_FORWARD && op != QT_GM_OP_GRAD_INPUT && op != QT_GM_OP_GRAD_WEIGHT) return QT_ERR_INVALID_ARG;
+    int64_t Ho, Wo;
+    int rc;
+    if (!gm_shape(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, Ho, Wo, rc)) return rc;      // an empty problem: no text
+    const int taps = kh * kw;
+    int shrunk[2] = {0, 0};
+    if (op == QT_GM_OP_GRAD_WEIGHT) {
+        const int ncbx = (int)cin_g / 8, rt = (int)cout_g / 16;
+        const GmwPlan pl = gmw_plan(gmw_geom(N, G, cin_g, cout_g, H, W, Ho, Wo, sh, ph, pw), taps, ncbx, rt, shrunk);
+        snprintf(out, (size_t)cap,
+                 "kernel=gmw_kernel<%d,%d,%d> TR=%d TC=%d tiles_r=%d tiles_c=%d units=%lld splits=%d npmax=%d gpix=%d lds_bytes=%d "
+                 "tr_shrunk=%d tc_shrunk=%d grid=%lld block=%d",
+                 taps, ncbx, rt, pl.TR, pl.TC, pl.tiles_r, pl.tiles_c, (long long)(N * pl.tiles_r * pl.tiles_c), pl.splits, pl.npmax,
+                 pl.gpix, pl.lds_bytes, shrunk[0], shrunk[1], (long long)(G * pl.splits), DW_THREADS);
+        return QT_OK;
+    }
+    const GmGeom g = gm_geom(op == QT_GM_OP_GRAD_INPUT, N, G, cin_g, cout_g, H, W, Ho, Wo, sh, ph, pw);
+    const GmPlan pl = gm_plan(g, taps, g.KC / 8, shrunk);
+    snprintf(out, (size_t)cap,
+             "kernel=gm_kernel<%d,%d> TR=%d TC=%d tiles_r=%d tiles_c=%d units=%lld splits=%d npmax=%d lds_bytes=%d tr_shrunk=%d "
+             "tc_shrunk=%d grid=%lld block=%d",
+             taps, g.KC / 8, pl.TR, pl.TC, pl.tiles_r, pl.tiles_c, (long long)(N * pl.tiles_r * pl.tiles_c), pl.splits, pl.npmax,
+             pl.lds_bytes, shrunk[0], shrunk[1], (long long)(G * pl.splits), DW_THREADS);
+    return QT_OK;
 }
 
 extern "C" int qt_gmconv2d_grad_weight_f32(const float* go, const float* x, const float* w, float* gw, float* gbias, float* work,

@@ -32,8 +32,11 @@
 //                 write different bytes of a word: nothing is read back, nothing is atomic.  The border of a halo plane is
 //                 zeroed by dw_zero_border (dw_planes.h); the nibble row of a pixel comes by one cross-lane read per i from the
 //                 lane that walks that pixel.
+#include <cstdio>
+
 #include "qt_common.h"
 #include "dw_planes.h"
+#include "gm_describe.h"
 
 namespace {
 
@@ -227,29 +230,66 @@ void gp_go(int nct, unsigned grid, hipStream_t s, const uint32_t* x_plane, int64
     else gp_kernel<TAPS, CB, 3><<<grid, DW_THREADS, 0, s>>>(x_plane, ldx, w, bias, alpha, beta, o, g, ys, wk, kind);
 }
 
+// Steps 1 to 3 of the documented validation order, shared by the two entries and gp_describe.  False: the call ends with `rc`
+// (QT_OK: an empty problem); true: Ho x Wo is the output map of a problem inside the window.
+bool gp_shape(bool f32, int64_t halo_h, int64_t halo_w, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh,
+              int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t& Ho, int64_t& Wo, int& rc) {
+    rc = QT_ERR_INVALID_ARG;
+    if (halo_h < 0 || halo_w < 0) return false;
+    if (N < 0 || G < 0 || cin_g < 1 || cout_g < 1 || H < 0 || W < 0 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || ph < 0 || pw < 0 ||
+        dh < 1 || dw < 1)
+        return false;
+    rc = QT_ERR_UNSUPPORTED;
+    if ((int64_t)kh * kw > QT_DW_MAX_TAPS) return false;
+    if (N == 0 || G == 0 || H == 0 || W == 0) {
+        rc = QT_OK;
+        return false;
+    }
+    if ((cin_g != 16 && cin_g != 32) || (cout_g != 16 && cout_g != 32 && cout_g != 48)) return false;
+    if (!((kh == 1 && kw == 1) || (kh == 3 && kw == 3)) || sh != sw || sh > 2 || dh != 1 || dw != 1 || ph > 1 || pw > 1) return false;
+    if (N >= GP_MAX_ROWS || G >= GP_MAX_ROWS || H >= GP_MAX_ROWS || W >= GP_MAX_ROWS || halo_h > DW_MAX_HALO || halo_w > DW_MAX_HALO)
+        return false;
+    const int64_t eh = H + 2 * (int64_t)ph - kh, ew = W + 2 * (int64_t)pw - kw;
+    if (eh < 0 || ew < 0) {                                       // the kernel does not fit the padded image
+        rc = QT_ERR_INVALID_ARG;
+        return false;
+    }
+    Ho = eh / sh + 1;
+    Wo = ew / sw + 1;
+    // pixel rows of every plane below 2^31; so are the elements of y, whose offsets the kernel keeps in 32 bits
+    return !((double)N * (double)H * (double)W >= (double)GP_MAX_ROWS ||
+             (double)N * (double)(Ho + 2 * halo_h) * (double)(Wo + 2 * halo_w) >= (double)GP_MAX_ROWS ||
+             (f32 && (double)N * (double)(G * cout_g) * (double)Ho * (double)Wo >= (double)GP_MAX_ROWS) ||
+             G * cout_g > QT_DW_MAX_CHANNELS);
+}
+
+// the walk of a launch over N Ho Wo output pixels: tiles of 16, splits per group, what a step adds to a lane's (n, ho, wo)
+GpWalk gp_walk(int64_t N, int64_t G, int64_t Ho, int64_t Wo) {
+    const int64_t npix = N * Ho * Wo;
+    GpWalk wk{};
+    wk.G = (int)G;
+    wk.units = (int)((npix + GP_TILE - 1) / GP_TILE);
+    int64_t sp = (int64_t)GP_TARGET_WGS * GP_WAVES / G;
+    if (sp > wk.units) sp = wk.units;
+    wk.splits = (int)(sp < 1 ? 1 : sp);
+    const int64_t step = (int64_t)wk.splits * GP_TILE;
+    wk.d_wo = (int)(step % Wo);
+    wk.d_ho = (int)((step / Wo) % Ho);
+    wk.d_n = (int)(step / Wo / Ho);
+    return wk;
+}
+
+// workgroups of that launch: one wave per (split, group)
+unsigned gp_grid(const GpWalk& wk) { return (unsigned)(((int64_t)wk.G * wk.splits + GP_WAVES - 1) / GP_WAVES); }
+
 // the shared body of the two entries, in the documented validation order: o.y, or at least one of o.sign / o.nib
 int gp_launch(const uint32_t* x_plane, int64_t ldx, const float* w, const float* bias, const float* alpha, const float* beta,
               DwPlaneOut o, bool f32, int64_t halo_h, int64_t halo_w, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H,
               int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, DwStrides ys, int kind, qt_stream_t stream) {
-    if (halo_h < 0 || halo_w < 0) return QT_ERR_INVALID_ARG;
-    if (N < 0 || G < 0 || cin_g < 1 || cout_g < 1 || H < 0 || W < 0 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || ph < 0 || pw < 0 ||
-        dh < 1 || dw < 1)
-        return QT_ERR_INVALID_ARG;
-    if ((int64_t)kh * kw > QT_DW_MAX_TAPS) return QT_ERR_UNSUPPORTED;
-    if (N == 0 || G == 0 || H == 0 || W == 0) return QT_OK;
-    if ((cin_g != 16 && cin_g != 32) || (cout_g != 16 && cout_g != 32 && cout_g != 48)) return QT_ERR_UNSUPPORTED;
-    if (!((kh == 1 && kw == 1) || (kh == 3 && kw == 3)) || sh != sw || sh > 2 || dh != 1 || dw != 1 || ph > 1 || pw > 1)
-        return QT_ERR_UNSUPPORTED;
-    if (N >= GP_MAX_ROWS || G >= GP_MAX_ROWS || H >= GP_MAX_ROWS || W >= GP_MAX_ROWS || halo_h > DW_MAX_HALO || halo_w > DW_MAX_HALO)
-        return QT_ERR_UNSUPPORTED;
-    const int64_t eh = H + 2 * (int64_t)ph - kh, ew = W + 2 * (int64_t)pw - kw;
-    if (eh < 0 || ew < 0) return QT_ERR_INVALID_ARG;              // the kernel does not fit the padded image
-    const int64_t Ho = eh / sh + 1, Wo = ew / sw + 1, Cin = G * cin_g, Cout = G * cout_g;
-    // pixel rows of every plane below 2^31; so are the elements of y, whose offsets the kernel keeps in 32 bits
-    if ((double)N * (double)H * (double)W >= (double)GP_MAX_ROWS ||
-        (double)N * (double)(Ho + 2 * halo_h) * (double)(Wo + 2 * halo_w) >= (double)GP_MAX_ROWS ||
-        (f32 && (double)N * (double)Cout * (double)Ho * (double)Wo >= (double)GP_MAX_ROWS) || Cout > QT_DW_MAX_CHANNELS)
-        return QT_ERR_UNSUPPORTED;
+    int64_t Ho, Wo;
+    int rc;
+    if (!gp_shape(f32, halo_h, halo_w, N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, Ho, Wo, rc)) return rc;
+    const int64_t Cin = G * cin_g, Cout = G * cout_g;
     if (kind != QT_DW_RAW && kind != QT_DW_SIGN && kind != QT_DW_TERNARY) return QT_ERR_INVALID_ARG;
     if (!x_plane || !w) return QT_ERR_INVALID_ARG;
     if (f32) {
@@ -270,18 +310,8 @@ int gp_launch(const uint32_t* x_plane, int64_t ldx, const float* w, const float*
     g.N = (int)N; g.C = (int)Cin; g.H = (int)H; g.W = (int)W; g.Ho = (int)Ho; g.Wo = (int)Wo;
     g.kh = kh; g.kw = kw; g.sh = sh; g.sw = sw; g.ph = ph; g.pw = pw; g.dh = dh; g.dw = dw;
     g.Cout = Cout;
-    const int64_t npix = N * Ho * Wo;
-    GpWalk wk{};
-    wk.G = (int)G;
-    wk.units = (int)((npix + GP_TILE - 1) / GP_TILE);
-    int64_t sp = (int64_t)GP_TARGET_WGS * GP_WAVES / G;
-    if (sp > wk.units) sp = wk.units;
-    wk.splits = (int)(sp < 1 ? 1 : sp);
-    const int64_t step = (int64_t)wk.splits * GP_TILE;
-    wk.d_wo = (int)(step % Wo);
-    wk.d_ho = (int)((step / Wo) % Ho);
-    wk.d_n = (int)(step / Wo / Ho);
-    const unsigned grid = (unsigned)((G * wk.splits + GP_WAVES - 1) / GP_WAVES);
+    const GpWalk wk = gp_walk(N, G, Ho, Wo);
+    const unsigned grid = gp_grid(wk);
     hipStream_t s = (hipStream_t)stream;
     const int nct = (int)(cout_g / 16);
 #define GP_ARGS nct, grid, s, x_plane, ldx, w, bias, alpha, beta, o, g, ys, wk, kind
@@ -297,6 +327,19 @@ int gp_launch(const uint32_t* x_plane, int64_t ldx, const float* w, const float*
 }
 
 }  // namespace
+
+// QT_GM_OP_PLANES of qt_gmconv2d_describe: gp_launch up to the walk, for qt_gmconv2d_sign without an output halo (the walk depends
+// on neither the output form nor the halo)
+int gp_describe(int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph,
+                int pw, int dh, int dw, char* out, int cap) {
+    int64_t Ho, Wo;
+    int rc;
+    if (!gp_shape(false, 0, 0, N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, Ho, Wo, rc)) return rc;
+    const GpWalk wk = gp_walk(N, G, Ho, Wo);
+    snprintf(out, (size_t)cap, "kernel=gp_kernel<%d,%d,%d> units=%d splits=%d d_n=%d d_ho=%d d_wo=%d grid=%u block=%d", kh * kw,
+             (int)cin_g / 16, (int)cout_g / 16, wk.units, wk.splits, wk.d_n, wk.d_ho, wk.d_wo, gp_grid(wk), DW_THREADS);
+    return QT_OK;
+}
 
 extern "C" int qt_gmconv2d_sign(const uint32_t* x_plane, int64_t ldx, const float* w, const float* bias, const float* alpha,
                                 const float* beta, uint32_t* sign_plane, int64_t ldb, uint32_t* nib_plane, int64_t ldn,

@@ -4864,6 +4864,40 @@ def grouped_mfma_grad_weight_work_floats(input_shape, weight_shape, stride=1, pa
                                                      *_pairs(dilation)))
 
 
+#: the ``op`` of grouped_mfma_plan -> QT_GM_OP_* of include/qt_hip.h
+GM_PLAN_OPS = {name: _lib.DEFINES["QT_GM_OP_" + name.upper()] for name in ("forward", "grad_input", "grad_weight", "planes")}
+
+
+def grouped_mfma_plan(op: str, input_shape, weight_shape, stride=1, padding=0, dilation=1, groups: int = 1) -> dict:
+    """How the matrix-core grouped conv ``op`` ("forward", "grad_input", "grad_weight": the fp32 entries; "planes":
+    ``grouped_mfma_conv2d_sign`` / ``grouped_mfma_conv2d_from_bits``) launches for these shapes, without launching it
+    (qt_gmconv2d_describe: the plan functions the launches call; host arithmetic, no GPU needed).  A dict of the words of
+    include/qt_hip.h — integers, but ``kernel`` (the instantiation as text) with ``template`` (its arguments as a tuple); empty for an
+    empty problem.  A shape the entry refuses raises QtStatusError."""
+    import ctypes
+    if op not in GM_PLAN_OPS:
+        raise ValueError(f"grouped_mfma_plan: op must be one of {sorted(GM_PLAN_OPS)}, got {op!r}")
+    if len(input_shape) != 4 or len(weight_shape) != 4:
+        raise ValueError(f"grouped_mfma_plan: expected 4-D input and weight shapes, got {tuple(input_shape)}, {tuple(weight_shape)}")
+    N, C, H, W = (int(v) for v in input_shape)
+    Cout, cin_g, kh, kw = (int(v) for v in weight_shape)
+    G = int(groups)
+    if G < 1 or C != G * cin_g or Cout % G:
+        raise ValueError(f"grouped_mfma_plan: {tuple(input_shape)} x {tuple(weight_shape)} is no conv of {groups} groups")
+    buf = ctypes.create_string_buffer(384)
+    rc = _lib.load().qt_gmconv2d_describe(GM_PLAN_OPS[op], N, G, cin_g, Cout // G, H, W, kh, kw, *_pairs(stride), *_pairs(padding),
+                                          *_pairs(dilation), buf, 384)
+    if rc != 0:
+        raise _lib.QtStatusError(f"qt_gmconv2d_describe failed: {_lib.strerror(rc)} (qt_status {rc})")
+    plan = {}
+    for word in buf.value.decode().split():
+        key, value = word.split("=", 1)
+        plan[key] = value if key == "kernel" else int(value)
+    if plan:
+        plan["template"] = tuple(int(v) for v in plan["kernel"].split("<", 1)[1].rstrip(">").split(","))
+    return plan
+
+
 def grouped_mfma_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, weight: torch.Tensor, stride=1, padding=0, dilation=1,
                                     groups: int = 1, ste_threshold: float = 0.0, want_bias: bool = False,
                                     out: Optional[torch.Tensor] = None, out_bias: Optional[torch.Tensor] = None,
