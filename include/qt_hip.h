@@ -1574,6 +1574,42 @@ int qt_gconv2d_grad_weight_h(const void* go, const void* x, int dtype, const voi
                              int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w,
                              float ste_threshold, qt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Grouped convolution on the matrix cores, half precision: qt_gmconv2d_f32 / qt_gmconv2d_grad_input_f32 for bf16 / fp16 tensors,
+ * inside the same window (cin_g in {16, 24, 32}, cout_g in {16, 32, 48}, 1 x 1 or 3 x 3, stride 1 or 2, padding 0 or 1, dilation
+ * 1) and with the argument lists of qt_gconv2d_h / qt_gconv2d_grad_input_h: csrc/gconv_mfma_h.hip, DESIGN.md "Grouped convs on
+ * the matrix cores, half precision".  The weight gradient of these layers is qt_gconv2d_grad_weight_h above (it takes up to 32
+ * channels per group).
+ *
+ * Operands: as in the section above — x / y / go / gx are 2-byte elements of `dtype`, w has `w_dtype` (`dtype` or QT_DTYPE_F32),
+ * bias is fp32; each tensor dense NCHW or channels-last, strides in elements; 2-byte pointers need 2-byte alignment only.
+ *
+ * Arithmetic — NOT that of the "_h" streaming entries: a 2-byte element is an MFMA operand as it is (v_mfma_f32_16x16x32_bf16 /
+ * v_mfma_f32_16x16x32_f16, ONE term).  Q(w) in {-1, 0, +1} is exact in both types; with QT_DW_RAW a weight of type `dtype` is used
+ * as it is; an fp32 weight is quantised (`kind`) and then rounded once, to nearest even, into `dtype`.  The products are exact
+ * in fp32 and are accumulated in fp32 inside the MFMA in an order fixed by the shapes alone (no atomics: equal inputs give equal
+ * bits); the fp32 bias is added once; the fp32 value is rounded ONCE, to nearest even, into `dtype`:
+ *   result = RNE(fp32 sum + bias).  The fp32 sum is exact where sum |terms| + |bias| stays below 2^24 units of a common power of
+ *   two (integers, say); otherwise it is within (Kp + 1) 2^-23 (sum |x q| + |bias|) of exact before the one rounding, Kp the
+ *   reduction length (cin_g kh kw forward, cout_g kh kw backward) padded to a multiple of 32.
+ *   specials : an inf or NaN element poisons every output whose window holds it, also through a zero weight: a NaN gives NaN; an
+ *              inf gives NaN through a zero weight (0 inf) and +-inf through a +-1 weight — with one term the product is exact,
+ *              where the three-term split of qt_gmconv2d_f32 turns an inf into NaN everywhere.  Overflow of the result rounds to inf; fp16 subnormal results are rounded gradually.  fp16 subnormal INPUTS are not flushed by the
+ *              matrix cores of gfx950 (checked on an MI355X: tests/test_gpu_gconv_mfma_half.py pins the kept-input reference).
+ *
+ * Validation, before anything is enqueued; a non-zero status means nothing was launched: an unknown `dtype`, or a `w_dtype` that
+ * is neither `dtype` nor QT_DTYPE_F32: QT_ERR_INVALID_ARG, before anything else; then steps 1 - 4 of qt_gmconv2d_f32 with the
+ * alignment rule above (an empty problem is QT_OK whatever the pointers are).
+ * ---------------------------------------------------------------------------------------- */
+int qt_gmconv2d_h(const void* x, int dtype, const void* w, int w_dtype, const float* bias, void* y, int64_t N, int64_t G,
+                  int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                  int dw, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, int64_t ys_n, int64_t ys_c, int64_t ys_h,
+                  int64_t ys_w, int kind, qt_stream_t stream);
+int qt_gmconv2d_grad_input_h(const void* go, int dtype, const void* w, int w_dtype, void* gx, int64_t N, int64_t G, int64_t cin_g,
+                             int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                             int64_t gs_n, int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h,
+                             int64_t xs_w, int kind, qt_stream_t stream);
+
 /* Depthwise convolution on bit planes: the forward above inside the fused inference chain conv -> BatchNorm -> Hardtanh ->
  * BinaryConnect -> next conv, reading and / or writing the planes a PackedActivation carries instead of fp32 tensors.  One
  * launch each; no allocation, no synchronisation.

@@ -2088,7 +2088,8 @@ def _streaming_backward(fam: _StreamingFamily, ctx, grad_output):
     return grad_input, grad_weight, grad_bias, None, None, None, None
 
 
-#: routes taken by ``depthwise_half_route`` / ``grouped_half_route`` layers, by family ("depthwise" | "grouped"); the tests read it
+#: routes taken by ``depthwise_half_route`` / ``grouped_half_route`` / ``grouped_mfma_half_route`` layers, by family ("depthwise" |
+#: "grouped" | "grouped_mfma"); the tests read it
 STREAMING_HALF_STATS: Counter = Counter()
 
 #: depthwise BinConv2d / TerConv2d on bf16 / fp16 activations run the "_h" streaming kernels (False: the dense library's half conv,
@@ -2241,11 +2242,31 @@ def grouped_mfma_route(layer, input) -> bool:
             and ops.grouped_mfma_applicable(input.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups))
 
 
+#: BinConv2d / TerConv2d layers inside the window on bf16 / fp16 activations take ``GroupedMfmaConv2dFn`` on the one-term entries
+#: (qt_gmconv2d_h / qt_gmconv2d_grad_input_h, csrc/gconv_mfma_h.hip; False: the dense library's half conv, counted in
+#: LIBRARY_PATHS).  Set from ``tools/bench_grouped_mfma.py --dtype`` by the rule of ``GROUPED_HALF_MAX_CIN_G``: True iff for both
+#: dtypes and on every row the route takes the forward + backward round range lies wholly below the library's and the forward median
+#: is not above the library's (profiles/grouped_mfma_half_bench_line.json, DESIGN.md "Grouped convs on the matrix cores, half
+#: precision").  Measured: the forward is 4.2x - 8.1x (bf16) and 1.5x - 2.6x (fp16) faster on all five rows and bf16 passes on all
+#: five, but the fp16 step loses on three rows (512 @ 14^2: 973 against 959 us; 768 -> 1536: 4278 against 1474 us; 1024 @ 7^2: 963
+#: against 464 us) to the streaming weight gradient: off by the rule.
+GROUPED_MFMA_HALF = False
+
+
+def grouped_mfma_half_route(layer, input) -> bool:
+    """``grouped_mfma_route`` for a bf16 / fp16 activation, switched by ``GROUPED_MFMA_HALF``: ``_streaming_half_common`` (same
+    half dtype, or an fp32 weight under autocast to the activation's dtype), ``groups >= GROUPED_MFMA_MIN_GROUPS`` and the shapes
+    of ``ops.grouped_mfma_applicable``."""
+    return (bool(GROUPED_MFMA_HALF) and _streaming_half_common(layer, input) and layer.groups >= GROUPED_MFMA_MIN_GROUPS
+            and ops.grouped_mfma_applicable(input.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups))
+
+
 class GroupedMfmaConv2dFn(QtFunction):
     """conv2d(x, Q(W), b, groups = G) with 16, 24 or 32 input channels per group on the matrix cores: the sibling of
     ``GroupedConv2dFn``, same arguments.  Forward qt_gmconv2d_f32, backward qt_gmconv2d_grad_input_f32 and a grad_weight (partials
     + combine inside one call, the bias gradient being a by-product): qt_gmconv2d_grad_weight_f32 where
-    ``grouped_mfma_wgrad_route`` says so, else the grouped family's streaming kernel."""
+    ``grouped_mfma_wgrad_route`` says so, else the grouped family's streaming kernel.  A bf16 / fp16 activation: qt_gmconv2d_h,
+    qt_gmconv2d_grad_input_h and ALWAYS the streaming qt_gconv2d_grad_weight_h (the matrix-core weight gradient has no half entry)."""
 
     @staticmethod
     def forward(ctx, input, weight, bias, kind, weight_q, ste, conv_args):
@@ -2253,8 +2274,8 @@ class GroupedMfmaConv2dFn(QtFunction):
 
     @staticmethod
     def backward(ctx, grad_output):
-        return _streaming_backward(_GROUPED_MFMA_WGRAD if grouped_mfma_wgrad_route(grad_output.shape) else _GROUPED_MFMA, ctx,
-                                   grad_output)
+        wgrad = ctx.saved_tensors[0].dtype == torch.float32 and grouped_mfma_wgrad_route(grad_output.shape)
+        return _streaming_backward(_GROUPED_MFMA_WGRAD if wgrad else _GROUPED_MFMA, ctx, grad_output)
 
 
 def grouped_quant_conv(layer, input, kind: str, quant_op):

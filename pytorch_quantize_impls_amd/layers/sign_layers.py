@@ -214,13 +214,16 @@ class _SignConv2d(EvalSwapMixin, torch.nn.Conv2d, QLayer):
         return fn.apply(input, self.weight, self.bias, "raw", self.weight.detach(), _fused.ops.STE_THRESHOLD, args)
 
     def _streaming_half_forward(self, input):
-        """``_streaming_forward`` for a bf16 / fp16 activation (``_fused.depthwise_half_route`` / ``grouped_half_route``): the same
-        autograd nodes on the "_h" entries — results rounded once into the activation's dtype, the weight gradient in the weight's
-        dtype.  Real-valued activations take it too (nothing asks for +-1); never deferred.  None: the counted library expression."""
+        """``_streaming_forward`` for a bf16 / fp16 activation (``_fused.depthwise_half_route`` / ``grouped_half_route`` /
+        ``grouped_mfma_half_route``): the same autograd nodes on the "_h" entries — results rounded once into the activation's dtype,
+        the weight gradient in the weight's dtype.  Real-valued activations take it too (nothing asks for +-1); never deferred.
+        None: the counted library expression."""
         if _fused.depthwise_half_route(self, input):
             fn, fam = _fused.DepthwiseConv2dFn, "depthwise"
         elif _fused.grouped_half_route(self, input):
             fn, fam = _fused.GroupedConv2dFn, "grouped"
+        elif _fused.grouped_mfma_half_route(self, input):       # 16 ... 32 channels per group: one-term MFMAs
+            fn, fam = _fused.GroupedMfmaConv2dFn, "grouped_mfma"
         else:
             return None
         args = (self.stride, self.padding, self.dilation, self.groups)

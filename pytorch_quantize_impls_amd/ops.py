@@ -4292,13 +4292,13 @@ def _gc_planes_geometry(x_shape, weight, stride, padding, dilation, groups):
 
 
 def _gm_geometry(x_shape, weight, stride, padding, dilation, groups, half: bool = False):
-    """``_gc_geometry`` inside the window of ``grouped_mfma_applicable``; fp32 only, whatever ``half`` says."""
-    _require(weight, "weight")
+    """``_gc_geometry`` inside the window of ``grouped_mfma_applicable``."""
+    _require_packable(weight, "weight") if half else _require(weight, "weight")
     if (len(x_shape) == 4 and weight.dim() == 4 and min(map(int, x_shape)) > 0
             and not grouped_mfma_applicable(x_shape, weight.shape, stride, padding, dilation, groups)):
         raise ValueError(f"not a grouped conv the matrix-core entry points take: input {tuple(x_shape)}, weight {tuple(weight.shape)}, "
                          f"groups {groups}, stride {stride}, padding {padding}, dilation {dilation}")
-    return _gc_geometry(x_shape, weight, stride, padding, dilation, groups)
+    return _gc_geometry(x_shape, weight, stride, padding, dilation, groups, half)
 
 
 def _gmp_geometry(x_shape, weight, stride, padding, dilation, groups):
@@ -4331,12 +4331,16 @@ def _streaming_entries(prefix: str) -> dict:
 _DW = _Streaming(_streaming_entries("qt_dwconv2d"), "depthwise", "C * m", _dw_geometry, _dw_geometry, True)
 _GC = _Streaming(_streaming_entries("qt_gconv2d"), "grouped", "G * cout_g", _gc_geometry, _gc_planes_geometry, False)
 #: 16 ... 32 input channels per group on the matrix cores (csrc/gconv_mfma.hip): fp32 forward and grad_input of its own, the weight
-#: gradient of the grouped family (whose entry takes up to 32 channels per group); no plane, code or "_h" entries
+#: gradient of the grouped family (whose entry takes up to 32 channels per group); bf16 / fp16 forward and grad_input on one-term
+#: MFMAs (csrc/gconv_mfma_h.hip) with the grouped family's "_h" weight gradient; no plane or code entries
 _GM = _Streaming({"f32": "qt_gmconv2d_f32", "grad_input_f32": "qt_gmconv2d_grad_input_f32",
-                  "grad_weight_f32": _GC.entry["grad_weight_f32"], "grad_weight_work_floats": _GC.entry["grad_weight_work_floats"]},
+                  "grad_weight_f32": _GC.entry["grad_weight_f32"], "grad_weight_work_floats": _GC.entry["grad_weight_work_floats"],
+                  "h": "qt_gmconv2d_h", "grad_input_h": "qt_gmconv2d_grad_input_h", "grad_weight_h": _GC.entry["grad_weight_h"]},
                  "matrix-core grouped", "G * cout_g", _gm_geometry, _gm_geometry, False)
-#: the same family with the weight gradient on the matrix cores too (qt_gmconv2d_grad_weight_f32: six bf16 products per term)
-_GMW = _GM._replace(entry={**_GM.entry, "grad_weight_f32": "qt_gmconv2d_grad_weight_f32",
+#: the same family with the weight gradient on the matrix cores too (qt_gmconv2d_grad_weight_f32: six bf16 products per term); fp32
+#: only: there is no half entry for it
+_GMW = _GM._replace(entry={"f32": _GM.entry["f32"], "grad_input_f32": _GM.entry["grad_input_f32"],
+                           "grad_weight_f32": "qt_gmconv2d_grad_weight_f32",
                            "grad_weight_work_floats": "qt_gmconv2d_grad_weight_work_floats"})
 #: 16 or 32 input channels per group on the bit planes of a +-1 activation, on the int8 matrix cores (csrc/gconv_planes_mfma.hip):
 #: the two plane entries alone
@@ -4393,8 +4397,10 @@ def grouped_mfma_conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[to
     is exact in bf16, accumulation is fp32 inside the MFMA, the bias is added once at the end — the arithmetic of
     ``float_linear(..., "sign", terms=3)``: the exact sum up to fp32 accumulation order, THE exact sum for integer data below
     2^24.  No detection, no host synchronisation, no allocation beyond the result.  The result has the layout of x, or is written
-    into ``out``."""
-    _require(x, "input")
+    into ``out``.  A bf16 / fp16 ``x`` (with a weight of the same dtype, or fp32 as under autocast; ``bias`` stays an fp32 vector)
+    runs qt_gmconv2d_h: the element is the MFMA operand as it is (one term, v_mfma_f32_16x16x32_bf16 / _f16), an fp32 weight is
+    quantised and rounded once into x's dtype, and the fp32 sum plus bias is rounded once, to nearest even, into a result of x's
+    dtype."""
     return _streaming_conv2d(_GM, x, weight, bias, stride, padding, dilation, groups, kind, out)
 
 
@@ -4752,8 +4758,8 @@ def grouped_mfma_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_outpu
                                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Gradient of ``grouped_mfma_conv2d`` with respect to x on the matrix cores (qt_gmconv2d_grad_input_f32): the gather of
     ``grouped_conv2d_grad_input`` with ``grad_output`` split into three bf16 terms inside the launch; no atomics, the result
-    written in full.  Layout rules as there."""
-    _require(grad_output, "grad_output")
+    written in full.  Layout rules as there.  A bf16 / fp16 ``grad_output`` runs qt_gmconv2d_grad_input_h (one term, the result
+    rounded once into ``grad_output``'s dtype)."""
     return _streaming_conv2d_grad_input(_GM, input_shape, weight, grad_output, stride, padding, dilation, groups, kind, channels_last,
                                         out)
 

@@ -23,6 +23,11 @@ against matrix cores, with ``hbm_share`` = 4 (|x| + |go|) / 8 TB/s and ``mfma_sh
 the matrix-core median.
 
     python tools/bench_grouped_mfma.py [--rounds 9] [--out profiles/grouped_mfma_wgrad_bench_line.json]
+
+``--dtype bf16|fp16|both`` measures the half-precision route instead (``child_half``: the one-term kernels of csrc/gconv_mfma_h.hip
+against the library's half conv, the fp32 route on the upcast tensors for information) on the rows the route takes and writes
+profiles/grouped_mfma_half_bench_line.json; ``grouped_mfma_half_by_rule`` (both dtypes measured, every row passing) is the value
+``_fused.GROUPED_MFMA_HALF`` has to ship with.
 """
 import argparse
 import json
@@ -40,6 +45,7 @@ sys.path.insert(0, B.ROOT)
 SHAPES = [(512, 14, 1, 32, 3, 512), (768, 14, 1, 32, 3, 768), (768, 14, 1, 32, 3, 1536), (1024, 7, 1, 32, 3, 1024),
           (512, 28, 2, 32, 3, 512), (256, 14, 1, 16, 1, 256)]
 BF16_FLOPS = 2.5e15
+DEFAULT_OUT = os.path.join(B.ROOT, "profiles", "grouped_mfma_wgrad_bench_line.json")
 
 
 def child(index, rounds):
@@ -146,6 +152,126 @@ def child(index, rounds):
     print(json.dumps(result))
 
 
+def child_half(index, rounds, dtype):
+    """``--dtype bf16|fp16``: one row the route takes, the layer as ``.to(dtype)`` on +-1 activations of that dtype.  Sides:
+    mfma_h   : ``_fused.GroupedMfmaConv2dFn`` on the half tensors (csrc/gconv_mfma_h.hip; qt_gconv2d_grad_weight_h in a step);
+    torch    : F.conv2d(x, sign(W), b, groups=G) in the same dtype through torch: what these layers run with the switch off;
+    mfma_f32 : for information, the fp32 node on the upcast tensors.
+    ``floor_share`` = max(2 (|x| + |y|) bytes (x 3 for a step) / 8 TB/s, 2 macs (x 3) / 2.5 PFLOP/s) / the mfma_h median, and
+    ``floor`` says which of the two it is."""
+    import torch
+    import torch.nn.functional as F
+    from pytorch_quantize_impls_amd import _lib, ops
+    from pytorch_quantize_impls_amd.functions import _fused
+    from pytorch_quantize_impls_amd.layers import BinConv2d
+
+    C, H, stride, G, k, Cout = SHAPES[index]
+    pad, tdt = k // 2, {"bf16": torch.bfloat16, "fp16": torch.float16}[dtype]
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(index)
+    layer32 = BinConv2d(C, Cout, k, stride=stride, padding=pad, groups=G).to(dev)
+    layer32.weight.data.uniform_(-1.2, 1.2)
+    layer32.bias.data.copy_(torch.randint(-3, 4, (Cout,), generator=g))          # integers: every route's sum is exact
+    layer = BinConv2d(C, Cout, k, stride=stride, padding=pad, groups=G).to(dev)
+    layer.load_state_dict(layer32.state_dict())
+    layer = layer.to(tdt)
+    args = (layer.stride, layer.padding, layer.dilation, G)
+    x32 = torch.where(torch.rand(B.BATCH, C, H, H, generator=g) < 0.5, -1.0, 1.0).to(dev)
+    x = x32.to(tdt)
+    assert ops.grouped_mfma_applicable(x.shape, layer.weight.shape, *args)
+    leaves = {"mfma_h": x.clone().requires_grad_(True), "torch": x.clone().requires_grad_(True), "mfma_f32": x32.clone().requires_grad_(True)}
+
+    def node(lay):
+        return lambda inp: _fused.GroupedMfmaConv2dFn.apply(inp, lay.weight, lay.bias, "binary", None, ops.STE_THRESHOLD, args)
+
+    def library(inp):                                       # in a step the library computes the weight gradient too
+        wq = torch.where(layer.weight.detach() < 0, -1.0, 1.0).to(tdt).requires_grad_(inp.requires_grad)
+        return F.conv2d(inp, wq, layer.bias, stride, pad, 1, G)
+
+    forward = {"mfma_h": node(layer), "torch": library, "mfma_f32": node(layer32)}
+    with torch.no_grad():
+        want = forward["mfma_f32"](x32).to(tdt)             # exact integer sums, rounded once
+        assert torch.equal(forward["mfma_h"](x), want)
+        go32 = torch.randn(want.shape, generator=g).to(dev)
+    gos = {"mfma_h": go32.to(tdt), "torch": go32.to(tdt), "mfma_f32": go32}
+    calls = dict(_lib.call_counts)
+    forward["mfma_h"](leaves["mfma_h"]).backward(gos["mfma_h"])
+    used = {k_: v - calls.get(k_, 0) for k_, v in _lib.call_counts.items() if v != calls.get(k_, 0)}
+    assert used == {"qt_gmconv2d_h": 1, "qt_gmconv2d_grad_input_h": 1, "qt_gconv2d_grad_weight_h": 1}, used
+
+    def fwd(r):
+        def run():
+            with torch.no_grad():
+                forward[r](leaves[r].detach())
+        return run
+
+    def step(r):
+        def run():
+            forward[r](leaves[r]).backward(gos[r])
+            leaves[r].grad = None
+            layer.zero_grad(set_to_none=True)
+            layer32.zero_grad(set_to_none=True)
+        return run
+
+    def run_us(fn, steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6 / steps
+
+    nb, m = 2 * (x.numel() + want.numel()), want.numel() * (C // G) * k * k
+    result = {"channels": C, "out_channels": Cout, "map": H, "stride": stride, "groups": G, "cin_g": C // G, "cout_g": Cout // G,
+              "kernel": k, "dtype": dtype, "bytes": {"fwd": nb, "fwd_bwd": 3 * nb}, "macs": {"fwd": m, "fwd_bwd": 3 * m}}
+    for mode, make, mult in (("fwd", fwd, 1), ("fwd_bwd", step, 3)):
+        fns = {r: make(r) for r in forward}
+        for fn in fns.values():
+            for _ in range(2):
+                fn()
+        samples = {r: [] for r in fns}
+        for _ in range(rounds):
+            for r, fn in fns.items():
+                samples[r].append(run_us(fn, 10))
+        result[mode] = {r: {"median_us": round(sorted(v)[len(v) // 2], 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1)}
+                        for r, v in samples.items()}
+        floors = {"hbm": mult * nb / B.HBM_BYTES_PER_S, "bf16": 2 * mult * m / BF16_FLOPS}
+        top = max(floors, key=floors.get)
+        result[mode]["mfma_h"].update(floor=top, floor_share=round(floors[top] / (result[mode]["mfma_h"]["median_us"] * 1e-6), 3))
+    print(json.dumps(result))
+
+
+def half_passes(s):
+    """The rule of ``GROUPED_HALF_MAX_CIN_G``: the step's round range wholly below the library's, the forward median not above it."""
+    return (s["fwd_bwd"]["mfma_h"]["max_us"] < s["fwd_bwd"]["torch"]["min_us"]
+            and s["fwd"]["mfma_h"]["median_us"] <= s["fwd"]["torch"]["median_us"])
+
+
+def main_half(a):
+    """Both dtypes on every row of SHAPES the route takes; profiles/grouped_mfma_half_bench_line.json."""
+    rows = [i for i, (C, _H, _s, G, _k, Cout) in enumerate(SHAPES) if (Cout // G) % 16 == 0]
+    shapes = []
+    for dtype in (a.dtype if a.dtype != "both" else "bf16,fp16").split(","):
+        for i in rows:
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(i), "--rounds", str(a.rounds), "--dtype", dtype],
+                               stdout=subprocess.PIPE, text=True, timeout=B.CHILD_LIMIT_S)
+            if p.returncode != 0:
+                raise SystemExit(f"shape {SHAPES[i]} in {dtype}: the measuring process ended with status {p.returncode}; nothing more was started")
+            shapes.append(json.loads(p.stdout.strip().splitlines()[-1]))
+            print(json.dumps(shapes[-1]), file=sys.stderr)
+    from pytorch_quantize_impls_amd.functions import _fused
+    line = {"bench": "grouped_mfma_half", "batch": B.BATCH, "rounds": a.rounds, "layout": "NCHW", "hbm_bytes_per_s": B.HBM_BYTES_PER_S,
+            "bf16_flops": BF16_FLOPS, "shapes": shapes, "shape_passes_rule": [half_passes(s) for s in shapes],
+            "grouped_mfma_half_by_rule": all(half_passes(s) for s in shapes) and {s["dtype"] for s in shapes} == {"bf16", "fp16"},
+            "grouped_mfma_half_shipped": bool(_fused.GROUPED_MFMA_HALF)}
+    text = json.dumps(line)
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(B.ROOT, "profiles", "grouped_mfma_half_bench_line.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        fh.write(text + "\n")
+    print(text)
+
+
 def trace_steps(steps):
     """For ``rocprofv3 --kernel-trace --stats -- python tools/bench_grouped_mfma.py --trace-steps 3``: every row the route takes, in
     one process, ``steps`` training steps with the weight-gradient switch off and then on.  Kernel times instead of wall-time
@@ -187,14 +313,18 @@ def wgrad_passes(s, against="mfma"):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
-    ap.add_argument("--out", default=os.path.join(B.ROOT, "profiles", "grouped_mfma_wgrad_bench_line.json"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
     ap.add_argument("--child", type=int, default=None)
     ap.add_argument("--trace-steps", type=int, default=None)
+    ap.add_argument("--dtype", default=None, choices=("bf16", "fp16", "both"),
+                    help="the half-precision route against the library's half conv (both: what the switch GROUPED_MFMA_HALF needs)")
     a = ap.parse_args()
     if a.trace_steps is not None:
         return trace_steps(a.trace_steps)
     if a.child is not None:
-        return child(a.child, a.rounds)
+        return child_half(a.child, a.rounds, a.dtype) if a.dtype else child(a.child, a.rounds)
+    if a.dtype:
+        return main_half(a)
     shapes = []
     for i in range(len(SHAPES)):
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(i), "--rounds", str(a.rounds)],
