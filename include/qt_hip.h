@@ -1578,8 +1578,8 @@ int qt_gconv2d_grad_weight_h(const void* go, const void* x, int dtype, const voi
  * Grouped convolution on the matrix cores, half precision: qt_gmconv2d_f32 / qt_gmconv2d_grad_input_f32 for bf16 / fp16 tensors,
  * inside the same window (cin_g in {16, 24, 32}, cout_g in {16, 32, 48}, 1 x 1 or 3 x 3, stride 1 or 2, padding 0 or 1, dilation
  * 1) and with the argument lists of qt_gconv2d_h / qt_gconv2d_grad_input_h: csrc/gconv_mfma_h.hip, DESIGN.md "Grouped convs on
- * the matrix cores, half precision".  The weight gradient of these layers is qt_gconv2d_grad_weight_h above (it takes up to 32
- * channels per group).
+ * the matrix cores, half precision".  The weight gradient of these layers is qt_gmconv2d_grad_weight_h below, or the streaming
+ * qt_gconv2d_grad_weight_h above (it takes up to 32 channels per group).
  *
  * Operands: as in the section above — x / y / go / gx are 2-byte elements of `dtype`, w has `w_dtype` (`dtype` or QT_DTYPE_F32),
  * bias is fp32; each tensor dense NCHW or channels-last, strides in elements; 2-byte pointers need 2-byte alignment only.
@@ -1609,6 +1609,41 @@ int qt_gmconv2d_grad_input_h(const void* go, int dtype, const void* w, int w_dty
                              int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                              int64_t gs_n, int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h,
                              int64_t xs_w, int kind, qt_stream_t stream);
+
+/* The weight gradient of the same layers on one-term MFMAs: qt_gmconv2d_grad_weight_f32 for bf16 / fp16 go and x, inside the same
+ * window (cin_g in {16, 24, 32}, cout_g in {16, 32, 48}, 1 x 1 or 3 x 3, stride 1 or 2, padding 0 or 1, dilation 1), with the
+ * argument list of qt_gconv2d_grad_weight_h and the two launches of qt_gmconv2d_grad_weight_f32 (partials [split][g][tap][oc][ci]
+ * + [oc], then the splits): csrc/gconv_mfma_h.hip "the weight gradient", DESIGN.md "The weight gradient on one-term MFMAs".
+ *
+ * Operands: go and x are 2-byte elements of `dtype`, each dense NCHW or channels-last (a view at an odd element offset is fine:
+ * 2-byte alignment only); w, gw and gbias have `w_dtype` (`dtype`, or QT_DTYPE_F32 under autocast; 2- / 4-byte alignment); `w` may
+ * be null when ste_threshold is 0, `gbias` may be null.  `work` is fp32, 16-byte aligned, need not be zero, and holds
+ * qt_gmconv2d_grad_weight_work_floats(...) floats — the ONE query serves both forms; the launch uses a prefix of it (a one-term tile
+ * is never smaller than the three-term tile, so there are never more units or splits).
+ *
+ * Arithmetic: a bf16 / fp16 element of go and of x is an MFMA operand as it is (v_mfma_f32_16x16x32_bf16 / _f16): ONE term each,
+ * ONE product per (go, x) pair where the fp32 entry needs six.  The products are exact in fp32 (barring fp32 underflow for bf16)
+ * and are accumulated in fp32 inside the MFMA and across the splits in an order fixed by the shapes and the layouts alone (no
+ * atomics: equal inputs give equal bits whatever the workspace held).  The second launch sums the splits in index order, applies
+ * the STE mask (|float(w)| > ste_threshold, compared in fp32) and rounds ONCE, to nearest even, into `w_dtype`; an fp32 `w_dtype`
+ * stores the fp32 sum.  gbias comes from the same pass (go against a fragment of ones).  For finite inputs, before the one
+ * rounding, with L = N Ho Wo:
+ *   |gw - exact| <= (L + QT_GM_WGRAD_MAX_SPLITS + 2) 2^-23 sum |go x|,   |gbias - exact| <= (L + QT_GM_WGRAD_MAX_SPLITS + 1) 2^-23 sum |go|
+ * (the fp32 entry's bound with one product per term instead of six, the bias one instead of three).  Where sum |go x| stays below
+ * 2^24 units of a common power of two, the fp32 sum IS the exact sum.  fp16 subnormal elements are kept, not flushed, in BOTH
+ * operands (fp16 gradients are routinely subnormal; tests/test_gpu_gconv_mfma_wgrad_half.py pins it).  Non-finite data: a NaN
+ * poisons every sum that contains it; nothing more is pinned.
+ *
+ * Validation, before anything is enqueued; a non-zero status means nothing was launched: an unknown `dtype`, or a `w_dtype` that
+ * is neither `dtype` nor QT_DTYPE_F32: QT_ERR_INVALID_ARG, before anything else; then steps 1 - 3 of qt_gmconv2d_f32 (an empty
+ * problem is QT_OK whatever the pointers are); then a null go, x, gw or work, a null w with ste_threshold > 0, a negative or NaN
+ * ste_threshold, strides that are neither dense layout, work_floats below qt_gmconv2d_grad_weight_work_floats(...):
+ * QT_ERR_INVALID_ARG; then the alignment rule above, `work` not 16-byte aligned: QT_ERR_ALIGNMENT. */
+int qt_gmconv2d_grad_weight_h(const void* go, const void* x, int dtype, const void* w, void* gw, void* gbias, int w_dtype,
+                              float* work, int64_t work_floats, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H,
+                              int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n,
+                              int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w,
+                              float ste_threshold, qt_stream_t stream);
 
 /* Depthwise convolution on bit planes: the forward above inside the fused inference chain conv -> BatchNorm -> Hardtanh ->
  * BinaryConnect -> next conv, reading and / or writing the planes a PackedActivation carries instead of fp32 tensors.  One

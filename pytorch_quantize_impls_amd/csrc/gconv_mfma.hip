@@ -270,17 +270,6 @@ int gm_entry(bool bwd, const float* in, const float* w, const float* bias, float
 // wave's go fragments of a 32-pixel chunk are reused across its taps.  cin_g = 24 reads 8 channels past the pixel in its second
 // column tile (the neighbour's, or the 16 bytes of slack after the last): MFMA rows are independent and those rows are never stored.
 
-constexpr int GMW_MAX_SPLITS = QT_GM_WGRAD_MAX_SPLITS;
-
-struct GmwPlan {
-    int TR, TC, tiles_r, tiles_c;
-    int splits;
-    int npmax;               // x patch pixels per term; pixel npmax is the zero pixel
-    int gpix;                // go tile pixels per term: TR * TC rounded up to the chunk of 32
-    int gvec;                // go is channels-last and 16-byte aligned (GmGeom::vec says so for x)
-    int lds_bytes;
-};
-
 typedef short gm_s4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) gm_s4 gm_lds_s4;
 
@@ -330,9 +319,6 @@ __device__ __forceinline__ void gmw_stage(const float* __restrict__ base, const 
         *reinterpret_cast<uint4*>(pd + 2 * TS) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
     }
 }
-
-// floats of one (split, group) block of the partials: [tap][oc][ci], then the bias gradient [oc]
-__host__ __device__ inline int64_t gmw_block(int taps, int cout_g, int cin_g) { return (int64_t)taps * cout_g * cin_g + cout_g; }
 
 // NCBX: blocks of 8 input channels of a group (2, 3, 4); RT: row tiles of 16 output channels (1, 2, 3)
 template <int TAPS, int NCBX, int RT>
@@ -494,48 +480,6 @@ __global__ __launch_bounds__(DW_THREADS) void gmw_reduce_kernel(const float* __r
     }
 }
 
-// the tile of the output map and the LDS it needs: as gm_plan, with the go tile beside the x patch and no weights
-GmwPlan gmw_plan(const GmGeom& g, int taps, int ncbx, int rt, int* shrunk = nullptr) {
-    GmwPlan pl{};
-    const int ks = taps == 9 ? 3 : 1, psx = gm_ps(ncbx), psg = gm_ps(2 * rt);
-    auto need = [&](int tr, int tc) { return gm_span_cap(0, tr, g.s, ks, g.Hs) * gm_span_cap(0, tc, g.s, ks, g.Ws); };
-    auto bytes = [&](int tr, int tc) {
-        return taps * GM_TILE_PIX * 4 + 3 * ((tr * tc + 31) & ~31) * psg + 3 * (need(tr, tc) + 1) * psx + 16;
-    };
-    int tc = gm_min(g.Wd, GM_TILE_COLS);
-    pl.tiles_c = (g.Wd + tc - 1) / tc;
-    tc = (g.Wd + pl.tiles_c - 1) / pl.tiles_c;
-    int tr = gm_min(g.Hd, GM_TILE_PIX / tc);
-    int dec[2] = {0, 0};
-    while (bytes(tr, tc) > GM_LDS_BYTES) {                            // a 1 x 1 tile needs under 20 KiB: this ends
-        if (tr > 1) --tr, ++dec[0];
-        else --tc, ++dec[1];
-    }
-    if (shrunk) shrunk[0] = dec[0], shrunk[1] = dec[1];
-    pl.tiles_c = (g.Wd + tc - 1) / tc;
-    pl.tiles_r = (g.Hd + tr - 1) / tr;
-    pl.TR = (g.Hd + pl.tiles_r - 1) / pl.tiles_r;
-    pl.TC = (g.Wd + pl.tiles_c - 1) / pl.tiles_c;
-    pl.npmax = need(pl.TR, pl.TC);
-    pl.gpix = (pl.TR * pl.TC + 31) & ~31;
-    pl.lds_bytes = bytes(pl.TR, pl.TC);
-    const int64_t units = (int64_t)g.N * pl.tiles_r * pl.tiles_c;
-    int64_t s = (GM_TARGET_WGS + g.G - 1) / g.G;
-    if (s > GMW_MAX_SPLITS) s = GMW_MAX_SPLITS;
-    if (s > units) s = units;
-    pl.splits = (int)s;
-    return pl;
-}
-
-GmGeom gmw_geom(int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int64_t Ho, int64_t Wo, int s, int ph,
-                int pw) {
-    GmGeom g{};
-    g.N = (int)N; g.G = (int)G; g.KC = (int)cin_g; g.NO = (int)cout_g;
-    g.Hs = (int)H; g.Ws = (int)W; g.Hd = (int)Ho; g.Wd = (int)Wo;
-    g.s = s; g.ph = ph; g.pw = pw;
-    return g;
-}
-
 template <int TAPS, int NCBX>
 void gmw_launch(int rt, unsigned grid, hipStream_t s, const float* go, const float* x, float* work, const GmGeom& g, const DwStrides& gs,
                 const DwStrides& xs, const GmwPlan& pl) {
@@ -557,7 +501,7 @@ int gmw_entry(const float* go, const float* x, const float* w, float* gw, float*
     if (dw_layout(N, G * cout_g, Ho, Wo, gs) < 0 || dw_layout(N, G * cin_g, H, W, xs) < 0) return QT_ERR_INVALID_ARG;
     GmGeom g = gmw_geom(N, G, cin_g, cout_g, H, W, Ho, Wo, sh, ph, pw);
     const int taps = kh * kw, ncbx = (int)cin_g / 8, rt = (int)cout_g / 16;
-    GmwPlan pl = gmw_plan(g, taps, ncbx, rt);
+    GmwPlan pl = gmw_plan(g, taps, ncbx, rt, 3);
     if (work_floats < (int64_t)pl.splits * G * gmw_block(taps, (int)cout_g, (int)cin_g)) return QT_ERR_INVALID_ARG;
     if (!dw_aligned4(gw) || !dw_aligned4(gbias) || !dw_aligned4(w) || !dw_aligned4(go) || !dw_aligned4(x) || !qt_aligned16(work))
         return QT_ERR_ALIGNMENT;                                      // the partials are written as float4
@@ -589,7 +533,7 @@ extern "C" int64_t qt_gmconv2d_grad_weight_work_floats(int64_t N, int64_t G, int
     int64_t Ho, Wo;
     int rc;
     if (!gm_shape(N, G, cin_g, cout_g, H, W, kh, kw, sh, sw, ph, pw, dh, dw, Ho, Wo, rc)) return rc;      // an empty problem: 0
-    const GmwPlan pl = gmw_plan(gmw_geom(N, G, cin_g, cout_g, H, W, Ho, Wo, sh, ph, pw), kh * kw, (int)cin_g / 8, (int)cout_g / 16);
+    const GmwPlan pl = gmw_plan(gmw_geom(N, G, cin_g, cout_g, H, W, Ho, Wo, sh, ph, pw), kh * kw, (int)cin_g / 8, (int)cout_g / 16, 3);
     return (int64_t)pl.splits * G * gmw_block(kh * kw, (int)cout_g, (int)cin_g);
 }
 
@@ -608,7 +552,7 @@ extern "C" int qt_gmconv2d_describe(int op, int64_t N, int64_t G, int64_t cin_g,
     int shrunk[2] = {0, 0};
     if (op == QT_GM_OP_GRAD_WEIGHT) {
         const int ncbx = (int)cin_g / 8, rt = (int)cout_g / 16;
-        const GmwPlan pl = gmw_plan(gmw_geom(N, G, cin_g, cout_g, H, W, Ho, Wo, sh, ph, pw), taps, ncbx, rt, shrunk);
+        const GmwPlan pl = gmw_plan(gmw_geom(N, G, cin_g, cout_g, H, W, Ho, Wo, sh, ph, pw), taps, ncbx, rt, 3, shrunk);
         snprintf(out, (size_t)cap,
                  "kernel=gmw_kernel<%d,%d,%d> TR=%d TC=%d tiles_r=%d tiles_c=%d units=%lld splits=%d npmax=%d gpix=%d lds_bytes=%d "
                  "tr_shrunk=%d tc_shrunk=%d grid=%lld block=%d",

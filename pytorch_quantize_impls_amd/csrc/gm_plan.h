@@ -1,6 +1,7 @@
 // What the matrix-core grouped convs of gconv_mfma.hip (fp32 operands, three bf16 terms) and gconv_mfma_h.hip (bf16 / fp16 operands,
 // one term) share: the gather's record of a problem, the tile plan with its LDS budget, the spans of a tile's source box and steps
-// 1 to 3 of the documented validation order.  The plan takes the number of operand planes (`terms`) the patch is staged as.
+// 1 to 3 of the documented validation order.  The plans (gm_plan; gmw_plan of the weight gradient) take the number of operand
+// planes (`terms`) the patch is staged as.
 #pragma once
 #include "qt_common.h"
 
@@ -89,6 +90,65 @@ inline GmPlan gm_plan(const GmGeom& g, int taps, int ncb, int terms, int* shrunk
     if (s > units) s = units;
     pl.splits = (int)(s < 1 ? 1 : s);
     return pl;
+}
+
+// ---- the weight gradient: gmw_kernel (gconv_mfma.hip, three terms) and gwh_kernel (gconv_mfma_h.hip, one term) -----------------
+
+constexpr int GMW_MAX_SPLITS = QT_GM_WGRAD_MAX_SPLITS;
+
+struct GmwPlan {
+    int TR, TC, tiles_r, tiles_c;
+    int splits;
+    int npmax;               // x patch pixels per term; pixel npmax is the zero pixel
+    int gpix;                // go tile pixels per term: TR * TC rounded up to the chunk of 32
+    int gvec;                // go is channels-last and 16-byte aligned (GmGeom::vec says so for x)
+    int lds_bytes;
+};
+
+// floats of one (split, group) block of the partials: [tap][oc][ci], then the bias gradient [oc]
+__host__ __device__ inline int64_t gmw_block(int taps, int cout_g, int cin_g) { return (int64_t)taps * cout_g * cin_g + cout_g; }
+
+// the tile of the output map and the LDS it needs: as gm_plan, with the go tile beside the x patch (`terms` planes of each) and no
+// weights.  A plan of fewer terms never has a smaller tile (the budget loop stops no later), so never more units or splits.
+inline GmwPlan gmw_plan(const GmGeom& g, int taps, int ncbx, int rt, int terms, int* shrunk = nullptr) {
+    GmwPlan pl{};
+    const int ks = taps == 9 ? 3 : 1, psx = gm_ps(ncbx), psg = gm_ps(2 * rt);
+    auto need = [&](int tr, int tc) { return gm_span_cap(0, tr, g.s, ks, g.Hs) * gm_span_cap(0, tc, g.s, ks, g.Ws); };
+    auto bytes = [&](int tr, int tc) {
+        return taps * GM_TILE_PIX * 4 + terms * ((tr * tc + 31) & ~31) * psg + terms * (need(tr, tc) + 1) * psx + 16;
+    };
+    int tc = gm_min(g.Wd, GM_TILE_COLS);
+    pl.tiles_c = (g.Wd + tc - 1) / tc;
+    tc = (g.Wd + pl.tiles_c - 1) / pl.tiles_c;
+    int tr = gm_min(g.Hd, GM_TILE_PIX / tc);
+    int dec[2] = {0, 0};
+    while (bytes(tr, tc) > GM_LDS_BYTES) {                            // a 1 x 1 tile needs under 20 KiB: this ends
+        if (tr > 1) --tr, ++dec[0];
+        else --tc, ++dec[1];
+    }
+    if (shrunk) shrunk[0] = dec[0], shrunk[1] = dec[1];
+    pl.tiles_c = (g.Wd + tc - 1) / tc;
+    pl.tiles_r = (g.Hd + tr - 1) / tr;
+    pl.TR = (g.Hd + pl.tiles_r - 1) / pl.tiles_r;
+    pl.TC = (g.Wd + pl.tiles_c - 1) / pl.tiles_c;
+    pl.npmax = need(pl.TR, pl.TC);
+    pl.gpix = (pl.TR * pl.TC + 31) & ~31;
+    pl.lds_bytes = bytes(pl.TR, pl.TC);
+    const int64_t units = (int64_t)g.N * pl.tiles_r * pl.tiles_c;
+    int64_t s = (GM_TARGET_WGS + g.G - 1) / g.G;
+    if (s > GMW_MAX_SPLITS) s = GMW_MAX_SPLITS;
+    if (s > units) s = units;
+    pl.splits = (int)s;
+    return pl;
+}
+
+inline GmGeom gmw_geom(int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int64_t Ho, int64_t Wo, int s, int ph,
+                       int pw) {
+    GmGeom g{};
+    g.N = (int)N; g.G = (int)G; g.KC = (int)cin_g; g.NO = (int)cout_g;
+    g.Hs = (int)H; g.Ws = (int)W; g.Hd = (int)Ho; g.Wd = (int)Wo;
+    g.s = s; g.ph = ph; g.pw = pw;
+    return g;
 }
 
 // Steps 1 to 3 of the documented validation order, shared by every entry: the sizes, the empty problem, the limits.  False: the

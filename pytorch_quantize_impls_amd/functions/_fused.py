@@ -2219,6 +2219,13 @@ GROUPED_MFMA_WGRAD = False
 #: then leave most of the 256 CUs without one and the split pass is pure overhead.  NOT tuned: nothing between this floor and the
 #: smallest benchmarked shape (L = 12544) has been measured.
 GROUPED_MFMA_WGRAD_MIN_L = 1024
+#: the same choice for a bf16 / fp16 activation: qt_gmconv2d_grad_weight_h (one product per term, csrc/gconv_mfma_h.hip) from the
+#: same floor up (False: the streaming qt_gconv2d_grad_weight_h, as before).  Set from ``tools/bench_grouped_mfma.py --dtype`` by
+#: the rule of ``GROUPED_MFMA_WGRAD``: True iff for both dtypes and on every row the route takes the step's round range with it on
+#: lies wholly below the range with it off.  Measured (profiles/grouped_mfma_wgrad_half_bench_line.json, DESIGN.md "The weight
+#: gradient on one-term MFMAs"): 2.2x - 6.0x faster steps on the eight 3 x 3 rows and 1.3x on the fp16 1 x 1 row, but the bf16
+#: 1 x 1 row is level (240 [236 - 246] against 244 [241 - 254] us, overlapping ranges): off by the rule.
+GROUPED_MFMA_WGRAD_HALF = False
 
 _GROUPED_MFMA = _StreamingFamily(ops._GM, None, None)          # the fp32 tensors' form; no code form
 _GROUPED_MFMA_WGRAD = _StreamingFamily(ops._GMW, None, None)
@@ -2226,12 +2233,13 @@ _GROUPED_MFMA_WGRAD = _StreamingFamily(ops._GMW, None, None)
 _GROUPED_MFMA_PLANES = _StreamingFamily(ops._GMP, _grouped_mfma_planes_admission, None)
 
 
-def grouped_mfma_wgrad_route(grad_output_shape) -> bool:
+def grouped_mfma_wgrad_route(grad_output_shape, half: bool = False) -> bool:
     """The backward of a ``GroupedMfmaConv2dFn`` node whose incoming gradient has this [N, Cout, Ho, Wo] shape takes the
-    matrix-core weight gradient: ``GROUPED_MFMA_WGRAD`` is on and N Ho Wo >= ``GROUPED_MFMA_WGRAD_MIN_L``.  A pure function of
-    the switch and the shape (the node is inside the entry's window already)."""
+    matrix-core weight gradient: ``GROUPED_MFMA_WGRAD`` (``half``, a bf16 / fp16 activation: ``GROUPED_MFMA_WGRAD_HALF``) is on
+    and N Ho Wo >= ``GROUPED_MFMA_WGRAD_MIN_L``.  A pure function of the switch and the shape (the node is inside the entry's
+    window already)."""
     N, _C, Ho, Wo = (int(v) for v in grad_output_shape)
-    return bool(GROUPED_MFMA_WGRAD) and N * Ho * Wo >= GROUPED_MFMA_WGRAD_MIN_L
+    return bool(GROUPED_MFMA_WGRAD_HALF if half else GROUPED_MFMA_WGRAD) and N * Ho * Wo >= GROUPED_MFMA_WGRAD_MIN_L
 
 
 def grouped_mfma_route(layer, input) -> bool:
@@ -2249,7 +2257,9 @@ def grouped_mfma_route(layer, input) -> bool:
 #: is not above the library's (profiles/grouped_mfma_half_bench_line.json, DESIGN.md "Grouped convs on the matrix cores, half
 #: precision").  Measured: the forward is 4.2x - 8.1x (bf16) and 1.5x - 2.6x (fp16) faster on all five rows and bf16 passes on all
 #: five, but the fp16 step loses on three rows (512 @ 14^2: 973 against 959 us; 768 -> 1536: 4278 against 1474 us; 1024 @ 7^2: 963
-#: against 464 us) to the streaming weight gradient: off by the rule.
+#: against 464 us) to the streaming weight gradient: off by the rule.  Re-evaluated with ``GROUPED_MFMA_WGRAD_HALF`` at its
+#: shipped value (off; profiles/grouped_mfma_wgrad_half_bench_line.json): the same three fp16 rows lose (971 against 955, 4272
+#: against 1456, 953 against 454 us): still off.  With that switch on every row of both dtypes passes.
 GROUPED_MFMA_HALF = False
 
 
@@ -2266,7 +2276,8 @@ class GroupedMfmaConv2dFn(QtFunction):
     ``GroupedConv2dFn``, same arguments.  Forward qt_gmconv2d_f32, backward qt_gmconv2d_grad_input_f32 and a grad_weight (partials
     + combine inside one call, the bias gradient being a by-product): qt_gmconv2d_grad_weight_f32 where
     ``grouped_mfma_wgrad_route`` says so, else the grouped family's streaming kernel.  A bf16 / fp16 activation: qt_gmconv2d_h,
-    qt_gmconv2d_grad_input_h and ALWAYS the streaming qt_gconv2d_grad_weight_h (the matrix-core weight gradient has no half entry)."""
+    qt_gmconv2d_grad_input_h and qt_gmconv2d_grad_weight_h where ``grouped_mfma_wgrad_route(..., half=True)`` says so, else the
+    streaming qt_gconv2d_grad_weight_h."""
 
     @staticmethod
     def forward(ctx, input, weight, bias, kind, weight_q, ste, conv_args):
@@ -2274,7 +2285,7 @@ class GroupedMfmaConv2dFn(QtFunction):
 
     @staticmethod
     def backward(ctx, grad_output):
-        wgrad = ctx.saved_tensors[0].dtype == torch.float32 and grouped_mfma_wgrad_route(grad_output.shape)
+        wgrad = grouped_mfma_wgrad_route(grad_output.shape, half=ctx.saved_tensors[0].dtype != torch.float32)
         return _streaming_backward(_GROUPED_MFMA_WGRAD if wgrad else _GROUPED_MFMA, ctx, grad_output)
 
 

@@ -4337,11 +4337,13 @@ _GM = _Streaming({"f32": "qt_gmconv2d_f32", "grad_input_f32": "qt_gmconv2d_grad_
                   "grad_weight_f32": _GC.entry["grad_weight_f32"], "grad_weight_work_floats": _GC.entry["grad_weight_work_floats"],
                   "h": "qt_gmconv2d_h", "grad_input_h": "qt_gmconv2d_grad_input_h", "grad_weight_h": _GC.entry["grad_weight_h"]},
                  "matrix-core grouped", "G * cout_g", _gm_geometry, _gm_geometry, False)
-#: the same family with the weight gradient on the matrix cores too (qt_gmconv2d_grad_weight_f32: six bf16 products per term); fp32
-#: only: there is no half entry for it
+#: the same family with the weight gradient on the matrix cores too: qt_gmconv2d_grad_weight_f32 (six bf16 products per term) and,
+#: for bf16 / fp16 operands, qt_gmconv2d_grad_weight_h (one product per term); one workspace query for both
 _GMW = _GM._replace(entry={"f32": _GM.entry["f32"], "grad_input_f32": _GM.entry["grad_input_f32"],
                            "grad_weight_f32": "qt_gmconv2d_grad_weight_f32",
-                           "grad_weight_work_floats": "qt_gmconv2d_grad_weight_work_floats"})
+                           "grad_weight_work_floats": "qt_gmconv2d_grad_weight_work_floats",
+                           "h": _GM.entry["h"], "grad_input_h": _GM.entry["grad_input_h"],
+                           "grad_weight_h": "qt_gmconv2d_grad_weight_h"})
 #: 16 or 32 input channels per group on the bit planes of a +-1 activation, on the int8 matrix cores (csrc/gconv_planes_mfma.hip):
 #: the two plane entries alone
 _GMP = _Streaming({"sign": "qt_gmconv2d_sign", "bits_f32": "qt_gmconv2d_bits_f32"}, "matrix-core grouped", "G * cout_g",
@@ -4909,13 +4911,15 @@ def grouped_mfma_conv2d_grad_weight(x: torch.Tensor, grad_output: torch.Tensor, 
                                     out: Optional[torch.Tensor] = None, out_bias: Optional[torch.Tensor] = None,
                                     workspace: Optional[torch.Tensor] = None):
     """``grouped_conv2d_grad_weight`` for the shapes of ``grouped_mfma_applicable`` on the bf16 matrix cores
-    (qt_gmconv2d_grad_weight_f32), fp32 only: ``x`` and ``grad_output`` of ANY value are each split exactly into three bf16 terms
+    (qt_gmconv2d_grad_weight_f32): fp32 ``x`` and ``grad_output`` of ANY value are each split exactly into three bf16 terms
     inside the launch and six of the nine cross products are kept (the dropped ones are below 2^-23 of the term), accumulated in
     fp32 over the N Ho Wo output pixels — within (6 L + ``GM_WGRAD_MAX_SPLITS`` + 2) 2^-23 sum |go x| of the exact sum, THE exact sum
     for integers of up to 16 bits whose sums of magnitudes stay below 2^24.  Same two launches, arguments and return; the
-    workspace is ``grouped_mfma_grad_weight_work_floats`` fp32 elements, 16-byte aligned."""
-    _require(x, "input")
-    _require(grad_output, "grad_output")
+    workspace is ``grouped_mfma_grad_weight_work_floats`` fp32 elements, 16-byte aligned.  bf16 / fp16 ``x`` and ``grad_output``
+    (one dtype, with a weight of that dtype, or fp32 as under autocast) run qt_gmconv2d_grad_weight_h: both are MFMA operands as
+    they are, ONE exact product per pair (v_mfma_f32_16x16x32_bf16 / _f16), within (L + ``GM_WGRAD_MAX_SPLITS`` + 2) 2^-23
+    sum |go x| before the one rounding to nearest even into the WEIGHT's dtype, which both gradients have (an fp32 weight gets the
+    fp32 sums); same workspace."""
     return _streaming_conv2d_grad_weight(_GMW, x, grad_output, weight, stride, padding, dilation, groups, ste_threshold, want_bias, out,
                                          out_bias, workspace)
 

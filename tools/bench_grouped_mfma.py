@@ -26,8 +26,13 @@ the matrix-core median.
 
 ``--dtype bf16|fp16|both`` measures the half-precision route instead (``child_half``: the one-term kernels of csrc/gconv_mfma_h.hip
 against the library's half conv, the fp32 route on the upcast tensors for information) on the rows the route takes and writes
-profiles/grouped_mfma_half_bench_line.json; ``grouped_mfma_half_by_rule`` (both dtypes measured, every row passing) is the value
-``_fused.GROUPED_MFMA_HALF`` has to ship with.
+profiles/grouped_mfma_wgrad_half_bench_line.json.  A step is measured with ``_fused.GROUPED_MFMA_WGRAD_HALF`` off (the streaming
+qt_gconv2d_grad_weight_h) and on (qt_gmconv2d_grad_weight_h); ``grouped_mfma_wgrad_half_by_rule`` is the value that switch has to
+ship with (both dtypes measured, on every row the step's round range with it on wholly below the range with it off), and
+``grouped_mfma_half_by_rule`` (both dtypes measured, every row passing with the weight-gradient switch at that value) the value of
+``_fused.GROUPED_MFMA_HALF``.  ``wgrad`` times the weight gradient's two launches alone through ``ops``: one-term matrix cores
+against the streaming "_h" entry, the fp32 matrix-core entry on the upcast tensors for information.  ``--dtype ... --trace-steps``
+traces half steps with the weight-gradient switch off and then on.
 """
 import argparse
 import json
@@ -154,11 +159,14 @@ def child(index, rounds):
 
 def child_half(index, rounds, dtype):
     """``--dtype bf16|fp16``: one row the route takes, the layer as ``.to(dtype)`` on +-1 activations of that dtype.  Sides:
-    mfma_h   : ``_fused.GroupedMfmaConv2dFn`` on the half tensors (csrc/gconv_mfma_h.hip; qt_gconv2d_grad_weight_h in a step);
+    mfma_h   : ``_fused.GroupedMfmaConv2dFn`` on the half tensors (csrc/gconv_mfma_h.hip; qt_gconv2d_grad_weight_h in a step:
+               ``_fused.GROUPED_MFMA_WGRAD_HALF`` off);
+    mfma_h_wgrad : the same node with that switch on (a step only: qt_gmconv2d_grad_weight_h);
     torch    : F.conv2d(x, sign(W), b, groups=G) in the same dtype through torch: what these layers run with the switch off;
     mfma_f32 : for information, the fp32 node on the upcast tensors.
     ``floor_share`` = max(2 (|x| + |y|) bytes (x 3 for a step) / 8 TB/s, 2 macs (x 3) / 2.5 PFLOP/s) / the mfma_h median, and
-    ``floor`` says which of the two it is."""
+    ``floor`` says which of the two it is.  ``wgrad``: the weight gradient alone through ``ops`` — mfma_h (one-term matrix cores),
+    stream_h (qt_gconv2d_grad_weight_h), mfma_f32 (the fp32 matrix-core entry on the upcast tensors)."""
     import torch
     import torch.nn.functional as F
     from pytorch_quantize_impls_amd import _lib, ops
@@ -194,10 +202,18 @@ def child_half(index, rounds, dtype):
         assert torch.equal(forward["mfma_h"](x), want)
         go32 = torch.randn(want.shape, generator=g).to(dev)
     gos = {"mfma_h": go32.to(tdt), "torch": go32.to(tdt), "mfma_f32": go32}
-    calls = dict(_lib.call_counts)
-    forward["mfma_h"](leaves["mfma_h"]).backward(gos["mfma_h"])
-    used = {k_: v - calls.get(k_, 0) for k_, v in _lib.call_counts.items() if v != calls.get(k_, 0)}
-    assert used == {"qt_gmconv2d_h": 1, "qt_gmconv2d_grad_input_h": 1, "qt_gconv2d_grad_weight_h": 1}, used
+
+    def switched(fn, on):                                   # the backward reads the switch when it runs
+        def run():
+            _fused.GROUPED_MFMA_WGRAD_HALF = on
+            return fn()
+        return run
+
+    for on, gwt in ((False, "qt_gconv2d_grad_weight_h"), (True, "qt_gmconv2d_grad_weight_h")):
+        calls = dict(_lib.call_counts)
+        switched(lambda: forward["mfma_h"](leaves["mfma_h"]).backward(gos["mfma_h"]), on)()
+        used = {k_: v - calls.get(k_, 0) for k_, v in _lib.call_counts.items() if v != calls.get(k_, 0)}
+        assert used == {"qt_gmconv2d_h": 1, "qt_gmconv2d_grad_input_h": 1, gwt: 1}, used
 
     def fwd(r):
         def run():
@@ -213,6 +229,11 @@ def child_half(index, rounds, dtype):
             layer32.zero_grad(set_to_none=True)
         return run
 
+    def wgrad(r):
+        op = ops.grouped_conv2d_grad_weight if r == "stream_h" else ops.grouped_mfma_conv2d_grad_weight
+        xa, ga, lay = (x32, go32, layer32) if r == "mfma_f32" else (x, gos["mfma_h"], layer)
+        return lambda: op(xa, ga, lay.weight, *args, ops.STE_THRESHOLD, True)
+
     def run_us(fn, steps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -224,8 +245,11 @@ def child_half(index, rounds, dtype):
     nb, m = 2 * (x.numel() + want.numel()), want.numel() * (C // G) * k * k
     result = {"channels": C, "out_channels": Cout, "map": H, "stride": stride, "groups": G, "cin_g": C // G, "cout_g": Cout // G,
               "kernel": k, "dtype": dtype, "bytes": {"fwd": nb, "fwd_bwd": 3 * nb}, "macs": {"fwd": m, "fwd_bwd": 3 * m}}
-    for mode, make, mult in (("fwd", fwd, 1), ("fwd_bwd", step, 3)):
-        fns = {r: make(r) for r in forward}
+    leaves["mfma_h_wgrad"], gos["mfma_h_wgrad"], forward["mfma_h_wgrad"] = leaves["mfma_h"], gos["mfma_h"], forward["mfma_h"]
+    sides = {"fwd": ("mfma_h", "torch", "mfma_f32"), "fwd_bwd": ("mfma_h", "mfma_h_wgrad", "torch", "mfma_f32"),
+             "wgrad": ("mfma_h", "stream_h", "mfma_f32")}
+    for mode, make, mult in (("fwd", fwd, 1), ("fwd_bwd", step, 3), ("wgrad", wgrad, 1)):
+        fns = {r: switched(make(r), r == "mfma_h_wgrad") for r in sides[mode]}
         for fn in fns.values():
             for _ in range(2):
                 fn()
@@ -235,20 +259,26 @@ def child_half(index, rounds, dtype):
                 samples[r].append(run_us(fn, 10))
         result[mode] = {r: {"median_us": round(sorted(v)[len(v) // 2], 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1)}
                         for r, v in samples.items()}
-        floors = {"hbm": mult * nb / B.HBM_BYTES_PER_S, "bf16": 2 * mult * m / BF16_FLOPS}
+        floors = {"hbm": mult * nb / B.HBM_BYTES_PER_S, "bf16": 2 * mult * m / BF16_FLOPS}          # wgrad reads |x| + |go| once
         top = max(floors, key=floors.get)
         result[mode]["mfma_h"].update(floor=top, floor_share=round(floors[top] / (result[mode]["mfma_h"]["median_us"] * 1e-6), 3))
     print(json.dumps(result))
 
 
-def half_passes(s):
-    """The rule of ``GROUPED_HALF_MAX_CIN_G``: the step's round range wholly below the library's, the forward median not above it."""
-    return (s["fwd_bwd"]["mfma_h"]["max_us"] < s["fwd_bwd"]["torch"]["min_us"]
+def half_passes(s, side="mfma_h"):
+    """The rule of ``GROUPED_HALF_MAX_CIN_G``: the step's round range wholly below the library's, the forward median not above it.
+    ``side``: the step with the weight-gradient switch at the value it ships with."""
+    return (s["fwd_bwd"][side]["max_us"] < s["fwd_bwd"]["torch"]["min_us"]
             and s["fwd"]["mfma_h"]["median_us"] <= s["fwd"]["torch"]["median_us"])
 
 
+def half_wgrad_passes(s):
+    """The rule of ``GROUPED_MFMA_WGRAD``: the step's round range with the switch on wholly below the range with it off."""
+    return s["fwd_bwd"]["mfma_h_wgrad"]["max_us"] < s["fwd_bwd"]["mfma_h"]["min_us"]
+
+
 def main_half(a):
-    """Both dtypes on every row of SHAPES the route takes; profiles/grouped_mfma_half_bench_line.json."""
+    """Both dtypes on every row of SHAPES the route takes; profiles/grouped_mfma_wgrad_half_bench_line.json."""
     rows = [i for i, (C, _H, _s, G, _k, Cout) in enumerate(SHAPES) if (Cout // G) % 16 == 0]
     shapes = []
     for dtype in (a.dtype if a.dtype != "both" else "bf16,fp16").split(","):
@@ -261,21 +291,28 @@ def main_half(a):
             print(json.dumps(shapes[-1]), file=sys.stderr)
     from pytorch_quantize_impls_amd.functions import _fused
     line = {"bench": "grouped_mfma_half", "batch": B.BATCH, "rounds": a.rounds, "layout": "NCHW", "hbm_bytes_per_s": B.HBM_BYTES_PER_S,
-            "bf16_flops": BF16_FLOPS, "shapes": shapes, "shape_passes_rule": [half_passes(s) for s in shapes],
-            "grouped_mfma_half_by_rule": all(half_passes(s) for s in shapes) and {s["dtype"] for s in shapes} == {"bf16", "fp16"},
-            "grouped_mfma_half_shipped": bool(_fused.GROUPED_MFMA_HALF)}
+            "bf16_flops": BF16_FLOPS, "shapes": shapes}
+    both = {s["dtype"] for s in shapes} == {"bf16", "fp16"}
+    wgrad_on = both and all(half_wgrad_passes(s) for s in shapes)
+    side = "mfma_h_wgrad" if wgrad_on else "mfma_h"
+    line.update(wgrad_passes_rule=[half_wgrad_passes(s) for s in shapes], grouped_mfma_wgrad_half_by_rule=wgrad_on,
+                grouped_mfma_wgrad_half_shipped=bool(_fused.GROUPED_MFMA_WGRAD_HALF), step_side_of_the_half_rule=side,
+                shape_passes_rule=[half_passes(s, side) for s in shapes],
+                grouped_mfma_half_by_rule=both and all(half_passes(s, side) for s in shapes),
+                grouped_mfma_half_shipped=bool(_fused.GROUPED_MFMA_HALF))
     text = json.dumps(line)
-    out = a.out if a.out != DEFAULT_OUT else os.path.join(B.ROOT, "profiles", "grouped_mfma_half_bench_line.json")
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(B.ROOT, "profiles", "grouped_mfma_wgrad_half_bench_line.json")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "w") as fh:
         fh.write(text + "\n")
     print(text)
 
 
-def trace_steps(steps):
+def trace_steps(steps, dtype=None):
     """For ``rocprofv3 --kernel-trace --stats -- python tools/bench_grouped_mfma.py --trace-steps 3``: every row the route takes, in
     one process, ``steps`` training steps with the weight-gradient switch off and then on.  Kernel times instead of wall-time
-    differences: the rows differ in their grids, the two sides in the grad_weight kernels' names."""
+    differences: the rows differ in their grids, the two sides in the grad_weight kernels' names.  ``dtype`` ("bf16" | "fp16"): the
+    layer and the activation in that dtype, the switch ``GROUPED_MFMA_WGRAD_HALF``."""
     import torch
     from pytorch_quantize_impls_amd import ops
     from pytorch_quantize_impls_amd.functions import _fused
@@ -283,13 +320,14 @@ def trace_steps(steps):
 
     dev = torch.device("cuda:0")
     for C, H, stride, G, k, Cout in SHAPES:
-        layer = BinConv2d(C, Cout, k, stride=stride, padding=k // 2, groups=G).to(dev)
+        tdt = {None: torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[dtype]
+        layer = BinConv2d(C, Cout, k, stride=stride, padding=k // 2, groups=G).to(dev).to(tdt)
         args = (layer.stride, layer.padding, layer.dilation, G)
-        xg = torch.where(torch.rand(B.BATCH, C, H, H) < 0.5, -1.0, 1.0).to(dev).requires_grad_(True)
+        xg = torch.where(torch.rand(B.BATCH, C, H, H) < 0.5, -1.0, 1.0).to(dev).to(tdt).requires_grad_(True)
         if not ops.grouped_mfma_applicable(xg.shape, layer.weight.shape, *args):
             continue
         for on in (False, True):
-            _fused.GROUPED_MFMA_WGRAD = on
+            _fused.GROUPED_MFMA_WGRAD = _fused.GROUPED_MFMA_WGRAD_HALF = on
             for _ in range(steps):
                 y = _fused.GroupedMfmaConv2dFn.apply(xg, layer.weight, layer.bias, "binary", None, ops.STE_THRESHOLD, args)
                 y.backward(torch.ones_like(y))
@@ -320,7 +358,7 @@ def main():
                     help="the half-precision route against the library's half conv (both: what the switch GROUPED_MFMA_HALF needs)")
     a = ap.parse_args()
     if a.trace_steps is not None:
-        return trace_steps(a.trace_steps)
+        return trace_steps(a.trace_steps, a.dtype)
     if a.child is not None:
         return child_half(a.child, a.rounds, a.dtype) if a.dtype else child(a.child, a.rounds)
     if a.dtype:
