@@ -1826,6 +1826,55 @@ int qt_gconv2d_codes_f32(const int8_t* x_plane, int64_t ldx_bytes, int64_t in_ha
                          int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                          int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, qt_stream_t stream);
 
+/* Grouped convolution on int8 code planes, on the matrix cores: a grouped DorefaConv2d with 16 or 32 input channels per group — the
+ * grouped 3 x 3 of ResNeXt's last stages — inside the fused DoReFa inference chain, on v_mfma_i32_16x16x64_i8.  One launch each; no
+ * allocation, no synchronisation, no separate weight pack; csrc/gconv_codes_mfma.hip, DESIGN.md "Grouped convs on code planes, on
+ * the matrix cores".
+ *
+ * The argument lists are those of qt_gconv2d_codes / qt_gconv2d_codes_f32 with ONE addition: the sibling signature has no place
+ * for the weight's scale and bit width, so both entries take a trailing `const float* w_scale, int w_bits` in front of `stream`.
+ *
+ * Input.  x_plane, ldx_bytes, in_halo_*, inv_n as for qt_gconv2d_codes: an int8 NHWC code plane over C = G cin_g channels whose halo
+ * is never read (taps outside the H x W image contribute 0).  w is the fp32 EVAL image [G cout_g, cin_g, kh, kw] of a w_bits-bit
+ * DoReFa weight, turned into int8 weight bytes inside the launch:
+ *   w_bits == 1        the image is +-E: the byte is the sign (w < 0 ? -1 : +1); the scale E is read from *w_scale (fp32, device
+ *                      memory, required), as scale_dev of qt_conv2d_implicit_codes;
+ *   2 <= w_bits <= 7   the byte is the integer level rint(fl(w (2^w_bits - 1))), |level| <= 127 (anything else: byte 0); the
+ *                      scale is fl(1 / (2^w_bits - 1)); w_scale is not read.
+ *
+ * Value.  S = the int32 sum of code x weight byte over the group's cin_g kh kw terms (|S| <= 127 127 288 < 2^24: (float)S is exact
+ * and independent of tiling and order).  y is the value the dense code conv (qt_conv2d_implicit, elem 1) states for the same
+ * operands, per group:
+ *   s = fl(inv_n * *w_scale)  (w_bits == 1)   or   fl(inv_n * fl(1 / (2^w_bits - 1)))  (w_bits >= 2);
+ *   y[n, g cout_g + j, ho, wo] = fl(fl((float)S * s) + bias[g cout_g + j])   (bias NULL: + 0.0f), nothing contracted.
+ * A grouped layer therefore equals the concatenation of its groups run through the dense code conv.
+ *
+ * Output forms — exactly those of qt_gconv2d_codes (code epilogue of csrc/codes_epilogue.h: folded or device-form BatchNorm, relu in
+ * {0, 1}, q = rint(fl((2^bit_width - 1) t)) unclamped, the overflow flag; EVERY byte of the plane written with dword stores, pad
+ * bytes, channels >= G cout_g and the border as zero) and of qt_gconv2d_codes_f32 (y by its element strides, dense NCHW or
+ * channels-last; NaN everywhere if *overflow is raised).
+ *
+ * Window: G >= 8, cin_g in {16, 32}, cout_g in {16, 32, 48}, a 1 x 1 or 3 x 3 kernel, stride 1 or 2 (equal on both axes), dilation
+ * 1, padding 0 or 1 per axis, halos <= 64, fewer than 2^31 pixel rows in either plane (and elements of y), ldc_bytes < 2^31; beyond
+ * it QT_ERR_UNSUPPORTED.  Validation before anything is enqueued, in this order:
+ *   1. a negative halo, a negative size, a kernel / stride / dilation below 1, a negative padding: QT_ERR_INVALID_ARG.
+ *   2. N, G, H or W zero: QT_OK, nothing is written.
+ *   3. outside the window: QT_ERR_UNSUPPORTED (a kernel that does not fit the padded image: QT_ERR_INVALID_ARG).
+ *   4. a null tensor (bias and bn_stats may be null; overflow only for the fp32 form), w_bits outside 1 .. 7, w_bits == 1 without
+ *      w_scale, strides that are no dense layout, bit_width outside 2 .. 8, relu outside {0, 1}, ldx_bytes / ldc_bytes below the
+ *      bounds of qt_gconv2d_codes: QT_ERR_INVALID_ARG; then a float or flag pointer that is not 4-byte aligned, ldx_bytes % 16 or
+ *      ldc_bytes % 16 != 0, a plane that is not 16-byte aligned: QT_ERR_ALIGNMENT. */
+int qt_gmconv2d_codes(const int8_t* x_plane, int64_t ldx_bytes, int64_t in_halo_h, int64_t in_halo_w, float inv_n, const float* w,
+                      const float* bias, const float* alpha, const float* beta, const float* bn_stats, int relu, int bit_width,
+                      int8_t* codes, int64_t ldc_bytes, int64_t out_halo_h, int64_t out_halo_w, int32_t* overflow, int64_t N,
+                      int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw,
+                      int dh, int dw, const float* w_scale, int w_bits, qt_stream_t stream);
+int qt_gmconv2d_codes_f32(const int8_t* x_plane, int64_t ldx_bytes, int64_t in_halo_h, int64_t in_halo_w, float inv_n,
+                          const float* w, const float* bias, const int32_t* overflow, float* y, int64_t N, int64_t G, int64_t cin_g,
+                          int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                          int64_t ys_n, int64_t ys_c, int64_t ys_h, int64_t ys_w, const float* w_scale, int w_bits,
+                          qt_stream_t stream);
+
 /* BatchNorm + shortcut + sign: the activation between two binarised convs of a residual block,
  *   s = BatchNorm(conv) + shortcut;  next conv input = sign([Hardtanh](s));  next shortcut = s
  * in ONE streaming pass over the fp32 conv result.  One launch; no allocation, no synchronisation, no atomics; capturable;

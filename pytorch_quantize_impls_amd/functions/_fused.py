@@ -935,6 +935,63 @@ def _grouped_codes_admission(layer, act, what: str) -> None:
                          "numeric zero padding and a shape inside the kernels' limits")
 
 
+#: module-by-module calls of streaming DoReFa convs that ran on the code tag of their fp32 input, by family ("grouped_mfma":
+#: ``dorefa_grouped_mfma_codes_forward``); the tests read it
+STREAMING_CODES_STATS: Counter = Counter()
+
+
+def _grouped_mfma_codes_window(layer, shape) -> bool:
+    """``layer`` (a DorefaConv2d) on a DoReFa activation of ``shape`` is a grouped conv the matrix-core code kernel takes: at least
+    ``GROUPED_MFMA_MIN_GROUPS`` groups of 16 or 32 input channels inside ``ops.grouped_mfma_codes_applicable``, a weight whose
+    integer levels fit int8 (bit_width 1 ... ``LEVEL_INT8_BITS``)."""
+    return (layer.padding_mode == "zeros" and not isinstance(layer.padding, str) and len(shape) == 4
+            and layer.groups >= GROUPED_MFMA_MIN_GROUPS and 1 <= int(layer.bit_width) <= LEVEL_INT8_BITS
+            and layer.weight.dtype == torch.float32
+            and ops.grouped_mfma_codes_applicable(shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups))
+
+
+def grouped_mfma_codes_scale(layer):
+    """The device scalar E of a 1-bit eval image (+-E: |w| == E everywhere after eval()), None for k-bit levels."""
+    return layer._eval_planes(lambda w2: w2.abs().amax(), key="E") if int(layer.bit_width) == 1 else None
+
+
+def codes_grouped_mfma_conv2d(layer, act):
+    """Eval-mode grouped DorefaConv2d inside ``_grouped_mfma_codes_window`` on a CodeActivation: the fp32 result from one launch on the
+    code plane (ops.grouped_mfma_conv2d_from_codes) — what such a deferred conv materialises to when its chain cannot run fused.
+    Layout and range flag as ``codes_grouped_conv2d``."""
+    if layer.training:
+        raise RuntimeError("CodeActivation inputs are an inference feature: call .eval() first")
+    if not _grouped_mfma_codes_window(layer, act.shape) or not layer._eval_on_grid():
+        raise ValueError(f"matrix-core grouped conv on codes needs at least {GROUPED_MFMA_MIN_GROUPS} groups of 16 or 32 input "
+                         "channels, an on-grid weight of 1 ... 7 bits and a shape inside ops.grouped_mfma_codes_applicable")
+    return ops.grouped_mfma_conv2d_from_codes(act.codes, act.shape, layer.weight.detach(), layer.bias, layer.stride, layer.padding,
+                                              layer.dilation, layer.groups, in_halo=act.halo,
+                                              channels_last=bool(act.source_channels_last), flagged=not ops._cfg("ASSUME_CODES_FIT"),
+                                              bit_width_w=layer.bit_width, scale_dev=grouped_mfma_codes_scale(layer))
+
+
+def dorefa_grouped_mfma_codes_forward(layer, input):
+    """Module-by-module form of the same conv: eval mode, no autograd, an fp32 device ``input`` that carries the int8 code tag of
+    the quantiser that wrote it.  The value of ``codes_grouped_mfma_conv2d`` (one launch, qt_gmconv2d_codes_f32) with the range
+    flag folded into the bias as on the dense int8 route; None when the tag is missing or unusable (the caller goes on)."""
+    if not (_streaming_f32_common(layer, input) and input.numel() > 0 and not layer.training
+            and not autograd_records(input, layer.weight, layer.bias) and _grouped_mfma_codes_window(layer, input.shape)):
+        return None
+    codes = packed.lookup_codes(input, packed.NHWC)
+    N_, C, H, W = (int(v) for v in input.shape)
+    if codes is None or codes.K != C or codes.rows != N_ * H * W:
+        return None
+    ok, flag = codes_route(codes, layer.weight)
+    if not ok:
+        return None
+    Cout = int(layer.weight.shape[0])
+    STREAMING_CODES_STATS["grouped_mfma"] += 1
+    return ops.grouped_mfma_conv2d_from_codes(codes, (N_, C, H, W), layer.weight.detach(),
+                                              poison_bias(layer.bias, flag, Cout, input.device), layer.stride, layer.padding,
+                                              layer.dilation, layer.groups, channels_last=ops._dw_channels_last(input), flagged=False,
+                                              bit_width_w=layer.bit_width, scale_dev=grouped_mfma_codes_scale(layer))
+
+
 def _packed_streaming_conv2d(fam, layer, act):
     """A deferred streaming conv (``fam``: ``_DEPTHWISE`` | ``_GROUPED``) materialised from the bit planes of its input."""
     if layer.training:

@@ -174,6 +174,13 @@ class DorefaConv2d(_DorefaLayer, torch.nn.Conv2d, QLayer):
             # at least GROUPED_MIN_GROUPS groups of a few input channels, any bit_width: the grouped kernels in the same way
             w = self.weight_op.forward(self.weight) if self.training else self.weight
             return _fused.GroupedConv2dFn.apply(input, w, self.bias, "raw", None, 0.0, args)
+        if lazy.DEFER_GROUPED_MFMA_CODES and self.groups != 1 and not isinstance(input, _CodeActivation):
+            # at least GROUPED_MFMA_MIN_GROUPS groups of 16 or 32 input channels, weights of 1 ... 7 bits, eval mode without
+            # autograd, an input that carries its quantiser's int8 codes: the int8 matrix cores on the code plane — the
+            # arithmetic the deferred chain has, so both give the same bits
+            y = _fused.dorefa_grouped_mfma_codes_forward(self, input)
+            if y is not None:
+                return y
         if self._w1_route(input):
             if self.training:
                 return _fused.DorefaW1Conv2dFn.apply(input, self.weight, self.bias, args)

@@ -581,6 +581,36 @@ class FusedGroupedDorefaBnQuant(_FusedStreamingDorefaBnQuant):
                              "channels can be fused (depthwise: FusedDepthwiseDorefaBnQuant; ungrouped: FusedDorefaConvBnQuant)")
 
 
+class FusedGroupedMfmaDorefaBnQuant(_FusedStreamingDorefaBnQuant):
+    """``FusedGroupedDorefaBnQuant`` for at least ``_fused.GROUPED_MFMA_MIN_GROUPS`` groups of 16 or 32 input channels (16, 32 or 48
+    output channels each, 1 x 1 or 3 x 3, ``ops.grouped_mfma_codes_applicable``) and a weight of 1 ... ``_fused.LEVEL_INT8_BITS``
+    bits whose eval image is on the quantiser's grid: ONE launch on the int8 matrix cores (qt_gmconv2d_codes) reads the int8 code
+    plane of a CodeActivation (any halo: it is never read), forms the weight bytes from the stored image (the sign of +-E, or the
+    integer levels), sums exact integers and writes the next layer's code plane with ``out_halo`` as its zero border.  The value in
+    front of the BatchNorm is that of the dense code conv applied group by group.  No residual, no ReLU in front of the BatchNorm."""
+    _noun, _takes_groups = "matrix-core grouped", True
+    _applicable = staticmethod(ops.grouped_mfma_codes_applicable)
+
+    def __init__(self, conv, bn, bit_width: int, relu=True, out_halo=(0, 0), fold=None):
+        super().__init__(conv, bn, bit_width, relu, out_halo, fold)
+
+    @staticmethod
+    def _admit(conv):
+        from ..functions import _fused
+        if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+            raise ValueError("only zero-padded convs with numeric padding can be fused")
+        if conv.groups < _fused.GROUPED_MFMA_MIN_GROUPS or int(conv.weight.shape[1]) not in ops.GMC_CIN_G:
+            raise ValueError(f"only convs with at least {_fused.GROUPED_MFMA_MIN_GROUPS} groups of 16 or 32 input channels can be fused "
+                             "(2 ... 8 channels per group: FusedGroupedDorefaBnQuant)")
+        if not 1 <= int(conv.bit_width) <= _fused.LEVEL_INT8_BITS:
+            raise ValueError(f"the weight's integer levels fit int8 for 1 <= bit_width <= {_fused.LEVEL_INT8_BITS}")
+
+    def _conv2d_codes(self, codes, shape, weight, bias, epi, stride, padding, dilation, groups, in_halo=(0, 0)):
+        from ..functions import _fused
+        return ops.grouped_mfma_conv2d_codes(codes, shape, weight, bias, epi, stride, padding, dilation, groups, in_halo=in_halo,
+                                             bit_width_w=self.conv.bit_width, scale_dev=_fused.grouped_mfma_codes_scale(self.conv))
+
+
 class CodeMaxPool(torch.nn.Module):
     """MaxPool2d on a CodeActivation (the reference's DoReFa CNNs pool AFTER the quantiser,
     models/samples/AlexNet_Dorefa.py:38-41): the max of the int8 codes, bit-identical to pooling the fp32 image.
@@ -1336,6 +1366,30 @@ def fuse_sequential_training(seq: torch.nn.Sequential) -> torch.nn.Sequential:
 _PLANE_PRODUCERS = (FusedConvPoolBnSign, PackedMaxPool, FusedDepthwiseBnSign, FusedGroupedBnSign)     # subclasses included
 
 
+#: the modules whose output is a CodeActivation: what a block that reads code planes may stand behind in ``fuse_sequential``
+_CODE_PRODUCERS = (FusedBnDorefaQuant, FusedDorefaConvBnQuant, _FusedStreamingDorefaBnQuant, CodeMaxPool)
+
+
+def _grouped_mfma_code_run(mods, i, fold):
+    """(FusedGroupedMfmaDorefaBnQuant, modules consumed) for the run [DorefaConv2d, BatchNorm2d, ReLU?, nnDorefaQuant(k)] that starts
+    at ``mods[i]`` when its conv has 16 or 32 input channels per group and the block admits it; (None, 0) otherwise."""
+    from .dorefa_layers import DorefaConv2d
+    conv = mods[i]
+    if not (isinstance(conv, DorefaConv2d) and conv.groups > 1 and int(conv.weight.shape[1]) in ops.GMC_CIN_G and i + 2 < len(mods)
+            and isinstance(mods[i + 1], torch.nn.BatchNorm2d)):
+        return None, 0
+    j = i + 2
+    relu = isinstance(mods[j], torch.nn.ReLU)
+    j += int(relu)
+    bits = getattr(getattr(mods[j], "core", None), "_qt_quant_bits", None) if j < len(mods) else None
+    if bits is None:
+        return None, 0
+    try:
+        return FusedGroupedMfmaDorefaBnQuant(conv, mods[i + 1], bits, relu=relu, fold=fold), j + 1 - i
+    except ValueError:
+        return None, 0
+
+
 def _is_det_binary_connect(m):
     return isinstance(m, _FunctionModule) and m.core is BinaryConnectDeterministic
 
@@ -1358,6 +1412,14 @@ def fuse_sequential(seq: torch.nn.Sequential, fuse_conv: bool = False, packed_po
     while i < len(mods):
         j = i
         conv = None
+        if fuse_conv and out and isinstance(out[-1], _CODE_PRODUCERS):
+            # grouped DorefaConv2d, 16 / 32 channels per group -> BatchNorm2d -> [ReLU] -> nnDorefaQuant(k) behind a producer of code
+            # planes: one FusedGroupedMfmaDorefaBnQuant; a run the block declines stays the un-fused modules
+            blk, used = _grouped_mfma_code_run(mods, i, fold)
+            if blk is not None:
+                out.append(blk)
+                i += used
+                continue
         if fuse_conv and isinstance(mods[j], (BinConv2d, TerConv2d, XNORConv2d)) and j + 1 < len(mods):
             conv, j = mods[j], j + 1
         pool = None

@@ -152,6 +152,16 @@ DEFER_GROUPED_CODES = True
 #: existing suites pass with it on.  False = every call runs exactly as without this mechanism (``grouped_mfma_deferred()`` switches
 #: it for a block).
 DEFER_GROUPED_MFMA = True
+#: grouped DorefaConv2d with ``groups >= _fused.GROUPED_MFMA_MIN_GROUPS``, 16 or 32 input channels per group and a weight of 1 ...
+#: ``_fused.LEVEL_INT8_BITS`` bits (shapes ``ops.grouped_mfma_codes_applicable`` takes) joins the DoReFa code chain — needs
+#: ``DEFER_CODES`` as well: the layer defers, reads its producer's int8 code plane and runs as
+#: ``layers.fused.FusedGroupedMfmaDorefaBnQuant``, one launch on the int8 matrix cores (qt_gmconv2d_codes) from codes to the next
+#: layer's codes; called module by module on a code-tagged fp32 tensor it computes its fp32 result with the same kernel
+#: (qt_gmconv2d_codes_f32) instead of the dense library.  Set by the shipping rule of its siblings (DESIGN.md "Grouped convs on code
+#: planes, on the matrix cores"): on every measured row the deferred triple's round range lies below the eager one's (1.2x at the
+#: 1 x 1, the deciding row, 1.6x - 3.8x at 3 x 3; profiles/grouped_mfma_codes_chain_bench_line.json) and the existing suites pass
+#: with it on.  False = every call runs exactly as without this mechanism (``grouped_mfma_deferred()`` switches it for a block).
+DEFER_GROUPED_MFMA_CODES = True
 #: ``bn(conv(...)) + shortcut`` on a BinConv2d / TerConv2d chain (the residual block of a binarised ResNet) is recorded and runs as
 #: ``layers.fused.FusedConvBnAddSign``: conv to fp32, then one launch (qt_bn_add_sign_f32) for BatchNorm (device arithmetic, verified on
 #: a probe) + shortcut + [Hardtanh] + sign that writes the next conv's operand and the fp32 sum — the next block's shortcut (DESIGN.md
@@ -250,14 +260,15 @@ def grouped_deferred(on: bool = True):
 
 @contextlib.contextmanager
 def grouped_mfma_deferred(on: bool = True):
-    """Defer grouped sign convs with 16 or 32 input channels per group (``DEFER_GROUPED_MFMA``) inside the block; process-wide,
-    restores the previous setting."""
-    global DEFER_GROUPED_MFMA
+    """Defer grouped sign convs (``DEFER_GROUPED_MFMA``) and grouped DoReFa convs (``DEFER_GROUPED_MFMA_CODES``) with 16 or 32 input
+    channels per group inside the block; process-wide, restores the previous settings."""
+    global DEFER_GROUPED_MFMA, DEFER_GROUPED_MFMA_CODES
     prev, DEFER_GROUPED_MFMA = DEFER_GROUPED_MFMA, bool(on)
+    prev_codes, DEFER_GROUPED_MFMA_CODES = DEFER_GROUPED_MFMA_CODES, bool(on)
     try:
         yield
     finally:
-        DEFER_GROUPED_MFMA = prev
+        DEFER_GROUPED_MFMA, DEFER_GROUPED_MFMA_CODES = prev, prev_codes
 
 
 @contextlib.contextmanager
@@ -362,6 +373,8 @@ class _Node:
                     from .functions import _fused
                     if self.layer.groups == self.layer.in_channels:
                         y = _fused.codes_depthwise_conv2d(self.layer, self.input)
+                    elif int(self.layer.weight.shape[1]) in ops.GMC_CIN_G:
+                        y = _fused.codes_grouped_mfma_conv2d(self.layer, self.input)
                     else:
                         y = _fused.codes_grouped_conv2d(self.layer, self.input)
                 else:
@@ -731,7 +744,8 @@ def _code_block(layer, bn, bit_width, relu, halo):
     blk = per.get(key)
     if blk is None:
         make = (fused.FusedDorefaConvBnQuant if layer.groups == 1 else
-                fused.FusedDepthwiseDorefaBnQuant if layer.groups == layer.in_channels else fused.FusedGroupedDorefaBnQuant)
+                fused.FusedDepthwiseDorefaBnQuant if layer.groups == layer.in_channels else
+                fused.FusedGroupedMfmaDorefaBnQuant if int(layer.weight.shape[1]) in ops.GMC_CIN_G else fused.FusedGroupedDorefaBnQuant)
         blk = make(layer, _BnView(rm, rv, w, b, eps), bit_width, relu=relu, out_halo=halo, fold="device")
         per[key] = blk
         while len(per) > _MAX_BLOCKS_PER_LAYER:
@@ -1375,9 +1389,12 @@ def _dorefa_can_defer(layer, input) -> bool:
                 return False
         else:
             from .functions import _fused
-            if not (DEFER_GROUPED_CODES and layer.groups >= _fused.GROUPED_MIN_GROUPS
-                    and 2 <= int(w.shape[1]) <= _fused.GROUPED_MAX_CIN_G
-                    and ops.grouped_codes_applicable(shape, tuple(w.shape), layer.stride, layer.padding, layer.dilation, layer.groups)):
+            if not ((DEFER_GROUPED_CODES and layer.groups >= _fused.GROUPED_MIN_GROUPS
+                     and 2 <= int(w.shape[1]) <= _fused.GROUPED_MAX_CIN_G
+                     and ops.grouped_codes_applicable(shape, tuple(w.shape), layer.stride, layer.padding, layer.dilation, layer.groups))
+                    # ... or 16 / 32 channels per group in at least GROUPED_MFMA_MIN_GROUPS groups, a weight of 1 ... 7 bits: the
+                    # matrix-core code kernel, which the module-by-module call runs as well
+                    or (DEFER_GROUPED_MFMA_CODES and _fused._grouped_mfma_codes_window(layer, shape))):
                 return False
     elif layer.bit_width != 1:
         return False
@@ -1418,7 +1435,7 @@ def dorefa_conv_forward(layer, input):
     if defer and not isinstance(input, packed.CodeActivation) and isinstance(input, torch.Tensor) and input.is_cuda \
             and input.dtype == torch.float32 and input.dim() == 4 and not torch.is_grad_enabled() and not layer.training \
             and (layer.bit_width == 1 if layer.groups == 1 else
-                 DEFER_DEPTHWISE_CODES if layer.groups == layer.in_channels else DEFER_GROUPED_CODES):
+                 DEFER_DEPTHWISE_CODES if layer.groups == layer.in_channels else (DEFER_GROUPED_CODES or DEFER_GROUPED_MFMA_CODES)):
         codes = packed.lookup_codes(input, packed.NHWC)
         N, C, H, W = (int(v) for v in input.shape)
         if codes is not None and codes.K == C and codes.rows == N * H * W:

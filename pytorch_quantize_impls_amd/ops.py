@@ -4198,6 +4198,22 @@ def grouped_mfma_planes_applicable(x_shape, w_shape, stride, padding, dilation, 
             and int(w_shape[0]) // int(groups) in GMP_COUT_G)
 
 
+#: input / output channels per group the matrix-core grouped CODE kernel takes (csrc/gconv_codes_mfma.hip): a K block of the int8
+#: MFMA is 16 channels
+GMC_CIN_G = (16, 32)
+GMC_COUT_G = (16, 32, 48)
+
+
+def grouped_mfma_codes_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
+    """``grouped_mfma_applicable`` with cin_g in ``GMC_CIN_G``, cout_g in ``GMC_COUT_G`` and fewer than 2^31 pixel rows: the grouped
+    convs that run on the int8 code plane of a DoReFa activation on the int8 matrix cores (``grouped_mfma_conv2d_codes`` /
+    ``grouped_mfma_conv2d_from_codes``).  Disjoint from the 2 ... 8 channels per group of the fused grouped code route.  A pure
+    function of the shapes: like ``grouped_codes_applicable`` it knows neither the halos nor the number of groups the entry asks
+    for (at least 8: QT_ERR_UNSUPPORTED below that, raised by the wrapper)."""
+    return (grouped_mfma_applicable(x_shape, w_shape, stride, padding, dilation, groups) and int(w_shape[1]) in GMC_CIN_G
+            and int(w_shape[0]) // int(groups) in GMC_COUT_G)
+
+
 def _dw_channels_last(t: torch.Tensor) -> bool:
     return t.is_contiguous(memory_format=torch.channels_last) and not t.is_contiguous()
 
@@ -4348,6 +4364,10 @@ _GMW = _GM._replace(entry={"f32": _GM.entry["f32"], "grad_input_f32": _GM.entry[
 #: the two plane entries alone
 _GMP = _Streaming({"sign": "qt_gmconv2d_sign", "bits_f32": "qt_gmconv2d_bits_f32"}, "matrix-core grouped", "G * cout_g",
                   _gm_geometry, _gmp_geometry, False)
+#: 16 or 32 input channels per group on the int8 code plane of a DoReFa activation, on the int8 matrix cores
+#: (csrc/gconv_codes_mfma.hip): the two code entries alone, which carry the weight's scale and bit width behind the geometry
+_GMC = _Streaming({"codes": "qt_gmconv2d_codes", "codes_f32": "qt_gmconv2d_codes_f32"}, "matrix-core grouped", "G * cout_g",
+                  _gm_geometry, _gm_geometry, False)
 #: most splits per group of that entry: the S_max of its error bound
 GM_WGRAD_MAX_SPLITS = _lib.DEFINES["QT_GM_WGRAD_MAX_SPLITS"]
 
@@ -4707,6 +4727,73 @@ def grouped_conv2d_from_codes(codes: CodePlanes, shape, weight: torch.Tensor, bi
     device."""
     return _streaming_conv2d_from_codes(_GC, codes, shape, weight, bias, stride, padding, dilation, groups, in_halo, channels_last, out,
                                         flagged)
+
+
+def _gmc_operands(codes, shape, weight, stride, padding, dilation, groups, in_halo, w_bits, w_scale):
+    """What the two matrix-core grouped code wrappers share: the checked plane, weight, geometry and weight scale."""
+    x_shape, halo = _dw_code_input(codes, shape, in_halo)
+    _require(weight, "weight")
+    if (weight.dim() == 4 and min(x_shape) > 0
+            and not grouped_mfma_codes_applicable(x_shape, weight.shape, stride, padding, dilation, groups)):
+        raise ValueError(f"not a grouped conv the matrix-core code kernel takes: input {tuple(x_shape)}, weight {tuple(weight.shape)}, "
+                         f"groups {groups}, stride {stride}, padding {padding}, dilation {dilation}")
+    w, geom, y_shape = _gc_geometry(x_shape, weight, stride, padding, dilation, groups)
+    if w.device != codes.device:
+        raise ValueError("input and weight are on different devices")
+    w_bits = int(w_bits)
+    if not 1 <= w_bits <= 7:
+        raise ValueError("the weight's integer levels fit int8 for 1 <= bit_width <= 7")
+    if w_bits == 1:
+        if w_scale is None:
+            raise ValueError("1-bit weights (+-E) need scale_dev = E, an fp32 device scalar")
+        w_scale = _require(w_scale, "scale_dev").reshape(1)
+        if w_scale.device != codes.device:
+            raise ValueError("scale_dev is on another device than the input")
+    else:
+        w_scale = None
+    return x_shape, halo, w, geom, y_shape, w_scale, w_bits
+
+
+def grouped_mfma_conv2d_codes(codes: CodePlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor], epi: CodeEpilogue,
+                              stride=1, padding=0, dilation=1, groups: int = 1, in_halo=(0, 0), out: Optional[torch.Tensor] = None,
+                              bit_width_w: int = 1, scale_dev: Optional[torch.Tensor] = None) -> CodePlanes:
+    """``grouped_conv2d_codes`` for at least 8 groups of 16 or 32 input channels (``grouped_mfma_codes_applicable``), ONE launch on
+    the int8 matrix cores (qt_gmconv2d_codes): a group's tap is one aligned 16-byte piece of the code plane; ``weight`` is the fp32
+    eval image of a ``bit_width_w``-bit DoReFa weight, whose bytes — the sign of +-E with ``scale_dev`` = E (1 bit), the integer
+    levels (2 ... 7 bits) — are formed inside the launch; the sums are exact integers and the value is that of ``conv2d_codes``
+    applied group by group.  ``epi``, ``out``, ``in_halo`` and the result as ``grouped_conv2d_codes``."""
+    x_shape, (ihy, ihx), w, geom, y_shape, w_scale, w_bits = _gmc_operands(codes, shape, weight, stride, padding, dilation, groups,
+                                                                          in_halo, bit_width_w, scale_dev)
+    dev = codes.device
+    bias, relu, alpha, beta, stats, (ohy, ohx), flag, out, rows, ldc = _streaming_code_epilogue(_GMC, epi, codes, bias, y_shape, dev, out)
+    N, Cout, Ho, Wo = y_shape
+    if N * Cout * Ho * Wo > 0:
+        with _on(dev):
+            _lib.call("qt_gmconv2d_codes", _p(codes.codes), int(codes.codes.shape[1]), ihy, ihx, float(codes.inv_n), _p(w), _p(bias),
+                      _p(alpha), _p(beta), _p(stats), relu, int(epi.bit_width), _p(out), ldc, ohy, ohx, _p(flag), *geom, _p(w_scale),
+                      w_bits, _stream(dev))
+    return CodePlanes(codes=out, rows=rows, K=Cout, inv_n=inv_levels(epi.bit_width), bit_width=int(epi.bit_width), overflow=flag)
+
+
+def grouped_mfma_conv2d_from_codes(codes: CodePlanes, shape, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1,
+                                   padding=0, dilation=1, groups: int = 1, in_halo=(0, 0), channels_last: bool = True,
+                                   out: Optional[torch.Tensor] = None, flagged: bool = True, bit_width_w: int = 1,
+                                   scale_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``grouped_conv2d_from_codes`` for the shapes of ``grouped_mfma_conv2d_codes``: the fp32 result — bit for bit that of
+    ``conv2d_codes`` applied group by group — in ``channels_last`` or NCHW storage or written into ``out`` (qt_gmconv2d_codes_f32,
+    one launch).  ``flagged``: a raised int8 range flag of the plane's chain makes every value NaN, on the device."""
+    x_shape, (ihy, ihx), w, geom, y_shape, w_scale, w_bits = _gmc_operands(codes, shape, weight, stride, padding, dilation, groups,
+                                                                          in_halo, bit_width_w, scale_dev)
+    dev = codes.device
+    bias = _check_bias(bias, y_shape[1], dev)
+    y = _streaming_result(out, y_shape, channels_last, w)
+    if y.numel() == 0:
+        return y
+    flag = codes.overflow if flagged else None
+    with _on(dev):
+        _lib.call("qt_gmconv2d_codes_f32", _p(codes.codes), int(codes.codes.shape[1]), ihy, ihx, float(codes.inv_n), _p(w), _p(bias),
+                  _p(flag), _p(y), *geom, *_dw_strides(y.shape, _dw_channels_last(y)), _p(w_scale), w_bits, _stream(dev))
+    return y
 
 
 def _streaming_conv2d_grad_input(fam: _Streaming, input_shape, weight, grad_output, stride, padding, dilation, groups, kind="raw",

@@ -57,6 +57,17 @@ profiles/grouped_mfma_bench_line.json inside ``ops.grouped_mfma_planes_applicabl
              qt_gmconv2d_f32 reads it, three library passes and a pack follow.
 ``bytes`` as for the sign family.  The line goes to profiles/grouped_mfma_chain_bench_line.json, the table between the
 ``grouped-mfma-chain-table`` markers; ``--kernel-times`` then times gp_kernel.
+
+``--family mfma_codes`` measures the DoReFa W1A4 triple of ``--family dorefa`` on the rows of ``--family mfma`` (16 or 32 input
+channels per group, inside ``ops.grouped_mfma_codes_applicable``), same protocol and byte count:
+  deferred : ``lazy.grouped_mfma_deferred(True)`` — ONE launch on the int8 matrix cores (qt_gmconv2d_codes) from the first pointwise
+             chain's code plane to the second pointwise conv's code plane;
+  eager    : ``lazy.grouped_mfma_deferred(False)`` — the path of the commit before the switch: the first chain materialises fp32, the
+             dense library computes the grouped conv, BatchNorm, ReLU and the quantiser are passes over fp32 tensors.
+The eager side sums in fp32 in the library's order, the deferred side exact integers: the two code planes may differ where a value
+sits on a rounding tie of the quantiser, so the sides are compared by the share of differing codes (recorded, below 1 %), not bit
+for bit.  The line goes to profiles/grouped_mfma_codes_chain_bench_line.json, the table between the
+``grouped-mfma-codes-chain-table`` markers; ``--kernel-times`` then times gq_kernel.
 """
 import argparse
 import json
@@ -88,7 +99,9 @@ FAMILIES = {"sign": {"mark": MARK, "out": "grouped_chain_bench_line.json", "kern
             "dorefa": {"mark": "grouped-codes-chain-table", "out": "grouped_codes_chain_bench_line.json", "kernel": "gc_codes_kernel",
                        "shapes": SHAPES},
             "mfma": {"mark": "grouped-mfma-chain-table", "out": "grouped_mfma_chain_bench_line.json", "kernel": "gp_kernel",
-                     "shapes": SHAPES_MFMA, "entries": ("qt_gmconv2d_sign", "qt_gmconv2d_f32"), "switch": "grouped_mfma_deferred"}}
+                     "shapes": SHAPES_MFMA, "entries": ("qt_gmconv2d_sign", "qt_gmconv2d_f32"), "switch": "grouped_mfma_deferred"},
+            "mfma_codes": {"mark": "grouped-mfma-codes-chain-table", "out": "grouped_mfma_codes_chain_bench_line.json",
+                           "kernel": "gq_kernel", "shapes": SHAPES_MFMA}}
 
 
 def algorithmic_bytes(C, H, stride, k, Co=None):
@@ -97,9 +110,9 @@ def algorithmic_bytes(C, H, stride, k, Co=None):
     return {"eager": 32 * x + 32 * y, "deferred": x // 4 + y // 2}
 
 
-def algorithmic_bytes_dorefa(C, H, stride, k):
+def algorithmic_bytes_dorefa(C, H, stride, k, Co=None):
     Ho = (H + 2 * (k // 2) - k) // stride + 1
-    x, y = BATCH * C * H * H, BATCH * C * Ho * Ho
+    x, y = BATCH * C * H * H, BATCH * (Co or C) * Ho * Ho
     return {"eager": 4 * x + 29 * y, "deferred": x + y}
 
 
@@ -197,14 +210,18 @@ def child(index, rounds, family="sign"):
     print(json.dumps(result))
 
 
-def child_dorefa(index, rounds):
+def child_dorefa(index, rounds, family="dorefa"):
     import torch
     import torch.nn as nn
     from pytorch_quantize_impls_amd import _lib, lazy
     from pytorch_quantize_impls_amd.functions import nnDorefaQuant
     from pytorch_quantize_impls_amd.layers import DorefaConv2d
 
-    C, H, stride, G, k = SHAPES[index]
+    wide = family == "mfma_codes"              # 16 / 32 channels per group: the matrix-core code kernel against the dense library
+    shape = FAMILIES[family]["shapes"][index]
+    C, H, stride, G, k = shape[:5]
+    Co = (shape + (C,))[5]                     # output channels of the grouped layer: C unless the shape names them
+    switch = lazy.grouped_mfma_deferred if wide else lazy.grouped_deferred
     dev = torch.device("cuda:0")
     torch.manual_seed(index)
     g = torch.Generator().manual_seed(index)
@@ -221,14 +238,14 @@ def child_dorefa(index, rounds):
         return [bn, nn.ReLU(), nnDorefaQuant(4)]
 
     triple = nn.Sequential(DorefaConv2d(C, C, 1, bit_width=1), *run(C, C),
-                           DorefaConv2d(C, C, k, stride=stride, padding=k // 2, groups=G, bit_width=1), *run(C, C // G * k * k),
-                           DorefaConv2d(C, C, 1, bit_width=1), *run(C, C))
+                           DorefaConv2d(C, Co, k, stride=stride, padding=k // 2, groups=G, bit_width=1), *run(Co, C // G * k * k),
+                           DorefaConv2d(Co, Co, 1, bit_width=1), *run(Co, Co))
     triple = triple.to(dev).to(memory_format=torch.channels_last).eval()
     with torch.no_grad():
         x = nnDorefaQuant(4)(torch.rand(BATCH, C, H, H, generator=g).to(dev).contiguous(memory_format=torch.channels_last))
 
     def forward(on):
-        with torch.no_grad(), lazy.grouped_deferred(on):
+        with torch.no_grad(), switch(on):
             out = triple(x)
             act = out._qt.force((0, 0))        # the code plane the next DoReFa layer would ask for
             assert act is not None
@@ -241,10 +258,17 @@ def child_dorefa(index, rounds):
     calls = dict(_lib.call_counts)
     b = sides["eager"]()
     used_off = {k_: v - calls.get(k_, 0) for k_, v in _lib.call_counts.items() if v != calls.get(k_, 0)}
-    assert torch.equal(a.codes, b.codes), "the two sides disagree"
+    differing = float((a.codes != b.codes).float().mean())
     assert int(a.overflow.item()) == 0 and int(b.overflow.item()) == 0 and int(a.codes.count_nonzero()) > 0
-    assert used_on.get("qt_gconv2d_codes") == 1 and "qt_gconv2d_f32" not in used_on, used_on
-    assert used_off.get("qt_gconv2d_f32") == 1 and "qt_gconv2d_codes" not in used_off, used_off
+    if wide:
+        # fp32 sums in the library's order against exact integers: codes differ only where a value sits on a rounding tie
+        assert differing < 0.01, f"the two sides disagree at {differing:.4f} of the codes"
+        assert used_on.get("qt_gmconv2d_codes") == 1 and "qt_gmconv2d_codes_f32" not in used_on, used_on
+        assert not [n for n in used_off if n.startswith("qt_gmconv2d")], used_off
+    else:
+        assert differing == 0.0, "the two sides disagree"
+        assert used_on.get("qt_gconv2d_codes") == 1 and "qt_gconv2d_f32" not in used_on, used_on
+        assert used_off.get("qt_gconv2d_f32") == 1 and "qt_gconv2d_codes" not in used_off, used_off
 
     def run_us(fn):
         torch.cuda.synchronize()
@@ -261,9 +285,11 @@ def child_dorefa(index, rounds):
     for _ in range(rounds):
         for s, fn in sides.items():
             samples[s].append(run_us(fn))
-    nbytes = algorithmic_bytes_dorefa(C, H, stride, k)
+    nbytes = algorithmic_bytes_dorefa(C, H, stride, k, Co)
     result = {"channels": C, "map": H, "stride": stride, "groups": G, "kernel": k, "bytes": nbytes,
               "launches": {"deferred": used_on, "eager": used_off}}
+    if wide:
+        result.update({"out_channels": Co, "codes_differing_share": round(differing, 6)})
     for s, v in samples.items():
         med = sorted(v)[len(v) // 2]
         result[s] = {"median_us": round(med, 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1),
@@ -304,7 +330,8 @@ def write_docs(text, mark=MARK):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
-    ap.add_argument("--family", choices=sorted(FAMILIES), default="sign", help="sign: BinConv2d triple (default); dorefa: DorefaConv2d triple; mfma: BinConv2d triple, 16 / 32 channels per group")
+    ap.add_argument("--family", choices=sorted(FAMILIES), default="sign", help="sign: BinConv2d triple (default); dorefa: DorefaConv2d triple; mfma: BinConv2d triple, 16 / 32 channels per group; "
+                                                                                   "mfma_codes: DorefaConv2d triple, 16 / 32 channels per group")
     ap.add_argument("--out", default=None, help="default: profiles/grouped_chain_bench_line.json (sign), "
                                                 "profiles/grouped_codes_chain_bench_line.json (dorefa)")
     ap.add_argument("--kernel-times", action="store_true", help="one more rocprofv3 --kernel-trace --stats pass per shape")
@@ -313,12 +340,12 @@ def main():
     ap.add_argument("--child", type=int, default=None)
     a = ap.parse_args()
     fam = FAMILIES[a.family]
-    dorefa = a.family == "dorefa"
-    kernel_name = "grouped code kernel" if dorefa else ("matrix-core plane kernel" if a.family == "mfma" else "grouped plane kernel")
+    dorefa = a.family in ("dorefa", "mfma_codes")
+    kernel_name = "matrix-core code kernel" if a.family == "mfma_codes" else "grouped code kernel" if dorefa else ("matrix-core plane kernel" if a.family == "mfma" else "grouped plane kernel")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", fam["out"])
     if a.child is not None:
-        return child_dorefa(a.child, a.rounds) if dorefa else child(a.child, a.rounds, a.family)
+        return child_dorefa(a.child, a.rounds, a.family) if dorefa else child(a.child, a.rounds, a.family)
     if a.from_json:
         with open(a.from_json) as fh:
             line = json.loads(fh.read().strip().splitlines()[-1])
@@ -349,6 +376,10 @@ def main():
         line.update({"bench": "grouped_codes_chain_resnext", "dtype": "float32 image of 4-bit codes, code-tagged", "layout": "channels_last"})
         del line["defer_grouped_shipped"]
         line["defer_grouped_codes_shipped"] = bool(lazy.DEFER_GROUPED_CODES)
+    if a.family == "mfma_codes":
+        line["bench"] = "grouped_mfma_codes_chain_resnext"
+        del line["defer_grouped_codes_shipped"]
+        line["defer_grouped_mfma_codes_shipped"] = bool(lazy.DEFER_GROUPED_MFMA_CODES)
     if a.family == "mfma":
         line["bench"] = "grouped_mfma_chain_resnext"
         del line["defer_grouped_shipped"]
