@@ -1519,6 +1519,45 @@ int qt_gmconv2d_describe(int op, int64_t N, int64_t G, int64_t cin_g, int64_t co
                          int sw, int ph, int pw, int dh, int dw, char* out, int cap);
 
 /* ------------------------------------------------------------------------------------------
+ * Grouped convolution on the matrix cores, wide groups: qt_gmconv2d_f32 / qt_gmconv2d_grad_input_f32 for cin_g and cout_g each
+ * one of 16, 24, 32, 40, 48, 64, every pair — the RegNet group widths and the 64 per group of ResNeXt-101 32x8d's last stage as
+ * BinConv2d / TerConv2d(groups = G).  csrc/gconv_wide_mfma.hip, DESIGN.md "Grouped convs on the matrix cores, wide groups": a
+ * workgroup still works inside ONE group, but neither a group's weights nor a tile's patch is resident in full; the reduction
+ * channels are walked in slices of at most 32 with the tile's accumulators in registers, and a slice of the weights serves a batch
+ * of tiles.
+ *
+ * Argument lists, operands, layouts, strides, `kind`, the validation order (steps 1 to 4) and the status codes are those of
+ * qt_gmconv2d_f32 / qt_gmconv2d_grad_input_f32 above; only the channel limit of step 3 differs.  The other limits are the same:
+ * a 1 x 1 or 3 x 3 kernel; stride 1 or 2, equal on both axes; dilation 1; padding 0 or 1 per axis; every tensor below 2^31
+ * elements; G cout_g <= QT_DW_MAX_CHANNELS.  The grid is G x splits (at most G + 1024 workgroups); dynamic LDS at most 64 KiB.
+ *
+ * Arithmetic: the contract above, word for word — the real operand split EXACTLY into three bf16 terms inside the launch, Q(w)
+ * exact in bf16, exact products, fp32 accumulation inside v_mfma_f32_16x16x32_bf16 in an order fixed by the shapes alone (no
+ * atomics: equal inputs give equal bits), the bias added once at the end:
+ *   |result - exact| <= (3 Kp + 1) 2^-23 (sum |x q| + |bias|),   Kp = the reduction length (cin_g kh kw forward, cout_g kh kw
+ *   backward) rounded up to a multiple of 32, at most + 31.
+ * The kernel pads the (channel block, tap) pairs of EACH reduction slice to its K chunk of four pairs (32 elements); the padding
+ * pairs are zero fragments on both sides, and adding an exact zero to an fp32 accumulator rounds nothing, so they do not enter Kp.
+ * Where the sum of |terms| stays below 2^24 units of a common power of two the result IS the exact sum.  Non-finite and
+ * out-of-range inputs: as above (not pinned).
+ *
+ * qt_gwconv2d_describe: how the forward (bwd = 0) or grad_input (bwd = 1) launch would run, as qt_gmconv2d_describe reports it
+ * for its entries (host arithmetic only; a null `out`, cap < 2 or another `bwd`: QT_ERR_INVALID_ARG): kernel, TR TC, tiles_r
+ * tiles_c, units, splits, batch (tiles that share one staging of a weight slice), npmax, scb (blocks of 8 reduction channels per
+ * slice), nslices, nopad (result channels padded to the column tile), lds_bytes, tr_shrunk tc_shrunk, grid, block.
+ * ---------------------------------------------------------------------------------------- */
+int qt_gwconv2d_f32(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t G, int64_t cin_g,
+                    int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                    int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w, int64_t ys_n, int64_t ys_c, int64_t ys_h,
+                    int64_t ys_w, int kind, qt_stream_t stream);
+int qt_gwconv2d_grad_input_f32(const float* go, const float* w, float* gx, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g,
+                               int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t gs_n,
+                               int64_t gs_c, int64_t gs_h, int64_t gs_w, int64_t xs_n, int64_t xs_c, int64_t xs_h, int64_t xs_w,
+                               int kind, qt_stream_t stream);
+int qt_gwconv2d_describe(int bwd, int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh,
+                         int sw, int ph, int pw, int dh, int dw, char* out, int cap);
+
+/* ------------------------------------------------------------------------------------------
  * Depthwise and grouped convolution on half-precision operands: the six entries above for bf16 / fp16 models
  * (model.bfloat16(), model.half(), fp32 models under torch.autocast), named by the "_h" convention of "Half-precision operands".
  *

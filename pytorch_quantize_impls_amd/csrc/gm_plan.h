@@ -152,9 +152,12 @@ inline GmGeom gmw_geom(int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int6
 }
 
 // Steps 1 to 3 of the documented validation order, shared by every entry: the sizes, the empty problem, the limits.  False: the
-// call ends with `rc`; true: Ho x Wo is the output map of a problem inside the window.
+// call ends with `rc`; true: Ho x Wo is the output map of a problem inside the window.  `wide`: the channel window of
+// gconv_wide_mfma.hip (cin_g and cout_g each one of 16, 24, 32, 40, 48, 64) in place of this family's.
+inline bool gm_wide_channels(int64_t c) { return c == 16 || c == 24 || c == 32 || c == 40 || c == 48 || c == 64; }
+
 inline bool gm_shape(int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph,
-                     int pw, int dh, int dw, int64_t& Ho, int64_t& Wo, int& rc) {
+                     int pw, int dh, int dw, int64_t& Ho, int64_t& Wo, int& rc, bool wide = false) {
     rc = QT_ERR_INVALID_ARG;
     if (N < 0 || G < 0 || cin_g < 1 || cout_g < 1 || H < 0 || W < 0 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || ph < 0 || pw < 0 ||
         dh < 1 || dw < 1)
@@ -165,7 +168,9 @@ inline bool gm_shape(int64_t N, int64_t G, int64_t cin_g, int64_t cout_g, int64_
         rc = QT_OK;
         return false;
     }
-    if ((cin_g != 16 && cin_g != 24 && cin_g != 32) || (cout_g & 15) || cout_g > GM_MAX_COUT_G) return false;
+    if (wide ? !(gm_wide_channels(cin_g) && gm_wide_channels(cout_g))
+             : (cin_g != 16 && cin_g != 24 && cin_g != 32) || (cout_g & 15) || cout_g > GM_MAX_COUT_G)
+        return false;
     if (!((kh == 1 && kw == 1) || (kh == 3 && kw == 3)) || sh != sw || sh > 2 || dh != 1 || dw != 1 || ph > 1 || pw > 1) return false;
     if (N >= GM_MAX_ELEMS || G >= GM_MAX_ELEMS || H >= GM_MAX_ELEMS || W >= GM_MAX_ELEMS) return false;
     const int64_t eh = H + 2 * (int64_t)ph - kh, ew = W + 2 * (int64_t)pw - kw;

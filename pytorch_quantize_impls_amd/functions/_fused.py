@@ -2346,6 +2346,60 @@ class GroupedMfmaConv2dFn(QtFunction):
         return _streaming_backward(_GROUPED_MFMA_WGRAD if wgrad else _GROUPED_MFMA, ctx, grad_output)
 
 
+# ---- grouped convs with up to 64 channels per group ---------------------------------------------------------------------------------
+# 24 / 40 / 64 output channels, 40 / 48 / 64 input channels per group (RegNet widths, the last stage of ResNeXt-101 32x8d): a
+# group's weights no longer fit in LDS beside a patch, so the kernel walks the reduction channels in slices with the accumulators in
+# registers (csrc/gconv_wide_mfma.hip, DESIGN.md "Grouped convs on the matrix cores, wide groups").  Forward and grad_input each one
+# launch; the weight gradient is ONE grouped call of the dense library (counted), where the per-group loop makes G.
+
+#: BinConv2d / TerConv2d layers inside ``ops.grouped_wide_applicable`` but outside ``ops.grouped_mfma_applicable`` take
+#: ``GroupedWideConv2dFn`` (False: the per-group loop, as before).  Set from ``tools/bench_grouped_mfma.py --family wide`` by the rule
+#: of ``GROUPED_MFMA``: True iff on every measured row the node's round range lies wholly below the per-group loop's, forward and
+#: forward + backward.  Measured (profiles/grouped_wide_bench_line.json): it does on all five rows, 4.7x - 6.6x forward and 2.6x - 6.6x
+#: a step; the dense library is still ahead of the node on the forward of three rows and the step of four.
+GROUPED_WIDE = True
+
+_GROUPED_WIDE = _StreamingFamily(ops._GW, None, None)          # fp32 forward and grad_input; nothing else
+
+
+def grouped_wide_route(layer, input) -> bool:
+    """``layer`` (a Conv2d subclass with an fp32 weight) applied to ``input`` is a grouped conv ONLY the wide-group kernel takes and
+    ``GROUPED_WIDE`` is on: a 4-D fp32 device tensor, ``groups >= GROUPED_MFMA_MIN_GROUPS``, padding mode "zeros", the shapes of
+    ``ops.grouped_wide_applicable`` and not those of ``ops.grouped_mfma_applicable`` (those keep ``grouped_mfma_route``)."""
+    args = (input.shape, layer.weight.shape, layer.stride, layer.padding, layer.dilation, layer.groups)
+    return (bool(GROUPED_WIDE) and _streaming_f32_common(layer, input) and layer.groups >= GROUPED_MFMA_MIN_GROUPS
+            and ops.grouped_wide_applicable(*args) and not ops.grouped_mfma_applicable(*args))
+
+
+class GroupedWideConv2dFn(QtFunction):
+    """conv2d(x, Q(W), b, groups = G) with up to 64 channels per group on the matrix cores: the sibling of ``GroupedMfmaConv2dFn``,
+    same arguments.  Forward qt_gwconv2d_f32, backward qt_gwconv2d_grad_input_f32; grad_weight is one grouped call of the dense
+    library (``lib_conv2d_weight``, counted) with the straight-through mask of ``ste`` applied, grad_bias the sum of the gradient."""
+
+    @staticmethod
+    def forward(ctx, input, weight, bias, kind, weight_q, ste, conv_args):
+        return _streaming_forward(_GROUPED_WIDE, ctx, input, weight, bias, kind, weight_q, ste, conv_args)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        input, weight, weight_q = ctx.saved_tensors
+        stride, padding, dilation, groups = ctx.conv_args
+        go = _streaming_grad_output(grad_output, input)
+        grad_input = grad_weight = grad_bias = None
+        if ctx.needs_input_grad[0]:
+            grad_input = ops.grouped_wide_conv2d_grad_input(
+                input.shape, weight if weight_q is None else weight_q, go, stride, padding, dilation, groups, ctx.kind,
+                input.is_contiguous(memory_format=torch.channels_last) and not input.is_contiguous())
+        if ctx.needs_input_grad[1]:
+            grad_weight = lib_conv2d_weight(input, weight.shape, go, stride, padding, dilation, groups,
+                                            reason="grouped conv grad_weight beyond 32 channels per group")
+            if ctx.ste > 0.0:           # the rule of gc_grad_weight_combine_kernel: zero where the UNquantised |w| exceeds it
+                grad_weight = grad_weight.masked_fill(weight.detach().abs() > ctx.ste, 0.0)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            grad_bias = go.sum((0, 2, 3)).to(ctx.bias_dtype)
+        return grad_input, grad_weight, grad_bias, None, None, None, None
+
+
 def grouped_quant_conv(layer, input, kind: str, quant_op):
     """BinConv2d / TerConv2d with ``groups`` > 1 (layers/binary_layers.py:59-60,103-106 hand ``groups`` to F.conv2d): group g is
     an independent conv of its channel slice with its rows of the weight, and the element-wise quantisers (safeSign, the fixed

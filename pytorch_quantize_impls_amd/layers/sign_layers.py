@@ -192,7 +192,8 @@ class _SignConv2d(EvalSwapMixin, torch.nn.Conv2d, QLayer):
 
     def _streaming_forward(self, input):
         """``groups == in_channels`` (``_fused.depthwise_route``) or at least ``_fused.GROUPED_MIN_GROUPS`` groups of a few input
-        channels (``_fused.grouped_route``; ``_fused.grouped_mfma_route``: at least 8 groups of 16, 24 or 32, on the matrix cores) on a
+        channels (``_fused.grouped_route``; ``_fused.grouped_mfma_route``: at least 8 groups of 16, 24 or 32, on the matrix cores;
+        ``_fused.grouped_wide_route``: at least 8 groups of up to 64 channels that the former declines) on a
         device fp32 input: the depthwise / grouped kernels, which quantise the taps
         themselves — training with the layer's quantiser and its STE mask (a stochastic layer draws once for the whole weight and
         hands the draw over), eval on the stored image; None for everything else, an off-grid eval weight included (it keeps the
@@ -203,6 +204,8 @@ class _SignConv2d(EvalSwapMixin, torch.nn.Conv2d, QLayer):
             fn = _fused.GroupedConv2dFn
         elif _fused.grouped_mfma_route(self, input):            # 16 ... 32 channels per group: the matrix-core kernels
             fn = _fused.GroupedMfmaConv2dFn
+        elif _fused.grouped_wide_route(self, input):            # up to 64 channels per group: the reduction-sliced kernel
+            fn = _fused.GroupedWideConv2dFn
         else:
             return None
         args = (self.stride, self.padding, self.dilation, self.groups)

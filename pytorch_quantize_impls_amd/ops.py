@@ -4184,6 +4184,23 @@ def grouped_mfma_applicable(x_shape, w_shape, stride, padding, dilation, groups)
             and sh == sw and sh <= 2 and (dh, dw) == (1, 1) and max(ph, pw) <= 1)
 
 
+#: input and output channels per group the wide-group matrix-core kernel takes (csrc/gconv_wide_mfma.hip), every pair
+GW_CHANNELS_G = (16, 24, 32, 40, 48, 64)
+
+
+def grouped_wide_applicable(x_shape, w_shape, stride, padding, dilation, groups) -> bool:
+    """``grouped_mfma_applicable`` with cin_g and cout_g each in ``GW_CHANNELS_G`` (every pair; the window of
+    ``grouped_mfma_applicable`` lies inside it): the convs ``grouped_wide_conv2d`` / ``grouped_wide_conv2d_grad_input`` take.  A
+    1 x 1 or 3 x 3 kernel, stride 1 or 2 (equal on both axes), dilation 1, numeric padding 0 or 1 per axis, every tensor non-empty
+    and below 2^31 elements.  A pure function of the shapes."""
+    if not _streaming_limits(x_shape, w_shape, stride, padding, dilation, groups):
+        return False
+    Cout, cin_g, kh, kw = map(int, w_shape)
+    (sh, sw), (ph, pw), (dh, dw) = _pairs(stride), _pairs(padding), _pairs(dilation)
+    return (cin_g in GW_CHANNELS_G and Cout // int(groups) in GW_CHANNELS_G and (kh, kw) in ((1, 1), (3, 3))
+            and sh == sw and sh <= 2 and (dh, dw) == (1, 1) and max(ph, pw) <= 1)
+
+
 #: input channels per group the matrix-core grouped PLANE kernel takes (csrc/gconv_planes_mfma.hip): a 24-bit field would straddle
 #: plane words; and its output channels per group
 GMP_CIN_G = (16, 32)
@@ -4283,14 +4300,15 @@ def _dw_geometry(x_shape, weight, stride, padding, dilation, groups=None, half: 
     return w, (N, C, m, H, W, kh, kw, sh, sw, ph, pw, dh, dw), (N, C * m, max(Ho, 0), max(Wo, 0))
 
 
-def _gc_geometry(x_shape, weight, stride, padding, dilation, groups, half: bool = False):
+def _gc_geometry(x_shape, weight, stride, padding, dilation, groups, half: bool = False, window=None, noun="HIP"):
+    """``window``: the family's shape predicate where it is not ``grouped_applicable``; ``noun`` names its entries in the message."""
     _require_packable(weight, "weight") if half else _require(weight, "weight")
     N, C, H, W = map(int, x_shape)
     G = int(groups)
     if weight.dim() != 4 or G < 1 or C != G * int(weight.shape[1]) or weight.shape[0] % G != 0 or weight.shape[0] < G:
         raise ValueError(f"weight: expected [G * cout_g, C / G, kh, kw] for C = {C}, G = {G}, got {tuple(weight.shape)}")
-    if not grouped_applicable(x_shape, weight.shape, stride, padding, dilation, G) and min(N, C, H, W) > 0:
-        raise ValueError(f"not a grouped conv the HIP entry points take: input {tuple(x_shape)}, weight {tuple(weight.shape)}, "
+    if not (window or grouped_applicable)(x_shape, weight.shape, stride, padding, dilation, G) and min(N, C, H, W) > 0:
+        raise ValueError(f"not a grouped conv the {noun} entry points take: input {tuple(x_shape)}, weight {tuple(weight.shape)}, "
                          f"groups {G}, stride {stride}, padding {padding}, dilation {dilation}")
     w = weight.detach()
     w = w if w.is_contiguous() else w.contiguous()
@@ -4315,6 +4333,12 @@ def _gm_geometry(x_shape, weight, stride, padding, dilation, groups, half: bool 
         raise ValueError(f"not a grouped conv the matrix-core entry points take: input {tuple(x_shape)}, weight {tuple(weight.shape)}, "
                          f"groups {groups}, stride {stride}, padding {padding}, dilation {dilation}")
     return _gc_geometry(x_shape, weight, stride, padding, dilation, groups, half)
+
+
+def _gw_geometry(x_shape, weight, stride, padding, dilation, groups, half: bool = False):
+    """``_gc_geometry`` with the window of ``grouped_wide_applicable`` in place of ``grouped_applicable`` (whose 32 channels per
+    group it reaches past).  The family has fp32 entries only: ``half`` is the shared bodies' argument and is not honoured."""
+    return _gc_geometry(x_shape, weight, stride, padding, dilation, groups, False, grouped_wide_applicable, "wide-group matrix-core")
 
 
 def _gmp_geometry(x_shape, weight, stride, padding, dilation, groups):
@@ -4368,6 +4392,10 @@ _GMP = _Streaming({"sign": "qt_gmconv2d_sign", "bits_f32": "qt_gmconv2d_bits_f32
 #: (csrc/gconv_codes_mfma.hip): the two code entries alone, which carry the weight's scale and bit width behind the geometry
 _GMC = _Streaming({"codes": "qt_gmconv2d_codes", "codes_f32": "qt_gmconv2d_codes_f32"}, "matrix-core grouped", "G * cout_g",
                   _gm_geometry, _gm_geometry, False)
+#: 16 ... 64 channels per group on the matrix cores, reduction-sliced (csrc/gconv_wide_mfma.hip): the fp32 forward and grad_input
+#: alone — no half, plane, code or weight-gradient entries
+_GW = _Streaming({"f32": "qt_gwconv2d_f32", "grad_input_f32": "qt_gwconv2d_grad_input_f32"}, "wide-group matrix-core", "G * cout_g",
+                 _gw_geometry, _gw_geometry, False)
 #: most splits per group of that entry: the S_max of its error bound
 GM_WGRAD_MAX_SPLITS = _lib.DEFINES["QT_GM_WGRAD_MAX_SPLITS"]
 
@@ -4424,6 +4452,46 @@ def grouped_mfma_conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[to
     quantised and rounded once into x's dtype, and the fp32 sum plus bias is rounded once, to nearest even, into a result of x's
     dtype."""
     return _streaming_conv2d(_GM, x, weight, bias, stride, padding, dilation, groups, kind, out)
+
+
+def grouped_wide_conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1,
+                        groups: int = 1, kind: str = "raw", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``grouped_mfma_conv2d`` for the shapes of ``grouped_wide_applicable`` (16 ... 64 input and output channels per group), one
+    launch (qt_gwconv2d_f32): the same arithmetic — fp32 ``x`` of ANY value split exactly into three bf16 terms inside the launch,
+    Q(weight) exact in bf16, fp32 accumulation inside the MFMA in an order the shapes fix, the bias added once — on a
+    reduction-sliced walk (csrc/gconv_wide_mfma.hip).  fp32 only.  The result has the layout of x, or is written into ``out``."""
+    return _streaming_conv2d(_GW, _require(x, "input"), weight, bias, stride, padding, dilation, groups, kind, out)
+
+
+def grouped_wide_conv2d_grad_input(input_shape, weight: torch.Tensor, grad_output: torch.Tensor, stride=1, padding=0, dilation=1,
+                                   groups: int = 1, kind: str = "raw", channels_last: Optional[bool] = None,
+                                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient of ``grouped_wide_conv2d`` with respect to x (qt_gwconv2d_grad_input_f32): the gather of
+    ``grouped_mfma_conv2d_grad_input`` on the same reduction-sliced walk; no atomics, the result written in full.  fp32 only.
+    Layout rules as there."""
+    return _streaming_conv2d_grad_input(_GW, input_shape, weight, _require(grad_output, "grad_output"), stride, padding, dilation,
+                                        groups, kind, channels_last, out)
+
+
+def grouped_wide_plan(op: str, input_shape, weight_shape, stride=1, padding=0, dilation=1, groups: int = 1) -> dict:
+    """How ``grouped_wide_conv2d`` (``op`` "forward") or ``grouped_wide_conv2d_grad_input`` ("grad_input") launches for these
+    shapes, without launching it (qt_gwconv2d_describe: the plan function the launch calls; host arithmetic, no GPU needed).  A
+    dict of the words of include/qt_hip.h, integers but ``kernel``; empty for an empty problem.  A shape the entry refuses raises
+    QtStatusError."""
+    import ctypes
+    if op not in ("forward", "grad_input"):
+        raise ValueError(f"grouped_wide_plan: op must be 'forward' or 'grad_input', got {op!r}")
+    N, C, H, W = (int(v) for v in input_shape)
+    Cout, cin_g, kh, kw = (int(v) for v in weight_shape)
+    G = int(groups)
+    if G < 1 or C != G * cin_g or Cout % G:
+        raise ValueError(f"grouped_wide_plan: {tuple(input_shape)} x {tuple(weight_shape)} is no conv of {groups} groups")
+    buf = ctypes.create_string_buffer(384)
+    rc = _lib.load().qt_gwconv2d_describe(int(op == "grad_input"), N, G, cin_g, Cout // G, H, W, kh, kw, *_pairs(stride),
+                                          *_pairs(padding), *_pairs(dilation), buf, 384)
+    if rc != 0:
+        raise _lib.QtStatusError(f"qt_gwconv2d_describe failed: {_lib.strerror(rc)} (qt_status {rc})")
+    return {k: (v if k == "kernel" else int(v)) for k, v in (word.split("=", 1) for word in buf.value.decode().split())}
 
 
 def _dw_plane_input(planes: BitPlanes, shape):

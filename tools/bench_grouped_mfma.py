@@ -33,6 +33,12 @@ ship with (both dtypes measured, on every row the step's round range with it on 
 ``_fused.GROUPED_MFMA_HALF``.  ``wgrad`` times the weight gradient's two launches alone through ``ops``: one-term matrix cores
 against the streaming "_h" entry, the fp32 matrix-core entry on the upcast tensors for information.  ``--dtype ... --trace-steps``
 traces half steps with the weight-gradient switch off and then on.
+
+``--family wide`` measures the wide-group route instead (``child_wide``: ``_fused.GroupedWideConv2dFn``, csrc/gconv_wide_mfma.hip,
+called directly, against the per-group loop and the library) on ``WIDE_SHAPES`` — 24 ... 64 channels per group, the rows the
+kernels above decline — and writes profiles/grouped_wide_bench_line.json.  ``grouped_wide_by_rule`` is the value
+``_fused.GROUPED_WIDE`` has to ship with, by the rule of ``grouped_mfma_by_rule``; ``library_wins`` lists the rows and modes where
+the library's median is below the route's.
 """
 import argparse
 import json
@@ -49,6 +55,10 @@ sys.path.insert(0, B.ROOT)
 #: of 16: the matrix-core route declines it (the row keeps its other three routes); 768 -> 1536 is the 24-channel row it takes.
 SHAPES = [(512, 14, 1, 32, 3, 512), (768, 14, 1, 32, 3, 768), (768, 14, 1, 32, 3, 1536), (1024, 7, 1, 32, 3, 1024),
           (512, 28, 2, 32, 3, 512), (256, 14, 1, 16, 1, 256)]
+#: the wide-group rows: 24 / 24 (the row above that the old kernel declines), ResNeXt-101 32x8d's last stage, two RegNet widths
+#: (40 per group; 48 per group under stride 2) and a grouped 1 x 1 of 64
+WIDE_SHAPES = [(768, 14, 1, 32, 3, 768), (2048, 7, 1, 32, 3, 2048), (1360, 7, 1, 34, 3, 1360), (1008, 14, 2, 21, 3, 1008),
+               (1024, 14, 1, 16, 1, 1024)]
 BF16_FLOPS = 2.5e15
 DEFAULT_OUT = os.path.join(B.ROOT, "profiles", "grouped_mfma_wgrad_bench_line.json")
 
@@ -155,6 +165,108 @@ def child(index, rounds):
         result[mode]["mfma"].update(hbm_share=round(nbytes[mode] / B.HBM_BYTES_PER_S / t, 3),
                                     mfma_share=round(6 * macs[mode] / BF16_FLOPS / t, 3))
     print(json.dumps(result))
+
+
+def child_wide(index, rounds):
+    import torch
+    import torch.nn.functional as F
+    from pytorch_quantize_impls_amd import _lib, ops
+    from pytorch_quantize_impls_amd.functions import _fused
+    from pytorch_quantize_impls_amd.layers import BinConv2d
+
+    C, H, stride, G, k, Cout = WIDE_SHAPES[index]
+    pad = k // 2
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(index)
+    layer = BinConv2d(C, Cout, k, stride=stride, padding=pad, groups=G).to(dev)
+    layer.weight.data.uniform_(-1.2, 1.2)
+    layer.binary_input = True
+    args = (layer.stride, layer.padding, layer.dilation, G)
+    x = torch.where(torch.rand(B.BATCH, C, H, H, generator=g) < 0.5, -1.0, 1.0).to(dev)
+    xg = x.clone().requires_grad_(True)
+    assert ops.grouped_wide_applicable(x.shape, layer.weight.shape, *args) and not ops.grouped_mfma_applicable(x.shape, layer.weight.shape, *args)
+
+    def library(inp):                                       # in a step the library computes the weight gradient too
+        wq = torch.where(layer.weight.detach() < 0, -1.0, 1.0).requires_grad_(inp.requires_grad)
+        return F.conv2d(inp, wq, layer.bias, stride, pad, 1, G)
+
+    forward = {"wide": lambda inp: _fused.GroupedWideConv2dFn.apply(inp, layer.weight, layer.bias, "binary", None, ops.STE_THRESHOLD, args),
+               "loop": lambda inp: _fused.grouped_quant_conv(layer, inp, "binary", layer._op), "torch": library}
+    with torch.no_grad():
+        want = forward["loop"](x)
+        go = torch.randn(want.shape, generator=g).to(dev)
+        assert torch.equal(forward["wide"](x), want)       # integer sums plus the bias: the same bits
+    calls = dict(_lib.call_counts)
+    forward["wide"](xg).backward(go)
+    used = {k_: v - calls.get(k_, 0) for k_, v in _lib.call_counts.items() if v != calls.get(k_, 0)}
+    assert used == {"qt_gwconv2d_f32": 1, "qt_gwconv2d_grad_input_f32": 1}, used
+
+    def fwd(r):
+        def run():
+            with torch.no_grad():
+                forward[r](x)
+        return run
+
+    def step(r):
+        def run():
+            forward[r](xg).backward(go)
+            xg.grad = None
+            layer.zero_grad(set_to_none=True)
+        return run
+
+    def run_us(fn, steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6 / steps
+
+    x_b, y_b, m = 4 * x.numel(), 4 * want.numel(), want.numel() * (C // G) * k * k
+    nbytes, macs = {"fwd": x_b + y_b, "fwd_bwd": 3 * (x_b + y_b)}, {"fwd": m, "fwd_bwd": 3 * m}
+    result = {"channels": C, "out_channels": Cout, "map": H, "stride": stride, "groups": G, "cin_g": C // G, "cout_g": Cout // G,
+              "kernel": k, "bytes": nbytes, "macs": macs,
+              "plan": {op: ops.grouped_wide_plan(op, x.shape, layer.weight.shape, *args) for op in ("forward", "grad_input")}}
+    for mode, make in (("fwd", fwd), ("fwd_bwd", step)):
+        fns = {r: make(r) for r in forward}
+        steps = {r: (2 if r == "loop" else 10) for r in fns}
+        for fn in fns.values():
+            for _ in range(2):
+                fn()
+        samples = {r: [] for r in fns}
+        for _ in range(rounds):
+            for r, fn in fns.items():
+                samples[r].append(run_us(fn, steps[r]))
+        result[mode] = {r: {"median_us": round(sorted(v)[len(v) // 2], 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1)}
+                        for r, v in samples.items()}
+        t = result[mode]["wide"]["median_us"] * 1e-6
+        result[mode]["wide"].update(hbm_share=round(nbytes[mode] / B.HBM_BYTES_PER_S / t, 3),
+                                    mfma_share=round(6 * macs[mode] / BF16_FLOPS / t, 3))
+    print(json.dumps(result))
+
+
+def main_wide(a):
+    shapes = []
+    for i in range(len(WIDE_SHAPES)):
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--family", "wide", "--child", str(i), "--rounds", str(a.rounds)],
+                           stdout=subprocess.PIPE, text=True, timeout=B.CHILD_LIMIT_S)
+        if p.returncode != 0:
+            raise SystemExit(f"shape {WIDE_SHAPES[i]}: the measuring process ended with status {p.returncode}; nothing more was started")
+        shapes.append(json.loads(p.stdout.strip().splitlines()[-1]))
+        print(json.dumps(shapes[-1]), file=sys.stderr)
+    from pytorch_quantize_impls_amd.functions import _fused
+    passes = [all(s[m]["wide"]["max_us"] < s[m]["loop"]["min_us"] for m in ("fwd", "fwd_bwd")) for s in shapes]
+    line = {"bench": "grouped_wide", "batch": B.BATCH, "rounds": a.rounds, "dtype": "float32", "layout": "NCHW",
+            "hbm_bytes_per_s": B.HBM_BYTES_PER_S, "bf16_flops": BF16_FLOPS, "shapes": shapes, "shape_passes_rule": passes,
+            "grouped_wide_by_rule": all(passes), "grouped_wide_shipped": bool(_fused.GROUPED_WIDE),
+            "library_wins": [[i, m] for i, s in enumerate(shapes) for m in ("fwd", "fwd_bwd")
+                             if s[m]["torch"]["median_us"] < s[m]["wide"]["median_us"]]}
+    text = json.dumps(line)
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(B.ROOT, "profiles", "grouped_wide_bench_line.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        fh.write(text + "\n")
+    print(text)
 
 
 def child_half(index, rounds, dtype):
@@ -356,7 +468,11 @@ def main():
     ap.add_argument("--trace-steps", type=int, default=None)
     ap.add_argument("--dtype", default=None, choices=("bf16", "fp16", "both"),
                     help="the half-precision route against the library's half conv (both: what the switch GROUPED_MFMA_HALF needs)")
+    ap.add_argument("--family", default="mfma", choices=("mfma", "wide"),
+                    help="wide: the wide-group route (24 ... 64 channels per group) against the per-group loop and the library")
     a = ap.parse_args()
+    if a.family == "wide":
+        return child_wide(a.child, a.rounds) if a.child is not None else main_wide(a)
     if a.trace_steps is not None:
         return trace_steps(a.trace_steps, a.dtype)
     if a.child is not None:
